@@ -6,13 +6,20 @@ with one rank per GPU.  Rank 0 prints ONE JSON line.  A "step" is one pass of th
 64 images per GPU (BASELINE.json configs[1]: multi-MNIST 50x50, max_steps=3, batch=64, fp32); data-parallel runs keep
 64 images per GPU (weak scaling) and all-reduce the flat gradient bucket once per step over RCCL.
 
-Besides the headline value the line carries
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the outputs of the last timed step
+(--dump-outputs DIR) and the line with `metric`, `value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step`.  With --full the
+line also carries the measurements that take runs of their own:
+  median_ms_per_step : HIP events around every step of a second, shorter run
+  fixed_batch  : the same engine timed again on one fixed batch (single GPU)
+  allreduce_us / roofline_comm : the step's gradient all-reduce on its own (N > 1)
   roofline     : the fused ST glimpse-read kernel (north_star's target kernel): algorithmic bytes per launch
                  (4*(HW+hw+4) B per image-step) / its average duration measured here with HIP events on the
                  engine's stream, vs the 8 TB/s HBM3E peak; plus the same figure over a batch sweep (the working set
                  only leaves the 256 MiB Infinity Cache at large batch) and for the other three ST kernels.
   cpu_baseline : the CPU oracle (reference-equivalent restatement, torch-CPU fp32) timed on this host's cores on a
                  bounded sample of the same workload (kind "port").
+  other_configs, roofline_gemm, roofline_sweep_*, stream_reference : the other named configurations, the MFMA figure, the
+                 batch sweeps of the ST kernels and the device copy rate (single GPU).
 """
 import argparse
 import ctypes
@@ -48,6 +55,10 @@ def quiet_host():
         if was:
             gc.enable()
 
+def round4(x):
+    return None if x is None else round(x, 4)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -55,10 +66,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default: 64; 1024 for --config c5)")
     ap.add_argument("--no-graph", action="store_true", help="eager C-ABI launches instead of hipGraph replay")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every measurement that takes runs of its own: median step time, fixed-batch run, "
+                         "rooflines and sweeps, other configurations, CPU baseline (the --no-* options below thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (engine read-outs + updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short captured runs of BASELINE configs[3] / configs[4] that the default headline run appends")
+                    help="skip the short captured runs of BASELINE configs[3] / configs[4] that --full appends")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-all-cores", action="store_true",
                     help="time the CPU oracle on every host cpu as well (minutes on a 256-cpu host: ~100 s per step)")
@@ -666,6 +682,22 @@ def stream_reference(device, mib=1024):
             "frac_of_spec_peak": round(gbs / HBM_PEAK_GBS, 4)}
 
 
+MAX_REPLICAS = 8       # every replica is a process of its own: a GPU host shared by many jobs limits how many one job starts
+
+
+def cpu_budget():
+    """The cpus this process may use: its affinity mask, and no more than OMP_NUM_THREADS when that is set (a shared host
+    gives a job far fewer cpus than os.cpu_count() shows)."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    omp = os.environ.get("OMP_NUM_THREADS", "").strip()
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def cpu_baseline(cfg_kw, batch, seconds, all_cores_flag=False):
     """The CPU oracle's full train step (reference-equivalent restatement) on this host's cores, bounded sample."""
     import torch
@@ -675,11 +707,9 @@ def cpu_baseline(cfg_kw, batch, seconds, all_cores_flag=False):
     slots = O.rmsprop_init(params)
     obs, _ = O.synthetic_batch(ocfg, batch, seed=0)
     # pick the thread count that serves this small-op workload best on this host (more threads != faster here)
-    avail = os.cpu_count() or 1
+    avail = cpu_budget()
     best = (None, 1e9)
-    for th in sorted({4, 8, 16, 32}):
-        if th > avail:
-            continue
+    for th in sorted({min(avail, t) for t in (4, 8, 16, 32)}):
         torch.set_num_threads(th)
         O.train_step(params, slots, ocfg, obs, O.make_noise(ocfg, batch, seed=90), global_step=0)
         t0 = time.perf_counter()
@@ -723,12 +753,12 @@ def cpu_baseline(cfg_kw, batch, seconds, all_cores_flag=False):
             "one_thread_value": round(one_thread, 1),
             # the "N = all host cores" leg of SURVEY 8(d): run on `many_threads` threads -- ALL host cpus only when that is <= 64 or
             # --cpu-all-cores was given (256 threads on these small ops take ~100 s per step: profiles/r03_a_*_all_cores.json)
-            "many_threads_value": round(all_cores, 2), "many_threads": all_threads, "host_cpus": avail,
-            "all_host_cores_value": round(all_cores, 2) if all_threads == avail else None,
+            "many_threads_value": round(all_cores, 2), "many_threads": all_threads, "host_cpus": os.cpu_count(), "cpus_available": avail,
+            "all_host_cores_value": round(all_cores, 2) if all_threads == os.cpu_count() else None,
             # ... and all host cores the way a CPU would be used for this workload: independent replicas, rates added
-            "all_host_cores_replicas": cpu_all_cores_replicas(cfg_kw, batch, cores),
+            "all_host_cores_replicas": cpu_all_cores_replicas(cfg_kw, batch, cores, cpus=avail),
             "sample": f"{n} full train steps at batch {batch} ({el:.1f} s) of the torch-CPU fp32 oracle "
-                      f"(oracle/air_oracle.py); threads={cores} chosen as the fastest of a sweep on this {avail}-cpu host"}
+                      f"(oracle/air_oracle.py); threads={cores} chosen as the fastest of a sweep over the {avail} cpus available"}
 
 
 _REPLICA_WORKER = r"""
@@ -752,14 +782,15 @@ print("RATE %.3f %d" % (batch * n / (time.perf_counter() - t0), n), flush=True)
 """
 
 
-def cpu_all_cores_replicas(cfg_kw, batch, threads_per_replica, seconds=4.0, limit_s=90.0):
+def cpu_all_cores_replicas(cfg_kw, batch, threads_per_replica, seconds=4.0, limit_s=90.0, cpus=None):
     """SURVEY 8(d)'s "N = all host cores" as the CPU would be used for this workload: host_cpus / threads_per_replica INDEPENDENT
     replicas of the oracle's train step (fresh interpreters, one batch each -- the data-parallel shape the multi-GPU line has),
     started together, their rates added.  (ONE step on all cores is pathological for these small ops: 0.6 images/s on 256 threads.)
-    Returns None when anything goes wrong or takes longer than limit_s: the leg never blocks the line."""
+    Returns None when anything goes wrong or takes longer than limit_s: the leg never blocks the line.  `cpus`: the cpus to fill
+    (default: every host cpu); never more than MAX_REPLICAS processes."""
     import subprocess
-    avail = os.cpu_count() or 1
-    n_rep = max(1, avail // max(1, threads_per_replica))
+    avail = cpus or os.cpu_count() or 1
+    n_rep = min(MAX_REPLICAS, max(1, avail // max(1, threads_per_replica)))
     root = os.path.dirname(os.path.abspath(__file__))
     env = dict(os.environ, OMP_NUM_THREADS=str(threads_per_replica), MKL_NUM_THREADS=str(threads_per_replica), HIP_VISIBLE_DEVICES="")
     procs = []
@@ -799,6 +830,51 @@ def cpu_all_cores_replicas(cfg_kw, batch, threads_per_replica, seconds=4.0, limi
                 pr.wait(timeout=5)
             except Exception:                  # noqa: BLE001
                 pass
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6       # (under 64 MB however counted, .npy headers included)
+
+
+def snapshot_outputs(eng):
+    """What a caller of the timed path receives after its last step, copied to the host: the engine's read-outs
+    (AIREngine.outputs(), the reference's model attributes) and the updated flat parameters, as float32 / float64 arrays."""
+    import numpy as np
+    import torch
+    arrays = {}
+    outs = dict(eng.outputs())
+    h, c = outs.pop("final_state")
+    outs["final_state_h"], outs["final_state_c"] = h, c
+    outs["flat_params"] = eng.flat_params
+    for name, v in outs.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            v = v.double() if v.dtype in (torch.float64, torch.int64, torch.int32) else v.float()
+            arrays[name] = v.cpu().numpy()
+        else:
+            arrays[name] = np.asarray(v, dtype=np.float64)
+    return arrays
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every array, at most `limit` bytes in all: the smallest arrays are written whole, an array larger than
+    its share of what is left is replaced by a fixed sample of its elements (flattened, in order, chosen by a generator seeded
+    from the array's name and size), so that two runs with the same arguments write the same elements."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].nbytes, kv[0]))
+    left, sampled = limit, []
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            rng = np.random.default_rng(zlib.crc32(("%s/%d" % (name, a.size)).encode()))
+            flat = a.reshape(-1)
+            a = flat[np.sort(rng.choice(flat.size, share // a.itemsize, replace=False, shuffle=False))]
+            sampled.append("%s (%d of %d elements)" % (name, a.size, flat.size))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    print("bench.py: wrote %d arrays (%.1f MB) to %s%s" % (len(items), (limit - left) / 1e6, out_dir,
+                                                             "; sampled: " + ", ".join(sampled) if sampled else ""), file=sys.stderr)
 
 
 def self_launch(n):
@@ -906,35 +982,39 @@ def main():
             elapsed = t.item()
         finite = bool(torch.isfinite(eng.flat_params).all().item())
         eng.synchronize()
+        outputs = snapshot_outputs(eng) if args.dump_outputs and rank == 0 else None     # (before any further step)
         # the model state the last timed step ran in: the canvas kernels cost what the glimpses cover (the scales of `where`)
         mstate = {"steps_present_per_image": round(float(eng.presence.sum(0).mean().item()), 3),
                   "mean_abs_where": [round(float(v), 3) for v in eng.where.abs().mean(dim=(0, 1)).tolist()]}
         in_sync = dp.replicas_in_sync()      # (collective; outside the timed region) every rank ended with the same bits
-        # SURVEY 8(d) asks for the median step time: HIP events around every step of a second, shorter run on the engine stream (the
-        # headline `value` stays "exactly K steps between two barriers", as the driver contract defines it).  EVERY rank runs these
-        # steps -- with world > 1 each of them contains the gradient all-reduce, which one rank cannot enter alone.
-        sp = eng._sp()
-        n_ev = min(args.steps // spr, 400)
-        evs = [ctypes.c_void_p() for _ in range(n_ev + 1)]
-        for e in evs:
-            _lib.check(lib.air_event_create(ctypes.byref(e)))
-        _lib.check(lib.air_event_record(evs[0], sp))
-        for i in range(n_ev):
-            dp.train_step()
-            _lib.check(lib.air_event_record(evs[i + 1], sp))
-        eng.synchronize()
-        per = []
-        for i in range(n_ev):
-            ms = ctypes.c_float()
-            _lib.check(lib.air_event_elapsed_ms(evs[i], evs[i + 1], ctypes.byref(ms)))
-            per.append(ms.value)
-        for e in evs:
-            lib.air_event_destroy(e)
-        per.sort()
+        median_ms = None
+        if args.full:
+            # SURVEY 8(d) asks for the median step time: HIP events around every step of a second, shorter run on the engine stream (the
+            # headline `value` stays "exactly K steps between two barriers", as the driver contract defines it).  EVERY rank runs these
+            # steps -- with world > 1 each of them contains the gradient all-reduce, which one rank cannot enter alone.
+            sp = eng._sp()
+            n_ev = min(args.steps // spr, 400)
+            evs = [ctypes.c_void_p() for _ in range(n_ev + 1)]
+            for e in evs:
+                _lib.check(lib.air_event_create(ctypes.byref(e)))
+            _lib.check(lib.air_event_record(evs[0], sp))
+            for i in range(n_ev):
+                dp.train_step()
+                _lib.check(lib.air_event_record(evs[i + 1], sp))
+            eng.synchronize()
+            per = []
+            for i in range(n_ev):
+                ms = ctypes.c_float()
+                _lib.check(lib.air_event_elapsed_ms(evs[i], evs[i + 1], ctypes.byref(ms)))
+                per.append(ms.value)
+            for e in evs:
+                lib.air_event_destroy(e)
+            per.sort()
+            median_ms = per[len(per) // 2] / spr
         barrier()
         return {"collective": dp.collective, "elapsed": elapsed, "finite": finite, "in_sync": in_sync, "spr": spr, "model_state": mstate,
-                "median_ms": per[len(per) // 2] / spr, "ms_per_step": elapsed / args.steps * 1e3,
-                "value": world * B * args.steps / elapsed, "rccl_nranks": dp.rccl_nranks}
+                "median_ms": median_ms, "ms_per_step": elapsed / args.steps * 1e3,
+                "value": world * B * args.steps / elapsed, "rccl_nranks": dp.rccl_nranks, "outputs": outputs}
 
     def bare_allreduce():
         """the step's one collective on its own: the flat gradient bucket, summed over the ranks, on the engine stream"""
@@ -998,14 +1078,14 @@ def main():
     if world == 1:
         head = run_protocol(None)
         protocol_ab = None
-        if not args.fixed_batch and not args.no_graph:
+        if args.full and not args.fixed_batch and not args.no_graph:
             # rounds 1-5's input beside it, for continuity: the same engine on ONE fixed batch (it collapses onto it within ~50 updates)
             eng.attach_dataset(None)
             eng.set_obs(torch.from_numpy(imgs).to(device))
             keep = (args.steps, args.warmup)
             fr = run_protocol(None)
             args.steps, args.warmup = keep
-            fixed_rec = {"ms_per_step": round(fr["ms_per_step"], 4), "median_ms_per_step": round(fr["median_ms"], 4), "value": round(fr["value"], 1),
+            fixed_rec = {"ms_per_step": round(fr["ms_per_step"], 4), "median_ms_per_step": round4(fr["median_ms"]), "value": round(fr["value"], 1),
                          "kernel_launches_per_step": sum(eng.kernel_launch_count().values()), "model_state_at_end": fr["model_state"],
                          "input": "one fixed synthetic batch (rounds 1-5's measurement), run after the headline on the same engine"}
             eng.attach_dataset(resident_dataset(cfg.img_size, n_obj, device, n=args.dataset_images, seed=rank), shuffle=True, seed=1)
@@ -1035,14 +1115,14 @@ def main():
     def make_line(rec, note=None):
         """the JSON line for the measurement `rec` -- everything that needs no further GPU work (the watchdog prints this form)"""
         ab = {k: {"images_per_sec": round(v["value"], 1), "ms_per_step": round(v["ms_per_step"], 4),
-                  "median_ms_per_step": round(v["median_ms"], 4), "replicas_in_sync_after_run": v["in_sync"],
+                  "median_ms_per_step": round4(v["median_ms"]), "replicas_in_sync_after_run": v["in_sync"],
                   "params_finite_after_run": v["finite"]} for k, v in state["ab"].items()} if world > 1 else None
         ar = state["allreduce"]
         line = {
             "metric": "images/sec (train step, ELBO backward) multi-MNIST 50x50, 3-step AIR" if args.config != "c4"
                       else "images/sec (train step, ELBO backward) 100x100 canvas, 5-step AIR, glimpse 28x28",
             "value": round(rec["value"], 1), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(rec["ms_per_step"], 4), "median_ms_per_step": round(rec["median_ms"], 4),
+            "warmup": args.warmup, "ms_per_step": round(rec["ms_per_step"], 4), "median_ms_per_step": round4(rec["median_ms"]),
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32" if args.mfma == "f32" else "bf16 operands / f32 accumulate+storage",
             "data": "synthetic" if not share_gpu else "synthetic; NOT A MEASUREMENT: all ranks share one GPU (AIR_BENCH_SHARE_GPU)",
@@ -1078,7 +1158,7 @@ def main():
 
     if world > 1:
         state["line_holder"]["make"] = make_line
-        ar = guarded("the bare gradient all-reduce", bare_allreduce, later_limit)
+        ar = guarded("the bare gradient all-reduce", bare_allreduce, later_limit) if args.full else None
         state["allreduce"] = ar
         # Protocols timed after the safe one.  "ipc-rsag" (round 5: barrier | shard sum + sharded RMSProp + parameter push | barrier as
         # kernel nodes over hipIpc-mapped peer buffers, no library collective) has only ever run with two processes on ONE GPU; a
@@ -1104,12 +1184,19 @@ def main():
         protocol_note = None
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(head["outputs"], args.dump_outputs)
+
         def full_line():
             line = make_line(head, protocol_note)
             if fixed_rec is not None:
                 line["fixed_batch"] = fixed_rec
+            if plan_env_overrides():
+                line["config"]["plan_env_overrides"] = plan_env_overrides()
             if args.breakdown:
                 plan_breakdown(eng)
+            if not args.full:
+                return line
             roof = st_rooflines(eng)
             # the dominant ST kernel AS IT RUNS IN THE TIMED STEP: attend_fwd_kernel (the fused affine-grid + bilinear glimpse read of
             # all T steps + the tiny heads around it), launched from the step's own plan entry on the step's buffers and timed with
@@ -1129,8 +1216,6 @@ def main():
                 line["roofline"] = dict(roof["attend_fwd"], kernel="attend_fwd_kernel, eager launches (--no-graph): back-to-back HIP-event time")
             else:
                 line["roofline"] = dict(roof["st_read_fwd"], kernel="st_read_fwd_lean_kernel (this plan has no fused attend launch: the read runs on its own)")
-            if plan_env_overrides():
-                line["config"]["plan_env_overrides"] = plan_env_overrides()
             line["roofline_standalone_read"] = dict(roof["st_read_fwd"], kernel="st_read_fwd_lean_kernel launched on its own at the in-step shape")
             line["roofline_other_kernels"] = {k: v for k, v in roof.items() if k not in ("st_read_fwd", "attend_fwd")}
             line["roofline_gemm"] = gemm_roofline(eng)

@@ -48,3 +48,32 @@ def test_configs3_line_is_the_aggregate_over_engine_seeds(monkeypatch):
     one = bench.run_other_config_seeds("c5", None)
     assert calls == [("c5", 1, True, None), ("c5", 1, False, None), ("c5", 1, True, 20.0)] and "per_seed" not in one
     assert one["fixed_batch"]["input"] == "fixed" and one["all_steps_present_probe"]["step_bias"] == 20.0
+
+
+def test_dump_outputs_writes_float_arrays_under_64_mb_and_the_same_sample_every_time(tmp_path):
+    """--dump-outputs: arrays that fit are written whole; a larger set is cut down to a fixed sample of the largest arrays, the same
+    elements on every call, so that two builds can be compared output for output."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"canvas": rng.random((5, 1024, 100, 100), dtype=np.float32), "final_canvas": rng.random((1024, 100, 100), dtype=np.float32),
+              "flat_params": rng.random(2630000, dtype=np.float32), "rec_loss": np.asarray(1.5), "small": rng.random((64, 4))}
+    for d in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(k + ".npy" for k in arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 10 ** 6
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    for k in ("flat_params", "rec_loss", "small"):                  # small enough to stay whole
+        assert np.array_equal(np.load(tmp_path / "a" / (k + ".npy")), arrays[k]), k
+    assert np.isin(np.load(tmp_path / "a" / "canvas.npy"), arrays["canvas"]).all()
+
+
+def test_cpu_legs_stay_within_the_cpus_the_process_may_use(monkeypatch):
+    import bench
+    monkeypatch.setenv("OMP_NUM_THREADS", "3")
+    assert bench.cpu_budget() == min(3, len(os.sched_getaffinity(0)))
+    monkeypatch.delenv("OMP_NUM_THREADS")
+    assert bench.cpu_budget() == len(os.sched_getaffinity(0))

@@ -14,7 +14,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-PY="python $ROOT/bench.py"
+PY="python $ROOT/bench.py --full"     # every pass profiles the full line (rooflines, sweeps, other configs)
 DIGEST=$(cd $ROOT && python -c "from attend_infer_repeat_amd import build; print(build.source_digest())")
 
 pmc_pass() {      # pmc_pass <cfg name> "<H W h w T B>" <bench args...>
