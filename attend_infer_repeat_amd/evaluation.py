@@ -161,6 +161,31 @@ def make_expr_logger(air, data_fn, num_batches, expr_dict, name, writer=None, me
     return logger
 
 
+def make_iw_logger(air, data_fn, num_batches, particles, name, writer=None, measure_time=True):
+    """The K-particle importance-weighted bound, the ELBO of the same particles, the effective sample size and the count
+    accuracy of the self-normalised posterior, averaged over `num_batches` batches from `data_fn` (air.evaluate_iw; the sums
+    live on the device in float64 and are read once).  Prints / writes one line like make_expr_logger."""
+    def logger(itr=0, num_batches_to_eval=None, write=True):
+        n = num_batches if num_batches_to_eval is None else num_batches_to_eval
+        n = max(int(n), 1)
+        start = time.time()
+        ev = air.iw_evaluator(particles)
+        ev.reset()
+        for _ in range(n):
+            obs, nums = data_fn()
+            air.evaluate_iw(obs, nums, particles=particles)
+        acc = ev.totals()
+        t = time.time() - start
+        msg = 'Step {}, Data {} IW({}) '.format(itr, name, particles) + ', '.join('{} = {:.4f}'.format(k, v) for k, v in acc.items())
+        if measure_time:
+            msg += ', eval time = {:.4}s'.format(t)
+        print(msg)
+        if write and writer is not None:
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_iw", particles=int(particles), **acc)) + "\n"); writer.flush()
+        return acc
+    return logger
+
+
 def make_logger(air, train_data_fn, train_batches, test_data_fn, test_batches, writer=None):
     """evaluation.py:68-109.  (The reference divides the batch counts by batch_size a second time, evaluation.py:94,100
     -- SURVEY B-8; here `*_batches` is simply the number of batches to average over.)"""

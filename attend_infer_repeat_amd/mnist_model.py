@@ -217,6 +217,44 @@ class AIRonMNIST(AIRModel):
         self._refresh_from_engine()
         return self
 
+    def iw_evaluator(self, particles=16):
+        """the ImportanceEvaluator behind evaluate_iw (built and captured on first use, rebuilt when `particles` changes)"""
+        eng = getattr(self, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("evaluate_iw needs the fused engine: call train_step(...) with an engine-eligible "
+                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        from .iw_eval import ImportanceEvaluator
+        ev = getattr(self, "_iw_evaluator", None)
+        if ev is None or ev.K != int(particles) or ev.B != eng.B or ev.engine.device != eng.device:
+            if ev is not None:
+                ev.release_graphs()
+            ev = ImportanceEvaluator(eng.cfg, eng.B, int(particles), device=eng.device)
+            ev.capture()
+            self._iw_evaluator = ev
+        return ev
+
+    def evaluate_iw(self, obs=None, nums=None, particles=16):
+        """K-particle importance-weighted evaluation on the device (iw_eval.ImportanceEvaluator: its own engine at
+        particles * batch_size rows, its own noise stream -- the training engine's parameters are read, nothing of it is
+        written).  Sets iw_bound / iw_elbo / iw_ess (batch means), iw_bound_per_sample [B], iw_num_steps_posterior [B, T+1]
+        (self-normalised posterior over the object count) and, with `nums`, iw_num_step_accuracy (its argmax against the truth)."""
+        ev = self.iw_evaluator(particles)
+        eng = self._engine
+        if obs is not None:
+            self.obs = obs
+        if nums is not None:
+            self.nums = nums
+        self._sync_engine_switches()
+        ev.load_from(eng)                                    # every time: the weights move
+        gt = None if self.nums is None else self.nums.sum(0).reshape(-1)
+        out = ev.evaluate(self.obs, gt)                      # (the caller's stream is ordered after it: the reads below are safe)
+        self.iw_bound_per_sample = out["iw_bound"]
+        self.iw_bound, self.iw_elbo, self.iw_ess = out["iw_bound"].mean(), out["elbo"].mean(), out["ess"].mean()
+        self.iw_num_steps_posterior = out["num_steps_posterior"]
+        if gt is not None:
+            self.iw_num_step_accuracy = (out["num_steps_posterior"].argmax(-1) == gt.to(torch.int64)).float().mean()
+        return self
+
     def refresh(self):
         """Re-expose the engine's current buffers under the reference's attribute names."""
         if self._engine is not None:

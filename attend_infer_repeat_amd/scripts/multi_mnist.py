@@ -20,7 +20,7 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from attend_infer_repeat_amd.data import DeviceFeeder, load_data, procedural_multi_mnist, synthetic_dataset  # noqa: E402
-from attend_infer_repeat_amd.evaluation import make_fig, make_logger, step_summaries  # noqa: E402
+from attend_infer_repeat_amd.evaluation import make_fig, make_iw_logger, make_logger, step_summaries  # noqa: E402
 from attend_infer_repeat_amd.mnist_model import AIRonMNIST  # noqa: E402
 from attend_infer_repeat_amd.utils import AttrDict  # noqa: E402
 
@@ -62,6 +62,10 @@ def main(argv=None):
     ap.add_argument("--grad-histograms", action="store_true",
                     help="add the per-variable gradient histograms of evaluation.gradient_summaries(histogram=True) (the reference's default, "
                          "evaluation.py:221-248) to the 1000-iteration summaries in log.jsonl")
+    ap.add_argument("--iw-particles", type=int, default=0, metavar="K",
+                    help="K > 0: at every --log-every also print / write the K-particle importance-weighted bound, the ELBO of the same "
+                         "particles, the effective sample size and the count accuracy of the self-normalised posterior on the validation "
+                         "batches (evaluation.make_iw_logger); 0 = off")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -140,6 +144,14 @@ def main(argv=None):
         air._engine.capture()
     writer = open(osp.join(logdir, "log.jsonl"), "a")
     log = make_logger(air, train_feed, args.eval_batches, valid_feed, args.eval_batches, writer)
+    if args.iw_particles > 0:
+        plain_log = log
+        iw_log = make_iw_logger(air, valid_feed, args.eval_batches, args.iw_particles, 'test', writer)
+
+        def log(train_itr):                               # noqa: F811
+            out = plain_log(train_itr)
+            iw_log(train_itr)
+            return out
 
     train_itr = int(global_step)
     print('Starting training at iter = {}'.format(train_itr))

@@ -514,6 +514,28 @@ AIR_ENGINE_API int air_imp_weight(const float *rec_parts, int n_parts, float *re
 AIR_ENGINE_API int air_nvil_parts(const float *imp_parts, int n_parts, float *imp_sum, const float *baseline, const float *logp,
                    float *out, float *dlogp, float *dbaseline, int B, float *ema_dev, void *stream);
 
+/* ---- K-particle importance-weighted evaluation (a read-out of a forward pass over R = K * B rows, row r = b * K + k: the K
+ * particles of image b are adjacent).  Discrete steps only; no backward.
+ * air_iw_logweight: per row, with n = the number of leading ones of presence[T,R] (the chain is monotone),
+ *   logw[r] = -rec[r] + log pi(n) - logp[r] + sum_{t<n} [ sum_a log p(what_ta)/q(what_ta) + sum_j log p(where_tj)/q(where_tj) ]
+ *   q = Normal(loc, scale) at the STORED sample (what / where [T,R,A] / [T,R,4]); p(what) = Normal(what_p_*), p(where) components
+ *   0, 2 = Normal(scale_p_*), 1, 3 = Normal(shift_p_*) with shift_p_loc = NaN meaning "centred on where_loc" (the convention of
+ *   air_gauss_sample_fwd).  pi = prior_f64[T+1] (air_steps_prior's table), divided by its sum when normalize_prior != 0; logp = log q(n)
+ *   as air_presence_numsteps_fwd leaves it.  No clamps: a zero scale gives +-inf / NaN.  num_steps[r] = n.  fp32, one fixed summation
+ *   order.  where / where_loc / where_scale must be 16-byte aligned (AIR_E_ALIGN).
+ * air_iw_reduce: per image b over lw_k = logw[b*K + k], m = max_k lw_k, w_k = exp(lw_k - m):
+ *   iw_bound[b] = m + log sum_k w_k - log K;  elbo[b] = mean_k lw_k;  ess[b] = (sum w)^2 / sum w^2;
+ *   q_n_iw[b, c] = sum_k w_k [num_steps_k = c] / sum_k w_k  (c = 0..T).
+ *   acc (optional; DEVICE double[8]): acc[0..4] += {sum_b iw_bound, sum_b elbo, sum_b ess, #images with argmax_c q_n_iw == gt_steps
+ *   (0 without gt_steps), B}, added in float64 in one fixed order by a single workgroup (a second kernel of the same call).      */
+AIR_ENGINE_API int air_iw_logweight(const float *what, const float *what_loc, const float *what_scale, const float *where,
+                     const float *where_loc, const float *where_scale, const float *presence, const float *rec,
+                     const float *logp, const double *prior_f64, int T, int R, int K, int A, float what_p_loc,
+                     float what_p_scale, float scale_p_loc, float scale_p_scale, float shift_p_loc, float shift_p_scale,
+                     int normalize_prior, float *logw, int *num_steps, void *stream);
+AIR_ENGINE_API int air_iw_reduce(const float *logw, const int *num_steps, int T, int R, int K, float *iw_bound, float *elbo,
+                  float *ess, float *q_n_iw, const int *gt_steps, double *acc, void *stream);
+
 
 /* Baseline input assembly, modules.py:131-139: out[B, HW + T*A + T*4 + T + S] =
  * [img | what (batch-major) | where | presence | state] from time-major what[T,B,A], where[T,B,4], presence[T,B],
