@@ -67,6 +67,40 @@ def make_fig(air, checkpoint_dir=None, global_step=None, n_samples=10):
     return fig
 
 
+def make_prior_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, count_probs="uniform"):
+    """Scenes drawn from the generative model (air.sample_scenes with `count_probs`; the sampler keeps the size it has): one column
+    per scene; the first row shows the mean canvas with the attention box of every step that is present, the next max_steps rows
+    the glimpse each step decoded, titled with its presence.  The caption names the count distribution.  Saved as
+    prior_fig_<global_step>.png when a directory is given."""
+    import os.path as osp
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    air.sample_scenes(count_probs=count_probs)
+    host = lambda t: t.detach().cpu().numpy()
+    mean, glimpse = host(air.generated_mean), host(air.generated_glimpse)
+    presence, where = host(air.generated_presence), host(air.generated_where)
+    T = air.max_steps
+    cols = min(n_samples, mean.shape[0])
+    img_h, img_w = mean.shape[1:]
+    inch = 1.5
+    fig, axes = plt.subplots(T + 1, cols, figsize=(inch * cols, inch * (T + 1)), squeeze=False)
+    for col in range(cols):
+        axes[0][col].imshow(mean[col], cmap='gray', vmin=0, vmax=1)
+        for t in range(T):
+            if presence[t, col] > .5:
+                rect_stn(axes[0][col], img_w, img_h, where[t, col], 'r')
+            axes[1 + t][col].imshow(glimpse[t, col], cmap='gray')
+            axes[1 + t][col].set_title('{:d}'.format(int(presence[t, col])), fontsize=4 * inch)
+    for ax in axes.ravel():
+        ax.set_axis_off()
+    fig.suptitle('prior samples, count distribution: {}'.format(air.scene_sampler().count_label), fontsize=5 * inch)
+    if checkpoint_dir is not None:
+        fig.savefig(osp.join(checkpoint_dir, 'prior_fig_{}.png'.format(global_step)), dpi=300)
+        plt.close(fig)
+    return fig
+
+
 def gradient_summaries(named_grads, named_vars, norm=True, ratio=True, histogram=False, bins=30):
     """evaluation.py:221-248: the global norm of the gradient, per variable mean(|g| / (|v| + 1e-8)) (log_ratio,
     evaluation.py:169-180) and -- histogram=True, the reference's default -- a histogram of every gradient tensor, the content of its

@@ -255,6 +255,40 @@ class AIRonMNIST(AIRModel):
             self.iw_num_step_accuracy = (out["num_steps_posterior"].argmax(-1) == gt.to(torch.int64)).float().mean()
         return self
 
+    def scene_sampler(self, n_scenes=None):
+        """the SceneSampler behind sample_scenes (built and captured on first use, rebuilt when the size or the device changes;
+        n_scenes=None: the size it has, the batch size on first use)"""
+        eng = getattr(self, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("sample_scenes needs the fused engine: call train_step(...) with an engine-eligible "
+                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        from .generate import SceneSampler
+        s = getattr(self, "_scene_sampler", None)
+        n = int(n_scenes) if n_scenes is not None else (s.R if s is not None else eng.B)
+        if s is None or s.R != n or s.device != eng.device:
+            if s is not None:
+                s.release_graphs()
+            s = SceneSampler(eng.cfg, n, device=eng.device)
+            s.capture()
+            self._scene_sampler = s
+        return s
+
+    def sample_scenes(self, n_scenes=None, num_objects=None, count_probs=None):
+        """Scenes from the generative model on the device (generate.SceneSampler: the trained decoder is copied, nothing of the
+        training engine is written).  count_probs: None = the model's own count prior at the current step (collapsed onto n = 0
+        once annealed -- see SceneSampler), 'uniform', or max_steps + 1 weights; num_objects: condition on these counts instead.
+        Sets generated_obs / generated_mean [N, H, W], generated_num_objects [N], generated_what [T, N, A], generated_where
+        [T, N, 4], generated_presence [T, N] and generated_glimpse [T, N, h, w]; the next call overwrites them."""
+        s = self.scene_sampler(n_scenes)
+        self._sync_engine_switches()
+        s.load_from(self._engine)                            # every time: the weights move
+        s.set_count_probs(count_probs)
+        out = s.sample(num_objects=num_objects)              # (the caller's stream is ordered after it)
+        self.generated_obs, self.generated_mean, self.generated_num_objects = out["obs"], out["mean"], out["num_objects"]
+        self.generated_what, self.generated_where, self.generated_presence = out["what"], out["where"], out["presence"]
+        self.generated_glimpse = out["glimpse"]
+        return self
+
     def refresh(self):
         """Re-expose the engine's current buffers under the reference's attribute names."""
         if self._engine is not None:

@@ -20,7 +20,7 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from attend_infer_repeat_amd.data import DeviceFeeder, load_data, procedural_multi_mnist, synthetic_dataset  # noqa: E402
-from attend_infer_repeat_amd.evaluation import make_fig, make_iw_logger, make_logger, step_summaries  # noqa: E402
+from attend_infer_repeat_amd.evaluation import make_fig, make_iw_logger, make_logger, make_prior_fig, step_summaries  # noqa: E402
 from attend_infer_repeat_amd.mnist_model import AIRonMNIST  # noqa: E402
 from attend_infer_repeat_amd.utils import AttrDict  # noqa: E402
 
@@ -66,6 +66,10 @@ def main(argv=None):
                     help="K > 0: at every --log-every also print / write the K-particle importance-weighted bound, the ELBO of the same "
                          "particles, the effective sample size and the count accuracy of the self-normalised posterior on the validation "
                          "batches (evaluation.make_iw_logger); 0 = off")
+    ap.add_argument("--prior-samples", type=int, default=0, metavar="N",
+                    help="N > 0: at every --log-every draw N scenes from the generative model on the device (AIRonMNIST.sample_scenes, the "
+                         "model's own count prior) and write the histogram of the generated object counts to log.jsonl; with --figures also "
+                         "prior_fig_<iter>.png (evaluation.make_prior_fig, uniform counts); 0 = off")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -151,6 +155,20 @@ def main(argv=None):
         def log(train_itr):                               # noqa: F811
             out = plain_log(train_itr)
             iw_log(train_itr)
+            return out
+
+    if args.prior_samples > 0:
+        inner_log = log
+
+        def log(train_itr):                               # noqa: F811
+            out = inner_log(train_itr)
+            counts = air.sample_scenes(args.prior_samples).generated_num_objects
+            hist = torch.bincount(counts.to(torch.int64), minlength=n_steps + 1).tolist()
+            print('Step {}, prior samples: counts 0..{} = {}'.format(train_itr, n_steps, hist))
+            writer.write(json.dumps(dict(step=int(train_itr), data="prior_samples", n_scenes=int(args.prior_samples),
+                                         count_probs="model", count_hist=hist)) + "\n"); writer.flush()
+            if args.figures:
+                make_prior_fig(air, logdir, train_itr)
             return out
 
     train_itr = int(global_step)

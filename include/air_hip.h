@@ -536,6 +536,30 @@ AIR_ENGINE_API int air_iw_logweight(const float *what, const float *what_loc, co
 AIR_ENGINE_API int air_iw_reduce(const float *logw, const int *num_steps, int T, int R, int K, float *iw_bound, float *elbo,
                   float *ess, float *q_n_iw, const int *gt_steps, double *acc, void *stream);
 
+/* ---- the generative direction: scenes from p(n) p(what) p(where) p(x | z) (model.py:92-97,126-216; cell.py:158-165).  Decoder and
+ * canvas between the two entries are air_linear_fwd / air_gemm_bf16 and air_canvas_unroll_fwd (obs = NULL).
+ * air_prior_latents: the ancestral draw of the latents of R scenes from caller-supplied noise; time-major like the engine:
+ *   eps_what[T,R,A], eps_where[T,R,4] ~ N(0,1), u_n[R] ~ U[0,1)  ->  what[T,R,A], where[T,R,4], presence[T,R], num_objects[R].
+ *   count: count_table_f64[T+1] holds non-negative weights (need not be normalised: air_steps_prior's table is not).  With the
+ *   running sums cum_c formed in float64 in index order and total = cum_T, n = #{c in 0..T-1 : cum_c <= (double)u * total} -- a
+ *   weight of exactly zero is never drawn, also at u = 0.  num_objects_in[R] (optional): n = that value clipped to 0..T, u_n and the
+ *   table are not read (both may then be NULL).  presence[t,r] = t < n ? 1 : 0 (the monotone chain the cell produces).
+ *   what = what_p_loc + what_p_scale * eps;  where = [sx, tx, sy, ty], sx / sy from Normal(scale_p_*), tx / ty from
+ *   Normal(shift_p_*); guard_eps > 0 keeps |sx|, |sy| >= guard_eps by the rule of air_gauss_sample_fwd (sign kept, +guard for 0).
+ *   Latents of absent steps are written too (inference draws them as well; the presence masks them).  One wavefront per scene;
+ *   T <= 32; eps_where / where 16-byte aligned (AIR_E_ALIGN).
+ * air_observe: mean = mult * canvas;  obs = clamp(mean + std * z_i, clamp_lo, clamp_hi) over n floats; a NaN bound = no clamp on
+ *   that side.  z_i is BY DEFINITION element i of what air_rng_fill(normal, n, NULL, 0, {seed, offset + counter_base}) writes with
+ *   state_dev = {seed, offset}: the noise is drawn in registers, one Philox call per four adjacent pixels, and never stored.
+ *   std == 0: no draw (state_dev may be NULL), obs == mean bit for bit.  One of mean_out / obs_out may be NULL.  The offset is
+ *   not advanced (air_rng_advance by (n + 3) / 4 behind it).                                                                     */
+AIR_ENGINE_API int air_prior_latents(const double *count_table_f64, const float *u_n, const int *num_objects_in, const float *eps_what,
+                      const float *eps_where, float what_p_loc, float what_p_scale, float scale_p_loc, float scale_p_scale,
+                      float shift_p_loc, float shift_p_scale, float guard_eps, int T, int R, int A, float *what, float *where,
+                      float *presence, int *num_objects, void *stream);
+AIR_ENGINE_API int air_observe(const float *canvas, float mult, float std, const uint64_t *state_dev, uint64_t counter_base,
+                float clamp_lo, float clamp_hi, float *mean_out, float *obs_out, size_t n, void *stream);
+
 
 /* Baseline input assembly, modules.py:131-139: out[B, HW + T*A + T*4 + T + S] =
  * [img | what (batch-major) | where | presence | state] from time-major what[T,B,A], where[T,B,4], presence[T,B],
