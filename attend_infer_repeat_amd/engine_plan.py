@@ -77,7 +77,7 @@ class PlanMixin:
                     return
             tiles16 = sum(((d.M + 15) // 16) * ((d.N + 15) // 16) for d in descs)
 
-            def wide_ok(d):       # what air_gemm_grouped's wide-tile kernels need of a problem (gemm_kernels.hip)
+            def wide_ok(d):       # what air_gemm_grouped's wide-tile kernels need of a problem (gemm_kernels.hip wide_group_eligible)
                 strict = tiles16 > 2048 or (d.A % 16 == 0 and d.lda % 4 == 0 and d.K % 4 == 0)
                 return (strict and not (d.ta and d.tb) and not d.A2 and d.B % 16 == 0 and d.ldb % 4 == 0
                         and (not (d.ta or d.tb) or d.K % 4 == 0) and d.M >= 4 and d.N >= 4 and d.K >= 4
@@ -949,7 +949,8 @@ class PlanMixin:
 
         def wide_form(entry):
             # the library declines (AIR_E_UNSUPPORTED) a group its wide-tile dispatch would take -- all weight gradients, K >= 256, more
-            # than AIR_GEMM_WIDE_MIN_TILES 16x16 tiles (a long batch at T = 1): such a plan keeps its closing launch
+            # than AIR_GEMM_WIDE_MIN_TILES 16x16 tiles (a long batch at T = 1; gemm_kernels.hip wide_regime_weight_gradients): such a plan keeps
+            # its closing launch
             arr, n = entry[1]
             tiles16 = sum(((arr[i].M + 15) // 16) * ((arr[i].N + 15) // 16) for i in range(n))
             return (tiles16 > int(os.environ.get("AIR_GEMM_WIDE_MIN_TILES", "1000")) and all(arr[i].ta and not arr[i].tb for i in range(n))

@@ -1279,6 +1279,65 @@ def test_gemm_grouped_random_groups(hip, case):
             assert_close(cs, cref, 1e-5, 1e-4 * np.sqrt(K), f"colsum {i}")
 
 
+def _tiles16(M, N):
+    return ((M + 15) // 16) * ((N + 15) // 16)
+
+
+@pytest.mark.parametrize("family", ["tile16", "long_k", "tile32", "short_k_mixed", "wide_f32_tn", "wide_f32_nn", "wide_bf16_tn",
+                                    "wide_bf16_nn", "tile16_c16"])
+def test_gemm_grouped_every_slot(hip, family):
+    """air_gemm_grouped with exactly 8 problems, every one with a different N: the kernels pick a problem's descriptor through an
+    8-way switch with one constant-index call per slot, so a slot routed to the wrong descriptor writes the wrong shape or the wrong
+    values.  One case per kernel family the call can reach (the dispatch rules of air_gemm_grouped, csrc/gemm_kernels.hip):
+      tile16         M = 16..48, K = 64, mixed layouts: a few tiles, 16x16 tiles, 4 waves split K -> gemm_grouped_kernel<1,1,4,false>
+      long_k         M = 16, N <= 32, K = 512 (K >= 512 and K >= 8 min(M, N), <= 1024 tiles) -> gemm_grouped_kernel<1,1,16,false>
+      tile32         K = 16, more than 1536 16x16 tiles, mixed layouts (no wide tiles) -> gemm_grouped_kernel<2,2,4,false>
+      short_k_mixed  one fp32 TN problem with K = 32, N = 64, M = 4096 (shortk_eligible) in slot 5 beside seven small ones
+                     -> gemm_grouped_sk_kernel<1,1>: that slot on the streaming body, the others on the tile body
+      wide_f32_tn    all TN, K = 256, 16-byte aligned, just over 1000 16x16 tiles -> gemm_grouped_wide_kernel<4,8,false,true,false>
+      wide_f32_nn    the same shapes, all NN -> gemm_grouped_wide_kernel<1,8,false,false,false>
+      wide_bf16_tn   the TN shapes with bf16 operands: air_gemm_grouped hands a bf16 weight-gradient group to the big-group launch
+                     -> gemm_big_group_wide16_tn_kernel<4,8> (a dynamic descriptor index, no slot switch: here for the shapes' sake)
+      wide_bf16_nn   the NN shapes with bf16 operands, no mirrors -> gemm_grouped_wide16_kernel<1,8,false,false,false,false>
+      tile16_c16     the tile16 shapes with bf16 operands and a bf16 mirror of every C -> gemm_grouped_c16_kernel<1,1,4>
+    Every problem against float64 (bf16: against the rounded operands) with test_gemm_grouped_random_groups' tolerances."""
+    gen = torch.Generator().manual_seed(5000 + len(family) * 7 + ord(family[-1]))
+    rn = lambda *s: torch.randn(*s, generator=gen).cuda()
+    precision = int("bf16" in family or family == "tile16_c16")
+    r = (lambda t: t.cpu().to(torch.bfloat16).double()) if precision else (lambda t: t.cpu().double())
+    layouts = [(False, False), (False, True), (True, False), (True, True)]
+    if family in ("tile16", "tile16_c16"):
+        shapes = [(16 + 4 * i, 8 + 5 * i, 64) + layouts[i % 4] for i in range(8)]
+    elif family == "long_k":
+        shapes = [(16, 4 + 4 * i, 512) + layouts[i % 4] for i in range(8)]
+    elif family == "tile32":
+        shapes = [(230, 200 + 9 * i, 16) + layouts[i % 4] for i in range(8)]
+        assert sum(_tiles16(M, N) for M, N, *_ in shapes) > 1536
+    elif family == "short_k_mixed":
+        shapes = [(16 + 4 * i, 8 + 5 * i, 64) + layouts[i % 4] for i in range(8)]
+        shapes[5] = (4096, 64, 32, True, False)
+    else:
+        ta = family.endswith("tn")
+        shapes = [(128, 208 + 16 * i, 256, ta, False) for i in range(8)]
+        assert 1000 < sum(_tiles16(M, N) for M, N, *_ in shapes) <= 2048
+    assert len({N for _, N, *_ in shapes}) == 8
+    problems, refs = [], []
+    for M, N, K, ta, tb in shapes:
+        A = rn(K, M) if ta else rn(M, K)
+        B = rn(N, K) if tb else rn(K, N)
+        pr = dict(A=A, B=B, ta=ta, tb=tb)
+        if family == "tile16_c16":
+            pr["C16"] = torch.zeros(M, N, dtype=torch.bfloat16).cuda()
+        problems.append(pr)
+        refs.append((r(A).t() if ta else r(A)) @ (r(B).t() if tb else r(B)))
+    outs = hip.gemm_grouped(problems, precision=precision)
+    for i, ((C_, _), ref, (M, N, K, _, _), pr) in enumerate(zip(outs, refs, shapes, problems)):
+        assert tuple(C_.shape) == (M, N)
+        assert_close(C_, ref, 2e-5, 2e-5 * np.sqrt(K) * 4 + 1e-5, f"{family}: slot {i} ({M}x{N}x{K})")
+        if "C16" in pr:
+            assert torch.equal(pr["C16"], C_.to(torch.bfloat16)), f"{family}: slot {i} bf16 mirror of C"
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # grid-stride launches (more work items than resident workgroups: the grid is a multiple of the resident count)
 # ---------------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@
 #include <cmath>
 #include <vector>
 #include <algorithm>
-#include "../../attend_infer_repeat_amd/csrc/gemm_kernels.hip"
+#include "../../attend_infer_repeat_amd/csrc/lstm_kernels.hip"
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 
