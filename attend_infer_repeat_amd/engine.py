@@ -25,30 +25,12 @@ from . import _lib
 from . import hip as H
 from .engine_config import (EngineConfig, _Mlp, _mlp_shapes, anneal_weight, geometric_prior_f64,  # noqa: F401 (re-exported)
                             param_shapes)
+from .engine_mirrors import MirrorMixin
 from .engine_plan import PlanMixin
+from .launch import LaunchMixin, destroy_graphs
 
 
-_ROCTX = [False, None]
-
-
-def _roctx():
-    """libroctx64 when AIR_ROCTX=1 (and the library is there), else None; resolved once per process"""
-    if not _ROCTX[0]:
-        _ROCTX[0] = True
-        if os.environ.get("AIR_ROCTX", "0") == "1":
-            for name in ("libroctx64.so", "/opt/rocm/lib/libroctx64.so", "librocprofiler-sdk-roctx.so"):
-                try:
-                    lib = ctypes.CDLL(name)
-                    lib.roctxRangePushA.argtypes = [ctypes.c_char_p]; lib.roctxRangePushA.restype = ctypes.c_int
-                    lib.roctxRangePop.restype = ctypes.c_int
-                    _ROCTX[1] = lib
-                    break
-                except (OSError, AttributeError):
-                    continue
-    return _ROCTX[1]
-
-
-class AIREngine(PlanMixin):
+class AIREngine(PlanMixin, MirrorMixin, LaunchMixin):
     def __init__(self, cfg: EngineConfig, batch_size: int, device=None, seed: int = 0, keep_canvas_steps: bool = True):
         H.lib()
         self.cfg = cfg
@@ -148,32 +130,8 @@ class AIREngine(PlanMixin):
         if getattr(self, "flat_params16", None) is not None:
             self._sync_param_shadow()
 
-    # ---- stream discipline ------------------------------------------------------------------------------------------
-    # The engine runs on its own stream.  Everything that enters its buffers from outside (a batch gathered on the default
-    # stream, checkpoint tensors, injected noise) is ordered explicitly: the engine stream first waits for the producer's
-    # stream, the copy runs ON the engine stream, and a device-side source is marked as in use by the engine stream so the
-    # caching allocator cannot hand its block to a later allocation while the copy is still pending.
-    def _copy_in(self, dst: torch.Tensor, src):
-        src_t = src if torch.is_tensor(src) else torch.as_tensor(src)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self.stream):
-            dst.copy_(src_t.reshape(dst.shape), non_blocking=True)
-        if src_t.is_cuda:
-            src_t.record_stream(self.stream)
-
-    def _fill_in(self, dst: torch.Tensor, value):
-        with torch.cuda.stream(self.stream):
-            dst.fill_(value)
-
-    def wait_for_engine(self):
-        """Order the CALLER's current stream after everything queued on the engine stream (before torch code on another
-        stream reads buffers the engine writes: the shared parameters, outputs)."""
-        torch.cuda.current_stream(self.device).wait_stream(self.stream)
-
-    def wait_for_caller(self):
-        """Order the engine stream after the caller's current stream (after torch code on another stream touched buffers
-        the next engine launch reads or overwrites)."""
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+    # ---- stream discipline: launch.LaunchMixin (_copy_in, _fill_in, wait_for_caller, _sp, _run, _capture_plans) ---------------
+    wait_for_engine = LaunchMixin.wait_for_stream
 
     def load_parameters(self, named: Dict[str, torch.Tensor]):
         for k, v in named.items():
@@ -252,40 +210,9 @@ class AIREngine(PlanMixin):
     # launch plans
     # ------------------------------------------------------------------------------------------------------------
 
-    def _run(self, plan, stream_ptr):
-        """Issue a plan: entries (fn, args, name[, ...]) on the engine stream, in order.  AIR_ROCTX=1: every entry inside a roctx range
-        named "<position> <C-ABI entry>" (rocprofv3 --marker-trace shows the plan next to the kernel trace of an EAGER
-        step -- `bench.py --no-graph`; a captured graph replays kernel nodes only, its positions are tools/probes/plan_dump.py's)."""
-        rx = _roctx()
-        for i, e in enumerate(plan):
-            if rx is not None:
-                rx.roctxRangePushA(("%02d %s" % (i, e[2])).encode())
-            st = e[0](*e[1], stream_ptr)
-            if rx is not None:
-                rx.roctxRangePop()
-            if st != 0:
-                _lib.check(st, e[2])
-
-    def _opt_slice_entry(self, lo, hi, lane, counters=False):
-        """centred RMSProp over elements [lo, hi) of the flat buffers (two learning rates around n_model) as one launch;
-        counters=True: the closing launch, which also advances the device step counter and the Philox offset"""
-        L, p, cfg = H.lib(), H._p, self.cfg
-        assert lo % 4 == 0 and hi % 4 == 0 and lo < hi
-        off = lambda t: ctypes.c_void_p(t.data_ptr() + 4 * lo)
-        n_model = min(max(self.n_model - lo, 0), hi - lo)
-        tail_mult = cfg.baseline_lr_mult if cfg.use_reinforce else 0.0
-        args = (off(self.flat_params), off(self.flat_grads), off(self.flat_ms), off(self.flat_mg), off(self.flat_mom),
-                ctypes.c_size_t(n_model), ctypes.c_size_t(hi - lo), p(self.lr_dev), tail_mult, cfg.rms_decay, cfg.rms_momentum,
-                cfg.rms_eps, 1.0, p(self.step_dev) if counters else None, p(self.rng_state) if counters else None,
-                ctypes.c_uint64(self._rng_inc if counters else 0))
-        return (L.air_step_epilogue, args, "air_step_epilogue", lane)
-
     # ------------------------------------------------------------------------------------------------------------
     # public API
     # ------------------------------------------------------------------------------------------------------------
-    def _sp(self):
-        return ctypes.c_void_p(self.stream.cuda_stream)
-
     def set_learning_rate(self, lr: float):
         self._fill_in(self.lr_dev, float(lr))
 
@@ -327,24 +254,6 @@ class AIREngine(PlanMixin):
         plan = self._plan_opt if grad_scale == 1.0 else self._opt_calls_factory(float(grad_scale))
         self._run(plan, self._sp())
         self.global_step += 1
-
-    def _capture_plans(self, plans):
-        """Capture a list of plan entries into one hipGraph.  An entry is either a launch plan (list of (fn, args, name)) or
-        a callable taking the stream pointer (collectives, stream forks / joins)."""
-        L = H.lib()
-        sp = self._sp()
-        _lib.check(L.air_graph_begin_capture(sp), "air_graph_begin_capture")
-        try:
-            for pl in plans:
-                if callable(pl):
-                    pl(sp)
-                else:
-                    self._run(pl, sp)
-        finally:
-            exe = ctypes.c_void_p()
-            st = L.air_graph_end_capture(sp, ctypes.byref(exe))
-        _lib.check(st, "air_graph_end_capture")
-        return exe
 
     def _allreduce_call(self, comm, lo, hi):
         L = H.lib()
@@ -537,10 +446,7 @@ class AIREngine(PlanMixin):
         return True
 
     def release_graphs(self):
-        L = H.lib()
-        for g in (self._graph_opt, getattr(self, "_graph_b2", None), self._graph):
-            if g is not None:
-                L.air_graph_destroy(g)
+        destroy_graphs((self._graph_opt, getattr(self, "_graph_b2", None), self._graph))
         self._graph = self._graph_opt = self._graph_b2 = None
 
     def stream_context(self):
@@ -593,9 +499,6 @@ class AIREngine(PlanMixin):
                     allreduce(self.flat_grads)
             self._run(self._plan_opt if self.world_size == 1 else self._opt_calls_factory(1.0 / self.world_size), sp)
         self.global_step += 1
-
-    def synchronize(self):
-        self.stream.synchronize()
 
     # ---- checkpoint / resume (the reference only ever *saves*, multi_mnist.py:116,145-146) ---------------
     def state_dict(self):

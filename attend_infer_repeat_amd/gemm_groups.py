@@ -1,0 +1,156 @@
+"""GEMM grouping policy of the train-step plans: which problems share a launch.  Pure arithmetic over `AirGemmDesc` fields -- no
+torch, no device, no library handle -- so it runs (and is tested) on the host.  Every function takes descriptors and returns lists
+of groups of descriptors; the caller (engine_plan.py) turns each group into an array, keeps it alive and appends the plan entry.
+
+Three policies live here:
+  plan_launch          the rule of every grouped launch of the forward and the backward;
+  deferred_dw_groups   the weight gradients the throughput regime forms at the end of the backward;
+  wide_form / shortk_mixed / tensors_read / foldable   what the folded closing update (engine_plan._fold_closing_update) must know
+                       of the library's dispatch and of the flat buffers before it folds an update into a grouped launch.
+The predicates restate rules of the library (csrc/gemm_kernels.hip); each names the function it mirrors."""
+from . import _lib
+
+GROUPED, SPLITK = "grouped", "splitk"      # kinds of plan_launch: air_gemm_grouped / the split-K single-GEMM entry (air_gemm, air_gemm_bf16)
+
+
+def tiles16(d):
+    return ((d.M + 15) // 16) * ((d.N + 15) // 16)
+
+
+def is_weight_gradient(d):
+    """a TN problem: K = rows of the batch, a small output nothing but the optimiser consumes"""
+    return bool(d.ta and not d.tb)
+
+
+def wide_ok(d, group_tiles16):
+    """what air_gemm_grouped's wide-tile kernels need of a problem (gemm_kernels.hip wide_group_eligible)"""
+    strict = group_tiles16 > 2048 or (d.A % 16 == 0 and d.lda % 4 == 0 and d.K % 4 == 0)
+    return bool(strict and not (d.ta and d.tb) and not d.A2 and d.B % 16 == 0 and d.ldb % 4 == 0
+                and (not (d.ta or d.tb) or d.K % 4 == 0) and d.M >= 4 and d.N >= 4 and d.K >= 4
+                and (not d.ta or d.M % 4 == 0) and (d.tb or d.N % 4 == 0))
+
+
+def plan_launch(descs, throughput, use16, allow_splitk=False):
+    """[(kind, problems)]: the launches that dispatch `descs`, in order.  kind SPLITK: a lone long-K problem for the split-K
+    single-GEMM entry; GROUPED: up to 8 problems for air_gemm_grouped."""
+    total = sum(tiles16(d) for d in descs)
+    if throughput and len(descs) > 1:
+        ok = [wide_ok(d, total) for d in descs]
+        if any(ok) and not all(ok):
+            # one odd problem (N = 1, K = 50 ...) would keep the whole group off the wide-tile kernels: it gets its own launch
+            return (plan_launch([d for d, w in zip(descs, ok) if w], throughput, use16)
+                    + plan_launch([d for d, w in zip(descs, ok) if not w], throughput, use16))
+    if (len(descs) == 1 and allow_splitk and descs[0].K >= 1024 and total > 256 and not use16
+            and not (throughput and wide_ok(descs[0], total))):
+        return [(SPLITK, list(descs))]
+    groups = [descs]
+    if total > 1536 and len(descs) > 1:
+        # large batch: launches are cheap relative to the work, and the library picks ONE tile shape / K-split per
+        # launch -- keep the long-K few-tile problems (weight gradients: K = T*B) apart from the many-tile ones
+        is_long = lambda d: d.K >= 1024 and tiles16(d) <= 1024
+        groups = [g for g in ([d for d in descs if is_long(d)], [d for d in descs if not is_long(d)]) if g]
+    return [(GROUPED, list(grp[i:i + 8])) for grp in groups for i in range(0, len(grp), 8)]
+
+
+# ---- deferred weight gradients (throughput regime) ------------------------------------------------------------------------------
+def deferred_wide_ok(d):
+    """16-byte loads along M and N: both multiples of 4, aligned"""
+    return bool(d.M % 4 == 0 and d.M >= 4 and d.N % 4 == 0 and d.ldb % 4 == 0 and d.K % 4 == 0 and d.B % 16 == 0)
+
+
+def split_rows(d):
+    """a row count that is not a multiple of 4 (50 latent / 677 baseline-input rows): the first M - M % 4 rows go wide, the
+    remaining one to three rows are a problem of their own (the bias gradient stays with the first part)"""
+    m4 = d.M // 4 * 4
+    if not (d.M % 4 and m4 >= 16 and d.N % 4 == 0 and d.ldb % 4 == 0 and d.K % 4 == 0 and d.B % 16 == 0):
+        return [d]
+    return [_lib.AirGemmDesc(d.ta, d.tb, m4, d.N, d.K, d.A, d.lda, d.B, d.ldb, d.C, d.ldc, d.bias,
+                             d.epilogue, d.aux, d.ldaux, d.beta, d.colsum, d.precision, None, None, 0, None),
+            _lib.AirGemmDesc(d.ta, d.tb, d.M - m4, d.N, d.K, d.A + 4 * m4, d.lda, d.B, d.ldb,
+                             d.C + 4 * m4 * d.ldc, d.ldc, d.bias, d.epilogue, d.aux, d.ldaux, d.beta, None,
+                             d.precision, None, None, 0, None)]
+
+
+def pack(problems, n_wide):
+    """launches of up to 24 problems while wide-tile members are among them (the library's mixed form needs at
+    least one), of up to 8 otherwise; the first `n_wide` of `problems` are the wide-tile eligible ones"""
+    out, i = [], 0
+    while i < len(problems):
+        step = 24 if i < n_wide else 8
+        chunk = problems[i:i + step]
+        if len(chunk) <= 8 and i < n_wide < i + len(chunk):     # (8 or fewer go through the all-one-kind launches)
+            out += [problems[i:n_wide], problems[n_wide:i + len(chunk)]]
+        else:
+            out.append(chunk)
+        i += step
+    return out
+
+
+def deferred_dw_groups(deferred, bf16):
+    """the launches of the deferred weight gradients: wide-tile eligible problems together, longest K first so that the heaviest
+    tiles start first; the rest (M = 50 / 677 / 1, N = 1) behind them.  The library takes up to 24 problems in one launch when at
+    least one is wide-tile eligible: the odd-shaped rest (one to three rows, a single column: eight long-K reductions) rides in
+    the same grid on 16x16 tiles instead of costing a 14.5 us launch of its own."""
+    parts = [q for d in deferred for q in split_rows(d)]
+    wide = sorted((d for d in parts if deferred_wide_ok(d)), key=lambda d: (-d.K, -d.M * d.N))
+    rest = [d for d in parts if not deferred_wide_ok(d)]
+    if not bf16:
+        # fp32 (MFMA-issue bound tiles): ONE launch for everything -- long-K tiles first, the CUs that finish early keep
+        # pulling short-K tiles instead of idling until a launch of their own (batch 1024: 0.636 -> 0.607 ms)
+        return pack(wide + rest, len(wide))
+    # bf16 operands (L2 / L1 traffic bound tiles): the long-K problems in a launch of 8 with the grid-wide
+    # XCD-contiguous tile map, the others + the rest in a second one (0.474 against 0.485 ms for a single launch)
+    return ([wide[:8]] if wide[:8] else []) + pack(wide[8:] + rest, len(wide[8:]))
+
+
+# ---- what the folded closing update asks of a grouped launch -----------------------------------------------------------------------
+def wide_form(descs, wide_min_tiles):
+    """the library declines (AIR_E_UNSUPPORTED) to fold an update into a group its wide-tile dispatch would take -- all weight
+    gradients, K >= 256, more than AIR_GEMM_WIDE_MIN_TILES 16x16 tiles (a long batch at T = 1; gemm_kernels.hip
+    wide_regime_weight_gradients): such a plan keeps its closing launch"""
+    return (sum(tiles16(d) for d in descs) > wide_min_tiles and all(is_weight_gradient(d) for d in descs)
+            and min(d.K for d in descs) >= 256)
+
+
+def shortk_mixed(descs, enabled, min_m):
+    """... and a group that MIXES a short-K streaming weight gradient (gemm_kernels.hip shortk_eligible: fp32 TN, K <= 64 in whole
+    chunks, N a multiple of 64 up to 256, >= AIR_GEMM_SHORTK_MIN_M rows, no epilogue) with tile problems: such a problem keeps
+    the product of the streaming body in every plan, and the folded launch takes it only when all its problems are of that kind"""
+    if not enabled or any(d.A2 or d.C16 or d.precision != 0 for d in descs):
+        return False
+    el = [bool(is_weight_gradient(d) and 16 <= d.K <= 64 and d.K % 16 == 0 and 64 <= d.N <= 256 and d.N % 64 == 0
+               and d.M >= min_m and d.epilogue == 0 and d.beta == 0.0 and not d.bias) for d in descs]
+    return any(el) and not all(el)
+
+
+def tensors_read(descs, p0, p1, spans):
+    """flat-buffer spans (of `spans`, in elements) of the parameter tensors the problems read, the parameters lying at byte
+    addresses [p0, p1) (a dX problem reads its layer's weights; weight gradients read activations / gradients only)"""
+    out = []
+    for d in descs:
+        for x in (d.A, d.B, d.aux, d.bias, d.A2):
+            if p0 <= int(x or 0) < p1:
+                off = (int(x) - p0) // 4
+                out += [sp for sp in spans if sp[0] <= off < sp[1]]
+    return out
+
+
+def foldable(descs, g0, r_lo, barred):
+    """(mask, covered spans) of the weight-gradient problems that write whole tensors of the head [0, r_lo) of the flat gradient
+    buffer (byte address g0) and whose parameters nothing in `barred` reads"""
+    mask, cov = 0, []
+    for i, d in enumerate(descs):
+        if not is_weight_gradient(d):
+            continue
+        off = (int(d.C) - g0) // 4
+        if not (0 <= off < r_lo) or d.ldc != d.N or d.beta != 0.0 or d.epilogue != 0:
+            continue
+        mine = [(off, off + d.M * d.N)]
+        if d.colsum:
+            coff = (int(d.colsum) - g0) // 4
+            mine.append((coff, coff + d.N))
+        if any(a0 < b1 and b0 < a1 for a0, a1 in mine for b0, b1 in barred):
+            continue
+        mask |= 1 << i
+        cov += mine
+    return mask, cov

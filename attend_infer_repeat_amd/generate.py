@@ -18,6 +18,7 @@ import ctypes
 from typing import Dict
 
 from .engine_config import EngineConfig, _mlp_shapes
+from .launch import LaunchMixin, destroy_graphs
 
 
 def check_config(cfg: EngineConfig) -> None:
@@ -47,7 +48,7 @@ def count_table(count_probs, T: int):
     return vals
 
 
-class SceneSampler:
+class SceneSampler(LaunchMixin):
     """count_probs=None: the model's own count prior at the sampler's global step (air_steps_prior: the float64 arithmetic of
     the engine's table, unnormalised geometric weights).  NOTE: under the training script's schedule that table collapses onto
     n = 0 once annealed (nsp_final = 1e-7: p(n = 0) = 1 - 1e-7) -- prior samples of a fully trained model are then empty
@@ -159,44 +160,12 @@ class SceneSampler:
         return {"rng_fill": 1 if sample_noise else 0, "prior_latents": 1, "decoder": len(self.shapes), "canvas": 1, "observe": 1,
                 "rng_advance": 1}
 
-    def _sp(self):
-        return ctypes.c_void_p(self.stream.cuda_stream)
-
-    def _run(self, plan):
-        from . import _lib
-        sp = self._sp()
-        for fn, args, name in plan:
-            st = fn(*args, sp)
-            if st != 0:
-                _lib.check(st, name)
-
     def _launch(self, key):
-        from . import _lib
-        if key in self._graphs:
-            _lib.check(self._H.lib().air_graph_launch(self._graphs[key], self._sp()), "air_graph_launch")
-        else:
-            self._run(self._plans[key])
+        self._replay_or_run(self._graphs.get(key), self._plans[key])
 
-    # ---- stream discipline (the engine's: work runs on the sampler's stream, whatever enters or leaves is ordered explicitly) ----
-    def wait_for_caller(self):
-        import torch
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-
-    def wait_for_sampler(self):
-        import torch
-        torch.cuda.current_stream(self.device).wait_stream(self.stream)
-
-    def _copy_in(self, dst, src):
-        import torch
-        src_t = src if torch.is_tensor(src) else torch.as_tensor(src)
-        self.wait_for_caller()
-        with torch.cuda.stream(self.stream):
-            dst.copy_(src_t.reshape(dst.shape), non_blocking=True)
-        if src_t.is_cuda:
-            src_t.record_stream(self.stream)
-
-    def synchronize(self):
-        self.stream.synchronize()
+    # ---- stream discipline: launch.LaunchMixin (the engine's: work runs on the sampler's stream, whatever enters or leaves is ordered
+    #      explicitly)
+    wait_for_sampler = LaunchMixin.wait_for_stream
 
     # ---- parameters and switches -----------------------------------------------------------------------------------------------
     def load_from(self, engine):
@@ -234,8 +203,7 @@ class SceneSampler:
     def set_global_step(self, step: int):
         """host mirror + the device counter the model's own count table is evaluated at"""
         self.global_step = int(step)
-        with self._on_stream():
-            self.step_dev.fill_(int(step))
+        self._fill_in(self.step_dev, int(step))
         self._refresh_table()
 
     def set_count_probs(self, count_probs=None):
@@ -249,10 +217,6 @@ class SceneSampler:
         self.count_probs = vals
         self.count_label = "uniform" if isinstance(count_probs, str) else "[%s]" % ", ".join("%.3g" % v for v in vals)
         self._copy_in(self.table, torch.tensor(vals, dtype=torch.float64))
-
-    def _on_stream(self):
-        import torch
-        return torch.cuda.stream(self.stream)
 
     def _refresh_table(self):
         if self.count_probs is not None:
@@ -274,25 +238,13 @@ class SceneSampler:
     # ---- graphs ----------------------------------------------------------------------------------------------------------------
     def capture(self):
         """every variant of the chain (fresh / kept latent noise, drawn / given counts, decode) as ONE hipGraph each"""
-        from . import _lib
-        L = self._H.lib()
         self.release_graphs()
         self.synchronize()
         for key, plan in self._plans.items():
-            sp = self._sp()
-            _lib.check(L.air_graph_begin_capture(sp), "air_graph_begin_capture")
-            try:
-                self._run(plan)
-            finally:
-                exe = ctypes.c_void_p()
-                st = L.air_graph_end_capture(sp, ctypes.byref(exe))
-            _lib.check(st, "air_graph_end_capture")
-            self._graphs[key] = exe
+            self._graphs[key] = self._capture_plans([plan])
 
     def release_graphs(self):
-        L = self._H.lib()
-        for g in self._graphs.values():
-            L.air_graph_destroy(g)
+        destroy_graphs(self._graphs.values())
         self._graphs = {}
 
     # ---- the three entries -----------------------------------------------------------------------------------------------------
@@ -309,7 +261,7 @@ class SceneSampler:
             n = torch.as_tensor(num_objects)
             if n.numel() not in (1, self.R):
                 raise ValueError("num_objects: one count, or one per scene (%d), got shape %s" % (self.R, tuple(n.shape)))
-            with self._on_stream():
+            with torch.cuda.stream(self.stream):
                 self.num_objects_in.copy_(n.reshape(-1).expand(self.R), non_blocking=True)
             if n.is_cuda:
                 n.record_stream(self.stream)

@@ -22,6 +22,7 @@ import dataclasses
 from typing import Dict
 
 from .engine_config import EngineConfig
+from .launch import destroy_graphs
 
 
 def check_config(cfg: EngineConfig, particles: int) -> None:
@@ -149,9 +150,7 @@ class ImportanceEvaluator:
             self._graphs[key] = self.engine._capture_plans([plan])
 
     def release_graphs(self):
-        L = self._H.lib()
-        for g in self._graphs.values():
-            L.air_graph_destroy(g)
+        destroy_graphs(self._graphs.values())
         self._graphs = {}
 
     # ---- evaluation ---------------------------------------------------------------------------------------------------------
@@ -161,7 +160,6 @@ class ImportanceEvaluator:
         ordered after it (a device-side wait, no host synchronisation), so torch code on that stream may read the results right
         away, and the next call waits for such readers before it overwrites them."""
         import torch
-        from . import _lib
         eng, B, K = self.engine, self.B, self.K
         obs = torch.as_tensor(obs)
         if obs.shape[0] != B or obs.numel() != B * eng.obs.shape[1]:
@@ -180,10 +178,7 @@ class ImportanceEvaluator:
         key = (bool(sample_noise), nums is not None)
         if nums is None:
             self._calls_without_counts += 1
-        if key in self._graphs:
-            _lib.check(self._H.lib().air_graph_launch(self._graphs[key], eng._sp()), "air_graph_launch")
-        else:
-            eng._run(self._plans[key], eng._sp())
+        eng._replay_or_run(self._graphs.get(key), self._plans[key])
         eng.wait_for_engine()
         return {"log_weights": self.log_weights, "num_steps": self.num_steps, "iw_bound": self.iw_bound, "elbo": self.elbo,
                 "ess": self.ess, "num_steps_posterior": self.num_steps_posterior}

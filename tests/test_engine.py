@@ -1381,3 +1381,21 @@ def test_tf_checkpoint_export_import_between_engines(gpu_device, tmp_path):
     eng_a.train_step(); eng_b.train_step()
     eng_a.synchronize(); eng_b.synchronize()
     assert torch.equal(eng_a.flat_params, eng_b.flat_params)
+
+
+@pytest.mark.parametrize("name,kw,B", [("default_b8", {}, 8), ("bf16_b256", dict(mfma_dtype="bf16"), 256)])
+def test_plan_rebuild_is_idempotent(gpu_device, name, kw, B):
+    """A second `_build_plans()` and a use_prior off / on round trip leave every plan, list and published flag as the first build made
+    them (engine_plan.describe_plans: every entry, every argument, pointers by tensor name): nothing of one build leaks into the next.
+    The default configuration at batch 8 (latency regime) and bf16 at 768 rows (the smallest throughput / bf16-data-path case)."""
+    from attend_infer_repeat_amd.engine import AIREngine, EngineConfig
+    from attend_infer_repeat_amd.engine_plan import describe_plans
+    eng = AIREngine(EngineConfig(**kw), B, seed=1)
+    assert eng._use16 == (name == "bf16_b256") and eng._defer_dw == (name == "bf16_b256")
+    first = describe_plans(eng)
+    eng._build_plans()
+    assert describe_plans(eng) == first
+    assert eng.update_config(use_prior=False)
+    assert describe_plans(eng) != first                      # (the prior's weight is a launch argument)
+    assert eng.update_config(use_prior=True)
+    assert describe_plans(eng) == first
