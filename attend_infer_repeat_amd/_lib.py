@@ -187,6 +187,9 @@ SIGNATURES = {
     "air_prior_latents": (c_int, [P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_int,
                                   P, P, P, P, P]),
     "air_observe": (c_int, [P, c_float, c_float, P, c_uint64, c_float, c_float, P, P, c_size_t, P]),
+    "air_parse_objects": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "air_parse_render": (c_int, [P, P, P, P, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 P, P, P, P, P, P]),
     "air_l2_grad_add": (c_int, [P, P, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t), c_int, c_float, P]),
     "air_baseline_pack": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "air_rmsprop_centered": (c_int, [P, P, P, P, P, c_size_t, P, c_float, c_float, c_float, c_float, c_float, P]),

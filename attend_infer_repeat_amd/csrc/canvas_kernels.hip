@@ -770,7 +770,6 @@ __global__ __launch_bounds__(1024) void st_write_bwd_gs_kernel(WriteBwdArgs a, N
 // ============================================================================================================
 // host side
 // ============================================================================================================
-static inline double lin_step(int n) { return n > 1 ? 2.0 / (double)(n - 1) : 0.0; }
 static inline int cv_grid(long items, int cap) { return (int)(items < cap ? items : cap); }
 // (developer override of the resident-workgroup cap of the throughput-regime launches: air_resident_grid in air_common.h)
 template <typename K>
@@ -781,20 +780,6 @@ static inline int cv_resident_cap(K kernel, int threads, size_t lds, int fallbac
 static inline int cv_check_dims(int n, int H, int W, int h, int w) {
     if (n <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0) return AIR_E_SHAPE;
     return AIR_OK;
-}
-#define CV_MAX_LDS (160 * 1024)
-template <typename K>
-static inline int cv_allow_lds(K kernel, size_t lds) {      // dynamic LDS above 64 KiB must be opted into per kernel
-    if (lds <= 64 * 1024) return AIR_OK;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return e == hipSuccess ? AIR_OK : (int)e;
-}
-// rows per band / number of bands actually used for a request of `want` bands
-static inline void wr_bands(int H, int want, int *NB, int *RB) {
-    int nb = want < 1 ? 1 : (want > H ? H : want);
-    const int rb = (H + nb - 1) / nb;
-    nb = (H + rb - 1) / rb;                                  // drop empty trailing bands
-    *NB = nb; *RB = rb;
 }
 static inline int bwd_threads(long units) { return units <= 512 ? 512 : ST_THREADS; }
 static int launch_write_fwd(const float *glimpse, const float *where, const float *presence, const float *canvas_in,

@@ -198,3 +198,20 @@ __device__ __forceinline__ int2 valid_span(const float2 *tab, int n) {
     }
     return make_int2(first, last);
 }
+
+// ---- host side, shared by the launches of the canvas write (canvas_kernels.hip) and of the parse render (parse_kernels.hip) ----
+static inline double lin_step(int n) { return n > 1 ? 2.0 / (double)(n - 1) : 0.0; }
+#define CV_MAX_LDS (160 * 1024)
+template <typename K>
+static inline int cv_allow_lds(K kernel, size_t lds) {      // dynamic LDS above 64 KiB must be opted into per kernel
+    if (lds <= 64 * 1024) return AIR_OK;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return e == hipSuccess ? AIR_OK : (int)e;
+}
+// rows per band / number of bands actually used for a request of `want` bands
+static inline void wr_bands(int H, int want, int *NB, int *RB) {
+    int nb = want < 1 ? 1 : (want > H ? H : want);
+    const int rb = (H + nb - 1) / nb;
+    nb = (H + rb - 1) / rb;                                  // drop empty trailing bands
+    *NB = nb; *RB = rb;
+}

@@ -302,7 +302,6 @@ __global__ __launch_bounds__(1024) void st_read_bwd_kernel(
 // ============================================================================================================
 // host side
 // ============================================================================================================
-static inline double lin_step(int n) { return n > 1 ? 2.0 / (double)(n - 1) : 0.0; }
 static inline int st_grid(int items, int cap = 256 * 8) {   // 256 CUs x up to 8 resident 256-thread workgroups; grid-stride beyond that
     return items < cap ? items : cap;
 }

@@ -101,6 +101,72 @@ def make_prior_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, cou
     return fig
 
 
+def make_parse_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, obs=None):
+    """The deterministic parse of a batch (air.parse): one column per image; the input, the reconstruction with the attention box
+    of every object the parse found (rect_stn), and the owner map (which object a pixel belongs to; background = -1).  Saved as
+    parse_fig_<global_step>.png when a directory is given."""
+    import os.path as osp
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    out = air.parse(obs)
+    host = lambda t: t.detach().cpu().numpy()
+    x, rec, owner = host(air.obs), host(out["reconstruction"]), host(out["owner"])
+    presence, where, count_prob = host(out["presence"]), host(out["where"]), host(out["count_prob"])
+    T = presence.shape[0]
+    cols = min(n_samples, x.shape[0])
+    img_h, img_w = x.shape[1:]
+    inch = 1.5
+    fig, axes = plt.subplots(3, cols, figsize=(inch * cols, inch * 3), squeeze=False)
+    colours = plt.get_cmap('tab10')
+    for col in range(cols):
+        axes[0][col].imshow(x[col], cmap='gray', vmin=0, vmax=1)
+        axes[1][col].imshow(rec[col], cmap='gray', vmin=0, vmax=1)
+        for t in range(T):
+            if presence[t, col] > .5:
+                rect_stn(axes[1][col], img_w, img_h, where[t, col], colours(t % 10), line_width=1)
+        axes[1][col].set_title('n = {:d}, q = {:.02f}'.format(int(presence[:, col].sum()), float(count_prob[col])), fontsize=4 * inch)
+        axes[2][col].imshow(owner[col], cmap='tab10', vmin=-1, vmax=max(T - 1, 8), interpolation='nearest')
+    for ax in axes.ravel():
+        ax.set_axis_off()
+    if checkpoint_dir is not None:
+        fig.savefig(osp.join(checkpoint_dir, 'parse_fig_{}.png'.format(global_step)), dpi=300)
+        plt.close(fig)
+    return fig
+
+
+def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time=True):
+    """The deterministic parse (air.parse: the mode of q(n | x), latents at their posterior means) over `num_batches` batches from
+    `data_fn`: map_num_step_acc (the count against the true one), the mean count_prob (q at the mode) and the mean number of
+    objects per image.  Prints / writes one line like make_expr_logger."""
+    import torch
+
+    def logger(itr=0, num_batches_to_eval=None, write=True):
+        n = num_batches if num_batches_to_eval is None else num_batches_to_eval
+        n = max(int(n), 1)
+        start = time.time()
+        tot = torch.zeros(3, dtype=torch.float64, device=air.obs.device)
+        images = 0
+        for _ in range(n):
+            obs, nums = data_fn()
+            out = air.parse(obs)
+            gt = nums.sum(0).reshape(-1).to(torch.int64)
+            cnt = out["num_objects"].to(torch.int64)
+            tot += torch.stack([(cnt == gt).double().sum(), out["count_prob"].double().sum(), cnt.double().sum()])
+            images += int(cnt.numel())
+        vals = (tot / images).tolist()
+        acc = dict(map_num_step_acc=vals[0], count_prob=vals[1], num_objects=vals[2])
+        t = time.time() - start
+        msg = 'Step {}, Data {} parse '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, v) for k, v in acc.items())
+        if measure_time:
+            msg += ', eval time = {:.4}s'.format(t)
+        print(msg)
+        if write and writer is not None:
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **acc)) + "\n"); writer.flush()
+        return acc
+    return logger
+
+
 def gradient_summaries(named_grads, named_vars, norm=True, ratio=True, histogram=False, bins=30):
     """evaluation.py:221-248: the global norm of the gradient, per variable mean(|g| / (|v| + 1e-8)) (log_ratio,
     evaluation.py:169-180) and -- histogram=True, the reference's default -- a histogram of every gradient tensor, the content of its

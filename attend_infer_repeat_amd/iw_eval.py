@@ -46,6 +46,23 @@ def inner_config(cfg: EngineConfig) -> EngineConfig:
     return dataclasses.replace(cfg, use_reinforce=False, decay_rate=None, l2_weight=0.0)
 
 
+def load_inner_engine(owner, train_engine):
+    """`owner.engine` takes another engine's parameters (+ the bf16 shadow), its step counter and run-time switches, device to
+    device; the switches go through `owner.update_config` (which re-captures the owner's graphs when one changed).  Shared by
+    ImportanceEvaluator and parse.SceneParser."""
+    eng = owner.engine
+    if train_engine.n_total != eng.n_total or dict(train_engine.param_offsets) != dict(eng.param_offsets):
+        raise ValueError("the engines differ in architecture (flat parameter layout)")
+    knobs = {k: getattr(train_engine.cfg, k) for k in eng.KNOBS if k != "use_prior"}
+    owner.update_config(**knobs)
+    train_engine.wait_for_engine()                           # the caller's stream now follows the training engine's pending updates
+    eng._copy_in(eng.flat_params, train_engine.flat_params)
+    eng._copy_in(eng.step_dev, train_engine.step_dev)
+    eng.global_step = int(train_engine.global_step)
+    eng._sync_param_shadow()
+    train_engine.stream.wait_stream(eng.stream)              # ... and its next update follows the copy
+
+
 class ImportanceEvaluator:
     def __init__(self, cfg: EngineConfig, batch_size: int, particles: int, device=None, seed: int = 0,
                  normalize_steps_prior: bool = True):
@@ -109,17 +126,7 @@ class ImportanceEvaluator:
     # ---- parameters ---------------------------------------------------------------------------------------------------------
     def load_from(self, train_engine):
         """device-to-device copy of another engine's parameters (+ the bf16 shadow), its step counter and run-time switches"""
-        eng = self.engine
-        if train_engine.n_total != eng.n_total or dict(train_engine.param_offsets) != dict(eng.param_offsets):
-            raise ValueError("the engines differ in architecture (flat parameter layout)")
-        knobs = {k: getattr(train_engine.cfg, k) for k in eng.KNOBS if k != "use_prior"}
-        self.update_config(**knobs)
-        train_engine.wait_for_engine()                       # the caller's stream now follows the training engine's pending updates
-        eng._copy_in(eng.flat_params, train_engine.flat_params)
-        eng._copy_in(eng.step_dev, train_engine.step_dev)
-        eng.global_step = int(train_engine.global_step)
-        eng._sync_param_shadow()
-        train_engine.stream.wait_stream(eng.stream)          # ... and its next update follows the copy
+        load_inner_engine(self, train_engine)
 
     def load_parameters(self, named):
         self.engine.load_parameters(named)

@@ -289,6 +289,37 @@ class AIRonMNIST(AIRModel):
         self.generated_glimpse = out["glimpse"]
         return self
 
+    def scene_parser(self, batch_size=None):
+        """the SceneParser behind parse (built and captured on first use, rebuilt when the size or the device changes;
+        batch_size=None: the size it has, the batch size on first use)"""
+        eng = getattr(self, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("parse needs the fused engine: call train_step(...) with an engine-eligible "
+                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        from .parse import SceneParser
+        s = getattr(self, "_scene_parser", None)
+        n = int(batch_size) if batch_size is not None else (s.R if s is not None else eng.B)
+        if s is None or s.R != n or s.engine.device != eng.device:
+            if s is not None:
+                s.release_graphs()
+            s = SceneParser(eng.cfg, n, device=eng.device)
+            s.capture()
+            self._scene_parser = s
+        return s
+
+    def parse(self, obs=None, num_objects=None):
+        """Deterministic scene parse on the device (parse.SceneParser: its own engine at the mode of the inference network -- the
+        training engine's parameters are read, nothing of it is written).  obs=None: the model's current batch.  Returns the
+        parser's dict of device tensors (SceneParser.parse lists them: num_objects, count_prob, presence, score, boxes, what, where,
+        the object table behind offsets, reconstruction, rec, owner, area); the next call overwrites them."""
+        if obs is not None:
+            self.obs = obs
+        s = self.scene_parser(self.obs.shape[0])
+        self._sync_engine_switches()
+        s.load_from(self._engine)                            # every time: the weights move
+        self.parsed = s.parse(self.obs, num_objects)         # (the caller's stream is ordered after it)
+        return self.parsed
+
     def refresh(self):
         """Re-expose the engine's current buffers under the reference's attribute names."""
         if self._engine is not None:

@@ -20,7 +20,8 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from attend_infer_repeat_amd.data import DeviceFeeder, load_data, procedural_multi_mnist, synthetic_dataset  # noqa: E402
-from attend_infer_repeat_amd.evaluation import make_fig, make_iw_logger, make_logger, make_prior_fig, step_summaries  # noqa: E402
+from attend_infer_repeat_amd.evaluation import (make_fig, make_iw_logger, make_logger, make_parse_fig, make_parse_logger,  # noqa: E402
+                                                make_prior_fig, step_summaries)
 from attend_infer_repeat_amd.mnist_model import AIRonMNIST  # noqa: E402
 from attend_infer_repeat_amd.utils import AttrDict  # noqa: E402
 
@@ -70,6 +71,10 @@ def main(argv=None):
                     help="N > 0: at every --log-every draw N scenes from the generative model on the device (AIRonMNIST.sample_scenes, the "
                          "model's own count prior) and write the histogram of the generated object counts to log.jsonl; with --figures also "
                          "prior_fig_<iter>.png (evaluation.make_prior_fig, uniform counts); 0 = off")
+    ap.add_argument("--parse-eval", action="store_true",
+                    help="at every --log-every also print / write the deterministic parse of the validation batches (AIRonMNIST.parse, "
+                         "evaluation.make_parse_logger): the accuracy of the MAP object count, the mean q(n) at the mode and the mean number "
+                         "of objects per image; with --figures also parse_fig_<iter>.png (evaluation.make_parse_fig)")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -169,6 +174,17 @@ def main(argv=None):
                                          count_probs="model", count_hist=hist)) + "\n"); writer.flush()
             if args.figures:
                 make_prior_fig(air, logdir, train_itr)
+            return out
+
+    if args.parse_eval:
+        before_parse_log = log
+        parse_log = make_parse_logger(air, valid_feed, args.eval_batches, 'test', writer)
+
+        def log(train_itr):                               # noqa: F811
+            out = before_parse_log(train_itr)
+            parse_log(train_itr)
+            if args.figures:
+                make_parse_fig(air, logdir, train_itr)
             return out
 
     train_itr = int(global_step)

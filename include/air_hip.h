@@ -560,6 +560,35 @@ AIR_ENGINE_API int air_prior_latents(const double *count_table_f64, const float 
 AIR_ENGINE_API int air_observe(const float *canvas, float mult, float std, const uint64_t *state_dev, uint64_t counter_base,
                 float clamp_lo, float clamp_hi, float *mean_out, float *obs_out, size_t n, void *stream);
 
+/* ---- scene parsing: the read-out behind a forward pass at the mode of the inference network (zero latent noise, every presence
+ * draw forced to succeed: what = what_loc, where = where_loc after the guard rule, all T steps computed).  Discrete steps only.
+ * air_parse_objects: from presence_prob[T,R] form, in float64 and in index order, m_0 = 1 - p_1, m_n = (prod_{i<=n} p_i)(1 - p_{n+1}),
+ *   m_T = prod_i p_i (the arithmetic of air_numsteps_fwd) and q(n) = m_n / sum m.  n^ = the SMALLEST n attaining max_n m_n (the
+ *   division does not enter the arg-max).  num_objects_in[R] (optional): n^ = that value clipped to 0..T, presence_prob is not
+ *   consulted for the count (the convention of air_prior_latents) and may be NULL -- score and count_prob are then NaN.
+ *   Per step and image: presence[t,r] = t < n^ ? 1 : 0;  score[t,r] = sum_{n>t} q(n), fp32, added from n = T down (the step weight
+ *   air_numsteps_fwd writes);  boxes[t,r,:] = (left, top, width, height) = (W (1 - sx + tx) / 2, H (1 - sy + ty) / 2, W sx, H sy) of
+ *   where[t,r] = [sx, tx, sy, ty], in fp32, in that operation order.  Per image: num_objects[r] = n^, count_prob[r] = (float) q(n^).
+ *   Object table, image-major, step order inside an image: offsets[R+1] = exclusive scan of num_objects; object j of image r is row
+ *   offsets[r] + j of obj_image / obj_step (int32), obj_box[.,4], obj_score, obj_where[.,4], obj_what[.,A] (copies of boxes, score,
+ *   where, what: the same bits).  Capacity T * R rows; rows at and beyond offsets[R] are not written.
+ *   Three kernels: one wavefront per image (count, T <= 32), ONE workgroup for the scan (R arbitrary, in passes; integers, fixed
+ *   order, no atomics), one wavefront per image for the table.  where / boxes / obj_box / obj_where 16-byte aligned (AIR_E_ALIGN).
+ * air_parse_render: layer_t = st_write(glimpse_t, where_t) (glimpse[T,R,h,w]: the decoder's raw output), canvas = sum of layer_t over
+ *   the steps with presence[t,r] > 0.5, added in step order with the operations of air_canvas_unroll_fwd (the same bits as that entry's
+ *   final_canvas for the same presences);  reconstruction[R,H,W] = mult * canvas;  rec_parts[n_bands,R] (optional, needs obs): each
+ *   row band's share of the reconstruction term of air_rec_loglik_fwd, to be added in band order (air_sum_leading); n_bands as for
+ *   air_canvas_unroll_fwd_banded.  owner[R,H,W] (int8) = the smallest present t attaining max_t mult * layer_t(p) if that maximum is
+ *   > mask_threshold, else -1;  area[T,R] (int32) = number of pixels step t owns (integer adds; the entry zeroes the buffer itself);
+ *   layers[T,R,H,W] (optional) = mult * layer_t, zeros for absent steps.  T <= 32; where 16-byte aligned (AIR_E_ALIGN).          */
+AIR_ENGINE_API int air_parse_objects(const float *presence_prob, const int *num_objects_in, const float *where, const float *what,
+                      int T, int R, int A, int H, int W, int *num_objects, float *count_prob, float *presence, float *score,
+                      float *boxes, int *offsets, int *obj_image, int *obj_step, float *obj_box, float *obj_score,
+                      float *obj_where, float *obj_what, void *stream);
+AIR_ENGINE_API int air_parse_render(const float *glimpse, const float *where, const float *presence, const float *obs, float mult,
+                     float std, float mask_threshold, int T, int R, int H, int W, int h, int w, int n_bands,
+                     float *reconstruction, float *rec_parts, signed char *owner, int *area, float *layers, void *stream);
+
 
 /* Baseline input assembly, modules.py:131-139: out[B, HW + T*A + T*4 + T + S] =
  * [img | what (batch-major) | where | presence | state] from time-major what[T,B,A], where[T,B,4], presence[T,B],

@@ -11,9 +11,7 @@
 #include <string>
 #include <functional>
 #include "../../attend_infer_repeat_amd/csrc/st_kernels.hip"
-#define lin_step lin_step_cv          // (both translation units define this host helper)
 #include "../../attend_infer_repeat_amd/csrc/canvas_kernels.hip"
-#undef lin_step
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 
