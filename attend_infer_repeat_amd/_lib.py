@@ -190,6 +190,9 @@ SIGNATURES = {
     "air_parse_objects": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "air_parse_render": (c_int, [P, P, P, P, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                  P, P, P, P, P, P]),
+    "air_score_contingency": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "air_score_match": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+    "air_score_reduce": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, P]),
     "air_l2_grad_add": (c_int, [P, P, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t), c_int, c_float, P]),
     "air_baseline_pack": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "air_rmsprop_centered": (c_int, [P, P, P, P, P, c_size_t, P, c_float, c_float, c_float, c_float, c_float, P]),

@@ -119,7 +119,8 @@ def _resize_templates(templates, obj_size):
 
 
 def create_multi_mnist(templates, labels=None, canvas_size=(50, 50), obj_size=(28, 28), n_objects=(0, 2), n_samples=None,
-                       dtype=np.uint8, expand_nums=True, with_overlap=False, seed=0, max_tries=5, rng=None):
+                       dtype=np.uint8, expand_nums=True, with_overlap=False, seed=0, max_tries=5, rng=None,
+                       return_annotations=False):
     """Multi-digit canvases from single-digit templates: the generator of the reference's dataset script (data.py:35-107),
     draw for draw.
 
@@ -134,7 +135,11 @@ def create_multi_mnist(templates, labels=None, canvas_size=(50, 50), obj_size=(2
     of its objects -- reaches `max_tries`, even if the last draw was free (:84-97), and a template's box is `_tight_box`.
     The reference cannot place three or more objects (rand(3) does not broadcast against two ranges: ValueError); here samples
     with n > 2 draw rand(2) per try instead (BASELINE configs[3]: 0-4 digits).
-    Returns dict(imgs [n,H,W] dtype, labels [n,max] uint8, nums [max+1,n,1] cumulative one-hot (data.py:101-105) or [n] counts)."""
+    Returns dict(imgs [n,H,W] dtype, labels [n,max] uint8, nums [max+1,n,1] cumulative one-hot (data.py:101-105) or [n] counts).
+    `return_annotations=True` adds what the generator knows about the placement (no draw on `rng` changes): boxes [n,max,4]
+    float32, (left, top, width, height) of object j in placement order in pixel-index units (evaluation.attention_box's convention;
+    rows from the sample's count on are zero), and instances [n,H,W] int8: the object a pixel belongs to, -1 = background -- inside
+    each pasted rectangle j where the crop is > 0 and -1 elsewhere, as the image write overwrites the rectangle."""
     rng = np.random.RandomState(seed) if rng is None else rng
     templates = np.asarray(templates)
     if templates.dtype != np.uint8:
@@ -147,6 +152,8 @@ def create_multi_mnist(templates, labels=None, canvas_size=(50, 50), obj_size=(2
     imgs = np.zeros((n_samples, H, W), dtype=dtype)
     lab = np.zeros((n_samples, max_objects), dtype=np.uint8)
     nums = rng.randint(max_objects + 1, size=n_samples, dtype=np.uint8)
+    gt_boxes = np.zeros((n_samples, max_objects, 4), np.float32)
+    instances = np.full((n_samples, H, W), -1, np.int8) if return_annotations else None
     boxes = {}
     occupancy = np.zeros((H, W), dtype=bool)
     i = 0
@@ -174,11 +181,17 @@ def create_multi_mnist(templates, labels=None, canvas_size=(50, 50), obj_size=(2
                         break
                 imgs[i, p[0]:p[0] + sh, p[1]:p[1] + sw] = templates[k, y0:y0 + sh, x0:x0 + sw]
                 occupancy[p[0]:p[0] + sh, p[1]:p[1] + sw] = True
+                gt_boxes[i, j] = (p[1], p[0], sw, sh)
+                if return_annotations:
+                    instances[i, p[0]:p[0] + sh, p[1]:p[1] + sw] = np.where(templates[k, y0:y0 + sh, x0:x0 + sw] > 0, j, -1)
                 if labels is not None:
                     lab[i, j] = labels[k]
         if retry:
             imgs[i] = 0
             lab[i] = 0
+            gt_boxes[i] = 0
+            if return_annotations:
+                instances[i] = -1
         else:
             i += 1
     if expand_nums:
@@ -186,6 +199,8 @@ def create_multi_mnist(templates, labels=None, canvas_size=(50, 50), obj_size=(2
         for s, n in enumerate(nums):
             expanded[:n, s] = 1
         nums = expanded
+    if return_annotations:
+        return dict(imgs=imgs, labels=lab, nums=nums, boxes=gt_boxes, instances=instances)
     return dict(imgs=imgs, labels=lab, nums=nums)
 
 
@@ -233,12 +248,13 @@ def procedural_digit_templates(n, seed=0, size=28):
     return out, labels
 
 
-def procedural_multi_mnist(n_samples, canvas_size=(50, 50), n_objects=(0, 2), seed=0, n_templates=4000):
+def procedural_multi_mnist(n_samples, canvas_size=(50, 50), n_objects=(0, 2), seed=0, n_templates=4000,
+                           return_annotations=False):
     """A multi-MNIST-shaped dataset in the reference's format (dict(imgs uint8, labels, nums) of create_multi_mnist, i.e. of
     data.py:35-107) from procedural digit templates: the reference's generator end to end, with only the MNIST download replaced."""
     templates, labels = procedural_digit_templates(n_templates, seed=seed)
     return create_multi_mnist(templates, labels, canvas_size=canvas_size, n_objects=n_objects, n_samples=n_samples,
-                              seed=seed + 1)
+                              seed=seed + 1, return_annotations=return_annotations)
 
 
 def load_mnist_idx(directory, partition="train"):

@@ -167,6 +167,44 @@ def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time
     return logger
 
 
+def make_parse_score_logger(air, data, num_batches, name, writer=None, thresholds=None, measure_time=True):
+    """The deterministic parse scored against the generator's annotations on the device (air.score_parse, score.ParseScorer):
+    `data` is an annotated dataset dict (imgs [N, H, W], boxes [N, G, 4], instances [N, H, W] int8 -- data.create_multi_mnist with
+    return_annotations=True), walked in order from its start in `num_batches` batches of the model's size (fewer when the data
+    runs out).  The sums and the predictions AP needs stay on the device; ParseScorer.summary() is the one readback.  Prints /
+    writes one line like make_parse_logger: count accuracy, precision / recall / F1 / AP per box-IoU threshold and their mean AP,
+    foreground ARI, mean best overlap."""
+    import torch
+    G = int(data["boxes"].shape[1])
+    kw = {} if thresholds is None else dict(thresholds=tuple(thresholds))
+
+    def logger(itr=0, num_batches_to_eval=None, write=True):
+        n = num_batches if num_batches_to_eval is None else num_batches_to_eval
+        B = int(air.obs.shape[0])
+        n = min(max(int(n), 1), int(data["imgs"].shape[0]) // B)
+        if n < 1:
+            raise ValueError("the annotated dataset holds fewer images than one batch of %d" % B)
+        start = time.time()
+        dev = air.obs.device
+        scorer = air.parse_scorer(G, **kw)
+        scorer.reset()
+        for i in range(n):
+            sl = slice(i * B, (i + 1) * B)
+            air.score_parse(torch.as_tensor(data["imgs"][sl], dtype=torch.float32).to(dev), torch.as_tensor(data["instances"][sl]),
+                            torch.as_tensor(data["boxes"][sl]), **kw)
+        acc = scorer.summary()
+        t = time.time() - start
+        shown = ["count_acc", "map", "ap@%.2f" % scorer.thresholds_host[0], "fg_ari", "mean_best_overlap", "matched_box_iou"]
+        msg = 'Step {}, Data {} parse score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
+        if measure_time:
+            msg += ', eval time = {:.4}s'.format(t)
+        print(msg)
+        if write and writer is not None:
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **acc)) + "\n"); writer.flush()
+        return acc
+    return logger
+
+
 def gradient_summaries(named_grads, named_vars, norm=True, ratio=True, histogram=False, bins=30):
     """evaluation.py:221-248: the global norm of the gradient, per variable mean(|g| / (|v| + 1e-8)) (log_ratio,
     evaluation.py:169-180) and -- histogram=True, the reference's default -- a histogram of every gradient tensor, the content of its

@@ -320,6 +320,31 @@ class AIRonMNIST(AIRModel):
         self.parsed = s.parse(self.obs, num_objects)         # (the caller's stream is ordered after it)
         return self.parsed
 
+    def parse_scorer(self, max_gt_objects, thresholds=None):
+        """the ParseScorer behind score_parse, bound to the scene parser of the current batch size (built and captured on first use,
+        rebuilt when the parser, the number of ground-truth slots or the thresholds change)"""
+        from .score import DEFAULT_THRESHOLDS, ParseScorer
+        parser = self.scene_parser(self.obs.shape[0])
+        th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
+        s = getattr(self, "_parse_scorer", None)
+        if s is None or s.parser is not parser or s.G != int(max_gt_objects) or s.thresholds_host != th:
+            if s is not None:
+                s.release_graphs()
+            s = ParseScorer(parser, max_gt_objects, th)
+            s.capture()
+            self._parse_scorer = s
+        return s
+
+    def score_parse(self, obs, gt_instances, gt_boxes, gt_count=None, thresholds=None, accumulate=True):
+        """Parse `obs` (AIRonMNIST.parse), then score the parse against the ground truth on the device (score.ParseScorer.score lists
+        the arguments and the returned device tensors).  gt_count=None: the number of rows of gt_boxes with width > 0.  The sums
+        accumulate in `parse_scorer(...)`: its reset() starts a validation set, its summary() reads the figures back once."""
+        import torch
+        self.parse(obs)
+        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds)
+        self.parse_scores = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
+        return self.parse_scores
+
     def refresh(self):
         """Re-expose the engine's current buffers under the reference's attribute names."""
         if self._engine is not None:

@@ -23,12 +23,16 @@ def main(argv=None):
     ap.add_argument("--mnist-dir", default="data/MNIST_data")
     ap.add_argument("--out-dir", default="data")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--annotations", action="store_true",
+                    help="also store where the generator put every digit: boxes [n, max, 4] (left, top, width, height) and instances "
+                         "[n, H, W] int8 (-1 = background), what scripts/multi_mnist.py --parse-score scores a parse against")
     args = ap.parse_args(argv)
     os.makedirs(args.out_dir, exist_ok=True)
     for i, (partition, n) in enumerate((("train", 60000), ("validation", 10000))):       # data.py:161-162
         print('Processing partition "{}"'.format(partition))
         templates, labels = load_mnist_idx(args.mnist_dir, partition)
-        data = create_multi_mnist(templates, labels, n_samples=n, seed=args.seed + i)
+        extra = dict(return_annotations=True) if args.annotations else {}
+        data = create_multi_mnist(templates, labels, n_samples=n, seed=args.seed + i, **extra)
         path = osp.join(args.out_dir, "mnist_{}.pickle".format(partition))
         print('saving to "{}"'.format(path))
         with open(path, "wb") as f:

@@ -20,7 +20,7 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from attend_infer_repeat_amd.data import DeviceFeeder, load_data, procedural_multi_mnist, synthetic_dataset  # noqa: E402
-from attend_infer_repeat_amd.evaluation import (make_fig, make_iw_logger, make_logger, make_parse_fig, make_parse_logger,  # noqa: E402
+from attend_infer_repeat_amd.evaluation import (make_fig, make_iw_logger, make_logger, make_parse_fig, make_parse_logger, make_parse_score_logger,  # noqa: E402
                                                 make_prior_fig, step_summaries)
 from attend_infer_repeat_amd.mnist_model import AIRonMNIST  # noqa: E402
 from attend_infer_repeat_amd.utils import AttrDict  # noqa: E402
@@ -75,6 +75,11 @@ def main(argv=None):
                     help="at every --log-every also print / write the deterministic parse of the validation batches (AIRonMNIST.parse, "
                          "evaluation.make_parse_logger): the accuracy of the MAP object count, the mean q(n) at the mode and the mean number "
                          "of objects per image; with --figures also parse_fig_<iter>.png (evaluation.make_parse_fig)")
+    ap.add_argument("--parse-score", action="store_true",
+                    help="at every --log-every also score the deterministic parse of the validation set against its annotations on the "
+                         "device (AIRonMNIST.score_parse, evaluation.make_parse_score_logger): count accuracy, precision / recall / F1 / AP "
+                         "over box-IoU thresholds, foreground ARI and mean best overlap of the instance masks.  Needs annotated data: "
+                         "--glyphs, or pickles written by create_dataset.py --annotations")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -98,11 +103,18 @@ def main(argv=None):
         print("no multi-MNIST pickles under {!r}: procedural digit templates through the reference's generator".format(args.data_dir))
         as_float = lambda d: dict(imgs=d["imgs"].astype("float32") / 255.0, nums=d["nums"].astype("float32"))
         train_data = as_float(procedural_multi_mnist(args.synthetic_samples, seed=args.seed))
-        valid_data = as_float(procedural_multi_mnist(max(args.synthetic_samples // 6, batch_size), seed=args.seed + 1000))
+        valid_raw = procedural_multi_mnist(max(args.synthetic_samples // 6, batch_size), seed=args.seed + 1000,
+                                           return_annotations=args.parse_score)
+        valid_data = as_float(valid_raw)
+        if args.parse_score:
+            valid_data.update(boxes=valid_raw["boxes"], instances=valid_raw["instances"])
     else:
         print("no multi-MNIST pickles under {!r}: using a synthetic dataset".format(args.data_dir))
         train_data = synthetic_dataset(args.synthetic_samples, seed=args.seed)
         valid_data = synthetic_dataset(max(args.synthetic_samples // 6, batch_size), seed=args.seed + 1)
+    if args.parse_score and not ("boxes" in valid_data and "instances" in valid_data):
+        ap.error("--parse-score needs annotated validation data (boxes and instances): pass --glyphs, or write the pickles with "
+                 "create_dataset.py --annotations; the stroke-blob synthetic dataset has no annotations")
     train_feed = DeviceFeeder(train_data, batch_size, device, shuffle=True, seed=args.seed)
     valid_feed = DeviceFeeder(valid_data, batch_size, device, shuffle=False)
     x, y = train_feed()
@@ -185,6 +197,15 @@ def main(argv=None):
             parse_log(train_itr)
             if args.figures:
                 make_parse_fig(air, logdir, train_itr)
+            return out
+
+    if args.parse_score:
+        before_score_log = log
+        score_log = make_parse_score_logger(air, valid_data, args.eval_batches, 'test', writer)
+
+        def log(train_itr):                               # noqa: F811
+            out = before_score_log(train_itr)
+            score_log(train_itr)
             return out
 
     train_itr = int(global_step)

@@ -589,6 +589,42 @@ AIR_ENGINE_API int air_parse_render(const float *glimpse, const float *where, co
                      float std, float mask_threshold, int T, int R, int H, int W, int h, int w, int n_bands,
                      float *reconstruction, float *rec_parts, signed char *owner, int *area, float *layers, void *stream);
 
+/* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
+ * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
+ * (AIR_E_SHAPE otherwise, and when R*H*W or R*(T+1)*(G+1) passes int32).  No floating-point atomics; float64 with contraction off
+ * wherever a float decides; the same bits run to run.  With n^ = clip(num_objects[r], 0, T) and g = clip(gt_count[r], 0, G):
+ * air_score_contingency: cont[R,T+1,G+1] (int32); cont[r,a,b] = #pixels of image r with owner + 1 == a and gt + 1 == b.  A pixel whose
+ *   owner is outside -1..T-1 or whose gt is outside -1..G-1 is counted nowhere.  Every bin is written (no pre-zeroing).  One workgroup
+ *   per image, one LDS histogram per wave, integer adds; 16-byte loads between the unaligned head and tail of an image's row.
+ * air_score_match: one wavefront per image.
+ *   box_iou[R,T,G]: with x0 = min(l, l+w), x1 = max(l, l+w) (y alike; widths may be negative), iw = max(0, min(ax1,bx1) - max(ax0,bx0)),
+ *     ih alike, inter = iw*ih, union = ((ax1-ax0)(ay1-ay0) + (bx1-bx0)(by1-by0)) - inter, all in float64 from the widened fp32 inputs:
+ *     inter/union if inter > 0, union > 0 and the quotient is finite, else 0 (a NaN coordinate scores 0).  Rounded once to fp32.
+ *   mask_iou[R,T,G] = n_tj / (a_t + b_j - n_tj) with n_tj = cont[r,t+1,j+1], a_t / b_j the sums of that row / column (integers, one
+ *     float64 division; 0 for an empty union).  Both are 0 for t >= n^ or j >= g.
+ *   match[K,T,R] (int8): for each threshold k, used = {}, for t = 0 .. n^-1 in step order (score order: score[t] is non-increasing in
+ *     t): among j < g not used with iou > 0 and iou >= (double)thresholds[k] the largest float64 box IoU, the smallest j on an exact
+ *     tie; that j is used and stored, -1 when there is none and for t >= n^.
+ *   ari[R]: foreground adjusted Rand index from the columns b >= 1 of cont, rows a = 0..T (predicted background is a cluster): int64
+ *     N = sum n_ab, S = sum C(n_ab,2), P = sum_a C(A_a,2), Q = sum_b C(B_b,2); float64 E = P*Q / C(N,2), M = (P+Q)/2,
+ *     ari = (S-E)/(M-E); NaN when N == 0, 1 when C(N,2) == 0 or M == E.
+ *   best_overlap[R,G] = max_{t<n^} mask_iou[r,t,j] (0 when n^ == 0), -1 for j >= g.  count_err[R] (int32) = n^ - g.
+ *   boxes / gt_boxes 16-byte aligned (AIR_E_ALIGN).
+ * air_score_reduce: totals_i[6+K] (int64) = {images, images with count_err == 0, sum |count_err|, sum n^, sum g, images with a finite
+ *   ari, true positives (match >= 0) per threshold};  totals_f[3] (float64) = {sum of the finite ari, sum of best_overlap over j < g,
+ *   sum of the stored box_iou of the pairs matched at thresholds[0]}.  accumulate == 0 overwrites the totals, != 0 adds to them.
+ *   ONE workgroup of 1024 threads: thread i adds the images i, i+1024, i+2048, ... in that order (inside an image: objects, then
+ *   steps, in index order), the 64 partial sums of a wave are added by the shuffle tree with offsets 32, 16, ..., 1, and the sixteen
+ *   wave totals in wave order: the order depends on R alone.                                                                     */
+AIR_ENGINE_API int air_score_contingency(const signed char *owner, const signed char *gt, int T, int G, int R, int H, int W, int *cont,
+                          void *stream);
+AIR_ENGINE_API int air_score_match(const int *cont, const float *boxes, const int *num_objects, const float *gt_boxes,
+                    const int *gt_count, const float *thresholds, int T, int G, int K, int R, float *box_iou, float *mask_iou,
+                    signed char *match, float *ari, float *best_overlap, int *count_err, void *stream);
+AIR_ENGINE_API int air_score_reduce(const int *num_objects, const int *gt_count, const int *count_err, const float *ari,
+                     const float *best_overlap, const signed char *match, const float *box_iou, int T, int G, int K, int R,
+                     int64_t *totals_i, double *totals_f, int accumulate, void *stream);
+
 
 /* Baseline input assembly, modules.py:131-139: out[B, HW + T*A + T*4 + T + S] =
  * [img | what (batch-major) | where | presence | state] from time-major what[T,B,A], where[T,B,4], presence[T,B],
