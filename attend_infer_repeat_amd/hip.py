@@ -442,14 +442,182 @@ def numsteps_bwd(presence_prob, presence, prior_f64, kl_scale, dstep_weight=None
     return dprob
 
 
+def _prior_f64(prior_f64, T):
+    if not torch.is_tensor(prior_f64) or prior_f64.dtype != torch.float64 or not prior_f64.is_cuda:
+        raise _lib.AirHipError("numsteps: prior must be a float64 CUDA tensor")
+    if prior_f64.numel() < T + 1:
+        raise _lib.AirHipError(f"numsteps: prior holds {prior_f64.numel()} entries, T + 1 = {T + 1} are read")
+    return prior_f64
+
+
+def _tb(shape, **tensors):
+    """every given tensor is [T, B] (or [B] when 1-D): the kernels index them by t * B + b without a bound of their own"""
+    for nm, t in tensors.items():
+        if t is not None and tuple(t.shape) != (tuple(shape) if t.dim() == 2 else (shape[1],)):
+            raise _lib.AirHipError(f"{nm}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _numsteps_outputs(T, B, dev):
+    e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    return e(T, B), e(T, B), e(B, T + 1), e(B), e(B), e(T, B)       # prob, presence, q, kl, logp, step weight
+
+
+def presence_numsteps_fwd(logit, u, step_bias, explore_eps, prior_f64):
+    """air_presence_numsteps_fwd: logit[T,B], u[T,B] (None: continuous steps, presence = presence_prob)
+    -> presence_prob, presence, q[B,T+1], kl_per_sample[B], logp[B], step_weight[T,B]"""
+    logit = _f32(logit, "logit", 2); u = _f32(u, "u", 2)
+    T, B = logit.shape
+    _tb((T, B), u=u)
+    prior_f64 = _prior_f64(prior_f64, T)
+    prob, pres, q, kl, logp, w = _numsteps_outputs(T, B, logit.device)
+    eps = -1.0 if explore_eps is None else float(explore_eps)
+    _lib.check(lib().air_presence_numsteps_fwd(_p(logit), _p(u), float(step_bias), eps, _p(prior_f64), _p(prob), _p(pres),
+                                               _p(q), _p(kl), _p(logp), _p(w), T, B, _stream()), "air_presence_numsteps_fwd")
+    return prob, pres, q, kl, logp, w
+
+
+def numsteps_presence_bwd(presence_prob, presence, prior_f64, kl_scale, kl_row_a, kl_row_b, w_scale, dlogp, dpresence, logit,
+                          step_bias, explore_eps):
+    """air_numsteps_presence_bwd -> dlogit[T,B]; kl_row_a / kl_row_b / dlogp / dpresence may be None"""
+    presence_prob = _f32(presence_prob, "presence_prob", 2); logit = _f32(logit, "logit", 2)
+    T, B = presence_prob.shape
+    _tb((T, B), presence=presence, kl_row_a=kl_row_a, kl_row_b=kl_row_b, dlogp=dlogp, dpresence=dpresence, logit=logit)
+    prior_f64 = _prior_f64(prior_f64, T)
+    dlogit = torch.empty_like(logit)
+    eps = -1.0 if explore_eps is None else float(explore_eps)
+    _lib.check(lib().air_numsteps_presence_bwd(_p(presence_prob), _p(_f32(presence, "presence", 2)), _p(prior_f64), float(kl_scale),
+                                               _p(_f32(kl_row_a, "kl_row_a", 2)), _p(_f32(kl_row_b, "kl_row_b", 2)), float(w_scale),
+                                               _p(_f32(dlogp, "dlogp", 1)), _p(_f32(dpresence, "dpresence", 2)), _p(logit),
+                                               float(step_bias), eps, _p(dlogit), T, B, _stream()), "air_numsteps_presence_bwd")
+    return dlogit
+
+
+def _gauss_pre(pre, name):
+    if not (torch.is_tensor(pre) and pre.is_cuda and pre.dtype == torch.float32 and pre.dim() == 2 and pre.stride(1) == 1):
+        raise _lib.AirHipError(f"{name}: pre must be a 2-D float32 CUDA tensor with unit inner stride")
+    return pre.stride(0) if pre.shape[0] > 1 else pre.shape[1]
+
+
+def heads_fwd(pre, eps, raw_offset, loc_mode, prior4, logit, u, step_bias, explore_eps, prior_f64, guard_eps=0.0):
+    """air_heads_fwd = gauss_sample_fwd(pre, eps, ...) || presence_numsteps_fwd(logit, u, ...) in one launch
+    -> (loc, scale, sample, kl_row), (presence_prob, presence, q, kl_per_sample, logp, step_weight)"""
+    ld = _gauss_pre(pre, "heads_fwd")
+    eps = _f32(eps, "eps", 2); logit = _f32(logit, "logit", 2); u = _f32(u, "u", 2)
+    M, D = eps.shape
+    T, B = logit.shape
+    _tb((T, B), u=u)
+    if pre.shape[0] != M or pre.shape[1] < 2 * D:
+        raise _lib.AirHipError(f"heads_fwd: pre is {tuple(pre.shape)}, eps {tuple(eps.shape)}")
+    prior_f64 = _prior_f64(prior_f64, T)
+    dev = pre.device
+    loc = torch.empty((M, D), dtype=torch.float32, device=dev); scale = torch.empty_like(loc); sample = torch.empty_like(loc)
+    kl_row = torch.empty((M,), dtype=torch.float32, device=dev)
+    prob, pres, q, kl, logp, w = _numsteps_outputs(T, B, dev)
+    a, b, c, d = (float(v) for v in prior4)
+    xe = -1.0 if explore_eps is None else float(explore_eps)
+    _lib.check(lib().air_heads_fwd(_p(pre), ld, _p(eps), float(raw_offset), int(loc_mode), a, b, c, d, _p(loc), _p(scale),
+                                   _p(sample), _p(kl_row), M, D, _p(logit), _p(u), float(step_bias), xe, _p(prior_f64),
+                                   _p(prob), _p(pres), _p(q), _p(kl), _p(logp), _p(w), T, B, float(guard_eps), _stream()),
+               "air_heads_fwd")
+    return (loc, scale, sample, kl_row), (prob, pres, q, kl, logp, w)
+
+
+def heads_bwd(pre, eps, raw_offset, loc_mode, prior4, loc, scale, dsample, dkl_row, presence_prob, presence, prior_f64,
+              kl_scale, kl_row_a, kl_row_b, w_scale, dlogp, dpresence, logit, step_bias, explore_eps, guard_eps=0.0):
+    """air_heads_bwd = gauss_sample_bwd || numsteps_presence_bwd in one launch -> dpre[M,2D], dlogit[T,B]"""
+    ld = _gauss_pre(pre, "heads_bwd")
+    loc = _f32(loc, "loc", 2); scale = _f32(scale, "scale", 2); eps = _f32(eps, "eps", 2)
+    presence_prob = _f32(presence_prob, "presence_prob", 2); logit = _f32(logit, "logit", 2)
+    M, D = loc.shape
+    T, B = presence_prob.shape
+    _tb((T, B), presence=presence, kl_row_a=kl_row_a, kl_row_b=kl_row_b, dlogp=dlogp, dpresence=dpresence, logit=logit)
+    _tb((M, D), scale=scale, eps=eps, dsample=dsample)
+    if pre.shape[0] != M or pre.shape[1] < 2 * D or (dkl_row is not None and tuple(dkl_row.shape) != (M,)):
+        raise _lib.AirHipError(f"heads_bwd: pre is {tuple(pre.shape)}, loc {tuple(loc.shape)}")
+    prior_f64 = _prior_f64(prior_f64, T)
+    dpre = torch.empty((M, 2 * D), dtype=torch.float32, device=pre.device)
+    dlogit = torch.empty_like(logit)
+    a, b, c, d = (float(v) for v in prior4)
+    xe = -1.0 if explore_eps is None else float(explore_eps)
+    _lib.check(lib().air_heads_bwd(_p(pre), ld, _p(eps), float(raw_offset), int(loc_mode), a, b, c, d, _p(loc), _p(scale),
+                                   _p(_f32(dsample, "dsample", 2)), None, _p(_f32(dkl_row, "dkl_row", 1)), 1.0, _p(dpre), 2 * D,
+                                   M, D, _p(presence_prob), _p(_f32(presence, "presence", 2)), _p(prior_f64), float(kl_scale),
+                                   _p(_f32(kl_row_a, "kl_row_a", 2)), _p(_f32(kl_row_b, "kl_row_b", 2)), float(w_scale),
+                                   _p(_f32(dlogp, "dlogp", 1)), _p(_f32(dpresence, "dpresence", 2)), _p(logit), float(step_bias),
+                                   xe, _p(dlogit), T, B, float(guard_eps), _stream()), "air_heads_bwd")
+    return dpre, dlogit
+
+
+ANNEAL_TYPES = {None: 0, "exp": 1, "linear": 2}
+
+
+def steps_prior(global_step_dev, T, init, final_value=0.0, anneal_type=None, anneal_steps=1.0, hold_for=0.0, steps_div=1.0):
+    """air_steps_prior: the annealed geometric prior table [T+1] (float64, not renormalised) at the step count held on the
+    device in global_step_dev (an int64 CUDA tensor of one element)."""
+    if not (torch.is_tensor(global_step_dev) and global_step_dev.is_cuda and global_step_dev.dtype == torch.int64
+            and global_step_dev.numel() >= 1):
+        raise _lib.AirHipError("steps_prior: global_step_dev must be an int64 CUDA tensor")
+    if anneal_type not in ANNEAL_TYPES:
+        raise _lib.AirHipError(f"steps_prior: anneal_type must be one of {list(ANNEAL_TYPES)}")
+    out = torch.empty((int(T) + 1,), dtype=torch.float64, device=global_step_dev.device)
+    _lib.check(lib().air_steps_prior(_p(global_step_dev), ANNEAL_TYPES[anneal_type], float(init), float(final_value),
+                                     float(anneal_steps), float(hold_for), float(steps_div), _p(out), int(T), _stream()),
+               "air_steps_prior")
+    return out
+
+
 def nvil(imp, baseline, logp, ema=None):
+    """ema: None, or the DEVICE block of four floats {moving_mean, moving_var, decay, update} (updated in place when update != 0)"""
     imp = _f32(imp, "imp", 1); baseline = _f32(baseline, "baseline", 1); logp = _f32(logp, "logp", 1)
+    ema = _f32(ema, "ema", 1)
+    if ema is not None and ema.numel() != 4:
+        raise _lib.AirHipError("nvil: ema must hold four floats {moving_mean, moving_var, decay, update}")
     B = imp.shape[0]
     dev = imp.device
     out = torch.empty((4,), dtype=torch.float32, device=dev)
     dlogp = torch.empty((B,), dtype=torch.float32, device=dev); dbase = torch.empty((B,), dtype=torch.float32, device=dev)
     _lib.check(lib().air_nvil(_p(imp), _p(baseline), _p(logp), _p(out), _p(dlogp), _p(dbase), B, _p(ema), _stream()), "air_nvil")
     return out, dlogp, dbase
+
+
+def nvil_parts(imp_parts, baseline, logp, ema=None, want_sum=True):
+    """air_nvil_parts: imp_parts[n_parts, B] shares of the importance weight -> out[4], dlogp[B], dbaseline[B], imp_sum[B] | None"""
+    imp_parts = _f32(imp_parts, "imp_parts", 2); baseline = _f32(baseline, "baseline", 1); logp = _f32(logp, "logp", 1)
+    ema = _f32(ema, "ema", 1)
+    if ema is not None and ema.numel() != 4:
+        raise _lib.AirHipError("nvil_parts: ema must hold four floats {moving_mean, moving_var, decay, update}")
+    n_parts, B = imp_parts.shape
+    if baseline.shape[0] != B or logp.shape[0] != B:
+        raise _lib.AirHipError("nvil_parts: baseline / logp must hold B entries")
+    dev = imp_parts.device
+    out = torch.empty((4,), dtype=torch.float32, device=dev)
+    dlogp = torch.empty((B,), dtype=torch.float32, device=dev); dbase = torch.empty((B,), dtype=torch.float32, device=dev)
+    imp_sum = torch.empty((B,), dtype=torch.float32, device=dev) if want_sum else None
+    _lib.check(lib().air_nvil_parts(_p(imp_parts), n_parts, _p(imp_sum), _p(baseline), _p(logp), _p(out), _p(dlogp), _p(dbase),
+                                    B, _p(ema), _stream()), "air_nvil_parts")
+    return out, dlogp, dbase, imp_sum
+
+
+def imp_weight(rec_parts, step_weight, kl_n=None, nsp_weight=1.0, kl_row_a=None, kl_row_b=None, want_imp=True,
+               dpresence_inout=None, dkl_scale=0.0, want_rec=True):
+    """air_imp_weight: rec_parts[n_parts,B], step_weight[T,B] -> rec[B] | None, imp[B] | None;
+    dpresence_inout[T,B] (optional) += dkl_scale * (kl_row_a + kl_row_b) in place."""
+    rec_parts = _f32(rec_parts, "rec_parts", 2); step_weight = _f32(step_weight, "step_weight", 2)
+    n_parts, B = rec_parts.shape
+    T = step_weight.shape[0]
+    for t, nm in ((kl_row_a, "kl_row_a"), (kl_row_b, "kl_row_b"), (dpresence_inout, "dpresence_inout")):
+        _f32(t, nm, 2)
+    _tb((T, B), step_weight=step_weight, kl_n=_f32(kl_n, "kl_n", 1), kl_row_a=kl_row_a, kl_row_b=kl_row_b,
+        dpresence_inout=dpresence_inout)
+    if not want_imp and dpresence_inout is None:
+        raise _lib.AirHipError("imp_weight: one of imp / dpresence_inout is required")
+    dev = rec_parts.device
+    rec = torch.empty((B,), dtype=torch.float32, device=dev) if want_rec else None
+    imp = torch.empty((B,), dtype=torch.float32, device=dev) if want_imp else None
+    _lib.check(lib().air_imp_weight(_p(rec_parts), n_parts, _p(rec), _p(_f32(kl_n, "kl_n", 1)), float(nsp_weight), _p(kl_row_a),
+                                    _p(kl_row_b), _p(step_weight), T, B, _p(imp), _p(dpresence_inout), float(dkl_scale),
+                                    _stream()), "air_imp_weight")
+    return rec, imp
 
 
 def baseline_pack(img, what, where, presence, state_parts):
