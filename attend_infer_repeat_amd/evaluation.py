@@ -101,15 +101,16 @@ def make_prior_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, cou
     return fig
 
 
-def make_parse_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, obs=None):
-    """The deterministic parse of a batch (air.parse): one column per image; the input, the reconstruction with the attention box
-    of every object the parse found (rect_stn), and the owner map (which object a pixel belongs to; background = -1).  Saved as
-    parse_fig_<global_step>.png when a directory is given."""
+def make_parse_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, obs=None, particles=None, select="joint"):
+    """The parse of a batch (air.parse; particles=None: the deterministic parse at the mode, particles=K: the best of K posterior
+    particles under `select`): one column per image; the input, the reconstruction with the attention box of every object the parse
+    found (rect_stn), and the owner map (which object a pixel belongs to; background = -1).  Saved as parse_fig_<global_step>.png
+    when a directory is given."""
     import os.path as osp
     import matplotlib
     matplotlib.use('Agg')
     import matplotlib.pyplot as plt
-    out = air.parse(obs)
+    out = air.parse(obs) if particles is None else air.parse(obs, particles=particles, select=select)
     host = lambda t: t.detach().cpu().numpy()
     x, rec, owner = host(air.obs), host(out["reconstruction"]), host(out["owner"])
     presence, where, count_prob = host(out["presence"]), host(out["where"]), host(out["count_prob"])
@@ -135,48 +136,61 @@ def make_parse_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, obs
     return fig
 
 
-def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time=True):
+def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time=True, particles=None, select="joint"):
     """The deterministic parse (air.parse: the mode of q(n | x), latents at their posterior means) over `num_batches` batches from
     `data_fn`: map_num_step_acc (the count against the true one), the mean count_prob (q at the mode) and the mean number of
-    objects per image.  Prints / writes one line like make_expr_logger."""
+    objects per image.  particles=K: the best of K posterior particles under `select` instead (the count and count_prob are then
+    the kept particle's), and two more figures: best_particle_moved (the share of images whose kept particle is not particle 0)
+    and ess (the mean effective sample size); the record names K and the criterion.  Prints / writes one line like
+    make_expr_logger."""
     import torch
+    pk = {} if particles is None else dict(particles=int(particles), select=select)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
         n = max(int(n), 1)
         start = time.time()
-        tot = torch.zeros(3, dtype=torch.float64, device=air.obs.device)
+        tot = torch.zeros(5 if pk else 3, dtype=torch.float64, device=air.obs.device)
         images = 0
         for _ in range(n):
             obs, nums = data_fn()
-            out = air.parse(obs)
+            out = air.parse(obs, **pk)
             gt = nums.sum(0).reshape(-1).to(torch.int64)
             cnt = out["num_objects"].to(torch.int64)
-            tot += torch.stack([(cnt == gt).double().sum(), out["count_prob"].double().sum(), cnt.double().sum()])
+            sums = [(cnt == gt).double().sum(), out["count_prob"].double().sum(), cnt.double().sum()]
+            if pk:
+                sums += [(out["best_particle"] != 0).double().sum(), out["ess"].double().sum()]
+            tot += torch.stack(sums)
             images += int(cnt.numel())
         vals = (tot / images).tolist()
         acc = dict(map_num_step_acc=vals[0], count_prob=vals[1], num_objects=vals[2])
+        if pk:
+            acc.update(best_particle_moved=vals[3], ess=vals[4])
         t = time.time() - start
-        msg = 'Step {}, Data {} parse '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, v) for k, v in acc.items())
+        label = 'parse({}, {}) '.format(pk["particles"], select) if pk else 'parse '
+        msg = 'Step {}, Data {} '.format(itr, name) + label + ', '.join('{} = {:.4f}'.format(k, v) for k, v in acc.items())
         if measure_time:
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **acc)) + "\n"); writer.flush()
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **pk, **acc)) + "\n"); writer.flush()
         return acc
     return logger
 
 
-def make_parse_score_logger(air, data, num_batches, name, writer=None, thresholds=None, measure_time=True):
+def make_parse_score_logger(air, data, num_batches, name, writer=None, thresholds=None, measure_time=True, particles=None,
+                            select="joint"):
     """The deterministic parse scored against the generator's annotations on the device (air.score_parse, score.ParseScorer):
     `data` is an annotated dataset dict (imgs [N, H, W], boxes [N, G, 4], instances [N, H, W] int8 -- data.create_multi_mnist with
     return_annotations=True), walked in order from its start in `num_batches` batches of the model's size (fewer when the data
     runs out).  The sums and the predictions AP needs stay on the device; ParseScorer.summary() is the one readback.  Prints /
     writes one line like make_parse_logger: count accuracy, precision / recall / F1 / AP per box-IoU threshold and their mean AP,
-    foreground ARI, mean best overlap."""
+    foreground ARI, mean best overlap.  particles=K: the best of K posterior particles under `select` is scored instead; the line
+    also reports best_particle_moved and ess as make_parse_logger does, and the record names K and the criterion."""
     import torch
     G = int(data["boxes"].shape[1])
     kw = {} if thresholds is None else dict(thresholds=tuple(thresholds))
+    pk = {} if particles is None else dict(particles=int(particles), select=select)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -186,21 +200,29 @@ def make_parse_score_logger(air, data, num_batches, name, writer=None, threshold
             raise ValueError("the annotated dataset holds fewer images than one batch of %d" % B)
         start = time.time()
         dev = air.obs.device
-        scorer = air.parse_scorer(G, **kw)
+        scorer = air.parse_scorer(G, **kw, **pk)
         scorer.reset()
+        extra = torch.zeros(2, dtype=torch.float64, device=dev) if pk else None
         for i in range(n):
             sl = slice(i * B, (i + 1) * B)
             air.score_parse(torch.as_tensor(data["imgs"][sl], dtype=torch.float32).to(dev), torch.as_tensor(data["instances"][sl]),
-                            torch.as_tensor(data["boxes"][sl]), **kw)
+                            torch.as_tensor(data["boxes"][sl]), **kw, **pk)
+            if pk:
+                extra += torch.stack([(air.parsed["best_particle"] != 0).double().sum(), air.parsed["ess"].double().sum()])
         acc = scorer.summary()
-        t = time.time() - start
         shown = ["count_acc", "map", "ap@%.2f" % scorer.thresholds_host[0], "fg_ari", "mean_best_overlap", "matched_box_iou"]
-        msg = 'Step {}, Data {} parse score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
+        if pk:
+            moved, ess = (extra / (n * B)).tolist()
+            acc.update(best_particle_moved=moved, ess=ess)
+            shown += ["best_particle_moved", "ess"]
+        t = time.time() - start
+        label = 'parse score({}, {}) '.format(pk["particles"], select) if pk else 'parse score '
+        msg = 'Step {}, Data {} '.format(itr, name) + label + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **acc)) + "\n"); writer.flush()
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **pk, **acc)) + "\n"); writer.flush()
         return acc
     return logger
 

@@ -307,24 +307,54 @@ class AIRonMNIST(AIRModel):
             self._scene_parser = s
         return s
 
-    def parse(self, obs=None, num_objects=None):
-        """Deterministic scene parse on the device (parse.SceneParser: its own engine at the mode of the inference network -- the
-        training engine's parameters are read, nothing of it is written).  obs=None: the model's current batch.  Returns the
-        parser's dict of device tensors (SceneParser.parse lists them: num_objects, count_prob, presence, score, boxes, what, where,
-        the object table behind offsets, reconstruction, rec, owner, area); the next call overwrites them."""
+    def particle_parser(self, batch_size=None, particles=16, select="joint"):
+        """the ParticleParser behind parse(particles=K) (built and captured on first use, rebuilt when the size, K, the criterion or
+        the device changes; batch_size=None: the size it has, the batch size on first use)"""
+        eng = getattr(self, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("parse needs the fused engine: call train_step(...) with an engine-eligible "
+                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        from .particle_parse import ParticleParser
+        s = getattr(self, "_particle_parser", None)
+        n = int(batch_size) if batch_size is not None else (s.B if s is not None else eng.B)
+        if s is None or s.B != n or s.K != int(particles) or s.select != select or s.engine.device != eng.device:
+            if s is not None:
+                s.release_graphs()
+            s = ParticleParser(eng.cfg, n, int(particles), select=select, device=eng.device)
+            s.capture()
+            self._particle_parser = s
+        return s
+
+    def _parser_for(self, particles, select):
+        n = self.obs.shape[0]
+        return self.scene_parser(n) if particles is None else self.particle_parser(n, particles, select)
+
+    def parse(self, obs=None, num_objects=None, particles=None, select="joint"):
+        """Scene parse on the device.  particles=None: the deterministic parse (parse.SceneParser: its own engine at the mode of the
+        inference network); particles=K: K posterior particles per image and the best one under `select` ("joint": the largest
+        log p(x, z), "weight": the largest importance weight) kept (particle_parse.ParticleParser: its own engine at K * batch
+        rows, its own noise stream).  The training engine's parameters are read, nothing of it is written.  obs=None: the model's
+        current batch.  Returns the parser's dict of device tensors (SceneParser.parse lists them: num_objects, count_prob,
+        presence, score, boxes, what, where, the object table behind offsets, reconstruction, rec, owner, area; ParticleParser.parse
+        adds best_particle, the weights, the spread of `where`); the next call overwrites them.  num_objects (counts to use instead
+        of the model's) goes with the deterministic parse only."""
+        if particles is not None and num_objects is not None:
+            raise ValueError("parse: num_objects together with particles is not supported (conditioning the sampled chain on a "
+                             "count is out of scope); pass one of them")
         if obs is not None:
             self.obs = obs
-        s = self.scene_parser(self.obs.shape[0])
+        s = self._parser_for(particles, select)
         self._sync_engine_switches()
         s.load_from(self._engine)                            # every time: the weights move
-        self.parsed = s.parse(self.obs, num_objects)         # (the caller's stream is ordered after it)
+        # (the caller's stream is ordered after it)
+        self.parsed = s.parse(self.obs, num_objects) if particles is None else s.parse(self.obs)
         return self.parsed
 
-    def parse_scorer(self, max_gt_objects, thresholds=None):
-        """the ParseScorer behind score_parse, bound to the scene parser of the current batch size (built and captured on first use,
-        rebuilt when the parser, the number of ground-truth slots or the thresholds change)"""
+    def parse_scorer(self, max_gt_objects, thresholds=None, particles=None, select="joint"):
+        """the ParseScorer behind score_parse, bound to the parser of the current batch size that parse(particles=..., select=...)
+        uses (built and captured on first use, rebuilt when the parser, the number of ground-truth slots or the thresholds change)"""
         from .score import DEFAULT_THRESHOLDS, ParseScorer
-        parser = self.scene_parser(self.obs.shape[0])
+        parser = self._parser_for(particles, select)
         th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
         s = getattr(self, "_parse_scorer", None)
         if s is None or s.parser is not parser or s.G != int(max_gt_objects) or s.thresholds_host != th:
@@ -335,13 +365,14 @@ class AIRonMNIST(AIRModel):
             self._parse_scorer = s
         return s
 
-    def score_parse(self, obs, gt_instances, gt_boxes, gt_count=None, thresholds=None, accumulate=True):
-        """Parse `obs` (AIRonMNIST.parse), then score the parse against the ground truth on the device (score.ParseScorer.score lists
+    def score_parse(self, obs, gt_instances, gt_boxes, gt_count=None, thresholds=None, accumulate=True, particles=None,
+                    select="joint"):
+        """Parse `obs` (AIRonMNIST.parse, with `particles` / `select` as there), then score the parse against the ground truth on the device (score.ParseScorer.score lists
         the arguments and the returned device tensors).  gt_count=None: the number of rows of gt_boxes with width > 0.  The sums
         accumulate in `parse_scorer(...)`: its reset() starts a validation set, its summary() reads the figures back once."""
         import torch
-        self.parse(obs)
-        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds)
+        self.parse(obs, particles=particles, select=select)
+        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds, particles, select)
         self.parse_scores = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores
 

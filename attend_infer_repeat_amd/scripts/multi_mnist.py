@@ -80,6 +80,13 @@ def main(argv=None):
                          "device (AIRonMNIST.score_parse, evaluation.make_parse_score_logger): count accuracy, precision / recall / F1 / AP "
                          "over box-IoU thresholds, foreground ARI and mean best overlap of the instance masks.  Needs annotated data: "
                          "--glyphs, or pickles written by create_dataset.py --annotations")
+    ap.add_argument("--parse-particles", type=int, default=0, metavar="K",
+                    help="K > 0: --parse-eval and --parse-score parse with K posterior particles per image and keep the best one "
+                         "(AIRonMNIST.parse(particles=K), particle_parse.ParticleParser) instead of the parse at the mode; the log record "
+                         "names K and the criterion; 0 = the deterministic parse")
+    ap.add_argument("--parse-select", default="joint", choices=("joint", "weight"),
+                    help="with --parse-particles: the particle kept per image -- 'joint' = the largest log p(x, z), 'weight' = the largest "
+                         "importance weight log p(x, z) - log q(z | x)")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -188,20 +195,21 @@ def main(argv=None):
                 make_prior_fig(air, logdir, train_itr)
             return out
 
+    parse_kw = dict(particles=args.parse_particles, select=args.parse_select) if args.parse_particles > 0 else {}
     if args.parse_eval:
         before_parse_log = log
-        parse_log = make_parse_logger(air, valid_feed, args.eval_batches, 'test', writer)
+        parse_log = make_parse_logger(air, valid_feed, args.eval_batches, 'test', writer, **parse_kw)
 
         def log(train_itr):                               # noqa: F811
             out = before_parse_log(train_itr)
             parse_log(train_itr)
             if args.figures:
-                make_parse_fig(air, logdir, train_itr)
+                make_parse_fig(air, logdir, train_itr, **parse_kw)
             return out
 
     if args.parse_score:
         before_score_log = log
-        score_log = make_parse_score_logger(air, valid_data, args.eval_batches, 'test', writer)
+        score_log = make_parse_score_logger(air, valid_data, args.eval_batches, 'test', writer, **parse_kw)
 
         def log(train_itr):                               # noqa: F811
             out = before_score_log(train_itr)

@@ -589,6 +589,32 @@ AIR_ENGINE_API int air_parse_render(const float *glimpse, const float *where, co
                      float std, float mask_threshold, int T, int R, int H, int W, int h, int w, int n_bands,
                      float *reconstruction, float *rec_parts, signed char *owner, int *area, float *layers, void *stream);
 
+/* ---- best-of-K scene parsing: read-outs behind a K-tiled forward pass (R = K * B rows, row r = b * K + k) and air_iw_logweight.
+ * T <= 32; K arbitrary.  No atomics, one fixed summation order: the same bits run to run.
+ * air_iw_logposterior: per row, with n = the number of leading ones of presence[T,R],
+ *   log_q[r] = logp[r] + sum_{t<n} [ sum_a log N(what_ta | what_loc, what_scale) + sum_j log N(where_tj | where_loc, where_scale) ]
+ *   with the -1/2 log 2 pi of every term; fp32 terms in the lane layout of air_iw_logweight, the closing add in float64.  No clamps:
+ *   a zero scale gives +-inf / NaN.  where / where_loc / where_scale 16-byte aligned (AIR_E_ALIGN).
+ * air_particle_select: per image b the scores s_k = log_w[b*K+k] (criterion 0, "weight"; log_q may be NULL) or log_w + log_q
+ *   (criterion 1, "joint" = log p(x, z_k)), formed in float64 from the fp32 values.  k* = the SMALLEST k attaining max_k s_k over the
+ *   non-NaN scores (-inf is an ordinary value); every score NaN: k* = 0 and degenerate[b] = 1 (else 0), best_score[b] = NaN.
+ *   best_particle[b] = k*, best_score[b] = (float) s_k*, num_objects[b] = num_steps[b*K + k*].  A second kernel copies, bit for bit,
+ *   row t*R + b*K + k* of where[T,R,4], what[T,R,A], presence_prob[T,R], glimpse[T,R,G] to row t*B + b of the *_sel buffers (16-byte
+ *   vectors where A resp. G is a multiple of 4 and the buffers are 16-byte aligned, 4-byte words otherwise).
+ * air_particle_spread: per image with m = max_k log_w, w_k = exp(log_w_k - m) in float64, and per step t with S_t = {k : num_steps_k > t},
+ *   W = sum_{S_t} w_k:  where_mean[t,b,:] = sum_{S_t} w_k where[t,b*K+k,:] / W;  where_std = sqrt(max(0, sum_{S_t} w_k (where - mean)^2
+ *   / W)) (two passes);  presence_iw[t,b] = W / sum_k w_k.  W == 0: mean and std are NaN, presence_iw 0.  where / where_mean /
+ *   where_std 16-byte aligned (AIR_E_ALIGN).                                                                                      */
+AIR_ENGINE_API int air_iw_logposterior(const float *what, const float *what_loc, const float *what_scale, const float *where,
+                        const float *where_loc, const float *where_scale, const float *presence, const float *logp,
+                        int T, int R, int K, int A, float *log_q, void *stream);
+AIR_ENGINE_API int air_particle_select(const float *log_w, const float *log_q, const int *num_steps, const float *where, const float *what,
+                        const float *presence_prob, const float *glimpse, int T, int R, int K, int A, int G, int criterion,
+                        int *best_particle, float *best_score, int *num_objects, int *degenerate, float *where_sel,
+                        float *what_sel, float *presence_prob_sel, float *glimpse_sel, void *stream);
+AIR_ENGINE_API int air_particle_spread(const float *log_w, const int *num_steps, const float *where, int T, int R, int K,
+                        float *where_mean, float *where_std, float *presence_iw, void *stream);
+
 /* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
  * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
  * (AIR_E_SHAPE otherwise, and when R*H*W or R*(T+1)*(G+1) passes int32).  No floating-point atomics; float64 with contraction off
