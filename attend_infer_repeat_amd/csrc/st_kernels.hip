@@ -692,9 +692,10 @@ extern "C" int air_attend_fwd(const float *tr_h, const float *tr_w, const float 
     // image once for the T reads (measured at batch 1024: 20 -> see DESIGN.md)
     g.img_major = ((long)T * B > 2048 && T > 1) ? 1 : 0;
     // image-major: the read role in the lean kernel's form when its outputs come in 16-byte groups (AIR_ATTEND_LEAN=0: the per-pixel form, A/B)
+    // (W >= 4 as in air_st_read_fwd: the bordered staging steps over ONE row end per 16-byte group; a one-pixel-wide image crosses three)
     const size_t lds_lean = read_lean_bytes(H, W, h, w, T) + 16 * (size_t)T;
     const char *env_lean = getenv("AIR_ATTEND_LEAN");
-    g.lean = (g.img_major && w % 4 == 0 && air_aligned16(glimpse) && lds_lean <= ST_MAX_LDS && !(env_lean && atoi(env_lean) == 0)) ? 1 : 0;
+    g.lean = (g.img_major && w % 4 == 0 && W >= 4 && air_aligned16(glimpse) && lds_lean <= ST_MAX_LDS && !(env_lean && atoi(env_lean) == 0)) ? 1 : 0;
     if (g.lean && lds_lean > lds) lds = lds_lean;
     const int grid = (g.img_major ? B : T * B) + air_cdiv(B, 64);
 #define AIR_ATTEND_FWD_LAUNCH(MT_, NT_, EX_)                                                                         \

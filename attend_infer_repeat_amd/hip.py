@@ -639,6 +639,158 @@ def baseline_pack(img, what, where, presence, state_parts):
     return out
 
 
+# ---- the fused launches around the glimpse read, the `what` head ---------------------------------------------------
+def _nan(*shape, device):
+    """an output buffer filled with NaN: an element the launch leaves out shows up in the caller's comparison"""
+    return torch.full(shape, float("nan"), dtype=torch.float32, device=device)
+
+
+def _mat(t, name, cols=None):
+    """a 2-D float32 CUDA tensor with unit inner stride (a row view of a wider buffer is fine) -> its leading dimension"""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1):
+        raise _lib.AirHipError(f"{name}: expected a 2-D float32 CUDA tensor with unit inner stride")
+    if cols is not None and t.shape[1] != cols:
+        raise _lib.AirHipError(f"{name}: expected {cols} columns, got shape {tuple(t.shape)}")
+    return max(t.stride(0), t.shape[1])                         # (a single row keeps the stride of the buffer it was cut from)
+
+
+def attend_fwd(tr_h, tr_w, tr_b, st_h, st_w, st_b, eps, raw_offset, prior4, u, step_bias, explore_eps, prior_f64, img, crop_size,
+               precision=0, guard_eps=0.0):
+    """air_attend_fwd: tr_h[T*B, tr_k], tr_w[tr_k, 8], tr_b[8], st_h[T*B, st_k], st_w[st_k], st_b[1], eps[T*B, 4], u[T, B] | None,
+    img[B, H, W] -> (pre[T*B, 8], logit[T, B]), (loc, scale, where [T*B, 4], kl_row[T*B]),
+    (presence_prob, presence, q[B, T+1], kl_per_sample[B], logp[B], step_weight[T, B]), glimpse[T*B, h, w]"""
+    tr_h = _f32(tr_h, "tr_h", 2); tr_w = _f32(tr_w, "tr_w", 2); tr_b = _f32(tr_b, "tr_b", 1)
+    st_h = _f32(st_h, "st_h", 2); st_w = _f32(st_w, "st_w"); st_b = _f32(st_b, "st_b", 1)
+    eps = _f32(eps, "eps", 2); img = _f32(img, "img", 3); u = _f32(u, "u", 2)
+    B, H, W = img.shape
+    M, tr_k = tr_h.shape
+    st_k = st_h.shape[1]
+    T = M // B
+    if T * B != M or st_h.shape[0] != M or tuple(eps.shape) != (M, 4) or tuple(tr_w.shape) != (tr_k, 8) or tr_b.numel() != 8 \
+            or st_w.numel() != st_k or st_b.numel() != 1:
+        raise _lib.AirHipError(f"attend_fwd: tr_h {tuple(tr_h.shape)}, tr_w {tuple(tr_w.shape)}, st_h {tuple(st_h.shape)}, st_w "
+                               f"{tuple(st_w.shape)}, eps {tuple(eps.shape)} for {B} images")
+    _tb((T, B), u=u)
+    prior_f64 = _prior_f64(prior_f64, T)
+    h, w = int(crop_size[0]), int(crop_size[1])
+    dev = img.device
+    pre = _nan(M, 8, device=dev); logit = _nan(T, B, device=dev)
+    loc, scale, where = (_nan(M, 4, device=dev) for _ in range(3))
+    kl_row = _nan(M, device=dev)
+    prob, pres, step_w = (_nan(T, B, device=dev) for _ in range(3))
+    q = _nan(B, T + 1, device=dev); kl = _nan(B, device=dev); logp = _nan(B, device=dev)
+    glimpse = _nan(M, h, w, device=dev)
+    a, b, c, d = (float(v) for v in prior4)
+    xe = -1.0 if explore_eps is None else float(explore_eps)
+    _lib.check(lib().air_attend_fwd(_p(tr_h), _p(tr_w), _p(tr_b), tr_k, _p(st_h), _p(st_w), _p(st_b), st_k, _p(pre), _p(logit), _p(eps),
+                                    float(raw_offset), a, b, c, d, _p(loc), _p(scale), _p(where), _p(kl_row), _p(u), float(step_bias), xe,
+                                    _p(prior_f64), _p(prob), _p(pres), _p(q), _p(kl), _p(logp), _p(step_w), _p(img), _p(glimpse),
+                                    T, B, H, W, h, w, int(precision), float(guard_eps), _stream()), "air_attend_fwd")
+    return (pre, logit), (loc, scale, where, kl_row), (prob, pres, q, kl, logp, step_w), glimpse
+
+
+def attend_bwd(img, where, dglimpse, pre, eps, raw_offset, prior4, loc, scale, dwhere_w, dkl_row, dkl_scale, presence_prob, presence,
+               prior_f64, kl_scale, kl_row_a, kl_row_b, w_scale, dlogp, dpresence, logit, step_bias, explore_eps, guard_eps=0.0,
+               tr_w=None, tr_y=None, tr_dx=None, st_w=None, st_y=None, st_dx=None, precision=0):
+    """air_attend_bwd -> dwhere_r[T*B, 4], dpre[T*B, 8], dlogit[T, B].  dwhere_w[slabs, T*B, 4] (1..4 slabs); dkl_row, kl_row_a,
+    kl_row_b, dlogp, dpresence may be None.
+    With tr_w[tr_k, 8] and st_w[st_k] given: air_attend_bwd_dx, which also returns tr_dx[T*B, tr_k] and st_dx[T*B, st_k].  tr_y / st_y
+    (or None) and tr_dx / st_dx (or None: allocated here) may be row views of wider buffers, all of one leading dimension per layer."""
+    img = _f32(img, "img", 3); where = _f32(where, "where", 2); dglimpse = _f32(dglimpse, "dglimpse", 3)
+    pre = _f32(pre, "pre", 2); eps = _f32(eps, "eps", 2); loc = _f32(loc, "loc", 2); scale = _f32(scale, "scale", 2)
+    dwhere_w = _f32(dwhere_w, "dwhere_w", 3); dkl_row = _f32(dkl_row, "dkl_row", 1)
+    presence_prob = _f32(presence_prob, "presence_prob", 2); logit = _f32(logit, "logit", 2)
+    B, H, W = img.shape
+    M, h, w = dglimpse.shape
+    T = presence_prob.shape[0]
+    if T * B != M or presence_prob.shape[1] != B or tuple(pre.shape) != (M, 8) or tuple(dwhere_w.shape[1:]) != (M, 4) \
+            or (dkl_row is not None and dkl_row.shape[0] != M):
+        raise _lib.AirHipError(f"attend_bwd: dglimpse {tuple(dglimpse.shape)}, pre {tuple(pre.shape)}, dwhere_w {tuple(dwhere_w.shape)}, "
+                               f"presence_prob {tuple(presence_prob.shape)} for {B} images")
+    _tb((M, 4), where=where, eps=eps, loc=loc, scale=scale)
+    _tb((T, B), presence=_f32(presence, "presence", 2), kl_row_a=_f32(kl_row_a, "kl_row_a", 2), kl_row_b=_f32(kl_row_b, "kl_row_b", 2),
+        dlogp=_f32(dlogp, "dlogp", 1), dpresence=_f32(dpresence, "dpresence", 2), logit=logit)
+    prior_f64 = _prior_f64(prior_f64, T)
+    dev = img.device
+    dwhere_r = _nan(M, 4, device=dev); dpre = _nan(M, 8, device=dev); dlogit = _nan(T, B, device=dev)
+    a, b, c, d = (float(v) for v in prior4)
+    xe = -1.0 if explore_eps is None else float(explore_eps)
+    head = (_p(img), _p(where), _p(dglimpse), _p(dwhere_r), _p(pre), _p(eps), float(raw_offset), a, b, c, d, _p(loc), _p(scale),
+            _p(dwhere_w), int(dwhere_w.shape[0]), _p(dkl_row), float(dkl_scale), _p(dpre), _p(presence_prob), _p(presence), _p(prior_f64),
+            float(kl_scale), _p(kl_row_a), _p(kl_row_b), float(w_scale), _p(dlogp), _p(dpresence), _p(logit), float(step_bias), xe,
+            _p(dlogit), T, B, H, W, h, w)
+    if tr_w is None and st_w is None:
+        _lib.check(lib().air_attend_bwd(*head, float(guard_eps), _stream()), "air_attend_bwd")
+        return dwhere_r, dpre, dlogit
+    tr_w = _f32(tr_w, "tr_w", 2); st_w = _f32(st_w, "st_w")
+    tr_k, st_k = tr_w.shape[0], st_w.numel()
+    if tr_dx is None:
+        tr_dx = _nan(M, tr_k, device=dev)
+    if st_dx is None:
+        st_dx = _nan(M, st_k, device=dev)
+    tr_ld, st_ld = _mat(tr_dx, "tr_dx", tr_k), _mat(st_dx, "st_dx", st_k)
+    for y, ld, k, nm in ((tr_y, tr_ld, tr_k, "tr_y"), (st_y, st_ld, st_k, "st_y")):
+        if y is not None and (_mat(y, nm, k) != ld or y.shape[0] != M):
+            raise _lib.AirHipError(f"attend_bwd: {nm} must hold {M} rows of the leading dimension of its dx ({ld})")
+    if tr_dx.shape[0] != M or st_dx.shape[0] != M or tr_w.shape[1] != 8:
+        raise _lib.AirHipError(f"attend_bwd: tr_dx {tuple(tr_dx.shape)}, st_dx {tuple(st_dx.shape)}, tr_w {tuple(tr_w.shape)}")
+    _lib.check(lib().air_attend_bwd_dx(*head, _p(tr_w), _p(tr_y), _p(tr_dx), tr_k, tr_ld, _p(st_w), _p(st_y), _p(st_dx), st_k, st_ld,
+                                       int(precision), float(guard_eps), _stream()), "air_attend_bwd_dx")
+    return dwhere_r, dpre, dlogit, tr_dx, st_dx
+
+
+def _what_pack_args(where, presence, state_parts, T, B):
+    where = _f32(where, "where", 3); presence = _f32(presence, "presence")
+    parts = [_f32(s, "state", 2) for s in state_parts]
+    if len(parts) > 2 or tuple(where.shape) != (T, B, 4) or presence.numel() != T * B or any(s.shape[0] != B for s in parts):
+        raise _lib.AirHipError(f"what head: where {tuple(where.shape)}, presence {tuple(presence.shape)}, {len(parts)} state parts")
+    s0 = parts[0] if len(parts) > 0 else None
+    s1 = parts[1] if len(parts) > 1 else None
+    return where, presence, s0, s1, (s0.shape[1] if s0 is not None else 0), (s1.shape[1] if s1 is not None else 0)
+
+
+def what_head_fwd(x, w, b, eps, raw_offset, prior2, where, presence, state_parts, T, precision=0, guard_eps=0.0):
+    """air_what_head_fwd: x[T*B, K] (a row view is fine), w[K, 2A], b[2A], eps[T*B, A], where[T, B, 4], presence[T, B], up to two
+    state parts [B, S] -> q[T*B, 2A], loc, scale, sample [T*B, A], kl_parts[ceil(A / 8), T*B], pack_out[B, T*A + 5T + S0 + S1]"""
+    ldx = _mat(x, "x")
+    w = _f32(w, "w", 2); b = _f32(b, "b", 1); eps = _f32(eps, "eps", 2)
+    M, K = x.shape
+    A = w.shape[1] // 2
+    B = M // int(T)
+    if B * T != M or tuple(w.shape) != (K, 2 * A) or b.numel() != 2 * A or tuple(eps.shape) != (M, A):
+        raise _lib.AirHipError(f"what_head_fwd: x {tuple(x.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}, eps {tuple(eps.shape)}, T {T}")
+    where, presence, s0, s1, S0, S1 = _what_pack_args(where, presence, state_parts, T, B)
+    dev = x.device
+    q = _nan(M, 2 * A, device=dev)
+    loc, scale, sample = (_nan(M, A, device=dev) for _ in range(3))
+    kl_parts = _nan(int(lib().air_what_head_parts(A)), M, device=dev)
+    pack = _nan(B, T * A + 5 * T + S0 + S1, device=dev)
+    _lib.check(lib().air_what_head_fwd(_p(x), ldx, K, _p(w), _p(b), _p(eps), float(raw_offset), float(prior2[0]), float(prior2[1]), _p(q),
+                                       _p(loc), _p(scale), _p(sample), _p(kl_parts), A, _p(where), _p(presence), _p(s0), _p(s1), _p(pack),
+                                       int(T), B, S0, S1, float(guard_eps), int(precision), _stream()), "air_what_head_fwd")
+    return q, loc, scale, sample, kl_parts, pack
+
+
+def what_sample_pack(pre, eps, raw_offset, prior2, where, presence, state_parts, T, guard_eps=0.0):
+    """air_what_sample_pack: pre[T*B, >= 2A] (row stride allowed), eps[T*B, A] -> loc, scale, sample [T*B, A], kl_row[T*B],
+    pack_out[B, T*A + 5T + S0 + S1]"""
+    ld = _mat(pre, "pre")
+    eps = _f32(eps, "eps", 2)
+    M, A = eps.shape
+    B = M // int(T)
+    if B * T != M or pre.shape[0] != M or pre.shape[1] < 2 * A:
+        raise _lib.AirHipError(f"what_sample_pack: pre {tuple(pre.shape)}, eps {tuple(eps.shape)}, T {T}")
+    where, presence, s0, s1, S0, S1 = _what_pack_args(where, presence, state_parts, T, B)
+    dev = pre.device
+    loc, scale, sample = (_nan(M, A, device=dev) for _ in range(3))
+    kl_row = _nan(M, device=dev)
+    pack = _nan(B, T * A + 5 * T + S0 + S1, device=dev)
+    _lib.check(lib().air_what_sample_pack(_p(pre), ld, _p(eps), float(raw_offset), float(prior2[0]), float(prior2[1]), _p(loc), _p(scale),
+                                          _p(sample), _p(kl_row), A, _p(where), _p(presence), _p(s0), _p(s1), _p(pack), int(T), B, S0, S1,
+                                          float(guard_eps), _stream()), "air_what_sample_pack")
+    return loc, scale, sample, kl_row, pack
+
+
 # ---- optimiser / noise / utils -------------------------------------------------------------------------------------
 def rmsprop_centered_(p, g, ms, mg, mom, lr_dev, lr_mult=1.0, decay=0.9, momentum=0.9, eps=1e-10, grad_scale=1.0,
                       centered=True):

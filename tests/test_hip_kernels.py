@@ -9,6 +9,8 @@ import torch
 from oracle import air_oracle as O
 from oracle import st_loops as C
 
+from attend_cases import rand_where
+
 pytestmark = pytest.mark.gpu
 
 
@@ -21,12 +23,6 @@ def hip(gpu_device):
 
 def g(x, dtype=torch.float32):
     return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype).cuda()
-
-
-def rand_where(B, rng, wide=False):
-    sx = rng.uniform(0.2, 1.4, B) * (rng.choice([-1, 1], B) if wide else 1)
-    sy = rng.uniform(0.2, 1.4, B)
-    return np.stack([sx, rng.uniform(-0.8, 0.8, B), sy, rng.uniform(-0.8, 0.8, B)], 1).astype(np.float32)
 
 
 def assert_close(a, b, rtol, atol, what=""):

@@ -16,9 +16,10 @@ import torch
 
 from oracle import air_oracle as O
 
-pytestmark = pytest.mark.gpu
+from attend_cases import (BWD_VARIANTS, KL_SCALE, NSP, W_SCALE, _check_fused_forward, _margin_u, _objective64, _posterior_refs,
+                          _presence_prob64, assert_bits, assert_close, g, print_worst)
 
-WORST = {}
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -31,37 +32,7 @@ def hip(gpu_device):
 @pytest.fixture(scope="module", autouse=True)
 def report_worst_ratios():
     yield
-    for grp in sorted(WORST):
-        ratio, what = WORST[grp]
-        print(f"\n[objective kernels] group {grp}: worst error / tolerance = {ratio:.3g} ({what})")
-
-
-def g(x, dtype=torch.float32):
-    if x is None:
-        return None
-    return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype).cuda()
-
-
-def assert_close(a, b, rtol, atol, what="", group=None):
-    """err <= atol + rtol * |b| for every element (the semantics of tests/test_hip_kernels.py), shapes equal"""
-    a = a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, np.float64)
-    b = b.detach().cpu().double().numpy() if torch.is_tensor(b) else np.asarray(b, np.float64)
-    assert a.shape == b.shape, f"{what}: shape {a.shape} against {b.shape}"
-    err = np.abs(a - b)
-    tol = atol + rtol * np.abs(b)
-    if group is not None and err.size:
-        ratio = np.where(err > 0, err / np.maximum(tol, 1e-300), 0.0)
-        worst = float(np.nanmax(ratio)) if np.isfinite(ratio).any() else float("inf")
-        if group not in WORST or worst > WORST[group][0]:
-            WORST[group] = (worst, what)
-    assert (err <= tol).all(), f"{what}: max err {err.max():.3e} (tol {tol.flat[err.argmax()]:.3e}) at {np.unravel_index(err.argmax(), err.shape)}"
-
-
-def assert_bits(a, b, what=""):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    assert a.shape == b.shape and a.dtype == b.dtype, f"{what}: {tuple(a.shape)} {a.dtype} against {tuple(b.shape)} {b.dtype}"
-    same = a.view(torch.int32) == b.view(torch.int32) if a.dtype == torch.float32 else a == b
-    assert bool(same.all()), f"{what}: {int((~same).sum())} of {same.numel()} elements differ in their bits"
+    print_worst("objective kernels", "ABC")
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -69,29 +40,6 @@ def assert_bits(a, b, what=""):
 # ---------------------------------------------------------------------------------------------------------------
 # every T at B = 130 (three blocks of the fused form, one of the generic), every B at the T == MT edge (8), the first <32> size (9) and 32
 TB_CASES = [(T, 130) for T in (1, 5, 8, 9, 16, 32)] + [(T, B) for T in (8, 9, 32) for B in (1, 63, 65)]
-NSP = 0.3                                                                       # success probability of the geometric prior
-
-
-def _rev_cumsum(q):
-    """step weights w[t, b] = sum_{n > t} q[b, n] from q[B, T+1]"""
-    return torch.flip(torch.cumsum(torch.flip(q[:, 1:].t(), [0]), 0), [0])
-
-
-def _posterior_refs(prob32, count, prior):
-    """the oracle path of test_numsteps_fwd_bwd: the f32 posterior, re-cast to f64 inside tabular_kl like the reference"""
-    q = O.bernoulli_to_modified_geometric(prob32.t())
-    return q, O.tabular_kl(q, prior[None]).sum(1), _rev_cumsum(q), O.num_steps_log_prob(q, count)
-
-
-def _objective64(p64, count, prior, kl_scale, dw, dlogp):
-    """kl_scale * KL + sum(w * dw) + sum(dlogp * logp) in float64 (terms given as None are left out)"""
-    q64 = O.bernoulli_to_modified_geometric(p64.t())
-    L = kl_scale * O.tabular_kl(q64, prior[None]).sum()
-    if dw is not None:
-        L = L + (_rev_cumsum(q64) * dw.double()).sum()
-    if dlogp is not None:
-        L = L + (O.num_steps_log_prob(q64, count) * dlogp.double()).sum()
-    return L
 
 
 def _assert_clamp_column(p64, pres, T, clamped, q32=None):
@@ -136,21 +84,6 @@ def test_numsteps_generic_up_to_32_steps(hip, T, B):
     assert_close(dprob, c["dprob"], 2e-4, 2e-4, f"numsteps_bwd T={T} B={B} dprob", "A")
 
 
-def _presence_prob64(l64, step_bias, eps):
-    p = torch.sigmoid(l64 + step_bias)
-    return p if eps is None else eps / 2 + (1 - eps) * p
-
-
-def _margin_u(u, p64):
-    """u with every element at least 1e-5 away from the float64 p (the kernel's p is within 1e-6 p + 1e-7 of it), so that
-    (u < p) is the same in the kernel and in float64 and the Bernoulli chain can be compared exactly"""
-    u64 = u.double()
-    near = (u64 - p64).abs() < 1e-5
-    u = torch.where(near, torch.where(u64 >= p64, p64 + 2e-5, p64 - 2e-5), u64).float()
-    assert bool(((u.double() - p64).abs() >= 1e-5).all())
-    return u
-
-
 @functools.lru_cache(maxsize=None)
 def _fused_case(T, B, step_bias, eps, continuous=False):
     """logits (randn * 3) with, for B > 1 on the discrete path, column 0 at p ~ 1 - 1e-4 and column 1 at p ~ 1e-4 with its presence
@@ -183,22 +116,6 @@ def _fused_case(T, B, step_bias, eps, continuous=False):
     return dict(logit=logit, u=u, p64=p64, pres=pres, count=pres.sum(0))
 
 
-def _check_fused_forward(out, c, prior, tag):
-    """prob against the float64 chain; presence exactly; q / KL / w / log q(n*) against the oracle's f32-posterior path evaluated on
-    the prob the kernel wrote.  (The posterior is ill-conditioned in p near 1: q(n) carries (1 - p_n), so one float32 ulp of p at
-    p = 1 - 1e-4 moves q(n) by 6e-8, six times its atol.  Feeding the oracle the written prob keeps the tolerances of the generic
-    kernel's test meaningful, and still fails if the posterior was formed from any other p than the one written.)"""
-    prob, pres, q, kl, logp, w = out
-    assert_close(prob, c["p64"], 1e-6, 1e-7, tag + "prob", "A")
-    if c["u"] is None:
-        assert_bits(pres, prob, tag + "presence = prob")
-    else:
-        assert torch.equal(pres.cpu().double(), c["pres"]), tag + "presence"
-    rq, rkl, rw, rlogp = _posterior_refs(prob.cpu(), c["count"], prior)
-    assert_close(q, rq, 1e-6, 1e-8, tag + "q", "A"); assert_close(kl, rkl, 1e-5, 1e-6, tag + "kl", "A")
-    assert_close(w, rw, 1e-6, 1e-7, tag + "w", "A"); assert_close(logp, rlogp, 1e-5, 1e-6, tag + "logp", "A")
-
-
 @pytest.mark.parametrize("explore_eps", [1e-3, None])
 @pytest.mark.parametrize("step_bias", [0.0, 0.75])
 @pytest.mark.parametrize("T,B", TB_CASES)
@@ -216,19 +133,6 @@ def test_presence_numsteps_fwd_continuous_steps(hip, T, B, step_bias, explore_ep
     prior = O.geometric_prior(NSP, T)
     out = hip.presence_numsteps_fwd(c["logit"].cuda(), None, step_bias, explore_eps, prior.cuda())
     _check_fused_forward(out, c, prior, f"presence_numsteps_fwd (u = None) T={T} B={B} bias={step_bias} eps={explore_eps} ")
-
-
-# name, continuous, kl_a, kl_b, dlogp, dpresence, step_bias, explore_eps
-BWD_VARIANTS = [
-    ("discrete, both kl rows, dlogp", False, True, True, True, False, 0.75, 1e-3),
-    ("discrete, kl_b only, no dlogp, no eps", False, False, True, False, False, 0.0, None),
-    ("discrete, kl_a only, dlogp", False, True, False, True, False, 0.0, 1e-3),
-    ("discrete, no kl rows, dlogp, no eps", False, False, False, True, False, 0.75, None),
-    ("continuous, both kl rows, dlogp, dpresence", True, True, True, True, True, 0.75, 1e-3),
-    ("continuous, dpresence alone, no eps", True, False, False, False, True, 0.0, None),
-    ("continuous, both kl rows, dlogp, no dpresence", True, True, True, True, False, 0.0, None),
-]
-KL_SCALE, W_SCALE = 0.37, 1.0 / 64
 
 
 @functools.lru_cache(maxsize=None)
