@@ -193,6 +193,9 @@ SIGNATURES = {
     "air_iw_logposterior": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "air_particle_select": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P]),
     "air_particle_spread": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P]),
+    "air_refine_step": (c_int, [P, P, P, P, P, c_int, P, P, P, c_float, c_float, c_float, c_float, c_float, c_float, P, P, P, P,
+                                c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_int, c_int,
+                                c_int, c_int, P, P, P, P, P, P, P]),
     "air_score_contingency": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "air_score_match": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "air_score_reduce": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, P]),

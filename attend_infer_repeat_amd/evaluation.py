@@ -136,61 +136,90 @@ def make_parse_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, obs
     return fig
 
 
-def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time=True, particles=None, select="joint"):
+def _refine_kw(refine, refine_lr):
+    if refine is None:
+        return {}
+    rk = dict(refine=int(refine))
+    if refine_lr is not None:
+        rk["refine_lr"] = tuple(float(v) for v in refine_lr)
+    return rk
+
+
+def _refine_sums(out):
+    """[sum of the objective gain, number of images whose best iterate is not the start parse] (an image whose gain is NaN or
+    infinite adds 0; the callers divide by the number of all images)"""
+    import torch
+    gain = torch.nan_to_num(out["objective"] - out["objective_start"].double(), nan=0.0, posinf=0.0, neginf=0.0)
+    return [gain.sum(), (out["best_iter"] > 0).double().sum()]
+
+
+def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time=True, particles=None, select="joint", refine=None,
+                      refine_lr=None):
     """The deterministic parse (air.parse: the mode of q(n | x), latents at their posterior means) over `num_batches` batches from
     `data_fn`: map_num_step_acc (the count against the true one), the mean count_prob (q at the mode) and the mean number of
     objects per image.  particles=K: the best of K posterior particles under `select` instead (the count and count_prob are then
     the kept particle's), and two more figures: best_particle_moved (the share of images whose kept particle is not particle 0)
-    and ess (the mean effective sample size); the record names K and the criterion.  Prints / writes one line like
-    make_expr_logger."""
+    and ess (the mean effective sample size); the record names K and the criterion.  refine=N: that parse refined by N gradient
+    iterations (air.parse(refine=N, refine_lr=...)), and two more figures: objective_gain (the mean of objective - objective_start
+    over ALL images, an image whose gain is not finite counting as 0) and refine_moved (the share of images whose best iterate is not the start parse); the
+    record names N.  Prints / writes one line like make_expr_logger."""
     import torch
     pk = {} if particles is None else dict(particles=int(particles), select=select)
+    rk = _refine_kw(refine, refine_lr)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
         n = max(int(n), 1)
         start = time.time()
-        tot = torch.zeros(5 if pk else 3, dtype=torch.float64, device=air.obs.device)
+        tot = torch.zeros(3 + (2 if pk else 0) + (2 if rk else 0), dtype=torch.float64, device=air.obs.device)
         images = 0
         for _ in range(n):
             obs, nums = data_fn()
-            out = air.parse(obs, **pk)
+            out = air.parse(obs, **pk, **rk)
             gt = nums.sum(0).reshape(-1).to(torch.int64)
             cnt = out["num_objects"].to(torch.int64)
             sums = [(cnt == gt).double().sum(), out["count_prob"].double().sum(), cnt.double().sum()]
             if pk:
                 sums += [(out["best_particle"] != 0).double().sum(), out["ess"].double().sum()]
+            if rk:
+                sums += _refine_sums(out)
             tot += torch.stack(sums)
             images += int(cnt.numel())
         vals = (tot / images).tolist()
         acc = dict(map_num_step_acc=vals[0], count_prob=vals[1], num_objects=vals[2])
         if pk:
             acc.update(best_particle_moved=vals[3], ess=vals[4])
+        if rk:
+            acc.update(objective_gain=vals[-2], refine_moved=vals[-1])
         t = time.time() - start
         label = 'parse({}, {}) '.format(pk["particles"], select) if pk else 'parse '
+        if rk:
+            label = label[:-1] + '+refine({}) '.format(rk["refine"])
         msg = 'Step {}, Data {} '.format(itr, name) + label + ', '.join('{} = {:.4f}'.format(k, v) for k, v in acc.items())
         if measure_time:
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **pk, **acc)) + "\n"); writer.flush()
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **pk, **rk, **acc)) + "\n"); writer.flush()
         return acc
     return logger
 
 
 def make_parse_score_logger(air, data, num_batches, name, writer=None, thresholds=None, measure_time=True, particles=None,
-                            select="joint"):
+                            select="joint", refine=None, refine_lr=None):
     """The deterministic parse scored against the generator's annotations on the device (air.score_parse, score.ParseScorer):
     `data` is an annotated dataset dict (imgs [N, H, W], boxes [N, G, 4], instances [N, H, W] int8 -- data.create_multi_mnist with
     return_annotations=True), walked in order from its start in `num_batches` batches of the model's size (fewer when the data
     runs out).  The sums and the predictions AP needs stay on the device; ParseScorer.summary() is the one readback.  Prints /
     writes one line like make_parse_logger: count accuracy, precision / recall / F1 / AP per box-IoU threshold and their mean AP,
     foreground ARI, mean best overlap.  particles=K: the best of K posterior particles under `select` is scored instead; the line
-    also reports best_particle_moved and ess as make_parse_logger does, and the record names K and the criterion."""
+    also reports best_particle_moved and ess as make_parse_logger does, and the record names K and the criterion.  refine=N: the
+    refined parse is scored; the line also reports objective_gain and refine_moved as make_parse_logger does."""
     import torch
     G = int(data["boxes"].shape[1])
     kw = {} if thresholds is None else dict(thresholds=tuple(thresholds))
     pk = {} if particles is None else dict(particles=int(particles), select=select)
+    rk = _refine_kw(refine, refine_lr)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -200,29 +229,38 @@ def make_parse_score_logger(air, data, num_batches, name, writer=None, threshold
             raise ValueError("the annotated dataset holds fewer images than one batch of %d" % B)
         start = time.time()
         dev = air.obs.device
-        scorer = air.parse_scorer(G, **kw, **pk)
+        scorer = air.parse_scorer(G, **kw, **pk, **rk)
         scorer.reset()
         extra = torch.zeros(2, dtype=torch.float64, device=dev) if pk else None
+        extra_r = torch.zeros(2, dtype=torch.float64, device=dev) if rk else None
         for i in range(n):
             sl = slice(i * B, (i + 1) * B)
             air.score_parse(torch.as_tensor(data["imgs"][sl], dtype=torch.float32).to(dev), torch.as_tensor(data["instances"][sl]),
-                            torch.as_tensor(data["boxes"][sl]), **kw, **pk)
+                            torch.as_tensor(data["boxes"][sl]), **kw, **pk, **rk)
             if pk:
                 extra += torch.stack([(air.parsed["best_particle"] != 0).double().sum(), air.parsed["ess"].double().sum()])
+            if rk:
+                extra_r += torch.stack(_refine_sums(air.parsed))
         acc = scorer.summary()
         shown = ["count_acc", "map", "ap@%.2f" % scorer.thresholds_host[0], "fg_ari", "mean_best_overlap", "matched_box_iou"]
         if pk:
             moved, ess = (extra / (n * B)).tolist()
             acc.update(best_particle_moved=moved, ess=ess)
             shown += ["best_particle_moved", "ess"]
+        if rk:
+            gain, moved_r = (extra_r / (n * B)).tolist()
+            acc.update(objective_gain=gain, refine_moved=moved_r)
+            shown += ["objective_gain", "refine_moved"]
         t = time.time() - start
         label = 'parse score({}, {}) '.format(pk["particles"], select) if pk else 'parse score '
+        if rk:
+            label = label[:-1] + '+refine({}) '.format(rk["refine"])
         msg = 'Step {}, Data {} '.format(itr, name) + label + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **pk, **acc)) + "\n"); writer.flush()
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **pk, **rk, **acc)) + "\n"); writer.flush()
         return acc
     return logger
 

@@ -325,11 +325,38 @@ class AIRonMNIST(AIRModel):
             self._particle_parser = s
         return s
 
-    def _parser_for(self, particles, select):
+    def _parser_for(self, particles, select, refine=None, refine_lr=None):
         n = self.obs.shape[0]
-        return self.scene_parser(n) if particles is None else self.particle_parser(n, particles, select)
+        parser = self.scene_parser(n) if particles is None else self.particle_parser(n, particles, select)
+        return parser if refine is None else self.parse_refiner(parser, refine, refine_lr)
 
-    def parse(self, obs=None, num_objects=None, particles=None, select="joint"):
+    MAX_PARSE_REFINERS = 4
+
+    def parse_refiner(self, parser, steps, lr=None):
+        """the ParseRefiner behind parse(refine=N): one per (batch, particles, select, N, lr), bound to that parser (built and captured
+        on first use; dropped when its parser was rebuilt, and the least recently used one when more than MAX_PARSE_REFINERS are
+        alive -- a scorer still bound to a dropped one keeps working, its refiner then launches eagerly)"""
+        from .refine import DEFAULT_LR, ParseRefiner
+        lr = tuple(float(v) for v in (DEFAULT_LR if lr is None else lr))
+        if len(lr) != 2:
+            raise ValueError("refine_lr: (lr_what, lr_where), got %r" % (lr,))
+        cache = self.__dict__.setdefault("_parse_refiners", {})
+        for k in [k for k, r in cache.items() if r.parser is not getattr(self, "_scene_parser", None)
+                  and r.parser is not getattr(self, "_particle_parser", None)]:
+            cache.pop(k).release_graphs()
+        key = (parser.R, getattr(parser, "K", None), getattr(parser, "select", None), int(steps), lr)
+        r = cache.pop(key, None)
+        if r is None or r.parser is not parser:
+            if r is not None:
+                r.release_graphs()
+            r = ParseRefiner(parser, int(steps), lr[0], lr[1])
+            r.capture()
+        cache[key] = r                                             # most recently used last
+        while len(cache) > self.MAX_PARSE_REFINERS:                # a learning-rate sweep must not pile up buffers and graphs
+            cache.pop(next(iter(cache))).release_graphs()
+        return r
+
+    def parse(self, obs=None, num_objects=None, particles=None, select="joint", refine=None, refine_lr=None):
         """Scene parse on the device.  particles=None: the deterministic parse (parse.SceneParser: its own engine at the mode of the
         inference network); particles=K: K posterior particles per image and the best one under `select` ("joint": the largest
         log p(x, z), "weight": the largest importance weight) kept (particle_parse.ParticleParser: its own engine at K * batch
@@ -337,24 +364,28 @@ class AIRonMNIST(AIRModel):
         current batch.  Returns the parser's dict of device tensors (SceneParser.parse lists them: num_objects, count_prob,
         presence, score, boxes, what, where, the object table behind offsets, reconstruction, rec, owner, area; ParticleParser.parse
         adds best_particle, the weights, the spread of `where`); the next call overwrites them.  num_objects (counts to use instead
-        of the model's) goes with the deterministic parse only."""
+        of the model's) goes with the deterministic parse only.  refine=N: N gradient-ascent iterations on log p(x, z) behind that
+        parse (refine.ParseRefiner; refine_lr = (lr_what, lr_where), None: refine.DEFAULT_LR); the result then describes the refined
+        parse and adds objective, objective_start, best_iter, objective_trace, grad_what, grad_where.  refine=None: the paths above,
+        untouched."""
         if particles is not None and num_objects is not None:
             raise ValueError("parse: num_objects together with particles is not supported (conditioning the sampled chain on a "
                              "count is out of scope); pass one of them")
         if obs is not None:
             self.obs = obs
-        s = self._parser_for(particles, select)
+        s = self._parser_for(particles, select, refine, refine_lr)
         self._sync_engine_switches()
         s.load_from(self._engine)                            # every time: the weights move
         # (the caller's stream is ordered after it)
         self.parsed = s.parse(self.obs, num_objects) if particles is None else s.parse(self.obs)
         return self.parsed
 
-    def parse_scorer(self, max_gt_objects, thresholds=None, particles=None, select="joint"):
+    def parse_scorer(self, max_gt_objects, thresholds=None, particles=None, select="joint", refine=None, refine_lr=None):
         """the ParseScorer behind score_parse, bound to the parser of the current batch size that parse(particles=..., select=...)
-        uses (built and captured on first use, rebuilt when the parser, the number of ground-truth slots or the thresholds change)"""
+        uses (built and captured on first use, rebuilt when the parser, the number of ground-truth slots or the thresholds change);
+        refine=N binds it to that parse's refiner instead, so the refined parse is what gets scored"""
         from .score import DEFAULT_THRESHOLDS, ParseScorer
-        parser = self._parser_for(particles, select)
+        parser = self._parser_for(particles, select, refine, refine_lr)
         th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
         s = getattr(self, "_parse_scorer", None)
         if s is None or s.parser is not parser or s.G != int(max_gt_objects) or s.thresholds_host != th:
@@ -366,13 +397,13 @@ class AIRonMNIST(AIRModel):
         return s
 
     def score_parse(self, obs, gt_instances, gt_boxes, gt_count=None, thresholds=None, accumulate=True, particles=None,
-                    select="joint"):
+                    select="joint", refine=None, refine_lr=None):
         """Parse `obs` (AIRonMNIST.parse, with `particles` / `select` as there), then score the parse against the ground truth on the device (score.ParseScorer.score lists
         the arguments and the returned device tensors).  gt_count=None: the number of rows of gt_boxes with width > 0.  The sums
         accumulate in `parse_scorer(...)`: its reset() starts a validation set, its summary() reads the figures back once."""
         import torch
-        self.parse(obs, particles=particles, select=select)
-        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds, particles, select)
+        self.parse(obs, particles=particles, select=select, refine=refine, refine_lr=refine_lr)
+        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds, particles, select, refine, refine_lr)
         self.parse_scores = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores
 

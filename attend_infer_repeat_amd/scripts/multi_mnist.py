@@ -87,10 +87,32 @@ def main(argv=None):
     ap.add_argument("--parse-select", default="joint", choices=("joint", "weight"),
                     help="with --parse-particles: the particle kept per image -- 'joint' = the largest log p(x, z), 'weight' = the largest "
                          "importance weight log p(x, z) - log q(z | x)")
+    ap.add_argument("--parse-refine", type=int, default=None, metavar="N",
+                    help="--parse-eval and --parse-score refine the parse by N gradient-ascent iterations on log p(x, z) in the continuous "
+                         "latents (AIRonMNIST.parse(refine=N), refine.ParseRefiner) behind the parse at the mode or the best of "
+                         "--parse-particles; the log record names N and adds objective_gain and refine_moved; N = 0 evaluates the start "
+                         "parse's objective only")
+    ap.add_argument("--parse-refine-lr", default=None, metavar="A,B",
+                    help="with --parse-refine: the Adam learning rates of the `what` and the `where` latents (default: refine.DEFAULT_LR)")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
     args = ap.parse_args(argv)
+    refine_kw = {}
+    if args.parse_refine_lr is not None and args.parse_refine is None:
+        ap.error("--parse-refine-lr goes with --parse-refine")
+    if args.parse_refine is not None:
+        if args.parse_refine < 0:
+            ap.error("--parse-refine needs N >= 0")
+        refine_kw["refine"] = args.parse_refine
+        if args.parse_refine_lr is not None:
+            try:
+                lr = tuple(float(v) for v in args.parse_refine_lr.split(","))
+            except ValueError:
+                lr = ()
+            if len(lr) != 2 or min(lr) < 0:
+                ap.error("--parse-refine-lr needs two learning rates >= 0 as A,B, got %r" % args.parse_refine_lr)
+            refine_kw["refine_lr"] = lr
 
     learning_rate, n_steps, batch_size = args.learning_rate, 3, 64    # multi_mnist.py:24-25,37
     num_steps_prior = AttrDict(anneal='exp', init=1. - 1e-15, final=1e-7, steps_div=1e4, steps=1e5, hold_init=1e3)
@@ -198,7 +220,7 @@ def main(argv=None):
     parse_kw = dict(particles=args.parse_particles, select=args.parse_select) if args.parse_particles > 0 else {}
     if args.parse_eval:
         before_parse_log = log
-        parse_log = make_parse_logger(air, valid_feed, args.eval_batches, 'test', writer, **parse_kw)
+        parse_log = make_parse_logger(air, valid_feed, args.eval_batches, 'test', writer, **parse_kw, **refine_kw)
 
         def log(train_itr):                               # noqa: F811
             out = before_parse_log(train_itr)
@@ -209,7 +231,7 @@ def main(argv=None):
 
     if args.parse_score:
         before_score_log = log
-        score_log = make_parse_score_logger(air, valid_data, args.eval_batches, 'test', writer, **parse_kw)
+        score_log = make_parse_score_logger(air, valid_data, args.eval_batches, 'test', writer, **parse_kw, **refine_kw)
 
         def log(train_itr):                               # noqa: F811
             out = before_score_log(train_itr)

@@ -105,7 +105,8 @@ AIR_ENGINE_API int air_canvas_unroll_fwd_banded(const float *glimpse, const floa
                                  float *canvas_steps, float *final_canvas, float *rec_parts, int n_bands,
                                  int T, int B, int H, int W, int h, int w, float mult, float std, void *stream);
 
-/* Backward of mean_b(rec_per_sample) * loss_scale through the fused op: dcanvas is formed on the fly from
+/* Backward of loss_scale * sum_b(rec_per_sample) through the fused op: every image's own gradient is multiplied by loss_scale
+ * (1/B gives the batch mean's gradient, 1 the gradient of the plain sum).  dcanvas is formed on the fly from
  * (final_canvas, obs).  Outputs dglimpse[T,B,h,w], dwhere[T,B,4].                                                  */
 AIR_API int air_canvas_unroll_bwd(const float *glimpse, const float *where, const float *presence, const float *obs,
                           const float *final_canvas, float *dglimpse, float *dwhere,
@@ -614,6 +615,37 @@ AIR_ENGINE_API int air_particle_select(const float *log_w, const float *log_q, c
                         float *what_sel, float *presence_prob_sel, float *glimpse_sel, void *stream);
 AIR_ENGINE_API int air_particle_spread(const float *log_w, const int *num_steps, const float *where, int T, int R, int K,
                         float *where_mean, float *where_std, float *presence_iw, void *stream);
+
+/* ---- refining a parse: gradient ascent on log p(x, z) in the continuous latents, the count held fixed (semi-amortised inference).
+ * air_refine_step: ONE launch per iteration `iter`, behind that iteration's decoder and air_canvas_unroll_fwd_banded and (do_update != 0)
+ *   air_canvas_unroll_bwd with loss_scale = 1 and the decoder's dX chain.  One workgroup per image; no atomics, one fixed order: the same
+ *   bits run to run.  what[T,B,A], where[T,B,4] (in/out), glimpse[T,B,G] (this iteration's raw decoder output), presence[T,B],
+ *   rec_parts[n_bands,B], dwhat / dwhere = d(sum_b rec_b)/d(what / where), where_loc[T,B,4] (read only when shift_p_loc is NaN: the
+ *   convention of air_iw_logweight; may be NULL otherwise), Adam moments m_*, v_* shaped like their latents.  Per image b, with
+ *   n = the number of leading ones of presence[:, b]:
+ *   rec = the band shares added in band order from 0 (the operations of air_sum_leading);
+ *   J = -rec + sum_{t<n} [ sum_a log N(what_ta | what_p) + sum_{j in 0,2} log N(where_tj | scale_p) + sum_{j in 1,3} log N(where_tj | shift_p) ]
+ *     with the -1/2 log 2 pi of every term; fp32 terms in the lane layout of air_iw_logposterior, the closing adds in float64.  No clamps:
+ *     a zero or NaN latent gives +-inf / NaN.  J_trace[iter, b] = (float) J (optional).
+ *   keep: the iterate is taken if iter == 0, else iff J is not NaN and (best_J[b] is NaN or J > best_J[b]) -- strict: the earliest
+ *     iteration wins a tie; -inf is an ordinary value.  Taking: best_J[b] = J (float64), best_iter[b] = iter, and bit copies of all T
+ *     rows of what / where / glimpse of the image into best_what / best_where / best_glimpse (16-byte vectors where A resp. G is a
+ *     multiple of 4 and the buffers are 16-byte aligned, 4-byte words otherwise).  Not taken: none of the five is written.
+ *   update (do_update != 0; rows t < n only; fp32; after the copies), per element z with gradient d and prior N(mu, sigma):
+ *     g = d + (z - mu) / sigma^2;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *     z = z - lr (m / c1) / (sqrt(v / c2) + eps)   with c1 = 1 - beta1^(iter+1), c2 = 1 - beta2^(iter+1) formed by the caller in float64;
+ *     then sx, sy (components 0, 2 of where) by the guard_eps rule of air_gauss_sample_fwd (|s| >= guard_eps, sign kept, +guard for 0).
+ *     A learning rate of exactly 0 leaves the latents of its group unwritten (the moments still move).  Rows t >= n keep latents and
+ *     moments bit for bit.  do_update == 0 (the closing call): dwhat / dwhere / the moments are not read and may be NULL.
+ *   T in 1..32, positive sizes, iter >= 0 (AIR_E_SHAPE); where / dwhere / where_loc / m_where / v_where / best_where 16-byte aligned
+ *   (AIR_E_ALIGN).  Checks come before the launch: a refused call writes nothing.                                                */
+AIR_ENGINE_API int air_refine_step(float *what, float *where, const float *glimpse, const float *presence, const float *rec_parts,
+                    int n_bands, const float *dwhat, const float *dwhere, const float *where_loc, float what_p_loc,
+                    float what_p_scale, float scale_p_loc, float scale_p_scale, float shift_p_loc, float shift_p_scale,
+                    float *m_what, float *v_what, float *m_where, float *v_where, float lr_what, float lr_where, float beta1,
+                    float beta2, float eps, float c1, float c2, float guard_eps, int iter, int do_update, int T, int B, int A, int G,
+                    double *best_J, int *best_iter, float *best_what, float *best_where, float *best_glimpse, float *J_trace,
+                    void *stream);
 
 /* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
  * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
