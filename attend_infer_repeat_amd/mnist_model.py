@@ -325,10 +325,12 @@ class AIRonMNIST(AIRModel):
             self._particle_parser = s
         return s
 
-    def _parser_for(self, particles, select, refine=None, refine_lr=None):
+    def _parser_for(self, particles, select, refine=None, refine_lr=None, prune=None):
         n = self.obs.shape[0]
         parser = self.scene_parser(n) if particles is None else self.particle_parser(n, particles, select)
-        return parser if refine is None else self.parse_refiner(parser, refine, refine_lr)
+        if refine is not None:
+            parser = self.parse_refiner(parser, refine, refine_lr)
+        return parser if prune is None else self.parse_pruner(parser, prune)
 
     MAX_PARSE_REFINERS = 4
 
@@ -356,7 +358,32 @@ class AIRonMNIST(AIRModel):
             cache.pop(next(iter(cache))).release_graphs()
         return r
 
-    def parse(self, obs=None, num_objects=None, particles=None, select="joint", refine=None, refine_lr=None):
+    MAX_PARSE_PRUNERS = 4
+
+    def parse_pruner(self, provider, candidates="present"):
+        """the ParsePruner behind parse(prune=...): one per (provider, candidates), bound to that scene parser, particle parser or
+        refiner (built and captured on first use; dropped when its provider was rebuilt or dropped, and the least recently used one
+        when more than MAX_PARSE_PRUNERS are alive -- a scorer still bound to a dropped one keeps working, its pruner then launches
+        eagerly)"""
+        from .prune import ParsePruner
+        cache = self.__dict__.setdefault("_parse_pruners", {})
+        alive = [getattr(self, "_scene_parser", None), getattr(self, "_particle_parser", None)]
+        alive += list(self.__dict__.get("_parse_refiners", {}).values())
+        for k in [k for k, r in cache.items() if not any(r.parser is a for a in alive)]:
+            cache.pop(k).release_graphs()
+        key = (id(provider), candidates)
+        r = cache.pop(key, None)
+        if r is None or r.parser is not provider:
+            if r is not None:
+                r.release_graphs()
+            r = ParsePruner(provider, candidates)
+            r.capture()
+        cache[key] = r                                             # most recently used last
+        while len(cache) > self.MAX_PARSE_PRUNERS:
+            cache.pop(next(iter(cache))).release_graphs()
+        return r
+
+    def parse(self, obs=None, num_objects=None, particles=None, select="joint", refine=None, refine_lr=None, prune=None):
         """Scene parse on the device.  particles=None: the deterministic parse (parse.SceneParser: its own engine at the mode of the
         inference network); particles=K: K posterior particles per image and the best one under `select` ("joint": the largest
         log p(x, z), "weight": the largest importance weight) kept (particle_parse.ParticleParser: its own engine at K * batch
@@ -367,25 +394,29 @@ class AIRonMNIST(AIRModel):
         of the model's) goes with the deterministic parse only.  refine=N: N gradient-ascent iterations on log p(x, z) behind that
         parse (refine.ParseRefiner; refine_lr = (lr_what, lr_where), None: refine.DEFAULT_LR); the result then describes the refined
         parse and adds objective, objective_start, best_iter, objective_trace, grad_what, grad_where.  refine=None: the paths above,
-        untouched."""
+        untouched.  prune="present" | "all": behind whichever of the paths above, the exact arg-max of log p(x, z_S) over the subsets
+        S of the computed steps (prune.ParsePruner; max_steps <= 6) -- "present" can only remove objects of the parse, "all" may also
+        switch on a step the presence chain left out; the result then describes the selected subset, compacted, and adds objective,
+        objective_start (float64), objective_subsets, best_mask, kept_step, evidence, num_objects_start.  prune=None: the paths
+        above, untouched."""
         if particles is not None and num_objects is not None:
             raise ValueError("parse: num_objects together with particles is not supported (conditioning the sampled chain on a "
                              "count is out of scope); pass one of them")
         if obs is not None:
             self.obs = obs
-        s = self._parser_for(particles, select, refine, refine_lr)
+        s = self._parser_for(particles, select, refine, refine_lr, prune)
         self._sync_engine_switches()
         s.load_from(self._engine)                            # every time: the weights move
         # (the caller's stream is ordered after it)
         self.parsed = s.parse(self.obs, num_objects) if particles is None else s.parse(self.obs)
         return self.parsed
 
-    def parse_scorer(self, max_gt_objects, thresholds=None, particles=None, select="joint", refine=None, refine_lr=None):
+    def parse_scorer(self, max_gt_objects, thresholds=None, particles=None, select="joint", refine=None, refine_lr=None, prune=None):
         """the ParseScorer behind score_parse, bound to the parser of the current batch size that parse(particles=..., select=...)
         uses (built and captured on first use, rebuilt when the parser, the number of ground-truth slots or the thresholds change);
-        refine=N binds it to that parse's refiner instead, so the refined parse is what gets scored"""
+        refine=N binds it to that parse's refiner instead, so the refined parse is what gets scored; prune=... to that parse's pruner"""
         from .score import DEFAULT_THRESHOLDS, ParseScorer
-        parser = self._parser_for(particles, select, refine, refine_lr)
+        parser = self._parser_for(particles, select, refine, refine_lr, prune)
         th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
         s = getattr(self, "_parse_scorer", None)
         if s is None or s.parser is not parser or s.G != int(max_gt_objects) or s.thresholds_host != th:
@@ -397,13 +428,13 @@ class AIRonMNIST(AIRModel):
         return s
 
     def score_parse(self, obs, gt_instances, gt_boxes, gt_count=None, thresholds=None, accumulate=True, particles=None,
-                    select="joint", refine=None, refine_lr=None):
+                    select="joint", refine=None, refine_lr=None, prune=None):
         """Parse `obs` (AIRonMNIST.parse, with `particles` / `select` as there), then score the parse against the ground truth on the device (score.ParseScorer.score lists
         the arguments and the returned device tensors).  gt_count=None: the number of rows of gt_boxes with width > 0.  The sums
         accumulate in `parse_scorer(...)`: its reset() starts a validation set, its summary() reads the figures back once."""
         import torch
-        self.parse(obs, particles=particles, select=select, refine=refine, refine_lr=refine_lr)
-        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds, particles, select, refine, refine_lr)
+        self.parse(obs, particles=particles, select=select, refine=refine, refine_lr=refine_lr, prune=prune)
+        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds, particles, select, refine, refine_lr, prune)
         self.parse_scores = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores
 

@@ -1,0 +1,406 @@
+"""Letting a scene parse change its count on the device: the exact arg-max of log p(x, z_S) over the subsets S of the T computed steps.
+
+    log p(x, z_S) = log p(x | mult * sum_{t in S} layer_t) + sum_{t in S} log p(z_t) + log pi(|S|)
+
+The canvas is a sum and the per-step priors are i.i.d., so the joint is defined for every subset of steps, not only for the leading-
+ones chains the inference network emits; with T <= 6 there are at most 64 subsets and the discrete problem refine.py leaves open
+("the count stays fixed") is solved by enumeration -- one pass over the pixels for all subsets.  The forward pass computes latents and
+glimpses of all T steps, so the enumeration may also switch ON a step the presence chain declined (candidates="all").
+
+A subset is a mask m, bit t = step t is kept.  Per image: n = the number of leading ones of the start parse's presence, the candidate
+steps are t < c with c = n ("present": objects can only be removed) or c = T ("all"), the start mask is m0 = 2^n - 1.  m0 is visited
+first and always taken, then every other mask from 2^c - 1 down to 0; a mask replaces the best one iff its J is not NaN and (the best
+is NaN or J > best), strictly: the parse is unchanged on a tie, never worse than the start, unchanged when everything is NaN.
+evidence[t] = J(m0 with bit t) - J(m0 without bit t): how much the model wants object t, a ranking figure of its own.
+
+`ParsePruner` owns no engine: it binds to a parse.SceneParser, a particle_parse.ParticleParser or a refine.ParseRefiner, runs that
+provider's own `parse()` and then, on the same engine stream, its own launch list of libair_hip.so entries (include/air_hip.h), captured
+as ONE hipGraph by `capture()`:
+
+  air_prune_score    the reconstruction term of every mask in row bands (the hot path);
+  air_prune_select   the latent terms, J of every mask in float64, the arg-max, the evidence, and the rows compacted into a
+                     leading-ones chain (a stable partition: kept steps in step order, then the others; bit copies);
+  air_parse_objects  (given counts) on the compacted rows, with the start parse's presence_prob: count_prob = q(n');
+  air_prune_relabel  score / obj_score / obj_step of the kept rows: air_parse_objects labels rows by position;
+  air_parse_render, air_sum_leading   reconstruction, rec, owner, area of the selected subset.
+
+One exception to "one hipGraph", the one refine.py has: behind a ParticleParser with a shift prior given without `loc`, particle 0's
+where_loc rows are gathered by a strided device copy on the engine stream BEFORE the launch list.
+
+This closes "the count stays fixed" only for subsets of the T computed steps; proposing new objects from a residual image stays open.
+`reference_score` and `reference_select` restate the two kernels in numpy float64.
+"""
+import ctypes
+import math
+from typing import Dict
+
+from . import iw_eval
+from .engine_config import EngineConfig
+from .launch import destroy_graphs
+
+HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+MAX_STEPS = 6                      # air_prune_score is instantiated for T = 1 .. 6: at most 64 subsets
+CANDIDATES = {"present": 0, "all": 1}
+
+
+def check_arguments(cfg: EngineConfig, candidates: str = "present") -> None:
+    """Refuse what cannot be pruned this way (pure host code: importable and callable without a GPU).  The priors are needed: they
+    are the latent terms of log p(x, z).  bf16 MLPs are fine: nothing here runs the decoder."""
+    if candidates not in CANDIDATES:
+        raise ValueError('candidates must be "present" or "all", got %r' % (candidates,))
+    if int(cfg.max_steps) > MAX_STEPS:
+        raise ValueError("subset pruning enumerates every subset of the computed steps and stops at 64 subsets: max_steps <= %d, "
+                         "got %d" % (MAX_STEPS, int(cfg.max_steps)))
+    iw_eval.check_config(cfg, 1)
+
+
+def _st_write(glimpse, where, img):
+    """float64 inverse spatial-transformer write of one step: glimpse [B, h, w], where [B, 4] = [sx, tx, sy, ty] -> [B, H, W]
+    (the taps and the bilinear form of air_parse_render; a tap outside the glimpse is zero, a coordinate outside (-1, extent) gives 0)"""
+    import numpy as np
+    B, h, w = glimpse.shape
+    H, W = img
+    out = np.zeros((B, H, W))
+    X, Y = np.linspace(-1.0, 1.0, W), np.linspace(-1.0, 1.0, H)
+    if W == 1:
+        X = np.array([-1.0])
+    if H == 1:
+        Y = np.array([-1.0])
+    pad = np.zeros((B, h + 2, w + 2))
+    pad[:, 1:-1, 1:-1] = glimpse
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for b in range(B):
+            sx, tx, sy, ty = where[b]
+            cx = ((1.0 / sx) * X + (-tx / sx) + 1.0) * ((w - 1) / 2.0)
+            cy = ((1.0 / sy) * Y + (-ty / sy) + 1.0) * ((h - 1) / 2.0)
+            vx, vy = (cx > -1.0) & (cx < w), (cy > -1.0) & (cy < h)
+            fx = np.where(vx, np.floor(np.where(vx, cx, 0.0)), 0.0).astype(np.int64)
+            fy = np.where(vy, np.floor(np.where(vy, cy, 0.0)), 0.0).astype(np.int64)
+            dx, dy = (fx + 1.0) - np.where(vx, cx, 0.0), (fy + 1.0) - np.where(vy, cy, 0.0)
+            g = pad[b]
+            iy, ix = fy[:, None] + 1, fx[None, :] + 1
+            DX, DY = dx[None, :], dy[:, None]
+            val = (DX * DY) * g[iy, ix] + ((1 - DX) * (1 - DY)) * g[iy + 1, ix + 1] + (DX * (1 - DY)) * g[iy + 1, ix] \
+                + ((1 - DX) * DY) * g[iy, ix + 1]
+            out[b] = np.where(vy[:, None] & vx[None, :], val, 0.0)
+    return out
+
+
+def leading_ones(presence):
+    import numpy as np
+    return np.cumprod(np.asarray(presence) > 0.5, axis=0).sum(0).astype(np.int64)
+
+
+def reference_score(glimpse, where, presence, obs, mult, std, all_candidates, layers=None):
+    """air_prune_score restated in plain numpy float64 (include/air_hip.h states the rule), summed over the bands: glimpse [T, B, h, w],
+    where [T, B, 4], presence [T, B], obs [B, H, W].  `layers` [T, B, H, W]: float64 st_write layers computed elsewhere, used instead
+    of this module's own inverse warp.  Returns rec_sub [B, 2^T] float64, NaN for the masks m >= 2^c that the kernel does not write."""
+    import numpy as np
+    glimpse, where, obs = np.asarray(glimpse, np.float64), np.asarray(where, np.float64), np.asarray(obs, np.float64)
+    T, B = glimpse.shape[:2]
+    H, W = obs.shape[1:]
+    n = leading_ones(presence)
+    c = np.full(B, T) if all_candidates else n
+    if layers is None:
+        layers = np.stack([_st_write(glimpse[t], where[t], (H, W)) for t in range(T)], 0)
+    layers = np.asarray(layers, np.float64)
+    out = np.full((B, 1 << T), np.nan)
+    cst = HALF_LOG_2PI + math.log(std)
+    for m in range(1 << T):
+        canvas = np.zeros((B, H, W))
+        for t in range(T):                                         # step order from 0
+            if (m >> t) & 1:
+                canvas = canvas + layers[t]
+        with np.errstate(invalid="ignore", over="ignore"):
+            z = (obs - mult * canvas) / std
+            rec = (0.5 * z * z + cst).reshape(B, -1).sum(1)
+        live = m < (1 << c)
+        out[live, m] = rec[live]
+    return out
+
+
+def _log_normal(x, loc, scale):
+    import numpy as np
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        z = (x - loc) / scale
+        return -0.5 * z * z - np.log(scale) - HALF_LOG_2PI
+
+
+def select_masks(J_sub, n, T, all_candidates):
+    """the visiting rule on a table of joints J_sub [B, 2^T] (any float dtype; compared as float64): returns best_mask [B] int64"""
+    import numpy as np
+    J = np.asarray(J_sub, np.float64)
+    best_mask = np.zeros(len(n), np.int64)
+    for b in range(len(n)):
+        c = T if all_candidates else int(n[b])
+        m0 = (1 << int(n[b])) - 1
+        bm, best = m0, J[b, m0]                                    # m0 first: always taken
+        for m in range((1 << c) - 1, -1, -1):
+            if m == m0:
+                continue
+            v = J[b, m]
+            if not math.isnan(v) and (math.isnan(best) or v > best):
+                bm, best = m, v
+        best_mask[b] = bm
+    return best_mask
+
+
+def partition(mask, T):
+    """stable partition of 0 .. T-1: the steps in `mask` in step order, then all other steps in step order"""
+    return [t for t in range(T) if (mask >> t) & 1] + [t for t in range(T) if not (mask >> t) & 1]
+
+
+def reference_select(what, where, glimpse, score, presence, where_loc, priors, prior, normalize_prior, all_candidates, rec_sub,
+                     J_sub=None):
+    """air_prune_select restated in plain numpy float64.  Arrays as the kernel takes them (what [T, B, A], where [T, B, 4], glimpse
+    [T, B, G], score [T, B], presence [T, B], rec_sub [n_bands, B, 2^T] or band-summed [B, 2^T]); priors = (what_loc, what_scale,
+    scale_loc, scale_scale, shift_loc or None / NaN, shift_scale); prior = the count table [T+1].  J_sub: a table of joints to run
+    the selection, the evidence and the objectives on instead of the one formed here (the device's own, say).  Returns
+      lp [T, B], J_sub [B, 2^T] (NaN for m >= 2^c), best_mask, num_objects, n [B], kept_step [T, B], objective, objective_start [B],
+      evidence [T, B] (NaN for t >= c), and what / where / glimpse / score compacted (the inputs' dtype: copies)."""
+    import numpy as np
+    f = lambda a: np.array(a, dtype=np.float64)
+    T, B, A = np.shape(what)
+    NM = 1 << T
+    w_loc, w_scale, s_loc, s_scale, h_loc, h_scale = [float("nan") if v is None else float(v) for v in priors]
+    n = leading_ones(presence)
+    c = np.full(B, T) if all_candidates else n
+    mu = np.empty((T, B, 4))
+    mu[..., 0::2] = s_loc
+    mu[..., 1::2] = f(where_loc)[..., 1::2] if math.isnan(h_loc) else h_loc
+    sd = np.empty((T, B, 4))
+    sd[..., 0::2], sd[..., 1::2] = s_scale, h_scale
+    lp = _log_normal(f(what), w_loc, w_scale).sum(-1) + _log_normal(f(where), mu, sd).sum(-1)                  # [T, B]
+    pi = f(prior)
+    total = 1.0
+    if normalize_prior:
+        total = 0.0
+        for v in pi:
+            total = total + v
+    with np.errstate(divide="ignore", invalid="ignore"):
+        log_pi = np.log(pi / total)
+    rec = f(rec_sub)
+    if rec.ndim == 3:
+        acc = np.zeros((B, NM))
+        for k in range(rec.shape[0]):
+            acc = acc + rec[k]
+        rec = acc
+    J = np.full((B, NM), np.nan)
+    for m in range(NM):
+        lat = np.zeros(B)
+        for t in range(T):
+            if (m >> t) & 1:
+                lat = lat + lp[t]
+        with np.errstate(invalid="ignore"):
+            v = (-rec[:, m] + lat) + log_pi[bin(m).count("1")]
+        live = m < (1 << c)
+        J[live, m] = v[live]
+    own_J = J
+    if J_sub is not None:
+        J = np.asarray(J_sub, np.float64)
+    best = select_masks(J, n, T, all_candidates)
+    m0 = (1 << n) - 1
+    rows = np.arange(B)
+    evidence = np.full((T, B), np.nan)
+    for t in range(T):
+        with np.errstate(invalid="ignore"):
+            e = J[rows, m0 | (1 << t)] - J[rows, m0 & ~(1 << t)]
+        evidence[t, t < c] = e[t < c]
+    kept = np.array([partition(int(best[b]), T) for b in range(B)], np.int32).T.reshape(T, B)                   # [T, B]
+    gather = lambda a: np.stack([np.asarray(a)[kept[:, b], b] for b in range(B)], 1)
+    return {"lp": lp, "J_sub": own_J, "best_mask": best, "num_objects": np.array([bin(int(m)).count("1") for m in best], np.int64),
+            "n": n, "kept_step": kept, "objective": J[rows, best], "objective_start": J[rows, m0], "evidence": evidence,
+            "what": gather(what), "where": gather(where), "glimpse": gather(glimpse), "score": gather(score)}
+
+
+def _start_buffers(provider):
+    """the device buffers the provider's `parse()` returns that the pruner reads -- the start rows, the presence chain, the per-step
+    score, the count, presence_prob, the B-row images -- and the where_loc rows that centre a shift prior given without `loc` (None: to
+    be gathered from particle 0 before every call).  refine._start_buffers, extended by the refiner itself as a provider."""
+    eng = provider.engine
+    if hasattr(provider, "best_what"):                              # refine.ParseRefiner
+        from .refine import _start_buffers as refiner_start
+        inner = refiner_start(provider.parser)
+        return {"what": provider.best_what, "where": provider.best_where, "glimpse": provider.best_glimpse,
+                "presence_prob": inner["presence_prob"], "obs": inner["obs"], "where_loc": provider.where_loc, "gather_loc": False}
+    if hasattr(provider, "what_sel"):                               # particle_parse.ParticleParser
+        return {"what": provider.what_sel, "where": provider.where_sel, "glimpse": provider.glimpse_sel,
+                "presence_prob": provider.presence_prob_sel, "obs": provider.obs, "where_loc": None, "gather_loc": True}
+    return {"what": eng.what, "where": eng.where, "glimpse": eng.gd.out[-1], "presence_prob": eng.presence_prob, "obs": eng.obs,
+            "where_loc": eng.where_loc, "gather_loc": False}
+
+
+class ParsePruner:
+    def __init__(self, parser, candidates: str = "present", normalize_steps_prior: bool = True):
+        cfg = parser.engine.cfg
+        check_arguments(cfg, candidates)
+        import torch
+        from . import hip as H
+        self.parser, self.engine = parser, parser.engine
+        self.candidates, self.normalize_steps_prior = candidates, bool(normalize_steps_prior)
+        self.T, self.R = parser.T, parser.R
+        self.mask_threshold = parser.mask_threshold
+        eng, dev = self.engine, self.engine.device
+        T, B, A = self.T, self.R, int(cfg.n_appearance)
+        (Hi, Wi), hw = cfg.img_size, cfg.n_crop
+        NM = 1 << T
+        self.n_bands = int(H.lib().air_canvas_unroll_bands(B, int(Hi)))
+        self._start = _start_buffers(parser)
+        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+        with torch.cuda.device(dev):
+            self.where_loc = self._start["where_loc"] if self._start["where_loc"] is not None else z((T, B, 4))
+            self.rec_sub = z((self.n_bands, B, NM))
+            self.J_sub = torch.full((B, NM), float("nan"), dtype=torch.float64, device=dev)
+            self.best_mask, self.num_objects_in = z((B,), torch.int32), z((B,), torch.int32)
+            self.kept_step = z((T, B), torch.int32)
+            self.objective, self.objective_start = z((B,), torch.float64), z((B,), torch.float64)
+            self.evidence = z((T, B), torch.float64)
+            self.what, self.where, self.glimpse, self.score_src = z((T, B, A)), z((T, B, 4)), z((T, B, hw)), z((T, B))
+            # the read-out of the selected subset (what the parsers keep)
+            self.num_objects, self.count_prob = z((B,), torch.int32), z((B,))
+            self.presence, self.score, self.boxes = z((T, B)), z((T, B)), z((T, B, 4))
+            self.offsets = z((B + 1,), torch.int32)
+            self.obj_image, self.obj_step = z((T * B,), torch.int32), z((T * B,), torch.int32)
+            self.obj_box, self.obj_score = z((T * B, 4)), z((T * B,))
+            self.obj_where, self.obj_what = z((T * B, 4)), z((T * B, A))
+            self.reconstruction = z((B, Hi, Wi))
+            self.rec_parts, self.rec = z((self.n_bands, B)), z((B,))
+            self.owner = z((B, Hi, Wi), torch.int8)
+            self.area = z((T, B), torch.int32)
+        self._graph = None
+        self._H = H
+        self._build_plan()
+        eng.synchronize()
+
+    # ---- the launches behind the provider's own call -------------------------------------------------------------------------
+    def _build_plan(self):
+        H, eng, par, st = self._H, self.engine, self.parser, self._start
+        cfg = eng.cfg
+        check_arguments(cfg, self.candidates)
+        L, p, size = H.lib(), H._p, ctypes.c_size_t
+        T, B, A = self.T, self.R, int(cfg.n_appearance)
+        (Hi, Wi), (hc, wc) = cfg.img_size, cfg.crop_size
+        mult, std = float(cfg.output_multiplier), float(cfg.output_std)
+        shift_loc = cfg.where_shift_prior[0]
+        priors = (float(cfg.what_prior[0]), float(cfg.what_prior[1]), float(cfg.where_scale_prior[0]), float(cfg.where_scale_prior[1]),
+                  float("nan") if shift_loc is None else float(shift_loc), float(cfg.where_shift_prior[1]))
+        allc = CANDIDATES[self.candidates]
+        self._plan = [
+            (L.air_prune_score,
+             (p(st["glimpse"]), p(st["where"]), p(par.presence), p(st["obs"]), mult, std, allc, T, B, Hi, Wi, hc, wc, self.n_bands,
+              p(self.rec_sub)), "air_prune_score"),
+            (L.air_prune_select,
+             (p(st["what"]), p(st["where"]), p(st["glimpse"]), p(par.score), p(par.presence), p(self.where_loc), *priors,
+              p(eng.prior_dev), 1 if self.normalize_steps_prior else 0, allc, p(self.rec_sub), self.n_bands, T, B, A, hc * wc,
+              p(self.J_sub), p(self.best_mask), p(self.num_objects_in), p(self.kept_step), p(self.objective), p(self.objective_start),
+              p(self.evidence), p(self.what), p(self.where), p(self.glimpse), p(self.score_src)), "air_prune_select"),
+            (L.air_parse_objects,
+             (p(st["presence_prob"]), p(self.num_objects_in), p(self.where), p(self.what), T, B, A, Hi, Wi, p(self.num_objects),
+              p(self.count_prob), p(self.presence), p(self.score), p(self.boxes), p(self.offsets), p(self.obj_image), p(self.obj_step),
+              p(self.obj_box), p(self.obj_score), p(self.obj_where), p(self.obj_what)), "air_parse_objects"),
+            (L.air_prune_relabel,
+             (p(self.score_src), p(self.kept_step), p(self.num_objects), p(self.offsets), T, B, p(self.score), p(self.obj_score),
+              p(self.obj_step)), "air_prune_relabel"),
+            (L.air_parse_render,
+             (p(self.glimpse), p(self.where), p(self.presence), p(st["obs"]), mult, std, self.mask_threshold, T, B, Hi, Wi, hc, wc,
+              self.n_bands, p(self.reconstruction), p(self.rec_parts), p(self.owner), p(self.area), None), "air_parse_render"),
+            (L.air_sum_leading, (p(self.rec_parts), p(self.rec), self.n_bands, size(B)), "air_sum_leading")]
+        self._built_for = self._plan_key()
+
+    def _plan_key(self):
+        """what of the engine's configuration the launch list holds by value"""
+        cfg = self.engine.cfg
+        return (cfg.output_multiplier, cfg.output_std, cfg.what_prior, cfg.where_scale_prior, cfg.where_shift_prior)
+
+    def _refresh_plan(self):
+        """rebuild (and re-capture) when a switch of the provider's engine moved without the pruner being told -- the provider is also
+        used on its own, and its `update_config` does not know its pruners"""
+        if self._plan_key() == self._built_for:
+            return False
+        had = self._graph is not None
+        self.release_graphs()
+        self._build_plan()
+        if had:
+            self.capture()
+        return True
+
+    def launch_count(self) -> Dict[str, int]:
+        """entries of one `parse()` call behind the bound provider's own (`parser` holds that provider's launch_count())"""
+        return {"parser": self.parser.launch_count(), "prune_score": 1, "prune_select": 1, "parse_objects": 1, "prune_relabel": 1,
+                "parse_render": 1, "rec_sum": 1}
+
+    # ---- parameters ---------------------------------------------------------------------------------------------------------
+    def load_from(self, train_engine):
+        """device-to-device copy of another engine's parameters into the bound provider's engine, its step counter (the count prior
+        pi depends on it) and run-time switches"""
+        iw_eval.load_inner_engine(self, train_engine)
+
+    def load_parameters(self, named):
+        self.parser.load_parameters(named)
+
+    def set_global_step(self, step: int):
+        self.parser.set_global_step(step)
+
+    def update_config(self, **changes) -> bool:
+        """run-time switches of the bound provider's engine (AIREngine.KNOBS): the provider re-captures its graphs, the pruner rebuilds
+        its launch list (output_multiplier is one of its arguments) and re-captures when one changed"""
+        changed = self.parser.update_config(**changes)
+        return self._refresh_plan() or changed
+
+    # ---- graphs -------------------------------------------------------------------------------------------------------------
+    def capture(self):
+        """every launch behind the provider's own call as ONE hipGraph (the provider's graphs are its own: `parser.capture()`; the
+        where_loc gather of the module docstring's exception stays a copy in front of the graph)"""
+        self.release_graphs()
+        self.engine.synchronize()
+        self._graph = self.engine._capture_plans([self._plan])
+
+    def release_graphs(self):
+        destroy_graphs([self._graph])
+        self._graph = None
+
+    # ---- the parse ----------------------------------------------------------------------------------------------------------
+    def parse(self, obs, *args, **kwargs):
+        """The bound provider's `parse(obs, ...)` (further arguments go to it unchanged), then the subset search.  Returns device
+        tensors that the NEXT call overwrites: every key of the provider's result -- num_objects, count_prob, presence, score, boxes,
+        what, where, glimpse, the object table, reconstruction, rec, owner, area now describe the selected subset, compacted into a
+        leading-ones chain (row j of what / where / glimpse / score is the start parse's row kept_step[j]); presence_prob,
+        num_steps_posterior and a provider's other read-outs are the provider's -- and
+          objective, objective_start [B] float64 (J of the selected mask / of the start mask), objective_subsets [B, 2^T] float64
+          (J of every mask, NaN beyond 2^c), best_mask [B] int32, kept_step [T, B] int32, evidence [T, B] float64 (NaN for t >= c),
+          num_objects_start [B] int32;
+        behind a ParseRefiner also refine_objective, refine_objective_start: the refiner's objective / objective_start, whose own
+        keys now hold the pruner's.
+        Same stream contract as the parsers."""
+        import torch
+        eng, par, st = self.engine, self.parser, self._start
+        self._refresh_plan()
+        base = par.parse(obs, *args, **kwargs)
+        for k in ("what", "where", "glimpse", "presence_prob"):
+            if base[k].data_ptr() != st[k].data_ptr():
+                raise RuntimeError("the bound parser returned %r from another buffer than the pruner was built on" % k)
+        for k in ("presence", "score", "num_objects"):
+            if base[k].data_ptr() != getattr(par, k).data_ptr():
+                raise RuntimeError("the bound parser returned %r from another buffer than the pruner was built on" % k)
+        if st["gather_loc"] and eng.cfg.where_shift_prior[0] is None:
+            with torch.cuda.stream(eng.stream):                    # particle 0's rows (the particles of an image share where_loc)
+                self.where_loc.copy_(eng.where_loc.view(self.T, self.R, -1, 4)[:, :, 0], non_blocking=True)
+        eng._replay_or_run(self._graph, self._plan)
+        eng.wait_for_engine()
+        cfg = eng.cfg
+        out = dict(base)
+        if "best_iter" in base:                                    # behind a refiner: its objectives keep a name of their own
+            out["refine_objective"], out["refine_objective_start"] = base["objective"], base["objective_start"]
+        out.update({"num_objects": self.num_objects, "count_prob": self.count_prob, "presence": self.presence, "score": self.score,
+                    "boxes": self.boxes, "what": self.what, "where": self.where,
+                    "glimpse": self.glimpse.view(self.T, self.R, *cfg.crop_size), "offsets": self.offsets,
+                    "obj_image": self.obj_image, "obj_step": self.obj_step, "obj_box": self.obj_box, "obj_score": self.obj_score,
+                    "obj_where": self.obj_where, "obj_what": self.obj_what, "reconstruction": self.reconstruction, "rec": self.rec,
+                    "owner": self.owner, "area": self.area, "objective": self.objective, "objective_start": self.objective_start,
+                    "objective_subsets": self.J_sub, "best_mask": self.best_mask, "kept_step": self.kept_step,
+                    "evidence": self.evidence, "num_objects_start": par.num_objects})
+        out.pop("layers", None)                                    # (the provider's layers are the start parse's)
+        return out
+
+    def synchronize(self):
+        self.engine.synchronize()

@@ -92,6 +92,11 @@ def main(argv=None):
                          "latents (AIRonMNIST.parse(refine=N), refine.ParseRefiner) behind the parse at the mode or the best of "
                          "--parse-particles; the log record names N and adds objective_gain and refine_moved; N = 0 evaluates the start "
                          "parse's objective only")
+    ap.add_argument("--parse-prune", choices=("present", "all"), default=None,
+                    help="--parse-eval and --parse-score search the subsets of the computed steps for the largest log p(x, z) "
+                         "(AIRonMNIST.parse(prune=...), prune.ParsePruner) behind the parse, its particles and its refinement: "
+                         "\"present\" can only remove objects, \"all\" may also switch on a step the presence chain left out; the log "
+                         "record names the mode and adds count_changed, objects_dropped, objects_added and objective_gain")
     ap.add_argument("--parse-refine-lr", default=None, metavar="A,B",
                     help="with --parse-refine: the Adam learning rates of the `what` and the `where` latents (default: refine.DEFAULT_LR)")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
@@ -113,6 +118,8 @@ def main(argv=None):
             if len(lr) != 2 or min(lr) < 0:
                 ap.error("--parse-refine-lr needs two learning rates >= 0 as A,B, got %r" % args.parse_refine_lr)
             refine_kw["refine_lr"] = lr
+    if args.parse_prune is not None:
+        refine_kw["prune"] = args.parse_prune
 
     learning_rate, n_steps, batch_size = args.learning_rate, 3, 64    # multi_mnist.py:24-25,37
     num_steps_prior = AttrDict(anneal='exp', init=1. - 1e-15, final=1e-7, steps_div=1e4, steps=1e5, hold_init=1e3)

@@ -647,6 +647,59 @@ AIR_ENGINE_API int air_refine_step(float *what, float *where, const float *glimp
                     double *best_J, int *best_iter, float *best_what, float *best_where, float *best_glimpse, float *J_trace,
                     void *stream);
 
+/* ---- letting a parse change its count: the exact arg-max of log p(x, z_S) over the subsets S of the T computed steps, T <= 6 (at
+ * most 64 subsets).  A subset is a mask m, bit t = step t is kept.  Per image b: n_b = the number of leading ones of presence[:, b],
+ * the candidate steps are t < c_b with c_b = n_b (all_candidates == 0: objects can only be removed) or c_b = T (all_candidates != 0:
+ * a computed step the chain left out may be switched on), the masks are 0 .. 2^c_b - 1, the start mask is m0 = 2^n_b - 1.
+ * No atomics, no cross-workgroup traffic, one fixed summation order: the same bits run to run.
+ * air_prune_score: layer_t = st_write(glimpse_t, where_t) with the per-pixel operations of air_parse_render (the same taps, the same
+ *   bilinear form, contraction off), exactly 0 for t >= c_b;  canvas_m(p) = 0 + the layers of the set bits, added in step order from
+ *   0 (the bits air_parse_render's canvas has for a presence row equal to the mask's bits);  per pixel the term
+ *   1/2 ((x_p - mult * canvas_m(p)) / std)^2 + 1/2 log 2 pi + log std.  rec_sub[n_bands, R, 2^T]: entry (k, r, m) = the sum of the
+ *   terms of mask m over the pixels of row band k (air_canvas_unroll_bands' banding; inside a band a fixed order of the kernel's
+ *   own), to be added over k in band order (the operations of air_sum_leading).  Only entries m < 2^c_b are written.  One workgroup
+ *   per (image, band), one kernel instantiation per T with the 2^T accumulators in registers.  AIR_E_SHAPE: T outside 1..6,
+ *   non-positive sizes, n_bands != air_canvas_unroll_bands(R, H);  AIR_E_ALIGN: where not 16-byte aligned;  AIR_E_UNSUPPORTED: the
+ *   LDS carve (T bordered glimpses, the axis tables) above 160 KiB, as air_parse_render.
+ * air_prune_select: one wavefront per image.  what[T,R,A], where[T,R,4], glimpse[T,R,G], score[T,R] (the start parse's per-step
+ *   score), presence[T,R], where_loc[T,R,4] (read only when shift_p_loc is NaN: the convention of air_iw_logweight; may be NULL
+ *   otherwise), prior_f64[T+1] (air_steps_prior's table; divided by its sum when normalize_prior != 0).
+ *   lp_t (t < c_b) = sum_a log N(what_ta | what_p) + sum_{j in 0,2} log N(where_tj | scale_p) + sum_{j in 1,3} log N(where_tj | shift_p)
+ *     with the -1/2 log 2 pi of every term, fp32: the lanes stride over the step's A / V vectors of `what` (V = 4 / 2 / 1 as for
+ *     air_refine_step; items in index order), lane 0 adds the step's four `where` terms behind its items, a butterfly adds the lanes:
+ *     the layout of one step of air_iw_logposterior, the same for every t (equal latents give equal terms, bit for bit).
+ *     No clamps.
+ *   J_m = -(double) rec_m + sum_{t in m, step order} (double) lp_t + log(prior[popcount m] / total), float64; rec_m = the band shares
+ *     of rec_sub added in band order in fp32.  J_sub[R, 2^T] = J_m, NaN for m >= 2^c_b.
+ *   selection: m0 is visited first and always taken; then every other mask from 2^c_b - 1 down to 0; a mask replaces the best one iff
+ *     its J is not NaN and (the best is NaN or J > best), strictly: a tie leaves the parse as it is, the result is never worse than
+ *     the start, everything NaN leaves m0; -inf is an ordinary value.  best_mask[r], num_objects_out[r] = popcount(best mask),
+ *     objective[r] = J of the best mask, objective_start[r] = J_m0 (float64).
+ *   evidence[T,R] (float64) = J(m0 with bit t) - J(m0 without bit t) for t < c_b, NaN for t >= c_b.
+ *   compaction: kept_step[T,R] (int32) = the stable partition of 0 .. T-1 into the kept steps (in step order) followed by all other
+ *     steps (in step order); row j of what_out / where_out / glimpse_out / score_out = row kept_step[j] of the inputs, bit copies
+ *     (16-byte vectors where A resp. G is a multiple of 4 and the buffers are 16-byte aligned, 4-byte words otherwise).  The outputs
+ *     must not overlap the inputs.  rec_sub is read as [n_bands, R, 2^T]: the entry cannot see how the buffer was sized, so it must be
+ *     called with the (T, R, n_bands) of the air_prune_score call that filled it; n_bands above 8, the most
+ *     air_canvas_unroll_bands returns, is refused.  T in 1..6, positive sizes, n_bands in 1..8 (AIR_E_SHAPE); where / where_loc / where_out 16-byte aligned, the
+ *     float64 buffers 8-byte aligned (AIR_E_ALIGN).
+ * air_prune_relabel: behind air_parse_objects in its given-counts form on the compacted rows, which labels rows by position.  One
+ *   wavefront per image; for j < n' = num_objects[r] clipped to 0..T:  score[j,r] = score_src[j,r],
+ *   obj_score[offsets[r] + j] = score_src[j,r], obj_step[offsets[r] + j] = kept_step[j,r].  Everything else keeps what
+ *   air_parse_objects wrote.  T in 1..6.
+ * Checks come before the launch: a refused call writes nothing.                                                                   */
+AIR_ENGINE_API int air_prune_score(const float *glimpse, const float *where, const float *presence, const float *obs, float mult,
+                    float std, int all_candidates, int T, int R, int H, int W, int h, int w, int n_bands, float *rec_sub,
+                    void *stream);
+AIR_ENGINE_API int air_prune_select(const float *what, const float *where, const float *glimpse, const float *score, const float *presence,
+                    const float *where_loc, float what_p_loc, float what_p_scale, float scale_p_loc, float scale_p_scale,
+                    float shift_p_loc, float shift_p_scale, const double *prior_f64, int normalize_prior, int all_candidates,
+                    const float *rec_sub, int n_bands, int T, int R, int A, int G, double *J_sub, int *best_mask,
+                    int *num_objects_out, int *kept_step, double *objective, double *objective_start, double *evidence,
+                    float *what_out, float *where_out, float *glimpse_out, float *score_out, void *stream);
+AIR_ENGINE_API int air_prune_relabel(const float *score_src, const int *kept_step, const int *num_objects, const int *offsets, int T,
+                    int R, float *score, float *obj_score, int *obj_step, void *stream);
+
 /* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
  * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
  * (AIR_E_SHAPE otherwise, and when R*H*W or R*(T+1)*(G+1) passes int32).  No floating-point atomics; float64 with contraction off
