@@ -165,8 +165,23 @@ def _prune_sums(out):
             bits(best & ~m0).double().sum(), gain.sum()]
 
 
+def _propose_kw(propose):
+    """keyword arguments of air.parse for propose=P | (P, rounds): the spec as a plain int / list, so that the record can be written"""
+    if propose is None:
+        return {}
+    return dict(propose=[int(v) for v in propose] if isinstance(propose, (tuple, list)) else int(propose))
+
+
+def _propose_sums(out):
+    """[objects of the result that came from a proposal, number of images whose count changed, sum of the objective gain] of a parse
+    behind residual proposals (an image whose gain is NaN or infinite adds 0; the callers divide by the number of all images)"""
+    import torch
+    gain = torch.nan_to_num(out["objective"] - out["objective_start"].double(), nan=0.0, posinf=0.0, neginf=0.0)
+    return [out["objects_proposed_kept"].double().sum(), (out["num_objects"] != out["num_objects_start"]).double().sum(), gain.sum()]
+
+
 def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time=True, particles=None, select="joint", refine=None,
-                      refine_lr=None, prune=None):
+                      refine_lr=None, prune=None, propose=None):
     """The deterministic parse (air.parse: the mode of q(n | x), latents at their posterior means) over `num_batches` batches from
     `data_fn`: map_num_step_acc (the count against the true one), the mean count_prob (q at the mode) and the mean number of
     objects per image.  particles=K: the best of K posterior particles under `select` instead (the count and count_prob are then
@@ -177,22 +192,26 @@ def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time
     record names N.  prune="present" | "all": that parse behind the subset search (air.parse(prune=...)), and count_changed (the share
     of images with num_objects != num_objects_start), objects_dropped and objects_added (means per image) and objective_gain (as
     above, of the subset search: objective - objective_start of the pruner; together with refine=N it is reported as
-    prune_objective_gain, objective_gain stays the refiner's); the record names the mode.  Prints / writes one line like
-    make_expr_logger."""
+    prune_objective_gain, objective_gain stays the refiner's); the record names the mode.  propose=P | (P, rounds): that parse behind
+    residual proposals (air.parse(propose=...); not together with prune), and objects_added_from_residual (objects of the result that
+    came from a proposal, mean per image), count_changed and objective_gain (of the proposer; propose_objective_gain next to
+    refine=N); the record names the spec.  Prints / writes one line like make_expr_logger."""
     import torch
     pk = {} if particles is None else dict(particles=int(particles), select=select)
     rk = _refine_kw(refine, refine_lr)
     qk = {} if prune is None else dict(prune=prune)
+    uk = _propose_kw(propose)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
         n = max(int(n), 1)
         start = time.time()
-        tot = torch.zeros(3 + (2 if pk else 0) + (2 if rk else 0) + (4 if qk else 0), dtype=torch.float64, device=air.obs.device)
+        tot = torch.zeros(3 + (2 if pk else 0) + (2 if rk else 0) + (4 if qk else 0) + (3 if uk else 0), dtype=torch.float64,
+                          device=air.obs.device)
         images = 0
         for _ in range(n):
             obs, nums = data_fn()
-            out = air.parse(obs, **pk, **rk, **qk)
+            out = air.parse(obs, **pk, **rk, **qk, **uk)
             gt = nums.sum(0).reshape(-1).to(torch.int64)
             cnt = out["num_objects"].to(torch.int64)
             sums = [(cnt == gt).double().sum(), out["count_prob"].double().sum(), cnt.double().sum()]
@@ -202,6 +221,8 @@ def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time
                 sums += _refine_sums(out)
             if qk:
                 sums += _prune_sums(out)
+            if uk:
+                sums += _propose_sums(out)
             tot += torch.stack(sums)
             images += int(cnt.numel())
         vals = (tot / images).tolist()
@@ -214,24 +235,29 @@ def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time
         if qk:
             acc.update(count_changed=vals[-4], objects_dropped=vals[-3], objects_added=vals[-2])
             acc["prune_objective_gain" if rk else "objective_gain"] = vals[-1]
+        if uk:
+            acc.update(objects_added_from_residual=vals[-3], count_changed=vals[-2])
+            acc["propose_objective_gain" if rk else "objective_gain"] = vals[-1]
         t = time.time() - start
         label = 'parse({}, {}) '.format(pk["particles"], select) if pk else 'parse '
         if rk:
             label = label[:-1] + '+refine({}) '.format(rk["refine"])
         if qk:
             label = label[:-1] + '+prune({}) '.format(prune)
+        if uk:
+            label = label[:-1] + '+propose({}) '.format(uk["propose"])
         msg = 'Step {}, Data {} '.format(itr, name) + label + ', '.join('{} = {:.4f}'.format(k, v) for k, v in acc.items())
         if measure_time:
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **pk, **rk, **qk, **acc)) + "\n"); writer.flush()
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **pk, **rk, **qk, **uk, **acc)) + "\n"); writer.flush()
         return acc
     return logger
 
 
 def make_parse_score_logger(air, data, num_batches, name, writer=None, thresholds=None, measure_time=True, particles=None,
-                            select="joint", refine=None, refine_lr=None, prune=None):
+                            select="joint", refine=None, refine_lr=None, prune=None, propose=None):
     """The deterministic parse scored against the generator's annotations on the device (air.score_parse, score.ParseScorer):
     `data` is an annotated dataset dict (imgs [N, H, W], boxes [N, G, 4], instances [N, H, W] int8 -- data.create_multi_mnist with
     return_annotations=True), walked in order from its start in `num_batches` batches of the model's size (fewer when the data
@@ -241,13 +267,15 @@ def make_parse_score_logger(air, data, num_batches, name, writer=None, threshold
     also reports best_particle_moved and ess as make_parse_logger does, and the record names K and the criterion.  refine=N: the
     refined parse is scored; the line also reports objective_gain and refine_moved as make_parse_logger does.  prune=...: the pruned
     parse is scored; the line also reports count_changed, objects_dropped, objects_added and objective_gain (prune_objective_gain
-    next to refine=N) as make_parse_logger does."""
+    next to refine=N) as make_parse_logger does.  propose=...: the parse behind residual proposals is scored; the line also reports
+    objects_added_from_residual, count_changed and objective_gain (propose_objective_gain next to refine=N) as make_parse_logger does."""
     import torch
     G = int(data["boxes"].shape[1])
     kw = {} if thresholds is None else dict(thresholds=tuple(thresholds))
     pk = {} if particles is None else dict(particles=int(particles), select=select)
     rk = _refine_kw(refine, refine_lr)
     qk = {} if prune is None else dict(prune=prune)
+    uk = _propose_kw(propose)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -257,21 +285,24 @@ def make_parse_score_logger(air, data, num_batches, name, writer=None, threshold
             raise ValueError("the annotated dataset holds fewer images than one batch of %d" % B)
         start = time.time()
         dev = air.obs.device
-        scorer = air.parse_scorer(G, **kw, **pk, **rk, **qk)
+        scorer = air.parse_scorer(G, **kw, **pk, **rk, **qk, **uk)
         scorer.reset()
         extra = torch.zeros(2, dtype=torch.float64, device=dev) if pk else None
         extra_r = torch.zeros(2, dtype=torch.float64, device=dev) if rk else None
         extra_q = torch.zeros(4, dtype=torch.float64, device=dev) if qk else None
+        extra_u = torch.zeros(3, dtype=torch.float64, device=dev) if uk else None
         for i in range(n):
             sl = slice(i * B, (i + 1) * B)
             air.score_parse(torch.as_tensor(data["imgs"][sl], dtype=torch.float32).to(dev), torch.as_tensor(data["instances"][sl]),
-                            torch.as_tensor(data["boxes"][sl]), **kw, **pk, **rk, **qk)
+                            torch.as_tensor(data["boxes"][sl]), **kw, **pk, **rk, **qk, **uk)
             if pk:
                 extra += torch.stack([(air.parsed["best_particle"] != 0).double().sum(), air.parsed["ess"].double().sum()])
             if rk:
                 extra_r += torch.stack(_refine_sums(air.parsed))
             if qk:
                 extra_q += torch.stack(_prune_sums(air.parsed))
+            if uk:
+                extra_u += torch.stack(_propose_sums(air.parsed))
         acc = scorer.summary()
         shown = ["count_acc", "map", "ap@%.2f" % scorer.thresholds_host[0], "fg_ari", "mean_best_overlap", "matched_box_iou"]
         if pk:
@@ -288,18 +319,26 @@ def make_parse_score_logger(air, data, num_batches, name, writer=None, threshold
             acc.update(count_changed=changed, objects_dropped=dropped, objects_added=added)
             acc[gain_key] = gain_q
             shown += ["count_changed", "objects_dropped", "objects_added", gain_key]
+        if uk:
+            added_u, changed_u, gain_u = (extra_u / (n * B)).tolist()
+            gain_key = "propose_objective_gain" if rk else "objective_gain"
+            acc.update(objects_added_from_residual=added_u, count_changed=changed_u)
+            acc[gain_key] = gain_u
+            shown += ["objects_added_from_residual", "count_changed", gain_key]
         t = time.time() - start
         label = 'parse score({}, {}) '.format(pk["particles"], select) if pk else 'parse score '
         if rk:
             label = label[:-1] + '+refine({}) '.format(rk["refine"])
         if qk:
             label = label[:-1] + '+prune({}) '.format(prune)
+        if uk:
+            label = label[:-1] + '+propose({}) '.format(uk["propose"])
         msg = 'Step {}, Data {} '.format(itr, name) + label + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **pk, **rk, **qk, **acc)) + "\n"); writer.flush()
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **pk, **rk, **qk, **uk, **acc)) + "\n"); writer.flush()
         return acc
     return logger
 

@@ -325,11 +325,16 @@ class AIRonMNIST(AIRModel):
             self._particle_parser = s
         return s
 
-    def _parser_for(self, particles, select, refine=None, refine_lr=None, prune=None):
+    def _parser_for(self, particles, select, refine=None, refine_lr=None, prune=None, propose=None):
+        if prune is not None and propose is not None:
+            raise ValueError("parse: prune together with propose is not supported: the search over the candidate pool already "
+                             "contains prune=\"all\"; pass one of them")
         n = self.obs.shape[0]
         parser = self.scene_parser(n) if particles is None else self.particle_parser(n, particles, select)
         if refine is not None:
             parser = self.parse_refiner(parser, refine, refine_lr)
+        if propose is not None:
+            return self.parse_proposer(parser, propose)
         return parser if prune is None else self.parse_pruner(parser, prune)
 
     MAX_PARSE_REFINERS = 4
@@ -383,7 +388,38 @@ class AIRonMNIST(AIRModel):
             cache.pop(next(iter(cache))).release_graphs()
         return r
 
-    def parse(self, obs=None, num_objects=None, particles=None, select="joint", refine=None, refine_lr=None, prune=None):
+    MAX_PARSE_PROPOSERS = 4
+
+    def parse_proposer(self, provider, propose=1):
+        """the ParseProposer behind parse(propose=...): one per (provider, proposals, rounds), bound to that scene parser, particle
+        parser or refiner (built and captured on first use; dropped when its provider was rebuilt or dropped, and the least recently
+        used one when more than MAX_PARSE_PROPOSERS are alive -- a scorer still bound to a dropped one keeps working, its proposer
+        then launches eagerly).  propose: P, or (P, rounds)."""
+        from .propose import ParseProposer
+        try:
+            spec = (int(propose), 1) if not isinstance(propose, (tuple, list)) else tuple(int(v) for v in propose)
+        except (TypeError, ValueError):
+            spec = ()
+        if len(spec) != 2 or isinstance(propose, bool):
+            raise ValueError("propose: the number of proposals per round, or (proposals, rounds), got %r" % (propose,))
+        cache = self.__dict__.setdefault("_parse_proposers", {})
+        alive = [getattr(self, "_scene_parser", None), getattr(self, "_particle_parser", None)]
+        alive += list(self.__dict__.get("_parse_refiners", {}).values())
+        for k in [k for k, r in cache.items() if not any(r.parser is a for a in alive)]:
+            cache.pop(k).release_graphs()
+        key = (id(provider),) + spec
+        r = cache.pop(key, None)
+        if r is None or r.parser is not provider:
+            if r is not None:
+                r.release_graphs()
+            r = ParseProposer(provider, spec[0], spec[1])
+            r.capture()
+        cache[key] = r                                             # most recently used last
+        while len(cache) > self.MAX_PARSE_PROPOSERS:
+            cache.pop(next(iter(cache))).release_graphs()
+        return r
+
+    def parse(self, obs=None, num_objects=None, particles=None, select="joint", refine=None, refine_lr=None, prune=None, propose=None):
         """Scene parse on the device.  particles=None: the deterministic parse (parse.SceneParser: its own engine at the mode of the
         inference network); particles=K: K posterior particles per image and the best one under `select` ("joint": the largest
         log p(x, z), "weight": the largest importance weight) kept (particle_parse.ParticleParser: its own engine at K * batch
@@ -398,25 +434,31 @@ class AIRonMNIST(AIRModel):
         S of the computed steps (prune.ParsePruner; max_steps <= 6) -- "present" can only remove objects of the parse, "all" may also
         switch on a step the presence chain left out; the result then describes the selected subset, compacted, and adds objective,
         objective_start (float64), objective_subsets, best_mask, kept_step, evidence, num_objects_start.  prune=None: the paths
-        above, untouched."""
+        above, untouched.  propose=P | (P, rounds): behind whichever of the paths above (not together with prune: the search over
+        the pool contains prune="all"), `rounds` rounds of P proposals from the residual image and the exact subset search over the
+        pool of max_steps + P <= 6 rows (propose.ParseProposer); the result has the pruner's keys -- kept_step now names start steps
+        (< max_steps) and proposals (max_steps + round * P + j) -- and adds objective_rounds, residual, residual_energy,
+        proposal_what / _where / _glimpse / _score, objects_proposed_kept.  propose=None: the paths above, untouched."""
         if particles is not None and num_objects is not None:
             raise ValueError("parse: num_objects together with particles is not supported (conditioning the sampled chain on a "
                              "count is out of scope); pass one of them")
         if obs is not None:
             self.obs = obs
-        s = self._parser_for(particles, select, refine, refine_lr, prune)
+        s = self._parser_for(particles, select, refine, refine_lr, prune, propose)
         self._sync_engine_switches()
         s.load_from(self._engine)                            # every time: the weights move
         # (the caller's stream is ordered after it)
         self.parsed = s.parse(self.obs, num_objects) if particles is None else s.parse(self.obs)
         return self.parsed
 
-    def parse_scorer(self, max_gt_objects, thresholds=None, particles=None, select="joint", refine=None, refine_lr=None, prune=None):
+    def parse_scorer(self, max_gt_objects, thresholds=None, particles=None, select="joint", refine=None, refine_lr=None, prune=None,
+                     propose=None):
         """the ParseScorer behind score_parse, bound to the parser of the current batch size that parse(particles=..., select=...)
         uses (built and captured on first use, rebuilt when the parser, the number of ground-truth slots or the thresholds change);
-        refine=N binds it to that parse's refiner instead, so the refined parse is what gets scored; prune=... to that parse's pruner"""
+        refine=N binds it to that parse's refiner instead, so the refined parse is what gets scored; prune=... to that parse's pruner,
+        propose=... to that parse's proposer"""
         from .score import DEFAULT_THRESHOLDS, ParseScorer
-        parser = self._parser_for(particles, select, refine, refine_lr, prune)
+        parser = self._parser_for(particles, select, refine, refine_lr, prune, propose)
         th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
         s = getattr(self, "_parse_scorer", None)
         if s is None or s.parser is not parser or s.G != int(max_gt_objects) or s.thresholds_host != th:
@@ -428,13 +470,13 @@ class AIRonMNIST(AIRModel):
         return s
 
     def score_parse(self, obs, gt_instances, gt_boxes, gt_count=None, thresholds=None, accumulate=True, particles=None,
-                    select="joint", refine=None, refine_lr=None, prune=None):
+                    select="joint", refine=None, refine_lr=None, prune=None, propose=None):
         """Parse `obs` (AIRonMNIST.parse, with `particles` / `select` as there), then score the parse against the ground truth on the device (score.ParseScorer.score lists
         the arguments and the returned device tensors).  gt_count=None: the number of rows of gt_boxes with width > 0.  The sums
         accumulate in `parse_scorer(...)`: its reset() starts a validation set, its summary() reads the figures back once."""
         import torch
-        self.parse(obs, particles=particles, select=select, refine=refine, refine_lr=refine_lr, prune=prune)
-        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds, particles, select, refine, refine_lr, prune)
+        self.parse(obs, particles=particles, select=select, refine=refine, refine_lr=refine_lr, prune=prune, propose=propose)
+        s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds, particles, select, refine, refine_lr, prune, propose)
         self.parse_scores = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores
 

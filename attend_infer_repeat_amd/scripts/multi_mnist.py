@@ -97,6 +97,12 @@ def main(argv=None):
                          "(AIRonMNIST.parse(prune=...), prune.ParsePruner) behind the parse, its particles and its refinement: "
                          "\"present\" can only remove objects, \"all\" may also switch on a step the presence chain left out; the log "
                          "record names the mode and adds count_changed, objects_dropped, objects_added and objective_gain")
+    ap.add_argument("--parse-propose", default=None, metavar="P[,ROUNDS]",
+                    help="--parse-eval and --parse-score propose P missed objects per round from the residual image behind the parse, its "
+                         "particles and its refinement, and search the pool of max_steps + P <= 6 rows for the largest log p(x, z) "
+                         "(AIRonMNIST.parse(propose=...), propose.ParseProposer), ROUNDS times (default 1); not together with "
+                         "--parse-prune; the log record names the spec and adds objects_added_from_residual, count_changed and "
+                         "objective_gain")
     ap.add_argument("--parse-refine-lr", default=None, metavar="A,B",
                     help="with --parse-refine: the Adam learning rates of the `what` and the `where` latents (default: refine.DEFAULT_LR)")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
@@ -120,6 +126,16 @@ def main(argv=None):
             refine_kw["refine_lr"] = lr
     if args.parse_prune is not None:
         refine_kw["prune"] = args.parse_prune
+    if args.parse_propose is not None:
+        if args.parse_prune is not None:
+            ap.error("--parse-propose and --parse-prune exclude each other: the search over the pool already contains --parse-prune all")
+        try:
+            spec = tuple(int(v) for v in args.parse_propose.split(","))
+        except ValueError:
+            spec = ()
+        if len(spec) not in (1, 2) or min(spec) < 1:
+            ap.error("--parse-propose needs P >= 1 or P,ROUNDS with ROUNDS >= 1, got %r" % args.parse_propose)
+        refine_kw["propose"] = spec[0] if len(spec) == 1 else spec
 
     learning_rate, n_steps, batch_size = args.learning_rate, 3, 64    # multi_mnist.py:24-25,37
     num_steps_prior = AttrDict(anneal='exp', init=1. - 1e-15, final=1e-7, steps_div=1e4, steps=1e5, hold_init=1e3)

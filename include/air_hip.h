@@ -700,6 +700,42 @@ AIR_ENGINE_API int air_prune_select(const float *what, const float *where, const
 AIR_ENGINE_API int air_prune_relabel(const float *score_src, const int *kept_step, const int *num_objects, const int *offsets, int T,
                     int R, float *score, float *obj_score, int *obj_step, void *stream);
 
+/* ---- proposing missed objects from the residual image behind a parse.  One round: air_propose_residual on the current rows, the
+ * forward plan at the mode on the residual (its steps 0 .. P-1 are the proposals), air_propose_pool, then air_prune_score /
+ * air_prune_select with T := C = T + P <= 6, all_candidates = 1, the pool's presence chain and padded prior, obs = the ORIGINAL image,
+ * then air_propose_source.  The first T rows of the compacted [C,R,.] outputs are the next round's current rows.  T, P: T in 1..6,
+ * P in 1..T, T + P <= 6.  n_b = the number of leading ones of presence[:, b], or num_objects_in[b] clipped to 0..T when that is given:
+ * with both passed the counts win and presence is not read (it may then be NULL); neither passed is AIR_E_NULL.  No atomics, one fixed summation order: the same bits run to run.  Checks come before the launch: a
+ * refused call writes nothing.
+ * air_propose_residual: canvas(p) = 0 + layer_t(p) for t = 0 .. n_b - 1 in step order, layer_t = st_write(glimpse_t, where_t) with the
+ *   per-pixel operations of air_parse_render (the same taps, the same bilinear form, contraction off: the bits of that entry's canvas
+ *   for the presence chain t < n_b);  d = obs_p - mult * canvas(p) in fp32;  res[R,H,W]: res_p = d > 0 ? min(d, clamp_hi) : 0 (a NaN
+ *   gives 0).  res_parts[n_bands,R] (optional): each row band's sum of res_p^2 (air_canvas_unroll_bands' banding; inside a band a
+ *   fixed order of the kernel's own), to be added in band order (air_sum_leading).  Nothing else is written.  One 256-thread
+ *   workgroup per (image, band).  AIR_E_SHAPE: T outside 1..6, non-positive sizes, n_bands != air_canvas_unroll_bands(R, H);
+ *   AIR_E_ALIGN: where not 16-byte aligned, or any other pointer (glimpse, presence, num_objects_in, obs, res, res_parts) not 4-byte
+ *   aligned;  AIR_E_UNSUPPORTED: the LDS carve (T bordered glimpses, the axis tables) above 160 KiB, as air_parse_render.
+ * air_propose_pool: one wavefront per image.  Current rows what[T,R,A], where[T,R,4], glimpse[T,R,G], score[T,R]; proposal rows = rows
+ *   0 .. P-1 of prop_what / prop_where / prop_glimpse / prop_score (time-major with R rows per step, as the engine leaves them).
+ *   Row j < T of pool_what / pool_where / pool_glimpse / pool_score [C,R,.] = current row j, row T + i = proposal row i: bit copies
+ *   (16-byte vectors where A resp. G is a multiple of 4 and the three buffers are 16-byte aligned, 4-byte words otherwise: the rule
+ *   of air_particle_select).  pool_presence[j,r] = j < n_b ? 1 : 0.  pool_source[j,r] (int32) = source_in[j,r] (j itself when
+ *   source_in is NULL: round 0) for j < T, T + round * P + (j - T) for the proposals.  pool_prior[C+1] (float64) = prior_f64[0..T]
+ *   followed by zeros (written by the wavefront of image 0): a subset of more than T rows has log pi = -inf, never beats the start
+ *   strictly, and the selected count stays <= T.  The pool must not overlap the inputs.  AIR_E_ALIGN: any pointer not 4-byte aligned,
+ *   prior_f64 / pool_prior not 8-byte aligned (16-byte alignment only selects the vector copies).
+ * air_propose_source: source_out[j,r] = pool_source[kept_step[j,r], r] for j < C (kept_step as air_prune_select wrote it for T := C; a
+ *   value outside 0 .. C-1 is clipped).  C in 1..6.  A launch of its own: it runs behind air_prune_select, the pool in front.       */
+AIR_ENGINE_API int air_propose_residual(const float *glimpse, const float *where, const float *presence, const int *num_objects_in,
+                    const float *obs, float mult, float clamp_hi, int T, int R, int H, int W, int h, int w, int n_bands,
+                    float *res, float *res_parts, void *stream);
+AIR_ENGINE_API int air_propose_pool(const float *what, const float *where, const float *glimpse, const float *score, const float *presence,
+                    const int *num_objects_in, const int *source_in, const float *prop_what, const float *prop_where,
+                    const float *prop_glimpse, const float *prop_score, const double *prior_f64, int round, int T, int P, int R,
+                    int A, int G, float *pool_what, float *pool_where, float *pool_glimpse, float *pool_score,
+                    float *pool_presence, int *pool_source, double *pool_prior, void *stream);
+AIR_ENGINE_API int air_propose_source(const int *pool_source, const int *kept_step, int C, int R, int *source_out, void *stream);
+
 /* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
  * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
  * (AIR_E_SHAPE otherwise, and when R*H*W or R*(T+1)*(G+1) passes int32).  No floating-point atomics; float64 with contraction off
