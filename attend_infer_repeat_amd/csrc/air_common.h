@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <mutex>
 #include "../../include/air_hip.h"
 
@@ -9,6 +10,25 @@
 
 #define AIR_REQUIRE(cond, code) do { if (!(cond)) return (code); } while (0)
 #define AIR_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
+
+// ---- tile-form rules of the latency-regime GEMM launches that more than one source file has to state (a problem's product must not
+// depend on which launch carries it: gemm_kernels.hip decides the body of air_gemm_grouped with them, and the launches that fold a
+// product into another kernel -- air_gemm_grouped_gather, air_lstm_first_step_fwd -- take only what that body would have run) ---------
+static inline long air_gemm_wide_min_tiles() {
+    static const long wide_min = getenv("AIR_GEMM_WIDE_MIN_TILES") ? atol(getenv("AIR_GEMM_WIDE_MIN_TILES")) : 1000;
+    return wide_min;
+}
+// tile shape for a whole group: 16x16 tiles (more, shorter-lived workgroups) while the group is far from filling the chip, 32x32 tiles
+// once it holds thousands of them (less operand re-read, fewer workgroup rounds)
+static inline int air_gemm_latency_tile(long tiles16) { return tiles16 > 1536 ? 32 : 16; }
+// long K on a handful of tiles: 16 waves split K inside the workgroup (per problem; a group needs it of every problem, and <= 1024 tiles)
+static inline bool air_gemm_long_k(int M, int N, int K) { return K >= 512 && K >= 8 * (M < N ? M : N); }
+// a LONE problem [M, N, K] that air_gemm_grouped runs on the 4-wave 16x16 body whatever its layout and alignment: too few tiles for
+// the wide-tile regime and for 32x32 tiles, and not the long-K split
+static inline bool air_gemm_lone_on_tile16_kw4(int M, int N, int K) {
+    const long t = (long)((M + 15) / 16) * ((N + 15) / 16);
+    return t <= air_gemm_wide_min_tiles() && air_gemm_latency_tile(t) == 16 && !air_gemm_long_k(M, N, K);
+}
 
 static inline hipStream_t air_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline bool air_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -1469,12 +1469,12 @@ static long group_tiles16(const AirGemmDesc *descs, int count, unsigned skip_mas
 }
 // tile shape for the whole group: 16x16 tiles (more, shorter-lived workgroups) while the group is far from filling
 // the chip, 32x32 tiles once it holds thousands of them (less operand re-read, fewer workgroup rounds)
-static inline int latency_tile(long tiles16) { return tiles16 > 1536 ? 32 : 16; }
+static inline int latency_tile(long tiles16) { return air_gemm_latency_tile(tiles16); }
 // long K on a handful of tiles (the BPTT products, 64x256x1024): 16 waves split K inside the workgroup, so every wave
 // still needs only one or two memory round trips and no second (split-K epilogue) launch is paid
 static bool group_long_k(const AirGemmDesc *descs, int count, long tiles16) {
     bool long_k = tiles16 <= 1024;
-    for (int i = 0; i < count; ++i) long_k = long_k && descs[i].K >= 512 && descs[i].K >= 8 * (descs[i].M < descs[i].N ? descs[i].M : descs[i].N);
+    for (int i = 0; i < count; ++i) long_k = long_k && air_gemm_long_k(descs[i].M, descs[i].N, descs[i].K);
     return long_k;
 }
 // one precision per launch: problem d against the launch's (bf), and a whole group against its first problem's
@@ -1491,9 +1491,12 @@ static int group_precision(const AirGemmDesc *descs, int count, bool *bf) {
 }
 
 // ---- the wide-tile (throughput) regime of a group of at most AIR_GEMM_GROUP_MAX problems ---------------------------------------
-static long wide_min_tiles() {
-    static const long wide_min = getenv("AIR_GEMM_WIDE_MIN_TILES") ? atol(getenv("AIR_GEMM_WIDE_MIN_TILES")) : 1000;
-    return wide_min;
+static long wide_min_tiles() { return air_gemm_wide_min_tiles(); }
+// A group air_gemm_grouped is SURE to run on the 16-wave K-split body, whatever its layouts and alignment: group_long_k, and too few
+// tiles for the wide-tile regime, which air_gemm_grouped tests first (a larger long-K group stays on the K split only where
+// wide_group_eligible turns it down for its layout or alignment: the launches that fold into that body do not take those).
+static bool group_on_long_k_body(const AirGemmDesc *descs, int count, long tiles16) {
+    return tiles16 <= wide_min_tiles() && group_long_k(descs, count, tiles16);
 }
 // The full rule (air_gemm_grouped): the wide-tile kernels (every operand load 16 bytes per lane) when the whole group has one
 // operand layout and every problem meets the alignment the interleaved loads need.  *min_k = the shortest K, *nt_short = a dX
@@ -1615,6 +1618,12 @@ static int launch_grouped_sk(const AirGemmDesc *descs, int count, unsigned sk_ma
 // dataset through the feeder's index instead; the problems of g->copy_mask write what they read into g->obs (together they must
 // cover every column once); g->idx_out receives the indices.  16x16 tiles, 16 waves splitting K (the latency-regime form of these
 // long-K products).  Returns AIR_E_UNSUPPORTED for anything else: the caller then plans air_batch_gather + air_gemm_grouped.
+// The launch has ONE body, the 16-wave K split, so it takes only groups air_gemm_grouped itself runs on that body: group_on_long_k_body
+// below.  (Until the kernel-level tests of the folded launches it asked for K >= 512 and at most 1024 tiles only.  Without
+// K >= 8 min(M, N) a group such as M = 128, N = 256, K = 512 ran on 16 waves here and on the 4-wave body in the unfolded plan; and
+// air_gemm_grouped tests the wide-tile regime BEFORE the long-K split, so an aligned NN group of wide_min_tiles() + 1 ... 1024 tiles
+// such as 64 x 4096 x 2500 ran on 16 waves here and on gemm_wide_kernel there -- other partial sums, other bits, against the rule
+// stated at shortk_eligible.  No shipped configuration has such a first layer; tests/test_fold_kernels.py keeps the shapes as declines.)
 extern "C" int air_gemm_grouped_gather_fits(const AirGemmDesc *descs, int count, const AirBatchGather *g) {
     if (!descs || !g || count < 1 || count > AIR_GEMM_GROUP_MAX) return 0;
     if (!g->dataset || !g->obs || !g->seed_dev || !g->step_dev || g->n_items <= 0 || g->item_floats <= 0 || g->B <= 0) return 0;
@@ -1625,10 +1634,9 @@ extern "C" int air_gemm_grouped_gather_fits(const AirGemmDesc *descs, int count,
         if (d.ta || d.A2 || d.C16 || d.precision != AIR_PREC_F32 || d.M != g->B || d.lda != g->item_floats) return 0;
         const long off = (const float *)d.A - (const float *)g->obs;
         if (off < 0 || off + d.K > g->item_floats || off % 4) return 0;
-        if (d.K < 512) return 0;
         tiles16 += (long)air_cdiv(d.M, 16) * air_cdiv(d.N, 16);
     }
-    return tiles16 <= 1024 ? 1 : 0;
+    return group_on_long_k_body(descs, count, tiles16) ? 1 : 0;
 }
 extern "C" int air_gemm_grouped_gather(const AirGemmDesc *descs, int count, const AirBatchGather *g, void *stream) {
     AIR_REQUIRE(descs && g, AIR_E_NULL);

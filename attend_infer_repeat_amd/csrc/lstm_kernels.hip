@@ -1028,7 +1028,8 @@ extern "C" int air_lstm_step_fwd_prologue(const float *h0, const float *c0, cons
 }
 
 // air_lstm_step_fwd_prologue with the hoisted input product x . W_x + b folded in (lstm_fwd_first_kernel): latency regime only --
-// AIR_E_UNSUPPORTED beyond 512 tiles of (batch, hidden), where the caller keeps the gx launch and the wide-tile first step.
+// AIR_E_UNSUPPORTED beyond 512 tiles of (batch, hidden) and where the gx product alone would leave the 4-wave 16x16 body: the caller
+// keeps the gx launch and the first step with the prologue there.
 extern "C" int air_lstm_first_step_fwd(const float *x, int ldx, int E, const float *w_x, const float *b_gates, const float *h0,
                                        const float *c0, const float *w_h, int ldw, float *gx_out, int ldgx, float *h, float *c,
                                        float *gate_act, int M, int Hd, float forget_bias, int precision, float *normal,
@@ -1041,6 +1042,11 @@ extern "C" int air_lstm_first_step_fwd(const float *x, int ldx, int E, const flo
     AIR_REQUIRE((n_normal == 0 || normal) && (n_uniform == 0 || uniform), AIR_E_NULL);
     AIR_REQUIRE(T > 0 && anneal_type >= 0 && anneal_type <= 2 && E > 0 && ldx >= E, AIR_E_SHAPE);
     AIR_REQUIRE(air_cdiv(M, 16) * air_cdiv(Hd, 16) <= 512, AIR_E_UNSUPPORTED);
+    // The kernel repeats the K order of the 4-wave 16x16 body, so it takes the shapes whose gx product [M, 4Hd, E] air_gemm_grouped runs
+    // on that body as a launch of its own.  Beyond (more than wide_min_tiles() tiles of gx: the wide-tile kernels or 32x32 tiles; a long
+    // K: the 16-wave split) the two launches it replaces give other bits -- found at M = 512, Hd = 256, E = 52 with bf16 operands, where
+    // 22 358 of 526 336 elements of gx differed -- and the caller keeps them.
+    AIR_REQUIRE(air_gemm_lone_on_tile16_kw4(M, 4 * Hd, E), AIR_E_UNSUPPORTED);
     LstmFwdArgs g;
     int st = lstm_fwd_fill(g, h0, 0, c0, 0, w_h, ldw, gx_out, ldgx, h, c, gate_act, M, Hd, forget_bias, precision);
     if (st) return st;

@@ -98,7 +98,10 @@ class _PlanBuilder:
         # (air_lstm_first_step_fwd: same sums, same order, one dependent launch fewer).  Not when the first encoder layer is the
         # only one (its K-split halves are reduced by the gx product's A-prologue) and not beyond the fused-step tile count.
         # (latency regime only: in the throughput regime the gx product keeps its wide-tile launch)
+        # ... and not where the gx product alone would leave the 4-wave 16x16 body (a batch of 256 or more at Hd = 256: the wide-tile
+        # kernels), whose K order the first step repeats: the launch declines those shapes (gemm_groups.first_step_fits).
         self.fold_gx = (e.enc.n > 1 and not self.throughput and lstm_tiles <= int(_env("AIR_FUSE_LSTM_TILES", "512"))
+                        and G.first_step_fits(B, Hd, self.E, int(_env("AIR_GEMM_WIDE_MIN_TILES", "1000")))
                         and _env("AIR_FOLD_GX", "1") == "1")
         # Recurrent product + gate math in ONE launch per step while the chain is latency bound (it is the only truly
         # sequential part of the step); at large batch the 32x32-tile GEMM + a pointwise pass re-reads less (measured:
@@ -849,7 +852,9 @@ class _PlanBuilder:
             # When the step opens with the products over the pixels of obs (latency regime: the K-split halves of the input
             # encoder's and the baseline's first layers), the gather is folded into their A-operand load -- row m is read from item
             # idx_m of the dataset and the first column of tiles writes it to `obs` for every later reader -- instead of being a
-            # dependent launch of its own (air_gemm_grouped_gather; AIR_FOLD_GATHER=0: the two launches).  Bit-identical either way.
+            # dependent launch of its own (air_gemm_grouped_gather; AIR_FOLD_GATHER=0: the two launches).  Bit-identical either way:
+            # the fits rule takes only groups air_gemm_grouped is sure to run on the gather's 16-wave K-split body (group_long_k below
+            # the wide-tile regime: gemm_kernels.hip group_on_long_k_body).
             # the problems that write obs: one per distinct (column offset, K) -- together they must tile [0, P)
             seen, mask = {}, 0
             for i, key in enumerate(self.opening):

@@ -6,8 +6,11 @@ Three policies live here:
   plan_launch          the rule of every grouped launch of the forward and the backward;
   deferred_dw_groups   the weight gradients the throughput regime forms at the end of the backward;
   wide_form / shortk_mixed / tensors_read / foldable   what the folded closing update (engine_plan._fold_closing_update) must know
-                       of the library's dispatch and of the flat buffers before it folds an update into a grouped launch.
-The predicates restate rules of the library (csrc/gemm_kernels.hip); each names the function it mirrors."""
+                       of the library's dispatch and of the flat buffers before it folds an update into a grouped launch;
+  latency_tile / group_long_k / on_long_k_body / shortk_eligible / shortk_workgroups / latency_form / gather_fits / first_step_fits /
+  lstm_fwd_wide        the tile-form rules of the latency-regime grouped launches and of the LSTM step
+                       (tests/test_fold_cases_host.py holds every kernel-level case against them).
+The predicates restate rules of the library (csrc/gemm_kernels.hip, csrc/lstm_kernels.hip); each names the function it mirrors."""
 from . import _lib
 
 GROUPED, SPLITK = "grouped", "splitk"      # kinds of plan_launch: air_gemm_grouped / the split-K single-GEMM entry (air_gemm, air_gemm_bf16)
@@ -112,15 +115,106 @@ def wide_form(descs, wide_min_tiles):
             and min(d.K for d in descs) >= 256)
 
 
-def shortk_mixed(descs, enabled, min_m):
-    """... and a group that MIXES a short-K streaming weight gradient (gemm_kernels.hip shortk_eligible: fp32 TN, K <= 64 in whole
-    chunks, N a multiple of 64 up to 256, >= AIR_GEMM_SHORTK_MIN_M rows, no epilogue) with tile problems: such a problem keeps
-    the product of the streaming body in every plan, and the folded launch takes it only when all its problems are of that kind"""
+def shortk_eligible(d, min_m):
+    """gemm_kernels.hip shortk_eligible: what the streaming body takes -- an fp32 TN weight gradient with no epilogue, K in
+    {16, 32, 48, 64}, N a multiple of 64 up to 256, at least AIR_GEMM_SHORTK_MIN_M (`min_m`) output rows"""
+    return bool(is_weight_gradient(d) and d.precision == 0 and 16 <= d.K <= 64 and d.K % 16 == 0 and 64 <= d.N <= 256 and d.N % 64 == 0
+                and d.M >= min_m and d.epilogue == 0 and d.beta == 0.0 and not d.bias and not d.A2 and not d.C16)
+
+
+def shortk_workgroups(M, cap=384):
+    """gemm_kernels.hip shortk_workgroups: one workgroup per 16-row slab up to AIR_GEMM_SHORTK_WGS (`cap`); beyond, the slabs go round"""
+    return min((M + 15) // 16, max(cap, 1))
+
+
+def shortk_mask(descs, enabled, min_m):
+    """gemm_kernels.hip shortk_mask: the problems of a plain fp32 group that go to the streaming body (0: none, or not such a group)"""
     if not enabled or any(d.A2 or d.C16 or d.precision != 0 for d in descs):
+        return 0
+    return sum(1 << i for i, d in enumerate(descs) if shortk_eligible(d, min_m))
+
+
+def shortk_mixed(descs, enabled, min_m):
+    """... and a group that MIXES a short-K streaming weight gradient (shortk_eligible) with tile problems: such a problem keeps
+    the product of the streaming body in every plan, and the folded launch takes it only when all its problems are of that kind"""
+    mask = shortk_mask(descs, enabled, min_m)
+    return mask != 0 and mask != (1 << len(descs)) - 1
+
+
+def latency_tile(group_tiles16):
+    """gemm_kernels.hip latency_tile: 16x16 tiles while the group is far from filling the chip, 32x32 beyond 1536 of them"""
+    return 32 if group_tiles16 > 1536 else 16
+
+
+def long_k(M, N, K):
+    """air_common.h air_gemm_long_k: per problem, K >= 512 and >= 8 min(M, N)"""
+    return K >= 512 and K >= 8 * min(M, N)
+
+
+def group_long_k(descs):
+    """gemm_kernels.hip group_long_k: the 16-wave K-split body -- at most 1024 tiles, every problem long_k"""
+    return sum(tiles16(d) for d in descs) <= 1024 and all(long_k(d.M, d.N, d.K) for d in descs)
+
+
+def on_long_k_body(descs, wide_min_tiles=1000):
+    """gemm_kernels.hip group_on_long_k_body: a group air_gemm_grouped is sure to run on the 16-wave K-split body -- group_long_k, and
+    too few tiles for the wide-tile regime, which air_gemm_grouped tests first"""
+    return sum(tiles16(d) for d in descs) <= wide_min_tiles and group_long_k(descs)
+
+
+def lone_on_tile16_kw4(M, N, K, wide_min_tiles=1000):
+    """air_common.h air_gemm_lone_on_tile16_kw4: a lone problem air_gemm_grouped runs on the 4-wave 16x16 body whatever its layout and
+    alignment -- too few tiles for the wide-tile regime and for 32x32 tiles, and not the long-K split"""
+    t = ((M + 15) // 16) * ((N + 15) // 16)
+    return t <= wide_min_tiles and latency_tile(t) == 16 and not long_k(M, N, K)
+
+
+def first_step_fits(M, Hd, E, wide_min_tiles=1000, max_tiles=512):
+    """lstm_kernels.hip air_lstm_first_step_fwd: at most 512 tiles of (batch, hidden), and a gx product [M, 4Hd, E] that as a launch of
+    its own runs on the 4-wave 16x16 body, whose K order the first step repeats (bit-identical either way, or not folded)"""
+    return ((M + 15) // 16) * ((Hd + 15) // 16) <= max_tiles and lone_on_tile16_kw4(M, 4 * Hd, E, wide_min_tiles)
+
+
+FIRST_STEP_MAX_TILES = 512      # air_lstm_first_step_fwd, and the edge between lstm_fwd_fused_kernel and lstm_fwd_wide_kernel
+
+
+def lstm_fwd_wide(M, Hd, ldw=None, ldh=None, w_h=0, h_prev=0):
+    """lstm_kernels.hip lstm_fwd_launch: the 512-thread lstm_fwd_wide_kernel (else lstm_fwd_fused_kernel) -- more than 512 tiles of
+    (batch, hidden), Hd a multiple of 64, rows of W_h [Hd, ldw = 4 Hd] and of h_prev [M, ldh = Hd; 0: one broadcast row] whole
+    float4s, both at 16-byte aligned byte addresses `w_h` / `h_prev`"""
+    ldw, ldh = 4 * Hd if ldw is None else ldw, Hd if ldh is None else ldh
+    return bool(((M + 15) // 16) * ((Hd + 15) // 16) > FIRST_STEP_MAX_TILES and Hd % 64 == 0 and ldw % 4 == 0 and ldh % 4 == 0
+                and w_h % 16 == 0 and h_prev % 16 == 0)
+
+
+GAUSS_FOLD_MAX_TILES = 1000     # air_gemm_grouped_gauss_bwd
+
+
+def latency_form(descs, enabled=True, min_m=4096):
+    """the tile form a latency-regime grouped launch (air_gemm_grouped below the wide-tile regime, air_gemm_grouped_opt,
+    air_gemm_grouped_gauss_bwd) runs `descs` on: "shortk" (every problem on the streaming body), "shortk_mixed", or (MT, NT, KW) =
+    (1, 1, 16) / (1, 1, 4) / (2, 2, 4), the template arguments of gemm_body"""
+    mask = shortk_mask(descs, enabled, min_m)
+    if mask:
+        return "shortk" if mask == (1 << len(descs)) - 1 else "shortk_mixed"
+    if group_long_k(descs):
+        return (1, 1, 16)
+    return (1, 1, 4) if latency_tile(sum(tiles16(d) for d in descs)) == 16 else (2, 2, 4)
+
+
+def gather_fits(descs, obs, item_floats, B, dataset=0, wide_min_tiles=1000):
+    """gemm_kernels.hip air_gemm_grouped_gather_fits: every A a 16-byte aligned column window of obs[B, item_floats] of an fp32 NN / NT
+    problem over all B rows, and the group one air_gemm_grouped is sure to run on the 16-wave K-split body (on_long_k_body) -- the body
+    the gather launch always runs, so that the product does not depend on which launch carries it"""
+    if not (1 <= len(descs) <= 8) or item_floats <= 0 or item_floats % 4 or B <= 0 or obs % 16 or dataset % 16:
         return False
-    el = [bool(is_weight_gradient(d) and 16 <= d.K <= 64 and d.K % 16 == 0 and 64 <= d.N <= 256 and d.N % 64 == 0
-               and d.M >= min_m and d.epilogue == 0 and d.beta == 0.0 and not d.bias) for d in descs]
-    return any(el) and not all(el)
+    for d in descs:
+        off = (int(d.A) - obs) // 4
+        if d.ta or d.A2 or d.C16 or d.precision != 0 or d.M != B or d.lda != item_floats:
+            return False
+        if (int(d.A) - obs) % 4 or off < 0 or off + d.K > item_floats or off % 4:
+            return False
+    return on_long_k_body(descs, wide_min_tiles)
 
 
 def tensors_read(descs, p0, p1, spans):

@@ -167,11 +167,9 @@ def gemm(A, B, ta=False, tb=False, bias=None, epilogue=EPI_NONE, aux=None, beta=
     return (out, cs) if colsum else out
 
 
-def gemm_grouped(problems, precision=0):
-    """Several independent GEMMs in one launch (air_gemm_grouped).  problems: dicts with A, B and optional ta, tb, bias,
-    epilogue, aux, beta, out, colsum (bool); a single problem may carry the K-split consumer prologue A2, a_bias, a_elu, a_out
-    (a = act(A + A2 + a_bias), see AirGemmDesc).  bf16 data path (precision=1): A16 / B16 = bf16 mirrors of A / B (same shape
-    and strides in elements), C16 = bf16 tensor that receives bf16(C).  Returns [(C, colsum|None)]."""
+def _gemm_descs(problems, precision, name):
+    """problem dicts (see gemm_grouped) -> (AirGemmDesc array, [(C, colsum|None)], the tensors the array points into).  `colsum` may be
+    True (allocated here) or a tensor to write into (a slice of a flat gradient buffer)."""
     descs, outs, keep = [], [], []
     for pr in problems:
         A, B = pr["A"], pr["B"]
@@ -183,7 +181,9 @@ def gemm_grouped(problems, precision=0):
         if out is None:
             out = torch.empty((M, N), dtype=torch.float32, device=A.device)
         aux, bias = pr.get("aux"), pr.get("bias")
-        cs = torch.empty((N,), dtype=torch.float32, device=A.device) if pr.get("colsum") else None
+        cs = pr.get("colsum")
+        if not torch.is_tensor(cs):
+            cs = torch.empty((N,), dtype=torch.float32, device=A.device) if cs else None
         ld = lambda t: t.stride(0) if t.shape[0] > 1 else t.shape[1]
         d = _lib.AirGemmDesc(int(ta), int(tb), M, N, K, A.data_ptr(), ld(A), B.data_ptr(), ld(B), out.data_ptr(), ld(out),
                              bias.data_ptr() if bias is not None else None, int(pr.get("epilogue", EPI_NONE)),
@@ -196,11 +196,19 @@ def gemm_grouped(problems, precision=0):
             t = pr.get(fld)
             if t is not None:
                 if t.dtype != torch.bfloat16 or not t.is_cuda:
-                    raise _lib.AirHipError(f"gemm_grouped: {fld} must be a bfloat16 CUDA tensor")
+                    raise _lib.AirHipError(f"{name}: {fld} must be a bfloat16 CUDA tensor")
                 setattr(d, fld, t.data_ptr())
         descs.append(d); outs.append((out, cs)); keep.append((A, B, aux, bias, pr.get("A16"), pr.get("B16"), pr.get("C16")))
-    arr = (_lib.AirGemmDesc * len(descs))(*descs)
-    _lib.check(lib().air_gemm_grouped(arr, len(descs), _stream()), "air_gemm_grouped")
+    return (_lib.AirGemmDesc * len(descs))(*descs), outs, keep
+
+
+def gemm_grouped(problems, precision=0):
+    """Several independent GEMMs in one launch (air_gemm_grouped).  problems: dicts with A, B and optional ta, tb, bias,
+    epilogue, aux, beta, out, colsum (bool); a single problem may carry the K-split consumer prologue A2, a_bias, a_elu, a_out
+    (a = act(A + A2 + a_bias), see AirGemmDesc).  bf16 data path (precision=1): A16 / B16 = bf16 mirrors of A / B (same shape
+    and strides in elements), C16 = bf16 tensor that receives bf16(C).  Returns [(C, colsum|None)]."""
+    arr, outs, keep = _gemm_descs(problems, precision, "gemm_grouped")
+    _lib.check(lib().air_gemm_grouped(arr, len(outs), _stream()), "air_gemm_grouped")
     return outs
 
 
@@ -839,3 +847,303 @@ def colsum(x):
     out = torch.empty((N,), dtype=torch.float32, device=x.device)
     _lib.check(lib().air_colsum(_p(x), x.stride(0) if M > 1 else N, _p(out), M, N, _stream()), "air_colsum")
     return out
+
+
+# ---- the folded launches of the train step (tests/test_fold_kernels.py calls each on its own) --------------------------------------
+E_UNSUPPORTED = -5                                                      # AIR_E_UNSUPPORTED: a launch declines a shape it has no form for
+
+
+def _status(st, what):
+    """0, or AIR_E_UNSUPPORTED handed back as the integer it is (a decline is an answer, the caller plans the unfused launches);
+    anything else raises"""
+    if st != E_UNSUPPORTED:
+        _lib.check(st, what)
+    return int(st)
+
+
+def _i64(t, name, n=1):
+    if t is None:
+        return None
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype in (torch.int64, getattr(torch, "uint64", torch.int64)) and t.numel() >= n):
+        raise _lib.AirHipError(f"{name}: expected an int64 CUDA tensor of at least {n} element(s)")
+    return t
+
+
+def step_epilogue_(p, g, ms, mg, mom, n_model, lr_dev, lr_mult_tail=1.0, decay=0.9, momentum=0.9, eps=1e-10, grad_scale=1.0,
+                   global_step_dev=None, rng_state_dev=None, rng_increment=0):
+    """air_step_epilogue over p.numel() elements, in place (elements >= n_model use lr * lr_mult_tail); the counters advance when given"""
+    for t, nm in ((p, "p"), (g, "g"), (ms, "ms"), (mg, "mg"), (mom, "mom"), (lr_dev, "lr_dev")):
+        _f32(t, nm)
+    _lib.check(lib().air_step_epilogue(_p(p), _p(g), _p(ms), _p(mg), _p(mom), ctypes.c_size_t(int(n_model)), ctypes.c_size_t(p.numel()),
+                                       _p(lr_dev), float(lr_mult_tail), float(decay), float(momentum), float(eps), float(grad_scale),
+                                       _p(_i64(global_step_dev, "global_step_dev")), _p(_i64(rng_state_dev, "rng_state_dev", 2)),
+                                       ctypes.c_uint64(int(rng_increment)), _stream()), "air_step_epilogue")
+
+
+def opt_fold(p, g, ms, mg, mom, n_model, lr_dev, fold_mask, ranges=(), lr_mult_tail=1.0, decay=0.9, momentum=0.9, eps=1e-10,
+             grad_scale=1.0, global_step_dev=None, rng_state_dev=None, rng_increment=0):
+    """AirOptFold over the flat buffers: the problems of fold_mask update where they write, `ranges` = up to four (lo, hi) rider slices"""
+    for t, nm in ((p, "p"), (g, "g"), (ms, "ms"), (mg, "mg"), (mom, "mom"), (lr_dev, "lr_dev")):
+        _f32(t, nm)
+    if len(ranges) > 4:
+        raise _lib.AirHipError("opt_fold: at most four rider ranges")
+    lo = (ctypes.c_size_t * 4)(*([int(r[0]) for r in ranges] + [0] * (4 - len(ranges))))
+    hi = (ctypes.c_size_t * 4)(*([int(r[1]) for r in ranges] + [0] * (4 - len(ranges))))
+    gs, rs = _i64(global_step_dev, "global_step_dev"), _i64(rng_state_dev, "rng_state_dev", 2)
+    return _lib.AirOptFold(p.data_ptr(), g.data_ptr(), ms.data_ptr(), mg.data_ptr(), mom.data_ptr(), int(n_model), lr_dev.data_ptr(),
+                           float(lr_mult_tail), float(decay), float(momentum), float(eps), float(grad_scale), int(fold_mask),
+                           len(ranges), lo, hi, gs.data_ptr() if gs is not None else None, rs.data_ptr() if rs is not None else None,
+                           int(rng_increment))
+
+
+def gemm_grouped_opt(problems, opt, precision=0):
+    """air_gemm_grouped_opt: problems as for gemm_grouped (a folded problem's `out` / `colsum` are views of the flat gradient buffer),
+    opt = opt_fold(...) -> (status, [(C, colsum|None)]); status is 0 or AIR_E_UNSUPPORTED (nothing launched)"""
+    arr, outs, keep = _gemm_descs(problems, precision, "gemm_grouped_opt")
+    st = _status(lib().air_gemm_grouped_opt(arr, len(outs), ctypes.byref(opt), _stream()), "air_gemm_grouped_opt")
+    return st, outs
+
+
+def gemm_grouped_gauss_bwd(problems, problem, pre, eps, raw_offset, prior2, loc, scale, dkl_row, dkl_scale, dpre, guard_eps=0.0,
+                           precision=0, nvil=None, kl_parts=None):
+    """air_gemm_grouped_gauss_bwd: problem `problem` of the group is dsample[M, D]; pre[M, >= 2D] and dpre[M, >= 2D] may be row views
+    (ld_pre, ld_dpre), eps / loc / scale [M, D], dkl_row[M] | None.  nvil: None, or dict(imp_parts[n_parts, B], baseline[B], logp[B],
+    ema = the four-float block | None).  kl_parts[n_kl_parts, M] | None.
+    -> (status, [(C, colsum|None)], dict(out[4], dlogp[B], dbaseline[B], imp_sum[B], kl_row[M]) of the riders that ran, NaN-primed)"""
+    arr, outs, keep = _gemm_descs(problems, precision, "gemm_grouped_gauss_bwd")
+    ld_pre, ld_dpre = _mat(pre, "pre"), _mat(dpre, "dpre")
+    eps = _f32(eps, "eps", 2); loc = _f32(loc, "loc", 2); scale = _f32(scale, "scale", 2); dkl_row = _f32(dkl_row, "dkl_row", 1)
+    M, D = eps.shape
+    _tb((M, D), loc=loc, scale=scale)
+    if pre.shape[0] != M or dpre.shape[0] != M or pre.shape[1] < 2 * D or dpre.shape[1] < 2 * D or (dkl_row is not None and dkl_row.shape[0] != M):
+        raise _lib.AirHipError(f"gemm_grouped_gauss_bwd: pre {tuple(pre.shape)}, dpre {tuple(dpre.shape)}, eps {tuple(eps.shape)}")
+    epi = _lib.AirGaussBwdEpi(int(problem), pre.data_ptr(), ld_pre, eps.data_ptr(), float(raw_offset), float(prior2[0]), float(prior2[1]),
+                              loc.data_ptr(), scale.data_ptr(), dkl_row.data_ptr() if dkl_row is not None else None, float(dkl_scale),
+                              dpre.data_ptr(), ld_dpre, D, float(guard_eps))
+    dev = eps.device
+    riders, nv, B = {}, (None, 0, None, None, None, None, None, None), 0
+    ema = None
+    if nvil is not None:
+        parts = _f32(nvil["imp_parts"], "imp_parts", 2); base = _f32(nvil["baseline"], "baseline", 1); logp = _f32(nvil["logp"], "logp", 1)
+        ema = _f32(nvil.get("ema"), "ema", 1)
+        n_parts, B = parts.shape
+        if base.shape[0] != B or logp.shape[0] != B or (ema is not None and ema.numel() != 4):
+            raise _lib.AirHipError("gemm_grouped_gauss_bwd: baseline / logp hold B entries, ema four floats")
+        riders = dict(out=_nan(4, device=dev), dlogp=_nan(B, device=dev), dbaseline=_nan(B, device=dev), imp_sum=_nan(B, device=dev))
+        nv = (_p(parts), n_parts, _p(riders["imp_sum"]), _p(base), _p(logp), _p(riders["out"]), _p(riders["dlogp"]), _p(riders["dbaseline"]))
+    klp, n_kl, kl_out = None, 0, None
+    if kl_parts is not None:
+        kl_parts = _f32(kl_parts, "kl_parts", 2)
+        if kl_parts.shape[1] != M:
+            raise _lib.AirHipError(f"gemm_grouped_gauss_bwd: kl_parts {tuple(kl_parts.shape)} for {M} rows")
+        n_kl = kl_parts.shape[0]
+        riders["kl_row"] = kl_out = _nan(M, device=dev)
+        klp = kl_parts
+    st = _status(lib().air_gemm_grouped_gauss_bwd(arr, len(outs), ctypes.byref(epi), *nv, B, _p(ema), _p(klp), n_kl, _p(kl_out), M,
+                                                  _stream()), "air_gemm_grouped_gauss_bwd")
+    return st, outs, riders
+
+
+def gauss_sample_bwd_nvil(pre, eps, raw_offset, prior2, loc, scale, dsample, dkl_row, dkl_scale, dpre, guard_eps=0.0, nvil=None,
+                          kl_parts=None):
+    """air_gauss_sample_bwd_nvil (loc_mode 0, one prior; air_gauss_sample_bwd when nvil is None): the launch
+    air_gemm_grouped_gauss_bwd folds away; arguments and riders as there, dsample[M, D] given"""
+    ld_pre, ld_dpre = _mat(pre, "pre"), _mat(dpre, "dpre")
+    eps = _f32(eps, "eps", 2); dsample = _f32(dsample, "dsample", 2); dkl_row = _f32(dkl_row, "dkl_row", 1)
+    M, D = eps.shape
+    dev = eps.device
+    riders, nv, B, ema = {}, (None, 0, None, None, None, None, None, None), 0, None
+    if nvil is not None:
+        parts = _f32(nvil["imp_parts"], "imp_parts", 2); ema = _f32(nvil.get("ema"), "ema", 1)
+        n_parts, B = parts.shape
+        riders = dict(out=_nan(4, device=dev), dlogp=_nan(B, device=dev), dbaseline=_nan(B, device=dev), imp_sum=_nan(B, device=dev))
+        nv = (_p(parts), n_parts, _p(riders["imp_sum"]), _p(_f32(nvil["baseline"], "baseline", 1)), _p(_f32(nvil["logp"], "logp", 1)),
+              _p(riders["out"]), _p(riders["dlogp"]), _p(riders["dbaseline"]))
+    n_kl, kl_out = 0, None
+    if kl_parts is not None:
+        n_kl = kl_parts.shape[0]
+        riders["kl_row"] = kl_out = _nan(M, device=dev)
+    pl, ps = float(prior2[0]), float(prior2[1])
+    head = (_p(pre), ld_pre, _p(eps), float(raw_offset), 0, pl, ps, pl, ps, _p(_f32(loc, "loc", 2)), _p(_f32(scale, "scale", 2)),
+            _p(dsample), None, _p(dkl_row), float(dkl_scale), _p(dpre), ld_dpre, M, D)
+    kl = (_p(_f32(kl_parts, "kl_parts", 2)), n_kl, _p(kl_out))
+    if nvil is None:                                                    # (that entry requires the NVIL rider)
+        _lib.check(lib().air_gauss_sample_bwd(*head, float(guard_eps), *kl, _stream()), "air_gauss_sample_bwd")
+    else:
+        _lib.check(lib().air_gauss_sample_bwd_nvil(*head, *nv, B, float(guard_eps), _p(ema), *kl, _stream()), "air_gauss_sample_bwd_nvil")
+    return riders
+
+
+def batch_gather(dataset, seed_dev, step_dev, shuffle, B, out=None, want_idx=True):
+    """air_batch_gather: dataset[n_items, item_floats] -> out[B, item_floats] (NaN-primed unless given), idx[B] int64 | None"""
+    dataset = _f32(dataset, "dataset", 2)
+    n_items, item_floats = dataset.shape
+    if out is None:
+        out = _nan(B, item_floats, device=dataset.device)
+    idx = torch.full((B,), -1, dtype=torch.int64, device=dataset.device) if want_idx else None
+    _lib.check(lib().air_batch_gather(_p(dataset), n_items, item_floats, _p(_i64(seed_dev, "seed_dev")), _p(_i64(step_dev, "step_dev")),
+                                      int(bool(shuffle)), _p(out), int(B), _p(idx), _stream()), "air_batch_gather")
+    return out, idx
+
+
+def batch_gather_desc(dataset, seed_dev, step_dev, shuffle, obs, idx_out=None, copy_mask=0, n_items=None, item_floats=None):
+    """AirBatchGather: rows of obs[B, item_floats] are drawn from dataset[n_items, item_floats] (the sizes may be overridden: what the
+    launch is told, for the shapes it declines)"""
+    return _lib.AirBatchGather(dataset.data_ptr(), int(dataset.shape[0] if n_items is None else n_items),
+                               int(dataset.shape[1] if item_floats is None else item_floats), int(bool(shuffle)), int(obs.shape[0]),
+                               _i64(seed_dev, "seed_dev").data_ptr(), _i64(step_dev, "step_dev").data_ptr(), obs.data_ptr(),
+                               idx_out.data_ptr() if idx_out is not None else None, int(copy_mask))
+
+
+def gemm_grouped_gather_fits(problems, bg, precision=0):
+    """air_gemm_grouped_gather_fits: 1 when air_gemm_grouped_gather takes the group (every A a column window of bg's obs), else 0"""
+    arr, outs, keep = _gemm_descs(problems, precision, "gemm_grouped_gather_fits")
+    return int(lib().air_gemm_grouped_gather_fits(arr, len(outs), ctypes.byref(bg)))
+
+
+def gemm_grouped_gather(problems, bg, precision=0):
+    """air_gemm_grouped_gather -> (status, [(C, colsum|None)]); status is 0 or AIR_E_UNSUPPORTED (nothing launched)"""
+    arr, outs, keep = _gemm_descs(problems, precision, "gemm_grouped_gather")
+    st = _status(lib().air_gemm_grouped_gather(arr, len(outs), ctypes.byref(bg), _stream()), "air_gemm_grouped_gather")
+    return st, outs
+
+
+def _prologue_tail(normal, uniform, rng_state_dev, global_step_dev, prior_out, T, init, final_value, anneal_type, anneal_steps, hold_for,
+                   steps_div):
+    """(normal, n_normal, uniform, n_uniform, rng_state, global_step, anneal_type, init, final, anneal_steps, hold_for, steps_div,
+    prior_out, T): the argument run every entry point with the step prologue shares.  normal / uniform: flat float32 tensors | None."""
+    if anneal_type not in ANNEAL_TYPES:
+        raise _lib.AirHipError(f"step prologue: anneal_type must be one of {list(ANNEAL_TYPES)}")
+    if prior_out.dtype != torch.float64 or not prior_out.is_cuda or prior_out.numel() < int(T) + 1:
+        raise _lib.AirHipError("step prologue: prior_out must be a float64 CUDA tensor of T + 1 entries")
+    normal = _f32(normal, "normal", 1); uniform = _f32(uniform, "uniform", 1)
+    return (_p(normal), ctypes.c_size_t(normal.numel() if normal is not None else 0), _p(uniform),
+            ctypes.c_size_t(uniform.numel() if uniform is not None else 0), _p(_i64(rng_state_dev, "rng_state_dev", 2)),
+            _p(_i64(global_step_dev, "global_step_dev")), ANNEAL_TYPES[anneal_type], float(init), float(final_value), float(anneal_steps),
+            float(hold_for), float(steps_div), _p(prior_out), int(T))
+
+
+def step_prologue(normal, uniform, rng_state_dev, global_step_dev, T, h0, c0, B, init, final_value=0.0, anneal_type=None, anneal_steps=1.0,
+                  hold_for=0.0, steps_div=1.0, x=None, gather=None):
+    """air_step_prologue; with x[n] given air_step_prologue_cvt (-> the bf16 mirror of x); with gather = batch_gather_desc(...)
+    air_step_prologue_gather_cvt (rows drawn from the dataset into the descriptor's obs and into the mirror).  normal / uniform: the flat
+    buffers to fill (None: no draw).  -> prior[T+1] float64, h_tiled, c_tiled [B, Hd], x_bf16 | None; all NaN-primed"""
+    h0 = _f32(h0, "h0"); c0 = _f32(c0, "c0")
+    Hd = h0.numel()
+    dev = h0.device
+    prior = torch.full((int(T) + 1,), float("nan"), dtype=torch.float64, device=dev)
+    h_t, c_t = _nan(B, Hd, device=dev), _nan(B, Hd, device=dev)
+    args = _prologue_tail(normal, uniform, rng_state_dev, global_step_dev, prior, T, init, final_value, anneal_type, anneal_steps,
+                          hold_for, steps_div) + (_p(h0), _p(c0), _p(h_t), _p(c_t), int(B), Hd)
+    x16 = None
+    if gather is not None:
+        x16 = torch.full((gather.B, gather.item_floats), float("nan"), dtype=torch.bfloat16, device=dev)
+        _lib.check(lib().air_step_prologue_gather_cvt(*args, ctypes.byref(gather), _p(x16), _stream()), "air_step_prologue_gather_cvt")
+    elif x is not None:
+        x = _f32(x, "x")
+        x16 = torch.full(tuple(x.shape), float("nan"), dtype=torch.bfloat16, device=dev)
+        _lib.check(lib().air_step_prologue_cvt(*args, _p(x), _p(x16), ctypes.c_size_t(x.numel()), _stream()), "air_step_prologue_cvt")
+    else:
+        _lib.check(lib().air_step_prologue(*args, _stream()), "air_step_prologue")
+    return prior, h_t, c_t, x16
+
+
+def lstm_step_fwd_prologue(h0, c0, w_h, gx, forget_bias, precision, normal, uniform, rng_state_dev, global_step_dev, T, init,
+                           final_value=0.0, anneal_type=None, anneal_steps=1.0, hold_for=0.0, steps_div=1.0):
+    """air_lstm_step_fwd_prologue: h0, c0 [Hd] (one row for the batch), w_h[Hd, 4Hd] and gx[M, 4Hd] (row views are fine)
+    -> (h, c [M, Hd], gate_act[M, 4Hd]), (prior[T+1] float64, h_tiled, c_tiled [M, Hd]); all NaN-primed"""
+    h0 = _f32(h0, "h0"); c0 = _f32(c0, "c0")
+    Hd = h0.numel()
+    ldw, ldgx = _mat(w_h, "w_h", 4 * Hd), _mat(gx, "gx", 4 * Hd)
+    M = gx.shape[0]
+    dev = gx.device
+    h, c, act = _nan(M, Hd, device=dev), _nan(M, Hd, device=dev), _nan(M, 4 * Hd, device=dev)
+    prior = torch.full((int(T) + 1,), float("nan"), dtype=torch.float64, device=dev)
+    h_t, c_t = _nan(M, Hd, device=dev), _nan(M, Hd, device=dev)
+    tail = _prologue_tail(normal, uniform, rng_state_dev, global_step_dev, prior, T, init, final_value, anneal_type, anneal_steps, hold_for,
+                          steps_div)
+    _lib.check(lib().air_lstm_step_fwd_prologue(_p(h0), _p(c0), _p(w_h), ldw, _p(gx), ldgx, _p(h), _p(c), _p(act), M, Hd, float(forget_bias),
+                                                int(precision), *tail, _p(h_t), _p(c_t), _stream()), "air_lstm_step_fwd_prologue")
+    return (h, c, act), (prior, h_t, c_t)
+
+
+def lstm_first_step_fwd(x, w_x, b_gates, h0, c0, w_h, gx_out, forget_bias, precision, normal, uniform, rng_state_dev, global_step_dev, T,
+                        init, final_value=0.0, anneal_type=None, anneal_steps=1.0, hold_for=0.0, steps_div=1.0):
+    """air_lstm_first_step_fwd: x[M, E] (a row view is fine: ldx), w_x[E, 4Hd] and w_h[Hd, 4Hd] of ONE leading dimension, b_gates[4Hd],
+    gx_out[M, 4Hd] (a row view of the caller's buffer: ldgx) -> status (0 | AIR_E_UNSUPPORTED), (h, c, gate_act), (prior, h_tiled, c_tiled)"""
+    h0 = _f32(h0, "h0"); c0 = _f32(c0, "c0"); b_gates = _f32(b_gates, "b_gates", 1)
+    Hd = h0.numel()
+    ldx = _mat(x, "x")
+    M, E = x.shape
+    ldw, ldgx = _mat(w_h, "w_h", 4 * Hd), _mat(gx_out, "gx_out", 4 * Hd)
+    if _mat(w_x, "w_x", 4 * Hd) != ldw or w_x.shape[0] != E or gx_out.shape[0] != M or b_gates.numel() != 4 * Hd:
+        raise _lib.AirHipError(f"lstm_first_step_fwd: x {tuple(x.shape)}, w_x {tuple(w_x.shape)} (ld {w_x.stride(0)}), w_h ld {ldw}")
+    dev = x.device
+    h, c, act = _nan(M, Hd, device=dev), _nan(M, Hd, device=dev), _nan(M, 4 * Hd, device=dev)
+    prior = torch.full((int(T) + 1,), float("nan"), dtype=torch.float64, device=dev)
+    h_t, c_t = _nan(M, Hd, device=dev), _nan(M, Hd, device=dev)
+    tail = _prologue_tail(normal, uniform, rng_state_dev, global_step_dev, prior, T, init, final_value, anneal_type, anneal_steps, hold_for,
+                          steps_div)
+    st = _status(lib().air_lstm_first_step_fwd(_p(x), ldx, E, _p(w_x), _p(b_gates), _p(h0), _p(c0), _p(w_h), ldw, _p(gx_out), ldgx, _p(h),
+                                               _p(c), _p(act), M, Hd, float(forget_bias), int(precision), *tail, _p(h_t), _p(c_t),
+                                               _stream()), "air_lstm_first_step_fwd")
+    return st, (h, c, act), (prior, h_t, c_t)
+
+
+def _canvas_bwd_args(glimpse, where, presence, obs, final_canvas):
+    glimpse = _f32(glimpse, "glimpse", 4); where = _f32(where, "where", 3); presence = _f32(presence, "presence", 2)
+    obs = _f32(obs, "obs", 3); final_canvas = _f32(final_canvas, "final_canvas", 3)
+    T, B, h, w = glimpse.shape
+    H, W = obs.shape[1:]
+    if tuple(where.shape) != (T, B, 4) or tuple(presence.shape) != (T, B) or obs.shape[0] != B:
+        raise _lib.AirHipError(f"canvas backward: glimpse {tuple(glimpse.shape)}, where {tuple(where.shape)}, presence {tuple(presence.shape)}")
+    dg = _nan(T, B, h, w, device=glimpse.device); dwhere = _nan(T, B, 4, device=glimpse.device)
+    return (_p(glimpse), _p(where), _p(presence), _p(obs), _p(final_canvas), _p(dg), _p(dwhere)), (T, B, H, W, h, w), dg, dwhere
+
+
+def canvas_unroll_bwd_dpresence(glimpse, where, presence, obs, final_canvas, mult, std, loss_scale):
+    """air_canvas_unroll_bwd_dpresence -> dglimpse[T,B,h,w], dwhere[T,B,4], dpresence[T,B] (NaN-primed)"""
+    ptrs, dims, dg, dwhere = _canvas_bwd_args(glimpse, where, presence, obs, final_canvas)
+    dpres = _nan(dims[0], dims[1], device=dg.device)
+    _lib.check(lib().air_canvas_unroll_bwd_dpresence(*ptrs, _p(dpres), *dims, float(mult), float(std), float(loss_scale), _stream()),
+               "air_canvas_unroll_bwd_dpresence")
+    return dg, dwhere, dpres
+
+
+def canvas_unroll_bwd_nvil(glimpse, where, presence, obs, final_canvas, mult, std, loss_scale, imp_parts, baseline, logp, ema=None):
+    """air_canvas_unroll_bwd_nvil -> dglimpse, dwhere, (out[4], dlogp[B], dbaseline[B], imp_sum[B]) (NaN-primed)"""
+    ptrs, dims, dg, dwhere = _canvas_bwd_args(glimpse, where, presence, obs, final_canvas)
+    imp_parts = _f32(imp_parts, "imp_parts", 2); baseline = _f32(baseline, "baseline", 1); logp = _f32(logp, "logp", 1)
+    ema = _f32(ema, "ema", 1)
+    n_parts, B = imp_parts.shape
+    if B != dims[1] or baseline.shape[0] != B or logp.shape[0] != B or (ema is not None and ema.numel() != 4):
+        raise _lib.AirHipError("canvas_unroll_bwd_nvil: imp_parts[n_parts, B], baseline[B], logp[B], ema of four floats")
+    dev = dg.device
+    out, dlogp, dbase, imp_sum = _nan(4, device=dev), _nan(B, device=dev), _nan(B, device=dev), _nan(B, device=dev)
+    _lib.check(lib().air_canvas_unroll_bwd_nvil(*ptrs, *dims, float(mult), float(std), float(loss_scale), _p(imp_parts), n_parts,
+                                                _p(imp_sum), _p(baseline), _p(logp), _p(out), _p(dlogp), _p(dbase), _p(ema), _stream()),
+               "air_canvas_unroll_bwd_nvil")
+    return dg, dwhere, (out, dlogp, dbase, imp_sum)
+
+
+def sum_leading(x):
+    """air_sum_leading: x[T, n] -> out[n] = sum_t x[t], added in order from t = 0"""
+    x = _f32(x, "x", 2)
+    T, n = x.shape
+    out = _nan(n, device=x.device)
+    _lib.check(lib().air_sum_leading(_p(x), _p(out), T, ctypes.c_size_t(n), _stream()), "air_sum_leading")
+    return out
+
+
+def l2_grad_add_(g, p, ranges, l2_weight):
+    """air_l2_grad_add: g += l2_weight * p on the (lo, hi) slices of the flat buffers, in place"""
+    g = _f32(g, "g", 1); p = _f32(p, "p", 1)
+    lo = (ctypes.c_size_t * len(ranges))(*[int(r[0]) for r in ranges]); hi = (ctypes.c_size_t * len(ranges))(*[int(r[1]) for r in ranges])
+    if any(not (0 <= r[0] <= r[1] <= g.numel()) for r in ranges) or p.numel() != g.numel():
+        raise _lib.AirHipError("l2_grad_add_: ranges must lie inside the flat buffers")
+    _lib.check(lib().air_l2_grad_add(_p(g), _p(p), lo, hi, len(ranges), float(l2_weight), _stream()), "air_l2_grad_add")
+
+
+def counter_add_(counter_dev, increment):
+    """air_counter_add: counter_dev[0] += increment on the device"""
+    _lib.check(lib().air_counter_add(_p(_i64(counter_dev, "counter_dev")), int(increment), _stream()), "air_counter_add")

@@ -198,7 +198,10 @@ AIR_ENGINE_API int air_gemm_grouped(const AirGemmDesc *descs, int count, void *s
  * in HBM): the gather of air_batch_gather folded into the A-operand load.  Every problem's A lies inside obs[B, item_floats] (row 0 + a
  * column offset, lda = item_floats, not transposed, fp32) and is read from item idx_m of `dataset` instead -- idx_m drawn exactly as
  * air_batch_gather draws it --; the problems of copy_mask write the rows they read into obs (together they must cover every column),
- * idx_out (optional) receives the indices.  air_gemm_grouped_gather_fits answers, without launching, whether a launch qualifies.       */
+ * idx_out (optional) receives the indices.  air_gemm_grouped_gather_fits answers, without launching, whether a launch qualifies: K
+ * and the column offsets multiples of 4, and a group air_gemm_grouped is sure to run on the 16-wave K-split body (every K >= 512 and
+ * >= 8 min(M, N), at most 1024 tiles and no more than AIR_GEMM_WIDE_MIN_TILES, default 1000: beyond, air_gemm_grouped may take its
+ * wide-tile kernels) -- the one body this launch has, so the products are those of air_batch_gather + air_gemm_grouped. */
 typedef struct AirBatchGather {
     const float *dataset;
     long long n_items;
@@ -274,7 +277,9 @@ AIR_ENGINE_API int air_lstm_step_fwd_prologue(const float *h0, const float *c0, 
  * is computed once): step 0's recurrent operand is the trainable initial state -- one row for the whole batch -- so this launch
  * accumulates x[M,E](ldx) . w_x[E,4Hd](ldw) and h0[1,Hd] . w_h[Hd,4Hd](ldw) side by side, writes gx_out[M,4Hd](ldgx) = x . w_x +
  * b_gates for the later steps and finishes step 0 on gx + h0 . w_h: the results of the gx launch + air_lstm_step_fwd_prologue it
- * replaces, bit for bit.  Latency regime only: AIR_E_UNSUPPORTED beyond 512 tiles of 16 x 16 over (M, Hd).                    */
+ * replaces, bit for bit.  Latency regime only: AIR_E_UNSUPPORTED beyond 512 tiles of 16 x 16 over (M, Hd), and wherever the gx
+ * product [M, 4Hd, E] as a launch of its own would not run on the 4-wave 16 x 16 body whose K order this kernel repeats (more than
+ * AIR_GEMM_WIDE_MIN_TILES = 1000 tiles of gx, or E >= 512 with E >= 8 min(M, 4Hd)): the promise would not hold there.            */
 AIR_ENGINE_API int air_lstm_first_step_fwd(const float *x, int ldx, int E, const float *w_x, const float *b_gates, const float *h0,
                             const float *c0, const float *w_h, int ldw, float *gx_out, int ldgx, float *h, float *c,
                             float *gate_act, int M, int Hd, float forget_bias, int precision, float *normal, size_t n_normal,

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from fold_cases import philox_normals
 from oracle import air_oracle as O
 from test_engine import CONFIGS, OUT_L2, OUT_TOL, check_tensor, f64, l2_err, make_pair
 
@@ -297,15 +298,6 @@ def run_observe(canvas, mult, std, state, counter_base, clamp=(float("nan"), flo
     _lib.check(st, "air_observe")
     torch.cuda.synchronize()
     return mean, obs
-
-
-def philox_normals(seed, offset, n):
-    """what air_rng_fill(normal, n, NULL, 0, {seed, offset}) writes"""
-    from attend_infer_repeat_amd import hip as H
-    z = torch.zeros(n, device="cuda")
-    H.rng_fill(torch.tensor([seed, offset], dtype=torch.int64, device="cuda"), normal=z, advance=False)
-    torch.cuda.synchronize()
-    return z
 
 
 @pytest.mark.parametrize("n", [4 * 625, 4 * 625 + 3, 4 * (2048 * 256 + 1000) + 1])    # aligned body; + tail; more quads than grid threads

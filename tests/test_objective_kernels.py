@@ -245,17 +245,17 @@ def _nvil_ref(imp, base, logp, ema=None):
     return out, gl, gb, raw.detach().mean(), raw.detach().var(unbiased=False)
 
 
-def _check_nvil(got, ref, tag, rtol_only_baseline_loss=False):
+def _check_nvil(got, ref, tag, rtol_only_baseline_loss=False, group="B"):
     out, dlogp, dbase = got
     rout, rdlogp, rdbase = ref
     assert bool(torch.isfinite(out).all())
     if rtol_only_baseline_loss:                                                 # out[1] ~ 1.8e9: an absolute 1e-3 means nothing there
         keep = torch.tensor([0, 2, 3])
-        assert_close(out.cpu()[keep], rout[keep], 1e-5, 1e-3, tag + "scalars 0, 2, 3", "B")
-        assert_close(out.cpu()[1:2], rout[1:2], 1e-5, 0.0, tag + "baseline loss", "B")
+        assert_close(out.cpu()[keep], rout[keep], 1e-5, 1e-3, tag + "scalars 0, 2, 3", group)
+        assert_close(out.cpu()[1:2], rout[1:2], 1e-5, 0.0, tag + "baseline loss", group)
     else:
-        assert_close(out, rout, 1e-5, 1e-3, tag + "scalars", "B")
-    assert_close(dlogp, rdlogp, 1e-5, 1e-5, tag + "dlogp", "B"); assert_close(dbase, rdbase, 1e-5, 1e-5, tag + "dbaseline", "B")
+        assert_close(out, rout, 1e-5, 1e-3, tag + "scalars", group)
+    assert_close(dlogp, rdlogp, 1e-5, 1e-5, tag + "dlogp", group); assert_close(dbase, rdbase, 1e-5, 1e-5, tag + "dbaseline", group)
 
 
 @pytest.mark.parametrize("kind", ["plain", "equal_imp", "zero_variance", "offset"])
