@@ -343,6 +343,96 @@ def make_parse_score_logger(air, data, num_batches, name, writer=None, threshold
     return logger
 
 
+def make_tiled_parse_fig(air, scenes, checkpoint_dir=None, global_step=None, n_samples=4, stride=None, iou_merge=0.5, **parse_kw):
+    """The tiled parse of scenes larger than the canvas (air.parse_tiled): one column per scene; the scene, the reconstruction with
+    the window grid (thin lines) and the attention box of every kept object coloured by the WINDOW it came from (rect_stn on the
+    scene-frame `where`), and the owner map (which object a pixel belongs to; background = -1).  Saved as
+    tiled_parse_fig_<global_step>.png when a directory is given."""
+    import os.path as osp
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    import torch
+    from .tile import window_origins
+    out = air.parse_tiled(scenes, stride=stride, iou_merge=iou_merge, **parse_kw)
+    host = lambda t: t.detach().cpu().numpy()
+    x, rec, owner = host(torch.as_tensor(scenes)), host(out["reconstruction"]), host(out["owner"])
+    presence, where, kept, counts = host(out["presence"]), host(out["where"]), host(out["kept_cand"]), host(out["merge_counts"])
+    C = presence.shape[0]
+    cols = min(n_samples, x.shape[0])
+    Hs, Ws = x.shape[1:]
+    H, W = out["windows"].shape[1:]
+    T = out["cand_state"].shape[1] // out["window_num_objects"].shape[1]
+    oy, ox = window_origins((Hs, Ws), (H, W), stride)
+    inch = 2.5
+    fig, axes = plt.subplots(3, cols, figsize=(inch * cols * Ws / max(Hs, Ws), inch * 3 * Hs / max(Hs, Ws)), squeeze=False)
+    colours = plt.get_cmap('tab20')
+    for col in range(cols):
+        axes[0][col].imshow(x[col], cmap='gray', vmin=0, vmax=1)
+        axes[1][col].imshow(rec[col], cmap='gray', vmin=0, vmax=1)
+        for y in oy:
+            for xo in ox:
+                axes[1][col].add_patch(plt.Rectangle((xo - .5, y - .5), W, H, fill=False, lw=.3, ec='white', alpha=.4))
+        for j in range(C):
+            if presence[j, col] > .5:
+                rect_stn(axes[1][col], Ws, Hs, where[j, col], colours((int(kept[j, col]) // T) % 20), line_width=1)
+        axes[1][col].set_title('n = {:d}, dup = {:d}, not owned = {:d}'.format(int(presence[:, col].sum()), int(counts[col, 3]),
+                                                                               int(counts[col, 2])), fontsize=3 * inch)
+        axes[2][col].imshow(owner[col], cmap='tab20', vmin=-1, vmax=max(C - 1, 18), interpolation='nearest')
+    for ax in axes.ravel():
+        ax.set_axis_off()
+    if checkpoint_dir is not None:
+        fig.savefig(osp.join(checkpoint_dir, 'tiled_parse_fig_{}.png'.format(global_step)), dpi=300)
+        plt.close(fig)
+    return fig
+
+
+def make_tiled_parse_score_logger(air, data, num_batches, name, batch_size=None, writer=None, thresholds=None, measure_time=True,
+                                  stride=None, iou_merge=0.5, refine=None, refine_lr=None, prune=None, propose=None):
+    """make_parse_score_logger's counterpart for scenes larger than the canvas (air.score_parse_tiled): `data` is an annotated dataset
+    dict of SCENES (imgs [N, Hs, Ws], boxes [N, G, 4], instances [N, Hs, Ws] int8 -- data.create_multi_mnist with canvas_size = the
+    scene's and return_annotations=True), walked in `num_batches` batches of `batch_size` scenes (None: the model's batch size).
+    Prints / writes count accuracy, AP per threshold and mAP, foreground ARI, mean best overlap, and the totals of the merge's
+    candidate states over the scenes scored (merge_kept, merge_not_owned, merge_duplicate, merge_overflow, merge_nonfinite)."""
+    import torch
+    from .tile import STATES
+    kw = {} if thresholds is None else dict(thresholds=tuple(thresholds))
+    tk = dict(stride=stride, iou_merge=iou_merge, refine=refine, refine_lr=refine_lr, prune=prune, propose=propose)
+
+    def logger(itr=0, num_batches_to_eval=None, write=True):
+        n = num_batches if num_batches_to_eval is None else num_batches_to_eval
+        S = int(air.obs.shape[0]) if batch_size is None else int(batch_size)
+        n = min(max(int(n), 1), int(data["imgs"].shape[0]) // S)
+        if n < 1:
+            raise ValueError("the annotated dataset holds fewer scenes than one batch of %d" % S)
+        start = time.time()
+        dev = air.obs.device
+        states = torch.zeros(6, dtype=torch.int64, device=dev)
+        scorer = None
+        for i in range(n):
+            sl = slice(i * S, (i + 1) * S)
+            _, scorer = air.score_parse_tiled(torch.as_tensor(data["imgs"][sl], dtype=torch.float32).to(dev),
+                                              torch.as_tensor(data["instances"][sl]), torch.as_tensor(data["boxes"][sl]),
+                                              accumulate=i > 0, **kw, **tk)
+            states += air.parsed_tiled["merge_counts"].sum(0)
+        acc = scorer.summary()
+        for k, v in zip(STATES[1:], states.tolist()[1:]):
+            acc["merge_" + k] = v
+        shown = ["count_acc", "map", "ap@%.2f" % scorer.thresholds_host[0], "fg_ari", "mean_best_overlap", "merge_kept",
+                 "merge_not_owned", "merge_duplicate", "merge_overflow"]
+        t = time.time() - start
+        msg = 'Step {}, Data {} parse tiled score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
+        if measure_time:
+            msg += ', eval time = {:.4}s'.format(t)
+        print(msg)
+        if write and writer is not None:
+            rec = dict(step=int(itr), data=name + "_parse_tiled_score", scene_size=list(data["imgs"].shape[1:]),
+                       stride=None if stride is None else list(stride), **acc)
+            writer.write(json.dumps(rec) + "\n"); writer.flush()
+        return acc
+    return logger
+
+
 def gradient_summaries(named_grads, named_vars, norm=True, ratio=True, histogram=False, bins=30):
     """evaluation.py:221-248: the global norm of the gradient, per variable mean(|g| / (|v| + 1e-8)) (log_ratio,
     evaluation.py:169-180) and -- histogram=True, the reference's default -- a histogram of every gradient tensor, the content of its

@@ -1147,3 +1147,47 @@ def l2_grad_add_(g, p, ranges, l2_weight):
 def counter_add_(counter_dev, increment):
     """air_counter_add: counter_dev[0] += increment on the device"""
     _lib.check(lib().air_counter_add(_p(_i64(counter_dev, "counter_dev")), int(increment), _stream()), "air_counter_add")
+
+
+# ---- tiled scene parsing -------------------------------------------------------------------------------------------
+def tile_gather(scenes, img_size, stride):
+    """air_tile_gather: scenes[S, Hs, Ws] -> windows[S * Nw, H * W] (bit copies; tile.py states the window order)"""
+    from .tile import check_geometry
+    scenes = _f32(scenes, "scenes", 3)
+    S, Hs, Ws = scenes.shape
+    (H, W) = img_size
+    _, (sy, sx), (ny, nx) = check_geometry((Hs, Ws), (H, W), stride, n_scenes=S)
+    out = _nan(S * ny * nx, H * W, device=scenes.device)
+    _lib.check(lib().air_tile_gather(_p(scenes), S, Hs, Ws, H, W, sy, sx, _p(out), _stream()), "air_tile_gather")
+    return out
+
+
+def tile_merge(what, where, glimpse, score, num_objects, scene_size, img_size, stride, iou_merge=0.5):
+    """air_tile_merge on a provider's rows what[T, R, A], where[T, R, 4], glimpse[T, R, G], score[T, R], num_objects[R] int32
+    (R = S * Nw).  Returns a dict: what [C, S, A], where [C, S, 4], glimpse [C, S, G], score_src [C, S] (rows beyond a scene's count
+    hold NaN: the entry does not write them), kept_cand [C, S], num_objects [S], cand_state [S, Nc] int8, dup_of [S, Nc],
+    merge_counts [S, 6]."""
+    from .tile import MAX_SLOTS, check_geometry
+    what, where, glimpse, score = _f32(what, "what", 3), _f32(where, "where", 3), _f32(glimpse, "glimpse", 3), _f32(score, "score", 2)
+    T, R, A = what.shape
+    G = glimpse.shape[2]
+    if where.shape != (T, R, 4) or glimpse.shape[:2] != (T, R) or score.shape != (T, R):
+        raise _lib.AirHipError("tile_merge: where / glimpse / score do not match what[T, R, A]")
+    if num_objects.dtype != torch.int32 or num_objects.shape != (R,) or not num_objects.is_cuda or not num_objects.is_contiguous():
+        raise _lib.AirHipError("tile_merge: num_objects must be a contiguous int32 HIP tensor of R entries")
+    (Hs, Ws), (H, W) = scene_size, img_size
+    _, (sy, sx), (ny, nx) = check_geometry((Hs, Ws), (H, W), stride, T)
+    Nw = ny * nx
+    if R % Nw:
+        raise _lib.AirHipError("tile_merge: %d rows are no multiple of %d windows" % (R, Nw))
+    S, Nc, C = R // Nw, Nw * T, min(Nw * T, MAX_SLOTS)
+    dev = what.device
+    i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+    out = {"what": _nan(C, S, A, device=dev), "where": _nan(C, S, 4, device=dev), "glimpse": _nan(C, S, G, device=dev),
+           "score_src": _nan(C, S, device=dev), "kept_cand": i32(C, S), "num_objects": i32(S),
+           "cand_state": torch.zeros((S, Nc), dtype=torch.int8, device=dev), "dup_of": i32(S, Nc), "merge_counts": i32(S, 6)}
+    _lib.check(lib().air_tile_merge(_p(what), _p(where), _p(glimpse), _p(score), _p(num_objects), T, S, A, G, Hs, Ws, H, W, sy, sx,
+                                    float(iou_merge), _p(out["what"]), _p(out["where"]), _p(out["glimpse"]), _p(out["score_src"]),
+                                    _p(out["kept_cand"]), _p(out["num_objects"]), _p(out["cand_state"]), _p(out["dup_of"]),
+                                    _p(out["merge_counts"]), _stream()), "air_tile_merge")
+    return out

@@ -480,6 +480,87 @@ class AIRonMNIST(AIRModel):
         self.parse_scores = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores
 
+    MAX_TILED_PARSERS = 2
+
+    def tiled_parser(self, n_scenes, scene_size, stride=None, iou_merge=0.5, refine=None, refine_lr=None, prune=None, propose=None):
+        """the tile.TiledSceneParser behind parse_tiled: one per (n_scenes, scene_size, stride, iou_merge, refine, refine_lr, prune,
+        propose), over a provider stack of its own at n_scenes * windows rows -- a SceneParser, behind it the refiner / pruner /
+        proposer asked for -- so the parsers of `parse` and `self.obs` are never touched.  Built and captured on first use; the
+        least recently used one is dropped, with its stack, when more than MAX_TILED_PARSERS are alive (each owns an engine)."""
+        eng = getattr(self, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("parse_tiled needs the fused engine: call train_step(...) with an engine-eligible "
+                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        if prune is not None and propose is not None:
+            raise ValueError("parse_tiled: prune together with propose is not supported; pass one of them")
+        from . import tile
+        from .parse import SceneParser
+        from .refine import DEFAULT_LR
+        (Hs, Ws), (sy, sx), (ny, nx) = tile.check_arguments(eng.cfg, scene_size, stride, iou_merge, int(n_scenes))
+        lr = None if refine is None else tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
+        spec = propose if not isinstance(propose, list) else tuple(propose)
+        key = (int(n_scenes), (Hs, Ws), (sy, sx), float(iou_merge), refine, lr, prune, spec, str(eng.device))
+        cache = self.__dict__.setdefault("_tiled_parsers", {})
+        entry = cache.pop(key, None)
+        if entry is None:
+            stack = [SceneParser(eng.cfg, int(n_scenes) * ny * nx, device=eng.device)]
+            if refine is not None:
+                from .refine import ParseRefiner
+                stack.append(ParseRefiner(stack[-1], int(refine), lr[0], lr[1]))
+            if prune is not None:
+                from .prune import ParsePruner
+                stack.append(ParsePruner(stack[-1], prune))
+            if propose is not None:
+                from .propose import ParseProposer
+                p = (int(propose), 1) if not isinstance(propose, (tuple, list)) else tuple(int(v) for v in propose)
+                stack.append(ParseProposer(stack[-1], p[0], p[1]))
+            stack.append(tile.TiledSceneParser(stack[-1], (Hs, Ws), (sy, sx), iou_merge))
+            for s in stack:
+                s.capture()
+            entry = stack
+        cache[key] = entry                                         # most recently used last
+        while len(cache) > self.MAX_TILED_PARSERS:
+            for s in reversed(cache.pop(next(iter(cache)))):
+                s.release_graphs()
+        return entry[-1]
+
+    def parse_tiled(self, scenes, stride=None, iou_merge=0.5, refine=None, refine_lr=None, prune=None, propose=None):
+        """Parse scenes [S, Hs, Ws] LARGER than the model's canvas on the device: overlapping windows of the canvas's size at `stride`
+        (None: half the canvas), each parsed as `parse(refine=, prune=, propose=)` would parse it, and the windows' objects merged
+        into one parse per scene (tile.TiledSceneParser.parse lists the returned device tensors; the next call overwrites them).
+        The training engine's parameters are read, nothing of it is written; `self.obs` and the parsers of `parse` are not touched."""
+        import torch
+        scenes = torch.as_tensor(scenes)
+        if scenes.dim() != 3:
+            raise ValueError("parse_tiled: scenes [S, Hs, Ws], got shape %s" % (tuple(scenes.shape),))
+        s = self.tiled_parser(scenes.shape[0], tuple(scenes.shape[1:]), stride, iou_merge, refine, refine_lr, prune, propose)
+        self._sync_engine_switches()
+        s.load_from(self._engine)                            # every time: the weights move
+        self.parsed_tiled = s.parse(scenes)
+        return self.parsed_tiled
+
+    def score_parse_tiled(self, scenes, gt_instances, gt_boxes, gt_count=None, thresholds=None, accumulate=True, stride=None,
+                          iou_merge=0.5, refine=None, refine_lr=None, prune=None, propose=None):
+        """parse_tiled, then score the scene parses against scene-level ground truth on the device (score.ParseScorer.score lists the
+        arguments and the returned tensors; gt_instances [S, Hs, Ws], gt_boxes [S, G, 4] with G <= 8).  The sums accumulate in the
+        scorer this returns alongside: (scores, scorer)."""
+        import torch
+        from .score import DEFAULT_THRESHOLDS, ParseScorer
+        self.parse_tiled(scenes, stride, iou_merge, refine, refine_lr, prune, propose)
+        scenes = torch.as_tensor(scenes)
+        parser = self.tiled_parser(scenes.shape[0], tuple(scenes.shape[1:]), stride, iou_merge, refine, refine_lr, prune, propose)
+        th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
+        G = int(torch.as_tensor(gt_boxes).shape[1])
+        s = getattr(self, "_tiled_scorer", None)
+        if s is None or s.parser is not parser or s.G != G or s.thresholds_host != th:
+            if s is not None:
+                s.release_graphs()
+            s = ParseScorer(parser, G, th)
+            s.capture()
+            self._tiled_scorer = s
+        self.parse_scores_tiled = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
+        return self.parse_scores_tiled, s
+
     def refresh(self):
         """Re-expose the engine's current buffers under the reference's attribute names."""
         if self._engine is not None:

@@ -105,6 +105,15 @@ def main(argv=None):
                          "objective_gain")
     ap.add_argument("--parse-refine-lr", default=None, metavar="A,B",
                     help="with --parse-refine: the Adam learning rates of the `what` and the `where` latents (default: refine.DEFAULT_LR)")
+    ap.add_argument("--parse-tiled", default=None, metavar="HSxWS[:STRIDE]",
+                    help="at every --log-every also parse and score held-out SCENES of HS x WS pixels, larger than the model's canvas, "
+                         "in overlapping windows merged on the device (AIRonMNIST.score_parse_tiled, tile.TiledSceneParser, "
+                         "evaluation.make_tiled_parse_score_logger): count accuracy, AP / mAP, foreground ARI and the totals of the "
+                         "merge's candidate states.  STRIDE: one number or SYxSX (default: half the canvas).  The scenes are built "
+                         "from procedural digit templates by the reference's generator with annotations; --parse-refine, "
+                         "--parse-prune and --parse-propose apply to every window")
+    ap.add_argument("--parse-tiled-objects", type=int, default=4, metavar="N",
+                    help="with --parse-tiled: a scene holds 0..N digits (N <= 8, the ground-truth slots of the scorer)")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -136,6 +145,22 @@ def main(argv=None):
         if len(spec) not in (1, 2) or min(spec) < 1:
             ap.error("--parse-propose needs P >= 1 or P,ROUNDS with ROUNDS >= 1, got %r" % args.parse_propose)
         refine_kw["propose"] = spec[0] if len(spec) == 1 else spec
+
+    tiled = None
+    if args.parse_tiled is not None:
+        try:
+            size, _, stride = args.parse_tiled.partition(":")
+            scene = tuple(int(v) for v in size.lower().split("x"))
+            stride = tuple(int(v) for v in stride.lower().split("x")) if stride else None
+            if len(scene) != 2 or (stride is not None and len(stride) not in (1, 2)):
+                raise ValueError
+        except ValueError:
+            ap.error("--parse-tiled needs HSxWS or HSxWS:STRIDE (STRIDE: a number or SYxSX), got %r" % args.parse_tiled)
+        if not 1 <= args.parse_tiled_objects <= 8:
+            ap.error("--parse-tiled-objects needs 1 <= N <= 8")
+        if args.parse_particles > 0:
+            ap.error("--parse-tiled does not go with --parse-particles: particle providers are out of scope for tiling")
+        tiled = dict(scene=scene, stride=None if stride is None else (stride * 2)[:2])
 
     learning_rate, n_steps, batch_size = args.learning_rate, 3, 64    # multi_mnist.py:24-25,37
     num_steps_prior = AttrDict(anneal='exp', init=1. - 1e-15, final=1e-7, steps_div=1e4, steps=1e5, hold_init=1e3)
@@ -259,6 +284,22 @@ def main(argv=None):
         def log(train_itr):                               # noqa: F811
             out = before_score_log(train_itr)
             score_log(train_itr)
+            return out
+
+    if tiled is not None:
+        from attend_infer_repeat_amd.evaluation import make_tiled_parse_score_logger
+        scenes_per_batch = 16
+        raw = procedural_multi_mnist(scenes_per_batch * max(args.eval_batches, 1), canvas_size=tiled["scene"],
+                                     n_objects=(0, args.parse_tiled_objects), seed=args.seed + 1000, n_templates=256,
+                                     return_annotations=True)            # the validation set's generator and its first templates
+        scene_data = dict(imgs=raw["imgs"].astype("float32") / 255.0, boxes=raw["boxes"], instances=raw["instances"])
+        before_tiled_log = log
+        tiled_log = make_tiled_parse_score_logger(air, scene_data, args.eval_batches, 'test', scenes_per_batch, writer,
+                                                  stride=tiled["stride"], **refine_kw)
+
+        def log(train_itr):                               # noqa: F811
+            out = before_tiled_log(train_itr)
+            tiled_log(train_itr)
             return out
 
     train_itr = int(global_step)

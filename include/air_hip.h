@@ -741,6 +741,42 @@ AIR_ENGINE_API int air_propose_pool(const float *what, const float *where, const
                     float *pool_presence, int *pool_source, double *pool_prior, void *stream);
 AIR_ENGINE_API int air_propose_source(const int *pool_source, const int *kept_step, int C, int R, int *source_out, void *stream);
 
+/* ---- parsing scenes larger than the model's canvas: overlapping windows in, one merged object list per scene out.  Canvas H x W
+ * (both > 1), scene Hs x Ws (Hs >= H, Ws >= W), stride 1 <= sy <= H, 1 <= sx <= W.  ny = 1 + ceil((Hs - H) / sy) windows along y at
+ * oy_i = min(i sy, Hs - H) (the last one clamped to the edge: every window is a real crop), nx / ox_j alike, Nw = ny nx, window
+ * v = i nx + j, window row r = s Nw + v.  No atomics, one fixed order: the same bits run to run.  Checks come before the launch: a
+ * refused call writes nothing.  AIR_E_SHAPE: a size or stride outside the above, Hs * Ws or S * Nw past int32.
+ * air_tile_gather: windows[S * Nw, H * W] = the crops, bit copies.  One workgroup per (window, band of rows); 16-byte moves for the
+ *   windows whose rows start on 16 bytes both in the scene and in the window (ox, Ws, W multiples of 4, both buffers 16-byte aligned),
+ *   4-byte moves otherwise.  AIR_E_ALIGN: a buffer not 4-byte aligned.
+ * air_tile_merge: the provider's rows what[T,R,A], where[T,R,4], glimpse[T,R,G], score[T,R], num_objects[R] (R = S Nw) -> one scene
+ *   parse.  Candidate c = v T + t, Nc = Nw T <= 256, C = min(Nc, 32) slots.
+ *   Lift of where = [sx, tx, sy, ty], float64 in this operation order, rounded once to fp32:  ax = (Ws - 1) / (W - 1),
+ *     bx = (ax - 1) - (2 ox) / (W - 1),  sx' = sx / ax,  tx' = (tx - bx) / ax;  y alike with Hs, H, oy.  Hs == H and Ws == W: the
+ *     input row bit for bit.  The scene box of a candidate is air_parse_objects' box of the lifted fp32 row at (Hs, Ws).
+ *   cand_state[S,Nc] (int8), decided in this order:  0 absent (t >= num_objects[r]);  5 non-finite (a lifted fp32 value or the score
+ *     is NaN or +-inf);  2 not owned: with cx = Ws (1 + tx') / 2, cy = Hs (1 + ty') / 2 (float64 from the lifted fp32 row), window j
+ *     owns [beta_{j-1}, beta_j) along x, beta_j = (ox_{j+1} + ox_j + W) / 2, beta_{-1} = -inf, beta_{nx-1} = +inf, y alike -- a
+ *     candidate whose centre is outside its own window's cell is dropped;  3 duplicate: the owned candidates are walked by score
+ *     descending (equal scores: the lower c first), and one is suppressed when a candidate kept before it, OF A DIFFERENT WINDOW, has
+ *     a float64 box IoU (air_score_match's) > iou_merge with it, strictly -- dup_of[S,Nc] (int32) = the first such candidate in walk
+ *     order, -1 for every other state;  4 overflow (not suppressed, but C are kept: it suppresses nothing);  1 kept.
+ *   The kept candidates fill slots 0 .. n-1 in ascending c:  what_out[C,S,A], glimpse_out[C,S,G], score_out[C,S] bit copies (16-byte
+ *     vectors where A resp. G is a multiple of 4 and both buffers are 16-byte aligned, 4-byte words otherwise), where_out[C,S,4] the
+ *     lifted row, kept_cand[C,S] (int32) = c, -1 from slot n on;  num_objects_out[S] = n;  merge_counts[S,6] (int32) = candidates per
+ *     state.  Rows from slot n on are not written.  One 256-thread workgroup per scene.  T in 1..32 (AIR_E_SHAPE); where / where_out
+ *     16-byte aligned, everything else 4-byte aligned (AIR_E_ALIGN).  The outputs must not overlap the inputs.
+ * air_tile_relabel: air_prune_relabel's rule with C in 1..32 rows and S images: for j < num_objects[s] clipped to 0..C,
+ *   score[j,s] = score_src[j,s], obj_score[offsets[s] + j] = score_src[j,s], obj_step[offsets[s] + j] = kept_cand[j,s].             */
+AIR_ENGINE_API int air_tile_gather(const float *scenes, int S, int Hs, int Ws, int H, int W, int sy, int sx, float *windows,
+                    void *stream);
+AIR_ENGINE_API int air_tile_merge(const float *what, const float *where, const float *glimpse, const float *score, const int *num_objects,
+                    int T, int S, int A, int G, int Hs, int Ws, int H, int W, int sy, int sx, double iou_merge, float *what_out,
+                    float *where_out, float *glimpse_out, float *score_out, int *kept_cand, int *num_objects_out,
+                    signed char *cand_state, int *dup_of, int *merge_counts, void *stream);
+AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand, const int *num_objects, const int *offsets, int C,
+                    int S, float *score, float *obj_score, int *obj_step, void *stream);
+
 /* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
  * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
  * (AIR_E_SHAPE otherwise, and when R*H*W or R*(T+1)*(G+1) passes int32).  No floating-point atomics; float64 with contraction off
