@@ -207,6 +207,10 @@ SIGNATURES = {
     "air_tile_merge": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
                                P, P, P, P, P, P, P, P, P, P]),
     "air_tile_relabel": (c_int, [P, P, P, P, c_int, c_int, P, P, P, P]),
+    "air_track_associate": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                    c_int, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "air_track_owner": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
+    "air_track_score": (c_int, [P, P, P, P, ctypes.c_double, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
     "air_score_contingency": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "air_score_match": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "air_score_reduce": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, P]),

@@ -1,0 +1,522 @@
+// Tracking objects across the frames of a sequence for gfx950: per-frame parses in, identities out.
+//   air_track_associate: per sequence the frames walked in order INSIDE the kernel; a table of at most 32 live tracks, the float64
+//                        affinity of every (track, object) pair, greedy matching by a workgroup arg-max, births, ageing;
+//   air_track_owner:     the parse's owner maps relabelled from step to track id (int8 in, int16 out): a streaming pass;
+//   air_track_score:     CLEAR-MOT counts of the tracks against ground truth whose slot g is one object over a sequence.
+// Everything a float decides is float64 with contraction off; no floating-point atomics, no cross-workgroup traffic, one fixed order:
+// the same bits run to run.
+#include <math.h>
+#include <limits.h>
+#include "air_common.h"
+
+#define TRACK_THREADS 256
+#define TRACK_MAXT 32                    // PARSE_MAXT / SCORE_MAXT: objects per frame, and live tracks per sequence
+#define TRACK_MAXG 8                     // SCORE_MAXG
+#define TRACK_MAX_IDS 32767              // F * T: an id fits the int16 of track_owner
+
+enum { TRACK_ABSENT = 0, TRACK_MATCHED = 1, TRACK_BORN = 2, TRACK_UNCONFIRMED = 3, TRACK_OVERFLOW = 4, TRACK_NONFINITE = 5 };
+
+// air_score_match's float64 box IoU of two (left, top, width, height) boxes
+__device__ __forceinline__ double track_box_iou(const float4 a, const float4 b) {
+#pragma clang fp contract(off)
+    const double al = (double)a.x, at = (double)a.y, ar = (double)a.x + (double)a.z, ab = (double)a.y + (double)a.w;
+    const double bl = (double)b.x, bt = (double)b.y, br = (double)b.x + (double)b.z, bb = (double)b.y + (double)b.w;
+    const double ax0 = fmin(al, ar), ax1 = fmax(al, ar), ay0 = fmin(at, ab), ay1 = fmax(at, ab);
+    const double bx0 = fmin(bl, br), bx1 = fmax(bl, br), by0 = fmin(bt, bb), by1 = fmax(bt, bb);
+    const bool nan = (a.x != a.x) || (a.y != a.y) || (a.z != a.z) || (a.w != a.w) || (b.x != b.x) || (b.y != b.y) ||
+                     (b.z != b.z) || (b.w != b.w);
+    const double iw = fmax(0.0, fmin(ax1, bx1) - fmax(ax0, bx0)), ih = fmax(0.0, fmin(ay1, by1) - fmax(ay0, by0));
+    const double inter = iw * ih;
+    const double uni = ((ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0)) - inter;
+    const double q = inter / uni;
+    return (!nan && inter > 0.0 && uni > 0.0 && isfinite(q)) ? q : 0.0;
+}
+
+__device__ __forceinline__ bool track_finite4(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w); }
+
+// the better of two (value, key, position) candidates: the larger value, the lower key between equal values.  A candidate that is
+// no candidate carries value -1, key INT_MAX, position -1; a NaN is never stored as a value.
+__device__ __forceinline__ void track_take_better(double &v, int &key, int &pos, double ov, int okey, int opos) {
+    if (ov > v || (ov == v && okey < key)) {
+        v = ov;
+        key = okey;
+        pos = opos;
+    }
+}
+__device__ __forceinline__ void track_wave_argmax(double &v, int &key, int &pos) {      // valid in every lane
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(v, off, 64);
+        const int okey = __shfl_xor(key, off, 64), opos = __shfl_xor(pos, off, 64);
+        track_take_better(v, key, pos, ov, okey, opos);
+    }
+}
+
+// ============================================================================================================
+// associate
+// ============================================================================================================
+struct TrackAssocArgs {
+    const float *what, *boxes, *score;
+    const int *num_objects;
+    int *track_id, *prev_frame, *prev_slot, *num_tracks, *track_first, *track_last, *track_length, *track_gaps, *state_counts;
+    float *affinity;
+    signed char *obj_state;
+    double iou_gate, w, birth_score;
+    int T, S, F, A, max_age;
+};
+
+// One 256-thread workgroup per sequence.  Track slot k and object j < 32; pair p = k * 32 + j, four pairs per thread.
+__global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(TrackAssocArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double aff_s[TRACK_MAXT * TRACK_MAXT];              // aff of an admissible pair still open, -1 otherwise
+    __shared__ float4 obox_s[TRACK_MAXT], tbox_s[TRACK_MAXT];      // the frame's boxes; the tracks' last-sighting boxes
+    __shared__ float oscore_s[TRACK_MAXT], oaff_s[TRACK_MAXT];
+    __shared__ int ostate_s[TRACK_MAXT], oid_s[TRACK_MAXT], opf_s[TRACK_MAXT], ops_s[TRACK_MAXT];
+    __shared__ int t_live[TRACK_MAXT], t_id[TRACK_MAXT], t_f[TRACK_MAXT], t_j[TRACK_MAXT], t_age[TRACK_MAXT], t_len[TRACK_MAXT],
+        t_gaps[TRACK_MAXT];
+    __shared__ double wave_v[TRACK_THREADS / 64];
+    __shared__ int wave_key[TRACK_THREADS / 64], wave_pos[TRACK_THREADS / 64];
+    __shared__ int counts_s[6], next_id_s, nonfinite_s[TRACK_MAXT];
+    const int T = a.T, F = a.F, A = a.A, R = a.S * F, FT = F * T;
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (tid < TRACK_MAXT) {
+        t_live[tid] = 0;
+        nonfinite_s[tid] = 0;
+    }
+    if (tid < 6) counts_s[tid] = 0;
+    if (tid == 0) next_id_s = 0;
+    __syncthreads();
+
+    for (int f = 0; f < F; ++f) {
+        const int r = s * F + f;
+        int n = a.num_objects[r];
+        n = n < 0 ? 0 : (n > T ? T : n);
+        // ---- 1. object states: the boxes and scores by the first threads, the T x A `what` values by the whole workgroup ----------------
+        if (tid < TRACK_MAXT) {
+            const int j = tid;
+            float4 box = make_float4(0.f, 0.f, 0.f, 0.f);
+            float sc = 0.f;
+            if (j < n) {
+                const size_t row = (size_t)j * R + r;
+                box = *reinterpret_cast<const float4 *>(a.boxes + 4 * row);
+                sc = a.score[row];
+            }
+            obox_s[j] = box;
+            oscore_s[j] = sc;
+            oid_s[j] = -1;
+            opf_s[j] = -1;
+            ops_s[j] = -1;
+            oaff_s[j] = 0.f;
+        }
+        for (int e = tid; e < n * A; e += TRACK_THREADS) {
+            const int j = e / A, q = e - j * A;
+            if (!isfinite(a.what[((size_t)j * R + r) * A + q])) nonfinite_s[j] = 1;      // (every writer writes 1)
+        }
+        __syncthreads();
+        // ---- 2. affinity -----------------------------------------------------------------------------------------------------------
+        if (tid < TRACK_MAXT) {
+            const int j = tid;
+            const bool finite = track_finite4(obox_s[j]) && isfinite(oscore_s[j]) && !nonfinite_s[j];
+            ostate_s[j] = j < n ? (finite ? TRACK_UNCONFIRMED : TRACK_NONFINITE) : TRACK_ABSENT;      // (finite and open: settled below)
+        }
+        for (int p = tid; p < TRACK_MAXT * TRACK_MAXT; p += TRACK_THREADS) {
+            const int k = p >> 5, j = p & 31;
+            double val = -1.0;
+            if (t_live[k] && j < n && track_finite4(obox_s[j]) && isfinite(oscore_s[j]) && !nonfinite_s[j]) {
+                const double iou = track_box_iou(tbox_s[k], obox_s[j]);
+                const float *wk = a.what + ((size_t)t_j[k] * R + (size_t)s * F + t_f[k]) * A;      // read in place
+                const float *wj = a.what + ((size_t)j * R + r) * A;
+                double sum = 0.0;
+                int q = 0;
+                for (; q + 8 <= A; q += 8) {                       // eight loads of each row in flight, added in ascending a
+                    float x[8], y[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        x[u] = wk[q + u];
+                        y[u] = wj[q + u];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const double d = (double)x[u] - (double)y[u];
+                        sum = sum + d * d;
+                    }
+                }
+                for (; q < A; ++q) {
+                    const double d = (double)wk[q] - (double)wj[q];
+                    sum = sum + d * d;
+                }
+                const double msd = sum / (double)A;
+                const double aff = (1.0 - a.w) * iou + a.w / (1.0 + msd);
+                if (iou > a.iou_gate) val = aff;
+            }
+            aff_s[p] = val;
+        }
+        __syncthreads();
+        // ---- 3. greedy matching -----------------------------------------------------------------------------------------------------
+        for (;;) {
+            double v = -1.0;
+            int key = INT_MAX, pos = -1;
+#pragma unroll
+            for (int q = 0; q < TRACK_MAXT * TRACK_MAXT / TRACK_THREADS; ++q) {
+                const int p = tid + q * TRACK_THREADS;
+                const double x = aff_s[p];
+                if (x >= 0.0) track_take_better(v, key, pos, x, t_id[p >> 5] * TRACK_MAXT + (p & 31), p);
+            }
+            track_wave_argmax(v, key, pos);
+            if (lane == 0) {
+                wave_v[wid] = v;
+                wave_key[wid] = key;
+                wave_pos[wid] = pos;
+            }
+            __syncthreads();
+            v = wave_v[0], key = wave_key[0], pos = wave_pos[0];
+#pragma unroll
+            for (int q = 1; q < TRACK_THREADS / 64; ++q) track_take_better(v, key, pos, wave_v[q], wave_key[q], wave_pos[q]);
+            if (pos < 0) break;                                    // workgroup-uniform
+            const int k = pos >> 5, j = pos & 31;
+            if (tid == 0) {
+                ostate_s[j] = TRACK_MATCHED;
+                oid_s[j] = t_id[k];
+                opf_s[j] = t_f[k];
+                ops_s[j] = t_j[k];
+                oaff_s[j] = (float)v;
+                t_gaps[k] += t_age[k] > 0 ? 1 : 0;
+                t_age[k] = 0;
+                t_len[k] += 1;
+                t_f[k] = f;
+                t_j[k] = j;
+                tbox_s[k] = obox_s[j];
+            }
+            if (tid < TRACK_MAXT) {
+                aff_s[k * TRACK_MAXT + tid] = -1.0;
+                aff_s[tid * TRACK_MAXT + j] = -1.0;
+            }
+            __syncthreads();
+        }
+        // ---- 4. births ----------------------------------------------------------------------------------------------------------------
+        if (tid == 0) {
+            int next_id = next_id_s;
+            for (int j = 0; j < n; ++j) {
+                if (ostate_s[j] != TRACK_UNCONFIRMED || !((double)oscore_s[j] >= a.birth_score)) continue;
+                int k = 0;
+                while (k < TRACK_MAXT && t_live[k]) ++k;
+                if (k == TRACK_MAXT) {
+                    ostate_s[j] = TRACK_OVERFLOW;
+                    continue;
+                }
+                ostate_s[j] = TRACK_BORN;
+                oid_s[j] = next_id;
+                t_live[k] = 1;
+                t_id[k] = next_id;
+                t_f[k] = f;
+                t_j[k] = j;
+                t_age[k] = 0;
+                t_len[k] = 1;
+                t_gaps[k] = 0;
+                tbox_s[k] = obox_s[j];
+                a.track_first[(size_t)s * FT + next_id] = f;        // next_id < F * T: one id per object at most
+                ++next_id;
+            }
+            next_id_s = next_id;
+        }
+        __syncthreads();
+        // ---- 5. ageing, and the frame's rows -------------------------------------------------------------------------------------------
+        if (tid < TRACK_MAXT) {
+            const int k = tid;
+            nonfinite_s[k] = 0;                                     // (for the next frame: read last in step 2)
+            if (t_live[k] && t_f[k] != f) {
+                t_age[k] += 1;
+                if (t_age[k] > a.max_age) {
+                    const size_t at = (size_t)s * FT + t_id[k];
+                    a.track_last[at] = t_f[k];
+                    a.track_length[at] = t_len[k];
+                    a.track_gaps[at] = t_gaps[k];
+                    t_live[k] = 0;
+                }
+            }
+            if (tid < T) {
+                const size_t row = (size_t)tid * R + r;
+                const int state = ostate_s[tid];
+                a.track_id[row] = oid_s[tid];
+                a.obj_state[row] = (signed char)state;
+                a.affinity[row] = oaff_s[tid];
+                a.prev_frame[row] = opf_s[tid];
+                a.prev_slot[row] = ops_s[tid];
+                atomicAdd(&counts_s[state], 1);                     // integer adds in LDS: the order does not matter
+            }
+        }
+        __syncthreads();
+    }
+    // ---- the tracks alive at the end, the unused rows of the track tables, the counts -------------------------------------------------
+    if (tid < TRACK_MAXT && t_live[tid]) {
+        const size_t at = (size_t)s * FT + t_id[tid];
+        a.track_last[at] = t_f[tid];
+        a.track_length[at] = t_len[tid];
+        a.track_gaps[at] = t_gaps[tid];
+    }
+    const int issued = next_id_s;
+    for (int i = issued + tid; i < FT; i += TRACK_THREADS) {
+        const size_t at = (size_t)s * FT + i;
+        a.track_first[at] = -1;
+        a.track_last[at] = -1;
+        a.track_length[at] = 0;
+        a.track_gaps[at] = 0;
+    }
+    if (tid == 0) a.num_tracks[s] = issued;
+    if (tid < 6) a.state_counts[(size_t)s * 6 + tid] = counts_s[tid];
+}
+
+extern "C" int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
+                                   int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
+                                   int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
+                                   int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
+                                   int *state_counts, void *stream) {
+    AIR_REQUIRE(what && boxes && score && num_objects && track_id && obj_state && affinity && prev_frame && prev_slot && num_tracks &&
+                track_first && track_last && track_length && track_gaps && state_counts, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && S > 0 && F > 0 && A > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(iou_gate >= 0.0 && iou_gate < 1.0 && appearance_weight >= 0.0 && appearance_weight <= 1.0, AIR_E_SHAPE);
+    AIR_REQUIRE(birth_score >= 0.0 && birth_score <= 1.0 && max_age >= 0, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(boxes), AIR_E_ALIGN);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(what) | reinterpret_cast<uintptr_t>(score) | reinterpret_cast<uintptr_t>(num_objects) |
+                           reinterpret_cast<uintptr_t>(track_id) | reinterpret_cast<uintptr_t>(affinity) |
+                           reinterpret_cast<uintptr_t>(prev_frame) | reinterpret_cast<uintptr_t>(prev_slot) |
+                           reinterpret_cast<uintptr_t>(num_tracks) | reinterpret_cast<uintptr_t>(track_first) |
+                           reinterpret_cast<uintptr_t>(track_last) | reinterpret_cast<uintptr_t>(track_length) |
+                           reinterpret_cast<uintptr_t>(track_gaps) | reinterpret_cast<uintptr_t>(state_counts);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    const TrackAssocArgs a = {what, boxes, score, num_objects, track_id, prev_frame, prev_slot, num_tracks, track_first, track_last,
+                              track_length, track_gaps, state_counts, affinity, obj_state, iou_gate, appearance_weight, birth_score,
+                              T, S, F, A, max_age};
+    hipLaunchKernelGGL(track_associate_kernel, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// ============================================================================================================
+// owner
+// ============================================================================================================
+__device__ __forceinline__ unsigned track_owner_pair(unsigned bytes, int shift, const short *lut, int T) {
+    const int o0 = (int)(signed char)(bytes >> shift) + 1, o1 = (int)(signed char)(bytes >> (shift + 8)) + 1;
+    const unsigned lo = (unsigned short)((unsigned)o0 <= (unsigned)T ? lut[o0] : (short)-1);
+    const unsigned hi = (unsigned short)((unsigned)o1 <= (unsigned)T ? lut[o1] : (short)-1);
+    return lo | (hi << 16);
+}
+
+// One workgroup per image (grid-stride over the images); lut[o + 1] = the track id of step o, lut[0] = -1.  The body of an image is
+// read as 16-byte vectors from the first 16-byte boundary of its owner row on and written as two 16-byte (or four 8-byte) vectors
+// when the output is aligned to that at the same pixel; the pixels in front of the boundary and behind the last whole vector -- and
+// the whole image when the output is aligned to neither -- go one at a time.
+__global__ __launch_bounds__(TRACK_THREADS) void track_owner_kernel(const signed char *__restrict__ owner,
+                                                                    const int *__restrict__ track_id, int T, int R, int HW,
+                                                                    short *__restrict__ out) {
+    __shared__ short lut[TRACK_MAXT + 1];
+    const int tid = threadIdx.x;
+    for (int r = blockIdx.x; r < R; r += gridDim.x) {
+        if (tid <= T) lut[tid] = tid == 0 ? (short)-1 : (short)track_id[(size_t)(tid - 1) * R + r];
+        __syncthreads();
+        const signed char *po = owner + (size_t)r * HW;
+        short *pt = out + (size_t)r * HW;
+        int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(po) & 15u)) & 15u);
+        if (head > HW) head = HW;
+        const unsigned out_mis = (unsigned)(reinterpret_cast<uintptr_t>(pt + head) & 15u);
+        int nvec = (HW - head) >> 4;
+        if (out_mis != 0 && out_mis != 8) {                        // every pixel on the word path
+            head = HW;
+            nvec = 0;
+        }
+        const int tail0 = head + 16 * nvec;
+        const uint4 *vo = reinterpret_cast<const uint4 *>(po + head);
+        for (int v = tid; v < nvec; v += TRACK_THREADS) {
+            const uint4 b = vo[v];
+            const uint4 lo = make_uint4(track_owner_pair(b.x, 0, lut, T), track_owner_pair(b.x, 16, lut, T),
+                                        track_owner_pair(b.y, 0, lut, T), track_owner_pair(b.y, 16, lut, T));
+            const uint4 hi = make_uint4(track_owner_pair(b.z, 0, lut, T), track_owner_pair(b.z, 16, lut, T),
+                                        track_owner_pair(b.w, 0, lut, T), track_owner_pair(b.w, 16, lut, T));
+            short *dst = pt + head + 16 * v;
+            if (out_mis == 0) {
+                reinterpret_cast<uint4 *>(dst)[0] = lo;
+                reinterpret_cast<uint4 *>(dst)[1] = hi;
+            } else {
+                reinterpret_cast<uint2 *>(dst)[0] = make_uint2(lo.x, lo.y);
+                reinterpret_cast<uint2 *>(dst)[1] = make_uint2(lo.z, lo.w);
+                reinterpret_cast<uint2 *>(dst)[2] = make_uint2(hi.x, hi.y);
+                reinterpret_cast<uint2 *>(dst)[3] = make_uint2(hi.z, hi.w);
+            }
+        }
+        const int n_edge = head + (HW - tail0);
+        for (int e = tid; e < n_edge; e += TRACK_THREADS) {
+            const int p = e < head ? e : tail0 + (e - head);
+            const int o = (int)po[p] + 1;
+            pt[p] = (unsigned)o <= (unsigned)T ? lut[o] : (short)-1;
+        }
+        __syncthreads();                                           // the table is rewritten for the next image
+    }
+}
+
+extern "C" int air_track_owner(const signed char *owner, const int *track_id, int T, int R, int H, int W, short *track_owner,
+                               void *stream) {
+    AIR_REQUIRE(owner && track_id && track_owner, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && R > 0 && H > 0 && W > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)H * W <= (long)INT_MAX && (long)R * H * W <= (long)INT_MAX && (long)R * T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE((reinterpret_cast<uintptr_t>(track_id) & 3u) == 0 && (reinterpret_cast<uintptr_t>(track_owner) & 1u) == 0, AIR_E_ALIGN);
+    const int cap = 256 * 16;
+    hipLaunchKernelGGL(track_owner_kernel, dim3((unsigned)(R < cap ? R : cap)), dim3(TRACK_THREADS), 0, air_stream(stream), owner,
+                       track_id, T, R, H * W, track_owner);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// ============================================================================================================
+// score
+// ============================================================================================================
+struct TrackScoreArgs {
+    const float *boxes, *gt_boxes;
+    const int *num_objects, *track_id;
+    int *seq_counts, *gt_match;
+    double *seq_iou;
+    double tau;
+    int T, G, S, F;
+};
+
+// One workgroup of one wavefront per sequence.  Pair p = g * 32 + j, four pairs per lane.
+__global__ __launch_bounds__(64) void track_score_kernel(TrackScoreArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double iou_s[TRACK_MAXG * TRACK_MAXT];
+    __shared__ float4 hbox_s[TRACK_MAXT], gbox_s[TRACK_MAXG];
+    __shared__ int hid_s[TRACK_MAXT], jused_s[TRACK_MAXT];         // a hypothesis' track id (-1: no hypothesis); taken by a match
+    __shared__ int gpresent_s[TRACK_MAXG], gm_s[TRACK_MAXG], cand_s[TRACK_MAXG], map_s[TRACK_MAXG], tracked_s[TRACK_MAXG],
+        frames_s[TRACK_MAXG];
+    const int T = a.T, G = a.G, F = a.F, R = a.S * F;
+    const int s = blockIdx.x, lane = threadIdx.x;
+    if (lane < TRACK_MAXG) {
+        map_s[lane] = -1;
+        tracked_s[lane] = 0;
+        frames_s[lane] = 0;
+    }
+    int n_gt = 0, n_match = 0, n_miss = 0, n_fp = 0, n_idsw = 0;   // lane 0's
+    double sum_iou = 0.0;
+    __syncthreads();
+    for (int f = 0; f < F; ++f) {
+        const int r = s * F + f;
+        int n = a.num_objects[r];
+        n = n < 0 ? 0 : (n > T ? T : n);
+        if (lane < TRACK_MAXT) {
+            const int j = lane;
+            float4 box = make_float4(0.f, 0.f, 0.f, 0.f);
+            int id = -1;
+            if (j < n) {
+                const size_t row = (size_t)j * R + r;
+                box = *reinterpret_cast<const float4 *>(a.boxes + 4 * row);
+                const int t = a.track_id[row];
+                if (t >= 0 && track_finite4(box)) id = t;
+            }
+            hbox_s[j] = box;
+            hid_s[j] = id;
+            jused_s[j] = 0;
+        }
+        if (lane < TRACK_MAXG) {
+            const int g = lane;
+            float4 gb = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (g < G) gb = *reinterpret_cast<const float4 *>(a.gt_boxes + 4 * ((size_t)r * G + g));
+            gbox_s[g] = gb;
+            gpresent_s[g] = (g < G && gb.z > 0.f) ? 1 : 0;
+            gm_s[g] = -1;
+        }
+        __syncthreads();
+        for (int p = lane; p < TRACK_MAXG * TRACK_MAXT; p += 64) {
+            const int g = p >> 5, j = p & 31;
+            iou_s[p] = (gpresent_s[g] && hid_s[j] >= 0) ? track_box_iou(gbox_s[g], hbox_s[j]) : 0.0;
+        }
+        __syncthreads();
+        // ---- 1. a remembered track that is still on its object keeps it (ascending g; a hypothesis is taken once) -------------------
+        if (lane < TRACK_MAXG) {
+            const int g = lane;
+            int cand = -1;
+            if (gpresent_s[g] && map_s[g] >= 0)
+                for (int j = 0; j < T && cand < 0; ++j)
+                    if (hid_s[j] == map_s[g] && iou_s[g * TRACK_MAXT + j] > a.tau) cand = j;
+            cand_s[g] = cand;
+        }
+        __syncthreads();
+        if (lane == 0)
+            for (int g = 0; g < G; ++g) {
+                const int c = cand_s[g];
+                if (c >= 0 && !jused_s[c]) {
+                    gm_s[g] = c;
+                    jused_s[c] = 1;
+                }
+            }
+        __syncthreads();
+        // ---- 2. the rest greedily by IoU ---------------------------------------------------------------------------------------------------
+        for (;;) {
+            double v = -1.0;
+            int key = INT_MAX, pos = -1;
+#pragma unroll
+            for (int q = 0; q < TRACK_MAXG * TRACK_MAXT / 64; ++q) {
+                const int p = lane + q * 64, g = p >> 5, j = p & 31;
+                const double x = iou_s[p];
+                if (gpresent_s[g] && gm_s[g] < 0 && hid_s[j] >= 0 && !jused_s[j] && x > a.tau) track_take_better(v, key, pos, x, p, p);
+            }
+            track_wave_argmax(v, key, pos);
+            if (pos < 0) break;                                    // wave-uniform
+            if (lane == 0) {
+                gm_s[pos >> 5] = pos & 31;
+                jused_s[pos & 31] = 1;
+            }
+            __syncthreads();
+        }
+        __syncthreads();
+        // ---- 3., 4. switches and counters -----------------------------------------------------------------------------------------------------
+        const int unmatched = __popcll(__ballot(lane < TRACK_MAXT && hid_s[lane & 31] >= 0 && !jused_s[lane & 31]));
+        if (lane < G) a.gt_match[(size_t)r * G + lane] = gm_s[lane];
+        if (lane == 0) {
+            n_fp += unmatched;
+            for (int g = 0; g < G; ++g) {
+                if (!gpresent_s[g]) continue;
+                ++n_gt;
+                frames_s[g] += 1;
+                const int j = gm_s[g];
+                if (j < 0) {
+                    ++n_miss;
+                    continue;
+                }
+                ++n_match;
+                tracked_s[g] += 1;
+                sum_iou = sum_iou + iou_s[g * TRACK_MAXT + j];
+                const int id = hid_s[j];
+                n_idsw += (map_s[g] >= 0 && map_s[g] != id) ? 1 : 0;
+                map_s[g] = id;
+            }
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        int mt = 0, ml = 0, objects = 0;
+        for (int g = 0; g < G; ++g) {
+            if (frames_s[g] <= 0) continue;
+            ++objects;
+            mt += 5 * tracked_s[g] >= 4 * frames_s[g] ? 1 : 0;
+            ml += 5 * tracked_s[g] <= frames_s[g] ? 1 : 0;
+        }
+        int *c = a.seq_counts + (size_t)s * 8;
+        c[0] = n_gt, c[1] = n_match, c[2] = n_miss, c[3] = n_fp, c[4] = n_idsw, c[5] = mt, c[6] = ml, c[7] = objects;
+        a.seq_iou[s] = sum_iou;
+    }
+}
+
+extern "C" int air_track_score(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
+                               int T, int G, int S, int F, int R, int *seq_counts, double *seq_iou, int *gt_match, void *stream) {
+    AIR_REQUIRE(boxes && num_objects && track_id && gt_boxes && seq_counts && seq_iou && gt_match, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && G >= 1 && G <= TRACK_MAXG && S > 0 && F > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(tau >= 0.0 && tau <= 1.0, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(boxes) && air_aligned16(gt_boxes) && (reinterpret_cast<uintptr_t>(seq_iou) & 7u) == 0, AIR_E_ALIGN);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(num_objects) | reinterpret_cast<uintptr_t>(track_id) |
+                           reinterpret_cast<uintptr_t>(seq_counts) | reinterpret_cast<uintptr_t>(gt_match);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    const TrackScoreArgs a = {boxes, gt_boxes, num_objects, track_id, seq_counts, gt_match, seq_iou, tau, T, G, S, F};
+    hipLaunchKernelGGL(track_score_kernel, dim3((unsigned)S), dim3(64), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}

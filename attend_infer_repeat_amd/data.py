@@ -257,6 +257,95 @@ def procedural_multi_mnist(n_samples, canvas_size=(50, 50), n_objects=(0, 2), se
                               seed=seed + 1, return_annotations=return_annotations)
 
 
+# ---- sequences with known identities ------------------------------------------------------------------------------------------
+def _bounce(p0, velocity, frames, free):
+    """the coordinate of a point that starts at p0 in [0, free], moves `velocity` pixels per frame and reflects off 0 and `free`, at
+    the given frame numbers (float64, not yet rounded): the triangle wave of period 2 free through p0"""
+    p = np.asarray(p0, np.float64) + np.asarray(frames, np.float64) * np.float64(velocity)
+    if free <= 0:
+        return np.zeros_like(p)
+    m = np.mod(p, 2.0 * free)
+    return np.where(m <= free, m, 2.0 * free - m)
+
+
+def create_moving_mnist(templates, n_sequences, n_frames, canvas_size=(50, 50), obj_size=(28, 28), n_objects=(0, 2),
+                        speed=(1.0, 3.0), spans=False, seed=0, rng=None, return_annotations=False):
+    """Sequences of multi-digit canvases with known identities: every object keeps its template (the `_tight_box` crop of
+    create_multi_mnist) over its sequence, starts at a uniformly drawn position inside the canvas, moves in a straight line at a drawn
+    direction and speed (pixels per frame) and reflects off the canvas edges (`_bounce`); its top-left corner is rounded to integer
+    pixels per frame (np.round).  Objects may overlap: pixels combine by np.maximum, and in `instances` the object with the higher
+    slot wins where both are > 0.  spans=True: every object is present only on a drawn interval [first, last] of frames, so births
+    and deaths occur.
+
+    Draws on `rng` (a numpy RandomState, default RandomState(seed)), in this order:  randint(max + 1, size=n_sequences) for the object
+    counts (max = the largest entry of n_objects);  then per sequence with n > 0 objects choice(n_templates, n, replace=False), and per
+    object j in slot order  rand(2) -> (y0, x0) = rand * (H - h, W - w),  rand() -> the direction 2 pi rand,  rand() -> the speed
+    speed[0] + rand * (speed[1] - speed[0]),  and with spans=True  randint(n_frames, size=2) -> first = min, last = max.  A fixed
+    seed gives the same bytes every time.
+
+    Returns dict(imgs [S, F, H, W] uint8, nums [S, F] int32: the objects present per frame); return_annotations=True adds boxes
+    [S, F, G, 4] float32, (left, top, width, height) in create_multi_mnist's convention with slot = identity and zero rows where the
+    object is absent (G = max), and instances [S, F, H, W] int8 (-1 = background)."""
+    rng = np.random.RandomState(seed) if rng is None else rng
+    templates = np.asarray(templates)
+    if templates.dtype != np.uint8:
+        templates = np.stack([_to_uint8(t) for t in templates])
+    templates = _resize_templates(templates, obj_size)
+    n_templates = templates.shape[0]
+    S, F = int(n_sequences), int(n_frames)
+    G = int(max(np.atleast_1d(n_objects)))
+    H, W = canvas_size
+    lo, hi = (float(v) for v in speed)
+    if S < 1 or F < 1 or G < 1 or not 0.0 <= lo <= hi:
+        raise ValueError("create_moving_mnist: n_sequences, n_frames, max(n_objects) >= 1 and 0 <= speed[0] <= speed[1], got %r"
+                         % ((n_sequences, n_frames, n_objects, speed),))
+    imgs = np.zeros((S, F, H, W), np.uint8)
+    nums = np.zeros((S, F), np.int32)
+    boxes = np.zeros((S, F, G, 4), np.float32)
+    instances = np.full((S, F, H, W), -1, np.int8)
+    counts = rng.randint(G + 1, size=S)
+    frames = np.arange(F)
+    for s in range(S):
+        n = int(counts[s])
+        if n == 0:
+            continue
+        idx = rng.choice(n_templates, n, replace=False)
+        for j in range(n):
+            k = int(idx[j])
+            (y0, x0), (sh, sw) = _tight_box(templates[k])
+            if sh > H or sw > W:
+                raise ValueError("template box %s does not fit the canvas %s" % ((sh, sw), (H, W)))
+            crop = templates[k, y0:y0 + sh, x0:x0 + sw]
+            start = rng.rand(2) * np.asarray([H - sh, W - sw], np.float64)
+            theta = 2.0 * np.pi * rng.rand()
+            v = lo + rng.rand() * (hi - lo)
+            first, last = 0, F - 1
+            if spans:
+                a, b = rng.randint(F, size=2)
+                first, last = int(min(a, b)), int(max(a, b))
+            ys = np.round(_bounce(start[0], v * np.sin(theta), frames, H - sh)).astype(np.int64)
+            xs = np.round(_bounce(start[1], v * np.cos(theta), frames, W - sw)).astype(np.int64)
+            for f in range(first, last + 1):
+                y, x = int(ys[f]), int(xs[f])
+                view = imgs[s, f, y:y + sh, x:x + sw]
+                np.maximum(view, crop, out=view)
+                inst = instances[s, f, y:y + sh, x:x + sw]
+                inst[crop > 0] = j
+                boxes[s, f, j] = (x, y, sw, sh)
+                nums[s, f] += 1
+    if return_annotations:
+        return dict(imgs=imgs, nums=nums, boxes=boxes, instances=instances)
+    return dict(imgs=imgs, nums=nums)
+
+
+def procedural_moving_mnist(n_sequences, n_frames, canvas_size=(50, 50), n_objects=(0, 2), speed=(1.0, 3.0), spans=False, seed=0,
+                            n_templates=4000, return_annotations=False):
+    """create_moving_mnist over procedural digit templates, as procedural_multi_mnist wraps create_multi_mnist"""
+    templates, _ = procedural_digit_templates(n_templates, seed=seed)
+    return create_moving_mnist(templates, n_sequences, n_frames, canvas_size=canvas_size, n_objects=n_objects, speed=speed,
+                               spans=spans, seed=seed + 1, return_annotations=return_annotations)
+
+
 def load_mnist_idx(directory, partition="train"):
     """MNIST digits from the standard idx-ubyte files (train-images-idx3-ubyte[.gz], ...), for create_multi_mnist.
     (The reference downloads them through tensorflow.examples.tutorials.mnist, data.py:38; there is no network here.)"""

@@ -433,6 +433,91 @@ def make_tiled_parse_score_logger(air, data, num_batches, name, batch_size=None,
     return logger
 
 
+def make_track_fig(frames, result, max_frames=8, checkpoint_dir=None, global_step=None, n_samples=4):
+    """The tracks of sequences (AIRonMNIST.track / track.SequenceTracker.track): one row per sequence, one panel per frame (the first
+    `max_frames`), the frame with the attention box of every object that has a track, coloured by track id (rect_stn on `where`); an
+    object without a track is drawn thin and white.  frames [S, F, H, W], result: the dict `track` returned.  Saved as
+    track_fig_<global_step>.png when a directory is given."""
+    import os.path as osp
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    import torch
+    host = lambda t: torch.as_tensor(t).detach().cpu().numpy()
+    x, ids, where, n = host(frames), host(result["track_id"]), host(result["where"]), host(result["num_objects"])
+    S, F, H, W = x.shape
+    T = ids.shape[0]
+    rows, cols = min(n_samples, S), min(int(max_frames), F)
+    inch = 1.5
+    fig, axes = plt.subplots(rows, cols, figsize=(inch * cols * W / max(H, W), inch * rows * H / max(H, W)), squeeze=False)
+    colours = plt.get_cmap('tab20')
+    for s in range(rows):
+        for f in range(cols):
+            r, ax = s * F + f, axes[s][f]
+            ax.imshow(x[s, f], cmap='gray', vmin=0, vmax=1)
+            for j in range(min(T, max(int(n[r]), 0))):
+                if ids[j, r] >= 0:
+                    rect_stn(ax, W, H, where[j, r], colours(int(ids[j, r]) % 20), line_width=1)
+                else:
+                    rect_stn(ax, W, H, where[j, r], 'white', line_width=.3)
+            ax.set_axis_off()
+    if checkpoint_dir is not None:
+        fig.savefig(osp.join(checkpoint_dir, 'track_fig_{}.png'.format(global_step)), dpi=300)
+        plt.close(fig)
+    return fig
+
+
+def make_track_score_logger(air, data, num_batches, name, batch_size=None, writer=None, tau=0.5, measure_time=True, iou_gate=None,
+                            appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None,
+                            propose=None):
+    """make_tiled_parse_score_logger's counterpart for sequences (air.score_track): `data` is an annotated dataset dict of SEQUENCES
+    (imgs [N, F, H, W], boxes [N, F, G, 4], instances [N, F, H, W] int8 -- data.create_moving_mnist with return_annotations=True),
+    walked in `num_batches` batches of `batch_size` sequences (None: the model's batch size).  Prints / writes the identity figures
+    (MOTA, MOTP, identity switches, mostly tracked / lost), the per-frame detection figures of the same parses (count accuracy, mAP)
+    and the totals of the association's object states (track_matched, track_born, track_unconfirmed, track_overflow,
+    track_nonfinite) and the tracks issued."""
+    import torch
+    from .track import STATES
+    tk = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
+              refine_lr=refine_lr, prune=prune, propose=propose)
+
+    def logger(itr=0, num_batches_to_eval=None, write=True):
+        n = num_batches if num_batches_to_eval is None else num_batches_to_eval
+        S = int(air.obs.shape[0]) if batch_size is None else int(batch_size)
+        n = min(max(int(n), 1), int(data["imgs"].shape[0]) // S)
+        if n < 1:
+            raise ValueError("the annotated dataset holds fewer sequences than one batch of %d" % S)
+        start = time.time()
+        dev = air.obs.device
+        states, issued = torch.zeros(6, dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
+        tracker = None
+        for i in range(n):
+            sl = slice(i * S, (i + 1) * S)
+            _, tracker = air.score_track(torch.as_tensor(data["imgs"][sl], dtype=torch.float32).to(dev), torch.as_tensor(data["boxes"][sl]),
+                                         tau=tau, accumulate=i > 0, gt_instances=torch.as_tensor(data["instances"][sl]), **tk)
+            states += air.tracked["state_counts"].sum(0)
+            issued += air.tracked["num_tracks"].sum()
+        acc = tracker.summary()
+        det = air.track_scorer.summary()
+        acc.update(count_acc=det["count_acc"], map=det["map"], frames=det["images"], objects_pred=det["objects_pred"],
+                   tracks=int(issued.item()))
+        for k, v in zip(STATES[1:], states.tolist()[1:]):
+            acc["track_" + k] = v
+        shown = ["mota", "motp", "id_switches", "mostly_tracked", "mostly_lost", "count_acc", "map", "tracks"]
+        t = time.time() - start
+        msg = 'Step {}, Data {} track score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
+        if measure_time:
+            msg += ', eval time = {:.4}s'.format(t)
+        print(msg)
+        if write and writer is not None:
+            rec = dict(step=int(itr), data=name + "_track_score", n_frames=int(data["imgs"].shape[1]), tau=float(tau),
+                       iou_gate=tracker.iou_gate, appearance_weight=tracker.appearance_weight, birth_score=tracker.birth_score,
+                       max_age=tracker.max_age, **acc)
+            writer.write(json.dumps(rec) + "\n"); writer.flush()
+        return acc
+    return logger
+
+
 def gradient_summaries(named_grads, named_vars, norm=True, ratio=True, histogram=False, bins=30):
     """evaluation.py:221-248: the global norm of the gradient, per variable mean(|g| / (|v| + 1e-8)) (log_ratio,
     evaluation.py:169-180) and -- histogram=True, the reference's default -- a histogram of every gradient tensor, the content of its

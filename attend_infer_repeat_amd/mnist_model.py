@@ -561,6 +561,107 @@ class AIRonMNIST(AIRModel):
         self.parse_scores_tiled = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores_tiled, s
 
+    MAX_TRACKERS = 2
+
+    def tracker(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
+                refine_lr=None, prune=None, propose=None):
+        """the track.SequenceTracker behind `track`: one per (n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age,
+        refine, refine_lr, prune, propose), over a provider stack of its own at n_sequences * n_frames rows -- a SceneParser, behind it
+        the refiner / pruner / proposer asked for -- so the parsers of `parse` and `self.obs` are never touched.  None for one of the
+        four association arguments: track.DEFAULTS (provisional).  Built and captured on first use; the least recently used one is
+        dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
+        eng = getattr(self, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("track needs the fused engine: call train_step(...) with an engine-eligible "
+                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        if prune is not None and propose is not None:
+            raise ValueError("track: prune together with propose is not supported; pass one of them")
+        from . import track as tr
+        from .parse import SceneParser
+        from .refine import DEFAULT_LR
+        given = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age)
+        assoc = {k: (tr.DEFAULTS[k] if v is None else v) for k, v in given.items()}
+        S, F = int(n_sequences), int(n_frames)
+        tr.check_arguments(eng.cfg.max_steps, F, S * F if S >= 1 else None, **assoc)
+        if S < 1:
+            raise ValueError("track: at least one sequence, got %r" % (n_sequences,))
+        lr = None if refine is None else tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
+        spec = propose if not isinstance(propose, list) else tuple(propose)
+        key = (S, F, float(assoc["iou_gate"]), float(assoc["appearance_weight"]), float(assoc["birth_score"]), int(assoc["max_age"]),
+               refine, lr, prune, spec, str(eng.device))
+        cache = self.__dict__.setdefault("_trackers", {})
+        entry = cache.pop(key, None)
+        if entry is None:
+            stack = [SceneParser(eng.cfg, S * F, device=eng.device)]
+            if refine is not None:
+                from .refine import ParseRefiner
+                stack.append(ParseRefiner(stack[-1], int(refine), lr[0], lr[1]))
+            if prune is not None:
+                from .prune import ParsePruner
+                stack.append(ParsePruner(stack[-1], prune))
+            if propose is not None:
+                from .propose import ParseProposer
+                p = (int(propose), 1) if not isinstance(propose, (tuple, list)) else tuple(int(v) for v in propose)
+                stack.append(ParseProposer(stack[-1], p[0], p[1]))
+            stack.append(tr.SequenceTracker(stack[-1], F, **assoc))
+            for s in stack:
+                s.capture()
+            entry = stack
+        cache[key] = entry                                         # most recently used last
+        while len(cache) > self.MAX_TRACKERS:
+            for s in reversed(cache.pop(next(iter(cache)))):
+                s.release_graphs()
+        return entry[-1]
+
+    def track(self, frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None,
+              prune=None, propose=None):
+        """Parse the frames [S, F, H, W] of S sequences on the device, each frame as `parse(refine=, prune=, propose=)` would parse
+        it, and give the objects identities over time (track.SequenceTracker.track lists the returned device tensors: the parse of
+        the S * F frames, row s * F + f, and next to it track_id, obj_state, affinity, prev_frame, prev_slot, the per-track tables and
+        track_owner; the next call overwrites them).  The training engine's parameters are read, nothing of it is written;
+        `self.obs` and the parsers of `parse` are not touched."""
+        import torch
+        frames = torch.as_tensor(frames)
+        if frames.dim() != 4:
+            raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
+        t = self.tracker(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
+                         propose)
+        self._sync_engine_switches()
+        t.load_from(self._engine)                            # every time: the weights move
+        self.tracked = t.track(frames)
+        return self.tracked
+
+    def score_track(self, frames, gt_boxes, tau=0.5, accumulate=True, gt_instances=None, thresholds=None, iou_gate=None,
+                    appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None):
+        """`track`, then the identity metric of the tracks against gt_boxes [S, F, G, 4] (G <= 8; slot g is the same object in every
+        frame of a sequence, width <= 0 = absent) on the device (track.SequenceTracker.score).  The sums accumulate in the tracker
+        this returns alongside -- (scores, tracker): its summary() reads MOTA, MOTP, the identity switches and the mostly tracked /
+        lost fractions back once, its reset() starts a validation set.  With gt_instances [S, F, H, W] (int8, -1 = background) the
+        S * F frames are also scored as images by a score.ParseScorer bound to the same provider (per-frame detection figures next to
+        the identity figures): scores["detection"] holds its tensors, `self.track_scorer` is that scorer."""
+        import torch
+        self.track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose)
+        frames = torch.as_tensor(frames)
+        t = self.tracker(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
+                         propose)
+        gb = torch.as_tensor(gt_boxes)
+        scores = dict(t.score(gb, tau, accumulate))
+        if gt_instances is not None:
+            from .score import DEFAULT_THRESHOLDS, ParseScorer
+            th = tuple(float(v) for v in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
+            G = int(gb.shape[-2])
+            s = getattr(self, "track_scorer", None)
+            if s is None or s.parser is not t.provider or s.G != G or s.thresholds_host != th:
+                if s is not None:
+                    s.release_graphs()
+                s = ParseScorer(t.provider, G, th)
+                s.capture()
+                self.track_scorer = s
+            gi = torch.as_tensor(gt_instances)
+            scores["detection"] = s.score(gi.reshape((t.R,) + tuple(gi.shape[-2:])), gb.reshape(t.R, G, 4), accumulate=accumulate)
+        self.track_scores = scores
+        return scores, t
+
     def refresh(self):
         """Re-expose the engine's current buffers under the reference's attribute names."""
         if self._engine is not None:

@@ -114,6 +114,13 @@ def main(argv=None):
                          "--parse-prune and --parse-propose apply to every window")
     ap.add_argument("--parse-tiled-objects", type=int, default=4, metavar="N",
                     help="with --parse-tiled: a scene holds 0..N digits (N <= 8, the ground-truth slots of the scorer)")
+    ap.add_argument("--track-eval", default=None, metavar="F[:SPEED]",
+                    help="at every --log-every also track held-out SEQUENCES of F frames on the model's canvas and score the identities "
+                         "on the device (AIRonMNIST.score_track, track.SequenceTracker, evaluation.make_track_score_logger): MOTA, MOTP, "
+                         "identity switches, mostly tracked / lost, next to the per-frame count accuracy and mAP.  The sequences are "
+                         "procedural digits that move in straight lines at up to SPEED pixels per frame (default 3) and reflect off "
+                         "the canvas edges (data.procedural_moving_mnist, with births and deaths); --parse-refine, --parse-prune and "
+                         "--parse-propose apply to every frame")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -161,6 +168,20 @@ def main(argv=None):
         if args.parse_particles > 0:
             ap.error("--parse-tiled does not go with --parse-particles: particle providers are out of scope for tiling")
         tiled = dict(scene=scene, stride=None if stride is None else (stride * 2)[:2])
+
+    track_eval = None
+    if args.track_eval is not None:
+        try:
+            frames, _, top = args.track_eval.partition(":")
+            track_eval = dict(frames=int(frames), speed=float(top) if top else 3.0)
+        except ValueError:
+            ap.error("--track-eval needs F or F:SPEED (F: frames per sequence, SPEED: pixels per frame), got %r" % args.track_eval)
+        if not 1 <= track_eval["frames"] <= 32767 // 3:
+            ap.error("--track-eval needs 1 <= F <= %d (F * max_steps track ids must fit int16)" % (32767 // 3))
+        if not track_eval["speed"] >= 0.0 or track_eval["speed"] == float("inf"):
+            ap.error("--track-eval needs a finite SPEED >= 0, got %r" % args.track_eval)
+        if args.parse_particles > 0:
+            ap.error("--track-eval does not go with --parse-particles: particle providers are out of scope for tracking")
 
     learning_rate, n_steps, batch_size = args.learning_rate, 3, 64    # multi_mnist.py:24-25,37
     num_steps_prior = AttrDict(anneal='exp', init=1. - 1e-15, final=1e-7, steps_div=1e4, steps=1e5, hold_init=1e3)
@@ -300,6 +321,23 @@ def main(argv=None):
         def log(train_itr):                               # noqa: F811
             out = before_tiled_log(train_itr)
             tiled_log(train_itr)
+            return out
+
+    if track_eval is not None:
+        from attend_infer_repeat_amd.data import procedural_moving_mnist
+        from attend_infer_repeat_amd.evaluation import make_track_score_logger
+        sequences_per_batch = 16
+        raw = procedural_moving_mnist(sequences_per_batch * max(args.eval_batches, 1), track_eval["frames"],
+                                      canvas_size=tuple(int(v) for v in air.obs.shape[-2:]),
+                                      n_objects=(0, 2), speed=(min(1.0, track_eval["speed"]), track_eval["speed"]), spans=True,
+                                      seed=args.seed + 2000, n_templates=256, return_annotations=True)
+        seq_data = dict(imgs=raw["imgs"].astype("float32") / 255.0, boxes=raw["boxes"], instances=raw["instances"])
+        before_track_log = log
+        track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, **refine_kw)
+
+        def log(train_itr):                               # noqa: F811
+            out = before_track_log(train_itr)
+            track_log(train_itr)
             return out
 
     train_itr = int(global_step)

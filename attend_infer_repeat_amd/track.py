@@ -1,0 +1,483 @@
+"""Tracking objects across the frames of a sequence on the device: the per-frame parses of a bound provider in, identities out.
+
+A sequence of F frames is F rows of a parser, and its parse is F unrelated object lists: slot t of frame f has nothing to do with slot
+t of frame f + 1.  This module associates them -- tracking by association: no latent is carried from one frame into the next frame's
+inference, the assignment is greedy (the house rule of air_score_match and air_tile_merge), and the metric is CLEAR-MOT.
+
+Layout.  The provider has R = S F rows, sequence-major: row r = s F + f (the tile layout r = s Nw + v, with frames for windows).
+1 <= T <= 32 objects per frame, F T <= 32767 (a track id fits the int16 of `track_owner`).
+
+The association rule (air_track_associate; include/air_hip.h states the same).  Each sequence on its own, the frames in ascending order,
+a table of at most 32 LIVE tracks: slot, id, the (frame, slot) of the last sighting, age (frames since that sighting), length, gaps.
+For frame f with n = clip(num_objects[r], 0, T), in this order:
+  1. states: object j >= n is ABSENT; j < n is NONFINITE if any of its four box values, its score or its A `what` values is not finite,
+     and takes no further part.
+  2. affinity of every live track k and finite object j:  iou = air_score_match's float64 box IoU of the track's last-sighting box and
+     the object's box;  msd = (sum_a (what_k[a] - what_j[a])^2) / A in float64 from the widened fp32 values, summed in ascending a;
+     aff = (1 - w) * iou + w / (1 + msd).  Admissible iff iou > iou_gate, strictly.  No transcendental function: device and numpy agree
+     to the bit.
+  3. greedy matching: while an admissible pair of an unmatched track and an unmatched object exists, the one with the largest aff (equal
+     aff: the lower track id, then the lower j): the object is MATCHED with the track's id, prev_frame / prev_slot = the track's last
+     sighting, affinity = aff rounded once to fp32;  the track: gaps += (age > 0), age = 0, length += 1, last sighting (f, j).
+  4. births: the unmatched finite objects in ascending j:  score >= birth_score: BORN with id = next_id++ in the lowest free slot, or
+     OVERFLOW (id -1) when no slot is free;  score < birth_score: UNCONFIRMED (id -1).  Matching ignores birth_score, so an object
+     below it still continues an existing track.
+  5. ageing: every live track neither matched nor born in this frame gets age += 1; one with age > max_age is retired, its slot is
+     free from frame f + 1 on.  Ids are never reused.
+So a track survives max_age frames without a sighting: with max_age = 1 an object missing in one frame comes back under its id, and a
+slot held by a track last seen in frame f is free again in frame f + max_age + 2.
+
+The identity metric (air_track_score).  gt_boxes [R, G, 4], G <= 8: ground-truth slot g is the SAME object in every frame of a sequence,
+width <= 0 = absent in that frame.  The hypotheses of a frame are its objects j < n with track_id >= 0 and finite boxes.  map[g] = none
+at the start of a sequence.  Per frame:
+  1. for g ascending: a present g whose map[g] is the id of a hypothesis j not yet taken with iou(gt_g, box_j) > tau keeps j;
+  2. the remaining present g and hypotheses greedily by float64 IoU descending, strictly > tau (equal: the lower g, then the lower j);
+  3. for every matched (g, j) in ascending g: idsw += (map[g] exists and != id_j), then map[g] = id_j (map persists while g is unmatched
+     or absent);
+  4. gt += present g, matches, misses += present unmatched g, fp += unmatched hypotheses, sum_iou += the matches' iou (float64, frame
+     order, then g order), tracked[g] / present[g] += 1.
+seq_counts [S, 8] = {gt, matches, misses, fp, idsw, mostly tracked (5 tracked[g] >= 4 present[g]), mostly lost (5 tracked[g] <=
+present[g]), gt objects}, the last three over g with present[g] > 0, in integers.
+
+`SequenceTracker` owns no engine, like tile.TiledSceneParser and score.ParseScorer: it binds to a parse.SceneParser, refine.ParseRefiner,
+prune.ParsePruner, propose.ParseProposer or tile.TiledSceneParser at R = S F rows, runs that provider's own `parse()` on the frames and
+then, on the same engine stream, its own launch list of libair_hip.so entries (include/air_hip.h), ONE hipGraph after `capture()`
+whatever F is -- the frames are walked inside air_track_associate:
+
+  air_track_associate   the rule above;
+  air_track_owner       track_owner[r, y, x] (int16) = the track id of the step that owns the pixel, -1 for background.
+
+A particle_parse.ParticleParser is refused, with tile._provider_rows' wording: its `parse()` takes no counts and its rows are particles
+of an image, and the buffers the tracker reads next to the `what` rows (`boxes`, `score`, `num_objects`, `owner`) are the selected
+particle's only behind a pruner or proposer -- bind one of those, they bind as every other provider.
+
+The defaults of iou_gate, appearance_weight, birth_score and max_age are provisional: UNMEASURED on a trained model (profiles/track.txt
+says what was measured).  `reference_associate` and `reference_score` restate the two rules in numpy float64.
+"""
+import ctypes
+import math
+from collections import OrderedDict
+from typing import Dict
+
+from .launch import destroy_graphs
+from .tile import box_iou
+
+MAX_SLOTS = 32                     # PARSE_MAXT / SCORE_MAXT: objects per frame and live tracks per sequence
+MAX_GT = 8                         # SCORE_MAXG
+MAX_IDS = 32767                    # F * T: an id fits int16
+ABSENT, MATCHED, BORN, UNCONFIRMED, OVERFLOW, NONFINITE = range(6)
+STATES = ("absent", "matched", "born", "unconfirmed", "overflow", "nonfinite")
+COUNTS = ("gt", "matches", "misses", "fp", "idsw", "mostly_tracked", "mostly_lost", "gt_objects")
+DEFAULTS = dict(iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1)
+
+
+def check_arguments(max_steps, n_frames, n_rows=None, iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1):
+    """Refuse what air_track_associate refuses (pure host code: importable and callable without a GPU).  Returns (T, F, S) with S = None
+    when `n_rows` is not given."""
+    gate, w, birth = float(iou_gate), float(appearance_weight), float(birth_score)
+    if not (math.isfinite(gate) and 0.0 <= gate < 1.0):
+        raise ValueError("iou_gate must be a number within [0, 1), got %r" % (iou_gate,))
+    if not (math.isfinite(w) and 0.0 <= w <= 1.0):
+        raise ValueError("appearance_weight must be a number within [0, 1], got %r" % (appearance_weight,))
+    if not (math.isfinite(birth) and 0.0 <= birth <= 1.0):
+        raise ValueError("birth_score must be a number within [0, 1], got %r" % (birth_score,))
+    if isinstance(max_age, bool) or int(max_age) != max_age or int(max_age) < 0:
+        raise ValueError("max_age must be an integer >= 0, got %r" % (max_age,))
+    T, F = int(max_steps), int(n_frames)
+    if not 1 <= T <= MAX_SLOTS:
+        raise ValueError("max_steps must be within 1..%d, got %d" % (MAX_SLOTS, T))
+    if int(n_frames) != n_frames or F < 1:
+        raise ValueError("n_frames must be an integer >= 1, got %r" % (n_frames,))
+    if F * T > MAX_IDS:
+        raise ValueError("%d frames of %d steps could issue %d track ids; an id must fit int16: at most %d" % (F, T, F * T, MAX_IDS))
+    S = None
+    if n_rows is not None:
+        if int(n_rows) < 1 or int(n_rows) % F:
+            raise ValueError("the provider's %d rows are no multiple of %d frames" % (int(n_rows), F))
+        S = int(n_rows) // F
+    return T, F, S
+
+
+def _sequential_sum(x):
+    """the sum over the last axis added in ascending index order (np.sum adds pairwise)"""
+    import numpy as np
+    return np.cumsum(x, axis=-1)[..., -1]
+
+
+def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1,
+                        return_margins=False):
+    """air_track_associate restated in numpy float64.  Arrays as the kernel takes them: what [T, R, A], boxes [T, R, 4], score [T, R]
+    (fp32), num_objects [R], R = S * n_frames.  Returns track_id [T, R] int32, obj_state [T, R] int8, affinity [T, R] float32,
+    prev_frame, prev_slot [T, R] int32, num_tracks [S] int32, track_first, track_last, track_length, track_gaps [S, F * T] int32,
+    state_counts [S, 6] int32.  return_margins=True adds how far the decisions are from flipping, per sequence: gate_margin [S] (the
+    smallest |iou - iou_gate| over the pairs of step 2), round_margin [S] (the smallest aff(winner) - aff(runner-up) over the greedy
+    rounds with more than one open admissible pair; inf without any)."""
+    import numpy as np
+    what, boxes, score = (np.asarray(a, np.float32) for a in (what, boxes, score))
+    n_in = np.asarray(num_objects).astype(np.int64)
+    T, R, A = what.shape
+    T, F, S = check_arguments(T, n_frames, R, iou_gate, appearance_weight, birth_score, max_age)
+    gate, w, birth, max_age = float(iou_gate), float(appearance_weight), float(birth_score), int(max_age)
+    FT = F * T
+    out = {"track_id": np.full((T, R), -1, np.int32), "obj_state": np.zeros((T, R), np.int8), "affinity": np.zeros((T, R), np.float32),
+           "prev_frame": np.full((T, R), -1, np.int32), "prev_slot": np.full((T, R), -1, np.int32), "num_tracks": np.zeros(S, np.int32),
+           "track_first": np.full((S, FT), -1, np.int32), "track_last": np.full((S, FT), -1, np.int32),
+           "track_length": np.zeros((S, FT), np.int32), "track_gaps": np.zeros((S, FT), np.int32),
+           "state_counts": np.zeros((S, 6), np.int32)}
+    gate_margin, round_margin = np.full(S, np.inf), np.full(S, np.inf)
+    what64 = what.astype(np.float64)
+    for s in range(S):
+        live = {}                                                  # slot -> dict(id, f, j, age, length, gaps)
+        next_id = 0
+
+        def retire(k):
+            t = live.pop(k)
+            out["track_last"][s, t["id"]], out["track_length"][s, t["id"]], out["track_gaps"][s, t["id"]] = t["f"], t["length"], t["gaps"]
+
+        for f in range(F):
+            r = s * F + f
+            n = int(min(max(n_in[r], 0), T))
+            state = np.zeros(T, np.int64)
+            finite = []
+            for j in range(n):                                     # 1. states
+                ok = np.isfinite(boxes[j, r]).all() and np.isfinite(score[j, r]) and np.isfinite(what[j, r]).all()
+                state[j] = UNCONFIRMED if ok else NONFINITE        # (finite and open: settled below)
+                if ok:
+                    finite.append(j)
+            aff = {}                                               # 2. affinity of the admissible pairs
+            for k, t in live.items():
+                if not finite:
+                    break
+                d = what64[t["j"], s * F + t["f"]][None, :] - what64[finite, r]
+                msd = _sequential_sum(d * d) / np.float64(A)
+                for q, j in enumerate(finite):
+                    iou = box_iou(boxes[t["j"], s * F + t["f"]], boxes[j, r])
+                    gate_margin[s] = min(gate_margin[s], abs(iou - gate))
+                    if iou > gate:
+                        aff[(k, j)] = (1.0 - w) * iou + w / (1.0 + float(msd[q]))
+            while aff:                                             # 3. greedy matching
+                ranked = sorted(aff, key=lambda kj: (-aff[kj], live[kj[0]]["id"], kj[1]))
+                k, j = ranked[0]
+                if len(ranked) > 1:
+                    round_margin[s] = min(round_margin[s], aff[ranked[0]] - aff[ranked[1]])
+                t = live[k]
+                state[j] = MATCHED
+                out["track_id"][j, r], out["prev_frame"][j, r], out["prev_slot"][j, r] = t["id"], t["f"], t["j"]
+                out["affinity"][j, r] = np.float32(aff[(k, j)])
+                t["gaps"] += 1 if t["age"] > 0 else 0
+                t["age"], t["length"], t["f"], t["j"] = 0, t["length"] + 1, f, j
+                aff = {kj: v for kj, v in aff.items() if kj[0] != k and kj[1] != j}
+            for j in finite:                                       # 4. births
+                if state[j] != UNCONFIRMED or not float(score[j, r]) >= birth:
+                    continue
+                free = [k for k in range(MAX_SLOTS) if k not in live]
+                if not free:
+                    state[j] = OVERFLOW
+                    continue
+                state[j] = BORN
+                live[free[0]] = dict(id=next_id, f=f, j=j, age=0, length=1, gaps=0)
+                out["track_id"][j, r] = next_id
+                out["track_first"][s, next_id] = f
+                next_id += 1
+            for k in sorted(live):                                 # 5. ageing
+                t = live[k]
+                if t["f"] != f:
+                    t["age"] += 1
+                    if t["age"] > max_age:
+                        retire(k)
+            out["obj_state"][:, r] = state
+            out["state_counts"][s] += np.bincount(state, minlength=6).astype(np.int32)
+        for k in sorted(live):
+            retire(k)
+        out["num_tracks"][s] = next_id
+    if return_margins:
+        out["gate_margin"], out["round_margin"] = gate_margin, round_margin
+    return out
+
+
+def reference_score(boxes, num_objects, track_id, gt_boxes, n_frames, tau=0.5):
+    """air_track_score restated in numpy float64.  boxes [T, R, 4], num_objects [R], track_id [T, R], gt_boxes [R, G, 4] (or
+    [S, F, G, 4]).  Returns seq_counts [S, 8] int32 (COUNTS), seq_iou [S] float64, gt_match [R, G] int32."""
+    import numpy as np
+    boxes = np.asarray(boxes, np.float32)
+    gt = np.asarray(gt_boxes, np.float32)
+    gt = gt.reshape(-1, gt.shape[-2], 4)
+    ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
+    T, R = ids.shape
+    G, F = gt.shape[1], int(n_frames)
+    if not 1 <= G <= MAX_GT:
+        raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+    if F < 1 or R % F or gt.shape[0] != R:
+        raise ValueError("%d rows / %d ground-truth rows are not sequences of %d frames" % (R, gt.shape[0], F))
+    tau = float(tau)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError("tau must be within [0, 1], got %r" % (tau,))
+    S = R // F
+    counts, seq_iou, gt_match = np.zeros((S, 8), np.int32), np.zeros(S, np.float64), np.full((R, G), -1, np.int32)
+    for s in range(S):
+        remembered = [-1] * G
+        tracked, frames = [0] * G, [0] * G
+        c = dict.fromkeys(COUNTS, 0)
+        for f in range(F):
+            r = s * F + f
+            n = int(min(max(n_in[r], 0), T))
+            hyp = [j for j in range(n) if ids[j, r] >= 0 and np.isfinite(boxes[j, r]).all()]
+            present = [g for g in range(G) if gt[r, g, 2] > 0]
+            iou = {(g, j): box_iou(gt[r, g], boxes[j, r]) for g in present for j in hyp}
+            match, taken = {}, set()
+            for g in present:                                      # 1. the remembered track keeps its object
+                if remembered[g] < 0:
+                    continue
+                j = next((j for j in hyp if ids[j, r] == remembered[g] and iou[(g, j)] > tau), None)
+                if j is not None and j not in taken:
+                    match[g] = j
+                    taken.add(j)
+            while True:                                            # 2. the rest greedily
+                open_pairs = [(g, j) for (g, j), v in iou.items() if g not in match and j not in taken and v > tau]
+                if not open_pairs:
+                    break
+                g, j = min(open_pairs, key=lambda gj: (-iou[gj], gj[0], gj[1]))
+                match[g] = j
+                taken.add(j)
+            for g in present:                                      # 3., 4.
+                c["gt"] += 1
+                frames[g] += 1
+                if g not in match:
+                    c["misses"] += 1
+                    continue
+                j = match[g]
+                gt_match[r, g] = j
+                c["matches"] += 1
+                tracked[g] += 1
+                seq_iou[s] = seq_iou[s] + iou[(g, j)]
+                c["idsw"] += 1 if remembered[g] >= 0 and remembered[g] != ids[j, r] else 0
+                remembered[g] = int(ids[j, r])
+            c["fp"] += len(hyp) - len(taken)
+        for g in range(G):
+            if frames[g] > 0:
+                c["gt_objects"] += 1
+                c["mostly_tracked"] += 1 if 5 * tracked[g] >= 4 * frames[g] else 0
+                c["mostly_lost"] += 1 if 5 * tracked[g] <= frames[g] else 0
+        counts[s] = [c[k] for k in COUNTS]
+    return {"seq_counts": counts, "seq_iou": seq_iou, "gt_match": gt_match}
+
+
+def mot_summary(counts, sum_iou) -> Dict[str, float]:
+    """the CLEAR-MOT figures of summed counts (COUNTS order) and the summed IoU of the matches; a denominator of 0 gives nan"""
+    c = dict(zip(COUNTS, (int(v) for v in counts)))
+    div = lambda a, b: a / b if b else float("nan")
+    return {"mota": 1.0 - div(c["misses"] + c["fp"] + c["idsw"], c["gt"]) if c["gt"] else float("nan"),
+            "motp": div(float(sum_iou), c["matches"]), "id_switches": c["idsw"],
+            "mostly_tracked": div(c["mostly_tracked"], c["gt_objects"]), "mostly_lost": div(c["mostly_lost"], c["gt_objects"]),
+            "false_positives": c["fp"], "misses": c["misses"], "gt": c["gt"], "matches": c["matches"], "gt_objects": c["gt_objects"]}
+
+
+def _provider_what(provider):
+    """the `what` rows [T, R, A] of the provider's `parse()` (tile._provider_rows; a TiledSceneParser keeps its compacted rows itself)"""
+    from .tile import _provider_rows
+    if hasattr(provider, "kept_cand") and not hasattr(provider, "what_sel"):       # tile.TiledSceneParser
+        return provider.what
+    return _provider_rows(provider)["what"]
+
+
+class SequenceTracker:
+    def __init__(self, provider, n_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
+                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"]):
+        what = _provider_what(provider)
+        T, F, S = check_arguments(provider.T, n_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age)
+        import torch
+        from . import hip as H
+        self.provider, self.engine = provider, provider.engine
+        self.T, self.R, self.S, self.F = T, int(provider.R), S, F
+        self.iou_gate, self.appearance_weight, self.birth_score, self.max_age = (float(iou_gate), float(appearance_weight),
+                                                                                 float(birth_score), int(max_age))
+        self._what = what
+        self.A = int(what.shape[-1])
+        self.img_size = tuple(int(v) for v in provider.owner.shape[1:])
+        dev = self.engine.device
+        R, FT = self.R, F * T
+        z = lambda shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
+        with torch.cuda.device(dev):
+            self.track_id, self.obj_state, self.affinity = z((T, R)), z((T, R), torch.int8), z((T, R), torch.float32)
+            self.prev_frame, self.prev_slot = z((T, R)), z((T, R))
+            self.num_tracks = z((S,))
+            self.track_first, self.track_last, self.track_length, self.track_gaps = z((S, FT)), z((S, FT)), z((S, FT)), z((S, FT))
+            self.state_counts = z((S, 6))
+            self.track_owner = z((R,) + self.img_size, torch.int16)
+            self.totals_i, self.totals_f = z((8,), torch.int64), z((1,), torch.float64)
+        self._graph = None
+        self._score = {}                                           # (G, tau) -> buffers, plan, graph
+        self._H = H
+        L, p = H.lib(), H._p
+        Hi, Wi = self.img_size
+        self.segments = OrderedDict([
+            ("associate", [(L.air_track_associate,
+                            (p(what), p(provider.boxes), p(provider.score), p(provider.num_objects), T, S, F, R, self.A, self.iou_gate,
+                             self.appearance_weight, self.birth_score, self.max_age, p(self.track_id), p(self.obj_state), p(self.affinity),
+                             p(self.prev_frame), p(self.prev_slot), p(self.num_tracks), p(self.track_first), p(self.track_last),
+                             p(self.track_length), p(self.track_gaps), p(self.state_counts)), "air_track_associate")]),
+            ("owner", [(L.air_track_owner, (p(provider.owner), p(self.track_id), T, R, Hi, Wi, p(self.track_owner)),
+                        "air_track_owner")])])
+        self._plan = [e for seg in self.segments.values() for e in seg]
+        self.engine.synchronize()
+
+    def launch_count(self) -> Dict[str, int]:
+        """entries of one `track()` call behind the bound provider's own (`parser` holds that provider's launch_count())"""
+        return {"parser": self.provider.launch_count(), "track_associate": 1, "track_owner": 1}
+
+    # ---- parameters ---------------------------------------------------------------------------------------------------------
+    def load_from(self, train_engine):
+        self.provider.load_from(train_engine)
+
+    def load_parameters(self, named):
+        self.provider.load_parameters(named)
+
+    def set_global_step(self, step: int):
+        self.provider.set_global_step(step)
+
+    def update_config(self, **changes) -> bool:
+        """run-time switches of the bound provider's engine: nothing of them is held by the tracker's launch list"""
+        return self.provider.update_config(**changes)
+
+    # ---- graphs -------------------------------------------------------------------------------------------------------------
+    def capture(self):
+        """the launches behind the provider's own call as ONE hipGraph, whatever F is (the provider's graphs are its own:
+        `provider.capture()`); the scoring launch of every (G, tau) used so far as one more each"""
+        self.release_graphs()
+        self.engine.synchronize()
+        self._graph = self.engine._capture_plans([self._plan])
+        for entry in self._score.values():
+            entry["graph"] = self.engine._capture_plans([entry["plan"]])
+
+    def release_graphs(self):
+        destroy_graphs([self._graph] + [e["graph"] for e in self._score.values()])
+        self._graph = None
+        for e in self._score.values():
+            e["graph"] = None
+
+    # ---- tracking -----------------------------------------------------------------------------------------------------------
+    def run_segments(self, *names):
+        """issue the named segments eagerly, in the order given, on the engine's stream (tests and probes run the pieces this way)"""
+        eng = self.engine
+        eng.wait_for_caller()
+        for name in names:
+            eng._run(self.segments[name], eng._sp())
+        eng.wait_for_engine()
+
+    def run_provider(self, frames, *args, **kwargs):
+        """the bound provider's `parse()` on the frames as its R = S F rows (further arguments go to it unchanged)"""
+        import torch
+        par = self.provider
+        frames = torch.as_tensor(frames)
+        Hi, Wi = self.img_size
+        if frames.numel() != self.R * Hi * Wi or frames.dim() < 2 or tuple(frames.shape[:2]) != (self.S, self.F):
+            raise ValueError("expected frames [%d, %d, %d, %d], got %s" % (self.S, self.F, Hi, Wi, tuple(frames.shape)))
+        base = par.parse(frames.reshape(self.R, Hi, Wi), *args, **kwargs)
+        if base["what"].data_ptr() != self._what.data_ptr():
+            raise RuntimeError("the bound provider returned 'what' from another buffer than the tracker was built on")
+        for k in ("boxes", "score", "num_objects", "owner"):
+            if base[k].data_ptr() != getattr(par, k).data_ptr():
+                raise RuntimeError("the bound provider returned %r from another buffer than the tracker was built on" % k)
+        return base
+
+    def track(self, frames, *args, **kwargs):
+        """frames [S, F, H, W]; further arguments go to the provider's `parse()` unchanged (its rows are the frames, row s F + f).
+        Returns the provider's dict of device tensors, untouched, and next to it (the NEXT call overwrites them): track_id [T, R] int32
+        (-1 = none), obj_state [T, R] int8 (STATES), affinity [T, R] (aff of the match, 0 unless matched), prev_frame, prev_slot [T, R]
+        int32 (the track's previous sighting, -1 unless matched), num_tracks [S] int32, track_first, track_last, track_length,
+        track_gaps [S, F * T] int32 per id (-1 / -1 / 0 / 0 from num_tracks[s] on), state_counts [S, 6] int32, track_owner
+        [R, H, W] int16 (the track id a pixel belongs to, -1 = background or an object without a track).  Same stream contract as
+        SceneParser.parse: the work runs on the engine's stream, on return the caller's current stream is ordered after it, and the
+        next call waits for the caller's reads before it overwrites them."""
+        eng = self.engine
+        base = self.run_provider(frames, *args, **kwargs)
+        eng._replay_or_run(self._graph, self._plan)
+        eng.wait_for_engine()
+        return self.result(base)
+
+    def result(self, base=None):
+        out = dict(base) if base is not None else {}
+        out.update(track_id=self.track_id, obj_state=self.obj_state, affinity=self.affinity, prev_frame=self.prev_frame,
+                   prev_slot=self.prev_slot, num_tracks=self.num_tracks, track_first=self.track_first, track_last=self.track_last,
+                   track_length=self.track_length, track_gaps=self.track_gaps, state_counts=self.state_counts,
+                   track_owner=self.track_owner)
+        return out
+
+    # ---- the identity metric ------------------------------------------------------------------------------------------------
+    def _score_entry(self, G, tau):
+        import torch
+        key = (int(G), float(tau))
+        entry = self._score.get(key)
+        if entry is None:
+            if not 1 <= key[0] <= MAX_GT:
+                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, key[0]))
+            if not 0.0 <= key[1] <= 1.0:
+                raise ValueError("tau must be within [0, 1], got %r" % (tau,))
+            H, par, dev = self._H, self.provider, self.engine.device
+            L, p = H.lib(), H._p
+            with torch.cuda.device(dev):
+                entry = {"gt_boxes": torch.zeros((self.R, key[0], 4), device=dev),
+                         "seq_counts": torch.zeros((self.S, 8), dtype=torch.int32, device=dev),
+                         "seq_iou": torch.zeros((self.S,), dtype=torch.float64, device=dev),
+                         "gt_match": torch.zeros((self.R, key[0]), dtype=torch.int32, device=dev), "graph": None}
+            entry["plan"] = [(L.air_track_score, (p(par.boxes), p(par.num_objects), p(self.track_id), p(entry["gt_boxes"]), key[1], self.T,
+                                                  key[0], self.S, self.F, self.R, p(entry["seq_counts"]), p(entry["seq_iou"]),
+                                                  p(entry["gt_match"])), "air_track_score")]
+            if self._graph is not None:
+                self.engine.synchronize()
+                entry["graph"] = self.engine._capture_plans([entry["plan"]])
+            while len(self._score) >= 4:                           # a sweep over tau must not pile up buffers and graphs
+                destroy_graphs([self._score.pop(next(iter(self._score)))["graph"]])
+            self._score[key] = entry
+        return entry
+
+    def score(self, gt_boxes, tau=0.5, accumulate=True):
+        """Score the LATEST `track()` against gt_boxes [R, G, 4] (or [S, F, G, 4]; G <= 8; slot g is the same object in every frame of
+        a sequence, width <= 0 = absent).  Returns device tensors that the next call with the same (G, tau) overwrites: seq_counts
+        [S, 8] int32 (COUNTS), seq_iou [S] float64, gt_match [R, G] int32, and the running totals_i [8] int64 / totals_f [1] float64,
+        which this call adds to (accumulate=False: restarts) on the device, with no read-back.  Same stream contract as `track`."""
+        import torch
+        eng = self.engine
+        gb = torch.as_tensor(gt_boxes)
+        if gb.dim() not in (3, 4) or gb.shape[-1] != 4 or gb.numel() != self.R * gb.shape[-2] * 4:
+            raise ValueError("gt_boxes: expected [%d, G, 4] or [%d, %d, G, 4], got %s" % (self.R, self.S, self.F, tuple(gb.shape)))
+        entry = self._score_entry(gb.shape[-2], tau)
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            entry["gt_boxes"].copy_(gb.reshape(entry["gt_boxes"].shape), non_blocking=True)
+        if gb.is_cuda:
+            gb.record_stream(eng.stream)
+        eng._replay_or_run(entry["graph"], entry["plan"])
+        with torch.cuda.stream(eng.stream):
+            ti, tf = entry["seq_counts"].sum(0, dtype=torch.int64), entry["seq_iou"].sum(0, keepdim=True)
+            if accumulate:
+                self.totals_i += ti
+                self.totals_f += tf
+            else:
+                self.totals_i.copy_(ti)
+                self.totals_f.copy_(tf)
+        eng.wait_for_engine()
+        return {"seq_counts": entry["seq_counts"], "seq_iou": entry["seq_iou"], "gt_match": entry["gt_match"],
+                "totals_i": self.totals_i, "totals_f": self.totals_f}
+
+    def reset(self):
+        """zero the totals"""
+        import torch
+        eng = self.engine
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            self.totals_i.zero_()
+            self.totals_f.zero_()
+        eng.wait_for_engine()
+
+    def summary(self) -> Dict[str, float]:
+        """The figures of everything scored since the last reset (ONE read-back): mota = 1 - (misses + fp + idsw) / gt, motp =
+        sum_iou / matches, id_switches, mostly_tracked, mostly_lost (fractions of the ground-truth objects), false_positives, misses,
+        and the counts gt, matches, gt_objects.  A denominator of 0 gives nan."""
+        import torch
+        self.engine.wait_for_engine()
+        flat = torch.cat([self.totals_i.double(), self.totals_f]).tolist()
+        return mot_summary(flat[:8], flat[8])
+
+    def synchronize(self):
+        self.engine.synchronize()

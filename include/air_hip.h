@@ -777,6 +777,59 @@ AIR_ENGINE_API int air_tile_merge(const float *what, const float *where, const f
 AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand, const int *num_objects, const int *offsets, int C,
                     int S, float *score, float *obj_score, int *obj_step, void *stream);
 
+/* ---- tracking objects across the frames of a sequence: the per-frame parses of R = S F rows in (sequence-major: row r = s F + f),
+ * identities out.  T in 1..32 objects per frame, F T <= 32767 (an id fits int16), R == S F (AIR_E_SHAPE otherwise).  Float64 with
+ * contraction off wherever a float decides; no transcendental functions; no atomics on floats; one fixed order: the same bits run
+ * to run.  Checks come before the launch: a refused call writes nothing.
+ * air_track_associate: what[T,R,A], boxes[T,R,4] (air_parse_objects' boxes), score[T,R], num_objects[R].  Each sequence on its own, one
+ *   256-thread workgroup, the frames walked in ascending order inside the kernel.  A table of at most 32 LIVE tracks: slot, id, the
+ *   (frame, slot) of the last sighting, age (frames since that sighting), length, gaps.  For frame f with n = clip(num_objects[r], 0, T),
+ *   in this order:
+ *   1. states: object j >= n is 0 ABSENT; j < n is 5 NONFINITE if any of its four box values, its score or its A what values is not
+ *      finite, and takes no further part.
+ *   2. affinity of every live track k and finite object j:  iou = air_score_match's float64 box IoU of the track's last-sighting box
+ *      and the object's box;  msd = (sum_a (what_k[a] - what_j[a])^2) / A in float64 from the widened fp32 values, summed in ascending
+ *      a (what_k = the what row of the track's last sighting);  aff = (1 - w) * iou + w / (1 + msd).  Admissible iff iou > iou_gate,
+ *      strictly.
+ *   3. greedy matching: while an admissible pair of an unmatched track and an unmatched object exists, the one with the largest aff
+ *      (equal aff: the lower track id, then the lower j): the object is 1 MATCHED, track_id = the track's id, prev_frame / prev_slot =
+ *      the track's last sighting, affinity = aff rounded once to fp32;  the track: gaps += (age > 0), age = 0, length += 1, last
+ *      sighting (f, j).
+ *   4. births: the unmatched finite objects in ascending j:  score >= birth_score: 2 BORN with id = next_id++ in the lowest free slot,
+ *      or 4 OVERFLOW (id -1) when no slot is free;  score < birth_score: 3 UNCONFIRMED (id -1).  Matching ignores birth_score.
+ *   5. ageing: every live track neither matched nor born in this frame gets age += 1; one with age > max_age is retired, its slot is
+ *      free from frame f + 1 on.  Ids are never reused.
+ *   Every element of every output is written:  track_id[T,R] (int32, -1 = none), obj_state[T,R] (int8), affinity[T,R] (0 unless
+ *   MATCHED), prev_frame / prev_slot[T,R] (int32, -1 unless MATCHED), num_tracks[S] = ids issued, track_first / track_last (frames of
+ *   the first and last sighting) / track_length (sightings) / track_gaps [S, F T] (int32) per id, -1 / -1 / 0 / 0 from num_tracks[s] on,
+ *   state_counts[S,6] (int32) = objects per state (they sum to T F).  AIR_E_SHAPE also: iou_gate outside [0, 1), appearance_weight or
+ *   birth_score outside [0, 1] (NaN included), max_age < 0.  boxes 16-byte aligned, every other pointer 4-byte aligned (AIR_E_ALIGN).
+ * air_track_owner: track_owner[r,y,x] (int16) = owner[r,y,x] < 0 or >= T ? -1 : (int16) track_id[owner[r,y,x], r].  One workgroup per
+ *   image (grid-stride); 16-byte loads from the first 16-byte boundary of an image's owner row on, 16-byte stores (8-byte ones when the
+ *   output is only that aligned at the same pixel) between the head and the tail, pixel by pixel there and for an image whose output
+ *   is aligned to neither.  track_id 4-byte, track_owner 2-byte aligned (AIR_E_ALIGN).
+ * air_track_score: CLEAR-MOT counts, one workgroup (one wavefront) per sequence, the frames walked inside.  gt_boxes[R,G,4], G in 1..8:
+ *   slot g is the SAME object in every frame of a sequence, width <= 0 = absent in that frame.  Hypotheses of a frame: its objects
+ *   j < clip(num_objects[r], 0, T) with track_id >= 0 and four finite box values.  map[g] = none at the start of a sequence.  Per frame:
+ *   1. for g ascending: a present g whose map[g] is the id of a hypothesis j not yet taken with iou(gt_g, box_j) > tau keeps j;
+ *   2. the remaining present g and hypotheses greedily by float64 IoU descending, strictly > tau (equal: the lower g, then the lower j);
+ *   3. for every matched (g, j) in ascending g: idsw += (map[g] exists and != id_j), then map[g] = id_j (map persists while g is
+ *      unmatched or absent);
+ *   4. gt += present g, matches, misses += present unmatched g, fp += unmatched hypotheses, sum_iou += the matches' iou (float64, frame
+ *      order, then g order), tracked[g] / present[g] += 1.
+ *   seq_counts[S,8] (int32) = {gt, matches, misses, fp, idsw, mostly tracked (5 tracked[g] >= 4 present[g]), mostly lost
+ *   (5 tracked[g] <= present[g]), gt objects (present[g] > 0)}, the last three over g with present[g] > 0;  seq_iou[S] (float64) =
+ *   sum_iou;  gt_match[R,G] (int32) = the matched slot j, -1 otherwise.  tau in [0, 1] (AIR_E_SHAPE).  boxes / gt_boxes 16-byte,
+ *   seq_iou 8-byte, everything else 4-byte aligned (AIR_E_ALIGN).                                                                   */
+AIR_ENGINE_API int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
+                    int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
+                    int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,
+                    int *track_first, int *track_last, int *track_length, int *track_gaps, int *state_counts, void *stream);
+AIR_ENGINE_API int air_track_owner(const signed char *owner, const int *track_id, int T, int R, int H, int W, short *track_owner,
+                    void *stream);
+AIR_ENGINE_API int air_track_score(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
+                    int T, int G, int S, int F, int R, int *seq_counts, double *seq_iou, int *gt_match, void *stream);
+
 /* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
  * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
  * (AIR_E_SHAPE otherwise, and when R*H*W or R*(T+1)*(G+1) passes int32).  No floating-point atomics; float64 with contraction off
