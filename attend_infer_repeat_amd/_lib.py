@@ -203,6 +203,8 @@ SIGNATURES = {
     "air_propose_residual": (c_int, [P, P, P, P, P, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "air_propose_pool": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
     "air_propose_source": (c_int, [P, P, c_int, c_int, P, P]),
+    "air_temporal_pool": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
+                                  c_int, c_int, P, P, P, P, P, P, P, P, P, P, P]),
     "air_tile_gather": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "air_tile_merge": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
                                P, P, P, P, P, P, P, P, P, P]),

@@ -163,6 +163,17 @@ __device__ __forceinline__ float grid_coord(float s, float X, float t, float hal
     const float c = b + 1.0f;
     return c * half_extent;
 }
+// evaluation.attention_box of a where row [sx, tx, sy, ty] on a W x H image, operation by operation in fp32:
+// (left, top, width, height).  air_parse_objects' boxes; every entry that needs a row's box calls this, so the bits agree.
+__device__ __forceinline__ float4 attention_box4(const float4 w4, float Wf, float Hf) {
+#pragma clang fp contract(off)
+    float4 bx;
+    bx.x = Wf * ((1.f - w4.x) + w4.y) * 0.5f;
+    bx.y = Hf * ((1.f - w4.z) + w4.w) * 0.5f;
+    bx.z = Wf * w4.x;
+    bx.w = Hf * w4.z;
+    return bx;
+}
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float softplus_acc(float x) { return x > 20.0f ? x : log1pf(expf(x)); }

@@ -78,12 +78,7 @@ __global__ __launch_bounds__(256) void parse_count_kernel(const float *__restric
         presence[k] = lane < n_hat ? 1.f : 0.f;
         score[k] = sc;
         const float4 w4 = *reinterpret_cast<const float4 *>(where + 4 * k);      // [sx, tx, sy, ty]
-        float4 bx;                                                 // evaluation.attention_box, operation by operation
-        bx.x = Wf * ((1.f - w4.x) + w4.y) * 0.5f;
-        bx.y = Hf * ((1.f - w4.z) + w4.w) * 0.5f;
-        bx.z = Wf * w4.x;
-        bx.w = Hf * w4.z;
-        *reinterpret_cast<float4 *>(boxes + 4 * k) = bx;
+        *reinterpret_cast<float4 *>(boxes + 4 * k) = attention_box4(w4, Wf, Hf);   // evaluation.attention_box, operation by operation
     }
 }
 

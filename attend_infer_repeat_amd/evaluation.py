@@ -469,17 +469,18 @@ def make_track_fig(frames, result, max_frames=8, checkpoint_dir=None, global_ste
 
 def make_track_score_logger(air, data, num_batches, name, batch_size=None, writer=None, tau=0.5, measure_time=True, iou_gate=None,
                             appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None,
-                            propose=None):
+                            propose=None, temporal=None):
     """make_tiled_parse_score_logger's counterpart for sequences (air.score_track): `data` is an annotated dataset dict of SEQUENCES
     (imgs [N, F, H, W], boxes [N, F, G, 4], instances [N, F, H, W] int8 -- data.create_moving_mnist with return_annotations=True),
     walked in `num_batches` batches of `batch_size` sequences (None: the model's batch size).  Prints / writes the identity figures
     (MOTA, MOTP, identity switches, mostly tracked / lost), the per-frame detection figures of the same parses (count accuracy, mAP)
     and the totals of the association's object states (track_matched, track_born, track_unconfirmed, track_overflow,
-    track_nonfinite) and the tracks issued."""
+    track_nonfinite) and the tracks issued.  temporal=P | (P, rounds): the frames' parses are repaired from their neighbour frames
+    first (air.track's argument); temporal_kept then counts the objects that came from a neighbour."""
     import torch
     from .track import STATES
     tk = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
-              refine_lr=refine_lr, prune=prune, propose=propose)
+              refine_lr=refine_lr, prune=prune, propose=propose, temporal=temporal)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -490,6 +491,7 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
         start = time.time()
         dev = air.obs.device
         states, issued = torch.zeros(6, dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
+        repaired = torch.zeros((), dtype=torch.int64, device=dev)
         tracker = None
         for i in range(n):
             sl = slice(i * S, (i + 1) * S)
@@ -497,10 +499,14 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
                                          tau=tau, accumulate=i > 0, gt_instances=torch.as_tensor(data["instances"][sl]), **tk)
             states += air.tracked["state_counts"].sum(0)
             issued += air.tracked["num_tracks"].sum()
+            if temporal is not None:
+                repaired += air.tracked["objects_temporal_kept"].sum()
         acc = tracker.summary()
         det = air.track_scorer.summary()
         acc.update(count_acc=det["count_acc"], map=det["map"], frames=det["images"], objects_pred=det["objects_pred"],
                    tracks=int(issued.item()))
+        if temporal is not None:
+            acc["temporal_kept"] = int(repaired.item())
         for k, v in zip(STATES[1:], states.tolist()[1:]):
             acc["track_" + k] = v
         shown = ["mota", "motp", "id_switches", "mostly_tracked", "mostly_lost", "count_acc", "map", "tracks"]

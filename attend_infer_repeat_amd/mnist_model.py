@@ -563,12 +563,48 @@ class AIRonMNIST(AIRModel):
 
     MAX_TRACKERS = 2
 
+    @staticmethod
+    def _temporal_spec(temporal):
+        """temporal=None | P | (P, rounds) -> None | (P, rounds)"""
+        if temporal is None:
+            return None
+        try:
+            spec = (int(temporal), 1) if not isinstance(temporal, (tuple, list)) else tuple(int(v) for v in temporal)
+        except (TypeError, ValueError):
+            spec = ()
+        if len(spec) != 2 or isinstance(temporal, bool):
+            raise ValueError("temporal: the number of neighbour proposals per round, or (proposals, rounds), got %r" % (temporal,))
+        return spec
+
+    def _sequence_stack(self, S, F, refine, lr, prune, propose, temporal):
+        """the provider stack of `tracker` / `temporal_proposer` at S * F rows: a SceneParser, behind it the refiner / pruner /
+        proposer asked for, and last the temporal.TemporalProposer (temporal = (P, rounds) or None)"""
+        from .parse import SceneParser
+        eng = self._engine
+        stack = [SceneParser(eng.cfg, S * F, device=eng.device)]
+        if refine is not None:
+            from .refine import ParseRefiner
+            stack.append(ParseRefiner(stack[-1], int(refine), lr[0], lr[1]))
+        if prune is not None:
+            from .prune import ParsePruner
+            stack.append(ParsePruner(stack[-1], prune))
+        if propose is not None:
+            from .propose import ParseProposer
+            p = (int(propose), 1) if not isinstance(propose, (tuple, list)) else tuple(int(v) for v in propose)
+            stack.append(ParseProposer(stack[-1], p[0], p[1]))
+        if temporal is not None:
+            from .temporal import TemporalProposer
+            stack.append(TemporalProposer(stack[-1], F, temporal[0], temporal[1]))
+        return stack
+
     def tracker(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-                refine_lr=None, prune=None, propose=None):
+                refine_lr=None, prune=None, propose=None, temporal=None):
         """the track.SequenceTracker behind `track`: one per (n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age,
-        refine, refine_lr, prune, propose), over a provider stack of its own at n_sequences * n_frames rows -- a SceneParser, behind it
-        the refiner / pruner / proposer asked for -- so the parsers of `parse` and `self.obs` are never touched.  None for one of the
-        four association arguments: track.DEFAULTS (provisional).  Built and captured on first use; the least recently used one is
+        refine, refine_lr, prune, propose, temporal), over a provider stack of its own at n_sequences * n_frames rows -- a SceneParser,
+        behind it the refiner / pruner / proposer asked for and, last, with temporal=P | (P, rounds) a temporal.TemporalProposer
+        (objects a frame's parse missed are proposed from its neighbour frames; its defaults are provisional) -- so the parsers of
+        `parse` and `self.obs` are never touched.  temporal=None builds exactly the stack without it.  None for one of the four
+        association arguments: track.DEFAULTS (provisional).  Built and captured on first use; the least recently used one is
         dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
         eng = getattr(self, "_engine", None)
         if eng is None:
@@ -577,7 +613,6 @@ class AIRonMNIST(AIRModel):
         if prune is not None and propose is not None:
             raise ValueError("track: prune together with propose is not supported; pass one of them")
         from . import track as tr
-        from .parse import SceneParser
         from .refine import DEFAULT_LR
         given = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age)
         assoc = {k: (tr.DEFAULTS[k] if v is None else v) for k, v in given.items()}
@@ -587,22 +622,16 @@ class AIRonMNIST(AIRModel):
             raise ValueError("track: at least one sequence, got %r" % (n_sequences,))
         lr = None if refine is None else tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
         spec = propose if not isinstance(propose, list) else tuple(propose)
+        tspec = self._temporal_spec(temporal)
+        if tspec is not None:
+            from .temporal import check_arguments as check_temporal
+            check_temporal(eng.cfg, F, S * F, tspec[0], tspec[1])
         key = (S, F, float(assoc["iou_gate"]), float(assoc["appearance_weight"]), float(assoc["birth_score"]), int(assoc["max_age"]),
-               refine, lr, prune, spec, str(eng.device))
+               refine, lr, prune, spec, str(eng.device)) + (() if tspec is None else (("temporal",) + tspec,))
         cache = self.__dict__.setdefault("_trackers", {})
         entry = cache.pop(key, None)
         if entry is None:
-            stack = [SceneParser(eng.cfg, S * F, device=eng.device)]
-            if refine is not None:
-                from .refine import ParseRefiner
-                stack.append(ParseRefiner(stack[-1], int(refine), lr[0], lr[1]))
-            if prune is not None:
-                from .prune import ParsePruner
-                stack.append(ParsePruner(stack[-1], prune))
-            if propose is not None:
-                from .propose import ParseProposer
-                p = (int(propose), 1) if not isinstance(propose, (tuple, list)) else tuple(int(v) for v in propose)
-                stack.append(ParseProposer(stack[-1], p[0], p[1]))
+            stack = self._sequence_stack(S, F, refine, lr, prune, propose, tspec)
             stack.append(tr.SequenceTracker(stack[-1], F, **assoc))
             for s in stack:
                 s.capture()
@@ -613,10 +642,46 @@ class AIRonMNIST(AIRModel):
                 s.release_graphs()
         return entry[-1]
 
+    MAX_TEMPORAL_PROPOSERS = 2
+
+    def temporal_proposer(self, n_sequences, n_frames, proposals=1, rounds=1, refine=None, refine_lr=None, prune=None, propose=None):
+        """the temporal.TemporalProposer for callers who want the repaired per-frame parses without identities: one per (n_sequences,
+        n_frames, proposals, rounds, refine, refine_lr, prune, propose), last in a provider stack of its own at n_sequences * n_frames
+        rows (`tracker`'s).  Built and captured on first use; `load_from(self._engine)` before `parse(frames_as_rows)` is the
+        caller's.  The least recently used one is dropped, with its stack, when more than MAX_TEMPORAL_PROPOSERS are alive."""
+        eng = getattr(self, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("temporal_proposer needs the fused engine: call train_step(...) with an engine-eligible "
+                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        if prune is not None and propose is not None:
+            raise ValueError("temporal_proposer: prune together with propose is not supported; pass one of them")
+        from . import temporal as tp
+        from .refine import DEFAULT_LR
+        S, F = int(n_sequences), int(n_frames)
+        if S < 1:
+            raise ValueError("temporal_proposer: at least one sequence, got %r" % (n_sequences,))
+        tspec = self._temporal_spec((proposals, rounds))
+        tp.check_arguments(eng.cfg, F, S * F, tspec[0], tspec[1])
+        lr = None if refine is None else tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
+        spec = propose if not isinstance(propose, list) else tuple(propose)
+        key = (S, F, tspec, refine, lr, prune, spec, str(eng.device))
+        cache = self.__dict__.setdefault("_temporal_proposers", {})
+        entry = cache.pop(key, None)
+        if entry is None:
+            entry = self._sequence_stack(S, F, refine, lr, prune, propose, tspec)
+            for s in entry:
+                s.capture()
+        cache[key] = entry                                         # most recently used last
+        while len(cache) > self.MAX_TEMPORAL_PROPOSERS:
+            for s in reversed(cache.pop(next(iter(cache)))):
+                s.release_graphs()
+        return entry[-1]
+
     def track(self, frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None,
-              prune=None, propose=None):
+              prune=None, propose=None, temporal=None):
         """Parse the frames [S, F, H, W] of S sequences on the device, each frame as `parse(refine=, prune=, propose=)` would parse
-        it, and give the objects identities over time (track.SequenceTracker.track lists the returned device tensors: the parse of
+        it -- with temporal=P | (P, rounds) followed by proposals from the neighbour frames (temporal.TemporalProposer) -- and give
+        the objects identities over time (track.SequenceTracker.track lists the returned device tensors: the parse of
         the S * F frames, row s * F + f, and next to it track_id, obj_state, affinity, prev_frame, prev_slot, the per-track tables and
         track_owner; the next call overwrites them).  The training engine's parameters are read, nothing of it is written;
         `self.obs` and the parsers of `parse` are not touched."""
@@ -625,14 +690,15 @@ class AIRonMNIST(AIRModel):
         if frames.dim() != 4:
             raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
         t = self.tracker(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                         propose)
+                         propose, temporal)
         self._sync_engine_switches()
         t.load_from(self._engine)                            # every time: the weights move
         self.tracked = t.track(frames)
         return self.tracked
 
     def score_track(self, frames, gt_boxes, tau=0.5, accumulate=True, gt_instances=None, thresholds=None, iou_gate=None,
-                    appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None):
+                    appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None,
+                    temporal=None):
         """`track`, then the identity metric of the tracks against gt_boxes [S, F, G, 4] (G <= 8; slot g is the same object in every
         frame of a sequence, width <= 0 = absent) on the device (track.SequenceTracker.score).  The sums accumulate in the tracker
         this returns alongside -- (scores, tracker): its summary() reads MOTA, MOTP, the identity switches and the mostly tracked /
@@ -640,10 +706,10 @@ class AIRonMNIST(AIRModel):
         S * F frames are also scored as images by a score.ParseScorer bound to the same provider (per-frame detection figures next to
         the identity figures): scores["detection"] holds its tensors, `self.track_scorer` is that scorer."""
         import torch
-        self.track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose)
+        self.track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal)
         frames = torch.as_tensor(frames)
         t = self.tracker(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                         propose)
+                         propose, temporal)
         gb = torch.as_tensor(gt_boxes)
         scores = dict(t.score(gb, tau, accumulate))
         if gt_instances is not None:

@@ -121,6 +121,11 @@ def main(argv=None):
                          "procedural digits that move in straight lines at up to SPEED pixels per frame (default 3) and reflect off "
                          "the canvas edges (data.procedural_moving_mnist, with births and deaths); --parse-refine, --parse-prune and "
                          "--parse-propose apply to every frame")
+    ap.add_argument("--track-temporal", default=None, metavar="P[,ROUNDS]",
+                    help="with --track-eval: before the association, propose to every frame up to P objects its parse missed from the "
+                         "parses of the frames before and after it, ROUNDS times (default 1; temporal.TemporalProposer: the exact "
+                         "subset search of --parse-prune over the frame's rows and its neighbours' rows, no network evaluation); "
+                         "max_steps + P <= 6")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -182,6 +187,18 @@ def main(argv=None):
             ap.error("--track-eval needs a finite SPEED >= 0, got %r" % args.track_eval)
         if args.parse_particles > 0:
             ap.error("--track-eval does not go with --parse-particles: particle providers are out of scope for tracking")
+
+    track_temporal = None
+    if args.track_temporal is not None:
+        try:
+            spec = tuple(int(v) for v in args.track_temporal.split(","))
+        except ValueError:
+            spec = ()
+        if len(spec) not in (1, 2) or min(spec) < 1:
+            ap.error("--track-temporal needs P >= 1 or P,ROUNDS with ROUNDS >= 1, got %r" % args.track_temporal)
+        if track_eval is None:
+            ap.error("--track-temporal goes with --track-eval")
+        track_temporal = spec[0] if len(spec) == 1 else spec
 
     learning_rate, n_steps, batch_size = args.learning_rate, 3, 64    # multi_mnist.py:24-25,37
     num_steps_prior = AttrDict(anneal='exp', init=1. - 1e-15, final=1e-7, steps_div=1e4, steps=1e5, hold_init=1e3)
@@ -333,7 +350,8 @@ def main(argv=None):
                                       seed=args.seed + 2000, n_templates=256, return_annotations=True)
         seq_data = dict(imgs=raw["imgs"].astype("float32") / 255.0, boxes=raw["boxes"], instances=raw["instances"])
         before_track_log = log
-        track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, **refine_kw)
+        track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
+                                            **refine_kw)
 
         def log(train_itr):                               # noqa: F811
             out = before_track_log(train_itr)

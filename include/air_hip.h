@@ -741,6 +741,44 @@ AIR_ENGINE_API int air_propose_pool(const float *what, const float *where, const
                     float *pool_presence, int *pool_source, double *pool_prior, void *stream);
 AIR_ENGINE_API int air_propose_source(const int *pool_source, const int *kept_step, int C, int R, int *source_out, void *stream);
 
+/* ---- recovering objects a frame's parse missed from its neighbour frames.  Rows are sequence-major, r = s F + f, R = S F (the layout of
+ * air_track_associate).  One round: air_temporal_pool on the current rows of ALL frames, then air_prune_score / air_prune_select with
+ * T := C = T + P <= 6, all_candidates = 1, the pool's presence chain and padded prior, obs = the frame itself, then air_propose_source.
+ * The first T rows of the compacted [C,R,.] outputs are the next round's current rows.  No network evaluation.
+ * air_temporal_pool: one wavefront per row.  Current rows what[T,R,A], where[T,R,4], glimpse[T,R,G], score[T,R];  n_r = the number of
+ *   leading ones of presence[:, r], or num_objects_in[r] clipped to 0..T when that is given (the counts win; neither is AIR_E_NULL):
+ *   air_propose_pool's two forms.  For row r, in this order:
+ *   1. the box of any row = evaluation.attention_box(where, W, H) in fp32 with air_parse_objects' operations (the bits of its boxes).
+ *   2. candidates q = 0 .. 2T-1: q < T is slot q of frame f - 1, otherwise slot q - T of frame f + 1, both read from this call's INPUT
+ *      rows of the same sequence (Jacobi); never across a sequence boundary.
+ *   3. cand_state[R,2T] (int8):  0 ABSENT: the neighbour frame does not exist, or both_sides == 0 and q >= T, or slot >= the
+ *      neighbour's n;  5 NONFINITE: a where, score or what value of the candidate is not finite (the glimpse is not checked: a
+ *      non-finite glimpse gives a NaN joint, which air_prune_select never takes);  2 KNOWN: for some current object j < n_r,
+ *      IoU(box_q, box_j) > iou_novel, strictly (air_score_match's float64 box IoU, contraction off; a NaN comparison is false).
+ *   4. the remaining candidates ranked by score descending, the lower q between equal scores, and walked in that order:  3 DUPLICATE
+ *      of the first already TAKEN d with IoU(box_q, box_d) > iou_novel;  otherwise 1 TAKEN if fewer than P are taken so far, else
+ *      4 FULL.  taken[R] (int32) = the number taken.
+ *   5. partner[P,R] (int32): partner[i] of the i-th taken candidate d = the first DUPLICATE of d in walk order that comes from the
+ *      other side, -1 without one and for i >= taken.  With interpolate != 0 and a partner c, the pool's where row is
+ *      (float)(0.5 * ((double) where_d + (double) where_c)) per component (tx, ty are linear in position: for linear motion the
+ *      object's place in frame f), otherwise a bit copy of where_d; what, glimpse and score are always d's bits.
+ *   6. the pool [C,R,.]: rows j < T = the current rows, bit copies (16-byte vectors where A resp. G is a multiple of 4 and both
+ *      buffers are 16-byte aligned, 4-byte words otherwise: air_propose_pool's rule);  row T + i = the i-th taken candidate;  an
+ *      unused proposal row (i >= taken): what = quiet NaN (0x7fc00000), where = (1, 0, 1, 0), glimpse = 0, score = 0,
+ *      pool_source = -1 -- by air_prune_select's rule every subset containing it has a NaN joint and is never taken.
+ *      pool_presence[j,r] = j < n_r.  pool_source[j,r] (int32) = source_in[j,r] (j itself when source_in is NULL: round 0) for
+ *      j < T, T + round * 2T + q for a taken candidate q.  pool_prior[C+1] (float64) = prior_f64[0..T] followed by zeros (written by
+ *      the wavefront of row 0): the selected count stays <= T.
+ *   Every element of every output is written.  No atomics, one fixed order: the same bits run to run.  Checks come before the launch:
+ *   a refused call writes nothing.  AIR_E_SHAPE: T outside 1..6, P outside 1..min(2T, 6 - T), S F past int32, non-positive sizes,
+ *   round < 0;  AIR_E_ALIGN: a pointer not 4-byte aligned, prior_f64 / pool_prior not 8-byte aligned;  AIR_E_NULL: a missing
+ *   buffer (source_in may be NULL, and one of presence / num_objects_in).  The pool must not overlap the inputs.                       */
+AIR_ENGINE_API int air_temporal_pool(const float *what, const float *where, const float *glimpse, const float *score, const float *presence,
+                    const int *num_objects_in, const int *source_in, const double *prior_f64, int round, int T, int P, int S, int F,
+                    int A, int G, int H, int W, double iou_novel, int both_sides, int interpolate, float *pool_what,
+                    float *pool_where, float *pool_glimpse, float *pool_score, float *pool_presence, int *pool_source,
+                    double *pool_prior, signed char *cand_state, int *taken, int *partner, void *stream);
+
 /* ---- parsing scenes larger than the model's canvas: overlapping windows in, one merged object list per scene out.  Canvas H x W
  * (both > 1), scene Hs x Ws (Hs >= H, Ws >= W), stride 1 <= sy <= H, 1 <= sx <= W.  ny = 1 + ceil((Hs - H) / sy) windows along y at
  * oy_i = min(i sy, Hs - H) (the last one clamped to the edge: every window is a real crop), nx / ox_j alike, Nw = ny nx, window
