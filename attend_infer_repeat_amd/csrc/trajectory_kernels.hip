@@ -1,0 +1,422 @@
+// Trajectories behind the sequence tracker for gfx950: smoothed, gap-filled and extrapolated tracks.
+//   air_track_smooth: per sequence one workgroup, one lane per track id (in passes of 64 ids); a constant-rate Kalman
+//                     filter forward over the track's span and a Rauch-Tung-Striebel pass (means only) back, per `where` component;
+//                     the completed table (a row for every track that spans a frame, sighted there or not) and the forecast table;
+//   air_track_fill:   what / glimpse / score of the completed or forecast rows: bit copies of the source sighting's rows.
+// The arithmetic is float64 from the widened fp32 values with contraction off, only + - * /, in the order include/air_hip.h states;
+// the row of a track in a frame is a count of integers in one fixed order; no floating-point atomics: the same bits run to run.
+#include <limits.h>
+#include "air_common.h"
+
+#define TRAJ_THREADS 256                 // air_track_fill: four wavefronts, one (row, column) each
+#define TRAJ_SMOOTH_THREADS 64           // air_track_smooth: one wavefront per sequence -- a dependent chain per lane, no cross-wave traffic
+#define TRAJ_MAXT 32                     // TRACK_MAXT: objects per frame, live tracks per sequence, rows of the completed table
+#define TRAJ_MAX_IDS 32767               // TRACK_MAX_IDS
+#define TRAJ_MAX_HORIZON 16
+#define TRAJ_WS_DOUBLES 28               // per (row, frame): 4 x (x, v, x-, v-), 2 noise classes x (P, P-) of three values each
+
+enum { TRAJ_ABSENT = 0, TRAJ_OBSERVED = 1, TRAJ_FILLED = 2, TRAJ_FORECAST = 3 };
+// workspace planes: plane k of row `row` in frame r is ws[((size_t)k * R + r) * C + row]
+enum { WS_X = 0, WS_V = 4, WS_XP = 8, WS_VP = 12, WS_P = 16, WS_PP = 19 };      // class c: WS_P + 6 c, WS_PP + 6 c
+
+struct TrajSmoothArgs {
+    const float *where;
+    const int *num_objects, *track_id, *num_tracks, *track_first, *track_last;
+    double *ws;
+    float *sm_where, *sm_boxes, *sm_velocity, *fc_where, *fc_boxes, *fc_velocity;
+    int *sm_id, *sm_src_frame, *sm_src_slot, *sm_count, *sm_counts, *fc_id, *fc_src_frame, *fc_src_slot, *fc_count;
+    signed char *sm_state, *fc_state;
+    double q[2], r, velocity_var;        // q[0]: the shift components tx, ty; q[1]: the scale components sx, sy
+    int T, S, F, C, Hz, max_age, H, W;
+};
+
+struct TrajCov {
+    double xx, xv, vv;
+};
+
+// predict: a = Pxx + Pxv, b = Pxv + Pvv, Pxx- = (a + b) + q4, Pxv- = b + q2, Pvv- = Pvv + q
+__device__ __forceinline__ TrajCov traj_predict_cov(const TrajCov p, double q, double q2, double q4) {
+#pragma clang fp contract(off)
+    const double a = p.xx + p.xv, b = p.xv + p.vv;
+    TrajCov o;
+    o.xx = (a + b) + q4;
+    o.xv = b + q2;
+    o.vv = p.vv + q;
+    return o;
+}
+
+// Every output of the sequence starts ABSENT; the lanes of the spanning tracks overwrite their rows behind a barrier.
+__device__ __forceinline__ void traj_fill_absent(const TrajSmoothArgs &a, int s, int tid) {
+    const int F = a.F, C = a.C, Hz = a.Hz;
+    const size_t R = (size_t)a.S * F, N = (size_t)a.S * Hz;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = tid; e < C * F; e += TRAJ_SMOOTH_THREADS) {
+        const int c = e / F, f = e - c * F;
+        const size_t at = (size_t)c * R + (size_t)s * F + f;
+        reinterpret_cast<float4 *>(a.sm_where)[at] = z4;
+        reinterpret_cast<float4 *>(a.sm_boxes)[at] = z4;
+        a.sm_velocity[2 * at] = 0.f;
+        a.sm_velocity[2 * at + 1] = 0.f;
+        a.sm_id[at] = -1;
+        a.sm_state[at] = (signed char)TRAJ_ABSENT;
+        a.sm_src_frame[at] = -1;
+        a.sm_src_slot[at] = -1;
+    }
+    for (int f = tid; f < F; f += TRAJ_SMOOTH_THREADS) a.sm_count[(size_t)s * F + f] = 0;
+    for (int e = tid; e < C * Hz; e += TRAJ_SMOOTH_THREADS) {
+        const int c = e / Hz, k = e - c * Hz;
+        const size_t at = (size_t)c * N + (size_t)s * Hz + k;
+        reinterpret_cast<float4 *>(a.fc_where)[at] = z4;
+        reinterpret_cast<float4 *>(a.fc_boxes)[at] = z4;
+        a.fc_velocity[2 * at] = 0.f;
+        a.fc_velocity[2 * at + 1] = 0.f;
+        a.fc_id[at] = -1;
+        a.fc_state[at] = (signed char)TRAJ_ABSENT;
+        a.fc_src_frame[at] = -1;
+        a.fc_src_slot[at] = -1;
+    }
+    for (int k = tid; k < Hz; k += TRAJ_SMOOTH_THREADS) a.fc_count[(size_t)s * Hz + k] = 0;
+}
+
+// One workgroup of one wavefront per sequence, lane = track id (passes of 64 ids).  A track is taken iff 0 <= first <= last < F.  Ids are
+// issued in frame order, so every id' < id was born no later than id: the ids below one's own that span a frame f >= first are
+// among those with last' >= first -- at most 31 of them, since all of them and id itself span `first`.  Their `last` values are
+// kept in LDS (olast_s[k][lane]); the row in frame f is the number of them with last' >= f.
+__global__ __launch_bounds__(TRAJ_SMOOTH_THREADS) void track_smooth_kernel(TrajSmoothArgs a) {
+#pragma clang fp contract(off)
+    __shared__ int olast_s[TRAJ_MAXT][TRAJ_SMOOTH_THREADS];
+    __shared__ int first_s[TRAJ_SMOOTH_THREADS], last_s[TRAJ_SMOOTH_THREADS];
+    __shared__ int counts_s[2];
+    const int T = a.T, F = a.F, C = a.C, Hz = a.Hz, R = a.S * F, FT = F * T;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const size_t N = (size_t)a.S * Hz;
+    int issued = a.num_tracks[s];
+    issued = issued < 0 ? 0 : (issued > FT ? FT : issued);
+    const int live_from = F - 1 - a.max_age;                       // a track last seen in this frame or later is live after frame F - 1
+    const double q2[2] = {0.5 * a.q[0], 0.5 * a.q[1]}, q4[2] = {0.25 * a.q[0], 0.25 * a.q[1]};
+    const float Wf = (float)a.W, Hf = (float)a.H;
+    if (tid < 2) counts_s[tid] = 0;
+    traj_fill_absent(a, s, tid);
+    __syncthreads();
+
+    for (int base = 0; base < issued; base += TRAJ_SMOOTH_THREADS) {
+        const int id = base + tid;
+        int first = -1, last = -1;
+        if (id < issued) {
+            first = a.track_first[(size_t)s * FT + id];
+            last = a.track_last[(size_t)s * FT + id];
+        }
+        const bool valid = first >= 0 && first <= last && last < F;
+        const bool forecast = valid && Hz > 0 && last >= live_from;
+        const int reach = forecast && live_from < first ? live_from : first;      // the ids below that matter have last' >= reach
+        // ---- the ids below one's own that overlap: chunks of 64 (first, last) pairs through LDS, read by every lane in ascending id ----
+        int m = 0;
+        for (int cb = 0; cb <= base; cb += TRAJ_SMOOTH_THREADS) {
+            __syncthreads();                                       // (the previous chunk, or the previous pass, is read)
+            const int oid = cb + tid;
+            int of = -1, ol = -1;
+            if (oid < issued) {
+                of = a.track_first[(size_t)s * FT + oid];
+                ol = a.track_last[(size_t)s * FT + oid];
+            }
+            first_s[tid] = of;
+            last_s[tid] = ol;
+            __syncthreads();
+            const int upto = id - cb < TRAJ_SMOOTH_THREADS ? id - cb : TRAJ_SMOOTH_THREADS;      // ids cb .. cb + upto - 1 are below one's own
+            if (valid)
+                for (int k = 0; k < upto; ++k) {
+                    const int of2 = first_s[k], ol2 = last_s[k];
+                    if (of2 >= 0 && of2 <= ol2 && ol2 < F && ol2 >= reach && m < TRAJ_MAXT) olast_s[m++][tid] = ol2;
+                }
+        }
+        if (!valid) continue;                                      // (no barrier below this line inside the pass)
+
+        // ---- forward: the filter over first .. last ------------------------------------------------------------------------------------------
+        double x[4] = {0.0, 0.0, 0.0, 0.0}, v[4] = {0.0, 0.0, 0.0, 0.0};
+        TrajCov P[2] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+        int src_f = -1, src_j = -1, n_obs = 0, n_fill = 0;
+        for (int f = first; f <= last; ++f) {
+            const int r = s * F + f;
+            int row = 0;
+            for (int k = 0; k < m; ++k) row += olast_s[k][tid] >= f ? 1 : 0;
+            int n = a.num_objects[r];
+            n = n < 0 ? 0 : (n > T ? T : n);
+            int j = -1;
+            for (int t = n - 1; t >= 0; --t)
+                if (a.track_id[(size_t)t * R + r] == id) j = t;    // the lowest slot that carries the id
+            const bool seen = j >= 0;
+            double z[4] = {0.0, 0.0, 0.0, 0.0};
+            if (seen) {
+                const float4 w4 = reinterpret_cast<const float4 *>(a.where)[(size_t)j * R + r];
+                z[0] = (double)w4.x, z[1] = (double)w4.y, z[2] = (double)w4.z, z[3] = (double)w4.w;
+                src_f = f;
+                src_j = j;
+            }
+            TrajCov Pp[2] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+            double xp[4] = {0.0, 0.0, 0.0, 0.0}, vp[4] = {0.0, 0.0, 0.0, 0.0};
+            if (f == first) {                                      // start: x = z, v = 0, P = (r, 0, velocity_var)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) x[c] = z[c], v[c] = 0.0;
+                P[0].xx = P[1].xx = a.r;
+                P[0].xv = P[1].xv = 0.0;
+                P[0].vv = P[1].vv = a.velocity_var;
+            } else {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) Pp[c] = traj_predict_cov(P[c], a.q[c], q2[c], q4[c]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) xp[c] = x[c] + v[c], vp[c] = v[c];
+                if (seen) {
+                    double kx[2], kv[2];
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const double sn = Pp[c].xx + a.r;
+                        kx[c] = Pp[c].xx / sn;
+                        kv[c] = Pp[c].xv / sn;
+                        P[c].xx = Pp[c].xx - kx[c] * Pp[c].xx;
+                        P[c].xv = Pp[c].xv - kx[c] * Pp[c].xv;
+                        P[c].vv = Pp[c].vv - kv[c] * Pp[c].xv;
+                    }
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int cl = (c & 1) ? 0 : 1;            // [sx, tx, sy, ty]: the odd components are shifts
+                        const double e = z[c] - xp[c];
+                        x[c] = xp[c] + kx[cl] * e;
+                        v[c] = vp[c] + kv[cl] * e;
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) x[c] = xp[c], v[c] = vp[c];
+                    P[0] = Pp[0];
+                    P[1] = Pp[1];
+                }
+            }
+            if (row < C) {
+                const size_t at = (size_t)row * R + r;
+                a.sm_id[at] = id;
+                a.sm_state[at] = (signed char)(seen ? TRAJ_OBSERVED : TRAJ_FILLED);
+                a.sm_src_frame[at] = src_f;
+                a.sm_src_slot[at] = src_j;
+                atomicMax(&a.sm_count[r], row + 1);                 // an integer maximum: the order does not matter
+                n_obs += seen ? 1 : 0;
+                n_fill += seen ? 0 : 1;
+                if (f < last) {                                    // what the backward pass reads
+                    double *w = a.ws + (size_t)r * C + row;
+                    const size_t plane = (size_t)R * C;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        w[(WS_X + c) * plane] = x[c];
+                        w[(WS_V + c) * plane] = v[c];
+                    }
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        w[(WS_P + 6 * c) * plane] = P[c].xx;
+                        w[(WS_P + 6 * c + 1) * plane] = P[c].xv;
+                        w[(WS_P + 6 * c + 2) * plane] = P[c].vv;
+                    }
+                }
+                if (f > first) {
+                    double *w = a.ws + (size_t)r * C + row;
+                    const size_t plane = (size_t)R * C;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        w[(WS_XP + c) * plane] = xp[c];
+                        w[(WS_VP + c) * plane] = vp[c];
+                    }
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        w[(WS_PP + 6 * c) * plane] = Pp[c].xx;
+                        w[(WS_PP + 6 * c + 1) * plane] = Pp[c].xv;
+                        w[(WS_PP + 6 * c + 2) * plane] = Pp[c].vv;
+                    }
+                }
+            }
+        }
+        if (n_obs) atomicAdd(&counts_s[0], n_obs);                  // integer adds in LDS: the order does not matter
+        if (n_fill) atomicAdd(&counts_s[1], n_fill);
+
+        // ---- the forecast: the filtered state at `last`, shifts extrapolated, scales held ----------------------------------------------------
+        if (forecast) {
+            int row = 0;
+            for (int k = 0; k < m; ++k) row += olast_s[k][tid] >= live_from ? 1 : 0;
+            if (row < C) {
+                const float2 vel = make_float2((float)(((double)a.W * v[1]) * 0.5), (float)(((double)a.H * v[3]) * 0.5));
+                for (int k = 1; k <= Hz; ++k) {
+                    const double mm = (double)(F - 1 - last + k);
+                    const float4 w4 = make_float4((float)x[0], (float)(x[1] + mm * v[1]), (float)x[2], (float)(x[3] + mm * v[3]));
+                    const size_t col = (size_t)s * Hz + (k - 1), at = (size_t)row * N + col;
+                    reinterpret_cast<float4 *>(a.fc_where)[at] = w4;
+                    reinterpret_cast<float4 *>(a.fc_boxes)[at] = attention_box4(w4, Wf, Hf);
+                    reinterpret_cast<float2 *>(a.fc_velocity)[at] = vel;
+                    a.fc_id[at] = id;
+                    a.fc_state[at] = (signed char)TRAJ_FORECAST;
+                    a.fc_src_frame[at] = src_f;
+                    a.fc_src_slot[at] = src_j;
+                    atomicMax(&a.fc_count[col], row + 1);
+                }
+            }
+        }
+
+        // ---- backward: xs[last] = x, vs[last] = v, then last - 1 down to first ----------------------------------------------------------------
+        double xs[4], vs[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xs[c] = x[c], vs[c] = v[c];
+        int row_next = -1;                                          // the row in frame f + 1
+        for (int f = last; f >= first; --f) {
+            const int r = s * F + f;
+            int row = 0;
+            for (int k = 0; k < m; ++k) row += olast_s[k][tid] >= f ? 1 : 0;
+            if (f < last && row < C && row_next < C) {
+                const size_t plane = (size_t)R * C;
+                const double *w = a.ws + (size_t)r * C + row, *wn = a.ws + (size_t)(r + 1) * C + row_next;
+                double C00[2], C01[2], C10[2], C11[2];
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const double pxx = w[(WS_P + 6 * c) * plane], pxv = w[(WS_P + 6 * c + 1) * plane], pvv = w[(WS_P + 6 * c + 2) * plane];
+                    const double nxx = wn[(WS_PP + 6 * c) * plane], nxv = wn[(WS_PP + 6 * c + 1) * plane],
+                                 nvv = wn[(WS_PP + 6 * c + 2) * plane];
+                    const double g00 = pxx + pxv, g01 = pxv, g10 = pxv + pvv, g11 = pvv;
+                    const double det = nxx * nvv - nxv * nxv;
+                    C00[c] = (g00 * nvv - g01 * nxv) / det;
+                    C01[c] = (g01 * nxx - g00 * nxv) / det;
+                    C10[c] = (g10 * nvv - g11 * nxv) / det;
+                    C11[c] = (g11 * nxx - g10 * nxv) / det;
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int cl = (c & 1) ? 0 : 1;
+                    const double dx = xs[c] - wn[(WS_XP + c) * plane], dv = vs[c] - wn[(WS_VP + c) * plane];
+                    xs[c] = w[(WS_X + c) * plane] + (C00[cl] * dx + C01[cl] * dv);
+                    vs[c] = w[(WS_V + c) * plane] + (C10[cl] * dx + C11[cl] * dv);
+                }
+            }
+            if (row < C) {
+                const size_t at = (size_t)row * R + r;
+                const float4 w4 = make_float4((float)xs[0], (float)xs[1], (float)xs[2], (float)xs[3]);
+                reinterpret_cast<float4 *>(a.sm_where)[at] = w4;
+                reinterpret_cast<float4 *>(a.sm_boxes)[at] = attention_box4(w4, Wf, Hf);
+                reinterpret_cast<float2 *>(a.sm_velocity)[at] =
+                    make_float2((float)(((double)a.W * vs[1]) * 0.5), (float)(((double)a.H * vs[3]) * 0.5));
+            }
+            row_next = row;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int *c = a.sm_counts + (size_t)s * 3;
+        c[TRAJ_OBSERVED] = counts_s[0];
+        c[TRAJ_FILLED] = counts_s[1];
+        c[TRAJ_ABSENT] = C * F - counts_s[0] - counts_s[1];
+    }
+}
+
+extern "C" size_t air_track_smooth_workspace_bytes(int C, int R) {
+    if (C < 1 || C > TRAJ_MAXT || R < 1) return 0;
+    return (size_t)TRAJ_WS_DOUBLES * sizeof(double) * (size_t)C * (size_t)R;
+}
+
+extern "C" int air_track_smooth(const float *where, const int *num_objects, const int *track_id, const int *num_tracks,
+                                const int *track_first, const int *track_last, int T, int S, int F, int R, int C, int Hz, int max_age,
+                                int H, int W, double q_shift, double q_scale, double r, double velocity_var, double *ws,
+                                size_t ws_bytes, float *sm_where, float *sm_boxes, int *sm_id, signed char *sm_state,
+                                int *sm_src_frame, int *sm_src_slot, float *sm_velocity, int *sm_count, int *sm_counts,
+                                float *fc_where, float *fc_boxes, int *fc_id, signed char *fc_state, int *fc_src_frame,
+                                int *fc_src_slot, float *fc_velocity, int *fc_count, void *stream) {
+    AIR_REQUIRE(where && num_objects && track_id && num_tracks && track_first && track_last && ws && sm_where && sm_boxes && sm_id &&
+                sm_state && sm_src_frame && sm_src_slot && sm_velocity && sm_count && sm_counts, AIR_E_NULL);
+    AIR_REQUIRE(Hz >= 0 && Hz <= TRAJ_MAX_HORIZON, AIR_E_SHAPE);
+    AIR_REQUIRE(Hz == 0 || (fc_where && fc_boxes && fc_id && fc_state && fc_src_frame && fc_src_slot && fc_velocity && fc_count),
+                AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRAJ_MAXT && S > 0 && F > 0 && H > 0 && W > 0 && max_age >= 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)F * T <= TRAJ_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
+    const long want_c = (long)T * ((long)max_age + 1) < TRAJ_MAXT ? (long)T * ((long)max_age + 1) : TRAJ_MAXT;
+    AIR_REQUIRE((long)C == want_c && (long)C * R <= (long)INT_MAX / 4, AIR_E_SHAPE);
+    AIR_REQUIRE(q_shift > 0.0 && q_scale > 0.0 && r > 0.0 && velocity_var >= 0.0, AIR_E_SHAPE);      // (a NaN fails every comparison)
+    AIR_REQUIRE(ws_bytes >= air_track_smooth_workspace_bytes(C, R), AIR_E_WORKSPACE);
+    AIR_REQUIRE(air_aligned16(where) && air_aligned16(sm_where) && air_aligned16(sm_boxes) &&
+                (Hz == 0 || (air_aligned16(fc_where) && air_aligned16(fc_boxes))), AIR_E_ALIGN);
+    AIR_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sm_velocity) & 7u) == 0 &&
+                (reinterpret_cast<uintptr_t>(fc_velocity) & 7u) == 0, AIR_E_ALIGN);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(num_objects) | reinterpret_cast<uintptr_t>(track_id) |
+                           reinterpret_cast<uintptr_t>(num_tracks) | reinterpret_cast<uintptr_t>(track_first) |
+                           reinterpret_cast<uintptr_t>(track_last) | reinterpret_cast<uintptr_t>(sm_id) |
+                           reinterpret_cast<uintptr_t>(sm_src_frame) | reinterpret_cast<uintptr_t>(sm_src_slot) |
+                           reinterpret_cast<uintptr_t>(sm_count) | reinterpret_cast<uintptr_t>(sm_counts) |
+                           reinterpret_cast<uintptr_t>(fc_id) | reinterpret_cast<uintptr_t>(fc_src_frame) |
+                           reinterpret_cast<uintptr_t>(fc_src_slot) | reinterpret_cast<uintptr_t>(fc_count);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    TrajSmoothArgs a;
+    a.where = where, a.num_objects = num_objects, a.track_id = track_id, a.num_tracks = num_tracks;
+    a.track_first = track_first, a.track_last = track_last, a.ws = ws;
+    a.sm_where = sm_where, a.sm_boxes = sm_boxes, a.sm_velocity = sm_velocity;
+    a.fc_where = fc_where, a.fc_boxes = fc_boxes, a.fc_velocity = fc_velocity;
+    a.sm_id = sm_id, a.sm_src_frame = sm_src_frame, a.sm_src_slot = sm_src_slot, a.sm_count = sm_count, a.sm_counts = sm_counts;
+    a.fc_id = fc_id, a.fc_src_frame = fc_src_frame, a.fc_src_slot = fc_src_slot, a.fc_count = fc_count;
+    a.sm_state = sm_state, a.fc_state = fc_state;
+    a.q[0] = q_shift, a.q[1] = q_scale, a.r = r, a.velocity_var = velocity_var;
+    a.T = T, a.S = S, a.F = F, a.C = C, a.Hz = Hz, a.max_age = max_age, a.H = H, a.W = W;
+    hipLaunchKernelGGL(track_smooth_kernel, dim3((unsigned)S), dim3(TRAJ_SMOOTH_THREADS), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// ============================================================================================================
+// fill
+// ============================================================================================================
+struct TrajFillArgs {
+    const float *what, *glimpse, *score;
+    const signed char *state;
+    const int *src_frame, *src_slot;
+    float *out_what, *out_glimpse, *out_score;
+    int T, F, R, C, N, per_seq, A, G, what_vec, glimpse_vec;
+};
+
+__device__ __forceinline__ void traj_copy_row(const float *__restrict__ src, float *__restrict__ dst, int n, bool vec, int lane) {
+    if (vec) {                                                     // 16-byte vectors: n % 4 == 0 and both buffers start aligned
+        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
+        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+        for (int i = lane; i < n / 4; i += 64) d4[i] = src ? s4[i] : make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        const unsigned *s1 = reinterpret_cast<const unsigned *>(src);
+        unsigned *d1 = reinterpret_cast<unsigned *>(dst);
+        for (int i = lane; i < n; i += 64) d1[i] = src ? s1[i] : 0u;
+    }
+}
+
+// One wavefront per (row c, column n) of the table; column n belongs to sequence n / per_seq (per_seq = F for the completed table,
+// the horizon for the forecast table).  A row that is ABSENT, or whose source is outside the provider's rows, gets zeros.
+__global__ __launch_bounds__(TRAJ_THREADS) void track_fill_kernel(TrajFillArgs a) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const long e = (long)blockIdx.x * (TRAJ_THREADS / 64) + wid;
+    if (e >= (long)a.C * a.N) return;
+    const int n = (int)(e % a.N);
+    const int s = n / a.per_seq;
+    const int st = (int)a.state[e], sf = a.src_frame[e], sj = a.src_slot[e];
+    const bool has = st != TRAJ_ABSENT && sf >= 0 && sf < a.F && sj >= 0 && sj < a.T;
+    const size_t from = has ? (size_t)sj * a.R + (size_t)s * a.F + sf : 0;
+    traj_copy_row(has ? a.what + from * a.A : nullptr, a.out_what + (size_t)e * a.A, a.A, a.what_vec != 0, lane);
+    traj_copy_row(has ? a.glimpse + from * a.G : nullptr, a.out_glimpse + (size_t)e * a.G, a.G, a.glimpse_vec != 0, lane);
+    if (lane == 0) reinterpret_cast<unsigned *>(a.out_score)[e] = has ? reinterpret_cast<const unsigned *>(a.score)[from] : 0u;
+}
+
+extern "C" int air_track_fill(const float *what, const float *glimpse, const float *score, const signed char *state,
+                              const int *src_frame, const int *src_slot, int T, int F, int R, int C, int N, int per_seq, int A, int G,
+                              float *out_what, float *out_glimpse, float *out_score, void *stream) {
+    AIR_REQUIRE(what && glimpse && score && state && src_frame && src_slot && out_what && out_glimpse && out_score, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRAJ_MAXT && C >= 1 && C <= TRAJ_MAXT && F > 0 && R > 0 && N > 0 && per_seq > 0 && A > 0 && G > 0,
+                AIR_E_SHAPE);
+    AIR_REQUIRE(R % F == 0 && N % per_seq == 0 && N / per_seq == R / F, AIR_E_SHAPE);
+    AIR_REQUIRE((long)C * N <= (long)INT_MAX && (long)T * R <= (long)INT_MAX, AIR_E_SHAPE);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(what) | reinterpret_cast<uintptr_t>(glimpse) | reinterpret_cast<uintptr_t>(score) |
+                           reinterpret_cast<uintptr_t>(src_frame) | reinterpret_cast<uintptr_t>(src_slot) |
+                           reinterpret_cast<uintptr_t>(out_what) | reinterpret_cast<uintptr_t>(out_glimpse) |
+                           reinterpret_cast<uintptr_t>(out_score);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    TrajFillArgs a = {what, glimpse, score, state, src_frame, src_slot, out_what, out_glimpse, out_score, T, F, R, C, N, per_seq, A, G,
+                      A % 4 == 0 && air_aligned16(what) && air_aligned16(out_what),
+                      G % 4 == 0 && air_aligned16(glimpse) && air_aligned16(out_glimpse)};
+    const long waves = (long)C * N;
+    hipLaunchKernelGGL(track_fill_kernel, dim3((unsigned)air_cdiv(waves, TRAJ_THREADS / 64)), dim3(TRAJ_THREADS), 0,
+                       air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}

@@ -467,20 +467,78 @@ def make_track_fig(frames, result, max_frames=8, checkpoint_dir=None, global_ste
     return fig
 
 
+def make_trajectory_fig(frames, result, max_frames=8, checkpoint_dir=None, global_step=None, n_samples=4, arrow_scale=3.0):
+    """The trajectories of sequences (AIRonMNIST.track(smooth=...) / trajectory.TrajectorySmoother.result): one row per sequence, one
+    panel per frame (the first `max_frames`), the frame with the SMOOTHED attention box of every row of the completed table, coloured
+    by track id -- an observed row solid, a FILLED row (the track coasted over this frame) dashed -- and an arrow of `arrow_scale`
+    frames of its velocity from the box centre; with a forecast horizon the predicted frames are appended, their forecast boxes
+    dotted.  frames [S, F, H, W].  Saved as trajectory_fig_<global_step>.png when a directory is given."""
+    import os.path as osp
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    import torch
+    from .trajectory import FILLED
+    host = lambda t: torch.as_tensor(t).detach().cpu().numpy()
+    x, ids, boxes, state = host(frames), host(result["sm_id"]), host(result["sm_boxes"]), host(result["sm_state"])
+    vel, n = host(result["sm_velocity"]), host(result["sm_count"])
+    S, F, H, W = x.shape
+    pred = host(result["frames_pred"]) if "frames_pred" in result else None
+    Hz = 0 if pred is None else pred.shape[1]
+    rows, shown = min(n_samples, S), min(int(max_frames), F)
+    cols = shown + Hz
+    inch = 1.5
+    fig, axes = plt.subplots(rows, cols, figsize=(inch * cols * W / max(H, W), inch * rows * H / max(H, W)), squeeze=False)
+    colours = plt.get_cmap('tab20')
+
+    def draw(ax, box, colour, style):
+        ax.add_patch(plt.Rectangle((box[0] - .5, box[1] - .5), box[2], box[3], fill=False, edgecolor=colour, linewidth=1, linestyle=style))
+
+    for s in range(rows):
+        for f in range(shown):
+            r, ax = s * F + f, axes[s][f]
+            ax.imshow(x[s, f], cmap='gray', vmin=0, vmax=1)
+            for j in range(int(n[r])):
+                colour = colours(int(ids[j, r]) % 20)
+                draw(ax, boxes[j, r], colour, '--' if state[j, r] == FILLED else '-')
+                cx, cy = boxes[j, r, 0] + boxes[j, r, 2] / 2 - .5, boxes[j, r, 1] + boxes[j, r, 3] / 2 - .5
+                dx, dy = arrow_scale * vel[j, r, 0], arrow_scale * vel[j, r, 1]
+                if dx or dy:
+                    ax.annotate('', xy=(cx + dx, cy + dy), xytext=(cx, cy), arrowprops=dict(arrowstyle='->', color=colour, lw=.6))
+            ax.set_axis_off()
+        for k in range(Hz):
+            c, ax = s * Hz + k, axes[s][shown + k]
+            ax.imshow(pred[s, k], cmap='gray', vmin=0, vmax=1)
+            fid, fbox = host(result["fc_id"]), host(result["fc_boxes"])
+            for j in range(int(host(result["fc_count"])[c])):
+                draw(ax, fbox[j, c], colours(int(fid[j, c]) % 20), ':')
+            ax.set_title('+%d' % (k + 1), fontsize=5, pad=1)
+            ax.set_axis_off()
+    if checkpoint_dir is not None:
+        fig.savefig(osp.join(checkpoint_dir, 'trajectory_fig_{}.png'.format(global_step)), dpi=300)
+        plt.close(fig)
+    return fig
+
+
 def make_track_score_logger(air, data, num_batches, name, batch_size=None, writer=None, tau=0.5, measure_time=True, iou_gate=None,
                             appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None,
-                            propose=None, temporal=None):
+                            propose=None, temporal=None, smooth=None):
     """make_tiled_parse_score_logger's counterpart for sequences (air.score_track): `data` is an annotated dataset dict of SEQUENCES
     (imgs [N, F, H, W], boxes [N, F, G, 4], instances [N, F, H, W] int8 -- data.create_moving_mnist with return_annotations=True),
     walked in `num_batches` batches of `batch_size` sequences (None: the model's batch size).  Prints / writes the identity figures
     (MOTA, MOTP, identity switches, mostly tracked / lost), the per-frame detection figures of the same parses (count accuracy, mAP)
     and the totals of the association's object states (track_matched, track_born, track_unconfirmed, track_overflow,
     track_nonfinite) and the tracks issued.  temporal=P | (P, rounds): the frames' parses are repaired from their neighbour frames
-    first (air.track's argument); temporal_kept then counts the objects that came from a neighbour."""
+    first (air.track's argument); temporal_kept then counts the objects that came from a neighbour.  smooth=True | dict: the tracks are
+    also smoothed and gap-filled (trajectory.TrajectorySmoother) and the COMPLETED table is scored by the same kernel, side by side:
+    smooth_mota, smooth_motp, smooth_id_switches, smooth_misses, smooth_false_positives, and the rows per state rows_observed,
+    rows_filled."""
     import torch
     from .track import STATES
     tk = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
               refine_lr=refine_lr, prune=prune, propose=propose, temporal=temporal)
+    if smooth is not None:
+        tk["smooth"] = smooth
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -492,6 +550,7 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
         dev = air.obs.device
         states, issued = torch.zeros(6, dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
         repaired = torch.zeros((), dtype=torch.int64, device=dev)
+        table_rows = torch.zeros(3, dtype=torch.int64, device=dev)
         tracker = None
         for i in range(n):
             sl = slice(i * S, (i + 1) * S)
@@ -501,6 +560,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
             issued += air.tracked["num_tracks"].sum()
             if temporal is not None:
                 repaired += air.tracked["objects_temporal_kept"].sum()
+            if smooth is not None:
+                table_rows += air.tracked["sm_counts"].sum(0)
         acc = tracker.summary()
         det = air.track_scorer.summary()
         acc.update(count_acc=det["count_acc"], map=det["map"], frames=det["images"], objects_pred=det["objects_pred"],
@@ -510,6 +571,12 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
         for k, v in zip(STATES[1:], states.tolist()[1:]):
             acc["track_" + k] = v
         shown = ["mota", "motp", "id_switches", "mostly_tracked", "mostly_lost", "count_acc", "map", "tracks"]
+        if smooth is not None:
+            done = air.track_smoother.summary()
+            for k in ("mota", "motp", "id_switches", "misses", "false_positives"):
+                acc["smooth_" + k] = done[k]
+            acc["rows_observed"], acc["rows_filled"] = (int(v) for v in table_rows.tolist()[1:])
+            shown += ["smooth_mota", "smooth_motp", "rows_filled"]
         t = time.time() - start
         msg = 'Step {}, Data {} track score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:

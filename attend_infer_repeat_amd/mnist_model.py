@@ -597,13 +597,50 @@ class AIRonMNIST(AIRModel):
             stack.append(TemporalProposer(stack[-1], F, temporal[0], temporal[1]))
         return stack
 
+    @staticmethod
+    def _smooth_spec(smooth):
+        """smooth=None | True | dict(horizon=, process_noise=, measurement_noise=, velocity_var=) -> None | the full dict"""
+        if smooth is None or smooth is False:
+            return None
+        from .trajectory import DEFAULTS
+        spec = dict(DEFAULTS, horizon=0)
+        if smooth is not True:
+            if not isinstance(smooth, dict) or set(smooth) - set(spec):
+                raise ValueError("smooth: None, True or a dict with keys among %s, got %r" % (sorted(spec), smooth))
+            spec.update(smooth)
+        try:
+            spec["process_noise"] = tuple(float(v) for v in spec["process_noise"])
+        except TypeError:
+            raise ValueError("smooth: process_noise must be two numbers (q_shift, q_scale), got %r" % (spec["process_noise"],))
+        return spec
+
     def tracker(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-                refine_lr=None, prune=None, propose=None, temporal=None):
-        """the track.SequenceTracker behind `track`: one per (n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age,
-        refine, refine_lr, prune, propose, temporal), over a provider stack of its own at n_sequences * n_frames rows -- a SceneParser,
+                refine_lr=None, prune=None, propose=None, temporal=None, smooth=None):
+        """the track.SequenceTracker behind `track` (`_tracker_entry` describes the cache; with smooth= the tracker of the stack that
+        ends in the trajectory.TrajectorySmoother `trajectory_smoother` returns)"""
+        entry = self._tracker_entry(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
+                                    propose, temporal, smooth)
+        return entry[-1] if self._smooth_spec(smooth) is None else entry[-2]
+
+    def trajectory_smoother(self, n_sequences, n_frames, smooth=True, iou_gate=None, appearance_weight=None, birth_score=None,
+                            max_age=None, refine=None, refine_lr=None, prune=None, propose=None, temporal=None):
+        """the trajectory.TrajectorySmoother behind `track(smooth=)` and `predict_frames`: last in the cached stack of
+        `tracker(..., smooth=smooth)`, bound to that stack's tracker (smoothed, gap-filled and extrapolated tracks; its defaults are
+        provisional)"""
+        if self._smooth_spec(smooth) is None:
+            raise ValueError("trajectory_smoother: smooth must be True or a dict of TrajectorySmoother's arguments, got %r" % (smooth,))
+        return self._tracker_entry(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
+                                   propose, temporal, smooth)[-1]
+
+    def _tracker_entry(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
+                       refine_lr=None, prune=None, propose=None, temporal=None, smooth=None):
+        """the cached stack whose track.SequenceTracker is behind `track`: one per (n_sequences, n_frames, iou_gate, appearance_weight,
+        birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth), over a provider stack of its own at
+        n_sequences * n_frames rows -- a SceneParser,
         behind it the refiner / pruner / proposer asked for and, last, with temporal=P | (P, rounds) a temporal.TemporalProposer
         (objects a frame's parse missed are proposed from its neighbour frames; its defaults are provisional) -- so the parsers of
-        `parse` and `self.obs` are never touched.  temporal=None builds exactly the stack without it.  None for one of the four
+        `parse` and `self.obs` are never touched.  temporal=None builds exactly the stack without it; so does smooth=None, and
+        smooth=True | dict appends a trajectory.TrajectorySmoother bound to the tracker (part of the key).  None for one of the four
         association arguments: track.DEFAULTS (provisional).  Built and captured on first use; the least recently used one is
         dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
         eng = getattr(self, "_engine", None)
@@ -626,13 +663,21 @@ class AIRonMNIST(AIRModel):
         if tspec is not None:
             from .temporal import check_arguments as check_temporal
             check_temporal(eng.cfg, F, S * F, tspec[0], tspec[1])
+        sspec = self._smooth_spec(smooth)
+        if sspec is not None:
+            from .trajectory import check_arguments as check_smooth
+            check_smooth(eng.cfg.max_steps, F, S * F, assoc["max_age"], **sspec)
         key = (S, F, float(assoc["iou_gate"]), float(assoc["appearance_weight"]), float(assoc["birth_score"]), int(assoc["max_age"]),
                refine, lr, prune, spec, str(eng.device)) + (() if tspec is None else (("temporal",) + tspec,))
+        key += () if sspec is None else (("smooth",) + tuple(sorted(sspec.items())),)
         cache = self.__dict__.setdefault("_trackers", {})
         entry = cache.pop(key, None)
         if entry is None:
             stack = self._sequence_stack(S, F, refine, lr, prune, propose, tspec)
             stack.append(tr.SequenceTracker(stack[-1], F, **assoc))
+            if sspec is not None:
+                from .trajectory import TrajectorySmoother
+                stack.append(TrajectorySmoother(stack[-1], **sspec))
             for s in stack:
                 s.capture()
             entry = stack
@@ -640,7 +685,7 @@ class AIRonMNIST(AIRModel):
         while len(cache) > self.MAX_TRACKERS:
             for s in reversed(cache.pop(next(iter(cache)))):
                 s.release_graphs()
-        return entry[-1]
+        return entry
 
     MAX_TEMPORAL_PROPOSERS = 2
 
@@ -678,40 +723,61 @@ class AIRonMNIST(AIRModel):
         return entry[-1]
 
     def track(self, frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None,
-              prune=None, propose=None, temporal=None):
+              prune=None, propose=None, temporal=None, smooth=None):
         """Parse the frames [S, F, H, W] of S sequences on the device, each frame as `parse(refine=, prune=, propose=)` would parse
         it -- with temporal=P | (P, rounds) followed by proposals from the neighbour frames (temporal.TemporalProposer) -- and give
         the objects identities over time (track.SequenceTracker.track lists the returned device tensors: the parse of
         the S * F frames, row s * F + f, and next to it track_id, obj_state, affinity, prev_frame, prev_slot, the per-track tables and
-        track_owner; the next call overwrites them).  The training engine's parameters are read, nothing of it is written;
-        `self.obs` and the parsers of `parse` are not touched."""
+        track_owner; the next call overwrites them).  With smooth=True | dict(horizon=, process_noise=, measurement_noise=,
+        velocity_var=) the tracks are then smoothed, gap-filled and extrapolated (trajectory.TrajectorySmoother.result lists the sm_
+        and fc_ tensors and frames_pred that come on top); smooth=None is exactly the call without it.  The training engine's
+        parameters are read, nothing of it is written; `self.obs` and the parsers of `parse` are not touched."""
         import torch
         frames = torch.as_tensor(frames)
         if frames.dim() != 4:
             raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
-        t = self.tracker(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                         propose, temporal)
+        t = self._tracker_entry(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr,
+                                prune, propose, temporal, smooth)[-1]
         self._sync_engine_switches()
         t.load_from(self._engine)                            # every time: the weights move
         self.tracked = t.track(frames)
         return self.tracked
 
+    def predict_frames(self, frames, horizon, smooth=True, **track_args):
+        """`track(frames, smooth=...)` with a forecast horizon of `horizon` frames (1..16): returns (frames_pred [S, horizon, H, W],
+        result) -- the frames F, F + 1, ... rendered from the tracks still live after the last frame, each at its extrapolated place
+        with the decoded glimpse of its last sighting (no network evaluation); `result` is `track`'s dict.  `smooth` may carry the
+        smoother's other arguments; its horizon is set from `horizon`."""
+        spec = dict(self._smooth_spec(smooth) or self._smooth_spec(True))
+        if isinstance(horizon, bool) or int(horizon) != horizon or int(horizon) < 1:
+            raise ValueError("predict_frames: horizon must be an integer >= 1, got %r" % (horizon,))
+        spec["horizon"] = int(horizon)
+        out = self.track(frames, smooth=spec, **track_args)
+        return out["frames_pred"], out
+
     def score_track(self, frames, gt_boxes, tau=0.5, accumulate=True, gt_instances=None, thresholds=None, iou_gate=None,
                     appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None,
-                    temporal=None):
+                    temporal=None, smooth=None):
         """`track`, then the identity metric of the tracks against gt_boxes [S, F, G, 4] (G <= 8; slot g is the same object in every
         frame of a sequence, width <= 0 = absent) on the device (track.SequenceTracker.score).  The sums accumulate in the tracker
         this returns alongside -- (scores, tracker): its summary() reads MOTA, MOTP, the identity switches and the mostly tracked /
         lost fractions back once, its reset() starts a validation set.  With gt_instances [S, F, H, W] (int8, -1 = background) the
         S * F frames are also scored as images by a score.ParseScorer bound to the same provider (per-frame detection figures next to
-        the identity figures): scores["detection"] holds its tensors, `self.track_scorer` is that scorer."""
+        the identity figures): scores["detection"] holds its tensors, `self.track_scorer` is that scorer.  With smooth= the COMPLETED
+        table of the trajectory smoother is scored next to the raw one by the same kernel (TrajectorySmoother.score):
+        scores["completed"] holds its tensors, `self.track_smoother` is the smoother, whose summary() / reset() are the completed
+        table's -- the raw figures stay the tracker's."""
         import torch
-        self.track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal)
+        self.track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth)
         frames = torch.as_tensor(frames)
         t = self.tracker(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                         propose, temporal)
+                         propose, temporal, smooth)
         gb = torch.as_tensor(gt_boxes)
         scores = dict(t.score(gb, tau, accumulate))
+        if self._smooth_spec(smooth) is not None:
+            self.track_smoother = self.trajectory_smoother(frames.shape[0], frames.shape[1], smooth, iou_gate, appearance_weight,
+                                                           birth_score, max_age, refine, refine_lr, prune, propose, temporal)
+            scores["completed"] = self.track_smoother.score(gb, tau, accumulate)
         if gt_instances is not None:
             from .score import DEFAULT_THRESHOLDS, ParseScorer
             th = tuple(float(v) for v in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))

@@ -126,6 +126,14 @@ def main(argv=None):
                          "parses of the frames before and after it, ROUNDS times (default 1; temporal.TemporalProposer: the exact "
                          "subset search of --parse-prune over the frame's rows and its neighbours' rows, no network evaluation); "
                          "max_steps + P <= 6")
+    ap.add_argument("--track-smooth", nargs="?", const="", default=None, metavar="QS,QC,R",
+                    help="with --track-eval: smooth and gap-fill the tracks on the device (trajectory.TrajectorySmoother: a constant-rate "
+                         "Kalman filter and a backward pass per track) and score the completed table next to the raw one.  QS,QC,R: the "
+                         "process noise of the shifts and of the scales and the measurement noise, in `where` units (default "
+                         "1e-4,1e-4,4e-4: provisional, unmeasured on a trained model)")
+    ap.add_argument("--track-predict", type=int, default=None, metavar="HZ",
+                    help="with --track-eval: also extrapolate the live tracks HZ frames (1..16) past every sequence and render the "
+                         "predicted frames (AIRonMNIST.predict_frames' forecast table; implies --track-smooth)")
     ap.add_argument("--tf-name-map", default=None, metavar="JSON",
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
@@ -199,6 +207,25 @@ def main(argv=None):
         if track_eval is None:
             ap.error("--track-temporal goes with --track-eval")
         track_temporal = spec[0] if len(spec) == 1 else spec
+
+    track_smooth = None
+    if args.track_smooth is not None or args.track_predict is not None:
+        if track_eval is None:
+            ap.error("--track-smooth and --track-predict go with --track-eval")
+        track_smooth = {}
+        if args.track_smooth:
+            try:
+                qs, qc, r = (float(v) for v in args.track_smooth.split(","))
+            except ValueError:
+                ap.error("--track-smooth needs QS,QC,R (three positive numbers) or no value, got %r" % args.track_smooth)
+            if not (qs > 0 and qc > 0 and r > 0):
+                ap.error("--track-smooth needs three positive numbers, got %r" % args.track_smooth)
+            track_smooth.update(process_noise=(qs, qc), measurement_noise=r)
+        if args.track_predict is not None:
+            if not 1 <= args.track_predict <= 16:
+                ap.error("--track-predict needs 1 <= HZ <= 16, got %r" % args.track_predict)
+            track_smooth["horizon"] = args.track_predict
+        track_smooth = track_smooth or True
 
     learning_rate, n_steps, batch_size = args.learning_rate, 3, 64    # multi_mnist.py:24-25,37
     num_steps_prior = AttrDict(anneal='exp', init=1. - 1e-15, final=1e-7, steps_div=1e4, steps=1e5, hold_init=1e3)
@@ -351,7 +378,7 @@ def main(argv=None):
         seq_data = dict(imgs=raw["imgs"].astype("float32") / 255.0, boxes=raw["boxes"], instances=raw["instances"])
         before_track_log = log
         track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
-                                            **refine_kw)
+                                            smooth=track_smooth, **refine_kw)
 
         def log(train_itr):                               # noqa: F811
             out = before_track_log(train_itr)

@@ -868,6 +868,59 @@ AIR_ENGINE_API int air_track_owner(const signed char *owner, const int *track_id
 AIR_ENGINE_API int air_track_score(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
                     int T, int G, int S, int F, int R, int *seq_counts, double *seq_iou, int *gt_match, void *stream);
 
+/* ---- trajectories behind the tracker: smoothed, gap-filled and extrapolated tracks.  Inputs: the provider's where[T,R,4] = [sx, tx,
+ * sy, ty] and num_objects[R], air_track_associate's track_id[T,R], num_tracks[S], track_first / track_last[S, F T]; rows sequence-major,
+ * r = s F + f.  The limits of air_track_associate on T, F T and R hold (AIR_E_SHAPE).  C = min(32, T (max_age + 1)) rows per frame
+ * (AIR_E_SHAPE otherwise): a track that spans f without a sighting there was last seen in one of the max_age frames before f, and
+ * the live table holds at most 32 tracks.  Checks come before the launch: a refused call writes nothing.
+ * air_track_smooth: each sequence, each track id with 0 <= first <= last < F, each of the four where components on its own, in
+ *   float64 from the widened fp32 values, contraction off, only + - * /, in exactly this order.  Constant-rate model, dt = 1 frame,
+ *   state (x, v), covariance (Pxx, Pxv, Pvv); q = q_shift for tx, ty and q_scale for sx, sy; q4 = 0.25 q, q2 = 0.5 q.
+ *   Start at the first sighting z:  x = z, v = 0, Pxx = r, Pxv = 0, Pvv = velocity_var.
+ *   Predict, every frame up to `last`:  a = Pxx + Pxv, b = Pxv + Pvv, x- = x + v, v- = v, Pxx- = (a + b) + q4, Pxv- = b + q2,
+ *     Pvv- = Pvv + q.
+ *   Update, only in a frame where the track was sighted (the lowest slot j < clip(num_objects[r], 0, T) with track_id[j,r] == id)
+ *     with value z:  s = Pxx- + r, kx = Pxx- / s, kv = Pxv- / s, e = z - x-, x = x- + kx e, v = v- + kv e, Pxx = Pxx- - kx Pxx-,
+ *     Pxv = Pxv- - kx Pxv-, Pvv = Pvv- - kv Pxv-.  In a coasted frame the filtered state is the predicted one.
+ *   Backward (Rauch-Tung-Striebel, means only), f = last - 1 down to first; xs[last] = x, vs[last] = v:
+ *     g00 = Pxx + Pxv, g01 = Pxv, g10 = Pxv + Pvv, g11 = Pvv (filtered, frame f);  det = Pxx- Pvv- - Pxv- Pxv- (predicted, frame f + 1);
+ *     C00 = (g00 Pvv- - g01 Pxv-) / det, C01 = (g01 Pxx- - g00 Pxv-) / det, C10 = (g10 Pvv- - g11 Pxv-) / det,
+ *     C11 = (g11 Pxx- - g10 Pxv-) / det;  dx = xs[f+1] - x-[f+1], dv = vs[f+1] - v-[f+1];  xs[f] = x + (C00 dx + C01 dv),
+ *     vs[f] = v + (C10 dx + C11 dv).
+ *   So a track with one sighting returns its where bits, and a track whose sightings all carry one value returns that value bit for
+ *   bit with v = 0.  The filtered and predicted states the backward pass reads live in ws (float64, 8-byte aligned, at least
+ *   air_track_smooth_workspace_bytes(C, R) bytes: AIR_E_WORKSPACE).
+ *   The completed table.  In frame f the tracks with first <= f <= last take rows 0 .. n_f - 1 in ascending id (the row is the number
+ *   of spanning ids below one's own: integers, one fixed order).  Every element of every output is written:  sm_where[C,R,4] = xs
+ *   rounded once to fp32;  sm_boxes[C,R,4] = air_parse_objects' box of that fp32 row on the W x H image;  sm_id[C,R] (int32, -1 from
+ *   n_f on);  sm_state[C,R] (int8): 0 ABSENT, 1 OBSERVED, 2 FILLED;  sm_src_frame / sm_src_slot[C,R] (int32): the sighting itself, for
+ *   FILLED the latest sighting before f, -1 for ABSENT;  sm_velocity[C,R,2] = ((W vs_tx) 0.5, (H vs_ty) 0.5) in float64, rounded once:
+ *   pixels per frame of the box centre;  sm_count[R] = n_f;  sm_counts[S,3] (int32) = rows per state (they sum to C F).  ABSENT rows
+ *   hold zeros.  A track without a sighting in its `first` frame (no tracker writes one) starts from z = 0 as FILLED with source -1.
+ *   The forecast table, Hz in 0..16 (AIR_E_SHAPE otherwise), laid out [C, S Hz] with column s Hz + (k - 1), k = 1 .. Hz: the tracks
+ *   still live after the last frame, F - 1 - last <= max_age, in ascending id.  With m = F - 1 - last + k and the filtered state at
+ *   `last`:  tx' = x + (double) m v rounded once, ty' alike;  sx, sy = the values at `last` (scales are held).  fc_state = 3 FORECAST,
+ *   fc_src_frame / fc_src_slot = the last sighting, fc_boxes as sm_boxes, fc_velocity from the filtered v at `last`, fc_count[S Hz].
+ *   With Hz == 0 the fc_ pointers are not touched and may be NULL.
+ *   AIR_E_SHAPE also: q_shift, q_scale or r not > 0, velocity_var not >= 0 (NaN included).  where / sm_where / sm_boxes / fc_where /
+ *   fc_boxes 16-byte, ws / sm_velocity / fc_velocity 8-byte, everything else 4-byte aligned (AIR_E_ALIGN).  One workgroup of one wavefront
+ *   per sequence, one lane per track id, in passes of 64 ids when num_tracks exceeds the workgroup.
+ * air_track_fill: for a table of C rows and N columns (the completed table: N = R, per_seq = F; the forecast table: N = S Hz,
+ *   per_seq = Hz; column n belongs to sequence n / per_seq), out_what[C,N,A], out_glimpse[C,N,G], out_score[C,N] = bit copies of rows
+ *   (src_slot, s F + src_frame) of the provider's what[T,R,A], glimpse[T,R,G], score[T,R] (16-byte vectors where A resp. G is a
+ *   multiple of 4 and both buffers are 16-byte aligned, 4-byte words otherwise: air_propose_pool's rule); zeros where state is ABSENT
+ *   or the source is outside the provider's rows.  One wavefront per (row, column).  Every pointer 4-byte aligned (AIR_E_ALIGN).       */
+AIR_ENGINE_API size_t air_track_smooth_workspace_bytes(int C, int R);
+AIR_ENGINE_API int air_track_smooth(const float *where, const int *num_objects, const int *track_id, const int *num_tracks,
+                    const int *track_first, const int *track_last, int T, int S, int F, int R, int C, int Hz, int max_age, int H,
+                    int W, double q_shift, double q_scale, double r, double velocity_var, double *ws, size_t ws_bytes,
+                    float *sm_where, float *sm_boxes, int *sm_id, signed char *sm_state, int *sm_src_frame, int *sm_src_slot,
+                    float *sm_velocity, int *sm_count, int *sm_counts, float *fc_where, float *fc_boxes, int *fc_id,
+                    signed char *fc_state, int *fc_src_frame, int *fc_src_slot, float *fc_velocity, int *fc_count, void *stream);
+AIR_ENGINE_API int air_track_fill(const float *what, const float *glimpse, const float *score, const signed char *state,
+                    const int *src_frame, const int *src_slot, int T, int F, int R, int C, int N, int per_seq, int A, int G,
+                    float *out_what, float *out_glimpse, float *out_score, void *stream);
+
 /* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
  * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
  * (AIR_E_SHAPE otherwise, and when R*H*W or R*(T+1)*(G+1) passes int32).  No floating-point atomics; float64 with contraction off
