@@ -27,7 +27,9 @@ __global__ __launch_bounds__(PW_THREADS) void lstm_pw_fwd_kernel(const float *__
         const float gj = tanhf(gr[Hd + u]);
         const float gf = sigmoid_acc(gr[2 * (size_t)Hd + u] + fb);
         const float go = sigmoid_acc(gr[3 * (size_t)Hd + u]);
-        const float cn = gf * c_prev[e] + gi * gj;
+        // one rounding of gf * c_prev + (gi * gj): the form the fused steps (lstm_kernels.hip) compile to.  Left to the compiler this
+        // kernel contracted the other product, fma(gi, gj, gf * c_prev), and c / h differed from the fused step's in the last bit
+        const float cn = fmaf(gf, c_prev[e], gi * gj);
         c[e] = cn;
         h[e] = tanhf(cn) * go;
         if (gate_act) {

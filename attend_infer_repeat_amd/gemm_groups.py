@@ -8,7 +8,7 @@ Three policies live here:
   wide_form / shortk_mixed / tensors_read / foldable   what the folded closing update (engine_plan._fold_closing_update) must know
                        of the library's dispatch and of the flat buffers before it folds an update into a grouped launch;
   latency_tile / group_long_k / on_long_k_body / shortk_eligible / shortk_workgroups / latency_form / gather_fits / first_step_fits /
-  lstm_fwd_wide        the tile-form rules of the latency-regime grouped launches and of the LSTM step
+  lstm_fwd_wide / lstm_bwd_form / lstm_bwd_entry_fits / lstm_bf16_fits        the tile-form rules of the latency-regime grouped launches and of the LSTM step
                        (tests/test_fold_cases_host.py holds every kernel-level case against them).
 The predicates restate rules of the library (csrc/gemm_kernels.hip, csrc/lstm_kernels.hip); each names the function it mirrors."""
 from . import _lib
@@ -185,6 +185,28 @@ def lstm_fwd_wide(M, Hd, ldw=None, ldh=None, w_h=0, h_prev=0):
     ldw, ldh = 4 * Hd if ldw is None else ldw, Hd if ldh is None else ldh
     return bool(((M + 15) // 16) * ((Hd + 15) // 16) > FIRST_STEP_MAX_TILES and Hd % 64 == 0 and ldw % 4 == 0 and ldh % 4 == 0
                 and w_h % 16 == 0 and h_prev % 16 == 0)
+
+
+def lstm_bwd_form(M, Hd, dgates_next=0, w_h=0):
+    """lstm_kernels.hip lstm_bwd_launch: the body of one BPTT link (air_lstm_step_bwd[_opt]) -- "kw16": lstm_bwd_fused_kernel<16> up to
+    512 tiles of (batch, hidden); beyond, "wide": lstm_bwd_wide_kernel where Hd is a multiple of 64 and dgates_next [M, 4 Hd] and
+    w_h [Hd, 4 Hd] lie at 16-byte aligned byte addresses `dgates_next` / `w_h` (vecA, vecB), else "kw4": lstm_bwd_fused_kernel<4>"""
+    tiles = ((M + 15) // 16) * ((Hd + 15) // 16)
+    if tiles > FIRST_STEP_MAX_TILES and Hd % 64 == 0 and dgates_next % 16 == 0 and w_h % 16 == 0:
+        return "wide"
+    return "kw16" if tiles <= FIRST_STEP_MAX_TILES else "kw4"
+
+
+def lstm_bwd_entry_fits(M, Hd):
+    """lstm_kernels.hip air_lstm_step_bwd_entry_fits: the entry of the BPTT folded into its first link (lstm_bwd_entry_kernel) -- whole
+    16-unit chunks and at most 512 tiles of (batch, hidden)"""
+    return bool(M > 0 and Hd > 0 and Hd % 16 == 0 and ((M + 15) // 16) * (Hd // 16) <= FIRST_STEP_MAX_TILES)
+
+
+def lstm_bf16_fits(M, Hd):
+    """lstm_kernels.hip air_lstm_step_fwd_bf16 / air_lstm_step_bwd_bf16: the shape rule of the steps on the bf16 data path
+    (lstm_fwd_wide16_kernel / lstm_bwd_wide16_kernel, whatever the tile count) -- Hd a multiple of 64; anything else is AIR_E_SHAPE"""
+    return bool(M > 0 and Hd > 0 and Hd % 64 == 0)
 
 
 GAUSS_FOLD_MAX_TILES = 1000     # air_gemm_grouped_gauss_bwd

@@ -239,47 +239,117 @@ def linear_bwd(x, w, y, dy, act, want_dx=True, want_db=True):
     return dx, dw, db
 
 
-def lstm_pointwise_fwd(gates, c_prev, forget_bias=1.0):
+def _lstm_out(out, shapes, device):
+    """the caller's output buffers (a tuple, so that a test can prime and pad what a launch writes), or fresh ones of `shapes`
+    (None: an output the launch is not asked for)"""
+    if out is None:
+        return tuple(torch.empty(s, dtype=torch.float32, device=device) if s is not None else None for s in shapes)
+    if len(out) != len(shapes):
+        raise _lib.AirHipError(f"expected {len(shapes)} output buffers, got {len(out)}")
+    for o, s in zip(out, shapes):
+        if (o is None) != (s is None) or (o is not None and tuple(_f32(o, "out").shape) != tuple(s)):
+            raise _lib.AirHipError("an output buffer does not match the shape the launch writes")
+    return tuple(out)
+
+
+def lstm_pointwise_fwd(gates, c_prev, forget_bias=1.0, out=None, want_act=True):
+    """out = (h, c, gate_act): caller-owned buffers; want_act=False: gate_act = NULL"""
     gates = _f32(gates, "gates", 2); c_prev = _f32(c_prev, "c_prev", 2)
     M, Hd = c_prev.shape
-    h = torch.empty_like(c_prev); c = torch.empty_like(c_prev); act = torch.empty_like(gates)
+    h, c, act = _lstm_out(out, ((M, Hd), (M, Hd), (M, 4 * Hd) if want_act else None), c_prev.device)
     _lib.check(lib().air_lstm_pointwise_fwd(_p(gates), _p(c_prev), _p(h), _p(c), _p(act), M, Hd, float(forget_bias),
                                             _stream()), "air_lstm_pointwise_fwd")
     return h, c, act
 
 
-def lstm_pointwise_bwd(gate_act, c_prev, c, dh, dc):
+def lstm_pointwise_bwd(gate_act, c_prev, c, dh, dc, dh2=None, out=None):
+    """out = (dgates, dc_prev): caller-owned buffers"""
     gate_act = _f32(gate_act, "gate_act", 2); c_prev = _f32(c_prev, "c_prev", 2); c = _f32(c, "c", 2)
-    dh = _f32(dh, "dh"); dc = _f32(dc, "dc")
+    dh = _f32(dh, "dh"); dc = _f32(dc, "dc"); dh2 = _f32(dh2, "dh2")
     M, Hd = c_prev.shape
-    dgates = torch.empty_like(gate_act); dc_prev = torch.empty_like(c_prev)
-    _lib.check(lib().air_lstm_pointwise_bwd(_p(gate_act), _p(c_prev), _p(c), _p(dh), None, _p(dc), _p(dgates),
+    dgates, dc_prev = _lstm_out(out, ((M, 4 * Hd), (M, Hd)), c_prev.device)
+    _lib.check(lib().air_lstm_pointwise_bwd(_p(gate_act), _p(c_prev), _p(c), _p(dh), _p(dh2), _p(dc), _p(dgates),
                                             _p(dc_prev), M, Hd, _stream()), "air_lstm_pointwise_bwd")
     return dgates, dc_prev
 
 
-def lstm_step_fwd(h_prev, c_prev, w_h, gx, forget_bias=1.0, precision=0):
-    """fused recurrent product + gate math: (h, c, gate_act) from h_prev[M,Hd], c_prev[M,Hd], w_h[Hd,4Hd], gx[M,4Hd]"""
-    h_prev = _f32(h_prev, "h_prev", 2); c_prev = _f32(c_prev, "c_prev", 2); gx = _f32(gx, "gx", 2)
+def _bf16(t, name, shape=None):
+    if t is None:
+        return None
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()):
+        raise _lib.AirHipError(f"{name}: expected a contiguous bfloat16 CUDA tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise _lib.AirHipError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def lstm_pointwise_bwd_bf16(gate_act, c_prev, c, dh, dc, dgates_bf16, dh2=None, out=None):
+    """air_lstm_pointwise_bwd_bf16: air_lstm_pointwise_bwd that also writes the bf16 mirror of dgates -> dgates, dc_prev"""
+    gate_act = _f32(gate_act, "gate_act", 2); c_prev = _f32(c_prev, "c_prev", 2); c = _f32(c, "c", 2)
+    dh = _f32(dh, "dh"); dc = _f32(dc, "dc"); dh2 = _f32(dh2, "dh2")
+    M, Hd = c_prev.shape
+    _bf16(dgates_bf16, "dgates_bf16", (M, 4 * Hd))
+    dgates, dc_prev = _lstm_out(out, ((M, 4 * Hd), (M, Hd)), c_prev.device)
+    _lib.check(lib().air_lstm_pointwise_bwd_bf16(_p(gate_act), _p(c_prev), _p(c), _p(dh), _p(dh2), _p(dc), _p(dgates), _p(dgates_bf16),
+                                                 _p(dc_prev), M, Hd, _stream()), "air_lstm_pointwise_bwd_bf16")
+    return dgates, dc_prev
+
+
+def lstm_step_fwd(h_prev, c_prev, w_h, gx, forget_bias=1.0, precision=0, out=None):
+    """fused recurrent product + gate math: (h, c, gate_act) from h_prev[M,Hd], c_prev[M,Hd], w_h[Hd,4Hd], gx[M,4Hd] (w_h and gx may
+    be row views of wider buffers); out = (h, c, gate_act): caller-owned buffers"""
+    h_prev = _f32(h_prev, "h_prev", 2); c_prev = _f32(c_prev, "c_prev", 2)
+    M, Hd = c_prev.shape
+    ldgx = _mat(gx, "gx", 4 * Hd)
     if not (w_h.is_cuda and w_h.dtype == torch.float32 and w_h.dim() == 2 and w_h.stride(1) == 1):
         raise ValueError("w_h must be a row-major fp32 CUDA matrix (row stride allowed)")
-    M, Hd = c_prev.shape
-    h = torch.empty_like(c_prev); c = torch.empty_like(c_prev); act = torch.empty_like(gx)
-    _lib.check(lib().air_lstm_step_fwd(_p(h_prev), _p(c_prev), _p(w_h), w_h.stride(0), _p(gx), gx.stride(0), _p(h), _p(c),
+    h, c, act = _lstm_out(out, ((M, Hd), (M, Hd), (M, 4 * Hd)), c_prev.device)
+    _lib.check(lib().air_lstm_step_fwd(_p(h_prev), _p(c_prev), _p(w_h), w_h.stride(0), _p(gx), ldgx, _p(h), _p(c),
                                        _p(act), M, Hd, float(forget_bias), int(precision), _stream()), "air_lstm_step_fwd")
     return h, c, act
 
 
-def lstm_step_bwd(dgates_next, w_h, dh_a, dh_b, dc_in, gate_act, c_prev, c, dgx_in=None, want_dgx=False, precision=0):
-    """fused BPTT link: dh = dgates_next . w_h^T + dh_a + dh_b, then the pointwise backward -> dgates, dc_prev[, dgx]"""
+def lstm_step_fwd_bf16(h_prev, c_prev, w_h_bf16, gx, forget_bias=1.0, h_prev_bf16=None, h_bf16=None, out=None):
+    """air_lstm_step_fwd_bf16: W_h from its bf16 shadow [Hd, 4Hd], h_prev from its bf16 mirror where one is given, the bf16 mirror of
+    h written where one is given -> h, c, gate_act"""
+    h_prev = _f32(h_prev, "h_prev", 2); c_prev = _f32(c_prev, "c_prev", 2)
+    M, Hd = c_prev.shape
+    ldgx = _mat(gx, "gx", 4 * Hd)
+    _bf16(w_h_bf16, "w_h_bf16", (Hd, 4 * Hd)); _bf16(h_prev_bf16, "h_prev_bf16", (M, Hd)); _bf16(h_bf16, "h_bf16", (M, Hd))
+    h, c, act = _lstm_out(out, ((M, Hd), (M, Hd), (M, 4 * Hd)), c_prev.device)
+    _lib.check(lib().air_lstm_step_fwd_bf16(_p(h_prev), _p(h_prev_bf16), _p(c_prev), _p(w_h_bf16), 4 * Hd, _p(gx), ldgx, _p(h), _p(h_bf16),
+                                            _p(c), _p(act), M, Hd, float(forget_bias), _stream()), "air_lstm_step_fwd_bf16")
+    return h, c, act
+
+
+def lstm_step_bwd(dgates_next, w_h, dh_a, dh_b, dc_in, gate_act, c_prev, c, dgx_in=None, want_dgx=False, precision=0, out=None):
+    """fused BPTT link: dh = dgates_next . w_h^T + dh_a + dh_b, then the pointwise backward -> dgates, dc_prev[, dgx];
+    out = (dgates, dc_prev, dgx | None): caller-owned buffers (dgx may be dgx_in itself: the running sum in place)"""
     dgates_next = _f32(dgates_next, "dgates_next", 2); w_h = _f32(w_h, "w_h", 2)
     gate_act = _f32(gate_act, "gate_act", 2); c_prev = _f32(c_prev, "c_prev", 2); c = _f32(c, "c", 2)
     M, Hd = c_prev.shape
-    dgates = torch.empty_like(gate_act); dc_prev = torch.empty_like(c_prev)
-    dgx = torch.empty_like(gate_act) if want_dgx else None
+    dgates, dc_prev, dgx = _lstm_out(out, ((M, 4 * Hd), (M, Hd), (M, 4 * Hd) if (want_dgx if out is None else out[2] is not None) else None),
+                                      c_prev.device)
     _lib.check(lib().air_lstm_step_bwd(_p(dgates_next), _p(w_h), _p(dh_a), _p(dh_b), _p(dc_in), _p(gate_act), _p(c_prev),
                                        _p(c), _p(dgx_in), _p(dgates), _p(dc_prev), _p(dgx), M, Hd, int(precision),
                                        _stream()), "air_lstm_step_bwd")
+    return dgates, dc_prev, dgx
+
+
+def lstm_step_bwd_bf16(dgates_next, w_h_bf16, dh_a, dh_b, dc_in, gate_act, c_prev, c, dgx_in=None, dgates_next_bf16=None, dgates_bf16=None,
+                       dgx_bf16=None, out=None):
+    """air_lstm_step_bwd_bf16: the link with W_h from its bf16 shadow, dgates_next from its mirror where one is given, and the mirrors
+    of dgates / the running dgx written where given; out = (dgates, dc_prev, dgx | None) -> dgates, dc_prev, dgx"""
+    dgates_next = _f32(dgates_next, "dgates_next", 2)
+    gate_act = _f32(gate_act, "gate_act", 2); c_prev = _f32(c_prev, "c_prev", 2); c = _f32(c, "c", 2)
+    M, Hd = c_prev.shape
+    _bf16(w_h_bf16, "w_h_bf16", (Hd, 4 * Hd))
+    for t, nm in ((dgates_next_bf16, "dgates_next_bf16"), (dgates_bf16, "dgates_bf16"), (dgx_bf16, "dgx_bf16")):
+        _bf16(t, nm, (M, 4 * Hd))
+    dgates, dc_prev, dgx = _lstm_out(out, ((M, 4 * Hd), (M, Hd), (M, 4 * Hd) if (out is None or out[2] is not None) else None), c_prev.device)
+    _lib.check(lib().air_lstm_step_bwd_bf16(_p(dgates_next), _p(dgates_next_bf16), _p(w_h_bf16), _p(dh_a), _p(dh_b), _p(dc_in), _p(gate_act),
+                                            _p(c_prev), _p(c), _p(dgx_in), _p(dgates), _p(dgates_bf16), _p(dc_prev), _p(dgx), _p(dgx_bf16),
+                                            M, Hd, _stream()), "air_lstm_step_bwd_bf16")
     return dgates, dc_prev, dgx
 
 
@@ -305,27 +375,27 @@ def lstm_pointwise_bwd_opt(gate_act, c_prev, c, dh, dc, opt):
     return dgates, dc_prev
 
 
-def lstm_step_bwd_opt(dgates_next, w_h, dh_a, dh_b, dc_in, gate_act, c_prev, c, opt, precision=0):
-    """air_lstm_step_bwd with an optimiser slice riding along"""
+def lstm_step_bwd_opt(dgates_next, w_h, dh_a, dh_b, dc_in, gate_act, c_prev, c, opt, precision=0, out=None):
+    """air_lstm_step_bwd with an optimiser slice riding along; out = (dgates, dc_prev): caller-owned buffers"""
     dgates_next = _f32(dgates_next, "dgates_next", 2); w_h = _f32(w_h, "w_h", 2)
     gate_act = _f32(gate_act, "gate_act", 2); c_prev = _f32(c_prev, "c_prev", 2); c = _f32(c, "c", 2)
     M, Hd = c_prev.shape
-    dgates = torch.empty_like(gate_act); dc_prev = torch.empty_like(c_prev)
+    dgates, dc_prev = _lstm_out(out, ((M, 4 * Hd), (M, Hd)), c_prev.device)
     _lib.check(lib().air_lstm_step_bwd_opt(_p(dgates_next), _p(w_h), _p(dh_a), _p(dh_b), _p(dc_in), _p(gate_act), _p(c_prev),
                                            _p(c), None, _p(dgates), _p(dc_prev), None, M, Hd, int(precision),
                                            ctypes.byref(opt) if opt is not None else None, _stream()), "air_lstm_step_bwd_opt")
     return dgates, dc_prev
 
 
-def lstm_step_bwd_entry(gate_act1, c_prev1, c1, dh_a1, dh_b1, w_h, dh_a, dh_b, gate_act, c_prev, c, opt=None, want_dgx=True):
+def lstm_step_bwd_entry(gate_act1, c_prev1, c1, dh_a1, dh_b1, w_h, dh_a, dh_b, gate_act, c_prev, c, opt=None, want_dgx=True, out=None):
     """air_lstm_step_bwd_entry: pointwise backward of the last step + the first BPTT link in one launch.
-    Returns (dgates1, dc_prev1, dgates, dc_prev, dgx)"""
+    out = (dgates1, dc_prev1, dgates, dc_prev, dgx | None): caller-owned buffers.  Returns (dgates1, dc_prev1, dgates, dc_prev, dgx)"""
     gate_act1 = _f32(gate_act1, "gate_act1", 2); c_prev1 = _f32(c_prev1, "c_prev1", 2); c1 = _f32(c1, "c1", 2)
     w_h = _f32(w_h, "w_h", 2); gate_act = _f32(gate_act, "gate_act", 2); c_prev = _f32(c_prev, "c_prev", 2); c = _f32(c, "c", 2)
     M, Hd = c_prev.shape
-    dgates1 = torch.empty_like(gate_act1); dc_prev1 = torch.empty_like(c_prev1)
-    dgates = torch.empty_like(gate_act); dc_prev = torch.empty_like(c_prev)
-    dgx = torch.empty_like(gate_act) if want_dgx else None
+    dgates1, dc_prev1, dgates, dc_prev, dgx = _lstm_out(out, ((M, 4 * Hd), (M, Hd), (M, 4 * Hd), (M, Hd),
+                                                              (M, 4 * Hd) if (want_dgx if out is None else out[4] is not None) else None),
+                                                        c_prev.device)
     _lib.check(lib().air_lstm_step_bwd_entry(_p(gate_act1), _p(c_prev1), _p(c1), _p(dh_a1), _p(dh_b1), _p(dgates1), _p(dc_prev1),
                                              _p(w_h), _p(dh_a), _p(dh_b), _p(gate_act), _p(c_prev), _p(c), _p(dgates), _p(dc_prev),
                                              _p(dgx), M, Hd, ctypes.byref(opt) if opt is not None else None, _stream()),
