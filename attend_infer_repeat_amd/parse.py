@@ -23,12 +23,12 @@ entry) and appends the launches of libair_hip.so that include/air_hip.h describe
 Forward and read-outs are one hipGraph per variant (model counts / given counts) after `capture()`.  Known waste, deliberate for
 now: the forward plan still writes an all-present canvas and its reconstruction sum; the parse discards both.
 """
-import ctypes
 from typing import Dict
 
 from .engine_config import EngineConfig
 from .iw_eval import inner_config, load_inner_engine
 from .launch import destroy_graphs
+from .stage import ReadOut, engine_rows
 
 
 def check_config(cfg: EngineConfig) -> None:
@@ -40,6 +40,8 @@ def check_config(cfg: EngineConfig) -> None:
 
 
 class SceneParser:
+    KIND = "scene"
+
     def __init__(self, cfg: EngineConfig, batch_size: int, device=None, seed: int = 0, mask_threshold: float = 0.02,
                  keep_layers: bool = False):
         check_config(cfg)
@@ -56,22 +58,11 @@ class SceneParser:
         self.engine = AIREngine(inner_config(cfg), self.R, device=device, seed=seed, keep_canvas_steps=False)
         eng, dev = self.engine, self.engine.device
         self.T = eng.T
-        R, T, A = self.R, self.T, int(cfg.n_appearance)
-        (Hi, Wi) = cfg.img_size
-        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
         with torch.cuda.device(dev):
-            self.num_objects_in = z((R,), torch.int32)
-            self.num_objects, self.count_prob = z((R,), torch.int32), z((R,))
-            self.presence, self.score, self.boxes = z((T, R)), z((T, R)), z((T, R, 4))
-            self.offsets = z((R + 1,), torch.int32)
-            self.obj_image, self.obj_step = z((T * R,), torch.int32), z((T * R,), torch.int32)
-            self.obj_box, self.obj_score = z((T * R, 4)), z((T * R,))
-            self.obj_where, self.obj_what = z((T * R, 4)), z((T * R, A))
-            self.reconstruction = z((R, Hi, Wi))
-            self.rec_parts, self.rec = z((eng.n_bands, R)), z((R,))
-            self.owner = z((R, Hi, Wi), torch.int8)
-            self.area = z((T, R), torch.int32)
-            self.layers = z((T, R, Hi, Wi)) if keep_layers else None
+            self.num_objects_in = torch.zeros((self.R,), dtype=torch.int32, device=dev)
+        self._ro = ReadOut(H, eng, self.T, self.R, cfg.n_appearance, cfg.img_size, eng.n_bands, self.mask_threshold, keep_layers)
+        self._ro.alias(self)
+        self.layers = self._ro.layers
         # bf16 data path: the engine's constructor zero-fills the parameter shadow on the caller's stream and converts into it on its own
         # stream without ordering the two; it has synchronised the device since, so converting once more here leaves the right shadow
         # (a parser that never loads parameters -- tools/parse_bench.py -- otherwise sometimes kept a zeroed one)
@@ -85,23 +76,14 @@ class SceneParser:
 
     # ---- the launches behind the engine's forward plan -----------------------------------------------------------------------
     def _build_tail(self):
-        H, eng, cfg = self._H, self.engine, self.engine.cfg
-        L, p = H.lib(), H._p
-        T, R, A = self.T, self.R, int(cfg.n_appearance)
-        (Hi, Wi), (hc, wc) = cfg.img_size, cfg.crop_size
+        eng, ro = self.engine, self._ro
+        tail = lambda given: [ro.objects(eng.presence_prob, self.num_objects_in if given else None, eng.where, eng.what)] + \
+            ro.tail(eng.gd.out[-1], eng.where, eng.obs)
+        self._plans = {given: list(eng._plan_fwd) + tail(given) for given in (False, True)}
 
-        def objects(given):
-            return (L.air_parse_objects,
-                    (p(eng.presence_prob), p(self.num_objects_in) if given else None, p(eng.where), p(eng.what), T, R, A, Hi, Wi,
-                     p(self.num_objects), p(self.count_prob), p(self.presence), p(self.score), p(self.boxes), p(self.offsets),
-                     p(self.obj_image), p(self.obj_step), p(self.obj_box), p(self.obj_score), p(self.obj_where), p(self.obj_what)),
-                    "air_parse_objects")
-        render = (L.air_parse_render,
-                  (p(eng.gd.out[-1]), p(eng.where), p(self.presence), p(eng.obs), float(cfg.output_multiplier), float(cfg.output_std),
-                   self.mask_threshold, T, R, Hi, Wi, hc, wc, eng.n_bands, p(self.reconstruction), p(self.rec_parts), p(self.owner),
-                   p(self.area), p(self.layers) if self.layers is not None else None), "air_parse_render")
-        rec_sum = (L.air_sum_leading, (p(self.rec_parts), p(self.rec), eng.n_bands, ctypes.c_size_t(R)), "air_sum_leading")
-        self._plans = {given: list(eng._plan_fwd) + [objects(given), render, rec_sum] for given in (False, True)}
+    def rows(self):
+        """the provider protocol (stage.py): the parse is left in the engine's own buffers"""
+        return engine_rows(self.engine)
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `parse()` call (air_parse_objects is three kernels: count, scan, table; air_parse_render zeroes `area` in
@@ -177,13 +159,8 @@ class SceneParser:
         key = n is not None
         eng._replay_or_run(self._graphs.get(key), self._plans[key])
         eng.wait_for_engine()
-        cfg = eng.cfg
-        out = {"num_objects": self.num_objects, "count_prob": self.count_prob, "num_steps_posterior": eng.q_n,
-               "presence_prob": eng.presence_prob, "presence": self.presence, "score": self.score, "boxes": self.boxes,
-               "what": eng.what, "where": eng.where, "glimpse": eng.gd.out[-1].view(self.T, R, *cfg.crop_size),
-               "offsets": self.offsets, "obj_image": self.obj_image, "obj_step": self.obj_step, "obj_box": self.obj_box,
-               "obj_score": self.obj_score, "obj_where": self.obj_where, "obj_what": self.obj_what,
-               "reconstruction": self.reconstruction, "rec": self.rec, "owner": self.owner, "area": self.area}
+        out = self._ro.result(eng.gd.out[-1])
+        out.update({"num_steps_posterior": eng.q_n, "presence_prob": eng.presence_prob, "what": eng.what, "where": eng.where})
         if self.layers is not None:
             out["layers"] = self.layers
         return out

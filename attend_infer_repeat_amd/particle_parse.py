@@ -28,6 +28,7 @@ from typing import Dict
 from . import iw_eval
 from .engine_config import EngineConfig
 from .launch import destroy_graphs
+from .stage import ReadOut
 
 CRITERIA = {"weight": 0, "joint": 1}
 
@@ -43,6 +44,8 @@ def check_arguments(cfg: EngineConfig, batch_size: int, particles: int, select: 
 
 
 class ParticleParser:
+    KIND = "particle"
+
     def __init__(self, cfg: EngineConfig, batch_size: int, particles: int, select: str = "joint", device=None, seed: int = 0,
                  mask_threshold: float = 0.02, keep_layers: bool = False, normalize_steps_prior: bool = True):
         check_arguments(cfg, batch_size, particles, select)
@@ -72,17 +75,9 @@ class ParticleParser:
             self.where_sel, self.what_sel, self.presence_prob_sel = z((T, B, 4)), z((T, B, A)), z((T, B))
             self.glimpse_sel = z((T, B, hc, wc))
             self.where_mean, self.where_std, self.presence_iw = z((T, B, 4)), z((T, B, 4)), z((T, B))
-            self.num_objects, self.count_prob = z((B,), torch.int32), z((B,))
-            self.presence, self.score, self.boxes = z((T, B)), z((T, B)), z((T, B, 4))
-            self.offsets = z((B + 1,), torch.int32)
-            self.obj_image, self.obj_step = z((T * B,), torch.int32), z((T * B,), torch.int32)
-            self.obj_box, self.obj_score = z((T * B, 4)), z((T * B,))
-            self.obj_where, self.obj_what = z((T * B, 4)), z((T * B, A))
-            self.reconstruction = z((B, Hi, Wi))
-            self.rec_parts, self.rec = z((self.n_bands, B)), z((B,))
-            self.owner = z((B, Hi, Wi), torch.int8)
-            self.area = z((T, B), torch.int32)
-            self.layers = z((T, B, Hi, Wi)) if keep_layers else None
+        self._ro = ReadOut(H, eng, T, B, A, cfg.img_size, self.n_bands, self.mask_threshold, keep_layers)
+        self._ro.alias(self)
+        self.layers = self._ro.layers
         eng._sync_param_shadow()                              # (see parse.SceneParser: the bf16 shadow of a parser that never loads)
         self._graphs = {}
         self._H = H
@@ -95,7 +90,7 @@ class ParticleParser:
         L, p = H.lib(), H._p
         B, K, T, A = self.B, self.K, self.T, int(cfg.n_appearance)
         R = B * K
-        (Hi, Wi), (hc, wc) = cfg.img_size, cfg.crop_size
+        (hc, wc) = cfg.crop_size
         shift_loc = cfg.where_shift_prior[0]
         tail = [
             (L.air_iw_logweight,
@@ -116,21 +111,16 @@ class ParticleParser:
               p(self.glimpse_sel)), "air_particle_select"),
             (L.air_particle_spread, (p(self.log_weights), p(self.num_steps), p(eng.where), T, R, K, p(self.where_mean),
                                      p(self.where_std), p(self.presence_iw)), "air_particle_spread"),
-            (L.air_parse_objects,
-             (p(self.presence_prob_sel), p(self.num_objects_in), p(self.where_sel), p(self.what_sel), T, B, A, Hi, Wi,
-              p(self.num_objects), p(self.count_prob), p(self.presence), p(self.score), p(self.boxes), p(self.offsets),
-              p(self.obj_image), p(self.obj_step), p(self.obj_box), p(self.obj_score), p(self.obj_where), p(self.obj_what)),
-             "air_parse_objects"),
-            (L.air_parse_render,
-             (p(self.glimpse_sel), p(self.where_sel), p(self.presence), p(self.obs), float(cfg.output_multiplier),
-              float(cfg.output_std), self.mask_threshold, T, B, Hi, Wi, hc, wc, self.n_bands, p(self.reconstruction),
-              p(self.rec_parts), p(self.owner), p(self.area), p(self.layers) if self.layers is not None else None),
-             "air_parse_render"),
-            (L.air_sum_leading, (p(self.rec_parts), p(self.rec), self.n_bands, ctypes.c_size_t(B)), "air_sum_leading"),
-        ]
+            self._ro.objects(self.presence_prob_sel, self.num_objects_in, self.where_sel, self.what_sel),
+            *self._ro.tail(self.glimpse_sel, self.where_sel, self.obs)]
         # fresh particles per call: the Philox offset moves behind the forward (a train step moves it in its closing update)
         advance = (L.air_rng_advance, (p(eng.rng_state), ctypes.c_uint64(eng._rng_inc)), "air_rng_advance")
         self._plans = {True: list(eng._plan_fwd_noise) + [advance] + tail, False: list(eng._plan_fwd) + tail}
+
+    def rows(self):
+        """the provider protocol (stage.py): the selected particle's rows; where_loc is particle 0's, to be gathered per call"""
+        return {"what": self.what_sel, "where": self.where_sel, "glimpse": self.glimpse_sel, "presence_prob": self.presence_prob_sel,
+                "obs": self.obs, "where_loc": None, "gather_loc": True, "compacted": False}
 
     def launch_count(self, sample_noise: bool = True) -> Dict[str, int]:
         """entries of one `parse()` call (air_particle_select is two kernels: arg-max, then the gather; air_parse_objects three)"""
@@ -199,16 +189,13 @@ class ParticleParser:
         key = bool(sample_noise)
         eng._replay_or_run(self._graphs.get(key), self._plans[key])
         eng.wait_for_engine()
-        out = {"num_objects": self.num_objects, "count_prob": self.count_prob,
-               "num_steps_posterior": eng.q_n.view(B, K, T + 1)[:, 0], "presence_prob": self.presence_prob_sel,
-               "presence": self.presence, "score": self.score, "boxes": self.boxes, "what": self.what_sel, "where": self.where_sel,
-               "glimpse": self.glimpse_sel, "offsets": self.offsets, "obj_image": self.obj_image, "obj_step": self.obj_step,
-               "obj_box": self.obj_box, "obj_score": self.obj_score, "obj_where": self.obj_where, "obj_what": self.obj_what,
-               "reconstruction": self.reconstruction, "rec": self.rec, "owner": self.owner, "area": self.area,
-               "best_particle": self.best_particle, "best_score": self.best_score, "degenerate": self.degenerate,
-               "log_weights": self.log_weights, "log_q": self.log_q, "num_steps": self.num_steps, "iw_bound": self.iw_bound,
-               "ess": self.ess, "num_steps_posterior_iw": self.num_steps_posterior_iw, "where_mean": self.where_mean,
-               "where_std": self.where_std, "presence_iw": self.presence_iw}
+        out = self._ro.result(self.glimpse_sel)
+        out.update({"num_steps_posterior": eng.q_n.view(B, K, T + 1)[:, 0], "presence_prob": self.presence_prob_sel,
+                    "what": self.what_sel, "where": self.where_sel,
+                    "best_particle": self.best_particle, "best_score": self.best_score, "degenerate": self.degenerate,
+                    "log_weights": self.log_weights, "log_q": self.log_q, "num_steps": self.num_steps, "iw_bound": self.iw_bound,
+                    "ess": self.ess, "num_steps_posterior_iw": self.num_steps_posterior_iw, "where_mean": self.where_mean,
+                    "where_std": self.where_std, "presence_iw": self.presence_iw})
         if self.layers is not None:
             out["layers"] = self.layers
         return out

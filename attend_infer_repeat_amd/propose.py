@@ -39,7 +39,7 @@ from typing import Dict
 
 from . import prune
 from .engine_config import EngineConfig
-from .launch import destroy_graphs
+from .stage import BoundStage, ReadOut, compacted_rows
 
 MAX_POOL = prune.MAX_STEPS                                         # air_prune_score is instantiated up to 6 rows
 SEGMENTS = ("residual", "forward", "pool", "score", "select", "source")
@@ -106,148 +106,81 @@ def reference_source(pool_source, kept_step):
     return np.take_along_axis(pool_source, kept_step.astype(np.int64), 0).astype(np.int32)
 
 
-class ParseProposer:
+class ParseProposer(BoundStage):
+    KIND = "subset"
+    ACCEPTS = prune.ParsePruner.ACCEPTS
+    KEY_FIELDS = prune.ParsePruner.KEY_FIELDS
+
     def __init__(self, parser, proposals: int = 1, rounds: int = 1, clamp_hi: float = 1.0, normalize_steps_prior: bool = True):
+        self._start = self.bind(parser)
         cfg = parser.engine.cfg
         check_arguments(cfg, proposals, rounds)
         import torch
         from . import hip as H
         from .parse import SceneParser
         self.parser, self.engine = parser, parser.engine
+        self._bound = parser
         self.proposals, self.rounds, self.clamp_hi = int(proposals), int(rounds), float(clamp_hi)
         self.normalize_steps_prior = bool(normalize_steps_prior)
         self.T, self.R = parser.T, parser.R
         self.C = self.T + self.proposals
         self.mask_threshold = parser.mask_threshold
         eng, dev = self.engine, self.engine.device
-        T, B, A, P, C, Rn = self.T, self.R, int(cfg.n_appearance), self.proposals, self.C, self.rounds
-        (Hi, Wi), hw = cfg.img_size, cfg.n_crop
-        NM = 1 << C
+        T, B, Rn = self.T, self.R, self.rounds
+        (Hi, Wi) = cfg.img_size
         # the proposal pass: a B-row engine at the mode, built as SceneParser builds its own
         self.proposal = SceneParser(cfg, B, device=dev, mask_threshold=self.mask_threshold)
         self.n_bands = int(H.lib().air_canvas_unroll_bands(B, int(Hi)))
-        self._start = prune._start_buffers(parser)
-        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
         with torch.cuda.device(dev):
-            self.res_parts, self.residual_energy = z((Rn, self.n_bands, B)), z((Rn, B))
-            self.pool_what, self.pool_where, self.pool_glimpse = z((Rn, C, B, A)), z((Rn, C, B, 4)), z((Rn, C, B, hw))
-            self.pool_score, self.pool_presence = z((Rn, C, B)), z((Rn, C, B))
-            # every round has its own pool, joint table and compacted rows; pool_prior is ONE buffer, not per-round state: every
-            # round's air_propose_pool rewrites it with the same values (the count table followed by zeros)
-            self.pool_source, self.pool_prior = z((Rn, C, B), torch.int32), z((C + 1,), torch.float64)
-            self.rec_sub = z((Rn, self.n_bands, B, NM))
-            self.J_sub = torch.full((Rn, B, NM), float("nan"), dtype=torch.float64, device=dev)
-            self.best_mask, self.num_objects_round = z((Rn, B), torch.int32), z((Rn, B), torch.int32)
-            self.kept_pool = z((Rn, C, B), torch.int32)
-            self.objective_rounds, self._objective_start = z((Rn + 1, B), torch.float64), z((Rn, B), torch.float64)
-            self.evidence = z((Rn, C, B), torch.float64)
-            self.out_what, self.out_where, self.out_glimpse = z((Rn, C, B, A)), z((Rn, C, B, 4)), z((Rn, C, B, hw))
-            self.out_score, self.source_out = z((Rn, C, B)), z((Rn, C, B), torch.int32)
-            # the read-out of the last round's first T rows (what the parsers keep)
-            self.what, self.where, self.glimpse = self.out_what[-1, :T], self.out_where[-1, :T], self.out_glimpse[-1, :T]
-            self.score_src, self.kept_step = self.out_score[-1, :T], self.source_out[-1, :T]
-            self.num_objects_in = self.num_objects_round[-1]
-            self.num_objects, self.count_prob = z((B,), torch.int32), z((B,))
-            self.presence, self.score, self.boxes = z((T, B)), z((T, B)), z((T, B, 4))
-            self.offsets = z((B + 1,), torch.int32)
-            self.obj_image, self.obj_step = z((T * B,), torch.int32), z((T * B,), torch.int32)
-            self.obj_box, self.obj_score = z((T * B, 4)), z((T * B,))
-            self.obj_where, self.obj_what = z((T * B, 4)), z((T * B, A))
-            self.reconstruction = z((B, Hi, Wi))
-            self.rec_parts, self.rec = z((self.n_bands, B)), z((B,))
-            self.owner = z((B, Hi, Wi), torch.int8)
-            self.area = z((T, B), torch.int32)
-        self.objective_start_rounds = [self.objective_rounds[0]] + [self._objective_start[r] for r in range(1, Rn)]
+            self.res_parts = torch.zeros((Rn, self.n_bands, B), device=dev)
+            self.residual_energy = torch.zeros((Rn, B), device=dev)
+        self._search = prune.SubsetSearchRounds(H, eng, Rn, T, self.proposals, B, self.n_bands)
+        self._search.alias(self)
+        # the read-out of the last round's first T rows (what the parsers keep)
+        self._ro = ReadOut(H, eng, T, B, cfg.n_appearance, cfg.img_size, self.n_bands, self.mask_threshold)
+        self._ro.alias(self)
         self.residual = self.proposal.engine.obs.view(B, Hi, Wi)
-        self._graph = None
         self._H = H
-        self._build_plan()
+        self._rebuild()
         eng.synchronize()
         self.proposal.engine.synchronize()
 
+    def rows(self):
+        """the provider protocol (stage.py): the compacted rows; presence_prob and the images are the start parse's"""
+        return compacted_rows(self, self._start["presence_prob"], self._start["obs"])
+
     # ---- the launches behind the provider's own call -------------------------------------------------------------------------
     def _build_plan(self):
-        H, eng, par, st, ieng = self._H, self.engine, self.parser, self._start, self.proposal.engine
+        H, eng, par, st, ieng, search = self._H, self.engine, self.parser, self._start, self.proposal.engine, self._search
         cfg = eng.cfg
         check_arguments(cfg, self.proposals, self.rounds)
         L, p, size = H.lib(), H._p, ctypes.c_size_t
-        T, B, A, P, C = self.T, self.R, int(cfg.n_appearance), self.proposals, self.C
+        T, B, A, P = self.T, self.R, int(cfg.n_appearance), self.proposals
         (Hi, Wi), (hc, wc) = cfg.img_size, cfg.crop_size
-        G = hc * wc
-        mult, std = float(cfg.output_multiplier), float(cfg.output_std)
-        priors = (float(cfg.what_prior[0]), float(cfg.what_prior[1]), float(cfg.where_scale_prior[0]), float(cfg.where_scale_prior[1]),
-                  float(cfg.where_shift_prior[0]), float(cfg.where_shift_prior[1]))
-        norm = 1 if self.normalize_steps_prior else 0
         self.segments = []                                         # per round: {name: launch list}, the names of SEGMENTS
         for r in range(self.rounds):
-            if r == 0:
-                cur = dict(what=st["what"], where=st["where"], glimpse=st["glimpse"], score=par.score)
-                presence, n_in, src_in = p(par.presence), None, None
-            else:
-                cur = dict(what=self.out_what[r - 1], where=self.out_where[r - 1], glimpse=self.out_glimpse[r - 1],
-                           score=self.out_score[r - 1])
-                presence, n_in, src_in = None, p(self.num_objects_round[r - 1]), p(self.source_out[r - 1])
-            start_out = self.objective_rounds[0] if r == 0 else self._objective_start[r]
+            (what, where, glimpse, score), presence, n_in, src_in = search.current(r, st, par.score, par.presence, None)
             seg = {
                 "residual": [
                     (L.air_propose_residual,
-                     (p(cur["glimpse"]), p(cur["where"]), presence, n_in, p(st["obs"]), mult, self.clamp_hi, T, B, Hi, Wi, hc, wc,
-                      self.n_bands, p(ieng.obs), p(self.res_parts[r])), "air_propose_residual"),
+                     (p(glimpse), p(where), presence, n_in, p(st["obs"]), float(cfg.output_multiplier), self.clamp_hi, T, B, Hi, Wi, hc,
+                      wc, self.n_bands, p(ieng.obs), p(self.res_parts[r])), "air_propose_residual"),
                     (L.air_sum_leading, (p(self.res_parts[r]), p(self.residual_energy[r]), self.n_bands, size(B)), "air_sum_leading")],
                 "forward": list(ieng._plan_fwd),
                 "pool": [
                     (L.air_propose_pool,
-                     (p(cur["what"]), p(cur["where"]), p(cur["glimpse"]), p(cur["score"]), presence, n_in, src_in, p(ieng.what),
-                      p(ieng.where), p(ieng.gd.out[-1]), p(ieng.step_w), p(eng.prior_dev), r, T, P, B, A, G, p(self.pool_what[r]),
-                      p(self.pool_where[r]), p(self.pool_glimpse[r]), p(self.pool_score[r]), p(self.pool_presence[r]),
-                      p(self.pool_source[r]), p(self.pool_prior)), "air_propose_pool")],
-                "score": [
-                    (L.air_prune_score,
-                     (p(self.pool_glimpse[r]), p(self.pool_where[r]), p(self.pool_presence[r]), p(st["obs"]), mult, std, 1, C, B, Hi,
-                      Wi, hc, wc, self.n_bands, p(self.rec_sub[r])), "air_prune_score")],
-                "select": [
-                    (L.air_prune_select,
-                     (p(self.pool_what[r]), p(self.pool_where[r]), p(self.pool_glimpse[r]), p(self.pool_score[r]),
-                      p(self.pool_presence[r]), None, *priors, p(self.pool_prior), norm, 1, p(self.rec_sub[r]), self.n_bands, C, B, A,
-                      G, p(self.J_sub[r]), p(self.best_mask[r]), p(self.num_objects_round[r]), p(self.kept_pool[r]),
-                      p(self.objective_rounds[r + 1]), p(start_out), p(self.evidence[r]), p(self.out_what[r]), p(self.out_where[r]),
-                      p(self.out_glimpse[r]), p(self.out_score[r])), "air_prune_select")],
-                "source": [
-                    (L.air_propose_source, (p(self.pool_source[r]), p(self.kept_pool[r]), C, B, p(self.source_out[r])),
-                     "air_propose_source")]}
+                     (p(what), p(where), p(glimpse), p(score), presence, n_in, src_in, p(ieng.what), p(ieng.where),
+                      p(ieng.gd.out[-1]), p(ieng.step_w), p(eng.prior_dev), r, T, P, B, A, hc * wc, *search.pool_out(r)),
+                     "air_propose_pool")]}
+            seg.update(search.search(r, st["obs"], self.normalize_steps_prior))
             self.segments.append(seg)
-        self.readout = [
-            (L.air_parse_objects,
-             (p(st["presence_prob"]), p(self.num_objects_in), p(self.where), p(self.what), T, B, A, Hi, Wi, p(self.num_objects),
-              p(self.count_prob), p(self.presence), p(self.score), p(self.boxes), p(self.offsets), p(self.obj_image), p(self.obj_step),
-              p(self.obj_box), p(self.obj_score), p(self.obj_where), p(self.obj_what)), "air_parse_objects"),
-            (L.air_prune_relabel,
-             (p(self.score_src), p(self.kept_step), p(self.num_objects), p(self.offsets), T, B, p(self.score), p(self.obj_score),
-              p(self.obj_step)), "air_prune_relabel"),
-            (L.air_parse_render,
-             (p(self.glimpse), p(self.where), p(self.presence), p(st["obs"]), mult, std, self.mask_threshold, T, B, Hi, Wi, hc, wc,
-              self.n_bands, p(self.reconstruction), p(self.rec_parts), p(self.owner), p(self.area), None), "air_parse_render"),
-            (L.air_sum_leading, (p(self.rec_parts), p(self.rec), self.n_bands, size(B)), "air_sum_leading")]
+        self.readout = search.readout(self._ro, st["presence_prob"], st["obs"])
         self._plan = [e for seg in self.segments for name in SEGMENTS for e in seg[name]] + self.readout
-        self._built_for = self._plan_key()
         self._built_on = ieng._plan_fwd
 
-    def _plan_key(self):
-        """what of the engine's configuration the launch list holds by value"""
-        cfg = self.engine.cfg
-        return (cfg.output_multiplier, cfg.output_std, cfg.what_prior, cfg.where_scale_prior, cfg.where_shift_prior)
-
-    def _refresh_plan(self):
-        """rebuild (and re-capture) when a switch of the provider's engine moved without the proposer being told, or the proposal
-        engine rebuilt its forward plan"""
-        if self._plan_key() == self._built_for and self.proposal.engine._plan_fwd is self._built_on:
-            return False
-        had = self._graph is not None
-        self.release_graphs()
-        self._build_plan()
-        if had:
-            self.capture()
-        return True
+    def _plan_is_current(self):
+        """... and the proposal engine has not rebuilt its forward plan, a part of this one"""
+        return super()._plan_is_current() and self.proposal.engine._plan_fwd is self._built_on
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `parse()` call behind the bound provider's own (`parser` holds that provider's launch_count()); the
@@ -257,12 +190,9 @@ class ParseProposer:
                 "forward": n * len(self.proposal.engine._plan_fwd), "propose_pool": n, "prune_score": n, "prune_select": n,
                 "propose_source": n, "parse_objects": 1, "prune_relabel": 1, "parse_render": 1, "rec_sum": 1}
 
-    # ---- parameters ---------------------------------------------------------------------------------------------------------
+    # ---- parameters: the bound provider's AND the proposal engine's ----------------------------------------------------------------
     def load_from(self, train_engine):
-        """device-to-device copy of another engine's parameters into the bound provider's engine AND the proposal engine, its step
-        counter (the count prior pi depends on it) and run-time switches"""
-        from . import iw_eval
-        iw_eval.load_inner_engine(self, train_engine)
+        self.parser.load_from(train_engine)
         self.proposal.load_from(train_engine)
         self._refresh_plan()
 
@@ -284,18 +214,11 @@ class ParseProposer:
         changed = self.proposal.update_config(**changes) or changed
         return self._refresh_plan() or changed
 
-    # ---- graphs -------------------------------------------------------------------------------------------------------------
     def capture(self):
         """every launch behind the provider's own call -- all rounds and the read-out -- as ONE hipGraph (the provider's graphs are its
         own: `parser.capture()`)"""
-        self.release_graphs()
-        self.engine.synchronize()
         self.proposal.engine.synchronize()
-        self._graph = self.engine._capture_plans([self._plan])
-
-    def release_graphs(self):
-        destroy_graphs([self._graph])
-        self._graph = None
+        super().capture()
 
     # ---- the parse ----------------------------------------------------------------------------------------------------------
     def _order_engines(self, before: bool):
@@ -319,15 +242,10 @@ class ParseProposer:
           residual_energy [rounds, B], proposal_what / proposal_where / proposal_glimpse / proposal_score [rounds, P, B, .],
           num_objects_start [B] int32, objects_proposed_kept [B] int32 (objects of the result that came from a proposal);
         behind a ParseRefiner also refine_objective, refine_objective_start.  Same stream contract as the parsers."""
-        eng, par, st = self.engine, self.parser, self._start
+        eng = self.engine
         self._refresh_plan()
-        base = par.parse(obs, *args, **kwargs)
-        for k in ("what", "where", "glimpse", "presence_prob"):
-            if base[k].data_ptr() != st[k].data_ptr():
-                raise RuntimeError("the bound parser returned %r from another buffer than the proposer was built on" % k)
-        for k in ("presence", "score", "num_objects"):
-            if base[k].data_ptr() != getattr(par, k).data_ptr():
-                raise RuntimeError("the bound parser returned %r from another buffer than the proposer was built on" % k)
+        base = self.parser.parse(obs, *args, **kwargs)
+        self.check_parse(base, "proposer")
         self._order_engines(True)
         eng._replay_or_run(self._graph, self._plan)
         self._order_engines(False)
@@ -335,27 +253,6 @@ class ParseProposer:
         return self._result(base)
 
     def _result(self, base):
-        import torch
-        cfg, T, B, P = self.engine.cfg, self.T, self.R, self.proposals
-        out = dict(base)
-        if "best_iter" in base:                                    # behind a refiner: its objectives keep a name of their own
-            out["refine_objective"], out["refine_objective_start"] = base["objective"], base["objective_start"]
-        with torch.cuda.device(self.engine.device):
-            proposed = ((self.kept_step >= T) & (self.presence > 0.5)).sum(0).to(torch.int32)
-        out.update({"num_objects": self.num_objects, "count_prob": self.count_prob, "presence": self.presence, "score": self.score,
-                    "boxes": self.boxes, "what": self.what, "where": self.where,
-                    "glimpse": self.glimpse.view(T, B, *cfg.crop_size), "offsets": self.offsets,
-                    "obj_image": self.obj_image, "obj_step": self.obj_step, "obj_box": self.obj_box, "obj_score": self.obj_score,
-                    "obj_where": self.obj_where, "obj_what": self.obj_what, "reconstruction": self.reconstruction, "rec": self.rec,
-                    "owner": self.owner, "area": self.area, "objective": self.objective_rounds[-1],
-                    "objective_start": self.objective_rounds[0], "objective_subsets": self.J_sub[-1], "best_mask": self.best_mask[-1],
-                    "kept_step": self.kept_step, "evidence": self.evidence[-1], "num_objects_start": self.parser.num_objects,
-                    "objective_rounds": self.objective_rounds, "residual": self.residual, "residual_energy": self.residual_energy,
-                    "proposal_what": self.pool_what[:, T:], "proposal_where": self.pool_where[:, T:],
-                    "proposal_glimpse": self.pool_glimpse[:, T:].view(self.rounds, P, B, *cfg.crop_size),
-                    "proposal_score": self.pool_score[:, T:], "objects_proposed_kept": proposed})
-        out.pop("layers", None)                                    # (the provider's layers are the start parse's)
+        out = self._search.result(base, self.parser, self._ro, "objects_proposed_kept")
+        out.update({"residual": self.residual, "residual_energy": self.residual_energy})
         return out
-
-    def synchronize(self):
-        self.engine.synchronize()

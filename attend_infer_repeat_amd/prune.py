@@ -30,13 +30,12 @@ where_loc rows are gathered by a strided device copy on the engine stream BEFORE
 This closes "the count stays fixed" only for subsets of the T computed steps; proposing new objects from a residual image stays open.
 `reference_score` and `reference_select` restate the two kernels in numpy float64.
 """
-import ctypes
 import math
 from typing import Dict
 
 from . import iw_eval
 from .engine_config import EngineConfig
-from .launch import destroy_graphs
+from .stage import BoundStage, ReadOut, compacted_rows, prior_arguments
 
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 MAX_STEPS = 6                      # air_prune_score is instantiated for T = 1 .. 6: at most 64 subsets
@@ -213,30 +212,37 @@ def reference_select(what, where, glimpse, score, presence, where_loc, priors, p
             "what": gather(what), "where": gather(where), "glimpse": gather(glimpse), "score": gather(score)}
 
 
-def _start_buffers(provider):
-    """the device buffers the provider's `parse()` returns that the pruner reads -- the start rows, the presence chain, the per-step
-    score, the count, presence_prob, the B-row images -- and the where_loc rows that centre a shift prior given without `loc` (None: to
-    be gathered from particle 0 before every call).  refine._start_buffers, extended by the refiner itself as a provider."""
-    eng = provider.engine
-    if hasattr(provider, "best_what"):                              # refine.ParseRefiner
-        from .refine import _start_buffers as refiner_start
-        inner = refiner_start(provider.parser)
-        return {"what": provider.best_what, "where": provider.best_where, "glimpse": provider.best_glimpse,
-                "presence_prob": inner["presence_prob"], "obs": inner["obs"], "where_loc": provider.where_loc, "gather_loc": False}
-    if hasattr(provider, "what_sel"):                               # particle_parse.ParticleParser
-        return {"what": provider.what_sel, "where": provider.where_sel, "glimpse": provider.glimpse_sel,
-                "presence_prob": provider.presence_prob_sel, "obs": provider.obs, "where_loc": None, "gather_loc": True}
-    return {"what": eng.what, "where": eng.where, "glimpse": eng.gd.out[-1], "presence_prob": eng.presence_prob, "obs": eng.obs,
-            "where_loc": eng.where_loc, "gather_loc": False}
+def score_entry(H, cfg, glimpse, where, presence, obs, all_candidates, T, B, n_bands, rec_sub):
+    L, p = H.lib(), H._p
+    (Hi, Wi), (hc, wc) = cfg.img_size, cfg.crop_size
+    return (L.air_prune_score, (p(glimpse), p(where), p(presence), p(obs), float(cfg.output_multiplier), float(cfg.output_std),
+                                all_candidates, T, B, Hi, Wi, hc, wc, n_bands, p(rec_sub)), "air_prune_score")
 
 
-class ParsePruner:
+def select_entry(H, cfg, rows, score, presence, where_loc, prior, normalize_prior, all_candidates, rec_sub, n_bands, T, B, out):
+    """air_prune_select on the rows (what, where, glimpse); `out` = (J_sub, best_mask, num_objects, kept_step, objective,
+    objective_start, evidence, what, where, glimpse, score)"""
+    L, p = H.lib(), H._p
+    (hc, wc) = cfg.crop_size
+    return (L.air_prune_select,
+            (p(rows[0]), p(rows[1]), p(rows[2]), p(score), p(presence), p(where_loc), *prior_arguments(cfg), p(prior),
+             1 if normalize_prior else 0, all_candidates, p(rec_sub), n_bands, T, B, int(cfg.n_appearance), hc * wc,
+             *(p(t) for t in out)), "air_prune_select")
+
+
+class ParsePruner(BoundStage):
+    KIND = "subset"
+    ACCEPTS = ("scene", "particle", "refiner")
+    KEY_FIELDS = ("output_multiplier", "output_std", "what_prior", "where_scale_prior", "where_shift_prior")
+
     def __init__(self, parser, candidates: str = "present", normalize_steps_prior: bool = True):
+        self._start = self.bind(parser)
         cfg = parser.engine.cfg
         check_arguments(cfg, candidates)
         import torch
         from . import hip as H
         self.parser, self.engine = parser, parser.engine
+        self._bound = parser
         self.candidates, self.normalize_steps_prior = candidates, bool(normalize_steps_prior)
         self.T, self.R = parser.T, parser.R
         self.mask_threshold = parser.mask_threshold
@@ -245,7 +251,6 @@ class ParsePruner:
         (Hi, Wi), hw = cfg.img_size, cfg.n_crop
         NM = 1 << T
         self.n_bands = int(H.lib().air_canvas_unroll_bands(B, int(Hi)))
-        self._start = _start_buffers(parser)
         z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
         with torch.cuda.device(dev):
             self.where_loc = self._start["where_loc"] if self._start["where_loc"] is not None else z((T, B, 4))
@@ -256,108 +261,36 @@ class ParsePruner:
             self.objective, self.objective_start = z((B,), torch.float64), z((B,), torch.float64)
             self.evidence = z((T, B), torch.float64)
             self.what, self.where, self.glimpse, self.score_src = z((T, B, A)), z((T, B, 4)), z((T, B, hw)), z((T, B))
-            # the read-out of the selected subset (what the parsers keep)
-            self.num_objects, self.count_prob = z((B,), torch.int32), z((B,))
-            self.presence, self.score, self.boxes = z((T, B)), z((T, B)), z((T, B, 4))
-            self.offsets = z((B + 1,), torch.int32)
-            self.obj_image, self.obj_step = z((T * B,), torch.int32), z((T * B,), torch.int32)
-            self.obj_box, self.obj_score = z((T * B, 4)), z((T * B,))
-            self.obj_where, self.obj_what = z((T * B, 4)), z((T * B, A))
-            self.reconstruction = z((B, Hi, Wi))
-            self.rec_parts, self.rec = z((self.n_bands, B)), z((B,))
-            self.owner = z((B, Hi, Wi), torch.int8)
-            self.area = z((T, B), torch.int32)
-        self._graph = None
+        # the read-out of the selected subset (what the parsers keep)
+        self._ro = ReadOut(H, eng, T, B, A, cfg.img_size, self.n_bands, self.mask_threshold)
+        self._ro.alias(self)
         self._H = H
-        self._build_plan()
+        self._rebuild()
         eng.synchronize()
+
+    def rows(self):
+        """the provider protocol (stage.py): the compacted rows; presence_prob and the images are the start parse's"""
+        return compacted_rows(self, self._start["presence_prob"], self._start["obs"])
 
     # ---- the launches behind the provider's own call -------------------------------------------------------------------------
     def _build_plan(self):
-        H, eng, par, st = self._H, self.engine, self.parser, self._start
+        H, eng, par, st, ro = self._H, self.engine, self.parser, self._start, self._ro
         cfg = eng.cfg
         check_arguments(cfg, self.candidates)
-        L, p, size = H.lib(), H._p, ctypes.c_size_t
-        T, B, A = self.T, self.R, int(cfg.n_appearance)
-        (Hi, Wi), (hc, wc) = cfg.img_size, cfg.crop_size
-        mult, std = float(cfg.output_multiplier), float(cfg.output_std)
-        shift_loc = cfg.where_shift_prior[0]
-        priors = (float(cfg.what_prior[0]), float(cfg.what_prior[1]), float(cfg.where_scale_prior[0]), float(cfg.where_scale_prior[1]),
-                  float("nan") if shift_loc is None else float(shift_loc), float(cfg.where_shift_prior[1]))
-        allc = CANDIDATES[self.candidates]
+        T, B, allc = self.T, self.R, CANDIDATES[self.candidates]
         self._plan = [
-            (L.air_prune_score,
-             (p(st["glimpse"]), p(st["where"]), p(par.presence), p(st["obs"]), mult, std, allc, T, B, Hi, Wi, hc, wc, self.n_bands,
-              p(self.rec_sub)), "air_prune_score"),
-            (L.air_prune_select,
-             (p(st["what"]), p(st["where"]), p(st["glimpse"]), p(par.score), p(par.presence), p(self.where_loc), *priors,
-              p(eng.prior_dev), 1 if self.normalize_steps_prior else 0, allc, p(self.rec_sub), self.n_bands, T, B, A, hc * wc,
-              p(self.J_sub), p(self.best_mask), p(self.num_objects_in), p(self.kept_step), p(self.objective), p(self.objective_start),
-              p(self.evidence), p(self.what), p(self.where), p(self.glimpse), p(self.score_src)), "air_prune_select"),
-            (L.air_parse_objects,
-             (p(st["presence_prob"]), p(self.num_objects_in), p(self.where), p(self.what), T, B, A, Hi, Wi, p(self.num_objects),
-              p(self.count_prob), p(self.presence), p(self.score), p(self.boxes), p(self.offsets), p(self.obj_image), p(self.obj_step),
-              p(self.obj_box), p(self.obj_score), p(self.obj_where), p(self.obj_what)), "air_parse_objects"),
-            (L.air_prune_relabel,
-             (p(self.score_src), p(self.kept_step), p(self.num_objects), p(self.offsets), T, B, p(self.score), p(self.obj_score),
-              p(self.obj_step)), "air_prune_relabel"),
-            (L.air_parse_render,
-             (p(self.glimpse), p(self.where), p(self.presence), p(st["obs"]), mult, std, self.mask_threshold, T, B, Hi, Wi, hc, wc,
-              self.n_bands, p(self.reconstruction), p(self.rec_parts), p(self.owner), p(self.area), None), "air_parse_render"),
-            (L.air_sum_leading, (p(self.rec_parts), p(self.rec), self.n_bands, size(B)), "air_sum_leading")]
-        self._built_for = self._plan_key()
-
-    def _plan_key(self):
-        """what of the engine's configuration the launch list holds by value"""
-        cfg = self.engine.cfg
-        return (cfg.output_multiplier, cfg.output_std, cfg.what_prior, cfg.where_scale_prior, cfg.where_shift_prior)
-
-    def _refresh_plan(self):
-        """rebuild (and re-capture) when a switch of the provider's engine moved without the pruner being told -- the provider is also
-        used on its own, and its `update_config` does not know its pruners"""
-        if self._plan_key() == self._built_for:
-            return False
-        had = self._graph is not None
-        self.release_graphs()
-        self._build_plan()
-        if had:
-            self.capture()
-        return True
+            score_entry(H, cfg, st["glimpse"], st["where"], par.presence, st["obs"], allc, T, B, self.n_bands, self.rec_sub),
+            select_entry(H, cfg, (st["what"], st["where"], st["glimpse"]), par.score, par.presence, self.where_loc, eng.prior_dev,
+                         self.normalize_steps_prior, allc, self.rec_sub, self.n_bands, T, B,
+                         (self.J_sub, self.best_mask, self.num_objects_in, self.kept_step, self.objective, self.objective_start,
+                          self.evidence, self.what, self.where, self.glimpse, self.score_src)),
+            ro.objects(st["presence_prob"], self.num_objects_in, self.where, self.what),
+            ro.relabel("air_prune_relabel", self.score_src, self.kept_step)] + ro.tail(self.glimpse, self.where, st["obs"])
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `parse()` call behind the bound provider's own (`parser` holds that provider's launch_count())"""
         return {"parser": self.parser.launch_count(), "prune_score": 1, "prune_select": 1, "parse_objects": 1, "prune_relabel": 1,
                 "parse_render": 1, "rec_sum": 1}
-
-    # ---- parameters ---------------------------------------------------------------------------------------------------------
-    def load_from(self, train_engine):
-        """device-to-device copy of another engine's parameters into the bound provider's engine, its step counter (the count prior
-        pi depends on it) and run-time switches"""
-        iw_eval.load_inner_engine(self, train_engine)
-
-    def load_parameters(self, named):
-        self.parser.load_parameters(named)
-
-    def set_global_step(self, step: int):
-        self.parser.set_global_step(step)
-
-    def update_config(self, **changes) -> bool:
-        """run-time switches of the bound provider's engine (AIREngine.KNOBS): the provider re-captures its graphs, the pruner rebuilds
-        its launch list (output_multiplier is one of its arguments) and re-captures when one changed"""
-        changed = self.parser.update_config(**changes)
-        return self._refresh_plan() or changed
-
-    # ---- graphs -------------------------------------------------------------------------------------------------------------
-    def capture(self):
-        """every launch behind the provider's own call as ONE hipGraph (the provider's graphs are its own: `parser.capture()`; the
-        where_loc gather of the module docstring's exception stays a copy in front of the graph)"""
-        self.release_graphs()
-        self.engine.synchronize()
-        self._graph = self.engine._capture_plans([self._plan])
-
-    def release_graphs(self):
-        destroy_graphs([self._graph])
-        self._graph = None
 
     # ---- the parse ----------------------------------------------------------------------------------------------------------
     def parse(self, obs, *args, **kwargs):
@@ -372,35 +305,116 @@ class ParsePruner:
         behind a ParseRefiner also refine_objective, refine_objective_start: the refiner's objective / objective_start, whose own
         keys now hold the pruner's.
         Same stream contract as the parsers."""
-        import torch
-        eng, par, st = self.engine, self.parser, self._start
+        eng, par = self.engine, self.parser
         self._refresh_plan()
         base = par.parse(obs, *args, **kwargs)
-        for k in ("what", "where", "glimpse", "presence_prob"):
-            if base[k].data_ptr() != st[k].data_ptr():
-                raise RuntimeError("the bound parser returned %r from another buffer than the pruner was built on" % k)
-        for k in ("presence", "score", "num_objects"):
-            if base[k].data_ptr() != getattr(par, k).data_ptr():
-                raise RuntimeError("the bound parser returned %r from another buffer than the pruner was built on" % k)
-        if st["gather_loc"] and eng.cfg.where_shift_prior[0] is None:
-            with torch.cuda.stream(eng.stream):                    # particle 0's rows (the particles of an image share where_loc)
-                self.where_loc.copy_(eng.where_loc.view(self.T, self.R, -1, 4)[:, :, 0], non_blocking=True)
+        self.check_parse(base, "pruner")
+        self.gather_where_loc()
         eng._replay_or_run(self._graph, self._plan)
         eng.wait_for_engine()
-        cfg = eng.cfg
         out = dict(base)
-        if "best_iter" in base:                                    # behind a refiner: its objectives keep a name of their own
+        if par.KIND == "refiner":                                  # its objectives keep a name of their own
             out["refine_objective"], out["refine_objective_start"] = base["objective"], base["objective_start"]
-        out.update({"num_objects": self.num_objects, "count_prob": self.count_prob, "presence": self.presence, "score": self.score,
-                    "boxes": self.boxes, "what": self.what, "where": self.where,
-                    "glimpse": self.glimpse.view(self.T, self.R, *cfg.crop_size), "offsets": self.offsets,
-                    "obj_image": self.obj_image, "obj_step": self.obj_step, "obj_box": self.obj_box, "obj_score": self.obj_score,
-                    "obj_where": self.obj_where, "obj_what": self.obj_what, "reconstruction": self.reconstruction, "rec": self.rec,
-                    "owner": self.owner, "area": self.area, "objective": self.objective, "objective_start": self.objective_start,
+        out.update(self._ro.result(self.glimpse))
+        out.update({"what": self.what, "where": self.where, "objective": self.objective, "objective_start": self.objective_start,
                     "objective_subsets": self.J_sub, "best_mask": self.best_mask, "kept_step": self.kept_step,
                     "evidence": self.evidence, "num_objects_start": par.num_objects})
         out.pop("layers", None)                                    # (the provider's layers are the start parse's)
         return out
 
-    def synchronize(self):
-        self.engine.synchronize()
+
+class SubsetSearchRounds:
+    """The rounds of a subset search over a candidate pool of C = T + P rows (propose.py, temporal.py): every round's pool, joint table
+    and compacted rows, the `score` / `select` / `source` segments that follow the owner's own pool segment, and the last round's first
+    T rows as what the read-out takes.  The owner exposes every buffer under the same name (`alias`)."""
+
+    def __init__(self, H, engine, rounds, T, P, B, n_bands):
+        import torch
+        cfg, dev = engine.cfg, engine.device
+        self._H, self.engine, self.rounds, self.T, self.P, self.C, self.B, self.n_bands = H, engine, rounds, T, P, T + P, B, n_bands
+        Rn, C, A, hw, NM = rounds, T + P, int(cfg.n_appearance), cfg.n_crop, 1 << (T + P)
+        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+        with torch.cuda.device(dev):
+            self.pool_what, self.pool_where, self.pool_glimpse = z((Rn, C, B, A)), z((Rn, C, B, 4)), z((Rn, C, B, hw))
+            self.pool_score, self.pool_presence = z((Rn, C, B)), z((Rn, C, B))
+            # every round has its own pool, joint table and compacted rows; pool_prior is ONE buffer, not per-round state: every
+            # round's pool entry rewrites it with the same values (the count table followed by zeros)
+            self.pool_source, self.pool_prior = z((Rn, C, B), torch.int32), z((C + 1,), torch.float64)
+            self.rec_sub = z((Rn, n_bands, B, NM))
+            self.J_sub = torch.full((Rn, B, NM), float("nan"), dtype=torch.float64, device=dev)
+            self.best_mask, self.num_objects_round = z((Rn, B), torch.int32), z((Rn, B), torch.int32)
+            self.kept_pool = z((Rn, C, B), torch.int32)
+            self.objective_rounds, self._objective_start = z((Rn + 1, B), torch.float64), z((Rn, B), torch.float64)
+            self.evidence = z((Rn, C, B), torch.float64)
+            self.out_what, self.out_where, self.out_glimpse = z((Rn, C, B, A)), z((Rn, C, B, 4)), z((Rn, C, B, hw))
+            self.out_score, self.source_out = z((Rn, C, B)), z((Rn, C, B), torch.int32)
+        # the last round's first T rows: what the read-out takes (and the owner's rows as a provider)
+        self.what, self.where, self.glimpse = self.out_what[-1, :T], self.out_where[-1, :T], self.out_glimpse[-1, :T]
+        self.score_src, self.kept_step = self.out_score[-1, :T], self.source_out[-1, :T]
+        self.num_objects_in = self.num_objects_round[-1]
+        self.objective_start_rounds = [self.objective_rounds[0]] + [self._objective_start[r] for r in range(1, Rn)]
+
+    def alias(self, owner):
+        for k, v in vars(self).items():
+            if k not in ("_H", "engine", "rounds", "T", "P", "C", "B", "n_bands"):
+                setattr(owner, k, v)
+
+    def current(self, r, rows, score, presence, counts):
+        """what round r's pool entry reads: (what, where, glimpse, score) and, as the entry takes them, the presence chain, the counts
+        and the sources -- round 0: the provider's (a chain or counts), later: what round r - 1 left"""
+        p = self._H._p
+        if r == 0:
+            return (rows["what"], rows["where"], rows["glimpse"], score), p(presence), p(counts), None
+        return ((self.out_what[r - 1], self.out_where[r - 1], self.out_glimpse[r - 1], self.out_score[r - 1]), None,
+                p(self.num_objects_round[r - 1]), p(self.source_out[r - 1]))
+
+    def pool_out(self, r):
+        """round r's pool as the pool entries take it: what, where, glimpse, score, presence, source, prior"""
+        p = self._H._p
+        return tuple(p(t) for t in (self.pool_what[r], self.pool_where[r], self.pool_glimpse[r], self.pool_score[r],
+                                    self.pool_presence[r], self.pool_source[r], self.pool_prior))
+
+    def search(self, r, obs, normalize_prior):
+        """the segments behind round r's pool: air_prune_score / air_prune_select with T := C and every row a candidate, then
+        air_propose_source: source_out[j] = pool_source[kept_pool[j]]"""
+        H, cfg, C, B = self._H, self.engine.cfg, self.C, self.B
+        L, p = H.lib(), H._p
+        start_out = self.objective_rounds[0] if r == 0 else self._objective_start[r]
+        return {
+            "score": [score_entry(H, cfg, self.pool_glimpse[r], self.pool_where[r], self.pool_presence[r], obs, 1, C, B, self.n_bands,
+                                  self.rec_sub[r])],
+            "select": [select_entry(H, cfg, (self.pool_what[r], self.pool_where[r], self.pool_glimpse[r]), self.pool_score[r],
+                                    self.pool_presence[r], None, self.pool_prior, normalize_prior, 1, self.rec_sub[r], self.n_bands, C, B,
+                                    (self.J_sub[r], self.best_mask[r], self.num_objects_round[r], self.kept_pool[r],
+                                     self.objective_rounds[r + 1], start_out, self.evidence[r], self.out_what[r], self.out_where[r],
+                                     self.out_glimpse[r], self.out_score[r]))],
+            "source": [(L.air_propose_source, (p(self.pool_source[r]), p(self.kept_pool[r]), C, B, p(self.source_out[r])),
+                        "air_propose_source")]}
+
+    def readout(self, ro, presence_prob, obs):
+        """the pruner's read-out on the last round's first T rows, with the START parse's presence_prob"""
+        return [ro.objects(presence_prob, self.num_objects_in, self.where, self.what),
+                ro.relabel("air_prune_relabel", self.score_src, self.kept_step)] + ro.tail(self.glimpse, self.where, obs)
+
+    def result(self, base, provider, ro, kept_key):
+        """the provider's result with the keys of ParsePruner.parse describing the parse after the last round, the rounds' own keys,
+        and under `kept_key` the objects of the result that came from beyond the start rows"""
+        import torch
+        T, P, B, crop = self.T, self.P, self.B, self.engine.cfg.crop_size
+        out = dict(base)
+        if provider.KIND == "refiner":                             # its objectives keep a name of their own
+            out["refine_objective"], out["refine_objective_start"] = base["objective"], base["objective_start"]
+        if provider.KIND == "subset":                              # behind a pruner or proposer
+            out["provider_objective"], out["provider_objective_start"] = base["objective"], base["objective_start"]
+        with torch.cuda.device(self.engine.device):
+            kept = ((self.kept_step >= T) & (ro.presence > 0.5)).sum(0).to(torch.int32)
+        out.update(ro.result(self.glimpse))
+        out.update({"what": self.what, "where": self.where, "objective": self.objective_rounds[-1],
+                    "objective_start": self.objective_rounds[0], "objective_subsets": self.J_sub[-1], "best_mask": self.best_mask[-1],
+                    "kept_step": self.kept_step, "evidence": self.evidence[-1], "num_objects_start": provider.num_objects,
+                    "objective_rounds": self.objective_rounds, "proposal_what": self.pool_what[:, T:],
+                    "proposal_where": self.pool_where[:, T:],
+                    "proposal_glimpse": self.pool_glimpse[:, T:].view(self.rounds, P, B, *crop),
+                    "proposal_score": self.pool_score[:, T:], kept_key: kept})
+        out.pop("layers", None)                                    # (the provider's layers are the start parse's)
+        return out

@@ -40,7 +40,7 @@ from typing import Dict
 
 from . import iw_eval
 from .engine_config import EngineConfig
-from .launch import destroy_graphs
+from .stage import BoundStage, ReadOut, prior_arguments
 
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 DEFAULT_LR = (1e-1, 1e-2)     # (lr_what, lr_where): the largest mean objective gain at N = 16 in the sweep of profiles/refine.txt
@@ -142,25 +142,20 @@ def reference_step(what, where, glimpse, presence, rec_parts, dwhat, dwhere, whe
     return out
 
 
-def _start_buffers(parser):
-    """the device buffers a parser's `parse()` returns under what / where / glimpse / presence_prob, its B-row images, and the where_loc
-    rows that centre a shift prior given without `loc` (None: to be gathered from particle 0 before every call)"""
-    eng = parser.engine
-    if hasattr(parser, "what_sel"):                                 # particle_parse.ParticleParser
-        return {"what": parser.what_sel, "where": parser.where_sel, "glimpse": parser.glimpse_sel,
-                "presence_prob": parser.presence_prob_sel, "obs": parser.obs, "where_loc": None}
-    return {"what": eng.what, "where": eng.where, "glimpse": eng.gd.out[-1], "presence_prob": eng.presence_prob, "obs": eng.obs,
-            "where_loc": eng.where_loc}
+class ParseRefiner(BoundStage):
+    KIND = "refiner"
+    ACCEPTS = ("scene", "particle")
+    KEY_FIELDS = ("output_multiplier", "output_std", "guard_eps", "what_prior", "where_scale_prior", "where_shift_prior", "mfma_dtype")
 
-
-class ParseRefiner:
     def __init__(self, parser, steps: int, lr_what: float, lr_where: float, beta1: float = 0.9, beta2: float = 0.999,
                  eps: float = 1e-8):
+        self._start = self.bind(parser)
         cfg = parser.engine.cfg
         check_arguments(cfg, steps, lr_what, lr_where, beta1, beta2, eps)
         import torch
         from . import hip as H
         self.parser, self.engine = parser, parser.engine
+        self._bound = parser
         self.steps, self.lr_what, self.lr_where = int(steps), float(lr_what), float(lr_where)
         self.beta1, self.beta2, self.eps = float(beta1), float(beta2), float(eps)
         self.T, self.R = parser.T, parser.R
@@ -169,7 +164,6 @@ class ParseRefiner:
         T, B, A, N = self.T, self.R, int(cfg.n_appearance), self.steps
         (Hi, Wi), hw, P = cfg.img_size, cfg.n_crop, cfg.n_pix
         self.n_bands = int(H.lib().air_canvas_unroll_bands(B, int(Hi)))
-        self._start = _start_buffers(parser)
         z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
         with torch.cuda.device(dev):
             self.what, self.where = z((T, B, A)), z((T, B, 4))
@@ -187,21 +181,18 @@ class ParseRefiner:
             self.best_J, self.best_iter = z((B,), torch.float64), z((B,), torch.int32)
             self.best_what, self.best_where, self.best_glimpse = z((T, B, A)), z((T, B, 4)), z((T, B, hw))
             self.J_trace = z((N + 1, B))
-            # the read-out of the best rows (what the parsers keep)
-            self.num_objects, self.count_prob = z((B,), torch.int32), z((B,))
-            self.presence, self.score, self.boxes = z((T, B)), z((T, B)), z((T, B, 4))
-            self.offsets = z((B + 1,), torch.int32)
-            self.obj_image, self.obj_step = z((T * B,), torch.int32), z((T * B,), torch.int32)
-            self.obj_box, self.obj_score = z((T * B, 4)), z((T * B,))
-            self.obj_where, self.obj_what = z((T * B, 4)), z((T * B, A))
-            self.reconstruction = z((B, Hi, Wi))
-            self.rec_parts_out, self.rec = z((self.n_bands, B)), z((B,))
-            self.owner = z((B, Hi, Wi), torch.int8)
-            self.area = z((T, B), torch.int32)
-        self._graph = None
+        # the read-out of the best rows (what the parsers keep)
+        self._ro = ReadOut(H, eng, T, B, A, cfg.img_size, self.n_bands, self.mask_threshold)
+        self._ro.alias(self, rec_parts="rec_parts_out")
         self._H = H
-        self._build_plan()
+        self._rebuild()
         eng.synchronize()
+
+    def rows(self):
+        """the provider protocol (stage.py): the best rows; presence_prob and the images are the start parse's"""
+        st = self._start
+        return {"what": self.best_what, "where": self.best_where, "glimpse": self.best_glimpse, "presence_prob": st["presence_prob"],
+                "obs": st["obs"], "where_loc": self.where_loc, "gather_loc": False, "compacted": False}
 
     # ---- the launches behind the parser's own call ---------------------------------------------------------------------------
     def _build_plan(self):
@@ -213,9 +204,7 @@ class ParseRefiner:
         M, nl = T * B, len(self.shapes)
         (Hi, Wi), (hc, wc) = cfg.img_size, cfg.crop_size
         mult, std = float(cfg.output_multiplier), float(cfg.output_std)
-        shift_loc = cfg.where_shift_prior[0]
-        priors = (float(cfg.what_prior[0]), float(cfg.what_prior[1]), float(cfg.where_scale_prior[0]), float(cfg.where_scale_prior[1]),
-                  float("nan") if shift_loc is None else float(shift_loc), float(cfg.where_shift_prior[1]))
+        priors = prior_arguments(cfg)
         w, b = eng.gd.w, eng.gd.b
         plan = [(L.air_tile_rows, (p(st["what"]), p(self.what), 1, M * A), "air_tile_rows"),
                 (L.air_tile_rows, (p(st["where"]), p(self.where), 1, M * 4), "air_tile_rows"),
@@ -250,72 +239,14 @@ class ParseRefiner:
                           *(opt[2:] if update else (None,) * 4), self.lr_what, self.lr_where, self.beta1, self.beta2, self.eps,
                           c1, c2, float(cfg.guard_eps), i, 1 if update else 0, T, B, A, hc * wc, p(self.best_J), p(self.best_iter),
                           p(self.best_what), p(self.best_where), p(self.best_glimpse), p(self.J_trace)), "air_refine_step"))
-        plan += [
-            (L.air_parse_objects,
-             (p(st["presence_prob"]), p(par.num_objects), p(self.best_where), p(self.best_what), T, B, A, Hi, Wi, p(self.num_objects),
-              p(self.count_prob), p(self.presence), p(self.score), p(self.boxes), p(self.offsets), p(self.obj_image), p(self.obj_step),
-              p(self.obj_box), p(self.obj_score), p(self.obj_where), p(self.obj_what)), "air_parse_objects"),
-            (L.air_parse_render,
-             (p(self.best_glimpse), p(self.best_where), p(self.presence), p(st["obs"]), mult, std, self.mask_threshold, T, B, Hi, Wi,
-              hc, wc, self.n_bands, p(self.reconstruction), p(self.rec_parts_out), p(self.owner), p(self.area), None),
-             "air_parse_render"),
-            (L.air_sum_leading, (p(self.rec_parts_out), p(self.rec), self.n_bands, size(B)), "air_sum_leading")]
-        self._plan = plan
-        self._built_for = self._plan_key()
-
-    def _plan_key(self):
-        """what of the engine's configuration the launch list holds by value"""
-        cfg = self.engine.cfg
-        return (cfg.output_multiplier, cfg.output_std, cfg.guard_eps, cfg.what_prior, cfg.where_scale_prior, cfg.where_shift_prior,
-                cfg.mfma_dtype)
-
-    def _refresh_plan(self):
-        """rebuild (and re-capture) when a switch of the parser's engine moved without the refiner being told -- the parser is also
-        used on its own, and its `update_config` does not know its refiners"""
-        if self._plan_key() == self._built_for:
-            return False
-        had = self._graph is not None
-        self.release_graphs()
-        self._build_plan()
-        if had:
-            self.capture()
-        return True
+        self._plan = plan + [self._ro.objects(st["presence_prob"], par.num_objects, self.best_where, self.best_what)] + \
+            self._ro.tail(self.best_glimpse, self.best_where, st["obs"])
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `parse()` call behind the bound parser's own (`parser` holds that parser's launch_count())"""
         N, nl = self.steps, len(self.shapes)
         return {"parser": self.parser.launch_count(), "start": 3, "decoder_fwd": nl * (N + 1 if N > 0 else 0), "canvas_fwd": N + 1,
                 "canvas_bwd": N, "decoder_dx": nl * N, "refine_step": N + 1, "parse_objects": 1, "parse_render": 1, "rec_sum": 1}
-
-    # ---- parameters ---------------------------------------------------------------------------------------------------------
-    def load_from(self, train_engine):
-        """device-to-device copy of another engine's parameters into the bound parser's engine (the decoder weights are read from there),
-        its step counter and run-time switches"""
-        iw_eval.load_inner_engine(self, train_engine)
-
-    def load_parameters(self, named):
-        self.parser.load_parameters(named)
-
-    def set_global_step(self, step: int):
-        self.parser.set_global_step(step)
-
-    def update_config(self, **changes) -> bool:
-        """run-time switches of the bound parser's engine (AIREngine.KNOBS): the parser re-captures its graphs, the refiner rebuilds its
-        launch list (output_multiplier is one of its arguments) and re-captures when one changed"""
-        changed = self.parser.update_config(**changes)
-        return self._refresh_plan() or changed
-
-    # ---- graphs -------------------------------------------------------------------------------------------------------------
-    def capture(self):
-        """every launch behind the parser's own call as ONE hipGraph (the parser's graphs are its own: `parser.capture()`; the
-        where_loc gather of the module docstring's exception stays a copy in front of the graph)"""
-        self.release_graphs()
-        self.engine.synchronize()
-        self._graph = self.engine._capture_plans([self._plan])
-
-    def release_graphs(self):
-        destroy_graphs([self._graph])
-        self._graph = None
 
     # ---- the parse ----------------------------------------------------------------------------------------------------------
     def parse(self, obs, *args, **kwargs):
@@ -327,32 +258,17 @@ class ParseRefiner:
           objective_trace [steps+1, B] (the fp32 roundings of every iteration's J), grad_what [T, B, A], grad_where [T, B, 4]
           (d sum_b rec_b / d latents at iteration steps-1: without the prior terms; zeros when steps = 0).
         Same stream contract as the parsers."""
-        import torch
-        eng, par, st = self.engine, self.parser, self._start
+        eng = self.engine
         self._refresh_plan()
-        base = par.parse(obs, *args, **kwargs)
-        for k in ("what", "where", "glimpse", "presence_prob"):
-            if base[k].data_ptr() != st[k].data_ptr():
-                raise RuntimeError("the bound parser returned %r from another buffer than the refiner was built on" % k)
-        if base["presence"].data_ptr() != par.presence.data_ptr() or base["num_objects"].data_ptr() != par.num_objects.data_ptr():
-            raise RuntimeError("the bound parser returned presence / num_objects from another buffer than the refiner was built on")
-        if st["where_loc"] is None and eng.cfg.where_shift_prior[0] is None:
-            with torch.cuda.stream(eng.stream):                    # particle 0's rows (the particles of an image share where_loc)
-                self.where_loc.copy_(eng.where_loc.view(self.T, self.R, -1, 4)[:, :, 0], non_blocking=True)
+        base = self.parser.parse(obs, *args, **kwargs)
+        self.check_parse(base, "refiner")
+        self.gather_where_loc()
         eng._replay_or_run(self._graph, self._plan)
         eng.wait_for_engine()
-        cfg = eng.cfg
         out = dict(base)
-        out.update({"num_objects": self.num_objects, "count_prob": self.count_prob, "presence": self.presence, "score": self.score,
-                    "boxes": self.boxes, "what": self.best_what, "where": self.best_where,
-                    "glimpse": self.best_glimpse.view(self.T, self.R, *cfg.crop_size), "offsets": self.offsets,
-                    "obj_image": self.obj_image, "obj_step": self.obj_step, "obj_box": self.obj_box, "obj_score": self.obj_score,
-                    "obj_where": self.obj_where, "obj_what": self.obj_what, "reconstruction": self.reconstruction, "rec": self.rec,
-                    "owner": self.owner, "area": self.area, "objective": self.best_J, "objective_start": self.J_trace[0],
+        out.update(self._ro.result(self.best_glimpse))
+        out.update({"what": self.best_what, "where": self.best_where, "objective": self.best_J, "objective_start": self.J_trace[0],
                     "best_iter": self.best_iter, "objective_trace": self.J_trace, "grad_what": self.grad_what,
                     "grad_where": self.grad_where})
         out.pop("layers", None)                                    # (the parser's layers are the start parse's)
         return out
-
-    def synchronize(self):
-        self.engine.synchronize()

@@ -48,13 +48,12 @@ round, tiled and particle providers.  The defaults iou_novel = 0.3, proposals = 
 UNMEASURED on a trained model (profiles/temporal.txt says what was measured).  `reference_pool` restates the kernel in numpy float64;
 the search is prune.reference_score / prune.reference_select.
 """
-import ctypes
 import math
 from typing import Dict
 
 from . import prune
 from .engine_config import EngineConfig
-from .launch import destroy_graphs
+from .stage import BoundStage, ReadOut, compacted_rows
 from .tile import box_iou, scene_boxes
 
 MAX_POOL = prune.MAX_STEPS                                         # air_prune_score is instantiated up to 6 rows
@@ -168,31 +167,20 @@ def reference_pool(what, where, glimpse, score, n, prior, n_frames, img_size, pr
     return out
 
 
-def _bind(provider):
-    """the device buffers of the provider's `parse()` a round 0 reads: the rows, the per-step score, the chain or the counts, and the
-    start parse's presence_prob and images.  `checked`: the keys of the provider's result that must come from these very buffers."""
-    if hasattr(provider, "what_sel"):
-        raise ValueError("a ParticleParser is out of scope for temporal proposals (its rows are particles of an image, not images): "
-                         "bind a SceneParser, ParseRefiner, ParsePruner or ParseProposer")
-    if hasattr(provider, "kept_cand"):
-        raise ValueError("a TiledSceneParser is out of scope for temporal proposals (its rows are scene slots, up to 32, and the subset "
-                         "search stops at %d rows): bind a SceneParser, ParseRefiner, ParsePruner or ParseProposer" % MAX_POOL)
-    if hasattr(provider, "kept_step"):                              # prune.ParsePruner, propose.ParseProposer: their compacted rows
-        st = provider._start
-        return {"what": provider.what, "where": provider.where, "glimpse": provider.glimpse, "score": provider.score,
-                "presence": None, "counts": provider.num_objects, "presence_prob": st["presence_prob"], "obs": st["obs"],
-                "checked": {}}
-    st = prune._start_buffers(provider)
-    return {"what": st["what"], "where": st["where"], "glimpse": st["glimpse"], "score": provider.score,
-            "presence": provider.presence, "counts": None, "presence_prob": st["presence_prob"], "obs": st["obs"],
-            "checked": {k: st[k] for k in ("what", "where", "glimpse", "presence_prob")}}
+class TemporalProposer(BoundStage):
+    KIND = "subset"
+    ACCEPTS = ("scene", "refiner", "subset")
+    REFUSALS = {
+        "particle": "a ParticleParser is out of scope for temporal proposals (its rows are particles of an image, not images): "
+                    "bind a SceneParser, ParseRefiner, ParsePruner or ParseProposer",
+        "tiled": "a TiledSceneParser is out of scope for temporal proposals (its rows are scene slots, up to 32, and the subset "
+                 "search stops at %d rows): bind a SceneParser, ParseRefiner, ParsePruner or ParseProposer" % MAX_POOL}
+    KEY_FIELDS = prune.ParsePruner.KEY_FIELDS
 
-
-class TemporalProposer:
     def __init__(self, provider, n_frames, proposals: int = DEFAULTS["proposals"], rounds: int = DEFAULTS["rounds"],
                  iou_novel: float = DEFAULTS["iou_novel"], direction: str = DEFAULTS["direction"],
                  interpolate: bool = DEFAULTS["interpolate"], normalize_steps_prior: bool = True):
-        start = _bind(provider)
+        rows = self.bind(provider)
         cfg = provider.engine.cfg
         if direction not in DIRECTIONS:
             raise ValueError('direction must be "past" or "both", got %r' % (direction,))
@@ -200,6 +188,7 @@ class TemporalProposer:
         import torch
         from . import hip as H
         self.parser, self.engine = provider, provider.engine
+        self._bound = provider
         self.proposals, self.rounds, self.iou_novel = int(proposals), int(rounds), float(iou_novel)
         self.direction, self.interpolate = direction, bool(interpolate)
         self.normalize_steps_prior = bool(normalize_steps_prior)
@@ -207,127 +196,49 @@ class TemporalProposer:
         self.C = self.T + self.proposals
         self.mask_threshold = provider.mask_threshold
         eng, dev = self.engine, self.engine.device
-        T, B, A, P, C, Rn = self.T, self.R, int(cfg.n_appearance), self.proposals, self.C, self.rounds
-        (Hi, Wi), hw = cfg.img_size, cfg.n_crop
-        NM = 1 << C
-        self.n_bands = int(H.lib().air_canvas_unroll_bands(B, int(Hi)))
-        self._start = start
+        T, B, P, Rn = self.T, self.R, self.proposals, self.rounds
+        self.n_bands = int(H.lib().air_canvas_unroll_bands(B, int(cfg.img_size[0])))
+        # what round 0 reads: the provider's rows and per-step score, and its presence chain -- or, behind compacted rows, its counts
+        comp = rows["compacted"]
+        self._start = dict(rows, score=provider.score, presence=None if comp else provider.presence,
+                           counts=provider.num_objects if comp else None)
         z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
         with torch.cuda.device(dev):
-            self.pool_what, self.pool_where, self.pool_glimpse = z((Rn, C, B, A)), z((Rn, C, B, 4)), z((Rn, C, B, hw))
-            self.pool_score, self.pool_presence = z((Rn, C, B)), z((Rn, C, B))
-            # every round has its own pool, joint table and compacted rows; pool_prior is ONE buffer: every round's air_temporal_pool
-            # rewrites it with the same values (the count table followed by zeros)
-            self.pool_source, self.pool_prior = z((Rn, C, B), torch.int32), z((C + 1,), torch.float64)
             self.cand_state, self.proposals_taken = z((Rn, B, 2 * T), torch.int8), z((Rn, B), torch.int32)
             self.partner = z((Rn, P, B), torch.int32)
-            self.rec_sub = z((Rn, self.n_bands, B, NM))
-            self.J_sub = torch.full((Rn, B, NM), float("nan"), dtype=torch.float64, device=dev)
-            self.best_mask, self.num_objects_round = z((Rn, B), torch.int32), z((Rn, B), torch.int32)
-            self.kept_pool = z((Rn, C, B), torch.int32)
-            self.objective_rounds, self._objective_start = z((Rn + 1, B), torch.float64), z((Rn, B), torch.float64)
-            self.evidence = z((Rn, C, B), torch.float64)
-            self.out_what, self.out_where, self.out_glimpse = z((Rn, C, B, A)), z((Rn, C, B, 4)), z((Rn, C, B, hw))
-            self.out_score, self.source_out = z((Rn, C, B)), z((Rn, C, B), torch.int32)
-            # the read-out of the last round's first T rows (what the parsers keep)
-            self.what, self.where, self.glimpse = self.out_what[-1, :T], self.out_where[-1, :T], self.out_glimpse[-1, :T]
-            self.score_src, self.kept_step = self.out_score[-1, :T], self.source_out[-1, :T]
-            self.num_objects_in = self.num_objects_round[-1]
-            self.num_objects, self.count_prob = z((B,), torch.int32), z((B,))
-            self.presence, self.score, self.boxes = z((T, B)), z((T, B)), z((T, B, 4))
-            self.offsets = z((B + 1,), torch.int32)
-            self.obj_image, self.obj_step = z((T * B,), torch.int32), z((T * B,), torch.int32)
-            self.obj_box, self.obj_score = z((T * B, 4)), z((T * B,))
-            self.obj_where, self.obj_what = z((T * B, 4)), z((T * B, A))
-            self.reconstruction = z((B, Hi, Wi))
-            self.rec_parts, self.rec = z((self.n_bands, B)), z((B,))
-            self.owner = z((B, Hi, Wi), torch.int8)
-            self.area = z((T, B), torch.int32)
-        self.objective_start_rounds = [self.objective_rounds[0]] + [self._objective_start[r] for r in range(1, Rn)]
-        self._graph = None
+        self._search = prune.SubsetSearchRounds(H, eng, Rn, T, P, B, self.n_bands)
+        self._search.alias(self)
+        # the read-out of the last round's first T rows (what the parsers keep)
+        self._ro = ReadOut(H, eng, T, B, cfg.n_appearance, cfg.img_size, self.n_bands, self.mask_threshold)
+        self._ro.alias(self)
         self._H = H
-        self._build_plan()
+        self._rebuild()
         eng.synchronize()
+
+    def rows(self):
+        """the provider protocol (stage.py): the compacted rows; presence_prob and the images are the start parse's"""
+        return compacted_rows(self, self._start["presence_prob"], self._start["obs"])
 
     # ---- the launches behind the provider's own call -------------------------------------------------------------------------
     def _build_plan(self):
-        H, eng, st = self._H, self.engine, self._start
+        H, eng, st, search = self._H, self.engine, self._start, self._search
         cfg = eng.cfg
         check_arguments(cfg, self.F, self.R, self.proposals, self.rounds, self.iou_novel)
-        L, p, size = H.lib(), H._p, ctypes.c_size_t
-        T, B, A, P, C = self.T, self.R, int(cfg.n_appearance), self.proposals, self.C
+        L, p = H.lib(), H._p
+        T, A, P = self.T, int(cfg.n_appearance), self.proposals
         (Hi, Wi), (hc, wc) = cfg.img_size, cfg.crop_size
-        G = hc * wc
-        mult, std = float(cfg.output_multiplier), float(cfg.output_std)
-        priors = (float(cfg.what_prior[0]), float(cfg.what_prior[1]), float(cfg.where_scale_prior[0]), float(cfg.where_scale_prior[1]),
-                  float(cfg.where_shift_prior[0]), float(cfg.where_shift_prior[1]))
-        norm = 1 if self.normalize_steps_prior else 0
         both, mid = DIRECTIONS[self.direction], 1 if self.interpolate else 0
         self.segments = []                                         # per round: {name: launch list}, the names of SEGMENTS
         for r in range(self.rounds):
-            if r == 0:
-                cur = dict(what=st["what"], where=st["where"], glimpse=st["glimpse"], score=st["score"])
-                presence = None if st["presence"] is None else p(st["presence"])
-                n_in = None if st["counts"] is None else p(st["counts"])
-                src_in = None
-            else:
-                cur = dict(what=self.out_what[r - 1], where=self.out_where[r - 1], glimpse=self.out_glimpse[r - 1],
-                           score=self.out_score[r - 1])
-                presence, n_in, src_in = None, p(self.num_objects_round[r - 1]), p(self.source_out[r - 1])
-            start_out = self.objective_rounds[0] if r == 0 else self._objective_start[r]
-            seg = {
-                "pool": [
-                    (L.air_temporal_pool,
-                     (p(cur["what"]), p(cur["where"]), p(cur["glimpse"]), p(cur["score"]), presence, n_in, src_in, p(eng.prior_dev), r,
-                      T, P, self.S, self.F, A, G, Hi, Wi, self.iou_novel, both, mid, p(self.pool_what[r]), p(self.pool_where[r]),
-                      p(self.pool_glimpse[r]), p(self.pool_score[r]), p(self.pool_presence[r]), p(self.pool_source[r]),
-                      p(self.pool_prior), p(self.cand_state[r]), p(self.proposals_taken[r]), p(self.partner[r])),
-                     "air_temporal_pool")],
-                "score": [
-                    (L.air_prune_score,
-                     (p(self.pool_glimpse[r]), p(self.pool_where[r]), p(self.pool_presence[r]), p(st["obs"]), mult, std, 1, C, B, Hi,
-                      Wi, hc, wc, self.n_bands, p(self.rec_sub[r])), "air_prune_score")],
-                "select": [
-                    (L.air_prune_select,
-                     (p(self.pool_what[r]), p(self.pool_where[r]), p(self.pool_glimpse[r]), p(self.pool_score[r]),
-                      p(self.pool_presence[r]), None, *priors, p(self.pool_prior), norm, 1, p(self.rec_sub[r]), self.n_bands, C, B, A,
-                      G, p(self.J_sub[r]), p(self.best_mask[r]), p(self.num_objects_round[r]), p(self.kept_pool[r]),
-                      p(self.objective_rounds[r + 1]), p(start_out), p(self.evidence[r]), p(self.out_what[r]), p(self.out_where[r]),
-                      p(self.out_glimpse[r]), p(self.out_score[r])), "air_prune_select")],
-                "source": [
-                    (L.air_propose_source, (p(self.pool_source[r]), p(self.kept_pool[r]), C, B, p(self.source_out[r])),
-                     "air_propose_source")]}
+            (what, where, glimpse, score), presence, n_in, src_in = search.current(r, st, st["score"], st["presence"], st["counts"])
+            seg = {"pool": [(L.air_temporal_pool,
+                             (p(what), p(where), p(glimpse), p(score), presence, n_in, src_in, p(eng.prior_dev), r, T, P, self.S,
+                              self.F, A, hc * wc, Hi, Wi, self.iou_novel, both, mid, *search.pool_out(r), p(self.cand_state[r]),
+                              p(self.proposals_taken[r]), p(self.partner[r])), "air_temporal_pool")]}
+            seg.update(search.search(r, st["obs"], self.normalize_steps_prior))
             self.segments.append(seg)
-        self.readout = [
-            (L.air_parse_objects,
-             (p(st["presence_prob"]), p(self.num_objects_in), p(self.where), p(self.what), T, B, A, Hi, Wi, p(self.num_objects),
-              p(self.count_prob), p(self.presence), p(self.score), p(self.boxes), p(self.offsets), p(self.obj_image), p(self.obj_step),
-              p(self.obj_box), p(self.obj_score), p(self.obj_where), p(self.obj_what)), "air_parse_objects"),
-            (L.air_prune_relabel,
-             (p(self.score_src), p(self.kept_step), p(self.num_objects), p(self.offsets), T, B, p(self.score), p(self.obj_score),
-              p(self.obj_step)), "air_prune_relabel"),
-            (L.air_parse_render,
-             (p(self.glimpse), p(self.where), p(self.presence), p(st["obs"]), mult, std, self.mask_threshold, T, B, Hi, Wi, hc, wc,
-              self.n_bands, p(self.reconstruction), p(self.rec_parts), p(self.owner), p(self.area), None), "air_parse_render"),
-            (L.air_sum_leading, (p(self.rec_parts), p(self.rec), self.n_bands, size(B)), "air_sum_leading")]
+        self.readout = search.readout(self._ro, st["presence_prob"], st["obs"])
         self._plan = [e for seg in self.segments for name in SEGMENTS for e in seg[name]] + self.readout
-        self._built_for = self._plan_key()
-
-    def _plan_key(self):
-        """what of the engine's configuration the launch list holds by value"""
-        cfg = self.engine.cfg
-        return (cfg.output_multiplier, cfg.output_std, cfg.what_prior, cfg.where_scale_prior, cfg.where_shift_prior)
-
-    def _refresh_plan(self):
-        """rebuild (and re-capture) when a switch of the provider's engine moved without the proposer being told"""
-        if self._plan_key() == self._built_for:
-            return False
-        had = self._graph is not None
-        self.release_graphs()
-        self._build_plan()
-        if had:
-            self.capture()
-        return True
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `parse()` call behind the bound provider's own (`parser` holds that provider's launch_count()); the
@@ -336,48 +247,7 @@ class TemporalProposer:
         return {"parser": self.parser.launch_count(), "temporal_pool": n, "prune_score": n, "prune_select": n, "propose_source": n,
                 "parse_objects": 1, "prune_relabel": 1, "parse_render": 1, "rec_sum": 1}
 
-    # ---- parameters ---------------------------------------------------------------------------------------------------------
-    def load_from(self, train_engine):
-        """the bound provider takes another engine's parameters, step counter and run-time switches (its own `load_from`)"""
-        self.parser.load_from(train_engine)
-        self._refresh_plan()
-
-    def load_parameters(self, named):
-        self.parser.load_parameters(named)
-
-    def set_global_step(self, step: int):
-        self.parser.set_global_step(step)
-
-    def update_config(self, **changes) -> bool:
-        """run-time switches of the bound provider's engine (AIREngine.KNOBS): the provider re-captures its graphs, the proposer
-        rebuilds its launch list (output_multiplier is one of its arguments) and re-captures when one changed"""
-        if self._graph is not None:
-            self.engine.synchronize()
-        changed = self.parser.update_config(**changes)
-        return self._refresh_plan() or changed
-
-    # ---- graphs -------------------------------------------------------------------------------------------------------------
-    def capture(self):
-        """every launch behind the provider's own call -- all rounds and the read-out -- as ONE hipGraph (the provider's graphs are its
-        own: `parser.capture()`)"""
-        self.release_graphs()
-        self.engine.synchronize()
-        self._graph = self.engine._capture_plans([self._plan])
-
-    def release_graphs(self):
-        destroy_graphs([self._graph])
-        self._graph = None
-
     # ---- the parse ----------------------------------------------------------------------------------------------------------
-    def run_segments(self, round: int, *names):
-        """issue the named segments of one round eagerly, in the order given, on the engine's stream (tests and probes run the pieces
-        this way)"""
-        eng = self.engine
-        eng.wait_for_caller()
-        for name in names:
-            eng._run(self.segments[round][name], eng._sp())
-        eng.wait_for_engine()
-
     def parse(self, obs, *args, **kwargs):
         """obs: the frames as the provider's R = S F rows, row s F + f (further arguments go to the provider's `parse()` unchanged),
         then the rounds and the read-out.  Returns device tensors that the NEXT call overwrites: every key of the provider's result and
@@ -393,44 +263,15 @@ class TemporalProposer:
           rows included), objects_temporal_kept [R] int32 (objects of the result that came from a neighbour frame);
         behind a ParseRefiner also refine_objective, refine_objective_start; behind a ParsePruner or ParseProposer that provider's
         objective / objective_start as provider_objective / provider_objective_start.  Same stream contract as the parsers."""
-        eng, par, st = self.engine, self.parser, self._start
+        eng = self.engine
         self._refresh_plan()
-        base = par.parse(obs, *args, **kwargs)
-        for k, buf in st["checked"].items():
-            if base[k].data_ptr() != buf.data_ptr():
-                raise RuntimeError("the bound parser returned %r from another buffer than the proposer was built on" % k)
-        for k in ("what", "where", "score", "num_objects") if not st["checked"] else ("presence", "score", "num_objects"):
-            if base[k].data_ptr() != getattr(par, k).data_ptr():
-                raise RuntimeError("the bound parser returned %r from another buffer than the proposer was built on" % k)
+        base = self.parser.parse(obs, *args, **kwargs)
+        self.check_parse(base, "proposer")
         eng._replay_or_run(self._graph, self._plan)
         eng.wait_for_engine()
         return self._result(base)
 
     def _result(self, base):
-        import torch
-        cfg, T, B, P = self.engine.cfg, self.T, self.R, self.proposals
-        out = dict(base)
-        if "best_iter" in base and "kept_step" not in base:        # behind a refiner: its objectives keep a name of their own
-            out["refine_objective"], out["refine_objective_start"] = base["objective"], base["objective_start"]
-        if "kept_step" in base:                                    # behind a pruner or proposer
-            out["provider_objective"], out["provider_objective_start"] = base["objective"], base["objective_start"]
-        with torch.cuda.device(self.engine.device):
-            kept = ((self.kept_step >= T) & (self.presence > 0.5)).sum(0).to(torch.int32)
-        out.update({"num_objects": self.num_objects, "count_prob": self.count_prob, "presence": self.presence, "score": self.score,
-                    "boxes": self.boxes, "what": self.what, "where": self.where,
-                    "glimpse": self.glimpse.view(T, B, *cfg.crop_size), "offsets": self.offsets,
-                    "obj_image": self.obj_image, "obj_step": self.obj_step, "obj_box": self.obj_box, "obj_score": self.obj_score,
-                    "obj_where": self.obj_where, "obj_what": self.obj_what, "reconstruction": self.reconstruction, "rec": self.rec,
-                    "owner": self.owner, "area": self.area, "objective": self.objective_rounds[-1],
-                    "objective_start": self.objective_rounds[0], "objective_subsets": self.J_sub[-1], "best_mask": self.best_mask[-1],
-                    "kept_step": self.kept_step, "evidence": self.evidence[-1], "num_objects_start": self.parser.num_objects,
-                    "objective_rounds": self.objective_rounds, "cand_state": self.cand_state,
-                    "proposals_taken": self.proposals_taken, "partner": self.partner,
-                    "proposal_what": self.pool_what[:, T:], "proposal_where": self.pool_where[:, T:],
-                    "proposal_glimpse": self.pool_glimpse[:, T:].view(self.rounds, P, B, *cfg.crop_size),
-                    "proposal_score": self.pool_score[:, T:], "objects_temporal_kept": kept})
-        out.pop("layers", None)                                    # (the provider's layers are the start parse's)
+        out = self._search.result(base, self.parser, self._ro, "objects_temporal_kept")
+        out.update({"cand_state": self.cand_state, "proposals_taken": self.proposals_taken, "partner": self.partner})
         return out
-
-    def synchronize(self):
-        self.engine.synchronize()

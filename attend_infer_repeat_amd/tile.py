@@ -33,12 +33,11 @@ engine stream, its own launch list of libair_hip.so entries (include/air_hip.h),
 Known waste: the provider copies the windows into its engine's `obs` (one device-to-device copy of the gathered bytes).
 `reference_gather`, `reference_lift` and `reference_merge` restate the definitions in numpy float64.
 """
-import ctypes
 import math
 from collections import OrderedDict
 from typing import Dict
 
-from .launch import destroy_graphs
+from .stage import BoundStage, ReadOut, compacted_rows
 
 MAX_SLOTS = 32                     # PARSE_MAXT / SCORE_MAXT; the owner map is int8
 MAX_CANDIDATES = 256               # air_tile_merge: one thread per candidate
@@ -241,20 +240,19 @@ def reference_merge(what, where, glimpse, score, num_objects, scene_size, img_si
 
 
 def _provider_rows(provider):
-    """the device buffers of the provider's `parse()` that the merge reads: what [T, R, A], where [T, R, 4], glimpse [T, R, G]"""
-    if hasattr(provider, "what_sel"):
-        raise ValueError("a ParticleParser is out of scope for tiling (its rows are particles of an image, not images): bind a "
-                         "SceneParser, ParseRefiner, ParsePruner or ParseProposer")
-    if hasattr(provider, "kept_step"):                              # prune.ParsePruner, propose.ParseProposer: their own compacted rows
-        return {"what": provider.what, "where": provider.where, "glimpse": provider.glimpse}
-    from .prune import _start_buffers
-    st = _start_buffers(provider)
-    return {k: st[k] for k in ("what", "where", "glimpse")}
+    """the device buffers of the provider's `parse()` that the merge reads (its rows()), or the refusal"""
+    return TiledSceneParser.bind(provider)
 
 
-class TiledSceneParser:
+class TiledSceneParser(BoundStage):
+    KIND = "tiled"
+    ACCEPTS = ("scene", "refiner", "subset")
+    REFUSALS = {"particle": "a ParticleParser is out of scope for tiling (its rows are particles of an image, not images): bind a "
+                            "SceneParser, ParseRefiner, ParsePruner or ParseProposer"}
+    KEY_FIELDS = ("output_multiplier", "output_std")
+
     def __init__(self, provider, scene_size, stride=None, iou_merge: float = 0.5):
-        rows = _provider_rows(provider)
+        rows = self.bind(provider)
         cfg = provider.engine.cfg
         (Hs, Ws), (sy, sx), (ny, nx) = check_arguments(cfg, scene_size, stride, iou_merge)
         Nw = ny * nx
@@ -265,6 +263,7 @@ class TiledSceneParser:
         import torch
         from . import hip as H
         self.provider, self.engine = provider, provider.engine
+        self._bound = provider
         self.scene_size, self.stride, self.grid, self.iou_merge = (Hs, Ws), (sy, sx), (ny, nx), float(iou_merge)
         self.n_windows, self.window_T = Nw, int(provider.T)
         self.T, self.R = min(Nw * self.window_T, MAX_SLOTS), provider.R // Nw
@@ -282,31 +281,28 @@ class TiledSceneParser:
             self.num_objects_in = z((S,), torch.int32)
             self.cand_state, self.dup_of = z((S, Nc), torch.int8), torch.full((S, Nc), -1, dtype=torch.int32, device=dev)
             self.merge_counts = z((S, 6), torch.int32)
-            # the read-out of the scene (what the parsers keep)
-            self.num_objects, self.count_prob = z((S,), torch.int32), z((S,))
-            self.presence, self.score, self.boxes = z((C, S)), z((C, S)), z((C, S, 4))
-            self.offsets = z((S + 1,), torch.int32)
-            self.obj_image, self.obj_step = z((C * S,), torch.int32), z((C * S,), torch.int32)
-            self.obj_box, self.obj_score = z((C * S, 4)), z((C * S,))
-            self.obj_where, self.obj_what = z((C * S, 4)), z((C * S, A))
-            self.reconstruction = z((S, Hs, Ws))
-            self.rec_parts, self.rec = z((self.n_bands, S)), z((S,))
-            self.owner = z((S, Hs, Ws), torch.int8)
-            self.area = z((C, S), torch.int32)
-        self._graph = None
+        # the read-out of the scene (what the parsers keep)
+        self._ro = ReadOut(H, eng, C, S, A, (Hs, Ws), self.n_bands, self.mask_threshold)
+        self._ro.alias(self)
         self._H = H
-        self._build_plan()
-        self._check_render()
+        self._rebuild()
+        self.check_render(self.segments["render"][0],
+                          "air_parse_render declines a %d x %d scene with %d slots: its LDS carve (the slots' bordered glimpses and "
+                          "the axis tables of a band) passes the 160 KiB of a workgroup; use fewer windows or a smaller scene"
+                          % (self.scene_size + (self.T,)))
         eng.synchronize()
+
+    def rows(self):
+        """the provider protocol (stage.py): the merged, lifted rows of the scenes; a scene has no count posterior"""
+        return compacted_rows(self, None, self.scenes)
 
     # ---- the launches around the provider's own call -------------------------------------------------------------------------
     def _build_plan(self):
-        H, eng, par, rows = self._H, self.engine, self.provider, self._rows
+        H, eng, par, rows, ro = self._H, self.engine, self.provider, self._rows, self._ro
         cfg = eng.cfg
-        L, p, size = H.lib(), H._p, ctypes.c_size_t
-        C, S, A, T = self.T, self.R, int(cfg.n_appearance), self.window_T
+        L, p = H.lib(), H._p
+        S, A, T = self.R, int(cfg.n_appearance), self.window_T
         (Hi, Wi), (hc, wc), (Hs, Ws), (sy, sx) = cfg.img_size, cfg.crop_size, self.scene_size, self.stride
-        mult, std = float(cfg.output_multiplier), float(cfg.output_std)
         self.segments = OrderedDict([
             ("gather", [(L.air_tile_gather, (p(self.scenes), S, Hs, Ws, Hi, Wi, sy, sx, p(self.windows)), "air_tile_gather")]),
             ("merge", [(L.air_tile_merge,
@@ -314,85 +310,16 @@ class TiledSceneParser:
                          Hs, Ws, Hi, Wi, sy, sx, self.iou_merge, p(self.what), p(self.where), p(self.glimpse), p(self.score_src),
                          p(self.kept_cand), p(self.num_objects_in), p(self.cand_state), p(self.dup_of), p(self.merge_counts)),
                         "air_tile_merge")]),
-            ("objects", [(L.air_parse_objects,
-                          (None, p(self.num_objects_in), p(self.where), p(self.what), C, S, A, Hs, Ws, p(self.num_objects),
-                           p(self.count_prob), p(self.presence), p(self.score), p(self.boxes), p(self.offsets), p(self.obj_image),
-                           p(self.obj_step), p(self.obj_box), p(self.obj_score), p(self.obj_where), p(self.obj_what)),
-                          "air_parse_objects")]),
-            ("relabel", [(L.air_tile_relabel,
-                          (p(self.score_src), p(self.kept_cand), p(self.num_objects), p(self.offsets), C, S, p(self.score),
-                           p(self.obj_score), p(self.obj_step)), "air_tile_relabel")]),
-            ("render", [(L.air_parse_render,
-                         (p(self.glimpse), p(self.where), p(self.presence), p(self.scenes), mult, std, self.mask_threshold, C, S, Hs,
-                          Ws, hc, wc, self.n_bands, p(self.reconstruction), p(self.rec_parts), p(self.owner), p(self.area), None),
-                         "air_parse_render")]),
-            ("rec_sum", [(L.air_sum_leading, (p(self.rec_parts), p(self.rec), self.n_bands, size(S)), "air_sum_leading")])])
+            ("objects", [ro.objects(None, self.num_objects_in, self.where, self.what)]),
+            ("relabel", [ro.relabel("air_tile_relabel", self.score_src, self.kept_cand)]),
+            ("render", [ro.render(self.glimpse, self.where, self.scenes)]),
+            ("rec_sum", [ro.rec_sum()])])
         self._plan = [e for name, seg in self.segments.items() if name != "gather" for e in seg]
-        self._built_for = self._plan_key()
-
-    def _check_render(self):
-        """air_parse_render stages the C bordered glimpses and the axis tables of a band in LDS: refuse here, by name, a scene it
-        declines (its first launch on the still empty rows decides)"""
-        fn, args, name = self.segments["render"][0]
-        st = fn(*args, self.engine._sp())
-        if st == -5:
-            raise ValueError("air_parse_render declines a %d x %d scene with %d slots: its LDS carve (the slots' bordered glimpses and "
-                             "the axis tables of a band) passes the 160 KiB of a workgroup; use fewer windows or a smaller scene"
-                             % (self.scene_size + (self.T,)))
-        from . import _lib
-        _lib.check(st, name)
-
-    def _plan_key(self):
-        """what of the engine's configuration the launch list holds by value"""
-        cfg = self.engine.cfg
-        return (cfg.output_multiplier, cfg.output_std)
-
-    def _refresh_plan(self):
-        """rebuild (and re-capture) when a switch of the provider's engine moved without this object being told"""
-        if self._plan_key() == self._built_for:
-            return False
-        had = self._graph is not None
-        self.release_graphs()
-        self._build_plan()
-        if had:
-            self.capture()
-        return True
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `parse()` call around the bound provider's own (`parser` holds that provider's launch_count())"""
         return {"tile_gather": 1, "parser": self.provider.launch_count(), "tile_merge": 1, "parse_objects": 1, "tile_relabel": 1,
                 "parse_render": 1, "rec_sum": 1}
-
-    # ---- parameters ---------------------------------------------------------------------------------------------------------
-    def load_from(self, train_engine):
-        self.provider.load_from(train_engine)
-        self._refresh_plan()
-
-    def load_parameters(self, named):
-        self.provider.load_parameters(named)
-
-    def set_global_step(self, step: int):
-        self.provider.set_global_step(step)
-
-    def update_config(self, **changes) -> bool:
-        """run-time switches of the bound provider's engine (AIREngine.KNOBS): the provider re-captures its graphs, this object rebuilds
-        its launch list (output_multiplier and output_std are among its arguments) and re-captures when one changed"""
-        if self._graph is not None:
-            self.engine.synchronize()
-        changed = self.provider.update_config(**changes)
-        return self._refresh_plan() or changed
-
-    # ---- graphs -------------------------------------------------------------------------------------------------------------
-    def capture(self):
-        """every launch behind the provider's own call as ONE hipGraph (the provider's graphs are its own: `provider.capture()`; the
-        gather in front of the provider stays a launch of its own)"""
-        self.release_graphs()
-        self.engine.synchronize()
-        self._graph = self.engine._capture_plans([self._plan])
-
-    def release_graphs(self):
-        destroy_graphs([self._graph])
-        self._graph = None
 
     # ---- the parse ----------------------------------------------------------------------------------------------------------
     def stage(self, scenes):
@@ -408,25 +335,13 @@ class TiledSceneParser:
         if scenes.is_cuda:
             scenes.record_stream(eng.stream)
 
-    def run_segments(self, *names):
-        """issue the named segments eagerly, in the order given, on the engine's stream (tests and probes run the pieces this way)"""
-        eng = self.engine
-        eng.wait_for_caller()
-        for name in names:
-            eng._run(self.segments[name], eng._sp())
-        eng.wait_for_engine()
-
     def run_provider(self, *args, **kwargs):
         """the bound provider's `parse()` on the gathered windows (further arguments go to it unchanged)"""
         par, rows = self.provider, self._rows
         (Hi, Wi) = self.engine.cfg.img_size
         base = par.parse(self.windows.view(-1, Hi, Wi), *args, **kwargs)
-        for k in ("what", "where", "glimpse"):
-            if base[k].data_ptr() != rows[k].data_ptr():
-                raise RuntimeError("the bound provider returned %r from another buffer than the tiled parser was built on" % k)
-        for k in ("score", "num_objects"):
-            if base[k].data_ptr() != getattr(par, k).data_ptr():
-                raise RuntimeError("the bound provider returned %r from another buffer than the tiled parser was built on" % k)
+        self.check_same_buffers(base, dict({k: rows[k] for k in ("what", "where", "glimpse")}, score=par.score,
+                                           num_objects=par.num_objects), "tiled parser", bound="provider")
         return base
 
     def parse(self, scenes, *args, **kwargs):
@@ -448,17 +363,12 @@ class TiledSceneParser:
         return self.result(base)
 
     def result(self, base=None):
-        cfg, C, S, Nw = self.engine.cfg, self.T, self.R, self.n_windows
-        out = {"num_objects": self.num_objects, "presence": self.presence, "score": self.score, "boxes": self.boxes, "what": self.what,
-               "where": self.where, "glimpse": self.glimpse.view(C, S, *cfg.crop_size), "offsets": self.offsets,
-               "obj_image": self.obj_image, "obj_step": self.obj_step, "obj_box": self.obj_box, "obj_score": self.obj_score,
-               "obj_where": self.obj_where, "obj_what": self.obj_what, "reconstruction": self.reconstruction, "rec": self.rec,
-               "owner": self.owner, "area": self.area, "kept_cand": self.kept_cand, "cand_state": self.cand_state,
-               "dup_of": self.dup_of, "merge_counts": self.merge_counts, "windows": self.windows.view(S * Nw, *cfg.img_size)}
+        cfg, S, Nw = self.engine.cfg, self.R, self.n_windows
+        out = self._ro.result(self.glimpse)
+        del out["count_prob"]                                      # (there is no count posterior of a scene)
+        out.update({"what": self.what, "where": self.where, "kept_cand": self.kept_cand, "cand_state": self.cand_state,
+                    "dup_of": self.dup_of, "merge_counts": self.merge_counts, "windows": self.windows.view(S * Nw, *cfg.img_size)})
         if base is not None:
             out["window_num_objects"] = base["num_objects"].view(S, Nw)
             out["window_count_prob"] = base["count_prob"].view(S, Nw)
         return out
-
-    def synchronize(self):
-        self.engine.synchronize()

@@ -47,20 +47,20 @@ whatever F is -- the frames are walked inside air_track_associate:
   air_track_associate   the rule above;
   air_track_owner       track_owner[r, y, x] (int16) = the track id of the step that owns the pixel, -1 for background.
 
-A particle_parse.ParticleParser is refused, with tile._provider_rows' wording: its `parse()` takes no counts and its rows are particles
+A particle_parse.ParticleParser is refused, with tile.TiledSceneParser's wording: its `parse()` takes no counts and its rows are particles
 of an image, and the buffers the tracker reads next to the `what` rows (`boxes`, `score`, `num_objects`, `owner`) are the selected
 particle's only behind a pruner or proposer -- bind one of those, they bind as every other provider.
 
 The defaults of iou_gate, appearance_weight, birth_score and max_age are provisional: UNMEASURED on a trained model (profiles/track.txt
 says what was measured).  `reference_associate` and `reference_score` restate the two rules in numpy float64.
 """
-import ctypes
 import math
 from collections import OrderedDict
 from typing import Dict
 
 from .launch import destroy_graphs
-from .tile import box_iou
+from .stage import BoundStage
+from .tile import TiledSceneParser, box_iou
 
 MAX_SLOTS = 32                     # PARSE_MAXT / SCORE_MAXT: objects per frame and live tracks per sequence
 MAX_GT = 8                         # SCORE_MAXG
@@ -272,27 +272,118 @@ def mot_summary(counts, sum_iou) -> Dict[str, float]:
             "false_positives": c["fp"], "misses": c["misses"], "gt": c["gt"], "matches": c["matches"], "gt_objects": c["gt_objects"]}
 
 
-def _provider_what(provider):
-    """the `what` rows [T, R, A] of the provider's `parse()` (tile._provider_rows; a TiledSceneParser keeps its compacted rows itself)"""
-    from .tile import _provider_rows
-    if hasattr(provider, "kept_cand") and not hasattr(provider, "what_sel"):       # tile.TiledSceneParser
-        return provider.what
-    return _provider_rows(provider)["what"]
+class IdentityScores:
+    """The identity metric of a stage (the tracker on its own table, the smoother on its two): the air_track_score launch of every
+    key used so far with its buffers and graph (`entries`, at most four: a sweep over tau must not pile up buffers and graphs), the
+    staging copy of the ground truth, and the running totals on the device."""
+
+    def __init__(self, stage, S):
+        import torch
+        self.stage, self.engine, self.S, self.entries = stage, stage.engine, int(S), {}
+        dev = self.engine.device
+        with torch.cuda.device(dev):
+            self.totals_i = torch.zeros((8,), dtype=torch.int64, device=dev)
+            self.totals_f = torch.zeros((1,), dtype=torch.float64, device=dev)
+
+    def entry(self, key, G, tau, T, n_frames, boxes, counts, ids):
+        """the air_track_score launch on a table of T rows by S * n_frames columns (boxes, counts, ids) with its buffers -- gt_boxes,
+        seq_counts, seq_iou, gt_match -- kept under key + (G, tau); captured when the stage holds a graph"""
+        import torch
+        eng, S, N = self.engine, self.S, self.S * n_frames
+        key = key + (int(G), float(tau))
+        G, tau_f = key[-2:]
+        entry = self.entries.get(key)
+        if entry is None:
+            if not 1 <= G <= MAX_GT:
+                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+            if not 0.0 <= tau_f <= 1.0:
+                raise ValueError("tau must be within [0, 1], got %r" % (tau,))
+            H, dev = self.stage._H, eng.device
+            L, p = H.lib(), H._p
+            with torch.cuda.device(dev):
+                entry = {"gt_boxes": torch.zeros((N, G, 4), device=dev),
+                         "seq_counts": torch.zeros((S, 8), dtype=torch.int32, device=dev),
+                         "seq_iou": torch.zeros((S,), dtype=torch.float64, device=dev),
+                         "gt_match": torch.zeros((N, G), dtype=torch.int32, device=dev), "graph": None}
+            entry["plan"] = [(L.air_track_score, (p(boxes), p(counts), p(ids), p(entry["gt_boxes"]), tau_f, T, G, S, n_frames, N,
+                                                  p(entry["seq_counts"]), p(entry["seq_iou"]), p(entry["gt_match"])), "air_track_score")]
+            if self.stage._graph is not None:
+                eng.synchronize()
+                entry["graph"] = eng._capture_plans([entry["plan"]])
+            while len(self.entries) >= 4:
+                destroy_graphs([self.entries.pop(next(iter(self.entries)))["graph"]])
+            self.entries[key] = entry
+        return entry
+
+    def run(self, gt_boxes, n_frames, entry_for):
+        """stage gt_boxes [N, G, 4] or [S, n_frames, G, 4] into the buffers of `entry_for(G)` and issue that entry; returns it"""
+        import torch
+        eng, N = self.engine, self.S * n_frames
+        gb = torch.as_tensor(gt_boxes)
+        if gb.dim() not in (3, 4) or gb.shape[-1] != 4 or gb.numel() != N * gb.shape[-2] * 4:
+            raise ValueError("gt_boxes: expected [%d, G, 4] or [%d, %d, G, 4], got %s" % (N, self.S, n_frames, tuple(gb.shape)))
+        entry = entry_for(gb.shape[-2])
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            entry["gt_boxes"].copy_(gb.reshape(entry["gt_boxes"].shape), non_blocking=True)
+        if gb.is_cuda:
+            gb.record_stream(eng.stream)
+        eng._replay_or_run(entry["graph"], entry["plan"])
+        return entry
+
+    def result(self, entry, accumulate=None):
+        """the entry's outputs; accumulate True / False: added to / restarting the totals on the device (no read-back), and the totals"""
+        import torch
+        eng = self.engine
+        out = {k: entry[k] for k in ("seq_counts", "seq_iou", "gt_match")}
+        if accumulate is not None:
+            with torch.cuda.stream(eng.stream):
+                ti, tf = entry["seq_counts"].sum(0, dtype=torch.int64), entry["seq_iou"].sum(0, keepdim=True)
+                if accumulate:
+                    self.totals_i += ti
+                    self.totals_f += tf
+                else:
+                    self.totals_i.copy_(ti)
+                    self.totals_f.copy_(tf)
+            out.update(totals_i=self.totals_i, totals_f=self.totals_f)
+        eng.wait_for_engine()
+        return out
+
+    def reset(self):
+        """zero the totals"""
+        import torch
+        eng = self.engine
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            self.totals_i.zero_()
+            self.totals_f.zero_()
+        eng.wait_for_engine()
+
+    def summary(self) -> Dict[str, float]:
+        """mot_summary of everything accumulated since the last reset (ONE read-back)"""
+        import torch
+        self.engine.wait_for_engine()
+        flat = torch.cat([self.totals_i.double(), self.totals_f]).tolist()
+        return mot_summary(flat[:8], flat[8])
 
 
-class SequenceTracker:
+class SequenceTracker(BoundStage):
+    ACCEPTS = ("scene", "refiner", "subset", "tiled")
+    REFUSALS = TiledSceneParser.REFUSALS
+
     def __init__(self, provider, n_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
                  birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"]):
-        what = _provider_what(provider)
+        self._rows = self.bind(provider)
         T, F, S = check_arguments(provider.T, n_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age)
         import torch
         from . import hip as H
         self.provider, self.engine = provider, provider.engine
+        self._bound = provider
         self.T, self.R, self.S, self.F = T, int(provider.R), S, F
         self.iou_gate, self.appearance_weight, self.birth_score, self.max_age = (float(iou_gate), float(appearance_weight),
                                                                                  float(birth_score), int(max_age))
-        self._what = what
-        self.A = int(what.shape[-1])
+        self._what = self._rows["what"]
+        self.A = int(self._what.shape[-1])
         self.img_size = tuple(int(v) for v in provider.owner.shape[1:])
         dev = self.engine.device
         R, FT = self.R, F * T
@@ -304,66 +395,37 @@ class SequenceTracker:
             self.track_first, self.track_last, self.track_length, self.track_gaps = z((S, FT)), z((S, FT)), z((S, FT)), z((S, FT))
             self.state_counts = z((S, 6))
             self.track_owner = z((R,) + self.img_size, torch.int16)
-            self.totals_i, self.totals_f = z((8,), torch.int64), z((1,), torch.float64)
-        self._graph = None
-        self._score = {}                                           # (G, tau) -> buffers, plan, graph
         self._H = H
-        L, p = H.lib(), H._p
+        self.scores = IdentityScores(self, S)
+        self._score = self.scores.entries                          # (G, tau) -> buffers, plan, graph
+        self.totals_i, self.totals_f = self.scores.totals_i, self.scores.totals_f
+        self._rebuild()
+        self.engine.synchronize()
+
+    def _build_plan(self):
+        """nothing of the engine's configuration is held by the tracker's launch list: built once"""
+        provider, T, R, S, F = self.provider, self.T, self.R, self.S, self.F
+        L, p = self._H.lib(), self._H._p
         Hi, Wi = self.img_size
         self.segments = OrderedDict([
             ("associate", [(L.air_track_associate,
-                            (p(what), p(provider.boxes), p(provider.score), p(provider.num_objects), T, S, F, R, self.A, self.iou_gate,
-                             self.appearance_weight, self.birth_score, self.max_age, p(self.track_id), p(self.obj_state), p(self.affinity),
-                             p(self.prev_frame), p(self.prev_slot), p(self.num_tracks), p(self.track_first), p(self.track_last),
-                             p(self.track_length), p(self.track_gaps), p(self.state_counts)), "air_track_associate")]),
+                            (p(self._what), p(provider.boxes), p(provider.score), p(provider.num_objects), T, S, F, R, self.A,
+                             self.iou_gate, self.appearance_weight, self.birth_score, self.max_age, p(self.track_id), p(self.obj_state),
+                             p(self.affinity), p(self.prev_frame), p(self.prev_slot), p(self.num_tracks), p(self.track_first),
+                             p(self.track_last), p(self.track_length), p(self.track_gaps), p(self.state_counts)),
+                            "air_track_associate")]),
             ("owner", [(L.air_track_owner, (p(provider.owner), p(self.track_id), T, R, Hi, Wi, p(self.track_owner)),
                         "air_track_owner")])])
         self._plan = [e for seg in self.segments.values() for e in seg]
-        self.engine.synchronize()
+
+    def _score_entries(self):
+        return self._score.values()
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `track()` call behind the bound provider's own (`parser` holds that provider's launch_count())"""
         return {"parser": self.provider.launch_count(), "track_associate": 1, "track_owner": 1}
 
-    # ---- parameters ---------------------------------------------------------------------------------------------------------
-    def load_from(self, train_engine):
-        self.provider.load_from(train_engine)
-
-    def load_parameters(self, named):
-        self.provider.load_parameters(named)
-
-    def set_global_step(self, step: int):
-        self.provider.set_global_step(step)
-
-    def update_config(self, **changes) -> bool:
-        """run-time switches of the bound provider's engine: nothing of them is held by the tracker's launch list"""
-        return self.provider.update_config(**changes)
-
-    # ---- graphs -------------------------------------------------------------------------------------------------------------
-    def capture(self):
-        """the launches behind the provider's own call as ONE hipGraph, whatever F is (the provider's graphs are its own:
-        `provider.capture()`); the scoring launch of every (G, tau) used so far as one more each"""
-        self.release_graphs()
-        self.engine.synchronize()
-        self._graph = self.engine._capture_plans([self._plan])
-        for entry in self._score.values():
-            entry["graph"] = self.engine._capture_plans([entry["plan"]])
-
-    def release_graphs(self):
-        destroy_graphs([self._graph] + [e["graph"] for e in self._score.values()])
-        self._graph = None
-        for e in self._score.values():
-            e["graph"] = None
-
     # ---- tracking -----------------------------------------------------------------------------------------------------------
-    def run_segments(self, *names):
-        """issue the named segments eagerly, in the order given, on the engine's stream (tests and probes run the pieces this way)"""
-        eng = self.engine
-        eng.wait_for_caller()
-        for name in names:
-            eng._run(self.segments[name], eng._sp())
-        eng.wait_for_engine()
-
     def run_provider(self, frames, *args, **kwargs):
         """the bound provider's `parse()` on the frames as its R = S F rows (further arguments go to it unchanged)"""
         import torch
@@ -373,11 +435,8 @@ class SequenceTracker:
         if frames.numel() != self.R * Hi * Wi or frames.dim() < 2 or tuple(frames.shape[:2]) != (self.S, self.F):
             raise ValueError("expected frames [%d, %d, %d, %d], got %s" % (self.S, self.F, Hi, Wi, tuple(frames.shape)))
         base = par.parse(frames.reshape(self.R, Hi, Wi), *args, **kwargs)
-        if base["what"].data_ptr() != self._what.data_ptr():
-            raise RuntimeError("the bound provider returned 'what' from another buffer than the tracker was built on")
-        for k in ("boxes", "score", "num_objects", "owner"):
-            if base[k].data_ptr() != getattr(par, k).data_ptr():
-                raise RuntimeError("the bound provider returned %r from another buffer than the tracker was built on" % k)
+        self.check_same_buffers(base, dict(what=self._what, boxes=par.boxes, score=par.score, num_objects=par.num_objects,
+                                           owner=par.owner), "tracker", bound="provider")
         return base
 
     def track(self, frames, *args, **kwargs):
@@ -405,79 +464,22 @@ class SequenceTracker:
 
     # ---- the identity metric ------------------------------------------------------------------------------------------------
     def _score_entry(self, G, tau):
-        import torch
-        key = (int(G), float(tau))
-        entry = self._score.get(key)
-        if entry is None:
-            if not 1 <= key[0] <= MAX_GT:
-                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, key[0]))
-            if not 0.0 <= key[1] <= 1.0:
-                raise ValueError("tau must be within [0, 1], got %r" % (tau,))
-            H, par, dev = self._H, self.provider, self.engine.device
-            L, p = H.lib(), H._p
-            with torch.cuda.device(dev):
-                entry = {"gt_boxes": torch.zeros((self.R, key[0], 4), device=dev),
-                         "seq_counts": torch.zeros((self.S, 8), dtype=torch.int32, device=dev),
-                         "seq_iou": torch.zeros((self.S,), dtype=torch.float64, device=dev),
-                         "gt_match": torch.zeros((self.R, key[0]), dtype=torch.int32, device=dev), "graph": None}
-            entry["plan"] = [(L.air_track_score, (p(par.boxes), p(par.num_objects), p(self.track_id), p(entry["gt_boxes"]), key[1], self.T,
-                                                  key[0], self.S, self.F, self.R, p(entry["seq_counts"]), p(entry["seq_iou"]),
-                                                  p(entry["gt_match"])), "air_track_score")]
-            if self._graph is not None:
-                self.engine.synchronize()
-                entry["graph"] = self.engine._capture_plans([entry["plan"]])
-            while len(self._score) >= 4:                           # a sweep over tau must not pile up buffers and graphs
-                destroy_graphs([self._score.pop(next(iter(self._score)))["graph"]])
-            self._score[key] = entry
-        return entry
+        par = self.provider
+        return self.scores.entry((), G, tau, self.T, self.F, par.boxes, par.num_objects, self.track_id)
 
     def score(self, gt_boxes, tau=0.5, accumulate=True):
         """Score the LATEST `track()` against gt_boxes [R, G, 4] (or [S, F, G, 4]; G <= 8; slot g is the same object in every frame of
         a sequence, width <= 0 = absent).  Returns device tensors that the next call with the same (G, tau) overwrites: seq_counts
         [S, 8] int32 (COUNTS), seq_iou [S] float64, gt_match [R, G] int32, and the running totals_i [8] int64 / totals_f [1] float64,
         which this call adds to (accumulate=False: restarts) on the device, with no read-back.  Same stream contract as `track`."""
-        import torch
-        eng = self.engine
-        gb = torch.as_tensor(gt_boxes)
-        if gb.dim() not in (3, 4) or gb.shape[-1] != 4 or gb.numel() != self.R * gb.shape[-2] * 4:
-            raise ValueError("gt_boxes: expected [%d, G, 4] or [%d, %d, G, 4], got %s" % (self.R, self.S, self.F, tuple(gb.shape)))
-        entry = self._score_entry(gb.shape[-2], tau)
-        eng.wait_for_caller()
-        with torch.cuda.stream(eng.stream):
-            entry["gt_boxes"].copy_(gb.reshape(entry["gt_boxes"].shape), non_blocking=True)
-        if gb.is_cuda:
-            gb.record_stream(eng.stream)
-        eng._replay_or_run(entry["graph"], entry["plan"])
-        with torch.cuda.stream(eng.stream):
-            ti, tf = entry["seq_counts"].sum(0, dtype=torch.int64), entry["seq_iou"].sum(0, keepdim=True)
-            if accumulate:
-                self.totals_i += ti
-                self.totals_f += tf
-            else:
-                self.totals_i.copy_(ti)
-                self.totals_f.copy_(tf)
-        eng.wait_for_engine()
-        return {"seq_counts": entry["seq_counts"], "seq_iou": entry["seq_iou"], "gt_match": entry["gt_match"],
-                "totals_i": self.totals_i, "totals_f": self.totals_f}
+        return self.scores.result(self.scores.run(gt_boxes, self.F, lambda G: self._score_entry(G, tau)), bool(accumulate))
 
     def reset(self):
         """zero the totals"""
-        import torch
-        eng = self.engine
-        eng.wait_for_caller()
-        with torch.cuda.stream(eng.stream):
-            self.totals_i.zero_()
-            self.totals_f.zero_()
-        eng.wait_for_engine()
+        self.scores.reset()
 
     def summary(self) -> Dict[str, float]:
         """The figures of everything scored since the last reset (ONE read-back): mota = 1 - (misses + fp + idsw) / gt, motp =
         sum_iou / matches, id_switches, mostly_tracked, mostly_lost (fractions of the ground-truth objects), false_positives, misses,
         and the counts gt, matches, gt_objects.  A denominator of 0 gives nan."""
-        import torch
-        self.engine.wait_for_engine()
-        flat = torch.cat([self.totals_i.double(), self.totals_f]).tolist()
-        return mot_summary(flat[:8], flat[8])
-
-    def synchronize(self):
-        self.engine.synchronize()
+        return self.scores.summary()

@@ -47,8 +47,8 @@ import ctypes
 from collections import OrderedDict
 from typing import Dict
 
-from .launch import destroy_graphs
-from .track import MAX_GT, MAX_IDS, MAX_SLOTS, mot_summary
+from .stage import BoundStage, ReadOut, compacted_rows
+from .track import MAX_IDS, MAX_SLOTS, IdentityScores
 from .track import check_arguments as check_track_arguments
 
 MAX_HORIZON = 16
@@ -207,19 +207,11 @@ def reference_smooth(where, num_objects, track_id, num_tracks, track_first, trac
     return out
 
 
-def _provider_where_glimpse(provider):
-    """the `where` [T, R, 4] and `glimpse` [T, R, G] rows of the provider's `parse()` (track._provider_what's rule)"""
-    from .tile import _provider_rows
-    if hasattr(provider, "kept_cand") and not hasattr(provider, "what_sel"):       # tile.TiledSceneParser: its own lifted rows
-        return provider.where, provider.glimpse
-    rows = _provider_rows(provider)
-    return rows["where"], rows["glimpse"]
-
-
 class CompletedFrames:
     """The completed frames of a TrajectorySmoother as a provider: what [C, R, A], where [C, R, 4], glimpse [C, R, G], boxes [C, R, 4],
     score, presence [C, R], num_objects [R], owner [R, H, W], T = C, R, engine, mask_threshold -- what score.ParseScorer reads, so it
     binds to this unchanged.  (The smoother itself carries the same buffers, but its `score` is the identity metric's method.)"""
+    KIND = "completed"
 
     def __init__(self, smoother):
         t = smoother.sm
@@ -228,6 +220,10 @@ class CompletedFrames:
         self.presence, self.num_objects, self.owner = t["presence"], t["num_objects"], t["owner"]
         self.mask_threshold = smoother.mask_threshold
 
+    def rows(self):
+        """the provider protocol (stage.py): the completed rows; there is no count posterior and no image of a completed frame"""
+        return compacted_rows(self, None, None)
+
     def launch_count(self):
         return self.smoother.launch_count()
 
@@ -235,81 +231,72 @@ class CompletedFrames:
         self.engine.synchronize()
 
 
-class TrajectorySmoother:
+class TrajectorySmoother(BoundStage):
+    """binds to a SequenceTracker (what it forwards parameters and switches to) and reads that tracker's provider"""
+    KEY_FIELDS = ("output_multiplier", "output_std")
+
     def __init__(self, tracker, horizon=0, process_noise=DEFAULTS["process_noise"], measurement_noise=DEFAULTS["measurement_noise"],
                  velocity_var=DEFAULTS["velocity_var"]):
         provider = tracker.provider
-        where, glimpse = _provider_where_glimpse(provider)
         T, F, S, C, Hz, q, r, vv = check_arguments(tracker.T, tracker.F, tracker.R, tracker.max_age, horizon, process_noise,
                                                    measurement_noise, velocity_var)
         import torch
         from . import hip as H
         self.tracker, self.provider, self.engine = tracker, provider, tracker.engine
         self.parser = provider
+        self._bound = tracker
         self.window_T, self.T, self.C, self.R, self.S, self.F, self.horizon = T, C, C, int(tracker.R), S, F, Hz
         self.process_noise, self.measurement_noise, self.velocity_var, self.max_age = q, r, vv, int(tracker.max_age)
         self.mask_threshold = provider.mask_threshold
         self.img_size = tuple(tracker.img_size)
-        self._rows = {"what": tracker._what, "where": where, "glimpse": glimpse}
+        self._rows = {k: tracker._rows[k] for k in ("what", "where", "glimpse")}
         cfg = self.engine.cfg
         self.A, self.G = int(tracker.A), int(cfg.crop_size[0]) * int(cfg.crop_size[1])
-        dev, R, N, A, G = self.engine.device, self.R, S * Hz, self.A, self.G
-        Hi, Wi = self.img_size
+        dev, R, N = self.engine.device, self.R, S * Hz
         L = H.lib()
-        self.n_bands = int(L.air_canvas_unroll_bands(R, Hi))
-        self.n_bands_fc = int(L.air_canvas_unroll_bands(N, Hi)) if N else 0
+        self.n_bands = int(L.air_canvas_unroll_bands(R, self.img_size[0]))
+        self.n_bands_fc = int(L.air_canvas_unroll_bands(N, self.img_size[0])) if N else 0
         self.workspace_bytes = int(L.air_track_smooth_workspace_bytes(C, R))
+        self._H = H
         z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
         with torch.cuda.device(dev):
             self.workspace = z((self.workspace_bytes // 8,), torch.float64)
-            self.sm, self.fc = self._table(z, R), (self._table(z, N) if N else None)
+            (self.sm, self._sm_ro), (self.fc, self._fc_ro) = self._table(z, R, self.n_bands), \
+                (self._table(z, N, self.n_bands_fc) if N else (None, None))
             self.sm_counts = z((S, 3), torch.int32)
-            self.totals_i, self.totals_f = z((8,), torch.int64), z((1,), torch.float64)
+        self.scores = IdentityScores(self, S)
+        self._score = self.scores.entries                          # (table, G, tau) -> buffers, plan, graph
+        self.totals_i, self.totals_f = self.scores.totals_i, self.scores.totals_f
         # the provider surface: the completed frames (`score` is this object's scoring method: the per-row score tensor is
         # `completed.score`, and `completed` is what a score.ParseScorer binds to)
         t = self.sm
         self.what, self.where, self.glimpse, self.boxes = t["what"], t["where"], t["glimpse"], t["boxes_out"]
         self.presence, self.num_objects, self.owner = t["presence"], t["num_objects"], t["owner"]
         self.completed = CompletedFrames(self)
-        self._graph = None
-        self._score = {}                                           # (table, G, tau) -> buffers, plan, graph
-        self._H = H
-        self._build_plan()
-        self._check_render()
+        self._rebuild()
+        for name in ("readout", "readout_forecast"):               # (tile.py's rule)
+            if name in self.segments:
+                self.check_render(self.segments[name][2],
+                                  "air_parse_render declines %d x %d frames with %d completed rows: its LDS carve passes the 160 KiB "
+                                  "of a workgroup; use a smaller max_age" % (self.img_size + (self.C,)))
         self.engine.synchronize()
 
-    def _table(self, z, N):
-        """the buffers of one table of C rows and N columns: air_track_smooth's and air_track_fill's outputs and the read-out"""
+    def _table(self, z, N, n_bands):
+        """the buffers of one table of C rows and N columns: air_track_smooth's and air_track_fill's outputs, and the read-out (what
+        the parsers keep; its score and boxes under score_out / boxes_out)"""
         import torch
         C, A, G = self.C, self.A, self.G
-        Hi, Wi = self.img_size
-        return {"where": z((C, N, 4)), "boxes": z((C, N, 4)), "id": z((C, N), torch.int32), "state": z((C, N), torch.int8),
-                "src_frame": z((C, N), torch.int32), "src_slot": z((C, N), torch.int32), "velocity": z((C, N, 2)),
-                "count": z((N,), torch.int32), "what": z((C, N, A)), "glimpse": z((C, N, G)), "score": z((C, N)),
-                # the read-out (what the parsers keep)
-                "num_objects": z((N,), torch.int32), "count_prob": z((N,)), "presence": z((C, N)), "score_out": z((C, N)),
-                "boxes_out": z((C, N, 4)), "offsets": z((N + 1,), torch.int32), "obj_image": z((C * N,), torch.int32),
-                "obj_step": z((C * N,), torch.int32), "obj_box": z((C * N, 4)), "obj_score": z((C * N,)), "obj_where": z((C * N, 4)),
-                "obj_what": z((C * N, A)), "reconstruction": z((N, Hi, Wi)), "owner": z((N, Hi, Wi), torch.int8),
-                "area": z((C, N), torch.int32)}
+        ro = ReadOut(self._H, self.engine, C, N, A, self.img_size, n_bands, self.mask_threshold, with_rec=False)
+        t = {"where": z((C, N, 4)), "boxes": z((C, N, 4)), "id": z((C, N), torch.int32), "state": z((C, N), torch.int8),
+             "src_frame": z((C, N), torch.int32), "src_slot": z((C, N), torch.int32), "velocity": z((C, N, 2)),
+             "count": z((N,), torch.int32), "what": z((C, N, A)), "glimpse": z((C, N, G)), "score": z((C, N))}
+        t.update(ro.tensors(score="score_out", boxes="boxes_out"))
+        return t, ro
 
     # ---- the launches behind the tracker's own -------------------------------------------------------------------------------
-    def _readout(self, t, N, n_bands):
-        H, cfg = self._H, self.engine.cfg
-        L, p = H.lib(), H._p
-        C, A = self.C, self.A
-        (Hi, Wi), (hc, wc) = self.img_size, cfg.crop_size
-        mult, std = float(cfg.output_multiplier), float(cfg.output_std)
-        return [(L.air_parse_objects,
-                 (None, p(t["count"]), p(t["where"]), p(t["what"]), C, N, A, Hi, Wi, p(t["num_objects"]), p(t["count_prob"]),
-                  p(t["presence"]), p(t["score_out"]), p(t["boxes_out"]), p(t["offsets"]), p(t["obj_image"]), p(t["obj_step"]),
-                  p(t["obj_box"]), p(t["obj_score"]), p(t["obj_where"]), p(t["obj_what"])), "air_parse_objects"),
-                (L.air_tile_relabel,
-                 (p(t["score"]), p(t["id"]), p(t["num_objects"]), p(t["offsets"]), C, N, p(t["score_out"]), p(t["obj_score"]),
-                  p(t["obj_step"])), "air_tile_relabel"),
-                (L.air_parse_render,
-                 (p(t["glimpse"]), p(t["where"]), p(t["presence"]), None, mult, std, self.mask_threshold, C, N, Hi, Wi, hc, wc, n_bands,
-                  p(t["reconstruction"]), None, p(t["owner"]), p(t["area"]), None), "air_parse_render")]
+    def _readout(self, t, ro):
+        return [ro.objects(None, t["count"], t["where"], t["what"]), ro.relabel("air_tile_relabel", t["score"], t["id"]),
+                ro.render(t["glimpse"], t["where"], None)]
 
     def _fill(self, t, N, per_seq):
         H, rows, par = self._H, self._rows, self.provider
@@ -334,39 +321,14 @@ class TrajectorySmoother:
                           fcp("where"), fcp("boxes"), fcp("id"), fcp("state"), fcp("src_frame"), fcp("src_slot"), fcp("velocity"),
                           fcp("count")), "air_track_smooth")]),
             ("fill", self._fill(sm, self.R, self.F)),
-            ("readout", self._readout(sm, self.R, self.n_bands))])
+            ("readout", self._readout(sm, self._sm_ro))])
         if fc is not None:
             self.segments["fill_forecast"] = self._fill(fc, self.S * Hz, Hz)
-            self.segments["readout_forecast"] = self._readout(fc, self.S * Hz, self.n_bands_fc)
+            self.segments["readout_forecast"] = self._readout(fc, self._fc_ro)
         self._plan = [e for seg in self.segments.values() for e in seg]
-        self._built_for = self._plan_key()
 
-    def _check_render(self):
-        """air_parse_render stages the C bordered glimpses of a band in LDS: refuse here, by name, what it declines (tile.py's rule)"""
-        from . import _lib
-        for name in ("readout", "readout_forecast"):
-            if name in self.segments:
-                fn, args, entry = self.segments[name][2]
-                st = fn(*args, self.engine._sp())
-                if st == -5:
-                    raise ValueError("air_parse_render declines %d x %d frames with %d completed rows: its LDS carve passes the 160 KiB "
-                                     "of a workgroup; use a smaller max_age" % (self.img_size + (self.C,)))
-                _lib.check(st, entry)
-
-    def _plan_key(self):
-        cfg = self.engine.cfg
-        return (cfg.output_multiplier, cfg.output_std)
-
-    def _refresh_plan(self):
-        """rebuild (and re-capture) when a switch of the provider's engine moved without this object being told"""
-        if self._plan_key() == self._built_for:
-            return False
-        had = self._graph is not None
-        self.release_graphs()
-        self._build_plan()
-        if had:
-            self.capture()
-        return True
+    def _score_entries(self):
+        return self._score.values()
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `run()` behind the tracker's own (`tracker` holds that tracker's launch_count())"""
@@ -374,48 +336,7 @@ class TrajectorySmoother:
         return {"tracker": self.tracker.launch_count(), "track_smooth": 1, "track_fill": n, "parse_objects": n, "tile_relabel": n,
                 "parse_render": n}
 
-    # ---- parameters: the bound tracker's ------------------------------------------------------------------------------------------
-    def load_from(self, train_engine):
-        self.tracker.load_from(train_engine)
-        self._refresh_plan()
-
-    def load_parameters(self, named):
-        self.tracker.load_parameters(named)
-
-    def set_global_step(self, step: int):
-        self.tracker.set_global_step(step)
-
-    def update_config(self, **changes) -> bool:
-        if self._graph is not None:
-            self.engine.synchronize()
-        changed = self.tracker.update_config(**changes)
-        return self._refresh_plan() or changed
-
-    # ---- graphs -------------------------------------------------------------------------------------------------------------
-    def capture(self):
-        """smooth, fill and both read-outs as ONE hipGraph, whatever F and the horizon are (the tracker's and the provider's graphs
-        are their own); the scoring launch of every (table, G, tau) used so far as one more each"""
-        self.release_graphs()
-        self.engine.synchronize()
-        self._graph = self.engine._capture_plans([self._plan])
-        for entry in self._score.values():
-            entry["graph"] = self.engine._capture_plans([entry["plan"]])
-
-    def release_graphs(self):
-        destroy_graphs([self._graph] + [e["graph"] for e in self._score.values()])
-        self._graph = None
-        for e in self._score.values():
-            e["graph"] = None
-
     # ---- the trajectories ---------------------------------------------------------------------------------------------------
-    def run_segments(self, *names):
-        """issue the named segments eagerly, in the order given, on the engine's stream (tests and probes run the pieces this way)"""
-        eng = self.engine
-        eng.wait_for_caller()
-        for name in names:
-            eng._run(self.segments[name], eng._sp())
-        eng.wait_for_engine()
-
     def run(self, base=None):
         """the trajectories of the tracker's LATEST `track()`; `base` (that call's result) is passed through into the returned dict.
         The tracker's and the provider's buffers are only read.  Same stream contract as SequenceTracker.track."""
@@ -456,97 +377,33 @@ class TrajectorySmoother:
 
     # ---- the identity metric on the tables ------------------------------------------------------------------------------------
     def _score_entry(self, table, G, tau):
-        import torch
-        key = (table, int(G), float(tau))
-        entry = self._score.get(key)
-        if entry is None:
-            if not 1 <= key[1] <= MAX_GT:
-                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, key[1]))
-            if not 0.0 <= key[2] <= 1.0:
-                raise ValueError("tau must be within [0, 1], got %r" % (tau,))
-            t, n_frames = (self.sm, self.F) if table == "completed" else (self.fc, self.horizon)
-            if n_frames * self.C > MAX_IDS:
-                raise ValueError("air_track_score takes at most %d rows per sequence; %d frames of %d completed rows are %d"
-                                 % (MAX_IDS, n_frames, self.C, n_frames * self.C))
-            H, dev, N = self._H, self.engine.device, self.S * n_frames
-            L, p = H.lib(), H._p
-            with torch.cuda.device(dev):
-                entry = {"gt_boxes": torch.zeros((N, key[1], 4), device=dev),
-                         "seq_counts": torch.zeros((self.S, 8), dtype=torch.int32, device=dev),
-                         "seq_iou": torch.zeros((self.S,), dtype=torch.float64, device=dev),
-                         "gt_match": torch.zeros((N, key[1]), dtype=torch.int32, device=dev), "graph": None}
-            entry["plan"] = [(L.air_track_score, (p(t["boxes"]), p(t["count"]), p(t["id"]), p(entry["gt_boxes"]), key[2], self.C, key[1],
-                                                  self.S, n_frames, N, p(entry["seq_counts"]), p(entry["seq_iou"]), p(entry["gt_match"])),
-                              "air_track_score")]
-            if self._graph is not None:
-                self.engine.synchronize()
-                entry["graph"] = self.engine._capture_plans([entry["plan"]])
-            while len(self._score) >= 4:                           # a sweep over tau must not pile up buffers and graphs
-                destroy_graphs([self._score.pop(next(iter(self._score)))["graph"]])
-            self._score[key] = entry
-        return entry
+        t, n_frames = (self.sm, self.F) if table == "completed" else (self.fc, self.horizon)
+        if n_frames * self.C > MAX_IDS:
+            raise ValueError("air_track_score takes at most %d rows per sequence; %d frames of %d completed rows are %d"
+                             % (MAX_IDS, n_frames, self.C, n_frames * self.C))
+        return self.scores.entry((table,), G, tau, self.C, n_frames, t["boxes"], t["count"], t["id"])
 
     def _run_score(self, table, gt_boxes, tau, n_frames):
-        import torch
-        eng = self.engine
-        gb = torch.as_tensor(gt_boxes)
-        N = self.S * n_frames
-        if gb.dim() not in (3, 4) or gb.shape[-1] != 4 or gb.numel() != N * gb.shape[-2] * 4:
-            raise ValueError("gt_boxes: expected [%d, G, 4] or [%d, %d, G, 4], got %s" % (N, self.S, n_frames, tuple(gb.shape)))
-        entry = self._score_entry(table, gb.shape[-2], tau)
-        eng.wait_for_caller()
-        with torch.cuda.stream(eng.stream):
-            entry["gt_boxes"].copy_(gb.reshape(entry["gt_boxes"].shape), non_blocking=True)
-        if gb.is_cuda:
-            gb.record_stream(eng.stream)
-        eng._replay_or_run(entry["graph"], entry["plan"])
-        return entry
+        return self.scores.run(gt_boxes, n_frames, lambda G: self._score_entry(table, G, tau))
 
     def score(self, gt_boxes, tau=0.5, accumulate=True):
         """SequenceTracker.score on the COMPLETED table of the latest `run()`: the unchanged air_track_score with T := C on sm_boxes,
         sm_count, sm_id, so a frame a track coasted over counts a match when the filled box is on the object.  gt_boxes [R, G, 4] or
         [S, F, G, 4].  Returns seq_counts [S, 8] int32 (track.COUNTS), seq_iou [S] float64, gt_match [R, G] int32 (the matched ROW)
         and this object's own running totals_i [8] int64 / totals_f [1] float64 (accumulate=False: restarts), all on the device."""
-        import torch
-        eng = self.engine
-        entry = self._run_score("completed", gt_boxes, tau, self.F)
-        with torch.cuda.stream(eng.stream):
-            ti, tf = entry["seq_counts"].sum(0, dtype=torch.int64), entry["seq_iou"].sum(0, keepdim=True)
-            if accumulate:
-                self.totals_i += ti
-                self.totals_f += tf
-            else:
-                self.totals_i.copy_(ti)
-                self.totals_f.copy_(tf)
-        eng.wait_for_engine()
-        return {"seq_counts": entry["seq_counts"], "seq_iou": entry["seq_iou"], "gt_match": entry["gt_match"],
-                "totals_i": self.totals_i, "totals_f": self.totals_f}
+        return self.scores.result(self._run_score("completed", gt_boxes, tau, self.F), bool(accumulate))
 
     def score_forecast(self, gt_future_boxes, tau=0.5):
         """the same kernel on the FORECAST table with F := Hz: gt_future_boxes [S Hz, G, 4] or [S, Hz, G, 4], slot g the same object
         over the horizon.  Returns seq_counts [S, 8], seq_iou [S], gt_match [S Hz, G]; nothing is accumulated."""
         if self.fc is None:
             raise ValueError("score_forecast needs a horizon >= 1; this smoother was built with horizon=0")
-        entry = self._run_score("forecast", gt_future_boxes, tau, self.horizon)
-        self.engine.wait_for_engine()
-        return {"seq_counts": entry["seq_counts"], "seq_iou": entry["seq_iou"], "gt_match": entry["gt_match"]}
+        return self.scores.result(self._run_score("forecast", gt_future_boxes, tau, self.horizon))
 
     def reset(self):
         """zero the totals"""
-        import torch
-        eng = self.engine
-        eng.wait_for_caller()
-        with torch.cuda.stream(eng.stream):
-            self.totals_i.zero_()
-            self.totals_f.zero_()
-        eng.wait_for_engine()
+        self.scores.reset()
 
     def summary(self) -> Dict[str, float]:
         """track.mot_summary of everything `score` took since the last reset (ONE read-back)"""
-        import torch
-        self.engine.wait_for_engine()
-        flat = torch.cat([self.totals_i.double(), self.totals_f]).tolist()
-        return mot_summary(flat[:8], flat[8])
-
-    def synchronize(self):
-        self.engine.synchronize()
+        return self.scores.summary()

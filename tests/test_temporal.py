@@ -601,9 +601,9 @@ def test_refusals(gpu_device):
     with pytest.raises(ValueError, match="direction"):
         TemporalProposer(ps, 5, direction="future")
     with pytest.raises(ValueError, match="ParticleParser"):
-        TemporalProposer(types.SimpleNamespace(what_sel=None, engine=ps.engine, R=10, T=3), 5)
+        TemporalProposer(types.SimpleNamespace(KIND="particle", engine=ps.engine, R=10, T=3), 5)
     with pytest.raises(ValueError, match="TiledSceneParser"):
-        TemporalProposer(types.SimpleNamespace(kept_cand=None, kept_step=None, engine=ps.engine, R=10, T=3), 5)
+        TemporalProposer(types.SimpleNamespace(KIND="tiled", engine=ps.engine, R=10, T=3), 5)
     past = TemporalProposer(ps, 5, direction="past", interpolate=False)
     out = past.parse(torch.zeros(10, *ocfg.img_size).cuda(), mixed_counts(ocfg, 10))
     past.synchronize()
@@ -678,7 +678,7 @@ def test_track_on_the_model_with_temporal(gpu_device):
         with pytest.raises(ValueError):
             air.track(frames, temporal=bad)
     with pytest.raises(ValueError, match="ParticleParser"):
-        TemporalProposer(types.SimpleNamespace(what_sel=None, engine=air._engine, R=S * F, T=3), F)
+        TemporalProposer(types.SimpleNamespace(KIND="particle", engine=air._engine, R=S * F, T=3), F)
     with pytest.raises(ValueError, match="TiledSceneParser"):
         TemporalProposer(air.tiled_parser(1, (75, 75)), 1)
 

@@ -536,7 +536,7 @@ def test_refusals(gpu_device):
     with pytest.raises(ValueError, match="smaller"):
         TiledSceneParser(ps, (2, 6))
     with pytest.raises(ValueError, match="ParticleParser"):
-        TiledSceneParser(types.SimpleNamespace(what_sel=None, engine=ps.engine, R=10, T=3), ocfg.img_size)     # a particle provider
+        TiledSceneParser(types.SimpleNamespace(KIND="particle", engine=ps.engine, R=10, T=3), ocfg.img_size)     # a particle provider
     tp = TiledSceneParser(ps, ocfg.img_size)
     with pytest.raises(ValueError, match="scenes"):
         tp.parse(torch.zeros(3, 3, 3).cuda())

@@ -372,7 +372,7 @@ def test_refusals(gpu_device):
     with pytest.raises(ValueError, match="iou_gate"):
         SequenceTracker(ps, 5, iou_gate=1.0)
     with pytest.raises(ValueError, match="ParticleParser"):
-        SequenceTracker(types.SimpleNamespace(what_sel=None, engine=ps.engine, R=10, T=3), 5)
+        SequenceTracker(types.SimpleNamespace(KIND="particle", engine=ps.engine, R=10, T=3), 5)
     tk = SequenceTracker(ps, 5)
     with pytest.raises(ValueError, match="frames"):
         tk.track(torch.zeros(5, 2, *ocfg.img_size).cuda())
