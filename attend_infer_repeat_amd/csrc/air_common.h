@@ -98,6 +98,16 @@ __device__ __forceinline__ float wave_sum_all(float v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;  // valid in every lane
 }
+__device__ __forceinline__ double wave_sum_all(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;  // valid in every lane
+}
+__device__ __forceinline__ float wave_max_all(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;  // valid in every lane
+}
 
 // Eight per-lane partial sums -> the eight totals over the 64 lanes of a wave in 10 cross-lane moves (a plain butterfly per
 // value takes 48): every exchange step halves the number of live values.  Afterwards lane L holds the total of output

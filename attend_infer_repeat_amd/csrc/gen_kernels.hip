@@ -5,7 +5,7 @@
 //                      (Philox4x32-10, the numbers air_rng_fill would write), no noise buffer exists.
 // Decoder and canvas in between are the entries the train step uses (air_linear_fwd / air_gemm_bf16, air_canvas_unroll_fwd).
 #include <math.h>
-#include "air_common.h"
+#include "scene_device.h"
 #include "engine_device.h"
 #include "prologue_device.h"
 
@@ -14,11 +14,6 @@
 struct GenPriors {
     float what_loc, what_scale, scale_loc, scale_scale, shift_loc, shift_scale;
 };
-
-template <int V> struct GenVec;
-template <> struct GenVec<4> { typedef float4 type; };
-template <> struct GenVec<2> { typedef float2 type; };
-template <> struct GenVec<1> { typedef float type; };
 
 // One wavefront per scene (row r).  Every lane forms the same count n (T + 1 float64 adds in index order: the table is tiny
 // and wave-uniform), lane t < T then writes presence[t, r] and the four `where` components of step t, and the T A-wide
@@ -29,7 +24,7 @@ __global__ __launch_bounds__(256) void prior_latents_kernel(
     const double *__restrict__ table, const float *__restrict__ u_n, const int *__restrict__ n_in,
     const float *__restrict__ eps_what, const float *__restrict__ eps_where, GenPriors pr, float guard, int T, int R, int A,
     float *__restrict__ what, float *__restrict__ where, float *__restrict__ presence, int *__restrict__ n_out) {
-    typedef typename GenVec<V>::type vec_t;
+    typedef typename VecOf<V>::type vec_t;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;                                            // wave-uniform

@@ -4,7 +4,7 @@
 //                     effective sample size and the self-normalised posterior over the object count (+ float64 running totals).
 // Rows are r = b * K + k: the K particles of an image are adjacent.
 #include <math.h>
-#include "air_common.h"
+#include "scene_device.h"
 
 #define IW_MAXT 32
 
@@ -19,11 +19,6 @@ __device__ __forceinline__ float iw_log_ratio(float x, float loc, float scale, f
     return 0.5f * (zq * zq - zp * zp) + (logf(scale) - log_p_scale);
 }
 
-template <int V> struct IwVec;
-template <> struct IwVec<4> { typedef float4 type; };
-template <> struct IwVec<2> { typedef float2 type; };
-template <> struct IwVec<1> { typedef float type; };
-
 // One wavefront per row.  The chain of presences is monotone, so the steps that count are t < n = the number of leading
 // ones; their A-wide `what` rows are spread over the lanes as n * A / V vectors of V floats (V = 4 / 2 / 1: what the row
 // starts allow), lane t < n takes the four `where` components of step t.  Every lane adds its items in index order, the
@@ -35,7 +30,7 @@ __global__ __launch_bounds__(256) void iw_logweight_kernel(
     const float *__restrict__ presence, const float *__restrict__ rec, const float *__restrict__ logp,
     const double *__restrict__ prior, int T, int R, int A, IwPriors pr, int normalize, float *__restrict__ logw,
     int *__restrict__ n_out) {
-    typedef typename IwVec<V>::type vec_t;
+    typedef typename VecOf<V>::type vec_t;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;                                            // wave-uniform
@@ -85,12 +80,6 @@ __global__ __launch_bounds__(256) void iw_logweight_kernel(
     }
 }
 
-__device__ __forceinline__ float iw_wave_max_all(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // One wavefront per image over its K log-weights (K arbitrary: the lanes stride over them, passes re-read them from cache).
 __global__ __launch_bounds__(256) void iw_reduce_kernel(const float *__restrict__ logw, const int *__restrict__ n, int K, int B,
                                                         int T, float *__restrict__ iw_bound, float *__restrict__ elbo,
@@ -106,7 +95,7 @@ __global__ __launch_bounds__(256) void iw_reduce_kernel(const float *__restrict_
         m = fmaxf(m, v);
         sum += v;
     }
-    m = iw_wave_max_all(m);
+    m = wave_max_all(m);
     sum = wave_sum_all(sum);
     const float shift = isinf(m) ? 0.f : m;                        // (all weights zero / one infinite: the usual logsumexp convention)
     float s1 = 0.f, s2 = 0.f;

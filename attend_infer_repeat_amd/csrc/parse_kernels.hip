@@ -21,14 +21,9 @@
 // (st_device.h: axis_entry2, load_taps_pad, bilerp; air_common.h: grid_coord, lin_m11; contraction off), so its canvas is
 // bit-identical to air_canvas_unroll_fwd's for the same presences.
 #include <math.h>
-#include "st_device.h"
+#include "scene_device.h"
 
 #define PARSE_MAXT 32
-
-template <int V> struct ParseVec;
-template <> struct ParseVec<4> { typedef float4 type; };
-template <> struct ParseVec<2> { typedef float2 type; };
-template <> struct ParseVec<1> { typedef float type; };
 
 // ============================================================================================================
 // objects
@@ -122,7 +117,7 @@ __global__ __launch_bounds__(256) void parse_scatter_kernel(const int *__restric
                                                             int R, int A, int *__restrict__ obj_image, int *__restrict__ obj_step,
                                                             float *__restrict__ obj_box, float *__restrict__ obj_score,
                                                             float *__restrict__ obj_where, float *__restrict__ obj_what) {
-    typedef typename ParseVec<V>::type vec_t;
+    typedef typename VecOf<V>::type vec_t;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;                                            // wave-uniform
@@ -176,27 +171,8 @@ extern "C" int air_parse_objects(const float *presence_prob, const int *num_obje
 // ============================================================================================================
 // render
 // ============================================================================================================
-struct CarvePr {
-    float *glm, *pres, *scratch;
-    float2 *xe, *ye;                 // per (t, column) / (t, band row): {floor index as int bits | ST_INVALID, d}
-    int *cnt;                        // pixels owned per step, this workgroup's band
-    int hwp;
-};
-__device__ __forceinline__ CarvePr carve_pr(float *smem, int T, int RB, int W, int h, int w) {
-    CarvePr c;
-    c.hwp = pad_count(h, w);
-    float *p = smem;
-    c.glm = p; p += (size_t)T * c.hwp;
-    c.xe = reinterpret_cast<float2 *>(p); p += 2 * T * W;
-    c.ye = reinterpret_cast<float2 *>(p); p += 2 * T * RB;
-    c.pres = p; p += PARSE_MAXT;
-    c.cnt = reinterpret_cast<int *>(p); p += PARSE_MAXT;
-    c.scratch = p;
-    return c;
-}
-static inline size_t carve_pr_bytes(int T, int RB, int W, int h, int w) {
-    return sizeof(float) * ((size_t)T * pad_count_host(h, w) + 2 * (size_t)T * (W + RB) + 2 * PARSE_MAXT + 32);
-}
+// behind the common head of the carve: the presence row, the pixels owned per step in this workgroup's band, block_sum's scratch
+#define PARSE_TAIL_FLOATS (2 * PARSE_MAXT + 32)
 struct ParseRenderArgs {
     const float *glimpse, *where, *presence, *obs;
     float *reconstruction, *rec_parts, *layers;
@@ -222,20 +198,17 @@ __global__ __launch_bounds__(1024) void parse_render_kernel(ParseRenderArgs a) {
     signed char *__restrict__ owner = a.owner;
     const int T = a.T, B = a.B, NB = a.NB, RB = a.RB, H = a.H, W = a.W, h = a.h, w = a.w;
     const float mult = a.mult, std = a.std, thr = a.thr;
-    const int HW = H * W, hw = h * w, tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
-    CarvePr c = carve_pr(smem, T, RB, W, h, w);
-    const float cxs = (float)((w - 1) / 2.0), cys = (float)((h - 1) / 2.0);
+    const int HW = H * W, tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
+    const BandCarve c = band_carve(smem, T, RB, W, h, w);
+    float *pres = c.tail, *scratch = c.tail + 2 * PARSE_MAXT;
+    int *cnt = reinterpret_cast<int *>(c.tail + PARSE_MAXT);
     const float cst = 0.5f * logf(6.283185307179586f) + logf(std);
     const int n_units = B * NB;
     const int pitch = w + 2;
-    const float inv_w = 1.0f / (float)w, inv_W = 1.0f / (float)W;
+    const float inv_W = 1.0f / (float)W;
     const bool owner_al4 = (reinterpret_cast<uintptr_t>(owner) & 3u) == 0;
     AIR_TR_INIT();
-    // the zero borders of the T bordered glimpses: written once, never overwritten (visible after the first barrier below)
-    for (int e = tid; e < T * pad_border(h, w); e += nt) {
-        const int t = e / pad_border(h, w);
-        c.glm[(size_t)t * c.hwp + pad_border_index(e - t * pad_border(h, w), h, w)] = 0.f;
-    }
+    band_zero_borders(c, T, h, w, tid, nt);                        // written once (visible after the first barrier below)
     for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
         const int b = unit % B, band = unit / B;
         const int r0 = band * RB, r1 = (r0 + RB < H) ? r0 + RB : H, npx = (r1 - r0) * W, pbase = r0 * W;
@@ -246,56 +219,27 @@ __global__ __launch_bounds__(1024) void parse_render_kernel(ParseRenderArgs a) {
         const int ob_last = rec_parts ? npx - 1 : 0;
         float xo[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {                              // unconditional loads from clamped addresses (no branches)
-            const int p = tid + u * nt;
-            xo[u] = ob[p < ob_last ? p : ob_last];
-        }
+        for (int u = 0; u < 4; ++u) xo[u] = band_prefetch_obs(ob, ob_last, tid + u * nt);
         if (unit != (int)blockIdx.x) __syncthreads();              // grid-stride reuse of the carve
-        if (a.vec4_glimpse) {                                      // (w % 4 == 0: a 16-byte group never straddles a glimpse row)
-            const int nq = hw >> 2;
-            for (int e = tid; e < T * nq; e += nt) {
-                const int t = e / nq, q = e - t * nq;
-                const float4 v = reinterpret_cast<const float4 *>(glimpse + ((size_t)t * B + b) * hw)[q];
-                float *d = c.glm + (size_t)t * c.hwp + pad_index(4 * q, w, inv_w);
-                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-            }
-        } else {
-            for (int e = tid; e < T * hw; e += nt) {
-                const int t = e / hw, q = e - t * hw;
-                c.glm[(size_t)t * c.hwp + pad_index(q, w, inv_w)] = glimpse[((size_t)t * B + b) * hw + q];
-            }
-        }
-        const int nrow = r1 - r0;
-        for (int k = tid; k < T * (W + nrow); k += nt) {
-            const int t = k / (W + nrow), r = k - t * (W + nrow);
-            const float4 wk = *reinterpret_cast<const float4 *>(where + 4 * ((size_t)t * B + b));      // [sx, tx, sy, ty]
-            if (r < W) {
-                c.xe[t * W + r] = axis_entry2(grid_coord(1.0f / wk.x, lin_m11(r, W, a.stepX), -wk.y / wk.x, cxs), w);
-            } else {
-                const int i = r - W;
-                c.ye[t * RB + i] = axis_entry2(grid_coord(1.0f / wk.z, lin_m11(r0 + i, H, a.stepY), -wk.w / wk.z, cys), h);
-            }
-        }
+        band_stage_glimpses(c, glimpse, a.vec4_glimpse != 0, T, B, b, h, w, tid, nt);
+        band_axis_tables(c, where, T, B, b, RB, H, W, h, w, r0, r1 - r0, a.stepX, a.stepY, tid, nt);
         if (tid < T) {
-            c.pres[tid] = presence[(size_t)tid * B + b];
-            c.cnt[tid] = 0;
+            pres[tid] = presence[(size_t)tid * B + b];
+            cnt[tid] = 0;
         }
         AIR_TR(1);
         __syncthreads();
         AIR_TR(2);
         const bool pack_ok = owner_al4 && (gbase & 3u) == 0;       // wave-uniform: quads of adjacent lanes start on a 4-byte boundary
         unsigned pmask = 0u;                                       // present steps, wave-uniform: read once per unit, not per pixel
-        for (int t = 0; t < T; ++t) pmask |= (c.pres[t] > 0.5f ? 1u : 0u) << t;
+        for (int t = 0; t < T; ++t) pmask |= (pres[t] > 0.5f ? 1u : 0u) << t;
         float s[1] = {0.f};
         int mine = 0;                                              // lane t: pixels step t owns among this wave's
         for (int base = 0; base < npx; base += 4 * nt) {           // (uniform trip count: ballots and shuffles inside)
             float xn[4] = {0.f, 0.f, 0.f, 0.f};
             if (base + 4 * nt < npx) {                             // next chunk's observations (bands above 4 pixels per thread)
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int p = base + tid + (4 + u) * nt;
-                    xn[u] = ob[p < ob_last ? p : ob_last];
-                }
+                for (int u = 0; u < 4; ++u) xn[u] = band_prefetch_obs(ob, ob_last, base + tid + (4 + u) * nt);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -350,15 +294,15 @@ __global__ __launch_bounds__(1024) void parse_render_kernel(ParseRenderArgs a) {
             for (int u = 0; u < 4; ++u) xo[u] = xn[u];
         }
         AIR_TR(3);
-        if (lane < T && mine) atomicAdd(&c.cnt[lane], mine);       // LDS, integers: the order does not matter
+        if (lane < T && mine) atomicAdd(&cnt[lane], mine);       // LDS, integers: the order does not matter
         if (rec_parts) {
-            block_sum<1>(s, c.scratch);                            // (its barrier also covers the counts)
+            block_sum<1>(s, scratch);                              // (its barrier also covers the counts)
             if (tid == 0) rec_parts[(size_t)band * B + b] = s[0];
         } else {
             __syncthreads();
         }
         if (tid < T) {
-            const int k = c.cnt[tid];
+            const int k = cnt[tid];
             if (k) atomicAdd(&a.area[(size_t)tid * B + b], k);
         }
         AIR_TR(4);
@@ -377,7 +321,7 @@ extern "C" int air_parse_render(const float *glimpse, const float *where, const 
     int NB, RB;
     wr_bands(H, n_bands, &NB, &RB);
     AIR_REQUIRE(NB == n_bands || !rec_parts, AIR_E_SHAPE);       // the caller sized rec_parts for exactly n_bands shares
-    const size_t lds = carve_pr_bytes(T, RB, W, h, w);
+    const size_t lds = sizeof(float) * (band_carve_floats(T, RB, W, h, w) + PARSE_TAIL_FLOATS);
     AIR_REQUIRE(lds <= CV_MAX_LDS, AIR_E_UNSUPPORTED);
     { int st_ = cv_allow_lds(parse_render_kernel, lds); if (st_) return st_; }
     hipError_t e = hipMemsetAsync(area, 0, sizeof(int) * (size_t)T * R, air_stream(stream));
@@ -393,6 +337,36 @@ extern "C" int air_parse_render(const float *glimpse, const float *where, const 
                                lin_step(W), lin_step(H), mult, std, mask_threshold, (w % 4 == 0) && air_aligned16(glimpse)};
     const int cap = units > 256 * 8 ? air_resident_grid(parse_render_kernel, threads, lds, 256 * 8) : 256 * 8;
     hipLaunchKernelGGL(parse_render_kernel, dim3((unsigned)(units < cap ? units : cap)), dim3(threads), lds, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// ============================================================================================================
+// relabel
+// ============================================================================================================
+// One wavefront per image; lane j < n rewrites what air_parse_objects labelled by position (scene_device.h states the rule).
+__global__ __launch_bounds__(256) void parse_relabel_kernel(const float *__restrict__ score_src, const int *__restrict__ ids,
+                                                            const int *__restrict__ n_obj, const int *__restrict__ offsets, int T,
+                                                            int R, float *__restrict__ score, float *__restrict__ obj_score,
+                                                            int *__restrict__ obj_step) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;                                            // wave-uniform
+    int n = n_obj[r];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    if (lane < n) {
+        const size_t src = (size_t)lane * R + r, dst = (size_t)offsets[r] + lane;
+        const float v = score_src[src];
+        score[src] = v;
+        obj_score[dst] = v;
+        obj_step[dst] = ids[src];
+    }
+}
+
+int parse_relabel_launch(const float *score_src, const int *ids, const int *num_objects, const int *offsets, int T, int R,
+                         float *score, float *obj_score, int *obj_step, void *stream) {
+    hipLaunchKernelGGL(parse_relabel_kernel, dim3(air_cdiv(R, 4)), dim3(256), 0, air_stream(stream), score_src, ids, num_objects,
+                       offsets, T, R, score, obj_score, obj_step);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

@@ -5,21 +5,16 @@
 //   air_particle_spread: per step and image the weighted mean / standard deviation of `where` over the particles that have the step.
 // Rows are r = b * K + k: the K particles of an image are adjacent.  No atomics; every sum has one fixed order.
 #include <math.h>
-#include "air_common.h"
+#include "scene_device.h"
 
 #define PP_MAXT 32
-#define PP_HALF_LOG_2PI 0.91893853320467274178f
 
-// log N(x | loc, scale).  No clamps: a zero scale gives the +-inf / NaN of the plain formula.
+// log N(x | loc, scale) of a per-element scale: scene_device.h's log_normal with the logarithm taken behind the division.  It stays
+// here: with logf(scale) formed at the call site the compiler moves the logarithm in front of the division and the kernel's code changes.
 __device__ __forceinline__ float pp_log_normal(float x, float loc, float scale) {
     const float z = (x - loc) / scale;
-    return -0.5f * (z * z) - logf(scale) - PP_HALF_LOG_2PI;
+    return -0.5f * (z * z) - logf(scale) - HALF_LOG_2PI;
 }
-
-template <int V> struct PpVec;
-template <> struct PpVec<4> { typedef float4 type; };
-template <> struct PpVec<2> { typedef float2 type; };
-template <> struct PpVec<1> { typedef float type; };
 
 // One wavefront per row, the lane layout of iw_logweight_kernel: the steps that count are t < n = the number of leading ones
 // of the presence chain; their A-wide `what` rows are spread over the lanes as n * A / V vectors of V floats, lane t < n takes
@@ -29,7 +24,7 @@ __global__ __launch_bounds__(256) void iw_logposterior_kernel(
     const float *__restrict__ what, const float *__restrict__ what_loc, const float *__restrict__ what_scale,
     const float *__restrict__ where, const float *__restrict__ where_loc, const float *__restrict__ where_scale,
     const float *__restrict__ presence, const float *__restrict__ logp, int T, int R, int A, float *__restrict__ log_q) {
-    typedef typename PpVec<V>::type vec_t;
+    typedef typename VecOf<V>::type vec_t;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;                                            // wave-uniform
@@ -97,18 +92,6 @@ __global__ __launch_bounds__(256) void particle_argmax_kernel(const float *__res
     }
 }
 
-__device__ __forceinline__ void pp_copy_row(const float *__restrict__ src, float *__restrict__ dst, int n, bool vec, int lane) {
-    if (vec) {                                                     // 16-byte vectors: n % 4 == 0 and both rows start aligned
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        for (int i = lane; i < n / 4; i += 64) d4[i] = s4[i];
-    } else {
-        const unsigned *s1 = reinterpret_cast<const unsigned *>(src);
-        unsigned *d1 = reinterpret_cast<unsigned *>(dst);
-        for (int i = lane; i < n; i += 64) d1[i] = s1[i];
-    }
-}
-
 // One wavefront per (step, image): the selected particle's row t * R + b * K + k* goes to row t * B + b.  Bit copies.
 __global__ __launch_bounds__(256) void particle_gather_kernel(const int *__restrict__ best_particle, const float *__restrict__ where,
                                                               const float *__restrict__ what, const float *__restrict__ presence_prob,
@@ -124,19 +107,8 @@ __global__ __launch_bounds__(256) void particle_gather_kernel(const int *__restr
     const size_t src = (size_t)t * B * K + (size_t)b * K + ks, dst = (size_t)row;
     if (lane < 4) reinterpret_cast<unsigned *>(where_sel)[dst * 4 + lane] = reinterpret_cast<const unsigned *>(where)[src * 4 + lane];
     if (lane == 4) reinterpret_cast<unsigned *>(presence_prob_sel)[dst] = reinterpret_cast<const unsigned *>(presence_prob)[src];
-    pp_copy_row(what + src * A, what_sel + dst * A, A, what_vec != 0, lane);
-    pp_copy_row(glimpse + src * G, glimpse_sel + dst * G, G, glimpse_vec != 0, lane);
-}
-
-__device__ __forceinline__ double pp_wave_sum_all(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;  // valid in every lane
-}
-__device__ __forceinline__ float pp_wave_max_all(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
+    copy_row_bits(what + src * A, what_sel + dst * A, A, what_vec != 0, lane);
+    copy_row_bits(glimpse + src * G, glimpse_sel + dst * G, G, glimpse_vec != 0, lane);
 }
 
 // One wavefront per image; float64, two passes per step (mean, then the spread about it).  The weights exp(log w - max) are formed
@@ -153,10 +125,10 @@ __global__ __launch_bounds__(256) void particle_spread_kernel(const float *__res
     const int *nk = num_steps + base;
     float mf = -INFINITY;
     for (int k = lane; k < K; k += 64) mf = fmaxf(mf, lw[k]);
-    const double m = (double)pp_wave_max_all(mf);
+    const double m = (double)wave_max_all(mf);
     double total = 0.0;
     for (int k = lane; k < K; k += 64) total += exp((double)lw[k] - m);
-    total = pp_wave_sum_all(total);
+    total = wave_sum_all(total);
     for (int t = 0; t < T; ++t) {
         double W = 0.0, a[4] = {0.0, 0.0, 0.0, 0.0};
         for (int k = lane; k < K; k += 64) {
@@ -167,10 +139,10 @@ __global__ __launch_bounds__(256) void particle_spread_kernel(const float *__res
                 a[0] += w * (double)x.x; a[1] += w * (double)x.y; a[2] += w * (double)x.z; a[3] += w * (double)x.w;
             }
         }
-        W = pp_wave_sum_all(W);
+        W = wave_sum_all(W);
         double mean[4], v[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) mean[j] = pp_wave_sum_all(a[j]) / W;
+        for (int j = 0; j < 4; ++j) mean[j] = wave_sum_all(a[j]) / W;
         for (int k = lane; k < K; k += 64) {
             if (nk[k] > t) {
                 const double w = exp((double)lw[k] - m);
@@ -182,7 +154,7 @@ __global__ __launch_bounds__(256) void particle_spread_kernel(const float *__res
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const double q = pp_wave_sum_all(v[j]) / W;
+            const double q = wave_sum_all(v[j]) / W;
             v[j] = sqrt(q < 0.0 ? 0.0 : q);                        // (a NaN stays a NaN: W == 0)
         }
         if (lane == 0) {

@@ -8,35 +8,16 @@
 //   air_propose_source:   the provenance of the compacted rows behind air_prune_select on the pool.
 // No atomics, no cross-workgroup traffic; every sum has one fixed order: the same bits run to run.
 #include <math.h>
-#include "st_device.h"
+#include "scene_device.h"
 
 #define PROPOSE_MAXT 6
 #define PROPOSE_THREADS 256
 
-extern "C" int air_canvas_unroll_bands(int B, int H);
-
 // ============================================================================================================
 // residual
 // ============================================================================================================
-struct CarvePp {
-    float *glm, *pres, *scratch;
-    float2 *xe, *ye;                 // per (t, column) / (t, band row): {floor index as int bits | ST_INVALID, d}
-    int hwp;
-};
-__device__ __forceinline__ CarvePp carve_pp(float *smem, int T, int RB, int W, int h, int w) {
-    CarvePp c;
-    c.hwp = pad_count(h, w);
-    float *p = smem;
-    c.glm = p; p += (size_t)T * c.hwp;
-    c.xe = reinterpret_cast<float2 *>(p); p += 2 * T * W;
-    c.ye = reinterpret_cast<float2 *>(p); p += 2 * T * RB;
-    c.pres = p; p += 8;
-    c.scratch = p;                   // PROPOSE_THREADS / 64 wave totals
-    return c;
-}
-static inline size_t carve_pp_bytes(int T, int RB, int W, int h, int w) {
-    return sizeof(float) * ((size_t)T * pad_count_host(h, w) + 2 * (size_t)T * (W + RB) + 8 + PROPOSE_THREADS / 64);
-}
+// behind the common head of the carve: the presence row (8 floats), then PROPOSE_THREADS / 64 wave totals
+#define PROPOSE_TAIL_FLOATS (8 + PROPOSE_THREADS / 64)
 struct ProposeResidualArgs {
     const float *glimpse, *where, *presence, *obs;
     const int *n_in;
@@ -58,11 +39,11 @@ __global__ __launch_bounds__(PROPOSE_THREADS) void propose_residual_kernel(Propo
     float *__restrict__ res = a.res;
     const int T = a.T, B = a.B, RB = a.RB, H = a.H, W = a.W, h = a.h, w = a.w;
     const float mult = a.mult, hi = a.clamp_hi;
-    const int HW = H * W, hw = h * w, tid = threadIdx.x, nt = PROPOSE_THREADS, lane = tid & 63, wid = tid >> 6;
-    CarvePp c = carve_pp(smem, T, RB, W, h, w);
-    const float cxs = (float)((w - 1) / 2.0), cys = (float)((h - 1) / 2.0);
+    const int HW = H * W, tid = threadIdx.x, nt = PROPOSE_THREADS, lane = tid & 63, wid = tid >> 6;
+    const BandCarve c = band_carve(smem, T, RB, W, h, w);
+    float *pres = c.tail, *scratch = c.tail + 8;
     const int pitch = w + 2;
-    const float inv_w = 1.0f / (float)w, inv_W = 1.0f / (float)W;
+    const float inv_W = 1.0f / (float)W;
     const int unit = blockIdx.x;                                   // < B * NB: the grid is exactly the units
     const int b = unit % B, band = unit / B;
     const int r0 = band * RB, r1 = (r0 + RB < H) ? r0 + RB : H, npx = (r1 - r0) * W, pbase = r0 * W;
@@ -72,52 +53,20 @@ __global__ __launch_bounds__(PROPOSE_THREADS) void propose_residual_kernel(Propo
     // ---- every global load of this unit ----------------------------------------------------------------------------------
     float xo[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {                                  // unconditional loads from clamped addresses (no branches)
-        const int p = tid + u * nt;
-        xo[u] = ob[p < ob_last ? p : ob_last];
-    }
-    for (int e = tid; e < T * pad_border(h, w); e += nt) {         // the zero borders of the T bordered glimpses
-        const int t = e / pad_border(h, w);
-        c.glm[(size_t)t * c.hwp + pad_border_index(e - t * pad_border(h, w), h, w)] = 0.f;
-    }
-    if (a.vec4_glimpse) {                                          // (w % 4 == 0: a 16-byte group never straddles a glimpse row)
-        const int nq = hw >> 2;
-        for (int e = tid; e < T * nq; e += nt) {
-            const int t = e / nq, q = e - t * nq;
-            const float4 v = reinterpret_cast<const float4 *>(glimpse + ((size_t)t * B + b) * hw)[q];
-            float *d = c.glm + (size_t)t * c.hwp + pad_index(4 * q, w, inv_w);
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-    } else {
-        for (int e = tid; e < T * hw; e += nt) {
-            const int t = e / hw, q = e - t * hw;
-            c.glm[(size_t)t * c.hwp + pad_index(q, w, inv_w)] = glimpse[((size_t)t * B + b) * hw + q];
-        }
-    }
-    const int nrow = r1 - r0;
-    for (int k = tid; k < T * (W + nrow); k += nt) {
-        const int t = k / (W + nrow), r = k - t * (W + nrow);
-        const float4 wk = *reinterpret_cast<const float4 *>(where + 4 * ((size_t)t * B + b));      // [sx, tx, sy, ty]
-        if (r < W) {
-            c.xe[t * W + r] = axis_entry2(grid_coord(1.0f / wk.x, lin_m11(r, W, a.stepX), -wk.y / wk.x, cxs), w);
-        } else {
-            const int i = r - W;
-            c.ye[t * RB + i] = axis_entry2(grid_coord(1.0f / wk.z, lin_m11(r0 + i, H, a.stepY), -wk.w / wk.z, cys), h);
-        }
-    }
-    if (tid < T) c.pres[tid] = a.n_in ? (tid < a.n_in[b] ? 1.f : 0.f) : a.presence[(size_t)tid * B + b];
+    for (int u = 0; u < 4; ++u) xo[u] = band_prefetch_obs(ob, ob_last, tid + u * nt);
+    band_zero_borders(c, T, h, w, tid, nt);
+    band_stage_glimpses(c, glimpse, a.vec4_glimpse != 0, T, B, b, h, w, tid, nt);
+    band_axis_tables(c, where, T, B, b, RB, H, W, h, w, r0, r1 - r0, a.stepX, a.stepY, tid, nt);
+    if (tid < T) pres[tid] = a.n_in ? (tid < a.n_in[b] ? 1.f : 0.f) : a.presence[(size_t)tid * B + b];
     __syncthreads();
     int nb = 0;                                                    // leading ones: workgroup-uniform
-    while (nb < T && c.pres[nb] > 0.5f) ++nb;
+    while (nb < T && pres[nb] > 0.5f) ++nb;
     float s = 0.f;
     for (int base = 0; base < npx; base += 4 * nt) {
         float xn[4] = {0.f, 0.f, 0.f, 0.f};
         if (base + 4 * nt < npx) {                                 // next chunk's observations (bands above 4 pixels per thread)
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int p = base + tid + (4 + u) * nt;
-                xn[u] = ob[p < ob_last ? p : ob_last];
-            }
+            for (int u = 0; u < 4; ++u) xn[u] = band_prefetch_obs(ob, ob_last, base + tid + (4 + u) * nt);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -144,12 +93,12 @@ __global__ __launch_bounds__(PROPOSE_THREADS) void propose_residual_kernel(Propo
     }
     if (a.res_parts) {                                             // (uniform)
         const float tot = wave_sum_all(s);
-        if (lane == 0) c.scratch[wid] = tot;
+        if (lane == 0) scratch[wid] = tot;
         __syncthreads();
         if (tid == 0) {
             float e = 0.f;
 #pragma unroll
-            for (int k = 0; k < PROPOSE_THREADS / 64; ++k) e += c.scratch[k];
+            for (int k = 0; k < PROPOSE_THREADS / 64; ++k) e += scratch[k];
             a.res_parts[(size_t)band * B + b] = e;
         }
     }
@@ -160,18 +109,12 @@ extern "C" int air_propose_residual(const float *glimpse, const float *where, co
                                     int n_bands, float *res, float *res_parts, void *stream) {
     AIR_REQUIRE(glimpse && where && obs && res && (presence || num_objects_in), AIR_E_NULL);
     AIR_REQUIRE(T > 0 && T <= PROPOSE_MAXT && R > 0 && H > 0 && W > 0 && h > 0 && w > 0 && n_bands > 0, AIR_E_SHAPE);
-    AIR_REQUIRE(n_bands == air_canvas_unroll_bands(R, H), AIR_E_SHAPE);      // the caller sized res_parts for exactly these shares
-    AIR_REQUIRE((long)R * n_bands <= (long)INT_MAX && (long)H * W <= (long)INT_MAX / 2, AIR_E_SHAPE);
-    AIR_REQUIRE(air_aligned16(where), AIR_E_ALIGN);
     const uintptr_t bits = reinterpret_cast<uintptr_t>(glimpse) | reinterpret_cast<uintptr_t>(presence) |
                            reinterpret_cast<uintptr_t>(num_objects_in) | reinterpret_cast<uintptr_t>(obs) |
                            reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(res_parts);
-    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
     int NB, RB;
-    wr_bands(H, n_bands, &NB, &RB);
-    AIR_REQUIRE(NB == n_bands, AIR_E_SHAPE);
-    const size_t lds = carve_pp_bytes(T, RB, W, h, w);
-    AIR_REQUIRE(lds <= CV_MAX_LDS, AIR_E_UNSUPPORTED);
+    size_t lds;                                                    // (n_bands: the caller sized res_parts for exactly these shares)
+    { int st_ = band_launch_prepare(T, R, H, W, h, w, n_bands, where, bits, PROPOSE_TAIL_FLOATS, &NB, &RB, &lds); if (st_) return st_; }
     { int st_ = cv_allow_lds(propose_residual_kernel, lds); if (st_) return st_; }
     const ProposeResidualArgs a = {glimpse, where, presence, obs, num_objects_in, res, res_parts, T, R, NB, RB, H, W, h, w,
                                    lin_step(W), lin_step(H), mult, clamp_hi, (w % 4 == 0) && air_aligned16(glimpse)};
@@ -183,17 +126,6 @@ extern "C" int air_propose_residual(const float *glimpse, const float *where, co
 // ============================================================================================================
 // pool
 // ============================================================================================================
-__device__ __forceinline__ void pp_copy_row(const float *__restrict__ src, float *__restrict__ dst, int n, bool vec, int lane) {
-    if (vec) {                                                     // 16-byte vectors: n % 4 == 0 and both buffers start aligned
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        for (int i = lane; i < n / 4; i += 64) d4[i] = s4[i];
-    } else {
-        const unsigned *s1 = reinterpret_cast<const unsigned *>(src);
-        unsigned *d1 = reinterpret_cast<unsigned *>(dst);
-        for (int i = lane; i < n; i += 64) d1[i] = s1[i];
-    }
-}
 
 struct ProposePoolArgs {
     const float *what, *where, *glimpse, *score, *presence;       // the current rows [T, R, .]
@@ -234,8 +166,8 @@ __global__ __launch_bounds__(256) void propose_pool_kernel(ProposePoolArgs a) {
         const float *wh = cur ? a.where : a.p_where, *sc = cur ? a.score : a.p_score;
         if (lane < 4) reinterpret_cast<unsigned *>(a.pool_where)[to * 4 + lane] = reinterpret_cast<const unsigned *>(wh)[from * 4 + lane];
         if (lane == 4) reinterpret_cast<unsigned *>(a.pool_score)[to] = reinterpret_cast<const unsigned *>(sc)[from];
-        pp_copy_row((cur ? a.what : a.p_what) + from * A, a.pool_what + to * A, A, a.what_vec != 0, lane);
-        pp_copy_row((cur ? a.glimpse : a.p_glimpse) + from * G, a.pool_glimpse + to * G, G, a.glimpse_vec != 0, lane);
+        copy_row_bits((cur ? a.what : a.p_what) + from * A, a.pool_what + to * A, A, a.what_vec != 0, lane);
+        copy_row_bits((cur ? a.glimpse : a.p_glimpse) + from * G, a.pool_glimpse + to * G, G, a.glimpse_vec != 0, lane);
     }
 }
 

@@ -7,36 +7,16 @@
 //   air_prune_relabel: score / obj_score / obj_step of the kept rows behind air_parse_objects, which labels rows by position.
 // No atomics, no cross-workgroup traffic; every sum has one fixed order: the same bits run to run.
 #include <math.h>
-#include "st_device.h"
+#include "scene_device.h"
 
 #define PRUNE_MAXT 6
 #define PRUNE_THREADS 256
-#define PRUNE_HALF_LOG_2PI 0.91893853320467274178f
-
-extern "C" int air_canvas_unroll_bands(int B, int H);
 
 // ============================================================================================================
 // score
 // ============================================================================================================
-struct CarvePn {
-    float *glm, *pres, *scratch;
-    float2 *xe, *ye;                 // per (t, column) / (t, band row): {floor index as int bits | ST_INVALID, d}
-    int hwp;
-};
-__device__ __forceinline__ CarvePn carve_pn(float *smem, int T, int RB, int W, int h, int w) {
-    CarvePn c;
-    c.hwp = pad_count(h, w);
-    float *p = smem;
-    c.glm = p; p += (size_t)T * c.hwp;
-    c.xe = reinterpret_cast<float2 *>(p); p += 2 * T * W;
-    c.ye = reinterpret_cast<float2 *>(p); p += 2 * T * RB;
-    c.pres = p; p += 8;
-    c.scratch = p;                   // (PRUNE_THREADS / 64) * 2^T wave totals
-    return c;
-}
-static inline size_t carve_pn_bytes(int T, int RB, int W, int h, int w) {
-    return sizeof(float) * ((size_t)T * pad_count_host(h, w) + 2 * (size_t)T * (W + RB) + 8 + (size_t)(PRUNE_THREADS / 64) * (1u << T));
-}
+// behind the common head of the carve: the presence row (8 floats), then (PRUNE_THREADS / 64) * 2^T wave totals
+static inline size_t prune_tail_floats(int T) { return 8 + (size_t)(PRUNE_THREADS / 64) * (1u << T); }
 struct PruneScoreArgs {
     const float *glimpse, *where, *presence, *obs;
     float *rec_sub;
@@ -93,12 +73,12 @@ __global__ __launch_bounds__(PRUNE_THREADS) void prune_score_kernel(PruneScoreAr
     const float *__restrict__ obs = a.obs;
     const int B = a.B, RB = a.RB, H = a.H, W = a.W, h = a.h, w = a.w;
     const float mult = a.mult, std = a.std;
-    const int HW = H * W, hw = h * w, tid = threadIdx.x, nt = PRUNE_THREADS, lane = tid & 63, wid = tid >> 6;
-    CarvePn c = carve_pn(smem, T, RB, W, h, w);
-    const float cxs = (float)((w - 1) / 2.0), cys = (float)((h - 1) / 2.0);
+    const int HW = H * W, tid = threadIdx.x, nt = PRUNE_THREADS, lane = tid & 63, wid = tid >> 6;
+    const BandCarve c = band_carve(smem, T, RB, W, h, w);
+    float *pres = c.tail, *scratch = c.tail + 8;
     const float cst = 0.5f * logf(6.283185307179586f) + logf(std);
     const int pitch = w + 2;
-    const float inv_w = 1.0f / (float)w, inv_W = 1.0f / (float)W;
+    const float inv_W = 1.0f / (float)W;
     const int unit = blockIdx.x;                                   // < B * NB: the grid is exactly the units
     const int b = unit % B, band = unit / B;
     const int r0 = band * RB, r1 = (r0 + RB < H) ? r0 + RB : H, npx = (r1 - r0) * W, pbase = r0 * W;
@@ -107,45 +87,16 @@ __global__ __launch_bounds__(PRUNE_THREADS) void prune_score_kernel(PruneScoreAr
     // ---- every global load of this unit ----------------------------------------------------------------------------------
     float xo[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {                                  // unconditional loads from clamped addresses (no branches)
-        const int p = tid + u * nt;
-        xo[u] = ob[p < ob_last ? p : ob_last];
-    }
-    for (int e = tid; e < T * pad_border(h, w); e += nt) {         // the zero borders of the T bordered glimpses
-        const int t = e / pad_border(h, w);
-        c.glm[(size_t)t * c.hwp + pad_border_index(e - t * pad_border(h, w), h, w)] = 0.f;
-    }
-    if (a.vec4_glimpse) {                                          // (w % 4 == 0: a 16-byte group never straddles a glimpse row)
-        const int nq = hw >> 2;
-        for (int e = tid; e < T * nq; e += nt) {
-            const int t = e / nq, q = e - t * nq;
-            const float4 v = reinterpret_cast<const float4 *>(glimpse + ((size_t)t * B + b) * hw)[q];
-            float *d = c.glm + (size_t)t * c.hwp + pad_index(4 * q, w, inv_w);
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-    } else {
-        for (int e = tid; e < T * hw; e += nt) {
-            const int t = e / hw, q = e - t * hw;
-            c.glm[(size_t)t * c.hwp + pad_index(q, w, inv_w)] = glimpse[((size_t)t * B + b) * hw + q];
-        }
-    }
-    const int nrow = r1 - r0;
-    for (int k = tid; k < T * (W + nrow); k += nt) {
-        const int t = k / (W + nrow), r = k - t * (W + nrow);
-        const float4 wk = *reinterpret_cast<const float4 *>(where + 4 * ((size_t)t * B + b));      // [sx, tx, sy, ty]
-        if (r < W) {
-            c.xe[t * W + r] = axis_entry2(grid_coord(1.0f / wk.x, lin_m11(r, W, a.stepX), -wk.y / wk.x, cxs), w);
-        } else {
-            const int i = r - W;
-            c.ye[t * RB + i] = axis_entry2(grid_coord(1.0f / wk.z, lin_m11(r0 + i, H, a.stepY), -wk.w / wk.z, cys), h);
-        }
-    }
-    if (tid < T) c.pres[tid] = presence[(size_t)tid * B + b];
+    for (int u = 0; u < 4; ++u) xo[u] = band_prefetch_obs(ob, ob_last, tid + u * nt);
+    band_zero_borders(c, T, h, w, tid, nt);
+    band_stage_glimpses(c, glimpse, a.vec4_glimpse != 0, T, B, b, h, w, tid, nt);
+    band_axis_tables(c, where, T, B, b, RB, H, W, h, w, r0, r1 - r0, a.stepX, a.stepY, tid, nt);
+    if (tid < T) pres[tid] = presence[(size_t)tid * B + b];
     __syncthreads();
     int cb = T;                                                    // candidates: workgroup-uniform
     if (!a.all_candidates) {
         cb = 0;
-        while (cb < T && c.pres[cb] > 0.5f) ++cb;                  // leading ones
+        while (cb < T && pres[cb] > 0.5f) ++cb;                  // leading ones
     }
     float s[NM];
 #pragma unroll
@@ -154,10 +105,7 @@ __global__ __launch_bounds__(PRUNE_THREADS) void prune_score_kernel(PruneScoreAr
         float xn[4] = {0.f, 0.f, 0.f, 0.f};
         if (base + 4 * nt < npx) {                                 // next chunk's observations (bands above 4 pixels per thread)
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int p = base + tid + (4 + u) * nt;
-                xn[u] = ob[p < ob_last ? p : ob_last];
-            }
+            for (int u = 0; u < 4; ++u) xn[u] = band_prefetch_obs(ob, ob_last, base + tid + (4 + u) * nt);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -180,12 +128,12 @@ __global__ __launch_bounds__(PRUNE_THREADS) void prune_score_kernel(PruneScoreAr
 #pragma unroll
         for (int u = 0; u < 4; ++u) xo[u] = xn[u];
     }
-    PruneMasks<T, 0>::fold(s, c.scratch, wid, lane);
+    PruneMasks<T, 0>::fold(s, scratch, wid, lane);
     __syncthreads();
     if (tid < (1 << cb)) {                                         // only the masks over the candidates are written
         float tot = 0.f;
 #pragma unroll
-        for (int k = 0; k < PRUNE_THREADS / 64; ++k) tot += c.scratch[k * NM + tid];
+        for (int k = 0; k < PRUNE_THREADS / 64; ++k) tot += scratch[k * NM + tid];
         a.rec_sub[((size_t)band * B + b) * NM + tid] = tot;
     }
 }
@@ -195,17 +143,11 @@ extern "C" int air_prune_score(const float *glimpse, const float *where, const f
                                float *rec_sub, void *stream) {
     AIR_REQUIRE(glimpse && where && presence && obs && rec_sub, AIR_E_NULL);
     AIR_REQUIRE(T > 0 && T <= PRUNE_MAXT && R > 0 && H > 0 && W > 0 && h > 0 && w > 0 && n_bands > 0, AIR_E_SHAPE);
-    AIR_REQUIRE(n_bands == air_canvas_unroll_bands(R, H), AIR_E_SHAPE);      // the caller sized rec_sub for exactly these shares
-    AIR_REQUIRE((long)R * n_bands <= (long)INT_MAX && (long)H * W <= (long)INT_MAX / 2, AIR_E_SHAPE);
-    AIR_REQUIRE(air_aligned16(where), AIR_E_ALIGN);
     const uintptr_t bits = reinterpret_cast<uintptr_t>(glimpse) | reinterpret_cast<uintptr_t>(presence) |
                            reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(rec_sub);
-    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
     int NB, RB;
-    wr_bands(H, n_bands, &NB, &RB);
-    AIR_REQUIRE(NB == n_bands, AIR_E_SHAPE);
-    const size_t lds = carve_pn_bytes(T, RB, W, h, w);
-    AIR_REQUIRE(lds <= CV_MAX_LDS, AIR_E_UNSUPPORTED);
+    size_t lds;                                                    // (n_bands: the caller sized rec_sub for exactly these shares)
+    { int st_ = band_launch_prepare(T, R, H, W, h, w, n_bands, where, bits, prune_tail_floats(T), &NB, &RB, &lds); if (st_) return st_; }
     const PruneScoreArgs a = {glimpse, where, presence, obs, rec_sub, R, NB, RB, H, W, h, w, lin_step(W), lin_step(H), mult, std,
                               all_candidates != 0, (w % 4 == 0) && air_aligned16(glimpse)};
     const dim3 grid((unsigned)((long)R * NB)), block(PRUNE_THREADS);
@@ -229,27 +171,6 @@ extern "C" int air_prune_score(const float *glimpse, const float *where, const f
 struct PrunePriors {
     float what_loc, what_scale, scale_loc, scale_scale, shift_loc, shift_scale;   // shift_loc NaN: centred on where_loc
 };
-// log N(x | loc, scale).  No clamps: a zero scale gives the +-inf / NaN of the plain formula.
-__device__ __forceinline__ float pn_log_normal(float x, float loc, float scale, float log_scale) {
-    const float z = (x - loc) / scale;
-    return -0.5f * (z * z) - log_scale - PRUNE_HALF_LOG_2PI;
-}
-template <int V> struct PnVec;
-template <> struct PnVec<4> { typedef float4 type; };
-template <> struct PnVec<2> { typedef float2 type; };
-template <> struct PnVec<1> { typedef float type; };
-
-__device__ __forceinline__ void pn_copy_row(const float *__restrict__ src, float *__restrict__ dst, int n, bool vec, int lane) {
-    if (vec) {                                                     // 16-byte vectors: n % 4 == 0 and both buffers start aligned
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        for (int i = lane; i < n / 4; i += 64) d4[i] = s4[i];
-    } else {
-        const unsigned *s1 = reinterpret_cast<const unsigned *>(src);
-        unsigned *d1 = reinterpret_cast<unsigned *>(dst);
-        for (int i = lane; i < n; i += 64) d1[i] = s1[i];
-    }
-}
 
 struct PruneSelectArgs {
     const float *what, *where, *glimpse, *score, *presence, *where_loc, *rec_sub;
@@ -269,7 +190,7 @@ struct PruneSelectArgs {
 // ends with the same mask: what the sequential visit with its strict comparison gives.
 template <int V>
 __global__ __launch_bounds__(256) void prune_select_kernel(PruneSelectArgs a) {
-    typedef typename PnVec<V>::type vec_t;
+    typedef typename VecOf<V>::type vec_t;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int T = a.T, R = a.R, A = a.A, G = a.G;
@@ -297,7 +218,7 @@ __global__ __launch_bounds__(256) void prune_select_kernel(PruneSelectArgs a) {
                 const vec_t x = *reinterpret_cast<const vec_t *>(a.what + row * A + (size_t)i * V);
                 const float *xf = reinterpret_cast<const float *>(&x);
 #pragma unroll
-                for (int v = 0; v < V; ++v) s += pn_log_normal(xf[v], pr.what_loc, pr.what_scale, log_pw);
+                for (int v = 0; v < V; ++v) s += log_normal(xf[v], pr.what_loc, pr.what_scale, log_pw);
             }
             if (lane == 0) {
                 const float4 x = *reinterpret_cast<const float4 *>(a.where + row * 4);
@@ -306,10 +227,10 @@ __global__ __launch_bounds__(256) void prune_select_kernel(PruneSelectArgs a) {
                     const float4 l = *reinterpret_cast<const float4 *>(a.where_loc + row * 4);
                     ly = l.y; lw = l.w;
                 }
-                s += pn_log_normal(x.x, pr.scale_loc, pr.scale_scale, log_ps);
-                s += pn_log_normal(x.y, ly, pr.shift_scale, log_ph);
-                s += pn_log_normal(x.z, pr.scale_loc, pr.scale_scale, log_ps);
-                s += pn_log_normal(x.w, lw, pr.shift_scale, log_ph);
+                s += log_normal(x.x, pr.scale_loc, pr.scale_scale, log_ps);
+                s += log_normal(x.y, ly, pr.shift_scale, log_ph);
+                s += log_normal(x.z, pr.scale_loc, pr.scale_scale, log_ps);
+                s += log_normal(x.w, lw, pr.shift_scale, log_ph);
             }
             lp[t] = (double)wave_sum_all(s);
         }
@@ -379,8 +300,8 @@ __global__ __launch_bounds__(256) void prune_select_kernel(PruneSelectArgs a) {
         const size_t from = (size_t)t * R + r, to = (size_t)j * R + r;
         if (lane < 4) reinterpret_cast<unsigned *>(a.where_out)[to * 4 + lane] = reinterpret_cast<const unsigned *>(a.where)[from * 4 + lane];
         if (lane == 4) reinterpret_cast<unsigned *>(a.score_out)[to] = reinterpret_cast<const unsigned *>(a.score)[from];
-        pn_copy_row(a.what + from * A, a.what_out + to * A, A, a.what_vec != 0, lane);
-        pn_copy_row(a.glimpse + from * G, a.glimpse_out + to * G, G, a.glimpse_vec != 0, lane);
+        copy_row_bits(a.what + from * A, a.what_out + to * A, A, a.what_vec != 0, lane);
+        copy_row_bits(a.glimpse + from * G, a.glimpse_out + to * G, G, a.glimpse_vec != 0, lane);
     }
 }
 
@@ -426,25 +347,7 @@ extern "C" int air_prune_select(const float *what, const float *where, const flo
 // ============================================================================================================
 // relabel
 // ============================================================================================================
-// One wavefront per image; lane j < n' rewrites what air_parse_objects labelled by position.
-__global__ __launch_bounds__(256) void prune_relabel_kernel(const float *__restrict__ score_src, const int *__restrict__ kept_step,
-                                                            const int *__restrict__ n_obj, const int *__restrict__ offsets, int T,
-                                                            int R, float *__restrict__ score, float *__restrict__ obj_score,
-                                                            int *__restrict__ obj_step) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;                                            // wave-uniform
-    int n = n_obj[r];
-    n = n < 0 ? 0 : (n > T ? T : n);
-    if (lane < n) {
-        const size_t src = (size_t)lane * R + r, dst = (size_t)offsets[r] + lane;
-        const float v = score_src[src];
-        score[src] = v;
-        obj_score[dst] = v;
-        obj_step[dst] = kept_step[src];
-    }
-}
-
+// The kernel is parse_relabel_kernel (parse_kernels.hip); this entry stops at the steps subset pruning enumerates.
 extern "C" int air_prune_relabel(const float *score_src, const int *kept_step, const int *num_objects, const int *offsets, int T,
                                  int R, float *score, float *obj_score, int *obj_step, void *stream) {
     AIR_REQUIRE(score_src && kept_step && num_objects && offsets && score && obj_score && obj_step, AIR_E_NULL);
@@ -453,8 +356,5 @@ extern "C" int air_prune_relabel(const float *score_src, const int *kept_step, c
                           reinterpret_cast<uintptr_t>(num_objects) | reinterpret_cast<uintptr_t>(offsets) |
                           reinterpret_cast<uintptr_t>(score) | reinterpret_cast<uintptr_t>(obj_score) | reinterpret_cast<uintptr_t>(obj_step);
     AIR_REQUIRE((all & 3u) == 0, AIR_E_ALIGN);
-    hipLaunchKernelGGL(prune_relabel_kernel, dim3(air_cdiv(R, 4)), dim3(256), 0, air_stream(stream), score_src, kept_step,
-                       num_objects, offsets, T, R, score, obj_score, obj_step);
-    AIR_LAUNCH_CHECK();
-    return AIR_OK;
+    return parse_relabel_launch(score_src, kept_step, num_objects, offsets, T, R, score, obj_score, obj_step, stream);
 }

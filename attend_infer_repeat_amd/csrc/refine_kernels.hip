@@ -4,12 +4,11 @@
 //                    (the best iterate so far, bit copies of its rows) and one Adam step on the continuous latents.
 // One workgroup per image.  No atomics; every sum has one fixed order: the same bits run to run.
 #include <math.h>
-#include "air_common.h"
+#include "scene_device.h"
 #include "engine_device.h"
 
 #define RF_MAXT 32
 #define RF_THREADS 256
-#define RF_HALF_LOG_2PI 0.91893853320467274178f
 
 struct RfPriors {
     float what_loc, what_scale, scale_loc, scale_scale, shift_loc, shift_scale;   // shift_loc NaN: centred on where_loc
@@ -17,29 +16,6 @@ struct RfPriors {
 struct RfAdam {
     float lr_what, lr_where, beta1, beta2, eps, c1, c2, guard;
 };
-
-// log N(x | loc, scale).  No clamps: a zero scale gives the +-inf / NaN of the plain formula.
-__device__ __forceinline__ float rf_log_normal(float x, float loc, float scale, float log_scale) {
-    const float z = (x - loc) / scale;
-    return -0.5f * (z * z) - log_scale - RF_HALF_LOG_2PI;
-}
-
-template <int V> struct RfVec;
-template <> struct RfVec<4> { typedef float4 type; };
-template <> struct RfVec<2> { typedef float2 type; };
-template <> struct RfVec<1> { typedef float type; };
-
-__device__ __forceinline__ void rf_copy_row(const float *__restrict__ src, float *__restrict__ dst, int n, bool vec, int lane) {
-    if (vec) {                                                     // 16-byte vectors: n % 4 == 0 and both buffers start aligned
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        for (int i = lane; i < n / 4; i += 64) d4[i] = s4[i];
-    } else {
-        const unsigned *s1 = reinterpret_cast<const unsigned *>(src);
-        unsigned *d1 = reinterpret_cast<unsigned *>(dst);
-        for (int i = lane; i < n; i += 64) d1[i] = s1[i];
-    }
-}
 
 // m, v and the latent of one element; returns the new latent (before the guard rule)
 __device__ __forceinline__ float rf_adam(float z, float d, float mu, float var, float lr, const RfAdam &ad, float &m, float &v) {
@@ -62,7 +38,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_step_kernel(
     float *__restrict__ m_where, float *__restrict__ v_where, RfAdam ad, int iter, int do_update, int T, int B, int A, int G,
     int what_vec, int glimpse_vec, double *__restrict__ best_J, int *__restrict__ best_iter, float *__restrict__ best_what,
     float *__restrict__ best_where, float *__restrict__ best_glimpse, float *__restrict__ J_trace) {
-    typedef typename RfVec<V>::type vec_t;
+    typedef typename VecOf<V>::type vec_t;
     __shared__ int sh_n, sh_take;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.x;
@@ -81,7 +57,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_step_kernel(
             const vec_t x = *reinterpret_cast<const vec_t *>(what + ((size_t)t * B + b) * A + (size_t)i * V);
             const float *xf = reinterpret_cast<const float *>(&x);
 #pragma unroll
-            for (int v = 0; v < V; ++v) s += rf_log_normal(xf[v], pr.what_loc, pr.what_scale, log_pw);
+            for (int v = 0; v < V; ++v) s += log_normal(xf[v], pr.what_loc, pr.what_scale, log_pw);
         }
         if (lane < n) {
             const size_t off = ((size_t)lane * B + b) * 4;
@@ -92,10 +68,10 @@ __global__ __launch_bounds__(RF_THREADS) void refine_step_kernel(
                 ly = l.y; lw = l.w;
             }
             const float log_ps = logf(pr.scale_scale), log_ph = logf(pr.shift_scale);
-            s += rf_log_normal(x.x, pr.scale_loc, pr.scale_scale, log_ps);
-            s += rf_log_normal(x.y, ly, pr.shift_scale, log_ph);
-            s += rf_log_normal(x.z, pr.scale_loc, pr.scale_scale, log_ps);
-            s += rf_log_normal(x.w, lw, pr.shift_scale, log_ph);
+            s += log_normal(x.x, pr.scale_loc, pr.scale_scale, log_ps);
+            s += log_normal(x.y, ly, pr.shift_scale, log_ph);
+            s += log_normal(x.z, pr.scale_loc, pr.scale_scale, log_ps);
+            s += log_normal(x.w, lw, pr.shift_scale, log_ph);
         }
         s = wave_sum_all(s);
         float rec = 0.f;                                           // the operations of air_sum_leading
@@ -123,8 +99,8 @@ __global__ __launch_bounds__(RF_THREADS) void refine_step_kernel(
         for (int t = wave; t < T; t += RF_THREADS / 64) {
             const size_t row = (size_t)t * B + b;
             if (lane < 4) reinterpret_cast<unsigned *>(best_where)[row * 4 + lane] = reinterpret_cast<const unsigned *>(where)[row * 4 + lane];
-            rf_copy_row(what + row * A, best_what + row * A, A, what_vec != 0, lane);
-            rf_copy_row(glimpse + row * G, best_glimpse + row * G, G, glimpse_vec != 0, lane);
+            copy_row_bits(what + row * A, best_what + row * A, A, what_vec != 0, lane);
+            copy_row_bits(glimpse + row * G, best_glimpse + row * G, G, glimpse_vec != 0, lane);
         }
     }
     if (!do_update) return;                                        // block-uniform

@@ -10,7 +10,7 @@
 // the order does not matter); no floating-point atomic anywhere, so a rerun gives the same bits.
 #include <limits.h>
 #include <math.h>
-#include "air_common.h"
+#include "scene_device.h"
 
 #define SCORE_MAXT 32
 #define SCORE_MAXG 8
@@ -133,22 +133,6 @@ __device__ __forceinline__ long long score_wave_sum(long long v) {      // valid
 }
 __device__ __forceinline__ long long score_pairs(long long n) { return n * (n - 1) / 2; }
 
-__device__ __forceinline__ double score_box_iou(const float4 a, const float4 b) {
-#pragma clang fp contract(off)
-    const double al = (double)a.x, at = (double)a.y, ar = (double)a.x + (double)a.z, ab = (double)a.y + (double)a.w;
-    const double bl = (double)b.x, bt = (double)b.y, br = (double)b.x + (double)b.z, bb = (double)b.y + (double)b.w;
-    const double ax0 = fmin(al, ar), ax1 = fmax(al, ar), ay0 = fmin(at, ab), ay1 = fmax(at, ab);
-    const double bx0 = fmin(bl, br), bx1 = fmax(bl, br), by0 = fmin(bt, bb), by1 = fmax(bt, bb);
-    // a NaN coordinate must score 0: fmin / fmax drop a NaN operand, so it is tested for on its own
-    const bool nan = (a.x != a.x) || (a.y != a.y) || (a.z != a.z) || (a.w != a.w) || (b.x != b.x) || (b.y != b.y) ||
-                     (b.z != b.z) || (b.w != b.w);
-    const double iw = fmax(0.0, fmin(ax1, bx1) - fmax(ax0, bx0)), ih = fmax(0.0, fmin(ay1, by1) - fmax(ay0, by0));
-    const double inter = iw * ih;
-    const double uni = ((ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0)) - inter;
-    const double q = inter / uni;
-    return (!nan && inter > 0.0 && uni > 0.0 && isfinite(q)) ? q : 0.0;
-}
-
 // One wavefront per image.  The image's contingency table and the float64 box IoUs of its T x G pairs live in the wave's slice of
 // LDS; lane a <= T owns row a of the table, lane b <= G column b, lane k < K walks the greedy assignment of threshold k.
 __global__ __launch_bounds__(256) void score_match_kernel(const int *__restrict__ cont, const float *__restrict__ boxes,
@@ -215,7 +199,7 @@ __global__ __launch_bounds__(256) void score_match_kernel(const int *__restrict_
         if (t < nh && j < g) {
             const float4 pb = *reinterpret_cast<const float4 *>(boxes + 4 * ((size_t)t * R + r));
             const float4 gb = *reinterpret_cast<const float4 *>(gt_boxes + 4 * ((size_t)r * G + j));
-            bi = score_box_iou(pb, gb);
+            bi = box_iou_f64(pb, gb);
             const long long n = c[(t + 1) * G1 + j + 1];
             const long long uni = (long long)rowsum_s[wid][t + 1] + (long long)colsum_s[wid][j + 1] - n;
             mi = uni > 0 ? (double)n / (double)uni : 0.0;

@@ -8,28 +8,12 @@
 // run to run.
 #include <math.h>
 #include <limits.h>
-#include "air_common.h"
+#include "scene_device.h"
 
 #define TEMPORAL_MAXT 6                  // PROPOSE_MAXT: air_prune_score is instantiated up to 6 rows
 #define TEMPORAL_NONE 15u                // an empty 4-bit entry of the packed lists below (a candidate id is < 12)
 
 enum { TEMPORAL_ABSENT = 0, TEMPORAL_TAKEN = 1, TEMPORAL_KNOWN = 2, TEMPORAL_DUPLICATE = 3, TEMPORAL_FULL = 4, TEMPORAL_NONFINITE = 5 };
-
-// air_score_match's float64 box IoU of two (left, top, width, height) boxes
-__device__ __forceinline__ double temporal_box_iou(const float4 a, const float4 b) {
-#pragma clang fp contract(off)
-    const double al = (double)a.x, at = (double)a.y, ar = (double)a.x + (double)a.z, ab = (double)a.y + (double)a.w;
-    const double bl = (double)b.x, bt = (double)b.y, br = (double)b.x + (double)b.z, bb = (double)b.y + (double)b.w;
-    const double ax0 = fmin(al, ar), ax1 = fmax(al, ar), ay0 = fmin(at, ab), ay1 = fmax(at, ab);
-    const double bx0 = fmin(bl, br), bx1 = fmax(bl, br), by0 = fmin(bt, bb), by1 = fmax(bt, bb);
-    const bool nan = (a.x != a.x) || (a.y != a.y) || (a.z != a.z) || (a.w != a.w) || (b.x != b.x) || (b.y != b.y) ||
-                     (b.z != b.z) || (b.w != b.w);
-    const double iw = fmax(0.0, fmin(ax1, bx1) - fmax(ax0, bx0)), ih = fmax(0.0, fmin(ay1, by1) - fmax(ay0, by0));
-    const double inter = iw * ih;
-    const double uni = ((ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0)) - inter;
-    const double q = inter / uni;
-    return (!nan && inter > 0.0 && uni > 0.0 && isfinite(q)) ? q : 0.0;
-}
 
 struct TemporalPoolArgs {
     const float *what, *where, *glimpse, *score, *presence;       // the current rows [T, R, .] of ALL frames (Jacobi: only read)
@@ -62,26 +46,6 @@ __device__ __forceinline__ float4 temporal_where(const float *__restrict__ where
 }
 __device__ __forceinline__ float4 temporal_shfl4(const float4 v, int src) {
     return make_float4(__shfl(v.x, src, 64), __shfl(v.y, src, 64), __shfl(v.z, src, 64), __shfl(v.w, src, 64));
-}
-__device__ __forceinline__ void temporal_copy_row(const float *__restrict__ src, float *__restrict__ dst, int n, bool vec, int lane) {
-    if (vec) {                                                     // 16-byte vectors: n % 4 == 0 and both buffers start aligned
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        for (int i = lane; i < n / 4; i += 64) d4[i] = s4[i];
-    } else {
-        const unsigned *s1 = reinterpret_cast<const unsigned *>(src);
-        unsigned *d1 = reinterpret_cast<unsigned *>(dst);
-        for (int i = lane; i < n; i += 64) d1[i] = s1[i];
-    }
-}
-__device__ __forceinline__ void temporal_fill_row(float *__restrict__ dst, int n, bool vec, int lane, unsigned bits) {
-    if (vec) {
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        for (int i = lane; i < n / 4; i += 64) d4[i] = make_uint4(bits, bits, bits, bits);
-    } else {
-        unsigned *d1 = reinterpret_cast<unsigned *>(dst);
-        for (int i = lane; i < n; i += 64) d1[i] = bits;
-    }
 }
 
 // One wavefront per row r = s F + f.  Lane q < 2T owns candidate q (slot q of frame f - 1, slot q - T of frame f + 1): its box, its
@@ -125,7 +89,7 @@ __global__ __launch_bounds__(256) void temporal_pool_kernel(TemporalPoolArgs a) 
     bool known = false;
     for (int j = 0; j < n; ++j) {                                  // the current objects' boxes: wave-uniform loads
         const float4 bj = attention_box4(temporal_where(a.where, (size_t)j * R + r), a.Wf, a.Hf);
-        known = known || temporal_box_iou(bq, bj) > a.iou_novel;   // a NaN comparison is false
+        known = known || box_iou_f64(bq, bj) > a.iou_novel;   // a NaN comparison is false
     }
     int state = !exists ? TEMPORAL_ABSENT : (!finite ? TEMPORAL_NONFINITE : (known ? TEMPORAL_KNOWN : -1));
     const bool open = state < 0;
@@ -146,7 +110,7 @@ __global__ __launch_bounds__(256) void temporal_pool_kernel(TemporalPoolArgs a) 
         int dup = -1;
         for (int i = 0; i < n_taken; ++i) {
             const float4 bd = temporal_shfl4(bq, (int)((taken_pack >> (4 * i)) & 15u));
-            if (dup < 0 && temporal_box_iou(bc, bd) > a.iou_novel) dup = i;
+            if (dup < 0 && box_iou_f64(bc, bd) > a.iou_novel) dup = i;
         }
         int st;
         if (dup >= 0) {
@@ -187,8 +151,8 @@ __global__ __launch_bounds__(256) void temporal_pool_kernel(TemporalPoolArgs a) 
         if (j >= T + n_taken) {                                    // an unused proposal row: a NaN joint in every subset that has it
             if (lane < 4) pwhere_u[to * 4 + lane] = __float_as_uint((lane & 1) ? 0.f : 1.f);
             if (lane == 4) pscore_u[to] = 0u;
-            temporal_fill_row(a.pool_what + to * A, A, a.what_vec != 0, lane, 0x7fc00000u);
-            temporal_fill_row(a.pool_glimpse + to * G, G, a.glimpse_vec != 0, lane, 0u);
+            fill_row_bits(a.pool_what + to * A, A, a.what_vec != 0, lane, 0x7fc00000u);
+            fill_row_bits(a.pool_glimpse + to * G, G, a.glimpse_vec != 0, lane, 0u);
             continue;
         }
         size_t from = to, mate = 0;
@@ -211,8 +175,8 @@ __global__ __launch_bounds__(256) void temporal_pool_kernel(TemporalPoolArgs a) 
             pwhere_u[to * 4 + lane] = bits;
         }
         if (lane == 4) pscore_u[to] = score_u[from];
-        temporal_copy_row(a.what + from * A, a.pool_what + to * A, A, a.what_vec != 0, lane);
-        temporal_copy_row(a.glimpse + from * G, a.pool_glimpse + to * G, G, a.glimpse_vec != 0, lane);
+        copy_row_bits(a.what + from * A, a.pool_what + to * A, A, a.what_vec != 0, lane);
+        copy_row_bits(a.glimpse + from * G, a.pool_glimpse + to * G, G, a.glimpse_vec != 0, lane);
     }
 }
 

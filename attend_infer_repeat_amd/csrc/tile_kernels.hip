@@ -8,7 +8,7 @@
 // No atomics, no cross-workgroup traffic, one fixed order: the same bits run to run.
 #include <math.h>
 #include <limits.h>
-#include "air_common.h"
+#include "scene_device.h"
 
 #define TILE_THREADS 256
 #define TILE_MAXC 32                     // PARSE_MAXT / SCORE_MAXT: the slots of a merged scene
@@ -98,22 +98,6 @@ struct TileMergeArgs {
     int T, S, A, G, Hs, Ws, H, W, sy, sx, ny, nx, C, what_vec, glimpse_vec;
 };
 
-// air_score_match's float64 box IoU of two (left, top, width, height) boxes
-__device__ __forceinline__ double tile_box_iou(const float4 a, const float4 b) {
-#pragma clang fp contract(off)
-    const double al = (double)a.x, at = (double)a.y, ar = (double)a.x + (double)a.z, ab = (double)a.y + (double)a.w;
-    const double bl = (double)b.x, bt = (double)b.y, br = (double)b.x + (double)b.z, bb = (double)b.y + (double)b.w;
-    const double ax0 = fmin(al, ar), ax1 = fmax(al, ar), ay0 = fmin(at, ab), ay1 = fmax(at, ab);
-    const double bx0 = fmin(bl, br), bx1 = fmax(bl, br), by0 = fmin(bt, bb), by1 = fmax(bt, bb);
-    const bool nan = (a.x != a.x) || (a.y != a.y) || (a.z != a.z) || (a.w != a.w) || (b.x != b.x) || (b.y != b.y) ||
-                     (b.z != b.z) || (b.w != b.w);
-    const double iw = fmax(0.0, fmin(ax1, bx1) - fmax(ax0, bx0)), ih = fmax(0.0, fmin(ay1, by1) - fmax(ay0, by0));
-    const double inter = iw * ih;
-    const double uni = ((ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0)) - inter;
-    const double q = inter / uni;
-    return (!nan && inter > 0.0 && uni > 0.0 && isfinite(q)) ? q : 0.0;
-}
-
 // one axis of the lift: (scale, shift) of a window at origin o -> the scene frame, float64, rounded once by the caller
 __device__ __forceinline__ void tile_lift_axis(float sc, float sh, int scene, int window, int o, double *sc_out, double *sh_out) {
 #pragma clang fp contract(off)
@@ -132,15 +116,11 @@ __device__ __forceinline__ bool tile_owns(double c, int i, int n, int stride, in
     return in;
 }
 
-template <int V> struct TileVec;
-template <> struct TileVec<4> { typedef uint4 type; };
-template <> struct TileVec<1> { typedef unsigned type; };
-
 // the kept rows of one table, copied by the whole workgroup: slot-major items of V words
 template <int V>
 __device__ __forceinline__ void tile_copy_rows(const float *__restrict__ src, float *__restrict__ dst, int n, int len, int R, int S,
                                                int s, int Nw, int T, const int *slot_cand, int tid) {
-    typedef typename TileVec<V>::type vec_t;
+    typedef typename VecOf<V>::type vec_t;
     const int LV = len / V, items = n * LV;
     for (int e = tid; e < items; e += TILE_THREADS) {
         const int slot = e / LV, q = e - slot * LV, c = slot_cand[slot], v = c / T, t = c - v * T;
@@ -225,7 +205,7 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_merge_kernel(TileMergeArgs 
         if (sup_s[ck] >= 0) continue;
         if (c == ck) kept_s[c] = 1;
         ++n_kept;
-        if (owned && c != ck && ck / T != v && sup_s[c] < 0 && !kept_s[c] && tile_box_iou(box_s[ck], box) > a.iou_merge) sup_s[c] = ck;
+        if (owned && c != ck && ck / T != v && sup_s[c] < 0 && !kept_s[c] && box_iou_f64(box_s[ck], box) > a.iou_merge) sup_s[c] = ck;
         __syncthreads();
     }
     __syncthreads();
@@ -303,25 +283,7 @@ extern "C" int air_tile_merge(const float *what, const float *where, const float
 // ============================================================================================================
 // relabel
 // ============================================================================================================
-// One wavefront per scene; lane j < n rewrites what air_parse_objects labelled by position.
-__global__ __launch_bounds__(256) void tile_relabel_kernel(const float *__restrict__ score_src, const int *__restrict__ kept_cand,
-                                                           const int *__restrict__ n_obj, const int *__restrict__ offsets, int C,
-                                                           int S, float *__restrict__ score, float *__restrict__ obj_score,
-                                                           int *__restrict__ obj_step) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= S) return;                                            // wave-uniform
-    int n = n_obj[r];
-    n = n < 0 ? 0 : (n > C ? C : n);
-    if (lane < n) {
-        const size_t src = (size_t)lane * S + r, dst = (size_t)offsets[r] + lane;
-        const float v = score_src[src];
-        score[src] = v;
-        obj_score[dst] = v;
-        obj_step[dst] = kept_cand[src];
-    }
-}
-
+// The kernel is parse_relabel_kernel (parse_kernels.hip); this entry takes up to the 32 slots of a merged scene.
 extern "C" int air_tile_relabel(const float *score_src, const int *kept_cand, const int *num_objects, const int *offsets, int C,
                                 int S, float *score, float *obj_score, int *obj_step, void *stream) {
     AIR_REQUIRE(score_src && kept_cand && num_objects && offsets && score && obj_score && obj_step, AIR_E_NULL);
@@ -330,8 +292,5 @@ extern "C" int air_tile_relabel(const float *score_src, const int *kept_cand, co
                           reinterpret_cast<uintptr_t>(num_objects) | reinterpret_cast<uintptr_t>(offsets) |
                           reinterpret_cast<uintptr_t>(score) | reinterpret_cast<uintptr_t>(obj_score) | reinterpret_cast<uintptr_t>(obj_step);
     AIR_REQUIRE((all & 3u) == 0, AIR_E_ALIGN);
-    hipLaunchKernelGGL(tile_relabel_kernel, dim3(air_cdiv(S, 4)), dim3(256), 0, air_stream(stream), score_src, kept_cand,
-                       num_objects, offsets, C, S, score, obj_score, obj_step);
-    AIR_LAUNCH_CHECK();
-    return AIR_OK;
+    return parse_relabel_launch(score_src, kept_cand, num_objects, offsets, C, S, score, obj_score, obj_step, stream);
 }

@@ -7,7 +7,7 @@
 // the same bits run to run.
 #include <math.h>
 #include <limits.h>
-#include "air_common.h"
+#include "scene_device.h"
 
 #define TRACK_THREADS 256
 #define TRACK_MAXT 32                    // PARSE_MAXT / SCORE_MAXT: objects per frame, and live tracks per sequence
@@ -15,22 +15,6 @@
 #define TRACK_MAX_IDS 32767              // F * T: an id fits the int16 of track_owner
 
 enum { TRACK_ABSENT = 0, TRACK_MATCHED = 1, TRACK_BORN = 2, TRACK_UNCONFIRMED = 3, TRACK_OVERFLOW = 4, TRACK_NONFINITE = 5 };
-
-// air_score_match's float64 box IoU of two (left, top, width, height) boxes
-__device__ __forceinline__ double track_box_iou(const float4 a, const float4 b) {
-#pragma clang fp contract(off)
-    const double al = (double)a.x, at = (double)a.y, ar = (double)a.x + (double)a.z, ab = (double)a.y + (double)a.w;
-    const double bl = (double)b.x, bt = (double)b.y, br = (double)b.x + (double)b.z, bb = (double)b.y + (double)b.w;
-    const double ax0 = fmin(al, ar), ax1 = fmax(al, ar), ay0 = fmin(at, ab), ay1 = fmax(at, ab);
-    const double bx0 = fmin(bl, br), bx1 = fmax(bl, br), by0 = fmin(bt, bb), by1 = fmax(bt, bb);
-    const bool nan = (a.x != a.x) || (a.y != a.y) || (a.z != a.z) || (a.w != a.w) || (b.x != b.x) || (b.y != b.y) ||
-                     (b.z != b.z) || (b.w != b.w);
-    const double iw = fmax(0.0, fmin(ax1, bx1) - fmax(ax0, bx0)), ih = fmax(0.0, fmin(ay1, by1) - fmax(ay0, by0));
-    const double inter = iw * ih;
-    const double uni = ((ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0)) - inter;
-    const double q = inter / uni;
-    return (!nan && inter > 0.0 && uni > 0.0 && isfinite(q)) ? q : 0.0;
-}
 
 __device__ __forceinline__ bool track_finite4(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w); }
 
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(TrackAss
             const int k = p >> 5, j = p & 31;
             double val = -1.0;
             if (t_live[k] && j < n && track_finite4(obox_s[j]) && isfinite(oscore_s[j]) && !nonfinite_s[j]) {
-                const double iou = track_box_iou(tbox_s[k], obox_s[j]);
+                const double iou = box_iou_f64(tbox_s[k], obox_s[j]);
                 const float *wk = a.what + ((size_t)t_j[k] * R + (size_t)s * F + t_f[k]) * A;      // read in place
                 const float *wj = a.what + ((size_t)j * R + r) * A;
                 double sum = 0.0;
@@ -426,7 +410,7 @@ __global__ __launch_bounds__(64) void track_score_kernel(TrackScoreArgs a) {
         __syncthreads();
         for (int p = lane; p < TRACK_MAXG * TRACK_MAXT; p += 64) {
             const int g = p >> 5, j = p & 31;
-            iou_s[p] = (gpresent_s[g] && hid_s[j] >= 0) ? track_box_iou(gbox_s[g], hbox_s[j]) : 0.0;
+            iou_s[p] = (gpresent_s[g] && hid_s[j] >= 0) ? box_iou_f64(gbox_s[g], hbox_s[j]) : 0.0;
         }
         __syncthreads();
         // ---- 1. a remembered track that is still on its object keeps it (ascending g; a hypothesis is taken once) -------------------

@@ -6,7 +6,7 @@
 // The arithmetic is float64 from the widened fp32 values with contraction off, only + - * /, in the order include/air_hip.h states;
 // the row of a track in a frame is a count of integers in one fixed order; no floating-point atomics: the same bits run to run.
 #include <limits.h>
-#include "air_common.h"
+#include "scene_device.h"
 
 #define TRAJ_THREADS 256                 // air_track_fill: four wavefronts, one (row, column) each
 #define TRAJ_SMOOTH_THREADS 64           // air_track_smooth: one wavefront per sequence -- a dependent chain per lane, no cross-wave traffic
@@ -370,18 +370,6 @@ struct TrajFillArgs {
     int T, F, R, C, N, per_seq, A, G, what_vec, glimpse_vec;
 };
 
-__device__ __forceinline__ void traj_copy_row(const float *__restrict__ src, float *__restrict__ dst, int n, bool vec, int lane) {
-    if (vec) {                                                     // 16-byte vectors: n % 4 == 0 and both buffers start aligned
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        for (int i = lane; i < n / 4; i += 64) d4[i] = src ? s4[i] : make_uint4(0u, 0u, 0u, 0u);
-    } else {
-        const unsigned *s1 = reinterpret_cast<const unsigned *>(src);
-        unsigned *d1 = reinterpret_cast<unsigned *>(dst);
-        for (int i = lane; i < n; i += 64) d1[i] = src ? s1[i] : 0u;
-    }
-}
-
 // One wavefront per (row c, column n) of the table; column n belongs to sequence n / per_seq (per_seq = F for the completed table,
 // the horizon for the forecast table).  A row that is ABSENT, or whose source is outside the provider's rows, gets zeros.
 __global__ __launch_bounds__(TRAJ_THREADS) void track_fill_kernel(TrajFillArgs a) {
@@ -393,8 +381,8 @@ __global__ __launch_bounds__(TRAJ_THREADS) void track_fill_kernel(TrajFillArgs a
     const int st = (int)a.state[e], sf = a.src_frame[e], sj = a.src_slot[e];
     const bool has = st != TRAJ_ABSENT && sf >= 0 && sf < a.F && sj >= 0 && sj < a.T;
     const size_t from = has ? (size_t)sj * a.R + (size_t)s * a.F + sf : 0;
-    traj_copy_row(has ? a.what + from * a.A : nullptr, a.out_what + (size_t)e * a.A, a.A, a.what_vec != 0, lane);
-    traj_copy_row(has ? a.glimpse + from * a.G : nullptr, a.out_glimpse + (size_t)e * a.G, a.G, a.glimpse_vec != 0, lane);
+    copy_row_bits_or_zero(has ? a.what + from * a.A : nullptr, a.out_what + (size_t)e * a.A, a.A, a.what_vec != 0, lane);
+    copy_row_bits_or_zero(has ? a.glimpse + from * a.G : nullptr, a.out_glimpse + (size_t)e * a.G, a.G, a.glimpse_vec != 0, lane);
     if (lane == 0) reinterpret_cast<unsigned *>(a.out_score)[e] = has ? reinterpret_cast<const unsigned *>(a.score)[from] : 0u;
 }
 
