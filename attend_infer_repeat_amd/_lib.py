@@ -25,6 +25,19 @@ class AirGemmDesc(ctypes.Structure):
                 ("A16", c_void_p), ("B16", c_void_p), ("C16", c_void_p)]
 
 
+class AirGemmForm(ctypes.Structure):
+    """mirror of `struct AirGemmForm` (include/air_hip.h): which kernel a GEMM launch runs"""
+    _fields_ = [(n, c_int) for n in ("family", "grouped", "MT", "NT", "KW", "bf", "ta", "tb", "tile", "long_k", "nt_short", "xcd_map")] + \
+               [(n, ctypes.c_uint) for n in ("sk_mask", "small_mask", "a16_mask", "b16_mask")] + \
+               [(n, c_int) for n in ("S", "chunks_per_split", "workgroups", "threads")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+GEMM_FAMILIES = ("tile", "c16", "apro", "shortk", "wide", "wide16", "big", "big16")     # AIR_GEMM_FAM_* in order
+
+
 class AirRmspropSlice(ctypes.Structure):
     """mirror of `struct AirRmspropSlice` (include/air_hip.h)"""
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("ms", c_void_p), ("mg", c_void_p), ("mom", c_void_p),
@@ -101,6 +114,8 @@ SIGNATURES = {
                               c_float, P, P, c_size_t, P]),
     "air_gemm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "air_gemm_grouped": (c_int, [ctypes.POINTER(AirGemmDesc), c_int, P]),
+    "air_gemm_grouped_form": (c_int, [ctypes.POINTER(AirGemmDesc), c_int, ctypes.POINTER(AirGemmForm)]),
+    "air_gemm_form": (c_int, [c_int, c_int, c_int, c_int, c_size_t, ctypes.POINTER(AirGemmForm)]),
     "air_gemm_grouped_gauss_bwd": (c_int, [ctypes.POINTER(AirGemmDesc), c_int, ctypes.POINTER(AirGaussBwdEpi), P, c_int, P, P, P, P, P, P,
                                            c_int, P, P, c_int, P, c_int, P]),
     "air_gemm_grouped_opt": (c_int, [ctypes.POINTER(AirGemmDesc), c_int, ctypes.POINTER(AirOptFold), P]),

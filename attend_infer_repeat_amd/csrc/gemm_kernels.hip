@@ -19,6 +19,7 @@
 #include "engine_device.h"
 #include "nvil_device.h"
 #include "gemm_device.h"
+#include <cstring>
 #include <type_traits>
 
 
@@ -736,8 +737,10 @@ __device__ __forceinline__ void gemm_wide16_body(const GemmArgs &g, const Gemm16
         e_c[i] = g.beta != 0.f ? gC[(size_t)m * g.ldc + n] : 0.f;
     }
 
-    // one 32-deep chunk: k = first of the lane group's eight k values, kn = number of them inside K (8 in the main loop)
-    auto load_chunk = [&](int k, int kn, u32x4 (&fa)[MT], u32x4 (&fb)[NT], bool full) {
+    // one 32-deep chunk: k = first of the lane group's eight k values, kn = number of them inside K (8 in the main loop); cs: the
+    // chunk counts towards colsum -- not the last chunk a short tail group re-reads: it is never multiplied and must not be summed
+    // a second time either (two chunks in flight, A16 && B16, and a K / 32 that is no multiple of 16)
+    auto load_chunk = [&](int k, int kn, u32x4 (&fa)[MT], u32x4 (&fb)[NT], bool full, bool cs) {
         if (TA) {
             if (A16) {
                 u32x2 w[8];
@@ -783,7 +786,7 @@ __device__ __forceinline__ void gemm_wide16_body(const GemmArgs &g, const Gemm16
                     if (!full && j >= kn) w[j] = (u32x2){0u, 0u};
                 }
                 fb[0] = tr16<0>(w); fb[1] = tr16<1>(w); fb[2] = tr16<2>(w); fb[3] = tr16<3>(w);
-                if (want_colsum) {       // the bias gradient sums the UNROUNDED gradient: the first row of tiles also reads the fp32 rows
+                if (want_colsum && cs) { // the bias gradient sums the UNROUNDED gradient: the first row of tiles also reads the fp32 rows
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         if (full || j < kn) {
@@ -801,7 +804,7 @@ __device__ __forceinline__ void gemm_wide16_body(const GemmArgs &g, const Gemm16
                     if (!full && j >= kn) w[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 }
                 fb[0] = tr32<0>(w); fb[1] = tr32<1>(w); fb[2] = tr32<2>(w); fb[3] = tr32<3>(w);
-                if (want_colsum) {
+                if (want_colsum && cs) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) { csum[0] += w[j].x; csum[1] += w[j].y; csum[2] += w[j].z; csum[3] += w[j].w; }
                 }
@@ -841,7 +844,7 @@ __device__ __forceinline__ void gemm_wide16_body(const GemmArgs &g, const Gemm16
         for (int u = 0; u < U; ++u) {
             int cu = c + u * KW;
             if (cu > full_end - 1) cu = full_end - 1;      // a short tail group re-reads the last chunk (never multiplied)
-            load_chunk((cu << 5) + 8 * lg, 8, fa[u], fb[u], true);
+            load_chunk((cu << 5) + 8 * lg, 8, fa[u], fb[u], true, c + u * KW < full_end);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -855,7 +858,7 @@ __device__ __forceinline__ void gemm_wide16_body(const GemmArgs &g, const Gemm16
         int kn = g.K - k;
         kn = kn < 0 ? 0 : (kn > 8 ? 8 : kn);
         u32x4 fa[MT], fb[NT];
-        load_chunk(kn > 0 ? k : 0, kn, fa, fb, false);
+        load_chunk(kn > 0 ? k : 0, kn, fa, fb, false, true);
         mma(fa, fb);
     }
 
@@ -1317,6 +1320,45 @@ extern "C" size_t air_gemm_workspace_bytes(int M, int N, int K) {
     return (size_t)16 * (size_t)M * (size_t)N * sizeof(float);     // up to 16 split-K slabs
 }
 
+// WHICH kernel air_gemm / air_gemm_bf16 run (M, N, K > 0): the decision gemm_dispatch consumes and air_gemm_form returns.
+// tile shape: few rows -> narrow tiles + intra-workgroup split-K; many tiles -> one tile per wave
+static void gemm_single_form(int M, int N, int K, bool colsum, bool ws, size_t ws_bytes, AirGemmForm &f) {
+    memset(&f, 0, sizeof f);
+    f.family = AIR_GEMM_FAM_TILE;
+    const int chunks = (K + 15) / 16;
+    const long tiles22 = (long)air_cdiv(M, 32) * air_cdiv(N, 32);
+    if (tiles22 >= 2048) {
+        f.MT = 2; f.NT = 2; f.KW = 1; f.tile = 32; f.S = 1; f.chunks_per_split = chunks;
+        f.workgroups = air_cdiv(M, 32) * air_cdiv(N, 128); f.threads = 256;
+        return;
+    }
+    // latency regime (the whole problem fits a fraction of the chip): 16x16 tiles, one per workgroup, 4 waves split K,
+    // 8 chunks in flight -- every wave does one or two memory round trips whatever the shape
+    const long tiles = (long)air_cdiv(M, 16) * air_cdiv(N, 16);
+    int S = 1;
+    // cross-workgroup split-K costs a second (epilogue) launch, ~4.5 us on this part: only worth it for long K
+    if (!colsum && ws && chunks >= 64) {
+        long want = 1024 / (tiles > 0 ? tiles : 1);                      // aim for ~4 workgroups per CU
+        long max_by_k = chunks / 16;                                     // >= 4 chunks per wave per split
+        long max_by_ws = (long)(ws_bytes / ((size_t)M * N * sizeof(float)));
+        long s = want;
+        if (s > max_by_k) s = max_by_k;
+        if (s > max_by_ws) s = max_by_ws;
+        if (s > 16) s = 16;
+        if (s >= 2) S = (int)s;
+    }
+    f.MT = 1; f.NT = 1; f.KW = 4; f.tile = 16;
+    f.chunks_per_split = (chunks + S - 1) / S;
+    f.S = (chunks + f.chunks_per_split - 1) / f.chunks_per_split;       // drop empty tail splits
+    f.workgroups = (int)tiles; f.threads = 256;
+}
+extern "C" int air_gemm_form(int M, int N, int K, int colsum, size_t ws_bytes, AirGemmForm *out) {
+    AIR_REQUIRE(out, AIR_E_NULL);
+    AIR_REQUIRE(M > 0 && N > 0 && K > 0, AIR_E_SHAPE);
+    gemm_single_form(M, N, K, colsum != 0, ws_bytes > 0, ws_bytes, *out);
+    return AIR_OK;
+}
+
 template <bool BF>
 static int gemm_dispatch(int ta, int tb, int M, int N, int K, const float *A, int lda, const float *B, int ldb,
                          float *C, int ldc, const float *bias, int epilogue, const float *aux, int ldaux, float beta,
@@ -1336,34 +1378,11 @@ static int gemm_dispatch(int ta, int tb, int M, int N, int K, const float *A, in
     g.vecA = (!ta && (lda % 4 == 0) && air_aligned16(A)) ? 1 : 0;
     g.vecB = (tb && (ldb % 4 == 0) && air_aligned16(B)) ? 1 : 0;
 
-    const int chunks = (K + 15) / 16;
-    // tile shape: few rows -> narrow tiles + intra-workgroup split-K; many tiles -> one tile per wave
-    const long tiles22 = (long)air_cdiv(M, 32) * air_cdiv(N, 32);
-    int S = 1;
+    AirGemmForm f;
+    gemm_single_form(M, N, K, colsum != nullptr, ws != nullptr, ws_bytes, f);
+    g.S = f.S; g.chunks_per_split = f.chunks_per_split;
     hipStream_t st = air_stream(stream);
-    if (tiles22 >= 2048) {
-        g.S = 1; g.chunks_per_split = chunks;
-        return launch_gemm<2, 2, 1, BF>(g, st);
-    }
-    // latency regime (the whole problem fits a fraction of the chip): 16x16 tiles, one per workgroup, 4 waves split K,
-    // 8 chunks in flight -- every wave does one or two memory round trips whatever the shape
-    const bool narrow = true;
-    const long tiles = (long)air_cdiv(M, 16) * air_cdiv(N, 16);
-    // cross-workgroup split-K costs a second (epilogue) launch, ~4.5 us on this part: only worth it for long K
-    if (!colsum && ws && chunks >= 64) {
-        long want = 1024 / (tiles > 0 ? tiles : 1);                      // aim for ~4 workgroups per CU
-        long max_by_k = chunks / 16;                                     // >= 4 chunks per wave per split
-        long max_by_ws = (long)(ws_bytes / ((size_t)M * N * sizeof(float)));
-        long s = want;
-        if (s > max_by_k) s = max_by_k;
-        if (s > max_by_ws) s = max_by_ws;
-        if (s > 16) s = 16;
-        if (s >= 2) S = (int)s;
-    }
-    g.S = S;
-    g.chunks_per_split = (chunks + S - 1) / S;
-    g.S = (chunks + g.chunks_per_split - 1) / g.chunks_per_split;       // drop empty tail splits
-    (void)narrow;
+    if (f.KW == 1) return launch_gemm<2, 2, 1, BF>(g, st);
     return launch_gemm<1, 1, 4, BF>(g, st);
 }
 
@@ -1542,43 +1561,78 @@ static bool wide_regime_weight_gradients(const AirGemmDesc *descs, int count, lo
     return tiles16 > wide_min_tiles() && all_tn && min_k >= 256;
 }
 
+// ---- WHICH kernel air_gemm_grouped runs: one decision (gemm_grouped_form below), consumed by the launch code and returned by
+// air_gemm_grouped_form.  Each *_form function validates the problems in the order the launch reports their errors. ---------------
+static int validate_group(const AirGemmDesc *descs, int count) {
+    GemmArgs scratch;
+    for (int i = 0; i < count; ++i)
+        if (int st = fill_gemm_args(scratch, descs[i])) return st;
+    return AIR_OK;
+}
+// The workgroups problem i gets under a decided form: the ONE statement of the tile shapes -- the *_form functions add it up into
+// f.workgroups, the launch code builds its workgroup ranges from it.
+static int form_workgroups_of(const AirGemmForm &f, int i, const AirGemmDesc &d) {
+    switch (f.family) {
+        case AIR_GEMM_FAM_BIG: case AIR_GEMM_FAM_BIG16:
+            return ((f.small_mask >> i) & 1u) ? air_cdiv(d.M, 16) * air_cdiv(d.N, 16) : air_cdiv(d.M, 64) * air_cdiv(d.N, 64);
+        case AIR_GEMM_FAM_WIDE: case AIR_GEMM_FAM_WIDE16:
+            return air_cdiv(d.M, 16 * f.MT) * air_cdiv(d.N, 64);
+        case AIR_GEMM_FAM_SHORTK:
+            if ((f.sk_mask >> i) & 1u) return shortk_workgroups(d.M);
+            [[fallthrough]];
+        default:
+            return air_cdiv(d.M, f.tile) * air_cdiv(d.N, f.tile);
+    }
+}
+static void form_sum_workgroups(AirGemmForm &f, const AirGemmDesc *descs, int count) {
+    f.workgroups = 0;
+    for (int i = 0; i < count; ++i) f.workgroups += form_workgroups_of(f, i, descs[i]);
+}
 // more than AIR_GEMM_GROUP_MAX problems: only the all-TN wide-tile form (the deferred weight gradients of a step)
-static int launch_big_tn_group(const AirGemmDesc *descs, int count, void *stream) {
+static int big_tn_form(const AirGemmDesc *descs, int count, AirGemmForm &f) {
     AIR_REQUIRE(count <= AIR_GEMM_BIG_GROUP_MAX, AIR_E_SHAPE);
-    BigGroupArgs ga;
     const bool bf = descs[0].precision == AIR_PREC_BF16;
-    int wt = 0, min_k = 1 << 30, n_wide = 0;
-    ga.small_mask = 0u;
-    int st = fill_group(ga, descs, count,
-        [&](int, const AirGemmDesc &d) -> int {
-            if (int e = problem_precision(d, bf)) return e;
-            AIR_REQUIRE(!d.A2, AIR_E_UNSUPPORTED);
-            return AIR_OK;
-        },
-        [&](int i, const AirGemmDesc &d) {
-            const bool wide = d.ta && !d.tb && air_aligned16(d.B) && d.ldb % 4 == 0 && d.K % 4 == 0 && d.M >= 4 && d.N >= 4 &&
-                              d.M % 4 == 0 && d.N % 4 == 0;
-            if (wide) {
-                if (d.K < min_k) min_k = d.K;
-                ++n_wide;
-                return air_cdiv(d.M, 64) * air_cdiv(d.N, 64);
-            }
-            ga.small_mask |= 1u << i;
-            return air_cdiv(d.M, 16) * air_cdiv(d.N, 16);
-        }, &wt);
-    if (st) return st;
+    int min_k = 1 << 30, n_wide = 0;
+    GemmArgs scratch;
+    for (int i = 0; i < count; ++i) {
+        const AirGemmDesc &d = descs[i];
+        if (int e = problem_precision(d, bf)) return e;
+        AIR_REQUIRE(!d.A2, AIR_E_UNSUPPORTED);
+        if (int e = fill_gemm_args(scratch, d)) return e;
+        const bool wide = d.ta && !d.tb && air_aligned16(d.B) && d.ldb % 4 == 0 && d.K % 4 == 0 && d.M >= 4 && d.N >= 4 &&
+                          d.M % 4 == 0 && d.N % 4 == 0;
+        if (wide) {
+            if (d.K < min_k) min_k = d.K;
+            ++n_wide;
+        } else f.small_mask |= 1u << i;
+        // per-problem operand kinds: each problem reads the mirrors it has
+        if (bf && bf16_storage() && mirror_usable(d.A16, d.lda)) f.a16_mask |= 1u << i;
+        if (bf && bf16_storage() && mirror_usable(d.B16, d.ldb)) f.b16_mask |= 1u << i;
+    }
     AIR_REQUIRE(n_wide > 0, AIR_E_UNSUPPORTED);            // this form exists for the weight gradients of a step
     // XCD-contiguous tiles: within each problem in fp32 (a map over the whole grid would hand every long-K problem -- they come
     // first -- to the first XCDs); over the whole grid with bf16 operands (launches of equal-K problems, L2-traffic bound)
     static const int big_xcd = getenv("AIR_GEMM_BIG_XCD") ? atoi(getenv("AIR_GEMM_BIG_XCD")) : 1;
-    ga.xcd_map = (big_xcd && min_k >= 1024) ? (bf ? 2 : 1) : 0;
+    f.xcd_map = (big_xcd && min_k >= 1024) ? (bf ? 2 : 1) : 0;
+    f.family = bf ? AIR_GEMM_FAM_BIG16 : AIR_GEMM_FAM_BIG;
+    f.grouped = 1; f.MT = 4; f.KW = 8; f.bf = bf ? 1 : 0; f.ta = 1; f.tb = 0;
+    f.threads = 512;
+    form_sum_workgroups(f, descs, count);
+    return AIR_OK;
+}
+static int launch_big_tn_group(const AirGemmDesc *descs, int count, const AirGemmForm &f, void *stream) {
+    BigGroupArgs ga;
+    int wt = 0;
+    int st = fill_group(ga, descs, count, accept_any, [&](int i, const AirGemmDesc &d) { return form_workgroups_of(f, i, d); }, &wt);
+    if (st) return st;
+    ga.small_mask = f.small_mask;
+    ga.xcd_map = f.xcd_map;
     hipStream_t stm = air_stream(stream);
-    if (bf) {
-        BigGroupArgs16 g16;       // per-problem operand kinds: each problem reads the mirrors it has
+    if (f.family == AIR_GEMM_FAM_BIG16) {
+        BigGroupArgs16 g16;
         group_to16(g16, ga, [&](int j) {
             const AirGemmDesc &d = descs[j];
-            return Gemm16Ptrs{bf16_storage() && mirror_usable(d.A16, d.lda) ? d.A16 : nullptr,
-                              bf16_storage() && mirror_usable(d.B16, d.ldb) ? d.B16 : nullptr, nullptr};
+            return Gemm16Ptrs{((f.a16_mask >> j) & 1u) ? d.A16 : nullptr, ((f.b16_mask >> j) & 1u) ? d.B16 : nullptr, nullptr};
         });
         g16.small_mask = ga.small_mask;
         hipLaunchKernelGGL((gemm_big_group_wide16_tn_kernel<4, 8>), dim3(wt), dim3(512), 0, stm, g16);
@@ -1597,17 +1651,14 @@ static unsigned shortk_mask(const AirGemmDesc *descs, int count) {
     }
     return m;
 }
-static int launch_grouped_sk(const AirGemmDesc *descs, int count, unsigned sk_mask, void *stream) {
+static int launch_grouped_sk(const AirGemmDesc *descs, int count, const AirGemmForm &f, void *stream) {
     GroupArgs ga;
-    const int T_ = latency_tile(group_tiles16(descs, count, sk_mask));
     int tiles = 0;
-    int err = fill_group(ga, descs, count, accept_any, [&](int i, const AirGemmDesc &d) {
-        return ((sk_mask >> i) & 1u) ? shortk_workgroups(d.M) : air_cdiv(d.M, T_) * air_cdiv(d.N, T_);
-    }, &tiles);
+    int err = fill_group(ga, descs, count, accept_any, [&](int i, const AirGemmDesc &d) { return form_workgroups_of(f, i, d); }, &tiles);
     if (err) return err;
-    ga.sk_mask = sk_mask;
+    ga.sk_mask = f.sk_mask;
     hipStream_t st = air_stream(stream);
-    if (T_ == 16) hipLaunchKernelGGL((gemm_grouped_sk_kernel<1, 1>), dim3(tiles), dim3(256), 0, st, ga);
+    if (f.MT == 1) hipLaunchKernelGGL((gemm_grouped_sk_kernel<1, 1>), dim3(tiles), dim3(256), 0, st, ga);
     else hipLaunchKernelGGL((gemm_grouped_sk_kernel<2, 2>), dim3(tiles), dim3(256), 0, st, ga);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
@@ -1655,35 +1706,43 @@ extern "C" int air_gemm_grouped_gather(const AirGemmDesc *descs, int count, cons
     return AIR_OK;
 }
 
-extern "C" int air_gemm_grouped(const AirGemmDesc *descs, int count, void *stream) {
-    AIR_REQUIRE(descs, AIR_E_NULL);
-    if (count > AIR_GEMM_GROUP_MAX) return launch_big_tn_group(descs, count, stream);
+static int gemm_grouped_form(const AirGemmDesc *descs, int count, AirGemmForm &f) {
+    memset(&f, 0, sizeof f);
+    if (count > AIR_GEMM_GROUP_MAX) return big_tn_form(descs, count, f);
     AIR_REQUIRE(count > 0 && count <= AIR_GEMM_GROUP_MAX, AIR_E_SHAPE);
-    if (const unsigned skm = shortk_mask(descs, count)) return launch_grouped_sk(descs, count, skm, stream);
-    GroupArgs ga;
+    f.grouped = count > 1 ? 1 : 0;
+    if (const unsigned skm = shortk_mask(descs, count)) {
+        if (int err = validate_group(descs, count)) return err;
+        f.family = AIR_GEMM_FAM_SHORTK; f.grouped = 1; f.sk_mask = skm;
+        f.tile = latency_tile(group_tiles16(descs, count, skm));
+        f.MT = f.NT = f.tile == 16 ? 1 : 2; f.KW = 4; f.threads = 256;
+        form_sum_workgroups(f, descs, count);
+        return AIR_OK;
+    }
     const long tiles16 = group_tiles16(descs, count, 0u);
     const int T_ = latency_tile(tiles16);
-    int tiles = 0;
-    int err = fill_group(ga, descs, count, accept_any,
-                         [&](int, const AirGemmDesc &d) { return air_cdiv(d.M, T_) * air_cdiv(d.N, T_); }, &tiles);
-    if (err) return err;
+    if (int err = validate_group(descs, count)) return err;
     const bool long_k = group_long_k(descs, count, tiles16);
     bool bf;
-    if ((err = group_precision(descs, count, &bf))) return err;
-    hipStream_t st = air_stream(stream);
+    if (int err = group_precision(descs, count, &bf)) return err;
+    f.bf = bf ? 1 : 0;
     {   // throughput regime
         const int ta = descs[0].ta ? 1 : 0, tb = descs[0].tb ? 1 : 0;
         int min_k;
         bool nt_short;
         const bool ok = wide_group_eligible(descs, count, tiles16, bf, &min_k, &nt_short);
-        if (ok && bf && ta) return launch_big_tn_group(descs, count, stream);   // per-problem operand kinds (mirrors) in one launch
+        if (ok && bf && ta) {   // per-problem operand kinds (mirrors) in one launch
+            memset(&f, 0, sizeof f);
+            return big_tn_form(descs, count, f);
+        }
         if (ok) {
-            const int TMw = ta ? 64 : (nt_short ? 32 : 16);
-            const int wt = group_tile_starts(ga, descs, count,
-                                             [&](int, const AirGemmDesc &d) { return air_cdiv(d.M, TMw) * air_cdiv(d.N, 64); });
+            f.family = bf ? AIR_GEMM_FAM_WIDE16 : AIR_GEMM_FAM_WIDE;
+            f.ta = ta; f.tb = tb; f.nt_short = nt_short ? 1 : 0;
+            f.MT = ta ? 4 : (nt_short ? 2 : 1); f.KW = 8; f.threads = 512;
+            form_sum_workgroups(f, descs, count);
             // long-K weight-gradient groups (1.5 MB of operands per tile): measured +1.3 % on the batch-1024 step with bf16
             // operands, nothing in fp32 (MFMA issue bound), -1.5 % at batch 256 (K = 768)
-            ga.xcd_map = (ta && min_k >= 1024) ? 1 : 0;
+            f.xcd_map = (ta && min_k >= 1024) ? 1 : 0;
             if (bf) {
                 // the bf16 data path: operands from their bf16 mirrors where EVERY problem of the launch has one (4-byte
                 // aligned rows), from the fp32 buffers otherwise; mirrors of C written by the epilogue
@@ -1692,45 +1751,102 @@ extern "C" int air_gemm_grouped(const AirGemmDesc *descs, int count, void *strea
                     a16 = a16 && mirror_usable(descs[i].A16, descs[i].lda);
                     b16 = b16 && mirror_usable(descs[i].B16, descs[i].ldb);
                 }
-                GroupArgs16 g16;
-                group_to16(g16, ga, [&](int j) {
-                    return Gemm16Ptrs{a16 ? descs[j].A16 : nullptr, b16 ? descs[j].B16 : nullptr, descs[j].C16};
-                });
-#define AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, A16_, B16_)                                                                              \
-                do {                                                                                                       \
-                    if (count == 1) hipLaunchKernelGGL((gemm_wide16_kernel<MT_, 8, TA_, TB_, A16_, B16_>), dim3(wt), dim3(512), 0, st, g16.g[0], g16.h[0]); \
-                    else hipLaunchKernelGGL((gemm_grouped_wide16_kernel<MT_, 8, TA_, TB_, A16_, B16_>), dim3(wt), dim3(512), 0, st, g16);                   \
-                } while (0)
-#define AIR_WIDE16_LAUNCH(MT_, TA_, TB_)                                                                                   \
-                do {                                                                                                       \
-                    if (a16 && b16) AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, true, true);                                         \
-                    else if (a16) AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, true, false);                                          \
-                    else if (b16) AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, false, true);                                          \
-                    else AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, false, false);                                                  \
-                } while (0)
-                if (ta) AIR_WIDE16_LAUNCH(4, true, false);
-                else if (nt_short) AIR_WIDE16_LAUNCH(2, false, true);
-                else if (tb) AIR_WIDE16_LAUNCH(1, false, true);
-                else AIR_WIDE16_LAUNCH(1, false, false);
-#undef AIR_WIDE16_LAUNCH
-#undef AIR_WIDE16_LAUNCH2
-                AIR_LAUNCH_CHECK();
-                return AIR_OK;
+                f.a16_mask = a16 ? (1u << count) - 1u : 0u;
+                f.b16_mask = b16 ? (1u << count) - 1u : 0u;
             }
-#define AIR_WIDE_LAUNCH(MT_, TA_, TB_)                                                                                     \
-            do {                                                                                                           \
-                if (count == 1) hipLaunchKernelGGL((gemm_wide_kernel<MT_, 8, false, TA_, TB_>), dim3(wt), dim3(512), 0, st, ga.g[0]);     \
-                else hipLaunchKernelGGL((gemm_grouped_wide_kernel<MT_, 8, false, TA_, TB_>), dim3(wt), dim3(512), 0, st, ga);             \
-            } while (0)
-            if (ta) AIR_WIDE_LAUNCH(4, true, false);
-            else if (nt_short) AIR_WIDE_LAUNCH(2, false, true);
-            else if (tb) AIR_WIDE_LAUNCH(1, false, true);
-            else AIR_WIDE_LAUNCH(1, false, false);
-#undef AIR_WIDE_LAUNCH
-            AIR_LAUNCH_CHECK();
             return AIR_OK;
         }
     }
+    for (int i = 0; i < count; ++i) AIR_REQUIRE(!descs[i].A2 || count == 1, AIR_E_UNSUPPORTED);
+    bool any_c16 = false;
+    for (int i = 0; i < count; ++i) any_c16 = any_c16 || (descs[i].C16 != nullptr);
+    f.tile = T_; f.long_k = long_k ? 1 : 0;
+    f.MT = f.NT = (long_k || T_ == 16) ? 1 : 2; f.KW = long_k ? 16 : 4; f.threads = 64 * f.KW;
+    if (any_c16) {
+        // bf16 data path on small tiles: fp32 operand fetch, rounded in registers; the epilogue also writes the bf16 mirror of C
+        AIR_REQUIRE(bf && !descs[0].A2, AIR_E_UNSUPPORTED);
+        f.family = AIR_GEMM_FAM_C16;
+    } else if (count == 1 && descs[0].A2) {
+        // latency-regime consumer of a K-split producer; a long K (the first hidden layer >= 512 wide at a small batch) stays
+        // on the 4-wave prologue kernel: correct for any K, the 16-wave K split has no prologue form
+        AIR_REQUIRE(T_ == 16, AIR_E_UNSUPPORTED);
+        f.family = AIR_GEMM_FAM_APRO; f.MT = f.NT = 1; f.KW = 4; f.threads = 256;
+    } else f.family = AIR_GEMM_FAM_TILE;
+    form_sum_workgroups(f, descs, count);
+    return AIR_OK;
+}
+extern "C" int air_gemm_grouped_form(const AirGemmDesc *descs, int count, AirGemmForm *out) {
+    AIR_REQUIRE(descs && out, AIR_E_NULL);
+    return gemm_grouped_form(descs, count, *out);
+}
+
+extern "C" int air_gemm_grouped(const AirGemmDesc *descs, int count, void *stream) {
+    AIR_REQUIRE(descs, AIR_E_NULL);
+    AirGemmForm f;
+    if (int err = gemm_grouped_form(descs, count, f)) return err;
+    if (f.family == AIR_GEMM_FAM_BIG || f.family == AIR_GEMM_FAM_BIG16) return launch_big_tn_group(descs, count, f, stream);
+    if (f.family == AIR_GEMM_FAM_SHORTK) return launch_grouped_sk(descs, count, f, stream);
+    GroupArgs ga;
+    int tiles = 0;
+    const bool wide = f.family == AIR_GEMM_FAM_WIDE || f.family == AIR_GEMM_FAM_WIDE16;
+    int err = fill_group(ga, descs, count, accept_any, [&](int i, const AirGemmDesc &d) { return form_workgroups_of(f, i, d); }, &tiles);
+    if (err) return err;
+    hipStream_t st = air_stream(stream);
+    const bool bf = f.bf != 0;
+    if (wide) {
+        const int wt = tiles;
+        ga.xcd_map = f.xcd_map;
+        if (bf) {
+            const bool a16 = f.a16_mask != 0u, b16 = f.b16_mask != 0u;
+            GroupArgs16 g16;
+            group_to16(g16, ga, [&](int j) {
+                return Gemm16Ptrs{a16 ? descs[j].A16 : nullptr, b16 ? descs[j].B16 : nullptr, descs[j].C16};
+            });
+#define AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, A16_, B16_)                                                                              \
+            do {                                                                                                           \
+                if (!f.grouped) hipLaunchKernelGGL((gemm_wide16_kernel<MT_, 8, TA_, TB_, A16_, B16_>), dim3(wt), dim3(512), 0, st, g16.g[0], g16.h[0]); \
+                else hipLaunchKernelGGL((gemm_grouped_wide16_kernel<MT_, 8, TA_, TB_, A16_, B16_>), dim3(wt), dim3(512), 0, st, g16);                   \
+            } while (0)
+#define AIR_WIDE16_LAUNCH(MT_, TA_, TB_)                                                                                   \
+            do {                                                                                                           \
+                if (a16 && b16) AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, true, true);                                             \
+                else if (a16) AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, true, false);                                              \
+                else if (b16) AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, false, true);                                              \
+                else AIR_WIDE16_LAUNCH2(MT_, TA_, TB_, false, false);                                                      \
+            } while (0)
+            // (<4, TN> is kept for the switch's sake only: gemm_grouped_form hands every bf16 TN group to the big-group launch)
+            if (f.MT == 4) AIR_WIDE16_LAUNCH(4, true, false);
+            else if (f.MT == 2) AIR_WIDE16_LAUNCH(2, false, true);
+            else if (f.tb) AIR_WIDE16_LAUNCH(1, false, true);
+            else AIR_WIDE16_LAUNCH(1, false, false);
+#undef AIR_WIDE16_LAUNCH
+#undef AIR_WIDE16_LAUNCH2
+            AIR_LAUNCH_CHECK();
+            return AIR_OK;
+        }
+#define AIR_WIDE_LAUNCH(MT_, TA_, TB_)                                                                                     \
+        do {                                                                                                               \
+            if (!f.grouped) hipLaunchKernelGGL((gemm_wide_kernel<MT_, 8, false, TA_, TB_>), dim3(wt), dim3(512), 0, st, ga.g[0]);         \
+            else hipLaunchKernelGGL((gemm_grouped_wide_kernel<MT_, 8, false, TA_, TB_>), dim3(wt), dim3(512), 0, st, ga);                 \
+        } while (0)
+        // (<2, NT> is kept for the switch's sake only: wide_group_eligible admits the NT-short form with bf16 operands alone)
+        if (f.MT == 4) AIR_WIDE_LAUNCH(4, true, false);
+        else if (f.MT == 2) AIR_WIDE_LAUNCH(2, false, true);
+        else if (f.tb) AIR_WIDE_LAUNCH(1, false, true);
+        else AIR_WIDE_LAUNCH(1, false, false);
+#undef AIR_WIDE_LAUNCH
+        AIR_LAUNCH_CHECK();
+        return AIR_OK;
+    }
+    // the tile families: <MT, NT, KW> = <1, 1, 16> (16 waves split K), <1, 1, 4> (16x16 tiles) or <2, 2, 4> (32x32 tiles; whole-tile
+    // waves instead of a 4-way K split for short contractions were measured in round 3 and removed in round 4: 0.2131-0.2223
+    // against 0.2077 ms at configs[1])
+#define AIR_TILE_FORMS(LAUNCH_)                                                                                      \
+    do {                                                                                                             \
+        if (f.KW == 16) LAUNCH_(1, 1, 16, 1024);                                                                     \
+        else if (f.MT == 1) LAUNCH_(1, 1, 4, 256);                                                                   \
+        else LAUNCH_(2, 2, 4, 256);                                                                                  \
+    } while (0)
 #define AIR_GROUP_LAUNCH(MT_, NT_, KW_, NTH_)                                                                        \
     do {                                                                                                             \
         if (bf) hipLaunchKernelGGL((gemm_grouped_kernel<MT_, NT_, KW_, true>), dim3(tiles), dim3(NTH_), 0, st, ga);   \
@@ -1743,46 +1859,25 @@ extern "C" int air_gemm_grouped(const AirGemmDesc *descs, int count, void *strea
         if (bf) hipLaunchKernelGGL((gemm_f32_mfma_kernel<MT_, NT_, KW_, true>), dim3(tiles, 1), dim3(NTH_), 0, st, ga.g[0]);  \
         else hipLaunchKernelGGL((gemm_f32_mfma_kernel<MT_, NT_, KW_, false>), dim3(tiles, 1), dim3(NTH_), 0, st, ga.g[0]);    \
     } while (0)
-    for (int i = 0; i < count; ++i) AIR_REQUIRE(!descs[i].A2 || count == 1, AIR_E_UNSUPPORTED);
-    bool any_c16 = false;
-    for (int i = 0; i < count; ++i) any_c16 = any_c16 || (descs[i].C16 != nullptr);
-    if (any_c16) {
-        // bf16 data path on small tiles: fp32 operand fetch, rounded in registers; the epilogue also writes the bf16 mirror of C
-        AIR_REQUIRE(bf && !descs[0].A2, AIR_E_UNSUPPORTED);
+    if (f.family == AIR_GEMM_FAM_C16) {
         C16Ptrs c16;
         for (int i = 0; i < AIR_GEMM_GROUP_MAX; ++i) c16.p[i] = i < count ? descs[i].C16 : nullptr;
 #define AIR_C16_LAUNCH(MT_, NT_, KW_, NTH_)                                                                          \
         do {                                                                                                         \
-            if (count == 1) hipLaunchKernelGGL((gemm_bf16_c16_kernel<MT_, NT_, KW_>), dim3(tiles, 1), dim3(NTH_), 0, st, ga.g[0], c16.p[0]);  \
+            if (!f.grouped) hipLaunchKernelGGL((gemm_bf16_c16_kernel<MT_, NT_, KW_>), dim3(tiles, 1), dim3(NTH_), 0, st, ga.g[0], c16.p[0]);  \
             else hipLaunchKernelGGL((gemm_grouped_c16_kernel<MT_, NT_, KW_>), dim3(tiles), dim3(NTH_), 0, st, ga, c16);                     \
         } while (0)
-        if (long_k) AIR_C16_LAUNCH(1, 1, 16, 1024);
-        else if (T_ == 16) AIR_C16_LAUNCH(1, 1, 4, 256);
-        else AIR_C16_LAUNCH(2, 2, 4, 256);
+        AIR_TILE_FORMS(AIR_C16_LAUNCH);
 #undef AIR_C16_LAUNCH
-        AIR_LAUNCH_CHECK();
-        return AIR_OK;
-    }
-    if (count == 1 && descs[0].A2) {
-        // latency-regime consumer of a K-split producer; a long K (the first hidden layer >= 512 wide at a small batch) stays
-        // on the 4-wave prologue kernel: correct for any K, the 16-wave K split has no prologue form
-        AIR_REQUIRE(T_ == 16, AIR_E_UNSUPPORTED);
+    } else if (f.family == AIR_GEMM_FAM_APRO) {
         const AproArgs pro = {descs[0].A2, descs[0].a_bias, descs[0].a_out, descs[0].a_elu};
         if (bf) hipLaunchKernelGGL((gemm_f32_mfma_apro_kernel<1, 1, 4, true>), dim3(tiles, 1), dim3(256), 0, st, ga.g[0], pro);
         else hipLaunchKernelGGL((gemm_f32_mfma_apro_kernel<1, 1, 4, false>), dim3(tiles, 1), dim3(256), 0, st, ga.g[0], pro);
-    } else if (count == 1) {
-        if (long_k) AIR_SINGLE_LAUNCH(1, 1, 16, 1024);
-        else if (T_ == 16) AIR_SINGLE_LAUNCH(1, 1, 4, 256);
-        else AIR_SINGLE_LAUNCH(2, 2, 4, 256);
-    } else if (long_k) AIR_GROUP_LAUNCH(1, 1, 16, 1024);
-    else if (T_ == 16) AIR_GROUP_LAUNCH(1, 1, 4, 256);
-    else {
-        // (whole-tile waves instead of a 4-way K split for short contractions -- K = batch in the weight gradients of the wide
-        //  first layers -- were measured in round 3 and removed in round 4: 0.2131-0.2223 against 0.2077 ms at configs[1])
-        AIR_GROUP_LAUNCH(2, 2, 4, 256);
-    }
+    } else if (!f.grouped) AIR_TILE_FORMS(AIR_SINGLE_LAUNCH);
+    else AIR_TILE_FORMS(AIR_GROUP_LAUNCH);
 #undef AIR_SINGLE_LAUNCH
 #undef AIR_GROUP_LAUNCH
+#undef AIR_TILE_FORMS
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

@@ -9,7 +9,10 @@ Three policies live here:
                        of the library's dispatch and of the flat buffers before it folds an update into a grouped launch;
   latency_tile / group_long_k / on_long_k_body / shortk_eligible / shortk_workgroups / latency_form / gather_fits / first_step_fits /
   lstm_fwd_wide / lstm_bwd_form / lstm_bwd_entry_fits / lstm_bf16_fits        the tile-form rules of the latency-regime grouped launches and of the LSTM step
-                       (tests/test_fold_cases_host.py holds every kernel-level case against them).
+                       (tests/test_fold_cases_host.py holds every kernel-level case against them);
+  grouped_form / single_form   the WHOLE dispatch rule of air_gemm_grouped and of air_gemm / air_gemm_bf16 -- kernel family, template
+                       arguments and what follows from them -- field for field what the library's own queries air_gemm_grouped_form /
+                       air_gemm_form return (tests/test_gemm_cases_host.py holds the two against each other).
 The predicates restate rules of the library (csrc/gemm_kernels.hip, csrc/lstm_kernels.hip); each names the function it mirrors."""
 from . import _lib
 
@@ -270,3 +273,198 @@ def foldable(descs, g0, r_lo, barred):
         mask |= 1 << i
         cov += mine
     return mask, cov
+
+
+# ---- the whole dispatch rule: which kernel carries a launch ------------------------------------------------------------------------
+E_NULL, E_SHAPE, E_ALIGN, E_UNSUPPORTED = -1, -2, -3, -5                      # include/air_hip.h AIR_E_*
+FORM_FIELDS = tuple(n for n, _ in _lib.AirGemmForm._fields_)
+
+
+def _form(**kw):
+    f = dict.fromkeys(FORM_FIELDS, 0)
+    f.update({k: int(v) for k, v in kw.items()})
+    return f
+
+
+def _cdiv(a, b):
+    return (a + b - 1) // b
+
+
+def _a(p):
+    return int(p or 0)
+
+
+def single_form(M, N, K, colsum=False, ws_bytes=0):
+    """gemm_kernels.hip gemm_single_form (air_gemm_form): the kernel of air_gemm / air_gemm_bf16 -- gemm_f32_mfma_kernel<2, 2, 1> from 2048
+    32x32 tiles, else <1, 1, 4> with a cross-workgroup K split S (no colsum, a workspace, at least 64 chunks of 16: about 1024 workgroups,
+    at least 16 chunks per split, what the workspace holds, at most 16; empty tail splits dropped) -> (status, form)"""
+    if M <= 0 or N <= 0 or K <= 0:
+        return E_SHAPE, None
+    chunks = _cdiv(K, 16)
+    if _cdiv(M, 32) * _cdiv(N, 32) >= 2048:
+        return 0, _form(family=0, MT=2, NT=2, KW=1, tile=32, S=1, chunks_per_split=chunks, workgroups=_cdiv(M, 32) * _cdiv(N, 128), threads=256)
+    tiles = _cdiv(M, 16) * _cdiv(N, 16)
+    S = 1
+    if not colsum and ws_bytes > 0 and chunks >= 64:
+        s = min(1024 // tiles, chunks // 16, ws_bytes // (M * N * 4), 16)
+        if s >= 2:
+            S = s
+    cps = _cdiv(chunks, S)
+    return 0, _form(family=0, MT=1, NT=1, KW=4, tile=16, S=_cdiv(chunks, cps), chunks_per_split=cps, workgroups=tiles, threads=256)
+
+
+def _desc_status(d):
+    """gemm_kernels.hip fill_gemm_args: what every grouped entry refuses of one problem"""
+    if not (_a(d.A) and _a(d.B) and _a(d.C)):
+        return E_NULL
+    if not (d.M > 0 and d.N > 0 and d.K > 0):
+        return E_SHAPE
+    if not (d.lda >= (d.M if d.ta else d.K) and d.ldb >= (d.K if d.tb else d.N) and d.ldc >= d.N):
+        return E_SHAPE
+    if not 0 <= d.epilogue <= 5:
+        return E_UNSUPPORTED
+    if d.epilogue in (1, 2) and not _a(d.bias):
+        return E_NULL
+    if d.epilogue >= 3 and not (_a(d.aux) and d.ldaux >= d.N):
+        return E_NULL
+    if _a(d.colsum) and not d.ta:
+        return E_UNSUPPORTED
+    if _a(d.A2):
+        if d.ta or not _a(d.a_bias) or d.K % 16 or d.lda % 4:
+            return E_UNSUPPORTED
+        if _a(d.A) % 16 or _a(d.A2) % 16 or _a(d.a_bias) % 16 or _a(d.a_out) % 16:
+            return E_ALIGN
+    return 0
+
+
+def _mirror_usable(m16, ld):
+    """gemm_kernels.hip mirror_usable: a bf16 mirror whose rows are 4-byte aligned"""
+    return bool(_a(m16) and ld % 2 == 0 and _a(m16) % 4 == 0)
+
+
+def _big_tn_form(descs, bf16_storage, big_xcd):
+    """gemm_kernels.hip big_tn_form: up to 24 problems, the TN ones with 16-byte B rows and M, N, K multiples of 4 on 64x64 tiles (at least
+    one), the rest (small_mask) on 16x16 tiles of the same grid; per-problem mirror kinds with bf16 operands"""
+    if len(descs) > 24:
+        return E_SHAPE, None
+    bf = descs[0].precision == 1
+    f = _form(grouped=1, MT=4, KW=8, bf=bf, ta=1, threads=512)
+    min_k, n_wide = 1 << 30, 0
+    for i, d in enumerate(descs):
+        if d.precision not in (0, 1) or (d.precision == 1) != bf or _a(d.A2):
+            return E_UNSUPPORTED, None
+        st = _desc_status(d)
+        if st:
+            return st, None
+        if (d.ta and not d.tb and _a(d.B) % 16 == 0 and d.ldb % 4 == 0 and d.K % 4 == 0 and d.M >= 4 and d.N >= 4 and d.M % 4 == 0
+                and d.N % 4 == 0):
+            min_k, n_wide = min(min_k, d.K), n_wide + 1
+            f["workgroups"] += _cdiv(d.M, 64) * _cdiv(d.N, 64)
+        else:
+            f["small_mask"] |= 1 << i
+            f["workgroups"] += _cdiv(d.M, 16) * _cdiv(d.N, 16)
+        if bf and bf16_storage and _mirror_usable(d.A16, d.lda):
+            f["a16_mask"] |= 1 << i
+        if bf and bf16_storage and _mirror_usable(d.B16, d.ldb):
+            f["b16_mask"] |= 1 << i
+    if not n_wide:
+        return E_UNSUPPORTED, None
+    f["xcd_map"] = ((2 if bf else 1) if (big_xcd and min_k >= 1024) else 0)
+    f["family"] = 7 if bf else 6
+    return 0, f
+
+
+def wide_group_eligible(descs, bf, wide_min_tiles=1000, wide_tn_bf16=48, wide_tn_f32=48, wide_nt_k=512):
+    """gemm_kernels.hip wide_group_eligible, the full rule -> (ok, min K, nt_short): more than `wide_min_tiles` 16x16 tiles, one layout
+    (not TT), no A prologue, B 16-byte aligned with ldb % 4 == 0, K % 4 == 0 unless NN, M, N, K >= 4, whole groups of 4 rows / columns of
+    an interleaved operand; up to 2048 tiles also A aligned, lda % 4 == 0, K % 4 == 0; TN: at least wide_tn 64x64 tiles and K >= 256;
+    NT below K = wide_nt_k: bf16 and more than 2048 tiles only"""
+    t16 = sum(tiles16(d) for d in descs)
+    ok = t16 > wide_min_tiles
+    ta, tb = bool(descs[0].ta), bool(descs[0].tb)
+    tiles64, min_k = 0, 1 << 30
+    for d in descs:
+        if not ok:
+            break
+        ok = bool(d.ta) == ta and bool(d.tb) == tb and not (ta and tb) and not _a(d.A2)
+        ok = ok and _a(d.B) % 16 == 0 and d.ldb % 4 == 0 and (not ta or d.K % 4 == 0) and (not tb or d.K % 4 == 0)
+        ok = ok and d.M >= 4 and d.N >= 4 and d.K >= 4 and (not ta or d.M % 4 == 0) and (tb or d.N % 4 == 0)
+        if t16 <= 2048:
+            ok = ok and _a(d.A) % 16 == 0 and d.lda % 4 == 0 and d.K % 4 == 0
+        tiles64 += _cdiv(d.M, 64) * _cdiv(d.N, 64)
+        min_k = min(min_k, d.K)
+    if ok and ta:
+        ok = tiles64 >= (wide_tn_bf16 if bf else wide_tn_f32) and min_k >= 256
+    nt_short = (not ta) and tb and min_k < wide_nt_k
+    if ok and nt_short:
+        ok = bf and t16 > 2048
+    return bool(ok), min_k, bool(nt_short)
+
+
+def grouped_form(descs, wide_min_tiles=1000, shortk=True, shortk_min_m=4096, shortk_wgs=384, wide_tn_bf16=48, wide_tn_f32=48, wide_nt_k=512,
+                 bf16_storage=True, big_xcd=True):
+    """gemm_kernels.hip gemm_grouped_form (air_gemm_grouped_form): the whole rule of air_gemm_grouped -> (status, form | None), the form a
+    dict over the fields of AirGemmForm.  The keyword arguments are the library's environment-tunable thresholds at their defaults
+    (AIR_GEMM_WIDE_MIN_TILES, AIR_GEMM_SHORTK, AIR_GEMM_SHORTK_MIN_M, AIR_GEMM_SHORTK_WGS, AIR_GEMM_WIDE_TN_BF16, AIR_GEMM_WIDE_TN_F32,
+    AIR_GEMM_WIDE_NT_K, AIR_GEMM_BF16_STORAGE, AIR_GEMM_BIG_XCD).  In order: more than 8 problems -> the big TN group; a plain fp32 group
+    with streaming short-K weight gradients -> "shortk"; the wide-tile regime (bf16 TN: the big-group launch, per-problem mirrors);
+    else the tile families "c16" / "apro" / "tile" on <1, 1, 16> (group_long_k), <1, 1, 4> or <2, 2, 4>."""
+    count = len(descs)
+    if count > 8:
+        return _big_tn_form(descs, bf16_storage, big_xcd)
+    if count <= 0:
+        return E_SHAPE, None
+
+    def validate():
+        for d in descs:
+            st = _desc_status(d)
+            if st:
+                return st
+        return 0
+
+    skm = 0
+    if shortk and not any(_a(d.A2) or _a(d.C16) or d.precision != 0 for d in descs):
+        skm = sum(1 << i for i, d in enumerate(descs) if shortk_eligible(d, shortk_min_m))
+    if skm:
+        st = validate()
+        if st:
+            return st, None
+        tile = latency_tile(sum(tiles16(d) for i, d in enumerate(descs) if not (skm >> i) & 1))
+        wgs = sum(shortk_workgroups(d.M, shortk_wgs) if (skm >> i) & 1 else _cdiv(d.M, tile) * _cdiv(d.N, tile) for i, d in enumerate(descs))
+        return 0, _form(family=3, grouped=1, sk_mask=skm, tile=tile, MT=tile // 16, NT=tile // 16, KW=4, threads=256, workgroups=wgs)
+    t16 = sum(tiles16(d) for d in descs)
+    tile = latency_tile(t16)
+    st = validate()
+    if st:
+        return st, None
+    lk = group_long_k(descs)
+    bf = descs[0].precision == 1
+    if any(d.precision not in (0, 1) or (d.precision == 1) != bf for d in descs):
+        return E_UNSUPPORTED, None
+    ok, min_k, nt_short = wide_group_eligible(descs, bf, wide_min_tiles, wide_tn_bf16, wide_tn_f32, wide_nt_k)
+    ta, tb = bool(descs[0].ta), bool(descs[0].tb)
+    if ok and bf and ta:
+        return _big_tn_form(descs, bf16_storage, big_xcd)
+    if ok:
+        MT = 4 if ta else (2 if nt_short else 1)
+        f = _form(family=5 if bf else 4, grouped=count > 1, bf=bf, ta=ta, tb=tb, nt_short=nt_short, MT=MT, KW=8, threads=512,
+                  workgroups=sum(_cdiv(d.M, 16 * MT) * _cdiv(d.N, 64) for d in descs), xcd_map=ta and min_k >= 1024)
+        if bf:
+            full = (1 << count) - 1
+            f["a16_mask"] = full if bf16_storage and all(_mirror_usable(d.A16, d.lda) for d in descs) else 0
+            f["b16_mask"] = full if bf16_storage and all(_mirror_usable(d.B16, d.ldb) for d in descs) else 0
+        return 0, f
+    if any(_a(d.A2) for d in descs) and count != 1:
+        return E_UNSUPPORTED, None
+    mt = 1 if (lk or tile == 16) else 2
+    f = _form(grouped=count > 1, bf=bf, tile=tile, long_k=lk, MT=mt, NT=mt, KW=16 if lk else 4, threads=1024 if lk else 256,
+              workgroups=sum(_cdiv(d.M, tile) * _cdiv(d.N, tile) for d in descs))
+    if any(_a(d.C16) for d in descs):
+        if not bf or _a(descs[0].A2):
+            return E_UNSUPPORTED, None
+        f["family"] = 1
+    elif count == 1 and _a(descs[0].A2):
+        if tile != 16:
+            return E_UNSUPPORTED, None
+        f.update(family=2, MT=1, NT=1, KW=4, threads=256)
+    return 0, f

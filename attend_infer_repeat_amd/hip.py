@@ -140,12 +140,16 @@ def canvas_unroll_bwd(glimpse, where, presence, obs, final_canvas, mult, std, lo
 
 # ---- dense ---------------------------------------------------------------------------------------------------------
 def gemm(A, B, ta=False, tb=False, bias=None, epilogue=EPI_NONE, aux=None, beta=0.0, out=None, colsum=False,
-         use_workspace=True):
+         use_workspace=True, precision=0, ws_bytes=None):
     """C = epi(op(A).op(B) + beta*C).  A, B: 2-D tensors whose last stride is 1 (row views with a leading dimension
-    are fine).  Returns C (and the column sums of op(B) when colsum=True)."""
+    are fine).  Returns C (and the column sums of op(B) when colsum is True or a tensor to write them into).  precision=1:
+    air_gemm_bf16 (operands rounded to bf16 in registers).  out: a caller-owned [M, N] view (any leading dimension);
+    ws_bytes: offer only that much of the workspace (caps the K split)."""
     for t, nm in ((A, "A"), (B, "B")):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1):
             raise _lib.AirHipError(f"gemm: {nm} must be a 2-D float32 CUDA tensor with unit inner stride")
+    if precision not in (0, 1):
+        raise _lib.AirHipError(f"gemm: precision {precision} is neither 0 (fp32) nor 1 (bf16)")
     M = A.shape[1] if ta else A.shape[0]
     K = A.shape[0] if ta else A.shape[1]
     Kb = B.shape[1] if tb else B.shape[0]
@@ -160,11 +164,29 @@ def gemm(A, B, ta=False, tb=False, bias=None, epilogue=EPI_NONE, aux=None, beta=
     ldaux = 0
     if aux is not None:
         ldaux = aux.stride(0) if aux.shape[0] > 1 else aux.shape[1]
-    cs = torch.empty((N,), dtype=torch.float32, device=A.device) if colsum else None
+    cs = colsum if torch.is_tensor(colsum) else (torch.empty((N,), dtype=torch.float32, device=A.device) if colsum else None)
     wsp, wsb = _ws_args(A) if use_workspace else (None, ctypes.c_size_t(0))
-    _lib.check(lib().air_gemm(int(ta), int(tb), M, N, K, _p(A), lda, _p(B), ldb, _p(out), ldc, _p(bias),
-                              int(epilogue), _p(aux), ldaux, float(beta), _p(cs), wsp, wsb, _stream()), "air_gemm")
-    return (out, cs) if colsum else out
+    if use_workspace and ws_bytes is not None:
+        wsb = ctypes.c_size_t(min(int(ws_bytes), wsb.value))
+    name = "air_gemm_bf16" if precision else "air_gemm"
+    _lib.check(getattr(lib(), name)(int(ta), int(tb), M, N, K, _p(A), lda, _p(B), ldb, _p(out), ldc, _p(bias),
+                                    int(epilogue), _p(aux), ldaux, float(beta), _p(cs), wsp, wsb, _stream()), name)
+    return (out, cs) if cs is not None else out
+
+
+def gemm_form(M, N, K, colsum=False, ws_bytes=_WS_BYTES):
+    """air_gemm_form: which kernel air_gemm / air_gemm_bf16 run on [M, N, K] -> dict over the fields of AirGemmForm (no launch)"""
+    f = _lib.AirGemmForm()
+    _lib.check(lib().air_gemm_form(M, N, K, int(bool(colsum)), ctypes.c_size_t(ws_bytes), ctypes.byref(f)), "air_gemm_form")
+    return f.as_dict()
+
+
+def gemm_grouped_form(problems, precision=0):
+    """air_gemm_grouped_form: which kernel air_gemm_grouped runs the problems on -> (status, dict over the fields of AirGemmForm)"""
+    arr, outs, keep = _gemm_descs(problems, precision, "gemm_grouped_form")
+    f = _lib.AirGemmForm()
+    st = int(lib().air_gemm_grouped_form(arr, len(outs), ctypes.byref(f)))
+    return st, f.as_dict()
 
 
 def _gemm_descs(problems, precision, name):
@@ -212,26 +234,35 @@ def gemm_grouped(problems, precision=0):
     return outs
 
 
-def linear_fwd(x, w, b, act):
+def linear_fwd(x, w, b, act, out=None):
+    """y = act(x . w + b); out: a caller-owned contiguous [M, N] tensor for y"""
     x = _f32(x, "x", 2); w = _f32(w, "w", 2); b = _f32(b, "b")
     M, K = x.shape
     N = w.shape[1]
     if w.shape[0] != K:
         raise _lib.AirHipError(f"linear: x is [{M},{K}] but w is {tuple(w.shape)}")
-    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    y = torch.empty((M, N), dtype=torch.float32, device=x.device) if out is None else _f32(out, "out", 2)
+    if tuple(y.shape) != (M, N):
+        raise _lib.AirHipError(f"linear: out is {tuple(y.shape)}, expected {(M, N)}")
     wsp, wsb = _ws_args(x)
     _lib.check(lib().air_linear_fwd(_p(x), _p(w), _p(b), _p(y), M, K, N, int(act), wsp, wsb, _stream()),
                "air_linear_fwd")
     return y
 
 
-def linear_bwd(x, w, y, dy, act, want_dx=True, want_db=True):
+def linear_bwd(x, w, y, dy, act, want_dx=True, want_db=True, out=None):
+    """-> dx, dw, db; out: caller-owned contiguous (dx[M, K] | None, dw[K, N], db[N] | None) to write into"""
     x = _f32(x, "x", 2); w = _f32(w, "w", 2); dy = _f32(dy, "dy", 2); y = _f32(y, "y")
     M, K = x.shape
     N = w.shape[1]
-    dx = torch.empty_like(x) if want_dx else None
-    dw = torch.empty_like(w)
-    db = torch.empty((N,), dtype=torch.float32, device=x.device) if want_db else None
+    if out is not None:
+        dx, dw, db = (_f32(t, "out") for t in out)
+        if (dx is not None and dx.shape != x.shape) or dw.shape != w.shape or (db is not None and tuple(db.shape) != (N,)):
+            raise _lib.AirHipError("linear_bwd: out does not match (dx[M, K], dw[K, N], db[N])")
+    else:
+        dx = torch.empty_like(x) if want_dx else None
+        dw = torch.empty_like(w)
+        db = torch.empty((N,), dtype=torch.float32, device=x.device) if want_db else None
     gbuf = torch.empty_like(dy) if act != ACT_NONE else None
     wsp, wsb = _ws_args(x)
     _lib.check(lib().air_linear_bwd(_p(x), _p(w), _p(y), _p(dy), _p(dx), _p(dw), _p(db), _p(gbuf), M, K, N, int(act),

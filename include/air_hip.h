@@ -194,6 +194,35 @@ typedef struct AirGemmDesc {
  * (no A2) on 16x16 tiles in the same grid.                                                                                 */
 AIR_ENGINE_API int air_gemm_grouped(const AirGemmDesc *descs, int count, void *stream);
 
+/* WHICH kernel a GEMM launch runs, decided by one host function per entry and consumed by the launch code: the kernel family, its
+ * template arguments and everything that follows from them.  The two queries below return that decision without launching (they
+ * read the descriptors' shapes, flags and pointer VALUES only, so they run on a machine without a GPU); the status is the one the
+ * launch itself would return before its first kernel.  Fields a family does not use are 0.
+ *   family   AIR_GEMM_FAM_TILE    gemm_body: gemm_f32_mfma_kernel (grouped == 0) / gemm_grouped_kernel <MT, NT, KW, bf>
+ *            AIR_GEMM_FAM_C16     the same body writing the bf16 mirror of C: gemm_bf16_c16_kernel / gemm_grouped_c16_kernel <MT, NT, KW>
+ *            AIR_GEMM_FAM_APRO    gemm_f32_mfma_apro_kernel <1, 1, 4, bf> (the A prologue, lone problem)
+ *            AIR_GEMM_FAM_SHORTK  gemm_grouped_sk_kernel <MT, NT>: the problems of sk_mask on shortk_dw_body, the rest on gemm_body <MT, NT, 4>
+ *            AIR_GEMM_FAM_WIDE    gemm_wide_body: gemm_wide_kernel / gemm_grouped_wide_kernel <MT, KW, false, ta, tb>
+ *            AIR_GEMM_FAM_WIDE16  gemm_wide16_body: gemm_wide16_kernel / gemm_grouped_wide16_kernel <MT, KW, ta, tb, a16_mask != 0, b16_mask != 0>
+ *            AIR_GEMM_FAM_BIG     gemm_big_group_wide_tn_kernel <MT, KW, false>: small_mask on 16x16 tiles, the rest on 64x64
+ *            AIR_GEMM_FAM_BIG16   gemm_big_group_wide16_tn_kernel <MT, KW>: a16_mask / b16_mask = the problems read from their mirrors
+ *   tile     the latency-regime tile edge T_ (16 / 32) of the TILE / C16 / APRO / SHORTK families
+ *   S, chunks_per_split   the cross-workgroup K split of air_gemm / air_gemm_bf16 (S > 1: gemm_splitk_epilogue_kernel follows)   */
+enum { AIR_GEMM_FAM_TILE = 0, AIR_GEMM_FAM_C16 = 1, AIR_GEMM_FAM_APRO = 2, AIR_GEMM_FAM_SHORTK = 3, AIR_GEMM_FAM_WIDE = 4,
+       AIR_GEMM_FAM_WIDE16 = 5, AIR_GEMM_FAM_BIG = 6, AIR_GEMM_FAM_BIG16 = 7 };
+typedef struct AirGemmForm {
+    int family, grouped;
+    int MT, NT, KW, bf;
+    int ta, tb;
+    int tile, long_k, nt_short, xcd_map;
+    unsigned sk_mask, small_mask, a16_mask, b16_mask;
+    int S, chunks_per_split;
+    int workgroups, threads;
+} AirGemmForm;
+AIR_ENGINE_API int air_gemm_grouped_form(const AirGemmDesc *descs, int count, AirGemmForm *out);
+/* air_gemm / air_gemm_bf16 (the precision does not enter): colsum, ws_bytes = whether a colsum is asked for, the workspace (0: none) */
+AIR_ENGINE_API int air_gemm_form(int M, int N, int K, int colsum, size_t ws_bytes, AirGemmForm *out);
+
 /* air_gemm_grouped for the FIRST product(s) of a train step whose batch is drawn from an HBM-resident dataset (data.py:121-158's feeder
  * in HBM): the gather of air_batch_gather folded into the A-operand load.  Every problem's A lies inside obs[B, item_floats] (row 0 + a
  * column offset, lda = item_floats, not transposed, fp32) and is read from item idx_m of `dataset` instead -- idx_m drawn exactly as
