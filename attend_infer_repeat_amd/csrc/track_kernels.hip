@@ -1,8 +1,12 @@
 // Tracking objects across the frames of a sequence for gfx950: per-frame parses in, identities out.
 //   air_track_associate: per sequence the frames walked in order INSIDE the kernel; a table of at most 32 live tracks, the float64
 //                        affinity of every (track, object) pair, greedy matching by a workgroup arg-max, births, ageing;
+//   air_track_associate_optimal: the same kernel with step 3 replaced: the assignment of the largest summed int64 profit, by a
+//                        shortest-augmenting-path Hungarian that one wavefront runs (lane = column);
 //   air_track_owner:     the parse's owner maps relabelled from step to track id (int8 in, int16 out): a streaming pass;
-//   air_track_score:     CLEAR-MOT counts of the tracks against ground truth whose slot g is one object over a sequence.
+//   air_track_score:     CLEAR-MOT counts of the tracks against ground truth whose slot g is one object over a sequence;
+//   air_track_idf:       the IDF1 counts of the same tracks: the (ground-truth slot, id) overlap table of a sequence and the largest
+//                        one-to-one sum over it, by dynamic programming over the subsets of slots.
 // Everything a float decides is float64 with contraction off; no floating-point atomics, no cross-workgroup traffic, one fixed order:
 // the same bits run to run.
 #include <math.h>
@@ -49,10 +53,68 @@ struct TrackAssocArgs {
     int T, S, F, A, max_age;
 };
 
-// One 256-thread workgroup per sequence.  Track slot k and object j < 32; pair p = k * 32 + j, four pairs per thread.
-__global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(TrackAssocArgs a) {
+// The assignment of the frame's finite objects (rows, inserted in ascending j) to the 64 columns of one wavefront -- column k < 32 is
+// track slot k, column 32 + j is "object j stays unmatched" -- that maximises the summed profit: profit_s[k * 32 + j] >= 1 for an
+// admissible pair, -1 for a forbidden one, 0 for staying unmatched.  Shortest augmenting paths with potentials (Jonker-Volgenant
+// style): u of row `lane`, v / minv / way / used of column `lane`, all int64, so the optimal value is exact; the column that enters
+// the tree next is the unused one of the least minv, the lowest column among equal values.  Returns the row assigned to column
+// `lane`, -1 for none.  Every lane of the wavefront must call it.
+#define TRACK_NO_COLUMN 64               // the virtual column an insertion starts from
+__device__ __forceinline__ int track_solve_wave(const long long *profit_s, const int *ostate_s, int n, int lane) {
+    long long u = 0, v = 0;
+    int row = -1;
+    for (int i = 0; i < n; ++i) {
+        if (ostate_s[i] != TRACK_UNCONFIRMED) continue;            // wave-uniform: a NONFINITE object takes no part
+        long long minv = LLONG_MAX;
+        int way = TRACK_NO_COLUMN, j0 = TRACK_NO_COLUMN, i0 = i;
+        bool used = false, in_tree = false;                        // column `lane` / row `lane` is on the alternating tree
+        for (;;) {
+            if (lane == j0) used = true;
+            if (lane == i0) in_tree = true;
+            const long long u0 = __shfl(u, i0, 64);
+            const long long profit = lane < TRACK_MAXT ? profit_s[lane * TRACK_MAXT + i0] : (lane - TRACK_MAXT == i0 ? 0 : -1);
+            if (!used && profit >= 0) {
+                const long long cur = -profit - u0 - v;
+                if (cur < minv) {
+                    minv = cur;
+                    way = j0;
+                }
+            }
+            long long delta = used ? LLONG_MAX : minv;             // object i0's own column is never forbidden: a finite minimum
+            int j1 = lane;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const long long od = __shfl_xor(delta, off, 64);
+                const int oj = __shfl_xor(j1, off, 64);
+                if (od < delta || (od == delta && oj < j1)) {
+                    delta = od;
+                    j1 = oj;
+                }
+            }
+            if (in_tree) u += delta;
+            if (used) v -= delta;
+            else if (minv != LLONG_MAX) minv -= delta;
+            j0 = j1;
+            i0 = __shfl(row, j0, 64);
+            if (i0 < 0) break;                                     // a free column: the path ends here
+        }
+        for (;;) {                                                 // the rows along the path move one column on
+            const int j1 = __shfl(way, j0, 64);
+            const int moved = __shfl(row, j1 & 63, 64);
+            if (lane == j0) row = j1 == TRACK_NO_COLUMN ? i : moved;
+            j0 = j1;
+            if (j0 == TRACK_NO_COLUMN) break;
+        }
+    }
+    return row;
+}
+
+// One 256-thread workgroup per sequence.  Track slot k and object j < 32; pair p = k * 32 + j, four pairs per thread.  OPTIMAL: step 3
+// is track_solve_wave's assignment (wavefront 0 runs it, the other three wait at the barrier), everything else is the same code.
+template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(TrackAssocArgs a) {
 #pragma clang fp contract(off)
     __shared__ double aff_s[TRACK_MAXT * TRACK_MAXT];              // aff of an admissible pair still open, -1 otherwise
+    __shared__ long long profit_s[OPTIMAL ? TRACK_MAXT * TRACK_MAXT : 1];      // OPTIMAL: 1 + floor(aff 2^32), -1 for a forbidden pair
     __shared__ float4 obox_s[TRACK_MAXT], tbox_s[TRACK_MAXT];      // the frame's boxes; the tracks' last-sighting boxes
     __shared__ float oscore_s[TRACK_MAXT], oaff_s[TRACK_MAXT];
     __shared__ int ostate_s[TRACK_MAXT], oid_s[TRACK_MAXT], opf_s[TRACK_MAXT], ops_s[TRACK_MAXT];
@@ -134,10 +196,31 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(TrackAss
                 if (iou > a.iou_gate) val = aff;
             }
             aff_s[p] = val;
+            if constexpr (OPTIMAL) profit_s[p] = val >= 0.0 ? 1 + (long long)floor(val * 4294967296.0) : -1;      // (exact: a power of two)
         }
         __syncthreads();
-        // ---- 3. greedy matching -----------------------------------------------------------------------------------------------------
-        for (;;) {
+        // ---- 3. matching: the optimal assignment, or greedily ---------------------------------------------------------------------------
+        if constexpr (OPTIMAL) {
+            if (wid == 0) {
+                const int j = track_solve_wave(profit_s, ostate_s, n, lane);
+                if (lane < TRACK_MAXT && j >= 0) {                  // the pairs share neither a track nor an object: any order
+                    const int k = lane;
+                    ostate_s[j] = TRACK_MATCHED;
+                    oid_s[j] = t_id[k];
+                    opf_s[j] = t_f[k];
+                    ops_s[j] = t_j[k];
+                    oaff_s[j] = (float)aff_s[k * TRACK_MAXT + j];
+                    t_gaps[k] += t_age[k] > 0 ? 1 : 0;
+                    t_age[k] = 0;
+                    t_len[k] += 1;
+                    t_f[k] = f;
+                    t_j[k] = j;
+                    tbox_s[k] = obox_s[j];
+                }
+            }
+            __syncthreads();
+        }
+        while (!OPTIMAL) {                                         // (a compile-time constant: no greedy round in the optimal kernel)
             double v = -1.0;
             int key = INT_MAX, pos = -1;
 #pragma unroll
@@ -250,11 +333,12 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(TrackAss
     if (tid < 6) a.state_counts[(size_t)s * 6 + tid] = counts_s[tid];
 }
 
-extern "C" int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
-                                   int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
-                                   int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
-                                   int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
-                                   int *state_counts, void *stream) {
+// the checks and the launch of both association entries
+static int track_associate_launch(bool optimal, const float *what, const float *boxes, const float *score, const int *num_objects, int T,
+                                  int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
+                                  int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
+                                  int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
+                                  int *state_counts, void *stream) {
     AIR_REQUIRE(what && boxes && score && num_objects && track_id && obj_state && affinity && prev_frame && prev_slot && num_tracks &&
                 track_first && track_last && track_length && track_gaps && state_counts, AIR_E_NULL);
     AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && S > 0 && F > 0 && A > 0, AIR_E_SHAPE);
@@ -272,9 +356,30 @@ extern "C" int air_track_associate(const float *what, const float *boxes, const 
     const TrackAssocArgs a = {what, boxes, score, num_objects, track_id, prev_frame, prev_slot, num_tracks, track_first, track_last,
                               track_length, track_gaps, state_counts, affinity, obj_state, iou_gate, appearance_weight, birth_score,
                               T, S, F, A, max_age};
-    hipLaunchKernelGGL(track_associate_kernel, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    if (optimal) hipLaunchKernelGGL(track_associate_kernel<true>, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    else hipLaunchKernelGGL(track_associate_kernel<false>, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
+}
+
+extern "C" int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
+                                   int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
+                                   int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
+                                   int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
+                                   int *state_counts, void *stream) {
+    return track_associate_launch(false, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score, max_age,
+                                  track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last, track_length,
+                                  track_gaps, state_counts, stream);
+}
+
+extern "C" int air_track_associate_optimal(const float *what, const float *boxes, const float *score, const int *num_objects, int T,
+                                           int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score,
+                                           int max_age, int *track_id, signed char *obj_state, float *affinity, int *prev_frame,
+                                           int *prev_slot, int *num_tracks, int *track_first, int *track_last, int *track_length,
+                                           int *track_gaps, int *state_counts, void *stream) {
+    return track_associate_launch(true, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score, max_age,
+                                  track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last, track_length,
+                                  track_gaps, state_counts, stream);
 }
 
 // ============================================================================================================
@@ -501,6 +606,133 @@ extern "C" int air_track_score(const float *boxes, const int *num_objects, const
     AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
     const TrackScoreArgs a = {boxes, gt_boxes, num_objects, track_id, seq_counts, gt_match, seq_iou, tau, T, G, S, F};
     hipLaunchKernelGGL(track_score_kernel, dim3((unsigned)S), dim3(64), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// ============================================================================================================
+// idf
+// ============================================================================================================
+struct TrackIdfArgs {
+    const float *boxes, *gt_boxes;
+    const int *num_objects, *track_id;
+    int *overlap, *seq_idf;
+    double tau;
+    int T, G, S, F, n_ids;
+};
+
+// One 256-thread workgroup per sequence.  The frames: pair p = g * 32 + j, one per thread, then thread g alone adds to row g of the
+// overlap table (no atomics: one writer per element).  The assignment: thread m holds best[m], the largest summed overlap of a
+// one-to-one assignment of the ids visited so far to ground-truth slots within the subset m; 32 ids (256 table entries, one per
+// thread) are staged per pass, an id without overlap is passed over.
+__global__ __launch_bounds__(TRACK_THREADS) void track_idf_kernel(TrackIdfArgs a) {
+#pragma clang fp contract(off)
+    __shared__ float4 hbox_s[TRACK_MAXT], gbox_s[TRACK_MAXG];
+    __shared__ int hid_s[TRACK_MAXT], gpresent_s[TRACK_MAXG], hit_s[TRACK_MAXG * TRACK_MAXT];
+    __shared__ int col_s[TRACK_MAXT * TRACK_MAXG];                 // [id within the pass][g]
+    __shared__ int best_s[2][1 << TRACK_MAXG];
+    __shared__ int max_id_s;
+    const int T = a.T, G = a.G, F = a.F, R = a.S * F, n_ids = a.n_ids;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    int *table = a.overlap + (size_t)s * G * n_ids;
+    for (int e = tid; e < G * n_ids; e += TRACK_THREADS) table[e] = 0;
+    if (tid == 0) max_id_s = -1;
+    int gt_frames = 0, hyp_frames = 0, max_id = -1;                // thread 0's
+    __syncthreads();
+    for (int f = 0; f < F; ++f) {
+        const int r = s * F + f;
+        int n = a.num_objects[r];
+        n = n < 0 ? 0 : (n > T ? T : n);
+        if (tid < TRACK_MAXT) {
+            const int j = tid;
+            float4 box = make_float4(0.f, 0.f, 0.f, 0.f);
+            int id = -1;
+            if (j < n) {
+                const size_t row = (size_t)j * R + r;
+                box = *reinterpret_cast<const float4 *>(a.boxes + 4 * row);
+                const int t = a.track_id[row];
+                if (t >= 0 && track_finite4(box)) id = t;
+            }
+            hbox_s[j] = box;
+            hid_s[j] = id;
+        }
+        if (tid >= 64 && tid < 64 + TRACK_MAXG) {                  // (the second wavefront: the two loads go side by side)
+            const int g = tid - 64;
+            float4 gb = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (g < G) gb = *reinterpret_cast<const float4 *>(a.gt_boxes + 4 * ((size_t)r * G + g));
+            gbox_s[g] = gb;
+            gpresent_s[g] = (g < G && gb.z > 0.f) ? 1 : 0;
+        }
+        __syncthreads();
+        {
+            const int g = tid >> 5, j = tid & 31, id = hid_s[j];
+            hit_s[tid] = (gpresent_s[g] && id >= 0 && id < n_ids && box_iou_f64(gbox_s[g], hbox_s[j]) > a.tau) ? 1 : 0;
+        }
+        __syncthreads();
+        if (tid < G && gpresent_s[tid])
+            for (int j = 0; j < T; ++j)
+                if (hit_s[tid * TRACK_MAXT + j]) table[(size_t)tid * n_ids + hid_s[j]] += 1;
+        if (tid == 0) {
+            for (int g = 0; g < G; ++g) gt_frames += gpresent_s[g];
+            for (int j = 0; j < T; ++j) {
+                const int id = hid_s[j];
+                hyp_frames += id >= 0 ? 1 : 0;
+                if (id < n_ids && id > max_id) max_id = id;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) max_id_s = max_id;
+    best_s[0][tid] = 0;
+    __syncthreads();                                               // the table is complete, and visible to the whole workgroup
+    const int last_id = max_id_s, full = (1 << G) - 1;
+    int cur = 0, with_overlap = 0;
+    for (int id0 = 0; id0 <= last_id; id0 += TRACK_MAXT) {
+        {
+            const int g = tid >> 5, id = id0 + (tid & 31);
+            col_s[(tid & 31) * TRACK_MAXG + g] = (g < G && id <= last_id) ? table[(size_t)g * n_ids + id] : 0;
+        }
+        __syncthreads();
+        for (int q = 0; q < TRACK_MAXT && id0 + q <= last_id; ++q) {
+            const int *col = col_s + q * TRACK_MAXG;
+            int any = 0;
+#pragma unroll
+            for (int g = 0; g < TRACK_MAXG; ++g) any |= col[g];
+            if (!any) continue;                                    // workgroup-uniform
+            ++with_overlap;
+            int b = best_s[cur][tid];
+            if (tid <= full) {
+#pragma unroll
+                for (int g = 0; g < TRACK_MAXG; ++g)
+                    if ((tid >> g) & 1) {
+                        const int c = best_s[cur][tid ^ (1 << g)] + col[g];
+                        b = c > b ? c : b;
+                    }
+            }
+            best_s[cur ^ 1][tid] = b;
+            cur ^= 1;
+            __syncthreads();
+        }
+        __syncthreads();                                           // (col_s is restaged)
+    }
+    if (tid == 0) {
+        int *o = a.seq_idf + (size_t)s * 4;
+        o[0] = best_s[cur][full], o[1] = gt_frames, o[2] = hyp_frames, o[3] = with_overlap;
+    }
+}
+
+extern "C" int air_track_idf(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau, int T,
+                             int G, int S, int F, int R, int n_ids, int *overlap, int *seq_idf, void *stream) {
+    AIR_REQUIRE(boxes && num_objects && track_id && gt_boxes && overlap && seq_idf, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && G >= 1 && G <= TRACK_MAXG && S > 0 && F > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(tau >= 0.0 && tau <= 1.0 && n_ids >= 1 && n_ids <= TRACK_MAX_IDS, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(boxes) && air_aligned16(gt_boxes), AIR_E_ALIGN);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(num_objects) | reinterpret_cast<uintptr_t>(track_id) |
+                           reinterpret_cast<uintptr_t>(overlap) | reinterpret_cast<uintptr_t>(seq_idf);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    const TrackIdfArgs a = {boxes, gt_boxes, num_objects, track_id, overlap, seq_idf, tau, T, G, S, F, n_ids};
+    hipLaunchKernelGGL(track_idf_kernel, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

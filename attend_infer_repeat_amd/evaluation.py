@@ -522,7 +522,7 @@ def make_trajectory_fig(frames, result, max_frames=8, checkpoint_dir=None, globa
 
 def make_track_score_logger(air, data, num_batches, name, batch_size=None, writer=None, tau=0.5, measure_time=True, iou_gate=None,
                             appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None,
-                            propose=None, temporal=None, smooth=None):
+                            propose=None, temporal=None, smooth=None, matching=None, identity=False):
     """make_tiled_parse_score_logger's counterpart for sequences (air.score_track): `data` is an annotated dataset dict of SEQUENCES
     (imgs [N, F, H, W], boxes [N, F, G, 4], instances [N, F, H, W] int8 -- data.create_moving_mnist with return_annotations=True),
     walked in `num_batches` batches of `batch_size` sequences (None: the model's batch size).  Prints / writes the identity figures
@@ -532,13 +532,19 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
     first (air.track's argument); temporal_kept then counts the objects that came from a neighbour.  smooth=True | dict: the tracks are
     also smoothed and gap-filled (trajectory.TrajectorySmoother) and the COMPLETED table is scored by the same kernel, side by side:
     smooth_mota, smooth_motp, smooth_id_switches, smooth_misses, smooth_false_positives, and the rows per state rows_observed,
-    rows_filled."""
+    rows_filled.  matching="optimal": the optimal assignment of every frame instead of the greedy one (air.track's argument; the
+    record names it).  identity=True: the IDF figures beside MOTA -- idf1, idp, idr, idtp, idfp, idfn (air_track_idf), and with smooth=
+    smooth_idf1 of the completed table."""
     import torch
     from .track import STATES
     tk = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
               refine_lr=refine_lr, prune=prune, propose=propose, temporal=temporal)
     if smooth is not None:
         tk["smooth"] = smooth
+    if matching is not None:
+        tk["matching"] = matching
+    if identity:
+        tk["identity"] = True
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -577,6 +583,13 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
                 acc["smooth_" + k] = done[k]
             acc["rows_observed"], acc["rows_filled"] = (int(v) for v in table_rows.tolist()[1:])
             shown += ["smooth_mota", "smooth_motp", "rows_filled"]
+        if identity:
+            idf = tracker.identity_summary()
+            acc.update({k: idf[k] for k in ("idf1", "idp", "idr", "idtp", "idfp", "idfn")})
+            shown[2:2] = ["idf1", "idp", "idr"]
+            if smooth is not None:
+                acc["smooth_idf1"] = air.track_smoother.identity_summary()["idf1"]
+                shown += ["smooth_idf1"]
         t = time.time() - start
         msg = 'Step {}, Data {} track score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:
@@ -586,6 +599,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
             rec = dict(step=int(itr), data=name + "_track_score", n_frames=int(data["imgs"].shape[1]), tau=float(tau),
                        iou_gate=tracker.iou_gate, appearance_weight=tracker.appearance_weight, birth_score=tracker.birth_score,
                        max_age=tracker.max_age, **acc)
+            if matching is not None:
+                rec["matching"] = tracker.matching
             writer.write(json.dumps(rec) + "\n"); writer.flush()
         return acc
     return logger

@@ -615,34 +615,35 @@ class AIRonMNIST(AIRModel):
         return spec
 
     def tracker(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-                refine_lr=None, prune=None, propose=None, temporal=None, smooth=None):
+                refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None):
         """the track.SequenceTracker behind `track` (`_tracker_entry` describes the cache; with smooth= the tracker of the stack that
         ends in the trajectory.TrajectorySmoother `trajectory_smoother` returns)"""
         entry = self._tracker_entry(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                                    propose, temporal, smooth)
+                                    propose, temporal, smooth, matching)
         return entry[-1] if self._smooth_spec(smooth) is None else entry[-2]
 
     def trajectory_smoother(self, n_sequences, n_frames, smooth=True, iou_gate=None, appearance_weight=None, birth_score=None,
-                            max_age=None, refine=None, refine_lr=None, prune=None, propose=None, temporal=None):
+                            max_age=None, refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None):
         """the trajectory.TrajectorySmoother behind `track(smooth=)` and `predict_frames`: last in the cached stack of
         `tracker(..., smooth=smooth)`, bound to that stack's tracker (smoothed, gap-filled and extrapolated tracks; its defaults are
         provisional)"""
         if self._smooth_spec(smooth) is None:
             raise ValueError("trajectory_smoother: smooth must be True or a dict of TrajectorySmoother's arguments, got %r" % (smooth,))
         return self._tracker_entry(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                                   propose, temporal, smooth)[-1]
+                                   propose, temporal, smooth, matching)[-1]
 
     def _tracker_entry(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-                       refine_lr=None, prune=None, propose=None, temporal=None, smooth=None):
+                       refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None):
         """the cached stack whose track.SequenceTracker is behind `track`: one per (n_sequences, n_frames, iou_gate, appearance_weight,
-        birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth), over a provider stack of its own at
+        birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth, matching), over a provider stack of its own at
         n_sequences * n_frames rows -- a SceneParser,
         behind it the refiner / pruner / proposer asked for and, last, with temporal=P | (P, rounds) a temporal.TemporalProposer
         (objects a frame's parse missed are proposed from its neighbour frames; its defaults are provisional) -- so the parsers of
         `parse` and `self.obs` are never touched.  temporal=None builds exactly the stack without it; so does smooth=None, and
         smooth=True | dict appends a trajectory.TrajectorySmoother bound to the tracker (part of the key).  None for one of the four
-        association arguments: track.DEFAULTS (provisional).  Built and captured on first use; the least recently used one is
-        dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
+        association arguments: track.DEFAULTS (provisional).  matching=None | "greedy" is exactly the stack without the argument,
+        "optimal" a tracker of its own with the optimal assignment (part of the key).  Built and captured on first use; the least
+        recently used one is dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
         eng = getattr(self, "_engine", None)
         if eng is None:
             raise NotImplementedError("track needs the fused engine: call train_step(...) with an engine-eligible "
@@ -654,7 +655,8 @@ class AIRonMNIST(AIRModel):
         given = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age)
         assoc = {k: (tr.DEFAULTS[k] if v is None else v) for k, v in given.items()}
         S, F = int(n_sequences), int(n_frames)
-        tr.check_arguments(eng.cfg.max_steps, F, S * F if S >= 1 else None, **assoc)
+        matching = "greedy" if matching is None else matching
+        tr.check_arguments(eng.cfg.max_steps, F, S * F if S >= 1 else None, matching=matching, **assoc)
         if S < 1:
             raise ValueError("track: at least one sequence, got %r" % (n_sequences,))
         lr = None if refine is None else tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
@@ -670,11 +672,12 @@ class AIRonMNIST(AIRModel):
         key = (S, F, float(assoc["iou_gate"]), float(assoc["appearance_weight"]), float(assoc["birth_score"]), int(assoc["max_age"]),
                refine, lr, prune, spec, str(eng.device)) + (() if tspec is None else (("temporal",) + tspec,))
         key += () if sspec is None else (("smooth",) + tuple(sorted(sspec.items())),)
+        key += () if matching == "greedy" else (("matching", matching),)
         cache = self.__dict__.setdefault("_trackers", {})
         entry = cache.pop(key, None)
         if entry is None:
             stack = self._sequence_stack(S, F, refine, lr, prune, propose, tspec)
-            stack.append(tr.SequenceTracker(stack[-1], F, **assoc))
+            stack.append(tr.SequenceTracker(stack[-1], F, matching=matching, **assoc))
             if sspec is not None:
                 from .trajectory import TrajectorySmoother
                 stack.append(TrajectorySmoother(stack[-1], **sspec))
@@ -723,21 +726,22 @@ class AIRonMNIST(AIRModel):
         return entry[-1]
 
     def track(self, frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None,
-              prune=None, propose=None, temporal=None, smooth=None):
+              prune=None, propose=None, temporal=None, smooth=None, matching=None):
         """Parse the frames [S, F, H, W] of S sequences on the device, each frame as `parse(refine=, prune=, propose=)` would parse
         it -- with temporal=P | (P, rounds) followed by proposals from the neighbour frames (temporal.TemporalProposer) -- and give
         the objects identities over time (track.SequenceTracker.track lists the returned device tensors: the parse of
         the S * F frames, row s * F + f, and next to it track_id, obj_state, affinity, prev_frame, prev_slot, the per-track tables and
         track_owner; the next call overwrites them).  With smooth=True | dict(horizon=, process_noise=, measurement_noise=,
         velocity_var=) the tracks are then smoothed, gap-filled and extrapolated (trajectory.TrajectorySmoother.result lists the sm_
-        and fc_ tensors and frames_pred that come on top); smooth=None is exactly the call without it.  The training engine's
+        and fc_ tensors and frames_pred that come on top); smooth=None is exactly the call without it.  matching="optimal": the
+        optimal assignment of every frame instead of the greedy one (track.py states both rules).  The training engine's
         parameters are read, nothing of it is written; `self.obs` and the parsers of `parse` are not touched."""
         import torch
         frames = torch.as_tensor(frames)
         if frames.dim() != 4:
             raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
         t = self._tracker_entry(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr,
-                                prune, propose, temporal, smooth)[-1]
+                                prune, propose, temporal, smooth, matching)[-1]
         self._sync_engine_switches()
         t.load_from(self._engine)                            # every time: the weights move
         self.tracked = t.track(frames)
@@ -757,7 +761,7 @@ class AIRonMNIST(AIRModel):
 
     def score_track(self, frames, gt_boxes, tau=0.5, accumulate=True, gt_instances=None, thresholds=None, iou_gate=None,
                     appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None,
-                    temporal=None, smooth=None):
+                    temporal=None, smooth=None, matching=None, identity=False):
         """`track`, then the identity metric of the tracks against gt_boxes [S, F, G, 4] (G <= 8; slot g is the same object in every
         frame of a sequence, width <= 0 = absent) on the device (track.SequenceTracker.score).  The sums accumulate in the tracker
         this returns alongside -- (scores, tracker): its summary() reads MOTA, MOTP, the identity switches and the mostly tracked /
@@ -766,18 +770,21 @@ class AIRonMNIST(AIRModel):
         the identity figures): scores["detection"] holds its tensors, `self.track_scorer` is that scorer.  With smooth= the COMPLETED
         table of the trajectory smoother is scored next to the raw one by the same kernel (TrajectorySmoother.score):
         scores["completed"] holds its tensors, `self.track_smoother` is the smoother, whose summary() / reset() are the completed
-        table's -- the raw figures stay the tracker's."""
+        table's -- the raw figures stay the tracker's.  matching= is `track`'s; identity=True adds the IDF1 counts (air_track_idf behind
+        air_track_score: seq_idf, idf_overlap, totals_idf; the tracker's -- and the smoother's -- identity_summary() reads IDF1, IDP
+        and IDR back)."""
         import torch
-        self.track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth)
+        self.track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth,
+                   matching)
         frames = torch.as_tensor(frames)
         t = self.tracker(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                         propose, temporal, smooth)
+                         propose, temporal, smooth, matching)
         gb = torch.as_tensor(gt_boxes)
-        scores = dict(t.score(gb, tau, accumulate))
+        scores = dict(t.score(gb, tau, accumulate, identity))
         if self._smooth_spec(smooth) is not None:
             self.track_smoother = self.trajectory_smoother(frames.shape[0], frames.shape[1], smooth, iou_gate, appearance_weight,
-                                                           birth_score, max_age, refine, refine_lr, prune, propose, temporal)
-            scores["completed"] = self.track_smoother.score(gb, tau, accumulate)
+                                                           birth_score, max_age, refine, refine_lr, prune, propose, temporal, matching)
+            scores["completed"] = self.track_smoother.score(gb, tau, accumulate, identity)
         if gt_instances is not None:
             from .score import DEFAULT_THRESHOLDS, ParseScorer
             th = tuple(float(v) for v in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))

@@ -131,6 +131,12 @@ def main(argv=None):
                          "Kalman filter and a backward pass per track) and score the completed table next to the raw one.  QS,QC,R: the "
                          "process noise of the shifts and of the scales and the measurement noise, in `where` units (default "
                          "1e-4,1e-4,4e-4: provisional, unmeasured on a trained model)")
+    ap.add_argument("--track-matching", choices=("greedy", "optimal"), default=None,
+                    help="with --track-eval: how a frame's objects are matched to the live tracks (track.SequenceTracker's matching): "
+                         "greedy (the default) or the optimal assignment of the whole frame (Hungarian, air_track_associate_optimal)")
+    ap.add_argument("--track-identity", action="store_true",
+                    help="with --track-eval: also report IDF1, IDP and IDR (air_track_idf: how long each ground-truth object keeps one "
+                         "identity) beside MOTA")
     ap.add_argument("--track-predict", type=int, default=None, metavar="HZ",
                     help="with --track-eval: also extrapolate the live tracks HZ frames (1..16) past every sequence and render the "
                          "predicted frames (AIRonMNIST.predict_frames' forecast table; implies --track-smooth)")
@@ -208,6 +214,8 @@ def main(argv=None):
             ap.error("--track-temporal goes with --track-eval")
         track_temporal = spec[0] if len(spec) == 1 else spec
 
+    if (args.track_matching is not None or args.track_identity) and track_eval is None:
+        ap.error("--track-matching and --track-identity go with --track-eval")
     track_smooth = None
     if args.track_smooth is not None or args.track_predict is not None:
         if track_eval is None:
@@ -378,7 +386,7 @@ def main(argv=None):
         seq_data = dict(imgs=raw["imgs"].astype("float32") / 255.0, boxes=raw["boxes"], instances=raw["instances"])
         before_track_log = log
         track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
-                                            smooth=track_smooth, **refine_kw)
+                                            smooth=track_smooth, matching=args.track_matching, identity=args.track_identity, **refine_kw)
 
         def log(train_itr):                               # noqa: F811
             out = before_track_log(train_itr)

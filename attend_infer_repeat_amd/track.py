@@ -2,7 +2,8 @@
 
 A sequence of F frames is F rows of a parser, and its parse is F unrelated object lists: slot t of frame f has nothing to do with slot
 t of frame f + 1.  This module associates them -- tracking by association: no latent is carried from one frame into the next frame's
-inference, the assignment is greedy (the house rule of air_score_match and air_tile_merge), and the metric is CLEAR-MOT.
+inference, the assignment is greedy by default (the house rule of air_score_match and air_tile_merge) or, with matching="optimal", the
+exact optimum of the frame (Hungarian), and the metrics are CLEAR-MOT and, on request, IDF1.
 
 Layout.  The provider has R = S F rows, sequence-major: row r = s F + f (the tile layout r = s Nw + v, with frames for windows).
 1 <= T <= 32 objects per frame, F T <= 32767 (a track id fits the int16 of `track_owner`).
@@ -27,6 +28,19 @@ For frame f with n = clip(num_objects[r], 0, T), in this order:
 So a track survives max_age frames without a sighting: with max_age = 1 an object missing in one frame comes back under its id, and a
 slot held by a track last seen in frame f is free again in frame f + max_age + 2.
 
+Optimal matching (matching="optimal": air_track_associate_optimal).  Steps 1, 2, 4 and 5 as above; step 3 becomes:
+  3. rows: the finite objects, ascending j.  Columns: the 32 track slots, and for each object one "stays unmatched" column of its own.
+     profit(k, j) = 1 + floor(aff * 2^32) as int64 for an admissible pair (the product by a power of two is exact; the 1 makes any
+     admissible pair beat staying unmatched), 0 for staying unmatched; an inadmissible pair is forbidden.  The matches are the
+     one-to-one assignment of the largest summed profit; all solver arithmetic is int64, so that sum is exact and the same for every
+     correct solver.  Among several assignments of that sum: the one `solve_assignment` yields -- a shortest-augmenting-path Hungarian
+     that inserts the objects in ascending j, grows the alternating tree from the inserted object by the unused column of the least
+     reduced cost (equal: the lowest column, slots before the unmatched columns; a column keeps the first tree column that gave it
+     that cost as its predecessor) until a free column is reached, and moves the rows along that path.  Every matched pair is booked
+     as in the greedy step 3.  Matching still ignores birth_score, and a NaN still never matches.
+The greedy rule takes the best pair first and can leave a second object without an admissible partner -- a spurious birth, a coasting
+track and an identity switch where two objects are close or cross; the optimal rule looks at the whole frame.
+
 The identity metric (air_track_score).  gt_boxes [R, G, 4], G <= 8: ground-truth slot g is the SAME object in every frame of a sequence,
 width <= 0 = absent in that frame.  The hypotheses of a frame are its objects j < n with track_id >= 0 and finite boxes.  map[g] = none
 at the start of a sequence.  Per frame:
@@ -39,12 +53,20 @@ at the start of a sequence.  Per frame:
 seq_counts [S, 8] = {gt, matches, misses, fp, idsw, mostly tracked (5 tracked[g] >= 4 present[g]), mostly lost (5 tracked[g] <=
 present[g]), gt objects}, the last three over g with present[g] > 0, in integers.
 
+IDF1 (air_track_idf; Ristani et al. 2016: how long each ground-truth object keeps ONE identity, where MOTA counts a switch once and
+forgets it).  Hypotheses and present ground-truth slots as above.  overlap[s, g, id] = the number of (frame, hypothesis) pairs in which
+present g and a hypothesis with that id have float64 IoU > tau, strictly (an id twice in a frame counts once per hypothesis; an id >=
+n_ids is ignored).  idtp = the largest sum of overlap[s, g, id] over one-to-one assignments of slots to ids: exact, by dynamic
+programming over the 2^G subsets of slots, the ids visited in ascending order.  seq_idf [S, 4] = {idtp, gt_frames (present g summed over
+the frames), hyp_frames (hypotheses summed over the frames), ids with overlap}.  On the host: IDFN = gt_frames - idtp, IDFP = hyp_frames
+- idtp, IDP = idtp / hyp_frames, IDR = idtp / gt_frames, IDF1 = 2 idtp / (gt_frames + hyp_frames); a denominator of 0 gives nan.
+
 `SequenceTracker` owns no engine, like tile.TiledSceneParser and score.ParseScorer: it binds to a parse.SceneParser, refine.ParseRefiner,
 prune.ParsePruner, propose.ParseProposer or tile.TiledSceneParser at R = S F rows, runs that provider's own `parse()` on the frames and
 then, on the same engine stream, its own launch list of libair_hip.so entries (include/air_hip.h), ONE hipGraph after `capture()`
 whatever F is -- the frames are walked inside air_track_associate:
 
-  air_track_associate   the rule above;
+  air_track_associate   the rule above (air_track_associate_optimal with matching="optimal": the same launch list otherwise);
   air_track_owner       track_owner[r, y, x] (int16) = the track id of the step that owns the pixel, -1 for background.
 
 A particle_parse.ParticleParser is refused, with tile.TiledSceneParser's wording: its `parse()` takes no counts and its rows are particles
@@ -52,7 +74,9 @@ of an image, and the buffers the tracker reads next to the `what` rows (`boxes`,
 particle's only behind a pruner or proposer -- bind one of those, they bind as every other provider.
 
 The defaults of iou_gate, appearance_weight, birth_score and max_age are provisional: UNMEASURED on a trained model (profiles/track.txt
-says what was measured).  `reference_associate` and `reference_score` restate the two rules in numpy float64.
+says what was measured); how often the optimal and the greedy matching differ on the parses of a trained model, and what that does to
+IDF1, is unmeasured too (profiles/track_optimal.txt).  `reference_associate`, `reference_score` and `reference_identity` restate the
+rules in numpy float64, `solve_assignment` the solver in Python integers.
 """
 import math
 from collections import OrderedDict
@@ -68,10 +92,14 @@ MAX_IDS = 32767                    # F * T: an id fits int16
 ABSENT, MATCHED, BORN, UNCONFIRMED, OVERFLOW, NONFINITE = range(6)
 STATES = ("absent", "matched", "born", "unconfirmed", "overflow", "nonfinite")
 COUNTS = ("gt", "matches", "misses", "fp", "idsw", "mostly_tracked", "mostly_lost", "gt_objects")
+IDF_COUNTS = ("idtp", "gt_frames", "hyp_frames", "ids_with_overlap")
+MATCHINGS = ("greedy", "optimal")
+PROFIT_SCALE = 4294967296.0        # 2^32: profit = 1 + floor(aff * 2^32)
 DEFAULTS = dict(iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1)
 
 
-def check_arguments(max_steps, n_frames, n_rows=None, iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1):
+def check_arguments(max_steps, n_frames, n_rows=None, iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1,
+                    matching="greedy"):
     """Refuse what air_track_associate refuses (pure host code: importable and callable without a GPU).  Returns (T, F, S) with S = None
     when `n_rows` is not given."""
     gate, w, birth = float(iou_gate), float(appearance_weight), float(birth_score)
@@ -83,6 +111,8 @@ def check_arguments(max_steps, n_frames, n_rows=None, iou_gate=0.1, appearance_w
         raise ValueError("birth_score must be a number within [0, 1], got %r" % (birth_score,))
     if isinstance(max_age, bool) or int(max_age) != max_age or int(max_age) < 0:
         raise ValueError("max_age must be an integer >= 0, got %r" % (max_age,))
+    if matching not in MATCHINGS:
+        raise ValueError("matching must be one of %s, got %r" % (" / ".join(repr(m) for m in MATCHINGS), matching))
     T, F = int(max_steps), int(n_frames)
     if not 1 <= T <= MAX_SLOTS:
         raise ValueError("max_steps must be within 1..%d, got %d" % (MAX_SLOTS, T))
@@ -104,19 +134,69 @@ def _sequential_sum(x):
     return np.cumsum(x, axis=-1)[..., -1]
 
 
+def solve_assignment(profit, admissible):
+    """The solver of air_track_associate_optimal restated in Python integers.  profit [n, m] (int64), admissible [n, m] (bool): row i
+    may take an admissible column c for profit[i, c] or stay unmatched for 0 (its own column m + i).  Returns col [n] (int64): the
+    column of row i, -1 for unmatched -- the one-to-one assignment of the largest summed profit, and among several of them the one
+    this procedure yields (the module text states it): rows inserted in ascending order; from the inserted row the alternating tree
+    grows by the unused column of the least reduced cost minv, the lowest column among equal values, a column keeping the first tree
+    column that gave it that cost (`way`); at a free column the rows along the path move one column on."""
+    import numpy as np
+    profit, admissible = np.asarray(profit).astype(np.int64), np.asarray(admissible).astype(bool)
+    n, m = profit.shape
+    C = m + n
+    NONE = C                                                       # the virtual column an insertion starts from
+    u, v, row = [0] * n, [0] * C, [-1] * C
+    for i in range(n):
+        minv, way, used, in_tree = [None] * C, [NONE] * C, [False] * C, [False] * n
+        j0, i0 = NONE, i
+        while True:
+            if j0 != NONE:
+                used[j0] = True
+            in_tree[i0] = True
+            for c in range(C):
+                if used[c] or not (admissible[i0, c] if c < m else c - m == i0):
+                    continue
+                cur = -(int(profit[i0, c]) if c < m else 0) - u[i0] - v[c]
+                if minv[c] is None or cur < minv[c]:
+                    minv[c], way[c] = cur, j0
+            delta, j1 = min((minv[c], c) for c in range(C) if not used[c] and minv[c] is not None)      # (row i0's own column is open)
+            for r in range(n):
+                if in_tree[r]:
+                    u[r] += delta
+            for c in range(C):
+                if used[c]:
+                    v[c] -= delta
+                elif minv[c] is not None:
+                    minv[c] -= delta
+            j0, i0 = j1, row[j1]
+            if i0 < 0:
+                break
+        while j0 != NONE:
+            j1 = way[j0]
+            row[j0] = i if j1 == NONE else row[j1]
+            j0 = j1
+    col = np.full(n, -1, np.int64)
+    for c in range(m):
+        if row[c] >= 0:
+            col[row[c]] = c
+    return col
+
+
 def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1,
-                        return_margins=False):
+                        return_margins=False, matching="greedy"):
     """air_track_associate restated in numpy float64.  Arrays as the kernel takes them: what [T, R, A], boxes [T, R, 4], score [T, R]
     (fp32), num_objects [R], R = S * n_frames.  Returns track_id [T, R] int32, obj_state [T, R] int8, affinity [T, R] float32,
     prev_frame, prev_slot [T, R] int32, num_tracks [S] int32, track_first, track_last, track_length, track_gaps [S, F * T] int32,
     state_counts [S, 6] int32.  return_margins=True adds how far the decisions are from flipping, per sequence: gate_margin [S] (the
     smallest |iou - iou_gate| over the pairs of step 2), round_margin [S] (the smallest aff(winner) - aff(runner-up) over the greedy
-    rounds with more than one open admissible pair; inf without any)."""
+    rounds with more than one open admissible pair; inf without any).  matching="optimal": air_track_associate_optimal, step 3 by
+    `solve_assignment`; return_margins then adds gate_margin only (there are no greedy rounds)."""
     import numpy as np
     what, boxes, score = (np.asarray(a, np.float32) for a in (what, boxes, score))
     n_in = np.asarray(num_objects).astype(np.int64)
     T, R, A = what.shape
-    T, F, S = check_arguments(T, n_frames, R, iou_gate, appearance_weight, birth_score, max_age)
+    T, F, S = check_arguments(T, n_frames, R, iou_gate, appearance_weight, birth_score, max_age, matching)
     gate, w, birth, max_age = float(iou_gate), float(appearance_weight), float(birth_score), int(max_age)
     FT = F * T
     out = {"track_id": np.full((T, R), -1, np.int32), "obj_state": np.zeros((T, R), np.int8), "affinity": np.zeros((T, R), np.float32),
@@ -155,17 +235,28 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
                     gate_margin[s] = min(gate_margin[s], abs(iou - gate))
                     if iou > gate:
                         aff[(k, j)] = (1.0 - w) * iou + w / (1.0 + float(msd[q]))
-            while aff:                                             # 3. greedy matching
-                ranked = sorted(aff, key=lambda kj: (-aff[kj], live[kj[0]]["id"], kj[1]))
-                k, j = ranked[0]
-                if len(ranked) > 1:
-                    round_margin[s] = min(round_margin[s], aff[ranked[0]] - aff[ranked[1]])
+            def matched(k, j):
                 t = live[k]
                 state[j] = MATCHED
                 out["track_id"][j, r], out["prev_frame"][j, r], out["prev_slot"][j, r] = t["id"], t["f"], t["j"]
                 out["affinity"][j, r] = np.float32(aff[(k, j)])
                 t["gaps"] += 1 if t["age"] > 0 else 0
                 t["age"], t["length"], t["f"], t["j"] = 0, t["length"] + 1, f, j
+
+            if matching == "optimal" and aff:                      # 3. the optimal assignment
+                profit, admissible = np.zeros((len(finite), MAX_SLOTS), np.int64), np.zeros((len(finite), MAX_SLOTS), bool)
+                for (k, j), v in aff.items():
+                    profit[finite.index(j), k], admissible[finite.index(j), k] = 1 + int(math.floor(v * PROFIT_SCALE)), True
+                for q, k in enumerate(solve_assignment(profit, admissible)):
+                    if k >= 0:
+                        matched(int(k), finite[q])
+                aff = {}
+            while aff:                                             # 3. greedy matching
+                ranked = sorted(aff, key=lambda kj: (-aff[kj], live[kj[0]]["id"], kj[1]))
+                k, j = ranked[0]
+                if len(ranked) > 1:
+                    round_margin[s] = min(round_margin[s], aff[ranked[0]] - aff[ranked[1]])
+                matched(k, j)
                 aff = {kj: v for kj, v in aff.items() if kj[0] != k and kj[1] != j}
             for j in finite:                                       # 4. births
                 if state[j] != UNCONFIRMED or not float(score[j, r]) >= birth:
@@ -191,7 +282,9 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
             retire(k)
         out["num_tracks"][s] = next_id
     if return_margins:
-        out["gate_margin"], out["round_margin"] = gate_margin, round_margin
+        out["gate_margin"] = gate_margin
+        if matching == "greedy":
+            out["round_margin"] = round_margin
     return out
 
 
@@ -272,10 +365,74 @@ def mot_summary(counts, sum_iou) -> Dict[str, float]:
             "false_positives": c["fp"], "misses": c["misses"], "gt": c["gt"], "matches": c["matches"], "gt_objects": c["gt_objects"]}
 
 
+def reference_identity(boxes, num_objects, track_id, gt_boxes, n_frames, tau=0.5, n_ids=None):
+    """air_track_idf restated in numpy float64.  boxes [T, R, 4], num_objects [R], track_id [T, R], gt_boxes [R, G, 4] (or
+    [S, F, G, 4]); n_ids: None = n_frames * T.  Returns overlap [S, G, n_ids] int32 and seq_idf [S, 4] int32 (IDF_COUNTS)."""
+    import numpy as np
+    boxes = np.asarray(boxes, np.float32)
+    gt = np.asarray(gt_boxes, np.float32)
+    gt = gt.reshape(-1, gt.shape[-2], 4)
+    ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
+    T, R = ids.shape
+    G, F = gt.shape[1], int(n_frames)
+    n_ids = F * T if n_ids is None else int(n_ids)
+    if not 1 <= G <= MAX_GT:
+        raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+    if F < 1 or R % F or gt.shape[0] != R:
+        raise ValueError("%d rows / %d ground-truth rows are not sequences of %d frames" % (R, gt.shape[0], F))
+    tau = float(tau)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError("tau must be within [0, 1], got %r" % (tau,))
+    if not 1 <= n_ids <= MAX_IDS:
+        raise ValueError("n_ids must be within 1..%d, got %d" % (MAX_IDS, n_ids))
+    S = R // F
+    overlap, seq_idf = np.zeros((S, G, n_ids), np.int32), np.zeros((S, 4), np.int32)
+    masks = np.arange(1 << G)
+    for s in range(S):
+        gt_frames = hyp_frames = 0
+        last_id = -1
+        for f in range(F):
+            r = s * F + f
+            n = int(min(max(n_in[r], 0), T))
+            hyp = [j for j in range(n) if ids[j, r] >= 0 and np.isfinite(boxes[j, r]).all()]
+            present = [g for g in range(G) if gt[r, g, 2] > 0]
+            gt_frames, hyp_frames = gt_frames + len(present), hyp_frames + len(hyp)
+            for j in hyp:
+                if ids[j, r] >= n_ids:
+                    continue
+                last_id = max(last_id, int(ids[j, r]))
+                for g in present:
+                    if box_iou(gt[r, g], boxes[j, r]) > tau:
+                        overlap[s, g, ids[j, r]] += 1
+        best = np.zeros(1 << G, np.int64)                          # best[m]: the ids so far assigned within the subset m of slots
+        with_overlap = 0
+        for i in range(last_id + 1):
+            col = overlap[s, :, i].astype(np.int64)
+            if not col.any():
+                continue
+            with_overlap += 1
+            new = best.copy()
+            for g in range(G):
+                has = (masks >> g) & 1 == 1
+                new[has] = np.maximum(new[has], best[masks[has] ^ (1 << g)] + col[g])
+            best = new
+        seq_idf[s] = [best[-1], gt_frames, hyp_frames, with_overlap]
+    return {"overlap": overlap, "seq_idf": seq_idf}
+
+
+def idf_summary(totals) -> Dict[str, float]:
+    """the identity figures of summed seq_idf rows (IDF_COUNTS order; only the first three enter); a denominator of 0 gives nan"""
+    idtp, gt_frames, hyp_frames = (int(v) for v in tuple(totals)[:3])
+    div = lambda a, b: a / b if b else float("nan")
+    return {"idf1": div(2 * idtp, gt_frames + hyp_frames), "idp": div(idtp, hyp_frames), "idr": div(idtp, gt_frames), "idtp": idtp,
+            "idfp": hyp_frames - idtp, "idfn": gt_frames - idtp, "gt_frames": gt_frames, "hyp_frames": hyp_frames}
+
+
 class IdentityScores:
     """The identity metric of a stage (the tracker on its own table, the smoother on its two): the air_track_score launch of every
     key used so far with its buffers and graph (`entries`, at most four: a sweep over tau must not pile up buffers and graphs), the
-    staging copy of the ground truth, and the running totals on the device."""
+    staging copy of the ground truth, and the running totals on the device.  An entry made with identity=True runs air_track_idf
+    behind air_track_score (one graph still) and feeds `totals_idf`."""
 
     def __init__(self, stage, S):
         import torch
@@ -284,16 +441,22 @@ class IdentityScores:
         with torch.cuda.device(dev):
             self.totals_i = torch.zeros((8,), dtype=torch.int64, device=dev)
             self.totals_f = torch.zeros((1,), dtype=torch.float64, device=dev)
+            self.totals_idf = torch.zeros((4,), dtype=torch.int64, device=dev)
 
-    def entry(self, key, G, tau, T, n_frames, boxes, counts, ids):
+    def entry(self, key, G, tau, T, n_frames, boxes, counts, ids, identity=False, n_ids=None):
         """the air_track_score launch on a table of T rows by S * n_frames columns (boxes, counts, ids) with its buffers -- gt_boxes,
-        seq_counts, seq_iou, gt_match -- kept under key + (G, tau); captured when the stage holds a graph"""
+        seq_counts, seq_iou, gt_match -- kept under key + (G, tau); captured when the stage holds a graph.  identity=True: kept under
+        key + (G, tau, "idf"), with air_track_idf behind it and its buffers seq_idf, idf_overlap [S, G, n_ids]"""
         import torch
         eng, S, N = self.engine, self.S, self.S * n_frames
         key = key + (int(G), float(tau))
         G, tau_f = key[-2:]
+        if identity:
+            key = key + ("idf",)
         entry = self.entries.get(key)
         if entry is None:
+            if identity and not 1 <= int(n_ids) <= MAX_IDS:
+                raise ValueError("n_ids must be within 1..%d, got %r" % (MAX_IDS, n_ids))
             if not 1 <= G <= MAX_GT:
                 raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
             if not 0.0 <= tau_f <= 1.0:
@@ -307,6 +470,12 @@ class IdentityScores:
                          "gt_match": torch.zeros((N, G), dtype=torch.int32, device=dev), "graph": None}
             entry["plan"] = [(L.air_track_score, (p(boxes), p(counts), p(ids), p(entry["gt_boxes"]), tau_f, T, G, S, n_frames, N,
                                                   p(entry["seq_counts"]), p(entry["seq_iou"]), p(entry["gt_match"])), "air_track_score")]
+            if identity:
+                with torch.cuda.device(dev):
+                    entry["seq_idf"] = torch.zeros((S, 4), dtype=torch.int32, device=dev)
+                    entry["idf_overlap"] = torch.zeros((S, G, int(n_ids)), dtype=torch.int32, device=dev)
+                entry["plan"].append((L.air_track_idf, (p(boxes), p(counts), p(ids), p(entry["gt_boxes"]), tau_f, T, G, S, n_frames, N,
+                                                        int(n_ids), p(entry["idf_overlap"]), p(entry["seq_idf"])), "air_track_idf"))
             if self.stage._graph is not None:
                 eng.synchronize()
                 entry["graph"] = eng._capture_plans([entry["plan"]])
@@ -336,6 +505,9 @@ class IdentityScores:
         import torch
         eng = self.engine
         out = {k: entry[k] for k in ("seq_counts", "seq_iou", "gt_match")}
+        identity = "seq_idf" in entry
+        if identity:
+            out.update(seq_idf=entry["seq_idf"], idf_overlap=entry["idf_overlap"])
         if accumulate is not None:
             with torch.cuda.stream(eng.stream):
                 ti, tf = entry["seq_counts"].sum(0, dtype=torch.int64), entry["seq_iou"].sum(0, keepdim=True)
@@ -345,7 +517,15 @@ class IdentityScores:
                 else:
                     self.totals_i.copy_(ti)
                     self.totals_f.copy_(tf)
+                if identity:
+                    td = entry["seq_idf"].sum(0, dtype=torch.int64)
+                    if accumulate:
+                        self.totals_idf += td
+                    else:
+                        self.totals_idf.copy_(td)
             out.update(totals_i=self.totals_i, totals_f=self.totals_f)
+            if identity:
+                out.update(totals_idf=self.totals_idf)
         eng.wait_for_engine()
         return out
 
@@ -357,6 +537,7 @@ class IdentityScores:
         with torch.cuda.stream(eng.stream):
             self.totals_i.zero_()
             self.totals_f.zero_()
+            self.totals_idf.zero_()
         eng.wait_for_engine()
 
     def summary(self) -> Dict[str, float]:
@@ -366,15 +547,20 @@ class IdentityScores:
         flat = torch.cat([self.totals_i.double(), self.totals_f]).tolist()
         return mot_summary(flat[:8], flat[8])
 
+    def identity_summary(self) -> Dict[str, float]:
+        """idf_summary of everything scored with identity=True since the last reset (ONE read-back)"""
+        self.engine.wait_for_engine()
+        return idf_summary(self.totals_idf.tolist())
+
 
 class SequenceTracker(BoundStage):
     ACCEPTS = ("scene", "refiner", "subset", "tiled")
     REFUSALS = TiledSceneParser.REFUSALS
 
     def __init__(self, provider, n_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
-                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"]):
+                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy"):
         self._rows = self.bind(provider)
-        T, F, S = check_arguments(provider.T, n_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age)
+        T, F, S = check_arguments(provider.T, n_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age, matching)
         import torch
         from . import hip as H
         self.provider, self.engine = provider, provider.engine
@@ -382,6 +568,7 @@ class SequenceTracker(BoundStage):
         self.T, self.R, self.S, self.F = T, int(provider.R), S, F
         self.iou_gate, self.appearance_weight, self.birth_score, self.max_age = (float(iou_gate), float(appearance_weight),
                                                                                  float(birth_score), int(max_age))
+        self.matching = matching
         self._what = self._rows["what"]
         self.A = int(self._what.shape[-1])
         self.img_size = tuple(int(v) for v in provider.owner.shape[1:])
@@ -398,7 +585,7 @@ class SequenceTracker(BoundStage):
         self._H = H
         self.scores = IdentityScores(self, S)
         self._score = self.scores.entries                          # (G, tau) -> buffers, plan, graph
-        self.totals_i, self.totals_f = self.scores.totals_i, self.scores.totals_f
+        self.totals_i, self.totals_f, self.totals_idf = self.scores.totals_i, self.scores.totals_f, self.scores.totals_idf
         self._rebuild()
         self.engine.synchronize()
 
@@ -407,13 +594,14 @@ class SequenceTracker(BoundStage):
         provider, T, R, S, F = self.provider, self.T, self.R, self.S, self.F
         L, p = self._H.lib(), self._H._p
         Hi, Wi = self.img_size
+        associate = "air_track_associate_optimal" if self.matching == "optimal" else "air_track_associate"
         self.segments = OrderedDict([
-            ("associate", [(L.air_track_associate,
+            ("associate", [(getattr(L, associate),
                             (p(self._what), p(provider.boxes), p(provider.score), p(provider.num_objects), T, S, F, R, self.A,
                              self.iou_gate, self.appearance_weight, self.birth_score, self.max_age, p(self.track_id), p(self.obj_state),
                              p(self.affinity), p(self.prev_frame), p(self.prev_slot), p(self.num_tracks), p(self.track_first),
                              p(self.track_last), p(self.track_length), p(self.track_gaps), p(self.state_counts)),
-                            "air_track_associate")]),
+                            associate)]),
             ("owner", [(L.air_track_owner, (p(provider.owner), p(self.track_id), T, R, Hi, Wi, p(self.track_owner)),
                         "air_track_owner")])])
         self._plan = [e for seg in self.segments.values() for e in seg]
@@ -463,16 +651,19 @@ class SequenceTracker(BoundStage):
         return out
 
     # ---- the identity metric ------------------------------------------------------------------------------------------------
-    def _score_entry(self, G, tau):
+    def _score_entry(self, G, tau, identity=False):
         par = self.provider
-        return self.scores.entry((), G, tau, self.T, self.F, par.boxes, par.num_objects, self.track_id)
+        return self.scores.entry((), G, tau, self.T, self.F, par.boxes, par.num_objects, self.track_id, identity, self.F * self.T)
 
-    def score(self, gt_boxes, tau=0.5, accumulate=True):
+    def score(self, gt_boxes, tau=0.5, accumulate=True, identity=False):
         """Score the LATEST `track()` against gt_boxes [R, G, 4] (or [S, F, G, 4]; G <= 8; slot g is the same object in every frame of
         a sequence, width <= 0 = absent).  Returns device tensors that the next call with the same (G, tau) overwrites: seq_counts
         [S, 8] int32 (COUNTS), seq_iou [S] float64, gt_match [R, G] int32, and the running totals_i [8] int64 / totals_f [1] float64,
-        which this call adds to (accumulate=False: restarts) on the device, with no read-back.  Same stream contract as `track`."""
-        return self.scores.result(self.scores.run(gt_boxes, self.F, lambda G: self._score_entry(G, tau)), bool(accumulate))
+        which this call adds to (accumulate=False: restarts) on the device, with no read-back.  identity=True runs air_track_idf
+        behind air_track_score and adds seq_idf [S, 4] int32 (IDF_COUNTS), idf_overlap [S, G, F * T] int32 and the running totals_idf
+        [4] int64 (`identity_summary()` reads them).  Same stream contract as `track`."""
+        return self.scores.result(self.scores.run(gt_boxes, self.F, lambda G: self._score_entry(G, tau, bool(identity))),
+                                  bool(accumulate))
 
     def reset(self):
         """zero the totals"""
@@ -483,3 +674,9 @@ class SequenceTracker(BoundStage):
         sum_iou / matches, id_switches, mostly_tracked, mostly_lost (fractions of the ground-truth objects), false_positives, misses,
         and the counts gt, matches, gt_objects.  A denominator of 0 gives nan."""
         return self.scores.summary()
+
+    def identity_summary(self) -> Dict[str, float]:
+        """The identity figures of everything scored with identity=True since the last reset (ONE read-back): idf1 = 2 idtp /
+        (gt_frames + hyp_frames), idp = idtp / hyp_frames, idr = idtp / gt_frames, and the counts idtp, idfp, idfn, gt_frames,
+        hyp_frames.  A denominator of 0 gives nan."""
+        return self.scores.identity_summary()

@@ -376,29 +376,32 @@ class TrajectorySmoother(BoundStage):
         return out
 
     # ---- the identity metric on the tables ------------------------------------------------------------------------------------
-    def _score_entry(self, table, G, tau):
+    def _score_entry(self, table, G, tau, identity=False):
         t, n_frames = (self.sm, self.F) if table == "completed" else (self.fc, self.horizon)
         if n_frames * self.C > MAX_IDS:
             raise ValueError("air_track_score takes at most %d rows per sequence; %d frames of %d completed rows are %d"
                              % (MAX_IDS, n_frames, self.C, n_frames * self.C))
-        return self.scores.entry((table,), G, tau, self.C, n_frames, t["boxes"], t["count"], t["id"])
+        return self.scores.entry((table,), G, tau, self.C, n_frames, t["boxes"], t["count"], t["id"], identity, self.F * self.window_T)
 
-    def _run_score(self, table, gt_boxes, tau, n_frames):
-        return self.scores.run(gt_boxes, n_frames, lambda G: self._score_entry(table, G, tau))
+    def _run_score(self, table, gt_boxes, tau, n_frames, identity=False):
+        return self.scores.run(gt_boxes, n_frames, lambda G: self._score_entry(table, G, tau, bool(identity)))
 
-    def score(self, gt_boxes, tau=0.5, accumulate=True):
+    def score(self, gt_boxes, tau=0.5, accumulate=True, identity=False):
         """SequenceTracker.score on the COMPLETED table of the latest `run()`: the unchanged air_track_score with T := C on sm_boxes,
         sm_count, sm_id, so a frame a track coasted over counts a match when the filled box is on the object.  gt_boxes [R, G, 4] or
         [S, F, G, 4].  Returns seq_counts [S, 8] int32 (track.COUNTS), seq_iou [S] float64, gt_match [R, G] int32 (the matched ROW)
-        and this object's own running totals_i [8] int64 / totals_f [1] float64 (accumulate=False: restarts), all on the device."""
-        return self.scores.result(self._run_score("completed", gt_boxes, tau, self.F), bool(accumulate))
+        and this object's own running totals_i [8] int64 / totals_f [1] float64 (accumulate=False: restarts), all on the device.
+        identity=True: air_track_idf behind it (the ids are the tracker's: n_ids = F T), as SequenceTracker.score describes --
+        seq_idf, idf_overlap, totals_idf, read by `identity_summary()`."""
+        return self.scores.result(self._run_score("completed", gt_boxes, tau, self.F, identity), bool(accumulate))
 
-    def score_forecast(self, gt_future_boxes, tau=0.5):
+    def score_forecast(self, gt_future_boxes, tau=0.5, identity=False):
         """the same kernel on the FORECAST table with F := Hz: gt_future_boxes [S Hz, G, 4] or [S, Hz, G, 4], slot g the same object
-        over the horizon.  Returns seq_counts [S, 8], seq_iou [S], gt_match [S Hz, G]; nothing is accumulated."""
+        over the horizon.  Returns seq_counts [S, 8], seq_iou [S], gt_match [S Hz, G], with identity=True seq_idf [S, 4] and
+        idf_overlap [S, G, F T] too; nothing is accumulated."""
         if self.fc is None:
             raise ValueError("score_forecast needs a horizon >= 1; this smoother was built with horizon=0")
-        return self.scores.result(self._run_score("forecast", gt_future_boxes, tau, self.horizon))
+        return self.scores.result(self._run_score("forecast", gt_future_boxes, tau, self.horizon, identity))
 
     def reset(self):
         """zero the totals"""
@@ -407,3 +410,7 @@ class TrajectorySmoother(BoundStage):
     def summary(self) -> Dict[str, float]:
         """track.mot_summary of everything `score` took since the last reset (ONE read-back)"""
         return self.scores.summary()
+
+    def identity_summary(self) -> Dict[str, float]:
+        """track.idf_summary of everything `score(identity=True)` took since the last reset (ONE read-back)"""
+        return self.scores.identity_summary()

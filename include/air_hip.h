@@ -887,7 +887,35 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *   seq_counts[S,8] (int32) = {gt, matches, misses, fp, idsw, mostly tracked (5 tracked[g] >= 4 present[g]), mostly lost
  *   (5 tracked[g] <= present[g]), gt objects (present[g] > 0)}, the last three over g with present[g] > 0;  seq_iou[S] (float64) =
  *   sum_iou;  gt_match[R,G] (int32) = the matched slot j, -1 otherwise.  tau in [0, 1] (AIR_E_SHAPE).  boxes / gt_boxes 16-byte,
- *   seq_iou 8-byte, everything else 4-byte aligned (AIR_E_ALIGN).                                                                   */
+ *   seq_iou 8-byte, everything else 4-byte aligned (AIR_E_ALIGN).
+ * air_track_associate_optimal: air_track_associate -- the same arguments, checks, outputs and steps 1, 2, 4 and 5 -- with step 3
+ *   replaced by the OPTIMAL assignment of the frame:
+ *   3. rows: the finite objects, ascending j.  Columns: the 32 track slots, and for each object one "stays unmatched" column of its
+ *      own (column 32 + j).  profit(k, j) = 1 + floor(aff 2^32) as int64 for an admissible pair (the product by a power of two is
+ *      exact; the 1 makes any admissible pair beat staying unmatched), 0 for staying unmatched; an inadmissible pair is forbidden.
+ *      The matches are the one-to-one assignment of the largest summed profit; all solver arithmetic is int64, so that sum is exact.
+ *      Among several assignments of that sum: the one a shortest-augmenting-path Hungarian yields that inserts the objects in
+ *      ascending j, grows the alternating tree from the inserted object by the unused column of the least reduced cost (equal: the
+ *      lowest column, slots before the unmatched columns; a column keeps the first tree column that gave it that cost as its
+ *      predecessor) until a free column is reached, and moves the rows along that path.  One wavefront runs it, lane = column.
+ *      Every matched pair: the object is 1 MATCHED, track_id, prev_frame / prev_slot, affinity = aff rounded once to fp32 and the
+ *      track's gaps, age, length and last sighting as in the greedy step 3.  Matching ignores birth_score; a NaN never matches.
+ * air_track_idf: the IDF1 counts (Ristani et al. 2016), one 256-thread workgroup per sequence, the frames walked inside.  Hypotheses
+ *   and present ground-truth slots as in air_track_score.  overlap[S,G,n_ids] (int32, every element written): overlap[s,g,id] = the
+ *   number of (frame, hypothesis) pairs in which present g and a hypothesis with that id have float64 box IoU > tau, strictly (an id
+ *   twice in a frame counts once per hypothesis; an id >= n_ids is ignored).  seq_idf[S,4] (int32) = {idtp, gt_frames, hyp_frames,
+ *   ids_with_overlap}: idtp = the largest sum of overlap[s,g,id] over one-to-one assignments of slots to ids, exact, by dynamic
+ *   programming over the 2^G subsets of slots with the ids visited in ascending order up to the largest id seen (an id without
+ *   overlap is passed over); gt_frames = present g summed over the frames; hyp_frames = hypotheses summed over the frames;
+ *   ids_with_overlap = ids with a nonzero column.  IDFN = gt_frames - idtp, IDFP = hyp_frames - idtp, IDF1 = 2 idtp / (gt_frames +
+ *   hyp_frames).  The limits and checks of air_track_score, and 1 <= n_ids <= 32767 (AIR_E_SHAPE).  boxes / gt_boxes 16-byte,
+ *   everything else 4-byte aligned (AIR_E_ALIGN).                                                                                  */
+AIR_ENGINE_API int air_track_associate_optimal(const float *what, const float *boxes, const float *score, const int *num_objects, int T,
+                    int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
+                    int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,
+                    int *track_first, int *track_last, int *track_length, int *track_gaps, int *state_counts, void *stream);
+AIR_ENGINE_API int air_track_idf(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
+                    int T, int G, int S, int F, int R, int n_ids, int *overlap, int *seq_idf, void *stream);
 AIR_ENGINE_API int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
                     int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
                     int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,

@@ -14,6 +14,12 @@ matching loop has work).  The frames of a sequence are one sparse random image s
   score      the air_track_score graph alone, against ground truth cut from the parse's own boxes;
   and every entry launched eagerly on its own.
 
+--matching optimal adds a second captured tracker with matching="optimal" over the SAME parser: its agreement with
+track.reference_associate(matching="optimal"), the share of frames (and sequences) on which its track ids differ from the greedy
+tracker's, its tail graph timed in turns with the greedy one (greedy, optimal, greedy, optimal) in this process, and
+air_track_associate_optimal launched eagerly beside air_track_associate.  --identity scores with identity=True: the air_track_score +
+air_track_idf graph beside the air_track_score graph, air_track_idf eagerly beside air_track_score, and the IDF figures.
+
 Timing: a warm-up, then 5 repeats of --iters calls each between device events; the median repeat is reported with all repeats.  The
 provider and the tracked route alternate inside one process."""
 import argparse
@@ -93,6 +99,39 @@ def one_length(args, F):
     tk.score(gt, accumulate=False)
     res["score_summary"] = tk.summary()
     entry = next(iter(tk._score.values()))
+    opt = None
+    if args.matching == "optimal":
+        opt = track.SequenceTracker(ps, F, birth_score=0.0, matching="optimal")
+        opt.capture()
+        greedy_ids = host(out["track_id"]).copy()
+        oo = opt.track(frames, counts)
+        torch.cuda.synchronize()
+        oref = track.reference_associate(host(oo["what"]).reshape(T, R, -1), host(oo["boxes"]), host(oo["score"]), host(oo["num_objects"]),
+                                         F, birth_score=0.0, return_margins=True, matching="optimal")
+        osafe = oref["gate_margin"] >= 1e-9
+        orows = np.repeat(osafe, F)
+        oagree = {k: bool((host(oo[k])[:, orows] == oref[k][:, orows]).all()) for k in ("track_id", "obj_state", "prev_frame", "prev_slot")}
+        oagree["affinity_bits"] = bool((host(oo["affinity"])[:, orows].view(np.uint32) == oref["affinity"][:, orows].view(np.uint32)).all())
+        for k in ("num_tracks", "track_first", "track_last", "track_length", "track_gaps", "state_counts"):
+            oagree[k] = bool((host(oo[k])[osafe] == oref[k][osafe]).all())
+        differ = (host(oo["track_id"]) != greedy_ids).any(0)
+        res.update(optimal_agreement=oagree, optimal_sequences_inside_margin=int(osafe.sum()), optimal_tracks=int(oref["num_tracks"].sum()),
+                   optimal_state_counts=dict(zip(track.STATES, oref["state_counts"].sum(0).tolist())),
+                   frames_where_matchings_differ=float(differ.mean()),
+                   sequences_where_matchings_differ=float(differ.reshape(S, F).any(1).mean()))
+        if not all(oagree.values()):
+            print(json.dumps(res))
+            raise SystemExit("the optimal tracker and the host reference disagree: %r" % (oagree,))
+        opt.score(gt, accumulate=False, identity=args.identity)
+        res["optimal_score_summary"] = opt.summary()
+        if args.identity:
+            res["optimal_identity_summary"] = opt.identity_summary()
+    id_entry = None
+    if args.identity:
+        tk.track(frames, counts)
+        tk.score(gt, accumulate=False, identity=True)
+        res["identity_summary"] = tk.identity_summary()
+        id_entry = tk._score[(G, 0.5, "idf")]
     rows_in = frames.reshape(R, *cfg.img_size)
     provider_ms, provider_reps = median_ms(lambda: ps.parse(rows_in, counts), args.iters, stream)
     tracked_ms, tracked_reps = median_ms(lambda: tk.track(frames, counts), args.iters, stream)
@@ -101,6 +140,19 @@ def one_length(args, F):
     torch.cuda.synchronize()
     tail_ms, tail_reps = median_ms(lambda: eng._replay_or_run(tk._graph, tk._plan), args.iters, eng.stream)
     score_ms, score_reps = median_ms(lambda: eng._replay_or_run(entry["graph"], entry["plan"]), args.iters, eng.stream)
+    if opt is not None:
+        turns = {"greedy": [], "optimal": []}
+        for _ in range(2):
+            for name, t in (("greedy", tk), ("optimal", opt)):
+                turns[name].append(median_ms(lambda: eng._replay_or_run(t._graph, t._plan), args.iters, eng.stream))
+        for name, v in turns.items():
+            res["tail_%s_turns_ms" % name] = [m for m, _ in v]
+            res["tail_%s_repeats_ms" % name] = [r for _, r in v]
+    if id_entry is not None:
+        idf_ms, idf_reps = median_ms(lambda: eng._replay_or_run(id_entry["graph"], id_entry["plan"]), args.iters, eng.stream)
+        score_ms2, score_reps2 = median_ms(lambda: eng._replay_or_run(entry["graph"], entry["plan"]), args.iters, eng.stream)
+        res.update(score_identity_graph_ms=idf_ms, score_identity_repeats_ms=idf_reps, score_graph_again_ms=score_ms2,
+                   score_again_repeats_ms=score_reps2)
     res.update(provider_graph_ms=provider_ms, provider_repeats_ms=provider_reps, tracked_graph_ms=tracked_ms, tracked_repeats_ms=tracked_reps,
                provider_graph_again_ms=provider_ms2, provider_again_repeats_ms=provider_reps2, tracked_graph_again_ms=tracked_ms2,
                tracked_again_repeats_ms=tracked_reps2, tail_graph_ms=tail_ms, tail_repeats_ms=tail_reps, score_graph_ms=score_ms,
@@ -108,7 +160,7 @@ def one_length(args, F):
                tracked_added_ms=tracked_ms - provider_ms, frames_per_s=R / (tracked_ms * 1e-3))
     per = {}
     for _ in range(7):
-        for (fn, a, name) in tk._plan + entry["plan"]:
+        for (fn, a, name) in tk._plan + (opt._plan[:1] if opt is not None else []) + (id_entry or entry)["plan"]:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(eng.stream)
             _lib.check(fn(*a, eng._sp()), name)
@@ -116,6 +168,9 @@ def one_length(args, F):
             e1.synchronize()
             per.setdefault(name, []).append(e0.elapsed_time(e1) * 1e3)
     res["eager_launch_us"] = {k: statistics.median(v) for k, v in per.items()}
+    if opt is not None:
+        res["optimal_over_greedy_associate"] = res["eager_launch_us"]["air_track_associate_optimal"] / res["eager_launch_us"]["air_track_associate"]
+        opt.release_graphs()
     tk.release_graphs(); ps.release_graphs()
     return res
 
@@ -125,6 +180,8 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 32])
     ap.add_argument("--rows", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--matching", choices=("greedy", "optimal"), default="greedy")
+    ap.add_argument("--identity", action="store_true")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("track_bench measures on the GPU; there is no CPU fallback")
