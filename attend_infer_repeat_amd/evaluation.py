@@ -136,13 +136,9 @@ def make_parse_fig(air, checkpoint_dir=None, global_step=None, n_samples=10, obs
     return fig
 
 
-def _refine_kw(refine, refine_lr):
-    if refine is None:
-        return {}
-    rk = dict(refine=int(refine))
-    if refine_lr is not None:
-        rk["refine_lr"] = tuple(float(v) for v in refine_lr)
-    return rk
+def _particle_sums(out):
+    """[number of images whose kept particle is not particle 0, sum of the effective sample size]"""
+    return [(out["best_particle"] != 0).double().sum(), out["ess"].double().sum()]
 
 
 def _refine_sums(out):
@@ -165,19 +161,58 @@ def _prune_sums(out):
             bits(best & ~m0).double().sum(), gain.sum()]
 
 
-def _propose_kw(propose):
-    """keyword arguments of air.parse for propose=P | (P, rounds): the spec as a plain int / list, so that the record can be written"""
-    if propose is None:
-        return {}
-    return dict(propose=[int(v) for v in propose] if isinstance(propose, (tuple, list)) else int(propose))
-
-
 def _propose_sums(out):
     """[objects of the result that came from a proposal, number of images whose count changed, sum of the objective gain] of a parse
     behind residual proposals (an image whose gain is NaN or infinite adds 0; the callers divide by the number of all images)"""
     import torch
     gain = torch.nan_to_num(out["objective"] - out["objective_start"].double(), nan=0.0, posinf=0.0, neginf=0.0)
     return [out["objects_proposed_kept"].double().sum(), (out["num_objects"] != out["num_objects_start"]).double().sum(), gain.sum()]
+
+
+class _ParseExtras:
+    """What a parse carries on top of the plain one -- particles, refine, prune, propose -- as the parse loggers need it: `kw`, the
+    keyword arguments of air.parse / parse_scorer / score_parse (plain ints, lists and tuples, so that the record can be written);
+    `suffix`, what the label of the line says about them; start(device) / add(out) / figures(n_images), the sums of their figures
+    over the parses `out` in float64 on the device and the means per image by name.  The gain of the subset search is objective_gain,
+    prune_objective_gain / propose_objective_gain next to refine=N, whose own gain keeps the name."""
+
+    def __init__(self, particles, select, refine, refine_lr, prune, propose):
+        self.kw, self.suffix, self.sums, self.names = {}, '', [], []
+        gain = "objective_gain"
+        if particles is not None:
+            self.kw.update(particles=int(particles), select=select)
+            self.suffix += '({}, {})'.format(int(particles), select)
+            self._figures(_particle_sums, "best_particle_moved", "ess")
+        if refine is not None:
+            self.kw["refine"] = int(refine)
+            if refine_lr is not None:
+                self.kw["refine_lr"] = tuple(float(v) for v in refine_lr)
+            self.suffix += '+refine({})'.format(int(refine))
+            self._figures(_refine_sums, gain, "refine_moved")
+        if prune is not None:
+            self.kw["prune"] = prune
+            self.suffix += '+prune({})'.format(prune)
+            self._figures(_prune_sums, "count_changed", "objects_dropped", "objects_added", gain if refine is None else "prune_" + gain)
+        if propose is not None:
+            self.kw["propose"] = [int(v) for v in propose] if isinstance(propose, (tuple, list)) else int(propose)
+            self.suffix += '+propose({})'.format(self.kw["propose"])
+            self._figures(_propose_sums, "objects_added_from_residual", "count_changed", gain if refine is None else "propose_" + gain)
+
+    def _figures(self, sums, *names):
+        self.sums.append(sums)
+        self.names += names
+
+    def start(self, device):
+        import torch
+        self.total = torch.zeros(len(self.names), dtype=torch.float64, device=device)
+
+    def add(self, out):
+        import torch
+        if self.sums:
+            self.total += torch.stack([v for sums in self.sums for v in sums(out)])
+
+    def figures(self, n_images):
+        return dict(zip(self.names, (self.total / n_images).tolist()))
 
 
 def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time=True, particles=None, select="joint", refine=None,
@@ -197,61 +232,31 @@ def make_parse_logger(air, data_fn, num_batches, name, writer=None, measure_time
     came from a proposal, mean per image), count_changed and objective_gain (of the proposer; propose_objective_gain next to
     refine=N); the record names the spec.  Prints / writes one line like make_expr_logger."""
     import torch
-    pk = {} if particles is None else dict(particles=int(particles), select=select)
-    rk = _refine_kw(refine, refine_lr)
-    qk = {} if prune is None else dict(prune=prune)
-    uk = _propose_kw(propose)
+    extras = _ParseExtras(particles, select, refine, refine_lr, prune, propose)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
         n = max(int(n), 1)
         start = time.time()
-        tot = torch.zeros(3 + (2 if pk else 0) + (2 if rk else 0) + (4 if qk else 0) + (3 if uk else 0), dtype=torch.float64,
-                          device=air.obs.device)
+        tot = torch.zeros(3, dtype=torch.float64, device=air.obs.device)
+        extras.start(air.obs.device)
         images = 0
         for _ in range(n):
             obs, nums = data_fn()
-            out = air.parse(obs, **pk, **rk, **qk, **uk)
+            out = air.parse(obs, **extras.kw)
             gt = nums.sum(0).reshape(-1).to(torch.int64)
             cnt = out["num_objects"].to(torch.int64)
-            sums = [(cnt == gt).double().sum(), out["count_prob"].double().sum(), cnt.double().sum()]
-            if pk:
-                sums += [(out["best_particle"] != 0).double().sum(), out["ess"].double().sum()]
-            if rk:
-                sums += _refine_sums(out)
-            if qk:
-                sums += _prune_sums(out)
-            if uk:
-                sums += _propose_sums(out)
-            tot += torch.stack(sums)
+            tot += torch.stack([(cnt == gt).double().sum(), out["count_prob"].double().sum(), cnt.double().sum()])
+            extras.add(out)
             images += int(cnt.numel())
-        vals = (tot / images).tolist()
-        acc = dict(map_num_step_acc=vals[0], count_prob=vals[1], num_objects=vals[2])
-        if pk:
-            acc.update(best_particle_moved=vals[3], ess=vals[4])
-        if rk:
-            at = 5 if pk else 3
-            acc.update(objective_gain=vals[at], refine_moved=vals[at + 1])
-        if qk:
-            acc.update(count_changed=vals[-4], objects_dropped=vals[-3], objects_added=vals[-2])
-            acc["prune_objective_gain" if rk else "objective_gain"] = vals[-1]
-        if uk:
-            acc.update(objects_added_from_residual=vals[-3], count_changed=vals[-2])
-            acc["propose_objective_gain" if rk else "objective_gain"] = vals[-1]
+        acc = dict(zip(("map_num_step_acc", "count_prob", "num_objects"), (tot / images).tolist()), **extras.figures(images))
         t = time.time() - start
-        label = 'parse({}, {}) '.format(pk["particles"], select) if pk else 'parse '
-        if rk:
-            label = label[:-1] + '+refine({}) '.format(rk["refine"])
-        if qk:
-            label = label[:-1] + '+prune({}) '.format(prune)
-        if uk:
-            label = label[:-1] + '+propose({}) '.format(uk["propose"])
-        msg = 'Step {}, Data {} '.format(itr, name) + label + ', '.join('{} = {:.4f}'.format(k, v) for k, v in acc.items())
+        msg = 'Step {}, Data {} parse{} '.format(itr, name, extras.suffix) + ', '.join('{} = {:.4f}'.format(k, v) for k, v in acc.items())
         if measure_time:
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **pk, **rk, **qk, **uk, **acc)) + "\n"); writer.flush()
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse", **extras.kw, **acc)) + "\n"); writer.flush()
         return acc
     return logger
 
@@ -272,10 +277,7 @@ def make_parse_score_logger(air, data, num_batches, name, writer=None, threshold
     import torch
     G = int(data["boxes"].shape[1])
     kw = {} if thresholds is None else dict(thresholds=tuple(thresholds))
-    pk = {} if particles is None else dict(particles=int(particles), select=select)
-    rk = _refine_kw(refine, refine_lr)
-    qk = {} if prune is None else dict(prune=prune)
-    uk = _propose_kw(propose)
+    extras = _ParseExtras(particles, select, refine, refine_lr, prune, propose)
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -285,60 +287,24 @@ def make_parse_score_logger(air, data, num_batches, name, writer=None, threshold
             raise ValueError("the annotated dataset holds fewer images than one batch of %d" % B)
         start = time.time()
         dev = air.obs.device
-        scorer = air.parse_scorer(G, **kw, **pk, **rk, **qk, **uk)
+        scorer = air.parse_scorer(G, **kw, **extras.kw)
         scorer.reset()
-        extra = torch.zeros(2, dtype=torch.float64, device=dev) if pk else None
-        extra_r = torch.zeros(2, dtype=torch.float64, device=dev) if rk else None
-        extra_q = torch.zeros(4, dtype=torch.float64, device=dev) if qk else None
-        extra_u = torch.zeros(3, dtype=torch.float64, device=dev) if uk else None
+        extras.start(dev)
         for i in range(n):
             sl = slice(i * B, (i + 1) * B)
             air.score_parse(torch.as_tensor(data["imgs"][sl], dtype=torch.float32).to(dev), torch.as_tensor(data["instances"][sl]),
-                            torch.as_tensor(data["boxes"][sl]), **kw, **pk, **rk, **qk, **uk)
-            if pk:
-                extra += torch.stack([(air.parsed["best_particle"] != 0).double().sum(), air.parsed["ess"].double().sum()])
-            if rk:
-                extra_r += torch.stack(_refine_sums(air.parsed))
-            if qk:
-                extra_q += torch.stack(_prune_sums(air.parsed))
-            if uk:
-                extra_u += torch.stack(_propose_sums(air.parsed))
+                            torch.as_tensor(data["boxes"][sl]), **kw, **extras.kw)
+            extras.add(air.parsed)
         acc = scorer.summary()
-        shown = ["count_acc", "map", "ap@%.2f" % scorer.thresholds_host[0], "fg_ari", "mean_best_overlap", "matched_box_iou"]
-        if pk:
-            moved, ess = (extra / (n * B)).tolist()
-            acc.update(best_particle_moved=moved, ess=ess)
-            shown += ["best_particle_moved", "ess"]
-        if rk:
-            gain, moved_r = (extra_r / (n * B)).tolist()
-            acc.update(objective_gain=gain, refine_moved=moved_r)
-            shown += ["objective_gain", "refine_moved"]
-        if qk:
-            changed, dropped, added, gain_q = (extra_q / (n * B)).tolist()
-            gain_key = "prune_objective_gain" if rk else "objective_gain"
-            acc.update(count_changed=changed, objects_dropped=dropped, objects_added=added)
-            acc[gain_key] = gain_q
-            shown += ["count_changed", "objects_dropped", "objects_added", gain_key]
-        if uk:
-            added_u, changed_u, gain_u = (extra_u / (n * B)).tolist()
-            gain_key = "propose_objective_gain" if rk else "objective_gain"
-            acc.update(objects_added_from_residual=added_u, count_changed=changed_u)
-            acc[gain_key] = gain_u
-            shown += ["objects_added_from_residual", "count_changed", gain_key]
+        acc.update(extras.figures(n * B))
+        shown = ["count_acc", "map", "ap@%.2f" % scorer.thresholds_host[0], "fg_ari", "mean_best_overlap", "matched_box_iou"] + extras.names
         t = time.time() - start
-        label = 'parse score({}, {}) '.format(pk["particles"], select) if pk else 'parse score '
-        if rk:
-            label = label[:-1] + '+refine({}) '.format(rk["refine"])
-        if qk:
-            label = label[:-1] + '+prune({}) '.format(prune)
-        if uk:
-            label = label[:-1] + '+propose({}) '.format(uk["propose"])
-        msg = 'Step {}, Data {} '.format(itr, name) + label + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
+        msg = 'Step {}, Data {} parse score{} '.format(itr, name, extras.suffix) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **pk, **rk, **qk, **uk, **acc)) + "\n"); writer.flush()
+            writer.write(json.dumps(dict(step=int(itr), data=name + "_parse_score", **extras.kw, **acc)) + "\n"); writer.flush()
         return acc
     return logger
 

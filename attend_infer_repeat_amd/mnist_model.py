@@ -12,6 +12,7 @@ import torch
 from .engine import AIREngine, EngineConfig
 from .model import AIRModel
 from .modules import BaselineMLP, Decoder, Encoder, StepsPredictor, StochasticTransformParam
+from . import stacks
 from .rnn import LSTM
 
 
@@ -219,19 +220,10 @@ class AIRonMNIST(AIRModel):
 
     def iw_evaluator(self, particles=16):
         """the ImportanceEvaluator behind evaluate_iw (built and captured on first use, rebuilt when `particles` changes)"""
-        eng = getattr(self, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("evaluate_iw needs the fused engine: call train_step(...) with an engine-eligible "
-                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        eng = stacks.require_engine(self, "evaluate_iw")
         from .iw_eval import ImportanceEvaluator
-        ev = getattr(self, "_iw_evaluator", None)
-        if ev is None or ev.K != int(particles) or ev.B != eng.B or ev.engine.device != eng.device:
-            if ev is not None:
-                ev.release_graphs()
-            ev = ImportanceEvaluator(eng.cfg, eng.B, int(particles), device=eng.device)
-            ev.capture()
-            self._iw_evaluator = ev
-        return ev
+        return stacks.slot(self, "_iw_evaluator", lambda ev: ev.K == int(particles) and ev.B == eng.B and ev.engine.device == eng.device,
+                           lambda: ImportanceEvaluator(eng.cfg, eng.B, int(particles), device=eng.device))
 
     def evaluate_iw(self, obs=None, nums=None, particles=16):
         """K-particle importance-weighted evaluation on the device (iw_eval.ImportanceEvaluator: its own engine at
@@ -258,20 +250,12 @@ class AIRonMNIST(AIRModel):
     def scene_sampler(self, n_scenes=None):
         """the SceneSampler behind sample_scenes (built and captured on first use, rebuilt when the size or the device changes;
         n_scenes=None: the size it has, the batch size on first use)"""
-        eng = getattr(self, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("sample_scenes needs the fused engine: call train_step(...) with an engine-eligible "
-                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        eng = stacks.require_engine(self, "sample_scenes")
         from .generate import SceneSampler
         s = getattr(self, "_scene_sampler", None)
         n = int(n_scenes) if n_scenes is not None else (s.R if s is not None else eng.B)
-        if s is None or s.R != n or s.device != eng.device:
-            if s is not None:
-                s.release_graphs()
-            s = SceneSampler(eng.cfg, n, device=eng.device)
-            s.capture()
-            self._scene_sampler = s
-        return s
+        return stacks.slot(self, "_scene_sampler", lambda s: s.R == n and s.device == eng.device,
+                           lambda: SceneSampler(eng.cfg, n, device=eng.device))
 
     def sample_scenes(self, n_scenes=None, num_objects=None, count_probs=None):
         """Scenes from the generative model on the device (generate.SceneSampler: the trained decoder is copied, nothing of the
@@ -292,132 +276,81 @@ class AIRonMNIST(AIRModel):
     def scene_parser(self, batch_size=None):
         """the SceneParser behind parse (built and captured on first use, rebuilt when the size or the device changes;
         batch_size=None: the size it has, the batch size on first use)"""
-        eng = getattr(self, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("parse needs the fused engine: call train_step(...) with an engine-eligible "
-                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        eng = stacks.require_engine(self, "parse")
         from .parse import SceneParser
         s = getattr(self, "_scene_parser", None)
         n = int(batch_size) if batch_size is not None else (s.R if s is not None else eng.B)
-        if s is None or s.R != n or s.engine.device != eng.device:
-            if s is not None:
-                s.release_graphs()
-            s = SceneParser(eng.cfg, n, device=eng.device)
-            s.capture()
-            self._scene_parser = s
-        return s
+        return stacks.slot(self, "_scene_parser", lambda s: s.R == n and s.engine.device == eng.device,
+                           lambda: SceneParser(eng.cfg, n, device=eng.device))
 
     def particle_parser(self, batch_size=None, particles=16, select="joint"):
         """the ParticleParser behind parse(particles=K) (built and captured on first use, rebuilt when the size, K, the criterion or
         the device changes; batch_size=None: the size it has, the batch size on first use)"""
-        eng = getattr(self, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("parse needs the fused engine: call train_step(...) with an engine-eligible "
-                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
+        eng = stacks.require_engine(self, "parse")
         from .particle_parse import ParticleParser
         s = getattr(self, "_particle_parser", None)
         n = int(batch_size) if batch_size is not None else (s.B if s is not None else eng.B)
-        if s is None or s.B != n or s.K != int(particles) or s.select != select or s.engine.device != eng.device:
-            if s is not None:
-                s.release_graphs()
-            s = ParticleParser(eng.cfg, n, int(particles), select=select, device=eng.device)
-            s.capture()
-            self._particle_parser = s
-        return s
+        return stacks.slot(self, "_particle_parser",
+                           lambda s: s.B == n and s.K == int(particles) and s.select == select and s.engine.device == eng.device,
+                           lambda: ParticleParser(eng.cfg, n, int(particles), select=select, device=eng.device))
+
+    def _scorer(self, name, parser, max_gt_objects, thresholds):
+        """the score.ParseScorer held under `self.<name>` (built and captured on first use, rebuilt when the parser, the number of
+        ground-truth slots or the thresholds change)"""
+        from .score import DEFAULT_THRESHOLDS, ParseScorer
+        th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
+        return stacks.slot(self, name, lambda s: s.parser is parser and s.G == int(max_gt_objects) and s.thresholds_host == th,
+                           lambda: ParseScorer(parser, max_gt_objects, th))
+
+    MAX_PARSE_REFINERS = MAX_PARSE_PRUNERS = MAX_PARSE_PROPOSERS = 4
+    MAX_TILED_PARSERS = MAX_TRACKERS = MAX_TEMPORAL_PROPOSERS = 2
+
+    def _cache(self, name):
+        """the stacks.BoundedCache `self._<name>` of at most MAX_<NAME> entries (the limit is read when used)"""
+        return self.__dict__.setdefault("_" + name, stacks.BoundedCache(lambda: getattr(self, "MAX_" + name.upper())))
 
     def _parser_for(self, particles, select, refine=None, refine_lr=None, prune=None, propose=None):
-        if prune is not None and propose is not None:
-            raise ValueError("parse: prune together with propose is not supported: the search over the candidate pool already "
-                             "contains prune=\"all\"; pass one of them")
+        spec = stacks.stack_spec(refine, refine_lr, prune, propose, who="parse")
         n = self.obs.shape[0]
         parser = self.scene_parser(n) if particles is None else self.particle_parser(n, particles, select)
-        if refine is not None:
-            parser = self.parse_refiner(parser, refine, refine_lr)
-        if propose is not None:
-            return self.parse_proposer(parser, propose)
-        return parser if prune is None else self.parse_pruner(parser, prune)
+        if spec.refine is not None:
+            parser = self.parse_refiner(parser, spec.refine, spec.lr)
+        if spec.propose is not None:
+            return self.parse_proposer(parser, spec.propose)
+        return parser if spec.prune is None else self.parse_pruner(parser, spec.prune)
 
-    MAX_PARSE_REFINERS = 4
+    def _parse_stage(self, name, provider, key, spec, refiners=()):
+        """The stage `spec` asks for behind `provider` in the cache `name` of `parse`: built and captured on first use; an entry found
+        under `key` but bound to another provider is released and rebuilt; dropped first is what is bound to neither the current scene
+        parser, the current particle parser nor one of `refiners`."""
+        alive = [getattr(self, "_scene_parser", None), getattr(self, "_particle_parser", None)] + list(refiners)
+        cache = self._cache(name)
+        cache.drop(lambda r: not any(r.parser is a for a in alive))
+        return cache.get(key, lambda: stacks.captured(stacks.build_stack(provider, spec)[-1]), lambda r: r.parser is provider)
 
     def parse_refiner(self, parser, steps, lr=None):
         """the ParseRefiner behind parse(refine=N): one per (batch, particles, select, N, lr), bound to that parser (built and captured
         on first use; dropped when its parser was rebuilt, and the least recently used one when more than MAX_PARSE_REFINERS are
         alive -- a scorer still bound to a dropped one keeps working, its refiner then launches eagerly)"""
-        from .refine import DEFAULT_LR, ParseRefiner
-        lr = tuple(float(v) for v in (DEFAULT_LR if lr is None else lr))
-        if len(lr) != 2:
-            raise ValueError("refine_lr: (lr_what, lr_where), got %r" % (lr,))
-        cache = self.__dict__.setdefault("_parse_refiners", {})
-        for k in [k for k, r in cache.items() if r.parser is not getattr(self, "_scene_parser", None)
-                  and r.parser is not getattr(self, "_particle_parser", None)]:
-            cache.pop(k).release_graphs()
-        key = (parser.R, getattr(parser, "K", None), getattr(parser, "select", None), int(steps), lr)
-        r = cache.pop(key, None)
-        if r is None or r.parser is not parser:
-            if r is not None:
-                r.release_graphs()
-            r = ParseRefiner(parser, int(steps), lr[0], lr[1])
-            r.capture()
-        cache[key] = r                                             # most recently used last
-        while len(cache) > self.MAX_PARSE_REFINERS:                # a learning-rate sweep must not pile up buffers and graphs
-            cache.pop(next(iter(cache))).release_graphs()
-        return r
-
-    MAX_PARSE_PRUNERS = 4
+        spec = stacks.stack_spec(refine=steps, refine_lr=lr)
+        key = (parser.R, getattr(parser, "K", None), getattr(parser, "select", None), spec.refine, spec.lr)
+        return self._parse_stage("parse_refiners", parser, key, spec)
 
     def parse_pruner(self, provider, candidates="present"):
         """the ParsePruner behind parse(prune=...): one per (provider, candidates), bound to that scene parser, particle parser or
         refiner (built and captured on first use; dropped when its provider was rebuilt or dropped, and the least recently used one
         when more than MAX_PARSE_PRUNERS are alive -- a scorer still bound to a dropped one keeps working, its pruner then launches
         eagerly)"""
-        from .prune import ParsePruner
-        cache = self.__dict__.setdefault("_parse_pruners", {})
-        alive = [getattr(self, "_scene_parser", None), getattr(self, "_particle_parser", None)]
-        alive += list(self.__dict__.get("_parse_refiners", {}).values())
-        for k in [k for k, r in cache.items() if not any(r.parser is a for a in alive)]:
-            cache.pop(k).release_graphs()
-        key = (id(provider), candidates)
-        r = cache.pop(key, None)
-        if r is None or r.parser is not provider:
-            if r is not None:
-                r.release_graphs()
-            r = ParsePruner(provider, candidates)
-            r.capture()
-        cache[key] = r                                             # most recently used last
-        while len(cache) > self.MAX_PARSE_PRUNERS:
-            cache.pop(next(iter(cache))).release_graphs()
-        return r
-
-    MAX_PARSE_PROPOSERS = 4
+        return self._parse_stage("parse_pruners", provider, (id(provider), candidates), stacks.stack_spec(prune=candidates),
+                                 self._cache("parse_refiners").values())
 
     def parse_proposer(self, provider, propose=1):
         """the ParseProposer behind parse(propose=...): one per (provider, proposals, rounds), bound to that scene parser, particle
         parser or refiner (built and captured on first use; dropped when its provider was rebuilt or dropped, and the least recently
         used one when more than MAX_PARSE_PROPOSERS are alive -- a scorer still bound to a dropped one keeps working, its proposer
         then launches eagerly).  propose: P, or (P, rounds)."""
-        from .propose import ParseProposer
-        try:
-            spec = (int(propose), 1) if not isinstance(propose, (tuple, list)) else tuple(int(v) for v in propose)
-        except (TypeError, ValueError):
-            spec = ()
-        if len(spec) != 2 or isinstance(propose, bool):
-            raise ValueError("propose: the number of proposals per round, or (proposals, rounds), got %r" % (propose,))
-        cache = self.__dict__.setdefault("_parse_proposers", {})
-        alive = [getattr(self, "_scene_parser", None), getattr(self, "_particle_parser", None)]
-        alive += list(self.__dict__.get("_parse_refiners", {}).values())
-        for k in [k for k, r in cache.items() if not any(r.parser is a for a in alive)]:
-            cache.pop(k).release_graphs()
-        key = (id(provider),) + spec
-        r = cache.pop(key, None)
-        if r is None or r.parser is not provider:
-            if r is not None:
-                r.release_graphs()
-            r = ParseProposer(provider, spec[0], spec[1])
-            r.capture()
-        cache[key] = r                                             # most recently used last
-        while len(cache) > self.MAX_PARSE_PROPOSERS:
-            cache.pop(next(iter(cache))).release_graphs()
-        return r
+        spec = stacks.stack_spec(propose=propose)
+        return self._parse_stage("parse_proposers", provider, (id(provider),) + spec.propose, spec, self._cache("parse_refiners").values())
 
     def parse(self, obs=None, num_objects=None, particles=None, select="joint", refine=None, refine_lr=None, prune=None, propose=None):
         """Scene parse on the device.  particles=None: the deterministic parse (parse.SceneParser: its own engine at the mode of the
@@ -457,79 +390,46 @@ class AIRonMNIST(AIRModel):
         uses (built and captured on first use, rebuilt when the parser, the number of ground-truth slots or the thresholds change);
         refine=N binds it to that parse's refiner instead, so the refined parse is what gets scored; prune=... to that parse's pruner,
         propose=... to that parse's proposer"""
-        from .score import DEFAULT_THRESHOLDS, ParseScorer
-        parser = self._parser_for(particles, select, refine, refine_lr, prune, propose)
-        th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
-        s = getattr(self, "_parse_scorer", None)
-        if s is None or s.parser is not parser or s.G != int(max_gt_objects) or s.thresholds_host != th:
-            if s is not None:
-                s.release_graphs()
-            s = ParseScorer(parser, max_gt_objects, th)
-            s.capture()
-            self._parse_scorer = s
-        return s
+        return self._scorer("_parse_scorer", self._parser_for(particles, select, refine, refine_lr, prune, propose), max_gt_objects,
+                            thresholds)
 
     def score_parse(self, obs, gt_instances, gt_boxes, gt_count=None, thresholds=None, accumulate=True, particles=None,
                     select="joint", refine=None, refine_lr=None, prune=None, propose=None):
         """Parse `obs` (AIRonMNIST.parse, with `particles` / `select` as there), then score the parse against the ground truth on the device (score.ParseScorer.score lists
         the arguments and the returned device tensors).  gt_count=None: the number of rows of gt_boxes with width > 0.  The sums
         accumulate in `parse_scorer(...)`: its reset() starts a validation set, its summary() reads the figures back once."""
-        import torch
         self.parse(obs, particles=particles, select=select, refine=refine, refine_lr=refine_lr, prune=prune, propose=propose)
         s = self.parse_scorer(torch.as_tensor(gt_boxes).shape[1], thresholds, particles, select, refine, refine_lr, prune, propose)
         self.parse_scores = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores
 
-    MAX_TILED_PARSERS = 2
+    def _own_stack(self, rows, spec, n_frames=None):
+        """a provider stack of its own at `rows` rows on the training engine's device: a SceneParser and behind it what `spec` asks
+        for (stacks.build_stack), so that the parsers of `parse` and `self.obs` are never touched"""
+        from .parse import SceneParser
+        return stacks.build_stack(SceneParser(self._engine.cfg, rows, device=self._engine.device), spec, n_frames)
 
     def tiled_parser(self, n_scenes, scene_size, stride=None, iou_merge=0.5, refine=None, refine_lr=None, prune=None, propose=None):
         """the tile.TiledSceneParser behind parse_tiled: one per (n_scenes, scene_size, stride, iou_merge, refine, refine_lr, prune,
         propose), over a provider stack of its own at n_scenes * windows rows -- a SceneParser, behind it the refiner / pruner /
         proposer asked for -- so the parsers of `parse` and `self.obs` are never touched.  Built and captured on first use; the
         least recently used one is dropped, with its stack, when more than MAX_TILED_PARSERS are alive (each owns an engine)."""
-        eng = getattr(self, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("parse_tiled needs the fused engine: call train_step(...) with an engine-eligible "
-                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
-        if prune is not None and propose is not None:
-            raise ValueError("parse_tiled: prune together with propose is not supported; pass one of them")
+        eng = stacks.require_engine(self, "parse_tiled")
+        spec = stacks.stack_spec(refine, refine_lr, prune, propose, who="parse_tiled")
         from . import tile
-        from .parse import SceneParser
-        from .refine import DEFAULT_LR
         (Hs, Ws), (sy, sx), (ny, nx) = tile.check_arguments(eng.cfg, scene_size, stride, iou_merge, int(n_scenes))
-        lr = None if refine is None else tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
-        spec = propose if not isinstance(propose, list) else tuple(propose)
-        key = (int(n_scenes), (Hs, Ws), (sy, sx), float(iou_merge), refine, lr, prune, spec, str(eng.device))
-        cache = self.__dict__.setdefault("_tiled_parsers", {})
-        entry = cache.pop(key, None)
-        if entry is None:
-            stack = [SceneParser(eng.cfg, int(n_scenes) * ny * nx, device=eng.device)]
-            if refine is not None:
-                from .refine import ParseRefiner
-                stack.append(ParseRefiner(stack[-1], int(refine), lr[0], lr[1]))
-            if prune is not None:
-                from .prune import ParsePruner
-                stack.append(ParsePruner(stack[-1], prune))
-            if propose is not None:
-                from .propose import ParseProposer
-                p = (int(propose), 1) if not isinstance(propose, (tuple, list)) else tuple(int(v) for v in propose)
-                stack.append(ParseProposer(stack[-1], p[0], p[1]))
-            stack.append(tile.TiledSceneParser(stack[-1], (Hs, Ws), (sy, sx), iou_merge))
-            for s in stack:
-                s.capture()
-            entry = stack
-        cache[key] = entry                                         # most recently used last
-        while len(cache) > self.MAX_TILED_PARSERS:
-            for s in reversed(cache.pop(next(iter(cache)))):
-                s.release_graphs()
-        return entry[-1]
+
+        def build():
+            stack = self._own_stack(int(n_scenes) * ny * nx, spec)
+            return stacks.captured(stack + [tile.TiledSceneParser(stack[-1], (Hs, Ws), (sy, sx), iou_merge)])
+        key = (int(n_scenes), (Hs, Ws), (sy, sx), float(iou_merge), spec, str(eng.device))
+        return self._cache("tiled_parsers").get(key, build)[-1]
 
     def parse_tiled(self, scenes, stride=None, iou_merge=0.5, refine=None, refine_lr=None, prune=None, propose=None):
         """Parse scenes [S, Hs, Ws] LARGER than the model's canvas on the device: overlapping windows of the canvas's size at `stride`
         (None: half the canvas), each parsed as `parse(refine=, prune=, propose=)` would parse it, and the windows' objects merged
         into one parse per scene (tile.TiledSceneParser.parse lists the returned device tensors; the next call overwrites them).
         The training engine's parameters are read, nothing of it is written; `self.obs` and the parsers of `parse` are not touched."""
-        import torch
         scenes = torch.as_tensor(scenes)
         if scenes.dim() != 3:
             raise ValueError("parse_tiled: scenes [S, Hs, Ws], got shape %s" % (tuple(scenes.shape),))
@@ -544,99 +444,38 @@ class AIRonMNIST(AIRModel):
         """parse_tiled, then score the scene parses against scene-level ground truth on the device (score.ParseScorer.score lists the
         arguments and the returned tensors; gt_instances [S, Hs, Ws], gt_boxes [S, G, 4] with G <= 8).  The sums accumulate in the
         scorer this returns alongside: (scores, scorer)."""
-        import torch
-        from .score import DEFAULT_THRESHOLDS, ParseScorer
         self.parse_tiled(scenes, stride, iou_merge, refine, refine_lr, prune, propose)
         scenes = torch.as_tensor(scenes)
         parser = self.tiled_parser(scenes.shape[0], tuple(scenes.shape[1:]), stride, iou_merge, refine, refine_lr, prune, propose)
-        th = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
-        G = int(torch.as_tensor(gt_boxes).shape[1])
-        s = getattr(self, "_tiled_scorer", None)
-        if s is None or s.parser is not parser or s.G != G or s.thresholds_host != th:
-            if s is not None:
-                s.release_graphs()
-            s = ParseScorer(parser, G, th)
-            s.capture()
-            self._tiled_scorer = s
+        s = self._scorer("_tiled_scorer", parser, int(torch.as_tensor(gt_boxes).shape[1]), thresholds)
         self.parse_scores_tiled = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores_tiled, s
-
-    MAX_TRACKERS = 2
-
-    @staticmethod
-    def _temporal_spec(temporal):
-        """temporal=None | P | (P, rounds) -> None | (P, rounds)"""
-        if temporal is None:
-            return None
-        try:
-            spec = (int(temporal), 1) if not isinstance(temporal, (tuple, list)) else tuple(int(v) for v in temporal)
-        except (TypeError, ValueError):
-            spec = ()
-        if len(spec) != 2 or isinstance(temporal, bool):
-            raise ValueError("temporal: the number of neighbour proposals per round, or (proposals, rounds), got %r" % (temporal,))
-        return spec
-
-    def _sequence_stack(self, S, F, refine, lr, prune, propose, temporal):
-        """the provider stack of `tracker` / `temporal_proposer` at S * F rows: a SceneParser, behind it the refiner / pruner /
-        proposer asked for, and last the temporal.TemporalProposer (temporal = (P, rounds) or None)"""
-        from .parse import SceneParser
-        eng = self._engine
-        stack = [SceneParser(eng.cfg, S * F, device=eng.device)]
-        if refine is not None:
-            from .refine import ParseRefiner
-            stack.append(ParseRefiner(stack[-1], int(refine), lr[0], lr[1]))
-        if prune is not None:
-            from .prune import ParsePruner
-            stack.append(ParsePruner(stack[-1], prune))
-        if propose is not None:
-            from .propose import ParseProposer
-            p = (int(propose), 1) if not isinstance(propose, (tuple, list)) else tuple(int(v) for v in propose)
-            stack.append(ParseProposer(stack[-1], p[0], p[1]))
-        if temporal is not None:
-            from .temporal import TemporalProposer
-            stack.append(TemporalProposer(stack[-1], F, temporal[0], temporal[1]))
-        return stack
-
-    @staticmethod
-    def _smooth_spec(smooth):
-        """smooth=None | True | dict(horizon=, process_noise=, measurement_noise=, velocity_var=) -> None | the full dict"""
-        if smooth is None or smooth is False:
-            return None
-        from .trajectory import DEFAULTS
-        spec = dict(DEFAULTS, horizon=0)
-        if smooth is not True:
-            if not isinstance(smooth, dict) or set(smooth) - set(spec):
-                raise ValueError("smooth: None, True or a dict with keys among %s, got %r" % (sorted(spec), smooth))
-            spec.update(smooth)
-        try:
-            spec["process_noise"] = tuple(float(v) for v in spec["process_noise"])
-        except TypeError:
-            raise ValueError("smooth: process_noise must be two numbers (q_shift, q_scale), got %r" % (spec["process_noise"],))
-        return spec
 
     def tracker(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
                 refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None):
         """the track.SequenceTracker behind `track` (`_tracker_entry` describes the cache; with smooth= the tracker of the stack that
         ends in the trajectory.TrajectorySmoother `trajectory_smoother` returns)"""
-        entry = self._tracker_entry(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                                    propose, temporal, smooth, matching)
-        return entry[-1] if self._smooth_spec(smooth) is None else entry[-2]
+        return self._tracker_entry(self._track_key(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine,
+                                                   refine_lr, prune, propose, temporal, smooth, matching))[0]
 
     def trajectory_smoother(self, n_sequences, n_frames, smooth=True, iou_gate=None, appearance_weight=None, birth_score=None,
                             max_age=None, refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None):
         """the trajectory.TrajectorySmoother behind `track(smooth=)` and `predict_frames`: last in the cached stack of
         `tracker(..., smooth=smooth)`, bound to that stack's tracker (smoothed, gap-filled and extrapolated tracks; its defaults are
         provisional)"""
-        if self._smooth_spec(smooth) is None:
+        if stacks.smooth_spec(smooth) is None:
             raise ValueError("trajectory_smoother: smooth must be True or a dict of TrajectorySmoother's arguments, got %r" % (smooth,))
-        return self._tracker_entry(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                                   propose, temporal, smooth, matching)[-1]
+        return self._tracker_entry(self._track_key(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine,
+                                                   refine_lr, prune, propose, temporal, smooth, matching))[1]
 
-    def _tracker_entry(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-                       refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None):
-        """the cached stack whose track.SequenceTracker is behind `track`: one per (n_sequences, n_frames, iou_gate, appearance_weight,
-        birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth, matching), over a provider stack of its own at
-        n_sequences * n_frames rows -- a SceneParser,
+    def _track_key(self, n_sequences, n_frames, *args):
+        """the stacks.TrackKey of the track family's arguments (`args`: iou_gate ... matching, in the order of `tracker`)"""
+        return stacks.track_key(stacks.require_engine(self, "track"), n_sequences, n_frames, *args)
+
+    def _tracker_entry(self, key):
+        """(tracker, smoother | None) for the stacks.TrackKey `key` -- those of the cached stack whose track.SequenceTracker is behind
+        `track`: one per (n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose,
+        temporal, smooth, matching), over a provider stack of its own at n_sequences * n_frames rows -- a SceneParser,
         behind it the refiner / pruner / proposer asked for and, last, with temporal=P | (P, rounds) a temporal.TemporalProposer
         (objects a frame's parse missed are proposed from its neighbour frames; its defaults are provisional) -- so the parsers of
         `parse` and `self.obs` are never touched.  temporal=None builds exactly the stack without it; so does smooth=None, and
@@ -644,86 +483,43 @@ class AIRonMNIST(AIRModel):
         association arguments: track.DEFAULTS (provisional).  matching=None | "greedy" is exactly the stack without the argument,
         "optimal" a tracker of its own with the optimal assignment (part of the key).  Built and captured on first use; the least
         recently used one is dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
-        eng = getattr(self, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("track needs the fused engine: call train_step(...) with an engine-eligible "
-                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
-        if prune is not None and propose is not None:
-            raise ValueError("track: prune together with propose is not supported; pass one of them")
-        from . import track as tr
-        from .refine import DEFAULT_LR
-        given = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age)
-        assoc = {k: (tr.DEFAULTS[k] if v is None else v) for k, v in given.items()}
-        S, F = int(n_sequences), int(n_frames)
-        matching = "greedy" if matching is None else matching
-        tr.check_arguments(eng.cfg.max_steps, F, S * F if S >= 1 else None, matching=matching, **assoc)
-        if S < 1:
-            raise ValueError("track: at least one sequence, got %r" % (n_sequences,))
-        lr = None if refine is None else tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
-        spec = propose if not isinstance(propose, list) else tuple(propose)
-        tspec = self._temporal_spec(temporal)
-        if tspec is not None:
-            from .temporal import check_arguments as check_temporal
-            check_temporal(eng.cfg, F, S * F, tspec[0], tspec[1])
-        sspec = self._smooth_spec(smooth)
-        if sspec is not None:
-            from .trajectory import check_arguments as check_smooth
-            check_smooth(eng.cfg.max_steps, F, S * F, assoc["max_age"], **sspec)
-        key = (S, F, float(assoc["iou_gate"]), float(assoc["appearance_weight"]), float(assoc["birth_score"]), int(assoc["max_age"]),
-               refine, lr, prune, spec, str(eng.device)) + (() if tspec is None else (("temporal",) + tspec,))
-        key += () if sspec is None else (("smooth",) + tuple(sorted(sspec.items())),)
-        key += () if matching == "greedy" else (("matching", matching),)
-        cache = self.__dict__.setdefault("_trackers", {})
-        entry = cache.pop(key, None)
-        if entry is None:
-            stack = self._sequence_stack(S, F, refine, lr, prune, propose, tspec)
-            stack.append(tr.SequenceTracker(stack[-1], F, matching=matching, **assoc))
-            if sspec is not None:
+        def build():
+            from .track import SequenceTracker
+            stack = self._own_stack(key.S * key.F, key.stack, key.F)
+            stack.append(SequenceTracker(stack[-1], key.F, matching=key.matching, **dict(key.assoc)))
+            if key.smooth is not None:
                 from .trajectory import TrajectorySmoother
-                stack.append(TrajectorySmoother(stack[-1], **sspec))
-            for s in stack:
-                s.capture()
-            entry = stack
-        cache[key] = entry                                         # most recently used last
-        while len(cache) > self.MAX_TRACKERS:
-            for s in reversed(cache.pop(next(iter(cache)))):
-                s.release_graphs()
-        return entry
-
-    MAX_TEMPORAL_PROPOSERS = 2
+                stack.append(TrajectorySmoother(stack[-1], **dict(key.smooth)))
+            return stacks.captured(stack)
+        stack = self._cache("trackers").get(key, build)
+        return (stack[-1], None) if key.smooth is None else (stack[-2], stack[-1])
 
     def temporal_proposer(self, n_sequences, n_frames, proposals=1, rounds=1, refine=None, refine_lr=None, prune=None, propose=None):
         """the temporal.TemporalProposer for callers who want the repaired per-frame parses without identities: one per (n_sequences,
         n_frames, proposals, rounds, refine, refine_lr, prune, propose), last in a provider stack of its own at n_sequences * n_frames
         rows (`tracker`'s).  Built and captured on first use; `load_from(self._engine)` before `parse(frames_as_rows)` is the
         caller's.  The least recently used one is dropped, with its stack, when more than MAX_TEMPORAL_PROPOSERS are alive."""
-        eng = getattr(self, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("temporal_proposer needs the fused engine: call train_step(...) with an engine-eligible "
-                                      "configuration first (AIRonMNIST._engine is None on the generic autograd path)")
-        if prune is not None and propose is not None:
-            raise ValueError("temporal_proposer: prune together with propose is not supported; pass one of them")
-        from . import temporal as tp
-        from .refine import DEFAULT_LR
+        eng = stacks.require_engine(self, "temporal_proposer")
+        spec = stacks.stack_spec(refine, refine_lr, prune, propose, (proposals, rounds), who="temporal_proposer")
+        from .temporal import check_arguments
         S, F = int(n_sequences), int(n_frames)
         if S < 1:
             raise ValueError("temporal_proposer: at least one sequence, got %r" % (n_sequences,))
-        tspec = self._temporal_spec((proposals, rounds))
-        tp.check_arguments(eng.cfg, F, S * F, tspec[0], tspec[1])
-        lr = None if refine is None else tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
-        spec = propose if not isinstance(propose, list) else tuple(propose)
-        key = (S, F, tspec, refine, lr, prune, spec, str(eng.device))
-        cache = self.__dict__.setdefault("_temporal_proposers", {})
-        entry = cache.pop(key, None)
-        if entry is None:
-            entry = self._sequence_stack(S, F, refine, lr, prune, propose, tspec)
-            for s in entry:
-                s.capture()
-        cache[key] = entry                                         # most recently used last
-        while len(cache) > self.MAX_TEMPORAL_PROPOSERS:
-            for s in reversed(cache.pop(next(iter(cache)))):
-                s.release_graphs()
-        return entry[-1]
+        check_arguments(eng.cfg, F, S * F, *spec.temporal)
+        return self._cache("temporal_proposers").get((S, F, spec, str(eng.device)),
+                                                     lambda: stacks.captured(self._own_stack(S * F, spec, F)))[-1]
+
+    def _track(self, frames, *args):
+        """`track` (`args`: iou_gate ... matching, in its order); returns the (tracker, smoother | None) that ran"""
+        frames = torch.as_tensor(frames)
+        if frames.dim() != 4:
+            raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
+        tracker, smoother = self._tracker_entry(self._track_key(frames.shape[0], frames.shape[1], *args))
+        last = tracker if smoother is None else smoother
+        self._sync_engine_switches()
+        last.load_from(self._engine)                         # every time: the weights move
+        self.tracked = last.track(frames)
+        return tracker, smoother
 
     def track(self, frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None,
               prune=None, propose=None, temporal=None, smooth=None, matching=None):
@@ -736,15 +532,7 @@ class AIRonMNIST(AIRModel):
         and fc_ tensors and frames_pred that come on top); smooth=None is exactly the call without it.  matching="optimal": the
         optimal assignment of every frame instead of the greedy one (track.py states both rules).  The training engine's
         parameters are read, nothing of it is written; `self.obs` and the parsers of `parse` are not touched."""
-        import torch
-        frames = torch.as_tensor(frames)
-        if frames.dim() != 4:
-            raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
-        t = self._tracker_entry(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr,
-                                prune, propose, temporal, smooth, matching)[-1]
-        self._sync_engine_switches()
-        t.load_from(self._engine)                            # every time: the weights move
-        self.tracked = t.track(frames)
+        self._track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth, matching)
         return self.tracked
 
     def predict_frames(self, frames, horizon, smooth=True, **track_args):
@@ -752,7 +540,7 @@ class AIRonMNIST(AIRModel):
         result) -- the frames F, F + 1, ... rendered from the tracks still live after the last frame, each at its extrapolated place
         with the decoded glimpse of its last sighting (no network evaluation); `result` is `track`'s dict.  `smooth` may carry the
         smoother's other arguments; its horizon is set from `horizon`."""
-        spec = dict(self._smooth_spec(smooth) or self._smooth_spec(True))
+        spec = dict(stacks.smooth_spec(smooth) or stacks.smooth_spec(True))
         if isinstance(horizon, bool) or int(horizon) != horizon or int(horizon) < 1:
             raise ValueError("predict_frames: horizon must be an integer >= 1, got %r" % (horizon,))
         spec["horizon"] = int(horizon)
@@ -773,29 +561,16 @@ class AIRonMNIST(AIRModel):
         table's -- the raw figures stay the tracker's.  matching= is `track`'s; identity=True adds the IDF1 counts (air_track_idf behind
         air_track_score: seq_idf, idf_overlap, totals_idf; the tracker's -- and the smoother's -- identity_summary() reads IDF1, IDP
         and IDR back)."""
-        import torch
-        self.track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth,
-                   matching)
-        frames = torch.as_tensor(frames)
-        t = self.tracker(frames.shape[0], frames.shape[1], iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune,
-                         propose, temporal, smooth, matching)
+        t, smoother = self._track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal,
+                                  smooth, matching)
         gb = torch.as_tensor(gt_boxes)
         scores = dict(t.score(gb, tau, accumulate, identity))
-        if self._smooth_spec(smooth) is not None:
-            self.track_smoother = self.trajectory_smoother(frames.shape[0], frames.shape[1], smooth, iou_gate, appearance_weight,
-                                                           birth_score, max_age, refine, refine_lr, prune, propose, temporal, matching)
-            scores["completed"] = self.track_smoother.score(gb, tau, accumulate, identity)
+        if smoother is not None:
+            self.track_smoother = smoother
+            scores["completed"] = smoother.score(gb, tau, accumulate, identity)
         if gt_instances is not None:
-            from .score import DEFAULT_THRESHOLDS, ParseScorer
-            th = tuple(float(v) for v in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))
             G = int(gb.shape[-2])
-            s = getattr(self, "track_scorer", None)
-            if s is None or s.parser is not t.provider or s.G != G or s.thresholds_host != th:
-                if s is not None:
-                    s.release_graphs()
-                s = ParseScorer(t.provider, G, th)
-                s.capture()
-                self.track_scorer = s
+            s = self._scorer("track_scorer", t.provider, G, thresholds)
             gi = torch.as_tensor(gt_instances)
             scores["detection"] = s.score(gi.reshape((t.R,) + tuple(gi.shape[-2:])), gb.reshape(t.R, G, 4), accumulate=accumulate)
         self.track_scores = scores

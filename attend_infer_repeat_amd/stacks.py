@@ -1,0 +1,171 @@
+"""Where the stacks of post-parse stages behind AIRonMNIST.parse / parse_tiled / track are specified, built and cached: the normalised
+spec of a stack (`stack_spec`), the one builder (`build_stack`), the bounded cache and the single-slot holder of built and captured
+stages (`BoundedCache`, `slot`), the key of the track family (`track_key`).  Pure Python; the stage classes are imported where a
+stack is built.
+"""
+from collections import namedtuple
+
+StackSpec = namedtuple("StackSpec", "refine lr prune propose temporal")     # int | None, (lr_what, lr_where) | None, the pruner's
+#                                                                             candidates | None, (P, rounds) | None, (P, rounds) | None
+TrackKey = namedtuple("TrackKey", "S F assoc stack smooth matching device")   # assoc, smooth: sorted (name, value) pairs; smooth | None
+
+
+def require_engine(air, who):
+    """the training engine of `air`; `who` names the entry that cannot do without it"""
+    eng = getattr(air, "_engine", None)
+    if eng is None:
+        raise NotImplementedError("%s needs the fused engine: call train_step(...) with an engine-eligible "
+                                  "configuration first (AIRonMNIST._engine is None on the generic autograd path)" % who)
+    return eng
+
+
+def _per_round(value, text):
+    """None | P | (P, rounds) -> None | (P, rounds); a bool is not a count"""
+    if value is None:
+        return None
+    try:
+        spec = (int(value), 1) if not isinstance(value, (tuple, list)) else tuple(int(v) for v in value)
+    except (TypeError, ValueError):
+        spec = ()
+    if len(spec) != 2 or isinstance(value, bool):
+        raise ValueError(text + ", or (proposals, rounds), got %r" % (value,))
+    return spec
+
+
+def stack_spec(refine=None, refine_lr=None, prune=None, propose=None, temporal=None, who="parse"):
+    """The arguments that ask for stages behind a parse, as one hashable StackSpec; `who` names the caller in the refusal."""
+    if prune is not None and propose is not None:
+        why = ": the search over the candidate pool already contains prune=\"all\"" if who == "parse" else ""
+        raise ValueError("%s: prune together with propose is not supported%s; pass one of them" % (who, why))
+    lr = None
+    if refine is not None:
+        from .refine import DEFAULT_LR
+        refine, lr = int(refine), tuple(float(v) for v in (DEFAULT_LR if refine_lr is None else refine_lr))
+        if len(lr) != 2:
+            raise ValueError("refine_lr: (lr_what, lr_where), got %r" % (lr,))
+    return StackSpec(refine, lr, prune, _per_round(propose, "propose: the number of proposals per round"),
+                     _per_round(temporal, "temporal: the number of neighbour proposals per round"))
+
+
+def smooth_spec(smooth):
+    """smooth=None | True | dict(horizon=, process_noise=, measurement_noise=, velocity_var=) -> None | the full dict"""
+    if smooth is None or smooth is False:
+        return None
+    from .trajectory import DEFAULTS
+    spec = dict(DEFAULTS, horizon=0)
+    if smooth is not True:
+        if not isinstance(smooth, dict) or set(smooth) - set(spec):
+            raise ValueError("smooth: None, True or a dict with keys among %s, got %r" % (sorted(spec), smooth))
+        spec.update(smooth)
+    try:
+        spec["process_noise"] = tuple(float(v) for v in spec["process_noise"])
+    except TypeError:
+        raise ValueError("smooth: process_noise must be two numbers (q_shift, q_scale), got %r" % (spec["process_noise"],))
+    return spec
+
+
+def track_key(eng, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
+              refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None):
+    """The arguments of the track family, normalised once and checked against the engine `eng` (track, temporal and trajectory
+    check_arguments, before anything is built): None for an association argument is track.DEFAULTS, temporal=None, smooth=None and
+    matching=None | "greedy" give the very key of a call without the argument."""
+    from . import track as tr
+    stack = stack_spec(refine, refine_lr, prune, propose, temporal, who="track")
+    given = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age)
+    assoc = {k: (tr.DEFAULTS[k] if v is None else v) for k, v in given.items()}
+    S, F = int(n_sequences), int(n_frames)
+    matching = "greedy" if matching is None else matching
+    tr.check_arguments(eng.cfg.max_steps, F, S * F if S >= 1 else None, matching=matching, **assoc)
+    if S < 1:
+        raise ValueError("track: at least one sequence, got %r" % (n_sequences,))
+    if stack.temporal is not None:
+        from .temporal import check_arguments as check_temporal
+        check_temporal(eng.cfg, F, S * F, *stack.temporal)
+    smooth = smooth_spec(smooth)
+    if smooth is not None:
+        from .trajectory import check_arguments as check_smooth
+        check_smooth(eng.cfg.max_steps, F, S * F, assoc["max_age"], **smooth)
+        smooth = tuple(sorted(smooth.items()))
+    assoc = {k: (int(v) if k == "max_age" else float(v)) for k, v in assoc.items()}
+    return TrackKey(S, F, tuple(sorted(assoc.items())), stack, smooth, matching, str(eng.device))
+
+
+def stage_classes():
+    from .propose import ParseProposer
+    from .prune import ParsePruner
+    from .refine import ParseRefiner
+    from .temporal import TemporalProposer
+    return ParseRefiner, ParsePruner, ParseProposer, TemporalProposer
+
+
+def build_stack(base, spec, n_frames=None, classes=None):
+    """[base, refiner?, pruner?, proposer?, temporal proposer?]: the stages `spec` asks for, each bound to the one before it (the
+    temporal proposer over sequences of `n_frames` frames).  classes: the four constructors in that order (None: stage_classes())."""
+    ParseRefiner, ParsePruner, ParseProposer, TemporalProposer = stage_classes() if classes is None else classes
+    stack = [base]
+    if spec.refine is not None:
+        stack.append(ParseRefiner(stack[-1], spec.refine, spec.lr[0], spec.lr[1]))
+    if spec.prune is not None:
+        stack.append(ParsePruner(stack[-1], spec.prune))
+    if spec.propose is not None:
+        stack.append(ParseProposer(stack[-1], spec.propose[0], spec.propose[1]))
+    if spec.temporal is not None:
+        stack.append(TemporalProposer(stack[-1], n_frames, spec.temporal[0], spec.temporal[1]))
+    return stack
+
+
+def _members(entry):
+    return entry if isinstance(entry, list) else [entry]
+
+
+def captured(entry):
+    """`entry` (a stage, or a stack) with every member captured, in stack order"""
+    for s in _members(entry):
+        s.capture()
+    return entry
+
+
+def release(entry):
+    """release the graphs of `entry` (a stage, or a stack: every member, last stage first)"""
+    for s in reversed(_members(entry)):
+        s.release_graphs()
+
+
+class BoundedCache(dict):
+    """key -> a built and captured stage or stack, least recently used first; at most limit() entries (the limit is read when used)"""
+
+    def __init__(self, limit):
+        super().__init__()
+        self.limit = limit
+
+    def get(self, key, build, valid=None):
+        """the entry under `key`, now the most recently used: build() on a miss -- a hit that valid() refuses is released and counts as
+        one -- then the oldest entries are released while there are more than the limit"""
+        entry = self.pop(key, None)
+        if entry is not None and valid is not None and not valid(entry):
+            release(entry)
+            entry = None
+        if entry is None:
+            entry = build()
+        self[key] = entry
+        while len(self) > self.limit():
+            release(self.pop(next(iter(self))))
+        return entry
+
+    def drop(self, predicate):
+        """release and forget every entry that predicate(entry) names"""
+        for key in [k for k, e in self.items() if predicate(e)]:
+            release(self.pop(key))
+
+
+def slot(owner, name, current, build):
+    """The single-slot holder: `owner.<name>` when there is one and current(it) holds; else what build() makes, captured, the old one
+    released."""
+    s = getattr(owner, name, None)
+    if s is None or not current(s):
+        if s is not None:
+            s.release_graphs()
+        s = build()
+        s.capture()
+        setattr(owner, name, s)
+    return s

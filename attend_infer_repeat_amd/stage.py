@@ -17,7 +17,8 @@ A stage states the kinds it binds to (`ACCEPTS`) and refuses the rest (`BoundSta
 attributes to find out what it is.  `ReadOut` owns the read-out buffers and writes the argument order of air_parse_objects,
 air_prune_relabel / air_tile_relabel, air_parse_render and air_sum_leading once.  `BoundStage` is the life cycle of an object that binds
 to a provider and runs a launch list behind that provider's own call: the plan and what it holds by value of the engine's configuration,
-the captured graph, the forwarding of parameters and run-time switches.  Pure Python; torch is imported where it is needed.
+the captured graph, the forwarding of parameters and run-time switches.  Which stages stand behind a parse, and how the built stacks
+are cached, is stacks.py's.  Pure Python; torch is imported where it is needed.
 """
 import ctypes
 
