@@ -228,9 +228,12 @@ SIGNATURES = {
                                     c_int, P, P, P, P, P, P, P, P, P, P, P, P]),
     "air_track_associate_optimal": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, c_int, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "air_track_associate_stream": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, c_int, P, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "air_track_idf": (c_int, [P, P, P, P, ctypes.c_double, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "air_track_owner": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
     "air_track_score": (c_int, [P, P, P, P, ctypes.c_double, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "air_track_score_stream": (c_int, [P, P, P, P, ctypes.c_double, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "air_track_smooth_workspace_bytes": (c_size_t, [c_int, c_int]),
     "air_track_smooth": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, P, c_size_t, P, P, P, P, P, P, P, P, P, P, P, P, P, P,

@@ -1,6 +1,9 @@
 // Tracking objects across the frames of a sequence for gfx950: per-frame parses in, identities out.
 //   air_track_associate: per sequence the frames walked in order INSIDE the kernel; a table of at most 32 live tracks, the float64
 //                        affinity of every (track, object) pair, greedy matching by a workgroup arg-max, births, ageing;
+//   air_track_associate_stream: the same per-frame code on a CHUNK of a stream: the track table is loaded from and stored to a state
+//                        that outlives the launch, the frames are numbered globally, the retired tracks come as a list;
+//   air_track_score_stream: air_track_score with its map, its per-slot counts, its counters and its IoU sum carried in a state;
 //   air_track_associate_optimal: the same kernel with step 3 replaced: the assignment of the largest summed int64 profit, by a
 //                        shortest-augmenting-path Hungarian that one wavefront runs (lane = column);
 //   air_track_owner:     the parse's owner maps relabelled from step to track id (int8 in, int16 out): a streaming pass;
@@ -11,6 +14,7 @@
 // the same bits run to run.
 #include <math.h>
 #include <limits.h>
+#include <type_traits>
 #include "scene_device.h"
 
 #define TRACK_THREADS 256
@@ -52,6 +56,16 @@ struct TrackAssocArgs {
     double iou_gate, w, birth_score;
     int T, S, F, A, max_age;
 };
+// a chunk of a stream: the one-shot arguments (num_tracks and the per-id tables unused) and the carried state (include/air_hip.h
+// states the layout)
+struct TrackStreamArgs : TrackAssocArgs {
+    const int *valid;
+    int *st_seq, *st_slots;
+    float *st_box, *st_what;
+    int *num_retired, *retired_id, *retired_first, *retired_last, *retired_length, *retired_gaps;
+};
+enum { TRACK_ST_LIVE = 0, TRACK_ST_ID, TRACK_ST_AGE, TRACK_ST_LENGTH, TRACK_ST_GAPS, TRACK_ST_FIRST, TRACK_ST_LAST_FRAME,
+       TRACK_ST_LAST_SLOT, TRACK_ST_FIELDS };
 
 // The assignment of the frame's finite objects (rows, inserted in ascending j) to the 64 columns of one wavefront -- column k < 32 is
 // track slot k, column 32 + j is "object j stays unmatched" -- that maximises the summed profit: profit_s[k * 32 + j] >= 1 for an
@@ -111,7 +125,11 @@ __device__ __forceinline__ int track_solve_wave(const long long *profit_s, const
 
 // One 256-thread workgroup per sequence.  Track slot k and object j < 32; pair p = k * 32 + j, four pairs per thread.  OPTIMAL: step 3
 // is track_solve_wave's assignment (wavefront 0 runs it, the other three wait at the barrier), everything else is the same code.
-template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(TrackAssocArgs a) {
+// STREAM: the table comes from and goes back to the state (one global round trip per launch, none per frame), the frames f <
+// clip(valid[s], 0, F) are walked under their global index frames_seen + f, a track last sighted before this chunk takes its `what`
+// row from the state, and a retired track goes to the chunk's retired list (its place by a ballot over the 32 slots).
+template <bool OPTIMAL, bool STREAM = false> __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(
+    std::conditional_t<STREAM, TrackStreamArgs, TrackAssocArgs> a) {
 #pragma clang fp contract(off)
     __shared__ double aff_s[TRACK_MAXT * TRACK_MAXT];              // aff of an admissible pair still open, -1 otherwise
     __shared__ long long profit_s[OPTIMAL ? TRACK_MAXT * TRACK_MAXT : 1];      // OPTIMAL: 1 + floor(aff 2^32), -1 for a forbidden pair
@@ -123,18 +141,40 @@ template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_a
     __shared__ double wave_v[TRACK_THREADS / 64];
     __shared__ int wave_key[TRACK_THREADS / 64], wave_pos[TRACK_THREADS / 64];
     __shared__ int counts_s[6], next_id_s, nonfinite_s[TRACK_MAXT];
+    __shared__ int t_first[STREAM ? TRACK_MAXT : 1], nret_s[1];   // STREAM only
     const int T = a.T, F = a.F, A = a.A, R = a.S * F, FT = F * T;
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int base = 0, V = F, n_ret = 0;                                // STREAM: frames_seen, the valid frames, retired so far (tid < 32's)
+    if constexpr (STREAM) {
+        base = a.st_seq[2 * s];
+        const int v = a.valid[s];
+        V = v < 0 ? 0 : (v > F ? F : v);
+    }
     if (tid < TRACK_MAXT) {
-        t_live[tid] = 0;
+        if constexpr (STREAM) {                                    // the table of the launch before: independent loads, one round trip
+            const int *sl = a.st_slots + (size_t)s * TRACK_ST_FIELDS * TRACK_MAXT + tid;
+            const int live = sl[TRACK_ST_LIVE * TRACK_MAXT], id = sl[TRACK_ST_ID * TRACK_MAXT], age = sl[TRACK_ST_AGE * TRACK_MAXT],
+                      len = sl[TRACK_ST_LENGTH * TRACK_MAXT], gaps = sl[TRACK_ST_GAPS * TRACK_MAXT],
+                      first = sl[TRACK_ST_FIRST * TRACK_MAXT], lf = sl[TRACK_ST_LAST_FRAME * TRACK_MAXT],
+                      lj = sl[TRACK_ST_LAST_SLOT * TRACK_MAXT];
+            const float4 box = *reinterpret_cast<const float4 *>(a.st_box + 4 * ((size_t)s * TRACK_MAXT + tid));
+            t_live[tid] = live, t_id[tid] = id, t_age[tid] = age, t_len[tid] = len, t_gaps[tid] = gaps, t_first[tid] = first;
+            t_f[tid] = lf, t_j[tid] = lj, tbox_s[tid] = box;
+        } else {
+            t_live[tid] = 0;
+        }
         nonfinite_s[tid] = 0;
     }
     if (tid < 6) counts_s[tid] = 0;
-    if (tid == 0) next_id_s = 0;
+    if (tid == 0) {
+        if constexpr (STREAM) next_id_s = a.st_seq[2 * s + 1];
+        else next_id_s = 0;
+    }
     __syncthreads();
 
-    for (int f = 0; f < F; ++f) {
+    for (int f = 0; f < V; ++f) {
         const int r = s * F + f;
+        const int fg = STREAM ? base + f : f;                      // the frame's index in the stream
         int n = a.num_objects[r];
         n = n < 0 ? 0 : (n > T ? T : n);
         // ---- 1. object states: the boxes and scores by the first threads, the T x A `what` values by the whole workgroup ----------------
@@ -170,7 +210,14 @@ template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_a
             double val = -1.0;
             if (t_live[k] && j < n && track_finite4(obox_s[j]) && isfinite(oscore_s[j]) && !nonfinite_s[j]) {
                 const double iou = box_iou_f64(tbox_s[k], obox_s[j]);
-                const float *wk = a.what + ((size_t)t_j[k] * R + (size_t)s * F + t_f[k]) * A;      // read in place
+                const float *wk;
+                if constexpr (STREAM) {                            // sighted in this chunk: in place; before it: the state's copy
+                    const int lf = t_f[k] - base;
+                    wk = lf >= 0 ? a.what + ((size_t)t_j[k] * R + (size_t)s * F + lf) * A
+                                 : a.st_what + ((size_t)s * TRACK_MAXT + k) * A;
+                } else {
+                    wk = a.what + ((size_t)t_j[k] * R + (size_t)s * F + t_f[k]) * A;      // read in place
+                }
                 const float *wj = a.what + ((size_t)j * R + r) * A;
                 double sum = 0.0;
                 int q = 0;
@@ -213,7 +260,7 @@ template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_a
                     t_gaps[k] += t_age[k] > 0 ? 1 : 0;
                     t_age[k] = 0;
                     t_len[k] += 1;
-                    t_f[k] = f;
+                    t_f[k] = fg;
                     t_j[k] = j;
                     tbox_s[k] = obox_s[j];
                 }
@@ -250,7 +297,7 @@ template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_a
                 t_gaps[k] += t_age[k] > 0 ? 1 : 0;
                 t_age[k] = 0;
                 t_len[k] += 1;
-                t_f[k] = f;
+                t_f[k] = fg;
                 t_j[k] = j;
                 tbox_s[k] = obox_s[j];
             }
@@ -267,7 +314,7 @@ template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_a
                 if (ostate_s[j] != TRACK_UNCONFIRMED || !((double)oscore_s[j] >= a.birth_score)) continue;
                 int k = 0;
                 while (k < TRACK_MAXT && t_live[k]) ++k;
-                if (k == TRACK_MAXT) {
+                if (k == TRACK_MAXT || (STREAM && next_id >= TRACK_MAX_IDS)) {      // STREAM: the ids of a stream are 0..32766
                     ostate_s[j] = TRACK_OVERFLOW;
                     continue;
                 }
@@ -275,13 +322,14 @@ template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_a
                 oid_s[j] = next_id;
                 t_live[k] = 1;
                 t_id[k] = next_id;
-                t_f[k] = f;
+                t_f[k] = fg;
                 t_j[k] = j;
                 t_age[k] = 0;
                 t_len[k] = 1;
                 t_gaps[k] = 0;
                 tbox_s[k] = obox_s[j];
-                a.track_first[(size_t)s * FT + next_id] = f;        // next_id < F * T: one id per object at most
+                if constexpr (STREAM) t_first[k] = fg;
+                else a.track_first[(size_t)s * FT + next_id] = f;   // next_id < F * T: one id per object at most
                 ++next_id;
             }
             next_id_s = next_id;
@@ -291,15 +339,33 @@ template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_a
         if (tid < TRACK_MAXT) {
             const int k = tid;
             nonfinite_s[k] = 0;                                     // (for the next frame: read last in step 2)
-            if (t_live[k] && t_f[k] != f) {
+            bool retire = false;
+            if (t_live[k] && t_f[k] != fg) {
                 t_age[k] += 1;
                 if (t_age[k] > a.max_age) {
-                    const size_t at = (size_t)s * FT + t_id[k];
-                    a.track_last[at] = t_f[k];
-                    a.track_length[at] = t_len[k];
-                    a.track_gaps[at] = t_gaps[k];
+                    if constexpr (STREAM) {
+                        retire = true;
+                    } else {
+                        const size_t at = (size_t)s * FT + t_id[k];
+                        a.track_last[at] = t_f[k];
+                        a.track_length[at] = t_len[k];
+                        a.track_gaps[at] = t_gaps[k];
+                        t_live[k] = 0;
+                    }
+                }
+            }
+            if constexpr (STREAM) {                                // the retired list: ascending frame, then ascending slot
+                const unsigned long long retiring = __ballot(retire);      // (the 32 threads of this branch are lanes 0..31 of one wavefront)
+                if (retire) {
+                    const size_t at = (size_t)s * (TRACK_MAXT + FT) + n_ret + __popcll(retiring & ((1ull << k) - 1ull));
+                    a.retired_id[at] = t_id[k];
+                    a.retired_first[at] = t_first[k];
+                    a.retired_last[at] = t_f[k];
+                    a.retired_length[at] = t_len[k];
+                    a.retired_gaps[at] = t_gaps[k];
                     t_live[k] = 0;
                 }
+                n_ret += __popcll(retiring);
             }
             if (tid < T) {
                 const size_t row = (size_t)tid * R + r;
@@ -313,6 +379,70 @@ template <bool OPTIMAL> __global__ __launch_bounds__(TRACK_THREADS) void track_a
             }
         }
         __syncthreads();
+    }
+    if constexpr (STREAM) {
+        // ---- the padding rows, the state, the unused rows of the retired list, the counts ---------------------------------------------
+        const int cap = TRACK_MAXT + FT;
+        if (tid == 0) nret_s[0] = n_ret;
+        for (int e = tid; e < (F - V) * T; e += TRACK_THREADS) {
+            const int fp = e / T, j = e - fp * T;
+            const size_t row = (size_t)j * R + (size_t)s * F + V + fp;
+            a.track_id[row] = -1;
+            a.obj_state[row] = (signed char)TRACK_ABSENT;
+            a.affinity[row] = 0.f;
+            a.prev_frame[row] = -1;
+            a.prev_slot[row] = -1;
+        }
+        if (tid < TRACK_MAXT) {                                    // a slot that is not live is stored in one canonical form
+            int *sl = a.st_slots + (size_t)s * TRACK_ST_FIELDS * TRACK_MAXT + tid;
+            const bool live = t_live[tid] != 0;
+            sl[TRACK_ST_LIVE * TRACK_MAXT] = live ? 1 : 0;
+            sl[TRACK_ST_ID * TRACK_MAXT] = live ? t_id[tid] : -1;
+            sl[TRACK_ST_AGE * TRACK_MAXT] = live ? t_age[tid] : 0;
+            sl[TRACK_ST_LENGTH * TRACK_MAXT] = live ? t_len[tid] : 0;
+            sl[TRACK_ST_GAPS * TRACK_MAXT] = live ? t_gaps[tid] : 0;
+            sl[TRACK_ST_FIRST * TRACK_MAXT] = live ? t_first[tid] : -1;
+            sl[TRACK_ST_LAST_FRAME * TRACK_MAXT] = live ? t_f[tid] : -1;
+            sl[TRACK_ST_LAST_SLOT * TRACK_MAXT] = live ? t_j[tid] : -1;
+            *reinterpret_cast<float4 *>(a.st_box + 4 * ((size_t)s * TRACK_MAXT + tid)) = live ? tbox_s[tid] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        // the `what` rows of the tracks sighted in this chunk: a bit copy, eight values per thread loaded before the first is stored
+        // (the stores may alias the loads for all the compiler knows: one global round trip per batch, not one per value)
+        for (int e0 = tid; e0 < TRACK_MAXT * A; e0 += 8 * TRACK_THREADS) {
+            float v[8];
+            int act[8];                                            // 0: leave the state's row, 1: store v
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int e = e0 + u * TRACK_THREADS;
+                v[u] = 0.f;
+                act[u] = 0;
+                if (e < TRACK_MAXT * A) {
+                    const int k = e / A, q = e - k * A;
+                    act[u] = !t_live[k] || t_f[k] >= base;
+                    if (t_live[k] && t_f[k] >= base) v[u] = a.what[((size_t)t_j[k] * R + (size_t)s * F + (t_f[k] - base)) * A + q];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (act[u]) a.st_what[(size_t)s * TRACK_MAXT * A + e0 + u * TRACK_THREADS] = v[u];
+        }
+        if (tid == 0) {
+            a.st_seq[2 * s] = base + V;
+            a.st_seq[2 * s + 1] = next_id_s;
+        }
+        __syncthreads();
+        const int nr = nret_s[0];
+        for (int i = nr + tid; i < cap; i += TRACK_THREADS) {
+            const size_t at = (size_t)s * cap + i;
+            a.retired_id[at] = -1;
+            a.retired_first[at] = -1;
+            a.retired_last[at] = -1;
+            a.retired_length[at] = 0;
+            a.retired_gaps[at] = 0;
+        }
+        if (tid == 0) a.num_retired[s] = nr;
+        if (tid < 6) a.state_counts[(size_t)s * 6 + tid] = counts_s[tid];
+        return;
     }
     // ---- the tracks alive at the end, the unused rows of the track tables, the counts -------------------------------------------------
     if (tid < TRACK_MAXT && t_live[tid]) {
@@ -380,6 +510,45 @@ extern "C" int air_track_associate_optimal(const float *what, const float *boxes
     return track_associate_launch(true, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score, max_age,
                                   track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last, track_length,
                                   track_gaps, state_counts, stream);
+}
+
+extern "C" int air_track_associate_stream(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
+                                          int F, int R, int A, double iou_gate, double appearance_weight, double birth_score,
+                                          int max_age, const int *valid, int matching, int *st_seq, int *st_slots, float *st_box,
+                                          float *st_what, int *track_id, signed char *obj_state, float *affinity, int *prev_frame,
+                                          int *prev_slot, int *state_counts, int *num_retired, int *retired_id, int *retired_first,
+                                          int *retired_last, int *retired_length, int *retired_gaps, void *stream) {
+    AIR_REQUIRE(what && boxes && score && num_objects && valid && st_seq && st_slots && st_box && st_what && track_id && obj_state &&
+                affinity && prev_frame && prev_slot && state_counts && num_retired && retired_id && retired_first && retired_last &&
+                retired_length && retired_gaps, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && S > 0 && F > 0 && A > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(iou_gate >= 0.0 && iou_gate < 1.0 && appearance_weight >= 0.0 && appearance_weight <= 1.0, AIR_E_SHAPE);
+    AIR_REQUIRE(birth_score >= 0.0 && birth_score <= 1.0 && max_age >= 0, AIR_E_SHAPE);
+    AIR_REQUIRE(matching == 0 || matching == 1, AIR_E_SHAPE);
+    AIR_REQUIRE((long)S * TRACK_MAXT * A <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(boxes) && air_aligned16(st_box), AIR_E_ALIGN);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(what) | reinterpret_cast<uintptr_t>(score) | reinterpret_cast<uintptr_t>(num_objects) |
+                           reinterpret_cast<uintptr_t>(valid) | reinterpret_cast<uintptr_t>(st_seq) | reinterpret_cast<uintptr_t>(st_slots) |
+                           reinterpret_cast<uintptr_t>(st_what) | reinterpret_cast<uintptr_t>(track_id) |
+                           reinterpret_cast<uintptr_t>(affinity) | reinterpret_cast<uintptr_t>(prev_frame) |
+                           reinterpret_cast<uintptr_t>(prev_slot) | reinterpret_cast<uintptr_t>(state_counts) |
+                           reinterpret_cast<uintptr_t>(num_retired) | reinterpret_cast<uintptr_t>(retired_id) |
+                           reinterpret_cast<uintptr_t>(retired_first) | reinterpret_cast<uintptr_t>(retired_last) |
+                           reinterpret_cast<uintptr_t>(retired_length) | reinterpret_cast<uintptr_t>(retired_gaps);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    TrackStreamArgs a;
+    static_cast<TrackAssocArgs &>(a) = {what, boxes, score, num_objects, track_id, prev_frame, prev_slot, nullptr, nullptr, nullptr,
+                                        nullptr, nullptr, state_counts, affinity, obj_state, iou_gate, appearance_weight, birth_score,
+                                        T, S, F, A, max_age};
+    a.valid = valid, a.st_seq = st_seq, a.st_slots = st_slots, a.st_box = st_box, a.st_what = st_what, a.num_retired = num_retired;
+    a.retired_id = retired_id, a.retired_first = retired_first, a.retired_last = retired_last, a.retired_length = retired_length;
+    a.retired_gaps = retired_gaps;
+    if (matching == 1)
+        hipLaunchKernelGGL((track_associate_kernel<true, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    else hipLaunchKernelGGL((track_associate_kernel<false, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
 }
 
 // ============================================================================================================
@@ -467,9 +636,17 @@ struct TrackScoreArgs {
     double tau;
     int T, G, S, F;
 };
+// a chunk of a stream: st_i [S, 32] = {gt, matches, misses, fp, idsw, 0, 0, 0, map[8], tracked[8], present[8]}, st_f [S] = sum_iou
+struct TrackScoreStreamArgs : TrackScoreArgs {
+    const int *valid;
+    int *st_i;
+    double *st_f;
+};
+#define TRACK_SCORE_ST 32
 
-// One workgroup of one wavefront per sequence.  Pair p = g * 32 + j, four pairs per lane.
-__global__ __launch_bounds__(64) void track_score_kernel(TrackScoreArgs a) {
+// One workgroup of one wavefront per sequence.  Pair p = g * 32 + j, four pairs per lane.  STREAM: map, tracked, present, the counters
+// and sum_iou continue from the state and go back to it; the frames f < clip(valid[s], 0, F) are walked.
+template <bool STREAM> __global__ __launch_bounds__(64) void track_score_kernel(std::conditional_t<STREAM, TrackScoreStreamArgs, TrackScoreArgs> a) {
 #pragma clang fp contract(off)
     __shared__ double iou_s[TRACK_MAXG * TRACK_MAXT];
     __shared__ float4 hbox_s[TRACK_MAXT], gbox_s[TRACK_MAXG];
@@ -478,15 +655,30 @@ __global__ __launch_bounds__(64) void track_score_kernel(TrackScoreArgs a) {
         frames_s[TRACK_MAXG];
     const int T = a.T, G = a.G, F = a.F, R = a.S * F;
     const int s = blockIdx.x, lane = threadIdx.x;
-    if (lane < TRACK_MAXG) {
-        map_s[lane] = -1;
-        tracked_s[lane] = 0;
-        frames_s[lane] = 0;
+    if constexpr (!STREAM) {
+        if (lane < TRACK_MAXG) {
+            map_s[lane] = -1;
+            tracked_s[lane] = 0;
+            frames_s[lane] = 0;
+        }
     }
     int n_gt = 0, n_match = 0, n_miss = 0, n_fp = 0, n_idsw = 0;   // lane 0's
     double sum_iou = 0.0;
+    int V = F;
+    if constexpr (STREAM) {
+        const int *c = a.st_i + (size_t)s * TRACK_SCORE_ST;
+        const int v = a.valid[s];
+        V = v < 0 ? 0 : (v > F ? F : v);
+        n_gt = c[0], n_match = c[1], n_miss = c[2], n_fp = c[3], n_idsw = c[4];
+        sum_iou = a.st_f[s];
+        if (lane < TRACK_MAXG) {
+            map_s[lane] = c[8 + lane];
+            tracked_s[lane] = c[16 + lane];
+            frames_s[lane] = c[24 + lane];
+        }
+    }
     __syncthreads();
-    for (int f = 0; f < F; ++f) {
+    for (int f = 0; f < V; ++f) {
         const int r = s * F + f;
         int n = a.num_objects[r];
         n = n < 0 ? 0 : (n > T ? T : n);
@@ -592,6 +784,19 @@ __global__ __launch_bounds__(64) void track_score_kernel(TrackScoreArgs a) {
         c[0] = n_gt, c[1] = n_match, c[2] = n_miss, c[3] = n_fp, c[4] = n_idsw, c[5] = mt, c[6] = ml, c[7] = objects;
         a.seq_iou[s] = sum_iou;
     }
+    if constexpr (STREAM) {
+        int *c = a.st_i + (size_t)s * TRACK_SCORE_ST;
+        if (lane == 0) {
+            c[0] = n_gt, c[1] = n_match, c[2] = n_miss, c[3] = n_fp, c[4] = n_idsw;
+            a.st_f[s] = sum_iou;
+        }
+        if (lane < TRACK_MAXG) {
+            c[8 + lane] = map_s[lane];
+            c[16 + lane] = tracked_s[lane];
+            c[24 + lane] = frames_s[lane];
+        }
+        for (int e = lane; e < (F - V) * G; e += 64) a.gt_match[((size_t)s * F + V) * G + e] = -1;      // the padding rows
+    }
 }
 
 extern "C" int air_track_score(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
@@ -605,7 +810,28 @@ extern "C" int air_track_score(const float *boxes, const int *num_objects, const
                            reinterpret_cast<uintptr_t>(seq_counts) | reinterpret_cast<uintptr_t>(gt_match);
     AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
     const TrackScoreArgs a = {boxes, gt_boxes, num_objects, track_id, seq_counts, gt_match, seq_iou, tau, T, G, S, F};
-    hipLaunchKernelGGL(track_score_kernel, dim3((unsigned)S), dim3(64), 0, air_stream(stream), a);
+    hipLaunchKernelGGL(track_score_kernel<false>, dim3((unsigned)S), dim3(64), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+extern "C" int air_track_score_stream(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
+                                      int T, int G, int S, int F, int R, const int *valid, int *st_i, double *st_f, int *seq_counts,
+                                      double *seq_iou, int *gt_match, void *stream) {
+    AIR_REQUIRE(boxes && num_objects && track_id && gt_boxes && valid && st_i && st_f && seq_counts && seq_iou && gt_match, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && G >= 1 && G <= TRACK_MAXG && S > 0 && F > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(tau >= 0.0 && tau <= 1.0, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(boxes) && air_aligned16(gt_boxes), AIR_E_ALIGN);
+    AIR_REQUIRE(((reinterpret_cast<uintptr_t>(seq_iou) | reinterpret_cast<uintptr_t>(st_f)) & 7u) == 0, AIR_E_ALIGN);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(num_objects) | reinterpret_cast<uintptr_t>(track_id) |
+                           reinterpret_cast<uintptr_t>(valid) | reinterpret_cast<uintptr_t>(st_i) |
+                           reinterpret_cast<uintptr_t>(seq_counts) | reinterpret_cast<uintptr_t>(gt_match);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    TrackScoreStreamArgs a;
+    static_cast<TrackScoreArgs &>(a) = {boxes, gt_boxes, num_objects, track_id, seq_counts, gt_match, seq_iou, tau, T, G, S, F};
+    a.valid = valid, a.st_i = st_i, a.st_f = st_f;
+    hipLaunchKernelGGL(track_score_kernel<true>, dim3((unsigned)S), dim3(64), 0, air_stream(stream), a);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

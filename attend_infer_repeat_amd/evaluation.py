@@ -572,6 +572,60 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
     return logger
 
 
+def make_track_stream_logger(air, data, num_batches, name, chunk_frames, batch_size=None, writer=None, tau=0.5, measure_time=True,
+                             **stream_args):
+    """make_track_score_logger's counterpart for STREAMS (air.track_stream, track.StreamTracker): the sequences of `data` (imgs
+    [N, F, H, W], boxes [N, F, G, 4]) are fed in chunks of `chunk_frames` frames, the last chunk ragged (`valid`), every batch of
+    `batch_size` sequences as a stream of its own (reset between batches), each chunk scored against its rows of the ground truth.
+    Prints / writes the tracker's summary() summed over the batches -- the counts add up; the rates come from track.mot_summary on the
+    sums -- and the tracks issued.  `stream_args` are AIRonMNIST.stream_tracker's."""
+    import numpy as np
+    import torch
+    from .track import COUNTS, mot_summary
+
+    def logger(itr=0, num_batches_to_eval=None, write=True):
+        n = num_batches if num_batches_to_eval is None else num_batches_to_eval
+        S = int(air.obs.shape[0]) if batch_size is None else int(batch_size)
+        n = min(max(int(n), 1), int(data["imgs"].shape[0]) // S)
+        if n < 1:
+            raise ValueError("the annotated dataset holds fewer sequences than one batch of %d" % S)
+        start = time.time()
+        dev = air.obs.device
+        F, C = int(data["imgs"].shape[1]), int(chunk_frames)
+        G = int(data["boxes"].shape[-2])
+        totals, sum_iou, issued = np.zeros(8, np.int64), 0.0, 0
+        for i in range(n):
+            sl = slice(i * S, (i + 1) * S)
+            imgs, boxes = np.asarray(data["imgs"][sl], np.float32), np.asarray(data["boxes"][sl], np.float32)
+            tracker = air.stream_tracker(S, C, **stream_args)
+            tracker.score_reset()
+            for at in range(0, F, C):
+                v = min(C, F - at)
+                frames, gt = np.zeros((S, C) + imgs.shape[2:], np.float32), np.zeros((S, C, G, 4), np.float32)
+                frames[:, :v], gt[:, :v] = imgs[:, at:at + v], boxes[:, at:at + v]
+                air.track_stream(torch.from_numpy(frames).to(dev), np.full(S, v, np.int64), reset=at == 0, **stream_args)
+                scores = tracker.score(torch.from_numpy(gt), tau)
+            tracker.synchronize()
+            totals += scores["seq_counts"].sum(0, dtype=torch.int64).cpu().numpy()
+            sum_iou += float(scores["seq_iou"].sum().item())
+            issued += int(tracker.state["seq"][:, 1].sum().item())
+        acc = mot_summary(totals, sum_iou)
+        acc["tracks"] = issued
+        shown = ["mota", "motp", "id_switches", "mostly_tracked", "mostly_lost", "tracks"]
+        t = time.time() - start
+        msg = 'Step {}, Data {} track stream '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
+        if measure_time:
+            msg += ', eval time = {:.4}s'.format(t)
+        print(msg)
+        if write and writer is not None:
+            rec = dict(step=int(itr), data=name + "_track_stream", n_frames=F, chunk_frames=C, tau=float(tau), iou_gate=tracker.iou_gate,
+                       appearance_weight=tracker.appearance_weight, birth_score=tracker.birth_score, max_age=tracker.max_age,
+                       matching=tracker.matching, **acc)
+            writer.write(json.dumps(rec) + "\n"); writer.flush()
+        return acc
+    return logger
+
+
 def gradient_summaries(named_grads, named_vars, norm=True, ratio=True, histogram=False, bins=30):
     """evaluation.py:221-248: the global norm of the gradient, per variable mean(|g| / (|v| + 1e-8)) (log_ratio,
     evaluation.py:169-180) and -- histogram=True, the reference's default -- a histogram of every gradient tensor, the content of its

@@ -494,6 +494,42 @@ class AIRonMNIST(AIRModel):
         stack = self._cache("trackers").get(key, build)
         return (stack[-1], None) if key.smooth is None else (stack[-2], stack[-1])
 
+    def stream_tracker(self, n_sequences, chunk_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None,
+                       refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None):
+        """the track.StreamTracker behind `track_stream`: identities over sequences of any length, fed in chunks of `chunk_frames`
+        frames, the track table carried on the device between the calls.  One per (n_sequences, chunk_frames, the association
+        arguments, refine, refine_lr, prune, propose, temporal, matching) under a key of its own (stacks.stream_key) in the cache of
+        `tracker` -- it counts against MAX_TRACKERS with the one-shot trackers -- over a provider stack of its own at n_sequences *
+        chunk_frames rows, so the parsers of `parse` and `self.obs` are never touched (a temporal proposer sees only its chunk).  Built
+        and captured on first use.  Dropped from the cache, its stream is lost with it."""
+        key = stacks.stream_key(stacks.require_engine(self, "track_stream"), n_sequences, chunk_frames, iou_gate, appearance_weight,
+                                birth_score, max_age, refine, refine_lr, prune, propose, temporal, matching)
+
+        def build():
+            from .track import StreamTracker
+            stack = self._own_stack(key.S * key.F, key.stack, key.F)
+            stack.append(StreamTracker(stack[-1], key.F, matching=key.matching, **dict(key.assoc)))
+            return stacks.captured(stack)
+        return self._cache("trackers").get(key, build)[-1]
+
+    def track_stream(self, frames, valid=None, reset=False, **stream_args):
+        """The next chunk of a stream: frames [S, F, H, W] parsed as `track` parses them and associated with the tracks of the chunks
+        before (track.StreamTracker.push lists the returned device tensors; prev_frame and the tracks' first / last are global frame
+        indices).  valid [S]: the frames each sequence has in this chunk (None: all F).  reset=True restarts every sequence first, a
+        list of sequence indices those (a slot reused for a new video).  `stream_args` are `stream_tracker`'s; the stream is that
+        tracker's: the same arguments continue it.  The training engine's parameters are read, nothing of it is written; `self.obs`
+        and the parsers of `parse` are not touched."""
+        frames = torch.as_tensor(frames)
+        if frames.dim() != 4:
+            raise ValueError("track_stream: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
+        t = self.stream_tracker(frames.shape[0], frames.shape[1], **stream_args)
+        if reset is not False and reset is not None:
+            t.reset(None if reset is True else reset)
+        self._sync_engine_switches()
+        t.load_from(self._engine)                            # every time: the weights move
+        self.tracked_stream = t.push(frames, valid)
+        return self.tracked_stream
+
     def temporal_proposer(self, n_sequences, n_frames, proposals=1, rounds=1, refine=None, refine_lr=None, prune=None, propose=None):
         """the temporal.TemporalProposer for callers who want the repaired per-frame parses without identities: one per (n_sequences,
         n_frames, proposals, rounds, refine, refine_lr, prune, propose), last in a provider stack of its own at n_sequences * n_frames

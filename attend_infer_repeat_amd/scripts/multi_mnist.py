@@ -137,6 +137,11 @@ def main(argv=None):
     ap.add_argument("--track-identity", action="store_true",
                     help="with --track-eval: also report IDF1, IDP and IDR (air_track_idf: how long each ground-truth object keeps one "
                          "identity) beside MOTA")
+    ap.add_argument("--track-stream", type=int, default=None, metavar="CHUNK",
+                    help="with --track-eval: also run the same sequences through a STREAM in chunks of CHUNK frames (the last chunk "
+                         "ragged; AIRonMNIST.track_stream, track.StreamTracker: the track table carried on the device between the chunks) "
+                         "and log its summary() as <name>_track_stream; --track-matching and --track-temporal apply, --track-smooth and "
+                         "--track-identity do not (out of scope on a stream)")
     ap.add_argument("--track-predict", type=int, default=None, metavar="HZ",
                     help="with --track-eval: also extrapolate the live tracks HZ frames (1..16) past every sequence and render the "
                          "predicted frames (AIRonMNIST.predict_frames' forecast table; implies --track-smooth)")
@@ -216,6 +221,11 @@ def main(argv=None):
 
     if (args.track_matching is not None or args.track_identity) and track_eval is None:
         ap.error("--track-matching and --track-identity go with --track-eval")
+    if args.track_stream is not None:
+        if track_eval is None:
+            ap.error("--track-stream goes with --track-eval")
+        if not 1 <= args.track_stream <= 32767 // 3:
+            ap.error("--track-stream needs 1 <= CHUNK <= %d (CHUNK * max_steps must fit int16)" % (32767 // 3))
     track_smooth = None
     if args.track_smooth is not None or args.track_predict is not None:
         if track_eval is None:
@@ -388,9 +398,17 @@ def main(argv=None):
         track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
                                             smooth=track_smooth, matching=args.track_matching, identity=args.track_identity, **refine_kw)
 
+        stream_log = None
+        if args.track_stream is not None:
+            from attend_infer_repeat_amd.evaluation import make_track_stream_logger
+            stream_log = make_track_stream_logger(air, seq_data, args.eval_batches, 'test', args.track_stream, sequences_per_batch, writer,
+                                                  temporal=track_temporal, matching=args.track_matching, **refine_kw)
+
         def log(train_itr):                               # noqa: F811
             out = before_track_log(train_itr)
             track_log(train_itr)
+            if stream_log is not None:
+                stream_log(train_itr)
             return out
 
     train_itr = int(global_step)

@@ -1,6 +1,6 @@
 """Where the stacks of post-parse stages behind AIRonMNIST.parse / parse_tiled / track are specified, built and cached: the normalised
 spec of a stack (`stack_spec`), the one builder (`build_stack`), the bounded cache and the single-slot holder of built and captured
-stages (`BoundedCache`, `slot`), the key of the track family (`track_key`).  Pure Python; the stage classes are imported where a
+stages (`BoundedCache`, `slot`), the keys of the track family (`track_key`, `stream_key`).  Pure Python; the stage classes are imported where a
 stack is built.
 """
 from collections import namedtuple
@@ -8,6 +8,7 @@ from collections import namedtuple
 StackSpec = namedtuple("StackSpec", "refine lr prune propose temporal")     # int | None, (lr_what, lr_where) | None, the pruner's
 #                                                                             candidates | None, (P, rounds) | None, (P, rounds) | None
 TrackKey = namedtuple("TrackKey", "S F assoc stack smooth matching device")   # assoc, smooth: sorted (name, value) pairs; smooth | None
+StreamKey = namedtuple("StreamKey", "S F assoc stack matching device stream")  # a track.StreamTracker's: stream is True (a key of its own)
 
 
 def require_engine(air, who):
@@ -88,6 +89,15 @@ def track_key(eng, n_sequences, n_frames, iou_gate=None, appearance_weight=None,
         smooth = tuple(sorted(smooth.items()))
     assoc = {k: (int(v) if k == "max_age" else float(v)) for k, v in assoc.items()}
     return TrackKey(S, F, tuple(sorted(assoc.items())), stack, smooth, matching, str(eng.device))
+
+
+def stream_key(eng, n_sequences, chunk_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
+               refine_lr=None, prune=None, propose=None, temporal=None, matching=None):
+    """The arguments of a stream tracker, normalised and checked as `track_key` does (there is no smoother on a stream): a key of its
+    own in the cache of the track family, never that of a one-shot tracker with the same arguments."""
+    k = track_key(eng, n_sequences, chunk_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose,
+                  temporal, None, matching)
+    return StreamKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, True)
 
 
 def stage_classes():

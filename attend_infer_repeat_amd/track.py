@@ -73,6 +73,22 @@ A particle_parse.ParticleParser is refused, with tile.TiledSceneParser's wording
 of an image, and the buffers the tracker reads next to the `what` rows (`boxes`, `score`, `num_objects`, `owner`) are the selected
 particle's only behind a pruner or proposer -- bind one of those, they bind as every other provider.
 
+Streams (`StreamTracker`; air_track_associate_stream, air_track_score_stream).  SequenceTracker is bound to n_frames = F and starts every
+call with an empty table: a video longer than F, a live loop and sequences of different lengths need state that outlives a call.  A
+STREAM is S sequences fed in CHUNKS of the tracker's F frames; a chunk carries valid[s] in 0..F frames of sequence s (rows s F + f with
+f < valid[s]; the rows behind them are padding whose contents do not matter); the global index of a frame is frames_seen[s] + f.  CHUNK
+INVARIANCE: feeding a sequence in any chunking -- ragged valid, valid = 0 included -- gives exactly the result of steps 1-5 (3' for
+matching="optimal") on the concatenation of its valid frames: the same track_id, obj_state, prev_slot and affinity bits, prev_frame as
+the GLOBAL frame index, the same first / last / length / gaps per track.  The carried state is device memory the kernel reads and
+writes in place (include/air_hip.h states the layout; `new_stream_state` builds it in numpy): per sequence frames_seen and next_id,
+per slot live, id, age, length, gaps, first, the last sighting's global frame and slot, its box and a BIT COPY of its `what` row.  The
+tracks retired in a chunk come as a list (ascending retirement frame, then slot), the live ones stay in the state.  A stream issues
+the ids 0..32766 (track_owner is int16); a birth beyond is OVERFLOW.  The metric continues across chunks: map[g], tracked[g],
+present[g], the counters and sum_iou are carried, seq_counts and seq_iou are cumulative.  Out of scope on a stream: IDF1 (its overlap
+table is indexed by global id: 1 MB per sequence at 32767 ids), trajectory.TrajectorySmoother (the backward pass needs the future), ids
+beyond 32766 without `reset`, more than 32 live tracks.  `reference_associate_stream` / `reference_score_stream` restate a chunk in numpy
+with the per-frame code of the one-shot references.
+
 The defaults of iou_gate, appearance_weight, birth_score and max_age are provisional: UNMEASURED on a trained model (profiles/track.txt
 says what was measured); how often the optimal and the greedy matching differ on the parses of a trained model, and what that does to
 IDF1, is unmeasured too (profiles/track_optimal.txt).  `reference_associate`, `reference_score` and `reference_identity` restate the
@@ -183,6 +199,83 @@ def solve_assignment(profit, admissible):
     return col
 
 
+def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id_limit=None):
+    """Steps 1-5 of the rule on ONE frame (the code reference_associate and reference_associate_stream share).  live: slot -> dict(id,
+    f, j, age, length, gaps, first, box, what) with the last sighting's box [4] and what row [A] as fp32 copies; fg: the frame's index
+    (in the stream); what [T, A], boxes [T, 4], score [T]: the frame's fp32 rows; n: its clipped count; rule = (gate, w, birth,
+    max_age, matching); margins: [gate_margin, round_margin], updated in place; id_limit: a birth at next_id == id_limit is OVERFLOW.
+    Returns (state, ids, affinity, prev_frame, prev_slot, next_id, born [tracks], retired [(slot, track)] in ascending slot)."""
+    import numpy as np
+    gate, w, birth, max_age, matching = rule
+    T, A = what.shape
+    state = np.zeros(T, np.int64)
+    ids, pf, ps, aff32 = np.full(T, -1, np.int32), np.full(T, -1, np.int32), np.full(T, -1, np.int32), np.zeros(T, np.float32)
+    what64 = what.astype(np.float64)
+    finite = []
+    for j in range(n):                                             # 1. states
+        ok = np.isfinite(boxes[j]).all() and np.isfinite(score[j]) and np.isfinite(what[j]).all()
+        state[j] = UNCONFIRMED if ok else NONFINITE                # (finite and open: settled below)
+        if ok:
+            finite.append(j)
+    aff = {}                                                       # 2. affinity of the admissible pairs
+    for k, t in live.items():
+        if not finite:
+            break
+        d = t["what"].astype(np.float64)[None, :] - what64[finite]
+        msd = _sequential_sum(d * d) / np.float64(A)
+        for q, j in enumerate(finite):
+            iou = box_iou(t["box"], boxes[j])
+            margins[0] = min(margins[0], abs(iou - gate))
+            if iou > gate:
+                aff[(k, j)] = (1.0 - w) * iou + w / (1.0 + float(msd[q]))
+
+    def matched(k, j):
+        t = live[k]
+        state[j] = MATCHED
+        ids[j], pf[j], ps[j] = t["id"], t["f"], t["j"]
+        aff32[j] = np.float32(aff[(k, j)])
+        t["gaps"] += 1 if t["age"] > 0 else 0
+        t["age"], t["length"], t["f"], t["j"] = 0, t["length"] + 1, fg, j
+        t["box"], t["what"] = boxes[j].copy(), what[j].copy()
+
+    if matching == "optimal" and aff:                              # 3. the optimal assignment
+        profit, admissible = np.zeros((len(finite), MAX_SLOTS), np.int64), np.zeros((len(finite), MAX_SLOTS), bool)
+        for (k, j), v in aff.items():
+            profit[finite.index(j), k], admissible[finite.index(j), k] = 1 + int(math.floor(v * PROFIT_SCALE)), True
+        for q, k in enumerate(solve_assignment(profit, admissible)):
+            if k >= 0:
+                matched(int(k), finite[q])
+        aff = {}
+    while aff:                                                     # 3. greedy matching
+        ranked = sorted(aff, key=lambda kj: (-aff[kj], live[kj[0]]["id"], kj[1]))
+        k, j = ranked[0]
+        if len(ranked) > 1:
+            margins[1] = min(margins[1], aff[ranked[0]] - aff[ranked[1]])
+        matched(k, j)
+        aff = {kj: v for kj, v in aff.items() if kj[0] != k and kj[1] != j}
+    born = []
+    for j in finite:                                               # 4. births
+        if state[j] != UNCONFIRMED or not float(score[j]) >= birth:
+            continue
+        free = [k for k in range(MAX_SLOTS) if k not in live]
+        if not free or (id_limit is not None and next_id >= id_limit):
+            state[j] = OVERFLOW
+            continue
+        state[j] = BORN
+        live[free[0]] = dict(id=next_id, f=fg, j=j, age=0, length=1, gaps=0, first=fg, box=boxes[j].copy(), what=what[j].copy())
+        born.append(live[free[0]])
+        ids[j] = next_id
+        next_id += 1
+    retired = []
+    for k in sorted(live):                                         # 5. ageing
+        t = live[k]
+        if t["f"] != fg:
+            t["age"] += 1
+            if t["age"] > max_age:
+                retired.append((k, live.pop(k)))
+    return state, ids, aff32, pf, ps, next_id, born, retired
+
+
 def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1,
                         return_margins=False, matching="greedy"):
     """air_track_associate restated in numpy float64.  Arrays as the kernel takes them: what [T, R, A], boxes [T, R, 4], score [T, R]
@@ -197,7 +290,7 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
     n_in = np.asarray(num_objects).astype(np.int64)
     T, R, A = what.shape
     T, F, S = check_arguments(T, n_frames, R, iou_gate, appearance_weight, birth_score, max_age, matching)
-    gate, w, birth, max_age = float(iou_gate), float(appearance_weight), float(birth_score), int(max_age)
+    rule = (float(iou_gate), float(appearance_weight), float(birth_score), int(max_age), matching)
     FT = F * T
     out = {"track_id": np.full((T, R), -1, np.int32), "obj_state": np.zeros((T, R), np.int8), "affinity": np.zeros((T, R), np.float32),
            "prev_frame": np.full((T, R), -1, np.int32), "prev_slot": np.full((T, R), -1, np.int32), "num_tracks": np.zeros(S, np.int32),
@@ -205,82 +298,30 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
            "track_length": np.zeros((S, FT), np.int32), "track_gaps": np.zeros((S, FT), np.int32),
            "state_counts": np.zeros((S, 6), np.int32)}
     gate_margin, round_margin = np.full(S, np.inf), np.full(S, np.inf)
-    what64 = what.astype(np.float64)
     for s in range(S):
-        live = {}                                                  # slot -> dict(id, f, j, age, length, gaps)
+        live = {}                                                  # slot -> the track
         next_id = 0
+        margins = [np.inf, np.inf]
 
-        def retire(k):
-            t = live.pop(k)
+        def retire(t):
             out["track_last"][s, t["id"]], out["track_length"][s, t["id"]], out["track_gaps"][s, t["id"]] = t["f"], t["length"], t["gaps"]
 
         for f in range(F):
             r = s * F + f
             n = int(min(max(n_in[r], 0), T))
-            state = np.zeros(T, np.int64)
-            finite = []
-            for j in range(n):                                     # 1. states
-                ok = np.isfinite(boxes[j, r]).all() and np.isfinite(score[j, r]) and np.isfinite(what[j, r]).all()
-                state[j] = UNCONFIRMED if ok else NONFINITE        # (finite and open: settled below)
-                if ok:
-                    finite.append(j)
-            aff = {}                                               # 2. affinity of the admissible pairs
-            for k, t in live.items():
-                if not finite:
-                    break
-                d = what64[t["j"], s * F + t["f"]][None, :] - what64[finite, r]
-                msd = _sequential_sum(d * d) / np.float64(A)
-                for q, j in enumerate(finite):
-                    iou = box_iou(boxes[t["j"], s * F + t["f"]], boxes[j, r])
-                    gate_margin[s] = min(gate_margin[s], abs(iou - gate))
-                    if iou > gate:
-                        aff[(k, j)] = (1.0 - w) * iou + w / (1.0 + float(msd[q]))
-            def matched(k, j):
-                t = live[k]
-                state[j] = MATCHED
-                out["track_id"][j, r], out["prev_frame"][j, r], out["prev_slot"][j, r] = t["id"], t["f"], t["j"]
-                out["affinity"][j, r] = np.float32(aff[(k, j)])
-                t["gaps"] += 1 if t["age"] > 0 else 0
-                t["age"], t["length"], t["f"], t["j"] = 0, t["length"] + 1, f, j
-
-            if matching == "optimal" and aff:                      # 3. the optimal assignment
-                profit, admissible = np.zeros((len(finite), MAX_SLOTS), np.int64), np.zeros((len(finite), MAX_SLOTS), bool)
-                for (k, j), v in aff.items():
-                    profit[finite.index(j), k], admissible[finite.index(j), k] = 1 + int(math.floor(v * PROFIT_SCALE)), True
-                for q, k in enumerate(solve_assignment(profit, admissible)):
-                    if k >= 0:
-                        matched(int(k), finite[q])
-                aff = {}
-            while aff:                                             # 3. greedy matching
-                ranked = sorted(aff, key=lambda kj: (-aff[kj], live[kj[0]]["id"], kj[1]))
-                k, j = ranked[0]
-                if len(ranked) > 1:
-                    round_margin[s] = min(round_margin[s], aff[ranked[0]] - aff[ranked[1]])
-                matched(k, j)
-                aff = {kj: v for kj, v in aff.items() if kj[0] != k and kj[1] != j}
-            for j in finite:                                       # 4. births
-                if state[j] != UNCONFIRMED or not float(score[j, r]) >= birth:
-                    continue
-                free = [k for k in range(MAX_SLOTS) if k not in live]
-                if not free:
-                    state[j] = OVERFLOW
-                    continue
-                state[j] = BORN
-                live[free[0]] = dict(id=next_id, f=f, j=j, age=0, length=1, gaps=0)
-                out["track_id"][j, r] = next_id
-                out["track_first"][s, next_id] = f
-                next_id += 1
-            for k in sorted(live):                                 # 5. ageing
-                t = live[k]
-                if t["f"] != f:
-                    t["age"] += 1
-                    if t["age"] > max_age:
-                        retire(k)
+            state, ids, aff32, pf, ps, next_id, born, retired = _associate_frame(live, next_id, f, what[:, r], boxes[:, r], score[:, r],
+                                                                                 n, rule, margins)
+            for t in born:
+                out["track_first"][s, t["id"]] = f
+            for _, t in retired:
+                retire(t)
+            out["track_id"][:, r], out["affinity"][:, r], out["prev_frame"][:, r], out["prev_slot"][:, r] = ids, aff32, pf, ps
             out["obj_state"][:, r] = state
             out["state_counts"][s] += np.bincount(state, minlength=6).astype(np.int32)
         for k in sorted(live):
-            retire(k)
+            retire(live[k])
         out["num_tracks"][s] = next_id
+        gate_margin[s], round_margin[s] = margins
     if return_margins:
         out["gate_margin"] = gate_margin
         if matching == "greedy":
@@ -288,9 +329,197 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
     return out
 
 
-def reference_score(boxes, num_objects, track_id, gt_boxes, n_frames, tau=0.5):
-    """air_track_score restated in numpy float64.  boxes [T, R, 4], num_objects [R], track_id [T, R], gt_boxes [R, G, 4] (or
-    [S, F, G, 4]).  Returns seq_counts [S, 8] int32 (COUNTS), seq_iou [S] float64, gt_match [R, G] int32."""
+# ---- streams: the state that outlives a call (include/air_hip.h states the layout) -------------------------------------------------------
+ST_LIVE, ST_ID, ST_AGE, ST_LENGTH, ST_GAPS, ST_FIRST, ST_LAST_FRAME, ST_LAST_SLOT = range(8)
+ST_FIELDS = ("live", "id", "age", "length", "gaps", "first", "last_frame", "last_slot")
+ST_EMPTY = (0, -1, 0, 0, 0, -1, -1, -1)                            # a slot that is not live, field by field (box and what: 0)
+STATE_KEYS = ("seq", "slots", "box", "what")
+SCORE_STATE_KEYS = ("score_i", "score_f")
+RETIRED = ("retired_id", "retired_first", "retired_last", "retired_length", "retired_gaps")
+STREAM_OUTPUTS = ("track_id", "obj_state", "affinity", "prev_frame", "prev_slot", "state_counts", "num_retired") + RETIRED
+MAX_FRAMES_SEEN = 2 ** 31 - 1
+
+
+def new_stream_state(n_sequences, what_size):
+    """the state of a stream that has seen nothing, as numpy arrays: seq [S, 2] int32 {frames_seen, next_id}, slots [S, 8, 32] int32
+    (ST_FIELDS), box [S, 32, 4] and what [S, 32, A] fp32"""
+    import numpy as np
+    S, A = int(n_sequences), int(what_size)
+    slots = np.empty((S, 8, MAX_SLOTS), np.int32)
+    slots[:] = np.asarray(ST_EMPTY, np.int32)[None, :, None]
+    return {"seq": np.zeros((S, 2), np.int32), "slots": slots, "box": np.zeros((S, MAX_SLOTS, 4), np.float32),
+            "what": np.zeros((S, MAX_SLOTS, A), np.float32)}
+
+
+def new_score_state(n_sequences):
+    """score_i [S, 32] int32 = {gt, matches, misses, fp, idsw, 0, 0, 0, map[8] (-1), tracked[8], present[8]}, score_f [S] float64"""
+    import numpy as np
+    si = np.zeros((int(n_sequences), 32), np.int32)
+    si[:, 8:16] = -1
+    return {"score_i": si, "score_f": np.zeros(int(n_sequences), np.float64)}
+
+
+def stream_live(state):
+    """the live tracks of a stream state, per sequence a list (ascending slot) of dict(slot, id, first, last, length, gaps, age)"""
+    import numpy as np
+    sl = np.asarray(state["slots"])
+    return [[dict(slot=k, id=int(q[ST_ID, k]), first=int(q[ST_FIRST, k]), last=int(q[ST_LAST_FRAME, k]), length=int(q[ST_LENGTH, k]),
+                  gaps=int(q[ST_GAPS, k]), age=int(q[ST_AGE, k])) for k in range(MAX_SLOTS) if q[ST_LIVE, k]] for q in sl]
+
+
+def check_valid(valid, n_sequences, n_frames):
+    """valid=None (every frame of the chunk) or [S] integers -> int64 [S] clipped to 0..F as the kernel clips it"""
+    import numpy as np
+    S, F = int(n_sequences), int(n_frames)
+    if valid is None:
+        return np.full(S, F, np.int64)
+    v = np.asarray(valid)
+    if v.shape != (S,) or not np.issubdtype(v.dtype, np.integer):
+        raise ValueError("valid: expected %d integers (the frames of each sequence in this chunk), got shape %s %s"
+                         % (S, tuple(v.shape), v.dtype))
+    return np.clip(v.astype(np.int64), 0, F)
+
+
+def check_frames_seen(frames_seen, valid):
+    """refuse a chunk that would take a sequence's global frame index past int32"""
+    import numpy as np
+    after = np.asarray(frames_seen, np.int64) + np.asarray(valid, np.int64)
+    if (after > MAX_FRAMES_SEEN).any():
+        s = int(np.argmax(after))
+        raise ValueError("frames_seen of sequence %d would reach %d; the global frame index must fit int32: reset() the sequence"
+                         % (s, int(after[s])))
+    return after
+
+
+def reference_associate_stream(state, what, boxes, score, num_objects, n_frames, valid=None, iou_gate=0.1, appearance_weight=0.25,
+                               birth_score=0.5, max_age=1, matching="greedy", return_margins=False):
+    """air_track_associate_stream restated in numpy float64, with reference_associate's per-frame code: ONE chunk.  state: None
+    (a stream starts) or what an earlier call returned (it is not modified); the arrays as the kernel takes them, R = S * n_frames;
+    valid [S] (None: every frame).  Returns (outputs, state): track_id, obj_state, affinity, prev_frame (GLOBAL), prev_slot [T, R]
+    with -1 / ABSENT / 0 / -1 / -1 on padding rows, state_counts [S, 6] (valid frames), num_retired [S], retired_id / _first / _last /
+    _length / _gaps [S, 32 + F * T] (ascending retirement frame, then slot; unused rows -1 / -1 / -1 / 0 / 0); and the new state
+    (new_stream_state's arrays).  Ids: 0..32766, a birth beyond is OVERFLOW.  return_margins as in reference_associate."""
+    import numpy as np
+    what, boxes, score = (np.asarray(a, np.float32) for a in (what, boxes, score))
+    n_in = np.asarray(num_objects).astype(np.int64)
+    T, R, A = what.shape
+    T, F, S = check_arguments(T, n_frames, R, iou_gate, appearance_weight, birth_score, max_age, matching)
+    rule = (float(iou_gate), float(appearance_weight), float(birth_score), int(max_age), matching)
+    v_in = check_valid(valid, S, F)
+    state = new_stream_state(S, A) if state is None else {k: np.array(state[k]) for k in STATE_KEYS}
+    if state["what"].shape != (S, MAX_SLOTS, A) or state["seq"].shape != (S, 2):
+        raise ValueError("the state is one of %s sequences with what rows of %d values, the chunk has %d and %d"
+                         % (state["seq"].shape[0], state["what"].shape[-1], S, A))
+    check_frames_seen(state["seq"][:, 0], v_in)
+    cap = MAX_SLOTS + F * T
+    out = {"track_id": np.full((T, R), -1, np.int32), "obj_state": np.zeros((T, R), np.int8), "affinity": np.zeros((T, R), np.float32),
+           "prev_frame": np.full((T, R), -1, np.int32), "prev_slot": np.full((T, R), -1, np.int32),
+           "state_counts": np.zeros((S, 6), np.int32), "num_retired": np.zeros(S, np.int32)}
+    out.update({k: np.full((S, cap), -1 if k in RETIRED[:3] else 0, np.int32) for k in RETIRED})
+    gate_margin, round_margin = np.full(S, np.inf), np.full(S, np.inf)
+    for s in range(S):
+        sl = state["slots"][s]
+        live = {k: dict(id=int(sl[ST_ID, k]), f=int(sl[ST_LAST_FRAME, k]), j=int(sl[ST_LAST_SLOT, k]), age=int(sl[ST_AGE, k]),
+                        length=int(sl[ST_LENGTH, k]), gaps=int(sl[ST_GAPS, k]), first=int(sl[ST_FIRST, k]),
+                        box=state["box"][s, k].copy(), what=state["what"][s, k].copy()) for k in range(MAX_SLOTS) if sl[ST_LIVE, k]}
+        base, next_id = int(state["seq"][s, 0]), int(state["seq"][s, 1])
+        margins = [np.inf, np.inf]
+        n_ret = 0
+        for f in range(int(v_in[s])):
+            r = s * F + f
+            n = int(min(max(n_in[r], 0), T))
+            st, ids, aff32, pf, ps, next_id, _, retired = _associate_frame(live, next_id, base + f, what[:, r], boxes[:, r], score[:, r],
+                                                                           n, rule, margins, MAX_IDS)
+            for _, t in retired:
+                for key, val in zip(RETIRED, (t["id"], t["first"], t["f"], t["length"], t["gaps"])):
+                    out[key][s, n_ret] = val
+                n_ret += 1
+            out["track_id"][:, r], out["affinity"][:, r], out["prev_frame"][:, r], out["prev_slot"][:, r] = ids, aff32, pf, ps
+            out["obj_state"][:, r] = st
+            out["state_counts"][s] += np.bincount(st, minlength=6).astype(np.int32)
+        out["num_retired"][s] = n_ret
+        state["seq"][s] = (base + int(v_in[s]), next_id)
+        sl[:] = np.asarray(ST_EMPTY, np.int32)[:, None]
+        state["box"][s], state["what"][s] = 0, 0
+        for k, t in live.items():
+            sl[:, k] = (1, t["id"], t["age"], t["length"], t["gaps"], t["first"], t["f"], t["j"])
+            state["box"][s, k], state["what"][s, k] = t["box"], t["what"]
+        gate_margin[s], round_margin[s] = margins
+    if return_margins:
+        out["gate_margin"] = gate_margin
+        if matching == "greedy":
+            out["round_margin"] = round_margin
+    return out, state
+
+
+def reset_stream_state(state, sequences=None):
+    """restart all (None) or some sequences of a numpy stream state, in place (association and, if present, score keys)"""
+    import numpy as np
+    S = state["seq"].shape[0]
+    rows = np.arange(S) if sequences is None else np.atleast_1d(np.asarray(sequences, np.int64))
+    if rows.size and (rows.min() < 0 or rows.max() >= S):
+        raise ValueError("reset: sequences within 0..%d, got %r" % (S - 1, sequences))
+    fresh = new_stream_state(1, state["what"].shape[-1])
+    for k in STATE_KEYS:
+        state[k][rows] = fresh[k][0]
+    if "score_i" in state:
+        fs = new_score_state(1)
+        state["score_i"][rows], state["score_f"][rows] = fs["score_i"][0], 0.0
+    return state
+
+
+def _score_frame(c, remembered, tracked, frames, sum_iou, boxes, ids, n, gt, tau):
+    """One frame of the identity metric (the code reference_score and reference_score_stream share): boxes [T, 4], ids [T], gt [G, 4].
+    c (the counters), remembered, tracked, frames are updated in place; returns (gt_match [G], sum_iou)."""
+    import numpy as np
+    G = gt.shape[0]
+    gm = np.full(G, -1, np.int32)
+    hyp = [j for j in range(n) if ids[j] >= 0 and np.isfinite(boxes[j]).all()]
+    present = [g for g in range(G) if gt[g, 2] > 0]
+    iou = {(g, j): box_iou(gt[g], boxes[j]) for g in present for j in hyp}
+    match, taken = {}, set()
+    for g in present:                                              # 1. the remembered track keeps its object
+        if remembered[g] < 0:
+            continue
+        j = next((j for j in hyp if ids[j] == remembered[g] and iou[(g, j)] > tau), None)
+        if j is not None and j not in taken:
+            match[g] = j
+            taken.add(j)
+    while True:                                                    # 2. the rest greedily
+        open_pairs = [(g, j) for (g, j), v in iou.items() if g not in match and j not in taken and v > tau]
+        if not open_pairs:
+            break
+        g, j = min(open_pairs, key=lambda gj: (-iou[gj], gj[0], gj[1]))
+        match[g] = j
+        taken.add(j)
+    for g in present:                                              # 3., 4.
+        c["gt"] += 1
+        frames[g] += 1
+        if g not in match:
+            c["misses"] += 1
+            continue
+        j = match[g]
+        gm[g] = j
+        c["matches"] += 1
+        tracked[g] += 1
+        sum_iou = sum_iou + iou[(g, j)]
+        c["idsw"] += 1 if remembered[g] >= 0 and remembered[g] != ids[j] else 0
+        remembered[g] = int(ids[j])
+    c["fp"] += len(hyp) - len(taken)
+    return gm, sum_iou
+
+
+def _score_objects(c, tracked, frames):
+    """mostly tracked / mostly lost / gt objects from the per-slot counts, into c"""
+    c["gt_objects"] = c["mostly_tracked"] = c["mostly_lost"] = 0
+    for g in range(len(frames)):
+        if frames[g] > 0:
+            c["gt_objects"] += 1
+            c["mostly_tracked"] += 1 if 5 * tracked[g] >= 4 * frames[g] else 0
+            c["mostly_lost"] += 1 if 5 * tracked[g] <= frames[g] else 0
+
+
+def _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau):
     import numpy as np
     boxes = np.asarray(boxes, np.float32)
     gt = np.asarray(gt_boxes, np.float32)
@@ -305,6 +534,14 @@ def reference_score(boxes, num_objects, track_id, gt_boxes, n_frames, tau=0.5):
     tau = float(tau)
     if not 0.0 <= tau <= 1.0:
         raise ValueError("tau must be within [0, 1], got %r" % (tau,))
+    return boxes, gt, ids, n_in, T, R, G, F, tau
+
+
+def reference_score(boxes, num_objects, track_id, gt_boxes, n_frames, tau=0.5):
+    """air_track_score restated in numpy float64.  boxes [T, R, 4], num_objects [R], track_id [T, R], gt_boxes [R, G, 4] (or
+    [S, F, G, 4]).  Returns seq_counts [S, 8] int32 (COUNTS), seq_iou [S] float64, gt_match [R, G] int32."""
+    import numpy as np
+    boxes, gt, ids, n_in, T, R, G, F, tau = _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau)
     S = R // F
     counts, seq_iou, gt_match = np.zeros((S, 8), np.int32), np.zeros(S, np.float64), np.full((R, G), -1, np.int32)
     for s in range(S):
@@ -314,45 +551,36 @@ def reference_score(boxes, num_objects, track_id, gt_boxes, n_frames, tau=0.5):
         for f in range(F):
             r = s * F + f
             n = int(min(max(n_in[r], 0), T))
-            hyp = [j for j in range(n) if ids[j, r] >= 0 and np.isfinite(boxes[j, r]).all()]
-            present = [g for g in range(G) if gt[r, g, 2] > 0]
-            iou = {(g, j): box_iou(gt[r, g], boxes[j, r]) for g in present for j in hyp}
-            match, taken = {}, set()
-            for g in present:                                      # 1. the remembered track keeps its object
-                if remembered[g] < 0:
-                    continue
-                j = next((j for j in hyp if ids[j, r] == remembered[g] and iou[(g, j)] > tau), None)
-                if j is not None and j not in taken:
-                    match[g] = j
-                    taken.add(j)
-            while True:                                            # 2. the rest greedily
-                open_pairs = [(g, j) for (g, j), v in iou.items() if g not in match and j not in taken and v > tau]
-                if not open_pairs:
-                    break
-                g, j = min(open_pairs, key=lambda gj: (-iou[gj], gj[0], gj[1]))
-                match[g] = j
-                taken.add(j)
-            for g in present:                                      # 3., 4.
-                c["gt"] += 1
-                frames[g] += 1
-                if g not in match:
-                    c["misses"] += 1
-                    continue
-                j = match[g]
-                gt_match[r, g] = j
-                c["matches"] += 1
-                tracked[g] += 1
-                seq_iou[s] = seq_iou[s] + iou[(g, j)]
-                c["idsw"] += 1 if remembered[g] >= 0 and remembered[g] != ids[j, r] else 0
-                remembered[g] = int(ids[j, r])
-            c["fp"] += len(hyp) - len(taken)
-        for g in range(G):
-            if frames[g] > 0:
-                c["gt_objects"] += 1
-                c["mostly_tracked"] += 1 if 5 * tracked[g] >= 4 * frames[g] else 0
-                c["mostly_lost"] += 1 if 5 * tracked[g] <= frames[g] else 0
+            gt_match[r], seq_iou[s] = _score_frame(c, remembered, tracked, frames, seq_iou[s], boxes[:, r], ids[:, r], n, gt[r], tau)
+        _score_objects(c, tracked, frames)
         counts[s] = [c[k] for k in COUNTS]
     return {"seq_counts": counts, "seq_iou": seq_iou, "gt_match": gt_match}
+
+
+def reference_score_stream(state, boxes, num_objects, track_id, gt_boxes, n_frames, valid=None, tau=0.5):
+    """air_track_score_stream restated in numpy float64, with reference_score's per-frame code: ONE chunk.  state: None (a stream
+    starts) or what an earlier call returned (not modified): new_score_state's arrays.  Returns (outputs, state): seq_counts [S, 8]
+    and seq_iou [S] CUMULATIVE over the stream, gt_match [R, G] of the chunk (-1 on padding rows)."""
+    import numpy as np
+    boxes, gt, ids, n_in, T, R, G, F, tau = _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau)
+    S = R // F
+    v_in = check_valid(valid, S, F)
+    state = new_score_state(S) if state is None else {k: np.array(state[k]) for k in SCORE_STATE_KEYS}
+    counts, seq_iou, gt_match = np.zeros((S, 8), np.int32), np.zeros(S, np.float64), np.full((R, G), -1, np.int32)
+    for s in range(S):
+        si = state["score_i"][s]
+        c = dict(zip(COUNTS[:5], (int(x) for x in si[:5])))
+        remembered, tracked, frames = ([int(x) for x in si[o:o + 8]] for o in (8, 16, 24))
+        sum_iou = np.float64(state["score_f"][s])
+        for f in range(int(v_in[s])):
+            r = s * F + f
+            n = int(min(max(n_in[r], 0), T))
+            gt_match[r], sum_iou = _score_frame(c, remembered, tracked, frames, sum_iou, boxes[:, r], ids[:, r], n, gt[r], tau)
+        si[:5], si[8:16], si[16:24], si[24:32] = [c[k] for k in COUNTS[:5]], remembered, tracked, frames
+        state["score_f"][s] = sum_iou
+        _score_objects(c, tracked[:G], frames[:G])
+        counts[s], seq_iou[s] = [c[k] for k in COUNTS], sum_iou
+    return {"seq_counts": counts, "seq_iou": seq_iou, "gt_match": gt_match}, state
 
 
 def mot_summary(counts, sum_iou) -> Dict[str, float]:
@@ -680,3 +908,265 @@ class SequenceTracker(BoundStage):
         (gt_frames + hyp_frames), idp = idtp / hyp_frames, idr = idtp / gt_frames, and the counts idtp, idfp, idfn, gt_frames,
         hyp_frames.  A denominator of 0 gives nan."""
         return self.scores.identity_summary()
+
+
+class StreamTracker(BoundStage):
+    """Identities over a STREAM: S sequences of any length fed in chunks of `chunk_frames` frames, the track table, the id counter and
+    the last sightings (box and a bit copy of the `what` row) carried on the device between the calls (include/air_hip.h states the
+    layout; nothing is read back between chunks).  Chunk invariance: whatever the chunking -- ragged `valid`, valid = 0 included -- a
+    sequence gets the ids, states, previous sightings and affinity bits SequenceTracker would give on the concatenation of its valid
+    frames, with prev_frame and the tracks' first / last as GLOBAL frame indices.  Binds to the providers SequenceTracker binds to (a
+    temporal.TemporalProposer sees only its chunk) and refuses the same ones with the same wording.  One `push` is the provider's
+    `parse()` and then ONE hipGraph after `capture()`: air_track_associate_stream, air_track_owner.
+
+    A push MUTATES the state, captured or not: pushing a chunk twice continues the stream with a repeated chunk, it does not repeat the
+    call -- `state_dict()` before and `load_state_dict()` after is how a chunk is re-run.  Ids: 0..32766 per sequence until `reset`;
+    a birth beyond is OVERFLOW.  Out of scope on a stream: IDF1 (its overlap table is indexed by global id), trajectory smoothing (the
+    backward pass needs the future), more than 32 live tracks."""
+    ACCEPTS = SequenceTracker.ACCEPTS
+    REFUSALS = SequenceTracker.REFUSALS
+
+    def __init__(self, provider, chunk_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
+                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy"):
+        self._rows = self.bind(provider)
+        T, F, S = check_arguments(provider.T, chunk_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age, matching)
+        import numpy as np
+        import torch
+        from . import hip as H
+        self.provider, self.engine = provider, provider.engine
+        self._bound = provider
+        self.T, self.R, self.S, self.F = T, int(provider.R), S, F
+        self.iou_gate, self.appearance_weight, self.birth_score, self.max_age = (float(iou_gate), float(appearance_weight),
+                                                                                 float(birth_score), int(max_age))
+        self.matching = matching
+        self._what = self._rows["what"]
+        self.A = int(self._what.shape[-1])
+        self.img_size = tuple(int(v) for v in provider.owner.shape[1:])
+        dev = self.engine.device
+        R, cap = self.R, MAX_SLOTS + F * T
+        z = lambda shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
+        with torch.cuda.device(dev):
+            self.track_id, self.obj_state, self.affinity = z((T, R)), z((T, R), torch.int8), z((T, R), torch.float32)
+            self.prev_frame, self.prev_slot = z((T, R)), z((T, R))
+            self.state_counts, self.num_retired = z((S, 6)), z((S,))
+            self.retired = {k: z((S, cap)) for k in RETIRED}
+            self.track_owner = z((R,) + self.img_size, torch.int16)
+            self.valid = z((S,))
+            self.state = {"seq": z((S, 2)), "slots": z((S, 8, MAX_SLOTS)), "box": z((S, MAX_SLOTS, 4), torch.float32),
+                          "what": z((S, MAX_SLOTS, self.A), torch.float32), "score_i": z((S, 32)), "score_f": z((S,), torch.float64)}
+        self.frames_seen = np.zeros(S, np.int64)                   # the host's mirror of state["seq"][:, 0]
+        # `valid` is staged in pinned memory and copied without blocking the host; a ring, so that the host waits only for the copy
+        # of four pushes ago (long done) before it reuses a buffer, never for the chunk that is still running
+        self._valid_ring = [(torch.zeros((S,), dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(4)]
+        self._pushes = 0
+        self._H = H
+        self._score = {}                                           # at most one entry: (G, tau) -> buffers, plan, graph
+        self._rebuild()
+        self.reset()
+        self.engine.synchronize()
+
+    def _build_plan(self):
+        """nothing of the engine's configuration is held by the launch list: built once"""
+        provider, T, R, S, F, st = self.provider, self.T, self.R, self.S, self.F, self.state
+        L, p = self._H.lib(), self._H._p
+        Hi, Wi = self.img_size
+        self.segments = OrderedDict([
+            ("associate", [(L.air_track_associate_stream,
+                            (p(self._what), p(provider.boxes), p(provider.score), p(provider.num_objects), T, S, F, R, self.A,
+                             self.iou_gate, self.appearance_weight, self.birth_score, self.max_age, p(self.valid),
+                             MATCHINGS.index(self.matching), p(st["seq"]), p(st["slots"]), p(st["box"]), p(st["what"]),
+                             p(self.track_id), p(self.obj_state), p(self.affinity), p(self.prev_frame), p(self.prev_slot),
+                             p(self.state_counts), p(self.num_retired), *[p(self.retired[k]) for k in RETIRED]),
+                            "air_track_associate_stream")]),
+            ("owner", [(L.air_track_owner, (p(provider.owner), p(self.track_id), T, R, Hi, Wi, p(self.track_owner)),
+                        "air_track_owner")])])
+        self._plan = [e for seg in self.segments.values() for e in seg]
+
+    def _score_entries(self):
+        return self._score.values()
+
+    def launch_count(self) -> Dict[str, int]:
+        """entries of one `push()` behind the bound provider's own (`parser` holds that provider's launch_count())"""
+        return {"parser": self.provider.launch_count(), "track_associate_stream": 1, "track_owner": 1}
+
+    # ---- the state ------------------------------------------------------------------------------------------------------------
+    def reset(self, sequences=None):
+        """Restart all (None) or some sequences ON THE DEVICE -- a slot reused for a new video: frames_seen and next_id 0, no live
+        track, and the sequence's score state with them (read `summary()` first if its figures matter).  No read-back."""
+        import numpy as np
+        import torch
+        rows = np.arange(self.S) if sequences is None else np.atleast_1d(np.asarray(sequences, np.int64))
+        if rows.size and (rows.min() < 0 or rows.max() >= self.S):
+            raise ValueError("reset: sequences within 0..%d, got %r" % (self.S - 1, sequences))
+        eng, st = self.engine, self.state
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            idx = torch.as_tensor(rows, device=eng.device)
+            empty = torch.tensor(ST_EMPTY, dtype=torch.int32, device=eng.device)
+            st["seq"][idx] = 0
+            st["slots"][idx] = empty[None, :, None].expand(len(rows), 8, MAX_SLOTS)
+            st["box"][idx] = 0
+            st["what"][idx] = 0
+            st["score_i"][idx] = 0
+            st["score_i"][idx, 8:16] = -1
+            st["score_f"][idx] = 0
+        self.frames_seen[rows] = 0
+        eng.wait_for_engine()
+
+    def score_reset(self):
+        """restart the identity metric of every sequence (the association state stays)"""
+        import torch
+        eng, st = self.engine, self.state
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            st["score_i"].zero_()
+            st["score_i"][:, 8:16] = -1
+            st["score_f"].zero_()
+            for e in self._score.values():
+                e["seq_counts"].zero_()
+                e["seq_iou"].zero_()
+        eng.wait_for_engine()
+
+    def live(self):
+        """the live tracks as VIEWS of the state (device tensors the next push rewrites): live, id, age, length, gaps, first,
+        last_frame, last_slot [S, 32] int32 (ST_FIELDS; a slot with live == 0 holds ST_EMPTY), box [S, 32, 4], what [S, 32, A]"""
+        out = {k: self.state["slots"][:, i] for i, k in enumerate(ST_FIELDS)}
+        out.update(box=self.state["box"], what=self.state["what"])
+        return out
+
+    def state_dict(self):
+        """a copy of the carried state as plain device tensors (STATE_KEYS + SCORE_STATE_KEYS): checkpoint, or re-run a chunk"""
+        import torch
+        eng = self.engine
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            out = {k: v.clone() for k, v in self.state.items()}
+        eng.wait_for_engine()
+        return out
+
+    def load_state_dict(self, state):
+        """take a state `state_dict()` gave (any device; score keys optional): copied INTO the buffers the graph holds; frames_seen is
+        read back once for the host's mirror"""
+        import torch
+        eng = self.engine
+        for k in STATE_KEYS:
+            if tuple(state[k].shape) != tuple(self.state[k].shape):
+                raise ValueError("load_state_dict: %s has shape %s, this stream's is %s"
+                                 % (k, tuple(state[k].shape), tuple(self.state[k].shape)))
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            for k, buf in self.state.items():
+                if k in state:
+                    buf.copy_(torch.as_tensor(state[k]).to(buf.dtype), non_blocking=True)
+        eng.wait_for_engine()
+        eng.synchronize()
+        self.frames_seen[:] = self.state["seq"][:, 0].cpu().numpy()
+
+    # ---- tracking -----------------------------------------------------------------------------------------------------------
+    run_provider = SequenceTracker.run_provider
+
+    def push(self, frames, valid=None, *args, **kwargs):
+        """The next chunk: frames [S, F, H, W], valid [S] integers on the host (None: every frame; sequence s has its first
+        clip(valid[s], 0, F) frames in this chunk, the rest of its rows is padding whose contents do not matter -- the provider still
+        parses them); further arguments go to the provider's `parse()` unchanged.  Returns the provider's dict of device tensors,
+        untouched, and next to it (the NEXT push overwrites them): track_id, obj_state, affinity, prev_frame (GLOBAL frame index),
+        prev_slot [T, R] (-1 / ABSENT / 0 / -1 / -1 on padding rows), state_counts [S, 6] (valid frames), num_retired [S] and retired_id
+        / _first / _last / _length / _gaps [S, 32 + F * T] (the tracks retired in this chunk; the live ones: `live()`), track_owner
+        [R, H, W] int16.  A chunk that would take frames_seen past int32 is refused before anything runs.  The push mutates the state:
+        not idempotent (the class text).  Same stream contract as SequenceTracker.track: the work runs on the engine's stream, on
+        return the caller's current stream is ordered after it, and the next call waits for the caller's reads before it overwrites
+        them."""
+        import numpy as np
+        import torch
+        eng = self.engine
+        if torch.is_tensor(valid):
+            valid = valid.cpu().numpy()
+        v = check_valid(valid, self.S, self.F)
+        after = check_frames_seen(self.frames_seen, v)
+        frames = torch.as_tensor(frames)
+        Hi, Wi = self.img_size
+        if frames.numel() != self.R * Hi * Wi or frames.dim() < 2 or tuple(frames.shape[:2]) != (self.S, self.F):
+            raise ValueError("expected frames [%d, %d, %d, %d], got %s" % (self.S, self.F, Hi, Wi, tuple(frames.shape)))
+        # `valid` goes to the device ahead of the parse, on the engine's stream: behind the launches that read the buffer for the
+        # chunk before (its tail, its score), in front of this chunk's tail; the host runs on
+        staged, copied = self._valid_ring[self._pushes % len(self._valid_ring)]
+        self._pushes += 1
+        copied.synchronize()
+        staged.copy_(torch.from_numpy(v.astype(np.int32)))
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            self.valid.copy_(staged, non_blocking=True)
+            copied.record(eng.stream)
+        base = self.run_provider(frames, *args, **kwargs)
+        eng._replay_or_run(self._graph, self._plan)
+        self.frames_seen = after
+        eng.wait_for_engine()
+        return self.result(base)
+
+    def result(self, base=None):
+        out = dict(base) if base is not None else {}
+        out.update(track_id=self.track_id, obj_state=self.obj_state, affinity=self.affinity, prev_frame=self.prev_frame,
+                   prev_slot=self.prev_slot, state_counts=self.state_counts, num_retired=self.num_retired, track_owner=self.track_owner,
+                   **self.retired)
+        return out
+
+    # ---- the identity metric ------------------------------------------------------------------------------------------------
+    def _score_entry(self, G, tau):
+        import torch
+        key = (int(G), float(tau))
+        entry = self._score.get(key)
+        if entry is None:
+            if self._score:
+                raise ValueError("this stream is scored with (G, tau) = %r; call score_reset() with nothing pushed in between, or a "
+                                 "stream of its own, for %r" % (next(iter(self._score)), key))
+            G, tau_f = key
+            if not 1 <= G <= MAX_GT:
+                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+            if not 0.0 <= tau_f <= 1.0:
+                raise ValueError("tau must be within [0, 1], got %r" % (tau,))
+            eng, par, st, S, R = self.engine, self.provider, self.state, self.S, self.R
+            L, p, dev = self._H.lib(), self._H._p, eng.device
+            with torch.cuda.device(dev):
+                entry = {"gt_boxes": torch.zeros((R, G, 4), device=dev), "seq_counts": torch.zeros((S, 8), dtype=torch.int32, device=dev),
+                         "seq_iou": torch.zeros((S,), dtype=torch.float64, device=dev),
+                         "gt_match": torch.zeros((R, G), dtype=torch.int32, device=dev), "graph": None}
+            entry["plan"] = [(L.air_track_score_stream,
+                              (p(par.boxes), p(par.num_objects), p(self.track_id), p(entry["gt_boxes"]), tau_f, self.T, G, S, self.F, R,
+                               p(self.valid), p(st["score_i"]), p(st["score_f"]), p(entry["seq_counts"]), p(entry["seq_iou"]),
+                               p(entry["gt_match"])), "air_track_score_stream")]
+            if self._graph is not None:
+                eng.synchronize()
+                entry["graph"] = eng._capture_plans([entry["plan"]])
+            self._score[key] = entry
+        return entry
+
+    def score(self, gt_boxes, tau=0.5):
+        """Score the LATEST chunk against gt_boxes [R, G, 4] (or [S, F, G, 4]; G <= 8; slot g is the same object over the whole stream
+        of a sequence, width <= 0 = absent; padding rows are not read), continuing the stream's metric: an identity switch at a chunk
+        boundary counts.  Once per push -- like the push it mutates its state.  Returns device tensors the next call overwrites:
+        seq_counts [S, 8] int32 (COUNTS) and seq_iou [S] float64 CUMULATIVE over the stream, gt_match [R, G] int32 of the chunk."""
+        import torch
+        eng, N = self.engine, self.R
+        gb = torch.as_tensor(gt_boxes)
+        if gb.dim() not in (3, 4) or gb.shape[-1] != 4 or gb.numel() != N * gb.shape[-2] * 4:
+            raise ValueError("gt_boxes: expected [%d, G, 4] or [%d, %d, G, 4], got %s" % (N, self.S, self.F, tuple(gb.shape)))
+        entry = self._score_entry(gb.shape[-2], tau)
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            entry["gt_boxes"].copy_(gb.reshape(entry["gt_boxes"].shape), non_blocking=True)
+        if gb.is_cuda:
+            gb.record_stream(eng.stream)
+        eng._replay_or_run(entry["graph"], entry["plan"])
+        eng.wait_for_engine()
+        return {k: entry[k] for k in ("seq_counts", "seq_iou", "gt_match")}
+
+    def summary(self) -> Dict[str, float]:
+        """mot_summary of the stream so far: the cumulative seq_counts and seq_iou summed over the S sequences at read-back (ONE
+        read-back; no totals are kept on the device).  Nothing scored yet: the figures of nothing (nan rates)."""
+        import torch
+        self.engine.wait_for_engine()
+        if not self._score:
+            return mot_summary([0] * 8, 0.0)
+        entry = next(iter(self._score.values()))
+        flat = torch.cat([entry["seq_counts"].sum(0, dtype=torch.int64).double(), entry["seq_iou"].sum(0, keepdim=True)]).tolist()
+        return mot_summary(flat[:8], flat[8])

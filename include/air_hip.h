@@ -909,7 +909,47 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *   overlap is passed over); gt_frames = present g summed over the frames; hyp_frames = hypotheses summed over the frames;
  *   ids_with_overlap = ids with a nonzero column.  IDFN = gt_frames - idtp, IDFP = hyp_frames - idtp, IDF1 = 2 idtp / (gt_frames +
  *   hyp_frames).  The limits and checks of air_track_score, and 1 <= n_ids <= 32767 (AIR_E_SHAPE).  boxes / gt_boxes 16-byte,
- *   everything else 4-byte aligned (AIR_E_ALIGN).                                                                                  */
+ *   everything else 4-byte aligned (AIR_E_ALIGN).
+ * Streams.  A stream is S sequences fed in CHUNKS of F frames: a chunk carries valid[s] frames of sequence s, v = clip(valid[s], 0, F);
+ *   rows s F + f with f < v are frames, the rows behind them are padding that is never read.  The global index of a frame is
+ *   frames_seen[s] + f.  CHUNK INVARIANCE: a sequence fed in any chunking (ragged valid, valid = 0 included) gets the track_id,
+ *   obj_state, prev_slot and affinity bits, and per track the first / last / length / gaps, that air_track_associate (matching 0) or
+ *   air_track_associate_optimal (matching 1) gives on the concatenation of its valid frames; prev_frame is the GLOBAL frame index.
+ *   The carried state is device memory the kernel reads and writes in place, per sequence s (a fresh stream: st_seq 0, live 0 and the
+ *   canonical values below; air_track_score_stream: st_i 0 with map -1, st_f 0):
+ *     st_seq  [S,2]     int32   {frames_seen, next_id};
+ *     st_slots[S,8,32]  int32   field-major, slot k < 32: {live, id, age, length, gaps, first (global frame), last-sighting global
+ *                               frame, last-sighting slot};
+ *     st_box  [S,32,4]  fp32    the last-sighting box (16-byte aligned);
+ *     st_what [S,32,A]  fp32    a BIT COPY of the last-sighting what row.
+ *   A slot that is not live is stored as live 0, id -1, age / length / gaps 0, first / last frame / last slot -1, box and what 0.
+ *   A track last sighted in an earlier chunk takes box and what from the state, one sighted in this chunk is read in place; at the end
+ *   of the launch the what rows of the live tracks sighted in this chunk are copied into the state by the whole workgroup.  One load
+ *   and one store of the state per launch, none per frame.  frames_seen must stay below 2^31 (the caller's to refuse: the host
+ *   mirrors it).  Running a chunk MUTATES the state: a second launch on the same chunk continues the stream, it does not repeat it.
+ * air_track_associate_stream: air_track_associate's inputs, rule arguments and checks, valid[S] (int32), matching in {0 greedy,
+ *   1 optimal} (AIR_E_SHAPE otherwise), the state, and the outputs of the chunk, every element written on every launch:
+ *   track_id / obj_state / affinity / prev_frame / prev_slot [T,R] (padding rows: -1 / 0 ABSENT / 0 / -1 / -1); state_counts[S,6] over
+ *   the valid frames only (they sum to T v); num_retired[S] and retired_id / retired_first / retired_last / retired_length /
+ *   retired_gaps [S, 32 + F T]: the tracks retired IN THIS CHUNK in ascending retirement frame, then ascending slot (first and last are
+ *   global frames), the unused rows -1 / -1 / -1 / 0 / 0.  The tracks still live are in the state, not in the list.  IDS: a stream
+ *   issues the ids 0..32766 (track_owner is int16 and air_track_owner is used as it is); a birth at next_id == 32767 is 4 OVERFLOW
+ *   (id -1), which a one-shot call cannot reach.  Null state pointers AIR_E_NULL; st_box 16-byte, the rest 4-byte aligned.
+ * air_track_score_stream: air_track_score on a chunk with map[g], tracked[g], present[g], the five counters (st_i[S,32] int32 = {gt,
+ *   matches, misses, fp, idsw, 0, 0, 0, map[8], tracked[8], present[8]}) and sum_iou (st_f[S] float64, 8-byte aligned) carried:
+ *   sum_iou is CONTINUED from the carried value, so seq_iou has the bits air_track_score gives on the concatenation.  seq_counts[S,8]
+ *   and seq_iou[S] are cumulative over the stream (mostly tracked / lost / objects from the cumulative tracked / present);
+ *   gt_match[R,G] is the chunk's, -1 on padding rows.  The same valid.
+ * Out of scope on a stream: IDF1 (its overlap table is indexed by global id: 1 MB per sequence at 32767 ids), trajectory smoothing
+ *   (the backward pass needs the future), ids beyond 32766 without a reset of the sequence, more than 32 live tracks.               */
+AIR_ENGINE_API int air_track_associate_stream(const float *what, const float *boxes, const float *score, const int *num_objects, int T,
+                    int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
+                    const int *valid, int matching, int *st_seq, int *st_slots, float *st_box, float *st_what, int *track_id,
+                    signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *state_counts, int *num_retired,
+                    int *retired_id, int *retired_first, int *retired_last, int *retired_length, int *retired_gaps, void *stream);
+AIR_ENGINE_API int air_track_score_stream(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes,
+                    double tau, int T, int G, int S, int F, int R, const int *valid, int *st_i, double *st_f, int *seq_counts,
+                    double *seq_iou, int *gt_match, void *stream);
 AIR_ENGINE_API int air_track_associate_optimal(const float *what, const float *boxes, const float *score, const int *num_objects, int T,
                     int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
                     int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,

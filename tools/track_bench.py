@@ -20,6 +20,16 @@ tracker's, its tail graph timed in turns with the greedy one (greedy, optimal, g
 air_track_associate_optimal launched eagerly beside air_track_associate.  --identity scores with identity=True: the air_track_score +
 air_track_idf graph beside the air_track_score graph, air_track_idf eagerly beside air_track_score, and the IDF figures.
 
+--stream CHUNK [CHUNK ...] measures stream tracking instead (track.StreamTracker): for every CHUNK, at --rows provider rows (S = rows /
+CHUNK sequences), ONE captured SceneParser with a captured SequenceTracker(F = CHUNK) and a captured StreamTracker(chunk_frames = CHUNK)
+over it.  --stream-chunks chunks (default 4) of one moving sequence are pushed; the stream's track ids of every chunk are compared with
+track.reference_associate (the ONE-SHOT rule) on the concatenation of the provider's rows read back chunk by chunk -- the share of
+(chunk, sequence) pairs that agree is printed and must be 1 over the sequences whose decisions are 1e-9 from flipping, or the tool
+exits with an error -- and the first chunk of a fresh stream with the one-shot tracker's device outputs.  Then the two captured tails
+(associate + owner) are timed in turns (one-shot, stream, one-shot, stream) in this process on the engine's stream, the stream restarted
+before each turn, and the ratio is reported; the whole calls (`track()` and `push()`, provider included) likewise; the stream launch
+alone with valid = 0; no bar on time.
+
 Timing: a warm-up, then 5 repeats of --iters calls each between device events; the median repeat is reported with all repeats.  The
 provider and the tracked route alternate inside one process."""
 import argparse
@@ -175,6 +185,118 @@ def one_length(args, F):
     return res
 
 
+def one_chunk_size(args, C):
+    from attend_infer_repeat_amd import _lib, track
+    from attend_infer_repeat_amd.engine_config import EngineConfig
+    from attend_infer_repeat_amd.parse import SceneParser
+    cfg = EngineConfig()
+    R, n_chunks = args.rows, args.stream_chunks
+    if R % C:
+        raise SystemExit("--rows %d is no multiple of %d frames" % (R, C))
+    S, T = R // C, int(cfg.max_steps)
+    ps = SceneParser(cfg, R, seed=0)
+    ps.capture()
+    one = track.SequenceTracker(ps, C, birth_score=0.0)
+    one.capture()
+    st = track.StreamTracker(ps, C, birth_score=0.0)
+    st.capture()
+    eng, dev = ps.engine, ps.engine.device
+    Ft = C * n_chunks
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    start = torch.rand(S, *cfg.img_size, generator=gen) * (torch.rand(S, *cfg.img_size, generator=gen) > 0.8)
+    frames = torch.stack([torch.roll(start, shifts=(f, f // 2), dims=(1, 2)) for f in range(Ft)], 1).contiguous().to(dev)
+    counts = (torch.arange(R, device=dev) % (T + 1)).to(torch.int32)
+    host = lambda t: t.cpu().numpy()
+    chunk = lambda c: frames[:, c * C:(c + 1) * C].contiguous()
+    first = one.track(chunk(0), counts)
+    torch.cuda.synchronize()
+    first = {k: host(first[k]).copy() for k in ("track_id", "obj_state", "affinity", "prev_frame", "prev_slot", "state_counts", "track_owner")}
+    rows, ids = [], []
+    for c in range(n_chunks):
+        out = st.push(chunk(c), None, counts)
+        torch.cuda.synchronize()
+        rows.append({k: host(out[k]).copy() for k in ("what", "boxes", "score", "num_objects")})
+        ids.append({k: host(out[k]).copy() for k in ("track_id", "obj_state", "prev_frame", "prev_slot", "affinity", "state_counts", "track_owner")})
+    same_first = {k: bool((ids[0][k].view(np.uint8) == first[k].view(np.uint8)).all()) for k in first}
+    # the one-shot rule on the concatenation: row s * Ft + c * C + f of the whole is row s * C + f of chunk c
+    cat = lambda k, tail: np.concatenate([r[k].reshape((T, S, C) + tail) for r in rows], 2).reshape((T, S * Ft) + tail)
+    A = rows[0]["what"].reshape(T, R, -1).shape[-1]
+    n_all = np.concatenate([r["num_objects"].reshape(S, C) for r in rows], 1).reshape(-1)
+    ref = track.reference_associate(np.concatenate([r["what"].reshape(T, S, C, A) for r in rows], 2).reshape(T, S * Ft, A),
+                                    cat("boxes", (4,)), cat("score", ()), n_all, Ft, birth_score=0.0, return_margins=True)
+    safe = (ref["gate_margin"] >= 1e-9) & (ref["round_margin"] >= 1e-9)
+    agree = np.zeros((n_chunks, S), bool)
+    for c in range(n_chunks):
+        for k in ("track_id", "obj_state", "prev_frame", "prev_slot"):
+            want = ref[k].reshape(T, S, Ft)[:, :, c * C:(c + 1) * C]
+            ok = (ids[c][k].reshape(T, S, C) == want).all((0, 2))
+            agree[c] = ok if k == "track_id" else agree[c] & ok
+    share = float(agree[:, safe].mean()) if safe.any() else float("nan")
+    res = dict(chunk_frames=C, sequences=S, rows=R, max_steps=T, chunks=n_chunks, sequences_inside_margins=int(safe.sum()),
+               chunks_where_stream_and_one_shot_agree=share, first_chunk_equals_one_shot_device=same_first,
+               ids_issued=int(host(st.state["seq"])[:, 1].sum()), one_shot_tracks=int(ref["num_tracks"].sum()))
+    if share != 1.0 or not all(same_first.values()):
+        print(json.dumps(res))
+        raise SystemExit("the stream and the one-shot rule disagree: share %r, first chunk %r" % (share, same_first))
+    one.track(chunk(0), counts)                                    # the provider's buffers hold chunk 0 for both tails
+    torch.cuda.synchronize()
+    turns = {"one_shot": [], "stream": []}
+    for _ in range(2):
+        for name, t in (("one_shot", one), ("stream", st)):
+            st.reset()
+            torch.cuda.synchronize()
+            turns[name].append(median_ms(lambda: eng._replay_or_run(t._graph, t._plan), args.iters, eng.stream))
+    for name, v in turns.items():
+        res["tail_%s_turns_ms" % name] = [m for m, _ in v]
+        res["tail_%s_repeats_ms" % name] = [r for _, r in v]
+    # the whole call, provider included: here the rows the tail reads were just written by the parse for both routes (replaying a tail
+    # alone leaves the one-shot tail's inputs in the cache, while the stream's state is rewritten by every replay)
+    stream = torch.cuda.current_stream()
+    calls = {"one_shot": [], "stream": []}
+    for _ in range(2):
+        st.reset()
+        calls["one_shot"].append(median_ms(lambda: one.track(chunk(0), counts), args.iters, stream)[0])
+        calls["stream"].append(median_ms(lambda: st.push(chunk(0), None, counts), args.iters, stream)[0])
+    res["call_one_shot_turns_ms"], res["call_stream_turns_ms"] = calls["one_shot"], calls["stream"]
+    res["stream_over_one_shot_call"] = statistics.median(calls["stream"]) / statistics.median(calls["one_shot"])
+    one.track(chunk(0), counts)
+    torch.cuda.synchronize()
+    res["stream_over_one_shot_tail"] = statistics.median(res["tail_stream_turns_ms"]) / statistics.median(res["tail_one_shot_turns_ms"])
+    res["stream_tail_us_per_frame_per_sequence"] = statistics.median(res["tail_stream_turns_ms"]) * 1e3 / C
+    per = {}
+    for _ in range(7):
+        for (fn, a, name) in one._plan[:1] + st._plan:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(eng.stream)
+            _lib.check(fn(*a, eng._sp()), name)
+            e1.record(eng.stream)
+            e1.synchronize()
+            per.setdefault(name, []).append(e0.elapsed_time(e1) * 1e3)
+    res["eager_launch_us"] = {k: statistics.median(v) for k, v in per.items()}
+    # what a chunk costs before its first frame and after its last: the same launch with valid = 0 (the state loaded and stored, the
+    # padding rows and the retired list written, no `what` row to copy on a restarted stream), and on the live table of the pushes
+    # above (valid = 0 again: the state and every live track's slot stored, no row copied either -- none was sighted in the chunk)
+    fn, a, name = st._plan[0]
+    for label, prepare in (("empty_table", st.reset), ("live_table", lambda: [st.push(chunk(c), None, counts) for c in range(2)])):
+        st.reset()
+        prepare()
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            st.valid.zero_()
+        torch.cuda.synchronize()
+        reps = []
+        for _ in range(7):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(eng.stream)
+            _lib.check(fn(*a, eng._sp()), name)
+            e1.record(eng.stream)
+            e1.synchronize()
+            reps.append(e0.elapsed_time(e1) * 1e3)
+        res["eager_stream_valid0_%s_us" % label] = statistics.median(reps)
+    st.release_graphs(); one.release_graphs(); ps.release_graphs()
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 32])
@@ -182,9 +304,18 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--matching", choices=("greedy", "optimal"), default="greedy")
     ap.add_argument("--identity", action="store_true")
+    ap.add_argument("--stream", type=int, nargs="+", default=None, metavar="CHUNK")
+    ap.add_argument("--stream-chunks", type=int, default=4)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("track_bench measures on the GPU; there is no CPU fallback")
+    if args.stream is not None:
+        res = dict(tool="track_bench --stream", device=torch.cuda.get_device_name(0), chunks=[one_chunk_size(args, C) for C in args.stream])
+        print(json.dumps(res))
+        for r in res["chunks"]:
+            for k, v in r.items():
+                print("CHUNK=%-4d %-40s %s" % (r["chunk_frames"], k, v))
+        return res
     res = dict(tool="track_bench", device=torch.cuda.get_device_name(0), lengths=[one_length(args, F) for F in args.frames])
     print(json.dumps(res))
     for r in res["lengths"]:
