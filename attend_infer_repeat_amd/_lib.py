@@ -35,6 +35,17 @@ class AirGemmForm(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class AirWarpForm(ctypes.Structure):
+    """mirror of `struct AirWarpForm` (include/air_hip.h): which kernel a glimpse read / canvas launch runs"""
+    _fields_ = [(n, c_int) for n in ("kernel", "NT", "VEC", "R", "RC", "IM", "SPLIT", "n_split", "n_fwd", "threads", "lds_bytes",
+                                     "vec4", "vec4_glimpse", "vec4_canvas", "per_glimpse", "NB", "RB", "items", "fixed_cap",
+                                     "resident_cap")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+WARP_KERNELS = ("read_fwd", "read_fwd_lean", "read_bwd", "write_fwd", "write_bwd", "fused")     # AIR_WARP_* in order
 GEMM_FAMILIES = ("tile", "c16", "apro", "shortk", "wide", "wide16", "big", "big16")     # AIR_GEMM_FAM_* in order
 
 
@@ -106,6 +117,12 @@ SIGNATURES = {
     "air_canvas_unroll_bands": (c_int, [c_int, c_int]),
     "air_canvas_unroll_fwd_banded": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                              c_float, c_float, P]),
+    "air_st_read_form": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(AirWarpForm)]),
+    "air_st_read_bwd_form": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(AirWarpForm)]),
+    "air_canvas_fwd_form": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(AirWarpForm)]),
+    "air_canvas_bwd_form": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(AirWarpForm)]),
+    "air_canvas_fwd_bwd_form": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        ctypes.POINTER(AirWarpForm)]),
     "air_imp_weight": (c_int, [P, c_int, P, P, c_float, P, P, P, c_int, c_int, P, P, c_float, P]),
     "air_nvil_parts": (c_int, [P, c_int, P, P, P, P, P, P, c_int, P, P]),
     "air_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, c_int, P, c_int,

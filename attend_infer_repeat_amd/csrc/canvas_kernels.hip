@@ -782,16 +782,33 @@ static inline int cv_check_dims(int n, int H, int W, int h, int w) {
     return AIR_OK;
 }
 static inline int bwd_threads(long units) { return units <= 512 ? 512 : ST_THREADS; }
-static int launch_write_fwd(const float *glimpse, const float *where, const float *presence, const float *canvas_in,
-                            const float *obs, float *canvas_steps, float *final_canvas, float *rec_parts, int n_bands,
-                            int T, int B, int H, int W, int h, int w, float mult, float std, void *stream) {
+// a unit count as AirWarpForm::items holds it: the product is taken in long, and one beyond int reports INT_MAX (the grid is
+// min(items, cap) with a cap of a few thousand, so the launch is the one the long count gives)
+static inline int cv_items(long units) { return units > (long)INT_MAX ? INT_MAX : (int)units; }
+// WHICH form the canvas forward runs (st_write_fwd_kernel's bands, workgroup size, LDS and glimpse staging): the decision the three
+// forward entries consume through launch_write_fwd and air_canvas_fwd_form returns.  own_bands: the band rule of air_canvas_unroll_fwd
+// (n_bands is then ignored); otherwise n_bands > 0 is the caller's.
+static int canvas_fwd_form(const float *glimpse, const float *where, const float *obs, const float *canvas_steps,
+                           const float *final_canvas, const float *rec_parts, bool own_bands, int n_bands, int T, int B, int H,
+                           int W, int h, int w, AirWarpForm &f) {
+    f = AirWarpForm{};
+    AIR_REQUIRE(glimpse && where && (final_canvas || canvas_steps), AIR_E_NULL);
+    AIR_REQUIRE(!rec_parts || obs, AIR_E_NULL);
+    AIR_REQUIRE(T > 0 && (own_bands || n_bands > 0), AIR_E_SHAPE);
+    int st = cv_check_dims(B, H, W, h, w);
+    if (st) return st;
     int NB, RB;
+    if (own_bands) {
+        // the complete per-sample reconstruction term needs the whole image in one workgroup; without it the bands are free
+        int nb = 1;
+        if (!rec_parts && (long)B * T <= 1024) nb = 256 / B < 1 ? 1 : 256 / B;
+        wr_bands(H, nb, &NB, &RB);
+        n_bands = NB;
+    }
     wr_bands(H, n_bands, &NB, &RB);
     AIR_REQUIRE(NB == n_bands || !rec_parts, AIR_E_SHAPE);   // the caller sized rec_parts for exactly n_bands shares
     const size_t lds = carve_wr_bytes(T, RB, W, h, w);
     AIR_REQUIRE(lds <= CV_MAX_LDS, AIR_E_UNSUPPORTED);
-    const int vec4g = (w % 4 == 0) && air_aligned16(glimpse);   // 16-byte groups that never straddle a glimpse row
-    { int st_ = cv_allow_lds(st_write_fwd_kernel, lds); if (st_) return st_; }
     // one pixel per thread while the launch is far from filling the chip (latency regime), 256-thread workgroups beyond
     const long units = (long)B * NB;
     int wr_threads = units <= 512 ? 512 : ST_THREADS;          // (measured at 50x50: 512 units 14 us with 512 threads, 16 / 17.5 with 1024 / 256)
@@ -800,10 +817,32 @@ static int launch_write_fwd(const float *glimpse, const float *where, const floa
         wr_threads = px >= 1024 ? 1024 : ((px + 63) / 64) * 64;
         if (wr_threads < 64) wr_threads = 64;
     }
-    const WriteFwdArgs a = {glimpse, where, presence, canvas_in, obs, canvas_steps, final_canvas, rec_parts, T, B, NB, RB, H, W, h, w,
-                            lin_step(W), lin_step(H), mult, std, vec4g};
-    const int cap = units > 256 * 8 ? cv_resident_cap(st_write_fwd_kernel, wr_threads, lds, 256 * 8) : 256 * 8;
-    hipLaunchKernelGGL(st_write_fwd_kernel, dim3(cv_grid(units, cap)), dim3(wr_threads), lds, air_stream(stream), a);
+    f.kernel = AIR_WARP_WRITE_FWD;
+    f.threads = wr_threads; f.lds_bytes = (int)lds;
+    f.vec4_glimpse = (w % 4 == 0) && air_aligned16(glimpse);   // 16-byte groups that never straddle a glimpse row
+    f.NB = NB; f.RB = RB;
+    f.items = cv_items(units); f.fixed_cap = 256 * 8; f.resident_cap = units > 256 * 8;
+    return AIR_OK;
+}
+extern "C" int air_canvas_fwd_form(const float *glimpse, const float *where, const float *obs, const float *canvas_steps,
+                                   const float *final_canvas, const float *rec_parts, int n_bands, int T, int B, int H, int W,
+                                   int h, int w, AirWarpForm *out) {
+    AIR_REQUIRE(out, AIR_E_NULL);
+    AIR_REQUIRE(n_bands >= 0, AIR_E_SHAPE);
+    return canvas_fwd_form(glimpse, where, obs, canvas_steps, final_canvas, rec_parts, n_bands == 0, n_bands, T, B, H, W, h, w, *out);
+}
+static int launch_write_fwd(const float *glimpse, const float *where, const float *presence, const float *canvas_in,
+                            const float *obs, float *canvas_steps, float *final_canvas, float *rec_parts, bool own_bands, int n_bands,
+                            int T, int B, int H, int W, int h, int w, float mult, float std, void *stream) {
+    AirWarpForm f;
+    int st = canvas_fwd_form(glimpse, where, obs, canvas_steps, final_canvas, rec_parts, own_bands, n_bands, T, B, H, W, h, w, f);
+    if (st) return st;
+    const size_t lds = (size_t)f.lds_bytes;
+    { int st_ = cv_allow_lds(st_write_fwd_kernel, lds); if (st_) return st_; }
+    const WriteFwdArgs a = {glimpse, where, presence, canvas_in, obs, canvas_steps, final_canvas, rec_parts, T, B, f.NB, f.RB, H, W, h, w,
+                            lin_step(W), lin_step(H), mult, std, f.vec4_glimpse};
+    const int cap = f.resident_cap ? cv_resident_cap(st_write_fwd_kernel, f.threads, lds, 256 * 8) : f.fixed_cap;
+    hipLaunchKernelGGL(st_write_fwd_kernel, dim3(cv_grid(f.items, cap)), dim3(f.threads), lds, air_stream(stream), a);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }
@@ -811,10 +850,7 @@ static int launch_write_fwd(const float *glimpse, const float *where, const floa
 extern "C" int air_st_write_fwd(const float *glimpse, const float *where, const float *presence,
                                 const float *canvas_in, float *canvas_out, int n, int H, int W, int h, int w,
                                 void *stream) {
-    AIR_REQUIRE(glimpse && where && canvas_out, AIR_E_NULL);
-    int st = cv_check_dims(n, H, W, h, w);
-    if (st) return st;
-    return launch_write_fwd(glimpse, where, presence, canvas_in, nullptr, nullptr, canvas_out, nullptr, 1, 1, n, H, W, h,
+    return launch_write_fwd(glimpse, where, presence, canvas_in, nullptr, nullptr, canvas_out, nullptr, false, 1, 1, n, H, W, h,
                             w, 1.0f, 1.0f, stream);
 }
 
@@ -822,17 +858,7 @@ extern "C" int air_canvas_unroll_fwd(const float *glimpse, const float *where, c
                                      const float *obs, float *canvas_steps, float *final_canvas,
                                      float *rec_per_sample, int T, int B, int H, int W, int h, int w, float mult,
                                      float std, void *stream) {
-    AIR_REQUIRE(glimpse && where && (final_canvas || canvas_steps), AIR_E_NULL);
-    AIR_REQUIRE(!rec_per_sample || obs, AIR_E_NULL);
-    AIR_REQUIRE(T > 0, AIR_E_SHAPE);
-    int st = cv_check_dims(B, H, W, h, w);
-    if (st) return st;
-    // the complete per-sample reconstruction term needs the whole image in one workgroup; without it the bands are free
-    int nb = 1;
-    if (!rec_per_sample && (long)B * T <= 1024) nb = 256 / B < 1 ? 1 : 256 / B;
-    int NB, RB;
-    wr_bands(H, nb, &NB, &RB);
-    return launch_write_fwd(glimpse, where, presence, nullptr, obs, canvas_steps, final_canvas, rec_per_sample, NB, T, B,
+    return launch_write_fwd(glimpse, where, presence, nullptr, obs, canvas_steps, final_canvas, rec_per_sample, true, 0, T, B,
                             H, W, h, w, mult, std, stream);
 }
 
@@ -848,31 +874,30 @@ extern "C" int air_canvas_unroll_fwd_banded(const float *glimpse, const float *w
                                             const float *obs, float *canvas_steps, float *final_canvas,
                                             float *rec_parts, int n_bands, int T, int B, int H, int W, int h, int w,
                                             float mult, float std, void *stream) {
-    AIR_REQUIRE(glimpse && where && (final_canvas || canvas_steps), AIR_E_NULL);
-    AIR_REQUIRE(!rec_parts || obs, AIR_E_NULL);
-    AIR_REQUIRE(T > 0 && n_bands > 0, AIR_E_SHAPE);
-    int st = cv_check_dims(B, H, W, h, w);
-    if (st) return st;
-    return launch_write_fwd(glimpse, where, presence, nullptr, obs, canvas_steps, final_canvas, rec_parts, n_bands, T, B,
+    return launch_write_fwd(glimpse, where, presence, nullptr, obs, canvas_steps, final_canvas, rec_parts, false, n_bands, T, B,
                             H, W, h, w, mult, std, stream);
 }
 
-static int launch_write_bwd(const float *glimpse, const float *where, const float *presence, const float *dcanvas,
-                            const float *final_canvas, const float *obs, float *dglimpse, float *dwhere,
-                            float *dpresence, int T, int B, int H, int W, int h, int w, float mult, float std,
-                            float loss_scale, void *stream, const NvilArgs *nvil = nullptr) {
+// WHICH form the canvas backward runs -- st_write_bwd_gs_kernel<RC, IM>: recompute (no dcanvas, no final_canvas), image-major (the
+// throughput regime of the stored-canvas form) or unit-major --, its workgroup size, LDS and staging: the decision launch_write_bwd
+// consumes and air_canvas_bwd_form returns.
+// Developer switches, read at every call (tests and A/B runs switch forms inside one process; a captured graph keeps what it
+// captured): AIR_CANVAS_BWD_IMG=0 keeps the unit-major form beyond 2048 units, AIR_CANVAS_GS_THREADS forces the workgroup size,
+// AIR_CANVAS_IMG_MIN_UNITS moves the switch to the image-major form
+static int canvas_bwd_form(const float *glimpse, const float *where, const float *dcanvas, const float *final_canvas,
+                           const float *obs, const float *dglimpse, const float *dwhere, int T, int B, int H, int W, int h, int w,
+                           AirWarpForm &f) {
+    f = AirWarpForm{};
+    AIR_REQUIRE(glimpse && where && (dcanvas || obs) && dglimpse && dwhere, AIR_E_NULL);
+    AIR_REQUIRE(T > 0, AIR_E_SHAPE);
+    int st = cv_check_dims(B, H, W, h, w);
+    if (st) return st;
     const bool rc = !dcanvas && !final_canvas;                // recompute form: the canvas is re-formed on the unit's footprint
-    NvilArgs nv = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, nullptr, nullptr};
-    if (nvil) nv = *nvil;
-    const int vec4g = (w % 4 == 0) && air_aligned16(glimpse);   // 16-byte groups that never straddle a glimpse row
-    const int vec4c = ((H * W) % 4 == 0) && (dcanvas ? air_aligned16(dcanvas) : ((rc || air_aligned16(final_canvas)) && air_aligned16(obs)));
+    f.kernel = AIR_WARP_WRITE_BWD;
+    f.vec4_glimpse = (w % 4 == 0) && air_aligned16(glimpse);   // 16-byte groups that never straddle a glimpse row
+    f.vec4_canvas = ((H * W) % 4 == 0) && (dcanvas ? air_aligned16(dcanvas) : ((rc || air_aligned16(final_canvas)) && air_aligned16(obs)));
     // 512 threads while the launch does not fill the chip; beyond that 256-thread workgroups hide each other's barriers
     const int wr_threads = bwd_threads((long)B * T);
-    const WriteBwdArgs a = {glimpse, where, presence, dcanvas, final_canvas, obs, dglimpse, dwhere, dpresence, T, B, H, W, h, w,
-                            lin_step(W), lin_step(H), mult, std, loss_scale, vec4g, vec4c, 1};
-    // developer switches, read at every call (tests and A/B runs switch forms inside one process; a captured graph keeps what it
-    // captured): AIR_CANVAS_BWD_IMG=0 keeps the unit-major form beyond 2048 units, AIR_CANVAS_GS_THREADS forces the workgroup size,
-    // AIR_CANVAS_IMG_MIN_UNITS moves the switch to the image-major form
     const char *env_img = getenv("AIR_CANVAS_BWD_IMG");
     const int img_major = env_img ? atoi(env_img) : 1;
     const char *env_thr = getenv("AIR_CANVAS_GS_THREADS");
@@ -884,10 +909,8 @@ static int launch_write_bwd(const float *glimpse, const float *where, const floa
         const int thr_r = thr_f && thr_f <= 512 ? thr_f : wr_threads;
         const size_t lds_r = carve_gs_bytes(H, W, h, w, 1, T, thr_r / 64);
         AIR_REQUIRE(lds_r <= CV_MAX_LDS, AIR_E_UNSUPPORTED);
-        { int st_ = cv_allow_lds(st_write_bwd_gs_kernel<true, false>, lds_r); if (st_) return st_; }
-        const int grid_r = cv_grid((long)T * B, 256 * 8) + (nvil ? 1 : 0);
-        hipLaunchKernelGGL((st_write_bwd_gs_kernel<true, false>), dim3(grid_r), dim3(thr_r), lds_r, air_stream(stream), a, nv);
-        AIR_LAUNCH_CHECK();
+        f.RC = 1; f.threads = thr_r; f.lds_bytes = (int)lds_r;
+        f.items = cv_items((long)T * B); f.fixed_cap = 256 * 8;
         return AIR_OK;
     }
     if (img_major && !dcanvas && final_canvas && (long)T * B > img_min_units && T <= 8) {
@@ -899,11 +922,8 @@ static int launch_write_bwd(const float *glimpse, const float *where, const floa
         }
         const size_t lds_i = carve_gs_bytes(H, W, h, w, T, T, thr_i / 64);
         if (lds_i <= CV_MAX_LDS) {
-            { int st_ = cv_allow_lds(st_write_bwd_gs_kernel<false, true>, lds_i); if (st_) return st_; }
-            const int cap_i = cv_resident_cap(st_write_bwd_gs_kernel<false, true>, thr_i, lds_i, 256 * 2);
-            const int grid_i = cv_grid(B, cap_i) + (nvil ? 1 : 0);
-            hipLaunchKernelGGL((st_write_bwd_gs_kernel<false, true>), dim3(grid_i), dim3(thr_i), lds_i, air_stream(stream), a, nv);
-            AIR_LAUNCH_CHECK();
+            f.IM = 1; f.threads = thr_i; f.lds_bytes = (int)lds_i;
+            f.items = B; f.fixed_cap = 0; f.resident_cap = 1;
             return AIR_OK;
         }
     }
@@ -911,11 +931,48 @@ static int launch_write_bwd(const float *glimpse, const float *where, const floa
     if (!thr_f && carve_gs_bytes(H, W, h, w, 1, 1, 4) > 40 * 1024) thr_u = 512;
     const size_t lds_u = carve_gs_bytes(H, W, h, w, 1, 1, thr_u / 64);
     AIR_REQUIRE(lds_u <= CV_MAX_LDS, AIR_E_UNSUPPORTED);
-    { int st_ = cv_allow_lds(st_write_bwd_gs_kernel<false, false>, lds_u); if (st_) return st_; }
-    int cap_u = 256 * 8;
-    if ((long)T * B > cap_u) cap_u = cv_resident_cap(st_write_bwd_gs_kernel<false, false>, thr_u, lds_u, cap_u);
-    const int grid_u = cv_grid((long)T * B, cap_u) + (nvil ? 1 : 0);
-    hipLaunchKernelGGL((st_write_bwd_gs_kernel<false, false>), dim3(grid_u), dim3(thr_u), lds_u, air_stream(stream), a, nv);
+    f.threads = thr_u; f.lds_bytes = (int)lds_u;
+    f.items = cv_items((long)T * B); f.fixed_cap = 256 * 8; f.resident_cap = (long)T * B > 256 * 8;
+    return AIR_OK;
+}
+extern "C" int air_canvas_bwd_form(const float *glimpse, const float *where, const float *dcanvas, const float *final_canvas,
+                                   const float *obs, const float *dglimpse, const float *dwhere, int T, int B, int H, int W,
+                                   int h, int w, AirWarpForm *out) {
+    AIR_REQUIRE(out, AIR_E_NULL);
+    return canvas_bwd_form(glimpse, where, dcanvas, final_canvas, obs, dglimpse, dwhere, T, B, H, W, h, w, *out);
+}
+static int launch_write_bwd(const float *glimpse, const float *where, const float *presence, const float *dcanvas,
+                            const float *final_canvas, const float *obs, float *dglimpse, float *dwhere,
+                            float *dpresence, int T, int B, int H, int W, int h, int w, float mult, float std,
+                            float loss_scale, void *stream, const NvilArgs *nvil = nullptr) {
+    AirWarpForm f;
+    int st = canvas_bwd_form(glimpse, where, dcanvas, final_canvas, obs, dglimpse, dwhere, T, B, H, W, h, w, f);
+    if (st) return st;
+    NvilArgs nv = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, nullptr, nullptr};
+    if (nvil) nv = *nvil;
+    const WriteBwdArgs a = {glimpse, where, presence, dcanvas, final_canvas, obs, dglimpse, dwhere, dpresence, T, B, H, W, h, w,
+                            lin_step(W), lin_step(H), mult, std, loss_scale, f.vec4_glimpse, f.vec4_canvas, 1};
+    const size_t lds = (size_t)f.lds_bytes;
+    if (f.RC) {
+        { int st_ = cv_allow_lds(st_write_bwd_gs_kernel<true, false>, lds); if (st_) return st_; }
+        const int grid_r = cv_grid(f.items, f.fixed_cap) + (nvil ? 1 : 0);
+        hipLaunchKernelGGL((st_write_bwd_gs_kernel<true, false>), dim3(grid_r), dim3(f.threads), lds, air_stream(stream), a, nv);
+        AIR_LAUNCH_CHECK();
+        return AIR_OK;
+    }
+    if (f.IM) {
+        { int st_ = cv_allow_lds(st_write_bwd_gs_kernel<false, true>, lds); if (st_) return st_; }
+        const int cap_i = cv_resident_cap(st_write_bwd_gs_kernel<false, true>, f.threads, lds, 256 * 2);
+        const int grid_i = cv_grid(f.items, cap_i) + (nvil ? 1 : 0);
+        hipLaunchKernelGGL((st_write_bwd_gs_kernel<false, true>), dim3(grid_i), dim3(f.threads), lds, air_stream(stream), a, nv);
+        AIR_LAUNCH_CHECK();
+        return AIR_OK;
+    }
+    { int st_ = cv_allow_lds(st_write_bwd_gs_kernel<false, false>, lds); if (st_) return st_; }
+    int cap_u = f.fixed_cap;
+    if (f.resident_cap) cap_u = cv_resident_cap(st_write_bwd_gs_kernel<false, false>, f.threads, lds, cap_u);
+    const int grid_u = cv_grid(f.items, cap_u) + (nvil ? 1 : 0);
+    hipLaunchKernelGGL((st_write_bwd_gs_kernel<false, false>), dim3(grid_u), dim3(f.threads), lds, air_stream(stream), a, nv);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }
@@ -923,9 +980,7 @@ static int launch_write_bwd(const float *glimpse, const float *where, const floa
 extern "C" int air_st_write_bwd(const float *glimpse, const float *where, const float *presence,
                                 const float *dcanvas, float *dglimpse, float *dwhere, float *dpresence, int n, int H,
                                 int W, int h, int w, void *stream) {
-    AIR_REQUIRE(glimpse && where && dcanvas && dglimpse && dwhere, AIR_E_NULL);
-    int st = cv_check_dims(n, H, W, h, w);
-    if (st) return st;
+    AIR_REQUIRE(dcanvas, AIR_E_NULL);                          // (everything else: canvas_bwd_form)
     return launch_write_bwd(glimpse, where, presence, dcanvas, nullptr, nullptr, dglimpse, dwhere, dpresence, 1, n, H,
                             W, h, w, 1.0f, 1.0f, 1.0f, stream);
 }
@@ -934,10 +989,7 @@ extern "C" int air_canvas_unroll_bwd(const float *glimpse, const float *where, c
                                      const float *obs, const float *final_canvas, float *dglimpse, float *dwhere,
                                      int T, int B, int H, int W, int h, int w, float mult, float std,
                                      float loss_scale, void *stream) {
-    AIR_REQUIRE(glimpse && where && obs && dglimpse && dwhere, AIR_E_NULL);      // final_canvas == NULL: the recompute form
-    AIR_REQUIRE(T > 0, AIR_E_SHAPE);
-    int st = cv_check_dims(B, H, W, h, w);
-    if (st) return st;
+    // final_canvas == NULL: the recompute form (required operands, T and the dimensions: canvas_bwd_form)
     return launch_write_bwd(glimpse, where, presence, nullptr, final_canvas, obs, dglimpse, dwhere, nullptr, T, B, H, W,
                             h, w, mult, std, loss_scale, stream);
 }
@@ -948,10 +1000,7 @@ extern "C" int air_canvas_unroll_bwd_dpresence(const float *glimpse, const float
                                                const float *obs, const float *final_canvas, float *dglimpse, float *dwhere,
                                                float *dpresence, int T, int B, int H, int W, int h, int w, float mult, float std,
                                                float loss_scale, void *stream) {
-    AIR_REQUIRE(glimpse && where && obs && dglimpse && dwhere && dpresence, AIR_E_NULL);
-    AIR_REQUIRE(T > 0, AIR_E_SHAPE);
-    int st = cv_check_dims(B, H, W, h, w);
-    if (st) return st;
+    AIR_REQUIRE(dpresence, AIR_E_NULL);
     return launch_write_bwd(glimpse, where, presence, nullptr, final_canvas, obs, dglimpse, dwhere, dpresence, T, B, H, W,
                             h, w, mult, std, loss_scale, stream);
 }
@@ -965,8 +1014,6 @@ extern "C" int air_canvas_unroll_bwd_nvil(const float *glimpse, const float *whe
     AIR_REQUIRE(glimpse && where && obs && dglimpse && dwhere, AIR_E_NULL);      // final_canvas == NULL: the recompute form
     AIR_REQUIRE(imp_parts && baseline && logp && nvil_out, AIR_E_NULL);
     AIR_REQUIRE(T > 0 && n_parts > 0, AIR_E_SHAPE);
-    int st = cv_check_dims(B, H, W, h, w);
-    if (st) return st;
     const NvilArgs nv = {imp_parts, baseline, logp, nvil_out, dlogp, dbaseline, B, n_parts, imp_sum, ema_dev};
     return launch_write_bwd(glimpse, where, presence, nullptr, final_canvas, obs, dglimpse, dwhere, nullptr, T, B, H, W,
                             h, w, mult, std, loss_scale, stream, &nv);
@@ -985,7 +1032,7 @@ __global__ __launch_bounds__(1024) void canvas_fused_gs_kernel(WriteFwdArgs f, W
     }
 }
 // The fused launch's shape for a problem: threads per workgroup, and whether it fits (LDS of both roles, both grids small
-// enough to run side by side).  n_split = workgroups per backward unit (1 or 2).
+// enough to run side by side).  n_split = workgroups per backward unit (1 .. 4).
 static int fused_shape(int n_bands, int n_split, int T, int B, int H, int W, int h, int w, int *threads, size_t *lds) {
     int NB, RB;
     wr_bands(H, n_bands, &NB, &RB);
@@ -1004,12 +1051,12 @@ extern "C" int air_canvas_unroll_fwd_bwd_fits(int n_bands, int n_split, int T, i
     if (T <= 0 || cv_check_dims(B, H, W, h, w)) return 0;
     return fused_shape(n_bands, n_split, T, B, H, W, h, w, &threads, &lds) == AIR_OK ? 1 : 0;
 }
-// forward (banded, as air_canvas_unroll_fwd_banded) + backward (recompute form of air_canvas_unroll_bwd) as ONE launch.
-// n_split workgroups per backward unit: dwhere then holds n_split slabs [n_split][T*B][4] whose SUM is the gradient.
-extern "C" int air_canvas_unroll_fwd_bwd(const float *glimpse, const float *where, const float *presence, const float *obs,
-                                         float *canvas_steps, float *final_canvas, float *rec_parts, int n_bands,
-                                         float *dglimpse, float *dwhere, int n_split, int T, int B, int H, int W, int h, int w,
-                                         float mult, float std, float loss_scale, void *stream) {
+// WHICH form the fused launch runs (canvas_fused_gs_kernel<SPLIT>, fused_shape's threads and LDS, the bands and both stagings): the
+// decision air_canvas_unroll_fwd_bwd consumes and air_canvas_fwd_bwd_form returns.
+static int canvas_fused_form(const float *glimpse, const float *where, const float *obs, const float *canvas_steps,
+                             const float *final_canvas, const float *rec_parts, int n_bands, const float *dglimpse, const float *dwhere,
+                             int n_split, int T, int B, int H, int W, int h, int w, AirWarpForm &f) {
+    f = AirWarpForm{};
     AIR_REQUIRE(glimpse && where && obs && (final_canvas || canvas_steps) && rec_parts && dglimpse && dwhere, AIR_E_NULL);
     AIR_REQUIRE(T > 0 && n_bands > 0, AIR_E_SHAPE);
     int st = cv_check_dims(B, H, W, h, w);
@@ -1017,18 +1064,41 @@ extern "C" int air_canvas_unroll_fwd_bwd(const float *glimpse, const float *wher
     int threads; size_t lds;
     st = fused_shape(n_bands, n_split, T, B, H, W, h, w, &threads, &lds);
     if (st) return st;
-    int NB, RB;
-    wr_bands(H, n_bands, &NB, &RB);
-    const int vec4g = (w % 4 == 0) && air_aligned16(glimpse);
-    const int vec4c = ((H * W) % 4 == 0) && air_aligned16(obs);
-    { int st_ = n_split > 1 ? cv_allow_lds(canvas_fused_gs_kernel<true>, lds) : cv_allow_lds(canvas_fused_gs_kernel<false>, lds); if (st_) return st_; }
-    const WriteFwdArgs f = {glimpse, where, presence, nullptr, obs, canvas_steps, final_canvas, rec_parts, T, B, NB, RB, H, W, h, w,
-                            lin_step(W), lin_step(H), mult, std, vec4g};
+    wr_bands(H, n_bands, &f.NB, &f.RB);
+    f.kernel = AIR_WARP_FUSED;
+    f.RC = 1; f.SPLIT = n_split > 1; f.n_split = n_split;
+    f.threads = threads; f.lds_bytes = (int)lds;
+    f.vec4_glimpse = (w % 4 == 0) && air_aligned16(glimpse);
+    f.vec4_canvas = ((H * W) % 4 == 0) && air_aligned16(obs);
+    f.n_fwd = B * f.NB;
+    f.items = f.n_fwd + T * B * n_split;                  // (fused_shape: both parts at most 4096)
+    return AIR_OK;
+}
+extern "C" int air_canvas_fwd_bwd_form(const float *glimpse, const float *where, const float *obs, const float *canvas_steps,
+                                       const float *final_canvas, const float *rec_parts, int n_bands, const float *dglimpse,
+                                       const float *dwhere, int n_split, int T, int B, int H, int W, int h, int w, AirWarpForm *out) {
+    AIR_REQUIRE(out, AIR_E_NULL);
+    return canvas_fused_form(glimpse, where, obs, canvas_steps, final_canvas, rec_parts, n_bands, dglimpse, dwhere, n_split, T, B, H, W,
+                             h, w, *out);
+}
+// forward (banded, as air_canvas_unroll_fwd_banded) + backward (recompute form of air_canvas_unroll_bwd) as ONE launch.
+// n_split workgroups per backward unit: dwhere then holds n_split slabs [n_split][T*B][4] whose SUM is the gradient.
+extern "C" int air_canvas_unroll_fwd_bwd(const float *glimpse, const float *where, const float *presence, const float *obs,
+                                         float *canvas_steps, float *final_canvas, float *rec_parts, int n_bands,
+                                         float *dglimpse, float *dwhere, int n_split, int T, int B, int H, int W, int h, int w,
+                                         float mult, float std, float loss_scale, void *stream) {
+    AirWarpForm ff;
+    int st = canvas_fused_form(glimpse, where, obs, canvas_steps, final_canvas, rec_parts, n_bands, dglimpse, dwhere, n_split, T, B, H, W,
+                               h, w, ff);
+    if (st) return st;
+    const size_t lds = (size_t)ff.lds_bytes;
+    { int st_ = ff.SPLIT ? cv_allow_lds(canvas_fused_gs_kernel<true>, lds) : cv_allow_lds(canvas_fused_gs_kernel<false>, lds); if (st_) return st_; }
+    const WriteFwdArgs f = {glimpse, where, presence, nullptr, obs, canvas_steps, final_canvas, rec_parts, T, B, ff.NB, ff.RB, H, W, h, w,
+                            lin_step(W), lin_step(H), mult, std, ff.vec4_glimpse};
     const WriteBwdArgs b = {glimpse, where, presence, nullptr, nullptr, obs, dglimpse, dwhere, nullptr, T, B, H, W, h, w,
-                            lin_step(W), lin_step(H), mult, std, loss_scale, vec4g, vec4c, n_split};
-    const int n_fwd = B * NB;
-    if (n_split > 1) hipLaunchKernelGGL(canvas_fused_gs_kernel<true>, dim3(n_fwd + T * B * n_split), dim3(threads), lds, air_stream(stream), f, b, n_fwd);
-    else hipLaunchKernelGGL(canvas_fused_gs_kernel<false>, dim3(n_fwd + T * B), dim3(threads), lds, air_stream(stream), f, b, n_fwd);
+                            lin_step(W), lin_step(H), mult, std, loss_scale, ff.vec4_glimpse, ff.vec4_canvas, ff.n_split};
+    if (ff.SPLIT) hipLaunchKernelGGL(canvas_fused_gs_kernel<true>, dim3(ff.items), dim3(ff.threads), lds, air_stream(stream), f, b, ff.n_fwd);
+    else hipLaunchKernelGGL(canvas_fused_gs_kernel<false>, dim3(ff.items), dim3(ff.threads), lds, air_stream(stream), f, b, ff.n_fwd);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

@@ -318,8 +318,11 @@ static inline int st_allow_lds(K kernel, size_t lds) {
     return e == hipSuccess ? AIR_OK : (int)e;
 }
 
-extern "C" int air_st_read_fwd(const float *img, const float *where, float *glimpse, int n, int n_img, int H, int W,
-                               int h, int w, void *stream) {
+// WHICH kernel air_st_read_fwd runs: the decision the launch below consumes and air_st_read_form returns (no launch, no device
+// memory: shapes, pointer values and the process-wide AIR_ST_READ_* switches only).
+static int st_read_fwd_form(const float *img, const float *where, const float *glimpse, int n, int n_img, int H, int W, int h, int w,
+                            AirWarpForm &f) {
+    f = AirWarpForm{};
     AIR_REQUIRE(img && where && glimpse, AIR_E_NULL);
     int st = st_check_dims(n, H, W, h, w);
     if (st) return st;
@@ -328,6 +331,7 @@ extern "C" int air_st_read_fwd(const float *img, const float *where, float *glim
     AIR_REQUIRE(lds <= ST_MAX_LDS, AIR_E_UNSUPPORTED);
     const int vec4 = ((H * W) % 4 == 0) && air_aligned16(img);
     const int nq = (H * W) / 4;
+    f.items = n_img; f.fixed_cap = 256 * 8; f.resident_cap = n_img > 256 * 8;
     // (W < 4: a 16-byte group of the row-major image can cross more than one row boundary, which the lean kernel's bordered staging
     //  -- "+2 once past the end of the row" -- does not handle: narrow images take the generic kernel)
     if (vec4 && W >= 4 && air_aligned16(where) && nq <= 3 * 1024) {
@@ -340,52 +344,80 @@ extern "C" int air_st_read_fwd(const float *img, const float *where, float *glim
         const bool vec = lean >= 2 && R >= 2 && (w % 4 == 0) && air_aligned16(glimpse) && read_lean_bytes(H, W, h, w, R) <= ST_MAX_LDS;
         const size_t lds_l = read_lean_bytes(H, W, h, w, vec ? R : 1);
         if (lean && lds_l <= ST_MAX_LDS) {
-            const bool big = touched > ((size_t)64 << 20);
             int nthr = threads;
             {   // (measured, profiles/r04_st_read_lean.txt: 256 threads beat 320 / 384 / 512 out of cache although 320 would form the
                 //  300 output groups of a 50x50 / 20x20 / T=3 image in one round: 186 against 198 / 212 / 210 us at 65536 images)
                 static const int forced = getenv("AIR_ST_READ_THREADS") ? atoi(getenv("AIR_ST_READ_THREADS")) : 0;
                 if (forced >= 64 && forced <= 1024 && forced % 64 == 0 && 3 * forced >= nq) nthr = forced;
             }
-            // out of cache: at least four images per workgroup (the per-workgroup preamble -- linspace, border, index set-up -- and the
-            // register prefetch of the next image only pay then: 25.1 against 26.8-27.2 us at 8192 images, 49.5-51 against 55-57 us at
-            // 16384, profiles/r04_st_read_grid.txt), at most 16384 workgroups (177.6 against 186 us with 2048 at 65536 images)
-            static const int grid_forced = getenv("AIR_ST_READ_GRID") ? atoi(getenv("AIR_ST_READ_GRID")) : 0;
-            // The grid is a whole multiple of the workgroups resident at once (air_resident_grid: other caps run in unequal phases).
-            const dim3 th(nthr);
-#define AIR_READ_CASE(NT_, VEC_) do { { int st_ = st_allow_lds(st_read_fwd_lean_kernel<NT_, VEC_>, lds_l); if (st_) return st_; } \
-            int cap_ = 256 * 8;                                                                                               \
-            if (n_img > cap_) {                                                                                               \
-                const int res_ = air_resident_grid(st_read_fwd_lean_kernel<NT_, VEC_>, nthr, lds_l, 256 * 8);                 \
-                int want_ = big ? (VEC_ ? n_img / 4 : 16384) : res_;    /* (one glimpse per image: 46 against 50 us at 24576 images with 16384) */ \
-                want_ = want_ > 16384 ? 16384 : want_;                                                                        \
-                /* images above 3 x 256 groups (100x100: 1024-thread workgroups, two per CU): exactly the resident workgroups, each    \
-                   walking its images with the next one in flight -- 0.74 / 0.75 / 0.70 of 8 TB/s at 8192 / 32768 / 65536 images of    \
-                   100x100 / 28x28 / T=5 against 0.71 / 0.73 / 0.66 with the rule above; beyond 48 k images two images per workgroup   \
-                   (0.70 against 0.70: a tie, kept for the short workgroups' tail) -- profiles/r06_read_c4_grid.txt */                 \
-                if (big && nthr == 1024) want_ = n_img >= 49152 ? n_img / 2 : res_;                                              \
-                if (grid_forced > 0) want_ = grid_forced;                                                                     \
-                cap_ = want_ <= res_ ? res_ : (want_ / res_) * res_;                                                          \
-            }                                                                                                                 \
-            hipLaunchKernelGGL((st_read_fwd_lean_kernel<NT_, VEC_>), dim3(st_grid(n_img, cap_)), th, lds_l, air_stream(stream), img, where, glimpse, \
-                               n, n_img, H, W, h, w, lin_step(w), lin_step(h)); } while (0)
-            if (big) { if (vec) AIR_READ_CASE(true, true); else AIR_READ_CASE(true, false); }
-            else { if (vec) AIR_READ_CASE(false, true); else AIR_READ_CASE(false, false); }
-#undef AIR_READ_CASE
-            AIR_LAUNCH_CHECK();
+            f.kernel = AIR_WARP_READ_FWD_LEAN;
+            f.NT = touched > ((size_t)64 << 20);
+            f.VEC = vec; f.R = vec ? R : 1;
+            f.threads = nthr; f.lds_bytes = (int)lds_l; f.vec4 = 1;
             return AIR_OK;
         }
     }
+    f.kernel = AIR_WARP_READ_FWD;
+    f.threads = ST_THREADS; f.lds_bytes = (int)lds; f.vec4 = vec4;
+    return AIR_OK;
+}
+extern "C" int air_st_read_form(const float *img, const float *where, const float *glimpse, int n, int n_img, int H, int W, int h,
+                                int w, AirWarpForm *out) {
+    AIR_REQUIRE(out, AIR_E_NULL);
+    return st_read_fwd_form(img, where, glimpse, n, n_img, H, W, h, w, *out);
+}
+
+extern "C" int air_st_read_fwd(const float *img, const float *where, float *glimpse, int n, int n_img, int H, int W,
+                               int h, int w, void *stream) {
+    AirWarpForm f;
+    int st = st_read_fwd_form(img, where, glimpse, n, n_img, H, W, h, w, f);
+    if (st) return st;
+    if (f.kernel == AIR_WARP_READ_FWD_LEAN) {
+        const bool big = f.NT != 0, vec = f.VEC != 0;
+        const int nthr = f.threads;
+        const size_t lds_l = (size_t)f.lds_bytes;
+        // out of cache: at least four images per workgroup (the per-workgroup preamble -- linspace, border, index set-up -- and the
+        // register prefetch of the next image only pay then: 25.1 against 26.8-27.2 us at 8192 images, 49.5-51 against 55-57 us at
+        // 16384, profiles/r04_st_read_grid.txt), at most 16384 workgroups (177.6 against 186 us with 2048 at 65536 images)
+        static const int grid_forced = getenv("AIR_ST_READ_GRID") ? atoi(getenv("AIR_ST_READ_GRID")) : 0;
+        // The grid is a whole multiple of the workgroups resident at once (air_resident_grid: other caps run in unequal phases).
+        const dim3 th(nthr);
+#define AIR_READ_CASE(NT_, VEC_) do { { int st_ = st_allow_lds(st_read_fwd_lean_kernel<NT_, VEC_>, lds_l); if (st_) return st_; } \
+        int cap_ = f.fixed_cap;                                                                                           \
+        if (f.resident_cap) {                                                                                             \
+            const int res_ = air_resident_grid(st_read_fwd_lean_kernel<NT_, VEC_>, nthr, lds_l, 256 * 8);                 \
+            int want_ = big ? (VEC_ ? n_img / 4 : 16384) : res_;    /* (one glimpse per image: 46 against 50 us at 24576 images with 16384) */ \
+            want_ = want_ > 16384 ? 16384 : want_;                                                                        \
+            /* images above 3 x 256 groups (100x100: 1024-thread workgroups, two per CU): exactly the resident workgroups, each    \
+               walking its images with the next one in flight -- 0.74 / 0.75 / 0.70 of 8 TB/s at 8192 / 32768 / 65536 images of    \
+               100x100 / 28x28 / T=5 against 0.71 / 0.73 / 0.66 with the rule above; beyond 48 k images two images per workgroup   \
+               (0.70 against 0.70: a tie, kept for the short workgroups' tail) -- profiles/r06_read_c4_grid.txt */                 \
+            if (big && nthr == 1024) want_ = n_img >= 49152 ? n_img / 2 : res_;                                              \
+            if (grid_forced > 0) want_ = grid_forced;                                                                     \
+            cap_ = want_ <= res_ ? res_ : (want_ / res_) * res_;                                                          \
+        }                                                                                                                 \
+        hipLaunchKernelGGL((st_read_fwd_lean_kernel<NT_, VEC_>), dim3(st_grid(n_img, cap_)), th, lds_l, air_stream(stream), img, where, glimpse, \
+                           n, n_img, H, W, h, w, lin_step(w), lin_step(h)); } while (0)
+        if (big) { if (vec) AIR_READ_CASE(true, true); else AIR_READ_CASE(true, false); }
+        else { if (vec) AIR_READ_CASE(false, true); else AIR_READ_CASE(false, false); }
+#undef AIR_READ_CASE
+        AIR_LAUNCH_CHECK();
+        return AIR_OK;
+    }
+    const size_t lds = (size_t)f.lds_bytes;
     { int st_ = st_allow_lds(st_read_fwd_kernel, lds); if (st_) return st_; }
-    const int cap_f = n_img > 256 * 8 ? air_resident_grid(st_read_fwd_kernel, ST_THREADS, lds, 256 * 8) : 256 * 8;
-    hipLaunchKernelGGL(st_read_fwd_kernel, dim3(st_grid(n_img, cap_f)), dim3(ST_THREADS), lds, air_stream(stream), img, where,
-                       glimpse, n, n_img, H, W, h, w, lin_step(w), lin_step(h), vec4);
+    const int cap_f = f.resident_cap ? air_resident_grid(st_read_fwd_kernel, ST_THREADS, lds, 256 * 8) : f.fixed_cap;
+    hipLaunchKernelGGL(st_read_fwd_kernel, dim3(st_grid(n_img, cap_f)), dim3(f.threads), lds, air_stream(stream), img, where,
+                       glimpse, n, n_img, H, W, h, w, lin_step(w), lin_step(h), f.vec4);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }
 
-extern "C" int air_st_read_bwd(const float *img, const float *where, const float *dglimpse, float *dwhere,
-                               float *dimg, int n, int n_img, int H, int W, int h, int w, void *stream) {
+// WHICH form air_st_read_bwd runs (st_read_bwd_kernel's vec4 / per_glimpse arguments, its LDS and its items): consumed by the launch,
+// returned by air_st_read_bwd_form.
+static int st_read_bwd_form(const float *img, const float *where, const float *dglimpse, const float *dwhere, const float *dimg,
+                            int n, int n_img, int H, int W, int h, int w, AirWarpForm &f) {
+    f = AirWarpForm{};
     AIR_REQUIRE(img && where && dglimpse && dwhere, AIR_E_NULL);
     int st = st_check_dims(n, H, W, h, w);
     if (st) return st;
@@ -393,14 +425,31 @@ extern "C" int air_st_read_bwd(const float *img, const float *where, const float
     AIR_REQUIRE(!dimg || n_img == n, AIR_E_UNSUPPORTED);
     const size_t lds = carve_bytes(H * W, dimg ? H * W : 0, w, h);
     AIR_REQUIRE(lds <= ST_MAX_LDS, AIR_E_UNSUPPORTED);
-    const int vec4 = ((H * W) % 4 == 0) && air_aligned16(img);
+    f.kernel = AIR_WARP_READ_BWD;
+    f.threads = ST_THREADS; f.lds_bytes = (int)lds;
+    f.vec4 = ((H * W) % 4 == 0) && air_aligned16(img);
+    f.per_glimpse = (!dimg && n <= 2048 && n_img < n) ? 1 : 0;
+    f.items = f.per_glimpse ? n : n_img;
+    f.fixed_cap = 256 * 8; f.resident_cap = f.items > 256 * 8;
+    return AIR_OK;
+}
+extern "C" int air_st_read_bwd_form(const float *img, const float *where, const float *dglimpse, const float *dwhere,
+                                    const float *dimg, int n, int n_img, int H, int W, int h, int w, AirWarpForm *out) {
+    AIR_REQUIRE(out, AIR_E_NULL);
+    return st_read_bwd_form(img, where, dglimpse, dwhere, dimg, n, n_img, H, W, h, w, *out);
+}
+
+extern "C" int air_st_read_bwd(const float *img, const float *where, const float *dglimpse, float *dwhere,
+                               float *dimg, int n, int n_img, int H, int W, int h, int w, void *stream) {
+    AirWarpForm f;
+    int st = st_read_bwd_form(img, where, dglimpse, dwhere, dimg, n, n_img, H, W, h, w, f);
+    if (st) return st;
+    const size_t lds = (size_t)f.lds_bytes;
     { int st_ = st_allow_lds(st_read_bwd_kernel, lds); if (st_) return st_; }
-    const int per_glimpse = (!dimg && n <= 2048 && n_img < n) ? 1 : 0;
-    const int units_b = per_glimpse ? n : n_img;
-    const int cap_b = units_b > 256 * 8 ? air_resident_grid(st_read_bwd_kernel, ST_THREADS, lds, 256 * 8) : 256 * 8;
-    hipLaunchKernelGGL(st_read_bwd_kernel, dim3(st_grid(units_b, cap_b)), dim3(ST_THREADS), lds,
+    const int cap_b = f.resident_cap ? air_resident_grid(st_read_bwd_kernel, ST_THREADS, lds, 256 * 8) : f.fixed_cap;
+    hipLaunchKernelGGL(st_read_bwd_kernel, dim3(st_grid(f.items, cap_b)), dim3(f.threads), lds,
                        air_stream(stream), img, where, dglimpse, dwhere, dimg, n, n_img, H, W, h, w, lin_step(w),
-                       lin_step(h), vec4, per_glimpse);
+                       lin_step(h), f.vec4, f.per_glimpse);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

@@ -138,6 +138,51 @@ def canvas_unroll_bwd(glimpse, where, presence, obs, final_canvas, mult, std, lo
     return dg, dwhere
 
 
+# ---- which kernel a read / canvas launch runs (host-only queries: no launch, no device memory) ---------------------------------
+def _addr(x):
+    """an operand of a form query: a tensor, an integer ADDRESS (only its alignment and NULL-ness matter) or None"""
+    if x is None:
+        return None
+    return ctypes.c_void_p(x.data_ptr() if torch.is_tensor(x) else int(x))
+
+
+def _warp_form(name, *args):
+    f = _lib.AirWarpForm()
+    st = getattr(lib(), name)(*args, ctypes.byref(f))
+    d = f.as_dict()
+    d["kernel"] = _lib.WARP_KERNELS[d["kernel"]]
+    return st, d
+
+
+def st_read_form(img, where, glimpse, n, n_img, H, W, h, w):
+    """air_st_read_form: which kernel air_st_read_fwd runs -> (status, dict over the fields of AirWarpForm)"""
+    return _warp_form("air_st_read_form", _addr(img), _addr(where), _addr(glimpse), n, n_img, H, W, h, w)
+
+
+def st_read_bwd_form(img, where, dglimpse, dwhere, dimg, n, n_img, H, W, h, w):
+    """air_st_read_bwd_form -> (status, form)"""
+    return _warp_form("air_st_read_bwd_form", _addr(img), _addr(where), _addr(dglimpse), _addr(dwhere), _addr(dimg), n, n_img, H, W, h, w)
+
+
+def canvas_fwd_form(glimpse, where, obs, canvas_steps, final_canvas, rec_parts, n_bands, T, B, H, W, h, w):
+    """air_canvas_fwd_form -> (status, form): air_st_write_fwd (T = 1, n_bands = 1), air_canvas_unroll_fwd (n_bands = 0) and
+    air_canvas_unroll_fwd_banded (n_bands > 0)"""
+    return _warp_form("air_canvas_fwd_form", _addr(glimpse), _addr(where), _addr(obs), _addr(canvas_steps), _addr(final_canvas),
+                      _addr(rec_parts), n_bands, T, B, H, W, h, w)
+
+
+def canvas_bwd_form(glimpse, where, dcanvas, final_canvas, obs, dglimpse, dwhere, T, B, H, W, h, w):
+    """air_canvas_bwd_form -> (status, form): air_st_write_bwd (dcanvas given, T = 1) and air_canvas_unroll_bwd / _dpresence / _nvil"""
+    return _warp_form("air_canvas_bwd_form", _addr(glimpse), _addr(where), _addr(dcanvas), _addr(final_canvas), _addr(obs),
+                      _addr(dglimpse), _addr(dwhere), T, B, H, W, h, w)
+
+
+def canvas_fwd_bwd_form(glimpse, where, obs, canvas_steps, final_canvas, rec_parts, n_bands, dglimpse, dwhere, n_split, T, B, H, W, h, w):
+    """air_canvas_fwd_bwd_form -> (status, form) of air_canvas_unroll_fwd_bwd"""
+    return _warp_form("air_canvas_fwd_bwd_form", _addr(glimpse), _addr(where), _addr(obs), _addr(canvas_steps), _addr(final_canvas),
+                      _addr(rec_parts), n_bands, _addr(dglimpse), _addr(dwhere), n_split, T, B, H, W, h, w)
+
+
 # ---- dense ---------------------------------------------------------------------------------------------------------
 def gemm(A, B, ta=False, tb=False, bias=None, epilogue=EPI_NONE, aux=None, beta=0.0, out=None, colsum=False,
          use_workspace=True, precision=0, ws_bytes=None):

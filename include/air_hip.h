@@ -138,6 +138,54 @@ AIR_ENGINE_API int air_canvas_unroll_fwd_bwd(const float *glimpse, const float *
                               float *canvas_steps, float *final_canvas, float *rec_parts, int n_bands, float *dglimpse,
                               float *dwhere, int n_split, int T, int B, int H, int W, int h, int w, float mult, float std,
                               float loss_scale, void *stream);
+/* WHICH kernel a glimpse read / canvas launch runs, decided by one host function per entry and consumed by the launch code (the only
+ * statement of the rule).  The queries below return that decision without launching and without touching device memory: they read
+ * the shapes, the operands' ADDRESSES (only their 16-byte alignment and NULL-ness matter) and the per-call environment switches
+ * (AIR_CANVAS_BWD_IMG, AIR_CANVAS_GS_THREADS, AIR_CANVAS_IMG_MIN_UNITS), so they run on a machine without a GPU; the status is the
+ * one the launch itself would return before its first kernel.  Fields an entry does not use are 0.
+ *   kernel        AIR_WARP_READ_FWD       st_read_fwd_kernel                      (vec4)
+ *                 AIR_WARP_READ_FWD_LEAN  st_read_fwd_lean_kernel<NT, VEC>        (R: glimpses of an image staged side by side)
+ *                 AIR_WARP_READ_BWD       st_read_bwd_kernel                      (vec4, per_glimpse)
+ *                 AIR_WARP_WRITE_FWD      st_write_fwd_kernel                     (vec4_glimpse, NB, RB)
+ *                 AIR_WARP_WRITE_BWD      st_write_bwd_gs_kernel<RC, IM>          (vec4_glimpse, vec4_canvas)
+ *                 AIR_WARP_FUSED          canvas_fused_gs_kernel<SPLIT>           (vec4_glimpse, vec4_canvas, NB, RB, n_split; items =
+ *                                         forward workgroups + backward workgroups, n_fwd = the former)
+ *   items         work items the grid walks (images, glimpses, (image, band) or (t, b) units)
+ *   fixed_cap     the grid is `items` while items <= fixed_cap (0: no such cap)
+ *   resident_cap  1 when the launch asks the device for its resident workgroup count and caps the grid by it: items > fixed_cap, and
+ *                 the image-major backward always (fixed_cap 0); the fused launch has neither cap, its grid is exactly `items`      */
+enum { AIR_WARP_READ_FWD = 0, AIR_WARP_READ_FWD_LEAN = 1, AIR_WARP_READ_BWD = 2, AIR_WARP_WRITE_FWD = 3, AIR_WARP_WRITE_BWD = 4,
+       AIR_WARP_FUSED = 5 };
+typedef struct AirWarpForm {
+    int kernel;
+    int NT, VEC, R;
+    int RC, IM;
+    int SPLIT, n_split, n_fwd;
+    int threads, lds_bytes;
+    int vec4, vec4_glimpse, vec4_canvas;
+    int per_glimpse;
+    int NB, RB;
+    int items, fixed_cap, resident_cap;
+} AirWarpForm;
+AIR_ENGINE_API int air_st_read_form(const float *img, const float *where, const float *glimpse, int n, int n_img, int H, int W, int h,
+                                    int w, AirWarpForm *out);
+AIR_ENGINE_API int air_st_read_bwd_form(const float *img, const float *where, const float *dglimpse, const float *dwhere,
+                                        const float *dimg, int n, int n_img, int H, int W, int h, int w, AirWarpForm *out);
+/* air_st_write_fwd (T = 1, n_bands = 1, canvas_steps = rec_parts = NULL, B = n), air_canvas_unroll_fwd (n_bands = 0: the entry's own
+ * band rule) and air_canvas_unroll_fwd_banded (n_bands > 0) */
+AIR_ENGINE_API int air_canvas_fwd_form(const float *glimpse, const float *where, const float *obs, const float *canvas_steps,
+                                       const float *final_canvas, const float *rec_parts, int n_bands, int T, int B, int H, int W,
+                                       int h, int w, AirWarpForm *out);
+/* air_st_write_bwd (dcanvas given, T = 1, B = n) and air_canvas_unroll_bwd / _dpresence / _nvil (dcanvas = NULL; final_canvas = NULL:
+ * the recompute form) */
+AIR_ENGINE_API int air_canvas_bwd_form(const float *glimpse, const float *where, const float *dcanvas, const float *final_canvas,
+                                       const float *obs, const float *dglimpse, const float *dwhere, int T, int B, int H, int W,
+                                       int h, int w, AirWarpForm *out);
+AIR_ENGINE_API int air_canvas_fwd_bwd_form(const float *glimpse, const float *where, const float *obs, const float *canvas_steps,
+                                           const float *final_canvas, const float *rec_parts, int n_bands, const float *dglimpse,
+                                           const float *dwhere, int n_split, int T, int B, int H, int W, int h, int w,
+                                           AirWarpForm *out);
+
 /* ---- dense layers -------------------------------------------------------------------------------------------
  * Replaces the TF MatMul/BiasAdd/Elu nodes under snt.Linear (neural.py:42-60) and snt.LSTM (mnist_model.py:35).   */
 
