@@ -256,6 +256,14 @@ SIGNATURES = {
                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, P, c_size_t, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                  P, P, P, P]),
     "air_track_fill": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "air_track_smooth_stream_state_bytes": (c_size_t, [c_int, c_int]),
+    "air_track_stash": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "air_track_smooth_stream": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, P, c_size_t, P, P, P, P,
+                                        P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "air_track_smooth_tail": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, P, P, P, P, P, P, P, P,
+                                      P]),
+    "air_track_fill_stream": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
     "air_score_contingency": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "air_score_match": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "air_score_reduce": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, P]),

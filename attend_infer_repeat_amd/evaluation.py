@@ -573,12 +573,15 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
 
 
 def make_track_stream_logger(air, data, num_batches, name, chunk_frames, batch_size=None, writer=None, tau=0.5, measure_time=True,
-                             **stream_args):
+                             smooth=None, **stream_args):
     """make_track_score_logger's counterpart for STREAMS (air.track_stream, track.StreamTracker): the sequences of `data` (imgs
     [N, F, H, W], boxes [N, F, G, 4]) are fed in chunks of `chunk_frames` frames, the last chunk ragged (`valid`), every batch of
     `batch_size` sequences as a stream of its own (reset between batches), each chunk scored against its rows of the ground truth.
     Prints / writes the tracker's summary() summed over the batches -- the counts add up; the rates come from track.mot_summary on the
-    sums -- and the tracks issued.  `stream_args` are AIRonMNIST.stream_tracker's."""
+    sums -- and the tracks issued.  `stream_args` are AIRonMNIST.stream_tracker's.  smooth=True | dict(lag=, horizon=, ...): the stream
+    goes through a trajectory.StreamSmoother (air.stream_smoother) and the EMITTED frames are scored instead -- fixed-lag smoothed and
+    gap-filled, `lag` frames late, each against the ground truth of its own global frame (emit_frame is read back per chunk); the last
+    `lag` frames of a sequence are never emitted and are not scored.  Logged as <name>_track_stream_smooth."""
     import numpy as np
     import torch
     from .track import COUNTS, mot_summary
@@ -597,14 +600,24 @@ def make_track_stream_logger(air, data, num_batches, name, chunk_frames, batch_s
         for i in range(n):
             sl = slice(i * S, (i + 1) * S)
             imgs, boxes = np.asarray(data["imgs"][sl], np.float32), np.asarray(data["boxes"][sl], np.float32)
-            tracker = air.stream_tracker(S, C, **stream_args)
-            tracker.score_reset()
+            smoother = None if smooth is None else air.stream_smoother(S, C, smooth, **stream_args)
+            tracker = air.stream_tracker(S, C, **stream_args) if smoother is None else smoother.tracker
+            if smoother is None:
+                tracker.score_reset()
             for at in range(0, F, C):
                 v = min(C, F - at)
                 frames, gt = np.zeros((S, C) + imgs.shape[2:], np.float32), np.zeros((S, C, G, 4), np.float32)
                 frames[:, :v], gt[:, :v] = imgs[:, at:at + v], boxes[:, at:at + v]
-                air.track_stream(torch.from_numpy(frames).to(dev), np.full(S, v, np.int64), reset=at == 0, **stream_args)
-                scores = tracker.score(torch.from_numpy(gt), tau)
+                out = air.track_stream(torch.from_numpy(frames).to(dev), np.full(S, v, np.int64), reset=at == 0, smooth=smooth,
+                                       **stream_args)
+                if smoother is None:
+                    scores = tracker.score(torch.from_numpy(gt), tau)
+                else:                                              # the ground truth of the frames this push emitted
+                    emit = out["emit_frame"].cpu().numpy()
+                    gt[:] = 0
+                    for s_, e_ in zip(*np.nonzero(emit >= 0)):
+                        gt[s_, e_] = boxes[s_, emit[s_, e_]]
+                    scores = smoother.score(torch.from_numpy(gt), tau)
             tracker.synchronize()
             totals += scores["seq_counts"].sum(0, dtype=torch.int64).cpu().numpy()
             sum_iou += float(scores["seq_iou"].sum().item())
@@ -618,9 +631,11 @@ def make_track_stream_logger(air, data, num_batches, name, chunk_frames, batch_s
             msg += ', eval time = {:.4}s'.format(t)
         print(msg)
         if write and writer is not None:
-            rec = dict(step=int(itr), data=name + "_track_stream", n_frames=F, chunk_frames=C, tau=float(tau), iou_gate=tracker.iou_gate,
-                       appearance_weight=tracker.appearance_weight, birth_score=tracker.birth_score, max_age=tracker.max_age,
-                       matching=tracker.matching, **acc)
+            rec = dict(step=int(itr), data=name + ("_track_stream" if smooth is None else "_track_stream_smooth"), n_frames=F,
+                       chunk_frames=C, tau=float(tau), iou_gate=tracker.iou_gate, appearance_weight=tracker.appearance_weight,
+                       birth_score=tracker.birth_score, max_age=tracker.max_age, matching=tracker.matching, **acc)
+            if smooth is not None:
+                rec.update(lag=smoother.lag, horizon=smoother.horizon)
             writer.write(json.dumps(rec) + "\n"); writer.flush()
         return acc
     return logger

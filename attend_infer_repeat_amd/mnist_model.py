@@ -512,17 +512,39 @@ class AIRonMNIST(AIRModel):
             return stacks.captured(stack)
         return self._cache("trackers").get(key, build)[-1]
 
-    def track_stream(self, frames, valid=None, reset=False, **stream_args):
+    def stream_smoother(self, n_sequences, chunk_frames, smooth=True, **stream_args):
+        """the trajectory.StreamSmoother behind `track_stream(smooth=)`: fixed-lag smoothed, gap-filled rows `lag` frames late and a
+        forecast per chunk.  smooth: True or dict(lag=, horizon=, process_noise=, measurement_noise=, velocity_var=) (lag None:
+        max_age; the defaults are provisional); `stream_args` are `stream_tracker`'s.  Last in a cached stack of its own
+        (stacks.stream_smoother_key) whose StreamTracker it is bound to: another stream than that of `stream_tracker` with the same
+        arguments.  Built and captured on first use; counts against MAX_TRACKERS."""
+        key = stacks.stream_smoother_key(stacks.require_engine(self, "track_stream"), n_sequences, chunk_frames, smooth, **stream_args)
+
+        def build():
+            from .track import StreamTracker
+            from .trajectory import StreamSmoother
+            stack = self._own_stack(key.S * key.F, key.stack, key.F)
+            stack.append(StreamTracker(stack[-1], key.F, matching=key.matching, **dict(key.assoc)))
+            stack.append(StreamSmoother(stack[-1], **dict(key.smooth)))
+            return stacks.captured(stack)
+        return self._cache("trackers").get(key, build)[-1]
+
+    def track_stream(self, frames, valid=None, reset=False, smooth=None, **stream_args):
         """The next chunk of a stream: frames [S, F, H, W] parsed as `track` parses them and associated with the tracks of the chunks
         before (track.StreamTracker.push lists the returned device tensors; prev_frame and the tracks' first / last are global frame
         indices).  valid [S]: the frames each sequence has in this chunk (None: all F).  reset=True restarts every sequence first, a
         list of sequence indices those (a slot reused for a new video).  `stream_args` are `stream_tracker`'s; the stream is that
         tracker's: the same arguments continue it.  The training engine's parameters are read, nothing of it is written; `self.obs`
-        and the parsers of `parse` are not touched."""
+        and the parsers of `parse` are not touched.  smooth=None is exactly the call without the argument; smooth=True | dict
+        (`stream_smoother`) pushes through a trajectory.StreamSmoother -- a stream of its own -- and adds the emitted table sm_*,
+        emit_frame, num_emitted and, with a horizon, fc_* and frames_pred (trajectory.StreamSmoother.result)."""
         frames = torch.as_tensor(frames)
         if frames.dim() != 4:
             raise ValueError("track_stream: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
-        t = self.stream_tracker(frames.shape[0], frames.shape[1], **stream_args)
+        if smooth is None:
+            t = self.stream_tracker(frames.shape[0], frames.shape[1], **stream_args)
+        else:
+            t = self.stream_smoother(frames.shape[0], frames.shape[1], smooth, **stream_args)
         if reset is not False and reset is not None:
             t.reset(None if reset is True else reset)
         self._sync_engine_switches()

@@ -141,7 +141,11 @@ def main(argv=None):
                     help="with --track-eval: also run the same sequences through a STREAM in chunks of CHUNK frames (the last chunk "
                          "ragged; AIRonMNIST.track_stream, track.StreamTracker: the track table carried on the device between the chunks) "
                          "and log its summary() as <name>_track_stream; --track-matching and --track-temporal apply, --track-smooth and "
-                         "--track-identity do not (out of scope on a stream)")
+                         "--track-identity do not (--track-stream-smooth is the stream's smoother; IDF1 is out of scope on a stream)")
+    ap.add_argument("--track-stream-smooth", type=str, default=None, metavar="LAG[,HZ]",
+                    help="with --track-stream: also run the stream through a trajectory.StreamSmoother with lag LAG (max_age..16) and "
+                         "horizon HZ (0..16, default 0) and log the score of the EMITTED frames (fixed-lag smoothed, gap-filled, LAG "
+                         "frames late) as <name>_track_stream_smooth; the lag and the noise terms are provisional")
     ap.add_argument("--track-predict", type=int, default=None, metavar="HZ",
                     help="with --track-eval: also extrapolate the live tracks HZ frames (1..16) past every sequence and render the "
                          "predicted frames (AIRonMNIST.predict_frames' forecast table; implies --track-smooth)")
@@ -226,6 +230,17 @@ def main(argv=None):
             ap.error("--track-stream goes with --track-eval")
         if not 1 <= args.track_stream <= 32767 // 3:
             ap.error("--track-stream needs 1 <= CHUNK <= %d (CHUNK * max_steps must fit int16)" % (32767 // 3))
+    stream_smooth = None
+    if args.track_stream_smooth is not None:
+        if args.track_stream is None:
+            ap.error("--track-stream-smooth goes with --track-stream")
+        try:
+            lag_hz = [int(v) for v in args.track_stream_smooth.split(",")]
+        except ValueError:
+            lag_hz = []
+        if len(lag_hz) not in (1, 2) or not 0 <= lag_hz[0] <= 16 or not 0 <= (lag_hz + [0])[1] <= 16:
+            ap.error("--track-stream-smooth needs LAG[,HZ] with LAG and HZ within 0..16, got %r" % args.track_stream_smooth)
+        stream_smooth = dict(lag=lag_hz[0], horizon=(lag_hz + [0])[1])
     track_smooth = None
     if args.track_smooth is not None or args.track_predict is not None:
         if track_eval is None:
@@ -403,6 +418,11 @@ def main(argv=None):
             from attend_infer_repeat_amd.evaluation import make_track_stream_logger
             stream_log = make_track_stream_logger(air, seq_data, args.eval_batches, 'test', args.track_stream, sequences_per_batch, writer,
                                                   temporal=track_temporal, matching=args.track_matching, **refine_kw)
+            if stream_smooth is not None:
+                plain_log, smooth_log = stream_log, make_track_stream_logger(
+                    air, seq_data, args.eval_batches, 'test', args.track_stream, sequences_per_batch, writer, smooth=stream_smooth,
+                    temporal=track_temporal, matching=args.track_matching, **refine_kw)
+                stream_log = lambda *a, **kw: (plain_log(*a, **kw), smooth_log(*a, **kw))[0]
 
         def log(train_itr):                               # noqa: F811
             out = before_track_log(train_itr)

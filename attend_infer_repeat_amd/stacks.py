@@ -9,6 +9,7 @@ StackSpec = namedtuple("StackSpec", "refine lr prune propose temporal")     # in
 #                                                                             candidates | None, (P, rounds) | None, (P, rounds) | None
 TrackKey = namedtuple("TrackKey", "S F assoc stack smooth matching device")   # assoc, smooth: sorted (name, value) pairs; smooth | None
 StreamKey = namedtuple("StreamKey", "S F assoc stack matching device stream")  # a track.StreamTracker's: stream is True (a key of its own)
+StreamSmoothKey = namedtuple("StreamSmoothKey", "S F assoc stack matching device stream smooth")      # ... with a trajectory.StreamSmoother
 
 
 def require_engine(air, who):
@@ -98,6 +99,32 @@ def stream_key(eng, n_sequences, chunk_frames, iou_gate=None, appearance_weight=
     k = track_key(eng, n_sequences, chunk_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose,
                   temporal, None, matching)
     return StreamKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, True)
+
+
+def stream_smooth_spec(smooth):
+    """smooth=True | dict(lag=, horizon=, process_noise=, measurement_noise=, velocity_var=) -> the full dict (lag None: max_age)"""
+    from .trajectory import DEFAULTS
+    spec = dict(DEFAULTS, lag=None, horizon=0)
+    if smooth is not True:
+        if not isinstance(smooth, dict) or set(smooth) - set(spec):
+            raise ValueError("smooth: True or a dict with keys among %s, got %r" % (sorted(spec), smooth))
+        spec.update(smooth)
+    try:
+        spec["process_noise"] = tuple(float(v) for v in spec["process_noise"])
+    except TypeError:
+        raise ValueError("smooth: process_noise must be two numbers (q_shift, q_scale), got %r" % (spec["process_noise"],))
+    return spec
+
+
+def stream_smoother_key(eng, n_sequences, chunk_frames, smooth=True, **stream_args):
+    """The key of a stream tracker with a trajectory.StreamSmoother behind it, checked by trajectory.check_stream_arguments before
+    anything is built: `stream_key`'s fields and the smoother's arguments -- a key of its own, never that of the stream tracker with
+    the same arguments (the two are different streams)."""
+    from .trajectory import check_stream_arguments
+    k = stream_key(eng, n_sequences, chunk_frames, **stream_args)
+    spec = stream_smooth_spec(smooth)
+    L = check_stream_arguments(eng.cfg.max_steps, k.F, k.S * k.F, dict(k.assoc)["max_age"], **spec)[4]
+    return StreamSmoothKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, True, tuple(sorted(dict(spec, lag=L).items())))
 
 
 def stage_classes():

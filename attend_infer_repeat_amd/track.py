@@ -85,8 +85,8 @@ per slot live, id, age, length, gaps, first, the last sighting's global frame an
 tracks retired in a chunk come as a list (ascending retirement frame, then slot), the live ones stay in the state.  A stream issues
 the ids 0..32766 (track_owner is int16); a birth beyond is OVERFLOW.  The metric continues across chunks: map[g], tracked[g],
 present[g], the counters and sum_iou are carried, seq_counts and seq_iou are cumulative.  Out of scope on a stream: IDF1 (its overlap
-table is indexed by global id: 1 MB per sequence at 32767 ids), trajectory.TrajectorySmoother (the backward pass needs the future), ids
-beyond 32766 without `reset`, more than 32 live tracks.  `reference_associate_stream` / `reference_score_stream` restate a chunk in numpy
+table is indexed by global id: 1 MB per sequence at 32767 ids), ids beyond 32766 without `reset`, more than 32 live tracks.  Trajectories
+on a stream are trajectory.StreamSmoother's: fixed-lag smoothed rows `lag` frames late and a forecast per chunk.  `reference_associate_stream` / `reference_score_stream` restate a chunk in numpy
 with the per-frame code of the one-shot references.
 
 The defaults of iou_gate, appearance_weight, birth_score and max_age are provisional: UNMEASURED on a trained model (profiles/track.txt
@@ -921,8 +921,8 @@ class StreamTracker(BoundStage):
 
     A push MUTATES the state, captured or not: pushing a chunk twice continues the stream with a repeated chunk, it does not repeat the
     call -- `state_dict()` before and `load_state_dict()` after is how a chunk is re-run.  Ids: 0..32766 per sequence until `reset`;
-    a birth beyond is OVERFLOW.  Out of scope on a stream: IDF1 (its overlap table is indexed by global id), trajectory smoothing (the
-    backward pass needs the future), more than 32 live tracks."""
+    a birth beyond is OVERFLOW.  Out of scope on a stream: IDF1 (its overlap table is indexed by global id), more than 32 live tracks.
+    Trajectories: a trajectory.StreamSmoother bound to this tracker (fixed-lag smoothing, `lag` frames late; the forecast at once)."""
     ACCEPTS = SequenceTracker.ACCEPTS
     REFUSALS = SequenceTracker.REFUSALS
 

@@ -42,6 +42,32 @@ air_track_score with T := C on the completed table (one object cannot carry both
 The defaults of process_noise, measurement_noise and velocity_var are provisional: UNMEASURED on a trained model (profiles/trajectory.txt
 says what was measured).  Out of scope: smoothed covariances, feeding the smoothed rows back into the association, rates on scales in
 the forecast, a learned motion prior, particle providers (refused by the tracker, in its wording).
+
+STREAMS (`StreamSmoother` behind a track.StreamTracker; air_track_smooth_stream, `reference_smooth_stream` restates a chunk in numpy).
+The rule above, unchanged, with a LAG L, max_age <= L <= MAX_LAG = 16: the forward filter is causal, and the backward pass over a
+bounded window is FIXED-LAG smoothing -- the estimate of global frame g that uses the sightings up to g + L is final once frame g + L
+has been seen, and it is exactly what the rule gives on the sequence truncated after frame g + L.  L >= max_age makes "does the track
+span g" final by then: a track that coasts at g without a sighting in g + 1 .. g + L is retired.  A push that takes frames_seen[s]
+from a to b:
+  emitted   the global frames max(0, a - L) <= g < max(0, b - L), once each, ascending, at most valid[s] of them: the tracks with a
+            sighting at or before g and a sighting in g .. g + L in ascending id, the backward pass run from the last sighting at or
+            before g + L down to g; src_frame is a GLOBAL frame.  TRUNCATION IDENTITY: bit for bit column g of `reference_smooth` on
+            the first g + L + 1 frames of the concatenation of the sequence's valid frames -- hence CHUNK INVARIANCE: any chunking,
+            ragged valid and valid = 0 included, gives frame g the same bits;
+  forecast  every push, no lag: bit for bit the forecast table of `reference_smooth` on the first b frames (the live tracks from the
+            filtered state at `last`, m = b - 1 - last + k); valid = 0 gives it again, a sequence that has seen nothing an empty one;
+  tail      on request and read-only: the frames max(0, b - L) .. b - 1, not final yet, smoothed with what is known -- the last
+            columns of `reference_smooth` on the first b frames; at the end of a video the flush; with L >= the video's length
+            emitted plus tail is the one-shot completed table;
+  fill      what / glimpse / score of every emitted, tail and forecast row are bit copies of the source sighting's provider rows,
+            which may lie in an earlier chunk: the provider's rows of the last D frames are carried.
+The carried state (`new_smooth_state`; include/air_hip.h states the layout) is the smoother's own: frames_seen and the next frame to
+emit per sequence; a table of at most 32 tracks derived from the chunk's track_id / num_objects / valid alone, which mirrors the
+tracker's births and retirements with the same max_age (the tracker's state is only read); and rings over the last D global frames of
+what the backward pass reads per (table row, frame) and of the provider's rows.  D = F + L + max_age (`ring_depth`): a push writes the
+frames a .. a + F - 1 and emits from a - L on, and the source of a FILLED row there lies up to max_age frames before it; the reference
+tags every ring entry with its frame and asserts the tag on every read.  The default lag (max_age) is provisional like the noise
+terms.  Out of scope on a stream: smoothed covariances, feeding smoothed rows back into the association, IDF1.
 """
 import ctypes
 from collections import OrderedDict
@@ -50,8 +76,10 @@ from typing import Dict
 from .stage import BoundStage, ReadOut, compacted_rows
 from .track import MAX_IDS, MAX_SLOTS, IdentityScores
 from .track import check_arguments as check_track_arguments
+from .track import check_frames_seen, check_valid
 
 MAX_HORIZON = 16
+MAX_LAG = 16                                                       # a stream smoother's lag L: max_age <= L <= MAX_LAG
 ABSENT, OBSERVED, FILLED, FORECAST = range(4)
 STATES = ("absent", "observed", "filled", "forecast")
 DEFAULTS = dict(process_noise=(1e-4, 1e-4), measurement_noise=4e-4, velocity_var=0.04)
@@ -83,44 +111,86 @@ def check_arguments(max_steps, n_frames, n_rows=None, max_age=1, horizon=0, proc
     return T, F, S, completed_rows(T, max_age), int(horizon), q, r, vv
 
 
+def _filter_start(z, r, vv):
+    """start: the filtered state (x, v, Pxx, Pxv, Pvv) at the first sighting z (float64 [4], None: zeros)"""
+    import numpy as np
+    return (np.zeros(4) if z is None else z.copy(), np.zeros(4), np.full(4, r), np.zeros(4), np.full(4, vv))
+
+
+def _filter_step(filt, z, q, r):
+    """predict, then update with the sighting z (None: a coasted frame keeps the predicted state).  Returns (predicted, filtered)"""
+    q2, q4 = 0.5 * q, 0.25 * q
+    x, v, Pxx, Pxv, Pvv = filt
+    a, b = Pxx + Pxv, Pxv + Pvv
+    xp, vp = x + v, v
+    Pxxp, Pxvp, Pvvp = (a + b) + q4, b + q2, Pvv + q
+    pred = (xp, vp, Pxxp, Pxvp, Pvvp)
+    if z is None:
+        return pred, pred
+    s = Pxxp + r
+    kx, kv = Pxxp / s, Pxvp / s
+    e = z - xp
+    return pred, (xp + kx * e, vp + kv * e, Pxxp - kx * Pxxp, Pxvp - kx * Pxvp, Pvvp - kv * Pxvp)
+
+
+def _back_step(filt, pred_next, xs_next, vs_next):
+    """back: (xs, vs) of frame f from its filtered state, the predicted state of frame f + 1 and (xs, vs) of frame f + 1"""
+    fx, fv, Pxx, Pxv, Pvv = filt
+    xp, vp, Pxxp, Pxvp, Pvvp = pred_next
+    g00, g01, g10, g11 = Pxx + Pxv, Pxv, Pxv + Pvv, Pvv
+    det = Pxxp * Pvvp - Pxvp * Pxvp
+    C00, C01 = (g00 * Pvvp - g01 * Pxvp) / det, (g01 * Pxxp - g00 * Pxvp) / det
+    C10, C11 = (g10 * Pvvp - g11 * Pxvp) / det, (g11 * Pxxp - g10 * Pxvp) / det
+    dx, dv = xs_next - xp, vs_next - vp
+    return fx + (C00 * dx + C01 * dv), fv + (C10 * dx + C11 * dv)
+
+
 def _smooth_track(z_of, first, last, q, r, vv):
     """the filter and the backward pass of one track: z_of(f) -> float64 [4] or None.  Returns xs, vs {f: [4]}, the filtered (x, v)
     at `last`, and the (frame, value) of every sighting"""
-    import numpy as np
-    q2, q4 = 0.5 * q, 0.25 * q
     filt, pred = {}, {}
-    x = v = Pxx = Pxv = Pvv = None
     for f in range(first, last + 1):
-        z = z_of(f)
         if f == first:
-            x = np.zeros(4) if z is None else z.copy()
-            v, Pxx, Pxv, Pvv = np.zeros(4), np.full(4, r), np.zeros(4), np.full(4, vv)
+            filt[f] = _filter_start(z_of(f), r, vv)
         else:
-            a, b = Pxx + Pxv, Pxv + Pvv
-            xp, vp = x + v, v
-            Pxxp, Pxvp, Pvvp = (a + b) + q4, b + q2, Pvv + q
-            pred[f] = (xp, vp, Pxxp, Pxvp, Pvvp)
-            if z is not None:
-                s = Pxxp + r
-                kx, kv = Pxxp / s, Pxvp / s
-                e = z - xp
-                x, v = xp + kx * e, vp + kv * e
-                Pxx, Pxv, Pvv = Pxxp - kx * Pxxp, Pxvp - kx * Pxvp, Pvvp - kv * Pxvp
-            else:
-                x, v, Pxx, Pxv, Pvv = xp, vp, Pxxp, Pxvp, Pvvp
-        filt[f] = (x, v, Pxx, Pxv, Pvv)
+            pred[f], filt[f] = _filter_step(filt[f - 1], z_of(f), q, r)
+    x, v = filt[last][:2]
     xs, vs = {last: x}, {last: v}
     for f in range(last - 1, first - 1, -1):
-        fx, fv, Pxx, Pxv, Pvv = filt[f]
-        xp, vp, Pxxp, Pxvp, Pvvp = pred[f + 1]
-        g00, g01, g10, g11 = Pxx + Pxv, Pxv, Pxv + Pvv, Pvv
-        det = Pxxp * Pvvp - Pxvp * Pxvp
-        C00, C01 = (g00 * Pvvp - g01 * Pxvp) / det, (g01 * Pxxp - g00 * Pxvp) / det
-        C10, C11 = (g10 * Pvvp - g11 * Pxvp) / det, (g11 * Pxxp - g10 * Pxvp) / det
-        dx, dv = xs[f + 1] - xp, vs[f + 1] - vp
-        xs[f] = fx + (C00 * dx + C01 * dv)
-        vs[f] = fv + (C10 * dx + C11 * dv)
+        xs[f], vs[f] = _back_step(filt[f], pred[f + 1], xs[f + 1], vs[f + 1])
     return xs, vs, (x, v)
+
+
+def _new_table(pre, C, cols):
+    """an ABSENT table of C rows and `cols` columns under the prefix `pre`"""
+    import numpy as np
+    return {pre + "where": np.zeros((C, cols, 4), np.float32), pre + "boxes": np.zeros((C, cols, 4), np.float32),
+            pre + "id": np.full((C, cols), -1, np.int32), pre + "state": np.zeros((C, cols), np.int8),
+            pre + "src_frame": np.full((C, cols), -1, np.int32), pre + "src_slot": np.full((C, cols), -1, np.int32),
+            pre + "velocity": np.zeros((C, cols, 2), np.float32), pre + "count": np.zeros(cols, np.int32)}
+
+
+def _velocity(v, H, W):
+    """pixels per frame of the box centre from the rates of tx and ty, float64 rounded once"""
+    import numpy as np
+    half = np.float64(0.5)
+    return np.array([(np.float64(W) * v[1]) * half, (np.float64(H) * v[3]) * half]).astype(np.float32)
+
+
+def _put(out, img_size, pre, row, col, w32, vel, tid, state, src):
+    """one row of a table"""
+    from .tile import scene_boxes
+    out[pre + "where"][row, col], out[pre + "boxes"][row, col] = w32, scene_boxes(w32, img_size)
+    out[pre + "velocity"][row, col], out[pre + "id"][row, col], out[pre + "state"][row, col] = vel, tid, state
+    out[pre + "src_frame"][row, col], out[pre + "src_slot"][row, col] = src
+    out[pre + "count"][col] = max(out[pre + "count"][col], row + 1)
+
+
+def _forecast_where(xl, vl, m):
+    """the forecast m frames past the last sighting: shifts extrapolated from the filtered (x, v) at `last`, scales held"""
+    import numpy as np
+    m = np.float64(m)
+    return np.array([xl[0], xl[1] + m * vl[1], xl[2], xl[3] + m * vl[3]]).astype(np.float32)
 
 
 def reference_smooth(where, num_objects, track_id, num_tracks, track_first, track_last, n_frames, max_age, img_size, horizon=0,
@@ -144,19 +214,10 @@ def reference_smooth(where, num_objects, track_id, num_tracks, track_first, trac
     q = np.array([q_scale, q_shift, q_scale, q_shift], np.float64)
     out = {}
     for pre, cols in (("sm_", R), ("fc_", N)):
-        out.update({pre + "where": np.zeros((C, cols, 4), np.float32), pre + "boxes": np.zeros((C, cols, 4), np.float32),
-                    pre + "id": np.full((C, cols), -1, np.int32), pre + "state": np.zeros((C, cols), np.int8),
-                    pre + "src_frame": np.full((C, cols), -1, np.int32), pre + "src_slot": np.full((C, cols), -1, np.int32),
-                    pre + "velocity": np.zeros((C, cols, 2), np.float32), pre + "count": np.zeros(cols, np.int32)})
+        out.update(_new_table(pre, C, cols))
     out["sm_counts"] = np.zeros((S, 3), np.int32)
-    half = np.float64(0.5)
-    velocity = lambda v: np.array([(np.float64(W) * v[1]) * half, (np.float64(H) * v[3]) * half]).astype(np.float32)
-
-    def put(pre, row, col, w32, vel, tid, state, src):
-        out[pre + "where"][row, col], out[pre + "boxes"][row, col] = w32, scene_boxes(w32, (H, W))
-        out[pre + "velocity"][row, col], out[pre + "id"][row, col], out[pre + "state"][row, col] = vel, tid, state
-        out[pre + "src_frame"][row, col], out[pre + "src_slot"][row, col] = src
-        out[pre + "count"][col] = max(out[pre + "count"][col], row + 1)
+    velocity = lambda v: _velocity(v, H, W)
+    put = lambda *a: _put(out, (H, W), *a)
 
     with np.errstate(all="ignore"):
         for s in range(S):
@@ -188,9 +249,7 @@ def reference_smooth(where, num_objects, track_id, num_tracks, track_first, trac
                     if row >= C:
                         continue
                     for k in range(1, Hz + 1):
-                        m = np.float64(F - 1 - la + k)
-                        w32 = np.array([xl[0], xl[1] + m * vl[1], xl[2], xl[3] + m * vl[3]]).astype(np.float32)
-                        put("fc_", row, s * Hz + (k - 1), w32, velocity(vl), i, FORECAST, src)
+                        put("fc_", row, s * Hz + (k - 1), _forecast_where(xl, vl, F - 1 - la + k), velocity(vl), i, FORECAST, src)
             out["sm_counts"][s, ABSENT] = C * F - out["sm_counts"][s, OBSERVED] - out["sm_counts"][s, FILLED]
     if what is not None:
         rows = {"what": np.asarray(what, np.float32), "glimpse": np.asarray(glimpse, np.float32).reshape(T, R, -1),
@@ -204,6 +263,312 @@ def reference_smooth(where, num_objects, track_id, num_tracks, track_first, trac
                         if out[pre + "state"][c, n] != ABSENT and 0 <= sf < F and 0 <= sj < T:
                             dst[c, n] = src_rows[sj, (n // per_seq) * F + sf]
                 out[pre + k] = dst
+    return out
+
+
+# ---- streams: fixed-lag smoothing and forecasts per chunk (the module text and include/air_hip.h state the rule and the layout) --------
+SM_LIVE, SM_ID, SM_AGE, SM_FIRST, SM_LAST_FRAME, SM_LAST_SLOT = range(6)
+SM_FIELDS = ("live", "id", "age", "first", "last_frame", "last_slot")
+SM_EMPTY = (0, -1, 0, -1, -1, -1)                                  # a table row that is not live, field by field
+RING_ID, RING_STATE, RING_SRC_FRAME, RING_SRC_SLOT = range(4)
+RING_EMPTY = (-1, ABSENT, -1, -1)                                  # a table row that was not live in that frame
+WS_DOUBLES = 28                                                    # TRAJ_WS_DOUBLES: 4 x (x, v, x-, v-), 2 noise classes x (P, P-)
+SMOOTH_STATE_KEYS = ("seq", "slots", "ring_i", "ring")             # the packed device state, in this order
+ROW_RING_KEYS = ("what", "glimpse", "score")                       # the ring of provider rows (three buffers of their own)
+_CLASS = (1, 0, 1, 0)                                              # [sx, tx, sy, ty]: noise class 0 the shifts, 1 the scales
+
+
+def ring_depth(chunk_frames, lag, max_age) -> int:
+    """D = F + L + max_age frames.  A push that starts at frames_seen = a writes the frames a .. a + F - 1 and emits from a - L on;
+    the FILLED row of a track that coasts there has its source sighting up to max_age frames earlier: a - L - max_age is the oldest
+    frame read, a + F - 1 the newest written"""
+    return int(chunk_frames) + int(lag) + int(max_age)
+
+
+def check_stream_arguments(max_steps, chunk_frames, n_rows=None, max_age=1, lag=None, horizon=0,
+                           process_noise=DEFAULTS["process_noise"], measurement_noise=DEFAULTS["measurement_noise"],
+                           velocity_var=DEFAULTS["velocity_var"]):
+    """Refuse what air_track_smooth_stream refuses (pure host code).  lag=None: max_age.  Returns (T, F, S, C, L, Hz, D, (q_shift,
+    q_scale), r, velocity_var)."""
+    T, F, S, C, Hz, q, r, vv = check_arguments(max_steps, chunk_frames, n_rows, max_age, horizon, process_noise, measurement_noise,
+                                               velocity_var)
+    lag = int(max_age) if lag is None else lag
+    if isinstance(lag, bool) or int(lag) != lag or not int(max_age) <= int(lag) <= MAX_LAG:
+        raise ValueError("lag must be an integer within max_age..%d = %d..%d (a track that coasts over a frame must be retired, or "
+                         "seen again, by the time the frame is emitted), got %r" % (MAX_LAG, int(max_age), MAX_LAG, lag))
+    return T, F, S, C, int(lag), Hz, ring_depth(F, lag, max_age), q, r, vv
+
+
+def new_smooth_state(n_sequences, chunk_frames, lag, max_age, max_steps, what_size, glimpse_size, depth=None):
+    """the smoother state of a stream that has seen nothing, as numpy arrays.  The packed device state (SMOOTH_STATE_KEYS): seq [S, 2]
+    int32 {frames_seen, next frame to emit}, slots [S, 6, 32] int32 (SM_FIELDS), ring_i [S, D, 4, 32] int32 {id, state, src_frame,
+    src_slot} and ring [S, D, 28, 32] float64 over the frames g at g mod D.  The ring of provider rows (ROW_RING_KEYS): what
+    [S, D, T, A], glimpse [S, D, T, G], score [S, D, T] fp32.  Host bookkeeping only: ring_frame, rows_frame [S, D] int64, the frame a
+    ring entry holds (-1: none), which the reference asserts on every read.  depth: D, `ring_depth` if None."""
+    import numpy as np
+    S, T, A, G = int(n_sequences), int(max_steps), int(what_size), int(glimpse_size)
+    D = ring_depth(chunk_frames, lag, max_age) if depth is None else int(depth)
+    slots, ring_i = np.empty((S, 6, MAX_SLOTS), np.int32), np.empty((S, D, 4, MAX_SLOTS), np.int32)
+    slots[:] = np.asarray(SM_EMPTY, np.int32)[None, :, None]
+    ring_i[:] = np.asarray(RING_EMPTY, np.int32)[None, None, :, None]
+    return {"seq": np.zeros((S, 2), np.int32), "slots": slots, "ring_i": ring_i, "ring": np.zeros((S, D, WS_DOUBLES, MAX_SLOTS)),
+            "what": np.zeros((S, D, T, A), np.float32), "glimpse": np.zeros((S, D, T, G), np.float32),
+            "score": np.zeros((S, D, T), np.float32), "ring_frame": np.full((S, D), -1, np.int64),
+            "rows_frame": np.full((S, D), -1, np.int64)}
+
+
+def reset_smooth_state(state, sequences=None):
+    """restart all (None) or some sequences of a numpy smoother state, in place"""
+    import numpy as np
+    S, D = state["ring"].shape[:2]
+    rows = np.arange(S) if sequences is None else np.atleast_1d(np.asarray(sequences, np.int64))
+    if rows.size and (rows.min() < 0 or rows.max() >= S):
+        raise ValueError("reset: sequences within 0..%d, got %r" % (S - 1, sequences))
+    fresh = new_smooth_state(1, 0, 0, 0, state["score"].shape[2], state["what"].shape[3], state["glimpse"].shape[3], depth=D)
+    for k, v in fresh.items():
+        state[k][rows] = v[0]
+    return state
+
+
+def smooth_state_layout(n_sequences, depth):
+    """{key: (byte offset, dtype, shape)} of the packed device state and its size in bytes (air_track_smooth_stream_state_bytes)"""
+    import numpy as np
+    S, D = int(n_sequences), int(depth)
+    shapes = (("seq", np.int32, (S, 2)), ("slots", np.int32, (S, 6, MAX_SLOTS)), ("ring_i", np.int32, (S, D, 4, MAX_SLOTS)),
+              ("ring", np.float64, (S, D, WS_DOUBLES, MAX_SLOTS)))
+    at, layout = 0, {}
+    for k, dtype, shape in shapes:
+        layout[k] = (at, dtype, shape)
+        at += int(np.prod(shape)) * np.dtype(dtype).itemsize
+    return layout, at
+
+
+def pack_smooth_state(state):
+    """the packed device state of a numpy state: uint8 [state bytes]"""
+    import numpy as np
+    return np.concatenate([np.ascontiguousarray(state[k]).reshape(-1).view(np.uint8) for k in SMOOTH_STATE_KEYS])
+
+
+def unpack_smooth_state(packed, n_sequences, depth):
+    """{key: array} (copies) of a packed device state"""
+    import numpy as np
+    layout, size = smooth_state_layout(n_sequences, depth)
+    packed = np.ascontiguousarray(packed).reshape(-1).view(np.uint8)
+    if packed.size != size:
+        raise ValueError("a packed smoother state of %d sequences at depth %d has %d bytes, got %d" % (n_sequences, depth, size, packed.size))
+    return {k: packed[at:at + int(np.prod(shape)) * np.dtype(dtype).itemsize].view(dtype).reshape(shape).copy()
+            for k, (at, dtype, shape) in layout.items()}
+
+
+def _ring_put(plane, k, filt, pred):
+    """the filtered and predicted state of table row k into one frame's planes [28, 32] (csrc: WS_X, WS_V, WS_XP, WS_VP, WS_P, WS_PP)"""
+    plane[0:4, k], plane[4:8, k], plane[8:12, k], plane[12:16, k] = filt[0], filt[1], pred[0], pred[1]
+    for c, comp in ((0, 1), (1, 0)):                               # class 0 from tx, class 1 from sx: ty and sy hold the same bits
+        for i in range(3):
+            plane[16 + 6 * c + i, k], plane[19 + 6 * c + i, k] = filt[2 + i][comp], pred[2 + i][comp]
+
+
+def _ring_get(plane, k):
+    import numpy as np
+    cov = lambda base: tuple(np.array([plane[base + 6 * _CLASS[c] + i, k] for c in range(4)]) for i in range(3))
+    return (plane[0:4, k].copy(), plane[4:8, k].copy()) + cov(16), (plane[8:12, k].copy(), plane[12:16, k].copy()) + cov(19)
+
+
+def _ring_at(state, s, g, rows=False):
+    """the ring index of global frame g, the host's tag asserted: a ring too shallow has overwritten the frame"""
+    D = state["ring"].shape[1]
+    tag = state["rows_frame" if rows else "ring_frame"][s, g % D]
+    assert tag == g, "the ring of depth %d holds frame %d where frame %d is read: too shallow" % (D, tag, g)
+    return g % D
+
+
+def _stream_rows(state, s, g, hi):
+    """the rows of frame g given the frames up to hi: [(id, table row, last sighting within g .. hi, state, src_frame, src_slot)] in
+    ascending id of the tracks live in g that are sighted in g .. hi"""
+    ri = state["ring_i"][s]
+    found = []
+    for k in range(MAX_SLOTS):
+        tid, st, sf, sj = (int(v) for v in ri[_ring_at(state, s, g), :, k])
+        if tid < 0:
+            continue
+        la = None
+        for f in range(g, hi + 1):
+            e = ri[_ring_at(state, s, f), :, k]
+            if e[RING_ID] != tid:
+                break
+            if e[RING_STATE] == OBSERVED:
+                la = f
+        if la is not None:
+            found.append((tid, k, la, st, sf, sj))
+    return sorted(found)
+
+
+def _stream_column(state, out, pre, s, col, g, hi, C, img_size):
+    """frame g smoothed with the frames up to hi into column `col` of table `pre`: the backward pass from the track's last sighting
+    within g .. hi down to g over the ring.  Returns the rows written per state"""
+    H, W = img_size
+    counts = [0, 0, 0]
+    for row, (tid, k, la, st, sf, sj) in enumerate(_stream_rows(state, s, g, hi)):
+        if row >= C:
+            continue
+        filt, _ = _ring_get(state["ring"][s, _ring_at(state, s, la)], k)
+        xs, vs = filt[0], filt[1]
+        for f in range(la - 1, g - 1, -1):
+            filt, _ = _ring_get(state["ring"][s, _ring_at(state, s, f)], k)
+            _, pred = _ring_get(state["ring"][s, _ring_at(state, s, f + 1)], k)
+            xs, vs = _back_step(filt, pred, xs, vs)
+        _put(out, (H, W), pre, row, col, xs.astype("float32"), _velocity(vs, H, W), tid, st, (sf, sj))
+        counts[st] += 1
+    return counts
+
+
+def _stream_fill(state, out, pre, cols, per_seq, T):
+    """what / glimpse / score of a table's rows from the ring of provider rows: bit copies of the source sighting's rows"""
+    import numpy as np
+    C = out[pre + "id"].shape[0]
+    for key in ROW_RING_KEYS:
+        out[pre + key] = np.zeros((C, cols) + state[key].shape[3:], np.float32)
+    for c in range(C):
+        for n in range(cols):
+            sf, sj = int(out[pre + "src_frame"][c, n]), int(out[pre + "src_slot"][c, n])
+            if out[pre + "state"][c, n] != ABSENT and sf >= 0 and 0 <= sj < T:
+                s = n // per_seq
+                for key in ROW_RING_KEYS:
+                    out[pre + key][c, n] = state[key][s, _ring_at(state, s, sf, rows=True), sj]
+
+
+def reference_smooth_stream(state, where, num_objects, track_id, n_frames, valid=None, lag=None, max_age=1, img_size=(50, 50), horizon=0,
+                            process_noise=DEFAULTS["process_noise"], measurement_noise=DEFAULTS["measurement_noise"],
+                            velocity_var=DEFAULTS["velocity_var"], what=None, glimpse=None, score=None):
+    """air_track_stash, air_track_smooth_stream and air_track_fill_stream restated in numpy float64, on `_smooth_track`'s steps and
+    `reference_smooth`'s table code: ONE chunk.  state: None (a stream starts) or what an earlier call returned (it is not modified);
+    where [T, R, 4], num_objects [R], track_id [T, R] as the stream tracker leaves them, R = S n_frames, valid [S] (None: every frame);
+    what [T, R, A], glimpse [T, R, G], score [T, R] (None: the row ring is left alone and no row is filled).  Returns (outputs, state):
+    the emitted table sm_where .. sm_count at [C, S F] columns s F + e, e the order of emission, emit_frame [S, F] (GLOBAL, -1: none),
+    num_emitted [S], sm_counts [S, 3] (over the emitted columns), the forecast table fc_ at [C, S Hz], with the rows given sm_what /
+    sm_glimpse / sm_score and fc_ alike; and the new state (new_smooth_state's arrays)."""
+    import numpy as np
+    where = np.asarray(where, np.float32)
+    T, R = where.shape[:2]
+    T, F, S, C, L, Hz, D, (q_shift, q_scale), r, vv = check_stream_arguments(T, n_frames, R, max_age, lag, horizon, process_noise,
+                                                                             measurement_noise, velocity_var)
+    H, W = (int(v) for v in img_size)
+    ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
+    v_in = check_valid(valid, S, F)
+    rows = None if what is None else {"what": np.asarray(what, np.float32), "glimpse": np.asarray(glimpse, np.float32).reshape(T, R, -1),
+                                      "score": np.asarray(score, np.float32)}
+    if state is None:
+        A, G = (rows["what"].shape[2], rows["glimpse"].shape[2]) if rows else (1, 1)
+        state = new_smooth_state(S, F, L, max_age, T, A, G)
+    else:
+        state = {k: np.array(v) for k, v in state.items()}
+    D = state["ring"].shape[1] if state["ring"].ndim == 4 else -1
+    want = new_smooth_state(S, 1, 0, 0, T, state["what"].shape[-1], state["glimpse"].shape[-1], depth=max(D, 1))
+    for k, v in want.items():
+        if state[k].shape != v.shape or state[k].dtype != v.dtype:
+            raise ValueError("the state's %s is %s %s; a chunk of %d sequences and %d rows per frame needs %s %s"
+                             % (k, state[k].shape, state[k].dtype, S, T, v.shape, v.dtype))
+    if rows and (rows["what"].shape[2] != state["what"].shape[3] or rows["glimpse"].shape[2] != state["glimpse"].shape[3]):
+        raise ValueError("the state carries what rows of %d and glimpses of %d values, the chunk has %d and %d"
+                         % (state["what"].shape[3], state["glimpse"].shape[3], rows["what"].shape[2], rows["glimpse"].shape[2]))
+    check_frames_seen(state["seq"][:, 0], v_in)
+    q = np.array([q_scale, q_shift, q_scale, q_shift], np.float64)
+    N = S * Hz
+    out = dict(_new_table("sm_", C, R), **_new_table("fc_", C, N))
+    out.update(sm_counts=np.zeros((S, 3), np.int32), emit_frame=np.full((S, F), -1, np.int32), num_emitted=np.zeros(S, np.int32))
+    zeros5 = tuple(np.zeros(4) for _ in range(5))
+    with np.errstate(all="ignore"):
+        for s in range(S):
+            a, v = int(state["seq"][s, 0]), int(v_in[s])
+            b = a + v
+            sl, ring, ring_i = state["slots"][s], state["ring"][s], state["ring_i"][s]
+            for f in range(v):                                     # ---- forward: the table and the rings, frame by frame
+                g, rr = a + f, s * F + f
+                d = g % D
+                if rows:
+                    for key in ROW_RING_KEYS:
+                        state[key][s, d] = rows[key][:, rr]
+                    state["rows_frame"][s, d] = g
+                n = int(min(max(n_in[rr], 0), T))
+                seen, born = {}, set()
+                for j in range(n):                                 # sightings by id in ascending slot; births into the lowest free row
+                    i = int(ids[j, rr])
+                    if i < 0:
+                        continue
+                    k = next((k for k in range(MAX_SLOTS) if sl[SM_LIVE, k] and sl[SM_ID, k] == i), None)
+                    if k is None:
+                        k = next((k for k in range(MAX_SLOTS) if not sl[SM_LIVE, k]), None)
+                        if k is None:
+                            continue                               # (33 live ids: no tracker writes them)
+                        sl[:, k] = (1, i, 0, g, -1, -1)
+                        born.add(k)
+                        seen[k] = j
+                    elif k not in seen:
+                        seen[k] = j
+                for k in range(MAX_SLOTS):
+                    if not sl[SM_LIVE, k]:
+                        ring_i[d, :, k] = RING_EMPTY
+                        continue
+                    z = where[seen[k], rr].astype(np.float64) if k in seen else None
+                    if k in born:
+                        pred, filt = zeros5, _filter_start(z, r, vv)
+                    else:
+                        pred, filt = _filter_step(_ring_get(ring[_ring_at(state, s, g - 1)], k)[0], z, q, r)
+                    if k in seen:
+                        sl[SM_AGE, k], sl[SM_LAST_FRAME, k], sl[SM_LAST_SLOT, k] = 0, g, seen[k]
+                    else:
+                        sl[SM_AGE, k] += 1
+                    _ring_put(ring[d], k, filt, pred)
+                    ring_i[d, :, k] = (sl[SM_ID, k], OBSERVED if k in seen else FILLED, sl[SM_LAST_FRAME, k], sl[SM_LAST_SLOT, k])
+                state["ring_frame"][s, d] = g
+                for k in range(MAX_SLOTS):                         # retirement: the tracker's ageing
+                    if sl[SM_LIVE, k] and sl[SM_AGE, k] > max_age:
+                        sl[:, k] = SM_EMPTY
+            e = 0                                                  # ---- the frames that became final: g + L < b
+            for g in range(int(state["seq"][s, 1]), max(0, b - L)):
+                counts = _stream_column(state, out, "sm_", s, s * F + e, g, g + L, C, (H, W))
+                out["sm_counts"][s, OBSERVED] += counts[OBSERVED]
+                out["sm_counts"][s, FILLED] += counts[FILLED]
+                out["emit_frame"][s, e] = g
+                e += 1
+            assert e <= F
+            out["num_emitted"][s] = e
+            out["sm_counts"][s, ABSENT] = C * e - out["sm_counts"][s, OBSERVED] - out["sm_counts"][s, FILLED]
+            state["seq"][s] = (b, max(0, b - L))
+            live = sorted((int(sl[SM_ID, k]), k) for k in range(MAX_SLOTS) if sl[SM_LIVE, k])      # ---- the forecast
+            for row, (tid, k) in enumerate(live if Hz and b else []):
+                if row >= C:
+                    continue
+                la = int(sl[SM_LAST_FRAME, k])
+                (xl, vl) = _ring_get(ring[_ring_at(state, s, la)], k)[0][:2]
+                for kk in range(1, Hz + 1):
+                    _put(out, (H, W), "fc_", row, s * Hz + (kk - 1), _forecast_where(xl, vl, b - 1 - la + kk), _velocity(vl, H, W), tid,
+                         FORECAST, (la, int(sl[SM_LAST_SLOT, k])))
+        if rows:
+            _stream_fill(state, out, "sm_", R, F, T)
+            _stream_fill(state, out, "fc_", N, max(Hz, 1), T)
+    return out, state
+
+
+def reference_smooth_tail(state, lag, max_age, img_size, fill=True):
+    """air_track_smooth_tail (and, fill=True, air_track_fill_stream on it) restated: the frames max(0, b - L) .. b - 1 of every
+    sequence, not final yet, smoothed with what is known -- the last columns of `reference_smooth` on the first b frames.  The state
+    is only read.  Returns tl_where .. tl_count at [C, S L] columns s L + j, tail_frame [S, L] (GLOBAL, -1: none), num_tail [S]."""
+    import numpy as np
+    S, D, T = state["score"].shape
+    L, C = int(lag), completed_rows(T, max_age)
+    cols = S * L
+    out = _new_table("tl_", C, cols)
+    out.update(tail_frame=np.full((S, L), -1, np.int32), num_tail=np.zeros(S, np.int32))
+    with np.errstate(all="ignore"):
+        for s in range(S):
+            b = int(state["seq"][s, 0])
+            for j, g in enumerate(range(max(0, b - L), b)):
+                _stream_column(state, out, "tl_", s, s * L + j, g, b - 1, C, tuple(int(v) for v in img_size))
+                out["tail_frame"][s, j] = g
+                out["num_tail"][s] = j + 1
+        if fill:
+            _stream_fill(state, out, "tl_", cols, max(L, 1), T)
     return out
 
 
@@ -229,6 +594,15 @@ class CompletedFrames:
 
     def synchronize(self):
         self.engine.synchronize()
+
+
+def _table_result(pre, t, C, crop_size):
+    """the tensors of one table (TrajectorySmoother._table) under the prefix `pre`, the glimpses viewed as crops"""
+    out = {pre + k: t[k] for k in ("where", "boxes", "id", "state", "src_frame", "src_slot", "velocity", "count", "what", "score",
+                                   "presence", "offsets", "obj_image", "obj_step", "obj_box", "obj_score", "obj_where", "obj_what",
+                                   "reconstruction", "owner", "area")}
+    out[pre + "glimpse"] = t["glimpse"].view(C, t["count"].shape[0], *crop_size)
+    return out
 
 
 class TrajectorySmoother(BoundStage):
@@ -362,14 +736,8 @@ class TrajectorySmoother(BoundStage):
         cfg = self.engine.cfg
         out = dict(base) if base is not None else {}
         for pre, t in (("sm_", self.sm), ("fc_", self.fc)):
-            if t is None:
-                continue
-            N = t["count"].shape[0]
-            for k in ("where", "boxes", "id", "state", "src_frame", "src_slot", "velocity", "count", "what", "score", "presence",
-                      "offsets", "obj_image", "obj_step", "obj_box", "obj_score", "obj_where", "obj_what", "reconstruction", "owner",
-                      "area"):
-                out[pre + k] = t[k]
-            out[pre + "glimpse"] = t["glimpse"].view(self.C, N, *cfg.crop_size)
+            if t is not None:
+                out.update(_table_result(pre, t, self.C, cfg.crop_size))
         out["sm_counts"] = self.sm_counts
         if self.fc is not None:
             out["frames_pred"] = self.fc["reconstruction"].view(self.S, self.horizon, *self.img_size)
@@ -414,3 +782,275 @@ class TrajectorySmoother(BoundStage):
     def identity_summary(self) -> Dict[str, float]:
         """track.idf_summary of everything `score(identity=True)` took since the last reset (ONE read-back)"""
         return self.scores.identity_summary()
+
+
+class StreamSmoother(BoundStage):
+    """Trajectories on a STREAM: binds to a track.StreamTracker and gives every chunk fixed-lag smoothed, gap-filled rows and a forecast
+    (the module text states the rule; include/air_hip.h the layout of the carried state).  A frame is emitted `lag` frames late,
+    max_age <= lag <= MAX_LAG, with the bits TrajectorySmoother gives it on the sequence truncated `lag` frames behind it -- whatever the
+    chunking; the forecast needs no lag.  `push` is the tracker's `push` and then, after `capture()`, ONE hipGraph: air_track_stash,
+    air_track_smooth_stream, air_track_fill_stream and the unchanged read-out kernels on the emitted and on the forecast table.
+    `tail()` smooths the frames that are not final yet (the flush at the end of a video) on a plan and graph of its own and leaves
+    the state alone.  The tracker's state and the provider's buffers are only read; the smoother keeps a track table, the ring of
+    filter values and the ring of provider rows of the last D = chunk_frames + lag + max_age frames of its own, on the device.
+    `emitted` is the provider surface of the emitted frames (score.ParseScorer binds to it).  The default lag (max_age) and the noise
+    terms are provisional: UNMEASURED on a trained model."""
+    KEY_FIELDS = ("output_multiplier", "output_std")
+
+    def __init__(self, stream_tracker, lag=None, horizon=0, process_noise=DEFAULTS["process_noise"],
+                 measurement_noise=DEFAULTS["measurement_noise"], velocity_var=DEFAULTS["velocity_var"]):
+        import numpy as np
+        import torch
+        from . import hip as H
+        tk = stream_tracker
+        if not hasattr(tk, "frames_seen") or not hasattr(tk, "push"):
+            raise ValueError("StreamSmoother binds to a track.StreamTracker, got %s" % type(tk).__name__)
+        T, F, S, C, L, Hz, D, q, r, vv = check_stream_arguments(tk.T, tk.F, tk.R, tk.max_age, lag, horizon, process_noise,
+                                                                measurement_noise, velocity_var)
+        provider = tk.provider
+        self.tracker, self.provider, self.engine, self.parser, self._bound = tk, provider, tk.engine, provider, tk
+        self.window_T, self.T, self.C, self.R, self.S, self.F, self.horizon, self.lag, self.depth = T, C, C, int(tk.R), S, F, Hz, L, D
+        self.process_noise, self.measurement_noise, self.velocity_var, self.max_age = q, r, vv, int(tk.max_age)
+        self.mask_threshold, self.img_size = provider.mask_threshold, tuple(tk.img_size)
+        self._rows = {k: tk._rows[k] for k in ("what", "where", "glimpse")}
+        cfg = self.engine.cfg
+        self.A, self.G = int(tk.A), int(cfg.crop_size[0]) * int(cfg.crop_size[1])
+        dev, R = self.engine.device, self.R
+        lib = H.lib()
+        self._H = H
+        self._layout, self.state_bytes = smooth_state_layout(S, D)
+        if int(lib.air_track_smooth_stream_state_bytes(S, D)) != self.state_bytes:
+            raise ValueError("a smoother state of %d sequences at depth %d does not fit the kernel's limits" % (S, D))
+        bands = lambda N: int(lib.air_canvas_unroll_bands(N, self.img_size[0])) if N else 0
+        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+        with torch.cuda.device(dev):
+            self.packed = z((self.state_bytes,), torch.uint8)
+            self.state = {k: self.packed[at:at + int(np.prod(shape)) * np.dtype(dt).itemsize].view(getattr(torch, np.dtype(dt).name))
+                          .view(shape) for k, (at, dt, shape) in self._layout.items()}
+            self.rings = {"what": z((S, D, T, self.A)), "glimpse": z((S, D, T, self.G)), "score": z((S, D, T))}
+            self.score_state = {"score_i": z((S, 32), torch.int32), "score_f": z((S,), torch.float64)}
+            (self.sm, self._sm_ro) = self._table(z, R, bands(R))
+            (self.fc, self._fc_ro) = self._table(z, S * Hz, bands(S * Hz)) if Hz else (None, None)
+            (self.tl, self._tl_ro) = self._table(z, S * L, bands(S * L)) if L else (None, None)
+            self.sm_counts, self.emit_frame, self.num_emitted = z((S, 3), torch.int32), z((S, F), torch.int32), z((S,), torch.int32)
+            self.tail_frame = z((S, max(L, 1)), torch.int32)
+        self.frames_seen = np.zeros(S, np.int64)                   # the host's mirror of state["seq"][:, 0]
+        self._score, self._tail = {}, {"plan": [], "graph": None}
+        t = self.sm
+        self.what, self.where, self.glimpse, self.boxes = t["what"], t["where"], t["glimpse"], t["boxes_out"]
+        self.presence, self.num_objects, self.owner = t["presence"], t["num_objects"], t["owner"]
+        self.emitted = CompletedFrames(self)
+        self._rebuild()
+        for name in ("readout", "readout_forecast"):
+            if name in self.segments:
+                self.check_render(self.segments[name][2],
+                                  "air_parse_render declines %d x %d frames with %d emitted rows: its LDS carve passes the 160 KiB "
+                                  "of a workgroup; use a smaller max_age" % (self.img_size + (self.C,)))
+        self._reset_own(np.arange(S))
+        self.engine.synchronize()
+
+    _table = TrajectorySmoother._table
+    _readout = TrajectorySmoother._readout
+
+    def _fill(self, t, N, per_seq):
+        L, p, rg = self._H.lib(), self._H._p, self.rings
+        return [(L.air_track_fill_stream,
+                 (p(rg["what"]), p(rg["glimpse"]), p(rg["score"]), p(t["state"]), p(t["src_frame"]), p(t["src_slot"]), self.window_T,
+                  self.S, self.depth, self.C, N, per_seq, self.A, self.G, p(t["what"]), p(t["glimpse"]), p(t["score"])),
+                 "air_track_fill_stream")]
+
+    def _build_plan(self):
+        tk, par, rows, rg = self.tracker, self.provider, self._rows, self.rings
+        L, p, size = self._H.lib(), self._H._p, ctypes.c_size_t
+        Hi, Wi = self.img_size
+        sm, fc, tl, Hz = self.sm, self.fc, self.tl, self.horizon
+        fcp = lambda k: p(fc[k]) if fc is not None else None
+        qs, qc = self.process_noise
+        table = lambda t: [p(t[k]) for k in ("where", "boxes", "id", "state", "src_frame", "src_slot", "velocity", "count")]
+        self.segments = OrderedDict([
+            ("stash", [(L.air_track_stash,
+                        (p(rows["what"]), p(rows["glimpse"]), p(par.score), p(tk.valid), p(self.packed), self.window_T, self.S, self.F,
+                         self.R, self.A, self.G, self.depth, p(rg["what"]), p(rg["glimpse"]), p(rg["score"])), "air_track_stash")]),
+            ("smooth", [(L.air_track_smooth_stream,
+                         (p(rows["where"]), p(par.num_objects), p(tk.track_id), p(tk.valid), self.window_T, self.S, self.F, self.R,
+                          self.C, self.lag, Hz, self.depth, self.max_age, Hi, Wi, qs, qc, self.measurement_noise, self.velocity_var,
+                          p(self.packed), size(self.state_bytes), *table(sm), p(self.sm_counts), p(self.emit_frame),
+                          p(self.num_emitted), *[fcp(k) for k in ("where", "boxes", "id", "state", "src_frame", "src_slot", "velocity",
+                                                                   "count")]), "air_track_smooth_stream")]),
+            ("fill", self._fill(sm, self.R, self.F)),
+            ("readout", self._readout(sm, self._sm_ro))])
+        if fc is not None:
+            self.segments["fill_forecast"] = self._fill(fc, self.S * Hz, Hz)
+            self.segments["readout_forecast"] = self._readout(fc, self._fc_ro)
+        self._plan = [e for seg in self.segments.values() for e in seg]
+        self._tail["plan"] = [] if tl is None else (
+            [(L.air_track_smooth_tail, (self.window_T, self.S, self.C, self.lag, self.depth, self.max_age, Hi, Wi, p(self.packed),
+                                        size(self.state_bytes), *table(tl), p(self.tail_frame)), "air_track_smooth_tail")]
+            + self._fill(tl, self.S * self.lag, self.lag) + self._readout(tl, self._tl_ro))
+
+    def _score_entries(self):
+        return [e for e in list(self._score.values()) + [self._tail] if e["plan"]]
+
+    def launch_count(self) -> Dict[str, int]:
+        """entries of one `push()` behind the tracker's own (`tracker` holds that tracker's launch_count()); `tail` those of `tail()`"""
+        n = 2 if self.fc is not None else 1
+        return {"tracker": self.tracker.launch_count(), "track_stash": 1, "track_smooth_stream": 1, "track_fill_stream": n,
+                "parse_objects": n, "tile_relabel": n, "parse_render": n, "tail": len(self._tail["plan"])}
+
+    # ---- the state ----------------------------------------------------------------------------------------------------------------
+    def _reset_own(self, rows):
+        import torch
+        eng, st = self.engine, self.state
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            idx = torch.as_tensor(rows, device=eng.device)
+            i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=eng.device)
+            st["seq"][idx] = 0
+            st["slots"][idx] = i32(SM_EMPTY)[None, :, None].expand(len(rows), 6, MAX_SLOTS)
+            st["ring_i"][idx] = i32(RING_EMPTY)[None, None, :, None].expand(len(rows), self.depth, 4, MAX_SLOTS)
+            st["ring"][idx] = 0
+            for buf in self.rings.values():
+                buf[idx] = 0
+            self.score_state["score_i"][idx] = 0
+            self.score_state["score_i"][idx, 8:16] = -1
+            self.score_state["score_f"][idx] = 0
+        self.frames_seen[rows] = 0
+        eng.wait_for_engine()
+
+    def reset(self, sequences=None):
+        """restart all (None) or some sequences ON THE DEVICE: the tracker's state AND the smoother's (its table, rings and score state)"""
+        import numpy as np
+        rows = np.arange(self.S) if sequences is None else np.atleast_1d(np.asarray(sequences, np.int64))
+        self.tracker.reset(sequences)
+        self._reset_own(rows)
+
+    def state_dict(self):
+        """a copy of everything carried: the tracker's state_dict() under "tracker", the packed smoother state, the rings of provider
+        rows and the score state, as plain device tensors"""
+        import torch
+        out = {"tracker": self.tracker.state_dict()}
+        eng = self.engine
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            out["smooth"] = self.packed.clone()
+            out.update({"ring_" + k: v.clone() for k, v in self.rings.items()})
+            out.update({k: v.clone() for k, v in self.score_state.items()})
+        eng.wait_for_engine()
+        return out
+
+    def load_state_dict(self, state):
+        import torch
+        own = dict({"smooth": self.packed}, **{"ring_" + k: v for k, v in self.rings.items()}, **self.score_state)
+        for k, buf in own.items():
+            if tuple(state[k].shape) != tuple(buf.shape):
+                raise ValueError("load_state_dict: %s has shape %s, this stream's is %s" % (k, tuple(state[k].shape), tuple(buf.shape)))
+        self.tracker.load_state_dict(state["tracker"])
+        eng = self.engine
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            for k, buf in own.items():
+                buf.copy_(torch.as_tensor(state[k]).to(buf.dtype), non_blocking=True)
+        eng.wait_for_engine()
+        eng.synchronize()
+        self.frames_seen[:] = self.state["seq"][:, 0].cpu().numpy()
+
+    # ---- the trajectories -------------------------------------------------------------------------------------------------------------
+    def _check_mirror(self, fed_limit):
+        import numpy as np
+        fed = np.asarray(self.tracker.frames_seen, np.int64) - self.frames_seen
+        if (fed < 0).any() or (fed > fed_limit).any():
+            s = int(np.argmax((fed < 0) | (fed > fed_limit)))
+            raise ValueError("the tracker has seen %d frames of sequence %d, the smoother %d: the tracker was reset or pushed behind "
+                             "the smoother's back; reset() both through the smoother, or load_state_dict()"
+                             % (int(self.tracker.frames_seen[s]), s, int(self.frames_seen[s])))
+
+    def run(self, base=None):
+        """the trajectories of the tracker's LATEST push (which the smoother has not seen yet); `base` is passed through"""
+        eng = self.engine
+        self._check_mirror(self.F)
+        self._refresh_plan()
+        eng.wait_for_caller()
+        eng._replay_or_run(self._graph, self._plan)
+        self.frames_seen = self.tracker.frames_seen.copy()
+        eng.wait_for_engine()
+        return self.result(base)
+
+    def push(self, frames, valid=None, *args, **kwargs):
+        """the bound tracker's `push(frames, valid, ...)`, then `run()` on its result.  Refused when the tracker's frames_seen differs
+        from the smoother's"""
+        self._check_mirror(0)
+        return self.run(self.tracker.push(frames, valid, *args, **kwargs))
+
+    def result(self, base=None):
+        """TrajectorySmoother.result's tensors for the EMITTED table: sm_* at [C, S F] columns s F + e, emit_frame [S, F] (the global
+        frame of column e, -1: none), num_emitted [S]; with a horizon fc_* at [C, S Hz] and frames_pred [S, Hz, H, W]"""
+        out = TrajectorySmoother.result(self, base)
+        out.update(emit_frame=self.emit_frame, num_emitted=self.num_emitted)
+        return out
+
+    def tail(self):
+        """the frames max(0, b - lag) .. b - 1, not final yet, smoothed with what is known: tl_* at [C, S lag] columns s lag + j (every
+        tensor `result` lists under sm_), tail_frame [S, lag] (-1: none).  Reads the state and changes nothing: the stream goes on"""
+        if self.tl is None:
+            raise ValueError("lag = 0: every frame is final when it is seen; there is no tail")
+        eng = self.engine
+        self._refresh_plan()
+        eng.wait_for_caller()
+        eng._replay_or_run(self._tail["graph"], self._tail["plan"])
+        eng.wait_for_engine()
+        out = _table_result("tl_", self.tl, self.C, eng.cfg.crop_size)
+        out["tail_frame"] = self.tail_frame
+        return out
+
+    # ---- the identity metric on the emitted frames ------------------------------------------------------------------------------------
+    def score(self, gt_boxes, tau=0.5):
+        """StreamTracker.score on the EMITTED table of the latest push: the unchanged air_track_score_stream with T := C and valid :=
+        num_emitted on sm_boxes, sm_count, sm_id, continuing CLEAR-MOT across the pushes.  gt_boxes [R, G, 4] or [S, F, G, 4]: row
+        s F + e the ground truth of global frame emit_frame[s, e] (the caller keeps it `lag` frames).  Once per push.  Returns
+        seq_counts [S, 8], seq_iou [S] float64 (cumulative) and gt_match [R, G] of the emitted columns."""
+        import torch
+        from .track import MAX_GT
+        eng, R, S = self.engine, self.R, self.S
+        gb = torch.as_tensor(gt_boxes)
+        if gb.dim() not in (3, 4) or gb.shape[-1] != 4 or gb.numel() != R * gb.shape[-2] * 4:
+            raise ValueError("gt_boxes: expected [%d, G, 4] or [%d, %d, G, 4], got %s" % (R, S, self.F, tuple(gb.shape)))
+        key = (int(gb.shape[-2]), float(tau))
+        entry = self._score.get(key)
+        if entry is None:
+            if self._score:
+                raise ValueError("this stream is scored with (G, tau) = %r; a stream of its own for %r" % (next(iter(self._score)), key))
+            G, tau_f = key
+            if not 1 <= G <= MAX_GT or not 0.0 <= tau_f <= 1.0:
+                raise ValueError("gt_boxes: 1..%d ground-truth slots and tau within [0, 1], got %d and %r" % (MAX_GT, G, tau))
+            L, p, dev, sm, ss = self._H.lib(), self._H._p, eng.device, self.sm, self.score_state
+            with torch.cuda.device(dev):
+                entry = {"gt_boxes": torch.zeros((R, G, 4), device=dev), "seq_counts": torch.zeros((S, 8), dtype=torch.int32, device=dev),
+                         "seq_iou": torch.zeros((S,), dtype=torch.float64, device=dev),
+                         "gt_match": torch.zeros((R, G), dtype=torch.int32, device=dev), "graph": None}
+            entry["plan"] = [(L.air_track_score_stream,
+                              (p(sm["boxes"]), p(sm["count"]), p(sm["id"]), p(entry["gt_boxes"]), tau_f, self.C, G, S, self.F, R,
+                               p(self.num_emitted), p(ss["score_i"]), p(ss["score_f"]), p(entry["seq_counts"]), p(entry["seq_iou"]),
+                               p(entry["gt_match"])), "air_track_score_stream")]
+            if self._graph is not None:
+                eng.synchronize()
+                entry["graph"] = eng._capture_plans([entry["plan"]])
+            self._score[key] = entry
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            entry["gt_boxes"].copy_(gb.reshape(entry["gt_boxes"].shape), non_blocking=True)
+        if gb.is_cuda:
+            gb.record_stream(eng.stream)
+        eng._replay_or_run(entry["graph"], entry["plan"])
+        eng.wait_for_engine()
+        return {k: entry[k] for k in ("seq_counts", "seq_iou", "gt_match")}
+
+    def summary(self) -> Dict[str, float]:
+        """track.mot_summary of the emitted frames scored so far (ONE read-back)"""
+        import torch
+        from .track import mot_summary
+        self.engine.wait_for_engine()
+        if not self._score:
+            return mot_summary([0] * 8, 0.0)
+        entry = next(iter(self._score.values()))
+        flat = torch.cat([entry["seq_counts"].sum(0, dtype=torch.int64).double(), entry["seq_iou"].sum(0, keepdim=True)]).tolist()
+        return mot_summary(flat[:8], flat[8])

@@ -988,8 +988,9 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *   sum_iou is CONTINUED from the carried value, so seq_iou has the bits air_track_score gives on the concatenation.  seq_counts[S,8]
  *   and seq_iou[S] are cumulative over the stream (mostly tracked / lost / objects from the cumulative tracked / present);
  *   gt_match[R,G] is the chunk's, -1 on padding rows.  The same valid.
- * Out of scope on a stream: IDF1 (its overlap table is indexed by global id: 1 MB per sequence at 32767 ids), trajectory smoothing
- *   (the backward pass needs the future), ids beyond 32766 without a reset of the sequence, more than 32 live tracks.               */
+ * Out of scope on a stream: IDF1 (its overlap table is indexed by global id: 1 MB per sequence at 32767 ids), ids beyond 32766
+ *   without a reset of the sequence, more than 32 live tracks.  Trajectories on a stream are fixed-lag smoothed, L frames late:
+ *   air_track_smooth_stream, below.                                                                                              */
 AIR_ENGINE_API int air_track_associate_stream(const float *what, const float *boxes, const float *score, const int *num_objects, int T,
                     int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
                     const int *valid, int matching, int *st_seq, int *st_slots, float *st_box, float *st_what, int *track_id,
@@ -1065,6 +1066,74 @@ AIR_ENGINE_API int air_track_smooth(const float *where, const int *num_objects, 
 AIR_ENGINE_API int air_track_fill(const float *what, const float *glimpse, const float *score, const signed char *state,
                     const int *src_frame, const int *src_slot, int T, int F, int R, int C, int N, int per_seq, int A, int G,
                     float *out_what, float *out_glimpse, float *out_score, void *stream);
+
+/* ---- trajectories on a stream: fixed-lag smoothing and forecasts per chunk, behind air_track_associate_stream (its chunks, valid[S]
+ * and global frame indices; frames_seen below 2^31 is the caller's to refuse).  THE RULE is air_track_smooth's, unchanged: start /
+ * predict / update / back per sequence, track id and where component, float64 from the widened fp32 values, contraction off, only
+ * + - * /, in the stated order, the same q, r, velocity_var and C = min(32, T (max_age + 1)).  A stream smoother has a LAG L,
+ * max_age <= L <= 16 (AIR_E_SHAPE otherwise): the forward filter is causal, and the backward pass over a bounded window is final for
+ * global frame g once frame g + L has been seen.  L >= max_age makes "does the track span g" final by then: a track that coasts at
+ * g and has no sighting in g + 1 .. g + L is retired.  A push that takes frames_seen[s] from a to b:
+ *   EMITTED: the global frames max(0, a - L) <= g < max(0, b - L), each once, in ascending order, at most clip(valid[s], 0, F) of
+ *     them, into columns s F + e (e the order of emission) of the table sm_*[C, S F]; emit_frame[S,F] = g (-1 from num_emitted[s]
+ *     on, those columns ABSENT with count 0).  The rows of g: the tracks with a sighting at or before g and a sighting in g .. g + L,
+ *     in ascending id, rows at or beyond C dropped; each holds air_track_smooth's fields, the backward pass run from the track's
+ *     last sighting at or before g + L down to g; sm_src_frame is a GLOBAL frame (the last sighting at or before g), sm_state 1
+ *     OBSERVED / 2 FILLED.  sm_counts[S,3] = rows per state over the emitted columns (they sum to C num_emitted[s]).
+ *     TRUNCATION IDENTITY: the rows of g are, bit for bit, column g of air_track_smooth on the first g + L + 1 frames of the
+ *     concatenation of the sequence's valid frames.  Hence CHUNK INVARIANCE: any chunking (ragged valid, valid = 0) gives the same bits.
+ *   FORECAST, every push, Hz in 0..16: fc_*[C, S Hz] as air_track_smooth's on the first b frames, bit for bit -- the tracks with
+ *     b - 1 - last <= max_age (the live rows of the table) in ascending id, from the filtered state at `last`, m = b - 1 - last + k.
+ *     valid = 0 gives the same forecast again; a sequence that has seen nothing an empty one.  Hz == 0: the fc_ pointers may be NULL.
+ *   TAIL (air_track_smooth_tail; the state is only read): the frames max(0, b - L) .. b - 1, not final yet, smoothed with what is
+ *     known, into columns s L + j of tl_*[C, S L], tail_frame[S,L] = g or -1: bit for bit the last columns of air_track_smooth on
+ *     the first b frames.  At the end of a video the tail is the flush.  L == 0: nothing to do, AIR_OK without a launch.
+ *   FILL (air_track_fill_stream): what / glimpse / score of emitted, tail and forecast rows are bit copies of the source sighting's
+ *     provider rows, which may lie in an earlier chunk: air_track_stash keeps the provider's rows of the last D frames.
+ * THE CARRIED STATE is device memory read and written in place (air_track_smooth_tail, air_track_fill_stream: read only); the
+ * stream tracker's state and the provider are only read.  One buffer of air_track_smooth_stream_state_bytes(S, D) bytes, 8-byte
+ * aligned, in this order (a fresh stream: seq 0, slots {0, -1, 0, -1, -1, -1}, ring_i {-1, 0, -1, -1}, ring 0):
+ *     seq   [S,2]       int32    {frames_seen, the next frame to emit = max(0, frames_seen - L)};
+ *     slots [S,6,32]    int32    field-major, the smoother's OWN table of at most 32 tracks: {live, id, age, first, last-sighting
+ *                                global frame, last-sighting slot}.  It is derived from the chunk's track_id / num_objects / valid
+ *                                alone and mirrors the tracker's table: in a frame the ids of slots j < clip(num_objects, 0, T) in
+ *                                ascending slot -- an id the table holds is a sighting (its lowest slot), any other id >= 0 is born
+ *                                into the lowest free row (none free: dropped; no tracker writes 33 live ids); then a row without a
+ *                                sighting ages, and age > max_age retires it.  A row that is not live: {0, -1, 0, -1, -1, -1};
+ *     ring_i[S,D,4,32]  int32    per global frame g at g mod D and table row: {id or -1, state 1 sighted / 2 coasted / 0 not live,
+ *                                the last sighting at or before g: global frame, slot};
+ *     ring  [S,D,28,32] float64  per frame and table row what the backward pass reads: planes 0-3 x, 4-7 v, 8-11 x-, 12-15 v- (per
+ *                                where component), 16-18 P and 19-21 P- of the shifts, 22-24 P and 25-27 P- of the scales (xx, xv,
+ *                                vv); x- / v- / P- are 0 in a track's first frame.  The planes of a row that is not live are left
+ *                                as they were.  The filter state of a live track is its entry of frame frames_seen - 1.
+ *   The ring of provider rows (three buffers of their own): ring_what[S,D,T,A], ring_glimpse[S,D,T,G], ring_score[S,D,T] fp32, frame
+ *   g at g mod D.  DEPTH: D >= F + L + max_age (AIR_E_SHAPE otherwise; the tail alone: D >= L + max_age): a push writes the frames
+ *   a .. a + F - 1, emits from a - L on, and the source sighting of a FILLED row there lies up to max_age frames before it.
+ * air_track_stash: bit copies of the chunk's valid provider rows (j, s F + f), f < clip(valid[s], 0, F), into the ring at frame
+ *   (frames_seen[s] + f) mod D; launched BEFORE air_track_smooth_stream, which moves frames_seen.  One wavefront per row.
+ * air_track_smooth_stream: one workgroup of one wavefront per sequence, lane k < 32 = table row k, the table and the filter state in
+ *   registers, the rings in global memory; it walks the chunk's valid frames, then runs the backward pass of every emitted frame
+ *   (at most F L steps per lane), then the forecast.  Every element of every output is written.  Row order is a count of integers;
+ *   no floating-point atomics.  Checks as air_track_smooth's; state_bytes too small: AIR_E_WORKSPACE.
+ * air_track_fill_stream: air_track_fill with the ring as its source, row (s, src_frame mod D, src_slot); N columns, column n of
+ *   sequence n / per_seq (per_seq = F, Hz or L); zeros where the state is ABSENT or the source is outside the ring's rows.
+ * Out of scope: smoothed covariances, feeding smoothed rows back into the association, IDF1 on a stream.                            */
+AIR_ENGINE_API size_t air_track_smooth_stream_state_bytes(int S, int D);
+AIR_ENGINE_API int air_track_stash(const float *what, const float *glimpse, const float *score, const int *valid, const void *state,
+                    int T, int S, int F, int R, int A, int G, int D, float *ring_what, float *ring_glimpse, float *ring_score,
+                    void *stream);
+AIR_ENGINE_API int air_track_smooth_stream(const float *where, const int *num_objects, const int *track_id, const int *valid, int T,
+                    int S, int F, int R, int C, int L, int Hz, int D, int max_age, int H, int W, double q_shift, double q_scale,
+                    double r, double velocity_var, void *state, size_t state_bytes, float *sm_where, float *sm_boxes, int *sm_id,
+                    signed char *sm_state, int *sm_src_frame, int *sm_src_slot, float *sm_velocity, int *sm_count, int *sm_counts,
+                    int *emit_frame, int *num_emitted, float *fc_where, float *fc_boxes, int *fc_id, signed char *fc_state,
+                    int *fc_src_frame, int *fc_src_slot, float *fc_velocity, int *fc_count, void *stream);
+AIR_ENGINE_API int air_track_smooth_tail(int T, int S, int C, int L, int D, int max_age, int H, int W, const void *state,
+                    size_t state_bytes, float *tl_where, float *tl_boxes, int *tl_id, signed char *tl_state, int *tl_src_frame,
+                    int *tl_src_slot, float *tl_velocity, int *tl_count, int *tail_frame, void *stream);
+AIR_ENGINE_API int air_track_fill_stream(const float *ring_what, const float *ring_glimpse, const float *ring_score,
+                    const signed char *state, const int *src_frame, const int *src_slot, int T, int S, int D, int C, int N,
+                    int per_seq, int A, int G, float *out_what, float *out_glimpse, float *out_score, void *stream);
 
 /* ---- scoring a parse against ground truth (owner maps and boxes as air_parse_* leave them; gt maps int8 with -1 = background,
  * gt_boxes[R,G,4] = (left, top, width, height) in the units of air_parse_objects' boxes).  T in 1..32, G in 1..8, K in 1..16
