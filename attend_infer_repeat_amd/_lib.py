@@ -45,7 +45,7 @@ class AirWarpForm(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
-WARP_KERNELS = ("read_fwd", "read_fwd_lean", "read_bwd", "write_fwd", "write_bwd", "fused")     # AIR_WARP_* in order
+WARP_KERNELS = ("read_fwd", "read_fwd_lean", "read_bwd", "write_fwd", "write_bwd", "fused", "parse_render")     # AIR_WARP_* in order
 GEMM_FAMILIES = ("tile", "c16", "apro", "shortk", "wide", "wide16", "big", "big16")     # AIR_GEMM_FAM_* in order
 
 
@@ -123,6 +123,7 @@ SIGNATURES = {
     "air_canvas_bwd_form": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(AirWarpForm)]),
     "air_canvas_fwd_bwd_form": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(AirWarpForm)]),
+    "air_parse_render_form": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(AirWarpForm)]),
     "air_imp_weight": (c_int, [P, c_int, P, P, c_float, P, P, P, c_int, c_int, P, P, c_float, P]),
     "air_nvil_parts": (c_int, [P, c_int, P, P, P, P, P, P, c_int, P, P]),
     "air_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, c_int, P, c_int,

@@ -310,10 +310,12 @@ __global__ __launch_bounds__(1024) void parse_render_kernel(ParseRenderArgs a) {
     AIR_TR_FLUSH();
 }
 
-extern "C" int air_parse_render(const float *glimpse, const float *where, const float *presence, const float *obs, float mult,
-                                float std, float mask_threshold, int T, int R, int H, int W, int h, int w, int n_bands,
-                                float *reconstruction, float *rec_parts, signed char *owner, int *area, float *layers,
-                                void *stream) {
+// WHICH form air_parse_render runs (bands, workgroup size, LDS, glimpse staging, grid): the decision the launch below consumes and
+// air_parse_render_form returns -- no launch, no device memory touched; the status is the one the launch returns before its memset.
+static int parse_render_form(const float *glimpse, const float *where, const float *presence, const float *obs,
+                             const float *reconstruction, const float *rec_parts, const signed char *owner, const int *area, int T, int R,
+                             int H, int W, int h, int w, int n_bands, AirWarpForm &f) {
+    f = AirWarpForm{};
     AIR_REQUIRE(glimpse && where && presence && reconstruction && owner && area, AIR_E_NULL);
     AIR_REQUIRE(!rec_parts || obs, AIR_E_NULL);
     AIR_REQUIRE(T > 0 && T <= PARSE_MAXT && R > 0 && H > 0 && W > 0 && h > 0 && w > 0 && n_bands > 0, AIR_E_SHAPE);
@@ -323,9 +325,6 @@ extern "C" int air_parse_render(const float *glimpse, const float *where, const 
     AIR_REQUIRE(NB == n_bands || !rec_parts, AIR_E_SHAPE);       // the caller sized rec_parts for exactly n_bands shares
     const size_t lds = sizeof(float) * (band_carve_floats(T, RB, W, h, w) + PARSE_TAIL_FLOATS);
     AIR_REQUIRE(lds <= CV_MAX_LDS, AIR_E_UNSUPPORTED);
-    { int st_ = cv_allow_lds(parse_render_kernel, lds); if (st_) return st_; }
-    hipError_t e = hipMemsetAsync(area, 0, sizeof(int) * (size_t)T * R, air_stream(stream));
-    if (e != hipSuccess) return (int)e;
     // workgroup sizes of the canvas write (launch_write_fwd): one pixel per thread while the launch is far from filling the chip
     const long units = (long)R * NB;
     int threads = units <= 512 ? 512 : ST_THREADS;
@@ -333,10 +332,35 @@ extern "C" int air_parse_render(const float *glimpse, const float *where, const 
         const int px = RB * W;
         threads = px >= 1024 ? 1024 : ((px + 63) / 64) * 64;
     }
-    const ParseRenderArgs a = {glimpse, where, presence, obs, reconstruction, rec_parts, layers, owner, area, T, R, NB, RB, H, W, h, w,
-                               lin_step(W), lin_step(H), mult, std, mask_threshold, (w % 4 == 0) && air_aligned16(glimpse)};
-    const int cap = units > 256 * 8 ? air_resident_grid(parse_render_kernel, threads, lds, 256 * 8) : 256 * 8;
-    hipLaunchKernelGGL(parse_render_kernel, dim3((unsigned)(units < cap ? units : cap)), dim3(threads), lds, air_stream(stream), a);
+    f.kernel = AIR_WARP_PARSE_RENDER;
+    f.threads = threads; f.lds_bytes = (int)lds;
+    f.vec4_glimpse = (w % 4 == 0) && air_aligned16(glimpse);
+    f.NB = NB; f.RB = RB;
+    f.items = units > (long)INT_MAX ? INT_MAX : (int)units; f.fixed_cap = 256 * 8; f.resident_cap = units > 256 * 8;
+    return AIR_OK;
+}
+extern "C" int air_parse_render_form(const float *glimpse, const float *where, const float *presence, const float *obs,
+                                     const float *reconstruction, const float *rec_parts, const signed char *owner, const int *area,
+                                     int T, int R, int H, int W, int h, int w, int n_bands, AirWarpForm *out) {
+    AIR_REQUIRE(out, AIR_E_NULL);
+    return parse_render_form(glimpse, where, presence, obs, reconstruction, rec_parts, owner, area, T, R, H, W, h, w, n_bands, *out);
+}
+
+extern "C" int air_parse_render(const float *glimpse, const float *where, const float *presence, const float *obs, float mult,
+                                float std, float mask_threshold, int T, int R, int H, int W, int h, int w, int n_bands,
+                                float *reconstruction, float *rec_parts, signed char *owner, int *area, float *layers,
+                                void *stream) {
+    AirWarpForm f;
+    int st = parse_render_form(glimpse, where, presence, obs, reconstruction, rec_parts, owner, area, T, R, H, W, h, w, n_bands, f);
+    if (st) return st;
+    const size_t lds = (size_t)f.lds_bytes;
+    { int st_ = cv_allow_lds(parse_render_kernel, lds); if (st_) return st_; }
+    hipError_t e = hipMemsetAsync(area, 0, sizeof(int) * (size_t)T * R, air_stream(stream));
+    if (e != hipSuccess) return (int)e;
+    const ParseRenderArgs a = {glimpse, where, presence, obs, reconstruction, rec_parts, layers, owner, area, T, R, f.NB, f.RB, H, W, h, w,
+                               lin_step(W), lin_step(H), mult, std, mask_threshold, f.vec4_glimpse};
+    const int cap = f.resident_cap ? air_resident_grid(parse_render_kernel, f.threads, lds, f.fixed_cap) : f.fixed_cap;
+    hipLaunchKernelGGL(parse_render_kernel, dim3((unsigned)(f.items < cap ? f.items : cap)), dim3(f.threads), lds, air_stream(stream), a);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

@@ -113,6 +113,11 @@ __global__ __launch_bounds__(256) void particle_gather_kernel(const int *__restr
 
 // One wavefront per image; float64, two passes per step (mean, then the spread about it).  The weights exp(log w - max) are formed
 // again in every pass from the cached log-weights: K is small and the kernel is latency-bound.
+// A step that exactly one particle of non-zero weight has: (w x) / w is x only to the last float64 place, so the spread about that
+// mean would be 1e-16 |x|, not 0 -- the count of such particles decides, and the spread is exactly 0.  A step nobody has: W = 0, mean
+// and spread NaN, presence_iw exactly 0.  Non-finite log-weights follow iw_reduce_kernel: an infinite maximum shifts by 0, so all
+// -inf or one +inf give NaN means and spreads throughout, one NaN at every step that particle has, and presence_iw has the class of the
+// tail sums of the reduce's q_n (NaN; NaN for the steps the +inf particle has and 0 behind them; NaN).
 __global__ __launch_bounds__(256) void particle_spread_kernel(const float *__restrict__ log_w, const int *__restrict__ num_steps,
                                                               const float *__restrict__ where, int T, int B, int K,
                                                               float *__restrict__ where_mean, float *__restrict__ where_std,
@@ -125,21 +130,26 @@ __global__ __launch_bounds__(256) void particle_spread_kernel(const float *__res
     const int *nk = num_steps + base;
     float mf = -INFINITY;
     for (int k = lane; k < K; k += 64) mf = fmaxf(mf, lw[k]);
-    const double m = (double)wave_max_all(mf);
+    mf = wave_max_all(mf);
+    const double m = isinf(mf) ? 0.0 : (double)mf;
     double total = 0.0;
     for (int k = lane; k < K; k += 64) total += exp((double)lw[k] - m);
     total = wave_sum_all(total);
     for (int t = 0; t < T; ++t) {
         double W = 0.0, a[4] = {0.0, 0.0, 0.0, 0.0};
+        int cnt = 0;
         for (int k = lane; k < K; k += 64) {
             if (nk[k] > t) {
                 const double w = exp((double)lw[k] - m);
                 const float4 x = *reinterpret_cast<const float4 *>(where + ((size_t)t * R + base + k) * 4);
+                cnt += w > 0.0 ? 1 : 0;
                 W += w;
                 a[0] += w * (double)x.x; a[1] += w * (double)x.y; a[2] += w * (double)x.z; a[3] += w * (double)x.w;
             }
         }
         W = wave_sum_all(W);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
         double mean[4], v[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int j = 0; j < 4; ++j) mean[j] = wave_sum_all(a[j]) / W;
@@ -155,7 +165,7 @@ __global__ __launch_bounds__(256) void particle_spread_kernel(const float *__res
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const double q = wave_sum_all(v[j]) / W;
-            v[j] = sqrt(q < 0.0 ? 0.0 : q);                        // (a NaN stays a NaN: W == 0)
+            v[j] = (cnt == 1 && q == q) ? 0.0 : sqrt(q < 0.0 ? 0.0 : q);   // (a NaN stays a NaN: W == 0, or a weight of +inf)
         }
         if (lane == 0) {
             const size_t o = (size_t)t * B + b;

@@ -13,6 +13,9 @@ latents the caller supplies (traversals, edits of `where`), `dream()` fills a da
 
 Philox bookkeeping of one call at state {seed, offset}: the latent noise takes quads [offset, offset + q_lat), the pixel noise
 quads [offset + q_lat, offset + q_lat + q_pix) (air_observe's counter_base = q_lat), the state then moves by q_lat + q_pix.
+
+air_observe and values that are not numbers: a NaN clamp bound switches the clamp off on that side only; a NaN canvas pixel stays NaN
+in the mean and leaves a finite clamp as its lower bound (as the upper one when only that is given), with and without noise.
 """
 import ctypes
 from typing import Dict

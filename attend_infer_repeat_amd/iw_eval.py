@@ -16,6 +16,16 @@ With z_t the sampled cumulative presence and n = sum_t z_t:
 The mask z_t is exact: the LSTM never sees the samples, so the presence probabilities do not depend on what / where, and
 latents of absent steps reach neither the canvas nor a later step -- they integrate out of numerator and denominator.
 This is a property of the model: use_prior, nsp_weight, nsp_analytic, use_reinforce, l2_weight and decay_rate do not enter.
+
+air_iw_reduce on log-weights that are not finite (held by tests/test_readout_kernels.py; the shift of the logsumexp is 0 when the
+maximum is infinite, and a NaN never becomes the maximum):
+
+    all K weights -inf   iw_bound = -inf   elbo = -inf   ess = NaN   q_n = NaN for every count
+    one weight +inf      iw_bound = +inf   elbo = +inf   ess = NaN   q_n = NaN at that particle's count, 0 at the others
+    one weight NaN       iw_bound = NaN    elbo = NaN    ess = NaN   q_n = NaN for every count
+
+Single particles at -inf have a weight of exactly 0 and only move elbo (to -inf).  A num_steps outside 0..T is counted in no q_n, which
+then sums to less than 1 by that particle's share.  The running totals add such values as they are.
 """
 import ctypes
 import dataclasses

@@ -14,7 +14,11 @@ appends launches of libair_hip.so (include/air_hip.h describes them):
   air_particle_select  k* per image (NaN scores never win; all NaN: k* = 0 and degenerate = 1) and bit copies of the selected rows of
                        where / what / presence_prob / the decoder's raw glimpses into B-row buffers;
   air_particle_spread  per step and image the weighted mean / standard deviation of `where` over the particles that have the step, and
-                       the weight share of those particles;
+                       the weight share of those particles (a step no particle has: mean / std NaN, share exactly 0; a step exactly
+                       one particle of non-zero weight has: its row, std exactly 0; an image whose weights are all -inf or hold a
+                       +inf or a NaN: mean / std NaN (a NaN weight: at the steps that particle has) and the share of the class of the tail sums of air_iw_reduce's count posterior --
+                       the reduce's convention, so `presence_iw` and `num_steps_posterior_iw` never disagree about such an image;
+                       `degenerate` flags the all-NaN image, these outputs are not usable for it either way);
   air_parse_objects    given-counts form on the selected rows (count = n_{k*}; score = q(n > t), count_prob = q(n_{k*}));
   air_parse_render, air_sum_leading   as in parse.SceneParser, on the selected rows and a B-row copy of the images.
 

@@ -150,12 +150,13 @@ AIR_ENGINE_API int air_canvas_unroll_fwd_bwd(const float *glimpse, const float *
  *                 AIR_WARP_WRITE_BWD      st_write_bwd_gs_kernel<RC, IM>          (vec4_glimpse, vec4_canvas)
  *                 AIR_WARP_FUSED          canvas_fused_gs_kernel<SPLIT>           (vec4_glimpse, vec4_canvas, NB, RB, n_split; items =
  *                                         forward workgroups + backward workgroups, n_fwd = the former)
+ *                 AIR_WARP_PARSE_RENDER   parse_render_kernel                     (vec4_glimpse, NB, RB; items = R * NB (image, band) units)
  *   items         work items the grid walks (images, glimpses, (image, band) or (t, b) units)
  *   fixed_cap     the grid is `items` while items <= fixed_cap (0: no such cap)
  *   resident_cap  1 when the launch asks the device for its resident workgroup count and caps the grid by it: items > fixed_cap, and
  *                 the image-major backward always (fixed_cap 0); the fused launch has neither cap, its grid is exactly `items`      */
 enum { AIR_WARP_READ_FWD = 0, AIR_WARP_READ_FWD_LEAN = 1, AIR_WARP_READ_BWD = 2, AIR_WARP_WRITE_FWD = 3, AIR_WARP_WRITE_BWD = 4,
-       AIR_WARP_FUSED = 5 };
+       AIR_WARP_FUSED = 5, AIR_WARP_PARSE_RENDER = 6 };
 typedef struct AirWarpForm {
     int kernel;
     int NT, VEC, R;
@@ -608,7 +609,9 @@ AIR_ENGINE_API int air_nvil_parts(const float *imp_parts, int n_parts, float *im
  *   order.  where / where_loc / where_scale must be 16-byte aligned (AIR_E_ALIGN).
  * air_iw_reduce: per image b over lw_k = logw[b*K + k], m = max_k lw_k, w_k = exp(lw_k - m):
  *   iw_bound[b] = m + log sum_k w_k - log K;  elbo[b] = mean_k lw_k;  ess[b] = (sum w)^2 / sum w^2;
- *   q_n_iw[b, c] = sum_k w_k [num_steps_k = c] / sum_k w_k  (c = 0..T).
+ *   q_n_iw[b, c] = sum_k w_k [num_steps_k = c] / sum_k w_k  (c = 0..T); a num_steps outside 0..T is counted nowhere.
+ *   Non-finite log-weights: an infinite m shifts by 0 and a NaN never becomes m.  All -inf: iw_bound = elbo = -inf, ess and q_n_iw
+ *   NaN.  One +inf: iw_bound = elbo = +inf, ess NaN, q_n_iw NaN at that particle's count and 0 elsewhere.  One NaN: all four NaN.
  *   acc (optional; DEVICE double[8]): acc[0..4] += {sum_b iw_bound, sum_b elbo, sum_b ess, #images with argmax_c q_n_iw == gt_steps
  *   (0 without gt_steps), B}, added in float64 in one fixed order by a single workgroup (a second kernel of the same call).      */
 AIR_ENGINE_API int air_iw_logweight(const float *what, const float *what_loc, const float *what_scale, const float *where,
@@ -634,7 +637,9 @@ AIR_ENGINE_API int air_iw_reduce(const float *logw, const int *num_steps, int T,
  * air_observe: mean = mult * canvas;  obs = clamp(mean + std * z_i, clamp_lo, clamp_hi) over n floats; a NaN bound = no clamp on
  *   that side.  z_i is BY DEFINITION element i of what air_rng_fill(normal, n, NULL, 0, {seed, offset + counter_base}) writes with
  *   state_dev = {seed, offset}: the noise is drawn in registers, one Philox call per four adjacent pixels, and never stored.
- *   std == 0: no draw (state_dev may be NULL), obs == mean bit for bit.  One of mean_out / obs_out may be NULL.  The offset is
+ *   std == 0: no draw (state_dev may be NULL), obs == clamp(mean) bit for bit.  One of mean_out / obs_out may be NULL (obs_out
+ *   NULL: no draw either).  A NaN canvas pixel stays NaN in mean_out and comes out of a finite clamp as clamp_lo (clamp_hi when only
+ *   that bound is given): fmaxf / fminf drop a NaN operand.  The offset is
  *   not advanced (air_rng_advance by (n + 3) / 4 behind it).                                                                     */
 AIR_ENGINE_API int air_prior_latents(const double *count_table_f64, const float *u_n, const int *num_objects_in, const float *eps_what,
                       const float *eps_where, float what_p_loc, float what_p_scale, float scale_p_loc, float scale_p_scale,
@@ -649,6 +654,8 @@ AIR_ENGINE_API int air_observe(const float *canvas, float mult, float std, const
  *   m_T = prod_i p_i (the arithmetic of air_numsteps_fwd) and q(n) = m_n / sum m.  n^ = the SMALLEST n attaining max_n m_n (the
  *   division does not enter the arg-max).  num_objects_in[R] (optional): n^ = that value clipped to 0..T, presence_prob is not
  *   consulted for the count (the convention of air_prior_latents) and may be NULL -- score and count_prob are then NaN.
+ *   A NaN probability at step k makes m_k and every later m NaN: n^ is then the arg-max over m_0 .. m_{k-1} (a NaN never wins), and
+ *   count_prob and every score of that image are NaN.
  *   Per step and image: presence[t,r] = t < n^ ? 1 : 0;  score[t,r] = sum_{n>t} q(n), fp32, added from n = T down (the step weight
  *   air_numsteps_fwd writes);  boxes[t,r,:] = (left, top, width, height) = (W (1 - sx + tx) / 2, H (1 - sy + ty) / 2, W sx, H sy) of
  *   where[t,r] = [sx, tx, sy, ty], in fp32, in that operation order.  Per image: num_objects[r] = n^, count_prob[r] = (float) q(n^).
@@ -663,7 +670,8 @@ AIR_ENGINE_API int air_observe(const float *canvas, float mult, float std, const
  *   row band's share of the reconstruction term of air_rec_loglik_fwd, to be added in band order (air_sum_leading); n_bands as for
  *   air_canvas_unroll_fwd_banded.  owner[R,H,W] (int8) = the smallest present t attaining max_t mult * layer_t(p) if that maximum is
  *   > mask_threshold, else -1;  area[T,R] (int32) = number of pixels step t owns (integer adds; the entry zeroes the buffer itself);
- *   layers[T,R,H,W] (optional) = mult * layer_t, zeros for absent steps.  T <= 32; where 16-byte aligned (AIR_E_ALIGN).          */
+ *   layers[T,R,H,W] (optional) = mult * layer_t, zeros for absent steps.  A NaN glimpse cell reaches the pixels whose four taps
+ *   include it; a NaN layer never owns a pixel.  T <= 32; where 16-byte aligned (AIR_E_ALIGN).                                  */
 AIR_ENGINE_API int air_parse_objects(const float *presence_prob, const int *num_objects_in, const float *where, const float *what,
                       int T, int R, int A, int H, int W, int *num_objects, float *count_prob, float *presence, float *score,
                       float *boxes, int *offsets, int *obj_image, int *obj_step, float *obj_box, float *obj_score,
@@ -671,6 +679,13 @@ AIR_ENGINE_API int air_parse_objects(const float *presence_prob, const int *num_
 AIR_ENGINE_API int air_parse_render(const float *glimpse, const float *where, const float *presence, const float *obs, float mult,
                      float std, float mask_threshold, int T, int R, int H, int W, int h, int w, int n_bands,
                      float *reconstruction, float *rec_parts, signed char *owner, int *area, float *layers, void *stream);
+/* WHICH form air_parse_render runs for these shapes and ADDRESSES (AirWarpForm above: kernel = AIR_WARP_PARSE_RENDER, NB, RB, threads,
+ * lds_bytes, vec4_glimpse, items = R * NB, fixed_cap, resident_cap: the grid is min(items, fixed_cap), or min(items, the device's
+ * resident workgroup count) when resident_cap is 1).  Host only: no launch, nothing dereferenced; the status is the one
+ * air_parse_render returns before its first device call.  The launch consumes this decision.                                       */
+AIR_ENGINE_API int air_parse_render_form(const float *glimpse, const float *where, const float *presence, const float *obs,
+                     const float *reconstruction, const float *rec_parts, const signed char *owner, const int *area, int T, int R,
+                     int H, int W, int h, int w, int n_bands, AirWarpForm *out);
 
 /* ---- best-of-K scene parsing: read-outs behind a K-tiled forward pass (R = K * B rows, row r = b * K + k) and air_iw_logweight.
  * T <= 32; K arbitrary.  No atomics, one fixed summation order: the same bits run to run.
@@ -686,8 +701,12 @@ AIR_ENGINE_API int air_parse_render(const float *glimpse, const float *where, co
  *   vectors where A resp. G is a multiple of 4 and the buffers are 16-byte aligned, 4-byte words otherwise).
  * air_particle_spread: per image with m = max_k log_w, w_k = exp(log_w_k - m) in float64, and per step t with S_t = {k : num_steps_k > t},
  *   W = sum_{S_t} w_k:  where_mean[t,b,:] = sum_{S_t} w_k where[t,b*K+k,:] / W;  where_std = sqrt(max(0, sum_{S_t} w_k (where - mean)^2
- *   / W)) (two passes);  presence_iw[t,b] = W / sum_k w_k.  W == 0: mean and std are NaN, presence_iw 0.  where / where_mean /
- *   where_std 16-byte aligned (AIR_E_ALIGN).                                                                                      */
+ *   / W)) (two passes);  presence_iw[t,b] = W / sum_k w_k.  W == 0: mean and std are NaN, presence_iw 0.  A step that exactly one
+ *   particle of non-zero weight has: the mean is that particle's row and where_std exactly 0.  Non-finite log-weights follow
+ *   air_iw_reduce (an infinite maximum shifts by 0): all -inf or one +inf give NaN means and spreads for that image, one NaN at every
+ *   step that particle has, and presence_iw of the class of the tail sums of q_n_iw (NaN; NaN for the steps the +inf particle has and 0
+ *   behind them; NaN).
+ *   where / where_mean / where_std 16-byte aligned (AIR_E_ALIGN).                                                                 */
 AIR_ENGINE_API int air_iw_logposterior(const float *what, const float *what_loc, const float *what_scale, const float *where,
                         const float *where_loc, const float *where_scale, const float *presence, const float *logp,
                         int T, int R, int K, int A, float *log_q, void *stream);
