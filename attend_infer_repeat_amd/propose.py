@@ -7,7 +7,8 @@ what is left, and let the generative model decide -- by the same exact arg-max o
 steps belong in the scene.  One round, on the `current rows` (round 0: the provider's start rows; later: the first T rows the previous
 round left):
 
-  1. residual   res = clamp(x - mult * canvas of the rows t < n_b) into [0, clamp_hi], x always the ORIGINAL image;
+  1. residual   res = clamp(x - mult * canvas of the rows t < n_b) into [0, clamp_hi], x always the ORIGINAL image (a NaN pixel of x
+                gives exactly 0; clamp_hi = +inf or NaN clamps nothing above: res = max(d, 0));
   2. forward    the engine's forward plan at the mode on res, from the fresh initial state: its steps 0 .. P-1 are the proposals
                 (what, where, raw glimpse, and as score the step weight of that pass; its presence chain does not gate them);
   3. pool       C = T + P <= 6 candidate rows: the T current rows, then the P proposals (bit copies), pool_presence = the current

@@ -811,7 +811,8 @@ AIR_ENGINE_API int air_prune_relabel(const float *score_src, const int *kept_ste
  * air_propose_residual: canvas(p) = 0 + layer_t(p) for t = 0 .. n_b - 1 in step order, layer_t = st_write(glimpse_t, where_t) with the
  *   per-pixel operations of air_parse_render (the same taps, the same bilinear form, contraction off: the bits of that entry's canvas
  *   for the presence chain t < n_b);  d = obs_p - mult * canvas(p) in fp32;  res[R,H,W]: res_p = d > 0 ? min(d, clamp_hi) : 0 (a NaN
- *   gives 0).  res_parts[n_bands,R] (optional): each row band's sum of res_p^2 (air_canvas_unroll_bands' banding; inside a band a
+ *   d -- a NaN observation or canvas pixel -- gives exactly 0).  clamp_hi = +inf clamps nothing; a NaN clamp_hi clamps nothing
+ *   either (fminf drops a NaN operand): res_p = max(d, 0).  res_parts[n_bands,R] (optional): each row band's sum of res_p^2 (air_canvas_unroll_bands' banding; inside a band a
  *   fixed order of the kernel's own), to be added in band order (air_sum_leading).  Nothing else is written.  One 256-thread
  *   workgroup per (image, band).  AIR_E_SHAPE: T outside 1..6, non-positive sizes, n_bands != air_canvas_unroll_bands(R, H);
  *   AIR_E_ALIGN: where not 16-byte aligned, or any other pointer (glimpse, presence, num_objects_in, obs, res, res_parts) not 4-byte
