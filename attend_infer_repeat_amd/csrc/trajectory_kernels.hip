@@ -13,6 +13,12 @@
 #define TRAJ_MAXT 32                     // TRACK_MAXT: objects per frame, live tracks per sequence, rows of the completed table
 #define TRAJ_MAX_IDS 32767               // TRACK_MAX_IDS
 #define TRAJ_MAX_HORIZON 16
+// the supported noise domain (include/air_hip.h states it and where it was measured): outside it the call is refused
+#define TRAJ_Q_OVER_R_MIN 1e-29          // q_shift / r and q_scale / r, both
+#define TRAJ_Q_OVER_R_MAX 1e15
+#define TRAJ_V_OVER_R_MAX 1e6            // velocity_var / r (0 is inside)
+#define TRAJ_R_MIN 1e-146
+#define TRAJ_R_MAX 1e134
 #define TRAJ_WS_DOUBLES 28               // per (row, frame): 4 x (x, v, x-, v-), 2 noise classes x (P, P-) of three values each
 
 enum { TRAJ_ABSENT = 0, TRAJ_OBSERVED = 1, TRAJ_FILLED = 2, TRAJ_FORECAST = 3 };
@@ -89,6 +95,16 @@ __device__ __forceinline__ TrajCov traj_predict_cov(const TrajCov p, double q, d
             vs[c] = w[(WS_V + c) * plane] + (C10[cl] * dx + C11[cl] * dv);                                                    \
         }                                                                                                                     \
     }
+
+// the rule's arguments, one-shot and stream alike (host code; a NaN fails every comparison)
+static int traj_noise_check(double q_shift, double q_scale, double r, double velocity_var) {
+    AIR_REQUIRE(q_shift > 0.0 && q_scale > 0.0 && r > 0.0 && velocity_var >= 0.0, AIR_E_SHAPE);
+    AIR_REQUIRE(r >= TRAJ_R_MIN && r <= TRAJ_R_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(q_shift / r >= TRAJ_Q_OVER_R_MIN && q_shift / r <= TRAJ_Q_OVER_R_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(q_scale / r >= TRAJ_Q_OVER_R_MIN && q_scale / r <= TRAJ_Q_OVER_R_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(velocity_var / r <= TRAJ_V_OVER_R_MAX, AIR_E_SHAPE);
+    return AIR_OK;
+}
 
 // Every output of the sequence starts ABSENT; the lanes of the spanning tracks overwrite their rows behind a barrier.
 __device__ __forceinline__ void traj_fill_absent(const TrajSmoothArgs &a, int s, int tid) {
@@ -340,7 +356,7 @@ extern "C" int air_track_smooth(const float *where, const int *num_objects, cons
     AIR_REQUIRE((long)F * T <= TRAJ_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
     const long want_c = (long)T * ((long)max_age + 1) < TRAJ_MAXT ? (long)T * ((long)max_age + 1) : TRAJ_MAXT;
     AIR_REQUIRE((long)C == want_c && (long)C * R <= (long)INT_MAX / 4, AIR_E_SHAPE);
-    AIR_REQUIRE(q_shift > 0.0 && q_scale > 0.0 && r > 0.0 && velocity_var >= 0.0, AIR_E_SHAPE);      // (a NaN fails every comparison)
+    AIR_REQUIRE(traj_noise_check(q_shift, q_scale, r, velocity_var) == AIR_OK, AIR_E_SHAPE);
     AIR_REQUIRE(ws_bytes >= air_track_smooth_workspace_bytes(C, R), AIR_E_WORKSPACE);
     AIR_REQUIRE(air_aligned16(where) && air_aligned16(sm_where) && air_aligned16(sm_boxes) &&
                 (Hz == 0 || (air_aligned16(fc_where) && air_aligned16(fc_boxes))), AIR_E_ALIGN);
@@ -769,7 +785,7 @@ extern "C" int air_track_smooth_stream(const float *where, const int *num_object
     AIR_REQUIRE(st == AIR_OK, st);
     AIR_REQUIRE((long)F * T <= TRAJ_MAX_IDS && (long)C * R <= (long)INT_MAX / 4, AIR_E_SHAPE);
     AIR_REQUIRE((long)D >= (long)F + L + max_age, AIR_E_SHAPE);    // the ring: frame a - L - max_age is read, a + F - 1 written
-    AIR_REQUIRE(q_shift > 0.0 && q_scale > 0.0 && r > 0.0 && velocity_var >= 0.0, AIR_E_SHAPE);      // (a NaN fails every comparison)
+    AIR_REQUIRE(traj_noise_check(q_shift, q_scale, r, velocity_var) == AIR_OK, AIR_E_SHAPE);
     AIR_REQUIRE(air_aligned16(where), AIR_E_ALIGN);
     const uintptr_t bits = reinterpret_cast<uintptr_t>(num_objects) | reinterpret_cast<uintptr_t>(track_id) |
                            reinterpret_cast<uintptr_t>(valid) | reinterpret_cast<uintptr_t>(sm_counts) |

@@ -20,6 +20,10 @@ for sx, sy; q4 = 0.25 q, q2 = 0.5 q; r the measurement noise.
            v-[f+1], xs[f] = x + (C00 dx + C01 dv), vs[f] = v + (C10 dx + C11 dv).
 Two exact consequences: a track with one sighting returns its `where` bits, and a track whose sightings all carry one value returns
 that value bit for bit with v = 0.
+The noise terms must lie in THE SUPPORTED DOMAIN (Q_OVER_R_MIN .. R_MAX below): inside it the rule gives the posterior mean of the
+model to well under one float32 rounding of an output (measured against an exact solve: tests/smoother_cases.py, DESIGN.md section 19);
+outside it the differences P- - k P- and the quotients by det lose digits and then turn NaN, so `check_arguments` raises and the
+entries return AIR_E_SHAPE (the numpy restatements alone still run there: the domain was measured with them).  A user who does not know the velocity writes velocity_var = V_OVER_R_MAX * measurement_noise.
 
 The completed table has C = min(32, T (max_age + 1)) rows per frame: in frame f the tracks with first <= f <= last take rows
 0 .. n_f - 1 in ascending id (sm_where, sm_boxes, sm_id, sm_state, sm_src_frame, sm_src_slot, sm_velocity, sm_count, sm_counts).  The
@@ -83,6 +87,12 @@ MAX_LAG = 16                                                       # a stream sm
 ABSENT, OBSERVED, FILLED, FORECAST = range(4)
 STATES = ("absent", "observed", "filled", "forecast")
 DEFAULTS = dict(process_noise=(1e-4, 1e-4), measurement_noise=4e-4, velocity_var=0.04)
+# THE SUPPORTED NOISE DOMAIN (csrc: TRAJ_Q_OVER_R_MIN .. TRAJ_R_MAX; DESIGN.md section 19 has the measurement).  The rule's float64
+# chain forms covariance differences P- - k P- and a 2 x 2 inverse through det = Pxx- Pvv- - Pxv- Pxv-: it delivers the posterior mean
+# to well under one float32 rounding of the output inside this box and loses digits, then turns NaN, outside it.  Outside: refused.
+Q_OVER_R_MIN, Q_OVER_R_MAX = 1e-29, 1e15                           # process_noise / measurement_noise, each class
+V_OVER_R_MAX = 1e6                                                 # velocity_var / measurement_noise (0 is inside)
+R_MIN, R_MAX = 1e-146, 1e134                                       # measurement_noise
 
 
 def completed_rows(max_steps, max_age) -> int:
@@ -92,8 +102,11 @@ def completed_rows(max_steps, max_age) -> int:
 
 
 def check_arguments(max_steps, n_frames, n_rows=None, max_age=1, horizon=0, process_noise=DEFAULTS["process_noise"],
-                    measurement_noise=DEFAULTS["measurement_noise"], velocity_var=DEFAULTS["velocity_var"]):
-    """Refuse what air_track_smooth refuses (pure host code).  Returns (T, F, S, C, Hz, (q_shift, q_scale), r, velocity_var)."""
+                    measurement_noise=DEFAULTS["measurement_noise"], velocity_var=DEFAULTS["velocity_var"], domain=True):
+    """Refuse what air_track_smooth refuses (pure host code).  Returns (T, F, S, C, Hz, (q_shift, q_scale), r, velocity_var).
+    domain=False keeps every check but the supported noise domain: `reference_smooth` and `reference_smooth_stream` pass it, because
+    the restatement has to say what the rule's statements give for ANY positive noise -- the measurement of the domain, and the exact
+    consequences that hold whatever the noise, run it where the device entries refuse.  Everything that launches uses domain=True."""
     T, F, S = check_track_arguments(max_steps, n_frames, n_rows, max_age=max_age)
     try:
         q = tuple(float(v) for v in process_noise)
@@ -106,6 +119,17 @@ def check_arguments(max_steps, n_frames, n_rows=None, max_age=1, horizon=0, proc
         raise ValueError("measurement_noise must be a positive number, got %r" % (measurement_noise,))
     if not vv >= 0.0:
         raise ValueError("velocity_var must be a number >= 0, got %r" % (velocity_var,))
+    if not domain:
+        pass
+    elif not R_MIN <= r <= R_MAX:
+        raise ValueError("measurement_noise must lie within R_MIN..R_MAX = %g..%g, got %r" % (R_MIN, R_MAX, measurement_noise))
+    elif not all(Q_OVER_R_MIN <= v / r <= Q_OVER_R_MAX for v in q):
+        raise ValueError("process_noise / measurement_noise must lie within Q_OVER_R_MIN..Q_OVER_R_MAX = %g..%g (the float64 rule "
+                         "loses the posterior mean outside), got %r / %r" % (Q_OVER_R_MIN, Q_OVER_R_MAX, process_noise, measurement_noise))
+    elif not vv / r <= V_OVER_R_MAX:
+        raise ValueError("velocity_var / measurement_noise must be at most V_OVER_R_MAX = %g (the float64 rule loses the posterior "
+                         "mean beyond; an unknown velocity is velocity_var = V_OVER_R_MAX * measurement_noise), got %r / %r"
+                         % (V_OVER_R_MAX, velocity_var, measurement_noise))
     if isinstance(horizon, bool) or int(horizon) != horizon or not 0 <= int(horizon) <= MAX_HORIZON:
         raise ValueError("horizon must be an integer within 0..%d, got %r" % (MAX_HORIZON, horizon))
     return T, F, S, completed_rows(T, max_age), int(horizon), q, r, vv
@@ -200,13 +224,18 @@ def reference_smooth(where, num_objects, track_id, num_tracks, track_first, trac
     where [T, R, 4] fp32, num_objects [R], track_id [T, R], num_tracks [S], track_first / track_last [S, F T], R = S n_frames.
     Returns sm_where, sm_boxes [C, R, 4] float32, sm_id [C, R] int32, sm_state [C, R] int8, sm_src_frame, sm_src_slot [C, R] int32,
     sm_velocity [C, R, 2] float32, sm_count [R], sm_counts [S, 3] int32, the same with fc_ and [C, S Hz] for the forecast table
-    (fc_count [S Hz]), and sm_what / sm_glimpse / sm_score / fc_what / fc_glimpse / fc_score when the rows to copy are given."""
+    (fc_count [S Hz]), and sm_what / sm_glimpse / sm_score / fc_what / fc_glimpse / fc_score when the rows to copy are given.
+    Tables no tracker writes (the entry takes any integers; include/air_hip.h pins the same): num_tracks is clipped to 0 .. F T, a track
+    with first < 0, first > last or last >= F is skipped, a table row no slot names is a track without sightings (FILLED from z = 0),
+    of two slots that carry one id the lowest is read, and a row counts the ids below whose `last` reaches the frame whatever their
+    `first`.  The device keeps the 32 lowest such ids per track, as a tracker's live table does: with a 33rd, the rows are the
+    device's only in the frames the ids beyond the 32 lowest do not reach."""
     import numpy as np
     from .tile import scene_boxes
     where = np.asarray(where, np.float32)
     T, R = where.shape[:2]
     T, F, S, C, Hz, (q_shift, q_scale), r, vv = check_arguments(T, n_frames, R, max_age, horizon, process_noise, measurement_noise,
-                                                                velocity_var)
+                                                                velocity_var, domain=False)
     H, W = (int(v) for v in img_size)
     ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
     FT, N = F * T, S * Hz
@@ -287,11 +316,11 @@ def ring_depth(chunk_frames, lag, max_age) -> int:
 
 def check_stream_arguments(max_steps, chunk_frames, n_rows=None, max_age=1, lag=None, horizon=0,
                            process_noise=DEFAULTS["process_noise"], measurement_noise=DEFAULTS["measurement_noise"],
-                           velocity_var=DEFAULTS["velocity_var"]):
+                           velocity_var=DEFAULTS["velocity_var"], domain=True):
     """Refuse what air_track_smooth_stream refuses (pure host code).  lag=None: max_age.  Returns (T, F, S, C, L, Hz, D, (q_shift,
-    q_scale), r, velocity_var)."""
+    q_scale), r, velocity_var).  domain: as `check_arguments`."""
     T, F, S, C, Hz, q, r, vv = check_arguments(max_steps, chunk_frames, n_rows, max_age, horizon, process_noise, measurement_noise,
-                                               velocity_var)
+                                               velocity_var, domain)
     lag = int(max_age) if lag is None else lag
     if isinstance(lag, bool) or int(lag) != lag or not int(max_age) <= int(lag) <= MAX_LAG:
         raise ValueError("lag must be an integer within max_age..%d = %d..%d (a track that coasts over a frame must be retired, or "
@@ -451,7 +480,7 @@ def reference_smooth_stream(state, where, num_objects, track_id, n_frames, valid
     where = np.asarray(where, np.float32)
     T, R = where.shape[:2]
     T, F, S, C, L, Hz, D, (q_shift, q_scale), r, vv = check_stream_arguments(T, n_frames, R, max_age, lag, horizon, process_noise,
-                                                                             measurement_noise, velocity_var)
+                                                                             measurement_noise, velocity_var, domain=False)
     H, W = (int(v) for v in img_size)
     ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
     v_in = check_valid(valid, S, F)

@@ -1068,7 +1068,22 @@ AIR_ENGINE_API int air_track_score(const float *boxes, const int *num_objects, c
  *   `last`:  tx' = x + (double) m v rounded once, ty' alike;  sx, sy = the values at `last` (scales are held).  fc_state = 3 FORECAST,
  *   fc_src_frame / fc_src_slot = the last sighting, fc_boxes as sm_boxes, fc_velocity from the filtered v at `last`, fc_count[S Hz].
  *   With Hz == 0 the fc_ pointers are not touched and may be NULL.
- *   AIR_E_SHAPE also: q_shift, q_scale or r not > 0, velocity_var not >= 0 (NaN included).  where / sm_where / sm_boxes / fc_where /
+ *   AIR_E_SHAPE also: q_shift, q_scale or r not > 0, velocity_var not >= 0 (NaN included), or the noise terms outside THE SUPPORTED
+ *   DOMAIN  1e-146 <= r <= 1e134,  1e-29 <= q_shift / r <= 1e15 and q_scale / r alike,  velocity_var / r <= 1e6  (the quotients as
+ *   float64 divisions).  The chain above forms the differences P- - k P- and the quotients by det; measured against the exact posterior
+ *   mean of the model (prior x ~ N(z, r), v ~ N(0, velocity_var); process noise (1/2, 1) w, w ~ N(0, q); sightings z = x + N(0, r)), in
+ *   units of 2^-24 max|z| of the track, over spans of 2 .. 64 frames and gaps of 0 .. 40: inside the domain its worst float64 error is
+ *   3.5e-3 units (at velocity_var / r = 1e6; the forecast 16 frames ahead 1.0e-4), so every fp32 output is within one ulp of the
+ *   rounded exact value; at velocity_var / r = 1e7 it is 0.06, at 1e8 0.38, at 1e9 3.1, at 1e12 3.8e3, from 1e16 on NaN; q / r from
+ *   1e17 on is NaN at velocity_var = 0; r = 1e-148 and below or 1e136 and above under- or overflows the products in det (NaN).  Each
+ *   limit lies one decade inside the last decade that held 0.25 units (tests/smoother_cases.py has the sweep, DESIGN.md section 19 its
+ *   table); the lower limit of q / r is where the measurement ended (1e-30), not a failure.  Both stream entries below refuse the same.
+ *   TABLES NO TRACKER WRITES.  The entry takes any integers: num_tracks is clipped to 0 .. F T; a track with first < 0, first > last or
+ *   last >= F is skipped; a table row no slot names is a track without sightings (FILLED rows from z = 0, as above); of two slots that
+ *   carry one id the lowest is read.  A track's row counts the ids below it whose `last` reaches the frame, whatever their `first`;
+ *   the device keeps the 32 lowest such ids that reach the track's own first frame (a tracker's live table holds no more), so with a
+ *   33rd the rows are specified only in the frames that the ids beyond the 32 lowest do not reach.
+ *   where / sm_where / sm_boxes / fc_where /
  *   fc_boxes 16-byte, ws / sm_velocity / fc_velocity 8-byte, everything else 4-byte aligned (AIR_E_ALIGN).  One workgroup of one wavefront
  *   per sequence, one lane per track id, in passes of 64 ids when num_tracks exceeds the workgroup.
  * air_track_fill: for a table of C rows and N columns (the completed table: N = R, per_seq = F; the forecast table: N = S Hz,

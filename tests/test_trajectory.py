@@ -180,7 +180,12 @@ def test_a_refused_call_writes_nothing(gpu_device):
                      (dict(velocity_var=-1e-9), -2), (dict(velocity_var=nan), -2), (dict(Hz=17), -2), (dict(Hz=-1), -2), (dict(C=5), -2),
                      (dict(C=7), -2), (dict(T=0), -2), (dict(T=33), -2), (dict(R=11), -2), (dict(S=0), -2), (dict(F=0), -2),
                      (dict(max_age=-1), -2), (dict(where=None), -1), (dict(track_id=None), -1), (dict(sm_where=None), -1),
-                     (dict(fc_boxes=None), -1), (dict(ws=None), -1), (dict(ws_bytes=8), -4), (dict(where=Hh._p(off[1:])), -3)):
+                     (dict(fc_boxes=None), -1), (dict(ws=None), -1), (dict(ws_bytes=8), -4), (dict(where=Hh._p(off[1:])), -3),
+                     # outside the supported noise domain (r = 4e-4): velocity_var / r > 1e6, q / r > 1e15, q / r < 1e-29, r out of range
+                     (dict(velocity_var=1e6), -2), (dict(velocity_var=401.0), -2), (dict(q_shift=4.1e11), -2), (dict(q_scale=1e-33), -2),
+                     (dict(q_shift=1.0, q_scale=1.0, r=3e-17, velocity_var=0.0), -2),
+                     (dict(q_shift=1e-300, q_scale=1e-300, r=1e-300, velocity_var=0.0), -2),
+                     (dict(q_shift=1e140, q_scale=1e140, r=1e140, velocity_var=1e140), -2)):
         st, got, clean, fill, _ = run_smooth(case, 3, **kw)
         assert st == code, (kw, st)
         assert clean and all((got[k] == fill[k]).all() for k in got), kw

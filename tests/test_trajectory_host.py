@@ -30,7 +30,13 @@ def test_check_arguments():
                      (dict(process_noise=(nan, 1e-4)), "process_noise"), (dict(process_noise=1e-4), "process_noise"),
                      (dict(measurement_noise=0.0), "measurement_noise"), (dict(measurement_noise=nan), "measurement_noise"),
                      (dict(velocity_var=-1e-9), "velocity_var"), (dict(velocity_var=nan), "velocity_var"), (dict(horizon=17), "horizon"),
-                     (dict(horizon=-1), "horizon"), (dict(horizon=1.5), "horizon"), (dict(max_age=-1), "max_age")):
+                     (dict(horizon=-1), "horizon"), (dict(horizon=1.5), "horizon"), (dict(max_age=-1), "max_age"),
+                     # outside the supported noise domain: the rule loses the posterior mean there
+                     (dict(velocity_var=1e6), "V_OVER_R_MAX"), (dict(velocity_var=401.0), "V_OVER_R_MAX"),
+                     (dict(process_noise=(1.0, 1.0), measurement_noise=3e-17, velocity_var=0.0), "Q_OVER_R_MAX"),
+                     (dict(process_noise=(1e-4, 1e-33)), "Q_OVER_R_MIN"), (dict(process_noise=(4.1e11, 1e-4)), "Q_OVER_R_MAX"),
+                     (dict(process_noise=(1e-300,) * 2, measurement_noise=1e-300, velocity_var=0.0), "R_MIN"),
+                     (dict(process_noise=(1e140,) * 2, measurement_noise=1e140), "R_MAX")):
         with pytest.raises(ValueError, match=word):
             trajectory.check_arguments(3, 8, 16, **kw)
     with pytest.raises(ValueError, match="max_steps"):
@@ -40,6 +46,7 @@ def test_check_arguments():
     with pytest.raises(ValueError, match="multiple"):
         trajectory.check_arguments(3, 8, 15)
     assert trajectory.check_arguments(3, 8, 16, velocity_var=0.0)[-1] == 0.0
+    assert trajectory.check_arguments(3, 8, 16, velocity_var=400.0)[-1] == 400.0      # velocity_var / measurement_noise = 1e6: the limit
 
 
 @pytest.mark.parametrize("max_age,seed", [(1, 0), (2, 1), (0, 2), (3, 3)])

@@ -207,7 +207,12 @@ def test_argument_refusals():
                dict(horizon=0.5), dict(valid=[1, 1]), dict(valid=np.array([1.0])), dict(valid=np.array([[1]]))):
         with pytest.raises(ValueError):
             call(**kw)
-    for kw in (dict(lag=0, max_age=2), dict(lag=17, max_age=1), dict(lag=1, max_age=1, horizon=17)):
+    for kw in (dict(lag=0, max_age=2), dict(lag=17, max_age=1), dict(lag=1, max_age=1, horizon=17),
+               # outside the supported noise domain, as air_track_smooth_stream refuses it
+               dict(velocity_var=1e6), dict(velocity_var=401.0), dict(process_noise=(4.1e11, 1e-4)), dict(process_noise=(1e-4, 1e-33)),
+               dict(process_noise=(1.0, 1.0), measurement_noise=3e-17, velocity_var=0.0),
+               dict(process_noise=(1e-300,) * 2, measurement_noise=1e-300, velocity_var=0.0),
+               dict(process_noise=(1e140,) * 2, measurement_noise=1e140)):
         with pytest.raises(ValueError):
             trajectory.check_stream_arguments(3, 4, 8, **kw)
     assert trajectory.check_stream_arguments(3, 4, 8, max_age=1, lag=16, horizon=16)[:7] == (3, 4, 2, 6, 16, 16, 21)
