@@ -257,6 +257,8 @@ SIGNATURES = {
                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, P, c_size_t, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                  P, P, P, P]),
     "air_track_fill": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "air_track_noise_stats": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, ctypes.c_double, P, P, P, P, P]),
+    "air_track_noise_reduce": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "air_track_smooth_stream_state_bytes": (c_size_t, [c_int, c_int]),
     "air_track_stash": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
     "air_track_smooth_stream": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

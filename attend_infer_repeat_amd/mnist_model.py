@@ -494,6 +494,43 @@ class AIRonMNIST(AIRModel):
         stack = self._cache("trackers").get(key, build)
         return (stack[-1], None) if key.smooth is None else (stack[-2], stack[-1])
 
+    def noise_fitter(self, n_sequences, n_frames, shift_ratios=None, scale_ratios=None, velocity_ratio=None, **track_args):
+        """the trajectory.TrajectoryNoiseFitter behind `fit_track_noise`: last in a cached stack of its own (stacks.fit_key, in the
+        cache of `tracker`: it counts against MAX_TRACKERS) whose track.SequenceTracker it is bound to; `track_args` are `tracker`'s
+        without smooth=.  Built and captured on first use."""
+        key = stacks.fit_key(stacks.require_engine(self, "fit_track_noise"), n_sequences, n_frames, shift_ratios, scale_ratios,
+                             velocity_ratio, **track_args)
+
+        def build():
+            from .track import SequenceTracker
+            from .trajectory import TrajectoryNoiseFitter
+            stack = self._own_stack(key.S * key.F, key.stack, key.F)
+            stack.append(SequenceTracker(stack[-1], key.F, matching=key.matching, **dict(key.assoc)))
+            stack.append(TrajectoryNoiseFitter(stack[-1], *key.fit))
+            return stacks.captured(stack)
+        return self._cache("trackers").get(key, build)[-1]
+
+    def fit_track_noise(self, frames, shift_ratios=None, scale_ratios=None, velocity_ratio=None, zoom=0, accumulate=False, fit=True,
+                        **track_args):
+        """The trajectory smoother's noise terms by maximum likelihood from the tracks of frames [S, F, H, W] themselves -- no ground
+        truth: the frames are tracked as `track(frames, **track_args)` tracks them, and the likelihood of every track's sightings
+        under the constant-rate model is evaluated on the device on a grid of candidates (trajectory.TrajectoryNoiseFitter; None:
+        half-decades of process noise / measurement noise from 1e-6 to 1e3 and the default velocity_var / measurement_noise).
+        Returns trajectory.profile_fit's dict: process_noise, measurement_noise, velocity_var -- `track(frames, smooth={k: fit[k] for
+        k in trajectory.FIT_KEYS})` takes them as they are --, loglik, n_innovations, cell, on_edge, surface (and the grid they refer
+        to).  zoom=k refines the grid k times around the best cell.  accumulate=True adds the frames to those of the calls before
+        (`noise_fitter(...).reset()` starts over; zoom needs a single batch), fit=False only does that: no read-back, returns None.
+        The training engine's parameters are read, nothing of it is written."""
+        frames = torch.as_tensor(frames)
+        if frames.dim() != 4:
+            raise ValueError("fit_track_noise: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
+        f = self.noise_fitter(frames.shape[0], frames.shape[1], shift_ratios, scale_ratios, velocity_ratio, **track_args)
+        self._sync_engine_switches()
+        f.load_from(self._engine)                            # every time: the weights move
+        self.tracked = f.track(frames, accumulate=bool(accumulate))
+        self.track_noise_fit = f.fit(zoom) if fit else None
+        return self.track_noise_fit
+
     def stream_tracker(self, n_sequences, chunk_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None,
                        refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None):
         """the track.StreamTracker behind `track_stream`: identities over sequences of any length, fed in chunks of `chunk_frames`

@@ -131,6 +131,11 @@ def main(argv=None):
                          "Kalman filter and a backward pass per track) and score the completed table next to the raw one.  QS,QC,R: the "
                          "process noise of the shifts and of the scales and the measurement noise, in `where` units (default "
                          "1e-4,1e-4,4e-4: provisional, unmeasured on a trained model)")
+    ap.add_argument("--track-fit-noise", nargs="?", const=0, default=None, type=int, metavar="ZOOM",
+                    help="with --track-eval: fit the trajectory smoother's noise terms to the tracks of the same sequences by maximum "
+                         "likelihood on the device (AIRonMNIST.fit_track_noise: no ground truth is read) and log them as "
+                         "<name>_track_noise_fit with loglik / n_innovations and the same figure at the current defaults; ZOOM > 0 "
+                         "refines the grid ZOOM times around the best cell (needs --eval-batches 1)")
     ap.add_argument("--track-matching", choices=("greedy", "optimal"), default=None,
                     help="with --track-eval: how a frame's objects are matched to the live tracks (track.SequenceTracker's matching): "
                          "greedy (the default) or the optimal assignment of the whole frame (Hungarian, air_track_associate_optimal)")
@@ -241,6 +246,11 @@ def main(argv=None):
         if len(lag_hz) not in (1, 2) or not 0 <= lag_hz[0] <= 16 or not 0 <= (lag_hz + [0])[1] <= 16:
             ap.error("--track-stream-smooth needs LAG[,HZ] with LAG and HZ within 0..16, got %r" % args.track_stream_smooth)
         stream_smooth = dict(lag=lag_hz[0], horizon=(lag_hz + [0])[1])
+    if args.track_fit_noise is not None:
+        if track_eval is None:
+            ap.error("--track-fit-noise goes with --track-eval")
+        if args.track_fit_noise < 0 or (args.track_fit_noise > 0 and args.eval_batches > 1):
+            ap.error("--track-fit-noise needs ZOOM >= 0, and ZOOM > 0 needs --eval-batches 1 (the zoom re-runs on one batch's tracks)")
     track_smooth = None
     if args.track_smooth is not None or args.track_predict is not None:
         if track_eval is None:
@@ -424,11 +434,44 @@ def main(argv=None):
                     temporal=track_temporal, matching=args.track_matching, **refine_kw)
                 stream_log = lambda *a, **kw: (plain_log(*a, **kw), smooth_log(*a, **kw))[0]
 
+        fit_log = None
+        if args.track_fit_noise is not None:
+            from attend_infer_repeat_amd import trajectory as tj
+            D = tj.DEFAULTS
+            at_defaults = tuple(q / D["measurement_noise"] for q in D["process_noise"])
+            grid = tuple(sorted(set(tj.DEFAULT_FIT_RATIOS + at_defaults)))      # the defaults' own ratios are candidates too
+
+            def fit_log(train_itr):
+                n = min(max(args.eval_batches, 1), seq_data["imgs"].shape[0] // sequences_per_batch)
+                kw = dict(temporal=track_temporal, matching=args.track_matching, **refine_kw)
+                rec = dict(step=train_itr, data="test_track_noise_fit", zoom=args.track_fit_noise)
+                try:
+                    for b in range(n):
+                        sl = slice(b * sequences_per_batch, (b + 1) * sequences_per_batch)
+                        fit = air.fit_track_noise(torch.as_tensor(seq_data["imgs"][sl], dtype=torch.float32).to(air.obs.device), grid, grid,
+                                                  zoom=args.track_fit_noise, accumulate=b > 0, fit=b == n - 1, **kw)
+                    fitter = air.noise_fitter(sequences_per_batch, track_eval["frames"], grid, grid, **kw)
+                    first = fitter.read_totals()                   # the first grid's totals: the defaults' ratios are cells of it
+                    i, j = grid.index(at_defaults[0]), grid.index(at_defaults[1])
+                    rec.update(process_noise=list(fit["process_noise"]), measurement_noise=fit["measurement_noise"],
+                               velocity_var=fit["velocity_var"], n_innovations=fit["n_innovations"], cell=list(fit["cell"]),
+                               on_edge=list(fit["on_edge"]), loglik_per_innovation=fit["loglik"] / fit["n_innovations"],
+                               loglik_per_innovation_at_defaults=tj.profile_loglik(first, i, j, D["measurement_noise"]) / fit["n_innovations"])
+                    if any(fit["on_edge"]):
+                        print("warning: the fitted noise terms lie on the edge of the grid %s: the maximum may be outside it"
+                              % (fit["on_edge"],))
+                except ValueError as e:                            # no track with two sightings, every innovation zero, ...
+                    rec["refused"] = str(e)
+                print("{}: test_track_noise_fit {}".format(train_itr, {k: v for k, v in rec.items() if k not in ("step", "data")}))
+                writer.write(json.dumps(rec) + "\n"); writer.flush()
+
         def log(train_itr):                               # noqa: F811
             out = before_track_log(train_itr)
             track_log(train_itr)
             if stream_log is not None:
                 stream_log(train_itr)
+            if fit_log is not None:
+                fit_log(train_itr)
             return out
 
     train_itr = int(global_step)

@@ -1,6 +1,6 @@
 """Where the stacks of post-parse stages behind AIRonMNIST.parse / parse_tiled / track are specified, built and cached: the normalised
 spec of a stack (`stack_spec`), the one builder (`build_stack`), the bounded cache and the single-slot holder of built and captured
-stages (`BoundedCache`, `slot`), the keys of the track family (`track_key`, `stream_key`).  Pure Python; the stage classes are imported where a
+stages (`BoundedCache`, `slot`), the keys of the track family (`track_key`, `stream_key`, `stream_smoother_key`, `fit_key`).  Pure Python; the stage classes are imported where a
 stack is built.
 """
 from collections import namedtuple
@@ -9,6 +9,7 @@ StackSpec = namedtuple("StackSpec", "refine lr prune propose temporal")     # in
 #                                                                             candidates | None, (P, rounds) | None, (P, rounds) | None
 TrackKey = namedtuple("TrackKey", "S F assoc stack smooth matching device")   # assoc, smooth: sorted (name, value) pairs; smooth | None
 StreamKey = namedtuple("StreamKey", "S F assoc stack matching device stream")  # a track.StreamTracker's: stream is True (a key of its own)
+FitKey = namedtuple("FitKey", "S F assoc stack matching device fit")             # ... with a trajectory.TrajectoryNoiseFitter: the grids
 StreamSmoothKey = namedtuple("StreamSmoothKey", "S F assoc stack matching device stream smooth")      # ... with a trajectory.StreamSmoother
 
 
@@ -125,6 +126,17 @@ def stream_smoother_key(eng, n_sequences, chunk_frames, smooth=True, **stream_ar
     spec = stream_smooth_spec(smooth)
     L = check_stream_arguments(eng.cfg.max_steps, k.F, k.S * k.F, dict(k.assoc)["max_age"], **spec)[4]
     return StreamSmoothKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, True, tuple(sorted(dict(spec, lag=L).items())))
+
+
+def fit_key(eng, n_sequences, n_frames, shift_ratios=None, scale_ratios=None, velocity_ratio=None, **track_args):
+    """The key of a tracker with a trajectory.TrajectoryNoiseFitter behind it, checked by trajectory.check_fit_arguments before
+    anything is built: `track_key`'s fields (without a smoother) and the fitter's grids -- a key of its own."""
+    from .trajectory import check_fit_arguments
+    if track_args.get("smooth") is not None:
+        raise ValueError("fit_track_noise: the noise terms are fitted to the tracker's sightings; smooth= has no part in it")
+    k = track_key(eng, n_sequences, n_frames, **dict(track_args, smooth=None))
+    fit = check_fit_arguments(eng.cfg.max_steps, k.F, k.S * k.F, shift_ratios, scale_ratios, velocity_ratio)[3:]
+    return FitKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, fit)
 
 
 def stage_classes():

@@ -44,7 +44,8 @@ so a score.ParseScorer binds to the completed frames unchanged; the smoother's o
 air_track_score with T := C on the completed table (one object cannot carry both a `score` tensor and a `score` method).
 
 The defaults of process_noise, measurement_noise and velocity_var are provisional: UNMEASURED on a trained model (profiles/trajectory.txt
-says what was measured).  Out of scope: smoothed covariances, feeding the smoothed rows back into the association, rates on scales in
+says what was measured).  `TrajectoryNoiseFitter` (NOISE FIT below) fits them to a model's own tracks by maximum likelihood, without
+ground truth.  Out of scope: smoothed covariances, feeding the smoothed rows back into the association, rates on scales in
 the forecast, a learned motion prior, particle providers (refused by the tracker, in its wording).
 
 STREAMS (`StreamSmoother` behind a track.StreamTracker; air_track_smooth_stream, `reference_smooth_stream` restates a chunk in numpy).
@@ -72,6 +73,21 @@ what the backward pass reads per (table row, frame) and of the provider's rows. 
 frames a .. a + F - 1 and emits from a - L on, and the source of a FILLED row there lies up to max_age frames before it; the reference
 tags every ring entry with its frame and asserts the tag on every read.  The default lag (max_age) is provisional like the noise
 terms.  Out of scope on a stream: smoothed covariances, feeding smoothed rows back into the association, IDF1.
+
+NOISE FIT (`TrajectoryNoiseFitter` behind a track.SequenceTracker; air_track_noise_stats, air_track_noise_reduce; `reference_noise_stats`
+restates both in numpy, bit for bit).  The forward filter above computes every innovation e = z - x- and its variance s = Pxx- + r: the
+log-likelihood of a track's sightings after its first, given its first, is  l = -1/2 sum_updates sum_components [log 2 pi + log s +
+e^2 / s]  (a track with one sighting and a coasted frame contribute nothing).  SCALE FAMILY: with the four terms written as
+r (rho_shift, rho_scale, 1, nu), the rule at r = 1, q = rho, velocity_var = nu gives the same gains and innovations and s~ = s / r; with N
+innovations, Q = sum e^2 / s~ and Lambda = sum log s~:  l(r) = -1/2 [N log(2 pi r) + Lambda + Q / r],  r^ = Q / N,
+l^ = -1/2 [N (log(2 pi Q / N) + 1) + Lambda].  The covariances are per noise class, so Q = Q_0(rho_shift) + Q_1(rho_scale), Lambda alike,
+and G evaluations per class give the G x G profile surface (`profile_fit`).  The device runs no transcendental function: per track and
+class, at each update, s~ = Pxx- + 1, d = (e_a e_a + e_b e_b) / s~ (a < b the class's two components), Q = Q + d, and the product of
+the s~ as a pair (m, k), value m 2^k, from (0.5, 1): (m_s, k_s) = frexp(s~), (m, j) = frexp(m m_s), k += k_s + j -- each s~ once, the
+host doubles Lambda.  The combine order is fixed: a binary tree over the 64 lanes of a pass (strides 32 .. 1, lane i < stride takes lane
+i + stride, idle lanes the identities 0.0 and (0.5, 1)), the passes, then the sequences, in ascending order, then the totals.  The
+fit's domain is the smoother's (FIT_*), so a fitted setting is one `check_arguments` takes.  Out of scope: fitting on a stream;
+fitting nu jointly (fit twice and compare `loglik`: comparable on the same tracks); noise terms per sequence; the association defaults.
 """
 import ctypes
 from collections import OrderedDict
@@ -1083,3 +1099,396 @@ class StreamSmoother(BoundStage):
         entry = next(iter(self._score.values()))
         flat = torch.cat([entry["seq_counts"].sum(0, dtype=torch.int64).double(), entry["seq_iou"].sum(0, keepdim=True)]).tolist()
         return mot_summary(flat[:8], flat[8])
+
+
+# ---- the noise terms by maximum likelihood (the module text states the statistics; include/air_hip.h the kernels' order) --------------------
+FIT_MAX_CANDIDATES = 32                                            # NFIT_MAX_G: candidates per launch
+# the fit's domain (csrc/noise_fit_kernels.hip: NFIT_*): the smoother's supported ratios, so that a fitted setting is one it takes
+FIT_Q_OVER_R_MIN, FIT_Q_OVER_R_MAX, FIT_V_OVER_R_MAX = Q_OVER_R_MIN, Q_OVER_R_MAX, V_OVER_R_MAX
+DEFAULT_FIT_RATIOS = tuple(float(10.0 ** (0.5 * k)) for k in range(-12, 7))      # half-decades of rho from 1e-6 to 1e3: 19 values
+FIT_KEYS = ("process_noise", "measurement_noise", "velocity_var")  # what of a fit `smooth=` takes as it is
+TOTAL_KEYS = ("tot_q", "tot_m", "tot_k", "tot_n")
+
+
+def default_velocity_ratio() -> float:
+    return DEFAULTS["velocity_var"] / DEFAULTS["measurement_noise"]
+
+
+def check_fit_arguments(max_steps, n_frames, n_rows=None, shift_ratios=None, scale_ratios=None, velocity_ratio=None, domain=True):
+    """Refuse what air_track_noise_stats refuses (pure host code).  None: DEFAULT_FIT_RATIOS / default_velocity_ratio().  Returns
+    (T, F, S, shift_ratios, scale_ratios, velocity_ratio), the ratios as tuples of G floats.  domain=False keeps every check but the
+    limits of the ratios (the numpy restatement runs wherever the statements do)."""
+    T, F, S = check_track_arguments(max_steps, n_frames, n_rows)
+    grids = []
+    for name, given in (("shift_ratios", shift_ratios), ("scale_ratios", scale_ratios)):
+        try:
+            g = tuple(float(v) for v in (DEFAULT_FIT_RATIOS if given is None else given))
+        except TypeError:
+            raise ValueError("%s must be a sequence of numbers, got %r" % (name, given))
+        if not 1 <= len(g) <= FIT_MAX_CANDIDATES:
+            raise ValueError("%s must hold 1..%d candidates, got %d" % (name, FIT_MAX_CANDIDATES, len(g)))
+        if not all(v > 0.0 for v in g):
+            raise ValueError("%s must be positive numbers (process noise / measurement noise), got %r" % (name, g))
+        if domain and not all(FIT_Q_OVER_R_MIN <= v <= FIT_Q_OVER_R_MAX for v in g):
+            raise ValueError("%s must lie within FIT_Q_OVER_R_MIN..FIT_Q_OVER_R_MAX = %g..%g (the smoother's supported domain), got %r"
+                             % (name, FIT_Q_OVER_R_MIN, FIT_Q_OVER_R_MAX, g))
+        grids.append(g)
+    if len(grids[0]) != len(grids[1]):
+        raise ValueError("shift_ratios and scale_ratios must hold the same number of candidates (one launch evaluates candidate g of "
+                         "both), got %d and %d" % (len(grids[0]), len(grids[1])))
+    nu = default_velocity_ratio() if velocity_ratio is None else float(velocity_ratio)
+    if not nu >= 0.0:
+        raise ValueError("velocity_ratio must be a number >= 0 (velocity_var / measurement noise), got %r" % (velocity_ratio,))
+    if domain and not nu <= FIT_V_OVER_R_MAX:
+        raise ValueError("velocity_ratio must be at most FIT_V_OVER_R_MAX = %g (the smoother's supported domain), got %r"
+                         % (FIT_V_OVER_R_MAX, velocity_ratio))
+    return T, F, S, grids[0], grids[1], nu
+
+
+def _pair_mul(m, k, ms, ks):
+    """(m, k) x (ms, ks) of products kept as m 2^k: (m, j) = frexp(m ms), k += ks + j.  Arrays, elementwise"""
+    import numpy as np
+    mm, j = np.frexp(m * ms)
+    return mm, k + ks + j.astype(np.int64)
+
+
+def _track_noise_stats(z_of, first, last, rho, nu):
+    """the forward filter of one track at r = 1 on every candidate at once: rho [2, G] float64 (class 0 the shifts, 1 the scales),
+    z_of(f) -> float64 [4] or None.  Returns Q, m [2, G] float64, k [2, G] int64 and the number of updates.  The statements are
+    `_filter_step`'s at r = 1, elementwise over the candidates; per update and class s~ = Pxx- + 1, d = (e_a e_a + e_b e_b) / s~,
+    Q = Q + d, (m, k) x frexp(s~)."""
+    import numpy as np
+    G = rho.shape[1]
+    one = np.float64(1.0)
+    q, q2, q4 = rho, np.float64(0.5) * rho, np.float64(0.25) * rho
+    Q, M, K, n = np.zeros((2, G)), np.full((2, G), 0.5), np.ones((2, G), np.int64), 0
+    cls = list(_CLASS)
+    x = v = Pxx = Pxv = Pvv = None
+    for f in range(first, last + 1):
+        z = z_of(f)
+        if f == first:                                             # start: x = z, v = 0, P = (1, 0, nu)
+            x = np.repeat((np.zeros(4) if z is None else z)[:, None], G, axis=1)
+            v, Pxx, Pxv, Pvv = np.zeros((4, G)), np.ones((2, G)), np.zeros((2, G)), np.full((2, G), np.float64(nu))
+            continue
+        a, b = Pxx + Pxv, Pxv + Pvv
+        Pxxp, Pxvp, Pvvp = (a + b) + q4, b + q2, Pvv + q
+        xp = x + v
+        if z is None:                                              # a coasted frame keeps the predicted state
+            x, Pxx, Pxv, Pvv = xp, Pxxp, Pxvp, Pvvp
+            continue
+        sn = Pxxp + one
+        kx, kv = Pxxp / sn, Pxvp / sn
+        Pxx, Pxv, Pvv = Pxxp - kx * Pxxp, Pxvp - kx * Pxvp, Pvvp - kv * Pxvp
+        e = z[:, None] - xp
+        x, v = xp + kx[cls] * e, v + kv[cls] * e
+        for c, (ca, cb) in enumerate(((1, 3), (0, 2))):
+            Q[c] = Q[c] + (e[ca] * e[ca] + e[cb] * e[cb]) / sn[c]
+            ms, ks = np.frexp(sn[c])
+            M[c], K[c] = _pair_mul(M[c], K[c], ms, ks.astype(np.int64))
+        n += 1
+    return Q, M, K, n
+
+
+def new_noise_totals(n_candidates):
+    """totals that hold nothing: the identities 0.0 and (0.5, 1) and n = 0"""
+    import numpy as np
+    G = int(n_candidates)
+    return {"tot_q": np.zeros((G, 2)), "tot_m": np.full((G, 2), 0.5), "tot_k": np.ones((G, 2), np.int64), "tot_n": np.zeros(1, np.int64)}
+
+
+def reference_noise_reduce(q, m, k, n, totals=None, accumulate=True):
+    """air_track_noise_reduce restated: q, m [S, G, 2] float64, k [S, G, 2], n [S] integers combined in ascending s from the
+    identities; then written (totals None or accumulate False) or combined into `totals` (total first; it is not modified).
+    Returns {tot_q, tot_m [G, 2] float64, tot_k [G, 2] int64, tot_n [1] int64}."""
+    import numpy as np
+    q, m, k = np.asarray(q, np.float64), np.asarray(m, np.float64), np.asarray(k).astype(np.int64)
+    fresh = new_noise_totals(q.shape[1])
+    Q, M, K = fresh["tot_q"], fresh["tot_m"], fresh["tot_k"]
+    with np.errstate(all="ignore"):
+        for s in range(q.shape[0]):
+            Q = Q + q[s]
+            M, K = _pair_mul(M, K, m[s], k[s])
+        N = np.asarray(n).astype(np.int64).sum(keepdims=True).reshape(1)
+        if totals is not None and accumulate:
+            Q = np.asarray(totals["tot_q"], np.float64) + Q
+            M, K = _pair_mul(np.asarray(totals["tot_m"], np.float64), np.asarray(totals["tot_k"]).astype(np.int64), M, K)
+            N = np.asarray(totals["tot_n"]).astype(np.int64).reshape(1) + N
+    return {"tot_q": Q, "tot_m": M, "tot_k": K, "tot_n": N}
+
+
+def reference_noise_stats(where, num_objects, track_id, num_tracks, track_first, track_last, n_frames, shift_ratios, scale_ratios,
+                          velocity_ratio, totals=None, accumulate=True):
+    """air_track_noise_stats and air_track_noise_reduce restated in numpy float64, bit for bit, the combine order included: the tables
+    as `reference_smooth` takes them (the same clipping and skip rules), G candidates, the filter at r = 1.  Per sequence and
+    candidate the lanes of a pass of 64 ids are combined by a binary tree (strides 32 .. 1, lane i < stride takes lane i + stride, an
+    idle lane the identities 0.0 and (0.5, 1)), the passes in ascending order, the sequences in ascending order, then the totals
+    (`reference_noise_reduce`: totals / accumulate).  Several calls accumulate by passing the totals of the call before.  Returns
+    q, m [S, G, 2] float64, k [S, G, 2] int32, n [S] int32 and tot_q, tot_m, tot_k, tot_n.  The ratios' domain is not checked here."""
+    import numpy as np
+    where = np.asarray(where, np.float32)
+    T, R = where.shape[:2]
+    T, F, S, shift, scale, nu = check_fit_arguments(T, n_frames, R, shift_ratios, scale_ratios, velocity_ratio, domain=False)
+    G, FT = len(shift), F * T
+    rho = np.array([shift, scale], np.float64)
+    ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
+    first, last = np.asarray(track_first).reshape(S, FT).astype(np.int64), np.asarray(track_last).reshape(S, FT).astype(np.int64)
+    out = {"q": np.zeros((S, G, 2)), "m": np.zeros((S, G, 2)), "k": np.zeros((S, G, 2), np.int32), "n": np.zeros(S, np.int32)}
+    with np.errstate(all="ignore"):
+        for s in range(S):
+            issued = int(min(max(int(np.asarray(num_tracks)[s]), 0), FT))
+
+            def sighting(i, f):
+                rr = s * F + f
+                n = int(min(max(n_in[rr], 0), T))
+                return next((j for j in range(n) if ids[j, rr] == i), None)
+
+            Qs, Ms, Ks, Ns = np.zeros((2, G)), np.full((2, G), 0.5), np.ones((2, G), np.int64), 0
+            for base in range(0, issued, 64):
+                Ql, Ml, Kl = np.zeros((64, 2, G)), np.full((64, 2, G), 0.5), np.ones((64, 2, G), np.int64)
+                for lane in range(64):
+                    i = base + lane
+                    if i >= issued or not 0 <= first[s, i] <= last[s, i] < F:
+                        continue
+                    fi, la = int(first[s, i]), int(last[s, i])
+                    slots = {f: sighting(i, f) for f in range(fi, la + 1)}
+                    z_of = lambda f: None if slots[f] is None else where[slots[f], s * F + f].astype(np.float64)
+                    Ql[lane], Ml[lane], Kl[lane], n_t = _track_noise_stats(z_of, fi, la, rho, nu)
+                    Ns += n_t
+                stride = 32
+                while stride >= 1:                                 # lane i < stride takes lane i + stride
+                    Ql[:stride] = Ql[:stride] + Ql[stride:2 * stride]
+                    Ml[:stride], Kl[:stride] = _pair_mul(Ml[:stride], Kl[:stride], Ml[stride:2 * stride], Kl[stride:2 * stride])
+                    stride //= 2
+                Qs = Qs + Ql[0]                                    # the passes in ascending order
+                Ms, Ks = _pair_mul(Ms, Ks, Ml[0], Kl[0])
+            out["q"][s], out["m"][s], out["k"][s], out["n"][s] = Qs.T, Ms.T, Ks.T.astype(np.int32), Ns
+    out.update(reference_noise_reduce(out["q"], out["m"], out["k"], out["n"], totals, accumulate))
+    return out
+
+
+def _profile_terms(totals):
+    """(N, Q [G, G], Lambda [G, G]) of the totals: Q = Q_0(i) + Q_1(j), Lambda = Lambda_0(i) + Lambda_1(j) with
+    Lambda_c = 2 (log m + k log 2) -- the two components of a class share every s~ --, N = 4 n"""
+    import numpy as np
+    tq, tm = np.asarray(totals["tot_q"], np.float64), np.asarray(totals["tot_m"], np.float64)
+    tk = np.asarray(totals["tot_k"]).astype(np.float64)
+    with np.errstate(all="ignore"):
+        lam = 2.0 * (np.log(tm) + tk * np.log(2.0))
+    N = 4 * int(np.asarray(totals["tot_n"]).reshape(-1)[0])
+    return N, tq[:, 0][:, None] + tq[:, 1][None, :], lam[:, 0][:, None] + lam[:, 1][None, :]
+
+
+def profile_loglik(totals, i, j, r):
+    """loglik(r) = -1/2 [N log(2 pi r) + Lambda + Q / r] of cell (i, j): the value at a GIVEN measurement noise r -- at the current
+    settings, say, to compare with a fit's `loglik` on the same tracks"""
+    import math
+    N, Q, lam = _profile_terms(totals)
+    return float(-0.5 * (N * math.log(2.0 * math.pi * float(r)) + lam[i, j] + Q[i, j] / float(r)))
+
+
+def profile_fit(totals, shift_ratios, scale_ratios, velocity_ratio):
+    """The maximum-likelihood noise terms from the totals, host float64.  The G x G profile surface is
+    loglik^[i, j] = -1/2 [N (log(2 pi Q / N) + 1) + Lambda], r concentrated out as r^ = Q / N; its arg-max is the FIRST cell in
+    row-major order (i: shift, j: scale) that no later cell exceeds, and a NaN never wins.  Returns dict(process_noise=(r^ rho_shift,
+    r^ rho_scale), measurement_noise=r^, velocity_var=r^ nu, loglik, n_innovations=N, cell=(i, j), on_edge=(bool, bool), surface
+    [G, G]); the first three are what `smooth=` takes.  ValueError: no track with two sightings (n = 0); Q = 0 (every innovation is
+    zero: the likelihood is unbounded); no finite cell; fitted terms outside the smoother's supported domain."""
+    import numpy as np
+    shift, scale = [float(v) for v in shift_ratios], [float(v) for v in scale_ratios]
+    nu = float(velocity_ratio)
+    N, Q, lam = _profile_terms(totals)
+    G = Q.shape[0]
+    if len(shift) != G or len(scale) != G:
+        raise ValueError("the totals hold %d candidates, the grids %d and %d" % (G, len(shift), len(scale)))
+    if N == 0:
+        raise ValueError("no track with two sightings: there is no innovation to fit the noise terms to")
+    if (Q == 0.0).any():
+        raise ValueError("every innovation is zero (the tracks do not move off their prediction): the likelihood is unbounded as the "
+                         "measurement noise goes to 0, there is no maximum")
+    with np.errstate(all="ignore"):
+        surface = -0.5 * (N * (np.log(2.0 * np.pi * Q / N) + 1.0) + lam)
+    best = None
+    for i in range(G):
+        for j in range(G):
+            v = surface[i, j]
+            if v == v and (best is None or v > surface[best]):
+                best = (i, j)
+    if best is None:
+        raise ValueError("the likelihood is NaN in every cell (a non-finite sighting?)")
+    i, j = best
+    r = float(Q[i, j] / N)
+    fit = dict(process_noise=(r * shift[i], r * scale[j]), measurement_noise=r, velocity_var=r * nu)
+    try:
+        check_arguments(1, 1, None, 0, 0, **fit)
+    except ValueError as e:
+        raise ValueError("the fitted terms fall outside the smoother's supported domain (cell %r, r = %g): %s" % (best, r, e))
+    fit.update(loglik=float(surface[i, j]), n_innovations=N, cell=best, on_edge=(i in (0, G - 1), j in (0, G - 1)), surface=surface)
+    return fit
+
+
+def zoom_grid(ratios, best):
+    """the next grid of a zoom: as many candidates, log-spaced between the two neighbours of candidate `best` (the end of the grid
+    where there is none), the incumbent itself kept in place of the candidate nearest to it -- so the best cell stays a cell and the
+    likelihood cannot go down"""
+    import numpy as np
+    ratios = [float(v) for v in ratios]
+    G = len(ratios)
+    lo, hi = ratios[max(best - 1, 0)], ratios[min(best + 1, G - 1)]
+    lo, hi = min(lo, hi), max(lo, hi)
+    if G == 1 or not hi > lo:
+        return tuple(ratios)
+    grid = [float(v) for v in np.geomspace(lo, hi, G)]
+    grid[0], grid[-1] = lo, hi                                     # (the ends as they were: inside the domain)
+    at = int(np.argmin([abs(np.log(g) - np.log(ratios[best])) for g in grid]))
+    grid[at] = ratios[best]
+    return tuple(grid)
+
+
+def fit_with_zoom(evaluate, shift_ratios, scale_ratios, velocity_ratio, zoom=0, totals=None):
+    """`profile_fit`, then `zoom` times: both grids replaced by `zoom_grid` around the best cell, evaluate(shift, scale) -> totals on
+    the SAME tracks, and the better of the two fits kept.  totals: those of the first grid (None: evaluate them).  The returned dict
+    also holds shift_ratios / scale_ratios / velocity_ratio, the grid the fit's cell refers to, and `totals`, that grid's."""
+    if isinstance(zoom, bool) or int(zoom) != zoom or int(zoom) < 0:
+        raise ValueError("zoom must be an integer >= 0, got %r" % (zoom,))
+    shift, scale = tuple(float(v) for v in shift_ratios), tuple(float(v) for v in scale_ratios)
+    totals = evaluate(shift, scale) if totals is None else totals
+    fit = dict(profile_fit(totals, shift, scale, velocity_ratio), shift_ratios=shift, scale_ratios=scale,
+               velocity_ratio=float(velocity_ratio), totals=totals)
+    for _ in range(int(zoom)):
+        shift, scale = zoom_grid(fit["shift_ratios"], fit["cell"][0]), zoom_grid(fit["scale_ratios"], fit["cell"][1])
+        totals = evaluate(shift, scale)
+        nxt = dict(profile_fit(totals, shift, scale, velocity_ratio), shift_ratios=shift, scale_ratios=scale,
+                   velocity_ratio=float(velocity_ratio), totals=totals)
+        if nxt["loglik"] >= fit["loglik"]:
+            fit = nxt
+    return fit
+
+
+class TrajectoryNoiseFitter(BoundStage):
+    """The smoother's noise terms by maximum likelihood, on the device: binds to a track.SequenceTracker like TrajectorySmoother, only
+    reads that tracker's and its provider's buffers, and runs, after `capture()`, ONE hipGraph of two launches:
+
+      air_track_noise_stats    the forward filter at r = 1 on a grid of G candidates per noise class, all tracks of all sequences;
+      air_track_noise_reduce   the sequences into device-resident totals (always accumulate = 1: `reset()` writes the identities).
+
+    `run()` returns nothing and reads nothing back, so a fit runs over many batches of videos; `fit()` is ONE read-back and
+    `profile_fit`.  fit(zoom=k) re-runs k times on `zoom_grid` around the best cell: eager launches into buffers of their own on the
+    tracker's CURRENT tables, so it is refused once more than one `run()` has been accumulated (calibration is offline).  Out of
+    scope: fitting on a stream; fitting velocity_ratio jointly (fit twice and compare `loglik`: it is comparable on the same tracks);
+    noise terms per sequence; the association defaults."""
+
+    def __init__(self, tracker, shift_ratios=None, scale_ratios=None, velocity_ratio=None):
+        import torch
+        from . import hip as H
+        if not hasattr(tracker, "track_first") or hasattr(tracker, "push"):
+            raise ValueError("TrajectoryNoiseFitter binds to a track.SequenceTracker, got %s" % type(tracker).__name__)
+        T, F, S, shift, scale, nu = check_fit_arguments(tracker.T, tracker.F, tracker.R, shift_ratios, scale_ratios, velocity_ratio)
+        self.tracker, self.provider, self.engine, self._bound = tracker, tracker.provider, tracker.engine, tracker
+        self.T, self.F, self.S, self.R, self.G = T, F, S, int(tracker.R), len(shift)
+        self.shift_ratios, self.scale_ratios, self.velocity_ratio = shift, scale, nu
+        self._where = tracker._rows["where"]
+        self._H = H
+        dev, G = self.engine.device, self.G
+        with torch.cuda.device(dev):
+            self.stats = self._stat_buffers(torch, dev)
+            self.totals, self._zoom_totals = self._total_buffers(torch, dev), self._total_buffers(torch, dev)
+            self._identity = {k: torch.as_tensor(v, device=dev) for k, v in new_noise_totals(G).items()}
+        self._grid = self._host_grid(shift, scale)
+        self.runs = 0
+        self._rebuild()
+        self.reset()
+        self.engine.synchronize()
+
+    def _stat_buffers(self, torch, dev):
+        S, G = self.S, self.G
+        return {"q": torch.zeros((S, G, 2), dtype=torch.float64, device=dev), "m": torch.zeros((S, G, 2), dtype=torch.float64, device=dev),
+                "k": torch.zeros((S, G, 2), dtype=torch.int32, device=dev), "n": torch.zeros((S,), dtype=torch.int32, device=dev)}
+
+    def _total_buffers(self, torch, dev):
+        G = self.G
+        return {"tot_q": torch.zeros((G, 2), dtype=torch.float64, device=dev), "tot_m": torch.zeros((G, 2), dtype=torch.float64, device=dev),
+                "tot_k": torch.zeros((G, 2), dtype=torch.int64, device=dev), "tot_n": torch.zeros((1,), dtype=torch.int64, device=dev)}
+
+    @staticmethod
+    def _host_grid(shift, scale):
+        """the host arrays the entry copies into the kernel arguments (kept alive by whoever holds the plan)"""
+        arr = ctypes.c_double * len(shift)
+        return arr(*shift), arr(*scale)
+
+    def _entries(self, grid, totals, accumulate):
+        H, tk, par, st = self._H, self.tracker, self.provider, self.stats
+        L, p = H.lib(), H._p
+        return [(L.air_track_noise_stats,
+                 (p(self._where), p(par.num_objects), p(tk.track_id), p(tk.num_tracks), p(tk.track_first), p(tk.track_last), self.T,
+                  self.S, self.F, self.R, self.G, grid[0], grid[1], self.velocity_ratio, p(st["q"]), p(st["m"]), p(st["k"]),
+                  p(st["n"])), "air_track_noise_stats"),
+                (L.air_track_noise_reduce,
+                 (p(st["q"]), p(st["m"]), p(st["k"]), p(st["n"]), self.S, self.G, int(accumulate), p(totals["tot_q"]),
+                  p(totals["tot_m"]), p(totals["tot_k"]), p(totals["tot_n"])), "air_track_noise_reduce")]
+
+    def _build_plan(self):
+        self.segments = OrderedDict([("fit", self._entries(self._grid, self.totals, 1))])
+        self._plan = list(self.segments["fit"])
+
+    def launch_count(self) -> Dict[str, int]:
+        """entries of one `run()` behind the tracker's own"""
+        return {"tracker": self.tracker.launch_count(), "track_noise_stats": 1, "track_noise_reduce": 1}
+
+    def reset(self):
+        """the totals hold nothing: the identities 0.0, (0.5, 1) and n = 0, written on the engine's stream"""
+        import torch
+        eng = self.engine
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            for k, v in self._identity.items():
+                self.totals[k].copy_(v, non_blocking=True)
+        eng.wait_for_engine()
+        self.runs = 0
+
+    def run(self, accumulate=True):
+        """the statistics of the tracker's LATEST `track()` into the totals (accumulate=False: `reset()` first).  Returns nothing: no
+        read-back.  The tracker's and the provider's buffers are only read.  Same stream contract as SequenceTracker.track."""
+        if not accumulate:
+            self.reset()
+        eng = self.engine
+        self._refresh_plan()
+        eng.wait_for_caller()
+        eng._replay_or_run(self._graph, self._plan)
+        eng.wait_for_engine()
+        self.runs += 1
+
+    def track(self, frames, *args, accumulate=True, **kwargs):
+        """the bound tracker's `track(frames, ...)`, then `run(accumulate)`; returns the tracker's result"""
+        base = self.tracker.track(frames, *args, **kwargs)
+        self.run(accumulate)
+        return base
+
+    def read_totals(self, totals=None):
+        """{tot_q, tot_m, tot_k, tot_n} as numpy arrays: ONE read-back"""
+        import torch
+        t = self.totals if totals is None else totals
+        self.engine.wait_for_engine()
+        flat = torch.cat([t["tot_q"].reshape(-1).view(torch.int64), t["tot_m"].reshape(-1).view(torch.int64), t["tot_k"].reshape(-1),
+                          t["tot_n"]]).cpu().numpy()             # (the float64 bits travel as integers)
+        G2 = 2 * self.G
+        import numpy as np
+        return {"tot_q": flat[:G2].view(np.float64).reshape(self.G, 2).copy(), "tot_m": flat[G2:2 * G2].view(np.float64).reshape(self.G, 2).copy(),
+                "tot_k": flat[2 * G2:3 * G2].reshape(self.G, 2).copy(), "tot_n": flat[3 * G2:].copy()}
+
+    def _evaluate(self, shift, scale):
+        """eager: the two launches on another grid of G candidates into the zoom's own totals (the tracker's current tables)"""
+        check_fit_arguments(self.T, self.F, self.R, shift, scale, self.velocity_ratio)
+        eng = self.engine
+        grid = self._host_grid(shift, scale)
+        eng.wait_for_caller()
+        eng._run(self._entries(grid, self._zoom_totals, 0), eng._sp())
+        eng.wait_for_engine()
+        return self.read_totals(self._zoom_totals)
+
+    def fit(self, zoom=0):
+        """`profile_fit` of everything `run()` took since the last reset (ONE read-back); zoom=k: `fit_with_zoom`, k eager re-runs on
+        the tracker's current tables -- refused when the totals hold more than that one `run()`"""
+        if int(zoom) > 0 and self.runs != 1:
+            raise ValueError("fit(zoom=%r) re-runs on the tracker's current tables, but the totals hold %d runs: zoom after exactly one "
+                             "run() since reset()" % (zoom, self.runs))
+        return fit_with_zoom(self._evaluate, self.shift_ratios, self.scale_ratios, self.velocity_ratio, zoom, self.read_totals())

@@ -1102,6 +1102,40 @@ AIR_ENGINE_API int air_track_fill(const float *what, const float *glimpse, const
                     const int *src_frame, const int *src_slot, int T, int F, int R, int C, int N, int per_seq, int A, int G,
                     float *out_what, float *out_glimpse, float *out_score, void *stream);
 
+/* ---- the smoother's noise terms by maximum likelihood: the prediction-error decomposition of air_track_smooth's filter on a grid of
+ * G candidates, 1 <= G <= 32, in one pass over the same tracker tables (where[T,R,4], num_objects[R], track_id[T,R], num_tracks[S],
+ * track_first / track_last[S, F T]; the same clipping and the same skip rules: num_tracks clipped to 0 .. F T, a track taken iff
+ * 0 <= first <= last < F, the lowest slot that carries an id; a track without a sighting in its `first` frame starts from z = 0).
+ * SCALE FAMILY: the four terms are r (rho_shift, rho_scale, 1, nu).  The filter is run at r = 1 exactly, q = rho (shift_ratios[g] for
+ * tx, ty: class 0; scale_ratios[g] for sx, sy: class 1), velocity_var = nu = velocity_ratio: the gains and the innovations e = z - x-
+ * are those of every r, and s~ = Pxx- + 1 = s / r.  With N innovations, Q = sum e^2 / s~ and Lambda = sum log s~:
+ * loglik(r) = -1/2 [N log(2 pi r) + Lambda + Q / r], maximal at r^ = Q / N.  The covariances are per class, so G evaluations per class
+ * give the G x G surface.  No transcendental function runs on the device: Lambda is kept as the PRODUCT of the s~.
+ * air_track_noise_stats: float64 from the widened fp32 values, contraction off, only + - * / and frexp; start, predict and update are
+ *   air_track_smooth's statements at r = 1.  An UPDATE is a frame after `first` with a sighting; the start and a coasted frame
+ *   contribute nothing.  Per track and class, at each update, in this order:  s~ = Pxx- + 1;  d = (e_a e_a + e_b e_b) / s~ with a < b
+ *   the two components of the class (class 0: 1, 3; class 1: 0, 2);  Q_t = Q_t + d;  the product of the s~ as a normalised pair (m, k),
+ *   value m 2^k, started at (0.5, 1):  (m_s, k_s) = frexp(s~), (m, j) = frexp(m m_s), k += k_s + j.  Each s~ is counted once (the two
+ *   components of a class share it: the host doubles Lambda).
+ *   THE COMBINE ORDER.  One workgroup of one wavefront per (sequence, candidate); lanes are track ids in passes of 64.  Over the lanes
+ *   of a pass a binary tree with strides 32, 16, .., 1: lane i < stride takes lane i + stride; an idle lane (no such id, or a skipped
+ *   track) carries the identities 0.0 and (0.5, 1).  The passes are combined in ascending order into a value started at the identities.
+ *   Sums are +; products (m, k) x (m', k'): (m, j) = frexp(m m'), k += k' + j.  No floating-point atomics, no workspace.
+ *   Outputs: q[S,G,2], m[S,G,2] (float64), k[S,G,2] (int32; class 0 first), n[S] (int32: the updates of the sequence; N = 4 n over both
+ *   classes, 2 n per class).  shift_ratios / scale_ratios are HOST arrays of G values, copied into the kernel arguments.
+ *   AIR_E_SHAPE: T, S, F, R as air_track_smooth refuses them; G outside 1..32; a ratio outside 1e-29 .. 1e15; velocity_ratio outside
+ *   0 .. 1e6; a NaN (the smoother's supported domain: a fitted setting is one air_track_smooth takes).  where 16-byte, q / m 8-byte,
+ *   everything else 4-byte aligned (AIR_E_ALIGN).  Checks come before the launch: a refused call writes nothing.
+ * air_track_noise_reduce: one workgroup, one lane per (candidate, class): the sequences combined in ascending s from the identities
+ *   (k widened to int64), then with accumulate = 0 written to, with accumulate = 1 combined into (total first, the call's value
+ *   second), tot_q[G,2], tot_m[G,2] (float64), tot_k[G,2] (int64), tot_n[1] (int64, the sum of n).  AIR_E_SHAPE: S < 1, G outside
+ *   1..32, accumulate not 0 / 1; q, m and the totals 8-byte, k and n 4-byte aligned (AIR_E_ALIGN).                                    */
+AIR_ENGINE_API int air_track_noise_stats(const float *where, const int *num_objects, const int *track_id, const int *num_tracks,
+                    const int *track_first, const int *track_last, int T, int S, int F, int R, int G, const double *shift_ratios,
+                    const double *scale_ratios, double velocity_ratio, double *q, double *m, int *k, int *n, void *stream);
+AIR_ENGINE_API int air_track_noise_reduce(const double *q, const double *m, const int *k, const int *n, int S, int G, int accumulate,
+                    double *tot_q, double *tot_m, long long *tot_k, long long *tot_n, void *stream);
+
 /* ---- trajectories on a stream: fixed-lag smoothing and forecasts per chunk, behind air_track_associate_stream (its chunks, valid[S]
  * and global frame indices; frames_seen below 2^31 is the caller's to refuse).  THE RULE is air_track_smooth's, unchanged: start /
  * predict / update / back per sequence, track id and where component, float64 from the widened fp32 values, contraction off, only
