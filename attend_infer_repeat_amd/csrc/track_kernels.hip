@@ -4,6 +4,8 @@
 //   air_track_associate_stream: the same per-frame code on a CHUNK of a stream: the track table is loaded from and stored to a state
 //                        that outlives the launch, the frames are numbered globally, the retired tracks come as a list;
 //   air_track_score_stream: air_track_score with its map, its per-slot counts, its counters and its IoU sum carried in a state;
+//   air_track_associate_motion: the same kernel (either matching) with a per-track Kalman filter: every pair is gated and ranked by the
+//                        IoU with the box the track is PREDICTED to have, and a match or a birth advances or starts the filter;
 //   air_track_associate_optimal: the same kernel with step 3 replaced: the assignment of the largest summed int64 profit, by a
 //                        shortest-augmenting-path Hungarian that one wavefront runs (lane = column);
 //   air_track_owner:     the parse's owner maps relabelled from step to track id (int8 in, int16 out): a streaming pass;
@@ -16,6 +18,7 @@
 #include <limits.h>
 #include <type_traits>
 #include "scene_device.h"
+#include "traj_device.h"
 
 #define TRACK_THREADS 256
 #define TRACK_MAXT 32                    // PARSE_MAXT / SCORE_MAXT: objects per frame, and live tracks per sequence
@@ -66,6 +69,15 @@ struct TrackStreamArgs : TrackAssocArgs {
 };
 enum { TRACK_ST_LIVE = 0, TRACK_ST_ID, TRACK_ST_AGE, TRACK_ST_LENGTH, TRACK_ST_GAPS, TRACK_ST_FIRST, TRACK_ST_LAST_FRAME,
        TRACK_ST_LAST_SLOT, TRACK_ST_FIELDS };
+// motion: the one-shot arguments, the `where` rows, the noise terms of the trajectory filter and the two prediction outputs
+struct TrackMotionArgs : TrackAssocArgs {
+    const float *where;
+    float *pred_where, *pred_boxes;
+    double q[2], r, velocity_var;        // q[0]: the shift components tx, ty; q[1]: the scale components sx, sy (TrajSmoothArgs')
+    float Wf, Hf;
+};
+// the filtered state of slot k, value i: mstate_s[i * 32 + k]
+enum { TRACK_MS_X = 0, TRACK_MS_V = 4, TRACK_MS_P = 8, TRACK_MS_DOUBLES = 14 };      // class c: TRACK_MS_P + 3 c (xx, xv, vv)
 
 // The assignment of the frame's finite objects (rows, inserted in ascending j) to the 64 columns of one wavefront -- column k < 32 is
 // track slot k, column 32 + j is "object j stays unmatched" -- that maximises the summed profit: profit_s[k * 32 + j] >= 1 for an
@@ -128,9 +140,19 @@ __device__ __forceinline__ int track_solve_wave(const long long *profit_s, const
 // STREAM: the table comes from and goes back to the state (one global round trip per launch, none per frame), the frames f <
 // clip(valid[s], 0, F) are walked under their global index frames_seen + f, a track last sighted before this chunk takes its `what`
 // row from the state, and a retired track goes to the chunk's retired list (its place by a ballot over the 32 slots).
-template <bool OPTIMAL, bool STREAM = false> __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(
-    std::conditional_t<STREAM, TrackStreamArgs, TrackAssocArgs> a) {
+// MOTION: slot k carries the FILTERED state of the trajectory filter at its last sighting (14 doubles in LDS, read and written by
+// lane k alone); lane k forms the slot's predicted row and box in step 1, the pair loop of step 2 reads that box where it reads the
+// last-sighting box otherwise, and in step 5 lane k advances (a matched track: the coasted frames predicted one by one, then the
+// update with the new sighting's `where` row) or starts (a born track) its state.  An object with a non-finite `where` value is
+// NONFINITE.  The bits of every other output are those of the kernel without MOTION while every track's rate is exactly 0.
+template <bool OPTIMAL, bool STREAM = false, bool MOTION = false> __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(
+    std::conditional_t<STREAM, TrackStreamArgs, std::conditional_t<MOTION, TrackMotionArgs, TrackAssocArgs>> a) {
 #pragma clang fp contract(off)
+    static_assert(!(STREAM && MOTION), "the motion state is not carried across the chunks of a stream");
+    __shared__ double mstate_s[MOTION ? TRACK_MS_DOUBLES * TRACK_MAXT : 1];      // MOTION only, as the three below
+    __shared__ float4 owhere_s[MOTION ? TRACK_MAXT : 1];           // the frame's `where` rows
+    __shared__ float4 pwhere_s[MOTION ? TRACK_MAXT : 1], pbox_s[MOTION ? TRACK_MAXT : 1];      // the slots' predicted rows and boxes
+    __shared__ int omk_s[MOTION ? TRACK_MAXT : 1];                 // the slot a matched object was matched to
     __shared__ double aff_s[TRACK_MAXT * TRACK_MAXT];              // aff of an admissible pair still open, -1 otherwise
     __shared__ long long profit_s[OPTIMAL ? TRACK_MAXT * TRACK_MAXT : 1];      // OPTIMAL: 1 + floor(aff 2^32), -1 for a forbidden pair
     __shared__ float4 obox_s[TRACK_MAXT], tbox_s[TRACK_MAXT];      // the frame's boxes; the tracks' last-sighting boxes
@@ -193,6 +215,29 @@ template <bool OPTIMAL, bool STREAM = false> __global__ __launch_bounds__(TRACK_
             opf_s[j] = -1;
             ops_s[j] = -1;
             oaff_s[j] = 0.f;
+            if constexpr (MOTION) {
+                float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (j < n) w4 = *reinterpret_cast<const float4 *>(a.where + 4 * ((size_t)j * R + r));
+                owhere_s[j] = w4;
+                omk_s[j] = -1;
+                if (!track_finite4(w4)) nonfinite_s[j] = 1;        // (every writer writes 1)
+                // slot k = tid: where the track is predicted to be m frames after its last sighting -- trajectory's forecast row
+                // (shifts extrapolated, scales held; one product and one sum in float64, rounded once) and its box in fp32
+                const int k = tid;
+                float4 pw = make_float4(0.f, 0.f, 0.f, 0.f), pb = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (t_live[k]) {
+                    const double m = (double)(fg - t_f[k]);
+                    const double *ms = mstate_s + k;
+                    pw = make_float4((float)ms[(TRACK_MS_X + 0) * TRACK_MAXT],
+                                     (float)(ms[(TRACK_MS_X + 1) * TRACK_MAXT] + m * ms[(TRACK_MS_V + 1) * TRACK_MAXT]),
+                                     (float)ms[(TRACK_MS_X + 2) * TRACK_MAXT],
+                                     (float)(ms[(TRACK_MS_X + 3) * TRACK_MAXT] + m * ms[(TRACK_MS_V + 3) * TRACK_MAXT]));
+                    pb = attention_box4(pw, a.Wf, a.Hf);
+                    if (!track_finite4(pb)) pb = tbox_s[k];        // a prediction that leaves fp32: the last-sighting box
+                }
+                pwhere_s[k] = pw;
+                pbox_s[k] = pb;
+            }
         }
         for (int e = tid; e < n * A; e += TRACK_THREADS) {
             const int j = e / A, q = e - j * A;
@@ -209,7 +254,9 @@ template <bool OPTIMAL, bool STREAM = false> __global__ __launch_bounds__(TRACK_
             const int k = p >> 5, j = p & 31;
             double val = -1.0;
             if (t_live[k] && j < n && track_finite4(obox_s[j]) && isfinite(oscore_s[j]) && !nonfinite_s[j]) {
-                const double iou = box_iou_f64(tbox_s[k], obox_s[j]);
+                double iou;
+                if constexpr (MOTION) iou = box_iou_f64(pbox_s[k], obox_s[j]);
+                else iou = box_iou_f64(tbox_s[k], obox_s[j]);
                 const float *wk;
                 if constexpr (STREAM) {                            // sighted in this chunk: in place; before it: the state's copy
                     const int lf = t_f[k] - base;
@@ -257,6 +304,7 @@ template <bool OPTIMAL, bool STREAM = false> __global__ __launch_bounds__(TRACK_
                     opf_s[j] = t_f[k];
                     ops_s[j] = t_j[k];
                     oaff_s[j] = (float)aff_s[k * TRACK_MAXT + j];
+                    if constexpr (MOTION) omk_s[j] = k;
                     t_gaps[k] += t_age[k] > 0 ? 1 : 0;
                     t_age[k] = 0;
                     t_len[k] += 1;
@@ -294,6 +342,7 @@ template <bool OPTIMAL, bool STREAM = false> __global__ __launch_bounds__(TRACK_
                 opf_s[j] = t_f[k];
                 ops_s[j] = t_j[k];
                 oaff_s[j] = (float)v;
+                if constexpr (MOTION) omk_s[j] = k;
                 t_gaps[k] += t_age[k] > 0 ? 1 : 0;
                 t_age[k] = 0;
                 t_len[k] += 1;
@@ -354,6 +403,55 @@ template <bool OPTIMAL, bool STREAM = false> __global__ __launch_bounds__(TRACK_
                     }
                 }
             }
+            if constexpr (MOTION) {                                // the filter state of a slot sighted in this frame: lane = slot
+                if (t_live[k] && t_f[k] == fg) {
+                    const int j = t_j[k];
+                    const float4 w4 = owhere_s[j];
+                    const double z[4] = {(double)w4.x, (double)w4.y, (double)w4.z, (double)w4.w};
+                    double *ms = mstate_s + k;
+                    double x[4], v[4];
+                    TrajCov P[2];
+                    if (ostate_s[j] == TRACK_BORN) {               // start: x = z, v = 0, P = (r, 0, velocity_var)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) x[c] = z[c], v[c] = 0.0;
+                        P[0].xx = P[1].xx = a.r;
+                        P[0].xv = P[1].xv = 0.0;
+                        P[0].vv = P[1].vv = a.velocity_var;
+                    } else {                                       // matched: the frames coasted over one by one, then the update
+                        const double q2[2] = {0.5 * a.q[0], 0.5 * a.q[1]}, q4[2] = {0.25 * a.q[0], 0.25 * a.q[1]};
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) x[c] = ms[(TRACK_MS_X + c) * TRACK_MAXT], v[c] = ms[(TRACK_MS_V + c) * TRACK_MAXT];
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) {
+                            P[c].xx = ms[(TRACK_MS_P + 3 * c) * TRACK_MAXT];
+                            P[c].xv = ms[(TRACK_MS_P + 3 * c + 1) * TRACK_MAXT];
+                            P[c].vv = ms[(TRACK_MS_P + 3 * c + 2) * TRACK_MAXT];
+                        }
+                        const int m = fg - opf_s[j];               // 1 .. max_age + 1
+                        for (int i = 1; i < m; ++i) {
+#pragma unroll
+                            for (int c = 0; c < 2; ++c) P[c] = traj_predict_cov(P[c], a.q[c], q2[c], q4[c]);
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) x[c] = x[c] + v[c];
+                        }
+                        TrajCov Pp[2];
+                        double xp[4], vp[4];
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) Pp[c] = traj_predict_cov(P[c], a.q[c], q2[c], q4[c]);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) xp[c] = x[c] + v[c], vp[c] = v[c];
+                        TRAJ_UPDATE(P, Pp, x, v, xp, vp, z, a.r)
+                    }
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) ms[(TRACK_MS_X + c) * TRACK_MAXT] = x[c], ms[(TRACK_MS_V + c) * TRACK_MAXT] = v[c];
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        ms[(TRACK_MS_P + 3 * c) * TRACK_MAXT] = P[c].xx;
+                        ms[(TRACK_MS_P + 3 * c + 1) * TRACK_MAXT] = P[c].xv;
+                        ms[(TRACK_MS_P + 3 * c + 2) * TRACK_MAXT] = P[c].vv;
+                    }
+                }
+            }
             if constexpr (STREAM) {                                // the retired list: ascending frame, then ascending slot
                 const unsigned long long retiring = __ballot(retire);      // (the 32 threads of this branch are lanes 0..31 of one wavefront)
                 if (retire) {
@@ -375,7 +473,14 @@ template <bool OPTIMAL, bool STREAM = false> __global__ __launch_bounds__(TRACK_
                 a.affinity[row] = oaff_s[tid];
                 a.prev_frame[row] = opf_s[tid];
                 a.prev_slot[row] = ops_s[tid];
-                atomicAdd(&counts_s[state], 1);                     // integer adds in LDS: the order does not matter
+                if constexpr (MOTION) {                            // the prediction the match was made against; zero unless matched
+                    const int mk = omk_s[tid];
+                    float4 pw = pwhere_s[mk < 0 ? 0 : mk], pb = pbox_s[mk < 0 ? 0 : mk];      // (a select of values, not of addresses)
+                    if (mk < 0) pw = pb = make_float4(0.f, 0.f, 0.f, 0.f);
+                    reinterpret_cast<float4 *>(a.pred_where)[row] = pw;
+                    reinterpret_cast<float4 *>(a.pred_boxes)[row] = pb;
+                }
+                atomicAdd(&counts_s[state], 1);                    // integer adds in LDS: the order does not matter
             }
         }
         __syncthreads();
@@ -468,7 +573,7 @@ static int track_associate_launch(bool optimal, const float *what, const float *
                                   int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
                                   int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
                                   int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
-                                  int *state_counts, void *stream) {
+                                  int *state_counts, void *stream, const TrackMotionArgs *motion = nullptr) {
     AIR_REQUIRE(what && boxes && score && num_objects && track_id && obj_state && affinity && prev_frame && prev_slot && num_tracks &&
                 track_first && track_last && track_length && track_gaps && state_counts, AIR_E_NULL);
     AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && S > 0 && F > 0 && A > 0, AIR_E_SHAPE);
@@ -486,8 +591,18 @@ static int track_associate_launch(bool optimal, const float *what, const float *
     const TrackAssocArgs a = {what, boxes, score, num_objects, track_id, prev_frame, prev_slot, num_tracks, track_first, track_last,
                               track_length, track_gaps, state_counts, affinity, obj_state, iou_gate, appearance_weight, birth_score,
                               T, S, F, A, max_age};
-    if (optimal) hipLaunchKernelGGL(track_associate_kernel<true>, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
-    else hipLaunchKernelGGL(track_associate_kernel<false>, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    if (motion) {                                                  // (its own fields were checked by the entry)
+        TrackMotionArgs m = *motion;
+        static_cast<TrackAssocArgs &>(m) = a;
+        if (optimal)
+            hipLaunchKernelGGL((track_associate_kernel<true, false, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), m);
+        else
+            hipLaunchKernelGGL((track_associate_kernel<false, false, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), m);
+    } else if (optimal) {
+        hipLaunchKernelGGL(track_associate_kernel<true>, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    } else {
+        hipLaunchKernelGGL(track_associate_kernel<false>, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    }
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }
@@ -510,6 +625,27 @@ extern "C" int air_track_associate_optimal(const float *what, const float *boxes
     return track_associate_launch(true, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score, max_age,
                                   track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last, track_length,
                                   track_gaps, state_counts, stream);
+}
+
+extern "C" int air_track_associate_motion(const float *what, const float *where, const float *boxes, const float *score,
+                                          const int *num_objects, int T, int S, int F, int R, int A, int H, int W, double iou_gate,
+                                          double appearance_weight, double birth_score, int max_age, int matching, double q_shift,
+                                          double q_scale, double measurement_noise, double velocity_var, int *track_id,
+                                          signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,
+                                          int *track_first, int *track_last, int *track_length, int *track_gaps, int *state_counts,
+                                          float *pred_where, float *pred_boxes, void *stream) {
+    AIR_REQUIRE(where && pred_where && pred_boxes, AIR_E_NULL);
+    AIR_REQUIRE(matching == 0 || matching == 1, AIR_E_SHAPE);
+    AIR_REQUIRE(H >= 1 && W >= 1, AIR_E_SHAPE);
+    AIR_REQUIRE(traj_noise_check(q_shift, q_scale, measurement_noise, velocity_var) == AIR_OK, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(where) && air_aligned16(pred_where) && air_aligned16(pred_boxes), AIR_E_ALIGN);
+    TrackMotionArgs m = {};
+    m.where = where, m.pred_where = pred_where, m.pred_boxes = pred_boxes;
+    m.q[0] = q_shift, m.q[1] = q_scale, m.r = measurement_noise, m.velocity_var = velocity_var;
+    m.Wf = (float)W, m.Hf = (float)H;
+    return track_associate_launch(matching == 1, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score,
+                                  max_age, track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last,
+                                  track_length, track_gaps, state_counts, stream, &m);
 }
 
 extern "C" int air_track_associate_stream(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,

@@ -7,6 +7,7 @@
 // the row of a track in a frame is a count of integers in one fixed order; no floating-point atomics: the same bits run to run.
 #include <limits.h>
 #include "scene_device.h"
+#include "traj_device.h"
 
 #define TRAJ_THREADS 256                 // air_track_fill: four wavefronts, one (row, column) each
 #define TRAJ_SMOOTH_THREADS 64           // air_track_smooth: one wavefront per sequence -- a dependent chain per lane, no cross-wave traffic
@@ -36,43 +37,8 @@ struct TrajSmoothArgs {
     int T, S, F, C, Hz, max_age, H, W;
 };
 
-struct TrajCov {
-    double xx, xv, vv;
-};
-
-// predict: a = Pxx + Pxv, b = Pxv + Pvv, Pxx- = (a + b) + q4, Pxv- = b + q2, Pvv- = Pvv + q
-__device__ __forceinline__ TrajCov traj_predict_cov(const TrajCov p, double q, double q2, double q4) {
-#pragma clang fp contract(off)
-    const double a = p.xx + p.xv, b = p.xv + p.vv;
-    TrajCov o;
-    o.xx = (a + b) + q4;
-    o.xv = b + q2;
-    o.vv = p.vv + q;
-    return o;
-}
-
-// The update and the backward step, shared by track_smooth_kernel and the stream kernels as TEXT (the statements are those the one-shot
-// kernel has always had, so its code object does not change with the sharing; a function would be inlined into another register
-// allocation).  Both are used under `#pragma clang fp contract(off)`.
-// update with the sighting z:  s = Pxx- + r, kx = Pxx- / s, kv = Pxv- / s, P = P- - k P-;  e = z - x-, x = x- + kx e, v = v- + kv e
-#define TRAJ_UPDATE(P, Pp, x, v, xp, vp, z, r_)                                                                               \
-    {                                                                                                                         \
-        double kx[2], kv[2];                                                                                                  \
-        _Pragma("unroll") for (int c = 0; c < 2; ++c) {                                                                       \
-            const double sn = Pp[c].xx + r_;                                                                                  \
-            kx[c] = Pp[c].xx / sn;                                                                                            \
-            kv[c] = Pp[c].xv / sn;                                                                                            \
-            P[c].xx = Pp[c].xx - kx[c] * Pp[c].xx;                                                                            \
-            P[c].xv = Pp[c].xv - kx[c] * Pp[c].xv;                                                                            \
-            P[c].vv = Pp[c].vv - kv[c] * Pp[c].xv;                                                                            \
-        }                                                                                                                     \
-        _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                                       \
-            const int cl = (c & 1) ? 0 : 1; /* [sx, tx, sy, ty]: the odd components are shifts */                             \
-            const double e = z[c] - xp[c];                                                                                    \
-            x[c] = xp[c] + kx[cl] * e;                                                                                        \
-            v[c] = vp[c] + kv[cl] * e;                                                                                        \
-        }                                                                                                                     \
-    }
+// The predict step and the update (TRAJ_UPDATE) are traj_device.h's: the tracker's motion state runs the same text.  The backward step
+// is shared by track_smooth_kernel and the stream kernels as TEXT, like the update.
 // back: (xs, vs) of frame f in place from those of frame f + 1; w: the planes of frame f, wn: of frame f + 1, `plane` apart
 #define TRAJ_BACK(w, wn, plane, xs, vs)                                                                                       \
     {                                                                                                                         \
@@ -96,8 +62,8 @@ __device__ __forceinline__ TrajCov traj_predict_cov(const TrajCov p, double q, d
         }                                                                                                                     \
     }
 
-// the rule's arguments, one-shot and stream alike (host code; a NaN fails every comparison)
-static int traj_noise_check(double q_shift, double q_scale, double r, double velocity_var) {
+// the rule's arguments, one-shot and stream alike, and air_track_associate_motion's (host code; a NaN fails every comparison)
+int traj_noise_check(double q_shift, double q_scale, double r, double velocity_var) {
     AIR_REQUIRE(q_shift > 0.0 && q_scale > 0.0 && r > 0.0 && velocity_var >= 0.0, AIR_E_SHAPE);
     AIR_REQUIRE(r >= TRAJ_R_MIN && r <= TRAJ_R_MAX, AIR_E_SHAPE);
     AIR_REQUIRE(q_shift / r >= TRAJ_Q_OVER_R_MIN && q_shift / r <= TRAJ_Q_OVER_R_MAX, AIR_E_SHAPE);

@@ -136,6 +136,12 @@ def main(argv=None):
                          "likelihood on the device (AIRonMNIST.fit_track_noise: no ground truth is read) and log them as "
                          "<name>_track_noise_fit with loglik / n_innovations and the same figure at the current defaults; ZOOM > 0 "
                          "refines the grid ZOOM times around the best cell (needs --eval-batches 1)")
+    ap.add_argument("--track-motion", nargs="?", const="", default=None, metavar="QS,QC,R,VV",
+                    help="with --track-eval: match every track against where a per-track Kalman filter predicts it to be, not against "
+                         "its last box (track.SequenceTracker's motion): no value = the default noise terms, QS,QC,R,VV = process noise "
+                         "of shifts and scales, measurement noise, prior variance of the rate.  With --track-fit-noise the identity "
+                         "figures are also logged with motion at the defaults and at the fitted terms (<name>_motion_defaults, "
+                         "<name>_motion_fit); does not apply to --track-stream (out of scope on a stream)")
     ap.add_argument("--track-matching", choices=("greedy", "optimal"), default=None,
                     help="with --track-eval: how a frame's objects are matched to the live tracks (track.SequenceTracker's matching): "
                          "greedy (the default) or the optimal assignment of the whole frame (Hungarian, air_track_associate_optimal)")
@@ -251,6 +257,18 @@ def main(argv=None):
             ap.error("--track-fit-noise goes with --track-eval")
         if args.track_fit_noise < 0 or (args.track_fit_noise > 0 and args.eval_batches > 1):
             ap.error("--track-fit-noise needs ZOOM >= 0, and ZOOM > 0 needs --eval-batches 1 (the zoom re-runs on one batch's tracks)")
+    track_motion = None
+    if args.track_motion is not None:
+        if track_eval is None:
+            ap.error("--track-motion goes with --track-eval")
+        track_motion = True
+        if args.track_motion:
+            try:
+                qs, qc, r, vv = (float(v) for v in args.track_motion.split(","))
+                from attend_infer_repeat_amd.track import check_motion
+                track_motion = check_motion(dict(process_noise=(qs, qc), measurement_noise=r, velocity_var=vv))
+            except ValueError as e:
+                ap.error("--track-motion needs QS,QC,R,VV inside the smoother's noise domain or no value, got %r (%s)" % (args.track_motion, e))
     track_smooth = None
     if args.track_smooth is not None or args.track_predict is not None:
         if track_eval is None:
@@ -421,7 +439,8 @@ def main(argv=None):
         seq_data = dict(imgs=raw["imgs"].astype("float32") / 255.0, boxes=raw["boxes"], instances=raw["instances"])
         before_track_log = log
         track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
-                                            smooth=track_smooth, matching=args.track_matching, identity=args.track_identity, **refine_kw)
+                                            smooth=track_smooth, matching=args.track_matching, identity=args.track_identity,
+                                            motion=track_motion, **refine_kw)
 
         stream_log = None
         if args.track_stream is not None:
@@ -444,6 +463,8 @@ def main(argv=None):
             def fit_log(train_itr):
                 n = min(max(args.eval_batches, 1), seq_data["imgs"].shape[0] // sequences_per_batch)
                 kw = dict(temporal=track_temporal, matching=args.track_matching, **refine_kw)
+                if track_motion is not None:
+                    kw["motion"] = track_motion                    # the tracks the terms are fitted to are the ones being evaluated
                 rec = dict(step=train_itr, data="test_track_noise_fit", zoom=args.track_fit_noise)
                 try:
                     for b in range(n):
@@ -464,6 +485,12 @@ def main(argv=None):
                     rec["refused"] = str(e)
                 print("{}: test_track_noise_fit {}".format(train_itr, {k: v for k, v in rec.items() if k not in ("step", "data")}))
                 writer.write(json.dumps(rec) + "\n"); writer.flush()
+                if track_motion is not None and "refused" not in rec:      # the identity figures with motion at the defaults and at the fit
+                    fitted = {k: fit[k] for k in tj.FIT_KEYS}
+                    for tag, terms in (("defaults", True), ("fit", fitted)):
+                        make_track_score_logger(air, seq_data, args.eval_batches, 'test_motion_' + tag, sequences_per_batch, writer,
+                                                temporal=track_temporal, matching=args.track_matching, identity=args.track_identity,
+                                                motion=terms, **refine_kw)(train_itr)
 
         def log(train_itr):                               # noqa: F811
             out = before_track_log(train_itr)

@@ -41,6 +41,40 @@ Optimal matching (matching="optimal": air_track_associate_optimal).  Steps 1, 2,
 The greedy rule takes the best pair first and can leave a second object without an admissible partner -- a spurious birth, a coasting
 track and an identity switch where two objects are close or cross; the optimal rule looks at the whole frame.
 
+MOTION (motion=True | dict: air_track_associate_motion, either matching; `reference_associate_motion` restates it).  The rule above has no
+notion of motion: a track that coasts over a frame or two while its object moves finds the object where its old box no longer reaches
+-- a new id, a fragmented track --, and in the frame after two objects cross each track's last box lies on the OTHER object.  With
+motion every live track is matched against where it is predicted to be.  Steps 1-5 (3' for "optimal") stay, with these exceptions:
+  state    each live track carries the FILTERED state of the trajectory filter (trajectory.py: start / predict / update) at its last
+           sighting, in float64: x[4] and v[4] over [sx, tx, sy, ty] and (Pxx, Pxv, Pvv) per noise class -- shifts tx, ty with q_shift,
+           scales sx, sy with q_scale --, 14 doubles per track.
+  step 1   an object whose `where` row holds a non-finite value is NONFINITE as well.
+  step 2   for live track k last sighted at frame l, m = f - l >= 1:  pred_where = float32([x_sx, x_tx + m v_tx, x_sy, x_ty + m v_ty]),
+           exactly trajectory._forecast_where(x, v, m): shifts extrapolated, scales held, one product and one sum in float64, rounded
+           once;  pred_box = tile.scene_boxes(pred_where, img_size) in fp32, operation by operation;  if any of its four values is not
+           finite, pred_box is the last-sighting box;  iou = the unchanged float64 box IoU of pred_box and the object's box.  The gate,
+           msd, aff, the profit and every tie order are unchanged.
+  booking a match (k, j): as in step 3, and the state advances by trajectory._filter_step, verbatim: m - 1 times without a sighting
+           (predict only, one frame at a time, never as m v), then once with z = the object's `where` row widened to float64.
+  a birth  starts the state: trajectory._filter_start(z, measurement_noise, velocity_var).
+Two more outputs, pred_where and pred_boxes [T, R, 4] fp32: for a MATCHED object the prediction of its track that the match was made
+against, zero in every other row.  process_noise=(q_shift, q_scale), measurement_noise and velocity_var are what `smooth=` and
+`fit_track_noise` use, and must lie in the smoother's supported domain (trajectory.check_arguments raises, the entry returns
+AIR_E_SHAPE).  EXACT CONSEQUENCES:
+  1. zero velocity.  While a track's v is exactly 0 its prediction is its last `where` row bit for bit -- every track at its first
+     association after its birth, and a track whose sightings all carry one value.  Hence on sequences whose tracks are all static,
+     with boxes == scene_boxes(where), every output equals air_track_associate's / _optimal's bit for bit; and so on ANY input with
+     F <= 2.
+  2. one filter.  For a MATCHED object of track i in frame f, pred_where equals the fc_where row of track i, column k = 1, of
+     trajectory.reference_smooth(..., horizon=1) run on this tracker's own output restricted to the frames 0 .. f - 1 (track_last
+     recomputed from track_id, num_tracks = the ids issued before f): the filter inside the tracker and the smoother behind it are
+     one filter, and the state at a track's last sighting is the forward pass of `reference_smooth` on that track, bit for bit.
+A track has v = 0 until its second sighting: an object displaced by more than its box in its first step is linked by neither rule.
+Out of scope: motion on a stream (StreamTracker refuses it: the carried state would need the 14 doubles per slot, and its chunk-
+invariance tests), a Mahalanobis gate, rates on scales in the prediction, feeding smoothed (non-causal) rows back, motion for the
+temporal proposer.  What motion does to MOTA / IDF1 on the parses of a TRAINED model is unmeasured (profiles/track_motion.txt says what
+was measured: the cost of the tail).
+
 The identity metric (air_track_score).  gt_boxes [R, G, 4], G <= 8: ground-truth slot g is the SAME object in every frame of a sequence,
 width <= 0 = absent in that frame.  The hypotheses of a frame are its objects j < n with track_id >= 0 and finite boxes.  map[g] = none
 at the start of a sequence.  Per frame:
@@ -66,7 +100,8 @@ prune.ParsePruner, propose.ParseProposer or tile.TiledSceneParser at R = S F row
 then, on the same engine stream, its own launch list of libair_hip.so entries (include/air_hip.h), ONE hipGraph after `capture()`
 whatever F is -- the frames are walked inside air_track_associate:
 
-  air_track_associate   the rule above (air_track_associate_optimal with matching="optimal": the same launch list otherwise);
+  air_track_associate   the rule above (air_track_associate_optimal with matching="optimal", air_track_associate_motion with motion=,
+                        which also reads the provider's `where` rows: the same launch list otherwise);
   air_track_owner       track_owner[r, y, x] (int16) = the track id of the step that owns the pixel, -1 for background.
 
 A particle_parse.ParticleParser is refused, with tile.TiledSceneParser's wording: its `parse()` takes no counts and its rows are particles
@@ -112,6 +147,8 @@ IDF_COUNTS = ("idtp", "gt_frames", "hyp_frames", "ids_with_overlap")
 MATCHINGS = ("greedy", "optimal")
 PROFIT_SCALE = 4294967296.0        # 2^32: profit = 1 + floor(aff * 2^32)
 DEFAULTS = dict(iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1)
+MOTION_ON_A_STREAM = ("motion is out of scope on a stream: the state carried between chunks would need each slot's filter state (14 "
+                      "doubles); track the sequence in one call with SequenceTracker(motion=...)")
 
 
 def check_arguments(max_steps, n_frames, n_rows=None, iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1,
@@ -199,11 +236,53 @@ def solve_assignment(profit, admissible):
     return col
 
 
-def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id_limit=None):
+def check_motion(motion):
+    """motion=None / False (off), True (trajectory.DEFAULTS) or a dict with any of process_noise, measurement_noise, velocity_var (the
+    rest: the defaults) -> None or the complete dict, its noise terms inside the smoother's supported domain (trajectory.check_arguments
+    raises its own messages outside it)"""
+    if motion is None or motion is False:
+        return None
+    from . import trajectory                                       # (lazily: trajectory imports this module)
+    terms = dict(trajectory.DEFAULTS)
+    if motion is not True:
+        if not isinstance(motion, dict):
+            raise ValueError("motion must be None, True or a dict with any of %s, got %r" % (", ".join(terms), motion))
+        unknown = sorted(set(motion) - set(terms), key=str)
+        if unknown:
+            raise ValueError("motion: unknown keys %r; it takes %s" % (unknown, ", ".join(terms)))
+        terms.update(motion)
+    q, r, vv = trajectory.check_arguments(1, 1, **terms)[5:]
+    return dict(process_noise=q, measurement_noise=r, velocity_var=vv)
+
+
+def _motion_predict(filt, m, last_box, img_size):
+    """step 2 with motion: (pred_where, pred_box) of a track m frames after its last sighting, from its filtered state there --
+    trajectory._forecast_where's row and its scene box in fp32; a box that is not finite falls back to the last-sighting box"""
+    import numpy as np
+    from .tile import scene_boxes
+    from .trajectory import _forecast_where
+    with np.errstate(all="ignore"):
+        pred_where = _forecast_where(filt[0], filt[1], m)
+        pred_box = scene_boxes(pred_where, img_size)
+    return pred_where, (pred_box if np.isfinite(pred_box).all() else last_box.copy())
+
+
+def _motion_advance(filt, m, z, q, r):
+    """booking a match with motion: the filtered state m frames on -- the m - 1 frames coasted over predicted one by one, then the
+    step with the sighting z (trajectory._filter_step, verbatim)"""
+    from .trajectory import _filter_step
+    for _ in range(m - 1):
+        filt = _filter_step(filt, None, q, r)[1]
+    return _filter_step(filt, z, q, r)[1]
+
+
+def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id_limit=None, motion=None):
     """Steps 1-5 of the rule on ONE frame (the code reference_associate and reference_associate_stream share).  live: slot -> dict(id,
     f, j, age, length, gaps, first, box, what) with the last sighting's box [4] and what row [A] as fp32 copies; fg: the frame's index
     (in the stream); what [T, A], boxes [T, 4], score [T]: the frame's fp32 rows; n: its clipped count; rule = (gate, w, birth,
     max_age, matching); margins: [gate_margin, round_margin], updated in place; id_limit: a birth at next_id == id_limit is OVERFLOW.
+    motion: None, or dict(where [T, 4] fp32, img_size, q [4], r, vv, pred_where [T, 4], pred_boxes [T, 4] (written)): the rule of
+    reference_associate_motion, a track then carries `filt`, its filtered state at the last sighting.
     Returns (state, ids, affinity, prev_frame, prev_slot, next_id, born [tracks], retired [(slot, track)] in ascending slot)."""
     import numpy as np
     gate, w, birth, max_age, matching = rule
@@ -214,17 +293,21 @@ def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id
     finite = []
     for j in range(n):                                             # 1. states
         ok = np.isfinite(boxes[j]).all() and np.isfinite(score[j]) and np.isfinite(what[j]).all()
+        ok = ok and (motion is None or np.isfinite(motion["where"][j]).all())
         state[j] = UNCONFIRMED if ok else NONFINITE                # (finite and open: settled below)
         if ok:
             finite.append(j)
     aff = {}                                                       # 2. affinity of the admissible pairs
+    pred = {}                                                      # motion: slot -> (pred_where, pred_box)
     for k, t in live.items():
         if not finite:
             break
         d = t["what"].astype(np.float64)[None, :] - what64[finite]
         msd = _sequential_sum(d * d) / np.float64(A)
+        if motion is not None:
+            pred[k] = _motion_predict(t["filt"], fg - t["f"], t["box"], motion["img_size"])
         for q, j in enumerate(finite):
-            iou = box_iou(t["box"], boxes[j])
+            iou = box_iou(t["box"] if motion is None else pred[k][1], boxes[j])
             margins[0] = min(margins[0], abs(iou - gate))
             if iou > gate:
                 aff[(k, j)] = (1.0 - w) * iou + w / (1.0 + float(msd[q]))
@@ -234,6 +317,10 @@ def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id
         state[j] = MATCHED
         ids[j], pf[j], ps[j] = t["id"], t["f"], t["j"]
         aff32[j] = np.float32(aff[(k, j)])
+        if motion is not None:
+            motion["pred_where"][j], motion["pred_boxes"][j] = pred[k]
+            with np.errstate(all="ignore"):
+                t["filt"] = _motion_advance(t["filt"], fg - t["f"], motion["where"][j].astype(np.float64), motion["q"], motion["r"])
         t["gaps"] += 1 if t["age"] > 0 else 0
         t["age"], t["length"], t["f"], t["j"] = 0, t["length"] + 1, fg, j
         t["box"], t["what"] = boxes[j].copy(), what[j].copy()
@@ -263,6 +350,9 @@ def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id
             continue
         state[j] = BORN
         live[free[0]] = dict(id=next_id, f=fg, j=j, age=0, length=1, gaps=0, first=fg, box=boxes[j].copy(), what=what[j].copy())
+        if motion is not None:
+            from .trajectory import _filter_start
+            live[free[0]]["filt"] = _filter_start(motion["where"][j].astype(np.float64), motion["r"], motion["vv"])
         born.append(live[free[0]])
         ids[j] = next_id
         next_id += 1
@@ -285,6 +375,14 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
     smallest |iou - iou_gate| over the pairs of step 2), round_margin [S] (the smallest aff(winner) - aff(runner-up) over the greedy
     rounds with more than one open admissible pair; inf without any).  matching="optimal": air_track_associate_optimal, step 3 by
     `solve_assignment`; return_margins then adds gate_margin only (there are no greedy rounds)."""
+    return _associate_sequences(what, boxes, score, num_objects, n_frames, iou_gate, appearance_weight, birth_score, max_age,
+                                return_margins, matching)
+
+
+def _associate_sequences(what, boxes, score, num_objects, n_frames, iou_gate, appearance_weight, birth_score, max_age, return_margins,
+                         matching, motion=None):
+    """the body of reference_associate and reference_associate_motion (motion: None, or dict(where [T, R, 4], img_size, q [4], r,
+    vv, return_state))"""
     import numpy as np
     what, boxes, score = (np.asarray(a, np.float32) for a in (what, boxes, score))
     n_in = np.asarray(num_objects).astype(np.int64)
@@ -297,6 +395,10 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
            "track_first": np.full((S, FT), -1, np.int32), "track_last": np.full((S, FT), -1, np.int32),
            "track_length": np.zeros((S, FT), np.int32), "track_gaps": np.zeros((S, FT), np.int32),
            "state_counts": np.zeros((S, 6), np.int32)}
+    if motion is not None:
+        out.update(pred_where=np.zeros((T, R, 4), np.float32), pred_boxes=np.zeros((T, R, 4), np.float32))
+        if motion["return_state"]:
+            out["motion_state"] = {}
     gate_margin, round_margin = np.full(S, np.inf), np.full(S, np.inf)
     for s in range(S):
         live = {}                                                  # slot -> the track
@@ -305,12 +407,18 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
 
         def retire(t):
             out["track_last"][s, t["id"]], out["track_length"][s, t["id"]], out["track_gaps"][s, t["id"]] = t["f"], t["length"], t["gaps"]
+            if motion is not None and motion["return_state"]:
+                out["motion_state"][(s, t["id"])] = t["filt"]
 
         for f in range(F):
             r = s * F + f
             n = int(min(max(n_in[r], 0), T))
+            frame_motion = None
+            if motion is not None:
+                frame_motion = dict(motion, where=motion["where"][:, r], pred_where=out["pred_where"][:, r],
+                                    pred_boxes=out["pred_boxes"][:, r])
             state, ids, aff32, pf, ps, next_id, born, retired = _associate_frame(live, next_id, f, what[:, r], boxes[:, r], score[:, r],
-                                                                                 n, rule, margins)
+                                                                                 n, rule, margins, motion=frame_motion)
             for t in born:
                 out["track_first"][s, t["id"]] = f
             for _, t in retired:
@@ -327,6 +435,32 @@ def reference_associate(what, boxes, score, num_objects, n_frames, iou_gate=0.1,
         if matching == "greedy":
             out["round_margin"] = round_margin
     return out
+
+
+def reference_associate_motion(what, where, boxes, score, num_objects, n_frames, img_size, iou_gate=0.1, appearance_weight=0.25,
+                               birth_score=0.5, max_age=1, matching="greedy", process_noise=None, measurement_noise=None,
+                               velocity_var=None, return_margins=False, return_state=False):
+    """air_track_associate_motion restated in numpy float64 (MOTION in the module text): reference_associate's arrays and rule
+    arguments, where [T, R, 4] fp32 = [sx, tx, sy, ty], img_size (H, W), and the noise terms of the trajectory filter (None: trajectory.
+    DEFAULTS; outside the supported domain: trajectory.check_arguments' messages).  Returns reference_associate's outputs (matching=
+    "optimal": air_track_associate_optimal's step 3) and pred_where, pred_boxes [T, R, 4] float32: for a MATCHED object the prediction
+    of its track that the match was made against, zero otherwise.  return_margins as in reference_associate (gate_margin over the IoUs
+    with the PREDICTED boxes).  return_state=True adds motion_state: (s, id) -> the filtered state (x, v, Pxx, Pxv, Pvv), float64 [4]
+    each over [sx, tx, sy, ty], of every track at its last sighting."""
+    import numpy as np
+    terms = {k: v for k, v in dict(process_noise=process_noise, measurement_noise=measurement_noise, velocity_var=velocity_var).items()
+             if v is not None}
+    terms = check_motion(terms or True)
+    (q_shift, q_scale), H, W = terms["process_noise"], int(img_size[0]), int(img_size[1])
+    if H < 1 or W < 1:
+        raise ValueError("img_size must be (H, W) with H, W >= 1, got %r" % (img_size,))
+    where = np.asarray(where, np.float32)
+    if where.shape != tuple(np.shape(what)[:2]) + (4,):
+        raise ValueError("where: expected %s, got %s" % (tuple(np.shape(what)[:2]) + (4,), where.shape))
+    motion = dict(where=where, img_size=(H, W), q=np.array([q_scale, q_shift, q_scale, q_shift], np.float64),
+                  r=terms["measurement_noise"], vv=terms["velocity_var"], return_state=bool(return_state))
+    return _associate_sequences(what, boxes, score, num_objects, n_frames, iou_gate, appearance_weight, birth_score, max_age,
+                                return_margins, matching, motion)
 
 
 # ---- streams: the state that outlives a call (include/air_hip.h states the layout) -------------------------------------------------------
@@ -786,9 +920,13 @@ class SequenceTracker(BoundStage):
     REFUSALS = TiledSceneParser.REFUSALS
 
     def __init__(self, provider, n_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
-                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy"):
+                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None):
+        """motion: None (every track is matched against its last-sighting box), True (against its predicted box, MOTION in the module
+        text, with trajectory.DEFAULTS) or a dict with any of process_noise=(q_shift, q_scale), measurement_noise, velocity_var --
+        what `smooth=` and `fit_track_noise` use"""
         self._rows = self.bind(provider)
         T, F, S = check_arguments(provider.T, n_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age, matching)
+        self.motion = check_motion(motion)
         import torch
         from . import hip as H
         self.provider, self.engine = provider, provider.engine
@@ -810,6 +948,8 @@ class SequenceTracker(BoundStage):
             self.track_first, self.track_last, self.track_length, self.track_gaps = z((S, FT)), z((S, FT)), z((S, FT)), z((S, FT))
             self.state_counts = z((S, 6))
             self.track_owner = z((R,) + self.img_size, torch.int16)
+            if self.motion is not None:
+                self.pred_where, self.pred_boxes = z((T, R, 4), torch.float32), z((T, R, 4), torch.float32)
         self._H = H
         self.scores = IdentityScores(self, S)
         self._score = self.scores.entries                          # (G, tau) -> buffers, plan, graph
@@ -823,13 +963,19 @@ class SequenceTracker(BoundStage):
         L, p = self._H.lib(), self._H._p
         Hi, Wi = self.img_size
         associate = "air_track_associate_optimal" if self.matching == "optimal" else "air_track_associate"
+        rows = (p(self._what), p(provider.boxes), p(provider.score), p(provider.num_objects))
+        rule = (self.iou_gate, self.appearance_weight, self.birth_score, self.max_age)
+        outputs = (p(self.track_id), p(self.obj_state), p(self.affinity), p(self.prev_frame), p(self.prev_slot), p(self.num_tracks),
+                   p(self.track_first), p(self.track_last), p(self.track_length), p(self.track_gaps), p(self.state_counts))
+        if self.motion is None:
+            args = rows + (T, S, F, R, self.A) + rule + outputs
+        else:                                                      # the one entry of both matchings, still one launch
+            associate, m = "air_track_associate_motion", self.motion
+            args = (rows[0], p(self._rows["where"])) + rows[1:] + (T, S, F, R, self.A, Hi, Wi) + rule + (
+                MATCHINGS.index(self.matching), *m["process_noise"], m["measurement_noise"], m["velocity_var"]) + outputs + (
+                p(self.pred_where), p(self.pred_boxes))
         self.segments = OrderedDict([
-            ("associate", [(getattr(L, associate),
-                            (p(self._what), p(provider.boxes), p(provider.score), p(provider.num_objects), T, S, F, R, self.A,
-                             self.iou_gate, self.appearance_weight, self.birth_score, self.max_age, p(self.track_id), p(self.obj_state),
-                             p(self.affinity), p(self.prev_frame), p(self.prev_slot), p(self.num_tracks), p(self.track_first),
-                             p(self.track_last), p(self.track_length), p(self.track_gaps), p(self.state_counts)),
-                            associate)]),
+            ("associate", [(getattr(L, associate), args, associate)]),
             ("owner", [(L.air_track_owner, (p(provider.owner), p(self.track_id), T, R, Hi, Wi, p(self.track_owner)),
                         "air_track_owner")])])
         self._plan = [e for seg in self.segments.values() for e in seg]
@@ -851,8 +997,10 @@ class SequenceTracker(BoundStage):
         if frames.numel() != self.R * Hi * Wi or frames.dim() < 2 or tuple(frames.shape[:2]) != (self.S, self.F):
             raise ValueError("expected frames [%d, %d, %d, %d], got %s" % (self.S, self.F, Hi, Wi, tuple(frames.shape)))
         base = par.parse(frames.reshape(self.R, Hi, Wi), *args, **kwargs)
-        self.check_same_buffers(base, dict(what=self._what, boxes=par.boxes, score=par.score, num_objects=par.num_objects,
-                                           owner=par.owner), "tracker", bound="provider")
+        expected = dict(what=self._what, boxes=par.boxes, score=par.score, num_objects=par.num_objects, owner=par.owner)
+        if getattr(self, "motion", None) is not None:              # the rows the filter reads
+            expected.update(where=self._rows["where"])
+        self.check_same_buffers(base, expected, "tracker", bound="provider")
         return base
 
     def track(self, frames, *args, **kwargs):
@@ -861,7 +1009,8 @@ class SequenceTracker(BoundStage):
         (-1 = none), obj_state [T, R] int8 (STATES), affinity [T, R] (aff of the match, 0 unless matched), prev_frame, prev_slot [T, R]
         int32 (the track's previous sighting, -1 unless matched), num_tracks [S] int32, track_first, track_last, track_length,
         track_gaps [S, F * T] int32 per id (-1 / -1 / 0 / 0 from num_tracks[s] on), state_counts [S, 6] int32, track_owner
-        [R, H, W] int16 (the track id a pixel belongs to, -1 = background or an object without a track).  Same stream contract as
+        [R, H, W] int16 (the track id a pixel belongs to, -1 = background or an object without a track); with motion also pred_where,
+        pred_boxes [T, R, 4] (for a MATCHED object the prediction of its track that the match was made against, else 0).  Same stream contract as
         SceneParser.parse: the work runs on the engine's stream, on return the caller's current stream is ordered after it, and the
         next call waits for the caller's reads before it overwrites them."""
         eng = self.engine
@@ -876,6 +1025,8 @@ class SequenceTracker(BoundStage):
                    prev_slot=self.prev_slot, num_tracks=self.num_tracks, track_first=self.track_first, track_last=self.track_last,
                    track_length=self.track_length, track_gaps=self.track_gaps, state_counts=self.state_counts,
                    track_owner=self.track_owner)
+        if self.motion is not None:
+            out.update(pred_where=self.pred_where, pred_boxes=self.pred_boxes)
         return out
 
     # ---- the identity metric ------------------------------------------------------------------------------------------------
@@ -927,7 +1078,9 @@ class StreamTracker(BoundStage):
     REFUSALS = SequenceTracker.REFUSALS
 
     def __init__(self, provider, chunk_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
-                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy"):
+                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None):
+        if motion is not None and motion is not False:
+            raise ValueError(MOTION_ON_A_STREAM)
         self._rows = self.bind(provider)
         T, F, S = check_arguments(provider.T, chunk_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age, matching)
         import numpy as np

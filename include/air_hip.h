@@ -968,6 +968,32 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *      predecessor) until a free column is reached, and moves the rows along that path.  One wavefront runs it, lane = column.
  *      Every matched pair: the object is 1 MATCHED, track_id, prev_frame / prev_slot, affinity = aff rounded once to fp32 and the
  *      track's gaps, age, length and last sighting as in the greedy step 3.  Matching ignores birth_score; a NaN never matches.
+ * air_track_associate_motion: air_track_associate (matching 0) or air_track_associate_optimal (matching 1) -- the same inputs, checks,
+ *   outputs and steps -- with every live track matched against where it is PREDICTED to be.  where[T,R,4] = [sx, tx, sy, ty] are the
+ *   objects' rows, H x W the image (air_parse_objects' boxes are formed on it).  STATE: each live track carries the FILTERED state of
+ *   air_track_smooth's filter at its last sighting, in float64: x[4] and v[4] over [sx, tx, sy, ty], and (Pxx, Pxv, Pvv) per noise
+ *   class (shifts tx, ty with q_shift; scales sx, sy with q_scale): 14 doubles per slot, in LDS.  The exceptions to the rule above:
+ *   1. an object whose where row holds a non-finite value is 5 NONFINITE as well.
+ *   2. for live track k last sighted at frame l, m = f - l >= 1:  pred_where = float32([x_sx, x_tx + m v_tx, x_sy, x_ty + m v_ty]) --
+ *      air_track_smooth's forecast row: shifts extrapolated, scales held, one product and one sum in float64, rounded once;
+ *      pred_box = air_parse_objects' box of pred_where on the W x H image, operation by operation in fp32; if any of its four values
+ *      is not finite, pred_box is the last-sighting box.  iou = the same float64 box IoU of pred_box and the object's box.  The gate,
+ *      msd, aff, the profit and every tie order are unchanged.
+ *   Booking a match (k, j): as in step 3, and the state advances by air_track_smooth's statements: m - 1 times `predict` alone (the
+ *      frames coasted over, one by one, never as m v), then `predict` and `update` with z = the object's where row widened to
+ *      float64.  A birth starts the state: x = z, v = 0, Pxx = measurement_noise, Pxv = 0, Pvv = velocity_var.
+ *   Two more outputs, every element written: pred_where / pred_boxes [T,R,4] (fp32) = for a MATCHED object the pred_where / pred_box
+ *   of its track that the match was made against, zero in every other row.
+ *   EXACT CONSEQUENCES.  (1) While a track's v is exactly 0 its pred_where is its last where row bit for bit -- every track at its
+ *   first association after its birth, and a track whose sightings all carry one value: on sequences whose tracks are all static with
+ *   boxes = the boxes of the where rows, and on any input with F <= 2, every shared output equals air_track_associate's /
+ *   air_track_associate_optimal's bit for bit.  (2) For a MATCHED object of track i in frame f, pred_where is the fc_where row of
+ *   track i, column k = 1, of air_track_smooth with horizon 1 run on this entry's own outputs restricted to the frames 0 .. f - 1:
+ *   the filter inside the tracker and the smoother behind it are one filter.  A track has v = 0 until its second sighting: an
+ *   object displaced by more than its box in its first step is not linked, with or without motion.
+ *   AIR_E_SHAPE also: H or W < 1, matching outside {0, 1}, noise terms outside air_track_smooth's supported domain (below).  where,
+ *   pred_where and pred_boxes 16-byte aligned (AIR_E_ALIGN).  A stream entry with motion does not exist: the carried state would
+ *   need the 14 doubles per slot.
  * air_track_idf: the IDF1 counts (Ristani et al. 2016), one 256-thread workgroup per sequence, the frames walked inside.  Hypotheses
  *   and present ground-truth slots as in air_track_score.  overlap[S,G,n_ids] (int32, every element written): overlap[s,g,id] = the
  *   number of (frame, hypothesis) pairs in which present g and a hypothesis with that id have float64 box IoU > tau, strictly (an id
@@ -1023,6 +1049,12 @@ AIR_ENGINE_API int air_track_associate_optimal(const float *what, const float *b
                     int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
                     int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,
                     int *track_first, int *track_last, int *track_length, int *track_gaps, int *state_counts, void *stream);
+AIR_ENGINE_API int air_track_associate_motion(const float *what, const float *where, const float *boxes, const float *score,
+                    const int *num_objects, int T, int S, int F, int R, int A, int H, int W, double iou_gate, double appearance_weight,
+                    double birth_score, int max_age, int matching, double q_shift, double q_scale, double measurement_noise,
+                    double velocity_var, int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
+                    int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps, int *state_counts,
+                    float *pred_where, float *pred_boxes, void *stream);
 AIR_ENGINE_API int air_track_idf(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
                     int T, int G, int S, int F, int R, int n_ids, int *overlap, int *seq_idf, void *stream);
 AIR_ENGINE_API int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,

@@ -30,6 +30,15 @@ exits with an error -- and the first chunk of a fresh stream with the one-shot t
 before each turn, and the ratio is reported; the whole calls (`track()` and `push()`, provider included) likewise; the stream launch
 alone with valid = 0; no bar on time.
 
+--motion measures motion-predicted association instead (track.SequenceTracker(motion=True): air_track_associate_motion): for every
+F in --frames, at --rows provider rows, ONE captured SceneParser and over it, for both matchings, a captured tracker without motion
+(air_track_associate / air_track_associate_optimal: the kernels of the commit before, whose instantiations did not change) and one
+with motion at the default noise terms.  The motion tracker's outputs, pred_where and pred_boxes included, must agree bit for bit with
+track.reference_associate_motion on the read-back of the same parse over the sequences whose decisions are 1e-9 from flipping, or the
+tool exits with an error; the share of frames on which motion changes a track id is printed.  Then the two captured tails (associate +
+owner) are timed in turns (plain, motion, plain, motion) in this process on the engine's stream, and the ratio is reported, with the
+two association entries launched eagerly on their own; no bar on time.
+
 Timing: a warm-up, then 5 repeats of --iters calls each between device events; the median repeat is reported with all repeats.  The
 provider and the tracked route alternate inside one process."""
 import argparse
@@ -297,6 +306,75 @@ def one_chunk_size(args, C):
     return res
 
 
+def one_motion_length(args, F):
+    from attend_infer_repeat_amd import _lib, track
+    from attend_infer_repeat_amd.engine_config import EngineConfig
+    from attend_infer_repeat_amd.parse import SceneParser
+    cfg = EngineConfig()
+    R = args.rows
+    if R % F:
+        raise SystemExit("--rows %d is no multiple of %d frames" % (R, F))
+    S, T = R // F, int(cfg.max_steps)
+    ps = SceneParser(cfg, R, seed=0)
+    ps.capture()
+    eng, dev = ps.engine, ps.engine.device
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    start = torch.rand(S, *cfg.img_size, generator=gen) * (torch.rand(S, *cfg.img_size, generator=gen) > 0.8)
+    frames = torch.stack([torch.roll(start, shifts=(f, f // 2), dims=(1, 2)) for f in range(F)], 1).contiguous().to(dev)
+    counts = (torch.arange(R, device=dev) % (T + 1)).to(torch.int32)
+    host = lambda t: t.cpu().numpy()
+    res = dict(frames=F, sequences=S, rows=R, max_steps=T)
+    for matching in track.MATCHINGS:
+        plain = track.SequenceTracker(ps, F, birth_score=0.0, matching=matching)
+        plain.capture()
+        moved = track.SequenceTracker(ps, F, birth_score=0.0, matching=matching, motion=True)
+        moved.capture()
+        plain_ids = host(plain.track(frames, counts)["track_id"]).copy()
+        out = moved.track(frames, counts)
+        torch.cuda.synchronize()
+        ref = track.reference_associate_motion(host(out["what"]).reshape(T, R, -1), host(out["where"]).reshape(T, R, 4), host(out["boxes"]),
+                                               host(out["score"]), host(out["num_objects"]), F, moved.img_size, birth_score=0.0,
+                                               matching=matching, return_margins=True)
+        safe = (ref["gate_margin"] >= 1e-9) & (ref.get("round_margin", np.full(S, np.inf)) >= 1e-9)
+        rows = np.repeat(safe, F)
+        same = lambda a, b: bool((np.ascontiguousarray(a).view(np.uint8) == np.ascontiguousarray(b).view(np.uint8)).all())
+        agree = {k: same(host(out[k])[:, rows], ref[k][:, rows])
+                 for k in ("track_id", "obj_state", "affinity", "prev_frame", "prev_slot", "pred_where", "pred_boxes")}
+        for k in ("num_tracks", "track_first", "track_last", "track_length", "track_gaps", "state_counts"):
+            agree[k] = same(host(out[k])[safe], ref[k][safe])
+        differ = (host(out["track_id"]) != plain_ids).any(0)
+        r = dict(sequences_inside_margins=int(safe.sum()), agreement=agree, tracks=int(ref["num_tracks"].sum()),
+                 tracks_without_motion=int(host(plain.num_tracks).sum()),
+                 state_counts=dict(zip(track.STATES, ref["state_counts"].sum(0).tolist())),
+                 frames_where_motion_changes_an_id=float(differ.mean()))
+        res[matching] = r
+        if not all(agree.values()):
+            print(json.dumps(res))
+            raise SystemExit("the motion tracker and the host reference disagree (%s): %r" % (matching, agree))
+        turns = {"plain": [], "motion": []}
+        for _ in range(2):
+            for name, t in (("plain", plain), ("motion", moved)):
+                turns[name].append(median_ms(lambda: eng._replay_or_run(t._graph, t._plan), args.iters, eng.stream))
+        for name, v in turns.items():
+            r["tail_%s_turns_ms" % name] = [m for m, _ in v]
+            r["tail_%s_repeats_ms" % name] = [q for _, q in v]
+        r["tail_plain_ms"], r["tail_motion_ms"] = (statistics.median(r["tail_%s_turns_ms" % n]) for n in ("plain", "motion"))
+        r["motion_over_plain_tail"] = r["tail_motion_ms"] / r["tail_plain_ms"]
+        per = {}
+        for _ in range(7):
+            for (fn, a, name) in plain._plan[:1] + moved._plan[:1]:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(eng.stream)
+                _lib.check(fn(*a, eng._sp()), name)
+                e1.record(eng.stream)
+                e1.synchronize()
+                per.setdefault(name, []).append(e0.elapsed_time(e1) * 1e3)
+        r["eager_launch_us"] = {k: statistics.median(v) for k, v in per.items()}
+        plain.release_graphs(); moved.release_graphs()
+    ps.release_graphs()
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 32])
@@ -306,6 +384,7 @@ def main(argv=None):
     ap.add_argument("--identity", action="store_true")
     ap.add_argument("--stream", type=int, nargs="+", default=None, metavar="CHUNK")
     ap.add_argument("--stream-chunks", type=int, default=4)
+    ap.add_argument("--motion", action="store_true")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("track_bench measures on the GPU; there is no CPU fallback")
@@ -315,6 +394,14 @@ def main(argv=None):
         for r in res["chunks"]:
             for k, v in r.items():
                 print("CHUNK=%-4d %-40s %s" % (r["chunk_frames"], k, v))
+        return res
+    if args.motion:
+        res = dict(tool="track_bench --motion", device=torch.cuda.get_device_name(0), lengths=[one_motion_length(args, F) for F in args.frames])
+        print(json.dumps(res))
+        for r in res["lengths"]:
+            for matching in ("greedy", "optimal"):
+                for k, v in r[matching].items():
+                    print("F=%-4d %-8s %-36s %s" % (r["frames"], matching, k, v))
         return res
     res = dict(tool="track_bench", device=torch.cuda.get_device_name(0), lengths=[one_length(args, F) for F in args.frames])
     print(json.dumps(res))
