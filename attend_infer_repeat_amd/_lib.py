@@ -249,6 +249,10 @@ SIGNATURES = {
     "air_track_associate_motion": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_double, c_int, c_int, ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_double, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "air_track_associate_motion_gated": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
+                                                 ctypes.c_double, ctypes.c_double, c_int, c_int, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, P, P, P, P, P, P, P, P, P, P, P, P,
+                                                 P, P, P]),
     "air_track_associate_stream": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, c_int, P, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "air_track_idf": (c_int, [P, P, P, P, ctypes.c_double, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),

@@ -6,6 +6,8 @@
 //   air_track_score_stream: air_track_score with its map, its per-slot counts, its counters and its IoU sum carried in a state;
 //   air_track_associate_motion: the same kernel (either matching) with a per-track Kalman filter: every pair is gated and ranked by the
 //                        IoU with the box the track is PREDICTED to have, and a match or a birth advances or starts the filter;
+//   air_track_associate_motion_gated: the motion kernel with the pair rule replaced: every pair is gated by its squared Mahalanobis
+//                        distance from the filter's predicted state (mean AND covariance) and ranked by 1 / (1 + that distance);
 //   air_track_associate_optimal: the same kernel with step 3 replaced: the assignment of the largest summed int64 profit, by a
 //                        shortest-augmenting-path Hungarian that one wavefront runs (lane = column);
 //   air_track_owner:     the parse's owner maps relabelled from step to track id (int8 in, int16 out): a streaming pass;
@@ -78,6 +80,24 @@ struct TrackMotionArgs : TrackAssocArgs {
 };
 // the filtered state of slot k, value i: mstate_s[i * 32 + k]
 enum { TRACK_MS_X = 0, TRACK_MS_V = 4, TRACK_MS_P = 8, TRACK_MS_DOUBLES = 14 };      // class c: TRACK_MS_P + 3 c (xx, xv, vv)
+// the Mahalanobis gate: the motion arguments, the gate (a squared distance) and the d2 of every matched pair
+struct TrackGateArgs : TrackMotionArgs {
+    double gate_d2;
+    float *pred_d2;
+};
+// the PREDICTED state of slot k in this frame, value i: gstate_s[i * 32 + k] -- xp over [sx, tx, sy, ty], s = Pxx- + r per class
+enum { TRACK_GS_X = 0, TRACK_GS_S = 4, TRACK_GS_DOUBLES = 6 };     // class 0: the shifts, class 1: the scales (TRAJ_UPDATE's cl)
+
+// d2 of slot k's predicted state and the `where` row w: e = z - xp, ((e0^2 / s1 + e1^2 / s0) + e2^2 / s1) + e3^2 / s0 -- one product
+// and one quotient per term, added in the order [sx, tx, sy, ty].  The pair loop and the row's read-out both run it: the same bits.
+__device__ __forceinline__ double track_gate_d2(const double *gstate_s, int k, const float4 w) {
+#pragma clang fp contract(off)
+    const double *gs = gstate_s + k;
+    const double s0 = gs[(TRACK_GS_S + 0) * TRACK_MAXT], s1 = gs[(TRACK_GS_S + 1) * TRACK_MAXT];
+    const double e0 = (double)w.x - gs[(TRACK_GS_X + 0) * TRACK_MAXT], e1 = (double)w.y - gs[(TRACK_GS_X + 1) * TRACK_MAXT],
+                 e2 = (double)w.z - gs[(TRACK_GS_X + 2) * TRACK_MAXT], e3 = (double)w.w - gs[(TRACK_GS_X + 3) * TRACK_MAXT];
+    return ((e0 * e0 / s1 + e1 * e1 / s0) + e2 * e2 / s1) + e3 * e3 / s0;
+}
 
 // The assignment of the frame's finite objects (rows, inserted in ascending j) to the 64 columns of one wavefront -- column k < 32 is
 // track slot k, column 32 + j is "object j stays unmatched" -- that maximises the summed profit: profit_s[k * 32 + j] >= 1 for an
@@ -145,10 +165,19 @@ __device__ __forceinline__ int track_solve_wave(const long long *profit_s, const
 // last-sighting box otherwise, and in step 5 lane k advances (a matched track: the coasted frames predicted one by one, then the
 // update with the new sighting's `where` row) or starts (a born track) its state.  An object with a non-finite `where` value is
 // NONFINITE.  The bits of every other output are those of the kernel without MOTION while every track's rate is exactly 0.
-template <bool OPTIMAL, bool STREAM = false, bool MOTION = false> __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(
-    std::conditional_t<STREAM, TrackStreamArgs, std::conditional_t<MOTION, TrackMotionArgs, TrackAssocArgs>> a) {
+// GATED (with MOTION): in step 1 lane k also forms the PREDICTED state of its slot for this frame -- the frames coasted over predicted
+// one by one, then one more predict: xp[4] and s = Pxx- + r per class, 6 doubles per slot in LDS, the values step 5 computes again
+// when it books a match --; the pair loop gates on d2 <= gate_d2 and ranks by (1 - w) / (1 + d2) + w / (1 + msd), with no box IoU; the
+// row's read-out writes float(d2) of the matched pair.  Everything else is the MOTION kernel's.
+template <bool OPTIMAL, bool STREAM = false, bool MOTION = false, bool GATED = false>
+__global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(
+    std::conditional_t<STREAM, TrackStreamArgs,
+                       std::conditional_t<GATED, TrackGateArgs, std::conditional_t<MOTION, TrackMotionArgs, TrackAssocArgs>>> a) {
 #pragma clang fp contract(off)
     static_assert(!(STREAM && MOTION), "the motion state is not carried across the chunks of a stream");
+    static_assert(!GATED || MOTION, "the gate reads the covariance of the motion filter");
+    static_assert(!(STREAM && GATED), "no gate on a stream: there is no motion state there");
+    __shared__ double gstate_s[GATED ? TRACK_GS_DOUBLES * TRACK_MAXT : 1];       // GATED only
     __shared__ double mstate_s[MOTION ? TRACK_MS_DOUBLES * TRACK_MAXT : 1];      // MOTION only, as the three below
     __shared__ float4 owhere_s[MOTION ? TRACK_MAXT : 1];           // the frame's `where` rows
     __shared__ float4 pwhere_s[MOTION ? TRACK_MAXT : 1], pbox_s[MOTION ? TRACK_MAXT : 1];      // the slots' predicted rows and boxes
@@ -234,6 +263,32 @@ template <bool OPTIMAL, bool STREAM = false, bool MOTION = false> __global__ __l
                                      (float)(ms[(TRACK_MS_X + 3) * TRACK_MAXT] + m * ms[(TRACK_MS_V + 3) * TRACK_MAXT]));
                     pb = attention_box4(pw, a.Wf, a.Hf);
                     if (!track_finite4(pb)) pb = tbox_s[k];        // a prediction that leaves fp32: the last-sighting box
+                    if constexpr (GATED) {                         // the predicted state m frames on, by the statements of step 5
+                        const double q2[2] = {0.5 * a.q[0], 0.5 * a.q[1]}, q4[2] = {0.25 * a.q[0], 0.25 * a.q[1]};
+                        double x[4], v[4];
+                        TrajCov P[2];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) x[c] = ms[(TRACK_MS_X + c) * TRACK_MAXT], v[c] = ms[(TRACK_MS_V + c) * TRACK_MAXT];
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) {
+                            P[c].xx = ms[(TRACK_MS_P + 3 * c) * TRACK_MAXT];
+                            P[c].xv = ms[(TRACK_MS_P + 3 * c + 1) * TRACK_MAXT];
+                            P[c].vv = ms[(TRACK_MS_P + 3 * c + 2) * TRACK_MAXT];
+                        }
+                        const int mi = fg - t_f[k];                // 1 .. max_age + 1
+                        for (int i = 1; i < mi; ++i) {
+#pragma unroll
+                            for (int c = 0; c < 2; ++c) P[c] = traj_predict_cov(P[c], a.q[c], q2[c], q4[c]);
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) x[c] = x[c] + v[c];
+                        }
+                        double *gs = gstate_s + k;
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) gs[(TRACK_GS_X + c) * TRACK_MAXT] = x[c] + v[c];
+#pragma unroll
+                        for (int c = 0; c < 2; ++c)
+                            gs[(TRACK_GS_S + c) * TRACK_MAXT] = traj_predict_cov(P[c], a.q[c], q2[c], q4[c]).xx + a.r;
+                    }
                 }
                 pwhere_s[k] = pw;
                 pbox_s[k] = pb;
@@ -254,8 +309,9 @@ template <bool OPTIMAL, bool STREAM = false, bool MOTION = false> __global__ __l
             const int k = p >> 5, j = p & 31;
             double val = -1.0;
             if (t_live[k] && j < n && track_finite4(obox_s[j]) && isfinite(oscore_s[j]) && !nonfinite_s[j]) {
-                double iou;
-                if constexpr (MOTION) iou = box_iou_f64(pbox_s[k], obox_s[j]);
+                double iou;                                        // GATED: d2 in its place
+                if constexpr (GATED) iou = track_gate_d2(gstate_s, k, owhere_s[j]);
+                else if constexpr (MOTION) iou = box_iou_f64(pbox_s[k], obox_s[j]);
                 else iou = box_iou_f64(tbox_s[k], obox_s[j]);
                 const float *wk;
                 if constexpr (STREAM) {                            // sighted in this chunk: in place; before it: the state's copy
@@ -286,8 +342,13 @@ template <bool OPTIMAL, bool STREAM = false, bool MOTION = false> __global__ __l
                     sum = sum + d * d;
                 }
                 const double msd = sum / (double)A;
-                const double aff = (1.0 - a.w) * iou + a.w / (1.0 + msd);
-                if (iou > a.iou_gate) val = aff;
+                if constexpr (GATED) {                             // (a NaN or an inf fails the gate; iou_gate is not applied)
+                    const double aff = (1.0 - a.w) / (1.0 + iou) + a.w / (1.0 + msd);
+                    if (iou <= a.gate_d2) val = aff;
+                } else {
+                    const double aff = (1.0 - a.w) * iou + a.w / (1.0 + msd);
+                    if (iou > a.iou_gate) val = aff;
+                }
             }
             aff_s[p] = val;
             if constexpr (OPTIMAL) profit_s[p] = val >= 0.0 ? 1 + (long long)floor(val * 4294967296.0) : -1;      // (exact: a power of two)
@@ -479,6 +540,11 @@ template <bool OPTIMAL, bool STREAM = false, bool MOTION = false> __global__ __l
                     if (mk < 0) pw = pb = make_float4(0.f, 0.f, 0.f, 0.f);
                     reinterpret_cast<float4 *>(a.pred_where)[row] = pw;
                     reinterpret_cast<float4 *>(a.pred_boxes)[row] = pb;
+                    if constexpr (GATED) {                         // (gstate_s[mk] is this frame's: a matched slot stays its track's)
+                        float d2 = 0.f;
+                        if (mk >= 0) d2 = (float)track_gate_d2(gstate_s, mk, owhere_s[tid]);
+                        a.pred_d2[row] = d2;
+                    }
                 }
                 atomicAdd(&counts_s[state], 1);                    // integer adds in LDS: the order does not matter
             }
@@ -573,7 +639,8 @@ static int track_associate_launch(bool optimal, const float *what, const float *
                                   int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
                                   int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
                                   int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
-                                  int *state_counts, void *stream, const TrackMotionArgs *motion = nullptr) {
+                                  int *state_counts, void *stream, const TrackMotionArgs *motion = nullptr,
+                                  const TrackGateArgs *gated = nullptr) {
     AIR_REQUIRE(what && boxes && score && num_objects && track_id && obj_state && affinity && prev_frame && prev_slot && num_tracks &&
                 track_first && track_last && track_length && track_gaps && state_counts, AIR_E_NULL);
     AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && S > 0 && F > 0 && A > 0, AIR_E_SHAPE);
@@ -591,7 +658,16 @@ static int track_associate_launch(bool optimal, const float *what, const float *
     const TrackAssocArgs a = {what, boxes, score, num_objects, track_id, prev_frame, prev_slot, num_tracks, track_first, track_last,
                               track_length, track_gaps, state_counts, affinity, obj_state, iou_gate, appearance_weight, birth_score,
                               T, S, F, A, max_age};
-    if (motion) {                                                  // (its own fields were checked by the entry)
+    if (gated) {                                                   // (its own fields were checked by the entry)
+        TrackGateArgs g = *gated;
+        static_cast<TrackAssocArgs &>(g) = a;
+        if (optimal)
+            hipLaunchKernelGGL((track_associate_kernel<true, false, true, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0,
+                               air_stream(stream), g);
+        else
+            hipLaunchKernelGGL((track_associate_kernel<false, false, true, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0,
+                               air_stream(stream), g);
+    } else if (motion) {                                           // (its own fields were checked by the entry)
         TrackMotionArgs m = *motion;
         static_cast<TrackAssocArgs &>(m) = a;
         if (optimal)
@@ -646,6 +722,30 @@ extern "C" int air_track_associate_motion(const float *what, const float *where,
     return track_associate_launch(matching == 1, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score,
                                   max_age, track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last,
                                   track_length, track_gaps, state_counts, stream, &m);
+}
+
+extern "C" int air_track_associate_motion_gated(const float *what, const float *where, const float *boxes, const float *score,
+                                                const int *num_objects, int T, int S, int F, int R, int A, int H, int W, double iou_gate,
+                                                double appearance_weight, double birth_score, int max_age, int matching, double q_shift,
+                                                double q_scale, double measurement_noise, double velocity_var, double gate_d2,
+                                                int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
+                                                int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
+                                                int *state_counts, float *pred_where, float *pred_boxes, float *pred_d2, void *stream) {
+    AIR_REQUIRE(where && pred_where && pred_boxes && pred_d2, AIR_E_NULL);
+    AIR_REQUIRE(matching == 0 || matching == 1, AIR_E_SHAPE);
+    AIR_REQUIRE(H >= 1 && W >= 1, AIR_E_SHAPE);
+    AIR_REQUIRE(traj_noise_check(q_shift, q_scale, measurement_noise, velocity_var) == AIR_OK, AIR_E_SHAPE);
+    AIR_REQUIRE(isfinite(gate_d2) && gate_d2 > 0.0, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(where) && air_aligned16(pred_where) && air_aligned16(pred_boxes), AIR_E_ALIGN);
+    AIR_REQUIRE((reinterpret_cast<uintptr_t>(pred_d2) & 3u) == 0, AIR_E_ALIGN);
+    TrackGateArgs g = {};
+    g.where = where, g.pred_where = pred_where, g.pred_boxes = pred_boxes;
+    g.q[0] = q_shift, g.q[1] = q_scale, g.r = measurement_noise, g.velocity_var = velocity_var;
+    g.Wf = (float)W, g.Hf = (float)H;
+    g.gate_d2 = gate_d2, g.pred_d2 = pred_d2;
+    return track_associate_launch(matching == 1, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score,
+                                  max_age, track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last,
+                                  track_length, track_gaps, state_counts, stream, nullptr, &g);
 }
 
 extern "C" int air_track_associate_stream(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,

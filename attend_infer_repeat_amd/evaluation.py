@@ -488,7 +488,7 @@ def make_trajectory_fig(frames, result, max_frames=8, checkpoint_dir=None, globa
 
 def make_track_score_logger(air, data, num_batches, name, batch_size=None, writer=None, tau=0.5, measure_time=True, iou_gate=None,
                             appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None,
-                            propose=None, temporal=None, smooth=None, matching=None, identity=False, motion=None):
+                            propose=None, temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None):
     """make_tiled_parse_score_logger's counterpart for sequences (air.score_track): `data` is an annotated dataset dict of SEQUENCES
     (imgs [N, F, H, W], boxes [N, F, G, 4], instances [N, F, H, W] int8 -- data.create_moving_mnist with return_annotations=True),
     walked in `num_batches` batches of `batch_size` sequences (None: the model's batch size).  Prints / writes the identity figures
@@ -501,7 +501,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
     rows_filled.  matching="optimal": the optimal assignment of every frame instead of the greedy one (air.track's argument; the
     record names it).  identity=True: the IDF figures beside MOTA -- idf1, idp, idr, idtp, idfp, idfn (air_track_idf), and with smooth=
     smooth_idf1 of the completed table.  motion=True | dict: every track is matched against its predicted box (air.track's argument;
-    the record holds the noise terms under `motion`)."""
+    the record holds the noise terms under `motion`).  motion_gate=True | D2 (with motion): the pairs are gated and ranked by their
+    squared Mahalanobis distance (air.track's argument; the record holds the gate under `motion_gate`)."""
     import torch
     from .track import STATES
     tk = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
@@ -514,6 +515,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
         tk["identity"] = True
     if motion is not None:
         tk["motion"] = motion
+    if motion_gate is not None:
+        tk["motion_gate"] = motion_gate
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -572,6 +575,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
                 rec["matching"] = tracker.matching
             if motion is not None:
                 rec["motion"] = {k: list(v) if isinstance(v, tuple) else v for k, v in tracker.motion.items()}
+            if motion_gate is not None:
+                rec["motion_gate"] = tracker.motion_gate
             writer.write(json.dumps(rec) + "\n"); writer.flush()
         return acc
     return logger

@@ -452,31 +452,31 @@ class AIRonMNIST(AIRModel):
         return self.parse_scores_tiled, s
 
     def tracker(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-                refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None):
+                refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None, motion_gate=None):
         """the track.SequenceTracker behind `track` (`_tracker_entry` describes the cache; with smooth= the tracker of the stack that
         ends in the trajectory.TrajectorySmoother `trajectory_smoother` returns)"""
         return self._tracker_entry(self._track_key(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine,
-                                                   refine_lr, prune, propose, temporal, smooth, matching, motion))[0]
+                                                   refine_lr, prune, propose, temporal, smooth, matching, motion, motion_gate))[0]
 
     def trajectory_smoother(self, n_sequences, n_frames, smooth=True, iou_gate=None, appearance_weight=None, birth_score=None,
                             max_age=None, refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None,
-                            motion=None):
+                            motion=None, motion_gate=None):
         """the trajectory.TrajectorySmoother behind `track(smooth=)` and `predict_frames`: last in the cached stack of
         `tracker(..., smooth=smooth)`, bound to that stack's tracker (smoothed, gap-filled and extrapolated tracks; its defaults are
         provisional)"""
         if stacks.smooth_spec(smooth) is None:
             raise ValueError("trajectory_smoother: smooth must be True or a dict of TrajectorySmoother's arguments, got %r" % (smooth,))
         return self._tracker_entry(self._track_key(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine,
-                                                   refine_lr, prune, propose, temporal, smooth, matching, motion))[1]
+                                                   refine_lr, prune, propose, temporal, smooth, matching, motion, motion_gate))[1]
 
     def _track_key(self, n_sequences, n_frames, *args):
-        """the stacks.TrackKey of the track family's arguments (`args`: iou_gate ... motion, in the order of `tracker`)"""
+        """the stacks.TrackKey of the track family's arguments (`args`: iou_gate ... motion_gate, in the order of `tracker`)"""
         return stacks.track_key(stacks.require_engine(self, "track"), n_sequences, n_frames, *args)
 
     def _tracker_entry(self, key):
         """(tracker, smoother | None) for the stacks.TrackKey `key` -- those of the cached stack whose track.SequenceTracker is behind
         `track`: one per (n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose,
-        temporal, smooth, matching, motion), over a provider stack of its own at n_sequences * n_frames rows -- a SceneParser,
+        temporal, smooth, matching, motion, motion_gate), over a provider stack of its own at n_sequences * n_frames rows -- a SceneParser,
         behind it the refiner / pruner / proposer asked for and, last, with temporal=P | (P, rounds) a temporal.TemporalProposer
         (objects a frame's parse missed are proposed from its neighbour frames; its defaults are provisional) -- so the parsers of
         `parse` and `self.obs` are never touched.  temporal=None builds exactly the stack without it; so does smooth=None, and
@@ -484,13 +484,15 @@ class AIRonMNIST(AIRModel):
         association arguments: track.DEFAULTS (provisional).  matching=None | "greedy" is exactly the stack without the argument,
         "optimal" a tracker of its own with the optimal assignment (part of the key).  motion=None is exactly the stack without the
         argument; True | dict a tracker of its own that matches every track against its predicted box (track.py: MOTION; part of the
-        key; with smooth=dict(...) motion=True takes the smoother's noise terms).  Built and captured on first use; the least
+        key; with smooth=dict(...) motion=True takes the smoother's noise terms).  motion_gate=None is exactly the stack without the
+        argument; True | a squared Mahalanobis distance a tracker of its own whose pairs are gated by the filter's covariance (track.py:
+        THE GATE; part of the key; it needs motion).  Built and captured on first use; the least
         recently used one is dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
         def build():
             from .track import SequenceTracker
             stack = self._own_stack(key.S * key.F, key.stack, key.F)
             stack.append(SequenceTracker(stack[-1], key.F, matching=key.matching, motion=key.motion and dict(key.motion),
-                                         **dict(key.assoc)))
+                                         motion_gate=key.motion_gate, **dict(key.assoc)))
             if key.smooth is not None:
                 from .trajectory import TrajectorySmoother
                 stack.append(TrajectorySmoother(stack[-1], **dict(key.smooth)))
@@ -510,7 +512,7 @@ class AIRonMNIST(AIRModel):
             from .trajectory import TrajectoryNoiseFitter
             stack = self._own_stack(key.S * key.F, key.stack, key.F)
             stack.append(SequenceTracker(stack[-1], key.F, matching=key.matching, motion=key.motion and dict(key.motion),
-                                         **dict(key.assoc)))
+                                         motion_gate=key.motion_gate, **dict(key.assoc)))
             stack.append(TrajectoryNoiseFitter(stack[-1], *key.fit))
             return stacks.captured(stack)
         return self._cache("trackers").get(key, build)[-1]
@@ -539,16 +541,17 @@ class AIRonMNIST(AIRModel):
         return self.track_noise_fit
 
     def stream_tracker(self, n_sequences, chunk_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None,
-                       refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None, motion=None):
+                       refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None, motion=None,
+                       motion_gate=None):
         """the track.StreamTracker behind `track_stream`: identities over sequences of any length, fed in chunks of `chunk_frames`
-        frames, the track table carried on the device between the calls (motion= is refused: out of scope on a stream,
+        frames, the track table carried on the device between the calls (motion= and motion_gate= are refused: out of scope on a stream,
         track.MOTION_ON_A_STREAM).  One per (n_sequences, chunk_frames, the association
         arguments, refine, refine_lr, prune, propose, temporal, matching) under a key of its own (stacks.stream_key) in the cache of
         `tracker` -- it counts against MAX_TRACKERS with the one-shot trackers -- over a provider stack of its own at n_sequences *
         chunk_frames rows, so the parsers of `parse` and `self.obs` are never touched (a temporal proposer sees only its chunk).  Built
         and captured on first use.  Dropped from the cache, its stream is lost with it."""
         key = stacks.stream_key(stacks.require_engine(self, "track_stream"), n_sequences, chunk_frames, iou_gate, appearance_weight,
-                                birth_score, max_age, refine, refine_lr, prune, propose, temporal, matching, motion)
+                                birth_score, max_age, refine, refine_lr, prune, propose, temporal, matching, motion, motion_gate)
 
         def build():
             from .track import StreamTracker
@@ -613,7 +616,7 @@ class AIRonMNIST(AIRModel):
                                                      lambda: stacks.captured(self._own_stack(S * F, spec, F)))[-1]
 
     def _track(self, frames, *args):
-        """`track` (`args`: iou_gate ... motion, in its order); returns the (tracker, smoother | None) that ran"""
+        """`track` (`args`: iou_gate ... motion_gate, in its order); returns the (tracker, smoother | None) that ran"""
         frames = torch.as_tensor(frames)
         if frames.dim() != 4:
             raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
@@ -625,7 +628,7 @@ class AIRonMNIST(AIRModel):
         return tracker, smoother
 
     def track(self, frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None,
-              prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None):
+              prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None, motion_gate=None):
         """Parse the frames [S, F, H, W] of S sequences on the device, each frame as `parse(refine=, prune=, propose=)` would parse
         it -- with temporal=P | (P, rounds) followed by proposals from the neighbour frames (temporal.TemporalProposer) -- and give
         the objects identities over time (track.SequenceTracker.track lists the returned device tensors: the parse of
@@ -638,10 +641,13 @@ class AIRonMNIST(AIRModel):
         against its last box (track.py: MOTION; pred_where and pred_boxes come on top) -- an object missed for a frame or two while it
         moves keeps its id, two objects that cross keep theirs; motion=None is exactly the call without it.  The noise terms are the
         smoother's: `fit = m.fit_track_noise(frames)`, then `noise = {k: fit[k] for k in trajectory.FIT_KEYS}` and
-        `m.track(frames, motion=noise, smooth=noise)` (motion=True with smooth=dict(...) takes the smoother's terms).  The training
+        `m.track(frames, motion=noise, smooth=noise)` (motion=True with smooth=dict(...) takes the smoother's terms).
+        motion_gate=True | D2 (with motion): the pairs are gated by their squared Mahalanobis distance from the filter's predicted
+        state, D2 at most (True: track.MOTION_GATE_DEFAULT, provisional), and ranked by it instead of the IoU -- the fitted noise terms
+        and the gate then concern one quantity; pred_d2 comes on top; motion_gate=None is exactly the call without it.  The training
         engine's parameters are read, nothing of it is written; `self.obs` and the parsers of `parse` are not touched."""
         self._track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth, matching,
-                    motion)
+                    motion, motion_gate)
         return self.tracked
 
     def predict_frames(self, frames, horizon, smooth=True, **track_args):
@@ -658,7 +664,7 @@ class AIRonMNIST(AIRModel):
 
     def score_track(self, frames, gt_boxes, tau=0.5, accumulate=True, gt_instances=None, thresholds=None, iou_gate=None,
                     appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None,
-                    temporal=None, smooth=None, matching=None, identity=False, motion=None):
+                    temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None):
         """`track`, then the identity metric of the tracks against gt_boxes [S, F, G, 4] (G <= 8; slot g is the same object in every
         frame of a sequence, width <= 0 = absent) on the device (track.SequenceTracker.score).  The sums accumulate in the tracker
         this returns alongside -- (scores, tracker): its summary() reads MOTA, MOTP, the identity switches and the mostly tracked /
@@ -669,9 +675,9 @@ class AIRonMNIST(AIRModel):
         scores["completed"] holds its tensors, `self.track_smoother` is the smoother, whose summary() / reset() are the completed
         table's -- the raw figures stay the tracker's.  matching= is `track`'s; identity=True adds the IDF1 counts (air_track_idf behind
         air_track_score: seq_idf, idf_overlap, totals_idf; the tracker's -- and the smoother's -- identity_summary() reads IDF1, IDP
-        and IDR back).  motion= is `track`'s."""
+        and IDR back).  motion= and motion_gate= are `track`'s."""
         t, smoother = self._track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal,
-                                  smooth, matching, motion)
+                                  smooth, matching, motion, motion_gate)
         gb = torch.as_tensor(gt_boxes)
         scores = dict(t.score(gb, tau, accumulate, identity))
         if smoother is not None:

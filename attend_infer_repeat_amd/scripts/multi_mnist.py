@@ -142,6 +142,11 @@ def main(argv=None):
                          "of shifts and scales, measurement noise, prior variance of the rate.  With --track-fit-noise the identity "
                          "figures are also logged with motion at the defaults and at the fitted terms (<name>_motion_defaults, "
                          "<name>_motion_fit); does not apply to --track-stream (out of scope on a stream)")
+    ap.add_argument("--track-motion-gate", nargs="?", const="", default=None, metavar="D2",
+                    help="with --track-motion: gate every (track, object) pair by its squared Mahalanobis distance from the filter's "
+                         "predicted state, D2 at most, and rank by it instead of the IoU (track.SequenceTracker's motion_gate): no value = "
+                         "13.2767, the 0.99 quantile of chi-squared with 4 degrees of freedom (provisional).  With --track-fit-noise the "
+                         "<name>_motion_defaults / <name>_motion_fit figures are those under the gate")
     ap.add_argument("--track-matching", choices=("greedy", "optimal"), default=None,
                     help="with --track-eval: how a frame's objects are matched to the live tracks (track.SequenceTracker's matching): "
                          "greedy (the default) or the optimal assignment of the whole frame (Hungarian, air_track_associate_optimal)")
@@ -269,6 +274,15 @@ def main(argv=None):
                 track_motion = check_motion(dict(process_noise=(qs, qc), measurement_noise=r, velocity_var=vv))
             except ValueError as e:
                 ap.error("--track-motion needs QS,QC,R,VV inside the smoother's noise domain or no value, got %r (%s)" % (args.track_motion, e))
+    track_motion_gate = None
+    if args.track_motion_gate is not None:
+        if track_motion is None:
+            ap.error("--track-motion-gate goes with --track-motion")
+        try:
+            from attend_infer_repeat_amd.track import check_motion_gate
+            track_motion_gate = check_motion_gate(float(args.track_motion_gate) if args.track_motion_gate else True, track_motion)
+        except ValueError as e:
+            ap.error("--track-motion-gate needs a squared distance D2 > 0 or no value, got %r (%s)" % (args.track_motion_gate, e))
     track_smooth = None
     if args.track_smooth is not None or args.track_predict is not None:
         if track_eval is None:
@@ -440,7 +454,7 @@ def main(argv=None):
         before_track_log = log
         track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
                                             smooth=track_smooth, matching=args.track_matching, identity=args.track_identity,
-                                            motion=track_motion, **refine_kw)
+                                            motion=track_motion, motion_gate=track_motion_gate, **refine_kw)
 
         stream_log = None
         if args.track_stream is not None:
@@ -465,6 +479,8 @@ def main(argv=None):
                 kw = dict(temporal=track_temporal, matching=args.track_matching, **refine_kw)
                 if track_motion is not None:
                     kw["motion"] = track_motion                    # the tracks the terms are fitted to are the ones being evaluated
+                if track_motion_gate is not None:
+                    kw["motion_gate"] = track_motion_gate
                 rec = dict(step=train_itr, data="test_track_noise_fit", zoom=args.track_fit_noise)
                 try:
                     for b in range(n):
@@ -490,7 +506,7 @@ def main(argv=None):
                     for tag, terms in (("defaults", True), ("fit", fitted)):
                         make_track_score_logger(air, seq_data, args.eval_batches, 'test_motion_' + tag, sequences_per_batch, writer,
                                                 temporal=track_temporal, matching=args.track_matching, identity=args.track_identity,
-                                                motion=terms, **refine_kw)(train_itr)
+                                                motion=terms, motion_gate=track_motion_gate, **refine_kw)(train_itr)
 
         def log(train_itr):                               # noqa: F811
             out = before_track_log(train_itr)

@@ -7,10 +7,10 @@ from collections import namedtuple
 
 StackSpec = namedtuple("StackSpec", "refine lr prune propose temporal")     # int | None, (lr_what, lr_where) | None, the pruner's
 #                                                                             candidates | None, (P, rounds) | None, (P, rounds) | None
-TrackKey = namedtuple("TrackKey", "S F assoc stack smooth matching device motion", defaults=(None,))
-#   assoc, smooth, motion: sorted (name, value) pairs; smooth | None, motion | None
+TrackKey = namedtuple("TrackKey", "S F assoc stack smooth matching device motion motion_gate", defaults=(None, None))
+#   assoc, smooth, motion: sorted (name, value) pairs; smooth | None, motion | None; motion_gate: the float | None
 StreamKey = namedtuple("StreamKey", "S F assoc stack matching device stream")  # a track.StreamTracker's: stream is True (a key of its own)
-FitKey = namedtuple("FitKey", "S F assoc stack matching device fit motion", defaults=(None,))      # ... with a trajectory.
+FitKey = namedtuple("FitKey", "S F assoc stack matching device fit motion motion_gate", defaults=(None, None))      # ... with a trajectory.
 #   TrajectoryNoiseFitter: the grids
 StreamSmoothKey = namedtuple("StreamSmoothKey", "S F assoc stack matching device stream smooth")      # ... with a trajectory.StreamSmoother
 
@@ -70,11 +70,12 @@ def smooth_spec(smooth):
 
 
 def track_key(eng, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-              refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None):
+              refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None, motion_gate=None):
     """The arguments of the track family, normalised once and checked against the engine `eng` (track, temporal and trajectory
     check_arguments, before anything is built): None for an association argument is track.DEFAULTS, temporal=None, smooth=None,
     matching=None | "greedy" and motion=None give the very key of a call without the argument.  motion=True together with
-    smooth=dict(...) takes the smoother's noise terms; an explicit motion=dict(...) wins."""
+    smooth=dict(...) takes the smoother's noise terms; an explicit motion=dict(...) wins.  motion_gate=None | False is the key of a call
+    without it, True is track.MOTION_GATE_DEFAULT, and a gate without motion is refused (track.check_motion_gate)."""
     from . import track as tr
     stack = stack_spec(refine, refine_lr, prune, propose, temporal, who="track")
     given = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age)
@@ -95,18 +96,19 @@ def track_key(eng, n_sequences, n_frames, iou_gate=None, appearance_weight=None,
             motion = {k: smooth[k] for k in ("process_noise", "measurement_noise", "velocity_var")}
         smooth = tuple(sorted(smooth.items()))
     motion = tr.check_motion(motion)
+    motion_gate = tr.check_motion_gate(motion_gate, motion)
     if motion is not None:
         motion = tuple(sorted(motion.items()))
     assoc = {k: (int(v) if k == "max_age" else float(v)) for k, v in assoc.items()}
-    return TrackKey(S, F, tuple(sorted(assoc.items())), stack, smooth, matching, str(eng.device), motion)
+    return TrackKey(S, F, tuple(sorted(assoc.items())), stack, smooth, matching, str(eng.device), motion, motion_gate)
 
 
 def stream_key(eng, n_sequences, chunk_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-               refine_lr=None, prune=None, propose=None, temporal=None, matching=None, motion=None):
+               refine_lr=None, prune=None, propose=None, temporal=None, matching=None, motion=None, motion_gate=None):
     """The arguments of a stream tracker, normalised and checked as `track_key` does (there is no smoother on a stream): a key of its
-    own in the cache of the track family, never that of a one-shot tracker with the same arguments.  motion: refused (out of scope on
-    a stream)."""
-    if motion is not None and motion is not False:
+    own in the cache of the track family, never that of a one-shot tracker with the same arguments.  motion and motion_gate: refused
+    (out of scope on a stream)."""
+    if (motion is not None and motion is not False) or (motion_gate is not None and motion_gate is not False):
         from .track import MOTION_ON_A_STREAM
         raise ValueError(MOTION_ON_A_STREAM)
     k = track_key(eng, n_sequences, chunk_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose,
@@ -148,7 +150,7 @@ def fit_key(eng, n_sequences, n_frames, shift_ratios=None, scale_ratios=None, ve
         raise ValueError("fit_track_noise: the noise terms are fitted to the tracker's sightings; smooth= has no part in it")
     k = track_key(eng, n_sequences, n_frames, **dict(track_args, smooth=None))
     fit = check_fit_arguments(eng.cfg.max_steps, k.F, k.S * k.F, shift_ratios, scale_ratios, velocity_ratio)[3:]
-    return FitKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, fit, k.motion)
+    return FitKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, fit, k.motion, k.motion_gate)
 
 
 def stage_classes():

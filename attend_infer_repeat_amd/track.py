@@ -69,11 +69,33 @@ AIR_E_SHAPE).  EXACT CONSEQUENCES:
      trajectory.reference_smooth(..., horizon=1) run on this tracker's own output restricted to the frames 0 .. f - 1 (track_last
      recomputed from track_id, num_tracks = the ids issued before f): the filter inside the tracker and the smoother behind it are
      one filter, and the state at a track's last sighting is the forward pass of `reference_smooth` on that track, bit for bit.
-A track has v = 0 until its second sighting: an object displaced by more than its box in its first step is linked by neither rule.
-Out of scope: motion on a stream (StreamTracker refuses it: the carried state would need the 14 doubles per slot, and its chunk-
-invariance tests), a Mahalanobis gate, rates on scales in the prediction, feeding smoothed (non-causal) rows back, motion for the
-temporal proposer.  What motion does to MOTA / IDF1 on the parses of a TRAINED model is unmeasured (profiles/track_motion.txt says what
-was measured: the cost of the tail).
+A track has v = 0 until its second sighting: an object displaced by more than its box in its first step is linked by neither rule
+-- THE GATE below links it.
+THE GATE (motion_gate=True | G with motion=: air_track_associate_motion_gated, either matching; `reference_associate_motion(gate=)`
+restates it; motion_gate=None is exactly MOTION above).  MOTION uses the filter's predicted MEAN alone: the covariance it carries says
+how far a sighting may plausibly lie from that mean -- far for a newborn track, whose rate is unknown (velocity_var), near for a track
+followed for many frames -- and the IoU gate knows neither.  G is a squared Mahalanobis distance, finite and > 0; True is
+MOTION_GATE_DEFAULT = 13.2767, the 0.99 quantile of chi-squared with 4 degrees of freedom (provisional like the other association
+defaults: unmeasured on a trained model).  Steps 1-5 of MOTION stay; step 2 changes:
+  per track  for live track k last sighted at l, m = f - l >= 1: the PREDICTED state of its filter m frames on, by the statements a
+           match would run -- the m - 1 coasted frames predicted one by one (x = x + v and the covariance predict), then one more
+           predict: xp[4] and Pxx- per noise class; never m v.  s[cl] = Pxx-[cl] + measurement_noise.
+  per pair   (k, j) with a finite object j, in float64: e[c] = z[c] - xp[c] over [sx, tx, sy, ty], z = the object's `where` row
+           widened;  d2 = ((e0 e0 / s_scale + e1 e1 / s_shift) + e2 e2 / s_scale) + e3 e3 / s_shift.  Admissible iff d2 <= G (a NaN or an
+           inf fails); iou_gate is NOT applied.  aff = (1 - w) / (1 + d2) + w / (1 + msd): rational, within [0, 1], no transcendental.
+           The int64 profit, the greedy and the optimal step 3 and every tie order are unchanged.
+pred_where and pred_boxes stay the forecast row (scales held) and its box.  One more output, pred_d2 [T, R] fp32: for a MATCHED object
+float32(d2) of the pair that was matched, zero in every other row.  Booking a match, the advance of the state, births and ageing are
+MOTION's.  EXACT CONSEQUENCES:
+  1. for a MATCHED object pred_d2 is float32(sum e^2 / s) with (xp, Pxx-) the predicted tuple of trajectory._filter_step applied to the
+     track's filtered state, the coasted frames first, e = z - xp and s = Pxx- + r: the innovation and its variance of the very update
+     that books the match -- the quantities whose likelihood `fit_track_noise` maximises.
+  2. consequence 2 of MOTION holds under the gate: the final states equal the smoother's forward pass on the tracker's own output.
+`return_margins=True` reports gate_margin = min |d2 - G| under the gate.
+Out of scope: motion or the gate on a stream (StreamTracker refuses both: the carried state would need the 14 doubles per slot, and
+its chunk-invariance tests), a gate per component, rates on scales in pred_where, feeding smoothed (non-causal) rows back, motion for
+the temporal proposer.  What motion, the gate and the gate's default threshold do to MOTA / IDF1 on the parses of a TRAINED model is
+unmeasured (profiles/track_motion.txt and profiles/track_gate.txt say what was measured: the cost of the tail).
 
 The identity metric (air_track_score).  gt_boxes [R, G, 4], G <= 8: ground-truth slot g is the SAME object in every frame of a sequence,
 width <= 0 = absent in that frame.  The hypotheses of a frame are its objects j < n with track_id >= 0 and finite boxes.  map[g] = none
@@ -101,7 +123,8 @@ then, on the same engine stream, its own launch list of libair_hip.so entries (i
 whatever F is -- the frames are walked inside air_track_associate:
 
   air_track_associate   the rule above (air_track_associate_optimal with matching="optimal", air_track_associate_motion with motion=,
-                        which also reads the provider's `where` rows: the same launch list otherwise);
+                        which also reads the provider's `where` rows, air_track_associate_motion_gated with motion_gate= on top: the
+                        same launch list otherwise);
   air_track_owner       track_owner[r, y, x] (int16) = the track id of the step that owns the pixel, -1 for background.
 
 A particle_parse.ParticleParser is refused, with tile.TiledSceneParser's wording: its `parse()` takes no counts and its rows are particles
@@ -147,8 +170,9 @@ IDF_COUNTS = ("idtp", "gt_frames", "hyp_frames", "ids_with_overlap")
 MATCHINGS = ("greedy", "optimal")
 PROFIT_SCALE = 4294967296.0        # 2^32: profit = 1 + floor(aff * 2^32)
 DEFAULTS = dict(iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1)
+MOTION_GATE_DEFAULT = 13.2767       # motion_gate=True: the 0.99 quantile of chi-squared with 4 degrees of freedom (provisional)
 MOTION_ON_A_STREAM = ("motion is out of scope on a stream: the state carried between chunks would need each slot's filter state (14 "
-                      "doubles); track the sequence in one call with SequenceTracker(motion=...)")
+                      "doubles); track the sequence in one call with SequenceTracker(motion=...) (motion_gate= goes with motion=)")
 
 
 def check_arguments(max_steps, n_frames, n_rows=None, iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1,
@@ -255,6 +279,51 @@ def check_motion(motion):
     return dict(process_noise=q, measurement_noise=r, velocity_var=vv)
 
 
+def check_motion_gate(motion_gate, motion=None):
+    """motion_gate=None / False (off), True (MOTION_GATE_DEFAULT) or a finite number > 0: a squared Mahalanobis distance -> None or the
+    float.  A gate needs the filter whose covariance it reads: without motion (None / False) it raises."""
+    if motion_gate is None or motion_gate is False:
+        return None
+    if motion is None or motion is False:
+        raise ValueError("motion_gate gates on the covariance of the motion filter: it needs motion=True or motion=dict(...)")
+    if motion_gate is True:
+        return MOTION_GATE_DEFAULT
+    try:
+        gate = float(motion_gate)
+    except (TypeError, ValueError):
+        gate = float("nan")
+    if not (math.isfinite(gate) and gate > 0.0):
+        raise ValueError("motion_gate must be None, True or a finite squared Mahalanobis distance > 0, got %r" % (motion_gate,))
+    return gate
+
+
+def _motion_predicted_state(filt, m, q, r):
+    """the gate's step 2, per track: (xp [4], s [4]) of the filter m frames after its last sighting -- the m - 1 frames coasted over
+    predicted one by one, then the predicted tuple of one more trajectory._filter_step (never m v); s = Pxx- + r per component (the
+    two scales share one value, the two shifts another)"""
+    from .trajectory import _filter_step
+    for _ in range(m - 1):
+        filt = _filter_step(filt, None, q, r)[1]
+    pred = _filter_step(filt, None, q, r)[0]
+    return pred[0], pred[2] + r
+
+
+def _motion_d2(xp, s, z):
+    """the gate's step 2, per pair: the squared Mahalanobis distance of the sighting z from the predicted state, summed in the order
+    [sx, tx, sy, ty]: each term one product and one quotient"""
+    e = z - xp
+    return ((e[0] * e[0] / s[0] + e[1] * e[1] / s[1]) + e[2] * e[2] / s[2]) + e[3] * e[3] / s[3]
+
+
+def _gated_pair(d2, msd, w, gate, pred_box, box):
+    """the gate's step 2, per pair: None for an inadmissible pair (d2 <= gate fails, as it does for a NaN or an inf), else the affinity:
+    rational in d2 and msd, within [0, 1].  pred_box and box are NOT read -- iou_gate is not applied under the gate; they are passed so
+    that a test can plant a rule that does read them"""
+    if not d2 <= gate:
+        return None
+    return (1.0 - w) / (1.0 + d2) + w / (1.0 + msd)
+
+
 def _motion_predict(filt, m, last_box, img_size):
     """step 2 with motion: (pred_where, pred_box) of a track m frames after its last sighting, from its filtered state there --
     trajectory._forecast_where's row and its scene box in fp32; a box that is not finite falls back to the last-sighting box"""
@@ -282,7 +351,8 @@ def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id
     (in the stream); what [T, A], boxes [T, 4], score [T]: the frame's fp32 rows; n: its clipped count; rule = (gate, w, birth,
     max_age, matching); margins: [gate_margin, round_margin], updated in place; id_limit: a birth at next_id == id_limit is OVERFLOW.
     motion: None, or dict(where [T, 4] fp32, img_size, q [4], r, vv, pred_where [T, 4], pred_boxes [T, 4] (written)): the rule of
-    reference_associate_motion, a track then carries `filt`, its filtered state at the last sighting.
+    reference_associate_motion, a track then carries `filt`, its filtered state at the last sighting.  With motion["gate"] = G (and
+    pred_d2 [T], written) the pairs are gated and ranked by their squared Mahalanobis distance; margins[0] is then min |d2 - G|.
     Returns (state, ids, affinity, prev_frame, prev_slot, next_id, born [tracks], retired [(slot, track)] in ascending slot)."""
     import numpy as np
     gate, w, birth, max_age, matching = rule
@@ -299,6 +369,8 @@ def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id
             finite.append(j)
     aff = {}                                                       # 2. affinity of the admissible pairs
     pred = {}                                                      # motion: slot -> (pred_where, pred_box)
+    G = None if motion is None else motion.get("gate")
+    d2s = {}                                                       # the gate: (slot, j) -> d2 of an admissible pair
     for k, t in live.items():
         if not finite:
             break
@@ -306,7 +378,18 @@ def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id
         msd = _sequential_sum(d * d) / np.float64(A)
         if motion is not None:
             pred[k] = _motion_predict(t["filt"], fg - t["f"], t["box"], motion["img_size"])
+        if G is not None:
+            with np.errstate(all="ignore"):
+                xp, s_in = _motion_predicted_state(t["filt"], fg - t["f"], motion["q"], motion["r"])
         for q, j in enumerate(finite):
+            if G is not None:                                      # the Mahalanobis gate: iou_gate is not applied
+                with np.errstate(all="ignore"):
+                    d2 = float(_motion_d2(xp, s_in, motion["where"][j].astype(np.float64)))
+                    margins[0] = min(margins[0], abs(d2 - G))
+                    v = _gated_pair(d2, float(msd[q]), w, G, pred[k][1], boxes[j])
+                if v is not None:
+                    aff[(k, j)], d2s[(k, j)] = v, d2
+                continue
             iou = box_iou(t["box"] if motion is None else pred[k][1], boxes[j])
             margins[0] = min(margins[0], abs(iou - gate))
             if iou > gate:
@@ -319,6 +402,8 @@ def _associate_frame(live, next_id, fg, what, boxes, score, n, rule, margins, id
         aff32[j] = np.float32(aff[(k, j)])
         if motion is not None:
             motion["pred_where"][j], motion["pred_boxes"][j] = pred[k]
+            if G is not None:
+                motion["pred_d2"][j] = np.float32(d2s[(k, j)])
             with np.errstate(all="ignore"):
                 t["filt"] = _motion_advance(t["filt"], fg - t["f"], motion["where"][j].astype(np.float64), motion["q"], motion["r"])
         t["gaps"] += 1 if t["age"] > 0 else 0
@@ -397,6 +482,8 @@ def _associate_sequences(what, boxes, score, num_objects, n_frames, iou_gate, ap
            "state_counts": np.zeros((S, 6), np.int32)}
     if motion is not None:
         out.update(pred_where=np.zeros((T, R, 4), np.float32), pred_boxes=np.zeros((T, R, 4), np.float32))
+        if motion.get("gate") is not None:
+            out.update(pred_d2=np.zeros((T, R), np.float32))
         if motion["return_state"]:
             out["motion_state"] = {}
     gate_margin, round_margin = np.full(S, np.inf), np.full(S, np.inf)
@@ -417,6 +504,8 @@ def _associate_sequences(what, boxes, score, num_objects, n_frames, iou_gate, ap
             if motion is not None:
                 frame_motion = dict(motion, where=motion["where"][:, r], pred_where=out["pred_where"][:, r],
                                     pred_boxes=out["pred_boxes"][:, r])
+                if "pred_d2" in out:
+                    frame_motion.update(pred_d2=out["pred_d2"][:, r])
             state, ids, aff32, pf, ps, next_id, born, retired = _associate_frame(live, next_id, f, what[:, r], boxes[:, r], score[:, r],
                                                                                  n, rule, margins, motion=frame_motion)
             for t in born:
@@ -439,15 +528,19 @@ def _associate_sequences(what, boxes, score, num_objects, n_frames, iou_gate, ap
 
 def reference_associate_motion(what, where, boxes, score, num_objects, n_frames, img_size, iou_gate=0.1, appearance_weight=0.25,
                                birth_score=0.5, max_age=1, matching="greedy", process_noise=None, measurement_noise=None,
-                               velocity_var=None, return_margins=False, return_state=False):
+                               velocity_var=None, return_margins=False, return_state=False, gate=None):
     """air_track_associate_motion restated in numpy float64 (MOTION in the module text): reference_associate's arrays and rule
     arguments, where [T, R, 4] fp32 = [sx, tx, sy, ty], img_size (H, W), and the noise terms of the trajectory filter (None: trajectory.
     DEFAULTS; outside the supported domain: trajectory.check_arguments' messages).  Returns reference_associate's outputs (matching=
     "optimal": air_track_associate_optimal's step 3) and pred_where, pred_boxes [T, R, 4] float32: for a MATCHED object the prediction
     of its track that the match was made against, zero otherwise.  return_margins as in reference_associate (gate_margin over the IoUs
     with the PREDICTED boxes).  return_state=True adds motion_state: (s, id) -> the filtered state (x, v, Pxx, Pxv, Pvv), float64 [4]
-    each over [sx, tx, sy, ty], of every track at its last sighting."""
+    each over [sx, tx, sy, ty], of every track at its last sighting.  gate=G (None: off; True: MOTION_GATE_DEFAULT):
+    air_track_associate_motion_gated -- the pairs gated by d2 <= G and ranked by (1 - w) / (1 + d2) + w / (1 + msd), iou_gate not applied;
+    adds pred_d2 [T, R] float32 (the d2 of the pair a MATCHED object was matched in, zero otherwise), and gate_margin is then the
+    smallest |d2 - G|."""
     import numpy as np
+    gate = check_motion_gate(gate, True)
     terms = {k: v for k, v in dict(process_noise=process_noise, measurement_noise=measurement_noise, velocity_var=velocity_var).items()
              if v is not None}
     terms = check_motion(terms or True)
@@ -458,7 +551,7 @@ def reference_associate_motion(what, where, boxes, score, num_objects, n_frames,
     if where.shape != tuple(np.shape(what)[:2]) + (4,):
         raise ValueError("where: expected %s, got %s" % (tuple(np.shape(what)[:2]) + (4,), where.shape))
     motion = dict(where=where, img_size=(H, W), q=np.array([q_scale, q_shift, q_scale, q_shift], np.float64),
-                  r=terms["measurement_noise"], vv=terms["velocity_var"], return_state=bool(return_state))
+                  r=terms["measurement_noise"], vv=terms["velocity_var"], return_state=bool(return_state), gate=gate)
     return _associate_sequences(what, boxes, score, num_objects, n_frames, iou_gate, appearance_weight, birth_score, max_age,
                                 return_margins, matching, motion)
 
@@ -920,13 +1013,15 @@ class SequenceTracker(BoundStage):
     REFUSALS = TiledSceneParser.REFUSALS
 
     def __init__(self, provider, n_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
-                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None):
+                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None, motion_gate=None):
         """motion: None (every track is matched against its last-sighting box), True (against its predicted box, MOTION in the module
         text, with trajectory.DEFAULTS) or a dict with any of process_noise=(q_shift, q_scale), measurement_noise, velocity_var --
-        what `smooth=` and `fit_track_noise` use"""
+        what `smooth=` and `fit_track_noise` use.  motion_gate (needs motion): None (the pairs are gated by the IoU with the
+        predicted box), True (MOTION_GATE_DEFAULT, provisional) or a squared Mahalanobis distance > 0: THE GATE in the module text"""
         self._rows = self.bind(provider)
         T, F, S = check_arguments(provider.T, n_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age, matching)
         self.motion = check_motion(motion)
+        self.motion_gate = check_motion_gate(motion_gate, self.motion)
         import torch
         from . import hip as H
         self.provider, self.engine = provider, provider.engine
@@ -950,6 +1045,8 @@ class SequenceTracker(BoundStage):
             self.track_owner = z((R,) + self.img_size, torch.int16)
             if self.motion is not None:
                 self.pred_where, self.pred_boxes = z((T, R, 4), torch.float32), z((T, R, 4), torch.float32)
+            if self.motion_gate is not None:
+                self.pred_d2 = z((T, R), torch.float32)
         self._H = H
         self.scores = IdentityScores(self, S)
         self._score = self.scores.entries                          # (G, tau) -> buffers, plan, graph
@@ -974,6 +1071,10 @@ class SequenceTracker(BoundStage):
             args = (rows[0], p(self._rows["where"])) + rows[1:] + (T, S, F, R, self.A, Hi, Wi) + rule + (
                 MATCHINGS.index(self.matching), *m["process_noise"], m["measurement_noise"], m["velocity_var"]) + outputs + (
                 p(self.pred_where), p(self.pred_boxes))
+            if self.motion_gate is not None:                       # ... with gate_d2 behind the noise terms and pred_d2 last
+                associate = "air_track_associate_motion_gated"
+                at = len(args) - len(outputs) - 2
+                args = args[:at] + (self.motion_gate,) + args[at:] + (p(self.pred_d2),)
         self.segments = OrderedDict([
             ("associate", [(getattr(L, associate), args, associate)]),
             ("owner", [(L.air_track_owner, (p(provider.owner), p(self.track_id), T, R, Hi, Wi, p(self.track_owner)),
@@ -1010,7 +1111,8 @@ class SequenceTracker(BoundStage):
         int32 (the track's previous sighting, -1 unless matched), num_tracks [S] int32, track_first, track_last, track_length,
         track_gaps [S, F * T] int32 per id (-1 / -1 / 0 / 0 from num_tracks[s] on), state_counts [S, 6] int32, track_owner
         [R, H, W] int16 (the track id a pixel belongs to, -1 = background or an object without a track); with motion also pred_where,
-        pred_boxes [T, R, 4] (for a MATCHED object the prediction of its track that the match was made against, else 0).  Same stream contract as
+        pred_boxes [T, R, 4] (for a MATCHED object the prediction of its track that the match was made against, else 0); with
+        motion_gate also pred_d2 [T, R] (the squared Mahalanobis distance of the matched pair, else 0).  Same stream contract as
         SceneParser.parse: the work runs on the engine's stream, on return the caller's current stream is ordered after it, and the
         next call waits for the caller's reads before it overwrites them."""
         eng = self.engine
@@ -1027,6 +1129,8 @@ class SequenceTracker(BoundStage):
                    track_owner=self.track_owner)
         if self.motion is not None:
             out.update(pred_where=self.pred_where, pred_boxes=self.pred_boxes)
+        if self.motion_gate is not None:
+            out.update(pred_d2=self.pred_d2)
         return out
 
     # ---- the identity metric ------------------------------------------------------------------------------------------------
@@ -1078,8 +1182,8 @@ class StreamTracker(BoundStage):
     REFUSALS = SequenceTracker.REFUSALS
 
     def __init__(self, provider, chunk_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
-                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None):
-        if motion is not None and motion is not False:
+                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None, motion_gate=None):
+        if (motion is not None and motion is not False) or (motion_gate is not None and motion_gate is not False):
             raise ValueError(MOTION_ON_A_STREAM)
         self._rows = self.bind(provider)
         T, F, S = check_arguments(provider.T, chunk_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age, matching)

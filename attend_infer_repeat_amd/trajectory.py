@@ -47,7 +47,9 @@ The defaults of process_noise, measurement_noise and velocity_var are provisiona
 says what was measured).  `TrajectoryNoiseFitter` (NOISE FIT below) fits them to a model's own tracks by maximum likelihood, without
 ground truth.  The association itself can run this rule's forward filter: track.SequenceTracker(motion=...) matches every track against
 the forecast row of its filtered state (air_track_associate_motion; track.py states it under MOTION), with these noise terms, and its
-pred_where is this module's fc_where (horizon 1) on the tracker's own output truncated before the frame, bit for bit.  Out of scope:
+pred_where is this module's fc_where (horizon 1) on the tracker's own output truncated before the frame, bit for bit; with motion_gate=
+the pairs are gated by sum e^2 / s over this filter's innovation e and its variance s (track.py: THE GATE), the quantities NOISE FIT's
+likelihood is made of.  Out of scope:
 smoothed covariances, feeding the SMOOTHED (non-causal) rows back into the association, rates on scales in the forecast, a learned
 motion prior, particle providers (refused by the tracker, in its wording).
 
@@ -75,8 +77,8 @@ tracker's births and retirements with the same max_age (the tracker's state is o
 what the backward pass reads per (table row, frame) and of the provider's rows.  D = F + L + max_age (`ring_depth`): a push writes the
 frames a .. a + F - 1 and emits from a - L on, and the source of a FILLED row there lies up to max_age frames before it; the reference
 tags every ring entry with its frame and asserts the tag on every read.  The default lag (max_age) is provisional like the noise
-terms.  Out of scope on a stream: smoothed covariances, motion-predicted association (track.py: MOTION; a stream tracker would have to
-carry each slot's filter state), IDF1.
+terms.  Out of scope on a stream: smoothed covariances, motion-predicted association and its gate (track.py: MOTION, THE GATE; a stream
+tracker would have to carry each slot's filter state), IDF1.
 
 NOISE FIT (`TrajectoryNoiseFitter` behind a track.SequenceTracker; air_track_noise_stats, air_track_noise_reduce; `reference_noise_stats`
 restates both in numpy, bit for bit).  The forward filter above computes every innovation e = z - x- and its variance s = Pxx- + r: the

@@ -994,6 +994,24 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *   AIR_E_SHAPE also: H or W < 1, matching outside {0, 1}, noise terms outside air_track_smooth's supported domain (below).  where,
  *   pred_where and pred_boxes 16-byte aligned (AIR_E_ALIGN).  A stream entry with motion does not exist: the carried state would
  *   need the 14 doubles per slot.
+ * air_track_associate_motion_gated: air_track_associate_motion -- the same inputs, checks, state, outputs and steps -- with the pairs of
+ *   step 2 gated and ranked by the filter's own uncertainty.  gate_d2 is a squared Mahalanobis distance (13.2767 = the 0.99 quantile of
+ *   chi-squared with 4 degrees of freedom is the suggested, provisional value).  The exceptions to air_track_associate_motion:
+ *   2. per live track k last sighted at l, m = f - l >= 1: the PREDICTED state of its filter m frames on, by the statements a match
+ *      would run -- the m - 1 frames coasted over predicted one by one (x = x + v, `predict` on the covariances), then one more
+ *      `predict`: xp[4] and Pxx- per noise class; never m v.  s[cl] = Pxx-[cl] + measurement_noise (class 0: the shifts, class 1: the
+ *      scales).  Per pair (k, j) with a finite object j, in float64 with contraction off: e[c] = z[c] - xp[c] over [sx, tx, sy, ty]
+ *      with z = the object's where row widened;  d2 = ((e0 e0 / s[1] + e1 e1 / s[0]) + e2 e2 / s[1]) + e3 e3 / s[0].  Admissible iff
+ *      d2 <= gate_d2 (a NaN or an inf fails); iou_gate is still checked as an argument and NOT applied.  aff = (1 - w) / (1 + d2) +
+ *      w / (1 + msd): rational, within [0, 1], no transcendental.  The profit, both step 3 and every tie order are unchanged;
+ *      pred_where / pred_boxes stay the forecast row (scales held) and its box.
+ *   One more output, every element written: pred_d2[T,R] (fp32) = for a MATCHED object float(d2) of the pair it was matched in, zero in
+ *   every other row.  Booking a match, the advance of the state, births and ageing are air_track_associate_motion's: the advance
+ *   recomputes xp and s, so for a MATCHED object pred_d2 is the sum of e^2 / s over the innovation e and its variance s of that update,
+ *   and exact consequence (2) holds unchanged.  A newborn track has Pvv = velocity_var: its s says that its rate is unknown, and an
+ *   object displaced by more than its box in its first step can be linked.
+ *   AIR_E_SHAPE also: gate_d2 not finite or not > 0.  AIR_E_NULL / AIR_E_ALIGN as air_track_associate_motion; pred_d2 4-byte aligned.
+ *   A stream entry with the gate does not exist.
  * air_track_idf: the IDF1 counts (Ristani et al. 2016), one 256-thread workgroup per sequence, the frames walked inside.  Hypotheses
  *   and present ground-truth slots as in air_track_score.  overlap[S,G,n_ids] (int32, every element written): overlap[s,g,id] = the
  *   number of (frame, hypothesis) pairs in which present g and a hypothesis with that id have float64 box IoU > tau, strictly (an id
@@ -1055,6 +1073,12 @@ AIR_ENGINE_API int air_track_associate_motion(const float *what, const float *wh
                     double velocity_var, int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
                     int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps, int *state_counts,
                     float *pred_where, float *pred_boxes, void *stream);
+AIR_ENGINE_API int air_track_associate_motion_gated(const float *what, const float *where, const float *boxes, const float *score,
+                    const int *num_objects, int T, int S, int F, int R, int A, int H, int W, double iou_gate, double appearance_weight,
+                    double birth_score, int max_age, int matching, double q_shift, double q_scale, double measurement_noise,
+                    double velocity_var, double gate_d2, int *track_id, signed char *obj_state, float *affinity, int *prev_frame,
+                    int *prev_slot, int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
+                    int *state_counts, float *pred_where, float *pred_boxes, float *pred_d2, void *stream);
 AIR_ENGINE_API int air_track_idf(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
                     int T, int G, int S, int F, int R, int n_ids, int *overlap, int *seq_idf, void *stream);
 AIR_ENGINE_API int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,

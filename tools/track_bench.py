@@ -39,6 +39,11 @@ tool exits with an error; the share of frames on which motion changes a track id
 owner) are timed in turns (plain, motion, plain, motion) in this process on the engine's stream, and the ratio is reported, with the
 two association entries launched eagerly on their own; no bar on time.
 
+--motion --gate measures the Mahalanobis gate on top (track.SequenceTracker(motion=True, motion_gate=True):
+air_track_associate_motion_gated) the same way, against the motion tracker WITHOUT the gate of the same build: the gated tracker must
+agree bit for bit with track.reference_associate_motion(gate=True), pred_d2 included, over the sequences inside the margins; the two
+captured tails are timed in turns (motion, gated, motion, gated) in this process, and the ratio is reported; no bar on time.
+
 Timing: a warm-up, then 5 repeats of --iters calls each between device events; the median repeat is reported with all repeats.  The
 provider and the tracked route alternate inside one process."""
 import argparse
@@ -306,7 +311,9 @@ def one_chunk_size(args, C):
     return res
 
 
-def one_motion_length(args, F):
+def one_motion_length(args, F, gate=False):
+    """--motion: the tracker without motion against the one with it; gate=True (--motion --gate): the motion tracker against the gated
+    one"""
     from attend_infer_repeat_amd import _lib, track
     from attend_infer_repeat_amd.engine_config import EngineConfig
     from attend_infer_repeat_amd.parse import SceneParser
@@ -324,42 +331,44 @@ def one_motion_length(args, F):
     counts = (torch.arange(R, device=dev) % (T + 1)).to(torch.int32)
     host = lambda t: t.cpu().numpy()
     res = dict(frames=F, sequences=S, rows=R, max_steps=T)
+    base, test = ("motion", "gated") if gate else ("plain", "motion")
+    keys = ("track_id", "obj_state", "affinity", "prev_frame", "prev_slot", "pred_where", "pred_boxes") + (("pred_d2",) if gate else ())
     for matching in track.MATCHINGS:
-        plain = track.SequenceTracker(ps, F, birth_score=0.0, matching=matching)
+        plain = track.SequenceTracker(ps, F, birth_score=0.0, matching=matching, motion=True if gate else None)
         plain.capture()
-        moved = track.SequenceTracker(ps, F, birth_score=0.0, matching=matching, motion=True)
+        moved = track.SequenceTracker(ps, F, birth_score=0.0, matching=matching, motion=True, motion_gate=True if gate else None)
         moved.capture()
         plain_ids = host(plain.track(frames, counts)["track_id"]).copy()
         out = moved.track(frames, counts)
         torch.cuda.synchronize()
         ref = track.reference_associate_motion(host(out["what"]).reshape(T, R, -1), host(out["where"]).reshape(T, R, 4), host(out["boxes"]),
                                                host(out["score"]), host(out["num_objects"]), F, moved.img_size, birth_score=0.0,
-                                               matching=matching, return_margins=True)
+                                               matching=matching, return_margins=True, gate=True if gate else None)
         safe = (ref["gate_margin"] >= 1e-9) & (ref.get("round_margin", np.full(S, np.inf)) >= 1e-9)
         rows = np.repeat(safe, F)
         same = lambda a, b: bool((np.ascontiguousarray(a).view(np.uint8) == np.ascontiguousarray(b).view(np.uint8)).all())
-        agree = {k: same(host(out[k])[:, rows], ref[k][:, rows])
-                 for k in ("track_id", "obj_state", "affinity", "prev_frame", "prev_slot", "pred_where", "pred_boxes")}
+        agree = {k: same(host(out[k])[:, rows], ref[k][:, rows]) for k in keys}
         for k in ("num_tracks", "track_first", "track_last", "track_length", "track_gaps", "state_counts"):
             agree[k] = same(host(out[k])[safe], ref[k][safe])
         differ = (host(out["track_id"]) != plain_ids).any(0)
         r = dict(sequences_inside_margins=int(safe.sum()), agreement=agree, tracks=int(ref["num_tracks"].sum()),
-                 tracks_without_motion=int(host(plain.num_tracks).sum()),
-                 state_counts=dict(zip(track.STATES, ref["state_counts"].sum(0).tolist())),
-                 frames_where_motion_changes_an_id=float(differ.mean()))
+                 state_counts=dict(zip(track.STATES, ref["state_counts"].sum(0).tolist())))
+        r["tracks_without_the_gate" if gate else "tracks_without_motion"] = int(host(plain.num_tracks).sum())
+        r["frames_where_the_gate_changes_an_id" if gate else "frames_where_motion_changes_an_id"] = float(differ.mean())
         res[matching] = r
         if not all(agree.values()):
             print(json.dumps(res))
-            raise SystemExit("the motion tracker and the host reference disagree (%s): %r" % (matching, agree))
-        turns = {"plain": [], "motion": []}
+            raise SystemExit("the %s tracker and the host reference disagree (%s): %r" % (test, matching, agree))
+        turns = {base: [], test: []}
         for _ in range(2):
-            for name, t in (("plain", plain), ("motion", moved)):
+            for name, t in ((base, plain), (test, moved)):
                 turns[name].append(median_ms(lambda: eng._replay_or_run(t._graph, t._plan), args.iters, eng.stream))
         for name, v in turns.items():
             r["tail_%s_turns_ms" % name] = [m for m, _ in v]
             r["tail_%s_repeats_ms" % name] = [q for _, q in v]
-        r["tail_plain_ms"], r["tail_motion_ms"] = (statistics.median(r["tail_%s_turns_ms" % n]) for n in ("plain", "motion"))
-        r["motion_over_plain_tail"] = r["tail_motion_ms"] / r["tail_plain_ms"]
+        for n in (base, test):
+            r["tail_%s_ms" % n] = statistics.median(r["tail_%s_turns_ms" % n])
+        r["%s_over_%s_tail" % (test, base)] = r["tail_%s_ms" % test] / r["tail_%s_ms" % base]
         per = {}
         for _ in range(7):
             for (fn, a, name) in plain._plan[:1] + moved._plan[:1]:
@@ -385,6 +394,7 @@ def main(argv=None):
     ap.add_argument("--stream", type=int, nargs="+", default=None, metavar="CHUNK")
     ap.add_argument("--stream-chunks", type=int, default=4)
     ap.add_argument("--motion", action="store_true")
+    ap.add_argument("--gate", action="store_true", help="with --motion: the Mahalanobis gate against the motion tracker without it")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("track_bench measures on the GPU; there is no CPU fallback")
@@ -395,8 +405,11 @@ def main(argv=None):
             for k, v in r.items():
                 print("CHUNK=%-4d %-40s %s" % (r["chunk_frames"], k, v))
         return res
+    if args.gate and not args.motion:
+        raise SystemExit("--gate goes with --motion")
     if args.motion:
-        res = dict(tool="track_bench --motion", device=torch.cuda.get_device_name(0), lengths=[one_motion_length(args, F) for F in args.frames])
+        res = dict(tool="track_bench --motion" + (" --gate" if args.gate else ""), device=torch.cuda.get_device_name(0),
+                   lengths=[one_motion_length(args, F, args.gate) for F in args.frames])
         print(json.dumps(res))
         for r in res["lengths"]:
             for matching in ("greedy", "optimal"):
