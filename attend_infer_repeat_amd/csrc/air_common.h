@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 #include <mutex>
 #include "../../include/air_hip.h"
 
@@ -28,6 +29,48 @@ static inline bool air_gemm_long_k(int M, int N, int K) { return K >= 512 && K >
 static inline bool air_gemm_lone_on_tile16_kw4(int M, int N, int K) {
     const long t = (long)((M + 15) / 16) * ((N + 15) / 16);
     return t <= air_gemm_wide_min_tiles() && air_gemm_latency_tile(t) == 16 && !air_gemm_long_k(M, N, K);
+}
+
+// ---- the owned part of a 16x16 MFMA tile in the 16-wave long-K launches (the BPTT kernels of lstm_kernels.hip, the grouped long-K
+// products of gemm_kernels.hip): the developer switches AIR_LSTM_BWD_TILE / AIR_GEMM_LONGK_TILE = auto | 16x16 | 8x16 | 8x8, read at
+// EVERY call (one process can run every form; a captured graph keeps the form it was captured with).  A value may also name the
+// launches it is for, "entry=8x16,link=16x16" (`key`: the caller's name; a launch the list leaves out is on auto) -- the per-launch A/B
+// of profiles/half_tiles_ab.txt.  Anything else: AIR_TILE_UNKNOWN, which the entry points refuse.
+enum { AIR_TILE_AUTO = 0, AIR_TILE_16x16, AIR_TILE_8x16, AIR_TILE_8x8, AIR_TILE_UNKNOWN };
+static inline int air_tile_shape(const char *e, size_t n) {
+    if (n == 0 || (n == 4 && !strncmp(e, "auto", 4))) return AIR_TILE_AUTO;
+    if (n == 5 && !strncmp(e, "16x16", 5)) return AIR_TILE_16x16;
+    if (n == 4 && !strncmp(e, "8x16", 4)) return AIR_TILE_8x16;
+    if (n == 3 && !strncmp(e, "8x8", 3)) return AIR_TILE_8x8;
+    return AIR_TILE_UNKNOWN;
+}
+static inline int air_tile_env(const char *name, const char *key) {
+    const char *e = getenv(name);
+    if (!e) return AIR_TILE_AUTO;
+    if (!strchr(e, '=')) return air_tile_shape(e, strlen(e));
+    int shape = AIR_TILE_AUTO;
+    const size_t nk = strlen(key);
+    while (*e) {                                                 // key=shape[,key=shape...]
+        const char *end = strchr(e, ',');
+        const size_t n = end ? (size_t)(end - e) : strlen(e);
+        const char *eq = (const char *)memchr(e, '=', n);
+        if (!eq) return AIR_TILE_UNKNOWN;
+        const int s = air_tile_shape(eq + 1, n - (size_t)(eq + 1 - e));
+        if (s == AIR_TILE_UNKNOWN) return s;
+        if ((size_t)(eq - e) == nk && !strncmp(e, key, nk)) shape = s;
+        e += n + (end ? 1 : 0);
+    }
+    return shape;
+}
+// CUs of the current device (256 on an MI355X; that where the query fails)
+static inline int air_cu_count() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+            n = 256;
+        return n;
+    }();
+    return cus;
 }
 
 static inline hipStream_t air_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }

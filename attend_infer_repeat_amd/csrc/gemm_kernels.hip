@@ -136,10 +136,16 @@ __device__ __forceinline__ float apply_epilogue(float v, int m, int n, const Gem
 // MT x NT 16x16 MFMA tiles per wave.  KW = 4 / 16: the workgroup's KW waves split K for ONE tile (LDS reduce; 16
 // waves = 1024 threads for long-K problems with few tiles, so no second split-K launch is needed);
 // KW = 1: the 4 waves own 4 neighbouring N-tiles.
-template <int MT, int NT, int KW, bool BF, bool APRO = false, bool OPT = false, bool GBW = false, bool GATH = false>
+// HALF (<1, 1, 16> only, gemm_grouped_longk_half_kernel): the workgroup OWNS own_r x own_c (8x16 / 8x8 / 16x16, wave-uniform, per problem)
+// of its MFMA tile.  Lanes li >= own_r (own_c) issue NO operand load in the full chunks (zero fragments) and the accumulator rows /
+// columns they feed are never read.  An owned element keeps its K chunks, the order inside a chunk and the reduction over the waves:
+// the bits of the 16x16 tile.
+template <int MT, int NT, int KW, bool BF, bool APRO = false, bool OPT = false, bool GBW = false, bool GATH = false, bool HALF = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_tile, const int split, const AproArgs pro = AproArgs(),
                                           void *c16 = nullptr, const OptFold *opt = nullptr, const bool fold = false,
-                                          const GaussEpi *gb = nullptr, const GatherArgs *gt = nullptr, const bool gcopy = false) {
+                                          const GaussEpi *gb = nullptr, const GatherArgs *gt = nullptr, const bool gcopy = false,
+                                          const int own_r = 16, const int own_c = 16) {
+    static_assert(!HALF || (MT == 1 && NT == 1 && KW == 16 && !APRO && !OPT && !GBW && !GATH), "half tiles: the plain 16-wave body only");
     const gh_t hC = (gh_t)c16;             // bf16 mirror of C (bf16 data path: the next product reads it instead of the fp32 value)
     constexpr int TM = 16 * MT, TN = 16 * NT;
     constexpr int NWN = (KW == 1) ? 4 : 1;               // waves across N
@@ -153,10 +159,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_til
     const gf gC = (gf)g.C, gWs = (gf)g.ws, gCol = (gf)g.colsum;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, lg = lane >> 4;
-    const int tiles_n = (g.N + TN * NWN - 1) / (TN * NWN);
+    const int OWN_M = HALF ? own_r : TM, OWN_N = HALF ? own_c : TN;        // (not HALF: the constants they were)
+    const int tiles_n = (g.N + OWN_N * NWN - 1) / (OWN_N * NWN);
     const int tm = block_tile / tiles_n, tn = block_tile - tm * tiles_n;
-    const int m0 = tm * TM;
-    const int n0 = (tn * NWN + (KW == 1 ? wave : 0)) * TN;
+    const int m0 = tm * OWN_M;
+    const int n0 = (tn * NWN + (KW == 1 ? wave : 0)) * OWN_N;
+    const int own_sh = own_c == 8 ? 3 : 4;                                // e / own_c
 
     const int total_chunks = (g.K + 15) >> 4;
     const int c_begin = split * g.chunks_per_split;
@@ -176,9 +184,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_til
     int rowA[MT], colB[NT];
     bool okA[MT], okB[NT];
 #pragma unroll
-    for (int a = 0; a < MT; ++a) { rowA[a] = m0 + 16 * a + li; okA[a] = rowA[a] < g.M; }
+    for (int a = 0; a < MT; ++a) { rowA[a] = m0 + 16 * a + li; okA[a] = rowA[a] < g.M && (!HALF || li < own_r); }
 #pragma unroll
-    for (int b = 0; b < NT; ++b) { colB[b] = n0 + 16 * b + li; okB[b] = colB[b] < g.N; }
+    for (int b = 0; b < NT; ++b) { colB[b] = n0 + 16 * b + li; okB[b] = colB[b] < g.N && (!HALF || li < own_c); }
 
     // Epilogue operands (bias / aux / beta*C) are fetched NOW, before the K loop, so their memory round trip overlaps
     // the operand loads instead of following the LDS reduction (the kernel is a chain of round trips, not of flops).
@@ -188,9 +196,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_til
 #pragma unroll
         for (int i = 0; i < EPT; ++i) {
             const int e = threadIdx.x + NTH * i;
-            const int r = e / TN, cidx = e - r * TN;
+            const int r = HALF ? (e >> own_sh) : e / TN, cidx = e - r * OWN_N;
             const int m = m0 + r, n = n0 + cidx;
-            const bool ok = (e < TM * TN) && m < g.M && n < g.N;
+            const bool ok = (e < OWN_M * OWN_N) && m < g.M && n < g.N;
             e_bias[i] = (ok && g.bias != nullptr) ? gBias[n] : 0.f;
             e_aux[i] = (ok && g.epi >= AIR_EPI_MUL_DELU) ? gAux[(size_t)m * g.ldaux + n] : 0.f;
             e_c[i] = (ok && g.beta != 0.f) ? gC[(size_t)m * g.ldc + n] : 0.f;
@@ -202,9 +210,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_til
 #pragma unroll
         for (int i = 0; i < EPT; ++i) {
             const int e = threadIdx.x + NTH * i;
-            const int r = e / TN, cidx = e - r * TN;
+            const int r = HALF ? (e >> own_sh) : e / TN, cidx = e - r * OWN_N;
             const int m = m0 + r, n = n0 + cidx;
-            const bool ok = (e < TM * TN) && m < g.M && n < g.N;
+            const bool ok = (e < OWN_M * OWN_N) && m < g.M && n < g.N;
             const size_t o = ok ? (size_t)m * gb->D + n : 0;
             b_loc[i] = ok ? ((gcf)gb->loc)[o] : 0.f;
             b_scale[i] = ok ? ((gcf)gb->scale)[o] : 1.f;
@@ -221,9 +229,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_til
 #pragma unroll
         for (int i = 0; i < EPT; ++i) {
             const int e = threadIdx.x + NTH * i;
-            const int r = e / TN, cidx = e - r * TN;
+            const int r = HALF ? (e >> own_sh) : e / TN, cidx = e - r * OWN_N;
             const int m = m0 + r, n = n0 + cidx;
-            const bool ok = (e < TM * TN) && m < g.M && n < g.N;
+            const bool ok = (e < OWN_M * OWN_N) && m < g.M && n < g.N;
             const size_t idx = ok ? (size_t)((gC + (size_t)m * g.ldc + n) - (gf)opt->g0) : 0;
             o_p[i] = ok ? ((gf)opt->p)[idx] : 0.f;
             o_ms[i] = ok ? ((gf)opt->ms)[idx] : 0.f;
@@ -267,6 +275,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_til
                 const int k = (cu << 4) + 4 * lg;
 #pragma unroll
                 for (int a = 0; a < MT; ++a) {
+                    if (HALF && !okA[a]) { fa[u][a] = (f32x4){0.f, 0.f, 0.f, 0.f}; continue; }     // (outside the owned rows: no load)
                     fa[u][a] = g.ta ? ld_kstrided_full(gA, g.lda, rowAc[a], k)
                                     : ld_kcontig_full(gAs, ldAs, rowAs[a], k, g.vecA != 0);
                     if (APRO) {       // second K-split slab + bias of the producing layer: requested with the operand itself
@@ -275,9 +284,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_til
                     }
                 }
 #pragma unroll
-                for (int b = 0; b < NT; ++b)
+                for (int b = 0; b < NT; ++b) {
+                    if (HALF && !okB[b]) { fb[u][b] = (f32x4){0.f, 0.f, 0.f, 0.f}; continue; }
                     fb[u][b] = g.tb ? ld_kcontig_full(gB, g.ldb, colBc[b], k, g.vecB != 0)
                                     : ld_kstrided_full(gB, g.ldb, colBc[b], k);
+                }
             } else {
 #pragma unroll
                 for (int a = 0; a < MT; ++a) fa[u][a] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -365,8 +376,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int block_til
 #pragma unroll
         for (int i = 0; i < EPT; ++i) {
             const int e = threadIdx.x + NTH * i;
-            if (e >= TM * TN) continue;
-            const int r = e / TN, cidx = e - r * TN;
+            if (e >= OWN_M * OWN_N) continue;
+            const int r = HALF ? (e >> own_sh) : e / TN, cidx = e - r * OWN_N;
             const int m = m0 + r, n = n0 + cidx;
             if (m >= g.M || n >= g.N) continue;
             const int off = r * LDT + cidx;
@@ -978,6 +989,18 @@ __global__ __launch_bounds__(KW == 1 ? 256 : 64 * KW) void gemm_grouped_kernel(G
 #undef AIR_GG_CASE
 }
 
+// gemm_grouped_kernel<1, 1, 16, false> for a launch of few long-K NT problems (the d h_{-1} / d enc_out pair behind the BPTT: 2 x 64
+// tiles, K = 1024, each tile's CU taking in 128 KB of operands beside 128 idle CUs): problem i owns 8 rows (bit 2 i of own8) and 8
+// columns (bit 2 i + 1) of each MFMA tile instead of 16, on two or four times the workgroups; same bits (gemm_body, HALF).
+__global__ __launch_bounds__(1024) void gemm_grouped_longk_half_kernel(GroupArgs ga, unsigned own8) {
+#define AIR_GH_CASE(I_)                                                                                                              \
+    gemm_body<1, 1, 16, false, false, false, false, false, true>(ga.g[I_], (int)blockIdx.x - ga.tile_start[I_], blockIdx.y, AproArgs(),  \
+                                                                 nullptr, nullptr, false, nullptr, nullptr, false,                  \
+                                                                 ((own8 >> (2 * I_)) & 1u) ? 8 : 16, ((own8 >> (2 * I_ + 1)) & 1u) ? 8 : 16)
+    AIR_GROUP_DISPATCH(ga, (int)blockIdx.x, AIR_GH_CASE);
+#undef AIR_GH_CASE
+}
+
 // gemm_grouped_kernel<1, 1, 16> whose problems read their A rows through the feeder's index (GatherArgs): the first launch of a
 // latency-regime train step with an HBM-resident dataset attached (air_gemm_grouped_gather)
 __global__ __launch_bounds__(1024) void gemm_grouped_gather_kernel(GroupArgs ga, GatherArgs gt) {
@@ -1571,7 +1594,8 @@ static int validate_group(const AirGemmDesc *descs, int count) {
 }
 // The workgroups problem i gets under a decided form: the ONE statement of the tile shapes -- the *_form functions add it up into
 // f.workgroups, the launch code builds its workgroup ranges from it.
-static int form_workgroups_of(const AirGemmForm &f, int i, const AirGemmDesc &d) {
+// (own8: the half tiles of gemm_grouped_longk_half_kernel, two bits per problem as there; 0 elsewhere)
+static int form_workgroups_of(const AirGemmForm &f, int i, const AirGemmDesc &d, unsigned own8 = 0u) {
     switch (f.family) {
         case AIR_GEMM_FAM_BIG: case AIR_GEMM_FAM_BIG16:
             return ((f.small_mask >> i) & 1u) ? air_cdiv(d.M, 16) * air_cdiv(d.N, 16) : air_cdiv(d.M, 64) * air_cdiv(d.N, 64);
@@ -1581,12 +1605,36 @@ static int form_workgroups_of(const AirGemmForm &f, int i, const AirGemmDesc &d)
             if ((f.sk_mask >> i) & 1u) return shortk_workgroups(d.M);
             [[fallthrough]];
         default:
-            return air_cdiv(d.M, f.tile) * air_cdiv(d.N, f.tile);
+            return air_cdiv(d.M, ((own8 >> (2 * i)) & 1u) ? 8 : f.tile) * air_cdiv(d.N, ((own8 >> (2 * i + 1)) & 1u) ? 8 : f.tile);
     }
 }
-static void form_sum_workgroups(AirGemmForm &f, const AirGemmDesc *descs, int count) {
+static void form_sum_workgroups(AirGemmForm &f, const AirGemmDesc *descs, int count, unsigned own8 = 0u) {
     f.workgroups = 0;
-    for (int i = 0; i < count; ++i) f.workgroups += form_workgroups_of(f, i, descs[i]);
+    for (int i = 0; i < count; ++i) f.workgroups += form_workgroups_of(f, i, descs[i], own8);
+}
+// ---- half tiles for a launch the rule above puts on the 16-wave K split (family TILE, KW = 16) ------------------------------------
+// Domain: fp32, every problem an NT product (both operands k-contiguous) without colsum whose epilogue is NONE or MUL_DELU -- the
+// launch behind the BPTT.  AIR_GEMM_LONGK_TILE (air_common.h: air_tile_env) forces a shape for every problem of such a launch and is
+// refused (AIR_E_UNSUPPORTED, nothing launched) by a 16-wave launch outside the domain; launches of the other forms do not read it.
+// auto: 8x16 (GEMM_LONGK_TILE_AUTO) for a GROUP whose 16x16 tiling leaves at least half the CUs without a tile: what the A/B of the step
+// adopted (profiles/half_tiles_ab.txt; 8x8 lost 5 us there).  *own8: two bits per problem (rows, columns halved), 0 = the 16x16 launch.
+static constexpr bool GEMM_LONGK_TILE_AUTO = true;
+static int longk_half_shapes(const AirGemmDesc *descs, int count, const AirGemmForm &f, long tiles16, unsigned *own8) {
+    *own8 = 0u;
+    if (f.family != AIR_GEMM_FAM_TILE || f.KW != 16) return AIR_OK;
+    int shape = air_tile_env("AIR_GEMM_LONGK_TILE", "group");
+    AIR_REQUIRE(shape != AIR_TILE_UNKNOWN, AIR_E_UNSUPPORTED);
+    bool domain = !f.bf;
+    for (int i = 0; i < count; ++i)
+        domain = domain && !descs[i].ta && descs[i].tb && !descs[i].colsum &&
+                 (descs[i].epilogue == AIR_EPI_NONE || descs[i].epilogue == AIR_EPI_MUL_DELU);
+    AIR_REQUIRE(domain || shape == AIR_TILE_AUTO || shape == AIR_TILE_16x16, AIR_E_UNSUPPORTED);
+    if (shape == AIR_TILE_AUTO) {
+        shape = (GEMM_LONGK_TILE_AUTO && domain && count > 1 && 2 * tiles16 <= air_cu_count()) ? AIR_TILE_8x16 : AIR_TILE_16x16;
+    }
+    const unsigned per = shape == AIR_TILE_8x8 ? 3u : (shape == AIR_TILE_8x16 ? 1u : 0u);
+    for (int i = 0; i < count; ++i) *own8 |= per << (2 * i);
+    return AIR_OK;
 }
 // more than AIR_GEMM_GROUP_MAX problems: only the all-TN wide-tile form (the deferred weight gradients of a step)
 static int big_tn_form(const AirGemmDesc *descs, int count, AirGemmForm &f) {
@@ -1706,8 +1754,9 @@ extern "C" int air_gemm_grouped_gather(const AirGemmDesc *descs, int count, cons
     return AIR_OK;
 }
 
-static int gemm_grouped_form(const AirGemmDesc *descs, int count, AirGemmForm &f) {
+static int gemm_grouped_form(const AirGemmDesc *descs, int count, AirGemmForm &f, unsigned *own8_out = nullptr) {
     memset(&f, 0, sizeof f);
+    if (own8_out) *own8_out = 0u;
     if (count > AIR_GEMM_GROUP_MAX) return big_tn_form(descs, count, f);
     AIR_REQUIRE(count > 0 && count <= AIR_GEMM_GROUP_MAX, AIR_E_SHAPE);
     f.grouped = count > 1 ? 1 : 0;
@@ -1772,7 +1821,11 @@ static int gemm_grouped_form(const AirGemmDesc *descs, int count, AirGemmForm &f
         AIR_REQUIRE(T_ == 16, AIR_E_UNSUPPORTED);
         f.family = AIR_GEMM_FAM_APRO; f.MT = f.NT = 1; f.KW = 4; f.threads = 256;
     } else f.family = AIR_GEMM_FAM_TILE;
-    form_sum_workgroups(f, descs, count);
+    unsigned own8;
+    if (int err = longk_half_shapes(descs, count, f, tiles16, &own8)) return err;
+    if (own8) { f.grouped = 1; f.small_mask = (1u << count) - 1u; }        // half tiles: always the grouped kernel
+    if (own8_out) *own8_out = own8;
+    form_sum_workgroups(f, descs, count, own8);
     return AIR_OK;
 }
 extern "C" int air_gemm_grouped_form(const AirGemmDesc *descs, int count, AirGemmForm *out) {
@@ -1783,16 +1836,22 @@ extern "C" int air_gemm_grouped_form(const AirGemmDesc *descs, int count, AirGem
 extern "C" int air_gemm_grouped(const AirGemmDesc *descs, int count, void *stream) {
     AIR_REQUIRE(descs, AIR_E_NULL);
     AirGemmForm f;
-    if (int err = gemm_grouped_form(descs, count, f)) return err;
+    unsigned own8 = 0u;
+    if (int err = gemm_grouped_form(descs, count, f, &own8)) return err;
     if (f.family == AIR_GEMM_FAM_BIG || f.family == AIR_GEMM_FAM_BIG16) return launch_big_tn_group(descs, count, f, stream);
     if (f.family == AIR_GEMM_FAM_SHORTK) return launch_grouped_sk(descs, count, f, stream);
     GroupArgs ga;
     int tiles = 0;
     const bool wide = f.family == AIR_GEMM_FAM_WIDE || f.family == AIR_GEMM_FAM_WIDE16;
-    int err = fill_group(ga, descs, count, accept_any, [&](int i, const AirGemmDesc &d) { return form_workgroups_of(f, i, d); }, &tiles);
+    int err = fill_group(ga, descs, count, accept_any, [&](int i, const AirGemmDesc &d) { return form_workgroups_of(f, i, d, own8); }, &tiles);
     if (err) return err;
     hipStream_t st = air_stream(stream);
     const bool bf = f.bf != 0;
+    if (own8) {
+        hipLaunchKernelGGL(gemm_grouped_longk_half_kernel, dim3(tiles), dim3(1024), 0, st, ga, own8);
+        AIR_LAUNCH_CHECK();
+        return AIR_OK;
+    }
     if (wide) {
         const int wt = tiles;
         ga.xcd_map = f.xcd_map;

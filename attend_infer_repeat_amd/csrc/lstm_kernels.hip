@@ -14,7 +14,8 @@
 //
 // One 16x16 accumulator tile per workgroup, KW waves interleave the 16-deep K chunks (as gemm_body<1,1,KW>); A is always
 // k-contiguous, B is k-strided (forward: W_h[K=Hd, 4Hd]) or k-contiguous (backward: W_h read as [N=Hd, K=4Hd]).
-template <int KW, bool BF, bool B_KCONTIG>
+// (MASK: lanes whose row / column is not ok issue NO load in the full chunks instead of a clamped one -- the half tiles of the BPTT link)
+template <int KW, bool BF, bool B_KCONTIG, bool MASK = false>
 __device__ __forceinline__ void tile16_kloop(f32x4 (&acc)[1][1], gcf gA, int lda, int rowA, bool okA, bool vecA, gcf gB,
                                              int ldb, int colB, bool okB, bool vecB, int K, int limA, int limB) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lg = lane >> 4;
@@ -29,8 +30,10 @@ __device__ __forceinline__ void tile16_kloop(f32x4 (&acc)[1][1], gcf gA, int lda
             const int cu = c + u * KW;
             if (cu < full_end) {
                 const int k = (cu << 4) + 4 * lg;
-                fa[u][0] = ld_kcontig_full(gA, lda, rowAc, k, vecA);
-                fb[u][0] = B_KCONTIG ? ld_kcontig_full(gB, ldb, colBc, k, vecB) : ld_kstrided_full(gB, ldb, colBc, k);
+                fa[u][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                fb[u][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (!MASK || okA) fa[u][0] = ld_kcontig_full(gA, lda, rowAc, k, vecA);
+                if (!MASK || okB) fb[u][0] = B_KCONTIG ? ld_kcontig_full(gB, ldb, colBc, k, vecB) : ld_kstrided_full(gB, ldb, colBc, k);
             } else {
                 fa[u][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 fb[u][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -447,26 +450,32 @@ struct LstmBwdArgs {
 // that (m,u): dgates_t (4 values), dc_{t-1}, and the running sum over time of dgates (what x.W_x receives) -- all
 // element-wise in (m,u), so the 16x16 output tile finishes everything it owns
 // (opt: an optimiser slice on the workgroups past the tiles -- a separate kernel argument, untouched by the tile workgroups)
-template <int KW, bool BF>
+//
+// R x C (16x16, 8x16, 8x8): the part of the MFMA tile a workgroup OWNS.  Few 16x16 tiles with a long K (batch 64: 64 tiles, K = 1024)
+// leave most CUs without a tile while each tile's CU takes in (16 + 16) K floats; a half tile spreads the same product over two or
+// four times the workgroups at (R + C) K floats each.  Lanes li >= R (>= C) issue NO operand load (tile16_kloop, MASK: their
+// fragments are zero) and the accumulator rows / columns they feed are never read.  An owned element sees the K chunks, the order
+// inside a chunk and the reduction over the waves of the 16x16 tile: the same bits.
+template <int KW, bool BF, int R = 16, int C = 16>
 __global__ __launch_bounds__(64 * KW) void lstm_bwd_fused_kernel(LstmBwdArgs g, RmspropSlice opt) {
     constexpr int LDT = 20;
     __shared__ float s_tile[KW][16 * LDT];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
-    const int tiles_n = (g.Hd + 15) >> 4;
+    const int tiles_n = (g.Hd + C - 1) / C;
     {
-        const int tiles = ((g.M + 15) >> 4) * tiles_n;
+        const int tiles = ((g.M + R - 1) / R) * tiles_n;
         if ((int)blockIdx.x >= tiles) {
             rmsprop_slice_body(opt, (int)blockIdx.x - tiles, (int)gridDim.x - tiles);
             return;
         }
     }
     const int tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
-    const int m0 = tm * 16, n0 = tn * 16;
+    const int m0 = tm * R, n0 = tn * C;
     const int rowA = m0 + li, colB = n0 + li;
-    const bool okA = rowA < g.M, okB = colB < g.Hd;
+    const bool okA = li < R && rowA < g.M, okB = li < C && colB < g.Hd;
     const int K = 4 * g.Hd;
-    const int er = threadIdx.x >> 4, ec = threadIdx.x & 15, em = m0 + er, eu = n0 + ec;
-    const bool e_ok = threadIdx.x < 256 && em < g.M && eu < g.Hd;
+    const int er = threadIdx.x / C, ec = threadIdx.x & (C - 1), em = m0 + er, eu = n0 + ec;
+    const bool e_ok = threadIdx.x < R * C && em < g.M && eu < g.Hd;
     float gi = 0.f, gj = 0.f, gff = 0.f, go = 0.f, cp = 0.f, cc = 0.f, dha = 0.f, dhb = 0.f, dci = 0.f, sx[4] = {0.f, 0.f, 0.f, 0.f};
     if (e_ok) {
         const size_t e = (size_t)em * g.Hd + eu;
@@ -485,8 +494,8 @@ __global__ __launch_bounds__(64 * KW) void lstm_bwd_fused_kernel(LstmBwdArgs g, 
     }
     f32x4 acc[1][1];
     acc[0][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    tile16_kloop<KW, BF, true>(acc, (gcf)g.dgates_next, K, rowA, okA, g.vecA != 0, (gcf)g.w_h, K, colB, okB, g.vecB != 0, K,
-                               g.M, g.Hd - 1);
+    tile16_kloop<KW, BF, true, (R < 16 || C < 16)>(acc, (gcf)g.dgates_next, K, rowA, okA, g.vecA != 0, (gcf)g.w_h, K, colB, okB, g.vecB != 0, K,
+                                                   g.M, g.Hd - 1);
 #pragma unroll
     for (int r = 0; r < 4; ++r) s_tile[wave][(4 * lg + r) * LDT + li] = acc[0][0][r];
     __syncthreads();
@@ -547,27 +556,30 @@ __device__ __forceinline__ void lstm_pw_bwd_elem(float gi, float gj, float gf, f
     d[3] = dhe * tc * go * (1.f - go);
     dc_prev = dct * gf;
 }
+// R x C: the owned part of the MFMA tile, as in lstm_bwd_fused_kernel (lanes li >= R load nothing and form a zero operand row, lanes
+// li >= C load no weights; the first column of tiles stores the entry's own outputs: still one store per row tile).
+template <int R, int C>
 __global__ __launch_bounds__(1024) void lstm_bwd_entry_kernel(LstmBwdArgs g, LstmEntryArgs en, RmspropSlice opt) {
     constexpr int KW = 16, LDT = 20;
     __shared__ float s_tile[KW][16 * LDT];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
-    const int tiles_n = g.Hd >> 4;
+    const int tiles_n = g.Hd / C;
     {
-        const int tiles = ((g.M + 15) >> 4) * tiles_n;
+        const int tiles = ((g.M + R - 1) / R) * tiles_n;
         if ((int)blockIdx.x >= tiles) {
             rmsprop_slice_body(opt, (int)blockIdx.x - tiles, (int)gridDim.x - tiles);
             return;
         }
     }
     const int tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
-    const int m0 = tm * 16, n0 = tn * 16;
-    const int rowA = m0 + li, colB = n0 + li;                   // Hd % 16 == 0: every column of the tile exists
-    const bool okA = rowA < g.M;
-    const int rowAc = okA ? rowA : g.M - 1;
+    const int m0 = tm * R, n0 = tn * C;
+    const int rowA = m0 + li, colB = n0 + (li & (C - 1));       // Hd % 16 == 0: every column of the tile exists
+    const bool okA = li < R && rowA < g.M, okB = li < C;
+    const int rowAc = rowA < g.M ? rowA : g.M - 1;
     const int Hd = g.Hd, K = 4 * Hd;
     // ---- epilogue operands of thread (er, ec): step T-2's, and step T-1's for dc_in and the running sum
-    const int er = threadIdx.x >> 4, ec = threadIdx.x & 15, em = m0 + er, eu = n0 + ec;
-    const bool e_ok = threadIdx.x < 256 && em < g.M;
+    const int er = threadIdx.x / C, ec = threadIdx.x & (C - 1), em = m0 + er, eu = n0 + ec;
+    const bool e_ok = threadIdx.x < R * C && em < g.M;
     float gi = 0.f, gj = 0.f, gff = 0.f, go = 0.f, cp = 0.f, cc = 0.f, dha = 0.f, dhb = 0.f;
     float gi1 = 0.f, gj1 = 0.f, gf1 = 0.f, go1 = 0.f, cp1 = 0.f, cc1 = 0.f, dha1 = 0.f, dhb1 = 0.f;
     if (e_ok) {
@@ -594,14 +606,21 @@ __global__ __launch_bounds__(1024) void lstm_bwd_entry_kernel(LstmBwdArgs g, Lst
         const size_t eo = (size_t)rowAc * Hd + u4, ao = (size_t)rowAc * K + u4;
         // all loads of the group first: 4 gate vectors, 2 cell states, 2 dh terms, 4 weight fragments
         f32x4 a_g[4], fb[4];
+        const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+        f32x4 v_cp = zero4, v_c = zero4, v_da = zero4, v_db = zero4;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) a_g[q] = *(gcf4)((gcf)en.gate_act1 + ao + (size_t)q * Hd);
-        const f32x4 v_cp = *(gcf4)((gcf)en.c_prev1 + eo), v_c = *(gcf4)((gcf)en.c1 + eo);
-        f32x4 v_da = (f32x4){0.f, 0.f, 0.f, 0.f}, v_db = v_da;
-        if (en.dh_a1) v_da = *(gcf4)((gcf)en.dh_a1 + eo);
-        if (en.dh_b1) v_db = *(gcf4)((gcf)en.dh_b1 + eo);
+        for (int q = 0; q < 4; ++q) { a_g[q] = zero4; fb[q] = zero4; }
+        if (R == 16 || okA) {                                    // (half tiles: lanes outside the owned rows / columns load nothing)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) fb[q] = *(gcf4)(gW + (size_t)q * Hd + u4);
+            for (int q = 0; q < 4; ++q) a_g[q] = *(gcf4)((gcf)en.gate_act1 + ao + (size_t)q * Hd);
+            v_cp = *(gcf4)((gcf)en.c_prev1 + eo); v_c = *(gcf4)((gcf)en.c1 + eo);
+            if (en.dh_a1) v_da = *(gcf4)((gcf)en.dh_a1 + eo);
+            if (en.dh_b1) v_db = *(gcf4)((gcf)en.dh_b1 + eo);
+        }
+        if (C == 16 || okB) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) fb[q] = *(gcf4)(gW + (size_t)q * Hd + u4);
+        }
         f32x4 fa[4], v_dcp;
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
@@ -1065,6 +1084,19 @@ extern "C" int air_lstm_first_step_fwd(const float *x, int ldx, int E, const flo
     return AIR_OK;
 }
 
+// ---- the owned tile shape of the 16-wave BPTT kernels (lstm_bwd_fused_kernel<16, false, R, C>, lstm_bwd_entry_kernel<R, C>) ----------
+// AIR_LSTM_BWD_TILE (air_common.h: air_tile_env; the launches' names there are "link" and "entry").  A forced shape the entry point
+// cannot honour -- the 4-wave or wide-tile link, bf16 operands, a value the switch does not know -- is AIR_E_UNSUPPORTED before anything
+// is launched.
+// auto: half tiles where the 16x16 tiling leaves at least half the CUs without a tile and K = 4 Hd >= 512 (below, a tile's operands
+// are no more than a forward step's and the launch sits on its floor) -- the shape each launch's own A/B adopted
+// (profiles/half_tiles_ab.txt: 8x16 for both, with the optimiser riders aboard; 8x8, a tile on every CU, LOST 2-3 us per launch).
+enum { LSTM_LINK_TILE = AIR_TILE_8x16, LSTM_ENTRY_TILE = AIR_TILE_8x16 };
+static int lstm_bwd_tile_auto(int M, int Hd, int adopted) {
+    const long tiles16 = (long)air_cdiv(M, 16) * air_cdiv(Hd, 16);
+    return (2 * tiles16 > air_cu_count() || 4 * Hd < 512) ? (int)AIR_TILE_16x16 : adopted;
+}
+
 template <bool BF>
 static int lstm_bwd_launch(const LstmBwdArgs &g, const RmspropSlice &opt, size_t opt_nq, hipStream_t st) {
     const int tiles = air_cdiv(g.M, 16) * air_cdiv(g.Hd, 16);
@@ -1072,7 +1104,16 @@ static int lstm_bwd_launch(const LstmBwdArgs &g, const RmspropSlice &opt, size_t
     const bool wide = tiles > 512 && g.Hd % 64 == 0 && g.vecA && g.vecB;
     const int nth = tiles <= 512 ? 1024 : (wide ? 512 : 256);
     size_t extra = air_rider_blocks(opt_nq, nth, 512);                     // about two float4 per thread of the riding slice
+    int shape = air_tile_env("AIR_LSTM_BWD_TILE", "link");
+    AIR_REQUIRE(shape != AIR_TILE_UNKNOWN, AIR_E_UNSUPPORTED);
+    AIR_REQUIRE(shape == AIR_TILE_AUTO || shape == AIR_TILE_16x16 || (tiles <= 512 && !BF), AIR_E_UNSUPPORTED);
+    if (shape == AIR_TILE_AUTO)
+        shape = (tiles <= 512 && !BF) ? lstm_bwd_tile_auto(g.M, g.Hd, LSTM_LINK_TILE) : AIR_TILE_16x16;
     if (wide) hipLaunchKernelGGL((lstm_bwd_wide_kernel<BF>), dim3(air_cdiv(g.M, 16) * (g.Hd / 64) + (int)extra), dim3(512), 0, st, g, opt);
+    else if (shape == AIR_TILE_8x16)
+        hipLaunchKernelGGL((lstm_bwd_fused_kernel<16, false, 8, 16>), dim3(air_cdiv(g.M, 8) * air_cdiv(g.Hd, 16) + (int)extra), dim3(1024), 0, st, g, opt);
+    else if (shape == AIR_TILE_8x8)
+        hipLaunchKernelGGL((lstm_bwd_fused_kernel<16, false, 8, 8>), dim3(air_cdiv(g.M, 8) * air_cdiv(g.Hd, 8) + (int)extra), dim3(1024), 0, st, g, opt);
     else if (tiles <= 512) hipLaunchKernelGGL((lstm_bwd_fused_kernel<16, BF>), dim3(tiles + (int)extra), dim3(1024), 0, st, g, opt);
     else hipLaunchKernelGGL((lstm_bwd_fused_kernel<4, BF>), dim3(tiles + (int)extra), dim3(256), 0, st, g, opt);
     AIR_LAUNCH_CHECK();
@@ -1127,9 +1168,16 @@ extern "C" int air_lstm_step_bwd_entry(const float *gate_act1, const float *c_pr
     LstmEntryArgs en;
     en.gate_act1 = gate_act1; en.c_prev1 = c_prev1; en.c1 = c1; en.dh_a1 = dh_a1; en.dh_b1 = dh_b1; en.dgates1 = dgates1;
     en.dc_prev1 = dc_prev1;
-    const int tiles = air_cdiv(M, 16) * (Hd / 16);
     size_t extra = air_rider_blocks(onq, 1024, 512);
-    hipLaunchKernelGGL(lstm_bwd_entry_kernel, dim3(tiles + (int)extra), dim3(1024), 0, air_stream(stream), g, en, os);
+    int shape = air_tile_env("AIR_LSTM_BWD_TILE", "entry");
+    AIR_REQUIRE(shape != AIR_TILE_UNKNOWN, AIR_E_UNSUPPORTED);
+    if (shape == AIR_TILE_AUTO) shape = lstm_bwd_tile_auto(M, Hd, LSTM_ENTRY_TILE);
+    if (shape == AIR_TILE_8x16)
+        hipLaunchKernelGGL((lstm_bwd_entry_kernel<8, 16>), dim3(air_cdiv(M, 8) * (Hd / 16) + (int)extra), dim3(1024), 0, air_stream(stream), g, en, os);
+    else if (shape == AIR_TILE_8x8)
+        hipLaunchKernelGGL((lstm_bwd_entry_kernel<8, 8>), dim3(air_cdiv(M, 8) * (Hd / 8) + (int)extra), dim3(1024), 0, air_stream(stream), g, en, os);
+    else
+        hipLaunchKernelGGL((lstm_bwd_entry_kernel<16, 16>), dim3(air_cdiv(M, 16) * (Hd / 16) + (int)extra), dim3(1024), 0, air_stream(stream), g, en, os);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

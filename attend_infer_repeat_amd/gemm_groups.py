@@ -401,14 +401,25 @@ def wide_group_eligible(descs, bf, wide_min_tiles=1000, wide_tn_bf16=48, wide_tn
     return bool(ok), min_k, bool(nt_short)
 
 
+def longk_half_tile(descs, bf, cus=256, adopted=True):
+    """gemm_kernels.hip longk_half_shapes with AIR_GEMM_LONGK_TILE on auto, for a launch on the 16-wave K split of the tile family: the
+    (rows, columns) of a 16x16 MFMA tile a workgroup owns -- half tiles (gemm_grouped_longk_half_kernel) for an fp32 GROUP of NT products
+    without colsum whose epilogues are NONE / MUL_DELU and whose 16x16 tiling leaves at least half of the `cus` CUs without a tile:
+    (8, 16); (16, 16) everywhere else"""
+    t16 = sum(tiles16(d) for d in descs)
+    domain = not bf and all((not d.ta) and d.tb and not _a(d.colsum) and d.epilogue in (0, 3) for d in descs)
+    return (8, 16) if (adopted and domain and len(descs) > 1 and 2 * t16 <= cus) else (16, 16)
+
+
 def grouped_form(descs, wide_min_tiles=1000, shortk=True, shortk_min_m=4096, shortk_wgs=384, wide_tn_bf16=48, wide_tn_f32=48, wide_nt_k=512,
-                 bf16_storage=True, big_xcd=True):
+                 bf16_storage=True, big_xcd=True, cus=256):
     """gemm_kernels.hip gemm_grouped_form (air_gemm_grouped_form): the whole rule of air_gemm_grouped -> (status, form | None), the form a
     dict over the fields of AirGemmForm.  The keyword arguments are the library's environment-tunable thresholds at their defaults
     (AIR_GEMM_WIDE_MIN_TILES, AIR_GEMM_SHORTK, AIR_GEMM_SHORTK_MIN_M, AIR_GEMM_SHORTK_WGS, AIR_GEMM_WIDE_TN_BF16, AIR_GEMM_WIDE_TN_F32,
     AIR_GEMM_WIDE_NT_K, AIR_GEMM_BF16_STORAGE, AIR_GEMM_BIG_XCD).  In order: more than 8 problems -> the big TN group; a plain fp32 group
     with streaming short-K weight gradients -> "shortk"; the wide-tile regime (bf16 TN: the big-group launch, per-problem mirrors);
-    else the tile families "c16" / "apro" / "tile" on <1, 1, 16> (group_long_k), <1, 1, 4> or <2, 2, 4>."""
+    else the tile families "c16" / "apro" / "tile" on <1, 1, 16> (group_long_k), <1, 1, 4> or <2, 2, 4>; a "tile" launch on <1, 1, 16>
+    may run on half tiles (longk_half_tile: small_mask = its problems, workgroups = the half tiles; `cus` = the device's CUs)."""
     count = len(descs)
     if count > 8:
         return _big_tn_form(descs, bf16_storage, big_xcd)
@@ -467,4 +478,8 @@ def grouped_form(descs, wide_min_tiles=1000, shortk=True, shortk_min_m=4096, sho
         if tile != 16:
             return E_UNSUPPORTED, None
         f.update(family=2, MT=1, NT=1, KW=4, threads=256)
+    elif lk:
+        tr, tc = longk_half_tile(descs, bf, cus)
+        if (tr, tc) != (16, 16):
+            f.update(grouped=1, small_mask=(1 << count) - 1, workgroups=sum(_cdiv(d.M, tr) * _cdiv(d.N, tc) for d in descs))
     return 0, f
