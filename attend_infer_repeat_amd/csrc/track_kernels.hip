@@ -14,6 +14,8 @@
 //   air_track_score:     CLEAR-MOT counts of the tracks against ground truth whose slot g is one object over a sequence;
 //   air_track_idf:       the IDF1 counts of the same tracks: the (ground-truth slot, id) overlap table of a sequence and the largest
 //                        one-to-one sum over it, by dynamic programming over the subsets of slots.
+//   air_track_hota:      the HOTA counts of the same tracks at 19 localisation thresholds: two passes over the frames, the potential
+//                        table of every (slot, id) first, then one optimal matching per frame scored by it (the one-wavefront solver).
 // Everything a float decides is float64 with contraction off; no floating-point atomics, no cross-workgroup traffic, one fixed order:
 // the same bits run to run.
 #include <math.h>
@@ -1195,6 +1197,225 @@ extern "C" int air_track_idf(const float *boxes, const int *num_objects, const i
     AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
     const TrackIdfArgs a = {boxes, gt_boxes, num_objects, track_id, overlap, seq_idf, tau, T, G, S, F, n_ids};
     hipLaunchKernelGGL(track_idf_kernel, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// ============================================================================================================
+// hota
+// ============================================================================================================
+struct TrackHotaArgs {
+    const float *boxes, *gt_boxes;
+    const int *num_objects, *track_id;
+    double *potential, *seq_hota_f;
+    int *id_count, *gt_count, *matches, *seq_hota_i;
+    int T, G, S, F, n_ids;
+};
+#define TRACK_HOTA_ALPHAS 19             // alpha_k = k / 20.0, k = 1..19
+
+// One 256-thread workgroup per sequence; both passes over the frames run here.  The staging and the pair p = g * 32 + j, one per
+// thread, are track_idf_kernel's; a hypothesis that takes part has 0 <= id < n_ids.  Pass 1: thread (g, j) adds to pot[g, id_j] when j
+// is the first hypothesis of its id in the frame -- then it adds the frame's terms of that id in ascending j, so every element has one
+// writer per frame and the order is the stated one; thread j likewise adds the frame's count of its id to ic.  Pass 2: the int64
+// profits in LDS, wavefront 0 runs track_solve_wave (columns g < G, every other slot column forbidden), thread (a, g) books the match
+// of slot g at threshold a, thread a adds tp and loc over g in ascending order.  The end: thread (a, g) adds the ids in ascending
+// order, thread a the slots.  The tables are global memory written and read by this workgroup alone, a barrier between the two.
+__global__ __launch_bounds__(TRACK_THREADS) void track_hota_kernel(TrackHotaArgs a) {
+#pragma clang fp contract(off)
+    __shared__ long long profit_s[TRACK_MAXT * TRACK_MAXT];        // [column k][object j]; columns >= 8 stay forbidden
+    __shared__ double sim_s[TRACK_MAXG * TRACK_MAXT], rs_s[TRACK_MAXG], cs_s[TRACK_MAXT];
+    __shared__ double part_s[3][TRACK_HOTA_ALPHAS * TRACK_MAXG];
+    __shared__ float4 hbox_s[TRACK_MAXT], gbox_s[TRACK_MAXG];
+    __shared__ int hid_s[TRACK_MAXT], hyp_s[TRACK_MAXT], ostate_s[TRACK_MAXT], gpresent_s[TRACK_MAXG], gc_s[TRACK_MAXG];
+    __shared__ int match_s[TRACK_MAXG], max_id_s, dets_s[2];
+    const int T = a.T, G = a.G, F = a.F, R = a.S * F, n_ids = a.n_ids;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    double *pot = a.potential + (size_t)s * G * n_ids;
+    int *ic = a.id_count + (size_t)s * n_ids;
+    int *mat = a.matches + (size_t)s * TRACK_HOTA_ALPHAS * G * n_ids;
+    for (int e = tid; e < G * n_ids; e += TRACK_THREADS) pot[e] = 0.0;
+    for (int e = tid; e < n_ids; e += TRACK_THREADS) ic[e] = 0;
+    for (int e = tid; e < TRACK_HOTA_ALPHAS * G * n_ids; e += TRACK_THREADS) mat[e] = 0;
+    for (int e = tid; e < TRACK_MAXT * TRACK_MAXT; e += TRACK_THREADS) profit_s[e] = -1;
+    if (tid < TRACK_MAXG) gc_s[tid] = 0;
+    if (tid == 0) max_id_s = -1;
+    int gt_dets = 0, hyp_dets = 0;                                 // thread 0's, thread 128's
+    int tp = 0;                                                    // thread 192 + a: its threshold's
+    double loc = 0.0;
+    const int pg = tid >> 5, pj = tid & 31;                        // this thread's pair
+    const int ba = tid >> 3, bg = tid & 7;                         // this thread's (threshold, slot), ba < 19
+    const double alpha = (double)(ba + 1) / 20.0;
+    __syncthreads();
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int f = 0; f < F; ++f) {
+            const int r = s * F + f;
+            int n = a.num_objects[r];
+            n = n < 0 ? 0 : (n > T ? T : n);
+            if (tid < TRACK_MAXT) {
+                const int j = tid;
+                float4 box = make_float4(0.f, 0.f, 0.f, 0.f);
+                int id = -1, hyp = 0;
+                if (j < n) {
+                    const size_t row = (size_t)j * R + r;
+                    box = *reinterpret_cast<const float4 *>(a.boxes + 4 * row);
+                    const int t = a.track_id[row];
+                    if (t >= 0 && track_finite4(box)) {
+                        hyp = 1;
+                        if (t < n_ids) id = t;
+                    }
+                }
+                hbox_s[j] = box;
+                hid_s[j] = id;                                     // -1: takes no part
+                hyp_s[j] = hyp;
+                ostate_s[j] = id >= 0 ? TRACK_UNCONFIRMED : TRACK_ABSENT;
+            }
+            if (tid >= 64 && tid < 64 + TRACK_MAXG) {
+                const int g = tid - 64;
+                float4 gb = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (g < G) gb = *reinterpret_cast<const float4 *>(a.gt_boxes + 4 * ((size_t)r * G + g));
+                gbox_s[g] = gb;
+                gpresent_s[g] = (g < G && gb.z > 0.f) ? 1 : 0;
+                match_s[g] = -1;
+            }
+            __syncthreads();
+            const int id = hid_s[pj];
+            const double sim = (gpresent_s[pg] && id >= 0) ? box_iou_f64(gbox_s[pg], hbox_s[pj]) : 0.0;
+            sim_s[tid] = sim;
+            __syncthreads();
+            if (pass == 0) {
+                if (tid < TRACK_MAXG) {                            // rs[g]: ascending j (a pair that is none adds +0)
+                    double v = 0.0;
+                    for (int j = 0; j < TRACK_MAXT; ++j) v = v + sim_s[tid * TRACK_MAXT + j];
+                    rs_s[tid] = v;
+                    gc_s[tid] += gpresent_s[tid];
+                }
+                if (tid >= 64 && tid < 64 + TRACK_MAXT) {          // cs[j]: ascending g
+                    const int j = tid - 64;
+                    double v = 0.0;
+                    for (int g = 0; g < TRACK_MAXG; ++g) v = v + sim_s[g * TRACK_MAXT + j];
+                    cs_s[j] = v;
+                }
+                if (tid == 0)
+                    for (int g = 0; g < TRACK_MAXG; ++g) gt_dets += gpresent_s[g];
+                if (tid == 128) {
+                    int h = 0, top = max_id_s;
+                    for (int j = 0; j < TRACK_MAXT; ++j) {
+                        h += hyp_s[j];
+                        top = hid_s[j] > top ? hid_s[j] : top;
+                    }
+                    hyp_dets += h;
+                    max_id_s = top;
+                }
+                __syncthreads();
+                if (id >= 0) {
+                    bool first = true;
+                    for (int j = 0; j < pj; ++j) first = first && hid_s[j] != id;
+                    if (first) {
+                        if (gpresent_s[pg]) {
+                            double v = pot[(size_t)pg * n_ids + id];
+                            const double rsg = rs_s[pg];
+                            for (int j = pj; j < TRACK_MAXT; ++j) {
+                                if (hid_s[j] != id) continue;
+                                const double sj = sim_s[pg * TRACK_MAXT + j];
+                                const double d = (cs_s[j] + rsg) - sj;
+                                if (d > 0x1p-52) v = v + sj / d;
+                            }
+                            pot[(size_t)pg * n_ids + id] = v;
+                        }
+                        if (pg == 0) {
+                            int c = 0;
+                            for (int j = pj; j < TRACK_MAXT; ++j) c += hid_s[j] == id ? 1 : 0;
+                            ic[id] += c;
+                        }
+                    }
+                }
+            } else {
+                if (sim > 0.0) {                                   // admissible: present g < G, 0 <= id < n_ids
+                    const double p = pot[(size_t)pg * n_ids + id];
+                    const double A = p / (((double)gc_s[pg] + (double)ic[id]) - p);
+                    profit_s[tid] = 1 + (long long)floor((A * sim) * 4294967296.0);
+                } else {
+                    profit_s[tid] = -1;
+                }
+                __syncthreads();
+                if (tid < 64) {                                    // wavefront 0, every lane
+                    const int row = track_solve_wave(profit_s, ostate_s, T, tid);
+                    if (tid < G) match_s[tid] = row;
+                }
+                __syncthreads();
+                if (ba < TRACK_HOTA_ALPHAS && bg < G) {
+                    const int j = match_s[bg];
+                    if (j >= 0 && sim_s[bg * TRACK_MAXT + j] >= alpha) mat[((size_t)ba * G + bg) * n_ids + hid_s[j]] += 1;
+                }
+                if (tid >= 192 && tid < 192 + TRACK_HOTA_ALPHAS) { // thread a: the matched pairs in ascending g
+                    const double al = (double)(tid - 192 + 1) / 20.0;
+                    for (int g = 0; g < G; ++g) {
+                        const int j = match_s[g];
+                        if (j < 0) continue;
+                        const double sj = sim_s[g * TRACK_MAXT + j];
+                        if (sj >= al) {
+                            tp += 1;
+                            loc = loc + sj;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) dets_s[0] = gt_dets;
+    if (tid == 128) dets_s[1] = hyp_dets;
+    __syncthreads();
+    const int last_id = max_id_s;
+    if (ba < TRACK_HOTA_ALPHAS) {
+        double ass = 0.0, ass_re = 0.0, ass_pr = 0.0;
+        if (bg < G) {
+            const int *m = mat + ((size_t)ba * G + bg) * n_ids;
+            const double gcg = (double)gc_s[bg];
+            for (int i = 0; i <= last_id; ++i) {
+                const int ci = m[i];
+                if (ci <= 0) continue;
+                const double c = (double)ci, ici = (double)ic[i];
+                ass = ass + c * (c / ((gcg + ici) - c));
+                ass_re = ass_re + c * (c / gcg);
+                ass_pr = ass_pr + c * (c / ici);
+            }
+        }
+        part_s[0][tid] = ass, part_s[1][tid] = ass_re, part_s[2][tid] = ass_pr;
+    }
+    __syncthreads();
+    if (tid < TRACK_MAXG && tid < G) a.gt_count[(size_t)s * G + tid] = gc_s[tid];
+    if (tid >= 192 && tid < 192 + TRACK_HOTA_ALPHAS) {
+        const int k = tid - 192;
+        double v[3] = {0.0, 0.0, 0.0};
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) v[q] = v[q] + part_s[q][k * TRACK_MAXG + g];
+        int *oi = a.seq_hota_i + ((size_t)s * TRACK_HOTA_ALPHAS + k) * 3;
+        double *of = a.seq_hota_f + ((size_t)s * TRACK_HOTA_ALPHAS + k) * 4;
+        oi[0] = tp, oi[1] = dets_s[0] - tp, oi[2] = dets_s[1] - tp;
+        of[0] = v[0], of[1] = v[1], of[2] = v[2], of[3] = loc;
+    }
+}
+
+extern "C" int air_track_hota(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, int T, int G,
+                              int S, int F, int R, int n_ids, double *potential, int *id_count, int *gt_count, int *matches,
+                              int *seq_hota_i, double *seq_hota_f, void *stream) {
+    AIR_REQUIRE(boxes && num_objects && track_id && gt_boxes && potential && id_count && gt_count && matches && seq_hota_i &&
+                    seq_hota_f, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && G >= 1 && G <= TRACK_MAXG && S > 0 && F > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(n_ids >= 1 && n_ids <= TRACK_MAX_IDS, AIR_E_SHAPE);
+    AIR_REQUIRE((long)S * TRACK_HOTA_ALPHAS * G * n_ids <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(boxes) && air_aligned16(gt_boxes), AIR_E_ALIGN);
+    AIR_REQUIRE(((reinterpret_cast<uintptr_t>(potential) | reinterpret_cast<uintptr_t>(seq_hota_f)) & 7u) == 0, AIR_E_ALIGN);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(num_objects) | reinterpret_cast<uintptr_t>(track_id) |
+                           reinterpret_cast<uintptr_t>(id_count) | reinterpret_cast<uintptr_t>(gt_count) |
+                           reinterpret_cast<uintptr_t>(matches) | reinterpret_cast<uintptr_t>(seq_hota_i);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    const TrackHotaArgs a = {boxes, gt_boxes, num_objects, track_id, potential, seq_hota_f, id_count, gt_count, matches, seq_hota_i,
+                             T, G, S, F, n_ids};
+    hipLaunchKernelGGL(track_hota_kernel, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

@@ -488,7 +488,8 @@ def make_trajectory_fig(frames, result, max_frames=8, checkpoint_dir=None, globa
 
 def make_track_score_logger(air, data, num_batches, name, batch_size=None, writer=None, tau=0.5, measure_time=True, iou_gate=None,
                             appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None,
-                            propose=None, temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None):
+                            propose=None, temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None,
+                            hota=False):
     """make_tiled_parse_score_logger's counterpart for sequences (air.score_track): `data` is an annotated dataset dict of SEQUENCES
     (imgs [N, F, H, W], boxes [N, F, G, 4], instances [N, F, H, W] int8 -- data.create_moving_mnist with return_annotations=True),
     walked in `num_batches` batches of `batch_size` sequences (None: the model's batch size).  Prints / writes the identity figures
@@ -502,7 +503,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
     record names it).  identity=True: the IDF figures beside MOTA -- idf1, idp, idr, idtp, idfp, idfn (air_track_idf), and with smooth=
     smooth_idf1 of the completed table.  motion=True | dict: every track is matched against its predicted box (air.track's argument;
     the record holds the noise terms under `motion`).  motion_gate=True | D2 (with motion): the pairs are gated and ranked by their
-    squared Mahalanobis distance (air.track's argument; the record holds the gate under `motion_gate`)."""
+    squared Mahalanobis distance (air.track's argument; the record holds the gate under `motion_gate`).  hota=True: HOTA beside MOTA
+    -- hota, deta, assa, loca (air_track_hota; means over the 19 thresholds), and with smooth= smooth_hota of the completed table."""
     import torch
     from .track import STATES
     tk = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
@@ -517,6 +519,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
         tk["motion"] = motion
     if motion_gate is not None:
         tk["motion_gate"] = motion_gate
+    if hota:
+        tk["hota"] = True
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -562,6 +566,13 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
             if smooth is not None:
                 acc["smooth_idf1"] = air.track_smoother.identity_summary()["idf1"]
                 shown += ["smooth_idf1"]
+        if hota:
+            fig = tracker.hota_summary()
+            acc.update({k: fig[k] for k in ("hota", "deta", "assa", "loca")})
+            shown[2:2] = ["hota", "deta", "assa", "loca"]
+            if smooth is not None:
+                acc["smooth_hota"] = air.track_smoother.hota_summary()["hota"]
+                shown += ["smooth_hota"]
         t = time.time() - start
         msg = 'Step {}, Data {} track score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:

@@ -664,7 +664,7 @@ class AIRonMNIST(AIRModel):
 
     def score_track(self, frames, gt_boxes, tau=0.5, accumulate=True, gt_instances=None, thresholds=None, iou_gate=None,
                     appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None,
-                    temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None):
+                    temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None, hota=False):
         """`track`, then the identity metric of the tracks against gt_boxes [S, F, G, 4] (G <= 8; slot g is the same object in every
         frame of a sequence, width <= 0 = absent) on the device (track.SequenceTracker.score).  The sums accumulate in the tracker
         this returns alongside -- (scores, tracker): its summary() reads MOTA, MOTP, the identity switches and the mostly tracked /
@@ -675,7 +675,10 @@ class AIRonMNIST(AIRModel):
         scores["completed"] holds its tensors, `self.track_smoother` is the smoother, whose summary() / reset() are the completed
         table's -- the raw figures stay the tracker's.  matching= is `track`'s; identity=True adds the IDF1 counts (air_track_idf behind
         air_track_score: seq_idf, idf_overlap, totals_idf; the tracker's -- and the smoother's -- identity_summary() reads IDF1, IDP
-        and IDR back).  motion= and motion_gate= are `track`'s."""
+        and IDR back).  motion= and motion_gate= are `track`'s.  hota=True also runs air_track_hota (track.SequenceTracker.hota): scores[
+        "hota"] holds the tracker's tensors and totals (seq_hota_i, seq_hota_f, the tables, totals_hota_i / totals_hota_f), with smooth=
+        scores["completed"]["hota"] the completed table's; hota_summary() of the tracker / the smoother reads HOTA, DetA, AssA and LocA
+        back.  hota=False, the default: exactly the call without the argument."""
         t, smoother = self._track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal,
                                   smooth, matching, motion, motion_gate)
         gb = torch.as_tensor(gt_boxes)
@@ -683,6 +686,10 @@ class AIRonMNIST(AIRModel):
         if smoother is not None:
             self.track_smoother = smoother
             scores["completed"] = smoother.score(gb, tau, accumulate, identity)
+        if hota:
+            scores["hota"] = t.hota(gb, accumulate)
+            if smoother is not None:
+                scores["completed"] = dict(scores["completed"], hota=smoother.hota(gb, accumulate))
         if gt_instances is not None:
             G = int(gb.shape[-2])
             s = self._scorer("track_scorer", t.provider, G, thresholds)

@@ -153,6 +153,10 @@ def main(argv=None):
     ap.add_argument("--track-identity", action="store_true",
                     help="with --track-eval: also report IDF1, IDP and IDR (air_track_idf: how long each ground-truth object keeps one "
                          "identity) beside MOTA")
+    ap.add_argument("--track-hota", action="store_true",
+                    help="with --track-eval: also report HOTA, DetA, AssA and LocA (air_track_hota: how well objects are found and how "
+                         "well the matched detections are kept in one identity, over 19 localisation thresholds) beside MOTA; not with "
+                         "--track-stream (HOTA is out of scope on a stream)")
     ap.add_argument("--track-stream", type=int, default=None, metavar="CHUNK",
                     help="with --track-eval: also run the same sequences through a STREAM in chunks of CHUNK frames (the last chunk "
                          "ragged; AIRonMNIST.track_stream, track.StreamTracker: the track table carried on the device between the chunks) "
@@ -241,6 +245,10 @@ def main(argv=None):
 
     if (args.track_matching is not None or args.track_identity) and track_eval is None:
         ap.error("--track-matching and --track-identity go with --track-eval")
+    if args.track_hota and track_eval is None:
+        ap.error("--track-hota goes with --track-eval")
+    if args.track_hota and args.track_stream is not None:
+        ap.error("--track-hota does not go with --track-stream (HOTA is out of scope on a stream)")
     if args.track_stream is not None:
         if track_eval is None:
             ap.error("--track-stream goes with --track-eval")
@@ -454,7 +462,7 @@ def main(argv=None):
         before_track_log = log
         track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
                                             smooth=track_smooth, matching=args.track_matching, identity=args.track_identity,
-                                            motion=track_motion, motion_gate=track_motion_gate, **refine_kw)
+                                            motion=track_motion, motion_gate=track_motion_gate, hota=args.track_hota, **refine_kw)
 
         stream_log = None
         if args.track_stream is not None:

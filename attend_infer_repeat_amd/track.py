@@ -117,6 +117,39 @@ programming over the 2^G subsets of slots, the ids visited in ascending order.  
 the frames), hyp_frames (hypotheses summed over the frames), ids with overlap}.  On the host: IDFN = gt_frames - idtp, IDFP = hyp_frames
 - idtp, IDP = idtp / hyp_frames, IDR = idtp / gt_frames, IDF1 = 2 idtp / (gt_frames + hyp_frames); a denominator of 0 gives nan.
 
+HOTA (air_track_hota; Luiten et al., IJCV 2021, the figure TrackEval reports: HOTA = sqrt(DetA AssA) averaged over 19 localisation
+thresholds -- DetA says how well objects are found, AssA how well the matched detections are kept together in one identity, LocA how
+well the matches are localised; MOTA is dominated by detection, IDF1 is one global match at one tau).  Inputs as for air_track_idf.
+Hypotheses of a frame and present slots as above; a hypothesis whose id is >= n_ids takes no part in any table or matching (its sim
+is 0 everywhere, it is no row of the matching, it adds to no count but hyp_dets) and so counts as an unmatched hypothesis.  sim[g, j]
+= the float64 box IoU of a present slot g and a hypothesis j (id < n_ids), 0 otherwise.  Everything a float decides is float64 with
+contraction off, only + - * / and floor, in the order written here; no transcendental and no square root on the device.  Thresholds:
+alpha_k = k / 20.0, k = 1..19 (HOTA_ALPHAS), computed that way on the device too; a match counts at alpha_k iff sim >= alpha_k.
+  pass 1, the frames in order:  rs[g] = sum_j sim[g, j] in ascending j, cs[j] = sum_g sim[g, j] in ascending g;  for every present g and
+          hypothesis j, in ascending j:  d = (cs[j] + rs[g]) - sim[g, j], and if d > 2^-52:  pot[g, id_j] += sim[g, j] / d  (an id
+          twice in a frame adds twice; a pair with sim = 0 adds +0: no change of bits);  gc[g] += 1 per present slot, ic[id_j] += 1 per
+          hypothesis.
+  pass 2, the frames in order:  (g, j) is admissible iff sim[g, j] > 0;  A = pot[g, id] / ((gc[g] + ic[id]) - pot[g, id]) with the
+          counts widened to float64;  profit = 1 + (int64) floor((A sim) 2^32).  ONE matching per frame, whatever the threshold: the
+          exact optimal assignment of `solve_assignment` (air_track_associate_optimal's solver and tie rule, above) with the
+          hypotheses in ascending j as rows, the slots g < G as columns and every other slot column forbidden.  For every matched
+          (g, j) in ascending g, with L = the number of k with sim >= alpha_k:  for a < L:  tp[a] += 1, loc[a] += sim,
+          matches[a, g, id_j] += 1.  gt_dets += present slots, hyp_dets += hypotheses (those with an id >= n_ids included).
+  the end of the sequence:  fn[a] = gt_dets - tp[a], fp[a] = hyp_dets - tp[a];  with c = matches[a, g, id] over c > 0, the counts
+          widened:  ass[a] = sum c (c / ((gc[g] + ic[id]) - c)), ass_re[a] = sum c (c / gc[g]), ass_pr[a] = sum c (c / ic[id]) -- per
+          (a, g) over the ids in ascending order, then per a over g in ascending order.
+Outputs per sequence, every element written: seq_hota_i [S, 19, 3] int32 (HOTA_COUNTS: tp, fn, fp), seq_hota_f [S, 19, 4] float64
+(HOTA_SUMS: ass, ass_re, ass_pr, loc), hota_potential [S, G, n_ids] float64, hota_id_count [S, n_ids], hota_gt_count [S, G],
+hota_matches [S, 19, G, n_ids] int32.  `hota_summary` combines sequences in TrackEval's way: the counts and the numerators are summed,
+then per threshold DetA = tp / max(1, tp + fn + fp), DetRe = tp / max(1, tp + fn), DetPr = tp / max(1, tp + fp), AssA = ass / max(1,
+tp) (AssRe, AssPr alike), LocA = loc / tp or 1 when tp = 0, HOTA_a = sqrt(DetA AssA) -- the only square root, on the host -- and the
+figures are the means over the 19 thresholds; nan for every figure when there was neither ground truth nor a hypothesis.  TWO STATED
+DEPARTURES from TrackEval: 1. the matching score A sim is quantised to 2^-32 (and 1 is added) for an exact integer solver with a stated
+tie rule, where TrackEval hands floats to scipy's solver: the two can differ only where two assignments lie within 2^-32 per pair of
+each other;  2. no epsilon at the thresholds: TrackEval counts sim >= alpha - eps, this rule sim >= alpha.  Out of scope: HOTA on a
+stream (the tables are indexed by global id, as for IDF1), mask IoU, thresholds other than the 19, HOTA per class.  The HOTA of a
+trained model's tracks is unmeasured (profiles/track_hota.txt says what was measured: the cost of the launch).
+
 `SequenceTracker` owns no engine, like tile.TiledSceneParser and score.ParseScorer: it binds to a parse.SceneParser, refine.ParseRefiner,
 prune.ParsePruner, propose.ParseProposer or tile.TiledSceneParser at R = S F rows, runs that provider's own `parse()` on the frames and
 then, on the same engine stream, its own launch list of libair_hip.so entries (include/air_hip.h), ONE hipGraph after `capture()`
@@ -143,7 +176,8 @@ per slot live, id, age, length, gaps, first, the last sighting's global frame an
 tracks retired in a chunk come as a list (ascending retirement frame, then slot), the live ones stay in the state.  A stream issues
 the ids 0..32766 (track_owner is int16); a birth beyond is OVERFLOW.  The metric continues across chunks: map[g], tracked[g],
 present[g], the counters and sum_iou are carried, seq_counts and seq_iou are cumulative.  Out of scope on a stream: IDF1 (its overlap
-table is indexed by global id: 1 MB per sequence at 32767 ids), ids beyond 32766 without `reset`, more than 32 live tracks.  Trajectories
+table is indexed by global id: 1 MB per sequence at 32767 ids), HOTA (its tables are indexed by global id too, 19 thresholds deep:
+StreamTracker has no `hota`), ids beyond 32766 without `reset`, more than 32 live tracks.  Trajectories
 on a stream are trajectory.StreamSmoother's: fixed-lag smoothed rows `lag` frames late and a forecast per chunk.  `reference_associate_stream` / `reference_score_stream` restate a chunk in numpy
 with the per-frame code of the one-shot references.
 
@@ -167,6 +201,10 @@ ABSENT, MATCHED, BORN, UNCONFIRMED, OVERFLOW, NONFINITE = range(6)
 STATES = ("absent", "matched", "born", "unconfirmed", "overflow", "nonfinite")
 COUNTS = ("gt", "matches", "misses", "fp", "idsw", "mostly_tracked", "mostly_lost", "gt_objects")
 IDF_COUNTS = ("idtp", "gt_frames", "hyp_frames", "ids_with_overlap")
+HOTA_ALPHAS = tuple(k / 20.0 for k in range(1, 20))               # the 19 localisation thresholds 0.05 .. 0.95
+HOTA_COUNTS = ("tp", "fn", "fp")                                   # seq_hota_i [S, 19, 3]
+HOTA_SUMS = ("ass", "ass_re", "ass_pr", "loc")                     # seq_hota_f [S, 19, 4]
+HOTA_EPS = 2.0 ** -52                                              # pass 1 adds sim / d only where d > HOTA_EPS
 MATCHINGS = ("greedy", "optimal")
 PROFIT_SCALE = 4294967296.0        # 2^32: profit = 1 + floor(aff * 2^32)
 DEFAULTS = dict(iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1)
@@ -883,11 +921,146 @@ def idf_summary(totals) -> Dict[str, float]:
             "idfp": hyp_frames - idtp, "idfn": gt_frames - idtp, "gt_frames": gt_frames, "hyp_frames": hyp_frames}
 
 
+def _hota_score(A, sim):
+    """pass 2 of HOTA: the score a pair is matched by (a function of its own so that a test can plant another rule)"""
+    return A * sim
+
+
+def _hota_levels(sim):
+    """pass 2 of HOTA: L = the number of thresholds a match of this sim counts at: sim >= alpha_k, no epsilon"""
+    return sum(1 for alpha in HOTA_ALPHAS if sim >= alpha)
+
+
+def reference_hota(boxes, num_objects, track_id, gt_boxes, n_frames, n_ids=None, return_matching=False):
+    """air_track_hota restated in numpy float64 and `solve_assignment`, operation for operation (HOTA in the module text).  boxes
+    [T, R, 4], num_objects [R], track_id [T, R], gt_boxes [R, G, 4] (or [S, F, G, 4]); n_ids: None = n_frames * T.  Returns
+    seq_hota_i [S, 19, 3] int32 (HOTA_COUNTS), seq_hota_f [S, 19, 4] float64 (HOTA_SUMS), hota_potential [S, G, n_ids] float64,
+    hota_id_count [S, n_ids], hota_gt_count [S, G] and hota_matches [S, 19, G, n_ids] int32.  return_matching=True adds hota_match
+    [R, G] int32: the hypothesis matched to slot g in that frame (the one matching, before any threshold), -1 for none."""
+    import numpy as np
+    boxes = np.asarray(boxes, np.float32)
+    gt = np.asarray(gt_boxes, np.float32)
+    gt = gt.reshape(-1, gt.shape[-2], 4)
+    ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
+    T, R = ids.shape
+    G, F = gt.shape[1], int(n_frames)
+    n_ids = F * T if n_ids is None else int(n_ids)
+    if not 1 <= T <= MAX_SLOTS:
+        raise ValueError("track_id: 1..%d objects per frame, got %d" % (MAX_SLOTS, T))
+    if not 1 <= G <= MAX_GT:
+        raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+    if F < 1 or R % F or gt.shape[0] != R:
+        raise ValueError("%d rows / %d ground-truth rows are not sequences of %d frames" % (R, gt.shape[0], F))
+    if not 1 <= n_ids <= MAX_IDS:
+        raise ValueError("n_ids must be within 1..%d, got %d" % (MAX_IDS, n_ids))
+    S, NA = R // F, len(HOTA_ALPHAS)
+    if S * NA * G * n_ids > 2 ** 31 - 1:
+        raise ValueError("hota_matches [%d, %d, %d, %d] would have more than 2^31 - 1 elements" % (S, NA, G, n_ids))
+    out = {"seq_hota_i": np.zeros((S, NA, 3), np.int32), "seq_hota_f": np.zeros((S, NA, 4), np.float64),
+           "hota_potential": np.zeros((S, G, n_ids), np.float64), "hota_id_count": np.zeros((S, n_ids), np.int32),
+           "hota_gt_count": np.zeros((S, G), np.int32), "hota_matches": np.zeros((S, NA, G, n_ids), np.int32)}
+    hota_match = np.full((R, G), -1, np.int32)
+    for s in range(S):
+        pot, ic, gc, matches = out["hota_potential"][s], out["hota_id_count"][s], out["hota_gt_count"][s], out["hota_matches"][s]
+        frames = []
+        gt_dets = hyp_dets = 0
+        for f in range(F):                                         # pass 1
+            r = s * F + f
+            n = int(min(max(n_in[r], 0), T))
+            hyp = [j for j in range(n) if ids[j, r] >= 0 and np.isfinite(boxes[j, r]).all()]
+            rows = [j for j in hyp if ids[j, r] < n_ids]           # the hypotheses that take part
+            present = [g for g in range(G) if gt[r, g, 2] > 0]
+            sim = np.zeros((G, T), np.float64)
+            for g in present:
+                for j in rows:
+                    sim[g, j] = box_iou(gt[r, g], boxes[j, r])
+            rs, cs = _sequential_sum(sim), _sequential_sum(sim.T)
+            for g in present:
+                for j in rows:
+                    d = (cs[j] + rs[g]) - sim[g, j]
+                    if d > HOTA_EPS:
+                        pot[g, ids[j, r]] += sim[g, j] / d
+                gc[g] += 1
+            for j in rows:
+                ic[ids[j, r]] += 1
+            gt_dets, hyp_dets = gt_dets + len(present), hyp_dets + len(hyp)
+            frames.append((r, rows, present, sim))
+        tp, loc = np.zeros(NA, np.int64), np.zeros(NA, np.float64)
+        for r, rows, present, sim in frames:                       # pass 2
+            if not rows:
+                continue
+            profit, admissible = np.zeros((len(rows), MAX_SLOTS), np.int64), np.zeros((len(rows), MAX_SLOTS), bool)
+            for q, j in enumerate(rows):
+                i = ids[j, r]
+                for g in present:
+                    if sim[g, j] > 0.0:
+                        A = pot[g, i] / ((np.float64(gc[g]) + np.float64(ic[i])) - pot[g, i])
+                        profit[q, g], admissible[q, g] = 1 + int(math.floor(_hota_score(A, sim[g, j]) * PROFIT_SCALE)), True
+            for q, g in enumerate(solve_assignment(profit, admissible)):
+                if g >= 0:
+                    hota_match[r, g] = rows[q]
+            for g in range(G):                                     # the matched pairs in ascending g
+                j = int(hota_match[r, g])
+                if j < 0:
+                    continue
+                for a in range(_hota_levels(sim[g, j])):
+                    tp[a] += 1
+                    loc[a] = loc[a] + sim[g, j]
+                    matches[a, g, ids[j, r]] += 1
+        gcf, icf = gc.astype(np.float64), ic.astype(np.float64)
+        for a in range(NA):                                        # the end of the sequence
+            sums = [np.float64(0.0)] * 3
+            for g in range(G):
+                part = [np.float64(0.0)] * 3
+                for i in np.nonzero(matches[a, g])[0]:             # (ascending ids)
+                    c = np.float64(matches[a, g, i])
+                    part[0] = part[0] + c * (c / ((gcf[g] + icf[i]) - c))
+                    part[1] = part[1] + c * (c / gcf[g])
+                    part[2] = part[2] + c * (c / icf[i])
+                sums = [sums[k] + part[k] for k in range(3)]
+            out["seq_hota_i"][s, a] = (tp[a], gt_dets - tp[a], hyp_dets - tp[a])
+            out["seq_hota_f"][s, a] = (sums[0], sums[1], sums[2], loc[a])
+    if return_matching:
+        out["hota_match"] = hota_match
+    return out
+
+
+def hota_summary(totals_i, totals_f) -> Dict[str, object]:
+    """The HOTA figures of summed seq_hota_i [19, 3] (HOTA_COUNTS) and seq_hota_f [19, 4] (HOTA_SUMS) rows, TrackEval's way of
+    combining sequences: per threshold DetA = tp / max(1, tp + fn + fp), DetRe = tp / max(1, tp + fn), DetPr = tp / max(1, tp + fp),
+    AssA / AssRe / AssPr = ass / ass_re / ass_pr over max(1, tp), LocA = loc / tp (1 when tp = 0), HOTA = sqrt(DetA AssA).  Returns
+    hota, deta, assa, detre, detpr, assre, asspr, loca (the means over the 19 thresholds), hota0, loca0 (at alpha = 0.05), per_alpha
+    (the 19-long lists under the same names, and alpha) and the counts gt_dets, hyp_dets; every figure nan when there was neither
+    ground truth nor a hypothesis."""
+    import numpy as np
+    ti, tf = np.asarray(totals_i).astype(np.int64), np.asarray(totals_f, np.float64)
+    NA = len(HOTA_ALPHAS)
+    if ti.shape != (NA, 3) or tf.shape != (NA, 4):
+        raise ValueError("hota_summary: expected totals [%d, 3] and [%d, 4], got %s and %s" % (NA, NA, ti.shape, tf.shape))
+    names = ("hota", "deta", "assa", "detre", "detpr", "assre", "asspr", "loca")
+    per = {k: [] for k in names}
+    gt_dets, hyp_dets = int(ti[0, 0] + ti[0, 1]), int(ti[0, 0] + ti[0, 2])
+    empty = gt_dets == 0 and hyp_dets == 0
+    for a in range(NA):
+        tp, fn, fp = (int(v) for v in ti[a])
+        ass, ass_re, ass_pr, loc = (float(v) for v in tf[a])
+        row = dict(deta=tp / max(1, tp + fn + fp), detre=tp / max(1, tp + fn), detpr=tp / max(1, tp + fp), assa=ass / max(1, tp),
+                   assre=ass_re / max(1, tp), asspr=ass_pr / max(1, tp), loca=loc / tp if tp else 1.0)
+        row["hota"] = math.sqrt(row["deta"] * row["assa"])
+        for k in names:
+            per[k].append(float("nan") if empty else row[k])
+    out = {k: sum(per[k]) / NA for k in names}
+    out.update(hota0=per["hota"][0], loca0=per["loca"][0], gt_dets=gt_dets, hyp_dets=hyp_dets)
+    out["per_alpha"] = dict(per, alpha=list(HOTA_ALPHAS))
+    return out
+
+
 class IdentityScores:
     """The identity metric of a stage (the tracker on its own table, the smoother on its two): the air_track_score launch of every
     key used so far with its buffers and graph (`entries`, at most four: a sweep over tau must not pile up buffers and graphs), the
     staging copy of the ground truth, and the running totals on the device.  An entry made with identity=True runs air_track_idf
-    behind air_track_score (one graph still) and feeds `totals_idf`."""
+    behind air_track_score (one graph still) and feeds `totals_idf`.  HOTA has a cache of its own (`hota_entries`, at most two, keyed
+    by (table, G): the air_track_hota launch, its buffers and graph) and totals of its own (`totals_hota_i`, `totals_hota_f`)."""
 
     def __init__(self, stage, S):
         import torch
@@ -897,6 +1070,9 @@ class IdentityScores:
             self.totals_i = torch.zeros((8,), dtype=torch.int64, device=dev)
             self.totals_f = torch.zeros((1,), dtype=torch.float64, device=dev)
             self.totals_idf = torch.zeros((4,), dtype=torch.int64, device=dev)
+            self.totals_hota_i = torch.zeros((len(HOTA_ALPHAS), 3), dtype=torch.int64, device=dev)
+            self.totals_hota_f = torch.zeros((len(HOTA_ALPHAS), 4), dtype=torch.float64, device=dev)
+        self.hota_entries = {}                                     # (table, G) -> buffers, plan, graph: at most two, apart from `entries`
 
     def entry(self, key, G, tau, T, n_frames, boxes, counts, ids, identity=False, n_ids=None):
         """the air_track_score launch on a table of T rows by S * n_frames columns (boxes, counts, ids) with its buffers -- gt_boxes,
@@ -984,6 +1160,61 @@ class IdentityScores:
         eng.wait_for_engine()
         return out
 
+    def hota_entry(self, key, G, T, n_frames, boxes, counts, ids, n_ids):
+        """the air_track_hota launch on a table of T rows by S * n_frames columns (boxes, counts, ids) with its buffers -- gt_boxes,
+        seq_hota_i, seq_hota_f, hota_potential, hota_id_count, hota_gt_count, hota_matches -- kept in `hota_entries` under key + (G,);
+        captured (one graph) when the stage holds a graph.  `entries` and its keys are not touched."""
+        import torch
+        eng, S, N, NA = self.engine, self.S, self.S * n_frames, len(HOTA_ALPHAS)
+        G, n_ids = int(G), int(n_ids)
+        key = key + (G,)
+        entry = self.hota_entries.get(key)
+        if entry is None:
+            if not 1 <= n_ids <= MAX_IDS:
+                raise ValueError("n_ids must be within 1..%d, got %r" % (MAX_IDS, n_ids))
+            if not 1 <= G <= MAX_GT:
+                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+            if S * NA * G * n_ids > 2 ** 31 - 1:
+                raise ValueError("hota_matches [%d, %d, %d, %d] would have more than 2^31 - 1 elements" % (S, NA, G, n_ids))
+            H, dev = self.stage._H, eng.device
+            L, p = H.lib(), H._p
+            z = lambda shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
+            with torch.cuda.device(dev):
+                entry = {"gt_boxes": z((N, G, 4), torch.float32), "seq_hota_i": z((S, NA, 3)), "seq_hota_f": z((S, NA, 4), torch.float64),
+                         "hota_potential": z((S, G, n_ids), torch.float64), "hota_id_count": z((S, n_ids)),
+                         "hota_gt_count": z((S, G)), "hota_matches": z((S, NA, G, n_ids)), "graph": None}
+            entry["plan"] = [(L.air_track_hota, (p(boxes), p(counts), p(ids), p(entry["gt_boxes"]), T, G, S, n_frames, N, n_ids,
+                                                 p(entry["hota_potential"]), p(entry["hota_id_count"]), p(entry["hota_gt_count"]),
+                                                 p(entry["hota_matches"]), p(entry["seq_hota_i"]), p(entry["seq_hota_f"])),
+                              "air_track_hota")]
+            if self.stage._graph is not None:
+                eng.synchronize()
+                entry["graph"] = eng._capture_plans([entry["plan"]])
+            while len(self.hota_entries) >= 2:
+                destroy_graphs([self.hota_entries.pop(next(iter(self.hota_entries)))["graph"]])
+            self.hota_entries[key] = entry
+        return entry
+
+    def run_hota(self, gt_boxes, n_frames, entry_for, accumulate=None):
+        """stage gt_boxes into the buffers of `entry_for(G)` (a hota_entry), issue it and return its outputs; accumulate True / False:
+        added to / restarting totals_hota_i [19, 3] int64 and totals_hota_f [19, 4] float64 on the device (no read-back), and they"""
+        import torch
+        eng = self.engine
+        entry = self.run(gt_boxes, n_frames, entry_for)
+        out = {k: entry[k] for k in ("seq_hota_i", "seq_hota_f", "hota_potential", "hota_id_count", "hota_gt_count", "hota_matches")}
+        if accumulate is not None:
+            with torch.cuda.stream(eng.stream):
+                ti, tf = entry["seq_hota_i"].sum(0, dtype=torch.int64), entry["seq_hota_f"].sum(0)
+                if accumulate:
+                    self.totals_hota_i += ti
+                    self.totals_hota_f += tf
+                else:
+                    self.totals_hota_i.copy_(ti)
+                    self.totals_hota_f.copy_(tf)
+            out.update(totals_hota_i=self.totals_hota_i, totals_hota_f=self.totals_hota_f)
+        eng.wait_for_engine()
+        return out
+
     def reset(self):
         """zero the totals"""
         import torch
@@ -993,6 +1224,8 @@ class IdentityScores:
             self.totals_i.zero_()
             self.totals_f.zero_()
             self.totals_idf.zero_()
+            self.totals_hota_i.zero_()
+            self.totals_hota_f.zero_()
         eng.wait_for_engine()
 
     def summary(self) -> Dict[str, float]:
@@ -1006,6 +1239,15 @@ class IdentityScores:
         """idf_summary of everything scored with identity=True since the last reset (ONE read-back)"""
         self.engine.wait_for_engine()
         return idf_summary(self.totals_idf.tolist())
+
+    def hota_summary(self) -> Dict[str, object]:
+        """hota_summary of everything `hota` took since the last reset (ONE read-back)"""
+        import torch
+        self.engine.wait_for_engine()
+        NA = len(HOTA_ALPHAS)
+        flat = torch.cat([self.totals_hota_i.double().reshape(-1), self.totals_hota_f.reshape(-1)]).tolist()
+        return hota_summary([[int(v) for v in flat[3 * a:3 * a + 3]] for a in range(NA)],
+                            [flat[3 * NA + 4 * a:3 * NA + 4 * a + 4] for a in range(NA)])
 
 
 class SequenceTracker(BoundStage):
@@ -1082,7 +1324,7 @@ class SequenceTracker(BoundStage):
         self._plan = [e for seg in self.segments.values() for e in seg]
 
     def _score_entries(self):
-        return self._score.values()
+        return list(self._score.values()) + list(self.scores.hota_entries.values())
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `track()` call behind the bound provider's own (`parser` holds that provider's launch_count())"""
@@ -1148,6 +1390,22 @@ class SequenceTracker(BoundStage):
         return self.scores.result(self.scores.run(gt_boxes, self.F, lambda G: self._score_entry(G, tau, bool(identity))),
                                   bool(accumulate))
 
+    def hota(self, gt_boxes, accumulate=True):
+        """HOTA of the LATEST `track()` against gt_boxes as `score` takes them (air_track_hota; HOTA in the module text; n_ids = F T).
+        Returns device tensors that the next call with the same G overwrites: seq_hota_i [S, 19, 3] int32 (HOTA_COUNTS), seq_hota_f
+        [S, 19, 4] float64 (HOTA_SUMS), hota_potential [S, G, F T] float64, hota_id_count [S, F T], hota_gt_count [S, G],
+        hota_matches [S, 19, G, F T] int32, and the running totals_hota_i [19, 3] int64 / totals_hota_f [19, 4] float64, which this
+        call adds to (accumulate=False: restarts) on the device, with no read-back.  `score` and its cache are not touched.  Same
+        stream contract as `track`."""
+        par = self.provider
+        return self.scores.run_hota(gt_boxes, self.F, lambda G: self.scores.hota_entry(
+            (), G, self.T, self.F, par.boxes, par.num_objects, self.track_id, self.F * self.T), bool(accumulate))
+
+    def hota_summary(self) -> Dict[str, object]:
+        """The HOTA figures of everything `hota` took since the last reset (ONE read-back): hota, deta, assa, detre, detpr, assre,
+        asspr, loca (means over the 19 thresholds), hota0, loca0 (at alpha = 0.05), per_alpha; nan with nothing to score."""
+        return self.scores.hota_summary()
+
     def reset(self):
         """zero the totals"""
         self.scores.reset()
@@ -1176,8 +1434,8 @@ class StreamTracker(BoundStage):
 
     A push MUTATES the state, captured or not: pushing a chunk twice continues the stream with a repeated chunk, it does not repeat the
     call -- `state_dict()` before and `load_state_dict()` after is how a chunk is re-run.  Ids: 0..32766 per sequence until `reset`;
-    a birth beyond is OVERFLOW.  Out of scope on a stream: IDF1 (its overlap table is indexed by global id), more than 32 live tracks.
-    Trajectories: a trajectory.StreamSmoother bound to this tracker (fixed-lag smoothing, `lag` frames late; the forecast at once)."""
+    a birth beyond is OVERFLOW.  Out of scope on a stream: IDF1 and HOTA (their tables are indexed by global id), more than 32
+    live tracks.  Trajectories: a trajectory.StreamSmoother bound to this tracker (fixed-lag smoothing, `lag` frames late; the forecast at once)."""
     ACCEPTS = SequenceTracker.ACCEPTS
     REFUSALS = SequenceTracker.REFUSALS
 

@@ -78,7 +78,7 @@ what the backward pass reads per (table row, frame) and of the provider's rows. 
 frames a .. a + F - 1 and emits from a - L on, and the source of a FILLED row there lies up to max_age frames before it; the reference
 tags every ring entry with its frame and asserts the tag on every read.  The default lag (max_age) is provisional like the noise
 terms.  Out of scope on a stream: smoothed covariances, motion-predicted association and its gate (track.py: MOTION, THE GATE; a stream
-tracker would have to carry each slot's filter state), IDF1.
+tracker would have to carry each slot's filter state), IDF1 and HOTA (their tables are indexed by global id).
 
 NOISE FIT (`TrajectoryNoiseFitter` behind a track.SequenceTracker; air_track_noise_stats, air_track_noise_reduce; `reference_noise_stats`
 restates both in numpy, bit for bit).  The forward filter above computes every innovation e = z - x- and its variance s = Pxx- + r: the
@@ -753,7 +753,7 @@ class TrajectorySmoother(BoundStage):
         self._plan = [e for seg in self.segments.values() for e in seg]
 
     def _score_entries(self):
-        return self._score.values()
+        return list(self._score.values()) + list(self.scores.hota_entries.values())
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `run()` behind the tracker's own (`tracker` holds that tracker's launch_count())"""
@@ -821,6 +821,30 @@ class TrajectorySmoother(BoundStage):
         if self.fc is None:
             raise ValueError("score_forecast needs a horizon >= 1; this smoother was built with horizon=0")
         return self.scores.result(self._run_score("forecast", gt_future_boxes, tau, self.horizon, identity))
+
+    def _hota_entry(self, table, G):
+        t, n_frames = (self.sm, self.F) if table == "completed" else (self.fc, self.horizon)
+        if n_frames * self.C > MAX_IDS:
+            raise ValueError("air_track_hota takes at most %d rows per sequence; %d frames of %d completed rows are %d"
+                             % (MAX_IDS, n_frames, self.C, n_frames * self.C))
+        return self.scores.hota_entry((table,), G, self.C, n_frames, t["boxes"], t["count"], t["id"], self.F * self.window_T)
+
+    def hota(self, gt_boxes, accumulate=True):
+        """SequenceTracker.hota on the COMPLETED table of the latest `run()`: air_track_hota with T := C on sm_boxes, sm_count, sm_id
+        (the ids are the tracker's: n_ids = F T), so a frame a track coasted over and the smoother filled is a detection, no longer a
+        miss.  Returns seq_hota_i, seq_hota_f, hota_potential, hota_id_count, hota_gt_count, hota_matches and this object's own
+        running totals_hota_i / totals_hota_f (accumulate=False: restarts), all on the device."""
+        return self.scores.run_hota(gt_boxes, self.F, lambda G: self._hota_entry("completed", G), bool(accumulate))
+
+    def hota_forecast(self, gt_future_boxes):
+        """the same kernel on the FORECAST table with F := Hz, like `score_forecast`; nothing is accumulated"""
+        if self.fc is None:
+            raise ValueError("hota_forecast needs a horizon >= 1; this smoother was built with horizon=0")
+        return self.scores.run_hota(gt_future_boxes, self.horizon, lambda G: self._hota_entry("forecast", G))
+
+    def hota_summary(self) -> Dict[str, object]:
+        """track.hota_summary of everything `hota` took since the last reset (ONE read-back)"""
+        return self.scores.hota_summary()
 
     def reset(self):
         """zero the totals"""

@@ -1022,6 +1022,30 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *   ids_with_overlap = ids with a nonzero column.  IDFN = gt_frames - idtp, IDFP = hyp_frames - idtp, IDF1 = 2 idtp / (gt_frames +
  *   hyp_frames).  The limits and checks of air_track_score, and 1 <= n_ids <= 32767 (AIR_E_SHAPE).  boxes / gt_boxes 16-byte,
  *   everything else 4-byte aligned (AIR_E_ALIGN).
+ * air_track_hota: the HOTA counts (Luiten et al., IJCV 2021; HOTA = sqrt(DetA AssA) over 19 localisation thresholds), one 256-thread
+ *   workgroup per sequence, both passes over the frames inside.  Inputs as air_track_idf's.  Hypotheses of a frame: the objects j <
+ *   clip(n, 0, T) with track_id >= 0 and a finite box; one whose id is >= n_ids takes no part in any table or matching (its sim is 0, it
+ *   is no row of the matching) and counts as an unmatched hypothesis.  Present slots: gt_boxes[r,g,2] > 0.  sim[g,j] = the float64 box
+ *   IoU of a present slot and a hypothesis that takes part, 0 otherwise.  Everything a float decides is float64 with contraction
+ *   off, only + - * / and floor, in the order written here; no transcendental, no square root.  alpha_k = k / 20.0, k = 1..19; a match
+ *   counts at alpha_k iff sim >= alpha_k (TrackEval subtracts an epsilon there; this rule does not).
+ *   Pass 1, the frames in order: rs[g] = sum_j sim[g,j] in ascending j, cs[j] = sum_g sim[g,j] in ascending g; for every present g and
+ *   hypothesis j, ascending j: d = (cs[j] + rs[g]) - sim[g,j]; if d > 2^-52: pot[g,id_j] += sim[g,j] / d (an id twice in a frame adds
+ *   twice); gc[g] += 1 per present slot; ic[id_j] += 1 per hypothesis.
+ *   Pass 2, the frames in order: (g,j) admissible iff sim[g,j] > 0; A = pot[g,id] / ((gc[g] + ic[id]) - pot[g,id]), the counts widened
+ *   to float64; profit = 1 + (int64) floor((A sim) 2^32).  ONE matching per frame, whatever the threshold: the exact optimal assignment
+ *   of air_track_associate_optimal's solver with its tie rule, rows = the hypotheses in ascending j, columns g < G = the slots, every
+ *   other slot column forbidden (TrackEval gives float scores to a float solver: the scores here are quantised to 2^-32).  For every
+ *   matched (g,j) in ascending g, L = the number of k with sim >= alpha_k; for a < L: tp[a] += 1, loc[a] += sim, matches[a,g,id_j] += 1.
+ *   gt_dets += present slots, hyp_dets += hypotheses (those with an id >= n_ids included).
+ *   The end: fn[a] = gt_dets - tp[a], fp[a] = hyp_dets - tp[a]; with c = matches[a,g,id] over c > 0, the counts widened: ass[a] = sum
+ *   c (c / ((gc[g] + ic[id]) - c)), ass_re[a] = sum c (c / gc[g]), ass_pr[a] = sum c (c / ic[id]): per (a,g) over the ids in ascending
+ *   order, then per a over g in ascending order.
+ *   Outputs, every element written: seq_hota_i[S,19,3] (int32) = {tp, fn, fp}; seq_hota_f[S,19,4] (float64) = {ass, ass_re, ass_pr,
+ *   loc}; potential[S,G,n_ids] (float64) = pot; id_count[S,n_ids] = ic; gt_count[S,G] = gc; matches[S,19,G,n_ids] (int32).  On the
+ *   host per threshold: DetA = tp / max(1, tp + fn + fp), AssA = ass / max(1, tp), LocA = loc / tp, HOTA = sqrt(DetA AssA).
+ *   The limits and checks of air_track_idf, and S 19 G n_ids <= INT_MAX (AIR_E_SHAPE).  boxes / gt_boxes 16-byte, potential /
+ *   seq_hota_f 8-byte, everything else 4-byte aligned (AIR_E_ALIGN).  No floating-point atomics, no traffic between workgroups.
  * Streams.  A stream is S sequences fed in CHUNKS of F frames: a chunk carries valid[s] frames of sequence s, v = clip(valid[s], 0, F);
  *   rows s F + f with f < v are frames, the rows behind them are padding that is never read.  The global index of a frame is
  *   frames_seen[s] + f.  CHUNK INVARIANCE: a sequence fed in any chunking (ragged valid, valid = 0 included) gets the track_id,
@@ -1052,7 +1076,8 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *   sum_iou is CONTINUED from the carried value, so seq_iou has the bits air_track_score gives on the concatenation.  seq_counts[S,8]
  *   and seq_iou[S] are cumulative over the stream (mostly tracked / lost / objects from the cumulative tracked / present);
  *   gt_match[R,G] is the chunk's, -1 on padding rows.  The same valid.
- * Out of scope on a stream: IDF1 (its overlap table is indexed by global id: 1 MB per sequence at 32767 ids), ids beyond 32766
+ * Out of scope on a stream: IDF1 (its overlap table is indexed by global id: 1 MB per sequence at 32767 ids), HOTA (its tables are
+ *   indexed by global id too, 19 thresholds deep), ids beyond 32766
  *   without a reset of the sequence, more than 32 live tracks.  Trajectories on a stream are fixed-lag smoothed, L frames late:
  *   air_track_smooth_stream, below.                                                                                              */
 AIR_ENGINE_API int air_track_associate_stream(const float *what, const float *boxes, const float *score, const int *num_objects, int T,
@@ -1081,6 +1106,9 @@ AIR_ENGINE_API int air_track_associate_motion_gated(const float *what, const flo
                     int *state_counts, float *pred_where, float *pred_boxes, float *pred_d2, void *stream);
 AIR_ENGINE_API int air_track_idf(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, double tau,
                     int T, int G, int S, int F, int R, int n_ids, int *overlap, int *seq_idf, void *stream);
+AIR_ENGINE_API int air_track_hota(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, int T, int G,
+                    int S, int F, int R, int n_ids, double *potential, int *id_count, int *gt_count, int *matches, int *seq_hota_i,
+                    double *seq_hota_f, void *stream);
 AIR_ENGINE_API int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
                     int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
                     int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,

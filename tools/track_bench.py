@@ -44,6 +44,14 @@ air_track_associate_motion_gated) the same way, against the motion tracker WITHO
 agree bit for bit with track.reference_associate_motion(gate=True), pred_d2 included, over the sequences inside the margins; the two
 captured tails are timed in turns (motion, gated, motion, gated) in this process, and the ratio is reported; no bar on time.
 
+--hota measures the HOTA metric instead (SequenceTracker.hota: air_track_hota): for every F in --frames, at --rows provider rows, ONE
+captured SceneParser and a captured tracker (--matching) over it; ground truth cut from the parse's own boxes, every fifth frame
+shifted by 1.5 px so that the thresholds part.  The device outputs of the first --hota-check sequences must equal
+track.reference_hota bit for bit, or the tool exits with an error.  Then the three captured graphs -- air_track_score, air_track_score
++ air_track_idf, air_track_hota -- are timed in turns in this process, and the three entries launched eagerly, in turns as well (5
+repeats of --iters back-to-back launches between two device events) and one launch at a time as the other modes time it; the ratios
+are reported; no bar on time.
+
 Timing: a warm-up, then 5 repeats of --iters calls each between device events; the median repeat is reported with all repeats.  The
 provider and the tracked route alternate inside one process."""
 import argparse
@@ -384,6 +392,86 @@ def one_motion_length(args, F, gate=False):
     return res
 
 
+def one_hota_length(args, F):
+    """--hota: air_track_hota beside air_track_score and air_track_idf on the tracks of one captured tracker"""
+    from attend_infer_repeat_amd import _lib, track
+    from attend_infer_repeat_amd.engine_config import EngineConfig
+    from attend_infer_repeat_amd.parse import SceneParser
+    cfg = EngineConfig()
+    R = args.rows
+    if R % F:
+        raise SystemExit("--rows %d is no multiple of %d frames" % (R, F))
+    S, T, G = R // F, int(cfg.max_steps), 3
+    ps = SceneParser(cfg, R, seed=0)
+    ps.capture()
+    tk = track.SequenceTracker(ps, F, birth_score=0.0, matching=args.matching)
+    tk.capture()
+    eng, dev = ps.engine, ps.engine.device
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    start = torch.rand(S, *cfg.img_size, generator=gen) * (torch.rand(S, *cfg.img_size, generator=gen) > 0.8)
+    frames = torch.stack([torch.roll(start, shifts=(f, f // 2), dims=(1, 2)) for f in range(F)], 1).contiguous().to(dev)
+    counts = (torch.arange(R, device=dev) % (T + 1)).to(torch.int32)
+    out = tk.track(frames, counts)
+    torch.cuda.synchronize()
+    host = lambda t: t.cpu().numpy()
+    boxes, n, ids = host(out["boxes"]), host(out["num_objects"]), host(out["track_id"])
+    gt = np.zeros((R, G, 4), np.float32)
+    for g in range(G):
+        gt[n > g, g] = boxes[g, n > g]
+    gt[::5] += np.float32(1.5)                                     # (every fifth frame off its box: the thresholds have work)
+    gt_dev = torch.from_numpy(gt).to(dev)
+    got = tk.hota(gt_dev, accumulate=False)
+    torch.cuda.synchronize()
+    n_seq = min(S, args.hota_check)                                # the host reference walks these sequences
+    want = track.reference_hota(boxes[:, :n_seq * F], n[:n_seq * F], ids[:, :n_seq * F], gt[:n_seq * F], F, F * T)
+    same = lambda a, b: bool((np.ascontiguousarray(a).view(np.uint8) == np.ascontiguousarray(b).view(np.uint8)).all())
+    keys = ("seq_hota_i", "seq_hota_f", "hota_potential", "hota_id_count", "hota_gt_count", "hota_matches")
+    agree = {k: same(host(got[k])[:n_seq], want[k]) for k in keys}
+    fig = tk.hota_summary()
+    res = dict(frames=F, sequences=S, rows=R, max_steps=T, gt_slots=G, n_ids=F * T, matching=args.matching, sequences_checked=n_seq,
+               agreement=agree, hota_summary={k: v for k, v in fig.items() if k != "per_alpha"})
+    if not all(agree.values()):
+        print(json.dumps(res))
+        raise SystemExit("air_track_hota and the host reference disagree: %r" % (agree,))
+    tk.score(gt_dev, accumulate=False)
+    tk.score(gt_dev, accumulate=False, identity=True)
+    res["score_summary"], res["identity_summary"] = tk.summary(), tk.identity_summary()
+    graphs = {"score": tk._score[(G, 0.5)], "score_idf": tk._score[(G, 0.5, "idf")], "hota": tk.scores.hota_entries[(G,)]}
+    turns = {k: [] for k in graphs}
+    for _ in range(2):                                             # in turns, in this process
+        for name, e in graphs.items():
+            turns[name].append(median_ms(lambda: eng._replay_or_run(e["graph"], e["plan"]), args.iters, eng.stream))
+    for name, v in turns.items():
+        res["%s_graph_turns_ms" % name] = [m for m, _ in v]
+        res["%s_graph_repeats_ms" % name] = [r for _, r in v]
+        res["%s_graph_ms" % name] = statistics.median(res["%s_graph_turns_ms" % name])
+    res["hota_over_score_graph"] = res["hota_graph_ms"] / res["score_graph_ms"]
+    res["hota_over_score_idf_graph"] = res["hota_graph_ms"] / res["score_idf_graph_ms"]
+    plan = graphs["score_idf"]["plan"] + graphs["hota"]["plan"]    # air_track_score, air_track_idf, air_track_hota
+    launch = lambda fn, a, name: _lib.check(fn(*a, eng._sp()), name)
+    eager = {name: [] for _, _, name in plan}
+    for _ in range(2):
+        for fn, a, name in plan:
+            eager[name].append(median_ms(lambda: launch(fn, a, name), args.iters, eng.stream))
+    res["eager_launch_us"] = {k: statistics.median([m for m, _ in v]) * 1e3 for k, v in eager.items()}
+    res["eager_launch_turns_us"] = {k: [m * 1e3 for m, _ in v] for k, v in eager.items()}
+    per = {}
+    for _ in range(7):                                             # and one launch at a time between two events, as the other modes time it
+        for fn, a, name in plan:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(eng.stream)
+            launch(fn, a, name)
+            e1.record(eng.stream)
+            e1.synchronize()
+            per.setdefault(name, []).append(e0.elapsed_time(e1) * 1e3)
+    res["eager_single_launch_us"] = {k: statistics.median(v) for k, v in per.items()}
+    us = res["eager_launch_us"]
+    res["hota_over_score_eager"] = us["air_track_hota"] / us["air_track_score"]
+    res["hota_over_score_plus_idf_eager"] = us["air_track_hota"] / (us["air_track_score"] + us["air_track_idf"])
+    tk.release_graphs(); ps.release_graphs()
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 32])
@@ -395,9 +483,18 @@ def main(argv=None):
     ap.add_argument("--stream-chunks", type=int, default=4)
     ap.add_argument("--motion", action="store_true")
     ap.add_argument("--gate", action="store_true", help="with --motion: the Mahalanobis gate against the motion tracker without it")
+    ap.add_argument("--hota", action="store_true", help="air_track_hota beside air_track_score and air_track_idf (eager and captured)")
+    ap.add_argument("--hota-check", type=int, default=16, metavar="N", help="with --hota: the sequences the host reference walks")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("track_bench measures on the GPU; there is no CPU fallback")
+    if args.hota:
+        res = dict(tool="track_bench --hota", device=torch.cuda.get_device_name(0), lengths=[one_hota_length(args, F) for F in args.frames])
+        print(json.dumps(res))
+        for r in res["lengths"]:
+            for k, v in r.items():
+                print("F=%-4d %-34s %s" % (r["frames"], k, v))
+        return res
     if args.stream is not None:
         res = dict(tool="track_bench --stream", device=torch.cuda.get_device_name(0), chunks=[one_chunk_size(args, C) for C in args.stream])
         print(json.dumps(res))
