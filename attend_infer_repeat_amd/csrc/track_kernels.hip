@@ -636,52 +636,81 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_associate_kernel(
     if (tid < 6) a.state_counts[(size_t)s * 6 + tid] = counts_s[tid];
 }
 
-// the checks and the launch of both association entries
-static int track_associate_launch(bool optimal, const float *what, const float *boxes, const float *score, const int *num_objects, int T,
-                                  int S, int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
-                                  int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
-                                  int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
-                                  int *state_counts, void *stream, const TrackMotionArgs *motion = nullptr,
-                                  const TrackGateArgs *gated = nullptr) {
-    AIR_REQUIRE(what && boxes && score && num_objects && track_id && obj_state && affinity && prev_frame && prev_slot && num_tracks &&
-                track_first && track_last && track_length && track_gaps && state_counts, AIR_E_NULL);
-    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && S > 0 && F > 0 && A > 0, AIR_E_SHAPE);
-    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
-    AIR_REQUIRE(iou_gate >= 0.0 && iou_gate < 1.0 && appearance_weight >= 0.0 && appearance_weight <= 1.0, AIR_E_SHAPE);
-    AIR_REQUIRE(birth_score >= 0.0 && birth_score <= 1.0 && max_age >= 0, AIR_E_SHAPE);
-    AIR_REQUIRE(air_aligned16(boxes), AIR_E_ALIGN);
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(what) | reinterpret_cast<uintptr_t>(score) | reinterpret_cast<uintptr_t>(num_objects) |
-                           reinterpret_cast<uintptr_t>(track_id) | reinterpret_cast<uintptr_t>(affinity) |
-                           reinterpret_cast<uintptr_t>(prev_frame) | reinterpret_cast<uintptr_t>(prev_slot) |
-                           reinterpret_cast<uintptr_t>(num_tracks) | reinterpret_cast<uintptr_t>(track_first) |
-                           reinterpret_cast<uintptr_t>(track_last) | reinterpret_cast<uintptr_t>(track_length) |
-                           reinterpret_cast<uintptr_t>(track_gaps) | reinterpret_cast<uintptr_t>(state_counts);
-    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
-    const TrackAssocArgs a = {what, boxes, score, num_objects, track_id, prev_frame, prev_slot, num_tracks, track_first, track_last,
-                              track_length, track_gaps, state_counts, affinity, obj_state, iou_gate, appearance_weight, birth_score,
-                              T, S, F, A, max_age};
-    if (gated) {                                                   // (its own fields were checked by the entry)
-        TrackGateArgs g = *gated;
-        static_cast<TrackAssocArgs &>(g) = a;
-        if (optimal)
-            hipLaunchKernelGGL((track_associate_kernel<true, false, true, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0,
-                               air_stream(stream), g);
-        else
-            hipLaunchKernelGGL((track_associate_kernel<false, false, true, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0,
-                               air_stream(stream), g);
-    } else if (motion) {                                           // (its own fields were checked by the entry)
-        TrackMotionArgs m = *motion;
-        static_cast<TrackAssocArgs &>(m) = a;
-        if (optimal)
-            hipLaunchKernelGGL((track_associate_kernel<true, false, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), m);
-        else
-            hipLaunchKernelGGL((track_associate_kernel<false, false, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), m);
-    } else if (optimal) {
-        hipLaunchKernelGGL(track_associate_kernel<true>, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
-    } else {
-        hipLaunchKernelGGL(track_associate_kernel<false>, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+// ---- the host side of the association entries ------------------------------------------------------------------------------------
+// the arguments every entry has, from the prototypes' order into the kernel's struct (a stream has no per-id tables: nullptr)
+static TrackAssocArgs track_assoc_args(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
+                                       int F, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
+                                       int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
+                                       int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
+                                       int *state_counts) {
+    return {what, boxes, score, num_objects, track_id, prev_frame, prev_slot, num_tracks, track_first, track_last, track_length,
+            track_gaps, state_counts, affinity, obj_state, iou_gate, appearance_weight, birth_score, T, S, F, A, max_age};
+}
+
+static bool track_aligned4(std::initializer_list<const void *> pointers) {
+    uintptr_t bits = 0;
+    for (const void *q : pointers) bits |= reinterpret_cast<uintptr_t>(q);
+    return (bits & 3u) == 0;
+}
+
+// The checks every entry makes of those arguments, one status after the other: NULL, SHAPE, ALIGN.  `st`: a chunk of a stream, which
+// has its state and retired lists where a one-shot call has the per-id tables, and `matching` as an argument; its own checks stand
+// where the stream entry has always made them, so an input with several faults returns the status it always returned.
+static int track_associate_check(const TrackAssocArgs &a, int R, const TrackStreamArgs *st = nullptr, int matching = 0) {
+    AIR_REQUIRE(a.what && a.boxes && a.score && a.num_objects && a.track_id && a.obj_state && a.affinity && a.prev_frame &&
+                a.prev_slot && a.state_counts, AIR_E_NULL);
+    AIR_REQUIRE(st ? st->valid && st->st_seq && st->st_slots && st->st_box && st->st_what && st->num_retired && st->retired_id &&
+                     st->retired_first && st->retired_last && st->retired_length && st->retired_gaps
+                   : a.num_tracks && a.track_first && a.track_last && a.track_length && a.track_gaps, AIR_E_NULL);
+    AIR_REQUIRE(a.T >= 1 && a.T <= TRACK_MAXT && a.S > 0 && a.F > 0 && a.A > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)a.F * a.T <= TRACK_MAX_IDS && (long)a.S * a.F == (long)R && (long)a.S * a.F * a.T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(a.iou_gate >= 0.0 && a.iou_gate < 1.0 && a.w >= 0.0 && a.w <= 1.0, AIR_E_SHAPE);
+    AIR_REQUIRE(a.birth_score >= 0.0 && a.birth_score <= 1.0 && a.max_age >= 0, AIR_E_SHAPE);
+    if (st) {
+        AIR_REQUIRE(matching == 0 || matching == 1, AIR_E_SHAPE);
+        AIR_REQUIRE((long)a.S * TRACK_MAXT * a.A <= (long)INT_MAX, AIR_E_SHAPE);
     }
+    AIR_REQUIRE(air_aligned16(a.boxes) && (!st || air_aligned16(st->st_box)), AIR_E_ALIGN);
+    AIR_REQUIRE(track_aligned4({a.what, a.score, a.num_objects, a.track_id, a.affinity, a.prev_frame, a.prev_slot, a.num_tracks,
+                                a.track_first, a.track_last, a.track_length, a.track_gaps, a.state_counts}), AIR_E_ALIGN);
+    if (st)
+        AIR_REQUIRE(track_aligned4({st->valid, st->st_seq, st->st_slots, st->st_what, st->num_retired, st->retired_id, st->retired_first,
+                                    st->retired_last, st->retired_length, st->retired_gaps}), AIR_E_ALIGN);
+    return AIR_OK;
+}
+
+// the checks and the one dispatch: the kernel's template flags are the kind of its argument struct and the matching
+template <class Args>
+static int track_associate_launch(bool optimal, const Args &a, int R, void *stream, const TrackStreamArgs *st = nullptr, int matching = 0) {
+    constexpr bool STREAM = std::is_same_v<Args, TrackStreamArgs>, MOTION = std::is_base_of_v<TrackMotionArgs, Args>,
+                   GATED = std::is_same_v<Args, TrackGateArgs>;
+    const int status = track_associate_check(a, R, st, matching);
+    if (status != AIR_OK) return status;
+    if (optimal)
+        hipLaunchKernelGGL((track_associate_kernel<true, STREAM, MOTION, GATED>), dim3((unsigned)a.S), dim3(TRACK_THREADS), 0,
+                           air_stream(stream), a);
+    else
+        hipLaunchKernelGGL((track_associate_kernel<false, STREAM, MOTION, GATED>), dim3((unsigned)a.S), dim3(TRACK_THREADS), 0,
+                           air_stream(stream), a);
     AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// The motion entries' own checks and fields, into m.  `pred_d2`: the gated entry's, whose two checks stand where that entry has always
+// made them (its gate_d2 and pred_d2 fields are the caller's to set).
+static int track_motion_args(TrackMotionArgs &m, const float *where, int H, int W, int matching, double q_shift, double q_scale,
+                             double measurement_noise, double velocity_var, float *pred_where, float *pred_boxes, bool gated = false,
+                             double gate_d2 = 0.0, const float *pred_d2 = nullptr) {
+    AIR_REQUIRE(where && pred_where && pred_boxes && (!gated || pred_d2), AIR_E_NULL);
+    AIR_REQUIRE(matching == 0 || matching == 1, AIR_E_SHAPE);
+    AIR_REQUIRE(H >= 1 && W >= 1, AIR_E_SHAPE);
+    AIR_REQUIRE(traj_noise_check(q_shift, q_scale, measurement_noise, velocity_var) == AIR_OK, AIR_E_SHAPE);
+    AIR_REQUIRE(!gated || (isfinite(gate_d2) && gate_d2 > 0.0), AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(where) && air_aligned16(pred_where) && air_aligned16(pred_boxes), AIR_E_ALIGN);
+    AIR_REQUIRE(track_aligned4({pred_d2}), AIR_E_ALIGN);
+    m.where = where, m.pred_where = pred_where, m.pred_boxes = pred_boxes;
+    m.q[0] = q_shift, m.q[1] = q_scale, m.r = measurement_noise, m.velocity_var = velocity_var;
+    m.Wf = (float)W, m.Hf = (float)H;
     return AIR_OK;
 }
 
@@ -690,9 +719,10 @@ extern "C" int air_track_associate(const float *what, const float *boxes, const 
                                    int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
                                    int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
                                    int *state_counts, void *stream) {
-    return track_associate_launch(false, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score, max_age,
-                                  track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last, track_length,
-                                  track_gaps, state_counts, stream);
+    return track_associate_launch(false, track_assoc_args(what, boxes, score, num_objects, T, S, F, A, iou_gate, appearance_weight,
+                                                          birth_score, max_age, track_id, obj_state, affinity, prev_frame, prev_slot,
+                                                          num_tracks, track_first, track_last, track_length, track_gaps, state_counts),
+                                  R, stream);
 }
 
 extern "C" int air_track_associate_optimal(const float *what, const float *boxes, const float *score, const int *num_objects, int T,
@@ -700,9 +730,10 @@ extern "C" int air_track_associate_optimal(const float *what, const float *boxes
                                            int max_age, int *track_id, signed char *obj_state, float *affinity, int *prev_frame,
                                            int *prev_slot, int *num_tracks, int *track_first, int *track_last, int *track_length,
                                            int *track_gaps, int *state_counts, void *stream) {
-    return track_associate_launch(true, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score, max_age,
-                                  track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last, track_length,
-                                  track_gaps, state_counts, stream);
+    return track_associate_launch(true, track_assoc_args(what, boxes, score, num_objects, T, S, F, A, iou_gate, appearance_weight,
+                                                         birth_score, max_age, track_id, obj_state, affinity, prev_frame, prev_slot,
+                                                         num_tracks, track_first, track_last, track_length, track_gaps, state_counts),
+                                  R, stream);
 }
 
 extern "C" int air_track_associate_motion(const float *what, const float *where, const float *boxes, const float *score,
@@ -712,18 +743,13 @@ extern "C" int air_track_associate_motion(const float *what, const float *where,
                                           signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,
                                           int *track_first, int *track_last, int *track_length, int *track_gaps, int *state_counts,
                                           float *pred_where, float *pred_boxes, void *stream) {
-    AIR_REQUIRE(where && pred_where && pred_boxes, AIR_E_NULL);
-    AIR_REQUIRE(matching == 0 || matching == 1, AIR_E_SHAPE);
-    AIR_REQUIRE(H >= 1 && W >= 1, AIR_E_SHAPE);
-    AIR_REQUIRE(traj_noise_check(q_shift, q_scale, measurement_noise, velocity_var) == AIR_OK, AIR_E_SHAPE);
-    AIR_REQUIRE(air_aligned16(where) && air_aligned16(pred_where) && air_aligned16(pred_boxes), AIR_E_ALIGN);
     TrackMotionArgs m = {};
-    m.where = where, m.pred_where = pred_where, m.pred_boxes = pred_boxes;
-    m.q[0] = q_shift, m.q[1] = q_scale, m.r = measurement_noise, m.velocity_var = velocity_var;
-    m.Wf = (float)W, m.Hf = (float)H;
-    return track_associate_launch(matching == 1, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score,
-                                  max_age, track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last,
-                                  track_length, track_gaps, state_counts, stream, &m);
+    const int status = track_motion_args(m, where, H, W, matching, q_shift, q_scale, measurement_noise, velocity_var, pred_where, pred_boxes);
+    if (status != AIR_OK) return status;
+    static_cast<TrackAssocArgs &>(m) = track_assoc_args(what, boxes, score, num_objects, T, S, F, A, iou_gate, appearance_weight, birth_score,
+                                                        max_age, track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks,
+                                                        track_first, track_last, track_length, track_gaps, state_counts);
+    return track_associate_launch(matching == 1, m, R, stream);
 }
 
 extern "C" int air_track_associate_motion_gated(const float *what, const float *where, const float *boxes, const float *score,
@@ -733,21 +759,15 @@ extern "C" int air_track_associate_motion_gated(const float *what, const float *
                                                 int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot,
                                                 int *num_tracks, int *track_first, int *track_last, int *track_length, int *track_gaps,
                                                 int *state_counts, float *pred_where, float *pred_boxes, float *pred_d2, void *stream) {
-    AIR_REQUIRE(where && pred_where && pred_boxes && pred_d2, AIR_E_NULL);
-    AIR_REQUIRE(matching == 0 || matching == 1, AIR_E_SHAPE);
-    AIR_REQUIRE(H >= 1 && W >= 1, AIR_E_SHAPE);
-    AIR_REQUIRE(traj_noise_check(q_shift, q_scale, measurement_noise, velocity_var) == AIR_OK, AIR_E_SHAPE);
-    AIR_REQUIRE(isfinite(gate_d2) && gate_d2 > 0.0, AIR_E_SHAPE);
-    AIR_REQUIRE(air_aligned16(where) && air_aligned16(pred_where) && air_aligned16(pred_boxes), AIR_E_ALIGN);
-    AIR_REQUIRE((reinterpret_cast<uintptr_t>(pred_d2) & 3u) == 0, AIR_E_ALIGN);
     TrackGateArgs g = {};
-    g.where = where, g.pred_where = pred_where, g.pred_boxes = pred_boxes;
-    g.q[0] = q_shift, g.q[1] = q_scale, g.r = measurement_noise, g.velocity_var = velocity_var;
-    g.Wf = (float)W, g.Hf = (float)H;
+    const int status = track_motion_args(g, where, H, W, matching, q_shift, q_scale, measurement_noise, velocity_var, pred_where, pred_boxes,
+                                         true, gate_d2, pred_d2);
+    if (status != AIR_OK) return status;
     g.gate_d2 = gate_d2, g.pred_d2 = pred_d2;
-    return track_associate_launch(matching == 1, what, boxes, score, num_objects, T, S, F, R, A, iou_gate, appearance_weight, birth_score,
-                                  max_age, track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks, track_first, track_last,
-                                  track_length, track_gaps, state_counts, stream, nullptr, &g);
+    static_cast<TrackAssocArgs &>(g) = track_assoc_args(what, boxes, score, num_objects, T, S, F, A, iou_gate, appearance_weight, birth_score,
+                                                        max_age, track_id, obj_state, affinity, prev_frame, prev_slot, num_tracks,
+                                                        track_first, track_last, track_length, track_gaps, state_counts);
+    return track_associate_launch(matching == 1, g, R, stream);
 }
 
 extern "C" int air_track_associate_stream(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
@@ -756,37 +776,14 @@ extern "C" int air_track_associate_stream(const float *what, const float *boxes,
                                           float *st_what, int *track_id, signed char *obj_state, float *affinity, int *prev_frame,
                                           int *prev_slot, int *state_counts, int *num_retired, int *retired_id, int *retired_first,
                                           int *retired_last, int *retired_length, int *retired_gaps, void *stream) {
-    AIR_REQUIRE(what && boxes && score && num_objects && valid && st_seq && st_slots && st_box && st_what && track_id && obj_state &&
-                affinity && prev_frame && prev_slot && state_counts && num_retired && retired_id && retired_first && retired_last &&
-                retired_length && retired_gaps, AIR_E_NULL);
-    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && S > 0 && F > 0 && A > 0, AIR_E_SHAPE);
-    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
-    AIR_REQUIRE(iou_gate >= 0.0 && iou_gate < 1.0 && appearance_weight >= 0.0 && appearance_weight <= 1.0, AIR_E_SHAPE);
-    AIR_REQUIRE(birth_score >= 0.0 && birth_score <= 1.0 && max_age >= 0, AIR_E_SHAPE);
-    AIR_REQUIRE(matching == 0 || matching == 1, AIR_E_SHAPE);
-    AIR_REQUIRE((long)S * TRACK_MAXT * A <= (long)INT_MAX, AIR_E_SHAPE);
-    AIR_REQUIRE(air_aligned16(boxes) && air_aligned16(st_box), AIR_E_ALIGN);
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(what) | reinterpret_cast<uintptr_t>(score) | reinterpret_cast<uintptr_t>(num_objects) |
-                           reinterpret_cast<uintptr_t>(valid) | reinterpret_cast<uintptr_t>(st_seq) | reinterpret_cast<uintptr_t>(st_slots) |
-                           reinterpret_cast<uintptr_t>(st_what) | reinterpret_cast<uintptr_t>(track_id) |
-                           reinterpret_cast<uintptr_t>(affinity) | reinterpret_cast<uintptr_t>(prev_frame) |
-                           reinterpret_cast<uintptr_t>(prev_slot) | reinterpret_cast<uintptr_t>(state_counts) |
-                           reinterpret_cast<uintptr_t>(num_retired) | reinterpret_cast<uintptr_t>(retired_id) |
-                           reinterpret_cast<uintptr_t>(retired_first) | reinterpret_cast<uintptr_t>(retired_last) |
-                           reinterpret_cast<uintptr_t>(retired_length) | reinterpret_cast<uintptr_t>(retired_gaps);
-    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
     TrackStreamArgs a;
-    static_cast<TrackAssocArgs &>(a) = {what, boxes, score, num_objects, track_id, prev_frame, prev_slot, nullptr, nullptr, nullptr,
-                                        nullptr, nullptr, state_counts, affinity, obj_state, iou_gate, appearance_weight, birth_score,
-                                        T, S, F, A, max_age};
+    static_cast<TrackAssocArgs &>(a) = track_assoc_args(what, boxes, score, num_objects, T, S, F, A, iou_gate, appearance_weight, birth_score,
+                                                        max_age, track_id, obj_state, affinity, prev_frame, prev_slot, nullptr, nullptr,
+                                                        nullptr, nullptr, nullptr, state_counts);
     a.valid = valid, a.st_seq = st_seq, a.st_slots = st_slots, a.st_box = st_box, a.st_what = st_what, a.num_retired = num_retired;
     a.retired_id = retired_id, a.retired_first = retired_first, a.retired_last = retired_last, a.retired_length = retired_length;
     a.retired_gaps = retired_gaps;
-    if (matching == 1)
-        hipLaunchKernelGGL((track_associate_kernel<true, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
-    else hipLaunchKernelGGL((track_associate_kernel<false, true>), dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
-    AIR_LAUNCH_CHECK();
-    return AIR_OK;
+    return track_associate_launch(matching == 1, a, R, stream, &a, matching);
 }
 
 // ============================================================================================================

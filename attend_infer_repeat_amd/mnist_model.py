@@ -451,27 +451,29 @@ class AIRonMNIST(AIRModel):
         self.parse_scores_tiled = s.score(gt_instances, gt_boxes, gt_count, accumulate=accumulate)
         return self.parse_scores_tiled, s
 
-    def tracker(self, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-                refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None, motion_gate=None):
-        """the track.SequenceTracker behind `track` (`_tracker_entry` describes the cache; with smooth= the tracker of the stack that
-        ends in the trajectory.TrajectorySmoother `trajectory_smoother` returns)"""
-        return self._tracker_entry(self._track_key(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine,
-                                                   refine_lr, prune, propose, temporal, smooth, matching, motion, motion_gate))[0]
+    def tracker(self, n_sequences, n_frames, **track_args):
+        """the track.SequenceTracker behind `track` (`track_args` are `track`'s; `_tracker_entry` describes the cache; with smooth= the
+        tracker of the stack that ends in the trajectory.TrajectorySmoother `trajectory_smoother` returns)"""
+        return self._tracker_entry(self._track_key(n_sequences, n_frames, **track_args))[0]
 
-    def trajectory_smoother(self, n_sequences, n_frames, smooth=True, iou_gate=None, appearance_weight=None, birth_score=None,
-                            max_age=None, refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None,
-                            motion=None, motion_gate=None):
+    def trajectory_smoother(self, n_sequences, n_frames, smooth=True, **track_args):
         """the trajectory.TrajectorySmoother behind `track(smooth=)` and `predict_frames`: last in the cached stack of
         `tracker(..., smooth=smooth)`, bound to that stack's tracker (smoothed, gap-filled and extrapolated tracks; its defaults are
         provisional)"""
         if stacks.smooth_spec(smooth) is None:
             raise ValueError("trajectory_smoother: smooth must be True or a dict of TrajectorySmoother's arguments, got %r" % (smooth,))
-        return self._tracker_entry(self._track_key(n_sequences, n_frames, iou_gate, appearance_weight, birth_score, max_age, refine,
-                                                   refine_lr, prune, propose, temporal, smooth, matching, motion, motion_gate))[1]
+        return self._tracker_entry(self._track_key(n_sequences, n_frames, smooth=smooth, **track_args))[1]
 
-    def _track_key(self, n_sequences, n_frames, *args):
-        """the stacks.TrackKey of the track family's arguments (`args`: iou_gate ... motion_gate, in the order of `tracker`)"""
-        return stacks.track_key(stacks.require_engine(self, "track"), n_sequences, n_frames, *args)
+    def _track_key(self, n_sequences, n_frames, **track_args):
+        """the stacks.TrackKey of the track family's arguments (stacks.track_key names them: an unknown one is its TypeError)"""
+        return stacks.track_key(stacks.require_engine(self, "track"), n_sequences, n_frames, **track_args)
+
+    def _track_stack(self, key):
+        """the built and captured stack of a key of the track family (stacks.build_track_stack over a provider stack of its own at
+        key.S * key.F rows), from the one cache of the family: the least recently used stack is dropped when more than MAX_TRACKERS
+        are alive (each owns an engine)"""
+        return self._cache("trackers").get(key, lambda: stacks.captured(
+            stacks.build_track_stack(self._own_stack(key.S * key.F, key.stack, key.F), key)))
 
     def _tracker_entry(self, key):
         """(tracker, smoother | None) for the stacks.TrackKey `key` -- those of the cached stack whose track.SequenceTracker is behind
@@ -488,34 +490,15 @@ class AIRonMNIST(AIRModel):
         argument; True | a squared Mahalanobis distance a tracker of its own whose pairs are gated by the filter's covariance (track.py:
         THE GATE; part of the key; it needs motion).  Built and captured on first use; the least
         recently used one is dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
-        def build():
-            from .track import SequenceTracker
-            stack = self._own_stack(key.S * key.F, key.stack, key.F)
-            stack.append(SequenceTracker(stack[-1], key.F, matching=key.matching, motion=key.motion and dict(key.motion),
-                                         motion_gate=key.motion_gate, **dict(key.assoc)))
-            if key.smooth is not None:
-                from .trajectory import TrajectorySmoother
-                stack.append(TrajectorySmoother(stack[-1], **dict(key.smooth)))
-            return stacks.captured(stack)
-        stack = self._cache("trackers").get(key, build)
+        stack = self._track_stack(key)
         return (stack[-1], None) if key.smooth is None else (stack[-2], stack[-1])
 
     def noise_fitter(self, n_sequences, n_frames, shift_ratios=None, scale_ratios=None, velocity_ratio=None, **track_args):
         """the trajectory.TrajectoryNoiseFitter behind `fit_track_noise`: last in a cached stack of its own (stacks.fit_key, in the
         cache of `tracker`: it counts against MAX_TRACKERS) whose track.SequenceTracker it is bound to; `track_args` are `tracker`'s
         without smooth=.  Built and captured on first use."""
-        key = stacks.fit_key(stacks.require_engine(self, "fit_track_noise"), n_sequences, n_frames, shift_ratios, scale_ratios,
-                             velocity_ratio, **track_args)
-
-        def build():
-            from .track import SequenceTracker
-            from .trajectory import TrajectoryNoiseFitter
-            stack = self._own_stack(key.S * key.F, key.stack, key.F)
-            stack.append(SequenceTracker(stack[-1], key.F, matching=key.matching, motion=key.motion and dict(key.motion),
-                                         motion_gate=key.motion_gate, **dict(key.assoc)))
-            stack.append(TrajectoryNoiseFitter(stack[-1], *key.fit))
-            return stacks.captured(stack)
-        return self._cache("trackers").get(key, build)[-1]
+        return self._track_stack(stacks.fit_key(stacks.require_engine(self, "fit_track_noise"), n_sequences, n_frames, shift_ratios,
+                                                scale_ratios, velocity_ratio, **track_args))[-1]
 
     def fit_track_noise(self, frames, shift_ratios=None, scale_ratios=None, velocity_ratio=None, zoom=0, accumulate=False, fit=True,
                         **track_args):
@@ -540,9 +523,7 @@ class AIRonMNIST(AIRModel):
         self.track_noise_fit = f.fit(zoom) if fit else None
         return self.track_noise_fit
 
-    def stream_tracker(self, n_sequences, chunk_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None,
-                       refine=None, refine_lr=None, prune=None, propose=None, temporal=None, matching=None, motion=None,
-                       motion_gate=None):
+    def stream_tracker(self, n_sequences, chunk_frames, **stream_args):
         """the track.StreamTracker behind `track_stream`: identities over sequences of any length, fed in chunks of `chunk_frames`
         frames, the track table carried on the device between the calls (motion= and motion_gate= are refused: out of scope on a stream,
         track.MOTION_ON_A_STREAM).  One per (n_sequences, chunk_frames, the association
@@ -550,15 +531,8 @@ class AIRonMNIST(AIRModel):
         `tracker` -- it counts against MAX_TRACKERS with the one-shot trackers -- over a provider stack of its own at n_sequences *
         chunk_frames rows, so the parsers of `parse` and `self.obs` are never touched (a temporal proposer sees only its chunk).  Built
         and captured on first use.  Dropped from the cache, its stream is lost with it."""
-        key = stacks.stream_key(stacks.require_engine(self, "track_stream"), n_sequences, chunk_frames, iou_gate, appearance_weight,
-                                birth_score, max_age, refine, refine_lr, prune, propose, temporal, matching, motion, motion_gate)
-
-        def build():
-            from .track import StreamTracker
-            stack = self._own_stack(key.S * key.F, key.stack, key.F)
-            stack.append(StreamTracker(stack[-1], key.F, matching=key.matching, **dict(key.assoc)))
-            return stacks.captured(stack)
-        return self._cache("trackers").get(key, build)[-1]
+        return self._track_stack(stacks.stream_key(stacks.require_engine(self, "track_stream"), n_sequences, chunk_frames,
+                                                   **stream_args))[-1]
 
     def stream_smoother(self, n_sequences, chunk_frames, smooth=True, **stream_args):
         """the trajectory.StreamSmoother behind `track_stream(smooth=)`: fixed-lag smoothed, gap-filled rows `lag` frames late and a
@@ -566,16 +540,8 @@ class AIRonMNIST(AIRModel):
         max_age; the defaults are provisional); `stream_args` are `stream_tracker`'s.  Last in a cached stack of its own
         (stacks.stream_smoother_key) whose StreamTracker it is bound to: another stream than that of `stream_tracker` with the same
         arguments.  Built and captured on first use; counts against MAX_TRACKERS."""
-        key = stacks.stream_smoother_key(stacks.require_engine(self, "track_stream"), n_sequences, chunk_frames, smooth, **stream_args)
-
-        def build():
-            from .track import StreamTracker
-            from .trajectory import StreamSmoother
-            stack = self._own_stack(key.S * key.F, key.stack, key.F)
-            stack.append(StreamTracker(stack[-1], key.F, matching=key.matching, **dict(key.assoc)))
-            stack.append(StreamSmoother(stack[-1], **dict(key.smooth)))
-            return stacks.captured(stack)
-        return self._cache("trackers").get(key, build)[-1]
+        return self._track_stack(stacks.stream_smoother_key(stacks.require_engine(self, "track_stream"), n_sequences, chunk_frames, smooth,
+                                                            **stream_args))[-1]
 
     def track_stream(self, frames, valid=None, reset=False, smooth=None, **stream_args):
         """The next chunk of a stream: frames [S, F, H, W] parsed as `track` parses them and associated with the tracks of the chunks
@@ -615,12 +581,12 @@ class AIRonMNIST(AIRModel):
         return self._cache("temporal_proposers").get((S, F, spec, str(eng.device)),
                                                      lambda: stacks.captured(self._own_stack(S * F, spec, F)))[-1]
 
-    def _track(self, frames, *args):
-        """`track` (`args`: iou_gate ... motion_gate, in its order); returns the (tracker, smoother | None) that ran"""
+    def _track(self, frames, **track_args):
+        """`track` with its arguments by name; returns the (tracker, smoother | None) that ran"""
         frames = torch.as_tensor(frames)
         if frames.dim() != 4:
             raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
-        tracker, smoother = self._tracker_entry(self._track_key(frames.shape[0], frames.shape[1], *args))
+        tracker, smoother = self._tracker_entry(self._track_key(frames.shape[0], frames.shape[1], **track_args))
         last = tracker if smoother is None else smoother
         self._sync_engine_switches()
         last.load_from(self._engine)                         # every time: the weights move
@@ -646,8 +612,9 @@ class AIRonMNIST(AIRModel):
         state, D2 at most (True: track.MOTION_GATE_DEFAULT, provisional), and ranked by it instead of the IoU -- the fitted noise terms
         and the gate then concern one quantity; pred_d2 comes on top; motion_gate=None is exactly the call without it.  The training
         engine's parameters are read, nothing of it is written; `self.obs` and the parsers of `parse` are not touched."""
-        self._track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal, smooth, matching,
-                    motion, motion_gate)
+        self._track(frames, iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
+                    refine_lr=refine_lr, prune=prune, propose=propose, temporal=temporal, smooth=smooth, matching=matching, motion=motion,
+                    motion_gate=motion_gate)
         return self.tracked
 
     def predict_frames(self, frames, horizon, smooth=True, **track_args):
@@ -679,8 +646,9 @@ class AIRonMNIST(AIRModel):
         "hota"] holds the tracker's tensors and totals (seq_hota_i, seq_hota_f, the tables, totals_hota_i / totals_hota_f), with smooth=
         scores["completed"]["hota"] the completed table's; hota_summary() of the tracker / the smoother reads HOTA, DetA, AssA and LocA
         back.  hota=False, the default: exactly the call without the argument."""
-        t, smoother = self._track(frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose, temporal,
-                                  smooth, matching, motion, motion_gate)
+        t, smoother = self._track(frames, iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age,
+                                  refine=refine, refine_lr=refine_lr, prune=prune, propose=propose, temporal=temporal, smooth=smooth,
+                                  matching=matching, motion=motion, motion_gate=motion_gate)
         gb = torch.as_tensor(gt_boxes)
         scores = dict(t.score(gb, tau, accumulate, identity))
         if smoother is not None:

@@ -1,7 +1,7 @@
 """Where the stacks of post-parse stages behind AIRonMNIST.parse / parse_tiled / track are specified, built and cached: the normalised
 spec of a stack (`stack_spec`), the one builder (`build_stack`), the bounded cache and the single-slot holder of built and captured
-stages (`BoundedCache`, `slot`), the keys of the track family (`track_key`, `stream_key`, `stream_smoother_key`, `fit_key`).  Pure Python; the stage classes are imported where a
-stack is built.
+stages (`BoundedCache`, `slot`), the keys of the track family (`track_key`, `stream_key`, `stream_smoother_key`, `fit_key`) and the
+builder of the stack behind one (`build_track_stack`).  Pure Python; the stage classes are imported where a stack is built.
 """
 from collections import namedtuple
 
@@ -52,15 +52,16 @@ def stack_spec(refine=None, refine_lr=None, prune=None, propose=None, temporal=N
                      _per_round(temporal, "temporal: the number of neighbour proposals per round"))
 
 
-def smooth_spec(smooth):
-    """smooth=None | True | dict(horizon=, process_noise=, measurement_noise=, velocity_var=) -> None | the full dict"""
-    if smooth is None or smooth is False:
-        return None
+def smooth_spec(smooth, stream=False):
+    """smooth=None | True | dict(horizon=, process_noise=, measurement_noise=, velocity_var=) -> None | the full dict; stream=True
+    (`stream_smooth_spec`): a dict may carry lag= too (None: max_age), and there is no None: the caller asked for a smoother"""
     from .trajectory import DEFAULTS
-    spec = dict(DEFAULTS, horizon=0)
+    if not stream and (smooth is None or smooth is False):
+        return None
+    spec = dict(DEFAULTS, lag=None, horizon=0) if stream else dict(DEFAULTS, horizon=0)
     if smooth is not True:
         if not isinstance(smooth, dict) or set(smooth) - set(spec):
-            raise ValueError("smooth: None, True or a dict with keys among %s, got %r" % (sorted(spec), smooth))
+            raise ValueError("smooth: %s or a dict with keys among %s, got %r" % ("True" if stream else "None, True", sorted(spec), smooth))
         spec.update(smooth)
     try:
         spec["process_noise"] = tuple(float(v) for v in spec["process_noise"])
@@ -103,32 +104,22 @@ def track_key(eng, n_sequences, n_frames, iou_gate=None, appearance_weight=None,
     return TrackKey(S, F, tuple(sorted(assoc.items())), stack, smooth, matching, str(eng.device), motion, motion_gate)
 
 
-def stream_key(eng, n_sequences, chunk_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-               refine_lr=None, prune=None, propose=None, temporal=None, matching=None, motion=None, motion_gate=None):
-    """The arguments of a stream tracker, normalised and checked as `track_key` does (there is no smoother on a stream): a key of its
-    own in the cache of the track family, never that of a one-shot tracker with the same arguments.  motion and motion_gate: refused
-    (out of scope on a stream)."""
+def stream_key(eng, n_sequences, chunk_frames, motion=None, motion_gate=None, **track_args):
+    """The arguments of a stream tracker, normalised and checked as `track_key` does (`track_args` are its arguments; there is no
+    smooth= among a stream tracker's): a key of its own in the cache of the track family, never that of a one-shot tracker with the
+    same arguments.  motion and motion_gate: refused (out of scope on a stream)."""
     if (motion is not None and motion is not False) or (motion_gate is not None and motion_gate is not False):
         from .track import MOTION_ON_A_STREAM
         raise ValueError(MOTION_ON_A_STREAM)
-    k = track_key(eng, n_sequences, chunk_frames, iou_gate, appearance_weight, birth_score, max_age, refine, refine_lr, prune, propose,
-                  temporal, None, matching)
+    if "smooth" in track_args:
+        raise TypeError("stream_key() got an unexpected keyword argument 'smooth'")
+    k = track_key(eng, n_sequences, chunk_frames, **track_args)
     return StreamKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, True)
 
 
 def stream_smooth_spec(smooth):
     """smooth=True | dict(lag=, horizon=, process_noise=, measurement_noise=, velocity_var=) -> the full dict (lag None: max_age)"""
-    from .trajectory import DEFAULTS
-    spec = dict(DEFAULTS, lag=None, horizon=0)
-    if smooth is not True:
-        if not isinstance(smooth, dict) or set(smooth) - set(spec):
-            raise ValueError("smooth: True or a dict with keys among %s, got %r" % (sorted(spec), smooth))
-        spec.update(smooth)
-    try:
-        spec["process_noise"] = tuple(float(v) for v in spec["process_noise"])
-    except TypeError:
-        raise ValueError("smooth: process_noise must be two numbers (q_shift, q_scale), got %r" % (spec["process_noise"],))
-    return spec
+    return smooth_spec(smooth, stream=True)
 
 
 def stream_smoother_key(eng, n_sequences, chunk_frames, smooth=True, **stream_args):
@@ -174,6 +165,31 @@ def build_stack(base, spec, n_frames=None, classes=None):
         stack.append(ParseProposer(stack[-1], spec.propose[0], spec.propose[1]))
     if spec.temporal is not None:
         stack.append(TemporalProposer(stack[-1], n_frames, spec.temporal[0], spec.temporal[1]))
+    return stack
+
+
+def track_classes():
+    from .track import SequenceTracker, StreamTracker
+    from .trajectory import StreamSmoother, TrajectoryNoiseFitter, TrajectorySmoother
+    return SequenceTracker, StreamTracker, TrajectorySmoother, StreamSmoother, TrajectoryNoiseFitter
+
+
+def build_track_stack(stack, key, classes=None):
+    """`stack` (a provider stack, `build_stack`'s) with what a key of the track family asks for behind it: a SequenceTracker (TrackKey,
+    FitKey: with the key's motion and gate) or a StreamTracker (StreamKey, StreamSmoothKey) bound to its last member, then -- bound to
+    that tracker -- a TrajectorySmoother (TrackKey with smooth), a StreamSmoother (StreamSmoothKey), a TrajectoryNoiseFitter (FitKey)
+    or nothing.  classes: the five constructors in that order (None: track_classes())."""
+    SequenceTracker, StreamTracker, Smoother, StreamSmoother, Fitter = track_classes() if classes is None else classes
+    on_stream = isinstance(key, (StreamKey, StreamSmoothKey))
+    rule = dict(key.assoc, matching=key.matching)
+    if on_stream:
+        stack.append(StreamTracker(stack[-1], key.F, **rule))
+    else:
+        stack.append(SequenceTracker(stack[-1], key.F, motion=key.motion and dict(key.motion), motion_gate=key.motion_gate, **rule))
+    if isinstance(key, FitKey):
+        stack.append(Fitter(stack[-1], *key.fit))
+    elif getattr(key, "smooth", None) is not None:
+        stack.append((StreamSmoother if on_stream else Smoother)(stack[-1], **dict(key.smooth)))
     return stack
 
 

@@ -784,7 +784,9 @@ def _score_objects(c, tracked, frames):
             c["mostly_lost"] += 1 if 5 * tracked[g] <= frames[g] else 0
 
 
-def _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau):
+def _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau=None, n_ids=False, check_T=False):
+    """the arguments of the scoring references, normalised and checked in one order: T (check_T: air_track_hota's), G, the frames, tau
+    (None: the entry takes none), n_ids (False: the entry takes none and None comes back; None: n_frames * T)"""
     import numpy as np
     boxes = np.asarray(boxes, np.float32)
     gt = np.asarray(gt_boxes, np.float32)
@@ -792,21 +794,28 @@ def _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau):
     ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
     T, R = ids.shape
     G, F = gt.shape[1], int(n_frames)
+    if n_ids is not False:
+        n_ids = F * T if n_ids is None else int(n_ids)
+    if check_T and not 1 <= T <= MAX_SLOTS:
+        raise ValueError("track_id: 1..%d objects per frame, got %d" % (MAX_SLOTS, T))
     if not 1 <= G <= MAX_GT:
         raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
     if F < 1 or R % F or gt.shape[0] != R:
         raise ValueError("%d rows / %d ground-truth rows are not sequences of %d frames" % (R, gt.shape[0], F))
-    tau = float(tau)
-    if not 0.0 <= tau <= 1.0:
-        raise ValueError("tau must be within [0, 1], got %r" % (tau,))
-    return boxes, gt, ids, n_in, T, R, G, F, tau
+    if tau is not None:
+        tau = float(tau)
+        if not 0.0 <= tau <= 1.0:
+            raise ValueError("tau must be within [0, 1], got %r" % (tau,))
+    if n_ids is not False and not 1 <= n_ids <= MAX_IDS:
+        raise ValueError("n_ids must be within 1..%d, got %d" % (MAX_IDS, n_ids))
+    return boxes, gt, ids, n_in, T, R, G, F, tau, (None if n_ids is False else n_ids)
 
 
 def reference_score(boxes, num_objects, track_id, gt_boxes, n_frames, tau=0.5):
     """air_track_score restated in numpy float64.  boxes [T, R, 4], num_objects [R], track_id [T, R], gt_boxes [R, G, 4] (or
     [S, F, G, 4]).  Returns seq_counts [S, 8] int32 (COUNTS), seq_iou [S] float64, gt_match [R, G] int32."""
     import numpy as np
-    boxes, gt, ids, n_in, T, R, G, F, tau = _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau)
+    boxes, gt, ids, n_in, T, R, G, F, tau, _ = _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau)
     S = R // F
     counts, seq_iou, gt_match = np.zeros((S, 8), np.int32), np.zeros(S, np.float64), np.full((R, G), -1, np.int32)
     for s in range(S):
@@ -827,7 +836,7 @@ def reference_score_stream(state, boxes, num_objects, track_id, gt_boxes, n_fram
     starts) or what an earlier call returned (not modified): new_score_state's arrays.  Returns (outputs, state): seq_counts [S, 8]
     and seq_iou [S] CUMULATIVE over the stream, gt_match [R, G] of the chunk (-1 on padding rows)."""
     import numpy as np
-    boxes, gt, ids, n_in, T, R, G, F, tau = _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau)
+    boxes, gt, ids, n_in, T, R, G, F, tau, _ = _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau)
     S = R // F
     v_in = check_valid(valid, S, F)
     state = new_score_state(S) if state is None else {k: np.array(state[k]) for k in SCORE_STATE_KEYS}
@@ -862,22 +871,7 @@ def reference_identity(boxes, num_objects, track_id, gt_boxes, n_frames, tau=0.5
     """air_track_idf restated in numpy float64.  boxes [T, R, 4], num_objects [R], track_id [T, R], gt_boxes [R, G, 4] (or
     [S, F, G, 4]); n_ids: None = n_frames * T.  Returns overlap [S, G, n_ids] int32 and seq_idf [S, 4] int32 (IDF_COUNTS)."""
     import numpy as np
-    boxes = np.asarray(boxes, np.float32)
-    gt = np.asarray(gt_boxes, np.float32)
-    gt = gt.reshape(-1, gt.shape[-2], 4)
-    ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
-    T, R = ids.shape
-    G, F = gt.shape[1], int(n_frames)
-    n_ids = F * T if n_ids is None else int(n_ids)
-    if not 1 <= G <= MAX_GT:
-        raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
-    if F < 1 or R % F or gt.shape[0] != R:
-        raise ValueError("%d rows / %d ground-truth rows are not sequences of %d frames" % (R, gt.shape[0], F))
-    tau = float(tau)
-    if not 0.0 <= tau <= 1.0:
-        raise ValueError("tau must be within [0, 1], got %r" % (tau,))
-    if not 1 <= n_ids <= MAX_IDS:
-        raise ValueError("n_ids must be within 1..%d, got %d" % (MAX_IDS, n_ids))
+    boxes, gt, ids, n_in, T, R, G, F, tau, n_ids = _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, tau, n_ids)
     S = R // F
     overlap, seq_idf = np.zeros((S, G, n_ids), np.int32), np.zeros((S, 4), np.int32)
     masks = np.arange(1 << G)
@@ -938,21 +932,7 @@ def reference_hota(boxes, num_objects, track_id, gt_boxes, n_frames, n_ids=None,
     hota_id_count [S, n_ids], hota_gt_count [S, G] and hota_matches [S, 19, G, n_ids] int32.  return_matching=True adds hota_match
     [R, G] int32: the hypothesis matched to slot g in that frame (the one matching, before any threshold), -1 for none."""
     import numpy as np
-    boxes = np.asarray(boxes, np.float32)
-    gt = np.asarray(gt_boxes, np.float32)
-    gt = gt.reshape(-1, gt.shape[-2], 4)
-    ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64)
-    T, R = ids.shape
-    G, F = gt.shape[1], int(n_frames)
-    n_ids = F * T if n_ids is None else int(n_ids)
-    if not 1 <= T <= MAX_SLOTS:
-        raise ValueError("track_id: 1..%d objects per frame, got %d" % (MAX_SLOTS, T))
-    if not 1 <= G <= MAX_GT:
-        raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
-    if F < 1 or R % F or gt.shape[0] != R:
-        raise ValueError("%d rows / %d ground-truth rows are not sequences of %d frames" % (R, gt.shape[0], F))
-    if not 1 <= n_ids <= MAX_IDS:
-        raise ValueError("n_ids must be within 1..%d, got %d" % (MAX_IDS, n_ids))
+    boxes, gt, ids, n_in, T, R, G, F, _, n_ids = _score_arguments(boxes, num_objects, track_id, gt_boxes, n_frames, None, n_ids, True)
     S, NA = R // F, len(HOTA_ALPHAS)
     if S * NA * G * n_ids > 2 ** 31 - 1:
         raise ValueError("hota_matches [%d, %d, %d, %d] would have more than 2^31 - 1 elements" % (S, NA, G, n_ids))
@@ -1055,12 +1035,45 @@ def hota_summary(totals_i, totals_f) -> Dict[str, object]:
     return out
 
 
+# ---- the launch arguments by name ------------------------------------------------------------------------------------------------------
+# The parameters of every air_track_* entry this module launches, in the order of include/air_hip.h and without the trailing stream
+# (tests/test_track_optimal_host.py holds each tuple to the header's prototype).  A plan entry is the values filed under these names.
+_ROWS, _SHAPE = ("what", "boxes", "score", "num_objects"), ("T", "S", "F", "R", "A")
+_RULE = ("iou_gate", "appearance_weight", "birth_score", "max_age")
+_PER_OBJECT = ("track_id", "obj_state", "affinity", "prev_frame", "prev_slot")
+_TABLES = ("num_tracks", "track_first", "track_last", "track_length", "track_gaps", "state_counts")
+_MOTION = (("what", "where", "boxes", "score", "num_objects") + _SHAPE + ("H", "W") + _RULE
+           + ("matching", "q_shift", "q_scale", "measurement_noise", "velocity_var"))
+_SCORED, _SCORE_SHAPE = ("boxes", "num_objects", "track_id", "gt_boxes"), ("T", "G", "S", "F", "R")
+MOT_OUTPUTS = ("seq_counts", "seq_iou", "gt_match")
+ENTRY_ARGS = {
+    "air_track_associate": _ROWS + _SHAPE + _RULE + _PER_OBJECT + _TABLES,
+    "air_track_associate_motion": _MOTION + _PER_OBJECT + _TABLES + ("pred_where", "pred_boxes"),
+    "air_track_associate_motion_gated": _MOTION + ("gate_d2",) + _PER_OBJECT + _TABLES + ("pred_where", "pred_boxes", "pred_d2"),
+    "air_track_associate_stream": (_ROWS + _SHAPE + _RULE + ("valid", "matching", "st_seq", "st_slots", "st_box", "st_what") + _PER_OBJECT
+                                   + ("state_counts", "num_retired") + RETIRED),
+    "air_track_owner": ("owner", "track_id", "T", "R", "H", "W", "track_owner"),
+    "air_track_score": _SCORED + ("tau",) + _SCORE_SHAPE + MOT_OUTPUTS,
+    "air_track_score_stream": _SCORED + ("tau",) + _SCORE_SHAPE + ("valid", "st_i", "st_f") + MOT_OUTPUTS,
+    "air_track_idf": _SCORED + ("tau",) + _SCORE_SHAPE + ("n_ids", "overlap", "seq_idf"),
+    "air_track_hota": _SCORED + _SCORE_SHAPE + ("n_ids", "potential", "id_count", "gt_count", "matches", "seq_hota_i", "seq_hota_f"),
+}
+ENTRY_ARGS["air_track_associate_optimal"] = ENTRY_ARGS["air_track_associate"]
+
+
+def plan_entry(L, name, values):
+    """the plan entry of air_track_* `name`: values[n] of every parameter n of its prototype, in the prototype's order"""
+    return (getattr(L, name), tuple(values[n] for n in ENTRY_ARGS[name]), name)
+
+
 class IdentityScores:
     """The identity metric of a stage (the tracker on its own table, the smoother on its two): the air_track_score launch of every
     key used so far with its buffers and graph (`entries`, at most four: a sweep over tau must not pile up buffers and graphs), the
     staging copy of the ground truth, and the running totals on the device.  An entry made with identity=True runs air_track_idf
     behind air_track_score (one graph still) and feeds `totals_idf`.  HOTA has a cache of its own (`hota_entries`, at most two, keyed
-    by (table, G): the air_track_hota launch, its buffers and graph) and totals of its own (`totals_hota_i`, `totals_hota_f`)."""
+    by (table, G): the air_track_hota launch, its buffers and graph) and totals of its own (`totals_hota_i`, `totals_hota_f`).  A
+    stage on a STREAM holds one entry, air_track_score_stream's (`stream_entry`), and keeps no totals: its counts are cumulative.
+    A TABLE is what a launch scores: (T rows, frames per sequence, boxes, counts, ids)."""
 
     def __init__(self, stage, S):
         import torch
@@ -1074,46 +1087,90 @@ class IdentityScores:
             self.totals_hota_f = torch.zeros((len(HOTA_ALPHAS), 4), dtype=torch.float64, device=dev)
         self.hota_entries = {}                                     # (table, G) -> buffers, plan, graph: at most two, apart from `entries`
 
-    def entry(self, key, G, tau, T, n_frames, boxes, counts, ids, identity=False, n_ids=None):
-        """the air_track_score launch on a table of T rows by S * n_frames columns (boxes, counts, ids) with its buffers -- gt_boxes,
-        seq_counts, seq_iou, gt_match -- kept under key + (G, tau); captured when the stage holds a graph.  identity=True: kept under
-        key + (G, tau, "idf"), with air_track_idf behind it and its buffers seq_idf, idf_overlap [S, G, n_ids]"""
-        import torch
-        eng, S, N = self.engine, self.S, self.S * n_frames
-        key = key + (int(G), float(tau))
-        G, tau_f = key[-2:]
-        if identity:
-            key = key + ("idf",)
-        entry = self.entries.get(key)
+    # ---- the cache ------------------------------------------------------------------------------------------------------------------
+    def _cached(self, cache, limit, key, build):
+        """the entry of `cache` under `key`; a miss is what build() makes, captured when the stage holds a graph, and the oldest entries
+        are evicted, their graphs destroyed, while there would be more than `limit`"""
+        entry = cache.get(key)
         if entry is None:
-            if identity and not 1 <= int(n_ids) <= MAX_IDS:
-                raise ValueError("n_ids must be within 1..%d, got %r" % (MAX_IDS, n_ids))
-            if not 1 <= G <= MAX_GT:
-                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
-            if not 0.0 <= tau_f <= 1.0:
-                raise ValueError("tau must be within [0, 1], got %r" % (tau,))
-            H, dev = self.stage._H, eng.device
-            L, p = H.lib(), H._p
-            with torch.cuda.device(dev):
-                entry = {"gt_boxes": torch.zeros((N, G, 4), device=dev),
-                         "seq_counts": torch.zeros((S, 8), dtype=torch.int32, device=dev),
-                         "seq_iou": torch.zeros((S,), dtype=torch.float64, device=dev),
-                         "gt_match": torch.zeros((N, G), dtype=torch.int32, device=dev), "graph": None}
-            entry["plan"] = [(L.air_track_score, (p(boxes), p(counts), p(ids), p(entry["gt_boxes"]), tau_f, T, G, S, n_frames, N,
-                                                  p(entry["seq_counts"]), p(entry["seq_iou"]), p(entry["gt_match"])), "air_track_score")]
-            if identity:
-                with torch.cuda.device(dev):
-                    entry["seq_idf"] = torch.zeros((S, 4), dtype=torch.int32, device=dev)
-                    entry["idf_overlap"] = torch.zeros((S, G, int(n_ids)), dtype=torch.int32, device=dev)
-                entry["plan"].append((L.air_track_idf, (p(boxes), p(counts), p(ids), p(entry["gt_boxes"]), tau_f, T, G, S, n_frames, N,
-                                                        int(n_ids), p(entry["idf_overlap"]), p(entry["seq_idf"])), "air_track_idf"))
+            entry = build()
             if self.stage._graph is not None:
-                eng.synchronize()
-                entry["graph"] = eng._capture_plans([entry["plan"]])
-            while len(self.entries) >= 4:
-                destroy_graphs([self.entries.pop(next(iter(self.entries)))["graph"]])
-            self.entries[key] = entry
+                self.engine.synchronize()
+                entry["graph"] = self.engine._capture_plans([entry["plan"]])
+            while len(cache) >= limit:
+                destroy_graphs([cache.pop(next(iter(cache)))["graph"]])
+            cache[key] = entry
         return entry
+
+    @staticmethod
+    def _check(G, tau=None, n_ids=None):
+        """the refusals of an entry's arguments, in the one order every entry has them (None: the entry does not take it)"""
+        if n_ids is not None and not 1 <= int(n_ids) <= MAX_IDS:
+            raise ValueError("n_ids must be within 1..%d, got %r" % (MAX_IDS, n_ids))
+        if not 1 <= G <= MAX_GT:
+            raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+        if tau is not None and not 0.0 <= float(tau) <= 1.0:
+            raise ValueError("tau must be within [0, 1], got %r" % (tau,))
+
+    def _zeros(self, **buffers):
+        """an entry without plan and graph yet: a zeroed device buffer of every name=(shape, dtype)"""
+        import torch
+        dev = self.engine.device
+        with torch.cuda.device(dev):
+            return dict({k: torch.zeros(shape, dtype=dtype, device=dev) for k, (shape, dtype) in buffers.items()}, graph=None)
+
+    def _mot_buffers(self, N, G):
+        """the four CLEAR-MOT buffers of a table of N columns: gt_boxes, seq_counts, seq_iou, gt_match"""
+        import torch
+        return self._zeros(gt_boxes=((N, G, 4), torch.float32), seq_counts=((self.S, 8), torch.int32),
+                           seq_iou=((self.S,), torch.float64), gt_match=((N, G), torch.int32))
+
+    def _launch(self, name, table, entry, **more):
+        """the plan entry `name` on `table`: the buffers of `entry` filed under their own names, `more` under the prototype's"""
+        T, n_frames, boxes, counts, ids = table
+        L, p = self.stage._H.lib(), self.stage._H._p
+        values = {k: p(v) for k, v in entry.items() if k not in ("plan", "graph")}
+        values.update(boxes=p(boxes), num_objects=p(counts), track_id=p(ids), T=T, G=int(entry["gt_boxes"].shape[1]), S=self.S,
+                      F=n_frames, R=self.S * n_frames, **more)
+        return plan_entry(L, name, values)
+
+    def entry(self, key, G, tau, table, identity=False, n_ids=None):
+        """the air_track_score launch on `table` with its buffers -- gt_boxes, seq_counts, seq_iou, gt_match -- kept under key +
+        (G, tau); captured when the stage holds a graph.  identity=True: kept under key + (G, tau, "idf"), with air_track_idf behind
+        it and its buffers seq_idf, idf_overlap [S, G, n_ids]"""
+        import torch
+        G, tau_f = int(G), float(tau)
+
+        def build():
+            self._check(G, tau, n_ids if identity else None)
+            entry = self._mot_buffers(self.S * table[1], G)
+            entry["plan"] = [self._launch("air_track_score", table, entry, tau=tau_f)]
+            if identity:
+                entry.update(self._zeros(seq_idf=((self.S, 4), torch.int32), idf_overlap=((self.S, G, int(n_ids)), torch.int32)))
+                entry["plan"].append(self._launch("air_track_idf", table, entry, tau=tau_f, n_ids=int(n_ids),
+                                                  overlap=self.stage._H._p(entry["idf_overlap"])))
+            return entry
+        return self._cached(self.entries, 4, key + (G, tau_f) + (("idf",) if identity else ()), build)
+
+    def stream_entry(self, G, tau, table, valid, state, clash, invalid=None):
+        """the ONE entry of a stream, under (G, tau): air_track_score_stream on `table` with the valid-count buffer `valid` and the
+        score state carried between the chunks (state["score_i"], state["score_f"]), its buffers those of `entry`.  Another key is
+        refused with the stage's own text `clash` % (the key held, the key asked for); `invalid` % (MAX_GT, G, tau), where the stage
+        has one text for a G or a tau out of range"""
+        key = (int(G), float(tau))
+
+        def build():
+            if self.entries:
+                raise ValueError(clash % (next(iter(self.entries)), key))
+            if invalid is not None and not (1 <= key[0] <= MAX_GT and 0.0 <= key[1] <= 1.0):
+                raise ValueError(invalid % (MAX_GT, key[0], tau))
+            self._check(key[0], tau)
+            p = self.stage._H._p
+            entry = self._mot_buffers(self.S * table[1], key[0])
+            entry["plan"] = [self._launch("air_track_score_stream", table, entry, tau=key[1], valid=p(valid), st_i=p(state["score_i"]),
+                                          st_f=p(state["score_f"]))]
+            return entry
+        return self._cached(self.entries, 1, key, build)
 
     def run(self, gt_boxes, n_frames, entry_for):
         """stage gt_boxes [N, G, 4] or [S, n_frames, G, 4] into the buffers of `entry_for(G)` and issue that entry; returns it"""
@@ -1131,88 +1188,75 @@ class IdentityScores:
         eng._replay_or_run(entry["graph"], entry["plan"])
         return entry
 
+    def _accumulate(self, accumulate, entry, **totals):
+        """every total=source: the sum of entry[source] over the sequences is added to the running total of that name (accumulate) or
+        restarts it (not), on the device with no read-back; returns the totals by name"""
+        import torch
+        with torch.cuda.stream(self.engine.stream):
+            for name, source in totals.items():
+                total = getattr(self, name)
+                part = entry[source].sum(0, dtype=total.dtype).reshape(total.shape)
+                if accumulate:
+                    total += part
+                else:
+                    total.copy_(part)
+        return {name: getattr(self, name) for name in totals}
+
     def result(self, entry, accumulate=None):
         """the entry's outputs; accumulate True / False: added to / restarting the totals on the device (no read-back), and the totals"""
-        import torch
-        eng = self.engine
-        out = {k: entry[k] for k in ("seq_counts", "seq_iou", "gt_match")}
-        identity = "seq_idf" in entry
-        if identity:
-            out.update(seq_idf=entry["seq_idf"], idf_overlap=entry["idf_overlap"])
+        identity = {"totals_idf": "seq_idf"} if "seq_idf" in entry else {}
+        out = {k: entry[k] for k in MOT_OUTPUTS + (("seq_idf", "idf_overlap") if identity else ())}
         if accumulate is not None:
-            with torch.cuda.stream(eng.stream):
-                ti, tf = entry["seq_counts"].sum(0, dtype=torch.int64), entry["seq_iou"].sum(0, keepdim=True)
-                if accumulate:
-                    self.totals_i += ti
-                    self.totals_f += tf
-                else:
-                    self.totals_i.copy_(ti)
-                    self.totals_f.copy_(tf)
-                if identity:
-                    td = entry["seq_idf"].sum(0, dtype=torch.int64)
-                    if accumulate:
-                        self.totals_idf += td
-                    else:
-                        self.totals_idf.copy_(td)
-            out.update(totals_i=self.totals_i, totals_f=self.totals_f)
-            if identity:
-                out.update(totals_idf=self.totals_idf)
-        eng.wait_for_engine()
+            out.update(self._accumulate(accumulate, entry, totals_i="seq_counts", totals_f="seq_iou", **identity))
+        self.engine.wait_for_engine()
         return out
 
-    def hota_entry(self, key, G, T, n_frames, boxes, counts, ids, n_ids):
-        """the air_track_hota launch on a table of T rows by S * n_frames columns (boxes, counts, ids) with its buffers -- gt_boxes,
-        seq_hota_i, seq_hota_f, hota_potential, hota_id_count, hota_gt_count, hota_matches -- kept in `hota_entries` under key + (G,);
-        captured (one graph) when the stage holds a graph.  `entries` and its keys are not touched."""
+    def run_stream(self, gt_boxes, tau, table, *stream_entry_args):
+        """stage gt_boxes, issue the stream's entry (`stream_entry`'s arguments behind the table) and return its outputs: seq_counts
+        and seq_iou cumulative over the stream, gt_match of the chunk"""
+        return self.result(self.run(gt_boxes, table[1], lambda G: self.stream_entry(G, tau, table, *stream_entry_args)))
+
+    def stream_summary(self) -> Dict[str, float]:
+        """mot_summary of a stream so far: the cumulative seq_counts and seq_iou of its entry summed over the S sequences at read-back
+        (ONE read-back; no totals are kept on the device).  Nothing scored yet: the figures of nothing (nan rates)."""
         import torch
-        eng, S, N, NA = self.engine, self.S, self.S * n_frames, len(HOTA_ALPHAS)
+        self.engine.wait_for_engine()
+        if not self.entries:
+            return mot_summary([0] * 8, 0.0)
+        entry = next(iter(self.entries.values()))
+        flat = torch.cat([entry["seq_counts"].sum(0, dtype=torch.int64).double(), entry["seq_iou"].sum(0, keepdim=True)]).tolist()
+        return mot_summary(flat[:8], flat[8])
+
+    def hota_entry(self, key, G, table, n_ids):
+        """the air_track_hota launch on `table` with its buffers -- gt_boxes, seq_hota_i, seq_hota_f, hota_potential, hota_id_count,
+        hota_gt_count, hota_matches -- kept in `hota_entries` under key + (G,); captured (one graph) when the stage holds a graph.
+        `entries` and its keys are not touched."""
+        import torch
+        S, N, NA = self.S, self.S * table[1], len(HOTA_ALPHAS)
         G, n_ids = int(G), int(n_ids)
-        key = key + (G,)
-        entry = self.hota_entries.get(key)
-        if entry is None:
-            if not 1 <= n_ids <= MAX_IDS:
-                raise ValueError("n_ids must be within 1..%d, got %r" % (MAX_IDS, n_ids))
-            if not 1 <= G <= MAX_GT:
-                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+
+        def build():
+            self._check(G, n_ids=n_ids)
             if S * NA * G * n_ids > 2 ** 31 - 1:
                 raise ValueError("hota_matches [%d, %d, %d, %d] would have more than 2^31 - 1 elements" % (S, NA, G, n_ids))
-            H, dev = self.stage._H, eng.device
-            L, p = H.lib(), H._p
-            z = lambda shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
-            with torch.cuda.device(dev):
-                entry = {"gt_boxes": z((N, G, 4), torch.float32), "seq_hota_i": z((S, NA, 3)), "seq_hota_f": z((S, NA, 4), torch.float64),
-                         "hota_potential": z((S, G, n_ids), torch.float64), "hota_id_count": z((S, n_ids)),
-                         "hota_gt_count": z((S, G)), "hota_matches": z((S, NA, G, n_ids)), "graph": None}
-            entry["plan"] = [(L.air_track_hota, (p(boxes), p(counts), p(ids), p(entry["gt_boxes"]), T, G, S, n_frames, N, n_ids,
-                                                 p(entry["hota_potential"]), p(entry["hota_id_count"]), p(entry["hota_gt_count"]),
-                                                 p(entry["hota_matches"]), p(entry["seq_hota_i"]), p(entry["seq_hota_f"])),
-                              "air_track_hota")]
-            if self.stage._graph is not None:
-                eng.synchronize()
-                entry["graph"] = eng._capture_plans([entry["plan"]])
-            while len(self.hota_entries) >= 2:
-                destroy_graphs([self.hota_entries.pop(next(iter(self.hota_entries)))["graph"]])
-            self.hota_entries[key] = entry
-        return entry
+            i32, f64, p = torch.int32, torch.float64, self.stage._H._p
+            entry = self._zeros(gt_boxes=((N, G, 4), torch.float32), seq_hota_i=((S, NA, 3), i32), seq_hota_f=((S, NA, 4), f64),
+                                hota_potential=((S, G, n_ids), f64), hota_id_count=((S, n_ids), i32), hota_gt_count=((S, G), i32),
+                                hota_matches=((S, NA, G, n_ids), i32))
+            entry["plan"] = [self._launch("air_track_hota", table, entry, n_ids=n_ids, potential=p(entry["hota_potential"]),
+                                          id_count=p(entry["hota_id_count"]), gt_count=p(entry["hota_gt_count"]),
+                                          matches=p(entry["hota_matches"]))]
+            return entry
+        return self._cached(self.hota_entries, 2, key + (G,), build)
 
     def run_hota(self, gt_boxes, n_frames, entry_for, accumulate=None):
         """stage gt_boxes into the buffers of `entry_for(G)` (a hota_entry), issue it and return its outputs; accumulate True / False:
         added to / restarting totals_hota_i [19, 3] int64 and totals_hota_f [19, 4] float64 on the device (no read-back), and they"""
-        import torch
-        eng = self.engine
         entry = self.run(gt_boxes, n_frames, entry_for)
         out = {k: entry[k] for k in ("seq_hota_i", "seq_hota_f", "hota_potential", "hota_id_count", "hota_gt_count", "hota_matches")}
         if accumulate is not None:
-            with torch.cuda.stream(eng.stream):
-                ti, tf = entry["seq_hota_i"].sum(0, dtype=torch.int64), entry["seq_hota_f"].sum(0)
-                if accumulate:
-                    self.totals_hota_i += ti
-                    self.totals_hota_f += tf
-                else:
-                    self.totals_hota_i.copy_(ti)
-                    self.totals_hota_f.copy_(tf)
-            out.update(totals_hota_i=self.totals_hota_i, totals_hota_f=self.totals_hota_f)
-        eng.wait_for_engine()
+            out.update(self._accumulate(accumulate, entry, totals_hota_i="seq_hota_i", totals_hota_f="seq_hota_f"))
+        self.engine.wait_for_engine()
         return out
 
     def reset(self):
@@ -1250,20 +1294,17 @@ class IdentityScores:
                             [flat[3 * NA + 4 * a:3 * NA + 4 * a + 4] for a in range(NA)])
 
 
-class SequenceTracker(BoundStage):
+class TrackerBase(BoundStage):
+    """What SequenceTracker and StreamTracker share: the binding and its refusals, the association rule, the per-object outputs with
+    state_counts and track_owner, the launch list (the association entry, then air_track_owner), the provider's call with its checks
+    and an IdentityScores.  A subclass allocates what is its own behind this constructor and then `_rebuild()`s; it states its
+    association entry (`_associate`), the provider rows it reads next to `what` (`_read_rows`) and its own part of `result`."""
     ACCEPTS = ("scene", "refiner", "subset", "tiled")
     REFUSALS = TiledSceneParser.REFUSALS
 
-    def __init__(self, provider, n_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
-                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None, motion_gate=None):
-        """motion: None (every track is matched against its last-sighting box), True (against its predicted box, MOTION in the module
-        text, with trajectory.DEFAULTS) or a dict with any of process_noise=(q_shift, q_scale), measurement_noise, velocity_var --
-        what `smooth=` and `fit_track_noise` use.  motion_gate (needs motion): None (the pairs are gated by the IoU with the
-        predicted box), True (MOTION_GATE_DEFAULT, provisional) or a squared Mahalanobis distance > 0: THE GATE in the module text"""
+    def __init__(self, provider, n_frames, iou_gate, appearance_weight, birth_score, max_age, matching):
         self._rows = self.bind(provider)
         T, F, S = check_arguments(provider.T, n_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age, matching)
-        self.motion = check_motion(motion)
-        self.motion_gate = check_motion_gate(motion_gate, self.motion)
         import torch
         from . import hip as H
         self.provider, self.engine = provider, provider.engine
@@ -1275,77 +1316,118 @@ class SequenceTracker(BoundStage):
         self._what = self._rows["what"]
         self.A = int(self._what.shape[-1])
         self.img_size = tuple(int(v) for v in provider.owner.shape[1:])
-        dev = self.engine.device
-        R, FT = self.R, F * T
-        z = lambda shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
-        with torch.cuda.device(dev):
-            self.track_id, self.obj_state, self.affinity = z((T, R)), z((T, R), torch.int8), z((T, R), torch.float32)
-            self.prev_frame, self.prev_slot = z((T, R)), z((T, R))
-            self.num_tracks = z((S,))
-            self.track_first, self.track_last, self.track_length, self.track_gaps = z((S, FT)), z((S, FT)), z((S, FT)), z((S, FT))
-            self.state_counts = z((S, 6))
-            self.track_owner = z((R,) + self.img_size, torch.int16)
-            if self.motion is not None:
-                self.pred_where, self.pred_boxes = z((T, R, 4), torch.float32), z((T, R, 4), torch.float32)
-            if self.motion_gate is not None:
-                self.pred_d2 = z((T, R), torch.float32)
+        R, z = self.R, self._zeros
+        self.track_id, self.obj_state, self.affinity = z((T, R)), z((T, R), torch.int8), z((T, R), torch.float32)
+        self.prev_frame, self.prev_slot = z((T, R)), z((T, R))
+        self.state_counts = z((S, 6))
+        self.track_owner = z((R,) + self.img_size, torch.int16)
         self._H = H
         self.scores = IdentityScores(self, S)
         self._score = self.scores.entries                          # (G, tau) -> buffers, plan, graph
+
+    def _zeros(self, shape, dtype=None):
+        import torch
+        dev = self.engine.device
+        with torch.cuda.device(dev):
+            return torch.zeros(shape, dtype=torch.int32 if dtype is None else dtype, device=dev)
+
+    def _build_plan(self):
+        """nothing of the engine's configuration is held by the tracker's launch list: built once"""
+        provider, (Hi, Wi) = self.provider, self.img_size
+        L, p = self._H.lib(), self._H._p
+        values = dict(what=p(self._what), boxes=p(provider.boxes), score=p(provider.score), num_objects=p(provider.num_objects),
+                      T=self.T, S=self.S, F=self.F, R=self.R, A=self.A, H=Hi, W=Wi, iou_gate=self.iou_gate,
+                      appearance_weight=self.appearance_weight, birth_score=self.birth_score, max_age=self.max_age,
+                      matching=MATCHINGS.index(self.matching), state_counts=p(self.state_counts), owner=p(provider.owner),
+                      track_owner=p(self.track_owner), **{k: p(getattr(self, k)) for k in _PER_OBJECT})
+        associate, own = self._associate(p)
+        values.update(own)
+        self.segments = OrderedDict([("associate", [plan_entry(L, associate, values)]),
+                                     ("owner", [plan_entry(L, "air_track_owner", values)])])
+        self._plan = [e for seg in self.segments.values() for e in seg]
+
+    def _associate(self, p):
+        """(the association entry's name, its values next to the shared ones): the subclass's"""
+        raise NotImplementedError
+
+    def _read_rows(self):
+        """the keys of the provider's rows() that the association reads next to `what` (`run_provider` holds the provider to them)"""
+        return ()
+
+    def _score_entries(self):
+        return list(self._score.values()) + list(self.scores.hota_entries.values())
+
+    def _score_table(self):
+        """the table the metrics score: the provider's boxes and counts with this tracker's ids"""
+        return (self.T, self.F, self.provider.boxes, self.provider.num_objects, self.track_id)
+
+    def check_frames(self, frames):
+        """frames as a tensor of [S, F, H, W]"""
+        import torch
+        frames = torch.as_tensor(frames)
+        Hi, Wi = self.img_size
+        if frames.numel() != self.R * Hi * Wi or frames.dim() < 2 or tuple(frames.shape[:2]) != (self.S, self.F):
+            raise ValueError("expected frames [%d, %d, %d, %d], got %s" % (self.S, self.F, Hi, Wi, tuple(frames.shape)))
+        return frames
+
+    def run_provider(self, frames, *args, **kwargs):
+        """the bound provider's `parse()` on the frames as its R = S F rows (further arguments go to it unchanged)"""
+        par = self.provider
+        base = par.parse(self.check_frames(frames).reshape(self.R, *self.img_size), *args, **kwargs)
+        expected = dict(what=self._what, boxes=par.boxes, score=par.score, num_objects=par.num_objects, owner=par.owner)
+        expected.update({k: self._rows[k] for k in self._read_rows()})
+        self.check_same_buffers(base, expected, "tracker", bound="provider")
+        return base
+
+    def result(self, base=None):
+        out = dict(base) if base is not None else {}
+        out.update({k: getattr(self, k) for k in _PER_OBJECT}, state_counts=self.state_counts, track_owner=self.track_owner)
+        return out
+
+
+class SequenceTracker(TrackerBase):
+    def __init__(self, provider, n_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
+                 birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None, motion_gate=None):
+        """motion: None (every track is matched against its last-sighting box), True (against its predicted box, MOTION in the module
+        text, with trajectory.DEFAULTS) or a dict with any of process_noise=(q_shift, q_scale), measurement_noise, velocity_var --
+        what `smooth=` and `fit_track_noise` use.  motion_gate (needs motion): None (the pairs are gated by the IoU with the
+        predicted box), True (MOTION_GATE_DEFAULT, provisional) or a squared Mahalanobis distance > 0: THE GATE in the module text"""
+        super().__init__(provider, n_frames, iou_gate, appearance_weight, birth_score, max_age, matching)
+        self.motion = check_motion(motion)
+        self.motion_gate = check_motion_gate(motion_gate, self.motion)
+        import torch
+        T, R, S, FT, z = self.T, self.R, self.S, self.F * self.T, self._zeros
+        self.num_tracks = z((S,))
+        self.track_first, self.track_last, self.track_length, self.track_gaps = z((S, FT)), z((S, FT)), z((S, FT)), z((S, FT))
+        if self.motion is not None:
+            self.pred_where, self.pred_boxes = z((T, R, 4), torch.float32), z((T, R, 4), torch.float32)
+        if self.motion_gate is not None:
+            self.pred_d2 = z((T, R), torch.float32)
         self.totals_i, self.totals_f, self.totals_idf = self.scores.totals_i, self.scores.totals_f, self.scores.totals_idf
         self._rebuild()
         self.engine.synchronize()
 
-    def _build_plan(self):
-        """nothing of the engine's configuration is held by the tracker's launch list: built once"""
-        provider, T, R, S, F = self.provider, self.T, self.R, self.S, self.F
-        L, p = self._H.lib(), self._H._p
-        Hi, Wi = self.img_size
-        associate = "air_track_associate_optimal" if self.matching == "optimal" else "air_track_associate"
-        rows = (p(self._what), p(provider.boxes), p(provider.score), p(provider.num_objects))
-        rule = (self.iou_gate, self.appearance_weight, self.birth_score, self.max_age)
-        outputs = (p(self.track_id), p(self.obj_state), p(self.affinity), p(self.prev_frame), p(self.prev_slot), p(self.num_tracks),
-                   p(self.track_first), p(self.track_last), p(self.track_length), p(self.track_gaps), p(self.state_counts))
-        if self.motion is None:
-            args = rows + (T, S, F, R, self.A) + rule + outputs
-        else:                                                      # the one entry of both matchings, still one launch
-            associate, m = "air_track_associate_motion", self.motion
-            args = (rows[0], p(self._rows["where"])) + rows[1:] + (T, S, F, R, self.A, Hi, Wi) + rule + (
-                MATCHINGS.index(self.matching), *m["process_noise"], m["measurement_noise"], m["velocity_var"]) + outputs + (
-                p(self.pred_where), p(self.pred_boxes))
-            if self.motion_gate is not None:                       # ... with gate_d2 behind the noise terms and pred_d2 last
-                associate = "air_track_associate_motion_gated"
-                at = len(args) - len(outputs) - 2
-                args = args[:at] + (self.motion_gate,) + args[at:] + (p(self.pred_d2),)
-        self.segments = OrderedDict([
-            ("associate", [(getattr(L, associate), args, associate)]),
-            ("owner", [(L.air_track_owner, (p(provider.owner), p(self.track_id), T, R, Hi, Wi, p(self.track_owner)),
-                        "air_track_owner")])])
-        self._plan = [e for seg in self.segments.values() for e in seg]
+    def _associate(self, p):
+        """greedy and optimal have an entry each; motion has the one entry of both matchings, the gate another: still one launch"""
+        own, m = {k: p(getattr(self, k)) for k in _TABLES[:-1]}, self.motion
+        if m is None:
+            return "air_track_associate_optimal" if self.matching == "optimal" else "air_track_associate", own
+        own.update(where=p(self._rows["where"]), q_shift=m["process_noise"][0], q_scale=m["process_noise"][1],
+                   measurement_noise=m["measurement_noise"], velocity_var=m["velocity_var"], pred_where=p(self.pred_where),
+                   pred_boxes=p(self.pred_boxes))
+        if self.motion_gate is None:
+            return "air_track_associate_motion", own
+        own.update(gate_d2=self.motion_gate, pred_d2=p(self.pred_d2))
+        return "air_track_associate_motion_gated", own
 
-    def _score_entries(self):
-        return list(self._score.values()) + list(self.scores.hota_entries.values())
+    def _read_rows(self):
+        return ("where",) if self.motion is not None else ()               # the rows the filter reads
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `track()` call behind the bound provider's own (`parser` holds that provider's launch_count())"""
         return {"parser": self.provider.launch_count(), "track_associate": 1, "track_owner": 1}
 
     # ---- tracking -----------------------------------------------------------------------------------------------------------
-    def run_provider(self, frames, *args, **kwargs):
-        """the bound provider's `parse()` on the frames as its R = S F rows (further arguments go to it unchanged)"""
-        import torch
-        par = self.provider
-        frames = torch.as_tensor(frames)
-        Hi, Wi = self.img_size
-        if frames.numel() != self.R * Hi * Wi or frames.dim() < 2 or tuple(frames.shape[:2]) != (self.S, self.F):
-            raise ValueError("expected frames [%d, %d, %d, %d], got %s" % (self.S, self.F, Hi, Wi, tuple(frames.shape)))
-        base = par.parse(frames.reshape(self.R, Hi, Wi), *args, **kwargs)
-        expected = dict(what=self._what, boxes=par.boxes, score=par.score, num_objects=par.num_objects, owner=par.owner)
-        if getattr(self, "motion", None) is not None:              # the rows the filter reads
-            expected.update(where=self._rows["where"])
-        self.check_same_buffers(base, expected, "tracker", bound="provider")
-        return base
-
     def track(self, frames, *args, **kwargs):
         """frames [S, F, H, W]; further arguments go to the provider's `parse()` unchanged (its rows are the frames, row s F + f).
         Returns the provider's dict of device tensors, untouched, and next to it (the NEXT call overwrites them): track_id [T, R] int32
@@ -1364,11 +1446,8 @@ class SequenceTracker(BoundStage):
         return self.result(base)
 
     def result(self, base=None):
-        out = dict(base) if base is not None else {}
-        out.update(track_id=self.track_id, obj_state=self.obj_state, affinity=self.affinity, prev_frame=self.prev_frame,
-                   prev_slot=self.prev_slot, num_tracks=self.num_tracks, track_first=self.track_first, track_last=self.track_last,
-                   track_length=self.track_length, track_gaps=self.track_gaps, state_counts=self.state_counts,
-                   track_owner=self.track_owner)
+        out = super().result(base)
+        out.update({k: getattr(self, k) for k in _TABLES[:-1]})
         if self.motion is not None:
             out.update(pred_where=self.pred_where, pred_boxes=self.pred_boxes)
         if self.motion_gate is not None:
@@ -1377,8 +1456,7 @@ class SequenceTracker(BoundStage):
 
     # ---- the identity metric ------------------------------------------------------------------------------------------------
     def _score_entry(self, G, tau, identity=False):
-        par = self.provider
-        return self.scores.entry((), G, tau, self.T, self.F, par.boxes, par.num_objects, self.track_id, identity, self.F * self.T)
+        return self.scores.entry((), G, tau, self._score_table(), identity, self.F * self.T)
 
     def score(self, gt_boxes, tau=0.5, accumulate=True, identity=False):
         """Score the LATEST `track()` against gt_boxes [R, G, 4] (or [S, F, G, 4]; G <= 8; slot g is the same object in every frame of
@@ -1397,9 +1475,8 @@ class SequenceTracker(BoundStage):
         hota_matches [S, 19, G, F T] int32, and the running totals_hota_i [19, 3] int64 / totals_hota_f [19, 4] float64, which this
         call adds to (accumulate=False: restarts) on the device, with no read-back.  `score` and its cache are not touched.  Same
         stream contract as `track`."""
-        par = self.provider
-        return self.scores.run_hota(gt_boxes, self.F, lambda G: self.scores.hota_entry(
-            (), G, self.T, self.F, par.boxes, par.num_objects, self.track_id, self.F * self.T), bool(accumulate))
+        return self.scores.run_hota(gt_boxes, self.F, lambda G: self.scores.hota_entry((), G, self._score_table(), self.F * self.T),
+                                    bool(accumulate))
 
     def hota_summary(self) -> Dict[str, object]:
         """The HOTA figures of everything `hota` took since the last reset (ONE read-back): hota, deta, assa, detre, detpr, assre,
@@ -1423,7 +1500,7 @@ class SequenceTracker(BoundStage):
         return self.scores.identity_summary()
 
 
-class StreamTracker(BoundStage):
+class StreamTracker(TrackerBase):
     """Identities over a STREAM: S sequences of any length fed in chunks of `chunk_frames` frames, the track table, the id counter and
     the last sightings (box and a bit copy of the `what` row) carried on the device between the calls (include/air_hip.h states the
     layout; nothing is read back between chunks).  Chunk invariance: whatever the chunking -- ragged `valid`, valid = 0 included -- a
@@ -1436,69 +1513,34 @@ class StreamTracker(BoundStage):
     call -- `state_dict()` before and `load_state_dict()` after is how a chunk is re-run.  Ids: 0..32766 per sequence until `reset`;
     a birth beyond is OVERFLOW.  Out of scope on a stream: IDF1 and HOTA (their tables are indexed by global id), more than 32
     live tracks.  Trajectories: a trajectory.StreamSmoother bound to this tracker (fixed-lag smoothing, `lag` frames late; the forecast at once)."""
-    ACCEPTS = SequenceTracker.ACCEPTS
-    REFUSALS = SequenceTracker.REFUSALS
 
     def __init__(self, provider, chunk_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
                  birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None, motion_gate=None):
         if (motion is not None and motion is not False) or (motion_gate is not None and motion_gate is not False):
             raise ValueError(MOTION_ON_A_STREAM)
-        self._rows = self.bind(provider)
-        T, F, S = check_arguments(provider.T, chunk_frames, provider.R, iou_gate, appearance_weight, birth_score, max_age, matching)
+        super().__init__(provider, chunk_frames, iou_gate, appearance_weight, birth_score, max_age, matching)
         import numpy as np
         import torch
-        from . import hip as H
-        self.provider, self.engine = provider, provider.engine
-        self._bound = provider
-        self.T, self.R, self.S, self.F = T, int(provider.R), S, F
-        self.iou_gate, self.appearance_weight, self.birth_score, self.max_age = (float(iou_gate), float(appearance_weight),
-                                                                                 float(birth_score), int(max_age))
-        self.matching = matching
-        self._what = self._rows["what"]
-        self.A = int(self._what.shape[-1])
-        self.img_size = tuple(int(v) for v in provider.owner.shape[1:])
-        dev = self.engine.device
-        R, cap = self.R, MAX_SLOTS + F * T
-        z = lambda shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
-        with torch.cuda.device(dev):
-            self.track_id, self.obj_state, self.affinity = z((T, R)), z((T, R), torch.int8), z((T, R), torch.float32)
-            self.prev_frame, self.prev_slot = z((T, R)), z((T, R))
-            self.state_counts, self.num_retired = z((S, 6)), z((S,))
-            self.retired = {k: z((S, cap)) for k in RETIRED}
-            self.track_owner = z((R,) + self.img_size, torch.int16)
-            self.valid = z((S,))
-            self.state = {"seq": z((S, 2)), "slots": z((S, 8, MAX_SLOTS)), "box": z((S, MAX_SLOTS, 4), torch.float32),
-                          "what": z((S, MAX_SLOTS, self.A), torch.float32), "score_i": z((S, 32)), "score_f": z((S,), torch.float64)}
+        S, z = self.S, self._zeros
+        self.num_retired = z((S,))
+        self.retired = {k: z((S, MAX_SLOTS + self.F * self.T)) for k in RETIRED}
+        self.valid = z((S,))
+        self.state = {"seq": z((S, 2)), "slots": z((S, 8, MAX_SLOTS)), "box": z((S, MAX_SLOTS, 4), torch.float32),
+                      "what": z((S, MAX_SLOTS, self.A), torch.float32), "score_i": z((S, 32)), "score_f": z((S,), torch.float64)}
         self.frames_seen = np.zeros(S, np.int64)                   # the host's mirror of state["seq"][:, 0]
         # `valid` is staged in pinned memory and copied without blocking the host; a ring, so that the host waits only for the copy
         # of four pushes ago (long done) before it reuses a buffer, never for the chunk that is still running
         self._valid_ring = [(torch.zeros((S,), dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(4)]
         self._pushes = 0
-        self._H = H
-        self._score = {}                                           # at most one entry: (G, tau) -> buffers, plan, graph
         self._rebuild()
         self.reset()
         self.engine.synchronize()
 
-    def _build_plan(self):
-        """nothing of the engine's configuration is held by the launch list: built once"""
-        provider, T, R, S, F, st = self.provider, self.T, self.R, self.S, self.F, self.state
-        L, p = self._H.lib(), self._H._p
-        Hi, Wi = self.img_size
-        self.segments = OrderedDict([
-            ("associate", [(L.air_track_associate_stream,
-                            (p(self._what), p(provider.boxes), p(provider.score), p(provider.num_objects), T, S, F, R, self.A,
-                             self.iou_gate, self.appearance_weight, self.birth_score, self.max_age, p(self.valid),
-                             MATCHINGS.index(self.matching), p(st["seq"]), p(st["slots"]), p(st["box"]), p(st["what"]),
-                             p(self.track_id), p(self.obj_state), p(self.affinity), p(self.prev_frame), p(self.prev_slot),
-                             p(self.state_counts), p(self.num_retired), *[p(self.retired[k]) for k in RETIRED]),
-                            "air_track_associate_stream")]),
-            ("owner", [(L.air_track_owner, (p(provider.owner), p(self.track_id), T, R, Hi, Wi, p(self.track_owner)),
-                        "air_track_owner")])])
-        self._plan = [e for seg in self.segments.values() for e in seg]
-
-    def _score_entries(self):
-        return self._score.values()
+    def _associate(self, p):
+        st = self.state
+        return "air_track_associate_stream", dict(valid=p(self.valid), st_seq=p(st["seq"]), st_slots=p(st["slots"]), st_box=p(st["box"]),
+                                                  st_what=p(st["what"]), num_retired=p(self.num_retired),
+                                                  **{k: p(self.retired[k]) for k in RETIRED})
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `push()` behind the bound provider's own (`parser` holds that provider's launch_count())"""
@@ -1578,8 +1620,6 @@ class StreamTracker(BoundStage):
         self.frames_seen[:] = self.state["seq"][:, 0].cpu().numpy()
 
     # ---- tracking -----------------------------------------------------------------------------------------------------------
-    run_provider = SequenceTracker.run_provider
-
     def push(self, frames, valid=None, *args, **kwargs):
         """The next chunk: frames [S, F, H, W], valid [S] integers on the host (None: every frame; sequence s has its first
         clip(valid[s], 0, F) frames in this chunk, the rest of its rows is padding whose contents do not matter -- the provider still
@@ -1598,10 +1638,7 @@ class StreamTracker(BoundStage):
             valid = valid.cpu().numpy()
         v = check_valid(valid, self.S, self.F)
         after = check_frames_seen(self.frames_seen, v)
-        frames = torch.as_tensor(frames)
-        Hi, Wi = self.img_size
-        if frames.numel() != self.R * Hi * Wi or frames.dim() < 2 or tuple(frames.shape[:2]) != (self.S, self.F):
-            raise ValueError("expected frames [%d, %d, %d, %d], got %s" % (self.S, self.F, Hi, Wi, tuple(frames.shape)))
+        frames = self.check_frames(frames)
         # `valid` goes to the device ahead of the parse, on the engine's stream: behind the launches that read the buffer for the
         # chunk before (its tail, its score), in front of this chunk's tail; the host runs on
         staged, copied = self._valid_ring[self._pushes % len(self._valid_ring)]
@@ -1619,69 +1656,21 @@ class StreamTracker(BoundStage):
         return self.result(base)
 
     def result(self, base=None):
-        out = dict(base) if base is not None else {}
-        out.update(track_id=self.track_id, obj_state=self.obj_state, affinity=self.affinity, prev_frame=self.prev_frame,
-                   prev_slot=self.prev_slot, state_counts=self.state_counts, num_retired=self.num_retired, track_owner=self.track_owner,
-                   **self.retired)
+        out = super().result(base)
+        out.update(num_retired=self.num_retired, **self.retired)
         return out
 
     # ---- the identity metric ------------------------------------------------------------------------------------------------
-    def _score_entry(self, G, tau):
-        import torch
-        key = (int(G), float(tau))
-        entry = self._score.get(key)
-        if entry is None:
-            if self._score:
-                raise ValueError("this stream is scored with (G, tau) = %r; call score_reset() with nothing pushed in between, or a "
-                                 "stream of its own, for %r" % (next(iter(self._score)), key))
-            G, tau_f = key
-            if not 1 <= G <= MAX_GT:
-                raise ValueError("gt_boxes: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
-            if not 0.0 <= tau_f <= 1.0:
-                raise ValueError("tau must be within [0, 1], got %r" % (tau,))
-            eng, par, st, S, R = self.engine, self.provider, self.state, self.S, self.R
-            L, p, dev = self._H.lib(), self._H._p, eng.device
-            with torch.cuda.device(dev):
-                entry = {"gt_boxes": torch.zeros((R, G, 4), device=dev), "seq_counts": torch.zeros((S, 8), dtype=torch.int32, device=dev),
-                         "seq_iou": torch.zeros((S,), dtype=torch.float64, device=dev),
-                         "gt_match": torch.zeros((R, G), dtype=torch.int32, device=dev), "graph": None}
-            entry["plan"] = [(L.air_track_score_stream,
-                              (p(par.boxes), p(par.num_objects), p(self.track_id), p(entry["gt_boxes"]), tau_f, self.T, G, S, self.F, R,
-                               p(self.valid), p(st["score_i"]), p(st["score_f"]), p(entry["seq_counts"]), p(entry["seq_iou"]),
-                               p(entry["gt_match"])), "air_track_score_stream")]
-            if self._graph is not None:
-                eng.synchronize()
-                entry["graph"] = eng._capture_plans([entry["plan"]])
-            self._score[key] = entry
-        return entry
-
     def score(self, gt_boxes, tau=0.5):
         """Score the LATEST chunk against gt_boxes [R, G, 4] (or [S, F, G, 4]; G <= 8; slot g is the same object over the whole stream
         of a sequence, width <= 0 = absent; padding rows are not read), continuing the stream's metric: an identity switch at a chunk
         boundary counts.  Once per push -- like the push it mutates its state.  Returns device tensors the next call overwrites:
         seq_counts [S, 8] int32 (COUNTS) and seq_iou [S] float64 CUMULATIVE over the stream, gt_match [R, G] int32 of the chunk."""
-        import torch
-        eng, N = self.engine, self.R
-        gb = torch.as_tensor(gt_boxes)
-        if gb.dim() not in (3, 4) or gb.shape[-1] != 4 or gb.numel() != N * gb.shape[-2] * 4:
-            raise ValueError("gt_boxes: expected [%d, G, 4] or [%d, %d, G, 4], got %s" % (N, self.S, self.F, tuple(gb.shape)))
-        entry = self._score_entry(gb.shape[-2], tau)
-        eng.wait_for_caller()
-        with torch.cuda.stream(eng.stream):
-            entry["gt_boxes"].copy_(gb.reshape(entry["gt_boxes"].shape), non_blocking=True)
-        if gb.is_cuda:
-            gb.record_stream(eng.stream)
-        eng._replay_or_run(entry["graph"], entry["plan"])
-        eng.wait_for_engine()
-        return {k: entry[k] for k in ("seq_counts", "seq_iou", "gt_match")}
+        return self.scores.run_stream(gt_boxes, tau, self._score_table(), self.valid, self.state,
+                                      "this stream is scored with (G, tau) = %r; call score_reset() with nothing pushed in between, or a "
+                                      "stream of its own, for %r")
 
     def summary(self) -> Dict[str, float]:
         """mot_summary of the stream so far: the cumulative seq_counts and seq_iou summed over the S sequences at read-back (ONE
         read-back; no totals are kept on the device).  Nothing scored yet: the figures of nothing (nan rates)."""
-        import torch
-        self.engine.wait_for_engine()
-        if not self._score:
-            return mot_summary([0] * 8, 0.0)
-        entry = next(iter(self._score.values()))
-        flat = torch.cat([entry["seq_counts"].sum(0, dtype=torch.int64).double(), entry["seq_iou"].sum(0, keepdim=True)]).tolist()
-        return mot_summary(flat[:8], flat[8])
+        return self.scores.stream_summary()

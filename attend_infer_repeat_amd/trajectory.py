@@ -795,12 +795,16 @@ class TrajectorySmoother(BoundStage):
         return out
 
     # ---- the identity metric on the tables ------------------------------------------------------------------------------------
-    def _score_entry(self, table, G, tau, identity=False):
+    def _score_table(self, table, entry):
+        """the completed or the forecast table as IdentityScores takes one; `entry` names the kernel in the refusal"""
         t, n_frames = (self.sm, self.F) if table == "completed" else (self.fc, self.horizon)
         if n_frames * self.C > MAX_IDS:
-            raise ValueError("air_track_score takes at most %d rows per sequence; %d frames of %d completed rows are %d"
-                             % (MAX_IDS, n_frames, self.C, n_frames * self.C))
-        return self.scores.entry((table,), G, tau, self.C, n_frames, t["boxes"], t["count"], t["id"], identity, self.F * self.window_T)
+            raise ValueError("%s takes at most %d rows per sequence; %d frames of %d completed rows are %d"
+                             % (entry, MAX_IDS, n_frames, self.C, n_frames * self.C))
+        return (self.C, n_frames, t["boxes"], t["count"], t["id"])
+
+    def _score_entry(self, table, G, tau, identity=False):
+        return self.scores.entry((table,), G, tau, self._score_table(table, "air_track_score"), identity, self.F * self.window_T)
 
     def _run_score(self, table, gt_boxes, tau, n_frames, identity=False):
         return self.scores.run(gt_boxes, n_frames, lambda G: self._score_entry(table, G, tau, bool(identity)))
@@ -823,11 +827,7 @@ class TrajectorySmoother(BoundStage):
         return self.scores.result(self._run_score("forecast", gt_future_boxes, tau, self.horizon, identity))
 
     def _hota_entry(self, table, G):
-        t, n_frames = (self.sm, self.F) if table == "completed" else (self.fc, self.horizon)
-        if n_frames * self.C > MAX_IDS:
-            raise ValueError("air_track_hota takes at most %d rows per sequence; %d frames of %d completed rows are %d"
-                             % (MAX_IDS, n_frames, self.C, n_frames * self.C))
-        return self.scores.hota_entry((table,), G, self.C, n_frames, t["boxes"], t["count"], t["id"], self.F * self.window_T)
+        return self.scores.hota_entry((table,), G, self._score_table(table, "air_track_hota"), self.F * self.window_T)
 
     def hota(self, gt_boxes, accumulate=True):
         """SequenceTracker.hota on the COMPLETED table of the latest `run()`: air_track_hota with T := C on sm_boxes, sm_count, sm_id
@@ -910,7 +910,8 @@ class StreamSmoother(BoundStage):
             self.sm_counts, self.emit_frame, self.num_emitted = z((S, 3), torch.int32), z((S, F), torch.int32), z((S,), torch.int32)
             self.tail_frame = z((S, max(L, 1)), torch.int32)
         self.frames_seen = np.zeros(S, np.int64)                   # the host's mirror of state["seq"][:, 0]
-        self._score, self._tail = {}, {"plan": [], "graph": None}
+        self.scores = IdentityScores(self, S)
+        self._score, self._tail = self.scores.entries, {"plan": [], "graph": None}
         t = self.sm
         self.what, self.where, self.glimpse, self.boxes = t["what"], t["where"], t["glimpse"], t["boxes_out"]
         self.presence, self.num_objects, self.owner = t["presence"], t["num_objects"], t["owner"]
@@ -1083,52 +1084,14 @@ class StreamSmoother(BoundStage):
         num_emitted on sm_boxes, sm_count, sm_id, continuing CLEAR-MOT across the pushes.  gt_boxes [R, G, 4] or [S, F, G, 4]: row
         s F + e the ground truth of global frame emit_frame[s, e] (the caller keeps it `lag` frames).  Once per push.  Returns
         seq_counts [S, 8], seq_iou [S] float64 (cumulative) and gt_match [R, G] of the emitted columns."""
-        import torch
-        from .track import MAX_GT
-        eng, R, S = self.engine, self.R, self.S
-        gb = torch.as_tensor(gt_boxes)
-        if gb.dim() not in (3, 4) or gb.shape[-1] != 4 or gb.numel() != R * gb.shape[-2] * 4:
-            raise ValueError("gt_boxes: expected [%d, G, 4] or [%d, %d, G, 4], got %s" % (R, S, self.F, tuple(gb.shape)))
-        key = (int(gb.shape[-2]), float(tau))
-        entry = self._score.get(key)
-        if entry is None:
-            if self._score:
-                raise ValueError("this stream is scored with (G, tau) = %r; a stream of its own for %r" % (next(iter(self._score)), key))
-            G, tau_f = key
-            if not 1 <= G <= MAX_GT or not 0.0 <= tau_f <= 1.0:
-                raise ValueError("gt_boxes: 1..%d ground-truth slots and tau within [0, 1], got %d and %r" % (MAX_GT, G, tau))
-            L, p, dev, sm, ss = self._H.lib(), self._H._p, eng.device, self.sm, self.score_state
-            with torch.cuda.device(dev):
-                entry = {"gt_boxes": torch.zeros((R, G, 4), device=dev), "seq_counts": torch.zeros((S, 8), dtype=torch.int32, device=dev),
-                         "seq_iou": torch.zeros((S,), dtype=torch.float64, device=dev),
-                         "gt_match": torch.zeros((R, G), dtype=torch.int32, device=dev), "graph": None}
-            entry["plan"] = [(L.air_track_score_stream,
-                              (p(sm["boxes"]), p(sm["count"]), p(sm["id"]), p(entry["gt_boxes"]), tau_f, self.C, G, S, self.F, R,
-                               p(self.num_emitted), p(ss["score_i"]), p(ss["score_f"]), p(entry["seq_counts"]), p(entry["seq_iou"]),
-                               p(entry["gt_match"])), "air_track_score_stream")]
-            if self._graph is not None:
-                eng.synchronize()
-                entry["graph"] = eng._capture_plans([entry["plan"]])
-            self._score[key] = entry
-        eng.wait_for_caller()
-        with torch.cuda.stream(eng.stream):
-            entry["gt_boxes"].copy_(gb.reshape(entry["gt_boxes"].shape), non_blocking=True)
-        if gb.is_cuda:
-            gb.record_stream(eng.stream)
-        eng._replay_or_run(entry["graph"], entry["plan"])
-        eng.wait_for_engine()
-        return {k: entry[k] for k in ("seq_counts", "seq_iou", "gt_match")}
+        sm = self.sm
+        return self.scores.run_stream(gt_boxes, tau, (self.C, self.F, sm["boxes"], sm["count"], sm["id"]), self.num_emitted,
+                                      self.score_state, "this stream is scored with (G, tau) = %r; a stream of its own for %r",
+                                      "gt_boxes: 1..%d ground-truth slots and tau within [0, 1], got %d and %r")
 
     def summary(self) -> Dict[str, float]:
         """track.mot_summary of the emitted frames scored so far (ONE read-back)"""
-        import torch
-        from .track import mot_summary
-        self.engine.wait_for_engine()
-        if not self._score:
-            return mot_summary([0] * 8, 0.0)
-        entry = next(iter(self._score.values()))
-        flat = torch.cat([entry["seq_counts"].sum(0, dtype=torch.int64).double(), entry["seq_iou"].sum(0, keepdim=True)]).tolist()
-        return mot_summary(flat[:8], flat[8])
+        return self.scores.stream_summary()
 
 
 # ---- the noise terms by maximum likelihood (the module text states the statistics; include/air_hip.h the kernels' order) --------------------

@@ -287,3 +287,66 @@ def test_track_key_checks_before_anything_is_built():
             stacks.track_key(eng, 2, 3, temporal=bad)
     with pytest.raises(ValueError, match="smooth"):
         stacks.track_key(eng, 2, 3, smooth=dict(unknown=1))
+
+
+# ---- the stack behind a key of the track family -------------------------------------------------------------------------------------
+def track_stub_classes(log):
+    """stub constructors in the order of stacks.track_classes(); each remembers its keyword arguments too"""
+    def make(kind):
+        def build(provider, *args, **kwargs):
+            stage = Stage(kind, log, provider, *args)
+            stage.kwargs = kwargs
+            return stage
+        return build
+    return tuple(make(k) for k in ("tracker", "stream_tracker", "smoother", "stream_smoother", "fitter"))
+
+
+def test_track_classes_are_the_five_of_the_family():
+    from attend_infer_repeat_amd import track, trajectory
+    assert stacks.track_classes() == (track.SequenceTracker, track.StreamTracker, trajectory.TrajectorySmoother,
+                                      trajectory.StreamSmoother, trajectory.TrajectoryNoiseFitter)
+
+
+@pytest.mark.parametrize("kind", ["track", "track_smooth", "fit", "stream", "stream_smooth"])
+def test_build_track_stack(kind):
+    from attend_infer_repeat_amd.track import DEFAULTS, MOTION_GATE_DEFAULT, check_motion
+    eng = types.SimpleNamespace(cfg=EngineConfig(), device="cuda:0")
+    S, F, rule = 2, 5, dict(max_age=2, matching="optimal")
+    moving = dict(motion=True, motion_gate=True)
+    key = {"track": lambda: stacks.track_key(eng, S, F, **rule, **moving),
+           "track_smooth": lambda: stacks.track_key(eng, S, F, smooth=dict(horizon=2), **rule, **moving),
+           "fit": lambda: stacks.fit_key(eng, S, F, **rule, **moving),
+           "stream": lambda: stacks.stream_key(eng, S, F, **rule),
+           "stream_smooth": lambda: stacks.stream_smoother_key(eng, S, F, dict(lag=3), **rule)}[kind]()
+    log, base = [], [object(), object()]
+    stack = stacks.build_track_stack(list(base), key, classes=track_stub_classes(log))
+    assert stack[:2] == base and log == []                         # behind the provider stack; building captures nothing
+    tracker = stack[2]
+    assert tracker.parser is base[-1] and tracker.args == (F,)     # bound to the last provider, over F frames
+    want = dict(DEFAULTS, max_age=2, matching="optimal")
+    if kind.startswith("stream"):
+        assert tracker.kind == "stream_tracker" and tracker.kwargs == want          # no motion, no gate: not even as None
+    else:
+        assert tracker.kind == "tracker" and tracker.kwargs == dict(want, motion=check_motion(True), motion_gate=MOTION_GATE_DEFAULT)
+    last = {"track": None, "track_smooth": "smoother", "fit": "fitter", "stream": None, "stream_smooth": "stream_smoother"}[kind]
+    assert [s.kind for s in stack[3:]] == [last] * (last is not None)
+    if last is not None:
+        assert stack[3].parser is tracker                          # bound to the tracker
+        if kind == "fit":
+            assert stack[3].args == key.fit and stack[3].kwargs == {}
+        else:
+            assert stack[3].args == () and stack[3].kwargs == dict(key.smooth)
+            assert stack[3].kwargs["horizon"] == (2 if kind == "track_smooth" else 0)
+            assert ("lag" in stack[3].kwargs) == (kind != "track_smooth")
+    plain = stacks.build_track_stack([base[0]], stacks.track_key(eng, S, F), classes=track_stub_classes(log))
+    assert plain[1].kwargs == dict(DEFAULTS, matching="greedy", motion=None, motion_gate=None)
+
+
+def test_the_stream_keys_take_no_smooth_among_the_trackers_arguments():
+    eng = types.SimpleNamespace(cfg=EngineConfig(), device="cuda:0")
+    with pytest.raises(TypeError, match="smooth"):
+        stacks.stream_key(eng, 2, 5, smooth=True)
+    with pytest.raises(TypeError, match="bogus"):
+        stacks.stream_key(eng, 2, 5, bogus=1)
+    with pytest.raises(TypeError, match="bogus"):
+        stacks.track_key(eng, 2, 5, bogus=1)

@@ -353,6 +353,18 @@ def test_the_new_refusals():
         track.reference_identity(idc["boxes"], idc["n"], idc["ids"], idc["gt"], 3)
 
 
+def header_arguments(header):
+    """{entry: the parameter declarations of its prototype in include/air_hip.h, in order} of the ten entries track.py launches"""
+    src = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    args = {}
+    for name in ("associate", "associate_optimal", "associate_motion", "associate_motion_gated", "associate_stream", "owner", "score",
+                 "score_stream", "idf", "hota"):
+        m = re.search(r"AIR_ENGINE_API int air_track_%s\(([^;]*)\);" % name, src)
+        assert m, name
+        args["air_track_" + name] = [re.sub(r"\s+", " ", a).strip() for a in m.group(1).split(",")]
+    return args
+
+
 def test_abi_numbers_header_and_ctypes_table():
     import ctypes
 
@@ -360,15 +372,75 @@ def test_abi_numbers_header_and_ctypes_table():
     assert _lib.ABI_VERSION == 10 and _lib.ENGINE_ABI_VERSION == 5
     header = open(os.path.join(ROOT, "include", "air_hip.h")).read()
     assert re.search(r"#define\s+AIR_ABI_VERSION\s+10\b", header) and re.search(r"#define\s+AIR_ENGINE_ABI_VERSION\s+5\b", header)
-    src = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    args = {}
-    for name in ("air_track_associate", "air_track_associate_optimal", "air_track_idf", "air_track_score"):
-        m = re.search(r"AIR_ENGINE_API int %s\(([^;]*)\);" % name, src)
-        assert m, name
-        args[name] = [re.sub(r"\s+", " ", a).strip() for a in m.group(1).split(",")]
+    args = header_arguments(header)
+    assert set(args) == set(track.ENTRY_ARGS) and len(args) == 10                            # every air_track_* entry track.py launches
+    for name in args:
         assert len(args[name]) == len(_lib.SIGNATURES[name][1]) and _lib.SIGNATURES[name][0] is ctypes.c_int, name
         for text, ctype in zip(args[name], _lib.SIGNATURES[name][1]):
             want = _lib.P if "*" in text else (ctypes.c_double if text.startswith("double") else ctypes.c_int)
             assert ctype is want, (name, text)
+        names = [re.search(r"(\w+)$", text).group(1) for text in args[name]]
+        assert names[-1] == "stream" and tuple(names[:-1]) == track.ENTRY_ARGS[name], name   # the launch tuples: the header's order
     assert args["air_track_associate_optimal"] == args["air_track_associate"]                # exactly its argument list
     assert len(args["air_track_idf"]) == 14 and args["air_track_idf"][10] == "int n_ids"
+
+
+# ---- the launch list is built from the header's names -------------------------------------------------------------------------------
+class Named:
+    """a stand-in for a device buffer that knows the name it was made under"""
+
+    def __init__(self, name):
+        self.name = name
+
+    def __repr__(self):
+        return "<%s>" % self.name
+
+
+def stub_tracker(matching, motion, motion_gate):
+    """a SequenceTracker without its constructor: every buffer a Named, a library whose entries are their own names, p = identity"""
+    import types
+    tk = object.__new__(track.SequenceTracker)
+    lib = types.SimpleNamespace(**{name: name for name in track.ENTRY_ARGS})
+    tk._H = types.SimpleNamespace(lib=lambda: lib, _p=lambda t: t)
+    tk.provider = types.SimpleNamespace(**{k: Named("provider." + k) for k in ("boxes", "score", "num_objects", "owner")})
+    tk._what, tk._rows = Named("rows.what"), {"where": Named("rows.where")}
+    tk.T, tk.S, tk.F, tk.R, tk.A, tk.img_size = 3, 2, 5, 10, 7, (48, 50)
+    tk.iou_gate, tk.appearance_weight, tk.birth_score, tk.max_age, tk.matching = 0.125, 0.25, 0.5, 2, matching
+    tk.motion, tk.motion_gate = motion, motion_gate
+    for k in track._PER_OBJECT + track._TABLES + ("track_owner", "pred_where", "pred_boxes", "pred_d2"):
+        setattr(tk, k, Named(k))
+    tk._build_plan()
+    return tk
+
+
+@pytest.mark.parametrize("matching,motion,gate,entry", [("greedy", False, None, "air_track_associate"),
+                                                        ("optimal", False, None, "air_track_associate_optimal"),
+                                                        ("greedy", True, None, "air_track_associate_motion"),
+                                                        ("optimal", True, None, "air_track_associate_motion"),
+                                                        ("optimal", True, 9.5, "air_track_associate_motion_gated")])
+def test_the_built_plan_files_every_value_under_the_headers_name(matching, motion, gate, entry):
+    noise = dict(process_noise=(1e-3, 2e-3), measurement_noise=3e-3, velocity_var=4e-2)
+    tk = stub_tracker(matching, noise if motion else None, gate)
+    assert list(tk.segments) == ["associate", "owner"] and [e[2] for e in tk._plan] == [entry, "air_track_owner"]
+    assert all(fn == name for fn, _, name in tk._plan)             # the library's entry of that name
+    header = header_arguments(open(os.path.join(ROOT, "include", "air_hip.h")).read())
+    scalars = dict(T=3, S=2, F=5, R=10, A=7, H=48, W=50, iou_gate=0.125, appearance_weight=0.25, birth_score=0.5, max_age=2,
+                   matching=track.MATCHINGS.index(matching), q_shift=1e-3, q_scale=2e-3, measurement_noise=3e-3, velocity_var=4e-2,
+                   gate_d2=gate)
+    buffers = dict(what=tk._what, where=tk._rows["where"], boxes=tk.provider.boxes, score=tk.provider.score,
+                   num_objects=tk.provider.num_objects, owner=tk.provider.owner)
+    for _, got, name in tk._plan:
+        names = [re.search(r"(\w+)$", text).group(1) for text in header[name]][:-1]
+        assert len(got) == len(names), name
+        for n, v in zip(names, got):
+            if n in scalars:
+                assert v == scalars[n] and type(v) is type(scalars[n]), (name, n, v)
+            else:
+                assert v is (buffers[n] if n in buffers else getattr(tk, n)), (name, n, v)         # the very buffer: identity
+    got = dict(zip(track.ENTRY_ARGS[entry], tk._plan[0][1]))
+    if gate is not None:                                           # gate_d2 directly behind velocity_var, pred_d2 last
+        at = track.ENTRY_ARGS[entry].index("velocity_var")
+        assert tk._plan[0][1][at:at + 2] == (4e-2, 9.5) and tk._plan[0][1][-1] is tk.pred_d2 and tk._plan[0][1][-2] is tk.pred_boxes
+    else:
+        assert "gate_d2" not in got and "pred_d2" not in got
+    assert ("where" in got) == ("pred_where" in got) == bool(motion)
