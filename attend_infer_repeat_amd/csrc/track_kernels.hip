@@ -16,6 +16,9 @@
 //                        one-to-one sum over it, by dynamic programming over the subsets of slots.
 //   air_track_hota:      the HOTA counts of the same tracks at 19 localisation thresholds: two passes over the frames, the potential
 //                        table of every (slot, id) first, then one optimal matching per frame scored by it (the one-wavefront solver).
+//   air_track_stitch:    track fragments joined across long occlusions: per track its own Kalman filter, per (ended, begun later)
+//                        pair the Mahalanobis distance of the later track's first sighting from the earlier one's prediction and the
+//                        msd of their `what` rows, one optimal assignment over the tracks (the one-wavefront solver), ids relabelled.
 // Everything a float decides is float64 with contraction off; no floating-point atomics, no cross-workgroup traffic, one fixed order:
 // the same bits run to run.
 #include <math.h>
@@ -1413,6 +1416,277 @@ extern "C" int air_track_hota(const float *boxes, const int *num_objects, const 
     const TrackHotaArgs a = {boxes, gt_boxes, num_objects, track_id, potential, seq_hota_f, id_count, gt_count, matches, seq_hota_i,
                              T, G, S, F, n_ids};
     hipLaunchKernelGGL(track_hota_kernel, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// ============================================================================================================
+// stitch
+// ============================================================================================================
+struct TrackStitchArgs {
+    const float *what, *where;
+    const int *track_id, *num_tracks, *track_first, *track_last, *track_length, *track_gaps;
+    int *stitch_id, *stitch_parent, *stitch_root, *stitch_first, *stitch_last, *stitch_length, *stitch_gaps, *num_links, *stitch_status;
+    float *stitch_d2, *stitch_affinity;
+    double gate_d2, w, q[2], r, velocity_var;      // q[0]: the shifts, q[1]: the scales (TrackMotionArgs')
+    int T, S, F, A, max_gap;
+};
+
+// One 256-thread workgroup per sequence; N = the ids issued, at most 32 (more: the sequence is copied through, status 1).
+//   filter   lane i < N of wavefront 0 walks the frames clip(first[i]) .. clip(last[i]) of its id one by one -- the slot of a sighting is
+//            the lowest j with track_id == i -- and runs the tracker's own filter statements: a start at the first sighting; at a later
+//            one, m frames on, m - 1 predicts one by one, then a predict and TRAJ_UPDATE.  It keeps the 14 doubles in registers and the
+//            (frame, slot) of its first and last sighting and the first sighting's `where` row in LDS.
+//   predict  the same lane then predicts on, one frame at a time, up to max_gap frames or the end of the sequence; at step g it
+//            writes its predicted state into its own column of gstate_s and scores, by track_gate_d2, every b whose first sighting
+//            is frame last + g: one d2 per candidate pair, no loop over the gap per pair.  d2_s[a * 32 + b], -1 for no candidate.
+//   pairs    pair p = a * 32 + b, four per thread: the association's msd loop over the `what` rows of a's last and b's first sighting,
+//            aff and the int64 profit, laid out as track_solve_wave reads them (column a, row b).
+//   links    wavefront 0 runs track_solve_wave, unchanged: lane a < 32 gets the row b linked behind track a.
+//   relabel  lane i follows parent to its root and, if it is a root, the children to the tail; every thread relabels stitch_id and
+//            copies the table rows from N on.
+// Float64 with contraction off, one writer per output element, no atomics.
+__global__ __launch_bounds__(TRACK_THREADS) void track_stitch_kernel(TrackStitchArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double gstate_s[TRACK_GS_DOUBLES * TRACK_MAXT];     // the predicted state of track a at the current step: its own column
+    __shared__ double d2_s[TRACK_MAXT * TRACK_MAXT], aff_s[TRACK_MAXT * TRACK_MAXT];
+    __shared__ long long profit_s[TRACK_MAXT * TRACK_MAXT];        // [column a][row b]
+    __shared__ float4 fwhere_s[TRACK_MAXT];                        // the `where` row of the first sighting
+    __shared__ int ff_s[TRACK_MAXT], fj_s[TRACK_MAXT], lf_s[TRACK_MAXT], lj_s[TRACK_MAXT];      // first / last sighting: frame (-1: none), slot
+    __shared__ int ostate_s[TRACK_MAXT], parent_s[TRACK_MAXT], child_s[TRACK_MAXT], root_s[TRACK_MAXT];
+    const int T = a.T, F = a.F, A = a.A, R = a.S * F, FT = F * T;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const size_t tab = (size_t)s * FT;
+    int N = a.num_tracks[s];
+    N = N < 0 ? 0 : N;
+    if (N <= TRACK_MAXT && N > FT) N = FT;                         // (no more ids than objects: the table rows end at F T)
+    if (N > TRACK_MAXT) {                                         // OVERFLOW (workgroup-uniform): bit copies, no link
+        for (int e = tid; e < FT; e += TRACK_THREADS) {
+            const int f = e / T, j = e - f * T;
+            const size_t row = (size_t)j * R + (size_t)s * F + f;
+            a.stitch_id[row] = a.track_id[row];
+            a.stitch_first[tab + e] = a.track_first[tab + e];
+            a.stitch_last[tab + e] = a.track_last[tab + e];
+            a.stitch_length[tab + e] = a.track_length[tab + e];
+            a.stitch_gaps[tab + e] = a.track_gaps[tab + e];
+        }
+        if (tid < TRACK_MAXT) {
+            const size_t at = (size_t)s * TRACK_MAXT + tid;
+            a.stitch_parent[at] = -1;
+            a.stitch_root[at] = tid;
+            a.stitch_d2[at] = 0.f;
+            a.stitch_affinity[at] = 0.f;
+        }
+        if (tid == 0) {
+            a.num_links[s] = 0;
+            a.stitch_status[s] = 1;
+        }
+        return;
+    }
+    for (int p = tid; p < TRACK_MAXT * TRACK_MAXT; p += TRACK_THREADS) d2_s[p] = -1.0;
+    // ---- filter: lane i = id i -----------------------------------------------------------------------------------------------------------
+    double x[4], v[4];
+    TrajCov P[2];
+    int lastf = -1;                                                // the frame of this lane's last sighting
+    const double q2[2] = {0.5 * a.q[0], 0.5 * a.q[1]}, q4[2] = {0.25 * a.q[0], 0.25 * a.q[1]};
+    if (tid < TRACK_MAXT) {
+        const int i = tid;
+        int ff = -1, fj = -1, lj = -1;
+        float4 fw = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x[c] = 0.0, v[c] = 0.0;
+        P[0].xx = P[1].xx = P[0].xv = P[1].xv = P[0].vv = P[1].vv = 0.0;
+        if (i < N) {
+            int f0 = a.track_first[tab + i], f1 = a.track_last[tab + i];
+            f0 = f0 < 0 ? 0 : (f0 > F - 1 ? F - 1 : f0);
+            f1 = f1 < 0 ? 0 : (f1 > F - 1 ? F - 1 : f1);
+            for (int f = f0; f <= f1; ++f) {
+                const size_t r = (size_t)s * F + f;
+                int j = 0;
+                while (j < T && a.track_id[(size_t)j * R + r] != i) ++j;
+                if (j == T) continue;                              // not sighted in this frame: predicted when the next sighting is booked
+                const float4 w4 = *reinterpret_cast<const float4 *>(a.where + 4 * ((size_t)j * R + r));
+                if (ff < 0) {                                      // start: x = z, v = 0, P = (r, 0, velocity_var)
+                    fw = w4;
+                    x[0] = (double)w4.x, x[1] = (double)w4.y, x[2] = (double)w4.z, x[3] = (double)w4.w;
+                    P[0].xx = P[1].xx = a.r;
+                    P[0].vv = P[1].vv = a.velocity_var;
+                    ff = f, fj = j;
+                } else {                                           // the frames coasted over one by one, then the update
+                    const double z[4] = {(double)w4.x, (double)w4.y, (double)w4.z, (double)w4.w};
+                    const int m = f - lastf;
+                    for (int i2 = 1; i2 < m; ++i2) {
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) P[c] = traj_predict_cov(P[c], a.q[c], q2[c], q4[c]);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) x[c] = x[c] + v[c];
+                    }
+                    TrajCov Pp[2];
+                    double xp[4], vp[4];
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) Pp[c] = traj_predict_cov(P[c], a.q[c], q2[c], q4[c]);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) xp[c] = x[c] + v[c], vp[c] = v[c];
+                    TRAJ_UPDATE(P, Pp, x, v, xp, vp, z, a.r)
+                }
+                lastf = f, lj = j;
+            }
+        }
+        ff_s[i] = ff, fj_s[i] = fj, lf_s[i] = lastf, lj_s[i] = lj;
+        fwhere_s[i] = fw;
+        ostate_s[i] = i < N ? TRACK_UNCONFIRMED : TRACK_ABSENT;
+        parent_s[i] = -1;
+    }
+    __syncthreads();
+    // ---- predict: lane a one frame at a time; at step g the b that begin in frame last + g -------------------------------------------------
+    if (tid < N && lastf >= 0) {                                   // (x, v, P: the filtered state at the last sighting)
+        const int k = tid;
+        int steps = F - 1 - lastf;
+        steps = steps > a.max_gap ? a.max_gap : steps;
+        double *gs = gstate_s + k;
+        for (int g = 1; g <= steps; ++g) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) P[c] = traj_predict_cov(P[c], a.q[c], q2[c], q4[c]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) x[c] = x[c] + v[c];
+            bool staged = false;
+            for (int b = 0; b < N; ++b) {
+                if (ff_s[b] != lastf + g) continue;
+                if (!staged) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) gs[(TRACK_GS_X + c) * TRACK_MAXT] = x[c];
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) gs[(TRACK_GS_S + c) * TRACK_MAXT] = P[c].xx + a.r;
+                    staged = true;
+                }
+                const double d2 = track_gate_d2(gstate_s, k, fwhere_s[b]);
+                d2_s[k * TRACK_MAXT + b] = d2 <= a.gate_d2 ? d2 : -1.0;      // (a NaN or an inf fails the gate)
+            }
+        }
+    }
+    __syncthreads();
+    // ---- pairs: msd, aff, profit -----------------------------------------------------------------------------------------------------------
+    for (int p = tid; p < TRACK_MAXT * TRACK_MAXT; p += TRACK_THREADS) {
+        const int k = p >> 5, b = p & 31;
+        const double d2 = d2_s[p];
+        double val = -1.0;
+        if (d2 >= 0.0) {
+            const float *wk = a.what + ((size_t)lj_s[k] * R + (size_t)s * F + lf_s[k]) * A;
+            const float *wj = a.what + ((size_t)fj_s[b] * R + (size_t)s * F + ff_s[b]) * A;
+            double sum = 0.0;
+            int q = 0;
+            for (; q + 8 <= A; q += 8) {                           // eight loads of each row in flight, added in ascending index
+                float xs[8], ys[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    xs[u] = wk[q + u];
+                    ys[u] = wj[q + u];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const double d = (double)xs[u] - (double)ys[u];
+                    sum = sum + d * d;
+                }
+            }
+            for (; q < A; ++q) {
+                const double d = (double)wk[q] - (double)wj[q];
+                sum = sum + d * d;
+            }
+            const double msd = sum / (double)A;
+            val = (1.0 - a.w) / (1.0 + d2) + a.w / (1.0 + msd);
+        }
+        const bool ok = val >= 0.0;                                // (a NaN aff takes no part)
+        aff_s[p] = val;
+        profit_s[p] = ok ? 1 + (long long)floor(val * 4294967296.0) : -1;      // (exact: a power of two)
+    }
+    __syncthreads();
+    // ---- links -------------------------------------------------------------------------------------------------------------------------------
+    if (tid < 64) {                                                // wavefront 0, every lane
+        const int b = track_solve_wave(profit_s, ostate_s, N, tid);
+        const bool linked = tid < TRACK_MAXT && b >= 0;
+        const unsigned long long links = __ballot(linked);
+        if (tid < TRACK_MAXT) child_s[tid] = linked ? b : -1;
+        if (linked) parent_s[b] = tid;                             // one column per row: one writer
+        if (tid == 0) {
+            a.num_links[s] = __popcll(links);
+            a.stitch_status[s] = 0;
+        }
+    }
+    __syncthreads();
+    // ---- relabel -----------------------------------------------------------------------------------------------------------------------------
+    if (tid < TRACK_MAXT) {
+        const int i = tid;
+        const size_t at = (size_t)s * TRACK_MAXT + i;
+        const int pa = parent_s[i];
+        int root = -1;
+        if (i < N) {
+            root = i;
+            for (int hop = 0; hop < TRACK_MAXT && parent_s[root] >= 0; ++hop) root = parent_s[root];
+        }
+        root_s[i] = root;
+        a.stitch_parent[at] = pa;
+        a.stitch_root[at] = root;
+        a.stitch_d2[at] = pa >= 0 ? (float)d2_s[pa * TRACK_MAXT + i] : 0.f;
+        a.stitch_affinity[at] = pa >= 0 ? (float)aff_s[pa * TRACK_MAXT + i] : 0.f;
+        if (i < N) {
+            int first = -1, last = -1, length = 0, gaps = 0;
+            if (pa < 0) {                                          // a root: down the chain to its tail
+                int c = i, links = 0;
+                first = a.track_first[tab + i];
+                for (int hop = 0; hop < TRACK_MAXT; ++hop) {
+                    length += a.track_length[tab + c];
+                    gaps += a.track_gaps[tab + c];
+                    last = a.track_last[tab + c];
+                    if (child_s[c] < 0) break;
+                    c = child_s[c];
+                    ++links;
+                }
+                gaps += links;
+            }
+            a.stitch_first[tab + i] = first;
+            a.stitch_last[tab + i] = last;
+            a.stitch_length[tab + i] = length;
+            a.stitch_gaps[tab + i] = gaps;
+        }
+    }
+    __syncthreads();
+    for (int e = N + tid; e < FT; e += TRACK_THREADS) {            // the rows from N on: copied
+        a.stitch_first[tab + e] = a.track_first[tab + e];
+        a.stitch_last[tab + e] = a.track_last[tab + e];
+        a.stitch_length[tab + e] = a.track_length[tab + e];
+        a.stitch_gaps[tab + e] = a.track_gaps[tab + e];
+    }
+    for (int e = tid; e < FT; e += TRACK_THREADS) {
+        const int f = e / T, j = e - f * T;
+        const size_t row = (size_t)j * R + (size_t)s * F + f;
+        const int id = a.track_id[row];
+        a.stitch_id[row] = (id >= 0 && id < N) ? root_s[id] : id;
+    }
+}
+
+extern "C" int air_track_stitch(const float *what, const float *where, const int *track_id, const int *num_tracks, const int *track_first,
+                                const int *track_last, const int *track_length, const int *track_gaps, int T, int S, int F, int R,
+                                int A, int max_gap, double gate_d2, double appearance_weight, double q_shift, double q_scale,
+                                double measurement_noise, double velocity_var, int *stitch_id, int *stitch_parent, int *stitch_root,
+                                float *stitch_d2, float *stitch_affinity, int *stitch_first, int *stitch_last, int *stitch_length,
+                                int *stitch_gaps, int *num_links, int *stitch_status, void *stream) {
+    AIR_REQUIRE(what && where && track_id && num_tracks && track_first && track_last && track_length && track_gaps && stitch_id &&
+                    stitch_parent && stitch_root && stitch_d2 && stitch_affinity && stitch_first && stitch_last && stitch_length &&
+                    stitch_gaps && num_links && stitch_status, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && S > 0 && F > 0 && A > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)F * T <= TRACK_MAX_IDS && (long)S * F == (long)R && (long)S * F * T <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(max_gap >= 1 && isfinite(gate_d2) && gate_d2 > 0.0, AIR_E_SHAPE);
+    AIR_REQUIRE(appearance_weight >= 0.0 && appearance_weight <= 1.0, AIR_E_SHAPE);
+    AIR_REQUIRE(traj_noise_check(q_shift, q_scale, measurement_noise, velocity_var) == AIR_OK, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(where), AIR_E_ALIGN);
+    AIR_REQUIRE(track_aligned4({what, track_id, num_tracks, track_first, track_last, track_length, track_gaps, stitch_id, stitch_parent,
+                                stitch_root, stitch_d2, stitch_affinity, stitch_first, stitch_last, stitch_length, stitch_gaps, num_links,
+                                stitch_status}), AIR_E_ALIGN);
+    TrackStitchArgs a = {what, where, track_id, num_tracks, track_first, track_last, track_length, track_gaps, stitch_id, stitch_parent,
+                         stitch_root, stitch_first, stitch_last, stitch_length, stitch_gaps, num_links, stitch_status, stitch_d2,
+                         stitch_affinity, gate_d2, appearance_weight, {q_shift, q_scale}, measurement_noise, velocity_var, T, S, F, A,
+                         max_gap};
+    hipLaunchKernelGGL(track_stitch_kernel, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

@@ -402,15 +402,17 @@ def make_tiled_parse_score_logger(air, data, num_batches, name, batch_size=None,
 def make_track_fig(frames, result, max_frames=8, checkpoint_dir=None, global_step=None, n_samples=4):
     """The tracks of sequences (AIRonMNIST.track / track.SequenceTracker.track): one row per sequence, one panel per frame (the first
     `max_frames`), the frame with the attention box of every object that has a track, coloured by track id (rect_stn on `where`); an
-    object without a track is drawn thin and white.  frames [S, F, H, W], result: the dict `track` returned.  Saved as
-    track_fig_<global_step>.png when a directory is given."""
+    object without a track is drawn thin and white.  frames [S, F, H, W], result: the dict `track` returned; a stitcher's result
+    (`track(stitch=...)`, track.TrackStitcher) is drawn with its STITCHED ids.  Saved as track_fig_<global_step>.png when a directory
+    is given."""
     import os.path as osp
     import matplotlib
     matplotlib.use('Agg')
     import matplotlib.pyplot as plt
     import torch
     host = lambda t: torch.as_tensor(t).detach().cpu().numpy()
-    x, ids, where, n = host(frames), host(result["track_id"]), host(result["where"]), host(result["num_objects"])
+    x, ids = host(frames), host(result["stitch_id"] if "stitch_id" in result else result["track_id"])
+    where, n = host(result["where"]), host(result["num_objects"])
     S, F, H, W = x.shape
     T = ids.shape[0]
     rows, cols = min(n_samples, S), min(int(max_frames), F)
@@ -489,7 +491,7 @@ def make_trajectory_fig(frames, result, max_frames=8, checkpoint_dir=None, globa
 def make_track_score_logger(air, data, num_batches, name, batch_size=None, writer=None, tau=0.5, measure_time=True, iou_gate=None,
                             appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None,
                             propose=None, temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None,
-                            hota=False):
+                            hota=False, stitch=None):
     """make_tiled_parse_score_logger's counterpart for sequences (air.score_track): `data` is an annotated dataset dict of SEQUENCES
     (imgs [N, F, H, W], boxes [N, F, G, 4], instances [N, F, H, W] int8 -- data.create_moving_mnist with return_annotations=True),
     walked in `num_batches` batches of `batch_size` sequences (None: the model's batch size).  Prints / writes the identity figures
@@ -504,7 +506,11 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
     smooth_idf1 of the completed table.  motion=True | dict: every track is matched against its predicted box (air.track's argument;
     the record holds the noise terms under `motion`).  motion_gate=True | D2 (with motion): the pairs are gated and ranked by their
     squared Mahalanobis distance (air.track's argument; the record holds the gate under `motion_gate`).  hota=True: HOTA beside MOTA
-    -- hota, deta, assa, loca (air_track_hota; means over the 19 thresholds), and with smooth= smooth_hota of the completed table."""
+    -- hota, deta, assa, loca (air_track_hota; means over the 19 thresholds), and with smooth= smooth_hota of the completed table.
+    stitch=True | MAX_GAP | dict (not with smooth=): the track fragments are joined across long occlusions (track.TrackStitcher,
+    air.track's argument) and the STITCHED ids are scored beside the tracker's own on the same parses: stitch_mota,
+    stitch_id_switches, stitch_links, with identity= stitch_idf1, with hota= stitch_hota and stitch_assa; the record holds max_gap and
+    the gate under `stitch`."""
     import torch
     from .track import STATES
     tk = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
@@ -521,6 +527,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
         tk["motion_gate"] = motion_gate
     if hota:
         tk["hota"] = True
+    if stitch is not None:
+        tk["stitch"] = stitch
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -533,11 +541,18 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
         states, issued = torch.zeros(6, dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
         repaired = torch.zeros((), dtype=torch.int64, device=dev)
         table_rows = torch.zeros(3, dtype=torch.int64, device=dev)
-        tracker = None
+        tracker = stitcher = None
+        links = torch.zeros((), dtype=torch.int64, device=dev)
         for i in range(n):
             sl = slice(i * S, (i + 1) * S)
             _, tracker = air.score_track(torch.as_tensor(data["imgs"][sl], dtype=torch.float32).to(dev), torch.as_tensor(data["boxes"][sl]),
                                          tau=tau, accumulate=i > 0, gt_instances=torch.as_tensor(data["instances"][sl]), **tk)
+            if stitch is not None:                                 # the stitcher was scored: the tracker's own ids beside it, same parses
+                stitcher, tracker = tracker, tracker.tracker
+                tracker.score(torch.as_tensor(data["boxes"][sl]), tau, i > 0, identity)
+                if hota:
+                    tracker.hota(torch.as_tensor(data["boxes"][sl]), i > 0)
+                links += air.tracked["num_links"].sum()
             states += air.tracked["state_counts"].sum(0)
             issued += air.tracked["num_tracks"].sum()
             if temporal is not None:
@@ -573,6 +588,17 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
             if smooth is not None:
                 acc["smooth_hota"] = air.track_smoother.hota_summary()["hota"]
                 shown += ["smooth_hota"]
+        if stitch is not None:
+            joined = stitcher.summary()
+            acc.update(stitch_mota=joined["mota"], stitch_id_switches=joined["id_switches"], stitch_links=int(links.item()))
+            shown += ["stitch_mota", "stitch_id_switches", "stitch_links"]
+            if identity:
+                acc["stitch_idf1"] = stitcher.identity_summary()["idf1"]
+                shown += ["stitch_idf1"]
+            if hota:
+                fig = stitcher.hota_summary()
+                acc.update(stitch_hota=fig["hota"], stitch_assa=fig["assa"])
+                shown += ["stitch_hota", "stitch_assa"]
         t = time.time() - start
         msg = 'Step {}, Data {} track score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:
@@ -588,6 +614,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
                 rec["motion"] = {k: list(v) if isinstance(v, tuple) else v for k, v in tracker.motion.items()}
             if motion_gate is not None:
                 rec["motion_gate"] = tracker.motion_gate
+            if stitch is not None:
+                rec["stitch"] = dict(max_gap=stitcher.max_gap, gate=stitcher.gate, appearance_weight=stitcher.appearance_weight)
             writer.write(json.dumps(rec) + "\n"); writer.flush()
         return acc
     return logger

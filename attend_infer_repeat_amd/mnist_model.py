@@ -464,6 +464,13 @@ class AIRonMNIST(AIRModel):
             raise ValueError("trajectory_smoother: smooth must be True or a dict of TrajectorySmoother's arguments, got %r" % (smooth,))
         return self._tracker_entry(self._track_key(n_sequences, n_frames, smooth=smooth, **track_args))[1]
 
+    def stitcher(self, n_sequences, n_frames, stitch=True, **track_args):
+        """the track.TrackStitcher behind `track(stitch=)`: last in the cached stack of `tracker(..., stitch=stitch)`, bound to that
+        stack's tracker (track fragments joined across occlusions longer than max_age; its defaults are provisional)"""
+        if stacks.stitch_spec(stitch) is None:
+            raise ValueError("stitcher: stitch must be True, a max_gap or a dict of TrackStitcher's arguments, got %r" % (stitch,))
+        return self._tracker_entry(self._track_key(n_sequences, n_frames, stitch=stitch, **track_args))[1]
+
     def _track_key(self, n_sequences, n_frames, **track_args):
         """the stacks.TrackKey of the track family's arguments (stacks.track_key names them: an unknown one is its TypeError)"""
         return stacks.track_key(stacks.require_engine(self, "track"), n_sequences, n_frames, **track_args)
@@ -488,10 +495,12 @@ class AIRonMNIST(AIRModel):
         argument; True | dict a tracker of its own that matches every track against its predicted box (track.py: MOTION; part of the
         key; with smooth=dict(...) motion=True takes the smoother's noise terms).  motion_gate=None is exactly the stack without the
         argument; True | a squared Mahalanobis distance a tracker of its own whose pairs are gated by the filter's covariance (track.py:
-        THE GATE; part of the key; it needs motion).  Built and captured on first use; the least
+        THE GATE; part of the key; it needs motion).  stitch=None is exactly the stack without the argument; True | MAX_GAP | dict a
+        stack of its own that ends in a track.TrackStitcher bound to the tracker (track.py: STITCHING; part of the key; refused with
+        smooth=) -- the second member of the pair is then that stitcher.  Built and captured on first use; the least
         recently used one is dropped, with its stack, when more than MAX_TRACKERS are alive (each owns an engine)."""
         stack = self._track_stack(key)
-        return (stack[-1], None) if key.smooth is None else (stack[-2], stack[-1])
+        return (stack[-1], None) if key.smooth is None and key.stitch is None else (stack[-2], stack[-1])
 
     def noise_fitter(self, n_sequences, n_frames, shift_ratios=None, scale_ratios=None, velocity_ratio=None, **track_args):
         """the trajectory.TrajectoryNoiseFitter behind `fit_track_noise`: last in a cached stack of its own (stacks.fit_key, in the
@@ -582,7 +591,7 @@ class AIRonMNIST(AIRModel):
                                                      lambda: stacks.captured(self._own_stack(S * F, spec, F)))[-1]
 
     def _track(self, frames, **track_args):
-        """`track` with its arguments by name; returns the (tracker, smoother | None) that ran"""
+        """`track` with its arguments by name; returns the (tracker, smoother | stitcher | None) that ran"""
         frames = torch.as_tensor(frames)
         if frames.dim() != 4:
             raise ValueError("track: frames [S, F, H, W], got shape %s" % (tuple(frames.shape),))
@@ -594,7 +603,7 @@ class AIRonMNIST(AIRModel):
         return tracker, smoother
 
     def track(self, frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None,
-              prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None, motion_gate=None):
+              prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None, motion_gate=None, stitch=None):
         """Parse the frames [S, F, H, W] of S sequences on the device, each frame as `parse(refine=, prune=, propose=)` would parse
         it -- with temporal=P | (P, rounds) followed by proposals from the neighbour frames (temporal.TemporalProposer) -- and give
         the objects identities over time (track.SequenceTracker.track lists the returned device tensors: the parse of
@@ -610,11 +619,16 @@ class AIRonMNIST(AIRModel):
         `m.track(frames, motion=noise, smooth=noise)` (motion=True with smooth=dict(...) takes the smoother's terms).
         motion_gate=True | D2 (with motion): the pairs are gated by their squared Mahalanobis distance from the filter's predicted
         state, D2 at most (True: track.MOTION_GATE_DEFAULT, provisional), and ranked by it instead of the IoU -- the fitted noise terms
-        and the gate then concern one quantity; pred_d2 comes on top; motion_gate=None is exactly the call without it.  The training
+        and the gate then concern one quantity; pred_d2 comes on top; motion_gate=None is exactly the call without it.
+        stitch=True | MAX_GAP | dict(max_gap=, gate=, appearance_weight=, process_noise=, measurement_noise=, velocity_var=): a second
+        pass joins a track that ended to one that began at most max_gap frames later when the first one's filter predicts the second
+        one's first sighting and their `what` codes agree, the links by one optimal assignment (track.py: STITCHING; stitch_id, the
+        stitch_ tables and stitch_owner come on top, the tracker's own outputs stay); stitch=None is exactly the call without it;
+        together with smooth= it is refused.  The training
         engine's parameters are read, nothing of it is written; `self.obs` and the parsers of `parse` are not touched."""
         self._track(frames, iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
                     refine_lr=refine_lr, prune=prune, propose=propose, temporal=temporal, smooth=smooth, matching=matching, motion=motion,
-                    motion_gate=motion_gate)
+                    motion_gate=motion_gate, stitch=stitch)
         return self.tracked
 
     def predict_frames(self, frames, horizon, smooth=True, **track_args):
@@ -631,7 +645,7 @@ class AIRonMNIST(AIRModel):
 
     def score_track(self, frames, gt_boxes, tau=0.5, accumulate=True, gt_instances=None, thresholds=None, iou_gate=None,
                     appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None,
-                    temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None, hota=False):
+                    temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None, hota=False, stitch=None):
         """`track`, then the identity metric of the tracks against gt_boxes [S, F, G, 4] (G <= 8; slot g is the same object in every
         frame of a sequence, width <= 0 = absent) on the device (track.SequenceTracker.score).  The sums accumulate in the tracker
         this returns alongside -- (scores, tracker): its summary() reads MOTA, MOTP, the identity switches and the mostly tracked /
@@ -645,10 +659,14 @@ class AIRonMNIST(AIRModel):
         and IDR back).  motion= and motion_gate= are `track`'s.  hota=True also runs air_track_hota (track.SequenceTracker.hota): scores[
         "hota"] holds the tracker's tensors and totals (seq_hota_i, seq_hota_f, the tables, totals_hota_i / totals_hota_f), with smooth=
         scores["completed"]["hota"] the completed table's; hota_summary() of the tracker / the smoother reads HOTA, DetA, AssA and LocA
-        back.  hota=False, the default: exactly the call without the argument."""
+        back.  hota=False, the default: exactly the call without the argument.  stitch= is `track`'s: the STITCHED ids are scored
+        (identity= and hota= included) by the track.TrackStitcher, which is then the stage returned alongside -- its summary() /
+        identity_summary() / hota_summary() / reset() are the stitched table's, the tracker's totals are not touched."""
         t, smoother = self._track(frames, iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age,
                                   refine=refine, refine_lr=refine_lr, prune=prune, propose=propose, temporal=temporal, smooth=smooth,
-                                  matching=matching, motion=motion, motion_gate=motion_gate)
+                                  matching=matching, motion=motion, motion_gate=motion_gate, stitch=stitch)
+        if stacks.stitch_spec(stitch) is not None:                  # (never with smooth=: the key refuses it)
+            t, smoother = smoother, None
         gb = torch.as_tensor(gt_boxes)
         scores = dict(t.score(gb, tau, accumulate, identity))
         if smoother is not None:

@@ -157,6 +157,13 @@ def main(argv=None):
                     help="with --track-eval: also report HOTA, DetA, AssA and LocA (air_track_hota: how well objects are found and how "
                          "well the matched detections are kept in one identity, over 19 localisation thresholds) beside MOTA; not with "
                          "--track-stream (HOTA is out of scope on a stream)")
+    ap.add_argument("--track-stitch", nargs="?", const="", default=None, metavar="MAX_GAP[,D2]",
+                    help="with --track-eval: join track fragments across occlusions longer than max_age (track.TrackStitcher: a track "
+                         "that ended is linked to one that began at most MAX_GAP frames later when its Kalman filter predicts the later "
+                         "one's first sighting within the squared Mahalanobis distance D2 and their what codes agree, one optimal "
+                         "assignment per sequence) and log the MOT, identity and HOTA figures of the stitched ids beside the tracker's "
+                         "own (stitch_mota, stitch_idf1, stitch_hota, ...): no value = MAX_GAP 8 and D2 13.2767 (both provisional); not "
+                         "with --track-stream or --track-smooth (out of scope there)")
     ap.add_argument("--track-stream", type=int, default=None, metavar="CHUNK",
                     help="with --track-eval: also run the same sequences through a STREAM in chunks of CHUNK frames (the last chunk "
                          "ragged; AIRonMNIST.track_stream, track.StreamTracker: the track table carried on the device between the chunks) "
@@ -249,6 +256,28 @@ def main(argv=None):
         ap.error("--track-hota goes with --track-eval")
     if args.track_hota and args.track_stream is not None:
         ap.error("--track-hota does not go with --track-stream (HOTA is out of scope on a stream)")
+    track_stitch = None
+    if args.track_stitch is not None:
+        if track_eval is None:
+            ap.error("--track-stitch goes with --track-eval")
+        if args.track_stream is not None:
+            ap.error("--track-stitch does not go with --track-stream (stitching is out of scope on a stream)")
+        if args.track_smooth is not None or args.track_predict is not None:
+            ap.error("--track-stitch does not go with --track-smooth or --track-predict (the smoother's completed table assumes "
+                     "tracks seen within max_age frames)")
+        try:
+            from attend_infer_repeat_amd.stacks import stitch_spec
+            parts = args.track_stitch.split(",") if args.track_stitch else []
+            if len(parts) > 2:
+                raise ValueError("at most two values")
+            track_stitch = dict(max_gap=int(parts[0])) if parts else {}
+            if len(parts) == 2:
+                track_stitch["gate"] = float(parts[1])
+            stitch_spec(track_stitch or True)
+            track_stitch = track_stitch or True
+        except ValueError as e:
+            ap.error("--track-stitch needs MAX_GAP[,D2] with an integer MAX_GAP >= 1 and a squared distance D2 > 0, or no value, got %r (%s)"
+                     % (args.track_stitch, e))
     if args.track_stream is not None:
         if track_eval is None:
             ap.error("--track-stream goes with --track-eval")
@@ -462,7 +491,8 @@ def main(argv=None):
         before_track_log = log
         track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
                                             smooth=track_smooth, matching=args.track_matching, identity=args.track_identity,
-                                            motion=track_motion, motion_gate=track_motion_gate, hota=args.track_hota, **refine_kw)
+                                            motion=track_motion, motion_gate=track_motion_gate, hota=args.track_hota, stitch=track_stitch,
+                                            **refine_kw)
 
         stream_log = None
         if args.track_stream is not None:

@@ -1,14 +1,15 @@
 """Where the stacks of post-parse stages behind AIRonMNIST.parse / parse_tiled / track are specified, built and cached: the normalised
 spec of a stack (`stack_spec`), the one builder (`build_stack`), the bounded cache and the single-slot holder of built and captured
-stages (`BoundedCache`, `slot`), the keys of the track family (`track_key`, `stream_key`, `stream_smoother_key`, `fit_key`) and the
+stages (`BoundedCache`, `slot`), the keys of the track family (`track_key`, `stitch_spec`, `stream_key`, `stream_smoother_key`, `fit_key`) and the
 builder of the stack behind one (`build_track_stack`).  Pure Python; the stage classes are imported where a stack is built.
 """
 from collections import namedtuple
 
 StackSpec = namedtuple("StackSpec", "refine lr prune propose temporal")     # int | None, (lr_what, lr_where) | None, the pruner's
 #                                                                             candidates | None, (P, rounds) | None, (P, rounds) | None
-TrackKey = namedtuple("TrackKey", "S F assoc stack smooth matching device motion motion_gate", defaults=(None, None))
-#   assoc, smooth, motion: sorted (name, value) pairs; smooth | None, motion | None; motion_gate: the float | None
+TrackKey = namedtuple("TrackKey", "S F assoc stack smooth matching device motion motion_gate stitch", defaults=(None, None, None))
+#   assoc, smooth, motion: sorted (name, value) pairs; smooth | None, motion | None; motion_gate: the float | None; stitch: None |
+#   (max_gap, gate, appearance_weight | None, sorted noise pairs | None) -- `stitch_spec`'s
 StreamKey = namedtuple("StreamKey", "S F assoc stack matching device stream")  # a track.StreamTracker's: stream is True (a key of its own)
 FitKey = namedtuple("FitKey", "S F assoc stack matching device fit motion motion_gate", defaults=(None, None))      # ... with a trajectory.
 #   TrajectoryNoiseFitter: the grids
@@ -70,15 +71,46 @@ def smooth_spec(smooth, stream=False):
     return spec
 
 
+STITCH_KEYS = ("max_gap", "gate", "appearance_weight", "process_noise", "measurement_noise", "velocity_var")
+
+
+def stitch_spec(stitch):
+    """stitch=None | False (off), True (the defaults), MAX_GAP (an integer) or a dict with any of STITCH_KEYS -> None | (max_gap, gate,
+    appearance_weight | None, sorted noise pairs | None), checked by track.check_stitch: appearance_weight None is the tracker's, noise
+    None the tracker's motion terms or trajectory.DEFAULTS (track.TrackStitcher's rule); noise terms given are completed by the defaults"""
+    from . import track as tr
+    if stitch is None or stitch is False:
+        return None
+    spec = {}
+    if isinstance(stitch, dict):
+        unknown = sorted(set(stitch) - set(STITCH_KEYS), key=str)
+        if unknown:
+            raise ValueError("stitch: unknown keys %r; it takes %s" % (unknown, ", ".join(STITCH_KEYS)))
+        spec = {k: v for k, v in stitch.items() if v is not None}
+    elif stitch is not True:
+        spec = dict(max_gap=stitch)
+    noise = {k: spec[k] for k in STITCH_KEYS[3:] if k in spec}
+    w = spec.get("appearance_weight")
+    max_gap, gate, _, terms = tr.check_stitch(spec.get("max_gap", tr.STITCH_MAX_GAP), spec.get("gate", True),
+                                              tr.DEFAULTS["appearance_weight"] if w is None else w, noise or None)
+    return (max_gap, gate, None if w is None else float(w), tuple(sorted(terms.items())) if noise else None)
+
+
 def track_key(eng, n_sequences, n_frames, iou_gate=None, appearance_weight=None, birth_score=None, max_age=None, refine=None,
-              refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None, motion_gate=None):
+              refine_lr=None, prune=None, propose=None, temporal=None, smooth=None, matching=None, motion=None, motion_gate=None,
+              stitch=None):
     """The arguments of the track family, normalised once and checked against the engine `eng` (track, temporal and trajectory
     check_arguments, before anything is built): None for an association argument is track.DEFAULTS, temporal=None, smooth=None,
     matching=None | "greedy" and motion=None give the very key of a call without the argument.  motion=True together with
     smooth=dict(...) takes the smoother's noise terms; an explicit motion=dict(...) wins.  motion_gate=None | False is the key of a call
-    without it, True is track.MOTION_GATE_DEFAULT, and a gate without motion is refused (track.check_motion_gate)."""
+    without it, True is track.MOTION_GATE_DEFAULT, and a gate without motion is refused (track.check_motion_gate).  stitch=None | False
+    is the key of a call without it; True | MAX_GAP | dict(...) (`stitch_spec`) asks for a track.TrackStitcher behind the tracker -- with
+    smooth= it is refused (track.STITCH_WITH_SMOOTH), with temporal=, a provider, it is not."""
     from . import track as tr
     stack = stack_spec(refine, refine_lr, prune, propose, temporal, who="track")
+    stitch = stitch_spec(stitch)
+    if stitch is not None and smooth_spec(smooth) is not None:
+        raise ValueError(tr.STITCH_WITH_SMOOTH)
     given = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age)
     assoc = {k: (tr.DEFAULTS[k] if v is None else v) for k, v in given.items()}
     S, F = int(n_sequences), int(n_frames)
@@ -101,7 +133,7 @@ def track_key(eng, n_sequences, n_frames, iou_gate=None, appearance_weight=None,
     if motion is not None:
         motion = tuple(sorted(motion.items()))
     assoc = {k: (int(v) if k == "max_age" else float(v)) for k, v in assoc.items()}
-    return TrackKey(S, F, tuple(sorted(assoc.items())), stack, smooth, matching, str(eng.device), motion, motion_gate)
+    return TrackKey(S, F, tuple(sorted(assoc.items())), stack, smooth, matching, str(eng.device), motion, motion_gate, stitch)
 
 
 def stream_key(eng, n_sequences, chunk_frames, motion=None, motion_gate=None, **track_args):
@@ -111,8 +143,9 @@ def stream_key(eng, n_sequences, chunk_frames, motion=None, motion_gate=None, **
     if (motion is not None and motion is not False) or (motion_gate is not None and motion_gate is not False):
         from .track import MOTION_ON_A_STREAM
         raise ValueError(MOTION_ON_A_STREAM)
-    if "smooth" in track_args:
-        raise TypeError("stream_key() got an unexpected keyword argument 'smooth'")
+    for name in ("smooth", "stitch"):
+        if name in track_args:
+            raise TypeError("stream_key() got an unexpected keyword argument %r" % name)
     k = track_key(eng, n_sequences, chunk_frames, **track_args)
     return StreamKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, True)
 
@@ -139,7 +172,9 @@ def fit_key(eng, n_sequences, n_frames, shift_ratios=None, scale_ratios=None, ve
     from .trajectory import check_fit_arguments
     if track_args.get("smooth") is not None:
         raise ValueError("fit_track_noise: the noise terms are fitted to the tracker's sightings; smooth= has no part in it")
-    k = track_key(eng, n_sequences, n_frames, **dict(track_args, smooth=None))
+    if track_args.get("stitch") not in (None, False):
+        raise ValueError("fit_track_noise: the noise terms are fitted to the tracker's sightings; stitch= has no part in it")
+    k = track_key(eng, n_sequences, n_frames, **dict(track_args, smooth=None, stitch=None))
     fit = check_fit_arguments(eng.cfg.max_steps, k.F, k.S * k.F, shift_ratios, scale_ratios, velocity_ratio)[3:]
     return FitKey(k.S, k.F, k.assoc, k.stack, k.matching, k.device, fit, k.motion, k.motion_gate)
 
@@ -174,11 +209,12 @@ def track_classes():
     return SequenceTracker, StreamTracker, TrajectorySmoother, StreamSmoother, TrajectoryNoiseFitter
 
 
-def build_track_stack(stack, key, classes=None):
+def build_track_stack(stack, key, classes=None, stitcher=None):
     """`stack` (a provider stack, `build_stack`'s) with what a key of the track family asks for behind it: a SequenceTracker (TrackKey,
     FitKey: with the key's motion and gate) or a StreamTracker (StreamKey, StreamSmoothKey) bound to its last member, then -- bound to
     that tracker -- a TrajectorySmoother (TrackKey with smooth), a StreamSmoother (StreamSmoothKey), a TrajectoryNoiseFitter (FitKey)
-    or nothing.  classes: the five constructors in that order (None: track_classes())."""
+    or nothing; a TrackKey with stitch: a track.TrackStitcher bound to the tracker (never with smooth: `track_key` refuses that).
+    classes: the five constructors in that order (None: track_classes()); stitcher: TrackStitcher's (None: the class)."""
     SequenceTracker, StreamTracker, Smoother, StreamSmoother, Fitter = track_classes() if classes is None else classes
     on_stream = isinstance(key, (StreamKey, StreamSmoothKey))
     rule = dict(key.assoc, matching=key.matching)
@@ -190,6 +226,11 @@ def build_track_stack(stack, key, classes=None):
         stack.append(Fitter(stack[-1], *key.fit))
     elif getattr(key, "smooth", None) is not None:
         stack.append((StreamSmoother if on_stream else Smoother)(stack[-1], **dict(key.smooth)))
+    elif getattr(key, "stitch", None) is not None:
+        if stitcher is None:
+            from .track import TrackStitcher as stitcher
+        max_gap, gate, w, noise = key.stitch
+        stack.append(stitcher(stack[-1], max_gap=max_gap, gate=gate, appearance_weight=w, noise=noise and dict(noise)))
     return stack
 
 

@@ -150,6 +150,52 @@ each other;  2. no epsilon at the thresholds: TrackEval counts sim >= alpha - ep
 stream (the tables are indexed by global id, as for IDF1), mask IoU, thresholds other than the 19, HOTA per class.  The HOTA of a
 trained model's tracks is unmeasured (profiles/track_hota.txt says what was measured: the cost of the launch).
 
+STITCHING (air_track_stitch; `reference_stitch` restates it; `TrackStitcher` runs it behind a SequenceTracker).  A track that coasts more
+than max_age frames is retired, and its object, when it comes back, is born again under a new id -- the split track that HOTA books
+as AssA 0.5 and IDF1 as a lost half.  Raising max_age does not repair it (32 live slots, a completed table that grows with max_age, a
+long-coasting track that takes the sightings of newborn ones).  Stitching is a second pass over WHOLE tracks, tracklet linking: a
+track that ended is joined to one that began later when the motion filter of the first predicts where the second begins and their
+`what` codes agree, the links chosen by ONE optimal assignment.  Inputs: the tracker's output (track_id, num_tracks, track_first,
+track_last, track_length, track_gaps) and the provider rows it read (what [T, R, A], where [T, R, 4]); max_gap (an integer >= 1,
+default 8), gate (a squared Mahalanobis distance, finite and > 0; True: MOTION_GATE_DEFAULT), appearance_weight w in [0, 1] and the
+four noise terms of the trajectory filter (None: trajectory.DEFAULTS; `check_motion` holds them to the smoother's supported domain).
+Each sequence s on its own, N = max(num_tracks[s], 0); N > 32 is OVERFLOW, below.
+  filter   for every id i < N the forward filter of the trajectory smoother over the sightings of track i in frame order, the frames
+           clip(track_first[i]) .. clip(track_last[i]) (clipped to 0 .. F - 1) walked one by one; track i is sighted in frame f at the
+           lowest slot j with track_id[j, s F + f] == i.  The first sighting starts the filter as a birth does (x = z, v = 0, P = (r,
+           0, velocity_var)); then `_motion_advance`'s statements: every frame without a sighting is predicted on its own, a sighting
+           is a predict and an update.  The state at the last sighting is trajectory._filter_step's forward pass bit for bit -- the
+           motion_state of `reference_associate_motion(return_state=True)` when the tracker ran with motion= and the same terms.  The
+           frames of a track's first and last sighting are those this walk found (on the tracker's own output: track_first and
+           track_last); an id without a sighting there takes no part.
+  pair     (a, b), both with sightings: g = first[b] - last[a]; a candidate iff 1 <= g <= max_gap -- hence a != b, and a chain runs
+           forward in time.  (xp, s) = `_motion_predicted_state(filt_a, g, q, r)`: the gate's statements with m := g, g predicts one
+           by one, never g v.  z = the `where` row of b's FIRST sighting widened to float64; d2 = `_motion_d2(xp, s, z)` in the order
+           [sx, tx, sy, ty]; msd = the association's mean squared difference (float64, ascending index, over A) of the `what` row of
+           a's LAST sighting and that of b's first.  Admissible iff d2 <= gate (a NaN or an inf fails), and then aff = (1 - w) / (1 +
+           d2) + w / (1 + msd) must be >= 0 (a NaN msd fails); profit = 1 + floor(aff 2^32).
+  links    the exact optimal assignment of `solve_assignment`, the association's solver and tie rule: rows the ids b < N ascending,
+           column a = track a, column 32 + b = "b keeps its id".  parent[b] = a for a matched pair, else -1.  TWO STATED
+           SIMPLIFICATIONS: b's link to a later c is scored with b's OWN filter, not with the filter of the merged chain a -> b; and
+           there is one pass, no iteration.
+  relabel  root[i] = the head of i's chain; stitch_id[j, r] = root[track_id[j, r]] for an id within 0 .. N - 1, any other value (-1)
+           stays.  A root's tables: first = the head's, last = the tail's, length = the sum over the chain, gaps = the sum over the
+           chain + the number of links (a link is a gap); an id merged away gets -1 / -1 / 0 / 0; the rows from N on are copied.  Ids
+           are NOT compacted: n_ids stays F T for the metrics.
+Outputs, every element written: stitch_id [T, R] int32; stitch_parent, stitch_root [S, 32] int32 (-1 from N on); stitch_d2,
+stitch_affinity [S, 32] fp32 (float32(d2) and float32(aff) of the link INTO b, 0 without one); stitch_first, stitch_last,
+stitch_length, stitch_gaps [S, F T]; num_links [S]; stitch_status [S]: 0 stitched, 1 OVERFLOW.  OVERFLOW (N > 32: the solver has 32
+columns): the sequence passes through -- ids and tables are bit copies, no link, parent -1 and root[i] = i for i < 32.  EXACT
+CONSEQUENCES:
+  1. with no admissible pair (a gate of 1e-300; max_gap below every gap) stitch_id and the four tables are the tracker's bit for bit.
+  2. stitching is idempotent on ids in ONE case only: stitching the stitched output (ids relabelled, tables as written) links nothing
+     new provided every chain had one link fewer than max_gap allows -- otherwise the merged track's own filter, which has seen both
+     halves, may reach a fragment the halves' filters did not.  Nothing more is claimed.
+Out of scope: a TrajectorySmoother behind a stitcher (its completed table assumes that a track spanning a frame was seen within max_age
+frames of it: trajectory.completed_rows), stitching on a stream, more than 32 tracks per sequence.  max_gap = 8 and the chi-squared
+gate are provisional like every other association default: UNMEASURED on a trained model (profiles/track_stitch.txt says what was
+measured: the cost of the launch).
+
 `SequenceTracker` owns no engine, like tile.TiledSceneParser and score.ParseScorer: it binds to a parse.SceneParser, refine.ParseRefiner,
 prune.ParsePruner, propose.ParseProposer or tile.TiledSceneParser at R = S F rows, runs that provider's own `parse()` on the frames and
 then, on the same engine stream, its own launch list of libair_hip.so entries (include/air_hip.h), ONE hipGraph after `capture()`
@@ -1035,6 +1081,159 @@ def hota_summary(totals_i, totals_f) -> Dict[str, object]:
     return out
 
 
+# ---- STITCHING: track fragments joined across long occlusions (the module text states the rule) -------------------------------------------
+STITCH_MAX_GAP = 8                 # max_gap's default (provisional)
+STITCHED, STITCH_OVERFLOW = 0, 1   # stitch_status
+STITCH_PER_TRACK = ("stitch_parent", "stitch_root", "stitch_d2", "stitch_affinity")                # [S, 32]
+STITCH_TABLES = ("stitch_first", "stitch_last", "stitch_length", "stitch_gaps")                    # [S, F T]
+STITCH_OUTPUTS = ("stitch_id",) + STITCH_PER_TRACK + STITCH_TABLES + ("num_links", "stitch_status")
+STITCH_ON_A_STREAM = ("stitching is out of scope on a stream: it is a second pass over the WHOLE tracks of a sequence, and a stream has "
+                      "only the chunk and the live table; track the sequence in one call and bind TrackStitcher to that SequenceTracker")
+STITCH_WITH_SMOOTH = ("stitch= together with smooth= is not supported: the smoother's completed table assumes that a track spanning a "
+                      "frame was seen within max_age frames of it (trajectory.completed_rows), which a stitched track is not")
+
+
+def check_stitch(max_gap=STITCH_MAX_GAP, gate=True, appearance_weight=DEFAULTS["appearance_weight"], noise=None):
+    """Refuse what air_track_stitch refuses of its rule arguments (pure host code).  noise: None (trajectory.DEFAULTS) or a dict with
+    any of process_noise, measurement_noise, velocity_var, held to the smoother's supported domain by `check_motion`.  Returns
+    (max_gap, gate, w, the complete noise dict)."""
+    if isinstance(max_gap, bool) or not isinstance(max_gap, int) and int(max_gap) != max_gap or int(max_gap) < 1:
+        raise ValueError("max_gap must be an integer >= 1, got %r" % (max_gap,))
+    if int(max_gap) > 2 ** 31 - 1:
+        raise ValueError("max_gap must fit int32, got %r" % (max_gap,))
+    if gate is None or gate is False:
+        raise ValueError("stitching needs a gate: True (MOTION_GATE_DEFAULT) or a finite squared Mahalanobis distance > 0, got %r" % (gate,))
+    gate = check_motion_gate(gate, True)
+    w = float(appearance_weight)
+    if not (math.isfinite(w) and 0.0 <= w <= 1.0):
+        raise ValueError("appearance_weight must be a number within [0, 1], got %r" % (appearance_weight,))
+    return int(max_gap), gate, w, check_motion(noise or True)
+
+
+def _stitch_ends(sightings_a, sightings_b):
+    """the pair's step: the sighting (frame, slot) of a whose `what` row enters the msd and from whose frame the gap is counted -- its
+    LAST --, and that of b whose `where` and `what` rows are compared -- its FIRST (a function of its own so that a test can plant
+    another rule)"""
+    return sightings_a[-1], sightings_b[0]
+
+
+def _stitch_gaps(gaps, links):
+    """relabel: the gaps of a root -- the chain's own and one per link"""
+    return gaps + links
+
+
+def reference_stitch(what, where, track_id, num_tracks, track_first, track_last, track_length, track_gaps, n_frames,
+                     max_gap=STITCH_MAX_GAP, gate=True, appearance_weight=DEFAULTS["appearance_weight"], process_noise=None,
+                     measurement_noise=None, velocity_var=None, return_state=False, return_margins=False):
+    """air_track_stitch restated in numpy float64 and `solve_assignment` (STITCHING in the module text).  what [T, R, A], where
+    [T, R, 4] fp32, track_id [T, R], num_tracks [S], track_first / _last / _length / _gaps [S, F T], R = S * n_frames.  Returns
+    STITCH_OUTPUTS: stitch_id [T, R] int32, stitch_parent, stitch_root [S, 32] int32, stitch_d2, stitch_affinity [S, 32] float32,
+    stitch_first, stitch_last, stitch_length, stitch_gaps [S, F T] int32, num_links, stitch_status [S] int32.  return_state=True adds
+    stitch_state: (s, id) -> the filtered state (x, v, Pxx, Pxv, Pvv) of the track's own filter at its last sighting, and
+    stitch_pairs: (s, a, b) -> (d2, msd, aff | None for an inadmissible pair) of every candidate pair, in float64;
+    return_margins=True adds gate_margin [S]: the smallest |d2 - gate| over the candidate pairs (inf without one)."""
+    import numpy as np
+    from .trajectory import _filter_start
+    terms = {k: v for k, v in dict(process_noise=process_noise, measurement_noise=measurement_noise, velocity_var=velocity_var).items()
+             if v is not None}
+    max_gap, gate, w, terms = check_stitch(max_gap, gate, appearance_weight, terms)
+    what, where = np.asarray(what, np.float32), np.asarray(where, np.float32)
+    ids = np.asarray(track_id).astype(np.int32)
+    T, R, A = what.shape
+    T, F, S = check_arguments(T, n_frames, R)
+    FT = F * T
+    if where.shape != (T, R, 4) or ids.shape != (T, R):
+        raise ValueError("where / track_id: expected %s and %s, got %s and %s" % ((T, R, 4), (T, R), where.shape, ids.shape))
+    tables = [np.asarray(t).astype(np.int32) for t in (track_first, track_last, track_length, track_gaps)]
+    num_tracks = np.asarray(num_tracks).astype(np.int64)
+    if num_tracks.shape != (S,) or any(t.shape != (S, FT) for t in tables):
+        raise ValueError("num_tracks [%d] and the four track tables [%d, %d] expected" % (S, S, FT))
+    (q_shift, q_scale), r, vv = terms["process_noise"], terms["measurement_noise"], terms["velocity_var"]
+    q = np.array([q_scale, q_shift, q_scale, q_shift], np.float64)
+    out = {"stitch_id": ids.copy(), "stitch_parent": np.full((S, MAX_SLOTS), -1, np.int32),
+           "stitch_root": np.full((S, MAX_SLOTS), -1, np.int32), "stitch_d2": np.zeros((S, MAX_SLOTS), np.float32),
+           "stitch_affinity": np.zeros((S, MAX_SLOTS), np.float32), "num_links": np.zeros(S, np.int32),
+           "stitch_status": np.zeros(S, np.int32)}
+    out.update({k: t.copy() for k, t in zip(STITCH_TABLES, tables)})
+    states, pairs, gate_margin = {}, {}, np.full(S, np.inf)
+    clip =lambda f: min(max(int(f), 0), F - 1)
+    for s in range(S):
+        N = max(int(num_tracks[s]), 0)
+        if N > MAX_SLOTS:                                          # OVERFLOW: the sequence passes through
+            out["stitch_status"][s] = STITCH_OVERFLOW
+            out["stitch_root"][s] = np.arange(MAX_SLOTS)
+            continue
+        N = min(N, FT)                                             # (no more ids than objects: the table rows end at F T)
+        first, last, length, gaps = (t[s] for t in tables)
+        sightings, filt = {}, {}
+        for i in range(N):                                         # filter: the track's own, over its sightings in frame order
+            seen, state, prev = [], None, None
+            for f in range(clip(first[i]), clip(last[i]) + 1):
+                hit = np.flatnonzero(ids[:, s * F + f] == i)
+                if not hit.size:
+                    continue
+                j = int(hit[0])
+                z = where[j, s * F + f].astype(np.float64)
+                with np.errstate(all="ignore"):
+                    state = _filter_start(z, r, vv) if state is None else _motion_advance(state, f - prev, z, q, r)
+                seen.append((f, j))
+                prev = f
+            if seen:
+                sightings[i], filt[i] = seen, state
+                states[(s, i)] = state
+        profit, admissible = np.zeros((N, MAX_SLOTS), np.int64), np.zeros((N, MAX_SLOTS), bool)
+        d2s, affs = {}, {}
+        for a in sightings:                                        # pair
+            for b in sightings:
+                (fa, ja), (fb, jb) = _stitch_ends(sightings[a], sightings[b])
+                g = fb - fa
+                if not 1 <= g <= max_gap:
+                    continue
+                with np.errstate(all="ignore"):
+                    xp, s_in = _motion_predicted_state(filt[a], g, q, r)
+                    d2 = float(_motion_d2(xp, s_in, where[jb, s * F + fb].astype(np.float64)))
+                    d = what[ja, s * F + fa].astype(np.float64) - what[jb, s * F + fb].astype(np.float64)
+                    msd = float(_sequential_sum(d * d) / np.float64(A))
+                    gate_margin[s] = min(gate_margin[s], abs(d2 - gate))
+                    v = _gated_pair(d2, msd, w, gate, None, None)
+                if v is not None and not v >= 0.0:
+                    v = None
+                pairs[(s, a, b)] = (d2, msd, v)
+                if v is None:
+                    continue
+                profit[b, a], admissible[b, a] = 1 + int(math.floor(v * PROFIT_SCALE)), True
+                d2s[(a, b)], affs[(a, b)] = d2, v
+        parent, child = out["stitch_parent"][s], {}
+        for b, a in enumerate(solve_assignment(profit, admissible)):       # links
+            if a >= 0:
+                parent[b], child[int(a)] = a, b
+                out["stitch_d2"][s, b], out["stitch_affinity"][s, b] = np.float32(d2s[(int(a), b)]), np.float32(affs[(int(a), b)])
+        out["num_links"][s] = len(child)
+        for i in range(N):                                         # relabel
+            root = i
+            while parent[root] >= 0:
+                root = int(parent[root])
+            out["stitch_root"][s, i] = root
+            if parent[i] >= 0:
+                for k, empty in zip(STITCH_TABLES, (-1, -1, 0, 0)):
+                    out[k][s, i] = empty
+                continue
+            tail, total, total_gaps, links = i, int(length[i]), int(gaps[i]), 0
+            while tail in child:
+                tail, links = child[tail], links + 1
+                total, total_gaps = total + int(length[tail]), total_gaps + int(gaps[tail])
+            out["stitch_last"][s, i], out["stitch_length"][s, i] = last[tail], total
+            out["stitch_gaps"][s, i] = _stitch_gaps(total_gaps, links)
+        cols = ids[:, s * F:(s + 1) * F]
+        inside = (cols >= 0) & (cols < N)
+        out["stitch_id"][:, s * F:(s + 1) * F] = np.where(inside, out["stitch_root"][s][np.where(inside, cols, 0)], cols)
+    if return_state:
+        out["stitch_state"], out["stitch_pairs"] = states, pairs
+    if return_margins:
+        out["gate_margin"] = gate_margin
+    return out
+
+
 # ---- the launch arguments by name ------------------------------------------------------------------------------------------------------
 # The parameters of every air_track_* entry this module launches, in the order of include/air_hip.h and without the trailing stream
 # (tests/test_track_optimal_host.py holds each tuple to the header's prototype).  A plan entry is the values filed under these names.
@@ -1674,3 +1873,110 @@ class StreamTracker(TrackerBase):
         """mot_summary of the stream so far: the cumulative seq_counts and seq_iou summed over the S sequences at read-back (ONE
         read-back; no totals are kept on the device).  Nothing scored yet: the figures of nothing (nan rates)."""
         return self.scores.stream_summary()
+
+
+# ---- stitching behind a tracker ------------------------------------------------------------------------------------------------------------
+# air_track_stitch's parameters in the order of include/air_hip.h, without the trailing stream (ENTRY_ARGS holds the entries the trackers
+# themselves launch)
+STITCH_ARGS = (("what", "where", "track_id", "num_tracks", "track_first", "track_last", "track_length", "track_gaps", "T", "S", "F", "R",
+                "A", "max_gap", "gate_d2", "appearance_weight", "q_shift", "q_scale", "measurement_noise", "velocity_var")
+               + STITCH_OUTPUTS)
+
+
+class TrackStitcher(BoundStage):
+    """Track fragments joined across occlusions longer than max_age (STITCHING in the module text), behind a SequenceTracker -- with or
+    without motion=, under either matching; a StreamTracker is refused (STITCH_ON_A_STREAM).  Binds to the tracker (what parameters and
+    switches are forwarded to) and only READS it and its provider: ONE hipGraph of two launches behind the tracker's own --
+    air_track_stitch on the tracker's ids and tables and the provider's what / where rows, then the unchanged air_track_owner on
+    stitch_id into a `track_owner` buffer of this stage.  appearance_weight=None: the tracker's; noise=None: the tracker's motion
+    terms if it has them, else trajectory.DEFAULTS; max_gap and gate (True: MOTION_GATE_DEFAULT) are provisional.  It owns an
+    IdentityScores over (T, F, the provider's boxes and counts, stitch_id): score / hota / summary / identity_summary / hota_summary /
+    reset are SequenceTracker's, on the stitched ids (n_ids stays F T: the ids are not compacted)."""
+
+    def __init__(self, tracker, max_gap=STITCH_MAX_GAP, gate=True, appearance_weight=None, noise=None):
+        if isinstance(tracker, StreamTracker):
+            raise ValueError(STITCH_ON_A_STREAM)
+        if not isinstance(tracker, SequenceTracker):
+            raise ValueError("TrackStitcher binds to a track.SequenceTracker, got %s" % type(tracker).__name__)
+        self.max_gap, self.gate, self.appearance_weight, self.noise = check_stitch(
+            max_gap, gate, tracker.appearance_weight if appearance_weight is None else appearance_weight,
+            tracker.motion if noise is None else noise)
+        import torch
+        from . import hip as H
+        self.tracker, self.provider, self.engine = tracker, tracker.provider, tracker.engine
+        self._bound = tracker
+        self.T, self.R, self.S, self.F, self.A, self.img_size = tracker.T, tracker.R, tracker.S, tracker.F, tracker.A, tuple(tracker.img_size)
+        self._rows = {k: tracker._rows[k] for k in ("what", "where")}
+        self._H = H
+        dev, S, FT = self.engine.device, self.S, self.F * self.T
+        z = lambda shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
+        with torch.cuda.device(dev):
+            self.stitch_id = z((self.T, self.R))
+            self.stitch_parent, self.stitch_root = z((S, MAX_SLOTS)), z((S, MAX_SLOTS))
+            self.stitch_d2, self.stitch_affinity = z((S, MAX_SLOTS), torch.float32), z((S, MAX_SLOTS), torch.float32)
+            self.stitch_first, self.stitch_last, self.stitch_length, self.stitch_gaps = z((S, FT)), z((S, FT)), z((S, FT)), z((S, FT))
+            self.num_links, self.stitch_status = z((S,)), z((S,))
+            self.track_owner = z((self.R,) + self.img_size, torch.int16)
+        self.scores = IdentityScores(self, S)
+        self._score = self.scores.entries
+        self.totals_i, self.totals_f, self.totals_idf = self.scores.totals_i, self.scores.totals_f, self.scores.totals_idf
+        self._rebuild()
+        self.engine.synchronize()
+
+    def _build_plan(self):
+        """nothing of the engine's configuration is held by the launch list: built once"""
+        tk, par, (Hi, Wi) = self.tracker, self.provider, self.img_size
+        L, p, m = self._H.lib(), self._H._p, self.noise
+        values = dict(what=p(self._rows["what"]), where=p(self._rows["where"]), T=self.T, S=self.S, F=self.F, R=self.R, A=self.A,
+                      max_gap=self.max_gap, gate_d2=self.gate, appearance_weight=self.appearance_weight, q_shift=m["process_noise"][0],
+                      q_scale=m["process_noise"][1], measurement_noise=m["measurement_noise"], velocity_var=m["velocity_var"],
+                      **{k: p(getattr(tk, k)) for k in ("track_id",) + _TABLES[:-1]}, **{k: p(getattr(self, k)) for k in STITCH_OUTPUTS})
+        owner = dict(owner=p(par.owner), track_id=p(self.stitch_id), T=self.T, R=self.R, H=Hi, W=Wi, track_owner=p(self.track_owner))
+        self.segments = OrderedDict([("stitch", [(L.air_track_stitch, tuple(values[n] for n in STITCH_ARGS), "air_track_stitch")]),
+                                     ("owner", [plan_entry(L, "air_track_owner", owner)])])
+        self._plan = [e for seg in self.segments.values() for e in seg]
+
+    def _score_entries(self):
+        return list(self._score.values()) + list(self.scores.hota_entries.values())
+
+    def _score_table(self):
+        """the table the metrics score: the provider's boxes and counts with the STITCHED ids"""
+        return (self.T, self.F, self.provider.boxes, self.provider.num_objects, self.stitch_id)
+
+    def launch_count(self) -> Dict[str, object]:
+        """entries of one `run()` behind the tracker's own (`tracker` holds that tracker's launch_count())"""
+        return {"tracker": self.tracker.launch_count(), "track_stitch": 1, "track_owner": 1}
+
+    # ---- stitching ------------------------------------------------------------------------------------------------------------------
+    def run(self, base=None):
+        """stitch the tracker's LATEST `track()`; `base` (that call's result) is passed through into the returned dict and, when
+        given, held to the buffers the launch list was built on.  The tracker's and the provider's buffers are only read.  Same
+        stream contract as SequenceTracker.track."""
+        eng = self.engine
+        if base is not None:
+            self.check_same_buffers(base, dict(what=self._rows["what"], where=self._rows["where"], track_id=self.tracker.track_id,
+                                               num_tracks=self.tracker.num_tracks), "stitcher", bound="tracker")
+        eng.wait_for_caller()
+        eng._replay_or_run(self._graph, self._plan)
+        eng.wait_for_engine()
+        return self.result(base)
+
+    def stitch(self, frames, *args, **kwargs):
+        """the bound tracker's `track(frames, ...)`, then `run()` on its result"""
+        return self.run(self.tracker.track(frames, *args, **kwargs))
+
+    track = stitch                                                 # (the name the model's `track` calls on the last stage of a stack)
+
+    def result(self, base=None):
+        """Device tensors that the NEXT call overwrites, next to `base` (the tracker's dict, untouched -- its track_id and track_owner
+        stay the tracker's): STITCH_OUTPUTS -- stitch_id [T, R] int32, stitch_parent, stitch_root [S, 32] int32, stitch_d2,
+        stitch_affinity [S, 32] fp32, stitch_first / _last / _length / _gaps [S, F T] int32, num_links, stitch_status [S] int32 -- and
+        stitch_owner [R, H, W] int16: air_track_owner of stitch_id (this stage's `track_owner`)."""
+        out = dict(base) if base is not None else {}
+        out.update({k: getattr(self, k) for k in STITCH_OUTPUTS}, stitch_owner=self.track_owner)
+        return out
+
+    # ---- the identity metrics: SequenceTracker's methods as they are, on this stage's table -------------------------------------------------
+    _score_entry, score, hota = SequenceTracker._score_entry, SequenceTracker.score, SequenceTracker.hota
+    summary, identity_summary, hota_summary = SequenceTracker.summary, SequenceTracker.identity_summary, SequenceTracker.hota_summary
+    reset = SequenceTracker.reset

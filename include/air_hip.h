@@ -1046,6 +1046,32 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *   host per threshold: DetA = tp / max(1, tp + fn + fp), AssA = ass / max(1, tp), LocA = loc / tp, HOTA = sqrt(DetA AssA).
  *   The limits and checks of air_track_idf, and S 19 G n_ids <= INT_MAX (AIR_E_SHAPE).  boxes / gt_boxes 16-byte, potential /
  *   seq_hota_f 8-byte, everything else 4-byte aligned (AIR_E_ALIGN).  No floating-point atomics, no traffic between workgroups.
+ * air_track_stitch: track fragments joined across occlusions longer than max_age (tracklet linking), one 256-thread workgroup per
+ *   sequence.  Inputs: what[T,R,A], where[T,R,4] (the provider's rows) and air_track_associate*'s track_id[T,R], num_tracks[S],
+ *   track_first / track_last / track_length / track_gaps [S, F T].  N = max(num_tracks[s], 0); N > 32: OVERFLOW, below; else N =
+ *   min(N, F T).  Float64 with contraction off, only + - * / and floor, in the order written here.
+ *   Filter: for every id i < N the tracker's own Kalman filter (air_track_associate_motion: start, predict, update) over the
+ *   sightings of track i, the frames clip(track_first[i]) .. clip(track_last[i]) (clipped to 0 .. F - 1) walked in order; the sighting
+ *   of frame f is the lowest slot j with track_id[j, s F + f] == i; the first sighting starts the filter (x = z, v = 0, P = (r, 0,
+ *   velocity_var)), a later one, m frames after the one before, is m - 1 predicts one by one, then a predict and the update with z =
+ *   its where row.  first[i] / last[i] = the frames of the first and last sighting found; an id without one takes no part.
+ *   Pair (a, b): g = first[b] - last[a]; a candidate iff 1 <= g <= max_gap.  The predicted state of a's filter g frames on, g predicts
+ *   one by one (never g v): xp[4], s = Pxx- + r per class; z = the where row of b's FIRST sighting; d2 = ((e0 e0 / s_scale + e1 e1 /
+ *   s_shift) + e2 e2 / s_scale) + e3 e3 / s_shift, e = z - xp over [sx, tx, sy, ty] (air_track_associate_motion_gated's); msd = the
+ *   association's mean squared difference of the what row of a's LAST sighting and that of b's first.  Admissible iff d2 <= gate_d2
+ *   (a NaN or an inf fails) and aff = (1 - w) / (1 + d2) + w / (1 + msd) >= 0 (a NaN fails); profit = 1 + (int64) floor(aff 2^32).
+ *   Links: the exact optimal assignment of air_track_associate_optimal's solver with its tie rule: rows the ids b < N ascending,
+ *   column a = track a, column 32 + b = b keeps its id.  parent[b] = a of a matched pair, else -1.  b's link to a later c uses b's OWN
+ *   filter, not that of the merged chain; one pass, no iteration.
+ *   Relabel: root[i] = the head of i's chain; stitch_id[j,r] = root[track_id[j,r]] for an id within 0 .. N - 1, any other value stays.
+ *   A root's rows: first = the head's, last = the tail's, length = the chain's sum, gaps = the chain's sum + its links; an id merged
+ *   away: -1 / -1 / 0 / 0; the rows from N on are copied.  Ids are not compacted.
+ *   Outputs, every element written: stitch_id[T,R]; stitch_parent / stitch_root [S,32] (-1 from N on); stitch_d2 / stitch_affinity
+ *   [S,32] fp32 (of the link INTO b, 0 without one); stitch_first / _last / _length / _gaps [S, F T]; num_links[S]; stitch_status[S]
+ *   (0 stitched, 1 OVERFLOW).  OVERFLOW: ids and tables are bit copies, no link, parent -1, root[i] = i for i < 32.
+ *   1 <= T <= 32, F T <= 32767, S F == R, max_gap >= 1, gate_d2 finite and > 0, 0 <= appearance_weight <= 1, the noise terms inside the
+ *   supported domain of air_track_smooth (AIR_E_SHAPE).  where 16-byte, everything else 4-byte aligned (AIR_E_ALIGN).  No
+ *   floating-point atomics, no traffic between workgroups, one writer per output element: the same bits run to run.
  * Streams.  A stream is S sequences fed in CHUNKS of F frames: a chunk carries valid[s] frames of sequence s, v = clip(valid[s], 0, F);
  *   rows s F + f with f < v are frames, the rows behind them are padding that is never read.  The global index of a frame is
  *   frames_seen[s] + f.  CHUNK INVARIANCE: a sequence fed in any chunking (ragged valid, valid = 0 included) gets the track_id,
@@ -1109,6 +1135,12 @@ AIR_ENGINE_API int air_track_idf(const float *boxes, const int *num_objects, con
 AIR_ENGINE_API int air_track_hota(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, int T, int G,
                     int S, int F, int R, int n_ids, double *potential, int *id_count, int *gt_count, int *matches, int *seq_hota_i,
                     double *seq_hota_f, void *stream);
+AIR_ENGINE_API int air_track_stitch(const float *what, const float *where, const int *track_id, const int *num_tracks,
+                    const int *track_first, const int *track_last, const int *track_length, const int *track_gaps, int T, int S,
+                    int F, int R, int A, int max_gap, double gate_d2, double appearance_weight, double q_shift, double q_scale,
+                    double measurement_noise, double velocity_var, int *stitch_id, int *stitch_parent, int *stitch_root,
+                    float *stitch_d2, float *stitch_affinity, int *stitch_first, int *stitch_last, int *stitch_length,
+                    int *stitch_gaps, int *num_links, int *stitch_status, void *stream);
 AIR_ENGINE_API int air_track_associate(const float *what, const float *boxes, const float *score, const int *num_objects, int T, int S,
                     int F, int R, int A, double iou_gate, double appearance_weight, double birth_score, int max_age,
                     int *track_id, signed char *obj_state, float *affinity, int *prev_frame, int *prev_slot, int *num_tracks,

@@ -52,6 +52,14 @@ track.reference_hota bit for bit, or the tool exits with an error.  Then the thr
 repeats of --iters back-to-back launches between two device events) and one launch at a time as the other modes time it; the ratios
 are reported; no bar on time.
 
+--stitch measures stitching (track.TrackStitcher: air_track_stitch, then air_track_owner on the stitched ids): for every F in --frames, at
+--rows provider rows, ONE captured SceneParser, a captured tracker (--matching, max_age 1) and a captured stitcher over it; the counts
+leave two frames in five empty, so the tracks die and are born again and the stitcher has fragments to join.  The device outputs of the
+first --stitch-check sequences must equal track.reference_stitch bit for bit, or the tool exits with an error.  Then the two captured
+graphs -- the tracker's tail (associate + owner) and the stitcher's (stitch + owner) -- are timed in turns in this process, and the
+three entries launched eagerly, in turns as well; the ratios are reported; no bar on time.  Last, the stitch launch alone with max_gap = 1
+and with a gate that admits nothing: where its time goes, by difference.
+
 Timing: a warm-up, then 5 repeats of --iters calls each between device events; the median repeat is reported with all repeats.  The
 provider and the tracked route alternate inside one process."""
 import argparse
@@ -472,6 +480,75 @@ def one_hota_length(args, F):
     return res
 
 
+def one_stitch_length(args, F):
+    """--stitch: the stitcher's captured graph beside the tracker's captured tail, on the tracks of one captured tracker"""
+    from attend_infer_repeat_amd import _lib, track
+    from attend_infer_repeat_amd.engine_config import EngineConfig
+    from attend_infer_repeat_amd.parse import SceneParser
+    cfg = EngineConfig()
+    R = args.rows
+    if R % F:
+        raise SystemExit("--rows %d is no multiple of %d frames" % (R, F))
+    S, T = R // F, int(cfg.max_steps)
+    ps = SceneParser(cfg, R, seed=0)
+    ps.capture()
+    tk = track.SequenceTracker(ps, F, birth_score=0.0, matching=args.matching)
+    tk.capture()
+    st = track.TrackStitcher(tk)
+    st.capture()
+    eng, dev = ps.engine, ps.engine.device
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    start = torch.rand(S, *cfg.img_size, generator=gen) * (torch.rand(S, *cfg.img_size, generator=gen) > 0.8)
+    frames = torch.stack([torch.roll(start, shifts=(f, f // 2), dims=(1, 2)) for f in range(F)], 1).contiguous().to(dev)
+    counts = torch.where((torch.arange(R, device=dev) % F) % 5 < 3, T, 0).to(torch.int32)      # two frames in five empty: the tracks die
+    out = st.stitch(frames, counts)
+    torch.cuda.synchronize()
+    host = lambda t: t.cpu().numpy()
+    n_seq = min(S, args.stitch_check)                              # the host reference walks these sequences
+    cols = slice(0, n_seq * F)
+    want = track.reference_stitch(host(out["what"]).reshape(T, R, -1)[:, cols], host(out["where"]).reshape(T, R, 4)[:, cols],
+                                  host(out["track_id"])[:, cols], host(out["num_tracks"])[:n_seq],
+                                  *[host(out[k])[:n_seq] for k in ("track_first", "track_last", "track_length", "track_gaps")], F,
+                                  appearance_weight=tk.appearance_weight)
+    same = lambda a, b: bool((np.ascontiguousarray(a).view(np.uint8) == np.ascontiguousarray(b).view(np.uint8)).all())
+    agree = {k: same(host(out[k])[:, cols] if k == "stitch_id" else host(out[k])[:n_seq], want[k]) for k in track.STITCH_OUTPUTS}
+    tracks, status = host(out["num_tracks"]), host(out["stitch_status"])
+    res = dict(frames=F, sequences=S, rows=R, max_steps=T, matching=args.matching, max_gap=st.max_gap, gate=st.gate,
+               sequences_checked=n_seq, agreement=agree, tracks=int(tracks.sum()), tracks_per_sequence_max=int(tracks.max()),
+               links=int(host(out["num_links"]).sum()), sequences_overflow=int((status == track.STITCH_OVERFLOW).sum()))
+    if not all(agree.values()):
+        print(json.dumps(res))
+        raise SystemExit("air_track_stitch and the host reference disagree: %r" % (agree,))
+    graphs = {"tail": tk, "stitch": st}
+    turns = {k: [] for k in graphs}
+    for _ in range(2):                                             # in turns, in this process
+        for name, g in graphs.items():
+            turns[name].append(median_ms(lambda: eng._replay_or_run(g._graph, g._plan), args.iters, eng.stream))
+    for name, v in turns.items():
+        res["%s_graph_turns_ms" % name] = [m for m, _ in v]
+        res["%s_graph_repeats_ms" % name] = [r for _, r in v]
+        res["%s_graph_ms" % name] = statistics.median(res["%s_graph_turns_ms" % name])
+    res["stitch_over_tail_graph"] = res["stitch_graph_ms"] / res["tail_graph_ms"]
+    plan = tk._plan + st._plan[:1]                                 # the association entry, air_track_owner, air_track_stitch
+    launch = lambda fn, a, name: _lib.check(fn(*a, eng._sp()), name)
+    eager = {name: [] for _, _, name in plan}
+    for _ in range(2):
+        for fn, a, name in plan:
+            eager[name].append(median_ms(lambda: launch(fn, a, name), args.iters, eng.stream))
+    res["eager_launch_us"] = {k: statistics.median([m for m, _ in v]) * 1e3 for k, v in eager.items()}
+    res["eager_launch_turns_us"] = {k: [m * 1e3 for m, _ in v] for k, v in eager.items()}
+    res["stitch_over_associate_eager"] = res["eager_launch_us"]["air_track_stitch"] / res["eager_launch_us"][tk._plan[0][2]]
+    # where the time goes: the same launch with a gate that admits nothing (the filter walk, the predicts, every d2, the relabel; no msd,
+    # and a solver whose rows take their own column at once) and with max_gap = 1 (hardly a candidate: the filter walk and the relabel)
+    fn, a, name = st._plan[0]
+    at_gap, at_gate = track.STITCH_ARGS.index("max_gap"), track.STITCH_ARGS.index("gate_d2")
+    for label, args_ in (("gate_1e-300", a[:at_gate] + (1e-300,) + a[at_gate + 1:]), ("max_gap_1", a[:at_gap] + (1,) + a[at_gap + 1:])):
+        res["eager_stitch_%s_us" % label] = median_ms(lambda: launch(fn, args_, name), args.iters, eng.stream)[0] * 1e3
+    launch(fn, a, name)                                            # (the outputs of the rule as configured are back)
+    st.release_graphs(); tk.release_graphs(); ps.release_graphs()
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 32])
@@ -485,9 +562,18 @@ def main(argv=None):
     ap.add_argument("--gate", action="store_true", help="with --motion: the Mahalanobis gate against the motion tracker without it")
     ap.add_argument("--hota", action="store_true", help="air_track_hota beside air_track_score and air_track_idf (eager and captured)")
     ap.add_argument("--hota-check", type=int, default=16, metavar="N", help="with --hota: the sequences the host reference walks")
+    ap.add_argument("--stitch", action="store_true", help="the stitcher's captured graph beside the tracker's captured tail")
+    ap.add_argument("--stitch-check", type=int, default=16, metavar="N", help="with --stitch: the sequences the host reference walks")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("track_bench measures on the GPU; there is no CPU fallback")
+    if args.stitch:
+        res = dict(tool="track_bench --stitch", device=torch.cuda.get_device_name(0), lengths=[one_stitch_length(args, F) for F in args.frames])
+        print(json.dumps(res))
+        for r in res["lengths"]:
+            for k, v in r.items():
+                print("F=%-4d %-34s %s" % (r["frames"], k, v))
+        return res
     if args.hota:
         res = dict(tool="track_bench --hota", device=torch.cuda.get_device_name(0), lengths=[one_hota_length(args, F) for F in args.frames])
         print(json.dumps(res))
