@@ -257,6 +257,7 @@ SIGNATURES = {
                                            ctypes.c_double, c_int, P, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "air_track_idf": (c_int, [P, P, P, P, ctypes.c_double, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "air_track_hota": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+    "air_track_mots": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     "air_track_stitch": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, P, P, P, P, P, P, P, P, P, P, P, P]),
     "air_track_owner": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),

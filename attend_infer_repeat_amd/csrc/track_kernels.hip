@@ -16,6 +16,8 @@
 //                        one-to-one sum over it, by dynamic programming over the subsets of slots.
 //   air_track_hota:      the HOTA counts of the same tracks at 19 localisation thresholds: two passes over the frames, the potential
 //                        table of every (slot, id) first, then one optimal matching per frame scored by it (the one-wavefront solver).
+//   air_track_mots:      the MOTS counts of the same tracks as MASKS: from the pixel counts air_score_contingency writes for (step
+//                        owner map, ground-truth instance map), mask IoU > 1/2 decided in int64, one wavefront per sequence;
 //   air_track_stitch:    track fragments joined across long occlusions: per track its own Kalman filter, per (ended, begun later)
 //                        pair the Mahalanobis distance of the later track's first sighting from the earlier one's prediction and the
 //                        msd of their `what` rows, one optimal assignment over the tracks (the one-wavefront solver), ids relabelled.
@@ -1416,6 +1418,145 @@ extern "C" int air_track_hota(const float *boxes, const int *num_objects, const 
     const TrackHotaArgs a = {boxes, gt_boxes, num_objects, track_id, potential, seq_hota_f, id_count, gt_count, matches, seq_hota_i,
                              T, G, S, F, n_ids};
     hipLaunchKernelGGL(track_hota_kernel, dim3((unsigned)S), dim3(TRACK_THREADS), 0, air_stream(stream), a);
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+// ============================================================================================================
+// mots
+// ============================================================================================================
+struct TrackMotsArgs {
+    const int *cont, *num_objects, *track_id;
+    int *seq_mots_i, *mots_match;
+    double *seq_mots_f;
+    float *mots_iou;
+    int T, G, S, F;
+};
+#define TRACK_MOTS_BINS ((TRACK_MAXT + 1) * (TRACK_MAXG + 1))      // 297 counts per frame at most
+#define TRACK_MOTS_LOADS ((TRACK_MOTS_BINS + 63) / 64)             // 5 per lane
+
+// what one lane holds of a frame between its loads and its turn: its share of the counts, the frame's count, step `lane`'s id
+struct TrackMotsFrame {
+    int c[TRACK_MOTS_LOADS];
+    int n, id;
+};
+__device__ __forceinline__ void track_mots_load(TrackMotsFrame &x, const TrackMotsArgs &a, int r, int R, int nb, int lane) {
+    const int *c = a.cont + (size_t)r * nb;
+#pragma unroll
+    for (int k = 0; k < TRACK_MOTS_LOADS; ++k) {
+        const int i = lane + 64 * k;
+        x.c[k] = i < nb ? c[i] : 0;
+    }
+    x.n = a.num_objects[r];
+    x.id = lane < a.T ? a.track_id[(size_t)lane * R + r] : -1;
+}
+
+// One workgroup of one wavefront per sequence, the frames walked in order.  A frame's (T+1)(G+1) counts go global -> registers -> LDS;
+// the loads of frame f + 1 are issued behind the barrier that publishes frame f, so they are in flight while f is booked.  Lane =
+// step j for the row sums and the match test (one ballot per slot), lane = slot g for map, tracked and present, which never leave
+// their lane's registers.  inter > union - inter decides in int64.  For a non-negative table at most one step qualifies per slot
+// and at most one slot per step (a match holds more than half of both areas), so taking the LOWEST qualifying step of a slot, as
+// the ballot does, is no tie rule: any search order gives the same matching.
+__global__ __launch_bounds__(64) void track_mots_kernel(TrackMotsArgs a) {
+#pragma clang fp contract(off)
+    __shared__ int cont_s[TRACK_MOTS_BINS];
+    __shared__ long long row_s[TRACK_MAXT];
+    __shared__ long long col_s[TRACK_MAXG];
+    __shared__ int id_s[TRACK_MAXT];
+    const int T = a.T, G = a.G, F = a.F, R = a.S * F, W = G + 1, nb = (T + 1) * W;
+    const int s = blockIdx.x, lane = threadIdx.x;
+    int map = -1, tracked = 0, frames = 0, switches = 0;           // lane g's
+    int n_gt = 0, n_tp = 0, n_fn = 0, n_fp = 0;                    // wave-uniform
+    double soft = 0.0;                                             // wave-uniform
+    TrackMotsFrame next;
+    track_mots_load(next, a, s * F, R, nb, lane);
+    for (int f = 0; f < F; ++f) {
+        const int r = s * F + f;
+#pragma unroll
+        for (int k = 0; k < TRACK_MOTS_LOADS; ++k) {
+            const int i = lane + 64 * k;
+            if (i < nb) cont_s[i] = next.c[k];
+        }
+        const int n = next.n < 0 ? 0 : (next.n > T ? T : next.n), id = next.id;
+        __syncthreads();
+        if (f + 1 < F) track_mots_load(next, a, r + 1, R, nb, lane);
+        long long row = 0, col = 0;
+        if (lane < T)
+            for (int b = 0; b < W; ++b) row += (long long)cont_s[(lane + 1) * W + b];
+        if (lane < G)
+            for (int o = 0; o <= T; ++o) col += (long long)cont_s[o * W + lane + 1];
+        const bool hyp = lane < n && id >= 0 && row > 0;
+        if (lane < TRACK_MAXT) {
+            row_s[lane] = row;
+            id_s[lane] = id;
+        }
+        if (lane < TRACK_MAXG) col_s[lane] = col;
+        __syncthreads();
+        // ---- the match test: lane j against every present slot -----------------------------------------------------------------------------
+        bool taken = false;
+        int mine = -1;                                             // lane g: the step matched to slot g
+#pragma unroll
+        for (int g = 0; g < TRACK_MAXG; ++g) {
+            bool q = false;
+            if (g < G && hyp) {
+                const long long cg = col_s[g];
+                if (cg > 0) {
+                    const long long inter = (long long)cont_s[(lane + 1) * W + g + 1], uni = row + cg - inter;
+                    q = inter > uni - inter;
+                }
+            }
+            const unsigned long long m = __ballot(q);
+            const int j = m ? __ffsll(m) - 1 : -1;
+            taken = taken || (q && lane == j);
+            if (lane == g) mine = j;
+        }
+        // ---- booking: lane g ---------------------------------------------------------------------------------------------------------------
+        const bool here = lane < G && col > 0, hit = here && mine >= 0;
+        double iou = 0.0;
+        if (hit) {
+            const long long inter = (long long)cont_s[(mine + 1) * W + lane + 1], uni = row_s[mine] + col - inter;
+            iou = (double)inter / (double)uni;
+            const int idj = id_s[mine];
+            switches += (map >= 0 && map != idj) ? 1 : 0;
+            map = idj;
+            tracked += 1;
+        }
+        frames += here ? 1 : 0;
+        if (lane < G) {
+            a.mots_match[(size_t)r * G + lane] = hit ? mine : -1;
+            a.mots_iou[(size_t)r * G + lane] = (float)iou;
+        }
+#pragma unroll
+        for (int g = 0; g < TRACK_MAXG; ++g) soft = soft + __shfl(iou, g, 64);      // g order; an unmatched slot adds +0: no change of bits
+        const int hits = __popcll(__ballot(hit)), there = __popcll(__ballot(here));
+        n_gt += there;
+        n_tp += hits;
+        n_fn += there - hits;
+        n_fp += __popcll(__ballot(hyp && !taken));
+        __syncthreads();                                           // the next frame overwrites the counts
+    }
+    const bool object = lane < G && frames > 0;
+    const int objects = __popcll(__ballot(object));
+    const int mt = __popcll(__ballot(object && 5ll * tracked >= 4ll * frames));
+    const int ml = __popcll(__ballot(object && 5ll * tracked <= (long long)frames));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) switches += __shfl_xor(switches, off, 64);
+    if (lane == 0) {
+        int *c = a.seq_mots_i + (size_t)s * 8;
+        c[0] = n_gt, c[1] = n_tp, c[2] = n_fn, c[3] = n_fp, c[4] = switches, c[5] = mt, c[6] = ml, c[7] = objects;
+        a.seq_mots_f[s] = soft;
+    }
+}
+
+extern "C" int air_track_mots(const int *cont, const int *num_objects, const int *track_id, int T, int G, int S, int F, int R,
+                              int *seq_mots_i, double *seq_mots_f, int *mots_match, float *mots_iou, void *stream) {
+    AIR_REQUIRE(cont && num_objects && track_id && seq_mots_i && seq_mots_f && mots_match && mots_iou, AIR_E_NULL);
+    AIR_REQUIRE(T >= 1 && T <= TRACK_MAXT && G >= 1 && G <= TRACK_MAXG && S > 0 && F > 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)S * F == (long)R && (long)R * (T + 1) * (G + 1) <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE((reinterpret_cast<uintptr_t>(seq_mots_f) & 7u) == 0, AIR_E_ALIGN);
+    AIR_REQUIRE(track_aligned4({cont, num_objects, track_id, seq_mots_i, mots_match, mots_iou}), AIR_E_ALIGN);
+    const TrackMotsArgs a = {cont, num_objects, track_id, seq_mots_i, mots_match, seq_mots_f, mots_iou, T, G, S, F};
+    hipLaunchKernelGGL(track_mots_kernel, dim3((unsigned)S), dim3(64), 0, air_stream(stream), a);
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

@@ -491,7 +491,7 @@ def make_trajectory_fig(frames, result, max_frames=8, checkpoint_dir=None, globa
 def make_track_score_logger(air, data, num_batches, name, batch_size=None, writer=None, tau=0.5, measure_time=True, iou_gate=None,
                             appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None,
                             propose=None, temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None,
-                            hota=False, stitch=None):
+                            hota=False, stitch=None, mots=False):
     """make_tiled_parse_score_logger's counterpart for sequences (air.score_track): `data` is an annotated dataset dict of SEQUENCES
     (imgs [N, F, H, W], boxes [N, F, G, 4], instances [N, F, H, W] int8 -- data.create_moving_mnist with return_annotations=True),
     walked in `num_batches` batches of `batch_size` sequences (None: the model's batch size).  Prints / writes the identity figures
@@ -510,7 +510,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
     stitch=True | MAX_GAP | dict (not with smooth=): the track fragments are joined across long occlusions (track.TrackStitcher,
     air.track's argument) and the STITCHED ids are scored beside the tracker's own on the same parses: stitch_mota,
     stitch_id_switches, stitch_links, with identity= stitch_idf1, with hota= stitch_hota and stitch_assa; the record holds max_gap and
-    the gate under `stitch`."""
+    the gate under `stitch`.  mots=True: the tracks scored as MASKS beside MOTA -- motsa, smotsa, motsp (air_track_mots on the owner
+    map and data["instances"]), with smooth= smooth_smotsa of the completed table, with stitch= stitch_smotsa of the stitched ids."""
     import torch
     from .track import STATES
     tk = dict(iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age, refine=refine,
@@ -529,6 +530,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
         tk["hota"] = True
     if stitch is not None:
         tk["stitch"] = stitch
+    if mots:
+        tk["mots"] = True
 
     def logger(itr=0, num_batches_to_eval=None, write=True):
         n = num_batches if num_batches_to_eval is None else num_batches_to_eval
@@ -552,6 +555,8 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
                 tracker.score(torch.as_tensor(data["boxes"][sl]), tau, i > 0, identity)
                 if hota:
                     tracker.hota(torch.as_tensor(data["boxes"][sl]), i > 0)
+                if mots:
+                    tracker.mots(torch.as_tensor(data["instances"][sl]), int(data["boxes"].shape[-2]), i > 0)
                 links += air.tracked["num_links"].sum()
             states += air.tracked["state_counts"].sum(0)
             issued += air.tracked["num_tracks"].sum()
@@ -588,6 +593,13 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
             if smooth is not None:
                 acc["smooth_hota"] = air.track_smoother.hota_summary()["hota"]
                 shown += ["smooth_hota"]
+        if mots:
+            fig = tracker.mots_summary()
+            acc.update({k: fig[k] for k in ("motsa", "smotsa", "motsp")})
+            shown[2:2] = ["motsa", "smotsa", "motsp"]
+            if smooth is not None:
+                acc["smooth_smotsa"] = air.track_smoother.mots_summary()["smotsa"]
+                shown += ["smooth_smotsa"]
         if stitch is not None:
             joined = stitcher.summary()
             acc.update(stitch_mota=joined["mota"], stitch_id_switches=joined["id_switches"], stitch_links=int(links.item()))
@@ -599,6 +611,9 @@ def make_track_score_logger(air, data, num_batches, name, batch_size=None, write
                 fig = stitcher.hota_summary()
                 acc.update(stitch_hota=fig["hota"], stitch_assa=fig["assa"])
                 shown += ["stitch_hota", "stitch_assa"]
+            if mots:
+                acc["stitch_smotsa"] = stitcher.mots_summary()["smotsa"]
+                shown += ["stitch_smotsa"]
         t = time.time() - start
         msg = 'Step {}, Data {} track score '.format(itr, name) + ', '.join('{} = {:.4f}'.format(k, acc[k]) for k in shown)
         if measure_time:

@@ -645,7 +645,8 @@ class AIRonMNIST(AIRModel):
 
     def score_track(self, frames, gt_boxes, tau=0.5, accumulate=True, gt_instances=None, thresholds=None, iou_gate=None,
                     appearance_weight=None, birth_score=None, max_age=None, refine=None, refine_lr=None, prune=None, propose=None,
-                    temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None, hota=False, stitch=None):
+                    temporal=None, smooth=None, matching=None, identity=False, motion=None, motion_gate=None, hota=False, stitch=None,
+                    mots=False):
         """`track`, then the identity metric of the tracks against gt_boxes [S, F, G, 4] (G <= 8; slot g is the same object in every
         frame of a sequence, width <= 0 = absent) on the device (track.SequenceTracker.score).  The sums accumulate in the tracker
         this returns alongside -- (scores, tracker): its summary() reads MOTA, MOTP, the identity switches and the mostly tracked /
@@ -661,7 +662,15 @@ class AIRonMNIST(AIRModel):
         scores["completed"]["hota"] the completed table's; hota_summary() of the tracker / the smoother reads HOTA, DetA, AssA and LocA
         back.  hota=False, the default: exactly the call without the argument.  stitch= is `track`'s: the STITCHED ids are scored
         (identity= and hota= included) by the track.TrackStitcher, which is then the stage returned alongside -- its summary() /
-        identity_summary() / hota_summary() / reset() are the stitched table's, the tracker's totals are not touched."""
+        identity_summary() / hota_summary() / reset() are the stitched table's, the tracker's totals are not touched.  mots=True (needs
+        gt_instances) also scores the tracks as MASKS (track.SequenceTracker.mots: air_score_contingency of the owner map and the
+        instance maps, then air_track_mots, with G slots as in gt_boxes): scores["mots"] holds the stage's tensors and totals
+        (seq_mots_i, seq_mots_f, mots_match, mots_iou, cont, totals_mots_i / totals_mots_f), with smooth= scores["completed"]["mots"]
+        the completed table's, with stitch= the stitched ids are scored; mots_summary() of the stage reads MOTSA, sMOTSA and MOTSP
+        back.  mots=False, the default: exactly the call without the argument."""
+        if mots and gt_instances is None:
+            from .track import MOTS_NEEDS_INSTANCES
+            raise ValueError(MOTS_NEEDS_INSTANCES)
         t, smoother = self._track(frames, iou_gate=iou_gate, appearance_weight=appearance_weight, birth_score=birth_score, max_age=max_age,
                                   refine=refine, refine_lr=refine_lr, prune=prune, propose=propose, temporal=temporal, smooth=smooth,
                                   matching=matching, motion=motion, motion_gate=motion_gate, stitch=stitch)
@@ -681,6 +690,10 @@ class AIRonMNIST(AIRModel):
             s = self._scorer("track_scorer", t.provider, G, thresholds)
             gi = torch.as_tensor(gt_instances)
             scores["detection"] = s.score(gi.reshape((t.R,) + tuple(gi.shape[-2:])), gb.reshape(t.R, G, 4), accumulate=accumulate)
+            if mots:
+                scores["mots"] = t.mots(gi, G, accumulate)
+                if smoother is not None:
+                    scores["completed"] = dict(scores["completed"], mots=smoother.mots(gi, G, accumulate))
         self.track_scores = scores
         return scores, t
 

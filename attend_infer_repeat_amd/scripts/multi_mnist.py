@@ -157,6 +157,10 @@ def main(argv=None):
                     help="with --track-eval: also report HOTA, DetA, AssA and LocA (air_track_hota: how well objects are found and how "
                          "well the matched detections are kept in one identity, over 19 localisation thresholds) beside MOTA; not with "
                          "--track-stream (HOTA is out of scope on a stream)")
+    ap.add_argument("--track-mots", action="store_true",
+                    help="with --track-eval: also report MOTSA, sMOTSA and MOTSP (air_track_mots: the tracks scored as MASKS -- the "
+                         "owner map against the instance maps, mask IoU > 1/2 decided in integers) beside MOTA; not with --track-stream "
+                         "(MOTS is out of scope on a stream)")
     ap.add_argument("--track-stitch", nargs="?", const="", default=None, metavar="MAX_GAP[,D2]",
                     help="with --track-eval: join track fragments across occlusions longer than max_age (track.TrackStitcher: a track "
                          "that ended is linked to one that began at most MAX_GAP frames later when its Kalman filter predicts the later "
@@ -256,6 +260,10 @@ def main(argv=None):
         ap.error("--track-hota goes with --track-eval")
     if args.track_hota and args.track_stream is not None:
         ap.error("--track-hota does not go with --track-stream (HOTA is out of scope on a stream)")
+    if args.track_mots and track_eval is None:
+        ap.error("--track-mots goes with --track-eval")
+    if args.track_mots and args.track_stream is not None:
+        ap.error("--track-mots does not go with --track-stream (MOTS is out of scope on a stream)")
     track_stitch = None
     if args.track_stitch is not None:
         if track_eval is None:
@@ -492,7 +500,7 @@ def main(argv=None):
         track_log = make_track_score_logger(air, seq_data, args.eval_batches, 'test', sequences_per_batch, writer, temporal=track_temporal,
                                             smooth=track_smooth, matching=args.track_matching, identity=args.track_identity,
                                             motion=track_motion, motion_gate=track_motion_gate, hota=args.track_hota, stitch=track_stitch,
-                                            **refine_kw)
+                                            mots=args.track_mots, **refine_kw)
 
         stream_log = None
         if args.track_stream is not None:

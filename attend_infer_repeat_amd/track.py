@@ -147,8 +147,36 @@ figures are the means over the 19 thresholds; nan for every figure when there wa
 DEPARTURES from TrackEval: 1. the matching score A sim is quantised to 2^-32 (and 1 is added) for an exact integer solver with a stated
 tie rule, where TrackEval hands floats to scipy's solver: the two can differ only where two assignments lie within 2^-32 per pair of
 each other;  2. no epsilon at the thresholds: TrackEval counts sim >= alpha - eps, this rule sim >= alpha.  Out of scope: HOTA on a
-stream (the tables are indexed by global id, as for IDF1), mask IoU, thresholds other than the 19, HOTA per class.  The HOTA of a
-trained model's tracks is unmeasured (profiles/track_hota.txt says what was measured: the cost of the launch).
+stream (the tables are indexed by global id, as for IDF1), a mask similarity inside HOTA (MOTS, below, is where masks are scored),
+thresholds other than the 19, HOTA per class.  The HOTA of a trained model's tracks is unmeasured (profiles/track_hota.txt says what
+was measured: the cost of the launch).
+
+MOTS (air_track_mots; Voigtlaender et al., CVPR 2019: MOTSA, sMOTSA, MOTSP -- the tracks scored as MASKS).  Objects overlap, the
+renderer decides who owns a pixel, and the owner map records that decision; a box metric cannot see whether it was right.  Inputs:
+cont [R, T+1, G+1] int32 exactly as air_score_contingency writes it for (the step owner map, the ground-truth instance map) --
+cont[r, a, b] = the pixels with owner + 1 == a and gt + 1 == b; `mots_contingency` restates it --, num_objects [R] and the table's id
+column track_id [T, R] (the tracker's, the stitcher's stitch_id, the smoother's completed ids).  Boxes are not read.  Per frame, every
+sum in int64:  row[j] = sum_b cont[r, j+1, b], the hypothesis area;  col[g] = sum_a cont[r, a, g+1], the ground-truth area, the pixels
+owned by the background and by steps that are no hypothesis included.  Hypotheses: the steps j < clip(num_objects[r], 0, T) with
+track_id[j, r] >= 0 and row[j] > 0 -- a step without a track, or without a single pixel of its own, is neither a match nor a false
+positive.  Slot g is present iff col[g] > 0.  For a present g and a hypothesis j:  inter = cont[r, j+1, g+1], union = row[j] + col[g] -
+inter;  they match iff inter > union - inter: mask IoU > 1/2 with no float and no 2 inter that could overflow.  Within a frame the
+hypothesis masks are disjoint and the ground-truth masks are disjoint, so for a non-negative table at most one j qualifies per g and
+at most one g per j (a match holds more than half of both areas): the search order cannot change the result -- no Hungarian solver,
+no tie rule, no threshold sweep, and NO tau argument, because uniqueness rests on the 1/2.  (Stated for completeness: the lowest
+qualifying j of a slot is taken, and a hypothesis is unmatched iff no slot took it.)  For every matched (g, j) in ascending g:  tp +=
+1;  soft += float64(inter) / float64(union), summed in frame order, then g order;  ids += (map[g] exists and != id_j), then map[g] =
+id_j;  tracked[g] += 1.  map[g] is none at the start of a sequence and persists while g is unmatched or absent (step 3 of the
+identity metric above; the paper's latest tracked predecessor).  gt += present g, fn += present unmatched g, fp += unmatched
+hypotheses, present[g] += 1 per present g.  Outputs, every element written by one writer: seq_mots_i [S, 8] int32 (MOTS_COUNTS: gt,
+tp, fn, fp, ids, mostly tracked (5 tracked[g] >= 4 present[g]), mostly lost (5 tracked[g] <= present[g]), gt objects -- the last
+three over g with present[g] > 0), seq_mots_f [S] float64 = soft, mots_match [R, G] int32 (the matched step, -1 otherwise), mots_iou
+[R, G] fp32 (the quotient rounded once, 0 otherwise).  `mots_summary`, on the host after one read-back: MOTSA = (tp - fp - ids) / gt,
+sMOTSA = (soft - fp - ids) / gt, MOTSP = soft / tp, recall = tp / gt, precision = tp / (tp + fp), the mostly tracked / lost fractions;
+a denominator of 0 gives nan.  Out of scope: MOTS on a stream (StreamTracker's carried score state has a fixed layout), ignore
+regions, thresholds other than 1/2, a mask similarity inside HOTA or IDF1, sharing the contingency with a ParseScorer bound to the
+same provider.  What sMOTSA a TRAINED model's tracks reach is unmeasured (profiles/track_mots.txt says what was measured: the cost
+of the two launches).
 
 STITCHING (air_track_stitch; `reference_stitch` restates it; `TrackStitcher` runs it behind a SequenceTracker).  A track that coasts more
 than max_age frames is retired, and its object, when it comes back, is born again under a new id -- the split track that HOTA books
@@ -223,7 +251,8 @@ tracks retired in a chunk come as a list (ascending retirement frame, then slot)
 the ids 0..32766 (track_owner is int16); a birth beyond is OVERFLOW.  The metric continues across chunks: map[g], tracked[g],
 present[g], the counters and sum_iou are carried, seq_counts and seq_iou are cumulative.  Out of scope on a stream: IDF1 (its overlap
 table is indexed by global id: 1 MB per sequence at 32767 ids), HOTA (its tables are indexed by global id too, 19 thresholds deep:
-StreamTracker has no `hota`), ids beyond 32766 without `reset`, more than 32 live tracks.  Trajectories
+StreamTracker has no `hota`), MOTS (the carried score state has a fixed layout: StreamTracker has no `mots`), ids beyond 32766
+without `reset`, more than 32 live tracks.  Trajectories
 on a stream are trajectory.StreamSmoother's: fixed-lag smoothed rows `lag` frames late and a forecast per chunk.  `reference_associate_stream` / `reference_score_stream` restate a chunk in numpy
 with the per-frame code of the one-shot references.
 
@@ -251,6 +280,9 @@ HOTA_ALPHAS = tuple(k / 20.0 for k in range(1, 20))               # the 19 local
 HOTA_COUNTS = ("tp", "fn", "fp")                                   # seq_hota_i [S, 19, 3]
 HOTA_SUMS = ("ass", "ass_re", "ass_pr", "loc")                     # seq_hota_f [S, 19, 4]
 HOTA_EPS = 2.0 ** -52                                              # pass 1 adds sim / d only where d > HOTA_EPS
+MOTS_COUNTS = ("gt", "tp", "fn", "fp", "ids", "mostly_tracked", "mostly_lost", "gt_objects")      # seq_mots_i [S, 8]
+MOTS_OUTPUTS = ("seq_mots_i", "seq_mots_f", "mots_match", "mots_iou")
+MOTS_NEEDS_INSTANCES = "mots=True scores the tracks as masks: it needs gt_instances [S, F, H, W] (int8, -1 = background)"
 MATCHINGS = ("greedy", "optimal")
 PROFIT_SCALE = 4294967296.0        # 2^32: profit = 1 + floor(aff * 2^32)
 DEFAULTS = dict(iou_gate=0.1, appearance_weight=0.25, birth_score=0.5, max_age=1)
@@ -1081,6 +1113,116 @@ def hota_summary(totals_i, totals_f) -> Dict[str, object]:
     return out
 
 
+# ---- MOTS: the tracks scored as masks (the module text states the rule) ----------------------------------------------------------------------
+def mots_contingency(owner, gt_instances, T, G):
+    """air_score_contingency restated in numpy: owner and gt_instances [R, H, W] (or [S, F, H, W]) integer maps, -1 = background ->
+    cont [R, T+1, G+1] int32, cont[r, a, b] = the pixels of image r with owner + 1 == a and gt + 1 == b.  A pixel whose owner + 1 is
+    outside 0..T or whose gt + 1 is outside 0..G is counted nowhere."""
+    import numpy as np
+    T, G = int(T), int(G)
+    if not 1 <= T <= MAX_SLOTS or not 1 <= G <= MAX_GT:
+        raise ValueError("mots_contingency: T within 1..%d and G within 1..%d, got %d and %d" % (MAX_SLOTS, MAX_GT, T, G))
+    o, g = np.asarray(owner), np.asarray(gt_instances)
+    if o.shape != g.shape or o.ndim not in (3, 4):
+        raise ValueError("mots_contingency: two maps [R, H, W] (or [S, F, H, W]) of one shape, got %s and %s" % (o.shape, g.shape))
+    R = int(np.prod(o.shape[:-2]))
+    a, b = o.reshape(R, -1).astype(np.int64) + 1, g.reshape(R, -1).astype(np.int64) + 1
+    inside = (a >= 0) & (a <= T) & (b >= 0) & (b <= G)
+    nb = (T + 1) * (G + 1)
+    flat = (np.arange(R, dtype=np.int64)[:, None] * nb + a * (G + 1) + b)[inside]
+    return np.bincount(flat, minlength=R * nb).astype(np.int32).reshape(R, T + 1, G + 1)
+
+
+def _mots_gt_area(counts, g):
+    """col[g]: the area of ground-truth slot g, over EVERY owner row -- the background's and those of steps that are no hypothesis
+    included (a function of its own so that a test can plant another rule)"""
+    return sum(int(v) for v in counts[:, g + 1])
+
+
+def _mots_is_match(inter, union):
+    """mask IoU > 1/2, strictly, in integers (a function of its own so that a test can plant another rule)"""
+    return inter > union - inter
+
+
+def reference_mots(cont, num_objects, track_id, n_frames):
+    """air_track_mots restated in Python integers and numpy float64, with the kernel's bits (MOTS in the module text).  cont
+    [R, T+1, G+1] (mots_contingency's, or air_score_contingency's), num_objects [R], track_id [T, R], R = S * n_frames.  Returns
+    seq_mots_i [S, 8] int32 (MOTS_COUNTS), seq_mots_f [S] float64, mots_match [R, G] int32, mots_iou [R, G] float32."""
+    import numpy as np
+    cont = np.asarray(cont)
+    if cont.ndim != 3 or not np.issubdtype(cont.dtype, np.integer):
+        raise ValueError("reference_mots: cont must be an integer table [R, T+1, G+1], got %s %s" % (cont.shape, cont.dtype))
+    R, T, G, F = int(cont.shape[0]), int(cont.shape[1]) - 1, int(cont.shape[2]) - 1, int(n_frames)
+    if not 1 <= T <= MAX_SLOTS:
+        raise ValueError("reference_mots: 1..%d objects per frame, got %d" % (MAX_SLOTS, T))
+    if not 1 <= G <= MAX_GT:
+        raise ValueError("reference_mots: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+    if F < 1 or R < 1 or R % F:
+        raise ValueError("reference_mots: %d rows are not sequences of %d frames" % (R, F))
+    if R * (T + 1) * (G + 1) > 2 ** 31 - 1:
+        raise ValueError("reference_mots: cont [%d, %d, %d] would have more than 2^31 - 1 elements" % (R, T + 1, G + 1))
+    ids, n_in = np.asarray(track_id).astype(np.int64), np.asarray(num_objects).astype(np.int64).reshape(-1)
+    if ids.shape != (T, R) or n_in.shape != (R,):
+        raise ValueError("reference_mots: expected track_id [%d, %d] and num_objects [%d], got %s and %s"
+                         % (T, R, R, ids.shape, n_in.shape))
+    S = R // F
+    out = {"seq_mots_i": np.zeros((S, 8), np.int32), "seq_mots_f": np.zeros(S, np.float64),
+           "mots_match": np.full((R, G), -1, np.int32), "mots_iou": np.zeros((R, G), np.float32)}
+    for s in range(S):
+        remembered, tracked, present = [-1] * G, [0] * G, [0] * G
+        c = dict.fromkeys(MOTS_COUNTS, 0)
+        soft = np.float64(0.0)
+        for f in range(F):
+            r = s * F + f
+            counts = cont[r]
+            n = int(min(max(n_in[r], 0), T))
+            row = [sum(int(v) for v in counts[j + 1]) for j in range(T)]
+            col = [_mots_gt_area(counts, g) for g in range(G)]
+            hyp = [j for j in range(n) if ids[j, r] >= 0 and row[j] > 0]
+            taken = set()
+            for g in range(G):
+                if not col[g] > 0:
+                    continue
+                c["gt"] += 1
+                present[g] += 1
+                pairs = [(j, int(counts[j + 1, g + 1])) for j in hyp]
+                pairs = [(j, inter) for j, inter in pairs if _mots_is_match(inter, row[j] + col[g] - inter)]
+                if not pairs:
+                    c["fn"] += 1
+                    continue
+                j, inter = pairs[0]                                # (at most one on a non-negative table)
+                taken.add(j)
+                with np.errstate(all="ignore"):
+                    iou = np.float64(inter) / np.float64(row[j] + col[g] - inter)
+                c["tp"] += 1
+                tracked[g] += 1
+                soft = soft + iou
+                c["ids"] += 1 if remembered[g] >= 0 and remembered[g] != ids[j, r] else 0
+                remembered[g] = int(ids[j, r])
+                out["mots_match"][r, g], out["mots_iou"][r, g] = j, np.float32(iou)
+            c["fp"] += len(set(hyp) - taken)
+        _score_objects(c, tracked, present)
+        out["seq_mots_i"][s] = [c[k] for k in MOTS_COUNTS]
+        out["seq_mots_f"][s] = soft
+    return out
+
+
+def mots_summary(totals_i, soft) -> Dict[str, float]:
+    """the MOTS figures of summed seq_mots_i rows (MOTS_COUNTS order) and the summed seq_mots_f: motsa = (tp - fp - ids) / gt, smotsa =
+    (soft - fp - ids) / gt, motsp = soft / tp, recall = tp / gt, precision = tp / (tp + fp), mostly_tracked and mostly_lost (fractions
+    of the ground-truth objects), and the counts; a denominator of 0 gives nan"""
+    c = dict(zip(MOTS_COUNTS, (int(v) for v in totals_i)))
+    if len(c) != len(MOTS_COUNTS):
+        raise ValueError("mots_summary: expected the %d counters %s" % (len(MOTS_COUNTS), ", ".join(MOTS_COUNTS)))
+    soft = float(soft)
+    div = lambda a, b: a / b if b else float("nan")
+    return {"motsa": div(c["tp"] - c["fp"] - c["ids"], c["gt"]), "smotsa": div(soft - c["fp"] - c["ids"], c["gt"]),
+            "motsp": div(soft, c["tp"]), "recall": div(c["tp"], c["gt"]), "precision": div(c["tp"], c["tp"] + c["fp"]),
+            "mostly_tracked": div(c["mostly_tracked"], c["gt_objects"]), "mostly_lost": div(c["mostly_lost"], c["gt_objects"]),
+            "id_switches": c["ids"], "false_positives": c["fp"], "misses": c["fn"], "gt": c["gt"], "tp": c["tp"],
+            "gt_objects": c["gt_objects"], "soft": soft}
+
+
 # ---- STITCHING: track fragments joined across long occlusions (the module text states the rule) -------------------------------------------
 STITCH_MAX_GAP = 8                 # max_gap's default (provisional)
 STITCHED, STITCH_OVERFLOW = 0, 1   # stitch_status
@@ -1260,6 +1402,11 @@ ENTRY_ARGS = {
 ENTRY_ARGS["air_track_associate_optimal"] = ENTRY_ARGS["air_track_associate"]
 
 
+# air_track_mots' parameters in the same way.  It is no key of ENTRY_ARGS: that table is held to the ten entries above by
+# tests/test_track_optimal_host.py, as air_track_stitch's tuple (STITCH_ARGS) stands beside it for the same reason.
+MOTS_ARGS = ("cont", "num_objects", "track_id") + _SCORE_SHAPE + MOTS_OUTPUTS
+
+
 def plan_entry(L, name, values):
     """the plan entry of air_track_* `name`: values[n] of every parameter n of its prototype, in the prototype's order"""
     return (getattr(L, name), tuple(values[n] for n in ENTRY_ARGS[name]), name)
@@ -1270,9 +1417,12 @@ class IdentityScores:
     key used so far with its buffers and graph (`entries`, at most four: a sweep over tau must not pile up buffers and graphs), the
     staging copy of the ground truth, and the running totals on the device.  An entry made with identity=True runs air_track_idf
     behind air_track_score (one graph still) and feeds `totals_idf`.  HOTA has a cache of its own (`hota_entries`, at most two, keyed
-    by (table, G): the air_track_hota launch, its buffers and graph) and totals of its own (`totals_hota_i`, `totals_hota_f`).  A
-    stage on a STREAM holds one entry, air_track_score_stream's (`stream_entry`), and keeps no totals: its counts are cumulative.
-    A TABLE is what a launch scores: (T rows, frames per sequence, boxes, counts, ids)."""
+    by (table, G): the air_track_hota launch, its buffers and graph) and totals of its own (`totals_hota_i`, `totals_hota_f`).  So
+    has MOTS (`mots_entries`, at most two, keyed by (table, G): the unchanged air_score_contingency and air_track_mots as one plan and
+    one graph, the int8 staging copy of the instance maps, cont and the four outputs; `totals_mots_i`, `totals_mots_f`); a MOTS table
+    is (T rows, frames per sequence, owner map, counts, ids).  A stage on a STREAM holds one entry, air_track_score_stream's
+    (`stream_entry`), and keeps no totals: its counts are cumulative.  A TABLE is what a launch scores: (T rows, frames per
+    sequence, boxes, counts, ids)."""
 
     def __init__(self, stage, S):
         import torch
@@ -1284,7 +1434,10 @@ class IdentityScores:
             self.totals_idf = torch.zeros((4,), dtype=torch.int64, device=dev)
             self.totals_hota_i = torch.zeros((len(HOTA_ALPHAS), 3), dtype=torch.int64, device=dev)
             self.totals_hota_f = torch.zeros((len(HOTA_ALPHAS), 4), dtype=torch.float64, device=dev)
+            self.totals_mots_i = torch.zeros((8,), dtype=torch.int64, device=dev)
+            self.totals_mots_f = torch.zeros((1,), dtype=torch.float64, device=dev)
         self.hota_entries = {}                                     # (table, G) -> buffers, plan, graph: at most two, apart from `entries`
+        self.mots_entries = {}                                     # (table, G) -> buffers, plan, graph: at most two, apart from both
 
     # ---- the cache ------------------------------------------------------------------------------------------------------------------
     def _cached(self, cache, limit, key, build):
@@ -1458,6 +1611,59 @@ class IdentityScores:
         self.engine.wait_for_engine()
         return out
 
+    def mots_entry(self, key, G, table):
+        """the MOTS plan on `table` = (T rows, frames per sequence, owner map [N, H, W] int8, counts, ids): the unchanged
+        air_score_contingency of (owner map, the staged instance maps), then air_track_mots, with their buffers -- gt_instances
+        [N, H, W] int8, cont [N, T+1, G+1], seq_mots_i, seq_mots_f, mots_match, mots_iou -- kept in `mots_entries` under key + (G,);
+        captured (ONE graph of both launches) when the stage holds a graph.  `entries`, `hota_entries` and their keys are not touched."""
+        import torch
+        T, n_frames, owner, counts, ids = table
+        S, N, G = self.S, self.S * n_frames, int(G)
+
+        def build():
+            if not 1 <= G <= MAX_GT:
+                raise ValueError("mots: 1..%d ground-truth slots, got %d" % (MAX_GT, G))
+            if owner.dtype != torch.int8 or owner.dim() != 3 or owner.shape[0] != N:
+                raise ValueError("mots: the owner map must be int8 [%d, H, W], got %s %s" % (N, owner.dtype, tuple(owner.shape)))
+            Hi, Wi = (int(v) for v in owner.shape[1:])
+            i32, L, p = torch.int32, self.stage._H.lib(), self.stage._H._p
+            entry = self._zeros(gt_instances=((N, Hi, Wi), torch.int8), cont=((N, T + 1, G + 1), i32), seq_mots_i=((S, 8), i32),
+                                seq_mots_f=((S,), torch.float64), mots_match=((N, G), i32), mots_iou=((N, G), torch.float32))
+            values = {k: p(v) for k, v in entry.items() if k != "graph"}
+            values.update(num_objects=p(counts), track_id=p(ids), T=T, G=G, S=S, F=n_frames, R=N)
+            entry["plan"] = [(L.air_score_contingency, (p(owner), values["gt_instances"], T, G, N, Hi, Wi, values["cont"]),
+                              "air_score_contingency"),
+                             (L.air_track_mots, tuple(values[k] for k in MOTS_ARGS), "air_track_mots")]
+            return entry
+        return self._cached(self.mots_entries, 2, key + (G,), build)
+
+    def run_mots(self, gt_instances, key, G, table, accumulate=None):
+        """stage gt_instances [N, H, W] or [S, n_frames, H, W] (integers, -1 = background; a label from G on is counted nowhere) into
+        the buffers of `mots_entry(key, G, table)`, issue it and return its outputs and cont; accumulate True / False: added to /
+        restarting totals_mots_i [8] int64 and totals_mots_f [1] float64 on the device (no read-back), and they"""
+        import torch
+        eng, shape = self.engine, (self.S * table[1],) + tuple(int(v) for v in table[2].shape[1:])
+        gi = torch.as_tensor(gt_instances)
+        if gi.dim() not in (3, 4) or tuple(gi.shape[-2:]) != shape[1:] or gi.numel() != shape[0] * shape[1] * shape[2]:
+            raise ValueError("gt_instances: expected [%d, %d, %d] or [%d, %d, %d, %d], got %s"
+                             % (shape + (self.S, table[1]) + shape[1:] + (tuple(gi.shape),)))
+        entry = self.mots_entry(key, G, table)
+        eng.wait_for_caller()
+        with torch.cuda.stream(eng.stream):
+            entry["gt_instances"].copy_(gi.reshape(shape), non_blocking=True)
+        if gi.is_cuda:
+            gi.record_stream(eng.stream)
+        eng._replay_or_run(entry["graph"], entry["plan"])
+        out = {k: entry[k] for k in MOTS_OUTPUTS + ("cont",)}
+        if accumulate is not None:
+            out.update(self._accumulate(accumulate, entry, totals_mots_i="seq_mots_i", totals_mots_f="seq_mots_f"))
+        eng.wait_for_engine()
+        return out
+
+    def score_entries(self):
+        """every {"plan", "graph"} entry of the three caches: what a stage captures and releases with its own graph"""
+        return list(self.entries.values()) + list(self.hota_entries.values()) + list(self.mots_entries.values())
+
     def reset(self):
         """zero the totals"""
         import torch
@@ -1469,6 +1675,8 @@ class IdentityScores:
             self.totals_idf.zero_()
             self.totals_hota_i.zero_()
             self.totals_hota_f.zero_()
+            self.totals_mots_i.zero_()
+            self.totals_mots_f.zero_()
         eng.wait_for_engine()
 
     def summary(self) -> Dict[str, float]:
@@ -1491,6 +1699,14 @@ class IdentityScores:
         flat = torch.cat([self.totals_hota_i.double().reshape(-1), self.totals_hota_f.reshape(-1)]).tolist()
         return hota_summary([[int(v) for v in flat[3 * a:3 * a + 3]] for a in range(NA)],
                             [flat[3 * NA + 4 * a:3 * NA + 4 * a + 4] for a in range(NA)])
+
+
+    def mots_summary(self) -> Dict[str, float]:
+        """mots_summary of everything `mots` took since the last reset (ONE read-back)"""
+        import torch
+        self.engine.wait_for_engine()
+        flat = torch.cat([self.totals_mots_i.double(), self.totals_mots_f]).tolist()
+        return mots_summary(flat[:8], flat[8])
 
 
 class TrackerBase(BoundStage):
@@ -1554,7 +1770,7 @@ class TrackerBase(BoundStage):
         return ()
 
     def _score_entries(self):
-        return list(self._score.values()) + list(self.scores.hota_entries.values())
+        return self.scores.score_entries()
 
     def _score_table(self):
         """the table the metrics score: the provider's boxes and counts with this tracker's ids"""
@@ -1682,6 +1898,25 @@ class SequenceTracker(TrackerBase):
         asspr, loca (means over the 19 thresholds), hota0, loca0 (at alpha = 0.05), per_alpha; nan with nothing to score."""
         return self.scores.hota_summary()
 
+    def _mots_table(self):
+        """the table MOTS scores: the provider's step owner map and counts with this stage's ids"""
+        return (self.T, self.F, self.provider.owner, self.provider.num_objects, self._score_table()[4])
+
+    def mots(self, gt_instances, n_slots=MAX_GT, accumulate=True):
+        """MOTS of the LATEST `track()` against gt_instances [R, H, W] (or [S, F, H, W]; integers, -1 = background; label g is the same
+        object in every frame of a sequence, a label from n_slots on is counted nowhere): the unchanged air_score_contingency of the
+        provider's owner map and the instance maps, then air_track_mots (MOTS in the module text; 1 <= n_slots <= 8).  Returns device
+        tensors that the next call with the same n_slots overwrites: seq_mots_i [S, 8] int32 (MOTS_COUNTS), seq_mots_f [S] float64,
+        mots_match [R, n_slots] int32, mots_iou [R, n_slots] fp32, cont [R, T+1, n_slots+1] int32, and the running totals_mots_i [8]
+        int64 / totals_mots_f [1] float64, which this call adds to (accumulate=False: restarts) on the device, with no read-back.
+        `score`, `hota` and their caches are not touched.  Same stream contract as `track`."""
+        return self.scores.run_mots(gt_instances, (), n_slots, self._mots_table(), bool(accumulate))
+
+    def mots_summary(self) -> Dict[str, float]:
+        """The MOTS figures of everything `mots` took since the last reset (ONE read-back): motsa, smotsa, motsp, recall, precision,
+        mostly_tracked, mostly_lost and the counts; nan with nothing to score."""
+        return self.scores.mots_summary()
+
     def reset(self):
         """zero the totals"""
         self.scores.reset()
@@ -1710,8 +1945,10 @@ class StreamTracker(TrackerBase):
 
     A push MUTATES the state, captured or not: pushing a chunk twice continues the stream with a repeated chunk, it does not repeat the
     call -- `state_dict()` before and `load_state_dict()` after is how a chunk is re-run.  Ids: 0..32766 per sequence until `reset`;
-    a birth beyond is OVERFLOW.  Out of scope on a stream: IDF1 and HOTA (their tables are indexed by global id), more than 32
-    live tracks.  Trajectories: a trajectory.StreamSmoother bound to this tracker (fixed-lag smoothing, `lag` frames late; the forecast at once)."""
+    a birth beyond is OVERFLOW.  Out of scope on a stream: IDF1 and HOTA (their tables are indexed by global id), MOTS (there is no
+    `mots`: the carried score state has a fixed layout, st_i [S, 32] and st_f [S], with no room for a second metric's map, per-slot
+    counts and sum), more than 32 live tracks.  Trajectories: a trajectory.StreamSmoother bound to this tracker (fixed-lag
+    smoothing, `lag` frames late; the forecast at once)."""
 
     def __init__(self, provider, chunk_frames, iou_gate=DEFAULTS["iou_gate"], appearance_weight=DEFAULTS["appearance_weight"],
                  birth_score=DEFAULTS["birth_score"], max_age=DEFAULTS["max_age"], matching="greedy", motion=None, motion_gate=None):
@@ -1890,8 +2127,9 @@ class TrackStitcher(BoundStage):
     air_track_stitch on the tracker's ids and tables and the provider's what / where rows, then the unchanged air_track_owner on
     stitch_id into a `track_owner` buffer of this stage.  appearance_weight=None: the tracker's; noise=None: the tracker's motion
     terms if it has them, else trajectory.DEFAULTS; max_gap and gate (True: MOTION_GATE_DEFAULT) are provisional.  It owns an
-    IdentityScores over (T, F, the provider's boxes and counts, stitch_id): score / hota / summary / identity_summary / hota_summary /
-    reset are SequenceTracker's, on the stitched ids (n_ids stays F T: the ids are not compacted)."""
+    IdentityScores over (T, F, the provider's boxes and counts, stitch_id): score / hota / mots / summary / identity_summary /
+    hota_summary / mots_summary / reset are SequenceTracker's, on the stitched ids (n_ids stays F T: the ids are not compacted; MOTS
+    reads the provider's owner map with stitch_id)."""
 
     def __init__(self, tracker, max_gap=STITCH_MAX_GAP, gate=True, appearance_weight=None, noise=None):
         if isinstance(tracker, StreamTracker):
@@ -1937,7 +2175,7 @@ class TrackStitcher(BoundStage):
         self._plan = [e for seg in self.segments.values() for e in seg]
 
     def _score_entries(self):
-        return list(self._score.values()) + list(self.scores.hota_entries.values())
+        return self.scores.score_entries()
 
     def _score_table(self):
         """the table the metrics score: the provider's boxes and counts with the STITCHED ids"""
@@ -1979,4 +2217,5 @@ class TrackStitcher(BoundStage):
     # ---- the identity metrics: SequenceTracker's methods as they are, on this stage's table -------------------------------------------------
     _score_entry, score, hota = SequenceTracker._score_entry, SequenceTracker.score, SequenceTracker.hota
     summary, identity_summary, hota_summary = SequenceTracker.summary, SequenceTracker.identity_summary, SequenceTracker.hota_summary
+    _mots_table, mots, mots_summary = SequenceTracker._mots_table, SequenceTracker.mots, SequenceTracker.mots_summary
     reset = SequenceTracker.reset

@@ -100,7 +100,7 @@ from collections import OrderedDict
 from typing import Dict
 
 from .stage import BoundStage, ReadOut, compacted_rows
-from .track import MAX_IDS, MAX_SLOTS, IdentityScores
+from .track import MAX_GT, MAX_IDS, MAX_SLOTS, IdentityScores
 from .track import check_arguments as check_track_arguments
 from .track import check_frames_seen, check_valid
 
@@ -753,7 +753,7 @@ class TrajectorySmoother(BoundStage):
         self._plan = [e for seg in self.segments.values() for e in seg]
 
     def _score_entries(self):
-        return list(self._score.values()) + list(self.scores.hota_entries.values())
+        return self.scores.score_entries()
 
     def launch_count(self) -> Dict[str, int]:
         """entries of one `run()` behind the tracker's own (`tracker` holds that tracker's launch_count())"""
@@ -845,6 +845,20 @@ class TrajectorySmoother(BoundStage):
     def hota_summary(self) -> Dict[str, object]:
         """track.hota_summary of everything `hota` took since the last reset (ONE read-back)"""
         return self.scores.hota_summary()
+
+    def mots(self, gt_instances, n_slots=MAX_GT, accumulate=True):
+        """SequenceTracker.mots on the COMPLETED table of the latest `run()`: the unchanged air_score_contingency of sm_owner (the
+        ROW that owns a pixel of the completed frame's rendering) and the instance maps, then air_track_mots with T := C on sm_count
+        and sm_id -- so a frame a track coasted over counts a match when the filled mask is on the object.  Returns seq_mots_i,
+        seq_mots_f, mots_match (the matched ROW), mots_iou, cont and this object's own running totals_mots_i / totals_mots_f
+        (accumulate=False: restarts), all on the device."""
+        t = self.sm
+        return self.scores.run_mots(gt_instances, ("completed",), n_slots, (self.C, self.F, t["owner"], t["count"], t["id"]),
+                                    bool(accumulate))
+
+    def mots_summary(self) -> Dict[str, float]:
+        """track.mots_summary of everything `mots` took since the last reset (ONE read-back)"""
+        return self.scores.mots_summary()
 
     def reset(self):
         """zero the totals"""

@@ -1046,6 +1046,29 @@ AIR_ENGINE_API int air_tile_relabel(const float *score_src, const int *kept_cand
  *   host per threshold: DetA = tp / max(1, tp + fn + fp), AssA = ass / max(1, tp), LocA = loc / tp, HOTA = sqrt(DetA AssA).
  *   The limits and checks of air_track_idf, and S 19 G n_ids <= INT_MAX (AIR_E_SHAPE).  boxes / gt_boxes 16-byte, potential /
  *   seq_hota_f 8-byte, everything else 4-byte aligned (AIR_E_ALIGN).  No floating-point atomics, no traffic between workgroups.
+ * air_track_mots: the MOTS counts (Voigtlaender et al., CVPR 2019: MOTSA, sMOTSA, MOTSP) of the tracks as MASKS, one wavefront per
+ *   sequence, the frames walked inside.  Inputs: cont[R,T+1,G+1] (int32) exactly as air_score_contingency writes it for (the step
+ *   owner map, the ground-truth instance map): cont[r,a,b] = the pixels with owner + 1 == a and gt + 1 == b; num_objects[R];
+ *   track_id[T,R], the table's id column.  Boxes are not read.  Per frame, every sum in int64: row[j] = sum_b cont[r,j+1,b] (the
+ *   hypothesis area), col[g] = sum_a cont[r,a,g+1] (the ground-truth area, the pixels owned by the background and by steps that are no
+ *   hypothesis included).  Hypotheses: the steps j < clip(n, 0, T) with track_id >= 0 and row[j] > 0 -- a step without a track or
+ *   without a pixel of its own is neither a match nor a false positive.  Slot g is present iff col[g] > 0.  For a present g and a
+ *   hypothesis j: inter = cont[r,j+1,g+1], union = row[j] + col[g] - inter; they match iff inter > union - inter: mask IoU > 1/2 with no
+ *   float and no 2 inter that could overflow.  There is no tau: within a frame the hypothesis masks are disjoint and the ground-truth
+ *   masks are disjoint, so for a non-negative table at most one j qualifies per g and at most one g per j (a match holds more than half
+ *   of both areas): the search order cannot change the result, and no solver and no tie rule is needed.  (Stated for completeness: the
+ *   lowest qualifying j of a slot is taken, and a hypothesis is unmatched iff no slot took it.)
+ *   For every matched (g,j) in ascending g: tp += 1; soft += (double) inter / (double) union, float64 with contraction off, summed in
+ *   frame order, then g order; ids += (map[g] exists and != id_j), then map[g] = id_j; tracked[g] += 1.  map[g] is none at the start of a
+ *   sequence and persists while g is unmatched or absent (step 3 of air_track_score; the paper's latest tracked predecessor).  gt +=
+ *   present g; fn += present unmatched g; fp += unmatched hypotheses; present[g] += 1 per present g.
+ *   Outputs, every element written by exactly one writer, nothing pre-zeroed, no atomics on global memory: seq_mots_i[S,8] (int32) =
+ *   {gt, tp, fn, fp, ids, mostly tracked (5 tracked[g] >= 4 present[g]), mostly lost (5 tracked[g] <= present[g]), gt objects}, the last
+ *   three over g with present[g] > 0; seq_mots_f[S] (float64) = soft; mots_match[R,G] (int32) = the matched step, -1 otherwise;
+ *   mots_iou[R,G] (fp32) = the quotient rounded once, 0 otherwise.  On the host: MOTSA = (tp - fp - ids) / gt, sMOTSA = (soft - fp -
+ *   ids) / gt, MOTSP = soft / tp.
+ *   1 <= T <= 32, 1 <= G <= 8, S, F > 0, S F == R, R (T+1) (G+1) <= INT_MAX (AIR_E_SHAPE).  seq_mots_f 8-byte, everything else 4-byte
+ *   aligned (AIR_E_ALIGN).  Checks come before the launch: a refused call writes nothing.
  * air_track_stitch: track fragments joined across occlusions longer than max_age (tracklet linking), one 256-thread workgroup per
  *   sequence.  Inputs: what[T,R,A], where[T,R,4] (the provider's rows) and air_track_associate*'s track_id[T,R], num_tracks[S],
  *   track_first / track_last / track_length / track_gaps [S, F T].  N = max(num_tracks[s], 0); N > 32: OVERFLOW, below; else N =
@@ -1135,6 +1158,8 @@ AIR_ENGINE_API int air_track_idf(const float *boxes, const int *num_objects, con
 AIR_ENGINE_API int air_track_hota(const float *boxes, const int *num_objects, const int *track_id, const float *gt_boxes, int T, int G,
                     int S, int F, int R, int n_ids, double *potential, int *id_count, int *gt_count, int *matches, int *seq_hota_i,
                     double *seq_hota_f, void *stream);
+AIR_ENGINE_API int air_track_mots(const int *cont, const int *num_objects, const int *track_id, int T, int G, int S, int F, int R,
+                    int *seq_mots_i, double *seq_mots_f, int *mots_match, float *mots_iou, void *stream);
 AIR_ENGINE_API int air_track_stitch(const float *what, const float *where, const int *track_id, const int *num_tracks,
                     const int *track_first, const int *track_last, const int *track_length, const int *track_gaps, int T, int S,
                     int F, int R, int A, int max_gap, double gate_d2, double appearance_weight, double q_shift, double q_scale,

@@ -52,6 +52,13 @@ track.reference_hota bit for bit, or the tool exits with an error.  Then the thr
 repeats of --iters back-to-back launches between two device events) and one launch at a time as the other modes time it; the ratios
 are reported; no bar on time.
 
+--mots measures the MOTS measures instead (SequenceTracker.mots: the unchanged air_score_contingency, then air_track_mots): the same
+tracker; the instance maps are cut from the parse's own owner map (labels below 3), every fifth frame rolled two pixels, which takes
+those frames below IoU 1/2 (the misses and false positives of the figures).  cont and the four outputs of the first --mots-check
+sequences must equal track.mots_contingency and track.reference_mots bit for bit, or the tool exits with an error.  Then the two
+captured graphs -- air_track_score and the MOTS pair -- are timed in turns in this process, and the three entries launched eagerly,
+in turns as well and one launch at a time; the ratios are reported; no bar on time.
+
 --stitch measures stitching (track.TrackStitcher: air_track_stitch, then air_track_owner on the stitched ids): for every F in --frames, at
 --rows provider rows, ONE captured SceneParser, a captured tracker (--matching, max_age 1) and a captured stitcher over it; the counts
 leave two frames in five empty, so the tracks die and are born again and the stitcher has fragments to join.  The device outputs of the
@@ -480,6 +487,85 @@ def one_hota_length(args, F):
     return res
 
 
+def one_mots_length(args, F):
+    """--mots: air_score_contingency + air_track_mots beside air_track_score on the tracks of one captured tracker"""
+    from attend_infer_repeat_amd import _lib, track
+    from attend_infer_repeat_amd.engine_config import EngineConfig
+    from attend_infer_repeat_amd.parse import SceneParser
+    cfg = EngineConfig()
+    R = args.rows
+    if R % F:
+        raise SystemExit("--rows %d is no multiple of %d frames" % (R, F))
+    S, T, G = R // F, int(cfg.max_steps), 3
+    ps = SceneParser(cfg, R, seed=0)
+    ps.capture()
+    tk = track.SequenceTracker(ps, F, birth_score=0.0, matching=args.matching)
+    tk.capture()
+    eng, dev = ps.engine, ps.engine.device
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    start = torch.rand(S, *cfg.img_size, generator=gen) * (torch.rand(S, *cfg.img_size, generator=gen) > 0.8)
+    frames = torch.stack([torch.roll(start, shifts=(f, f // 2), dims=(1, 2)) for f in range(F)], 1).contiguous().to(dev)
+    counts = (torch.arange(R, device=dev) % (T + 1)).to(torch.int32)
+    out = tk.track(frames, counts)
+    torch.cuda.synchronize()
+    host = lambda t: t.cpu().numpy()
+    boxes, n, ids, owner = host(out["boxes"]), host(out["num_objects"]), host(out["track_id"]), host(out["owner"])
+    inst = np.where(owner < G, owner, -1).astype(np.int8)           # ground truth cut from the parse's own owner map ...
+    inst[::5] = np.roll(inst[::5], 2, axis=2)                       # ... every fifth frame two pixels off: those masks miss
+    gt = np.zeros((R, G, 4), np.float32)
+    for g in range(G):
+        gt[n > g, g] = boxes[g, n > g]
+    inst_dev, gt_dev = torch.from_numpy(inst).to(dev), torch.from_numpy(gt).to(dev)
+    got = tk.mots(inst_dev, G, accumulate=False)
+    torch.cuda.synchronize()
+    n_seq = min(S, args.mots_check)                                # the host reference walks these sequences
+    cont = track.mots_contingency(owner[:n_seq * F], inst[:n_seq * F], T, G)
+    want = track.reference_mots(cont, n[:n_seq * F], ids[:, :n_seq * F], F)
+    same = lambda a, b: bool((np.ascontiguousarray(a).view(np.uint8) == np.ascontiguousarray(b).view(np.uint8)).all())
+    agree = {k: same(host(got[k])[:n_seq * (1 if k.startswith("seq") else F)], want[k]) for k in track.MOTS_OUTPUTS}
+    agree["cont"] = same(host(got["cont"])[:n_seq * F], cont)
+    res = dict(frames=F, sequences=S, rows=R, max_steps=T, gt_slots=G, img_size=list(cfg.img_size), matching=args.matching,
+               sequences_checked=n_seq, agreement=agree, mots_summary=tk.mots_summary())
+    if not all(agree.values()):
+        print(json.dumps(res))
+        raise SystemExit("air_track_mots and the host reference disagree: %r" % (agree,))
+    tk.score(gt_dev, accumulate=False)
+    res["score_summary"] = tk.summary()
+    graphs = {"score": tk._score[(G, 0.5)], "mots": tk.scores.mots_entries[(G,)]}
+    turns = {k: [] for k in graphs}
+    for _ in range(2):                                             # in turns, in this process
+        for name, e in graphs.items():
+            turns[name].append(median_ms(lambda: eng._replay_or_run(e["graph"], e["plan"]), args.iters, eng.stream))
+    for name, v in turns.items():
+        res["%s_graph_turns_ms" % name] = [m for m, _ in v]
+        res["%s_graph_repeats_ms" % name] = [r for _, r in v]
+        res["%s_graph_ms" % name] = statistics.median(res["%s_graph_turns_ms" % name])
+    res["mots_over_score_graph"] = res["mots_graph_ms"] / res["score_graph_ms"]
+    plan = graphs["score"]["plan"] + graphs["mots"]["plan"]        # air_track_score, air_score_contingency, air_track_mots
+    launch = lambda fn, a, name: _lib.check(fn(*a, eng._sp()), name)
+    eager = {name: [] for _, _, name in plan}
+    for _ in range(2):
+        for fn, a, name in plan:
+            eager[name].append(median_ms(lambda: launch(fn, a, name), args.iters, eng.stream))
+    res["eager_launch_us"] = {k: statistics.median([m for m, _ in v]) * 1e3 for k, v in eager.items()}
+    res["eager_launch_turns_us"] = {k: [m * 1e3 for m, _ in v] for k, v in eager.items()}
+    per = {}
+    for _ in range(7):                                             # and one launch at a time between two events, as the other modes time it
+        for fn, a, name in plan:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(eng.stream)
+            launch(fn, a, name)
+            e1.record(eng.stream)
+            e1.synchronize()
+            per.setdefault(name, []).append(e0.elapsed_time(e1) * 1e3)
+    res["eager_single_launch_us"] = {k: statistics.median(v) for k, v in per.items()}
+    us = res["eager_launch_us"]
+    res["mots_kernel_over_score_eager"] = us["air_track_mots"] / us["air_track_score"]
+    res["mots_pair_over_score_eager"] = (us["air_score_contingency"] + us["air_track_mots"]) / us["air_track_score"]
+    tk.release_graphs(); ps.release_graphs()
+    return res
+
+
 def one_stitch_length(args, F):
     """--stitch: the stitcher's captured graph beside the tracker's captured tail, on the tracks of one captured tracker"""
     from attend_infer_repeat_amd import _lib, track
@@ -564,9 +650,19 @@ def main(argv=None):
     ap.add_argument("--hota-check", type=int, default=16, metavar="N", help="with --hota: the sequences the host reference walks")
     ap.add_argument("--stitch", action="store_true", help="the stitcher's captured graph beside the tracker's captured tail")
     ap.add_argument("--stitch-check", type=int, default=16, metavar="N", help="with --stitch: the sequences the host reference walks")
+    ap.add_argument("--mots", action="store_true",
+                    help="air_score_contingency + air_track_mots beside air_track_score (eager and captured)")
+    ap.add_argument("--mots-check", type=int, default=16, metavar="N", help="with --mots: the sequences the host reference walks")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("track_bench measures on the GPU; there is no CPU fallback")
+    if args.mots:
+        res = dict(tool="track_bench --mots", device=torch.cuda.get_device_name(0), lengths=[one_mots_length(args, F) for F in args.frames])
+        print(json.dumps(res))
+        for r in res["lengths"]:
+            for k, v in r.items():
+                print("F=%-4d %-34s %s" % (r["frames"], k, v))
+        return res
     if args.stitch:
         res = dict(tool="track_bench --stitch", device=torch.cuda.get_device_name(0), lengths=[one_stitch_length(args, F) for F in args.frames])
         print(json.dumps(res))
