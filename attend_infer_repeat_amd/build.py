@@ -15,7 +15,8 @@ LIB = os.path.join(LIBDIR, "libair_hip.so")
 SOURCES = ["st_kernels.hip", "canvas_kernels.hip", "gemm_kernels.hip", "lstm_kernels.hip", "pointwise_kernels.hip", "loss_kernels.hip", "engine_kernels.hip",
            "comm_rccl.hip", "comm_ipc.hip", "mlp_chain_kernels.hip", "iw_kernels.hip", "gen_kernels.hip", "parse_kernels.hip",
            "score_kernels.hip", "particle_kernels.hip", "refine_kernels.hip", "prune_kernels.hip", "propose_kernels.hip",
-           "tile_kernels.hip", "track_kernels.hip", "temporal_kernels.hip", "trajectory_kernels.hip", "noise_fit_kernels.hip"]
+           "tile_kernels.hip", "track_kernels.hip", "temporal_kernels.hip", "trajectory_kernels.hip", "noise_fit_kernels.hip",
+           "iw_train_kernels.hip"]
 ARCH = "gfx950"
 
 

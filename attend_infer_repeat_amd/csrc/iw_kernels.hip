@@ -3,21 +3,7 @@
 //   air_iw_reduce:    per image, over its K particles: the importance-weighted bound, the plain ELBO of the same particles, the
 //                     effective sample size and the self-normalised posterior over the object count (+ float64 running totals).
 // Rows are r = b * K + k: the K particles of an image are adjacent.
-#include <math.h>
-#include "scene_device.h"
-
-#define IW_MAXT 32
-
-struct IwPriors {
-    float what_loc, what_scale, scale_loc, scale_scale, shift_loc, shift_scale;   // shift_loc NaN: centred on where_loc
-};
-
-// log N(x | p_loc, p_scale) - log N(x | loc, scale); the -1/2 log 2 pi terms cancel.  No clamps: a zero scale gives the
-// +-inf / NaN of the plain formula.
-__device__ __forceinline__ float iw_log_ratio(float x, float loc, float scale, float p_loc, float p_scale, float log_p_scale) {
-    const float zq = (x - loc) / scale, zp = (x - p_loc) / p_scale;
-    return 0.5f * (zq * zq - zp * zp) + (logf(scale) - log_p_scale);
-}
+#include "iw_device.h"
 
 // One wavefront per row.  The chain of presences is monotone, so the steps that count are t < n = the number of leading
 // ones; their A-wide `what` rows are spread over the lanes as n * A / V vectors of V floats (V = 4 / 2 / 1: what the row

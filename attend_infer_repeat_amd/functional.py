@@ -276,3 +276,55 @@ class _NumSteps(torch.autograd.Function):
 
 def numsteps(presence_prob, presence, prior_f64):
     return _NumSteps.apply(presence_prob, presence, prior_f64)
+
+
+class _IwLogweight(torch.autograd.Function):
+    """log w = log p(x, z) - log q(z | x) per (image, particle) row (air_iw_logweight, iw_eval.py) and its hand-written backward
+    (air_iw_logweight_bwd).  The presence chain is discrete: no gradient reaches it, and log pi(n) is a constant."""
+
+    @staticmethod
+    def forward(ctx, what, what_loc, what_scale, where, where_loc, where_scale, presence, rec, logp, prior_f64, K, priors6, normalize):
+        saved = tuple(_c(t) for t in (what, what_loc, what_scale, where, where_loc, where_scale, presence))
+        logw, n = H.iw_logweight(*saved, _c(rec), _c(logp), prior_f64, K, priors6, normalize)
+        ctx.save_for_backward(*saved)
+        ctx.cfg = (K, priors6)
+        ctx.mark_non_differentiable(n)
+        return logw, n
+
+    @staticmethod
+    def backward(ctx, g, _dn):
+        K, priors6 = ctx.cfg
+        d = H.iw_logweight_bwd(*ctx.saved_tensors, _c(g), K, priors6)
+        return d[0], d[1], d[2], d[3], d[4], d[5], None, d[6], d[7], None, None, None, None
+
+
+def iw_logweight(what, what_loc, what_scale, where, where_loc, where_scale, presence, rec, logp, prior_f64, K, priors6, normalize=False):
+    """what-like [T,R,A], where-like [T,R,4], presence [T,R], rec / logp [R] (R = B * K, row b * K + k) -> logw [R], num_steps [R]"""
+    return _IwLogweight.apply(what, what_loc, what_scale, where, where_loc, where_scale, presence, rec, logp, prior_f64, int(K),
+                              tuple(float(v) for v in priors6), bool(normalize))
+
+
+class _Vimco(torch.autograd.Function):
+    """The K-particle bound per image and the surrogate -mean_b bound over the non-degenerate images (air_iw_vimco).  Backward: the
+    VIMCO estimator -- -wnorm[r] / B_eff to logw, -signal[r] / B_eff to logq = log q(n sampled); both coefficients are constants."""
+
+    @staticmethod
+    def forward(ctx, logw, logq, K):
+        bound, wnorm, signal, ess, degen = H.iw_vimco(_c(logw), K)
+        b_eff = (degen == 0).sum().clamp(min=1).to(torch.float32)
+        ctx.save_for_backward(-wnorm / b_eff, -signal / b_eff)
+        ctx.has_logq = logq is not None
+        ctx.mark_non_differentiable(bound, ess, degen)
+        return bound, -(bound.sum() / b_eff), ess, degen
+
+    @staticmethod
+    def backward(ctx, _db, dsur, _de, _dd):
+        cw, cs = ctx.saved_tensors
+        return cw * dsur, (cs * dsur if ctx.has_logq else None), None
+
+
+def vimco(logw, logq, K, return_stats=False):
+    """logw [B * K] (row b * K + k), logq [B * K] or None (no learning signal for the discrete count) -> bound [B], surrogate (scalar);
+    return_stats=True adds ess [B] and degenerate [B] (int32; such images have bound 0 and no gradient)"""
+    bound, sur, ess, degen = _Vimco.apply(logw.reshape(-1), None if logq is None else logq.reshape(-1), int(K))
+    return (bound, sur, ess, degen) if return_stats else (bound, sur)

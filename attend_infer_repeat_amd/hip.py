@@ -734,6 +734,71 @@ def nvil(imp, baseline, logp, ema=None):
     return out, dlogp, dbase
 
 
+def _iw_rows(what, what_loc, what_scale, where, where_loc, where_scale, presence, K):
+    """shapes behind air_iw_logweight / air_iw_logweight_bwd: what-like [T,R,A], where-like [T,R,4], presence [T,R] (or [T,R,1])"""
+    what = _f32(what, "what", 3)
+    T, R, A = what.shape
+    for t, nm in ((what_loc, "what_loc"), (what_scale, "what_scale")):
+        if tuple(_f32(t, nm, 3).shape) != (T, R, A):
+            raise _lib.AirHipError(f"{nm}: expected shape {(T, R, A)}, got {tuple(t.shape)}")
+    for t, nm in ((where, "where"), (where_loc, "where_loc"), (where_scale, "where_scale")):
+        if tuple(_f32(t, nm, 3).shape) != (T, R, 4):
+            raise _lib.AirHipError(f"{nm}: expected shape {(T, R, 4)}, got {tuple(t.shape)}")
+    if _f32(presence, "presence").numel() != T * R:
+        raise _lib.AirHipError(f"presence: expected {T * R} entries, got shape {tuple(presence.shape)}")
+    if int(K) < 1 or R % int(K):
+        raise _lib.AirHipError(f"K = {K} does not divide the {R} rows")
+    return T, R, A
+
+
+def _iw_row_vec(t, name, R):
+    if _f32(t, name, 1).shape[0] != R:
+        raise _lib.AirHipError(f"{name}: expected {R} entries, got shape {tuple(t.shape)}")
+    return t
+
+
+def iw_logweight(what, what_loc, what_scale, where, where_loc, where_scale, presence, rec, logp, prior_f64, K, priors6, normalize=False):
+    """air_iw_logweight: -> logw[R], num_steps[R] (int32).  priors6 = (what loc, scale, where-scale loc, scale, where-shift loc, scale),
+    the shift loc NaN for a prior centred on where_loc."""
+    T, R, A = _iw_rows(what, what_loc, what_scale, where, where_loc, where_scale, presence, K)
+    _iw_row_vec(rec, "rec", R); _iw_row_vec(logp, "logp", R)
+    prior_f64 = _prior_f64(prior_f64, T)
+    logw = torch.empty((R,), dtype=torch.float32, device=what.device)
+    n = torch.empty((R,), dtype=torch.int32, device=what.device)
+    pr = [float(v) for v in priors6]
+    _lib.check(lib().air_iw_logweight(_p(what), _p(what_loc), _p(what_scale), _p(where), _p(where_loc), _p(where_scale), _p(presence),
+                                      _p(rec), _p(logp), _p(prior_f64), T, R, int(K), A, *pr, 1 if normalize else 0, _p(logw), _p(n),
+                                      _stream()), "air_iw_logweight")
+    return logw, n
+
+
+def iw_logweight_bwd(what, what_loc, what_scale, where, where_loc, where_scale, presence, g, K, priors6):
+    """air_iw_logweight_bwd: -> d what, d what_loc, d what_scale [T,R,A], d where, d where_loc, d where_scale [T,R,4], d rec [R], d logp [R]"""
+    T, R, A = _iw_rows(what, what_loc, what_scale, where, where_loc, where_scale, presence, K)
+    _iw_row_vec(g, "g", R)
+    outs = [torch.empty_like(what) for _ in range(3)] + [torch.empty_like(where) for _ in range(3)] + \
+           [torch.empty((R,), dtype=torch.float32, device=what.device) for _ in range(2)]
+    pr = [float(v) for v in priors6]
+    _lib.check(lib().air_iw_logweight_bwd(_p(what), _p(what_loc), _p(what_scale), _p(where), _p(where_loc), _p(where_scale),
+                                          _p(presence), _p(g), T, R, int(K), A, *pr, *[_p(o) for o in outs], _stream()),
+               "air_iw_logweight_bwd")
+    return tuple(outs)
+
+
+def iw_vimco(logw, K):
+    """air_iw_vimco: logw[R] (R = B * K, row b * K + k) -> bound[B], wnorm[R], signal[R], ess[B], degenerate[B] (int32)"""
+    logw = _f32(logw, "logw", 1)
+    R, K = logw.shape[0], int(K)
+    if K < 2 or R == 0 or R % K:
+        raise _lib.AirHipError(f"iw_vimco: K = {K} must be >= 2 and divide the {R} rows")
+    dev = logw.device
+    B = R // K
+    e = lambda n, dt=torch.float32: torch.empty((n,), dtype=dt, device=dev)
+    bound, wnorm, signal, ess, degen = e(B), e(R), e(R), e(B), e(B, torch.int32)
+    _lib.check(lib().air_iw_vimco(_p(logw), R, K, _p(bound), _p(wnorm), _p(signal), _p(ess), _p(degen), _stream()), "air_iw_vimco")
+    return bound, wnorm, signal, ess, degen
+
+
 def nvil_parts(imp_parts, baseline, logp, ema=None, want_sum=True):
     """air_nvil_parts: imp_parts[n_parts, B] shares of the importance weight -> out[4], dlogp[B], dbaseline[B], imp_sum[B] | None"""
     imp_parts = _f32(imp_parts, "imp_parts", 2); baseline = _f32(baseline, "baseline", 1); logp = _f32(logp, "logp", 1)

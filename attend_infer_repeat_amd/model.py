@@ -246,6 +246,67 @@ class AIRModel(object):
             self.num_step_accuracy = (self.gt_num_steps == self.num_step_per_sample).float().mean()
         return opt_loss
 
+    # ---- training on the K-particle importance-weighted bound (iw_train.py; DESIGN 8: "Training on the bound") ------------------
+    def _iw_forward_losses(self, obs=None, nums=None, noise=None):
+        """The unroll on every image repeated K times (row b * K + k; noise: optional dict of time-major tensors for K * B rows)
+        and the objective -mean_b L_K over the non-degenerate images.  The output attributes then describe the K * B rows;
+        `obs`, `nums` and `batch_size` stay the caller's."""
+        if obs is not None:
+            self.obs = obs
+        if nums is not None:
+            self.nums = nums
+        K, B = self._iw_samples, self.batch_size
+        obs_b, nums_b = self.obs, self.nums
+        try:
+            self.obs, self.nums, self.batch_size = obs_b.repeat_interleave(K, 0), None, B * K
+            self.forward(noise=noise)
+            gt = None if nums_b is None else nums_b.sum(0).reshape(-1).repeat_interleave(K, 0)
+            return self._iw_losses(self.global_step, gt)
+        finally:
+            self.obs, self.nums, self.batch_size = obs_b, nums_b, B
+
+    def _iw_losses(self, global_step, gt_num_steps=None):
+        from .iw_train import priors6
+        T, R, K = self.max_steps, self.batch_size, self._iw_samples
+        nsp = self.num_steps_prior
+        self.rec_loss_per_sample = F.rec_loglik(self.obs, self._canvas_unscaled[-1], float(self.output_multiplier), self.output_std)
+        self.rec_loss = self.rec_loss_per_sample.mean()
+        if getattr(nsp, 'anneal', None) is not None:
+            s = self._anneal_weight(nsp.init, nsp.final, nsp.anneal, int(global_step), nsp.steps,
+                                    getattr(nsp, 'hold_init', 0.), getattr(nsp, 'steps_div', 1.))
+        else:
+            s = nsp.init
+        self.steps_prior_success_prob = s
+        prior = geometric_prior(s, T).to(self.obs.device).double()          # the training loss's table: not normalised
+        presence = self.presence.reshape(T, R)
+        q, kl_ps, logq, _ = F.numsteps(self.presence_prob.reshape(T, R), presence, prior)
+        self._num_steps_q, self._num_steps_logp = q, logq
+        self.kl_num_steps_per_sample, self.kl_num_steps = kl_ps.detach(), kl_ps.detach().mean()
+        logw, _ = F.iw_logweight(self.what, self.what_loc, self.what_scale, self.where, self.where_loc, self.where_scale, presence,
+                                 self.rec_loss_per_sample, logq, prior, K,
+                                 priors6(self.what_prior, self.where_scale_prior, self.where_shift_prior), normalize=False)
+        bound, surrogate, ess, degen = F.vimco(logw, logq if self.use_reinforce else None, K, return_stats=True)
+        live = (degen == 0).to(torch.float32)
+        self.iw_log_weights = logw.detach().reshape(-1, K)
+        self.iw_bound_per_sample = bound
+        self.iw_bound = -surrogate.detach()
+        self.iw_ess = (ess * live).sum() / live.sum().clamp(min=1)
+        self.iw_degenerate = degen.sum()
+        self.loss = Loss()
+        self.loss.add(-logw.detach().mean(), -logw.detach())                # the single-sample bound of every row
+        zero = torch.zeros((), device=self.obs.device)
+        self.reinforce_loss, self.baseline_loss = zero, zero
+        opt_loss = surrogate
+        if self.l2_weight and self.l2_weight > 0.:
+            weights = [p for p in self.cell.parameters() if p.dim() == 2]
+            self.l2_loss = self.l2_weight * sum((w * w).sum() / 2 for w in weights)
+            opt_loss = opt_loss + self.l2_loss
+        self.opt_loss = opt_loss
+        if gt_num_steps is not None:
+            self.gt_num_steps = gt_num_steps
+            self.num_step_accuracy = (gt_num_steps == self.num_step_per_sample).float().mean()
+        return opt_loss
+
     def evaluate(self, obs=None, nums=None, noise=None):
         """Forward pass + every loss attribute on (obs, nums) WITHOUT an update -- what `sess.run(exprs, feed_dict)` did
         in the reference's logger (evaluation.py:137-164).  Requires `train_step(...)` to have been called (priors)."""
@@ -260,13 +321,19 @@ class AIRModel(object):
 
     def train_step(self, learning_rate, l2_weight=0., what_prior=None, where_scale_prior=None,
                    where_shift_prior=None, num_steps_prior=None, use_prior=True, use_reinforce=True, baseline=None,
-                   decay_rate=None, optimizer=None, opt_kwargs=None):
+                   decay_rate=None, optimizer=None, opt_kwargs=None, iw_samples=None):
         """Creates the train step and the global_step (model.py:261-376).
+        `iw_samples=K` (an extension, default None = exactly the objective above): train on the K-particle importance-weighted
+        bound instead -- every image repeated K times with independent noise, IWAE weights for the continuous latents, VIMCO's
+        leave-one-out signal for the discrete count, no baseline (`_iw_losses`, iw_train.py).
         `optimizer` / `opt_kwargs` (model.py:265: `optimizer=tf.train.RMSPropOptimizer, opt_kwargs=dict(momentum=.9,
         centered=True)`, instantiated as optimizer(learning_rate, **opt_kwargs) and once more at 10x the rate for the
         baseline, model.py:355-363): the default runs on the HIP centred-RMSProp kernel with TF's slot initialisation; any
         other choice is given as a torch.optim class (same calling convention: optimizer(params, lr, **opt_kwargs)) and
         steps the generic autograd path."""
+        from .iw_train import check_train_arguments
+        self._iw_samples = check_train_arguments(iw_samples, decay_rate, use_prior, self.discrete_steps, what_prior,
+                                                 where_scale_prior, where_shift_prior, num_steps_prior)
         custom_opt = optimizer is not None
         self._custom_optimizer = (optimizer, dict(opt_kwargs or {})) if custom_opt else None
         # the reference's default class with other keywords (model.py:265: RMSPropOptimizer(lr, **opt_kwargs), e.g. momentum=.5
@@ -290,12 +357,16 @@ class AIRModel(object):
         if not hasattr(self, 'baseline'):
             self.baseline = baseline
         self.baseline_module = self.baseline if not torch.is_tensor(self.baseline) else None
+        if self._iw_samples is not None:                     # no baseline is built or stepped (evaluate() then uses a zero one)
+            self.baseline = self.baseline_module = None
+            self.baseline_vars = []
         self.use_prior = bool(use_prior)
         self.use_reinforce = use_reinforce
         self._decay_rate = decay_rate
         self.learning_rate = torch.tensor(float(learning_rate))
         self.global_step = torch.zeros((), dtype=torch.int64)
-        self._losses(self.global_step)                       # builds the baseline, exposes the loss attributes
+        if self._iw_samples is None:
+            self._losses(self.global_step)                   # builds the baseline, exposes the loss attributes
         self._slots = {}
         lr_dev = torch.tensor([float(learning_rate)], device=self.obs.device)
 
@@ -312,12 +383,15 @@ class AIRModel(object):
         def train_step_fn(obs=None, nums=None, noise=None):
             """One update (== sess.run(train_step)): fresh forward, both gradient sets, both RMSProp updates."""
             lr_dev.fill_(float(self.learning_rate))
-            self.forward(obs, nums, noise)
-            self._in_train_step = True
-            try:
-                opt_loss = self._losses(self.global_step)
-            finally:
-                self._in_train_step = False
+            if self._iw_samples is not None:
+                opt_loss = self._iw_forward_losses(obs, nums, noise)
+            else:
+                self.forward(obs, nums, noise)
+                self._in_train_step = True
+                try:
+                    opt_loss = self._losses(self.global_step)
+                finally:
+                    self._in_train_step = False
             baseline_vars = list(getattr(self, 'baseline_vars', []))
             bset = {id(p) for p in baseline_vars}
             model_vars = [p for p in self.cell.parameters() if id(p) not in bset]

@@ -67,6 +67,14 @@ def main(argv=None):
                     help="K > 0: at every --log-every also print / write the K-particle importance-weighted bound, the ELBO of the same "
                          "particles, the effective sample size and the count accuracy of the self-normalised posterior on the validation "
                          "batches (evaluation.make_iw_logger); 0 = off")
+    ap.add_argument("--iw-train", type=int, default=None, metavar="K",
+                    help="K >= 2: train on the K-particle importance-weighted bound (AIRonMNIST.train_step(iw_samples=K): IWAE weights "
+                         "for the continuous latents, VIMCO's leave-one-out signal for the object count, no baseline) on the generic "
+                         "autograd path -- the fused engine is not used; iw_bound, iw_ess and iw_degenerate go into the 1000-iteration "
+                         "summaries.  Not with --decay-rate or the options that need the engine")
+    ap.add_argument("--decay-rate", type=float, default=None, metavar="D",
+                    help="train_step's decay_rate: normalise the NVIL importance weight by moving averages with decay D (the reference "
+                         "script leaves it off)")
     ap.add_argument("--prior-samples", type=int, default=0, metavar="N",
                     help="N > 0: at every --log-every draw N scenes from the generative model on the device (AIRonMNIST.sample_scenes, the "
                          "model's own count prior) and write the histogram of the generated object counts to log.jsonl; with --figures also "
@@ -184,6 +192,21 @@ def main(argv=None):
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
     args = ap.parse_args(argv)
+    if args.iw_train is not None:
+        from attend_infer_repeat_amd.iw_train import NO_DECAY_RATE, check_iw_samples
+        try:
+            check_iw_samples(args.iw_train)
+        except ValueError as e:
+            ap.error("--iw-train: %s" % e)
+        if args.decay_rate is not None:
+            ap.error("--iw-train does not go with --decay-rate: %s" % NO_DECAY_RATE)
+        needs_engine = [flag for flag, on in (
+            ("--device-feeder", args.device_feeder), ("--resume", args.resume), ("--init-from-tf-ckpt", args.init_from_tf_ckpt),
+            ("--check-every", args.check_every), ("--iw-particles", args.iw_particles > 0), ("--prior-samples", args.prior_samples > 0),
+            ("--parse-eval", args.parse_eval), ("--parse-score", args.parse_score), ("--parse-tiled", args.parse_tiled),
+            ("--track-eval", args.track_eval), ("--grad-histograms", args.grad_histograms)) if on]
+        if needs_engine:
+            ap.error("--iw-train runs on the generic autograd path; %s need(s) the fused engine" % ", ".join(needs_engine))
     refine_kw = {}
     if args.parse_refine_lr is not None and args.parse_refine is None:
         ap.error("--parse-refine-lr goes with --parse-refine")
@@ -387,8 +410,13 @@ def main(argv=None):
                      transform_estimator_hidden=n_hiddens, steps_pred_hidden=[128, 64], baseline_hidden=[256, 128],
                      transform_var_bias=transform_var_bias, step_bias=step_bias, output_multiplier=output_multiplier,
                      guard_degenerate=args.guard_degenerate or None)
+    step_kw = {}
+    if args.decay_rate is not None:
+        step_kw["decay_rate"] = args.decay_rate
+    if args.iw_train is not None:
+        step_kw.update(use_engine=False, iw_samples=args.iw_train)
     train_step, global_step = air.train_step(learning_rate, l2_weight, appearance_prior, where_scale_prior,
-                                             where_shift_prior, num_steps_prior)
+                                             where_shift_prior, num_steps_prior, **step_kw)
     if args.init_from_tf_ckpt:
         from attend_infer_repeat_amd.tf_checkpoint import global_step_of, import_tf_checkpoint, import_tf_optimizer_slots, mapping_report
         name_map = None
@@ -568,9 +596,14 @@ def main(argv=None):
     if train_itr == 0:
         log(0)
     t0, last = time.time(), train_itr
+    iw_degenerate_total = 0
     while train_itr < args.iters:
         if args.device_feeder:
             train_itr = int(train_step(None, None, refresh=False))
+        elif args.iw_train is not None:
+            xb, yb = train_feed()
+            train_itr = int(train_step(xb, yb))
+            iw_degenerate_total = iw_degenerate_total + air.iw_degenerate      # (a device tensor: no sync per step)
         else:
             xb, yb = train_feed()
             train_itr = int(train_step(xb, yb, refresh=False))
@@ -597,7 +630,14 @@ def main(argv=None):
             top = sorted(worst.items(), key=lambda kv: -kv[1] if kv[1] == kv[1] else -float("inf"))[:3]
             diag["largest_grads"] = top
             writer.write(json.dumps(diag) + "\n"); writer.flush()
-        if args.summary_every and train_itr % args.summary_every == 0:
+        if args.iw_train is not None:
+            if args.summary_every and train_itr % args.summary_every == 0:
+                writer.write(json.dumps(dict(step=train_itr, data="summary", iw_samples=args.iw_train, iw_bound=float(air.iw_bound),
+                                             iw_ess=float(air.iw_ess), iw_degenerate=int(air.iw_degenerate),
+                                             iw_degenerate_total=int(iw_degenerate_total), rec=float(air.rec_loss),
+                                             loss=float(air.loss.value), opt_loss=float(air.opt_loss), num_step=float(air.num_step),
+                                             num_step_acc=float(air.num_step_accuracy))) + "\n")
+        elif args.summary_every and train_itr % args.summary_every == 0:
             # the reference's `all_summaries` (model.py's tf.summary scalars + evaluation.gradient_summaries), every 1000 iterations
             writer.write(json.dumps(dict(step=train_itr, data="summary", **step_summaries(air, histogram=args.grad_histograms))) + "\n")
         if train_itr % args.log_every == 0:
@@ -606,7 +646,10 @@ def main(argv=None):
             print("iter {}: {:.0f} images/s".format(train_itr, (train_itr - last) * batch_size / max(dt, 1e-9)))
             log(train_itr)
             t0, last = time.time(), train_itr
-        if train_itr % args.save_every == 0:
+        if train_itr % args.save_every == 0 and args.iw_train is not None:
+            torch.save({"cell": air.cell.state_dict(), "global_step": train_itr, "iw_samples": args.iw_train},
+                       osp.join(logdir, "model_{}.pt".format(train_itr)))
+        elif train_itr % args.save_every == 0:
             torch.save({"engine": air._engine.state_dict(), "train_feed": train_feed.state_dict(),
                         "valid_feed": valid_feed.state_dict()}, osp.join(logdir, "model_{}.pt".format(train_itr)))
             if args.figures:

@@ -622,6 +622,32 @@ AIR_ENGINE_API int air_iw_logweight(const float *what, const float *what_loc, co
 AIR_ENGINE_API int air_iw_reduce(const float *logw, const int *num_steps, int T, int R, int K, float *iw_bound, float *elbo,
                   float *ess, float *q_n_iw, const int *gt_steps, double *acc, void *stream);
 
+/* ---- training on the K-particle bound: the backward side of the two entries above (same rows r = b * K + k).
+ * air_iw_logweight_bwd: the gradient of air_iw_logweight's logw[r] times an upstream g[R], with the same priors and the same count n
+ *   (leading ones of presence).  Per element, with zq = (x - loc) / scale, zp = (x - p_loc) / p_scale, a = zq / scale, b = zp / p_scale,
+ *   in this order and without contraction:  d x = g * (a - b);  d loc = g * (0 - a), and g * (b - a) for the shift components when
+ *   shift_p_loc is NaN (the prior is centred on where_loc, so its term moves with it);  d scale = g * ((1 - zq * zq) / scale).
+ *   d_what / d_what_loc / d_what_scale [T,R,A], d_where / d_where_loc / d_where_scale [T,R,4]: rows of steps t >= n are WRITTEN as
+ *   exact zeros (no cleared buffer is assumed);  d_rec[r] = d_logp[r] = -g[r].  The presence chain is discrete: it has no gradient,
+ *   log pi(n) is a constant.  No clamps: a zero scale gives inf / NaN in that row only.  No reduction, one writer per element.  The six
+ *   where-shaped buffers must be 16-byte aligned (AIR_E_ALIGN); the A-wide ones are moved as vectors of 4 / 2 / 1 floats, what A and
+ *   the six starts allow.
+ * air_iw_vimco: per image b over lw_k = logw[b*K + k], K >= 2, float64 inside, every output rounded once to float32.  m = max_k lw_k,
+ *   e_k = exp(lw_k - m), S = sum_k e_k:
+ *     bound[b] = m + log S - log K;  ess[b] = S^2 / sum_k e_k^2;  wnorm[r] = e_k / S;
+ *     signal[r] = bound - log((1/K) (sum_{j != k} w_j + what_k)),  log what_k = (1/(K-1)) sum_{j != k} lw_j  (VIMCO's geometric mean);
+ *   the leave-one-out sums are formed without subtracting nearly equal totals.  An image is DEGENERATE when a log-weight is NaN or
+ *   +inf or all are -inf: degenerate[b] = 1, bound = ess = 0 and its wnorm / signal rows are exact zeros (0 otherwise).  A single
+ *   -inf among finite log-weights is a weight of exactly 0 and follows the plain formulas (at K = 2 the surviving particle's signal
+ *   is then +inf).  No atomics, one fixed butterfly order.                                                                          */
+AIR_ENGINE_API int air_iw_logweight_bwd(const float *what, const float *what_loc, const float *what_scale, const float *where,
+                     const float *where_loc, const float *where_scale, const float *presence, const float *g, int T,
+                     int R, int K, int A, float what_p_loc, float what_p_scale, float scale_p_loc, float scale_p_scale,
+                     float shift_p_loc, float shift_p_scale, float *d_what, float *d_what_loc, float *d_what_scale,
+                     float *d_where, float *d_where_loc, float *d_where_scale, float *d_rec, float *d_logp, void *stream);
+AIR_ENGINE_API int air_iw_vimco(const float *logw, int R, int K, float *bound, float *wnorm, float *signal, float *ess,
+                 int *degenerate, void *stream);
+
 /* ---- the generative direction: scenes from p(n) p(what) p(where) p(x | z) (model.py:92-97,126-216; cell.py:158-165).  Decoder and
  * canvas between the two entries are air_linear_fwd / air_gemm_bf16 and air_canvas_unroll_fwd (obs = NULL).
  * air_prior_latents: the ancestral draw of the latents of R scenes from caller-supplied noise; time-major like the engine:
