@@ -220,6 +220,7 @@ SIGNATURES = {
     "air_iw_logweight_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                      c_float, P, P, P, P, P, P, P, P, P]),
     "air_iw_vimco": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
+    "air_iw_logposterior_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
     "air_prior_latents": (c_int, [P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_int,
                                   P, P, P, P, P]),
     "air_observe": (c_int, [P, c_float, c_float, P, c_uint64, c_float, c_float, P, P, c_size_t, P]),

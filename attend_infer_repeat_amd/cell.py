@@ -51,6 +51,9 @@ class AIRCell(torch.nn.Module):
         self._what_distrib.guard_eps = self._guard_eps
         self._steps_predictor = steps_predictor()
         self.noise = None      # optional dict(eps_where[B,4], eps_what[B,A], u_pres[B,1]) consumed by the next call
+        # (extension, default False: nothing changes) the drawn `where` / `what` are fixed values: the glimpse read, the decoder and the
+        # canvas write see them detached, the same numbers.  The wake-phase update of reweighted wake-sleep sets it (model._iw_losses)
+        self.detach_samples = False
 
     @property
     def state_size(self):                                                    # cell.py:71-80
@@ -119,6 +122,8 @@ class AIRCell(torch.nn.Module):
         else:
             where_distrib = NormalWithSoftplusScale(*est(hidden_output))
         where_code = where_distrib.sample(noise.get("eps_where"))
+        if self.detach_samples:
+            where_code = where_code.detach()
         where_loc, where_scale = where_distrib.loc, where_distrib.scale
         self._validate("where_loc", where_loc, "loc"); self._validate("where_scale", where_scale, "scale")
 
@@ -149,6 +154,8 @@ class AIRCell(torch.nn.Module):
         what_params = self._glimpse_encoder(cropped)                         # cell.py:153-156
         what_distrib = self._what_distrib(what_params)
         what_code = what_distrib.sample(noise.get("eps_what"))
+        if self.detach_samples:
+            what_code = what_code.detach()
         what_loc, what_scale = what_distrib.loc, what_distrib.scale
         self._validate("what_loc", what_loc, "loc"); self._validate("what_scale", what_scale, "scale")
 

@@ -1,7 +1,9 @@
 // Training on the K-particle importance-weighted bound for gfx950: the backward side of iw_kernels.hip.
 //   air_iw_logweight_bwd: the gradient of air_iw_logweight's row value log w[r] given an upstream g[r];
 //   air_iw_vimco:         per image, over its K adjacent log-weights: the bound, the self-normalised weights (the coefficients of
-//                         grad log w) and VIMCO's leave-one-out learning signal (the coefficients of grad log q(n)), float64 inside.
+//                         grad log w) and VIMCO's leave-one-out learning signal (the coefficients of grad log q(n)), float64 inside;
+//   air_iw_logposterior_bwd: the gradient of air_iw_logposterior's row value log q[r] given an upstream g[r] (the wake-phase update of
+//                         reweighted wake-sleep: the samples are fixed values, their gradients optional).
 // Rows are r = b * K + k: the K particles of an image are adjacent.
 #include <limits.h>
 #include "iw_device.h"
@@ -93,6 +95,89 @@ __global__ __launch_bounds__(256) void iw_logweight_bwd_kernel(
         d_rec[r] = -gr;
         d_logp[r] = -gr;
     }
+}
+
+// The gradient of air_iw_logposterior's row value log q[r] = logp[r] + sum_{t<n} sum log N(x | loc, scale) given an upstream g[r]: the
+// layout above without the prior terms.  Per element, with zq = (x - loc) / scale and a = zq / scale, in this order and without
+// contraction,
+//     d loc   = g * a
+//     d scale = g * ((zq * zq - 1) / scale)
+//     d x     = g * (0 - a)
+// d_what / d_where may be NULL (the reweighted wake-sleep update holds the samples fixed and has no use for them): not written then.
+struct IwPostGrad3 { float x, loc, scale; };
+__device__ __forceinline__ IwPostGrad3 iw_log_normal_grad(float x, float loc, float scale, float g) {
+#pragma clang fp contract(off)
+    const float zq = (x - loc) / scale;
+    const float a = zq / scale;
+    IwPostGrad3 d;
+    d.loc = g * a;
+    d.scale = g * ((zq * zq - 1.f) / scale);
+    d.x = g * (0.f - a);
+    return d;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void iw_logposterior_bwd_kernel(
+    const float *__restrict__ what, const float *__restrict__ what_loc, const float *__restrict__ what_scale,
+    const float *__restrict__ where, const float *__restrict__ where_loc, const float *__restrict__ where_scale,
+    const float *__restrict__ presence, const float *__restrict__ g, int T, int R, int A, float *__restrict__ d_what,
+    float *__restrict__ d_what_loc, float *__restrict__ d_what_scale, float *__restrict__ d_where, float *__restrict__ d_where_loc,
+    float *__restrict__ d_where_scale, float *__restrict__ d_logp) {
+#pragma clang fp contract(off)
+    typedef typename VecOf<V>::type vec_t;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;                                            // wave-uniform
+    const float z = lane < T ? presence[(size_t)lane * R + r] : 0.f;
+    const unsigned long long present = __ballot(z > 0.5f);         // lanes >= T (T <= 32) are clear: ~present is never 0
+    const int n = __ffsll((long long)~present) - 1;
+    const float gr = g[r];
+
+    const int AV = A / V, items = T * AV;
+    for (int j = lane; j < items; j += 64) {
+        const int t = j / AV, i = j - t * AV;
+        const size_t off = ((size_t)t * R + r) * A + (size_t)i * V;
+        vec_t dx, dl, dc;
+        float *dxf = reinterpret_cast<float *>(&dx), *dlf = reinterpret_cast<float *>(&dl), *dcf = reinterpret_cast<float *>(&dc);
+        if (t < n) {
+            const vec_t x = *reinterpret_cast<const vec_t *>(what + off);
+            const vec_t l = *reinterpret_cast<const vec_t *>(what_loc + off);
+            const vec_t c = *reinterpret_cast<const vec_t *>(what_scale + off);
+            const float *xf = reinterpret_cast<const float *>(&x), *lf = reinterpret_cast<const float *>(&l),
+                        *cf = reinterpret_cast<const float *>(&c);
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const IwPostGrad3 d = iw_log_normal_grad(xf[v], lf[v], cf[v], gr);
+                dxf[v] = d.x; dlf[v] = d.loc; dcf[v] = d.scale;
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < V; ++v) dxf[v] = dlf[v] = dcf[v] = 0.f;
+        }
+        if (d_what) *reinterpret_cast<vec_t *>(d_what + off) = dx;     // uniform over the launch
+        *reinterpret_cast<vec_t *>(d_what_loc + off) = dl;
+        *reinterpret_cast<vec_t *>(d_what_scale + off) = dc;
+    }
+    if (lane < T) {
+        const size_t off = ((size_t)lane * R + r) * 4;
+        float4 dx = make_float4(0.f, 0.f, 0.f, 0.f), dl = dx, dc = dx;
+        if (lane < n) {
+            const float4 x = *reinterpret_cast<const float4 *>(where + off);
+            const float4 l = *reinterpret_cast<const float4 *>(where_loc + off);
+            const float4 c = *reinterpret_cast<const float4 *>(where_scale + off);
+            const IwPostGrad3 d0 = iw_log_normal_grad(x.x, l.x, c.x, gr);
+            const IwPostGrad3 d1 = iw_log_normal_grad(x.y, l.y, c.y, gr);
+            const IwPostGrad3 d2 = iw_log_normal_grad(x.z, l.z, c.z, gr);
+            const IwPostGrad3 d3 = iw_log_normal_grad(x.w, l.w, c.w, gr);
+            dx = make_float4(d0.x, d1.x, d2.x, d3.x);
+            dl = make_float4(d0.loc, d1.loc, d2.loc, d3.loc);
+            dc = make_float4(d0.scale, d1.scale, d2.scale, d3.scale);
+        }
+        if (d_where) *reinterpret_cast<float4 *>(d_where + off) = dx;
+        *reinterpret_cast<float4 *>(d_where_loc + off) = dl;
+        *reinterpret_cast<float4 *>(d_where_scale + off) = dc;
+    }
+    if (lane == 0) d_logp[r] = gr;
 }
 
 __device__ __forceinline__ double wave_max_all_f64(double v) {
@@ -208,6 +293,33 @@ extern "C" int air_iw_logweight_bwd(const float *what, const float *what_loc, co
     else if (A % 2 == 0 && (bits & 7u) == 0) IW_BWD_LAUNCH(2);
     else IW_BWD_LAUNCH(1);
 #undef IW_BWD_LAUNCH
+    AIR_LAUNCH_CHECK();
+    return AIR_OK;
+}
+
+extern "C" int air_iw_logposterior_bwd(const float *what, const float *what_loc, const float *what_scale, const float *where,
+                                       const float *where_loc, const float *where_scale, const float *presence, const float *g, int T,
+                                       int R, int K, int A, float *d_what, float *d_what_loc, float *d_what_scale, float *d_where,
+                                       float *d_where_loc, float *d_where_scale, float *d_logp, void *stream) {
+    AIR_REQUIRE(what && what_loc && what_scale && where && where_loc && where_scale && presence && g && d_what_loc && d_what_scale &&
+                d_where_loc && d_where_scale && d_logp, AIR_E_NULL);                 // d_what / d_where: optional
+    AIR_REQUIRE(K > 0 && T > 0 && T <= IW_MAXT && R > 0 && A > 0 && R % K == 0, AIR_E_SHAPE);
+    AIR_REQUIRE((long)T * R * A <= (long)INT_MAX, AIR_E_SHAPE);
+    AIR_REQUIRE(air_aligned16(where) && air_aligned16(where_loc) && air_aligned16(where_scale) && air_aligned16(d_where) &&
+                air_aligned16(d_where_loc) && air_aligned16(d_where_scale), AIR_E_ALIGN);   // (a NULL d_where is aligned)
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(what) | reinterpret_cast<uintptr_t>(what_loc) |
+                           reinterpret_cast<uintptr_t>(what_scale) | reinterpret_cast<uintptr_t>(d_what) |
+                           reinterpret_cast<uintptr_t>(d_what_loc) | reinterpret_cast<uintptr_t>(d_what_scale);
+    AIR_REQUIRE((bits & 3u) == 0, AIR_E_ALIGN);
+    const dim3 grid(air_cdiv(R, 4)), block(256);
+#define IW_POST_BWD_LAUNCH(V)                                                                                                      \
+    hipLaunchKernelGGL(iw_logposterior_bwd_kernel<V>, grid, block, 0, air_stream(stream), what, what_loc, what_scale, where,        \
+                       where_loc, where_scale, presence, g, T, R, A, d_what, d_what_loc, d_what_scale, d_where, d_where_loc,       \
+                       d_where_scale, d_logp)
+    if (A % 4 == 0 && (bits & 15u) == 0) IW_POST_BWD_LAUNCH(4);
+    else if (A % 2 == 0 && (bits & 7u) == 0) IW_POST_BWD_LAUNCH(2);
+    else IW_POST_BWD_LAUNCH(1);
+#undef IW_POST_BWD_LAUNCH
     AIR_LAUNCH_CHECK();
     return AIR_OK;
 }

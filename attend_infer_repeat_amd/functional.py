@@ -304,6 +304,30 @@ def iw_logweight(what, what_loc, what_scale, where, where_loc, where_scale, pres
                               tuple(float(v) for v in priors6), bool(normalize))
 
 
+class _IwLogposterior(torch.autograd.Function):
+    """log q(z | x) per (image, particle) row (air_iw_logposterior) and its hand-written backward (air_iw_logposterior_bwd).  The
+    gradients of the samples themselves are formed only when asked for: reweighted wake-sleep holds them fixed."""
+
+    @staticmethod
+    def forward(ctx, what, what_loc, what_scale, where, where_loc, where_scale, presence, logp, K):
+        saved = tuple(_c(t) for t in (what, what_loc, what_scale, where, where_loc, where_scale, presence))
+        log_q = H.iw_logposterior(*saved, _c(logp), K)
+        ctx.save_for_backward(*saved)
+        ctx.K = K
+        return log_q
+
+    @staticmethod
+    def backward(ctx, g):
+        d = H.iw_logposterior_bwd(*ctx.saved_tensors, _c(g), ctx.K, want_what=ctx.needs_input_grad[0],
+                                  want_where=ctx.needs_input_grad[3])
+        return d[0], d[1], d[2], d[3], d[4], d[5], None, d[6], None
+
+
+def iw_logposterior(what, what_loc, what_scale, where, where_loc, where_scale, presence, logp, K):
+    """what-like [T,R,A], where-like [T,R,4], presence [T,R], logp [R] = log q(n | x) (R = B * K, row b * K + k) -> log_q [R]"""
+    return _IwLogposterior.apply(what, what_loc, what_scale, where, where_loc, where_scale, presence, logp, int(K))
+
+
 class _Vimco(torch.autograd.Function):
     """The K-particle bound per image and the surrogate -mean_b bound over the non-degenerate images (air_iw_vimco).  Backward: the
     VIMCO estimator -- -wnorm[r] / B_eff to logw, -signal[r] / B_eff to logq = log q(n sampled); both coefficients are constants."""

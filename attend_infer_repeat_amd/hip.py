@@ -799,6 +799,30 @@ def iw_vimco(logw, K):
     return bound, wnorm, signal, ess, degen
 
 
+def iw_logposterior(what, what_loc, what_scale, where, where_loc, where_scale, presence, logp, K):
+    """air_iw_logposterior: -> log_q[R] = logp + sum_{t<n} log N(what_t | .) + log N(where_t | .) (with the -1/2 log 2 pi of every term)"""
+    T, R, A = _iw_rows(what, what_loc, what_scale, where, where_loc, where_scale, presence, K)
+    _iw_row_vec(logp, "logp", R)
+    log_q = torch.empty((R,), dtype=torch.float32, device=what.device)
+    _lib.check(lib().air_iw_logposterior(_p(what), _p(what_loc), _p(what_scale), _p(where), _p(where_loc), _p(where_scale),
+                                         _p(presence), _p(logp), T, R, int(K), A, _p(log_q), _stream()), "air_iw_logposterior")
+    return log_q
+
+
+def iw_logposterior_bwd(what, what_loc, what_scale, where, where_loc, where_scale, presence, g, K, want_what=True, want_where=True):
+    """air_iw_logposterior_bwd: -> d what (None without want_what), d what_loc, d what_scale [T,R,A], d where (None without
+    want_where), d where_loc, d where_scale [T,R,4], d logp [R]"""
+    T, R, A = _iw_rows(what, what_loc, what_scale, where, where_loc, where_scale, presence, K)
+    _iw_row_vec(g, "g", R)
+    outs = [torch.empty_like(what) if want_what else None, torch.empty_like(what), torch.empty_like(what),
+            torch.empty_like(where) if want_where else None, torch.empty_like(where), torch.empty_like(where),
+            torch.empty((R,), dtype=torch.float32, device=what.device)]
+    _lib.check(lib().air_iw_logposterior_bwd(_p(what), _p(what_loc), _p(what_scale), _p(where), _p(where_loc), _p(where_scale),
+                                             _p(presence), _p(g), T, R, int(K), A, *[_p(o) for o in outs], _stream()),
+               "air_iw_logposterior_bwd")
+    return tuple(outs)
+
+
 def nvil_parts(imp_parts, baseline, logp, ema=None, want_sum=True):
     """air_nvil_parts: imp_parts[n_parts, B] shares of the importance weight -> out[4], dlogp[B], dbaseline[B], imp_sum[B] | None"""
     imp_parts = _f32(imp_parts, "imp_parts", 2); baseline = _f32(baseline, "baseline", 1); logp = _f32(logp, "logp", 1)

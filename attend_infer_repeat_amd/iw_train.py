@@ -21,6 +21,11 @@ This module restates the two device entries (include/air_hip.h: air_iw_vimco, ai
   reference_logweight_grad  numpy float32 (or any dtype), operation by operation in the kernel's order: the kernel's bits;
   analytic_logweight_grad   the same gradient in float64 from the closed-form derivative of the densities;
   reference_logweight       the forward value in float64 (what a finite difference is taken of).
+
+iw_objective="rws" trains on the same particles by the wake-phase update of reweighted wake-sleep instead (Bornschein & Bengio 2015;
+Le et al. 2019): sum_k wnorm_k grad log q(z_k | x) for the inference network and sum_k wnorm_k grad log p(x, z_k) for the decoder,
+z_k fixed values, wnorm_k constants, no signal term.  reference_rws, reference_logposterior_grad, analytic_logposterior_grad and
+reference_logposterior restate its entry (air_iw_logposterior_bwd) the same way.
 """
 import numpy as np
 
@@ -31,6 +36,11 @@ NO_DECAY_RATE = ("iw_samples: decay_rate normalises the NVIL importance weight, 
 NEEDS_PRIOR = ("iw_samples: use_prior=False removes the generative density the importance weight is a ratio of; the importance-"
                "weighted objective needs use_prior=True")
 NEEDS_STEPS_PRIOR = "iw_samples: num_steps_prior is needed (log pi(n) is a term of the importance weight)"
+IW_OBJECTIVES = ("vimco", "rws")
+OBJECTIVE_NEEDS_SAMPLES = ("iw_objective chooses the estimator of the K-particle objective and needs iw_samples >= 2; without iw_samples "
+                           "the default objective (ELBO with the NVIL baseline) is trained and iw_objective must stay None")
+RWS_NEEDS_LOGQ = ('iw_objective="rws": use_reinforce=False switches off a score-function term, and the wake-phase update has none -- '
+                  "log q(n | x) is part of its target log q(z | x); leave use_reinforce at True")
 
 
 def check_iw_samples(K):
@@ -46,9 +56,26 @@ def check_iw_samples(K):
     return int(K)
 
 
-def check_train_arguments(K, decay_rate, use_prior, discrete_steps, what_prior, where_scale_prior, where_shift_prior, num_steps_prior):
-    """What train_step(iw_samples=K) refuses, each with a message (ValueError); the prior configuration by iw_eval.check_config's rules"""
+def check_iw_objective(iw_objective, K, use_reinforce=True):
+    """None / "vimco": the VIMCO estimator (returns "vimco", or None when K is None).  "rws": the wake-phase update of reweighted
+    wake-sleep; needs K >= 2 and use_reinforce.  An objective without iw_samples, or any other value: ValueError."""
+    if iw_objective is not None and iw_objective not in IW_OBJECTIVES:
+        raise ValueError("iw_objective must be None, %s, got %r" % (" or ".join(repr(o) for o in IW_OBJECTIVES), iw_objective))
+    if K is None:
+        if iw_objective is not None:
+            raise ValueError(OBJECTIVE_NEEDS_SAMPLES)
+        return None
+    if iw_objective == "rws" and not use_reinforce:
+        raise ValueError(RWS_NEEDS_LOGQ)
+    return iw_objective or "vimco"
+
+
+def check_train_arguments(K, decay_rate, use_prior, discrete_steps, what_prior, where_scale_prior, where_shift_prior, num_steps_prior,
+                          iw_objective=None, use_reinforce=True):
+    """What train_step(iw_samples=K) refuses, each with a message (ValueError); the prior configuration by iw_eval.check_config's rules.
+    Returns K; `iw_objective` (None / "vimco": nothing changes; "rws") is checked by check_iw_objective."""
     K = check_iw_samples(K)
+    check_iw_objective(iw_objective, K, use_reinforce)
     if K is None:
         return None
     if decay_rate is not None:
@@ -196,3 +223,71 @@ def reference_logweight(what, what_loc, what_scale, where, where_loc, where_scal
     if normalize:
         table = table / table.sum()
     return -f(rec) + np.log(table)[n] - f(logp) + np.where(live, s, 0.0).sum(0)
+
+
+# ---- reweighted wake-sleep: air_iw_logposterior and its backward -----------------------------------------------------------------------
+def reference_rws(logw, K):
+    """The coefficients of the wake-phase update: reference_vimco's bound[B], wnorm[R], ess[B] and degenerate[B] (wnorm_k multiplies
+    grad log q(z_k | x) and grad log p(x, z_k); VIMCO's signal is not used)."""
+    out = reference_vimco(logw, K)
+    return {k: out[k] for k in ("bound", "wnorm", "ess", "degenerate")}
+
+
+def reference_logposterior_grad(what, what_loc, what_scale, where, where_loc, where_scale, presence, g, dtype=np.float32):
+    """air_iw_logposterior_bwd operation by operation in `dtype` (float32: the kernel's bits).  Returns the seven outputs in the entry's
+    order: d what, d what_loc, d what_scale [T,R,A], d where, d where_loc, d where_scale [T,R,4], d logp [R]."""
+    dt = np.dtype(dtype).type
+    c = lambda a: np.ascontiguousarray(np.asarray(a), dtype=dt)
+    what, what_loc, what_scale, where, where_loc, where_scale, g = (c(a) for a in (what, what_loc, what_scale, where, where_loc,
+                                                                                  where_scale, g))
+    T, R = what.shape[:2]
+    live = (np.arange(T)[:, None] < leading_ones(presence)[None, :])[..., None]       # [T, R, 1]
+    gr = g.reshape(1, R, 1)
+    one, zero = dt(1), dt(0)
+
+    def grads(x, loc, scale):
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            zq = (x - loc) / scale
+            a = zq / scale
+            dloc = gr * a
+            dscale = gr * ((zq * zq - one) / scale)
+            dx = gr * (zero - a)
+        return tuple(np.where(live, d, zero).astype(dt) for d in (dx, dloc, dscale))
+
+    return grads(what, what_loc, what_scale) + grads(where, where_loc, where_scale) + (g.copy(),)
+
+
+def analytic_logposterior_grad(what, what_loc, what_scale, where, where_loc, where_scale, presence, g):
+    """The same seven gradients in float64 from the closed-form derivative of log N(x | loc, scale):
+    d/dx = -(x - loc) / scale^2;  d/dloc = (x - loc) / scale^2;  d/dscale = (x - loc)^2 / scale^3 - 1 / scale."""
+    f = lambda a: np.asarray(a, np.float64)
+    what, what_loc, what_scale, where, where_loc, where_scale, g = (f(a) for a in (what, what_loc, what_scale, where, where_loc,
+                                                                                  where_scale, g))
+    T, R = what.shape[:2]
+    live = (np.arange(T)[:, None] < leading_ones(presence)[None, :])[..., None]
+    gr = g.reshape(1, R, 1)
+
+    def grads(x, loc, scale):
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            q = (x - loc) / scale ** 2
+            out = (gr * -q, gr * q, gr * ((x - loc) ** 2 / scale ** 3 - 1.0 / scale))
+        return tuple(np.where(live, d, 0.0) for d in out)
+
+    return grads(what, what_loc, what_scale) + grads(where, where_loc, where_scale) + (g.copy(),)
+
+
+def reference_logposterior(what, what_loc, what_scale, where, where_loc, where_scale, presence, logp):
+    """air_iw_logposterior's row value in float64: logp + sum_{t<n} (sum_a log N(what) + sum_j log N(where)), every term with its
+    -1/2 log 2 pi"""
+    f = lambda a: np.asarray(a, np.float64)
+    what, what_loc, what_scale, where, where_loc, where_scale = (f(a) for a in (what, what_loc, what_scale, where, where_loc,
+                                                                               where_scale))
+    T = what.shape[0]
+    live = np.arange(T)[:, None] < leading_ones(presence)[None, :]
+
+    def log_normal(x, loc, scale):
+        zq = (x - loc) / scale
+        return (-0.5 * (zq * zq) - np.log(scale) - 0.5 * np.log(2.0 * np.pi)).sum(-1)
+
+    s = log_normal(what, what_loc, what_scale) + log_normal(where, where_loc, where_scale)
+    return f(logp) + np.where(live, s, 0.0).sum(0)

@@ -34,6 +34,7 @@ class AIRonMNIST(AIRModel):
         self.baseline = BaselineMLP(baseline_hidden)
         # (extension, default None: the reference's objective) the default of train_step's `iw_samples`
         self.iw_samples = kwargs.pop("iw_samples", None)
+        self._iw_objective_default = kwargs.pop("iw_objective", None)          # ... and of its `iw_objective`
         self._hyper = dict(inpt_encoder_hidden=tuple(inpt_encoder_hidden),
                            glimpse_encoder_hidden=tuple(glimpse_encoder_hidden),
                            glimpse_decoder_hidden=tuple(glimpse_decoder_hidden),
@@ -140,16 +141,20 @@ class AIRonMNIST(AIRModel):
     def train_step(self, learning_rate, l2_weight=0., what_prior=None, where_scale_prior=None,
                    where_shift_prior=None, num_steps_prior=None, use_prior=True, use_reinforce=True, baseline=None,
                    decay_rate=None, optimizer=None, opt_kwargs=None, use_engine=True, capture_graph=True,
-                   mfma_dtype="f32", iw_samples=None):
+                   mfma_dtype="f32", iw_samples=None, iw_objective=None):
         """model.py:261-376 on the fused engine.  Extras over the reference signature: `use_engine` / `capture_graph`, and
         `mfma_dtype` ("f32" exact fp32 MFMA, "bf16" = bf16-rounded operands with fp32 accumulate in every dense product).
         `iw_samples=K` (None: the constructor's, itself None by default): the K-particle importance-weighted objective of
-        AIRModel.train_step, on the generic autograd path -- the engine, its plans and its graphs are not built."""
+        AIRModel.train_step, on the generic autograd path -- the engine, its plans and its graphs are not built.
+        `iw_objective` (None: the constructor's): its estimator, "vimco" (the default) or "rws" (reweighted wake-sleep)."""
         if iw_samples is None:
             iw_samples = self.iw_samples
+        if iw_objective is None:
+            iw_objective = self._iw_objective_default
         fn, gs = super(AIRonMNIST, self).train_step(learning_rate, l2_weight, what_prior, where_scale_prior,
                                                     where_shift_prior, num_steps_prior, use_prior, use_reinforce,
-                                                    baseline, decay_rate, optimizer, opt_kwargs, iw_samples=iw_samples)
+                                                    baseline, decay_rate, optimizer, opt_kwargs, iw_samples=iw_samples,
+                                                    iw_objective=iw_objective)
         if not self._engine_eligible(use_engine, l2_weight, what_prior, where_scale_prior, where_shift_prior,
                                      num_steps_prior, decay_rate):
             return fn, gs

@@ -249,7 +249,8 @@ class AIRModel(object):
     # ---- training on the K-particle importance-weighted bound (iw_train.py; DESIGN 8: "Training on the bound") ------------------
     def _iw_forward_losses(self, obs=None, nums=None, noise=None):
         """The unroll on every image repeated K times (row b * K + k; noise: optional dict of time-major tensors for K * B rows)
-        and the objective -mean_b L_K over the non-degenerate images.  The output attributes then describe the K * B rows;
+        and the objective -mean_b L_K over the non-degenerate images (iw_objective "rws": the wake-phase surrogate on samples the
+        cell detaches, which is not a bound).  The output attributes then describe the K * B rows;
         `obs`, `nums` and `batch_size` stay the caller's."""
         if obs is not None:
             self.obs = obs
@@ -259,10 +260,12 @@ class AIRModel(object):
         obs_b, nums_b = self.obs, self.nums
         try:
             self.obs, self.nums, self.batch_size = obs_b.repeat_interleave(K, 0), None, B * K
+            self.cell.detach_samples = self.iw_objective == "rws"    # the wake-phase update: the particles are fixed values
             self.forward(noise=noise)
             gt = None if nums_b is None else nums_b.sum(0).reshape(-1).repeat_interleave(K, 0)
             return self._iw_losses(self.global_step, gt)
         finally:
+            self.cell.detach_samples = False
             self.obs, self.nums, self.batch_size = obs_b, nums_b, B
 
     def _iw_losses(self, global_step, gt_num_steps=None):
@@ -282,10 +285,26 @@ class AIRModel(object):
         q, kl_ps, logq, _ = F.numsteps(self.presence_prob.reshape(T, R), presence, prior)
         self._num_steps_q, self._num_steps_logp = q, logq
         self.kl_num_steps_per_sample, self.kl_num_steps = kl_ps.detach(), kl_ps.detach().mean()
-        logw, _ = F.iw_logweight(self.what, self.what_loc, self.what_scale, self.where, self.where_loc, self.where_scale, presence,
-                                 self.rec_loss_per_sample, logq, prior, K,
-                                 priors6(self.what_prior, self.where_scale_prior, self.where_shift_prior), normalize=False)
-        bound, surrogate, ess, degen = F.vimco(logw, logq if self.use_reinforce else None, K, return_stats=True)
+        latents = (self.what, self.what_loc, self.what_scale, self.where, self.where_loc, self.where_scale, presence)
+        pr6 = priors6(self.what_prior, self.where_scale_prior, self.where_shift_prior)
+        if self.iw_objective == "rws":
+            # The wake-phase update of reweighted wake-sleep: sum_k wnorm_k grad log p(x, z_k) for the decoder (the prior terms of
+            # log p(x, z) carry no gradient: -rec is what is left) and sum_k wnorm_k grad log q(z_k | x) for everything else, at fixed
+            # particles (cell.detach_samples) and constant weights.  A SURROGATE whose gradient is that update, not a bound.
+            with torch.no_grad():
+                logw, _ = F.iw_logweight(*latents, self.rec_loss_per_sample, logq, prior, K, pr6, normalize=False)
+                bound, wnorm, _, ess, degen = H.iw_vimco(logw, K)
+                b_eff = (degen == 0).sum().clamp(min=1).to(torch.float32)
+                coef = wnorm / b_eff
+                surrogate = -(bound.sum() / b_eff)
+            log_q = F.iw_logposterior(*latents, logq, K)
+            rows = self.rec_loss_per_sample - log_q
+            opt_loss = (coef * torch.where(coef != 0, rows, torch.zeros_like(rows))).sum()    # a row of weight 0 may hold a NaN
+            self.iw_weights = coef
+        else:
+            logw, _ = F.iw_logweight(*latents, self.rec_loss_per_sample, logq, prior, K, pr6, normalize=False)
+            bound, surrogate, ess, degen = F.vimco(logw, logq if self.use_reinforce else None, K, return_stats=True)
+            opt_loss = surrogate
         live = (degen == 0).to(torch.float32)
         self.iw_log_weights = logw.detach().reshape(-1, K)
         self.iw_bound_per_sample = bound
@@ -296,7 +315,6 @@ class AIRModel(object):
         self.loss.add(-logw.detach().mean(), -logw.detach())                # the single-sample bound of every row
         zero = torch.zeros((), device=self.obs.device)
         self.reinforce_loss, self.baseline_loss = zero, zero
-        opt_loss = surrogate
         if self.l2_weight and self.l2_weight > 0.:
             weights = [p for p in self.cell.parameters() if p.dim() == 2]
             self.l2_loss = self.l2_weight * sum((w * w).sum() / 2 for w in weights)
@@ -321,19 +339,25 @@ class AIRModel(object):
 
     def train_step(self, learning_rate, l2_weight=0., what_prior=None, where_scale_prior=None,
                    where_shift_prior=None, num_steps_prior=None, use_prior=True, use_reinforce=True, baseline=None,
-                   decay_rate=None, optimizer=None, opt_kwargs=None, iw_samples=None):
+                   decay_rate=None, optimizer=None, opt_kwargs=None, iw_samples=None, iw_objective=None):
         """Creates the train step and the global_step (model.py:261-376).
         `iw_samples=K` (an extension, default None = exactly the objective above): train on the K-particle importance-weighted
         bound instead -- every image repeated K times with independent noise, IWAE weights for the continuous latents, VIMCO's
         leave-one-out signal for the discrete count, no baseline (`_iw_losses`, iw_train.py).
+        `iw_objective` (with iw_samples only; None / "vimco": the estimator just described): "rws" trains by the wake-phase update
+        of reweighted wake-sleep instead -- the K particles are fixed values, the decoder follows sum_k wnorm_k grad log p(x, z_k)
+        and the inference network sum_k wnorm_k grad log q(z_k | x), neither reparameterisation nor a control variate.  `opt_loss`
+        is then a surrogate whose gradient is that update, NOT a bound; `iw_bound` / `loss` report the bound as before.
         `optimizer` / `opt_kwargs` (model.py:265: `optimizer=tf.train.RMSPropOptimizer, opt_kwargs=dict(momentum=.9,
         centered=True)`, instantiated as optimizer(learning_rate, **opt_kwargs) and once more at 10x the rate for the
         baseline, model.py:355-363): the default runs on the HIP centred-RMSProp kernel with TF's slot initialisation; any
         other choice is given as a torch.optim class (same calling convention: optimizer(params, lr, **opt_kwargs)) and
         steps the generic autograd path."""
-        from .iw_train import check_train_arguments
+        from .iw_train import check_iw_objective, check_train_arguments
         self._iw_samples = check_train_arguments(iw_samples, decay_rate, use_prior, self.discrete_steps, what_prior,
-                                                 where_scale_prior, where_shift_prior, num_steps_prior)
+                                                 where_scale_prior, where_shift_prior, num_steps_prior, iw_objective=iw_objective,
+                                                 use_reinforce=use_reinforce)
+        self.iw_objective = check_iw_objective(iw_objective, self._iw_samples, use_reinforce)   # None, "vimco" or "rws"
         custom_opt = optimizer is not None
         self._custom_optimizer = (optimizer, dict(opt_kwargs or {})) if custom_opt else None
         # the reference's default class with other keywords (model.py:265: RMSPropOptimizer(lr, **opt_kwargs), e.g. momentum=.5

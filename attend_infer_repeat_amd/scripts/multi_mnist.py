@@ -72,6 +72,10 @@ def main(argv=None):
                          "for the continuous latents, VIMCO's leave-one-out signal for the object count, no baseline) on the generic "
                          "autograd path -- the fused engine is not used; iw_bound, iw_ess and iw_degenerate go into the 1000-iteration "
                          "summaries.  Not with --decay-rate or the options that need the engine")
+    ap.add_argument("--iw-objective", choices=("vimco", "rws"), default=None,
+                    help="with --iw-train K: the gradient estimator.  vimco (the default): IWAE weights and VIMCO's leave-one-out signal; "
+                         "rws: the wake-phase update of reweighted wake-sleep -- the particles are fixed values, the decoder follows "
+                         "sum_k w_k grad log p(x, z_k), the inference network sum_k w_k grad log q(z_k | x)")
     ap.add_argument("--decay-rate", type=float, default=None, metavar="D",
                     help="train_step's decay_rate: normalise the NVIL importance weight by moving averages with decay D (the reference "
                          "script leaves it off)")
@@ -192,6 +196,8 @@ def main(argv=None):
                     help="with --init-from-tf-ckpt: a JSON file {engine parameter name: checkpoint variable name} that replaces the shape-based "
                          "matcher (tf_checkpoint.default_name_map) when it stops or guesses wrong")
     args = ap.parse_args(argv)
+    if args.iw_objective is not None and args.iw_train is None:
+        ap.error("--iw-objective chooses the estimator of --iw-train K and needs it")
     if args.iw_train is not None:
         from attend_infer_repeat_amd.iw_train import NO_DECAY_RATE, check_iw_samples
         try:
@@ -414,7 +420,7 @@ def main(argv=None):
     if args.decay_rate is not None:
         step_kw["decay_rate"] = args.decay_rate
     if args.iw_train is not None:
-        step_kw.update(use_engine=False, iw_samples=args.iw_train)
+        step_kw.update(use_engine=False, iw_samples=args.iw_train, iw_objective=args.iw_objective)
     train_step, global_step = air.train_step(learning_rate, l2_weight, appearance_prior, where_scale_prior,
                                              where_shift_prior, num_steps_prior, **step_kw)
     if args.init_from_tf_ckpt:
@@ -632,7 +638,8 @@ def main(argv=None):
             writer.write(json.dumps(diag) + "\n"); writer.flush()
         if args.iw_train is not None:
             if args.summary_every and train_itr % args.summary_every == 0:
-                writer.write(json.dumps(dict(step=train_itr, data="summary", iw_samples=args.iw_train, iw_bound=float(air.iw_bound),
+                writer.write(json.dumps(dict(step=train_itr, data="summary", iw_samples=args.iw_train, iw_objective=air.iw_objective,
+                                             iw_bound=float(air.iw_bound),
                                              iw_ess=float(air.iw_ess), iw_degenerate=int(air.iw_degenerate),
                                              iw_degenerate_total=int(iw_degenerate_total), rec=float(air.rec_loss),
                                              loss=float(air.loss.value), opt_loss=float(air.opt_loss), num_step=float(air.num_step),
@@ -647,7 +654,8 @@ def main(argv=None):
             log(train_itr)
             t0, last = time.time(), train_itr
         if train_itr % args.save_every == 0 and args.iw_train is not None:
-            torch.save({"cell": air.cell.state_dict(), "global_step": train_itr, "iw_samples": args.iw_train},
+            torch.save({"cell": air.cell.state_dict(), "global_step": train_itr, "iw_samples": args.iw_train,
+                        "iw_objective": air.iw_objective},
                        osp.join(logdir, "model_{}.pt".format(train_itr)))
         elif train_itr % args.save_every == 0:
             torch.save({"engine": air._engine.state_dict(), "train_feed": train_feed.state_dict(),

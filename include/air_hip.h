@@ -639,7 +639,16 @@ AIR_ENGINE_API int air_iw_reduce(const float *logw, const int *num_steps, int T,
  *   the leave-one-out sums are formed without subtracting nearly equal totals.  An image is DEGENERATE when a log-weight is NaN or
  *   +inf or all are -inf: degenerate[b] = 1, bound = ess = 0 and its wnorm / signal rows are exact zeros (0 otherwise).  A single
  *   -inf among finite log-weights is a weight of exactly 0 and follows the plain formulas (at K = 2 the surviving particle's signal
- *   is then +inf).  No atomics, one fixed butterfly order.                                                                          */
+ *   is then +inf).  No atomics, one fixed butterfly order.
+ * air_iw_logposterior_bwd: the gradient of air_iw_logposterior's log_q[r] times an upstream g[R], with the same count n (the wake-phase
+ *   update of reweighted wake-sleep: sum_k wnorm_k grad log q(z_k | x) at fixed z_k).  Per element, with zq = (x - loc) / scale and
+ *   a = zq / scale, in this order and without contraction:  d loc = g * a;  d scale = g * ((zq * zq - 1) / scale);  d x = g * (0 - a).
+ *   d_what_loc / d_what_scale [T,R,A], d_where_loc / d_where_scale [T,R,4]: rows of steps t >= n are WRITTEN as exact zeros (no cleared
+ *   buffer is assumed);  d_logp[r] = g[r].  d_what [T,R,A] and d_where [T,R,4] are OPTIONAL: a NULL pointer means not written (a
+ *   caller that holds the samples fixed has no use for them).  No clamps: a zero scale gives inf / NaN in that row only.  No
+ *   reduction, no atomics, one writer per element.  T <= 32.  The where-shaped buffers must be 16-byte aligned (AIR_E_ALIGN); the
+ *   A-wide ones are moved as vectors of 4 / 2 / 1 floats, what A and the buffer starts allow.  NULL and shape errors are returned
+ *   before any device call.                                                                                                      */
 AIR_ENGINE_API int air_iw_logweight_bwd(const float *what, const float *what_loc, const float *what_scale, const float *where,
                      const float *where_loc, const float *where_scale, const float *presence, const float *g, int T,
                      int R, int K, int A, float what_p_loc, float what_p_scale, float scale_p_loc, float scale_p_scale,
@@ -647,6 +656,10 @@ AIR_ENGINE_API int air_iw_logweight_bwd(const float *what, const float *what_loc
                      float *d_where, float *d_where_loc, float *d_where_scale, float *d_rec, float *d_logp, void *stream);
 AIR_ENGINE_API int air_iw_vimco(const float *logw, int R, int K, float *bound, float *wnorm, float *signal, float *ess,
                  int *degenerate, void *stream);
+AIR_ENGINE_API int air_iw_logposterior_bwd(const float *what, const float *what_loc, const float *what_scale, const float *where,
+                     const float *where_loc, const float *where_scale, const float *presence, const float *g, int T,
+                     int R, int K, int A, float *d_what, float *d_what_loc, float *d_what_scale, float *d_where,
+                     float *d_where_loc, float *d_where_scale, float *d_logp, void *stream);
 
 /* ---- the generative direction: scenes from p(n) p(what) p(where) p(x | z) (model.py:92-97,126-216; cell.py:158-165).  Decoder and
  * canvas between the two entries are air_linear_fwd / air_gemm_bf16 and air_canvas_unroll_fwd (obs = NULL).
